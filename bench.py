@@ -10,6 +10,11 @@ gradient all-reduce (RCCL, inside libp3dhip).  Rank 0 prints ONE JSON line.  Inp
 in HBM before the timed region.  After the timed region rank 0 runs one extra, untimed step with
 HIP events around every kernel launch (on the launch stream) to fill `roofline`, and -- at N=1
 only -- times the numpy oracle on the host cores for `cpu_baseline`.
+
+--dump-outputs DIR: rank 0 writes what the last timed step computed (dump_outputs) as DIR/<name>.npy, before
+the untimed steps above run.  Inputs, initial weights and dropout seeds are fixed by the arguments, so two
+builds run with the same arguments can be compared output for output; two runs of one build agree bit for
+bit (tests/test_gpu_determinism.py).
 """
 import argparse
 import json
@@ -26,6 +31,30 @@ PEAK_FP32_TFLOPS = 157.3      # MI355X_MICROARCH.md: fp32 vector == fp32 MFMA pe
 PEAK_FP16_TFLOPS = 2500.0     # dense fp16 MFMA (MI355X_MICROARCH.md; the headline 5 PF is with 2:1 sparsity)
 PEAK_HBM_GBS = 8000.0         # MI355X_MICROARCH.md: HBM3E spec (6.3 TB/s achievable)
 FLOP_PER_CLIP_FWD_BWD = 98.59e9   # algorithmic conv/deconv FLOPs per clip
+DUMP_CAP_FLOATS = (64 << 20) // 4  # --dump-outputs: at most 64 MB of float32 in all
+
+
+def dump_sample(a, cap, seed):
+    """`a` as float32 when it has at most `cap` elements; otherwise a fixed, seeded sample of `cap` of its elements (flat, in
+    index order), the same on every run and every build."""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.size <= cap:
+        return a
+    idx = np.sort(np.random.Generator(np.random.PCG64(seed)).choice(a.size, cap, replace=False))
+    return a.reshape(-1)[idx]
+
+
+def dump_outputs(sess, loss, out_dir):
+    """What a caller of the timed train step receives from its last step: the loss, the prediction of its forward pass and the
+    variables it left behind (Adam-updated trainables and BatchNorm moving statistics, flattened and concatenated in creation
+    order).  float32 .npy files; the prediction gets a quarter and the variables half of DUMP_CAP_FLOATS, sampled when larger."""
+    os.makedirs(out_dir, exist_ok=True)
+    variables = np.concatenate([sess.get_param(n).reshape(-1) for n, _, _ in sess.variables()])
+    outs = {"loss": np.array([loss], np.float32),
+            "pred": dump_sample(sess.activation("pred"), DUMP_CAP_FLOATS // 4, seed=1),
+            "variables": dump_sample(variables, DUMP_CAP_FLOATS // 2, seed=2)}
+    for name, a in outs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def kernel_table(recs):
@@ -191,7 +220,11 @@ def main():
     ap.add_argument("--kernels", action="store_true", help="also print the per-kernel table to stderr")
     ap.add_argument("--dump-launches", default=None, help="write every launch record of the profiled step to this CSV")
     ap.add_argument("--per-layer", default=None, help="write the per-layer roofline table of the profiled step to this CSV")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the loss, prediction and variables of the last timed step to DIR/<name>.npy (float32, <= 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # bare `python bench.py --gpus N`: this process has not touched the GPU yet; it only starts the N ranks as a CHILD
@@ -247,6 +280,10 @@ def main():
     plane.barrier()
     dt = plane.max_over_ranks(time.perf_counter() - t0)
     loss = sess.last_loss()
+    if args.dump_outputs:
+        if rank == 0:              # before any untimed step changes the variables
+            dump_outputs(sess, loss, args.dump_outputs)
+        plane.barrier()            # the other ranks wait, so that the dump stays out of their one-step timing below
     # host cost of enqueueing ONE step into empty queues (no back-pressure from a full hardware queue, unlike t_enqueued)
     t1 = time.perf_counter()
     sess.train_step_device(0.5, seed=999_999)

@@ -77,7 +77,10 @@ struct Param {
 
 // The stem: conv -> BatchNorm -> ReLU, and the conv has no input gradient.  The normalisation's backward then ends after its
 // reduce / finalize launches and hands its arguments to the conv's filter gradient, which applies it on its operand path.
-struct StemBnLink { bool enabled = false, pending = false; BnBwdArgs args; };
+struct StemBnLink {
+    bool enabled = false, pending = false; BnBwdArgs args;
+    std::vector<const Param*> reads;      // variables the filter gradient reads when it takes the apply pass (the BatchNorm's gamma)
+};
 
 struct Act {
     std::string name;

@@ -262,6 +262,7 @@
         bnbuf_count += (two ? 4 : 2) * (int64_t)y1->C;
         const int64_t M = y1->rows();
         const int C = y1->C;
+        if (mode == 0 && y1->stem_link) y1->stem_link->reads = {bn1->gamma};      // read by the stem's filter gradient (below)
         Op op;
         op.name = opname; op.kind = "bn_apply" + std::to_string(mode);
         const double tens = (double)M * C * 4.0;

@@ -67,11 +67,18 @@
                     throw P3dError("gradient bucket order broken at op " + ops[i].name + " / variable " + kv.first->name);
         }
         if (pos != 0) throw P3dError("gradient bucket walk does not reach offset 0");
-        // split point of the two-part optimiser step (run_backward): the lowest offset above which no variable belongs to op 0;
+        // split point of the two-part optimiser step (run_backward): the lowest offset above which no variable belongs to op 0
+        // and none is read by op 0's backward -- the first part updates its range while that backward (the stem's filter
+        // gradient, which reads the stem BatchNorm's gamma when it takes the apply pass) still runs on the side stream;
         // usable when it is 16-byte aligned and op 0 (the stem conv) really owns something below it
         adam_split = 0;
         size_t q = own_sorted.size();
         while (q > 0 && own_sufmin[q - 1] >= 1) --q;
+        int64_t read_end = 0;
+        for (auto& a : acts)
+            if (a.stem_link)
+                for (const Param* p : a.stem_link->reads) read_end = std::max(read_end, p->off + p->count);
+        while (q < own_sorted.size() && own_sorted[q].first < read_end) ++q;
         if (q > 0 && q < own_sorted.size() && (own_sorted[q].first & 3) == 0) adam_split = own_sorted[q].first;
     }
 

@@ -31,9 +31,9 @@
         HIPCHECK(fill_async(d_loss, 0, sizeof(double), c.s, "loss"));
         launch(c, "smooth_l1_kernel", 0, 12.0 * pred->rows(), [&]() { return p3d_smooth_l1(pred->p, d_y, pred->rows(), d_loss, d_dlogits, head_sigmoid ? 1 : 0, c.s); });
     }
-    // with_adam: the optimiser step is part of the call and split in two -- every variable but the first op's is updated while
-    // that op's filter gradient (the stem's: the last launch of the pass, alone on the side stream) is still running, the
-    // first op's own variables after it.  Returns whether Adam ran (false: the caller launches run_adam).
+    // with_adam: the optimiser step is part of the call and split in two -- every variable but the first op's (and those its
+    // backward reads, adam_split) is updated while that op's filter gradient (the stem's: the last launch of the pass, alone on
+    // the side stream) is still running, the rest after it.  Returns whether Adam ran (false: the caller launches run_adam).
     // Gradient buffer (248 MB), gradient arena of the activations and the double-precision reduction arena start a backward pass
     // at zero.  A train step knows that a backward pass follows its forward pass: it zeroes them on the side stream while the
     // forward runs (the previous step's optimiser has read the gradients: the side stream is joined before it) instead of

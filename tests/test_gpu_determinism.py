@@ -58,6 +58,29 @@ def test_adam_trajectories_are_bit_identical(structure, cfg, shape):
         assert np.array_equal(v, finals[1][1][n]), n
 
 
+def test_bench_step_trajectory_is_bit_identical_across_sessions():
+    """bench.py's timed path at its own configuration (p3d_unet, 8 clips of 16x112x112, device-resident inputs, dropout 0.5):
+    two fresh sessions must agree bit for bit.  The first Adam part runs beside the stem's filter gradient, which reads the
+    stem BatchNorm's gamma when it takes the normalisation's apply pass; with that gamma inside the first part, the
+    gradient of firstconv1 changed from run to run at this size."""
+    from sap3d_tensorflow_amd import P3DSession, synthetic
+    shape = (8, 16, 112, 112)
+    finals = []
+    for _ in range(2):
+        s = P3DSession("unet", batch=shape[0], frames=shape[1], height=shape[2], width=shape[3], seed=1)
+        s.upload(synthetic.synthetic_clip(0, shape + (3,)), synthetic.synthetic_target(3, shape))
+        losses = []
+        for i in range(2):
+            s.train_step_device(0.5, seed=i)
+            losses.append(np.float32(s.last_loss()).tobytes())
+        finals.append((losses, s.get_grad("firstconv1"), {n: s.get_param(n) for n, _, _ in s.variables()}))
+        s.close()
+    assert finals[0][0] == finals[1][0]
+    assert np.array_equal(finals[0][1], finals[1][1]), "firstconv1 gradient"
+    for n, v in finals[0][2].items():
+        assert np.array_equal(v, finals[1][2][n]), n
+
+
 def test_captured_step_graph_replays_the_eager_step_bit_for_bit():
     """P3D_GRAPH=1 (opt-in): the train step captured into a hipGraph over three streams -- parked side-stream jobs, the
     two-part optimiser step and the device-resident dropout seed / Adam step size included -- must give the eager
