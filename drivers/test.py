@@ -1,0 +1,145 @@
+#!/usr/bin/env python3
+"""Python-3 counterpart of the reference's evaluation program (/root/reference/test.py) on libp3dhip.
+
+Restores a checkpoint, runs the test clips batch by batch through ONE plain batched forward with training False (test.py:160;
+the backbone BatchNorm couples the clips of a batch, as in the reference -- not gen_pred's per-window predict_windows), and
+scores the last frame of every clip at the fixation maps' resolution: CC, SIM, AUC_Judd, AUC_Borji, NSS (test.py:166-176),
+all on the GPU (P3DSession.evaluate).  A trailing partial batch is dropped (BatchData(..., remainder=False), test.py:89).
+It prints test.py's two line formats: the running means every 100 batches (test.py:161-163, NaN-including like np.mean of
+the raw lists) and the NaN-dropped means at the end (test.py:177-183).
+
+The reference walks JPEG folders and decodes them with cv2 (test.py:73-90, dataflow.py:219-241); that stays out of scope.
+Here a test set is one .npz (--data) with
+    x         [N,16,112,112,3] float32, already normalised -- or raw uint8 BGR frames [N,16,H0,W0,3] (as cv2.imread gives them),
+              which go through the loader's pre-processing (sap3d_tensorflow_amd.dataflow.mapf_frames);
+    density   uint8 [N,Hd,Wd] or [N,16,Hd,Wd] (cv2.IMREAD_GRAYSCALE images; resized to the fixation size on the GPU);
+    fixation  uint8 [N,H,W] or [N,16,H,W] (H x W = 1080 x 960 in the reference).  Only the last frame is scored.
+Without --data, a synthetic set (sap3d_tensorflow_amd.synthetic.synthetic_test_set) is used.
+
+--sauc M adds a sixth column, shuffled AUC (utils/metrics.py:157-197) of the clean full-resolution prediction against the
+union of the fixations of M other clips (Borji's M = 10).  It draws from its own np.random.RandomState(seed): the five
+reference columns are identical with and without it.  --time prints per batch: forward, host random draws, host->device
+copy and the device metric stage."""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+STEP_LINE = " Step: %d, Metrics: CC: %.3f  SIM: %.3f   NSS: %.3f  AUC_Judd: %.3f   AUC_Borji: %.3f"        # test.py:161-163
+ALL_LINE = " All: %d, Metrics: CC: %.3f  SIM: %.3f   NSS: %.3f  AUC_Judd: %.3f   AUC_Borji: %.3f"          # test.py:182-183
+
+
+def batches(n, batch):
+    """[lo, hi) of every full batch: BatchData(..., remainder=False) drops a trailing partial batch (test.py:89)."""
+    return [(lo, lo + batch) for lo in range(0, n - batch + 1, batch)]
+
+
+def last_frame(maps):
+    maps = np.asarray(maps)
+    return maps[:, -1] if maps.ndim == 4 else maps
+
+
+def load_set(path, device=0):
+    d = np.load(path)
+    x, density, fixation = d["x"], last_frame(d["density"]), last_frame(d["fixation"])
+    if x.dtype == np.uint8:
+        from sap3d_tensorflow_amd import dataflow
+        n, t = x.shape[:2]
+        x = dataflow.mapf_frames(x.reshape((n * t,) + x.shape[2:]), 112, device=device).reshape(n, t, 112, 112, 3)
+    if density.dtype != np.uint8 or fixation.dtype != np.uint8:
+        raise ValueError("density and fixation maps must be uint8 images")
+    if not (len(x) == len(density) == len(fixation)):
+        raise ValueError("x, density and fixation hold different numbers of clips")
+    return np.asarray(x, np.float32), density, fixation
+
+
+def nan_dropped_means(cols):
+    """test.py:177-181: every metric's list without its NaNs, then the mean."""
+    return [float(np.mean(np.asarray(c)[~np.isnan(c)])) for c in cols]
+
+
+def metric_line(fmt, index, cols):
+    """cols in evaluate's order (CC, SIM, AUC_Judd, AUC_Borji, NSS [, sAUC]); the reference prints CC SIM NSS Judd Borji."""
+    cc, sim, judd, borji, nss = cols[:5]
+    line = fmt % (index, cc, sim, nss, judd, borji)
+    if len(cols) > 5:
+        line += "   sAUC: %.3f" % cols[5]
+    return line
+
+
+def shuffled_auc(sess, fixation, lo, m, rng, device=0):
+    """Column 6 for the clips of the batch at `lo`: shuffled AUC of the clean prediction (resized to the fixation size) against
+    the union of the fixations of m other clips of the set, drawn from `rng`."""
+    from sap3d_tensorflow_amd import dataflow, metrics
+    pred = sess.activation("pred")[:, -1, :, :, 0]
+    full = dataflow.resize_linear(pred, fixation.shape[1:], device=device)
+    out = []
+    for k in range(len(pred)):
+        i = lo + k
+        others = rng.choice(np.delete(np.arange(len(fixation)), i), size=min(m, len(fixation) - 1), replace=False)
+        other = np.any(fixation[others] >= 128, axis=0).astype(np.float32)
+        out.append(metrics.AUC_shuffled(full[k], (fixation[i] >= 128).astype(np.float32), other, device=device, rng=rng))
+    return out
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    p.add_argument("--model", type=str, default="", help="checkpoint: a directory with a TF `checkpoint` state file, a TF bundle "
+                   "prefix, or an .npz keyed by TF variable names (test.py:145-150); none: freshly initialised weights")
+    p.add_argument("--structure", type=str, default="unet++",
+                   help="unet, concat, unet++ (built as unet++ds, p3d_unetplusplus_ds, the buildable form of test.py:133-138), "
+                        "unet++nonsa, gn_p3d, gn_p3d_concat, gn_p3d_decoder")
+    p.add_argument("--data", type=str, default="", help="test set .npz (x, density, fixation); default: a synthetic set")
+    p.add_argument("--clips", type=int, default=6, help="clips of the synthetic set")
+    p.add_argument("--batch", type=int, default=2)
+    p.add_argument("--gpu", type=str, default="0")
+    p.add_argument("--seed", type=int, default=0, help="seeds numpy's global stream (the metrics' draws) and the synthetic set")
+    p.add_argument("--sauc", type=int, default=0, metavar="M", help="add shuffled AUC against the fixations of M other clips")
+    p.add_argument("--time", action="store_true", help="print the stage times of every batch")
+    # the reduced graph of the tests (the reference's is base 64, blocks 3/8/36)
+    p.add_argument("--base", type=int, default=64, help=argparse.SUPPRESS)
+    p.add_argument("--blocks", type=str, default="3,8,36", help=argparse.SUPPRESS)
+    args = p.parse_args(argv)
+
+    from sap3d_tensorflow_amd import P3DSession, synthetic
+    device = int(args.gpu)
+    if args.data:
+        x, density, fixation = load_set(args.data, device)
+    else:
+        x, density, fixation = synthetic.synthetic_test_set(args.seed, args.clips)
+    structure = "unet++ds" if args.structure == "unet++" else args.structure
+    blocks = tuple(int(v) for v in args.blocks.split(","))
+    sess = P3DSession(structure, batch=args.batch, frames=x.shape[1], height=x.shape[2], width=x.shape[3], base=args.base,
+                      blocks=blocks, device=device, seed=0)
+    if args.model:
+        print("loading checkpoint %s" % sess.restore(args.model))
+    print("Now using model %s with structure %s" % (args.model or "(initialised)", structure))
+    np.random.seed(args.seed)
+    sauc_rng = np.random.RandomState(args.seed) if args.sauc else None
+    cols = [[] for _ in range(6 if args.sauc else 5)]
+    index = 0
+    for lo, hi in batches(len(x), args.batch):
+        index += 1
+        if index % 100 == 0:
+            print(metric_line(STEP_LINE, index, [np.mean(c) for c in cols]))
+        m = sess.evaluate(x[lo:hi], density[lo:hi], fixation[lo:hi], size=fixation.shape[1:])
+        for k in range(5):
+            cols[k].extend(m[:, k].tolist())
+        if args.sauc:
+            cols[5].extend(shuffled_auc(sess, fixation, lo, args.sauc, sauc_rng, device))
+        if args.time:
+            t = sess.last_eval_ms
+            print("  batch %d: forward %.3f ms  host draws %.3f ms  host->device %.3f ms  device metrics %.3f ms"
+                  % (index, t["forward"], t["draws"], t["h2d"], t["device"]))
+    print(metric_line(ALL_LINE, index, nan_dropped_means(cols)))
+    print("Testing Finished!")
+    sess.close()
+    return cols
+
+
+if __name__ == "__main__":
+    main()

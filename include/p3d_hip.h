@@ -269,6 +269,31 @@ int p3d_metric_auc_borji(int device, const float* sal, const float* fix, const i
 int p3d_mapf_frames(int device, const unsigned char* bgr, int n, int H0, int W0, const float mean_rgb[3], int H, int W, float* out);
 int p3d_mapf_density(int device, const unsigned char* grey, int n, int H0, int W0, int H, int W, float* out);
 
+/* ---- the evaluation pass of test.py (test.py:160-183): metrics at ground-truth resolution, whole-GPU reductions.
+ * cv2.resize(map, (W, H), INTER_LINEAR) of float32 maps [n][h][w] -> [n][H][W] (test.py:170), bit-exact to the float32 path
+ * of OpenCV's generic resize (no FMA). */
+int p3d_resize_linear(int device, const float* src, int n, int h, int w, int H, int W, float* dst);
+/* AUC_shuffled, utils/metrics.py:157-197, one map: AUC_Borji's per-split sweep with S_rand = S at other_idx [n_rand][n_rep]
+ * (the pixels of the other maps' fixations the caller drew, row-major), n_rand = min(n_fix, fixated pixels of other_map);
+ * the false-positive rate still divides by n_fix (:151-152).  n_fix must equal the count of fix > 0.5.  out[n_rep] = area
+ * per split, NaN when nothing is fixated. */
+int p3d_metric_auc_shuffled(int device, const float* sal, const float* fix, const int* other_idx, int n_pix, int n_fix, int n_rand,
+                            int n_rep, double step_size, double* out);
+/* CC, SIM, AUC_Judd, AUC_Borji, NSS (out[B][5], in test.py:172-176's order) of the LAST frame of every clip of the handle's last
+ * forward pass, all on the device:
+ *   prediction [B][T][h][w] frame T-1 -> cv2.INTER_LINEAR float32 resize to H x W (test.py:170);
+ *   density [B][Hd][Wd] uint8 -> the uint8 resize to H x W (p3d_mapf_density's path), / 255. in double (dataflow.py:236-238);
+ *   fixation [B][H][W] uint8, fixated <=> / 255. > 0.5 <=> byte >= 128 (dataflow.py:239-241).
+ * jitter [B][H][W] (or NULL: jitter=False) is AUC_Judd's noise random.rand(H, W) * 1e-7 in float64; it is added to the
+ * prediction in double and rounded once to float32, in place as utils/metrics.py:65 does, so AUC_Borji and NSS see the
+ * jittered map and CC / SIM the clean one.  (p3d_metric_auc_judd takes float32 noise and adds it in float32.)
+ * borji_idx = the clips' randint(0, H*W, [n_fix_b, n_rep]) draws, concatenated; n_fix[B] = the host's fixation counts: a count
+ * that disagrees with the device's is refused.  Clips without fixation give NaN for AUC_Judd, AUC_Borji and NSS.
+ * stage_ms[2] (or NULL): device time of the host->device copies and of the metric stage (resizes included). */
+int p3d_eval_last_frames(p3d_handle* h, const unsigned char* density, int Hd, int Wd, const unsigned char* fixation, int H, int W,
+                         const double* jitter, const int* borji_idx, const int* n_fix, int n_rep, double step_size, double* out,
+                         double* stage_ms);
+
 /* CRC-32C of a host buffer (host-side helper of the TensorFlow checkpoint reader / writer, sap3d_tensorflow_amd/tf_checkpoint.py:
  * the bundle format of train.py:180-185,266-267 checksums every tensor); crc = running value, 0 to start. */
 uint32_t p3d_crc32c(const void* data, size_t n, uint32_t crc);

@@ -1007,6 +1007,187 @@ int p3d_mapf_density(int device, const unsigned char* grey, int n, int H0, int W
     API_END
 }
 
+// ---- ground-truth resolution (metrics_full.hip) ----------------------------------------------------------------------
+}  // extern "C"
+namespace {
+// Byte offsets of the buffers of one full-resolution evaluation inside one allocation (a first pass with base = null sizes it)
+struct Carve {
+    char* base = nullptr;
+    size_t off = 0;
+    template <typename T> T* take(size_t n) {
+        const size_t o = (off + 255) & ~(size_t)255;
+        off = o + (n > 0 ? n : 1) * sizeof(T);
+        return base ? (T*)(base + o) : nullptr;
+    }
+};
+int next_pow2(int n) { int p = 1; while (p < n) p <<= 1; return p; }
+// every scratch buffer of P3dFullMaps / P3dFullBorji; slot offsets and meta come from n_fix[n_maps]
+void carve_full(Carve& c, P3dFullMaps& a, P3dFullBorji& r, const std::vector<int>& meta) {
+    const int B = a.n_maps;
+    size_t slots = 0;
+    for (int b = 0; b < B; ++b) slots += next_pow2(meta[b * 3]);
+    a.meta = c.take<int>((size_t)B * 3);
+    a.partA = c.take<double>((size_t)B * a.nblk * 11);
+    a.partB = c.take<double>((size_t)B * a.nblk * 8);
+    a.partC = c.take<double>((size_t)B * a.nblk);
+    a.stats = c.take<double>((size_t)B * P3D_FULL_STATS);
+    a.fixv = c.take<float>(slots);
+    a.cnt = c.take<int>(slots + B);
+    r.per_rep = c.take<double>((size_t)B * r.n_rep);
+}
+std::vector<int> full_meta(const int* n_fix, int n_maps, int n_rep, long long n_pix, size_t& n_idx) {
+    std::vector<int> meta((size_t)n_maps * 3);
+    long long slot = 0, idx = 0;
+    for (int b = 0; b < n_maps; ++b) {
+        if (n_fix[b] < 0 || n_fix[b] > n_pix) throw P3dError("n_fix out of range");
+        meta[b * 3 + 0] = n_fix[b];
+        meta[b * 3 + 1] = (int)slot;
+        meta[b * 3 + 2] = (int)idx;
+        slot += next_pow2(n_fix[b]);
+        idx += (long long)n_fix[b] * n_rep;
+        if (slot > INT32_MAX / 2 || idx > INT32_MAX) throw P3dError("too many fixations");
+    }
+    n_idx = (size_t)idx;
+    return meta;
+}
+void check_indices(const int* idx, size_t n, long long n_pix, const char* what) {
+    for (size_t i = 0; i < n; ++i)
+        if (idx[i] < 0 || idx[i] >= n_pix) throw P3dError(std::string(what) + ": random index out of range");
+}
+}  // namespace
+extern "C" {
+
+int p3d_resize_linear(int device, const float* src, int n, int h, int w, int H, int W, float* dst) {
+    API_BEGIN
+    metric_args(device, src, src, 1, 1, dst);
+    if (n < 1 || h < 1 || w < 1 || H < 1 || W < 1) throw P3dError("resize: empty map");
+    DevArr<float> s((size_t)n * h * w, src), d((size_t)n * H * W);
+    HIPCHECK(p3d_resize_f32(s.p, (long long)h * w, 1, n, h, w, d.p, H, W, nullptr));
+    d.get(dst, (size_t)n * H * W);
+    API_END
+}
+
+int p3d_metric_auc_shuffled(int device, const float* sal, const float* fix, const int* other_idx, int n_pix, int n_fix, int n_rand,
+                            int n_rep, double step_size, double* out) {
+    API_BEGIN
+    metric_args(device, sal, fix, 1, n_pix, out);
+    if (n_rep < 1 || !(step_size > 0.0)) throw P3dError("AUC_shuffled needs n_rep >= 1 and a positive step");
+    if (n_rand < 0 || n_rand > n_fix) throw P3dError("AUC_shuffled: n_rand must be in [0, n_fix]");
+    if (n_rand > 0 && !other_idx) throw P3dError("AUC_shuffled: null random indices");
+    check_indices(other_idx, (size_t)n_rand * n_rep, n_pix, "AUC_shuffled");
+    P3dFullMaps a;
+    P3dFullBorji r;
+    a.fix = nullptr; a.fix_u8 = 0; a.n_pix = n_pix; a.n_maps = 1; a.nblk = p3d_full_blocks(n_pix);
+    r.n_rand = n_rand; r.n_rep = n_rep; r.step = step_size;
+    size_t n_idx = 0;
+    const std::vector<int> meta = full_meta(&n_fix, 1, 0, n_pix, n_idx);
+    Carve c;
+    carve_full(c, a, r, meta);
+    DevArr<char> scratch(c.off);
+    c = Carve{scratch.p, 0};
+    carve_full(c, a, r, meta);
+    DevArr<float> dsal(n_pix, sal), dfix(n_pix, fix);
+    DevArr<int> didx((size_t)n_rand * n_rep, other_idx);
+    const unsigned zero = 0;
+    DevArr<unsigned> counter(1, &zero);
+    HIPCHECK(copy_now((void*)a.meta, meta.data(), meta.size() * sizeof(int), hipMemcpyHostToDevice, nullptr));
+    a.P = dsal.p; a.fix = dfix.p; a.counter = counter.p; r.idx = didx.p;
+    HIPCHECK(p3d_full_moments(a, nullptr));
+    double st[P3D_FULL_STATS];
+    HIPCHECK(copy_now(st, a.stats, sizeof(st), hipMemcpyDeviceToHost, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    if ((int)st[P3D_FULL_STAT_NFIX] != n_fix)
+        throw P3dError("AUC_shuffled: n_fix = " + std::to_string(n_fix) + " but the fixation map has " +
+                       std::to_string((long long)st[P3D_FULL_STAT_NFIX]) + " fixated pixels");
+    if (n_fix == 0) { for (int i = 0; i < n_rep; ++i) out[i] = NAN; return 0; }      // "no fixation to predict"
+    HIPCHECK(p3d_full_borji(a, r, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    HIPCHECK(copy_now(out, r.per_rep, (size_t)n_rep * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    API_END
+}
+
+int p3d_eval_last_frames(p3d_handle* h, const unsigned char* density, int Hd, int Wd, const unsigned char* fixation, int H, int W,
+                         const double* jitter, const int* borji_idx, const int* n_fix, int n_rep, double step_size, double* out,
+                         double* stage_ms) {
+    API_BEGIN
+    if (!h || !density || !fixation || !n_fix || !out) throw P3dError("null argument");
+    if (Hd < 1 || Wd < 1 || H < 1 || W < 1) throw P3dError("eval: empty map");
+    if ((long long)H * W > INT32_MAX / 2) throw P3dError("eval: map too large");
+    if (n_rep < 1 || !(step_size > 0.0)) throw P3dError("eval: AUC_Borji needs n_rep >= 1 and a positive step");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    Act* pr = h->pred;
+    const int B = pr->N, T = pr->D;
+    const long long N = (long long)H * W;
+    size_t n_idx = 0;
+    const std::vector<int> meta = full_meta(n_fix, B, n_rep, N, n_idx);
+    if (n_idx > 0 && !borji_idx) throw P3dError("eval: null random indices");
+    check_indices(borji_idx, n_idx, N, "eval");
+    P3dFullMaps a;
+    P3dFullBorji r;
+    a.fix_u8 = 1; a.n_pix = N; a.n_maps = B; a.nblk = p3d_full_blocks(N); a.out = nullptr;
+    r.n_rand = -1; r.n_rep = n_rep; r.step = step_size;
+    float *P = nullptr, *D = nullptr;
+    unsigned char *dens = nullptr, *fixd = nullptr;
+    double *jit = nullptr, *dout = nullptr;
+    int* idx = nullptr;
+    auto layout = [&](Carve& c) {
+        P = c.take<float>((size_t)B * N);
+        D = c.take<float>((size_t)B * N);
+        dens = c.take<unsigned char>((size_t)B * Hd * Wd);
+        fixd = c.take<unsigned char>((size_t)B * N);
+        jit = c.take<double>(jitter ? (size_t)B * N : 0);
+        idx = c.take<int>(n_idx);
+        dout = c.take<double>((size_t)B * 5);
+        carve_full(c, a, r, meta);
+    };
+    Carve c;
+    layout(c);                                 // sizes the scratch
+    float* slab = nullptr;
+    unsigned* counters = nullptr;
+    const hipStream_t s = h->stream;
+    HIPCHECK(p3d_stream_scratch(s, (c.off + 3) / 4, (size_t)B, &slab, &counters));
+    c = Carve{(char*)slab, 0};
+    layout(c);
+    a.P = P; a.D = D; a.fix = fixd; a.jit = jitter ? jit : nullptr; a.counter = counters; a.out = dout; r.idx = idx;
+
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    if (stage_ms)
+        for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
+    if (stage_ms) HIPCHECK(hipEventRecord(ev[0], s));
+    HIPCHECK(copy_now(dens, density, (size_t)B * Hd * Wd, hipMemcpyHostToDevice, s));
+    HIPCHECK(copy_now(fixd, fixation, (size_t)B * N, hipMemcpyHostToDevice, s));
+    if (jitter) HIPCHECK(copy_now(jit, jitter, (size_t)B * N * sizeof(double), hipMemcpyHostToDevice, s));
+    if (n_idx) HIPCHECK(copy_now(idx, borji_idx, n_idx * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHECK(copy_now((void*)a.meta, meta.data(), meta.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    if (stage_ms) HIPCHECK(hipEventRecord(ev[1], s));
+    // the prediction of the last forward pass, frame T-1 of every clip: [B][T][h][w] with a row stride of ld floats
+    if (pr->materialize && h->last_forward_fused) pr->materialize(s);
+    const long long hw = (long long)pr->H * pr->W;
+    HIPCHECK(p3d_resize_f32(pr->p + (size_t)(T - 1) * hw * pr->ld, (long long)T * hw * pr->ld, pr->ld, B, pr->H, pr->W, P, H, W, s));
+    HIPCHECK(p3d_mapf_density(dens, B, Hd, Wd, D, H, W, s));                  // test.py's density: uint8 resize (dataflow.py:236-238)
+    HIPCHECK(p3d_full_moments(a, s));
+    HIPCHECK(p3d_full_rank(a, s));
+    HIPCHECK(p3d_full_borji(a, r, s));
+    if (stage_ms) HIPCHECK(hipEventRecord(ev[2], s));
+    std::vector<double> st((size_t)B * P3D_FULL_STATS);
+    HIPCHECK(copy_now(out, dout, (size_t)B * 5 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHECK(copy_now(st.data(), a.stats, st.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    if (stage_ms) {
+        float t0 = 0, t1 = 0;
+        HIPCHECK(hipEventElapsedTime(&t0, ev[0], ev[1]));
+        HIPCHECK(hipEventElapsedTime(&t1, ev[1], ev[2]));
+        stage_ms[0] = t0; stage_ms[1] = t1;
+        for (auto& e : ev) HIPCHECK(hipEventDestroy(e));
+    }
+    for (int b = 0; b < B; ++b)
+        if ((long long)st[(size_t)b * P3D_FULL_STATS + P3D_FULL_STAT_NFIX] != n_fix[b])
+            throw P3dError("eval: clip " + std::to_string(b) + ": n_fix = " + std::to_string(n_fix[b]) + " but its fixation map has " +
+                           std::to_string((long long)st[(size_t)b * P3D_FULL_STATS + P3D_FULL_STAT_NFIX]) + " fixated pixels");
+    API_END
+}
+
 // CRC-32C (Castagnoli) of a host buffer, slicing-by-8: the checksum of TensorFlow's checkpoint bundles
 // (tensorflow/core/lib/hash/crc32c.h), used by the Python reader / writer of sap3d_tensorflow_amd/tf_checkpoint.py on the
 // 248 MB of variables (train.py:180-185, 204-210, 266-267).  `crc` = running value (0 to start).

@@ -513,6 +513,42 @@ hipError_t p3d_mapf_frames(const unsigned char* bgr, int n_frames, int H0, int W
                            hipStream_t s);
 hipError_t p3d_mapf_density(const unsigned char* grey, int n_frames, int H0, int W0, float* dst, int H, int W, hipStream_t s);
 
+// ---- the same metrics at ground-truth resolution, whole-GPU reductions (metrics_full.hip; test.py:160-183) ------
+// cv2.INTER_LINEAR resize of float32 maps: map m's pixel (y, x) at src[m * map_stride + (y * w + x) * elem_stride]
+hipError_t p3d_resize_f32(const float* src, long long map_stride, int elem_stride, int n, int h, int w, float* dst, int H, int W,
+                          hipStream_t s);
+struct P3dFullMaps {
+    const float* P = nullptr;        // [n_maps][n_pix] saliency maps (clean)
+    const float* D = nullptr;        // [n_maps][n_pix] density maps as float32(v / 255.) of the uint8 resize, or null (no CC / SIM)
+    const void* fix = nullptr;       // [n_maps][n_pix] fixation maps: uint8 (>= 128) if fix_u8, else float32 (> 0.5)
+    int fix_u8 = 0;
+    const double* jit = nullptr;     // [n_maps][n_pix] AUC_Judd's noise, added in double and rounded to float32, or null
+    long long n_pix = 0;
+    int n_maps = 0, nblk = 0;        // nblk = p3d_full_blocks(n_pix) blocks per map
+    const int* meta = nullptr;       // [n_maps][3]: n_fix, slot offset in fixv (cnt: + map index; room for next_pow2(n_fix) (+1)), random-index offset
+    double* partA = nullptr;         // [n_maps][nblk][11]
+    double* partB = nullptr;         // [n_maps][nblk][8]
+    double* partC = nullptr;         // [n_maps][nblk]
+    unsigned* counter = nullptr;     // [n_maps] arrival counters, zero at launch (and after)
+    double* stats = nullptr;         // [n_maps][P3D_FULL_STATS]
+    float* fixv = nullptr;           // fixated values of the (jittered) map, sorted descending by p3d_full_rank
+    int* cnt = nullptr;              // AUC-Judd counters
+    double* out = nullptr;           // [n_maps][5] CC, SIM, AUC_Judd, AUC_Borji, NSS; null: the per-split AUCs only
+};
+struct P3dFullBorji {
+    const int* idx = nullptr;        // random pixel indices [n_rand][n_rep] per map (at meta[b][2])
+    int n_rand = -1;                 // -1: n_fix rows (AUC_Borji)
+    int n_rep = 0;
+    double step = 0.1;
+    double* per_rep = nullptr;       // [n_maps][n_rep]
+};
+constexpr int P3D_FULL_STATS = 12;            // per map: means, minima, maxima of P, D, J; the fixation count; SIM's range sums
+constexpr int P3D_FULL_STAT_NFIX = 9;         // stats[b][9]: the device's count of fixated pixels (a double)
+int p3d_full_blocks(long long n_pix);
+hipError_t p3d_full_moments(const P3dFullMaps& a, hipStream_t s);        // stats, CC, NSS, the fixated values
+hipError_t p3d_full_rank(const P3dFullMaps& a, hipStream_t s);           // thresholds sorted; SIM, AUC_Judd
+hipError_t p3d_full_borji(const P3dFullMaps& a, const P3dFullBorji& r, hipStream_t s);
+
 // ---- misc ---------------------------------------------------------------------------------------
 hipError_t p3d_add_inplace(float* dst, int lddst, const float* src, int ldsrc, long M, int C, hipStream_t s);
 hipError_t p3d_copy_strided(float* dst, int lddst, const float* src, int ldsrc, long M, int C, hipStream_t s);

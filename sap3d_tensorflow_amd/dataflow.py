@@ -38,3 +38,19 @@ def mapf_density(maps_grey, size=112, device=0):
     check(lib().p3d_mapf_density(device, f.ctypes.data_as(C.POINTER(C.c_ubyte)), f.shape[0], f.shape[1], f.shape[2], H, W,
                                  out.ctypes.data_as(C.POINTER(C.c_float))))
     return out
+
+
+def resize_linear(maps, size, device=0):
+    """cv2.resize(m, (W, H), interpolation=cv2.INTER_LINEAR) of float32 single-channel maps (test.py:170 resizes every
+    112x112 prediction to the 1080x960 fixation map): [n, h, w] or [h, w] -> [n, H, W] / [H, W]; size = (H, W) or an int."""
+    m = np.ascontiguousarray(maps, dtype=np.float32)
+    single = m.ndim == 2
+    if single:
+        m = m[None]
+    if m.ndim != 3 or m.size == 0:
+        raise ValueError("expected [n, h, w] or [h, w] float32 maps")
+    H, W = (size, size) if np.isscalar(size) else size
+    out = np.empty((m.shape[0], H, W), np.float32)
+    check(lib().p3d_resize_linear(device, m.ctypes.data_as(C.POINTER(C.c_float)), m.shape[0], m.shape[1], m.shape[2], H, W,
+                                  out.ctypes.data_as(C.POINTER(C.c_float))))
+    return out[0] if single else out

@@ -107,3 +107,31 @@ def AUC_Borji(saliency_map, fixation_map, n_rep=100, step_size=0.1, rand_sampler
     check(lib().p3d_metric_auc_borji(device, _fp(a), _fp(b), r.ctypes.data_as(C.POINTER(C.c_int)), a.size, n_fix, n_rep,
                                      float(step_size), _dp(out)))
     return float(np.mean(out))
+
+
+def AUC_shuffled(saliency_map, fixation_map, other_map, n_rep=100, step_size=0.1, device=0, rng=None, other_idx=None):
+    """utils/metrics.py:157-197: AUC_Borji with the random locations drawn from the fixations of OTHER images (other_map:
+    the union of M other fixation maps, Borji's M = 10).  The draws restate the Python-2 code: for each of the n_rep splits
+    in order, random.permutation(n_other)[:n_fix] (`map` is eager in Python 2), transposed to [min(n_fix, n_other), n_rep]
+    rows; with fewer other fixations than n_fix the rows are shorter but the false-positive rate still divides by n_fix
+    (:151-152); with none, no sample is drawn and the curve closes at (1, 1).  `other_idx` supplies the pixel indices instead.
+    NaN (and no draw) when nothing is fixated."""
+    other = np.asarray(other_map) > 0.5
+    if other.shape != np.shape(fixation_map):
+        raise ValueError("other_map.shape != fixation_map.shape")                            # :186-187
+    a, b = _maps(saliency_map, np.asarray(fixation_map, dtype=np.float32))
+    n_fix = int(np.count_nonzero(b > 0.5))
+    if n_fix == 0:
+        return float("nan")                 # AUC_Borji returns before it calls the sampler (:122-124)
+    if other_idx is None:
+        fixated = np.nonzero(other.ravel())[0]
+        src = rng if rng is not None else np.random
+        rows = [src.permutation(len(fixated))[:n_fix] for _ in range(n_rep)]                  # :190
+        other_idx = fixated[np.asarray(rows, dtype=np.int64).reshape(n_rep, -1).T]            # :191
+    r = np.ascontiguousarray(other_idx, dtype=np.int32).reshape(-1, n_rep)
+    if r.shape[0] > n_fix:
+        raise ValueError("other_idx has more than n_fix = %d rows" % n_fix)
+    out = np.empty(n_rep, np.float64)
+    check(lib().p3d_metric_auc_shuffled(device, _fp(a), _fp(b), r.ctypes.data_as(C.POINTER(C.c_int)), a.size, n_fix, r.shape[0],
+                                        n_rep, float(step_size), _dp(out)))
+    return float(np.mean(out))

@@ -246,6 +246,58 @@ class P3DSession:
         check(lib().p3d_backward(self._h, fptr(x), fptr(y), float(dropout), seed, C.byref(loss), fptr(pred)))
         return loss.value, pred
 
+    def evaluate(self, x, density, fixation, size=(1080, 960), jitter=True, n_rep=100, step_size=0.1, rng=None):
+        """The per-batch body of test.py (test.py:160-176) -> [B, 5] float64: CC, SIM, AUC_Judd, AUC_Borji, NSS of the last
+        frame of every clip, scored at the fixation maps' resolution.  One plain batched forward with training False (:160:
+        the backbone BatchNorm couples the clips of a batch, as in the reference), then one device pass that resizes the
+        prediction (cv2.resize(prediction, (960, 1080)), :170) and the density map (dataflow.py:236-238) and computes the
+        five metrics; only the five numbers per clip come back.
+        density: uint8 [B, Hd, Wd] or [B, T, Hd, Wd]; fixation: uint8 [B, H, W] or [B, T, H, W] with (H, W) == size; the last
+        frame is used (:167-169).  numpy's stream (`rng`, default np.random, as utils/metrics.py draws) is consumed per clip
+        in the reference's order: AUC_Judd's random.rand(H, W) (jitter=True, :64-65), then AUC_Borji's
+        random.randint(0, H*W, [n_fix, n_rep]) (:139); a clip without fixation draws nothing (:56-59, :122-124).
+        Stage times of the call are left in `last_eval_ms` (forward, draws, h2d, device; milliseconds)."""
+        import time
+        H, W = (size, size) if np.isscalar(size) else tuple(size)
+        B = self.x_shape[0]
+        dens = np.asarray(density)
+        fix = np.asarray(fixation)
+        if dens.dtype != np.uint8 or fix.dtype != np.uint8:
+            raise ValueError("density and fixation maps are uint8 images (cv2.IMREAD_GRAYSCALE)")
+        dens = np.ascontiguousarray(dens[:, -1] if dens.ndim == 4 else dens)
+        fix = np.ascontiguousarray(fix[:, -1] if fix.ndim == 4 else fix)
+        if dens.ndim != 3 or dens.shape[0] != B or fix.ndim != 3 or fix.shape[0] != B:
+            raise ValueError("expected %d density / fixation maps, [B, H, W] or [B, T, H, W]" % B)
+        if fix.shape[1:] != (H, W):
+            raise ValueError("fixation maps are %s, not %s: the reference would resize the prediction to them through skimage, "
+                             "which this library does not reproduce" % (fix.shape[1:], (H, W)))
+        t0 = time.perf_counter()
+        self.upload(x, None)
+        self.forward_device(training=False)
+        self.synchronize()
+        t1 = time.perf_counter()
+        src = rng if rng is not None else np.random
+        n_fix = np.count_nonzero(fix.reshape(B, -1) >= 128, axis=1).astype(np.int32)        # / 255. > 0.5
+        jit = np.zeros((B, H, W), np.float64) if jitter else None
+        idx = []
+        for b in range(B):
+            if n_fix[b] == 0:
+                continue
+            if jitter:
+                jit[b] = src.rand(H, W) * 1e-7
+            idx.append(src.randint(0, H * W, [int(n_fix[b]), n_rep]).astype(np.int32).ravel())
+        idx = np.ascontiguousarray(np.concatenate(idx) if idx else np.zeros(0, np.int32))
+        t2 = time.perf_counter()
+        out = np.empty((B, 5), np.float64)
+        ms = (C.c_double * 2)()
+        u8 = C.POINTER(C.c_ubyte)
+        check(lib().p3d_eval_last_frames(self._h, dens.ctypes.data_as(u8), dens.shape[1], dens.shape[2], fix.ctypes.data_as(u8),
+                                         H, W, jit.ctypes.data_as(_lib._dp) if jit is not None else None,
+                                         idx.ctypes.data_as(_lib._ip), n_fix.ctypes.data_as(_lib._ip), int(n_rep), float(step_size),
+                                         out.ctypes.data_as(_lib._dp), ms))
+        self.last_eval_ms = dict(forward=(t1 - t0) * 1e3, draws=(t2 - t1) * 1e3, h2d=ms[0], device=ms[1])
+        return out
+
     def set_adam(self, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8):
         check(lib().p3d_set_adam(self._h, lr, beta1, beta2, eps))
 

@@ -17,3 +17,19 @@ def synthetic_target(seed, shape):
     """shape [B,T,H,W] float32 saliency targets in [0,1)."""
     rng = np.random.Generator(np.random.PCG64(seed))
     return rng.random(size=shape, dtype=np.float32)
+
+
+def synthetic_test_set(seed, n, size=(1080, 960), density_size=(270, 480), frames=16, crop=112):
+    """An evaluation set for drivers/test.py: x [n,frames,crop,crop,3] float32 by the synthetic_clip law; density uint8
+    [n, Hd, Wd] uniform bytes; fixation uint8 [n, H, W]: clip i gets 255 at k ~ U{50..999} uniform pixel draws (with
+    replacement), except every third clip (i % 3 == 2), which stays empty (the reference's metrics give NaN there)."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    x = synthetic_clip(seed, (n, frames, crop, crop, 3))
+    density = rng.integers(0, 256, size=(n,) + tuple(density_size), dtype=np.uint8)
+    fixation = np.zeros((n,) + tuple(size), np.uint8)
+    for i in range(n):
+        k = int(rng.integers(50, 1000))
+        pix = rng.integers(0, size[0] * size[1], size=k)
+        if i % 3 != 2:
+            fixation[i].reshape(-1)[pix] = 255
+    return x, density, fixation
