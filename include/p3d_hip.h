@@ -237,6 +237,32 @@ int p3d_op_conv3d_transpose(int device, const float* x, const int64_t xshape[5],
  * y, dz [N,D,ceil(H/2),ceil(W/2),64]; tab [5][64] = scale, shift, mean, invstd, gamma; coef [64][2]; both results [1,7,7,3,64]. */
 int p3d_debug_stem_wgrad_through_bn(int device, const float* x, const int64_t xshape[5], const float* y, const float* dz, const float* tab,
                                     const float* coef, int batch, float* dw_fused, float* dw_two_launches);
+/* Test hooks: BatchNorm statistics behind a conv (tf.layers.conv3d / conv3d_transpose, then tf.layers.batch_normalization
+ * in training).  Shapes as p3d_op_conv3d (transpose = 0) or p3d_op_conv3d_transpose (transpose = 1).
+ * p3d_debug_conv_bn_stats: the conv's launches with the statistics epilogue, sized and routed like the network's, then the
+ * finalize (batch statistics, momentum-0.99 update of the moving statistics, eps 1e-3, gamma 1, beta 0).  w2 non-null: a sibling
+ * pair of forward convs on one input (ST_B), y2 its second output.  moving [pairs][2][C] = (mean, variance), updated in place;
+ * stats [pairs][4][C] = scale, shift, mean, invstd; nparts[pairs] = epilogue partials written (0: the small-tensor BatchNorm
+ * takes the tensor and computes its own -- the hook's statistics then come from p3d_bn_stats, not from bn_small.hip, whose
+ * statistics p3d_debug_bn_pass covers); *kernel = the plan of the first launch.
+ * p3d_debug_stat_parts (host only, no HIP call): the partials such a conv writes and the room the network reserves for them.
+ * p3d_debug_igemm_groupable (host only): would two sibling forward convs of this shape go out as one grouped launch (1 / 0). */
+int p3d_debug_conv_bn_stats(int device, const float* x, const int64_t xshape[5], const float* w, const float* w2, const int64_t wshape[5],
+                            const int s[3], const float* bias, int transpose, float* moving, float* y, float* y2, float* stats,
+                            int* nparts, const char** kernel);
+/* Test hook: one BatchNorm normalise / ReLU / add pass (modes of bn_apply: 0 relu(bn1(y1)), 1 relu(bn1(y1) + r),
+ * 2 relu(bn1(y1) + bn2(y2)), 3 relu(bn1(y1)) + relu(bn2(y2)), 4 r + relu(bn1(y1))) on [M][C] inputs, forward then backward,
+ * launched as the network launches it.  y2 is the second BN input or the residual r (null for mode 0).  params [bns][2][C] =
+ * gamma, beta; moving [bns][2][C] = moving (mean, variance), updated in place when update_moving and the BN uses batch
+ * statistics (batch1 / batch2).  dz: gradient of z; dy2 (modes 1-4): when acc2, holds the gradient to add to on entry.
+ * grads [bns][2][C] = dgamma, dbeta.  path: 0 = the network's rule, 1 = small-tensor kernels, 2 = fold-apply, 3 = finalize +
+ * apply (the last two with the three-launch backward); a forced path the kernels cannot take is an error.
+ * info[3] = path taken, forward statistics partials per BN, backward partials. */
+int p3d_debug_bn_pass(int device, int mode, int64_t M, int C, const float* y1, const float* y2, const float* params, int batch1,
+                      int batch2, int update_moving, const float* dz, int acc2, int path, float* z, float* dy1, float* dy2,
+                      float* grads, float* moving, int* info);
+int p3d_debug_stat_parts(const int64_t xshape[5], const int64_t wshape[5], const int s[3], int transpose, int* written, int* cap);
+int p3d_debug_igemm_groupable(const int64_t xshape[5], const int64_t wshape[5], const int s[3]);
 int p3d_op_max_pool3d(int device, const float* x, const int64_t xshape[5], const int ksize[3], const int s[3], float* y);
 int p3d_op_max_pool3d_grad(int device, const float* x, const int64_t xshape[5], const int ksize[3], const int s[3],
                            const float* dy, float* dx);

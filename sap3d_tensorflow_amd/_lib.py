@@ -78,6 +78,12 @@ SIGNATURES = {
     "p3d_debug_bucket_audit": (C.c_int, [C.c_void_p, C.c_float, C.c_uint64, C.c_int64, _i64p, _i64p, C.POINTER(C.c_int32), C.c_int,
                                          _i64p, _i64p]),
     "p3d_op_conv3d": (C.c_int, [C.c_int, _fp, _i64p, _fp, _i64p, _ip, _fp, _fp]),
+    "p3d_debug_conv_bn_stats": (C.c_int, [C.c_int, _fp, _i64p, _fp, _fp, _i64p, _ip, _fp, C.c_int, _fp, _fp, _fp, _fp, _ip,
+                                          C.POINTER(C.c_char_p)]),
+    "p3d_debug_bn_pass": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int,
+                                    C.c_int, _fp, _fp, _fp, _fp, _fp, _ip]),
+    "p3d_debug_stat_parts": (C.c_int, [_i64p, _i64p, _ip, C.c_int, _ip, _ip]),
+    "p3d_debug_igemm_groupable": (C.c_int, [_i64p, _i64p, _ip]),
     "p3d_op_conv3d_backprop_input": (C.c_int, [C.c_int, _fp, _fp, _i64p, _ip, _i64p, _fp]),
     "p3d_op_conv3d_backprop_filter": (C.c_int, [C.c_int, _fp, _i64p, _fp, _i64p, _ip, _fp, _fp]),
     "p3d_op_conv3d_transpose": (C.c_int, [C.c_int, _fp, _i64p, _fp, _i64p, _ip, _fp, _fp]),

@@ -1032,6 +1032,8 @@ bool p3d_igemm2_groupable(const IgemmArgs* v, int n, const P3dIgemmPlan& pl) {
             return false;
         const P3dIgemmPlan q = p3d_igemm2_plan(a, 1);
         if (q.bm != pl.bm || q.bn != pl.bn) return false;          // (each class keeps its own K-slice count)
+        // a streaming class reports one statistics partial per streaming block (p3d_igemm2_mtiles), the group kernel writes one per tile
+        if (q.stream_blocks > 0) return false;
     }
     return true;
 }

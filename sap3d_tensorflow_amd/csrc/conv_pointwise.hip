@@ -230,8 +230,11 @@ __global__ __launch_bounds__(256, 2) void pw_stream_kernel(const IgemmArgs p, co
 
 struct PwLaunch { size_t lds; int grid; int nslabs; };
 
+constexpr int PW_MAX_GRID = 512;                  // two blocks per CU (three measured the same); the slabs are dealt round-robin
+int pw_slab_rows(int N) { return N >= 128 ? 32 : 64; }
+
 size_t pw_lds_bytes(int N) {
-    const int SR = N >= 128 ? 32 : 64;
+    const int SR = pw_slab_rows(N);
     return ((size_t)3 * SR * PW_KC + 2 * N * 2) * sizeof(float);
 }
 
@@ -244,11 +247,11 @@ bool pw_shape(const IgemmArgs& a, PwLaunch& L) {
     // against the tiled kernel's 28.0 / 27.0 (forward / input gradient)
     if (a.K != 64 || (a.Nc != 64 && a.Nc != 128 && a.Nc != 256)) return false;
     if ((a.ldx & 3) || (a.ldy & 3) || M < 16384 || M >= (1ll << 31) / 256) return false;
-    const int SR = a.Nc >= 128 ? 32 : 64;
+    const int SR = pw_slab_rows(a.Nc);
     if (M % SR) return false;                    // whole slabs only: every wave issues the same number of stores per slab (the counted waits)
     L.lds = pw_lds_bytes(a.Nc);
     L.nslabs = (int)((M + SR - 1) / SR);
-    L.grid = std::min(L.nslabs, 512);            // two blocks per CU (three measured the same); the slabs are dealt round-robin
+    L.grid = std::min(L.nslabs, PW_MAX_GRID);
     return true;
 }
 
@@ -270,6 +273,13 @@ int p3d_pw_stream_blocks(const IgemmArgs& a) {
     static const bool off = p3d_tune_env("P3D_PW_STREAM") && atoi(p3d_tune_env("P3D_PW_STREAM")) == 0;      // A/B runs (tuning build)
     PwLaunch L;
     return !off && pw_shape(a, L) ? L.grid : 0;
+}
+
+// The most blocks (= statistics partials) any launch of this kernel that writes M rows of N channels can run with: what a
+// BatchNorm behind such a conv must have room for (net.hip, bn_part_cap).  0: no launch of that output shape streams.
+int p3d_pw_stream_max_blocks(long long M, int N) {
+    if ((N != 64 && N != 128 && N != 256) || M < 16384) return 0;
+    return (int)std::min<long long>(M / pw_slab_rows(N), PW_MAX_GRID);
 }
 
 hipError_t p3d_launch_pw_stream(const IgemmArgs& a0, hipStream_t s) {

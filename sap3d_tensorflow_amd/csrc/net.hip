@@ -309,6 +309,13 @@ void zero_strided(const Ctx& c, float* p, int ld, int64_t rows, int C);
 // (read by p3d_bn_finalize right after, on the same stream).
 struct StatSink { float* part = nullptr; int cap = 0; int* nparts = nullptr; };
 
+// Room for the statistics partials of a `rows` x C output, whichever producer writes them: one per 64-row tile of every
+// launch of the group (residue classes of a transposed conv: up to 64), one per block of p3d_bn_stats, or one per block
+// of the streaming 1x1x1 kernel (conv_pointwise.hip: up to 512 from 16 384 rows on, 32-row slabs at 128 channels).
+int bn_part_cap(int64_t rows, int C) {
+    return (int)std::max<int64_t>({rows / 64 + 80, (int64_t)p3d_bn_stats_parts((long)rows, C), (int64_t)p3d_pw_stream_max_blocks(rows, C)});
+}
+
 // A group of implicit-GEMM launches that together produce one output tensor (one conv forward,
 // or the residue classes of an input gradient / transposed conv).  Small problems slice K across blocks;
 // the slices are folded in a fixed order by the last arriving block (conv_igemm2.hip), so the output needs no
@@ -362,6 +369,28 @@ void run_igemm_group(const Ctx& c, std::vector<IgemmArgs>& v, float* out, int ld
         HIPCHECK(ev_wait(c.s, join));
     }
     if (stats && stats->nparts) *stats->nparts = base;
+}
+
+// Sibling convs on one input (ST_B, net_ops.inc conv()): each writes its statistics partials into its own BatchNorm's slot
+// from partial 0 ...
+void attach_sibling_stats(IgemmArgs& a, const StatSink& sink) {
+    const int mt = p3d_igemm2_mtiles(a, p3d_igemm2_plan(a, 1));
+    if (mt > sink.cap) throw P3dError("statistics partials overflow their arena slot");
+    a.statpart = sink.part; *sink.nparts = mt;
+}
+// ... and the pair goes out as ONE grouped launch when the plan allows it (either alone leaves most CUs idle), else as one
+// launch each.  Returns whether it was grouped.
+bool launch_siblings(const Ctx& c, std::vector<IgemmArgs>& v) {
+    const P3dIgemmPlan pl = p3d_igemm2_plan(v[0], 1);
+    if (p3d_igemm2_groupable(v.data(), (int)v.size(), pl)) {
+        double fl = 0, by = 0;
+        for (auto& q : v) { double f1, b1; igemm_work(q, f1, b1); fl += f1; by += b1; }
+        const std::string kn = std::string("igemm2_group_kernel<") + std::to_string(pl.bm) + "," + std::to_string(pl.bn) + ">(siblings)";
+        launch(c, kn.c_str(), fl, by, [&]() { return p3d_launch_igemm2_group(v.data(), (int)v.size(), pl, c.s); });
+        return true;
+    }
+    for (auto& q : v) launch_igemm(c, q, 1);
+    return false;
 }
 
 // Runs `f(side_ctx)` on the side stream after everything queued so far on the main stream.
@@ -811,12 +840,11 @@ struct p3d_handle {
         });
         return bn;
     }
-    // Reserve room for the producer's per-tile statistics partials of a `rows`-row output: one per 64-row tile of
-    // every launch of the group (residue classes of a transposed conv: up to 64), or per block of p3d_bn_stats.
+    // Reserve room for the producer's per-tile statistics partials of a `rows`-row output (bn_part_cap).
     float* statpart_arena = nullptr; int64_t statpart_count = 0;
     void reserve_stat_parts(BN* bn, int64_t rows) {
         if (bn->part_off >= 0) return;
-        bn->part_cap = (int)std::max<int64_t>(rows / 64 + 80, p3d_bn_stats_parts((long)rows, bn->C));
+        bn->part_cap = bn_part_cap(rows, bn->C);
         bn->part_off = statpart_count;
         statpart_count += (int64_t)bn->part_cap * bn->C * 2;
     }

@@ -801,6 +801,237 @@ int p3d_debug_stem_wgrad_through_bn(int device, const float* x, const int64_t xs
     API_END
 }
 
+// ---- BatchNorm statistics behind a conv (test hooks, include/p3d_hip.h) ----------------------------------------------------
+namespace {
+// The launches of one conv that feeds a BatchNorm, built the way conv() / deconv() build them.  transpose: xs is the input of
+// tf.layers.conv3d_transpose and ws its kernel [kd,kh,kw,Cout,Cin].  The stem ([1,kh,kw,3,C]) reads its packed copies x4 / w4.
+struct ConvBnGroup { std::vector<IgemmArgs> v; int64_t rows = 0; int C = 0; bool stem = false; ConvGeo g; StemGeo sg{}; };
+ConvBnGroup conv_bn_group(const int64_t xs[5], const int64_t ws[5], const int s[3], int transpose, const float* x, const float* w,
+                          float* y, const float* bias, const float* x4 = nullptr, const float* w4 = nullptr) {
+    ConvBnGroup r;
+    const int k[3] = {(int)ws[0], (int)ws[1], (int)ws[2]};
+    const int Cin = (int)xs[4];
+    if (transpose) {
+        r.C = (int)ws[3];
+        if (ws[4] != Cin) throw P3dError("kernel Cin mismatch");
+        r.g = make_geo((int)xs[1] * s[0], (int)xs[2] * s[1], (int)xs[3] * s[2], k, s);
+        r.rows = xs[0] * r.g.I[0] * r.g.I[1] * r.g.I[2];
+        r.v = igemm_conv_input_side(r.g, (int)xs[0], x, Cin, Cin, y, r.C, r.C, w, bias, 0, true);
+        return r;
+    }
+    r.C = (int)ws[4];
+    if (ws[3] != Cin) throw P3dError("filter Cin mismatch");
+    r.g = make_geo((int)xs[1], (int)xs[2], (int)xs[3], k, s);
+    r.rows = xs[0] * r.g.O[0] * r.g.O[1] * r.g.O[2];
+    if (is_stem_shape(xs, ws)) {
+        if (Cin != 3 || bias) throw P3dError("the stem path is for [1,kh,kw,3,C] kernels without bias");
+        r.stem = true;
+        r.sg = stem_geo(r.g, (int)xs[0]);
+        r.v.push_back(stem_forward_args(r.g, (int)xs[0], r.sg, x4, w4, y, r.C, r.C, nullptr));
+    } else {
+        r.v.push_back(igemm_conv_forward(r.g, (int)xs[0], x, Cin, Cin, y, r.C, r.C, w, bias, 0, false));
+    }
+    return r;
+}
+int group_parts(const std::vector<IgemmArgs>& v) {
+    int n = 0;
+    for (const IgemmArgs& a : v) n += p3d_igemm2_mtiles(a, p3d_igemm2_plan(a, 1));
+    return n;
+}
+}  // namespace
+
+int p3d_debug_stat_parts(const int64_t xs[5], const int64_t ws[5], const int s[3], int transpose, int* written, int* cap) {
+    API_BEGIN
+    if (!xs || !ws || !s || !written || !cap) throw P3dError("null argument");
+    const ConvBnGroup r = conv_bn_group(xs, ws, s, transpose, nullptr, nullptr, nullptr, nullptr);
+    const bool small = p3d_bn_small_ok((long)r.rows, r.C);      // (the network's stats_target: no epilogue partials)
+    *written = small ? 0 : group_parts(r.v);
+    *cap = small ? 0 : bn_part_cap(r.rows, r.C);
+    API_END
+}
+
+int p3d_debug_igemm_groupable(const int64_t xs[5], const int64_t ws[5], const int s[3]) {
+    try {
+        if (!xs || !ws || !s) throw P3dError("null argument");
+        // two sibling convs of one input, as conv() sends them (ST_B): distinct weights and outputs, shared everything else
+        static float dummy[4];
+        ConvBnGroup a = conv_bn_group(xs, ws, s, 0, dummy, dummy, dummy, nullptr);
+        ConvBnGroup b = conv_bn_group(xs, ws, s, 0, dummy, dummy + 1, dummy + 2, nullptr);
+        if (a.stem) throw P3dError("the stem has no sibling");
+        std::vector<IgemmArgs> v{a.v[0], b.v[0]};
+        return p3d_igemm2_groupable(v.data(), 2, p3d_igemm2_plan(v[0], 1)) ? 1 : 0;
+    } catch (const std::exception& e) {
+        g_err = e.what();
+        return -1;
+    }
+}
+
+int p3d_debug_conv_bn_stats(int device, const float* x, const int64_t xs[5], const float* w, const float* w2, const int64_t ws[5],
+                            const int s[3], const float* bias, int transpose, float* moving, float* y, float* y2, float* stats,
+                            int* nparts, const char** kernel) {
+    API_BEGIN
+    HIPCHECK(hipSetDevice(device));
+    if (!x || !w || !xs || !ws || !s || !moving || !y || !stats || !nparts) throw P3dError("null argument");
+    if (w2 && (transpose || !y2)) throw P3dError("a sibling pair is two forward convs with two outputs");
+    const int64_t nx = prod5(xs), nw = prod5(ws);
+    const ConvBnGroup shape = conv_bn_group(xs, ws, s, transpose, nullptr, nullptr, nullptr, nullptr);
+    const int C = shape.C, npair = w2 ? 2 : 1;
+    const int64_t rows = shape.rows, ny = rows * C;
+    DevBuf dx(nx, x), dw(nw, w), dw2(w2 ? nw : 1, w2), dy(ny), dy2(w2 ? ny : 1), db(C, bias);
+    std::vector<float> ones((size_t)C, 1.0f);
+    DevBuf gamma(C, ones.data()), beta(C), mv(2 * (int64_t)C * npair, moving), tab(4 * (int64_t)C * npair);
+    ensure_zero_page();
+    Ctx c;
+    DevBuf x4(shape.stem ? shape.sg.xrows * shape.sg.Wp * 4 : 1), w4(shape.stem ? (int64_t)shape.sg.KH * shape.sg.K4 * C : 1);
+    if (shape.stem) {
+        HIPCHECK(p3d_stem_pad(dx.p, x4.p, shape.sg.xrows, shape.g.I[2], shape.sg.Wp, shape.g.pad[2], c.s));
+        HIPCHECK(p3d_stem_pack_w(dw.p, w4.p, shape.sg.KH * shape.g.k[2], C, c.s));
+    }
+    ConvBnGroup r = conv_bn_group(xs, ws, s, transpose, dx.p, dw.p, dy.p, bias ? db.p : nullptr, x4.p, w4.p);
+    ConvBnGroup r2;
+    if (w2) r2 = conv_bn_group(xs, ws, s, 0, dx.p, dw2.p, dy2.p, bias ? db.p : nullptr);
+    // the network's rule (stats_target): a tensor the one-launch small-tensor BatchNorm consumes gets no epilogue partials --
+    // the statistics below then come from p3d_bn_stats
+    const bool small = p3d_bn_small_ok((long)rows, C);
+    const int cap = bn_part_cap(rows, C);
+    DevBuf part((int64_t)cap * C * 2 * npair);
+    int np[2] = {0, 0};
+    const P3dIgemmPlan pl = p3d_igemm2_plan(r.v[0], 1);
+    if (kernel) *kernel = r.v.size() == 1 && p3d_igemm2_tail_split(r.v[0], pl) ? "igemm2_group_kernel(tail)" : pl.name;
+    if (!w2) {
+        StatSink sink; sink.part = part.p; sink.cap = cap; sink.nparts = &np[0];
+        run_igemm_group(c, r.v, dy.p, C, rows, C, false, small ? nullptr : &sink, nullptr, nullptr);
+    } else {
+        // conv()'s sibling pair: sibling_prepare, then launch_siblings
+        std::vector<IgemmArgs> v{r.v[0], r2.v[0]};
+        for (int q = 0; q < 2; ++q) {
+            IgemmArgs& a = v[q];
+            a.zeros = g_zero_page; a.accum = 0; a.statpart = nullptr; a.stat_base = 0;
+            StatSink sink; sink.part = part.p + (int64_t)q * cap * C * 2; sink.cap = cap; sink.nparts = &np[q];
+            if (!small) attach_sibling_stats(a, sink);
+        }
+        if (launch_siblings(c, v) && kernel) *kernel = "igemm2_group_kernel(siblings)";
+    }
+    for (int q = 0; q < npair; ++q) {
+        float* pq = part.p + (int64_t)q * cap * C * 2;
+        if (small) {
+            if (p3d_bn_stats_parts((long)rows, C) > cap) throw P3dError("statistics partials overflow their arena slot");
+            HIPCHECK(p3d_bn_stats(q ? dy2.p : dy.p, C, (long)rows, C, pq, c.s));
+            np[q] = p3d_bn_stats_parts((long)rows, C);
+        }
+        BnParams b;
+        float* t = tab.p + (int64_t)q * 4 * C;
+        float* m = mv.p + (int64_t)q * 2 * C;
+        b.gamma = gamma.p; b.beta = beta.p; b.moving_mean = m; b.moving_var = m + C;
+        b.statpart = pq; b.nparts = np[q]; b.scale = t; b.shift = t + C; b.mean = t + 2 * C; b.invstd = t + 3 * C; b.C = C;
+        HIPCHECK(p3d_bn_finalize(b, (long)rows, 1, 1, 1e-3f, c.s));
+        nparts[q] = small ? 0 : np[q];
+    }
+    dy.get(y, ny);
+    if (w2) dy2.get(y2, ny);
+    mv.get(moving, 2 * (int64_t)C * npair);
+    tab.get(stats, 4 * (int64_t)C * npair);
+    API_END
+}
+
+// One normalise / ReLU / add pass of bn_apply (net_ops.inc) on raw inputs, forward and backward.  The launches and their
+// arguments are a literal transcription of bn_apply's forward and backward closures (those read Act / BN objects of a handle,
+// so the argument setup is not shared); the statistics of the non-small paths come from p3d_bn_stats.
+int p3d_debug_bn_pass(int device, int mode, int64_t M, int C, const float* y1, const float* y2, const float* params, int batch1,
+                      int batch2, int update_moving, const float* dz, int acc2, int path, float* z, float* dy1, float* dy2,
+                      float* grads, float* moving, int* info) {
+    API_BEGIN
+    HIPCHECK(hipSetDevice(device));
+    if (mode < 0 || mode > 4) throw P3dError("bn_pass: mode must be 0..4");
+    const bool two = (mode == 2 || mode == 3), has2 = mode != 0;
+    const int nbn = two ? 2 : 1;
+    if (!y1 || !params || !dz || !z || !dy1 || !grads || !moving || !info || (has2 && (!y2 || !dy2))) throw P3dError("null argument");
+    if (M < 1 || C < 4 || C > 1024 || (C & 3) || path < 0 || path > 3) throw P3dError("bn_pass: bad shape or path");
+    const int64_t n = M * C;
+    const bool b1 = batch1 != 0, b2 = two && batch2 != 0;
+    DevBuf dy1b(n, y1), dy2b(has2 ? n : 1, has2 ? y2 : nullptr), dzb(n, dz), zb(n), g1(n), g2(has2 ? n : 1, (has2 && acc2) ? dy2 : nullptr);
+    DevBuf prm(2 * (int64_t)C * nbn, params), mv(2 * (int64_t)C * nbn, moving), tab(4 * (int64_t)C * nbn), grd(2 * (int64_t)C * nbn);
+    const int sparts = p3d_bn_stats_parts((long)M, C), bparts = p3d_bn_bwd_parts((long)M, C);
+    DevBuf spart((int64_t)sparts * 2 * C * nbn), bpart((int64_t)bparts * 2 * C * nbn), coef(2 * (int64_t)C * nbn);
+    BnParams bp[2];
+    for (int q = 0; q < nbn; ++q) {
+        float* t = tab.p + (int64_t)q * 4 * C;
+        bp[q].gamma = prm.p + (int64_t)q * 2 * C; bp[q].beta = bp[q].gamma + C;
+        bp[q].moving_mean = mv.p + (int64_t)q * 2 * C; bp[q].moving_var = bp[q].moving_mean + C;
+        bp[q].statpart = spart.p + (int64_t)q * sparts * 2 * C; bp[q].nparts = sparts;
+        bp[q].scale = t; bp[q].shift = t + C; bp[q].mean = t + 2 * C; bp[q].invstd = t + 3 * C; bp[q].C = C;
+    }
+    if (!two) bp[1] = BnParams{};
+    Ctx c;
+    // the network's rule (bn_is_small, then p3d_bn_fold_apply_ok), or the forced path -- which must be one the kernels take
+    const bool small_ok = p3d_bn_small_ok((long)M, C);
+    const bool fold_ok = p3d_bn_fold_apply_ok((long)M, C, b1 ? sparts : 0, b2 ? sparts : 0, 0.f);
+    const int taken = path ? path : (small_ok ? 1 : (fold_ok ? 2 : 3));
+    if (taken == 1 && !small_ok) throw P3dError("bn_pass: the small-tensor path does not take this shape");
+    if (taken == 2 && !fold_ok) throw P3dError("bn_pass: the fold-apply path does not take this shape");
+    if (taken == 1) {
+        BnSmallArgs a;      // small_args (net_ops.inc)
+        memset(&a, 0, sizeof(a));
+        a.mode = mode; a.M = (int)M; a.C = C;
+        a.y1 = dy1b.p; a.ld1 = C;
+        if (has2) { a.y2 = dy2b.p; a.ld2 = C; }
+        a.bn1 = bp[0];
+        if (two) a.bn2 = bp[1];
+        a.update_moving = update_moving; a.eps = 1e-3f;
+        a.z = zb.p; a.ldz = C;
+        a.dz = dzb.p; a.lddz = C;
+        a.dy1 = g1.p; a.lddy1 = C;
+        if (has2) { a.dy2 = g2.p; a.lddy2 = C; a.acc2 = acc2 ? 1 : 0; }
+        a.dgamma1 = grd.p; a.dbeta1 = grd.p + C;
+        if (two) { a.dgamma2 = grd.p + 2 * C; a.dbeta2 = grd.p + 3 * C; }
+        a.batch1 = b1; a.batch2 = b2;
+        HIPCHECK(p3d_bn_small_fwd(a, c.s));
+        HIPCHECK(p3d_bn_small_bwd(a, c.s));
+    } else {
+        const float* yin[2] = {dy1b.p, dy2b.p};
+        for (int q = 0; q < nbn; ++q)
+            if (q ? b2 : b1) HIPCHECK(p3d_bn_stats(yin[q], C, (long)M, C, spart.p + (int64_t)q * sparts * 2 * C, c.s));
+        BnApplyArgs a;
+        memset(&a, 0, sizeof(a));
+        a.mode = mode; a.M = M; a.C = C;
+        a.y1 = dy1b.p; a.ld1 = C; a.scale1 = bp[0].scale; a.shift1 = bp[0].shift;
+        if (has2) { a.y2 = dy2b.p; a.ld2 = C; }
+        if (two) { a.scale2 = bp[1].scale; a.shift2 = bp[1].shift; }
+        a.z = zb.p; a.ldz = C;
+        if (taken == 2) {
+            HIPCHECK(p3d_bn_fold_apply(a, bp[0], bp[1], b1, b2, update_moving ? 1 : 0, 1e-3f, c.s));
+        } else {
+            HIPCHECK(p3d_bn_finalize(bp[0], (long)M, b1, b1 && update_moving, 1e-3f, c.s));
+            if (two) HIPCHECK(p3d_bn_finalize(bp[1], (long)M, b2, b2 && update_moving, 1e-3f, c.s));
+            HIPCHECK(p3d_bn_apply(a, c.s));
+        }
+        BnBwdArgs g;      // op.bwd (net_ops.inc): reduce, finalize, apply
+        memset(&g, 0, sizeof(g));
+        g.mode = mode; g.M = M; g.C = C;
+        g.dz = dzb.p; g.lddz = C;
+        g.y1 = dy1b.p; g.ld1 = C; g.scale1 = bp[0].scale; g.shift1 = bp[0].shift; g.mean1 = bp[0].mean; g.invstd1 = bp[0].invstd;
+        g.gamma1 = bp[0].gamma; g.dgamma1 = grd.p; g.dbeta1 = grd.p + C; g.batch1 = b1;
+        g.part1 = bpart.p; g.nparts = bparts; g.coef1 = coef.p;
+        g.dy1 = g1.p; g.lddy1 = C; g.acc1 = 0;
+        if (has2) { g.y2 = dy2b.p; g.ld2 = C; g.dy2 = g2.p; g.lddy2 = C; g.acc2 = acc2 ? 1 : 0; }
+        if (two) {
+            g.scale2 = bp[1].scale; g.shift2 = bp[1].shift; g.mean2 = bp[1].mean; g.invstd2 = bp[1].invstd;
+            g.gamma2 = bp[1].gamma; g.dgamma2 = grd.p + 2 * C; g.dbeta2 = grd.p + 3 * C; g.batch2 = b2;
+            g.part2 = bpart.p + (int64_t)bparts * 2 * C; g.coef2 = coef.p + 2 * C;
+        }
+        HIPCHECK(p3d_bn_bwd_reduce(g, c.s));
+        HIPCHECK(p3d_bn_bwd_finalize(g, c.s));
+        HIPCHECK(p3d_bn_bwd_apply(g, c.s));
+    }
+    info[0] = taken; info[1] = taken == 1 ? 0 : sparts; info[2] = taken == 1 ? 0 : bparts;
+    zb.get(z, n);
+    g1.get(dy1, n);
+    if (has2) g2.get(dy2, n);
+    grd.get(grads, 2 * (int64_t)C * nbn);
+    mv.get(moving, 2 * (int64_t)C * nbn);
+    API_END
+}
+
 int p3d_op_conv3d_transpose(int device, const float* x, const int64_t xs[5], const float* kh, const int64_t ks[5],
                             const int s[3], const float* bias, float* y) {
     API_BEGIN

@@ -69,12 +69,7 @@
         auto sibling_prepare = [=](const Ctx& c, IgemmArgs& a) {
             a.zeros = g_zero_page; a.accum = 0; a.statpart = nullptr; a.stat_base = 0;
             BN* sbn = bn ? ((c.fuse && cf.out_bn) ? bn : stats_target(bn, y->rows(), Cout, bn_has_dropout)) : nullptr;
-            if (sbn) {
-                const StatSink sink = bn_sink(sbn);
-                const int mt = p3d_igemm2_mtiles(a, p3d_igemm2_plan(a, 1));
-                if (mt > sink.cap) throw P3dError("statistics partials overflow their arena slot");
-                a.statpart = sink.part; *sink.nparts = mt;
-            }
+            if (sbn) attach_sibling_stats(a, bn_sink(sbn));
         };
         auto fwd_body = [=](const Ctx& c) {
             const bool fz = c.fuse && cf.at != 0;
@@ -111,15 +106,7 @@
                 sib_pending.push_back(a);
                 std::vector<IgemmArgs> v;
                 v.swap(sib_pending);
-                const P3dIgemmPlan pl = p3d_igemm2_plan(v[0], 1);
-                if (p3d_igemm2_groupable(v.data(), (int)v.size(), pl)) {
-                    double fl = 0, by = 0;
-                    for (auto& q : v) { double f1, b1; igemm_work(q, f1, b1); fl += f1; by += b1; }
-                    const std::string kn = std::string("igemm2_group_kernel<") + std::to_string(pl.bm) + "," + std::to_string(pl.bn) + ">(siblings)";
-                    launch(c, kn.c_str(), fl, by, [&]() { return p3d_launch_igemm2_group(v.data(), (int)v.size(), pl, c.s); });
-                } else {
-                    for (auto& q : v) launch_igemm(c, q, 1);
-                }
+                launch_siblings(c, v);
                 return;
             }
             fwd_body(c);

@@ -264,6 +264,7 @@ hipError_t p3d_launch_igemm2_group(const IgemmArgs* v, int n, const P3dIgemmPlan
 void p3d_igemm2_override(int tile, int splits);   // test / tools hook: force the tile (0: 64x64, 1: 128x64, 2: 128x128) and the K-slice count; -1 / 0 = no override
 // dense 1x1x1 convs over >= 16 384 positions with K * N <= 16 384 (conv_pointwise.hip): 0 = not that case, else the block count
 int p3d_pw_stream_blocks(const IgemmArgs& a);
+int p3d_pw_stream_max_blocks(long long M, int N);      // upper bound of p3d_pw_stream_blocks over every launch with an M x N output
 hipError_t p3d_launch_pw_stream(const IgemmArgs& a, hipStream_t s);
 hipError_t p3d_launch_wgrad2(const WgradArgs& a, hipStream_t s);
 hipError_t p3d_launch_wgrad2_group(const WgradArgs* probs, int n, hipStream_t s);   // up to P3D_WGRAD_GROUP problems, one launch

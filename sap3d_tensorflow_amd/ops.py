@@ -76,6 +76,72 @@ def conv3d_transpose(x, kernel, strides, bias=None, device=0):
     return y
 
 
+def conv_bn_stats(x, filter, strides, bias=None, transpose=False, filter2=None, moving=None, device=0):
+    """Test hook: a conv (transpose: tf.layers.conv3d_transpose, kernel [kd,kh,kw,Cout,Cin]) followed by the statistics step of
+    tf.layers.batch_normalization in training, as the network runs it (the conv's statistics epilogue, then the finalize).
+    filter2: a sibling conv on the same input, sent with the first as the network sends a pair.  moving: [pairs, 2, C] moving
+    (mean, variance) before the update (default zeros / ones).  Returns (ys, mean, invstd, moving after, nparts, kernel),
+    ys / mean / invstd / nparts with one entry per conv."""
+    x, w = _f32(x), _f32(filter)
+    s = _strides3(strides)
+    pairs = 2 if filter2 is not None else 1
+    if transpose:
+        C_ = w.shape[3]
+        yshape = (x.shape[0], x.shape[1] * s[0], x.shape[2] * s[1], x.shape[3] * s[2], C_)
+    else:
+        C_ = w.shape[4]
+        yshape = (x.shape[0],) + tuple(_same_out(x.shape[1 + i], s[i]) for i in range(3)) + (C_,)
+    if moving is None:
+        moving = np.stack([np.stack([np.zeros(C_), np.ones(C_)])] * pairs)
+    mv = np.array(moving, dtype=np.float32).reshape(pairs, 2, C_).copy()
+    ys = [np.empty(yshape, np.float32) for _ in range(pairs)]
+    stats = np.empty((pairs, 4, C_), np.float32)
+    nparts = (C.c_int * 2)()
+    kernel = C.c_char_p()
+    w2 = _f32(filter2) if filter2 is not None else None
+    b = _f32(bias) if bias is not None else None
+    check(lib().p3d_debug_conv_bn_stats(device, fptr(x), _shape5(x.shape), fptr(w), fptr(w2), _shape5(w.shape), _i3(s), fptr(b),
+                                        1 if transpose else 0, fptr(mv), fptr(ys[0]), fptr(ys[1]) if pairs == 2 else None,
+                                        fptr(stats), nparts, C.byref(kernel)))
+    return ys, stats[:, 2], stats[:, 3], mv, [nparts[q] for q in range(pairs)], kernel.value.decode()
+
+
+def bn_pass(mode, y1, y2, params, moving, dz, batch=(1, 1), update_moving=1, acc2=None, path=0, device=0):
+    """Test hook: one BatchNorm normalise / ReLU / add pass of the network (mode 0-4, see include/p3d_hip.h) forward and
+    backward on [M, C] arrays.  params [bns, 2, C] = gamma, beta; moving [bns, 2, C] moving (mean, variance) before.
+    acc2: the gradient of y2 to add to (None: overwrite).  path 0 = the network's rule, 1 small, 2 fold-apply, 3 finalize +
+    apply.  Returns (z, dy1, dy2, grads [bns, 2, C], moving after, (path taken, forward partials, backward partials))."""
+    y1 = _f32(y1)
+    M, C_ = y1.shape
+    bns = 2 if mode in (2, 3) else 1
+    y2 = _f32(y2) if mode != 0 else None
+    prm = _f32(np.asarray(params).reshape(bns, 2, C_))
+    mv = np.array(moving, dtype=np.float32).reshape(bns, 2, C_).copy()
+    z, dy1 = np.empty((M, C_), np.float32), np.empty((M, C_), np.float32)
+    dy2 = (_f32(acc2).copy() if acc2 is not None else np.empty((M, C_), np.float32)) if mode != 0 else None
+    grads = np.empty((bns, 2, C_), np.float32)
+    info = (C.c_int * 3)()
+    check(lib().p3d_debug_bn_pass(device, mode, M, C_, fptr(y1), fptr(y2), fptr(prm), int(batch[0]), int(batch[1]),
+                                  int(update_moving), fptr(_f32(dz)), 1 if acc2 is not None else 0, path, fptr(z), fptr(dy1),
+                                  fptr(dy2), fptr(grads), fptr(mv), info))
+    return z, dy1, dy2, grads, mv, tuple(info)
+
+
+def stat_parts(xshape, fshape, strides, transpose=False):
+    """Host-only test hook: (partials the conv's statistics epilogue writes, room the network reserves for them)."""
+    w, c = C.c_int(), C.c_int()
+    check(lib().p3d_debug_stat_parts(_shape5(xshape), _shape5(fshape), _i3(_strides3(strides)), 1 if transpose else 0,
+                                     C.byref(w), C.byref(c)))
+    return w.value, c.value
+
+
+def igemm_groupable(xshape, fshape, strides):
+    """Host-only test hook: would two sibling convs of this shape on one input go out as one grouped launch?"""
+    r = lib().p3d_debug_igemm_groupable(_shape5(xshape), _shape5(fshape), _i3(_strides3(strides)))
+    check(-1 if r < 0 else 0)
+    return bool(r)
+
+
 def bias_add_grad(dy, device=0):
     """BiasAddGrad (gradient of the bias of tf.layers.conv3d / conv3d_transpose): sum of dy over every axis but the last."""
     g = _f32(dy)
