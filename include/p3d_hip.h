@@ -261,6 +261,25 @@ int p3d_debug_conv_bn_stats(int device, const float* x, const int64_t xshape[5],
 int p3d_debug_bn_pass(int device, int mode, int64_t M, int C, const float* y1, const float* y2, const float* params, int batch1,
                       int batch2, int update_moving, const float* dz, int acc2, int path, float* z, float* dy1, float* dy2,
                       float* grads, float* moving, int* info);
+/* Test hook: one GroupNorm normalise / ReLU / add pass of the GN network (modes of gn.hip: 0 relu(gn1(y1)), 1 relu(gn1(y1) + r),
+ * 2 relu(gn1(y1) + gn2(y2)) (forward only), 3 relu(gn1(y1)) + relu(gn2(y2)), 4 r + relu(gn1(y1)), 5 gn1(y1),
+ * 6 relu(gn1(y1) + r * cs[n,c] * ss[row])) on N samples of R rows of C channels, G groups, forward then backward, launched as
+ * the network launches it.  y1 [N*R][ld1]; y2 [N*R][ld2] = the second GN input or the residual r (null for modes 0, 5);
+ * z and dz [N*R][ldz]; params [gns][2][C] = gamma, beta; cs [N][C] and ss [N*R] for mode 6.  In/out: z, dy1 [N*R][ld1] and
+ * dy2 [N*R][ld2] keep what they held outside the C columns of a row; dy2 (modes 1, 3, 4, 6) holds the gradient to add to when
+ * acc2; grads [gns][2][C] = dgamma, dbeta are stored.  drop_rate > 0: dropout on z with the kernels' hash of seed.
+ * tables [gns][4][N][C] = scale, shift, mean, invstd.  path: 0 = the network's rule, 1 = the one-launch small-tensor kernels,
+ * 2 = statistics / finalize / apply; a forced path the kernels cannot take is an error.  *info = path taken. */
+int p3d_debug_gn_pass(int device, int mode, int N, int R, int C, int G, float eps, const float* y1, int ld1, const float* y2, int ld2,
+                      int ldz, const float* params, const float* cs, const float* ss, const float* dz, int acc2, float drop_rate,
+                      uint64_t seed, int path, float* z, float* dy1, float* dy2, float* grads, float* tables, int* info);
+/* Test hook: CBAM forward and backward (the network's cbam(): p3d_cbam_forward / p3d_cbam_backward on a site's scratch layout).
+ * x [N*D*H*W][ld]; k0 [C][C/8], b0 [C/8], k1 [C/8][C], b1 [C], k7 [7][7][7][2][1]; chunks = row chunks per sample (0: the
+ * network's rule); dout [N*D*H*W][C] = gradient of the CBAM output.  Out: cs [N][C], sp [N*D*H*W][2], ss [N*D*H*W].  In/out:
+ * dx [N*D*H*W][ld] (overwritten, or added to when accx), pgrads = dk0 | db0 | dk1 | db1 | dk7 (added to).  *info = chunks used. */
+int p3d_debug_cbam(int device, int N, int D, int H, int W, int C, const float* x, int ld, const float* k0, const float* b0,
+                   const float* k1, const float* b1, const float* k7, int chunks, const float* dout, int accx, float* cs, float* sp,
+                   float* ss, float* dx, float* pgrads, int* info);
 int p3d_debug_stat_parts(const int64_t xshape[5], const int64_t wshape[5], const int s[3], int transpose, int* written, int* cap);
 int p3d_debug_igemm_groupable(const int64_t xshape[5], const int64_t wshape[5], const int s[3]);
 int p3d_op_max_pool3d(int device, const float* x, const int64_t xshape[5], const int ksize[3], const int s[3], float* y);

@@ -97,14 +97,25 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float* y, int ld, i
     }
 }
 
-// ---- finalize: thread per (n, c); the C/G (a power of two <= 32) lanes of a group fold with shuffles
+// A group's C/G lanes (consecutive i = n * C + c) fold their per-channel values.  A power-of-two group of at most 64 lanes lies
+// inside one wave and folds with xor shuffles (a pairwise tree); any other group size is summed by every lane from memory,
+// in channel order -- shuffles would mix in lanes of the neighbouring group.  (The condition is uniform over the grid.)
+__device__ __forceinline__ bool gn_fold_by_shuffle(int cg) { return cg <= 64 && (cg & (cg - 1)) == 0; }
+
+// ---- finalize: thread per (n, c)
 __global__ void gn_finalize_kernel(GnParams p, int N, int R, float eps) {
     P3D_CHAIN_PRIO();
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int cg = p.C / p.G;
     const bool ok = i < N * p.C;
-    double s1 = ok ? p.sums[(long long)i * 2] : 0.0, s2 = ok ? p.sums[(long long)i * 2 + 1] : 0.0;
-    for (int o = 1; o < cg; o <<= 1) { s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); }
+    double s1 = 0.0, s2 = 0.0;
+    if (gn_fold_by_shuffle(cg)) {
+        s1 = ok ? p.sums[(long long)i * 2] : 0.0; s2 = ok ? p.sums[(long long)i * 2 + 1] : 0.0;
+        for (int o = 1; o < cg; o <<= 1) { s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); }
+    } else if (ok) {
+        const long long g0 = (long long)(i - i % cg) * 2;
+        for (int k = 0; k < cg; ++k) { s1 += p.sums[g0 + 2 * k]; s2 += p.sums[g0 + 2 * k + 1]; }
+    }
     if (!ok) return;
     const int c = i % p.C;
     const double cnt = (double)R * cg;
@@ -259,8 +270,17 @@ __global__ void gn_bwd_finalize_kernel(GnParams p, int N, int R) {
     const bool ok = i < N * p.C;
     const int c = ok ? i % p.C : 0;
     const double gm = ok ? (double)p.gamma[c] : 0.0;
-    double A = ok ? gm * p.sums[(long long)i * 2] : 0.0, B = ok ? gm * p.sums[(long long)i * 2 + 1] : 0.0;
-    for (int o = 1; o < cg; o <<= 1) { A += __shfl_xor(A, o); B += __shfl_xor(B, o); }
+    double A = 0.0, B = 0.0;
+    if (gn_fold_by_shuffle(cg)) {
+        A = ok ? gm * p.sums[(long long)i * 2] : 0.0; B = ok ? gm * p.sums[(long long)i * 2 + 1] : 0.0;
+        for (int o = 1; o < cg; o <<= 1) { A += __shfl_xor(A, o); B += __shfl_xor(B, o); }
+    } else if (ok) {
+        const int i0 = i - i % cg, c0 = c - c % cg;
+        for (int k = 0; k < cg; ++k) {
+            const double gk = (double)p.gamma[c0 + k];
+            A += gk * p.sums[(long long)(i0 + k) * 2]; B += gk * p.sums[(long long)(i0 + k) * 2 + 1];
+        }
+    }
     if (!ok) return;
     const double cnt = (double)R * cg;
     const double inv = p.invstd[i];
@@ -487,11 +507,12 @@ __global__ __launch_bounds__(256) void gn_small_bwd_kernel(GnApplyArgs a) {
 #pragma unroll
             for (int k = 0; k < (TWO ? 4 : 2); ++k) acc[k] = add4(acc[k], pp[k]);
         }
-        st4(a.dbeta1 + c, add4(ld4(a.dbeta1 + c), acc[0]));
-        st4(a.dgamma1 + c, add4(ld4(a.dgamma1 + c), acc[1]));
+        // stored, as gn_bwd_params_kernel and BatchNorm's kernels store them
+        st4(a.dbeta1 + c, acc[0]);
+        st4(a.dgamma1 + c, acc[1]);
         if (TWO) {
-            st4(a.dbeta2 + c, add4(ld4(a.dbeta2 + c), acc[2]));
-            st4(a.dgamma2 + c, add4(ld4(a.dgamma2 + c), acc[3]));
+            st4(a.dbeta2 + c, acc[2]);
+            st4(a.dgamma2 + c, acc[3]);
         }
     }
 }
@@ -522,6 +543,7 @@ hipError_t p3d_gn_stats(const float* y, int ld, int N, int R, int C, double* sum
     return hipGetLastError();
 }
 hipError_t p3d_gn_finalize(const GnParams& p, int N, int R, float eps, hipStream_t s) {
+    if (p.G < 1 || p.C % p.G) return hipErrorInvalidValue;
     hipLaunchKernelGGL(gn_finalize_kernel, dim3((N * p.C + 255) / 256), dim3(256), 0, s, p, N, R, eps);
     return hipGetLastError();
 }
@@ -557,6 +579,7 @@ hipError_t p3d_gn_bwd_reduce(const GnApplyArgs& a0, hipStream_t s) {
     return hipGetLastError();
 }
 hipError_t p3d_gn_bwd_finalize(const GnParams& p, int N, int R, float* dgamma, float* dbeta, hipStream_t s) {
+    if (p.G < 1 || p.C % p.G) return hipErrorInvalidValue;
     hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3((N * p.C + 255) / 256), dim3(256), 0, s, p, N, R);
     hipLaunchKernelGGL(gn_bwd_params_kernel, dim3((p.C + 255) / 256), dim3(256), 0, s, p, N, dgamma, dbeta);
     return hipGetLastError();

@@ -393,6 +393,85 @@ bool launch_siblings(const Ctx& c, std::vector<IgemmArgs>& v) {
     return false;
 }
 
+// One GroupNorm pass (gn_apply in net_gn.inc, and the test hook p3d_debug_gn_pass): which kernels take it, and their launches.
+// A (sample, group) slab that fits one block goes to the one-launch small-tensor kernels unless the pass drops out; everything
+// else runs statistics -> finalize -> apply forward and reduce -> finalize (+ parameter gradients) -> apply backward.
+bool gn_small_rule(int R, int C, int G, bool dropout) {
+    static const bool no_small = p3d_tune_env("P3D_NO_GN_SMALL") != nullptr;
+    return !no_small && !dropout && p3d_gn_small_ok(R, C, G);
+}
+void gn_pass_forward(const Ctx& c, const GnApplyArgs& a, bool small) {
+    const double tens = (double)a.M * a.C * 4.0;
+    const int R = a.R, C = a.C, N = (int)(a.M / a.R), io = a.y2 ? 3 : 2;
+    if (small) {
+        const std::string ksf = "gn_small_fwd_kernel<" + std::to_string(a.mode) + ">";
+        launch(c, ksf.c_str(), 0, tens * io, [&]() { return p3d_gn_small_fwd(a, c.s); });
+        return;
+    }
+    const std::string ka = "gn_apply_kernel<" + std::to_string(a.mode) + ">";
+    launch(c, "gn_stats_kernel", 0, tens, [&]() { return p3d_gn_stats(a.y1, a.ld1, N, R, C, a.g1.sums, c.s); });
+    launch(c, "gn_finalize_kernel", 0, 32.0 * N * C, [&]() { return p3d_gn_finalize(a.g1, N, R, a.eps, c.s); });
+    if (a.mode == 2 || a.mode == 3) {
+        launch(c, "gn_stats_kernel", 0, tens, [&]() { return p3d_gn_stats(a.y2, a.ld2, N, R, C, a.g2.sums, c.s); });
+        launch(c, "gn_finalize_kernel", 0, 32.0 * N * C, [&]() { return p3d_gn_finalize(a.g2, N, R, a.eps, c.s); });
+    }
+    launch(c, ka.c_str(), 0, tens * io, [&]() { return p3d_gn_apply(a, c.s); });
+}
+void gn_pass_backward(const Ctx& c, const GnApplyArgs& a, bool small) {
+    const double tens = (double)a.M * a.C * 4.0;
+    const int R = a.R, C = a.C, N = (int)(a.M / a.R);
+    if (small) {
+        const std::string ksb = "gn_small_bwd_kernel<" + std::to_string(a.mode) + ">";
+        launch(c, ksb.c_str(), 0, tens * (a.y2 ? 5 : 3), [&]() { return p3d_gn_small_bwd(a, c.s); });
+        return;
+    }
+    const std::string kr = "gn_bwd_reduce_kernel<" + std::to_string(a.mode) + ">";
+    const std::string kb = "gn_bwd_apply_kernel<" + std::to_string(a.mode) + ">";
+    launch(c, kr.c_str(), 0, tens * (a.y2 ? 3 : 2), [&]() { return p3d_gn_bwd_reduce(a, c.s); });
+    launch(c, "gn_bwd_finalize_kernel", 0, 64.0 * N * C, [&]() { return p3d_gn_bwd_finalize(a.g1, N, R, a.dgamma1, a.dbeta1, c.s); });
+    if (a.mode == 3)
+        launch(c, "gn_bwd_finalize_kernel", 0, 64.0 * N * C, [&]() { return p3d_gn_bwd_finalize(a.g2, N, R, a.dgamma2, a.dbeta2, c.s); });
+    launch(c, kb.c_str(), 0, tens * (a.y2 ? 5 : 3), [&]() { return p3d_gn_bwd_apply(a, c.s); });
+}
+
+// CBAM (cbam() in net_gn.inc, and the test hook p3d_debug_cbam): row chunks per sample of the pooling and backward passes, and the
+// layout of a site's scratch, in floats from its base: part [N][chunks][C][3]; avg, mx, ties, cs, davg, dmx [N][C] each;
+// havg, hmx, dh [N][C/8], [N][C/8], [N][2][C/8] (+ 8); sp [M][2]; ss [M]; dpre [M]; dsp [M][2]; dcs_part [N][chunks][C]; dO [N][C].
+int cbam_chunks(int R) {
+    int chunks = R / 16;
+    if (chunks < 1) chunks = 1;
+    if (chunks > 64) chunks = 64;
+    return chunks;
+}
+struct CbamLayout { int64_t vec, cs, h, sp, ss, dpre, dsp, dcs, dO, total; };
+CbamLayout cbam_layout(int64_t N, int64_t M, int64_t C, int64_t chunks) {
+    CbamLayout L;
+    const int64_t nc = N * C;
+    L.vec = nc * chunks * 3;
+    L.cs = L.vec + 3 * nc;
+    L.h = L.vec + 6 * nc;
+    L.sp = L.h + 4 * N * (C / 8) + 8;
+    L.ss = L.sp + 2 * M;
+    L.dpre = L.ss + M;
+    L.dsp = L.dpre + M;
+    L.dcs = L.dsp + 2 * M;
+    L.dO = L.dcs + nc * chunks;
+    L.total = ((L.dO + nc + 63) / 64) * 64;
+    return L;
+}
+// the scratch pointers of CbamArgs for a site whose scratch starts at b (a.N, a.C, a.Ch and a.chunks already set)
+void cbam_scratch_args(CbamArgs& a, float* b, int64_t M) {
+    const CbamLayout L = cbam_layout(a.N, M, a.C, a.chunks);
+    const int64_t nc = (int64_t)a.N * a.C;
+    a.part = b;
+    float* v = b + L.vec;
+    a.avg = v; a.mx = v + nc; a.ties = v + 2 * nc; a.cs = v + 3 * nc; a.davg = v + 4 * nc; a.dmx = v + 5 * nc;
+    a.havg = b + L.h; a.hmx = a.havg + (int64_t)a.N * a.Ch; a.dh = a.hmx + (int64_t)a.N * a.Ch;
+    a.sp = b + L.sp; a.ss = b + L.ss; a.dpre = b + L.dpre; a.dsp = b + L.dsp;
+    a.dcs_part = b + L.dcs;
+    a.dO = b + L.dO;
+}
+
 // Runs `f(side_ctx)` on the side stream after everything queued so far on the main stream.
 template <typename F>
 void on_side_stream(const Ctx& c, hipEvent_t ev, F&& f) {

@@ -1032,6 +1032,123 @@ int p3d_debug_bn_pass(int device, int mode, int64_t M, int C, const float* y1, c
     API_END
 }
 
+// One GroupNorm pass of gn_apply (net_gn.inc) on raw inputs, forward and then backward, through the launch sequences the network
+// itself calls (gn_pass_forward / gn_pass_backward, net.hip).
+int p3d_debug_gn_pass(int device, int mode, int N, int R, int C, int G, float eps, const float* y1, int ld1, const float* y2, int ld2,
+                      int ldz, const float* params, const float* cs, const float* ss, const float* dz, int acc2, float drop_rate,
+                      uint64_t seed, int path, float* z, float* dy1, float* dy2, float* grads, float* tables, int* info) {
+    API_BEGIN
+    HIPCHECK(hipSetDevice(device));
+    if (mode < 0 || mode > 6) throw P3dError("gn_pass: mode must be 0..6");
+    const bool two = (mode == 2 || mode == 3), has2 = mode != 0 && mode != 5, bwd = mode != 2;
+    const bool d2 = mode == 1 || mode == 3 || mode == 4 || mode == 6;      // a second input gradient
+    const int ngn = two ? 2 : 1;
+    if (!y1 || !params || !z || !dy1 || !grads || !tables || !info || (has2 && !y2) || (bwd && !dz) || (bwd && d2 && !dy2) ||
+        (mode == 6 && (!cs || !ss)))
+        throw P3dError("null argument");
+    if (N < 1 || R < 1 || C < 4 || C > 1024 || (C & 3) || G < 1 || C % G || path < 0 || path > 2)
+        throw P3dError("gn_pass: bad shape or path");
+    if (ld1 < C || (ld1 & 3) || ldz < C || (ldz & 3) || (has2 && (ld2 < C || (ld2 & 3))))
+        throw P3dError("gn_pass: row strides must be multiples of 4, at least C");
+    if (!(drop_rate >= 0.f && drop_rate < 1.f)) throw P3dError("gn_pass: dropout rate must be in [0, 1)");
+    const int64_t M = (int64_t)N * R, nc = (int64_t)N * C;
+    const bool dropout = drop_rate > 0.f;
+    // the network's rule (gn_small_rule; mode 2, the per-sample BatchNorm of p3d_predict_windows, never takes the small
+    // kernels), or the forced path -- which must be one the kernels take
+    const bool small_ok = mode != 2 && !dropout && p3d_gn_small_ok(R, C, G);
+    const int taken = path ? path : ((mode != 2 && gn_small_rule(R, C, G, dropout)) ? 1 : 2);
+    if (taken == 1 && !small_ok) throw P3dError("gn_pass: the small-tensor path does not take this shape");
+    DevBuf y1b(M * ld1, y1), y2b(has2 ? M * ld2 : 1, has2 ? y2 : nullptr), zb(M * ldz, z), dzb(bwd ? M * ldz : 1, bwd ? dz : nullptr);
+    DevBuf g1b(M * ld1, dy1), g2b(bwd && d2 ? M * ld2 : 1, bwd && d2 ? dy2 : nullptr);
+    DevBuf prm(2 * (int64_t)C * ngn, params), grd(2 * (int64_t)C * ngn, grads), tab(7 * nc * ngn);
+    DevBuf csb(mode == 6 ? nc : 1, mode == 6 ? cs : nullptr), ssb(mode == 6 ? M : 1, mode == 6 ? ss : nullptr);
+    DevBuf fsums(4 * nc * ngn), bsums(4 * nc * ngn);           // [gn][N][C][2] doubles each: forward, backward (as the arenas)
+    auto params_of = [&](int q, bool backward) {
+        GnParams p;
+        memset(&p, 0, sizeof(p));
+        p.gamma = prm.p + (int64_t)q * 2 * C; p.beta = p.gamma + C;
+        p.sums = reinterpret_cast<double*>(backward ? bsums.p : fsums.p) + (int64_t)q * 2 * nc;
+        float* t = tab.p + (int64_t)q * 7 * nc;
+        p.scale = t; p.shift = t + nc; p.mean = t + 2 * nc; p.invstd = t + 3 * nc; p.coef = t + 4 * nc;
+        p.C = C; p.G = G;
+        return p;
+    };
+    GnApplyArgs a;      // as gn_apply's mk (net_gn.inc) builds it
+    memset(&a, 0, sizeof(a));
+    a.mode = mode; a.M = M; a.R = R; a.C = C;
+    a.y1 = y1b.p; a.ld1 = ld1; a.g1 = params_of(0, false);
+    if (has2) { a.y2 = y2b.p; a.ld2 = ld2; }
+    if (two) a.g2 = params_of(1, false);
+    if (mode == 6) { a.cs = csb.p; a.ss = ssb.p; }
+    a.z = zb.p; a.ldz = ldz; a.dz = dzb.p;
+    a.dy1 = g1b.p; a.lddy1 = ld1;
+    if (d2) { a.dy2 = g2b.p; a.lddy2 = ld2; a.acc2 = acc2 ? 1 : 0; }
+    if (dropout) { a.drop_rate = drop_rate; a.drop_scale = 1.f / (1.f - drop_rate); a.seed = seed; }
+    a.eps = eps;
+    a.dgamma1 = grd.p; a.dbeta1 = grd.p + C;
+    if (two) { a.dgamma2 = grd.p + 2 * C; a.dbeta2 = grd.p + 3 * C; }
+    Ctx c;
+    gn_pass_forward(c, a, taken == 1);
+    if (bwd) {
+        GnApplyArgs b = a;
+        b.g1 = params_of(0, true);
+        if (two) b.g2 = params_of(1, true);
+        gn_pass_backward(c, b, taken == 1);
+    }
+    info[0] = taken;
+    zb.get(z, M * ldz);
+    if (bwd) {
+        g1b.get(dy1, M * ld1);
+        if (d2) g2b.get(dy2, M * ld2);
+        grd.get(grads, 2 * (int64_t)C * ngn);
+    }
+    std::vector<float> t((size_t)(7 * nc * ngn));
+    tab.get(t.data(), 7 * nc * ngn);
+    for (int q = 0; q < ngn; ++q) std::copy(t.begin() + q * 7 * nc, t.begin() + q * 7 * nc + 4 * nc, tables + q * 4 * nc);
+    API_END
+}
+
+// CBAM forward and backward (cbam() in net_gn.inc) on raw inputs: p3d_cbam_forward / p3d_cbam_backward on a scratch laid out by
+// cbam_scratch_args, with the network's chunk rule unless chunks > 0.
+int p3d_debug_cbam(int device, int N, int D, int H, int W, int C, const float* x, int ld, const float* k0, const float* b0,
+                   const float* k1, const float* b1, const float* k7, int chunks, const float* dout, int accx, float* cs, float* sp,
+                   float* ss, float* dx, float* pgrads, int* info) {
+    API_BEGIN
+    HIPCHECK(hipSetDevice(device));
+    if (!x || !k0 || !b0 || !k1 || !b1 || !k7 || !dout || !cs || !sp || !ss || !dx || !pgrads || !info) throw P3dError("null argument");
+    if (N < 1 || D < 1 || H < 1 || W < 1 || C < 8 || C > 1024 || (C & 3) || chunks < 0 || chunks > 65535)
+        throw P3dError("cbam: bad shape or chunk count");
+    if (ld < C || (ld & 3)) throw P3dError("cbam: the row stride must be a multiple of 4, at least C");
+    const int R = D * H * W, Ch = C / 8;
+    const int64_t M = (int64_t)N * R, nc = (int64_t)N * C;
+    const int64_t ng = (int64_t)C * Ch * 2 + Ch + C + 686;      // dk0, db0, dk1, db1, dk7
+    CbamArgs a;
+    memset(&a, 0, sizeof(a));
+    a.N = N; a.D = D; a.H = H; a.W = W; a.C = C; a.Ch = Ch;
+    a.chunks = chunks ? chunks : cbam_chunks(R);
+    const CbamLayout L = cbam_layout(N, M, C, a.chunks);
+    DevBuf xb(M * ld, x), k0b((int64_t)C * Ch, k0), b0b(Ch, b0), k1b((int64_t)Ch * C, k1), b1b(C, b1), k7b(686, k7);
+    DevBuf doutb(M * C, dout), dxb(M * ld, dx), grd(ng, pgrads), scratch(L.total);
+    a.x = xb.p; a.ld = ld;
+    a.k0 = k0b.p; a.b0 = b0b.p; a.k1 = k1b.p; a.b1 = b1b.p; a.k7 = k7b.p;
+    cbam_scratch_args(a, scratch.p, M);
+    a.dout = doutb.p;
+    a.dx = dxb.p; a.lddx = ld; a.accx = accx ? 1 : 0;
+    a.dk0 = grd.p; a.db0 = a.dk0 + (int64_t)C * Ch; a.dk1 = a.db0 + Ch; a.db1 = a.dk1 + (int64_t)Ch * C; a.dk7 = a.db1 + C;
+    Ctx c;
+    HIPCHECK(p3d_cbam_forward(a, c.s));
+    HIPCHECK(p3d_cbam_backward(a, c.s));
+    std::vector<float> h((size_t)L.total);
+    scratch.get(h.data(), L.total);
+    std::copy(h.begin() + L.cs, h.begin() + L.cs + nc, cs);
+    std::copy(h.begin() + L.sp, h.begin() + L.sp + 2 * M, sp);
+    std::copy(h.begin() + L.ss, h.begin() + L.ss + M, ss);
+    dxb.get(dx, M * ld);
+    grd.get(pgrads, ng);
+    info[0] = a.chunks;
+    API_END
+}
+
 int p3d_op_conv3d_transpose(int device, const float* x, const int64_t xs[5], const float* kh, const int64_t ks[5],
                             const int s[3], const float* bias, float* y) {
     API_BEGIN

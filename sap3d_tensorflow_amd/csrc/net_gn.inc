@@ -5,6 +5,7 @@
         GN* g = &gns.back();
         g->name = unique("group_norm");
         g->C = C; g->G = C < 32 ? C : 32; g->N = cfg.batch;
+        if (C % g->G) throw P3dError("GroupNorm needs C (" + std::to_string(C) + ") to be a multiple of its 32 groups");
         g->gamma = add_param(g->name + "/gamma", {C}, true, INIT_ONES);
         g->beta = add_param(g->name + "/beta", {C}, true, INIT_ZEROS);
         const int64_t nc = (int64_t)cfg.batch * C;
@@ -35,9 +36,6 @@
         const int64_t M = y1->rows();
         const int R = y1->D * y1->H * y1->W, C = y1->C, N = y1->N;
         const double tens = (double)M * C * 4.0;
-        const std::string ka = "gn_apply_kernel<" + std::to_string(mode) + ">";
-        const std::string kr = "gn_bwd_reduce_kernel<" + std::to_string(mode) + ">";
-        const std::string kb = "gn_bwd_apply_kernel<" + std::to_string(mode) + ">";
         Op op;
         op.name = opname; op.kind = "gn_apply" + std::to_string(mode);
         op.bytes = tens * (y2 ? 4 : 3); op.bbytes = tens * (y2 ? 7 : 5);
@@ -62,10 +60,7 @@
             return a;
         };
         // small tensors (every GroupNorm of stage 3): one launch each way, see gn.hip
-        static const bool no_small = p3d_tune_env("P3D_NO_GN_SMALL") != nullptr;
-        const bool small = !no_small && !dropout && p3d_gn_small_ok(R, C, g1->G) && (!g2 || g2->G == g1->G);
-        const std::string ksf = "gn_small_fwd_kernel<" + std::to_string(mode) + ">";
-        const std::string ksb = "gn_small_bwd_kernel<" + std::to_string(mode) + ">";
+        const bool small = gn_small_rule(R, C, g1->G, dropout) && (!g2 || g2->G == g1->G);
         if (mode != 5) {
             // decisions of the last forward (p3d_debug_decision_*): the backward apply kernel on dz = 1 with a coefficient table
             // (k, c1, c2) = (1, 0, 0) -- what it writes is the gate itself.  scratch: 2 x [N][C][3] floats + the kernel's own needs
@@ -85,65 +80,26 @@
                 HIPCHECK(p3d_gn_bwd_apply(a, st));
             };
         }
-        op.fwd = [=](const Ctx& c) {
-            const GnApplyArgs a = mk(c, false);
-            if (small) {
-                launch(c, ksf.c_str(), 0, tens * (y2 ? 3 : 2), [&]() { return p3d_gn_small_fwd(a, c.s); });
-                return;
-            }
-            launch(c, "gn_stats_kernel", 0, tens, [&]() { return p3d_gn_stats(y1->p, y1->ld, N, R, C, a.g1.sums, c.s); });
-            launch(c, "gn_finalize_kernel", 0, 32.0 * N * C, [&]() { return p3d_gn_finalize(a.g1, N, R, 1e-5f, c.s); });
-            if (mode == 3) {
-                launch(c, "gn_stats_kernel", 0, tens, [&]() { return p3d_gn_stats(y2->p, y2->ld, N, R, C, a.g2.sums, c.s); });
-                launch(c, "gn_finalize_kernel", 0, 32.0 * N * C, [&]() { return p3d_gn_finalize(a.g2, N, R, 1e-5f, c.s); });
-            }
-            launch(c, ka.c_str(), 0, tens * (y2 ? 3 : 2), [&]() { return p3d_gn_apply(a, c.s); });
-        };
-        op.bwd = [=](const Ctx& c) {
-            const GnApplyArgs a = mk(c, true);
-            if (small) {
-                launch(c, ksb.c_str(), 0, tens * (y2 ? 5 : 3), [&]() { return p3d_gn_small_bwd(a, c.s); });
-                return;
-            }
-            launch(c, kr.c_str(), 0, tens * (y2 ? 3 : 2), [&]() { return p3d_gn_bwd_reduce(a, c.s); });
-            launch(c, "gn_bwd_finalize_kernel", 0, 64.0 * N * C, [&]() { return p3d_gn_bwd_finalize(a.g1, N, R, g1->gamma->g, g1->beta->g, c.s); });
-            if (mode == 3)
-                launch(c, "gn_bwd_finalize_kernel", 0, 64.0 * N * C, [&]() { return p3d_gn_bwd_finalize(a.g2, N, R, g2->gamma->g, g2->beta->g, c.s); });
-            launch(c, kb.c_str(), 0, tens * (y2 ? 5 : 3), [&]() { return p3d_gn_bwd_apply(a, c.s); });
-        };
+        op.fwd = [=](const Ctx& c) { gn_pass_forward(c, mk(c, false), small); };
+        op.bwd = [=](const Ctx& c) { gn_pass_backward(c, mk(c, true), small); };
         ops.push_back(op);
         return out;
     }
 
-    // scratch layout of one CBAM site inside bnbuf (floats)
-    static int64_t cbam_part_off(CbamSite*) { return 0; }
-    int64_t cbam_vec_off(CbamSite* cb) { return (int64_t)cb->x->N * cb->chunks * cb->x->C * 3; }                // avg, mx, ties, cs, davg, dmx: [N][C] each
-    int64_t cbam_cs_off(CbamSite* cb) { return cbam_vec_off(cb) + 3 * (int64_t)cb->x->N * cb->x->C; }
-    int64_t cbam_h_off(CbamSite* cb) { return cbam_vec_off(cb) + 6 * (int64_t)cb->x->N * cb->x->C; }            // havg, hmx [N][C/8]
-    int64_t cbam_sp_off(CbamSite* cb) { return cbam_h_off(cb) + 4 * (int64_t)cb->x->N * (cb->x->C / 8) + 8; }   // (+ dh [N][2][C/8]) then sp [M][2]
-    int64_t cbam_ss_off(CbamSite* cb) { return cbam_sp_off(cb) + 2 * cb->x->rows(); }                          // ss [M]
-    int64_t cbam_dpre_off(CbamSite* cb) { return cbam_ss_off(cb) + cb->x->rows(); }                             // dpre [M]
-    int64_t cbam_dsp_off(CbamSite* cb) { return cbam_dpre_off(cb) + cb->x->rows(); }                            // dsp [M][2]
-    int64_t cbam_dcs_off(CbamSite* cb) { return cbam_dsp_off(cb) + 2 * cb->x->rows(); }                         // dcs_part [N][chunks][C]
-    int64_t cbam_dO_off(CbamSite* cb) { return cbam_dcs_off(cb) + (int64_t)cb->x->N * cb->chunks * cb->x->C; }   // dO [N][C]
-    int64_t cbam_total(CbamSite* cb) { return ((cbam_dO_off(cb) + (int64_t)cb->x->N * cb->x->C + 63) / 64) * 64; }
+    // scratch layout of one CBAM site inside bnbuf: cbam_layout (net.hip)
+    CbamLayout cbam_site_layout(CbamSite* cb) { return cbam_layout(cb->x->N, cb->x->rows(), cb->x->C, cb->chunks); }
+    int64_t cbam_cs_off(CbamSite* cb) { return cbam_site_layout(cb).cs; }
+    int64_t cbam_ss_off(CbamSite* cb) { return cbam_site_layout(cb).ss; }
+    int64_t cbam_total(CbamSite* cb) { return cbam_site_layout(cb).total; }
 
     CbamArgs cbam_args(CbamSite* cb) {
         CbamArgs a;
         memset(&a, 0, sizeof(a));
         Act* x = cb->x;
-        const int64_t nc = (int64_t)x->N * x->C;
-        float* b = bnbuf + cb->buf_off;
         a.x = x->p; a.ld = x->ld; a.N = x->N; a.D = x->D; a.H = x->H; a.W = x->W; a.C = x->C; a.Ch = x->C / 8;
         a.k0 = cb->k0->p; a.b0 = cb->b0->p; a.k1 = cb->k1->p; a.b1 = cb->b1->p; a.k7 = cb->k7->p;
         a.chunks = cb->chunks;
-        a.part = b + cbam_part_off(cb);
-        float* v = b + cbam_vec_off(cb);
-        a.avg = v; a.mx = v + nc; a.ties = v + 2 * nc; a.cs = v + 3 * nc; a.davg = v + 4 * nc; a.dmx = v + 5 * nc;
-        a.havg = b + cbam_h_off(cb); a.hmx = a.havg + (int64_t)x->N * a.Ch; a.dh = a.hmx + (int64_t)x->N * a.Ch;
-        a.sp = b + cbam_sp_off(cb); a.ss = b + cbam_ss_off(cb); a.dpre = b + cbam_dpre_off(cb); a.dsp = b + cbam_dsp_off(cb);
-        a.dcs_part = b + cbam_dcs_off(cb);
-        a.dO = b + cbam_dO_off(cb);
+        cbam_scratch_args(a, bnbuf + cb->buf_off, x->rows());
         a.dout = cb->dout;
         a.dx = x->g; a.lddx = x->ld; a.accx = cb->xflag ? *cb->xflag : 0;
         a.dk0 = cb->k0->g; a.db0 = cb->b0->g; a.dk1 = cb->k1->g; a.db1 = cb->b1->g; a.dk7 = cb->k7->g;
@@ -163,11 +119,7 @@
         cb->b1 = add_param(nm + "/ch_at/mlp_1/bias", {C}, true, INIT_ZEROS);
         cb->k7 = add_param(nm + "/sp_at/conv3d/kernel", {7, 7, 7, 2, 1}, true, INIT_VS);
         cb->x = x;
-        const int R = x->D * x->H * x->W;
-        int chunks = R / 16;
-        if (chunks < 1) chunks = 1;
-        if (chunks > 64) chunks = 64;
-        cb->chunks = chunks;
+        cb->chunks = cbam_chunks(x->D * x->H * x->W);
         cb->dout = dalloc<float>(x->rows() * C);
         cb->buf_off = bnbuf_count; bnbuf_count += cbam_total(cb);
         cb->xflag = consume(x);

@@ -375,7 +375,7 @@ struct GnApplyArgs {
     float* dy1; int lddy1;
     float* dy2; int lddy2; int acc2;             // mode 3: GN2 input grad; 1,4: residual grad; 6: grad of the CBAM output
     float drop_scale; float drop_rate; unsigned long long seed; const unsigned long long* seed_dev;
-    // one-launch path for small tensors (p3d_gn_small_*): epsilon, and where the parameter gradients are ADDED
+    // epsilon of the one-launch path for small tensors (p3d_gn_small_*), and where its parameter gradients are STORED
     float eps; float* dgamma1; float* dbeta1; float* dgamma2; float* dbeta2;
     float* part; unsigned* counters;             // backward partial sums + arrival counters (set by the launchers)
 };

@@ -127,6 +127,86 @@ def bn_pass(mode, y1, y2, params, moving, dz, batch=(1, 1), update_moving=1, acc
     return z, dy1, dy2, grads, mv, tuple(info)
 
 
+def _strided(a, ld, fill):
+    """[rows, C] -> [rows, ld] float32 with `fill` in the columns past C."""
+    a = _f32(a)
+    out = np.full((a.shape[0], ld), fill, np.float32)
+    out[:, :a.shape[1]] = a
+    return out
+
+
+def gn_pass(mode, y1, y2, params, dz, G, eps=1e-5, cs=None, ss=None, acc2=None, grads=None, drop_rate=0.0, seed=0, path=0,
+            ld=(None, None, None), pad=np.nan, device=0):
+    """Test hook: one GroupNorm normalise / ReLU / add pass of the GN network (mode 0-6, see include/p3d_hip.h) forward and
+    backward (mode 2: forward only) on [N, R, C] arrays with G groups.  params [gns, 2, C] = gamma, beta; cs [N, C], ss [N, R]
+    for mode 6.  acc2: the gradient of y2 to add to (None: overwrite).  grads: [gns, 2, C] held by the parameter gradients
+    before the pass (default NaN: they must be stored).  ld = (ld of y1 / dy1, of y2 / dy2, of z / dz), None for C: the
+    operands are then stored with rows of ld floats, the columns past C filled with `pad`.  path 0 = the network's rule, 1 small,
+    2 statistics / finalize / apply.  Returns (z, dy1, dy2, grads, tables [gns, 4, N, C] = scale, shift, mean, invstd,
+    path taken, pads) -- z, dy1, dy2 [N, R, C] (None where the mode has none); pads = what z, dy1, dy2 held past column C."""
+    y1 = _f32(y1)
+    N, R, C_ = y1.shape
+    M = N * R
+    gns = 2 if mode in (2, 3) else 1
+    has2, bwd = mode not in (0, 5), mode != 2
+    d2 = mode in (1, 3, 4, 6)
+    l1, l2, lz = [C_ if v is None else int(v) for v in ld]
+    y1s = _strided(y1.reshape(M, C_), l1, pad)
+    y2s = _strided(_f32(y2).reshape(M, C_), l2, pad) if has2 else None
+    dzs = _strided(_f32(dz).reshape(M, C_), lz, pad) if bwd else None
+    zs = np.full((M, lz), pad, np.float32)
+    g1s = np.full((M, l1), pad, np.float32)
+    if d2:
+        g2s = _strided(_f32(acc2).reshape(M, C_), l2, pad) if acc2 is not None else np.full((M, l2), pad, np.float32)
+    else:
+        g2s = None
+    prm = _f32(np.asarray(params).reshape(gns, 2, C_))
+    grd = np.full((gns, 2, C_), np.nan, np.float32) if grads is None else _f32(np.asarray(grads).reshape(gns, 2, C_)).copy()
+    tables = np.empty((gns, 4, N, C_), np.float32)
+    csd = _f32(np.asarray(cs).reshape(N, C_)) if mode == 6 else None
+    ssd = _f32(np.asarray(ss).reshape(M)) if mode == 6 else None
+    info = (C.c_int * 1)()
+    check(lib().p3d_debug_gn_pass(device, mode, N, R, C_, int(G), float(eps), fptr(y1s), l1, fptr(y2s), l2, lz, fptr(prm),
+                                  fptr(csd), fptr(ssd), fptr(dzs), 1 if acc2 is not None else 0, float(drop_rate), int(seed),
+                                  path, fptr(zs), fptr(g1s), fptr(g2s), fptr(grd), fptr(tables), info))
+    z = zs[:, :C_].reshape(N, R, C_).copy()
+    dy1 = g1s[:, :C_].reshape(N, R, C_).copy() if bwd else None
+    dy2 = g2s[:, :C_].reshape(N, R, C_).copy() if (bwd and d2) else None
+    pads = (zs[:, C_:], g1s[:, C_:], g2s[:, C_:] if g2s is not None else None)
+    return z, dy1, dy2, (grd if bwd else None), tables, info[0], pads
+
+
+def cbam(x, k0, b0, k1, b1, k7, dout, chunks=0, dx=None, pgrads=None, ld=None, pad=np.nan, device=0):
+    """Test hook: CBAM (utils/network.py:198-274) forward and backward on x [N, D, H, W, C] as the network runs it.  k0 [C, C/8],
+    b0 [C/8], k1 [C/8, C], b1 [C], k7 [7, 7, 7, 2, 1]; dout: gradient of the output.  chunks: row chunks per sample (0: the
+    network's rule).  dx: the gradient of x to add to (None: overwrite); pgrads: (dk0, db0, dk1, db1, dk7) to add to (None:
+    zeros).  ld: row stride of x and dx (None: C; the columns past C hold `pad`).  Returns (cs [N, C], sp [N, D, H, W, 2],
+    ss [N, D, H, W], dx, (dk0, db0, dk1, db1, dk7), chunks used, what dx held past column C)."""
+    x = _f32(x)
+    N, D, H, W, C_ = x.shape
+    Ch = C_ // 8
+    M = N * D * H * W
+    l = C_ if ld is None else int(ld)
+    xs = _strided(x.reshape(M, C_), l, pad)
+    dxs = _strided(_f32(dx).reshape(M, C_), l, pad) if dx is not None else np.full((M, l), pad, np.float32)
+    shapes = [(C_, Ch), (Ch,), (Ch, C_), (C_,), (7, 7, 7, 2, 1)]
+    if pgrads is None:
+        pgrads = [np.zeros(s, np.float32) for s in shapes]
+    pg = np.concatenate([_f32(np.asarray(g).reshape(s)).ravel() for g, s in zip(pgrads, shapes)])
+    cs, sp, ss = np.empty((N, C_), np.float32), np.empty((M, 2), np.float32), np.empty((M,), np.float32)
+    info = (C.c_int * 1)()
+    check(lib().p3d_debug_cbam(device, N, D, H, W, C_, fptr(xs), l, fptr(_f32(k0)), fptr(_f32(b0)), fptr(_f32(k1)), fptr(_f32(b1)),
+                               fptr(_f32(k7)), int(chunks), fptr(_f32(dout)), 1 if dx is not None else 0, fptr(cs), fptr(sp),
+                               fptr(ss), fptr(dxs), fptr(pg), info))
+    out, o = [], 0
+    for s in shapes:
+        n = int(np.prod(s))
+        out.append(pg[o:o + n].reshape(s))
+        o += n
+    return (cs, sp.reshape(N, D, H, W, 2), ss.reshape(N, D, H, W), dxs[:, :C_].reshape(x.shape).copy(), tuple(out), info[0],
+            dxs[:, C_:])
+
+
 def stat_parts(xshape, fshape, strides, transpose=False):
     """Host-only test hook: (partials the conv's statistics epilogue writes, room the network reserves for them)."""
     w, c = C.c_int(), C.c_int()
