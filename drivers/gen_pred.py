@@ -1,17 +1,27 @@
 #!/usr/bin/env python3
-"""Python-3 counterpart of the reference's sliding-window inference (/root/reference/gen_pred.py) on libp3dhip.
+"""Python-3 counterpart of the reference's sliding-window inference (gen_pred.py) on libp3dhip.
 
 For every video: a 16-frame queue slides by ONE frame (gen_pred.py:100-134); the first window emits all 16 maps,
 every later window only its last map (gen_pred.py:154-168); frames are normalised like gen_pred.py:117-121
-((RGB - [90,102,98]) / 255 after resizing to 112x112) by the fused GPU pass of sap3d_tensorflow_amd.dataflow.  The reference decodes JPEG folders with cv2 and writes
-960x1080 JPEGs; cv2 is outside this path, so a video here is a .npy array [F,H,W,3] uint8 RGB and the maps come
-back as a float32 array [F,112,112].  Stride-1 windows are batched (`--batch`) instead of run one by one:
-`p3d_predict_windows` gives every window the result of its own batch-of-1 run (the backbone BatchNorm uses batch
-statistics even at inference, p3d.py:140, so a plain batched forward would couple the windows)."""
+((RGB - [90,102,98]) / 255 after resizing to 112x112) by the fused GPU pass of sap3d_tensorflow_amd.dataflow.  cv2 is outside
+this path, so a video here is a .npy array [F,H,W,3] uint8 RGB (decoding the reference's JPEG folders is out of scope).
+Stride-1 windows are batched (`--batch`) instead of run one by one: `p3d_predict_windows` gives every window the result of
+its own batch-of-1 run (the backbone BatchNorm uses batch statistics even at inference, p3d.py:140, so a plain batched
+forward would couple the windows).
+
+Output (`--write`):
+  npy       one float32 array [F,112,112] per video, <out>/<video>.npy (the default);
+  png, jpg  the reference's write-out (gen_pred.py:154-168): <out>/<video>/frame_<k>.<ext>, k = 1..F, one 8-bit image per
+            frame at `--size` (1080x960), the bytes cv2.imwrite(cv2.resize(float64(map * 255.), (960, 1080))) encodes,
+            resized and quantised on the GPU (P3DSession.pred_maps_u8).  A video whose directory exists is skipped
+            (gen_pred.py:83-86).  PNG is lossless: its pixels are exactly those bytes.  JPEG is written by PIL at
+            quality 95 (cv2's default); the files are not byte-identical to cv2's encoder.  Files are encoded on `--writers`
+            threads while the GPU runs the next batch."""
 import argparse
 import glob
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -44,7 +54,72 @@ def predict_video(sess, frames, batch):
     return out
 
 
-def main():
+def predict_video_images(sess, frames, batch, size=(1080, 960), scale=255.):
+    """The image mode of predict_video: the same windows and batches, but every batch's maps are resized and quantised on the
+    device (P3DSession.pred_maps_u8 with first_frame 0 for the window at s = 0, 15 for later ones, T for padding).  Yields,
+    per batch, (frames, maps): the 0-based frame index of every map and the uint8 maps [n, H, W]."""
+    F = len(frames)
+    if F < 16:
+        raise ValueError("need at least 16 frames")
+    starts = list(range(F - 15))
+    for i in range(0, len(starts), batch):
+        chunk = starts[i:i + batch]
+        clips = np.stack([frames[s:s + 16] for s in chunk] + [frames[chunk[-1]:chunk[-1] + 16]] * (batch - len(chunk)))
+        sess.predict_windows(clips)
+        first = [0 if s == 0 else 15 for s in chunk] + [16] * (batch - len(chunk))
+        maps = sess.pred_maps_u8(first, size=size, scale=scale)
+        yield [s + t for s, f0 in zip(chunk, first) for t in range(f0, 16)], maps
+
+
+def save_image(path, m, ext):
+    """One 8-bit map with PIL: PNG at compress_level 1 (lossless: the level changes the file size, not the pixels), JPEG at
+    quality 95 (cv2.IMWRITE_JPEG_QUALITY's default)."""
+    from PIL import Image
+    if m.dtype != np.uint8 or m.ndim != 2:
+        raise ValueError("expected a [H, W] uint8 map")
+    if ext == "png":
+        Image.fromarray(m).save(path, format="PNG", compress_level=1)
+    else:
+        Image.fromarray(m).save(path, format="JPEG", quality=95)
+
+
+def write_video_images(sess, frames, batch, video_dir, ext, size=(1080, 960), writers=4):
+    """<video_dir>/frame_<k>.<ext>, k = 1..F (gen_pred.py:159,165).  A batch's files are encoded on a pool of `writers`
+    threads (PIL releases the GIL while it compresses) while the device runs the next batch; at most two batches of maps are
+    held.  Returns milliseconds: gpu (wall time of the forward passes and map stages), device / d2h (pred_maps_u8's device
+    times), encode (thread time spent encoding), and the number of files."""
+    import threading
+    from concurrent.futures import ThreadPoolExecutor
+    t = dict(gpu=0.0, device=0.0, d2h=0.0, encode=0.0, files=0)
+    lock = threading.Lock()
+
+    def write(f, m):
+        t0 = time.perf_counter()
+        save_image(os.path.join(video_dir, "frame_%d.%s" % (f + 1, ext)), m, ext)
+        with lock:
+            t["encode"] += (time.perf_counter() - t0) * 1e3
+
+    held = []
+    with ThreadPoolExecutor(max_workers=writers) as pool:
+        batches = predict_video_images(sess, frames, batch, size=size)
+        while True:
+            t0 = time.perf_counter()
+            nxt = next(batches, None)
+            t["gpu"] += (time.perf_counter() - t0) * 1e3
+            for fut in held:              # the previous batch, encoded while this one ran on the device
+                fut.result()
+            if nxt is None:
+                break
+            idx, maps = nxt
+            ms = getattr(sess, "last_maps_ms", None) or {}
+            t["device"] += ms.get("device", 0.0)
+            t["d2h"] += ms.get("d2h", 0.0)
+            held = [pool.submit(write, f, m) for f, m in zip(idx, maps)]
+            t["files"] += len(held)
+    return t
+
+
+def parse_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--model", type=str, default="", help="checkpoint: a directory with a TF `checkpoint` state file (gen_pred.py:57-64), "
                    "a TF bundle prefix, or an .npz keyed by TF variable names")
@@ -55,16 +130,53 @@ def main():
     p.add_argument("--out", type=str, default="pred")
     p.add_argument("--batch", type=int, default=8)
     p.add_argument("--gpu", type=str, default="0")
-    args = p.parse_args()
+    p.add_argument("--write", choices=("npy", "png", "jpg"), default="npy",
+                   help="npy: one float32 [F,112,112] array per video; png / jpg: the reference's 8-bit frame_<k> images per video "
+                        "(gen_pred.py:154-168), resized and quantised on the GPU.  PNG pixels are exactly the bytes cv2.imwrite "
+                        "would encode; JPEG is PIL's encoder at quality 95, not byte-identical to cv2's")
+    p.add_argument("--size", type=int, nargs=2, default=(1080, 960), metavar=("H", "W"), help="image size for png / jpg")
+    p.add_argument("--writers", type=int, default=4, help="encoder threads for png / jpg (at most 16)")
+    p.add_argument("--time", action="store_true", help="print per-video wall times (png / jpg: also the device stage and the host encode)")
+    args = p.parse_args(argv)
+    if not 1 <= args.writers <= 16:
+        p.error("--writers must be in 1..16")
+    return args
+
+
+def run(sess, args):
+    os.makedirs(args.out, exist_ok=True)
+    for path in sorted(glob.glob(os.path.join(args.videos, "*.npy"))):
+        if args.write == "npy":
+            t0 = time.perf_counter()
+            sal = predict_video(sess, preprocess(np.load(path)), args.batch)
+            np.save(os.path.join(args.out, os.path.basename(path)), sal)
+            print(os.path.basename(path), sal.shape, float(sal.mean()))
+            if args.time:
+                print("  %s: wall %.1f ms" % (os.path.basename(path), (time.perf_counter() - t0) * 1e3))
+            continue
+        name = os.path.splitext(os.path.basename(path))[0]
+        video_dir = os.path.join(args.out, name)
+        if os.path.exists(video_dir):                 # gen_pred.py:83-86: a video already written is skipped
+            print(name, "skipped: %s exists" % video_dir)
+            continue
+        os.mkdir(video_dir)
+        t0 = time.perf_counter()
+        t = write_video_images(sess, preprocess(np.load(path)), args.batch, video_dir, args.write, size=tuple(args.size),
+                               writers=args.writers)
+        wall = (time.perf_counter() - t0) * 1e3
+        print(name, "%d %s files in %s" % (t["files"], args.write, video_dir))
+        if args.time:
+            print("  %s: wall %.1f ms | forward + maps %.1f ms (device resize/quantise %.2f ms, d2h %.2f ms) | encode %.1f ms "
+                  "thread time on %d writers" % (name, wall, t["gpu"], t["device"], t["d2h"], t["encode"], args.writers))
+
+
+def main(argv=None):
+    args = parse_args(argv)
     from sap3d_tensorflow_amd import P3DSession
     sess = P3DSession(args.structure, batch=args.batch, device=int(args.gpu), seed=0)
     if args.model:
         sess.restore(args.model)
-    os.makedirs(args.out, exist_ok=True)
-    for path in sorted(glob.glob(os.path.join(args.videos, "*.npy"))):
-        sal = predict_video(sess, preprocess(np.load(path)), args.batch)
-        np.save(os.path.join(args.out, os.path.basename(path)), sal)
-        print(os.path.basename(path), sal.shape, float(sal.mean()))
+    run(sess, args)
     sess.close()
 
 

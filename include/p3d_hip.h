@@ -339,6 +339,20 @@ int p3d_eval_last_frames(p3d_handle* h, const unsigned char* density, int Hd, in
                          const double* jitter, const int* borji_idx, const int* n_fix, int n_rep, double step_size, double* out,
                          double* stage_ms);
 
+/* ---- gen_pred.py's write-out (gen_pred.py:154-168): every emitted 112x112 map as an 8-bit image at 1080x960.
+ * cv2.imwrite(name, cv2.resize(float64(map * 255.), (W, H))) per map: the float32 product map * scale widened to double,
+ * INTER_LINEAR on CV_64F (the float32 path's coordinates and float32 weights, double arithmetic, no FMA; same size: a copy),
+ * then imwrite's saturate_cast<uchar>: round half to even, clamp to [0, 255]; NaN and rounded values outside int32 give 0
+ * (x86 OpenCV; the reference's semantics are pinned for |v| < 2^31 only).  H * W <= INT32_MAX.
+ * Host arrays [n][h][w] float32 -> [n][H][W] uint8 (op level, tests). */
+int p3d_resize_linear_u8(int device, const float* src, int n, int h, int w, float scale, int H, int W, unsigned char* dst);
+/* The same on the handle's last prediction (p3d_predict_windows / p3d_forward), [B][T][h][w]: clip b's frames first_frame[b] ..
+ * T-1, packed in clip order then frame order into out[sum(T - first_frame[b])][H][W].  first_frame[b] = 0 is the first
+ * window (all 16 maps, gen_pred.py:154-160), 15 a later one (its newest frame, :161-168), T a clip that writes nothing (the
+ * padding of a short last batch).  Refuses first_frame outside [0, T] and a handle that has run no forward pass.  Scratch
+ * from the stream pool.  stage_ms[2] (or NULL): device time of the resize / quantise stage and of the device->host copy. */
+int p3d_pred_maps_u8(p3d_handle* h, const int* first_frame, float scale, int H, int W, unsigned char* out, double* stage_ms);
+
 /* CRC-32C of a host buffer (host-side helper of the TensorFlow checkpoint reader / writer, sap3d_tensorflow_amd/tf_checkpoint.py:
  * the bundle format of train.py:180-185,266-267 checksums every tensor); crc = running value, 0 to start. */
 uint32_t p3d_crc32c(const void* data, size_t n, uint32_t crc);

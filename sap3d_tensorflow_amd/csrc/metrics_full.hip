@@ -5,6 +5,8 @@
 //    rule of metrics.hip's lin_coef and mapf_kernel's arithmetic (float32 products and sums, horizontal pass then vertical
 //    pass), with contraction switched off for the whole file: hipcc fuses a * b + c into one FMA by default, even through
 //    the __fmul_rn / __fadd_rn intrinsics of the HIP headers (their bodies are plain operators compiled outside any pragma).
+//  * resize_u8_kernel: gen_pred.py:154-168's write-out, cv2.imwrite(cv2.resize(float64(map * 255.), (W, H))): the same
+//    coordinates and weights, float64 arithmetic (OpenCV's CV_64F generic path), then imwrite's saturate_cast to uint8.
 //  * full_pass_a / full_pass_b / full_sort / full_pass_c / full_borji: CC, SIM, AUC-Judd, AUC-Borji, NSS (and shuffled AUC)
 //    of large maps with every map split over many blocks.  Cross-block folds use det_reduce.h (write-through partials, the
 //    last arriving block folds them in a fixed order); the only atomics are integer ones (arrival tickets, the AUC-Judd
@@ -86,8 +88,18 @@ __device__ __forceinline__ void lin_coef_rn(int d, double scale, int extent, int
     if (sx >= extent - 1) { sx = extent - 1; fx = 0.f; }
     s0 = sx; s1 = min(sx + 1, extent - 1); w1 = fx;
 }
+// The four source taps of destination pixel (y, x) and their weights: one coordinate rule for the float32 and the 8-bit resize.
 // src: map m's pixel (y, x) at src[m * map_stride + (y * w + x) * elem_stride] (elem_stride > 1: a channel of a wider
 // tensor, e.g. the last frame of every clip in the network's prediction buffer)
+struct LinTaps { float p00, p01, p10, p11, wx, wy; };
+__device__ __forceinline__ LinTaps lin_taps(const float* f0, int elem_stride, int h, int w, int y, int x, double sy, double sx) {
+    int x0, x1, y0, y1; LinTaps t;
+    lin_coef_rn(x, sx, w, x0, x1, t.wx);
+    lin_coef_rn(y, sy, h, y0, y1, t.wy);
+    t.p00 = f0[((size_t)y0 * w + x0) * elem_stride]; t.p01 = f0[((size_t)y0 * w + x1) * elem_stride];
+    t.p10 = f0[((size_t)y1 * w + x0) * elem_stride]; t.p11 = f0[((size_t)y1 * w + x1) * elem_stride];
+    return t;
+}
 __global__ __launch_bounds__(TPB) void resize_f32_kernel(const float* src, long long map_stride, int elem_stride, int n, int h, int w,
                                                          float* dst, int H, int W) {
     const double sx = (double)w / W, sy = (double)h / H;
@@ -96,16 +108,60 @@ __global__ __launch_bounds__(TPB) void resize_f32_kernel(const float* src, long 
         const int x = (int)(i % W);
         const int y = (int)((i / W) % H);
         const long long m = i / ((long long)W * H);
-        int x0, x1, y0, y1; float wx, wy;
-        lin_coef_rn(x, sx, w, x0, x1, wx);
-        lin_coef_rn(y, sy, h, y0, y1, wy);
-        const float* f0 = src + m * map_stride;
-        const float p00 = f0[((size_t)y0 * w + x0) * elem_stride], p01 = f0[((size_t)y0 * w + x1) * elem_stride];
-        const float p10 = f0[((size_t)y1 * w + x0) * elem_stride], p11 = f0[((size_t)y1 * w + x1) * elem_stride];
+        const LinTaps t = lin_taps(src + m * map_stride, elem_stride, h, w, y, x, sy, sx);
+        const float p00 = t.p00, p01 = t.p01, p10 = t.p10, p11 = t.p11, wx = t.wx, wy = t.wy;
         const float ax = 1.f - wx, ay = 1.f - wy;
         const float r0 = p00 * ax + p01 * wx;
         const float r1 = p10 * ax + p11 * wx;
         dst[i] = r0 * ay + r1 * wy;
+    }
+}
+
+// ---- 8-bit prediction maps (gen_pred.py:154-168) --------------------------------------------------------------------
+// saturate_cast<uchar>(double) as cv2.imwrite's conversion to CV_8U does it on x86: cvRound (round half to even) to int32,
+// then clamp to [0, 255].  NaN and a rounded value outside int32 (cvtsd2si's integer-indefinite INT_MIN) give 0.  Spelled
+// out rather than left to the hardware's saturating convert, whose out-of-range results differ from x86's.
+__device__ __forceinline__ unsigned sat_u8(double v) {
+    const double r = rint(v);                                  // NaN stays NaN and fails both range tests below
+    if (!(r >= -2147483648.0 && r <= 2147483647.0)) return 0u;
+    return r <= 0.0 ? 0u : r >= 255.0 ? 255u : (unsigned)r;
+}
+// one pixel: the source is float32(p * scale) widened exactly to double (numpy's float32 product); cv2's CV_64F INTER_LINEAR
+// has float32 weights widened to double and double sums, horizontal pass then vertical.  Same size: cv2.resize copies.
+__device__ __forceinline__ unsigned resize_u8_px(const float* f0, int elem_stride, int h, int w, int y, int x, double sy, double sx,
+                                                 float scale, bool same) {
+    if (same) return sat_u8((double)(f0[((size_t)y * w + x) * elem_stride] * scale));
+    const LinTaps t = lin_taps(f0, elem_stride, h, w, y, x, sy, sx);
+    const double ax = (double)(1.f - t.wx), bx = (double)t.wx, ay = (double)(1.f - t.wy), by = (double)t.wy;
+    const double r0 = (double)(t.p00 * scale) * ax + (double)(t.p01 * scale) * bx;
+    const double r1 = (double)(t.p10 * scale) * ax + (double)(t.p11 * scale) * bx;
+    return sat_u8(r0 * ay + r1 * by);
+}
+// [n][h][w] float -> [n][H][W] uint8 at dst[off ..): pixel j of this launch is byte off + j of dst (dst 4-byte aligned, off
+// arbitrary, so that several launches can pack their maps back to back).  Thread q owns the aligned word of bytes
+// 4q .. 4q+3 and stores it whole; only the (at most two) words cut by the launch's ends are stored byte by byte.
+// H * W <= INT32_MAX (checked by the callers): in-map offsets are int.
+__global__ __launch_bounds__(TPB) void resize_u8_kernel(const float* src, long long map_stride, int elem_stride, int n, int h, int w,
+                                                        float scale, unsigned char* dst, long long off, int H, int W) {
+    const double sx = (double)w / W, sy = (double)h / H;
+    const bool same = h == H && w == W;
+    const long long hw = (long long)H * W, end = off + (long long)n * hw;
+    const long long q0 = off >> 2, q1 = (end + 3) >> 2;
+    for (long long q = q0 + (long long)blockIdx.x * TPB + threadIdx.x; q < q1; q += (long long)gridDim.x * TPB) {
+        const long long b0 = max(q << 2, off), b1 = min((q << 2) + 4, end);
+        long long m = (b0 - off) / hw;
+        int p = (int)(b0 - off - m * hw);
+        int y = p / W, x = p - y * W;
+        unsigned v[4] = {0u, 0u, 0u, 0u};
+        for (long long b = b0; b < b1; ++b) {
+            v[b & 3] = resize_u8_px(src + m * map_stride, elem_stride, h, w, y, x, sy, sx, scale, same);
+            if (++x == W) { x = 0; if (++y == H) { y = 0; ++m; } }
+        }
+        if (b1 - b0 == 4) {
+            reinterpret_cast<unsigned*>(dst)[q] = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
+        } else {
+            for (long long b = b0; b < b1; ++b) dst[b] = (unsigned char)v[b & 3];
+        }
     }
 }
 
@@ -423,6 +479,13 @@ hipError_t p3d_resize_f32(const float* src, long long map_stride, int elem_strid
                           hipStream_t s) {
     hipLaunchKernelGGL(resize_f32_kernel, dim3(grid_for((long long)n * H * W)), dim3(TPB), 0, s, src, map_stride, elem_stride, n, h, w,
                        dst, H, W);
+    return hipGetLastError();
+}
+hipError_t p3d_resize_u8(const float* src, long long map_stride, int elem_stride, int n, int h, int w, float scale, unsigned char* dst,
+                         long long off, int H, int W, hipStream_t s) {
+    const long long words = ((off + (long long)n * H * W + 3) >> 2) - (off >> 2);
+    hipLaunchKernelGGL(resize_u8_kernel, dim3(grid_for(words)), dim3(TPB), 0, s, src, map_stride, elem_stride, n, h, w, scale, dst, off,
+                       H, W);
     return hipGetLastError();
 }
 hipError_t p3d_full_moments(const P3dFullMaps& a, hipStream_t s) {

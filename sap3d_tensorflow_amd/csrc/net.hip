@@ -1013,6 +1013,7 @@ struct p3d_handle {
     bool fuse_bn = false;
     bool fuse_bn_bwd = false;         // p3d_set_bn_fusion(h, 2): the backward pass fused too
     bool last_forward_fused = false;
+    bool pred_ready = false;          // a forward pass has been issued: `pred` holds a prediction (p3d_pred_maps_u8 refuses before)
     // Only bottlenecks whose inner tensors have at most this many rows are built fusable: there a BatchNorm pass is a
     // latency-bound launch of its own (stage 3 at 8 clips of 16x112x112: 784 rows), while on big tensors the passes stream at
     // HBM speed and the convs are throughput-bound, so per-step operand work costs more than the passes it removes

@@ -1536,6 +1536,71 @@ int p3d_eval_last_frames(p3d_handle* h, const unsigned char* density, int Hd, in
     API_END
 }
 
+int p3d_resize_linear_u8(int device, const float* src, int n, int h, int w, float scale, int H, int W, unsigned char* dst) {
+    API_BEGIN
+    metric_args(device, src, src, 1, 1, dst);
+    if (n < 1 || h < 1 || w < 1 || H < 1 || W < 1) throw P3dError("resize_u8: empty map");
+    if ((long long)H * W > INT32_MAX) throw P3dError("resize_u8: H * W exceeds the kernel's int32 in-map offsets");
+    DevArr<float> s((size_t)n * h * w, src);
+    DevArr<unsigned char> d((size_t)n * H * W);
+    HIPCHECK(p3d_resize_u8(s.p, (long long)h * w, 1, n, h, w, scale, d.p, 0, H, W, nullptr));
+    d.get(dst, (size_t)n * H * W);
+    API_END
+}
+
+int p3d_pred_maps_u8(p3d_handle* h, const int* first_frame, float scale, int H, int W, unsigned char* out, double* stage_ms) {
+    API_BEGIN
+    if (!h || !first_frame || !out) throw P3dError("null argument");
+    if (H < 1 || W < 1) throw P3dError("pred_maps_u8: empty map");
+    if ((long long)H * W > INT32_MAX) throw P3dError("pred_maps_u8: H * W exceeds the kernel's int32 in-map offsets");
+    if (!h->pred_ready) throw P3dError("pred_maps_u8: the handle has no prediction yet (run a forward pass first)");
+    Act* pr = h->pred;
+    const int B = pr->N, T = pr->D;
+    long long maps = 0;
+    for (int b = 0; b < B; ++b) {
+        if (first_frame[b] < 0 || first_frame[b] > T)
+            throw P3dError("pred_maps_u8: first_frame[" + std::to_string(b) + "] = " + std::to_string(first_frame[b]) +
+                           " is outside [0, " + std::to_string(T) + "]");
+        maps += T - first_frame[b];
+    }
+    const long long hw = (long long)H * W, bytes = maps * hw;
+    if (stage_ms) stage_ms[0] = stage_ms[1] = 0.0;
+    if (bytes == 0) return 0;
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    const hipStream_t s = h->stream;
+    float* slab = nullptr;
+    unsigned* counters = nullptr;
+    HIPCHECK(p3d_stream_scratch(s, (size_t)(bytes + 3) / 4, 0, &slab, &counters));
+    unsigned char* d = (unsigned char*)slab;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    if (stage_ms)
+        for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
+    if (stage_ms) HIPCHECK(hipEventRecord(ev[0], s));
+    // the prediction of the last forward pass: [B][T][h][w] with an element stride of ld floats; clip b's frames
+    // first_frame[b] .. T-1, packed after the maps of the clips before it
+    if (pr->materialize && h->last_forward_fused) pr->materialize(s);
+    const long long phw = (long long)pr->H * pr->W;
+    long long off = 0;
+    for (int b = 0; b < B; ++b) {
+        const int f0 = first_frame[b], n = T - f0;
+        if (n == 0) continue;
+        HIPCHECK(p3d_resize_u8(pr->p + ((size_t)b * T + f0) * phw * pr->ld, phw * pr->ld, pr->ld, n, pr->H, pr->W, scale, d, off, H, W, s));
+        off += n * hw;
+    }
+    if (stage_ms) HIPCHECK(hipEventRecord(ev[1], s));
+    HIPCHECK(hipMemcpyAsync(out, d, (size_t)bytes, hipMemcpyDeviceToHost, s));
+    if (stage_ms) HIPCHECK(hipEventRecord(ev[2], s));
+    HIPCHECK(hipStreamSynchronize(s));
+    if (stage_ms) {
+        float t0 = 0, t1 = 0;
+        HIPCHECK(hipEventElapsedTime(&t0, ev[0], ev[1]));
+        HIPCHECK(hipEventElapsedTime(&t1, ev[1], ev[2]));
+        stage_ms[0] = t0; stage_ms[1] = t1;
+        for (auto& e : ev) HIPCHECK(hipEventDestroy(e));
+    }
+    API_END
+}
+
 // CRC-32C (Castagnoli) of a host buffer, slicing-by-8: the checksum of TensorFlow's checkpoint bundles
 // (tensorflow/core/lib/hash/crc32c.h), used by the Python reader / writer of sap3d_tensorflow_amd/tf_checkpoint.py on the
 // 248 MB of variables (train.py:180-185, 204-210, 266-267).  `crc` = running value (0 to start).

@@ -99,6 +99,7 @@
         HIPCHECK(hipStreamSynchronize(c.s));
         HIPCHECK(fill_async(flat_g, 0, (size_t)n_train * sizeof(float), c.s, "gradients"));
         HIPCHECK(hipStreamSynchronize(c.s));
+        pred_ready = false;           // what these passes left in `pred` is no prediction of the caller's
     }
 
     // Dry-run forward and backward once: every dense buffer an op would zero-fill before adding into it

@@ -18,6 +18,7 @@
         Ctx cz = c; cz.z0 = zf; cz.z1 = zf + zf_bytes;
         cz.fuse = fuse_bn && !c.per_sample && !c.dry;
         last_forward_fused = cz.fuse;
+        if (!c.dry) pred_ready = true;
         const bool no_side_f = runtime_env().no_side_stream;
         cz.side = (c.prof || no_side_f || c.dry) ? nullptr : side_stream;      // ST_B sibling convs overlap
         const Ctx& c2 = cz;

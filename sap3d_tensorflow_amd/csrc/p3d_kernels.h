@@ -518,6 +518,10 @@ hipError_t p3d_mapf_density(const unsigned char* grey, int n_frames, int H0, int
 // cv2.INTER_LINEAR resize of float32 maps: map m's pixel (y, x) at src[m * map_stride + (y * w + x) * elem_stride]
 hipError_t p3d_resize_f32(const float* src, long long map_stride, int elem_stride, int n, int h, int w, float* dst, int H, int W,
                           hipStream_t s);
+// ... and gen_pred.py's 8-bit write-out: uint8(cvRound(resize_f64(float32(map * scale)))), clamped; NaN / outside int32 -> 0.
+// Writes bytes off .. off + n*H*W - 1 of dst (dst 4-byte aligned); needs H * W <= INT32_MAX.
+hipError_t p3d_resize_u8(const float* src, long long map_stride, int elem_stride, int n, int h, int w, float scale, unsigned char* dst,
+                         long long off, int H, int W, hipStream_t s);
 struct P3dFullMaps {
     const float* P = nullptr;        // [n_maps][n_pix] saliency maps (clean)
     const float* D = nullptr;        // [n_maps][n_pix] density maps as float32(v / 255.) of the uint8 resize, or null (no CC / SIM)

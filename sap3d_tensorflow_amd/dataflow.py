@@ -54,3 +54,20 @@ def resize_linear(maps, size, device=0):
     check(lib().p3d_resize_linear(device, m.ctypes.data_as(C.POINTER(C.c_float)), m.shape[0], m.shape[1], m.shape[2], H, W,
                                   out.ctypes.data_as(C.POINTER(C.c_float))))
     return out[0] if single else out
+
+
+def resize_linear_u8(maps, size, scale=255., device=0):
+    """gen_pred.py:154-168's write-out of float32 maps: uint8(cv2.resize(float64(m * scale), (W, H))) as cv2.imwrite stores it
+    (INTER_LINEAR in float64, round half to even, clamp to [0, 255]; NaN and values outside int32 -> 0), csrc/metrics_full.hip.
+    [n, h, w] or [h, w] -> [n, H, W] / [H, W] uint8; size = (H, W) or an int; m * scale is a float32 product."""
+    m = np.ascontiguousarray(maps, dtype=np.float32)
+    single = m.ndim == 2
+    if single:
+        m = m[None]
+    if m.ndim != 3 or m.size == 0:
+        raise ValueError("expected [n, h, w] or [h, w] float32 maps")
+    H, W = (size, size) if np.isscalar(size) else size
+    out = np.empty((m.shape[0], H, W), np.uint8)
+    check(lib().p3d_resize_linear_u8(device, m.ctypes.data_as(C.POINTER(C.c_float)), m.shape[0], m.shape[1], m.shape[2], float(scale),
+                                     H, W, out.ctypes.data_as(C.POINTER(C.c_ubyte))))
+    return out[0] if single else out

@@ -231,6 +231,25 @@ class P3DSession:
         check(lib().p3d_predict_windows(self._h, fptr(x), fptr(pred)))
         return pred
 
+    def pred_maps_u8(self, first_frame, size=(1080, 960), scale=255.):
+        """gen_pred.py:154-168's 8-bit images of the last prediction (predict_windows / forward), resized on the device:
+        clip b gives frames first_frame[b] .. T-1 (0: the first window's 16 maps, 15: a later window's newest map, T: none)
+        -> uint8 [sum(T - first_frame), H, W], in clip then frame order.  Each map is cv2.imwrite's byte image of
+        cv2.resize(float64(map * scale), (W, H)) (dataflow.resize_linear_u8).  Device times of the call are left in
+        `last_maps_ms` (device = resize / quantise, d2h = the copy back; milliseconds)."""
+        H, W = (size, size) if np.isscalar(size) else tuple(size)
+        B, T = self.x_shape[0], self.x_shape[1]
+        ff = np.ascontiguousarray(first_frame, dtype=np.int32)
+        if ff.shape != (B,):
+            raise ValueError("first_frame needs one entry per clip (%d)" % B)
+        valid = np.all((ff >= 0) & (ff <= T)) and H >= 1 and W >= 1 and H * W <= 2 ** 31 - 1
+        out = np.empty((int(np.sum(T - ff.astype(np.int64))), H, W) if valid else (0,), np.uint8)     # (the library refuses the rest)
+        ms = (C.c_double * 2)()
+        check(lib().p3d_pred_maps_u8(self._h, ff.ctypes.data_as(_lib._ip), float(scale), int(H), int(W),
+                                     out.ctypes.data_as(C.POINTER(C.c_ubyte)), ms))
+        self.last_maps_ms = dict(device=ms[0], d2h=ms[1])
+        return out
+
     def train_step(self, x, y, dropout=0.5, seed=0):
         """sess.run([train_op, loss], {x, y, dropout, training: True})  (train.py:217-218) -> loss."""
         x, y = self._x(x), self._y(y)
