@@ -280,6 +280,29 @@ int p3d_debug_gn_pass(int device, int mode, int N, int R, int C, int G, float ep
 int p3d_debug_cbam(int device, int N, int D, int H, int W, int C, const float* x, int ld, const float* k0, const float* b0,
                    const float* k1, const float* b1, const float* k7, int chunks, const float* dout, int accx, float* cs, float* sp,
                    float* ss, float* dx, float* pgrads, int* info);
+/* Test hook: the output head (head() of the network) forward, then both gradients, through the launchers the network calls.
+ * transpose 1: tf.layers.conv3d_transpose(x, 1, 3, 2, 'same'), logits / pred / dlogits [N,2D,2H,2W]; 0: the stride-1
+ * tf.layers.conv3d(x, 1, 3, 1, 'same') of the GN decoder-block network, [N,D,H,W].  x, dx [N,D,H,W,C]; k [27][C] (the kernel
+ * [3,3,3,1,C], or [3,3,3,C,1] at stride 1); bias [1]; sigmoid: pred = sigmoid(logits), else pred = logits.  dk and dbias
+ * hold the gradients to add to on entry.  fwd_path: 0 = the network's rule, 1 = L = C/4 lanes per position, 2 = one thread
+ * per position; filter_path: 0 = the rule, 1 = four channels per thread with HEAD_FOLD-block groups folded in two levels,
+ * 2 = one channel per thread, one-level fold (stride 1: both 0, one kernel each).  A forced kernel the shape does not allow
+ * is an error.  info[4] = forward kernel (1 lanes, 2 per position, 3 stride 1) and its blocks, filter-gradient kernel
+ * (1 four channels, 2 one channel, 3 stride 1) and its blocks. */
+int p3d_debug_head(int device, int transpose, int N, int D, int H, int W, int C, const float* x, const float* k, const float* bias,
+                   int sigmoid, const float* dlogits, int fwd_path, int filter_path, float* logits, float* pred, float* dx, float* dk,
+                   float* dbias, int* info);
+/* Test hook: the Smooth-L1 loss and dL/dlogits (p3d_smooth_l1, as the network's loss launches it) on n elements placed
+ * `offset` (0-3) elements into the device buffers: offsets 1-3 misalign them and force the scalar path.  through_sigmoid:
+ * dlogits = dL/dpred * pred * (1 - pred).  *loss is added to.  info[2] = path taken (1 float4, 2 scalar), blocks. */
+int p3d_debug_smooth_l1(int device, const float* pred, const float* target, int64_t n, int through_sigmoid, int offset, double* loss,
+                        float* dlogits, int* info);
+/* Test hook: one Adam launch (p3d_adam, as the network's optimiser step launches it) on n elements placed `offset` elements
+ * into the device buffers (p3d_adam refuses a base that is not 16-byte aligned).  p, m, v are updated in place from g with
+ * the bias-corrected step size of step t (the network's adam_step_size), passed as an argument or, when lr_on_device, through
+ * device memory as a captured train step passes it.  *lr_t = that step size. */
+int p3d_debug_adam(int device, float* p, const float* g, float* m, float* v, int64_t n, int offset, float lr, int64_t t, float b1,
+                   float b2, float eps, int lr_on_device, float* lr_t);
 int p3d_debug_stat_parts(const int64_t xshape[5], const int64_t wshape[5], const int s[3], int transpose, int* written, int* cap);
 int p3d_debug_igemm_groupable(const int64_t xshape[5], const int64_t wshape[5], const int s[3]);
 int p3d_op_max_pool3d(int device, const float* x, const int64_t xshape[5], const int ksize[3], const int s[3], float* y);

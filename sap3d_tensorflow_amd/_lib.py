@@ -87,6 +87,11 @@ SIGNATURES = {
                                     _ip]),
     "p3d_debug_cbam": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, _fp, _fp, _fp, _fp,
                                  C.c_int, _fp, C.c_int, _fp, _fp, _fp, _fp, _fp, _ip]),
+    "p3d_debug_head": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, C.c_int, _fp,
+                                 C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _ip]),
+    "p3d_debug_smooth_l1": (C.c_int, [C.c_int, _fp, _fp, C.c_int64, C.c_int, C.c_int, _dp, _fp, _ip]),
+    "p3d_debug_adam": (C.c_int, [C.c_int, _fp, _fp, _fp, _fp, C.c_int64, C.c_int, C.c_float, C.c_int64, C.c_float, C.c_float,
+                                 C.c_float, C.c_int, _fp]),
     "p3d_debug_stat_parts": (C.c_int, [_i64p, _i64p, _ip, C.c_int, _ip, _ip]),
     "p3d_debug_igemm_groupable": (C.c_int, [_i64p, _i64p, _ip]),
     "p3d_op_conv3d_backprop_input": (C.c_int, [C.c_int, _fp, _fp, _i64p, _ip, _i64p, _fp]),

@@ -446,17 +446,18 @@ __global__ __launch_bounds__(256) void headc_bwd_filter_kernel(HeadArgs a) {
 
 }  // namespace
 
-hipError_t p3d_headc_fwd(const HeadArgs& a, hipStream_t s) {
-    if ((a.C & 3) || a.C > 256) return hipErrorInvalidValue;
+hipError_t p3d_headc_fwd(const HeadArgs& a, hipStream_t s, HeadLaunch* done) {
+    if ((a.C & 3) || a.C < 4 || a.C > 256) return hipErrorInvalidValue;
     const long long total = (long long)a.N * a.D * a.H * a.W;
     long long b = (total + 255) / 256;
     if (b > 8192) b = 8192;
     hipLaunchKernelGGL(headc_fwd_kernel, dim3((unsigned)b), dim3(256), 27 * a.C * sizeof(float), s, a);
+    if (done) { done->kernel = P3D_HEAD_STRIDE1; done->blocks = (unsigned)b; }
     return hipGetLastError();
 }
 
 hipError_t p3d_headc_bwd_input(const HeadArgs& a, hipStream_t s) {
-    if ((a.C & 3) || a.C > 256) return hipErrorInvalidValue;
+    if ((a.C & 3) || a.C < 4 || a.C > 256) return hipErrorInvalidValue;
     const long long total = (long long)a.N * a.D * a.H * a.W * (a.C >> 2);
     long long b = (total + 255) / 256;
     if (b > 8192) b = 8192;
@@ -464,8 +465,9 @@ hipError_t p3d_headc_bwd_input(const HeadArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t p3d_headc_bwd_filter(const HeadArgs& a, hipStream_t s) {
-    if (a.C > 256 || a.C < 1 || (256 % a.C)) return hipErrorInvalidValue;
+// (256 / C position lanes per block; with C not dividing 256 the last 256 % C threads idle, as in head_bwd_filter_kernel)
+hipError_t p3d_headc_bwd_filter(const HeadArgs& a, hipStream_t s, HeadLaunch* done) {
+    if (a.C > 256 || a.C < 1) return hipErrorInvalidValue;
     const long long total = (long long)a.N * a.D * a.H * a.W;
     const int lanes = 256 / a.C;
     long long b = (total + (long long)lanes * 32 - 1) / ((long long)lanes * 32);
@@ -475,30 +477,38 @@ hipError_t p3d_headc_bwd_filter(const HeadArgs& a, hipStream_t s) {
     const hipError_t e = p3d_stream_scratch(s, (size_t)b * 28 * a.C, 1, &aa.part, &aa.counter);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(headc_bwd_filter_kernel, dim3((unsigned)b), dim3(256), 0, s, aa);
+    if (done) { done->kernel = P3D_HEAD_STRIDE1; done->blocks = (unsigned)b; }
     return hipGetLastError();
 }
 
-hipError_t p3d_head_fwd(const HeadArgs& a, hipStream_t s) {
-    if ((a.C & 3) || a.C > 256) return hipErrorInvalidValue;
+// The forward's rule: L = C/4 lanes per position when L is a power of two in [2, 64] and x is 16-byte aligned, else one
+// thread per position.  path P3D_HEAD_RULE follows it; a forced path the rule does not allow is refused.
+hipError_t p3d_head_fwd(const HeadArgs& a, hipStream_t s, int path, HeadLaunch* done) {
+    if ((a.C & 3) || a.C < 4 || a.C > 256) return hipErrorInvalidValue;
+    if (path != P3D_HEAD_RULE && path != P3D_HEAD_LANES && path != P3D_HEAD_GENERIC) return hipErrorInvalidValue;
     const long long total = (long long)a.N * a.D * a.H * a.W;
     const int L = a.C >> 2;
-    if (L > 1 && L <= 64 && (L & (L - 1)) == 0 && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0) {
+    const bool lanes_ok = L > 1 && L <= 64 && (L & (L - 1)) == 0 && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0;
+    if (path == P3D_HEAD_LANES && !lanes_ok) return hipErrorInvalidValue;
+    if (path == P3D_HEAD_LANES || (path == P3D_HEAD_RULE && lanes_ok)) {
         long long b = (total * L + 255) / 256;
         if (b > 16384) b = 16384;
         const size_t sm = 27 * a.C * sizeof(float);
 #define P3D_HL(L_) case L_: hipLaunchKernelGGL(head_fwd_lanes_kernel<L_>, dim3((unsigned)b), dim3(256), sm, s, a); break;
         switch (L) { P3D_HL(2) P3D_HL(4) P3D_HL(8) P3D_HL(16) P3D_HL(32) P3D_HL(64) }
 #undef P3D_HL
+        if (done) { done->kernel = P3D_HEAD_LANES; done->blocks = (unsigned)b; }
         return hipGetLastError();
     }
     long long b = (total + 255) / 256;
     if (b > 8192) b = 8192;
     hipLaunchKernelGGL(head_fwd_kernel, dim3((unsigned)b), dim3(256), 27 * a.C * sizeof(float), s, a);
+    if (done) { done->kernel = P3D_HEAD_GENERIC; done->blocks = (unsigned)b; }
     return hipGetLastError();
 }
 
 hipError_t p3d_head_bwd_input(const HeadArgs& a, hipStream_t s) {
-    if ((a.C & 3) || a.C > 256) return hipErrorInvalidValue;
+    if ((a.C & 3) || a.C < 4 || a.C > 256) return hipErrorInvalidValue;
     const long long total = (long long)a.N * a.D * a.H * a.W * (a.C >> 2);
     long long b = (total + 255) / 256;
     if (b > 8192) b = 8192;
@@ -506,10 +516,15 @@ hipError_t p3d_head_bwd_input(const HeadArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t p3d_head_bwd_filter(const HeadArgs& a, hipStream_t s) {
+// The filter gradient's rule: four channels per thread with the two-level fold when C % 4 == 0 and x is 16-byte aligned,
+// else one channel per thread and a one-level fold.  path as p3d_head_fwd.
+hipError_t p3d_head_bwd_filter(const HeadArgs& a, hipStream_t s, int path, HeadLaunch* done) {
     if (a.C > 256 || a.C < 1) return hipErrorInvalidValue;
+    if (path != P3D_HEAD_RULE && path != P3D_HEAD_FILTER4 && path != P3D_HEAD_FILTER1) return hipErrorInvalidValue;
     const long long total = (long long)a.N * a.D * a.H * a.W;
-    if ((a.C & 3) == 0 && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0) {
+    const bool four_ok = (a.C & 3) == 0 && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0;
+    if (path == P3D_HEAD_FILTER4 && !four_ok) return hipErrorInvalidValue;
+    if (path == P3D_HEAD_FILTER4 || (path == P3D_HEAD_RULE && four_ok)) {
         const int R = 256 / (a.C >> 2);
         long long b = (total + (long long)R * 4 - 1) / ((long long)R * 4);
         if (b > 1024) b = 1024;
@@ -519,6 +534,7 @@ hipError_t p3d_head_bwd_filter(const HeadArgs& a, hipStream_t s) {
         const hipError_t e = p3d_stream_scratch(s, (size_t)(b + groups) * 28 * a.C, (int)(1 + groups), &aa.part, &aa.counter);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(head_bwd_filter4_kernel, dim3((unsigned)b), dim3(256), 0, s, aa);
+        if (done) { done->kernel = P3D_HEAD_FILTER4; done->blocks = (unsigned)b; }
         return hipGetLastError();
     }
     const int lanes = 256 / a.C;
@@ -529,5 +545,6 @@ hipError_t p3d_head_bwd_filter(const HeadArgs& a, hipStream_t s) {
     const hipError_t e = p3d_stream_scratch(s, (size_t)b * 28 * a.C, 1, &aa.part, &aa.counter);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(head_bwd_filter_kernel, dim3((unsigned)b), dim3(256), 0, s, aa);
+    if (done) { done->kernel = P3D_HEAD_FILTER1; done->blocks = (unsigned)b; }
     return hipGetLastError();
 }

@@ -393,6 +393,13 @@ bool launch_siblings(const Ctx& c, std::vector<IgemmArgs>& v) {
     return false;
 }
 
+// tf.train.AdamOptimizer's bias-corrected step size lr * sqrt(1 - b2^t) / (1 - b1^t) for step t (train.py:168), in double from
+// the float hyper-parameters; the network's optimiser step and the test hook p3d_debug_adam both take it from here.
+float adam_step_size(float lr, float b1, float b2, int64_t t_step) {
+    const double t = (double)t_step;
+    return (float)(lr * std::sqrt(1.0 - std::pow((double)b2, t)) / (1.0 - std::pow((double)b1, t)));
+}
+
 // One GroupNorm pass (gn_apply in net_gn.inc, and the test hook p3d_debug_gn_pass): which kernels take it, and their launches.
 // A (sample, group) slab that fits one block goes to the one-launch small-tensor kernels unless the pass drops out; everything
 // else runs statistics -> finalize -> apply forward and reduce -> finalize (+ parameter gradients) -> apply backward.

@@ -1149,6 +1149,91 @@ int p3d_debug_cbam(int device, int N, int D, int H, int W, int C, const float* x
     API_END
 }
 
+// The output head (head() in net_graphs.inc) on raw inputs: forward, input gradient and filter gradient through the launchers the
+// network calls, on their rule or on a forced kernel.
+int p3d_debug_head(int device, int transpose, int N, int D, int H, int W, int C, const float* x, const float* k, const float* bias,
+                   int sigmoid, const float* dlogits, int fwd_path, int filter_path, float* logits, float* pred, float* dx, float* dk,
+                   float* dbias, int* info) {
+    API_BEGIN
+    HIPCHECK(hipSetDevice(device));
+    if (!x || !k || !bias || !dlogits || !logits || !pred || !dx || !dk || !dbias || !info) throw P3dError("null argument");
+    if (N < 1 || D < 1 || H < 1 || W < 1 || C < 1) throw P3dError("head: bad shape");
+    if (!transpose && (fwd_path || filter_path)) throw P3dError("head: the stride-1 head has one kernel per pass");
+    const int up = transpose ? 2 : 1;
+    const int64_t M = (int64_t)N * D * H * W, Mo = M * up * up * up;
+    DevBuf xb(M * C, x), kb(27 * (int64_t)C, k), bb(1, bias), lb(Mo), pb(Mo), dlb(Mo, dlogits), dxb(M * C), dkb(27 * (int64_t)C, dk),
+        dbb(1, dbias);
+    HeadArgs a;         // as head()'s mk builds it
+    memset(&a, 0, sizeof(a));
+    a.x = xb.p; a.N = N; a.D = D; a.H = H; a.W = W; a.C = C;
+    a.k = kb.p; a.bias = bb.p; a.logits = lb.p; a.pred = pb.p; a.sigmoid = sigmoid ? 1 : 0;
+    a.dlogits = dlb.p; a.dx = dxb.p; a.dk = dkb.p; a.dbias = dbb.p;
+    HeadLaunch f{0, 0}, w{0, 0};
+    hipStream_t s = nullptr;
+    if (transpose) {
+        HIPCHECK(p3d_head_fwd(a, s, fwd_path, &f));
+        HIPCHECK(p3d_head_bwd_filter(a, s, filter_path, &w));
+        HIPCHECK(p3d_head_bwd_input(a, s));
+    } else {
+        HIPCHECK(p3d_headc_fwd(a, s, &f));
+        HIPCHECK(p3d_headc_bwd_filter(a, s, &w));
+        HIPCHECK(p3d_headc_bwd_input(a, s));
+    }
+    lb.get(logits, Mo);
+    pb.get(pred, Mo);
+    dxb.get(dx, M * C);
+    dkb.get(dk, 27 * (int64_t)C);
+    dbb.get(dbias, 1);
+    info[0] = f.kernel; info[1] = (int)f.blocks; info[2] = w.kernel; info[3] = (int)w.blocks;
+    API_END
+}
+
+// The loss (run_loss in net_sched.inc) on raw inputs, `offset` elements into the device buffers.
+int p3d_debug_smooth_l1(int device, const float* pred, const float* target, int64_t n, int through_sigmoid, int offset, double* loss,
+                        float* dlogits, int* info) {
+    API_BEGIN
+    HIPCHECK(hipSetDevice(device));
+    if (!pred || !target || !loss || !dlogits || !info) throw P3dError("null argument");
+    if (n < 1 || offset < 0 || offset > 3) throw P3dError("smooth_l1: bad length or offset");
+    DevBuf pb(n + offset), tb(n + offset), db(n + offset), lb(2);
+    HIPCHECK(copy_now(pb.p + offset, pred, (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
+    HIPCHECK(copy_now(tb.p + offset, target, (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
+    HIPCHECK(copy_now(lb.p, loss, sizeof(double), hipMemcpyHostToDevice, nullptr));
+    unsigned done[2] = {0, 0};
+    HIPCHECK(p3d_smooth_l1(pb.p + offset, tb.p + offset, (long)n, reinterpret_cast<double*>(lb.p), db.p + offset,
+                           through_sigmoid ? 1 : 0, nullptr, done));
+    HIPCHECK(hipDeviceSynchronize());
+    HIPCHECK(copy_now(dlogits, db.p + offset, (size_t)n * 4, hipMemcpyDeviceToHost, nullptr));
+    HIPCHECK(copy_now(loss, lb.p, sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    info[0] = (int)done[0]; info[1] = (int)done[1];
+    API_END
+}
+
+// One optimiser launch (adam_range in net_sched.inc) on raw inputs, `offset` elements into the device buffers; the step size
+// for step t comes from adam_step_size, as an argument or (lr_on_device) through device memory as a captured step reads it.
+int p3d_debug_adam(int device, float* p, const float* g, float* m, float* v, int64_t n, int offset, float lr, int64_t t, float b1,
+                   float b2, float eps, int lr_on_device, float* lr_t) {
+    API_BEGIN
+    HIPCHECK(hipSetDevice(device));
+    if (!p || !g || !m || !v || !lr_t) throw P3dError("null argument");
+    if (n < 1 || t < 1 || offset < 0 || offset > 3) throw P3dError("adam: bad length, step or offset");
+    DevBuf pb(n + offset), gb(n + offset), mb(n + offset), vb(n + offset), lrb(1);
+    const float* host[4] = {p, g, m, v};
+    float* dev[4] = {pb.p, gb.p, mb.p, vb.p};
+    for (int q = 0; q < 4; ++q) HIPCHECK(copy_now(dev[q] + offset, host[q], (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
+    const float step = adam_step_size(lr, b1, b2, t);
+    if (lr_on_device) HIPCHECK(p3d_set_step_scalars(nullptr, lrb.p, 0, step, nullptr));
+    // from device memory the argument must not matter: NaN would show in every element if the kernel read it
+    HIPCHECK(p3d_adam(pb.p + offset, gb.p + offset, mb.p + offset, vb.p + offset, (long)n, lr_on_device ? NAN : step,
+                      lr_on_device ? lrb.p : nullptr, b1, b2, eps, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    float* out[3] = {p, m, v};
+    float* outd[3] = {pb.p, mb.p, vb.p};
+    for (int q = 0; q < 3; ++q) HIPCHECK(copy_now(out[q], outd[q] + offset, (size_t)n * 4, hipMemcpyDeviceToHost, nullptr));
+    *lr_t = step;
+    API_END
+}
+
 int p3d_op_conv3d_transpose(int device, const float* x, const int64_t xs[5], const float* kh, const int64_t ks[5],
                             const int s[3], const float* bias, float* y) {
     API_BEGIN

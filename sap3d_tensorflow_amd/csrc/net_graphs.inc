@@ -470,6 +470,9 @@
     // transpose = false: the stride-1 tf.layers.conv3d(x, 1, 3, 1, 'same') of gn/p3d_gn.py:537 instead
     void head(Act* x, Param* k, Param* bias, bool with_sigmoid = true, bool transpose = true) {
         head_sigmoid = with_sigmoid;
+        // the head's kernels address x as dense [rows][C] (HeadArgs has no row stride)
+        if (x->ld != x->C) throw P3dError("head input " + x->name + " has a row stride of " + std::to_string(x->ld) + ", not its " +
+                                          std::to_string(x->C) + " channels");
         const int up = transpose ? 2 : 1;
         logits = new_act("logits", x->N, up * x->D, up * x->H, up * x->W, 1, false);
         pred = new_act("pred", x->N, up * x->D, up * x->H, up * x->W, 1, false);

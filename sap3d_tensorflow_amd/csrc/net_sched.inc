@@ -214,16 +214,11 @@
         if (g_trace) g_trace->lines.push_back("C " + g_trace->sname(comm_stream) + " allreduce " + std::to_string(lo) + " " + std::to_string(hi));
         NCCLCHECK(ncclAllReduce(flat_g + lo, flat_g + lo, (size_t)(hi - lo), ncclFloat, ncclSum, comm, comm_stream));
     }
-    // tf.train.AdamOptimizer's bias-corrected step size lr * sqrt(1 - b2^t) / (1 - b1^t) for step t (train.py:168)
-    float adam_lr_t(int64_t t_step) const {
-        const double t = (double)t_step;
-        return (float)(lr * std::sqrt(1.0 - std::pow((double)b2, t)) / (1.0 - std::pow((double)b1, t)));
-    }
     float cur_lr_t = 0.f;
     int64_t adam_split = 0;              // flat offset below which only the first op's variables live (0: no split)
     hipEvent_t ev_side_early = nullptr, ev_comm_early = nullptr;
     void adam_begin(const Ctx& c) {      // c.lr_dev set: the step size comes from device memory (graph replay), `step` is the caller's
-        cur_lr_t = c.lr_dev ? 0.f : adam_lr_t(++step);
+        cur_lr_t = c.lr_dev ? 0.f : adam_step_size(lr, b1, b2, ++step);
     }
     void adam_range(const Ctx& c, int64_t lo, int64_t hi) {
         if (hi <= lo) return;
@@ -297,7 +292,7 @@
                 return;
             }
         }
-        HIPCHECK(p3d_set_step_scalars(d_seed, d_lr, seed, adam_lr_t(++step), stream));
+        HIPCHECK(p3d_set_step_scalars(d_seed, d_lr, seed, adam_step_size(lr, b1, b2, ++step), stream));
         HIPCHECK(hipGraphLaunch(step_exec, stream));
     }
 

@@ -480,21 +480,28 @@ struct HeadArgs {
     const float* dlogits; float* dx; float* dk; float* dbias;
     float* part; unsigned* counter;        // filter-gradient partials [blocks][28][C] + arrival counter (set by the launcher)
 };
-hipError_t p3d_head_fwd(const HeadArgs& a, hipStream_t s);
+// path: P3D_HEAD_RULE = the launcher's own choice (what the network runs); a forced kernel the shape or alignment does not allow
+// is hipErrorInvalidValue.  done (optional): the kernel that ran and its grid.
+enum { P3D_HEAD_RULE = 0, P3D_HEAD_LANES = 1, P3D_HEAD_GENERIC = 2, P3D_HEAD_FILTER4 = 1, P3D_HEAD_FILTER1 = 2, P3D_HEAD_STRIDE1 = 3 };
+struct HeadLaunch { int kernel; unsigned blocks; };
+hipError_t p3d_head_fwd(const HeadArgs& a, hipStream_t s, int path = P3D_HEAD_RULE, HeadLaunch* done = nullptr);
 hipError_t p3d_head_bwd_input(const HeadArgs& a, hipStream_t s);    // dx written
-hipError_t p3d_head_bwd_filter(const HeadArgs& a, hipStream_t s);   // dk, dbias += (per-block partials folded in block order)
+// dk, dbias += (per-block partials folded in block order; HEAD_FOLD blocks per group, then the groups, on the FILTER4 kernel)
+hipError_t p3d_head_bwd_filter(const HeadArgs& a, hipStream_t s, int path = P3D_HEAD_RULE, HeadLaunch* done = nullptr);
 // the stride-1 variant tf.layers.conv3d(x, 1, 3, 1, 'same') (gn/p3d_gn.py:537): D,H,W are both input and output extents
-hipError_t p3d_headc_fwd(const HeadArgs& a, hipStream_t s);
+hipError_t p3d_headc_fwd(const HeadArgs& a, hipStream_t s, HeadLaunch* done = nullptr);
 hipError_t p3d_headc_bwd_input(const HeadArgs& a, hipStream_t s);
-hipError_t p3d_headc_bwd_filter(const HeadArgs& a, hipStream_t s);
+hipError_t p3d_headc_bwd_filter(const HeadArgs& a, hipStream_t s, HeadLaunch* done = nullptr);
 
 // ---- loss: Smooth-L1 sum (utils/network.py:49-62, train.py:159) fused with sigmoid backward ---
-// loss_out: double accumulator (zeroed by caller).  dlogits = dL/dpred * pred*(1-pred).
+// *loss_out += the loss (a double accumulator; the network zeroes it first).  dlogits = dL/dpred * pred*(1-pred).
+// done (optional): [0] = 1 float4 path (n % 4 == 0, every operand 16-byte aligned), 2 scalar path; [1] = blocks
 hipError_t p3d_smooth_l1(const float* pred, const float* target, long n, double* loss_out,
-                         float* dlogits, int through_sigmoid, hipStream_t s);
+                         float* dlogits, int through_sigmoid, hipStream_t s, unsigned* done = nullptr);
 
 // ---- Adam (tf.train.AdamOptimizer, epsilon-hat form; train.py:168) ------------------------------
-// lr_dev non-null: the bias-corrected step size is read from device memory (captured step graphs), lr_t is ignored
+// lr_dev non-null: the bias-corrected step size is read from device memory (captured step graphs), lr_t is ignored.
+// p, g, m, v must be 16-byte aligned (hipErrorInvalidValue otherwise): the kernel moves four elements at a time.
 hipError_t p3d_adam(float* p, const float* g, float* m, float* v, long n, float lr_t, const float* lr_dev, float b1, float b2,
                     float eps, hipStream_t s);
 // per-step scalars of a captured train step: scal[0..1] = dropout seed (64 bit), scal[2] = Adam's bias-corrected step size

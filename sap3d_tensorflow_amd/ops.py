@@ -207,6 +207,54 @@ def cbam(x, k0, b0, k1, b1, k7, dout, chunks=0, dx=None, pgrads=None, ld=None, p
             dxs[:, C_:])
 
 
+def head(x, k, bias, dlogits, transpose=True, sigmoid=True, dk=None, dbias=None, fwd_path=0, filter_path=0, device=0):
+    """Test hook: the network's output head (include/p3d_hip.h p3d_debug_head) on x [N, D, H, W, C]: transpose = the
+    conv3d_transpose(x, 1, 3, 2) head, else the stride-1 conv3d(x, 1, 3, 1).  k: 27 * C floats ([3, 3, 3, 1, C] or
+    [3, 3, 3, C, 1]); dlogits [N, D', H', W'].  dk, dbias: the gradients to add to (None: zeros).  fwd_path / filter_path:
+    0 = the network's rule, else a forced kernel.  Returns (logits, pred, dx, dk [27, C], dbias (float32), (forward kernel,
+    its blocks, filter-gradient kernel, its blocks))."""
+    x = _f32(x)
+    N, D, H, W, C_ = x.shape
+    up = 2 if transpose else 1
+    oshape = (N, up * D, up * H, up * W)
+    logits, pred = np.empty(oshape, np.float32), np.empty(oshape, np.float32)
+    dx = np.empty(x.shape, np.float32)
+    dkk = np.zeros((27, C_), np.float32) if dk is None else _f32(np.asarray(dk).reshape(27, C_)).copy()
+    db = np.zeros(1, np.float32) if dbias is None else _f32(np.asarray(dbias).reshape(1)).copy()
+    info = (C.c_int * 4)()
+    check(lib().p3d_debug_head(device, 1 if transpose else 0, N, D, H, W, C_, fptr(x), fptr(_f32(np.asarray(k).reshape(27, C_))),
+                               fptr(_f32(np.asarray(bias).reshape(1))), 1 if sigmoid else 0, fptr(_f32(np.asarray(dlogits).reshape(oshape))),
+                               int(fwd_path), int(filter_path), fptr(logits), fptr(pred), fptr(dx), fptr(dkk), fptr(db), info))
+    return logits, pred, dx, dkk, db[0], tuple(info)
+
+
+def smooth_l1(pred, target, through_sigmoid=True, offset=0, loss=0.0, device=0):
+    """Test hook: the network's Smooth-L1 loss (p3d_debug_smooth_l1) on flat float32 pred / target placed `offset` elements
+    into the device buffers.  Returns (loss + the sum, in double; dL/dlogits; (path taken: 1 float4 / 2 scalar, blocks))."""
+    p, t = _f32(pred).ravel(), _f32(target).ravel()
+    if p.size != t.size:
+        raise ValueError("pred and target differ in size")
+    dl = np.empty(p.size, np.float32)
+    acc = C.c_double(float(loss))
+    info = (C.c_int * 2)()
+    check(lib().p3d_debug_smooth_l1(device, fptr(p), fptr(t), p.size, 1 if through_sigmoid else 0, int(offset), C.byref(acc),
+                                    fptr(dl), info))
+    return acc.value, dl, tuple(info)
+
+
+def adam(p, g, m, v, t, lr=1e-4, b1=0.9, b2=0.999, eps=1e-8, lr_on_device=False, offset=0, device=0):
+    """Test hook: one launch of the network's Adam kernel (p3d_debug_adam) on flat float32 arrays, step t (1-based).  Returns
+    (p, m, v after the step, the float32 step size lr * sqrt(1 - b2^t) / (1 - b1^t) it used)."""
+    p, m, v = (_f32(a).ravel().copy() for a in (p, m, v))
+    g = _f32(g).ravel()
+    if not (p.size == g.size == m.size == v.size):
+        raise ValueError("p, g, m, v differ in size")
+    lr_t = C.c_float()
+    check(lib().p3d_debug_adam(device, fptr(p), fptr(g), fptr(m), fptr(v), p.size, int(offset), float(lr), int(t), float(b1),
+                               float(b2), float(eps), 1 if lr_on_device else 0, C.byref(lr_t)))
+    return p, m, v, lr_t.value
+
+
 def stat_parts(xshape, fshape, strides, transpose=False):
     """Host-only test hook: (partials the conv's statistics epilogue writes, room the network reserves for them)."""
     w, c = C.c_int(), C.c_int()
