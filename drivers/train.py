@@ -2,10 +2,12 @@
 """Python-3 counterpart of the reference trainer (/root/reference/train.py) on libp3dhip.
 
 Same flags (train.py:21-45), same step semantics (train.py:217-218: dropout 0.5, training=True, Adam lr,
-Smooth-L1 sum), same periodic eval forward (train.py:225-226) and checkpoint cadence (train.py:266-267).  The
-dataset loaders (dataflow.py, tensorpack, cv2) are out of scope: clips come either from
-`--data clips.npz` (arrays x [N,16,112,112,3] already normalised like dataflow.py:204-208, y [N,16,112,112]; raw uint8
-frames go through sap3d_tensorflow_amd.dataflow.mapf_frames first) or are synthetic with the loader's value law.
+Smooth-L1 sum), same periodic eval forward (train.py:225-226) and checkpoint cadence (train.py:266-267).  One flag is an
+addition the reference does not have: `--loss bce | l1` trains with sigmoid cross-entropy on the head's logits or the L1
+sum instead of Smooth-L1 (P3DSession.set_loss).  The dataset loaders (dataflow.py, tensorpack, cv2) are out of scope
+(SURVEY.md 2.1): clips come either from `--data clips.npz` (arrays x [N,16,112,112,3] already normalised like
+dataflow.py:204-208, y [N,16,112,112]; raw uint8 frames go through sap3d_tensorflow_amd.dataflow.mapf_frames first) or
+are synthetic with the loader's value law.
 Checkpoints are TensorFlow-1.x V2 bundles `model/<info>/p3d_<step>.ckpt.*` with a `checkpoint` state file, keyed by the
 TF variable names of train.py:180-185 (trainables + BN moving statistics): the files the reference's Saver writes and
 restores (sap3d_tensorflow_amd/tf_checkpoint.py); `--pretrain` takes such a directory, a bundle prefix, or an .npz.
@@ -50,6 +52,10 @@ def get_arguments():
     p.add_argument("--data", type=str, default="", help="npz with x, y; empty = synthetic clips")
     p.add_argument("--steps", type=int, default=20, help="steps per epoch when synthetic")
     p.add_argument("--validclips", type=int, default=4, help="validation batches per validation pass when synthetic")
+    # not a reference flag (its flags are train.py:21-45): the loss option of P3DSession.set_loss
+    p.add_argument("--loss", choices=("smooth_l1", "bce", "l1"), default="smooth_l1",
+                   help="[addition, no reference flag] training loss: smooth_l1 (the reference's, train.py:159), bce (sigmoid "
+                        "cross-entropy on the head's logits, summed; no reference counterpart) or l1 (L1 sum, train.py:160)")
     return p.parse_args()
 
 
@@ -118,6 +124,7 @@ def main():
     sess = P3DSession(structure, batch=args.batch, frames=args.videolength, height=args.imagesize[0], width=args.imagesize[1],
                       device=int(args.gpu), seed=0)                                  # graph + global_variables_initializer
     sess.set_adam(args.lr)
+    sess.set_loss(args.loss)
     model_dir = os.path.join("model", args.info)
     os.makedirs(model_dir, exist_ok=True)
     if args.pretrain:

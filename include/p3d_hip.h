@@ -90,12 +90,12 @@ int p3d_forward(p3d_handle* h, const float* x, int training, float dropout_rate,
 int p3d_predict_windows(p3d_handle* h, const float* x, float* pred);
 
 /* ---- sess.run([train_op, loss], {x, y, dropout, training: True})   train.py:217-218.
- *      y [B,T,H,W]; Smooth-L1 SUM loss (utils/network.py:49-62), Adam on every trainable
- *      (train.py:168), BN moving-average updates (train.py:170-172).  With world_size > 1 the
+ *      y [B,T,H,W]; the selected loss, Smooth-L1 by default (SUM, utils/network.py:49-62; p3d_set_loss), Adam on
+ *      every trainable (train.py:168), BN moving-average updates (train.py:170-172).  With world_size > 1 the
  *      gradients are summed across replicas (RCCL) before Adam. */
 int p3d_train_step(p3d_handle* h, const float* x, const float* y, float dropout_rate, uint64_t seed, float* loss);
 
-/* Parity hook: forward (training=True) + loss + backward, no Adam, no moving-stat update.
+/* Parity hook: forward (training=True) + the selected loss (Smooth-L1 by default) + backward, no Adam, no moving-stat update.
  * pred may be NULL.  Gradients are then readable with p3d_get_grad. */
 int p3d_backward(p3d_handle* h, const float* x, const float* y, float dropout_rate, uint64_t seed,
                  float* loss, float* pred);
@@ -122,6 +122,18 @@ int p3d_set_bn_fusion(p3d_handle* h, int enable);
  *   0  (default) per block: 2 where the score matrix has 2^24 elements or more, else 1.
  * Switching to 1 allocates the score buffers of blocks that were built without them. */
 int p3d_set_attention_mode(p3d_handle* h, int mode);
+
+/* The training loss of p3d_train_step, p3d_backward, p3d_train_step_device and p3d_profile_step; every one is a SUM over
+ * the batch's elements, so with world_size > 1 the summed gradients are the global batch's.
+ *   P3D_LOSS_SMOOTH_L1  (default) Smooth-L1, sigma 1 (utils/network.py:49-62, train.py:159): the reference's loss;
+ *   P3D_LOSS_BCE        sigmoid cross-entropy on the head's logits, -sum[y log p + (1-y) log(1-p)] with p = sigmoid(logits),
+ *                       computed as max(z,0) - z y + log1p(exp(-|z|)) (tf.nn.sigmoid_cross_entropy_with_logits); no
+ *                       reference counterpart (BASELINE.json configs[2]).  On the heads without a sigmoid (concat and the
+ *                       GroupNorm nets) the raw output is taken as the logits, the only meaning the loss can have there;
+ *   P3D_LOSS_L1         L1 sum |pred - y| (the reference's commented-out alternative, train.py:160).
+ * Any other kind, or a null handle: -1.  Drops a captured step graph; the next step captures anew. */
+enum { P3D_LOSS_SMOOTH_L1 = 0, P3D_LOSS_BCE = 1, P3D_LOSS_L1 = 2 };
+int p3d_set_loss(p3d_handle* h, int kind);
 
 /* tf.train.AdamOptimizer(lr, beta1, beta2, epsilon) (train.py:168; defaults 1e-4, .9, .999, 1e-8). */
 int p3d_set_adam(p3d_handle* h, float lr, float beta1, float beta2, float eps);
@@ -297,6 +309,11 @@ int p3d_debug_head(int device, int transpose, int N, int D, int H, int W, int C,
  * dlogits = dL/dpred * pred * (1 - pred).  *loss is added to.  info[2] = path taken (1 float4, 2 scalar), blocks. */
 int p3d_debug_smooth_l1(int device, const float* pred, const float* target, int64_t n, int through_sigmoid, int offset, double* loss,
                         float* dlogits, int* info);
+/* Test hook: the loss of kind (P3D_LOSS_*) and dL/dlogits as the network launches it, on logits, pred (sigmoid(logits) when
+ * through_sigmoid, else the logits again) and target placed as p3d_debug_smooth_l1 places them, with its `info`; kind
+ * P3D_LOSS_SMOOTH_L1 is p3d_debug_smooth_l1 (logits unused).  *loss is added to. */
+int p3d_debug_loss(int device, int kind, const float* logits, const float* pred, const float* target, int64_t n, int through_sigmoid,
+                   int offset, double* loss, float* dlogits, int* info);
 /* Test hook: one Adam launch (p3d_adam, as the network's optimiser step launches it) on n elements placed `offset` elements
  * into the device buffers (p3d_adam refuses a base that is not 16-byte aligned).  p, m, v are updated in place from g with
  * the bias-corrected step size of step t (the network's adam_step_size), passed as an argument or, when lr_on_device, through

@@ -1,5 +1,5 @@
 // HBM-bound passes of the P3D path on gfx950: BatchNorm finalize / fused normalise+ReLU+add
-// passes and their backward, SAME max-pooling, Smooth-L1 loss, Adam.  All are float4-vectorised
+// passes and their backward, SAME max-pooling, Smooth-L1 loss and the other loss options, Adam.  All are float4-vectorised
 // over the channel axis of NDHWC rows (C % 4 == 0) with explicit row strides so they operate in
 // place on channel slices of the decoder's concat buffers (tf.concat at reference
 // p3d.py:203,208 never materialises).
@@ -509,6 +509,78 @@ __global__ __launch_bounds__(256) void smooth_l1_kernel(const float* pred, const
     if (threadIdx.x == 0) *loss_out += wsum[0] + wsum[1] + wsum[2] + wsum[3];
 }
 
+// The loss options beside Smooth-L1 (p3d_set_loss), with smooth_l1_kernel's lanes, grid and block-order fold.  z = logits,
+// p = pred (sigmoid(z) on a sigmoid head, z on a raw one), t = target.
+//   KIND 1, sigmoid cross-entropy on logits (tf.nn.sigmoid_cross_entropy_with_logits): max(z,0) - z t + log1p(exp(-|z|)),
+//     finite for every finite z; dL/dz = sigmoid(z) - t, where sigmoid(z) is the stored pred on a sigmoid head (the loss
+//     and the saliency map agree bit for bit) and the head's own 1/(1+expf(-z)) (head.hip) on a raw one.  Reads z, t and,
+//     on a sigmoid head, p.
+//   KIND 2, L1 sum (reference train.py:160): |p - t|; dL/dp = sign(p - t) (0 at 0, tf's Abs gradient), times p (1 - p)
+//     through the sigmoid.  Reads p and t.
+template <int KIND>
+__device__ __forceinline__ float loss_term(float z, float p, float t, int through_sigmoid, float& g) {
+    if (KIND == 1) {
+        g = (through_sigmoid ? p : 1.f / (1.f + expf(-z))) - t;
+        return fmaxf(z, 0.f) - z * t + log1pf(expf(-fabsf(z)));
+    }
+    const float d = p - t;
+    g = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+    if (through_sigmoid) g *= p * (1.f - p);
+    return fabsf(d);
+}
+
+template <int KIND>
+__device__ __forceinline__ void loss_body(const float* logits, const float* pred, const float* target, long long n,
+                                          double* loss_out, float* dl, int through_sigmoid, int vec4, double* part,
+                                          unsigned* counter) {
+    __shared__ double wsum[4];
+    __shared__ int last_flag;
+    double acc = 0.0;
+    const bool need_z = KIND == 1, need_p = KIND == 2 || through_sigmoid;
+    const long long gtid = (long long)blockIdx.x * blockDim.x + threadIdx.x, gsz = (long long)gridDim.x * blockDim.x;
+    if (vec4) {
+        const long long n4 = n >> 2;
+        for (long long i = gtid; i < n4; i += gsz) {
+            const float4 z = need_z ? ld4(logits + 4 * i) : f4(0.f), p = need_p ? ld4(pred + 4 * i) : f4(0.f);
+            const float4 t = ld4(target + 4 * i);
+            float4 g;
+            acc += loss_term<KIND>(z.x, p.x, t.x, through_sigmoid, g.x);
+            acc += loss_term<KIND>(z.y, p.y, t.y, through_sigmoid, g.y);
+            acc += loss_term<KIND>(z.z, p.z, t.z, through_sigmoid, g.z);
+            acc += loss_term<KIND>(z.w, p.w, t.w, through_sigmoid, g.w);
+            st4(dl + 4 * i, g);
+        }
+    } else {
+        for (long long i = gtid; i < n; i += gsz)
+            acc += loss_term<KIND>(need_z ? logits[i] : 0.f, need_p ? pred[i] : 0.f, target[i], through_sigmoid, dl[i]);
+    }
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) p3d_store_wt(part, blockIdx.x, wsum[0] + wsum[1] + wsum[2] + wsum[3]);
+    if (!p3d_last_block_wt(counter, gridDim.x, &last_flag)) return;
+    double t = 0.0;
+    for (unsigned b = threadIdx.x; b < gridDim.x; b += 256) t += part[b];
+    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = t;
+    __syncthreads();
+    if (threadIdx.x == 0) *loss_out += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+// one kernel per kind: the launch lists and the profiles name the loss
+__global__ __launch_bounds__(256) void sigmoid_ce_kernel(const float* logits, const float* pred, const float* target, long long n,
+                                                         double* loss_out, float* dl, int through_sigmoid, int vec4, double* part,
+                                                         unsigned* counter) {
+    P3D_CHAIN_PRIO();
+    loss_body<1>(logits, pred, target, n, loss_out, dl, through_sigmoid, vec4, part, counter);
+}
+__global__ __launch_bounds__(256) void l1_loss_kernel(const float* logits, const float* pred, const float* target, long long n,
+                                                      double* loss_out, float* dl, int through_sigmoid, int vec4, double* part,
+                                                      unsigned* counter) {
+    P3D_CHAIN_PRIO();
+    loss_body<2>(logits, pred, target, n, loss_out, dl, through_sigmoid, vec4, part, counter);
+}
+
 __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, float* m, float* v, long long n4,
                                                    long long n, float lr_arg, const float* lr_dev, float b1, float b2, float eps) {
     const float lr_t = lr_dev ? *lr_dev : lr_arg;
@@ -935,6 +1007,28 @@ hipError_t p3d_smooth_l1(const float* pred, const float* target, long n, double*
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(smooth_l1_kernel, dim3(g), dim3(256), 0, s, pred, target, (long long)n, loss_out, dlogits, through_sigmoid,
                        vec4, reinterpret_cast<double*>(slab), cnt);
+    if (done) { done[0] = vec4 ? 1 : 2; done[1] = g; }
+    return hipGetLastError();
+}
+
+hipError_t p3d_loss(int kind, const float* logits, const float* pred, const float* target, long n, double* loss_out,
+                    float* dlogits, int through_sigmoid, hipStream_t s, unsigned* done) {
+    if (n < 1 || (kind != 1 && kind != 2)) return hipErrorInvalidValue;
+    const unsigned g = grid_for(n, 256, 1024);
+    const int vec4 = (n & 3) == 0 &&
+                     ((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(target) |
+                       reinterpret_cast<uintptr_t>(dlogits)) & 15) == 0;
+    float* slab = nullptr; unsigned* cnt = nullptr;
+    const hipError_t e = p3d_stream_scratch(s, 2 * (size_t)g, 1, &slab, &cnt);
+    if (e != hipSuccess) return e;
+    const int ts = through_sigmoid ? 1 : 0;
+    double* part = reinterpret_cast<double*>(slab);
+    if (kind == 1)
+        hipLaunchKernelGGL(sigmoid_ce_kernel, dim3(g), dim3(256), 0, s, logits, pred, target, (long long)n, loss_out, dlogits, ts, vec4,
+                           part, cnt);
+    else
+        hipLaunchKernelGGL(l1_loss_kernel, dim3(g), dim3(256), 0, s, logits, pred, target, (long long)n, loss_out, dlogits, ts, vec4,
+                           part, cnt);
     if (done) { done[0] = vec4 ? 1 : 2; done[1] = g; }
     return hipGetLastError();
 }

@@ -815,6 +815,7 @@ struct p3d_handle {
     float* d_y = nullptr;          // target
     float* d_dlogits = nullptr;
     double* d_loss = nullptr;
+    int loss_kind = P3D_LOSS_SMOOTH_L1;      // p3d_set_loss
     float lr = 1e-4f, b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
     int64_t step = 0;
 

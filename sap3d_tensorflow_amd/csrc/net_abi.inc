@@ -306,6 +306,18 @@ int p3d_set_attention_mode(p3d_handle* h, int mode) {
     API_END
 }
 
+int p3d_set_loss(p3d_handle* h, int kind) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    if (kind != P3D_LOSS_SMOOTH_L1 && kind != P3D_LOSS_BCE && kind != P3D_LOSS_L1)
+        throw P3dError("loss kind is 0 (Smooth-L1), 1 (sigmoid cross-entropy on the logits) or 2 (L1 sum), not " +
+                       std::to_string(kind));
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->loss_kind = kind;
+    h->drop_step_graph();      // a captured step names the loss kernel it was captured with
+    API_END
+}
+
 int p3d_set_bn_fusion(p3d_handle* h, int enable) {
     API_BEGIN
     if (!h) throw P3dError("null handle");
@@ -1202,6 +1214,30 @@ int p3d_debug_smooth_l1(int device, const float* pred, const float* target, int6
     unsigned done[2] = {0, 0};
     HIPCHECK(p3d_smooth_l1(pb.p + offset, tb.p + offset, (long)n, reinterpret_cast<double*>(lb.p), db.p + offset,
                            through_sigmoid ? 1 : 0, nullptr, done));
+    HIPCHECK(hipDeviceSynchronize());
+    HIPCHECK(copy_now(dlogits, db.p + offset, (size_t)n * 4, hipMemcpyDeviceToHost, nullptr));
+    HIPCHECK(copy_now(loss, lb.p, sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    info[0] = (int)done[0]; info[1] = (int)done[1];
+    API_END
+}
+
+// The selectable loss (run_loss / run_loss_option in net_sched.inc) on raw inputs, placed as p3d_debug_smooth_l1 places them.
+int p3d_debug_loss(int device, int kind, const float* logits, const float* pred, const float* target, int64_t n, int through_sigmoid,
+                   int offset, double* loss, float* dlogits, int* info) {
+    API_BEGIN
+    if (kind == P3D_LOSS_SMOOTH_L1) return p3d_debug_smooth_l1(device, pred, target, n, through_sigmoid, offset, loss, dlogits, info);
+    if (kind != P3D_LOSS_BCE && kind != P3D_LOSS_L1) throw P3dError("loss: kind is 0, 1 or 2");
+    HIPCHECK(hipSetDevice(device));
+    if (!logits || !pred || !target || !loss || !dlogits || !info) throw P3dError("null argument");
+    if (n < 1 || offset < 0 || offset > 3) throw P3dError("loss: bad length or offset");
+    DevBuf zb(n + offset), pb(n + offset), tb(n + offset), db(n + offset), lb(2);
+    HIPCHECK(copy_now(zb.p + offset, logits, (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
+    HIPCHECK(copy_now(pb.p + offset, pred, (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
+    HIPCHECK(copy_now(tb.p + offset, target, (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
+    HIPCHECK(copy_now(lb.p, loss, sizeof(double), hipMemcpyHostToDevice, nullptr));
+    unsigned done[2] = {0, 0};
+    HIPCHECK(p3d_loss(kind, zb.p + offset, pb.p + offset, tb.p + offset, (long)n, reinterpret_cast<double*>(lb.p), db.p + offset,
+                      through_sigmoid ? 1 : 0, nullptr, done));
     HIPCHECK(hipDeviceSynchronize());
     HIPCHECK(copy_now(dlogits, db.p + offset, (size_t)n * 4, hipMemcpyDeviceToHost, nullptr));
     HIPCHECK(copy_now(loss, lb.p, sizeof(double), hipMemcpyDeviceToHost, nullptr));

@@ -30,7 +30,21 @@
     }
     void run_loss(const Ctx& c) {
         HIPCHECK(fill_async(d_loss, 0, sizeof(double), c.s, "loss"));
+        if (loss_kind != P3D_LOSS_SMOOTH_L1) return run_loss_option(c);
         launch(c, "smooth_l1_kernel", 0, 12.0 * pred->rows(), [&]() { return p3d_smooth_l1(pred->p, d_y, pred->rows(), d_loss, d_dlogits, head_sigmoid ? 1 : 0, c.s); });
+    }
+    // p3d_set_loss's options, into the same d_loss / d_dlogits.  Each rank's loss is a sum over its own clips, so under data
+    // parallelism the summed gradients are still the global batch's, as for Smooth-L1.  Per element: BCE reads the logits, the
+    // target and (sigmoid head) pred and writes dlogits, ~8 operations (+3 for the sigmoid of a raw head); L1 reads pred and
+    // the target, 3 operations (+3 through the sigmoid).
+    void run_loss_option(const Ctx& c) {
+        const double rows = (double)pred->rows();
+        const int ts = head_sigmoid ? 1 : 0;
+        const bool bce = loss_kind == P3D_LOSS_BCE;
+        const double flops = rows * (bce ? (ts ? 8.0 : 11.0) : (ts ? 6.0 : 3.0));
+        const double bytes = rows * (bce && ts ? 16.0 : 12.0);
+        launch(c, bce ? "sigmoid_ce_kernel" : "l1_loss_kernel", flops, bytes,
+               [&]() { return p3d_loss(loss_kind, logits->p, pred->p, d_y, pred->rows(), d_loss, d_dlogits, ts, c.s); });
     }
     // with_adam: the optimiser step is part of the call and split in two -- every variable but the first op's (and those its
     // backward reads, adam_split) is updated while that op's filter gradient (the stem's: the last launch of the pass, alone on

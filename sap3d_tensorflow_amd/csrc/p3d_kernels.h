@@ -498,6 +498,11 @@ hipError_t p3d_headc_bwd_filter(const HeadArgs& a, hipStream_t s, HeadLaunch* do
 // done (optional): [0] = 1 float4 path (n % 4 == 0, every operand 16-byte aligned), 2 scalar path; [1] = blocks
 hipError_t p3d_smooth_l1(const float* pred, const float* target, long n, double* loss_out,
                          float* dlogits, int through_sigmoid, hipStream_t s, unsigned* done = nullptr);
+// The loss options beside it (p3d_set_loss; same lanes, grid, fold and `done`): kind 1 sigmoid cross-entropy on the logits,
+// dlogits = sigmoid(z) - target (the stored pred when through_sigmoid); kind 2 L1 sum, dlogits = sign(pred - target), times
+// pred*(1-pred) when through_sigmoid.  Any other kind: hipErrorInvalidValue.
+hipError_t p3d_loss(int kind, const float* logits, const float* pred, const float* target, long n, double* loss_out,
+                    float* dlogits, int through_sigmoid, hipStream_t s, unsigned* done = nullptr);
 
 // ---- Adam (tf.train.AdamOptimizer, epsilon-hat form; train.py:168) ------------------------------
 // lr_dev non-null: the bias-corrected step size is read from device memory (captured step graphs), lr_t is ignored.

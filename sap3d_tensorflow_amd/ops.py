@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import check, fptr, lib
+from ._lib import LOSSES, check, fptr, lib
 
 
 def _f32(a):
@@ -239,6 +239,23 @@ def smooth_l1(pred, target, through_sigmoid=True, offset=0, loss=0.0, device=0):
     info = (C.c_int * 2)()
     check(lib().p3d_debug_smooth_l1(device, fptr(p), fptr(t), p.size, 1 if through_sigmoid else 0, int(offset), C.byref(acc),
                                     fptr(dl), info))
+    return acc.value, dl, tuple(info)
+
+
+def loss(kind, logits, pred, target, through_sigmoid=True, offset=0, loss=0.0, device=0):
+    """Test hook: the network's selectable loss (p3d_debug_loss) of kind "smooth_l1" | "bce" | "l1" (or its P3D_LOSS_*
+    number) on flat float32 logits / pred / target placed `offset` elements into the device buffers; pred is sigmoid(logits)
+    when through_sigmoid, else the logits again.  Returns (loss + the sum, in double; dL/dlogits; (path taken: 1 float4 /
+    2 scalar, blocks))."""
+    k = LOSSES[kind] if isinstance(kind, str) else int(kind)
+    z, p, t = _f32(logits).ravel(), _f32(pred).ravel(), _f32(target).ravel()
+    if not (z.size == p.size == t.size):
+        raise ValueError("logits, pred and target differ in size")
+    dl = np.empty(p.size, np.float32)
+    acc = C.c_double(float(loss))
+    info = (C.c_int * 2)()
+    check(lib().p3d_debug_loss(device, k, fptr(z), fptr(p), fptr(t), p.size, 1 if through_sigmoid else 0, int(offset),
+                               C.byref(acc), fptr(dl), info))
     return acc.value, dl, tuple(info)
 
 

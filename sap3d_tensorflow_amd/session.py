@@ -223,6 +223,14 @@ class P3DSession:
         chip, "auto" picks per block by the size of the score matrix."""
         check(lib().p3d_set_attention_mode(self._h, {"auto": 0, "gemm": 1, "flash": 2}[mode]))
 
+    def set_loss(self, name="smooth_l1"):
+        """The training loss of train_step / backward / train_step_device / profile_step: "smooth_l1" (the reference's,
+        train.py:159; default), "bce" (sigmoid cross-entropy on the head's logits, summed; no reference counterpart -- on the
+        heads without a sigmoid the raw output is taken as the logits) or "l1" (L1 sum, the reference's train.py:160)."""
+        if name not in _lib.LOSSES:
+            raise ValueError("loss %r: have %s" % (name, sorted(_lib.LOSSES)))
+        check(lib().p3d_set_loss(self._h, _lib.LOSSES[name]))
+
     def predict_windows(self, x):
         """B windows of gen_pred.py:100-168 at once: row k equals forward(x[k:k+1], training=False) of a batch-1
         session, i.e. every batch-statistics BN normalises each clip by its own statistics."""
