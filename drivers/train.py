@@ -2,9 +2,11 @@
 """Python-3 counterpart of the reference trainer (/root/reference/train.py) on libp3dhip.
 
 Same flags (train.py:21-45), same step semantics (train.py:217-218: dropout 0.5, training=True, Adam lr,
-Smooth-L1 sum), same periodic eval forward (train.py:225-226) and checkpoint cadence (train.py:266-267).  One flag is an
-addition the reference does not have: `--loss bce | l1` trains with sigmoid cross-entropy on the head's logits or the L1
-sum instead of Smooth-L1 (P3DSession.set_loss).  The dataset loaders (dataflow.py, tensorpack, cv2) are out of scope
+Smooth-L1 sum), same periodic eval forward (train.py:225-226) and checkpoint cadence (train.py:266-267).  Two flags are
+additions the reference does not have: `--loss bce | l1` trains with sigmoid cross-entropy on the head's logits or the L1
+sum instead of Smooth-L1 (P3DSession.set_loss); `--regularization weightdecay | l2 | both` adds the weight-decay and L2
+terms the reference builds and leaves commented out of its loss (train.py:161, gn/train_p3d_gn_dataset.py:188-189;
+P3DSession.set_regularization).  The dataset loaders (dataflow.py, tensorpack, cv2) are out of scope
 (SURVEY.md 2.1): clips come either from `--data clips.npz` (arrays x [N,16,112,112,3] already normalised like
 dataflow.py:204-208, y [N,16,112,112]; raw uint8 frames go through sap3d_tensorflow_amd.dataflow.mapf_frames first) or
 are synthetic with the loader's value law.
@@ -56,6 +58,15 @@ def get_arguments():
     p.add_argument("--loss", choices=("smooth_l1", "bce", "l1"), default="smooth_l1",
                    help="[addition, no reference flag] training loss: smooth_l1 (the reference's, train.py:159), bce (sigmoid "
                         "cross-entropy on the head's logits, summed; no reference counterpart) or l1 (L1 sum, train.py:160)")
+    # not a reference flag either: the regularisation option of P3DSession.set_regularization
+    p.add_argument("--regularization", choices=("none", "weightdecay", "l2", "both"), default="none",
+                   help="[addition, no reference flag] terms added to the loss: weightdecay (mean of wd * l2_loss over the "
+                        "get_conv_weight kernels, the reference's commented-out train.py:161 and gn/train_p3d_gn_dataset.py:188), "
+                        "l2 (mean of 0.0005 * l2_loss over the kernel_regularizer kernels, gn/train_p3d_gn_dataset.py:189; "
+                        "--net P3D_DECODER only) or both")
+    p.add_argument("--wd", type=float, default=0.0,
+                   help="[addition] weight-decay scale; 0 = the reference's (0.001 BatchNorm nets, 0.0005 GroupNorm nets)")
+    p.add_argument("--l2", type=float, default=0.0, help="[addition] l2 scale; 0 = the reference's 0.0005")
     return p.parse_args()
 
 
@@ -110,7 +121,7 @@ def validate(sess, args, step):
 
 def main():
     args = get_arguments()
-    from sap3d_tensorflow_amd import P3DSession
+    from sap3d_tensorflow_amd import P3dError, P3DSession
     gn_nets = {"P3D": "gn_p3d", "P3D_CONCAT": "gn_p3d_concat", "P3D_DECODER": "gn_p3d_decoder"}     # gn/train_p3d_gn_dataset.py:169-180
     gn = args.normalization.lower() == "gn"
     if gn and args.net not in gn_nets:
@@ -125,6 +136,12 @@ def main():
                       device=int(args.gpu), seed=0)                                  # graph + global_variables_initializer
     sess.set_adam(args.lr)
     sess.set_loss(args.loss)
+    terms = {"none": (), "weightdecay": ("weightdecay",), "l2": ("l2",), "both": ("weightdecay", "l2")}[args.regularization]
+    try:
+        sess.set_regularization(terms, wd=args.wd, l2=args.l2)
+    except P3dError as e:
+        sess.close()
+        raise SystemExit("--regularization %s: %s" % (args.regularization, e))
     model_dir = os.path.join("model", args.info)
     os.makedirs(model_dir, exist_ok=True)
     if args.pretrain:

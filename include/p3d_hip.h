@@ -135,6 +135,26 @@ int p3d_set_attention_mode(p3d_handle* h, int mode);
 enum { P3D_LOSS_SMOOTH_L1 = 0, P3D_LOSS_BCE = 1, P3D_LOSS_L1 = 2 };
 int p3d_set_loss(p3d_handle* h, int kind);
 
+/* Regularisation terms added to the loss of p3d_train_step, p3d_backward, p3d_train_step_device and p3d_profile_step: the two
+ * collections the reference builds and leaves out of its loss (train.py:161, gn/train_p3d_gn_dataset.py:188-189), as opt-in.
+ *   P3D_REG_WEIGHT_DECAY  wd_loss = (1/K) sum_k wd * 0.5 * sum(w_k^2) over the K kernels get_conv_weight makes with wd != 0
+ *                         (firstconv1 and the bottleneck kernels; p3d.py:10-16, gn/p3d_gn.py:54-60);
+ *   P3D_REG_L2            l2_loss = (1/K2) sum_j l2 * 0.5 * sum(w_j^2) over the kernel_regularizer kernels of scope P3D (the
+ *                         decoder-block GN head's layer kernels and P3D/results/kernel; gn/p3d_gn.py:11-21,538).  A net
+ *                         without any: -1, nothing changes.
+ * terms is a bitmask of the two (0: off, the default).  A scale <= 0 selects the reference's: wd 0.001 on the BatchNorm nets,
+ * 0.0005 on the GroupNorm nets; l2 0.0005.  Each variable's coefficient wd/K (l2/K2) is formed in double and rounded to float32
+ * once.  The gradient c*w is added to the variable's gradient after its all-reduce, identically on every rank, and the term
+ * is taken on the parameters before the step's update.  Each rank's loss is its data loss plus the whole term
+ * (p3d_last_regularization gives the term alone).  Drops a captured step graph. */
+enum { P3D_REG_WEIGHT_DECAY = 1, P3D_REG_L2 = 2 };
+int p3d_set_regularization(p3d_handle* h, int terms, float wd, float l2);
+/* The regularisation term of the last step or backward, in double (0 when off). */
+int p3d_last_regularization(p3d_handle* h, double* term);
+/* The float32 coefficients c the library applies to the trainable variable `name` under the current settings (0 for a term
+ * that is off or that does not cover the variable): its gradient gains (c_wd + c_l2) * w. */
+int p3d_param_regularization(p3d_handle* h, const char* name, float* c_wd, float* c_l2);
+
 /* tf.train.AdamOptimizer(lr, beta1, beta2, epsilon) (train.py:168; defaults 1e-4, .9, .999, 1e-8). */
 int p3d_set_adam(p3d_handle* h, float lr, float beta1, float beta2, float eps);
 
@@ -318,6 +338,14 @@ int p3d_debug_loss(int device, int kind, const float* logits, const float* pred,
  * into the device buffers (p3d_adam refuses a base that is not 16-byte aligned).  p, m, v are updated in place from g with
  * the bias-corrected step size of step t (the network's adam_step_size), passed as an argument or, when lr_on_device, through
  * device memory as a captured train step passes it.  *lr_t = that step size. */
+/* Test hook: one launch of the regularised optimiser step (p3d_adam_decay, as adam_range launches it when a term is on) on n
+ * elements placed `offset` (0..3) elements into the device buffers.  Tiles k = 0..ntile-1 cover [0, n) in order:
+ * [tile_off[k], tile_off[k] + tile_len[k]) with coefficient tile_c[k].  g becomes g + c*p; with update, p, m, v take the Adam
+ * step of step t on it (step size as p3d_debug_adam: argument or device memory), without it they stay as they are.
+ * *term = sum_k 0.5 * c_k * sum(p^2) over tile k, in double, before the update.  *lr_t = the step size. */
+int p3d_debug_adam_decay(int device, float* p, float* g, float* m, float* v, int64_t n, int offset, const int64_t* tile_off,
+                         const int64_t* tile_len, const float* tile_c, int ntile, float lr, int64_t t, float b1, float b2, float eps,
+                         int lr_on_device, int update, double* term, float* lr_t);
 int p3d_debug_adam(int device, float* p, const float* g, float* m, float* v, int64_t n, int offset, float lr, int64_t t, float b1,
                    float b2, float eps, int lr_on_device, float* lr_t);
 int p3d_debug_stat_parts(const int64_t xshape[5], const int64_t wshape[5], const int s[3], int transpose, int* written, int* cap);

@@ -11,6 +11,8 @@ LIB_PATH = os.environ.get("P3D_LIB") or os.path.join(_HERE, "libp3dhip.so")
 P3D_COMM_ID_BYTES = 128
 # p3d_set_loss kinds (include/p3d_hip.h P3D_LOSS_*)
 LOSSES = {"smooth_l1": 0, "bce": 1, "l1": 2}
+# p3d_set_regularization terms (include/p3d_hip.h P3D_REG_*)
+REGULARIZATION = {"weightdecay": 1, "l2": 2}
 
 
 class P3dConfig(C.Structure):
@@ -55,6 +57,9 @@ SIGNATURES = {
     "p3d_set_bn_fusion": (C.c_int, [C.c_void_p, C.c_int]),
     "p3d_set_attention_mode": (C.c_int, [C.c_void_p, C.c_int]),
     "p3d_set_loss": (C.c_int, [C.c_void_p, C.c_int]),
+    "p3d_set_regularization": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float]),
+    "p3d_last_regularization": (C.c_int, [C.c_void_p, _dp]),
+    "p3d_param_regularization": (C.c_int, [C.c_void_p, C.c_char_p, _fp, _fp]),
     "p3d_debug_dirty_counters": (C.c_int64, []),
     "p3d_debug_force_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "p3d_debug_schedule": (C.c_int, [C.c_void_p, C.c_float, C.c_uint64, C.c_char_p, C.c_int64, _i64p]),
@@ -94,6 +99,8 @@ SIGNATURES = {
                                  C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _ip]),
     "p3d_debug_smooth_l1": (C.c_int, [C.c_int, _fp, _fp, C.c_int64, C.c_int, C.c_int, _dp, _fp, _ip]),
     "p3d_debug_loss": (C.c_int, [C.c_int, C.c_int, _fp, _fp, _fp, C.c_int64, C.c_int, C.c_int, _dp, _fp, _ip]),
+    "p3d_debug_adam_decay": (C.c_int, [C.c_int, _fp, _fp, _fp, _fp, C.c_int64, C.c_int, _i64p, _i64p, _fp, C.c_int, C.c_float,
+                                       C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, _dp, _fp]),
     "p3d_debug_adam": (C.c_int, [C.c_int, _fp, _fp, _fp, _fp, C.c_int64, C.c_int, C.c_float, C.c_int64, C.c_float, C.c_float,
                                  C.c_float, C.c_int, _fp]),
     "p3d_debug_stat_parts": (C.c_int, [_i64p, _i64p, _ip, C.c_int, _ip, _ip]),

@@ -612,6 +612,105 @@ __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, flo
     }
 }
 
+// Regularisation (p3d_adam_decay).  Every rounding is explicit, so that a numpy float32 replay is bit-exact: contraction is
+// off and the two fused multiply-adds are fmaf.  adam_kernel's own arithmetic, as this compiler contracts it: on a whole
+// float4 group m and v are single fmas over the rounded (1-b) g terms; on the scalar tail of a range nothing is fused.
+__device__ __forceinline__ void adam_elem(float& p, float& m, float& v, float g, float lr_t, float b1, float b2, float eps,
+                                          bool whole) {
+#pragma clang fp contract(off)
+    const float a1 = 1.f - b1, a2 = 1.f - b2;
+    if (whole) {
+        m = fmaf(b1, m, a1 * g);
+        v = fmaf(b2, v, (a2 * g) * g);
+    } else {
+        m = b1 * m + a1 * g;
+        v = b2 * v + (a2 * g) * g;
+    }
+    p = p - (lr_t * m) / (sqrtf(v) + eps);
+}
+
+// One block per tile of uniform coefficient c: g' = g + c p (written back where c != 0), Adam on g' when UPDATE, and the tile's
+// 0.5 c sum(p^2) in double from the parameters before the update.  Elements of a 4-group shared with the neighbouring tile
+// (variables whose length is not a multiple of 4 end mid-group) go one by one, with the arithmetic of the group they are in.
+template <bool UPDATE>
+__device__ __forceinline__ void decay_body(float* p, float* g, float* m, float* v, long long n, const P3dRegTile* tiles,
+                                           long long tile_base, float lr_arg, const float* lr_dev, float b1, float b2, float eps,
+                                           double* part, const double* fold_part, int nfold, unsigned* counter, double* term) {
+#pragma clang fp contract(off)
+    __shared__ double wsum[4];
+    __shared__ int last_flag;
+    const P3dRegTile t = tiles[blockIdx.x];
+    const long long a = t.off - tile_base, b = a + t.len;
+    const float c = t.c;
+    const float lr_t = UPDATE ? (lr_dev ? *lr_dev : lr_arg) : 0.f;
+    double acc = 0.0;
+    if (UPDATE || c != 0.f) {
+        const long long a4 = (a + 3) & ~3LL, b4 = max(a4, b & ~3LL);
+        for (long long e = a4 + 4 * (long long)threadIdx.x; e < b4; e += 4 * 256) {
+            const float4 gg = ld4(g + e), pp = ld4(p + e);
+            float gs[4] = {gg.x, gg.y, gg.z, gg.w}, ps[4] = {pp.x, pp.y, pp.z, pp.w};
+            if (c != 0.f) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    acc += (double)ps[q] * (double)ps[q];
+                    gs[q] = gs[q] + c * ps[q];
+                }
+                st4(g + e, make_float4(gs[0], gs[1], gs[2], gs[3]));
+            }
+            if (UPDATE) {
+                const float4 mm = ld4(m + e), vv = ld4(v + e);
+                float ms[4] = {mm.x, mm.y, mm.z, mm.w}, vs[4] = {vv.x, vv.y, vv.z, vv.w};
+#pragma unroll
+                for (int q = 0; q < 4; ++q) adam_elem(ps[q], ms[q], vs[q], gs[q], lr_t, b1, b2, eps, true);
+                st4(m + e, make_float4(ms[0], ms[1], ms[2], ms[3]));
+                st4(v + e, make_float4(vs[0], vs[1], vs[2], vs[3]));
+                st4(p + e, make_float4(ps[0], ps[1], ps[2], ps[3]));
+            }
+        }
+        if (threadIdx.x < 8) {      // threads 0-3: [a, a4), the head; 4-7: [b4, b), the tail (each under 4 elements)
+            const long long e = threadIdx.x < 4 ? a + threadIdx.x : b4 + threadIdx.x - 4;
+            if (threadIdx.x < 4 ? e < min(a4, b) : e < b) {
+                float pe = p[e], ge = g[e];
+                if (c != 0.f) {
+                    acc += (double)pe * (double)pe;
+                    ge = ge + c * pe;
+                    g[e] = ge;
+                }
+                if (UPDATE) {
+                    float me = m[e], ve = v[e];
+                    adam_elem(pe, me, ve, ge, lr_t, b1, b2, eps, (e & ~3LL) + 3 < n);
+                    m[e] = me; v[e] = ve; p[e] = pe;
+                }
+            }
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) p3d_store_wt(part, blockIdx.x, 0.5 * (double)c * (wsum[0] + wsum[1] + wsum[2] + wsum[3]));
+    if (nfold <= 0) return;
+    if (!p3d_last_block_wt(counter, gridDim.x, &last_flag)) return;
+    double s = 0.0;
+    for (int k = threadIdx.x; k < nfold; k += 256) s += fold_part[k];
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) *term = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+// one kernel per mode: the launch lists and the profiles name them
+__global__ __launch_bounds__(256) void adam_decay_kernel(float* p, float* g, float* m, float* v, long long n, const P3dRegTile* tiles,
+                                                         long long tile_base, float lr_arg, const float* lr_dev, float b1, float b2,
+                                                         float eps, double* part, const double* fold_part, int nfold,
+                                                         unsigned* counter, double* term) {
+    decay_body<true>(p, g, m, v, n, tiles, tile_base, lr_arg, lr_dev, b1, b2, eps, part, fold_part, nfold, counter, term);
+}
+__global__ __launch_bounds__(256) void decay_grad_kernel(float* p, float* g, long long n, const P3dRegTile* tiles, long long tile_base,
+                                                         double* part, const double* fold_part, int nfold, unsigned* counter,
+                                                         double* term) {
+    decay_body<false>(p, g, nullptr, nullptr, n, tiles, tile_base, 0.f, nullptr, 0.f, 0.f, 0.f, part, fold_part, nfold, counter, term);
+}
+
 __global__ __launch_bounds__(256) void add_inplace_kernel(float* dst, int lddst, const float* src, int ldsrc, long long M, int C, int copy) {
     const int c4n = C >> 2;
     const long long total = M * c4n;
@@ -1030,6 +1129,22 @@ hipError_t p3d_loss(int kind, const float* logits, const float* pred, const floa
         hipLaunchKernelGGL(l1_loss_kernel, dim3(g), dim3(256), 0, s, logits, pred, target, (long long)n, loss_out, dlogits, ts, vec4,
                            part, cnt);
     if (done) { done[0] = vec4 ? 1 : 2; done[1] = g; }
+    return hipGetLastError();
+}
+
+hipError_t p3d_adam_decay(float* p, float* g, float* m, float* v, long n, const P3dRegTile* tiles, int ntile, long long tile_base,
+                          float lr_t, const float* lr_dev, float b1, float b2, float eps, int update, double* part,
+                          const double* fold_part, int nfold, unsigned* counter, double* term, hipStream_t s) {
+    if (n < 1 || ntile < 1 || !tiles || !part || (nfold > 0 && (!fold_part || !counter || !term)) ||
+        ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+          reinterpret_cast<uintptr_t>(v)) & 15))
+        return hipErrorInvalidValue;
+    if (update)
+        hipLaunchKernelGGL(adam_decay_kernel, dim3(ntile), dim3(256), 0, s, p, g, m, v, (long long)n, tiles, tile_base, lr_t, lr_dev,
+                           b1, b2, eps, part, fold_part, nfold, counter, term);
+    else
+        hipLaunchKernelGGL(decay_grad_kernel, dim3(ntile), dim3(256), 0, s, p, g, (long long)n, tiles, tile_base, part, fold_part,
+                           nfold, counter, term);
     return hipGetLastError();
 }
 

@@ -73,6 +73,7 @@ struct Param {
     int init = INIT_XAVIER;
     float* p = nullptr;     // device
     float* g = nullptr;     // device gradient (trainables)
+    int reg = 0;            // regularisation class, P3D_REG_*: what the reference's graph build adds to its collections
 };
 
 // The stem: conv -> BatchNorm -> ReLU, and the conv has no input gradient.  The normalisation's backward then ends after its

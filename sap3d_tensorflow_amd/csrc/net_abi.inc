@@ -318,6 +318,33 @@ int p3d_set_loss(p3d_handle* h, int kind) {
     API_END
 }
 
+int p3d_set_regularization(p3d_handle* h, int terms, float wd, float l2) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->set_regularization(terms, wd, l2);
+    API_END
+}
+
+int p3d_last_regularization(p3d_handle* h, double* term) {
+    API_BEGIN
+    if (!h || !term) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    *term = h->read_regularization();
+    API_END
+}
+
+int p3d_param_regularization(p3d_handle* h, const char* name, float* c_wd, float* c_l2) {
+    API_BEGIN
+    if (!h || !name || !c_wd || !c_l2) throw P3dError("null argument");
+    auto it = h->pindex.find(name);
+    if (it == h->pindex.end()) throw P3dError(std::string("no variable ") + name);
+    if (!it->second->trainable) throw P3dError(std::string(name) + " is not trainable");
+    *c_wd = (float)h->reg_coef64(it->second, P3D_REG_WEIGHT_DECAY);
+    *c_l2 = (float)h->reg_coef64(it->second, P3D_REG_L2);
+    API_END
+}
+
 int p3d_set_bn_fusion(p3d_handle* h, int enable) {
     API_BEGIN
     if (!h) throw P3dError("null handle");
@@ -347,6 +374,7 @@ int p3d_backward(p3d_handle* h, const float* x, const float* y, float dropout_ra
     h->run_forward(c);
     h->run_loss(c);
     h->run_backward(c, false);
+    if (h->reg_terms) h->decay_range(c, 0, h->n_train, false);      // the regularisation's gradient, after the backward's
     const float l = h->read_loss();
     if (loss) *loss = l;
     if (pred) h->download_act(h->pred, pred);
@@ -1266,6 +1294,44 @@ int p3d_debug_adam(int device, float* p, const float* g, float* m, float* v, int
     float* out[3] = {p, m, v};
     float* outd[3] = {pb.p, mb.p, vb.p};
     for (int q = 0; q < 3; ++q) HIPCHECK(copy_now(out[q], outd[q] + offset, (size_t)n * 4, hipMemcpyDeviceToHost, nullptr));
+    *lr_t = step;
+    API_END
+}
+
+// One regularised optimiser launch (decay_range in net_sched.inc) on raw inputs and a tile table, placed as p3d_debug_adam places them.
+int p3d_debug_adam_decay(int device, float* p, float* g, float* m, float* v, int64_t n, int offset, const int64_t* tile_off,
+                         const int64_t* tile_len, const float* tile_c, int ntile, float lr, int64_t t, float b1, float b2, float eps,
+                         int lr_on_device, int update, double* term, float* lr_t) {
+    API_BEGIN
+    HIPCHECK(hipSetDevice(device));
+    if (!p || !g || !m || !v || !tile_off || !tile_len || !tile_c || !term || !lr_t) throw P3dError("null argument");
+    if (n < 1 || t < 1 || offset < 0 || offset > 3 || ntile < 1) throw P3dError("adam_decay: bad length, step, offset or tile count");
+    std::vector<P3dRegTile> tiles((size_t)ntile);
+    int64_t at = 0;
+    for (int k = 0; k < ntile; ++k) {
+        if (tile_off[k] != at || tile_len[k] < 1 || tile_len[k] > (1 << 30)) throw P3dError("adam_decay: tiles must cover [0, n) in order");
+        tiles[k] = {(long long)tile_off[k], (int)tile_len[k], tile_c[k]};
+        at += tile_len[k];
+    }
+    if (at != n) throw P3dError("adam_decay: tiles must cover [0, n) in order");
+    DevBuf pb(n + offset), gb(n + offset), mb(n + offset), vb(n + offset), lrb(1), tb(4 * (int64_t)ntile), part(2 * (int64_t)ntile),
+        scal(4);
+    float* host[4] = {p, g, m, v};
+    float* dev[4] = {pb.p, gb.p, mb.p, vb.p};
+    for (int q = 0; q < 4; ++q) HIPCHECK(copy_now(dev[q] + offset, host[q], (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
+    HIPCHECK(copy_now(tb.p, tiles.data(), tiles.size() * sizeof(P3dRegTile), hipMemcpyHostToDevice, nullptr));
+    // scal (zeroed): [0..1] the term, [2] the fold's counter
+    const float step = adam_step_size(lr, b1, b2, t);
+    if (lr_on_device) HIPCHECK(p3d_set_step_scalars(nullptr, lrb.p, 0, step, nullptr));
+    double* dterm = reinterpret_cast<double*>(scal.p);
+    double* dpart = reinterpret_cast<double*>(part.p);
+    // from device memory the argument must not matter (as p3d_debug_adam)
+    HIPCHECK(p3d_adam_decay(pb.p + offset, gb.p + offset, mb.p + offset, vb.p + offset, (long)n, reinterpret_cast<P3dRegTile*>(tb.p), ntile,
+                            0, lr_on_device ? NAN : step, lr_on_device ? lrb.p : nullptr, b1, b2, eps, update ? 1 : 0, dpart, dpart,
+                            ntile, reinterpret_cast<unsigned*>(scal.p + 2), dterm, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    for (int q = 0; q < 4; ++q) HIPCHECK(copy_now(host[q], dev[q] + offset, (size_t)n * 4, hipMemcpyDeviceToHost, nullptr));
+    HIPCHECK(copy_now(term, dterm, sizeof(double), hipMemcpyDeviceToHost, nullptr));
     *lr_t = step;
     API_END
 }

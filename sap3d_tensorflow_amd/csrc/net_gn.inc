@@ -147,17 +147,17 @@
         const int* s = (first && stride2) ? s2 : one;
         const int kS[3] = {1, 3, 3}, kT[3] = {3, 1, 1};
         const std::string B = "block" + sid + "/";
-        Param* w1 = conv_weight("conv3_" + sid + "_1", {1, 1, 1, inplanes, planes});
+        Param* w1 = wd_weight("conv3_" + sid + "_1", {1, 1, 1, inplanes, planes});
         GN* g1 = add_gn(planes);
         Act* y1 = conv(B + "conv1", x, w1, nullptr, one, s, planes, nullptr, "");
         Act* z1 = gn_apply(B + "gn1", 0, y1, g1, nullptr, nullptr, nullptr, B + "conv1_bn_relu");
         const std::string nm = std::string("ST") + st + "_" + sid + "_2";
-        Param* wS = conv_weight(nm + "_S", {1, 3, 3, planes, planes});
+        Param* wS = wd_weight(nm + "_S", {1, 3, 3, planes, planes});
         Param* bS = conv_weight(nm + "_S_bias", {planes});
         GN* gS = add_gn(planes);
         Act* yS = conv(B + "convS", z1, wS, bS, kS, one, planes, nullptr, "");
         Act* zS = (st == 'B') ? nullptr : gn_apply(B + "gnS", 0, yS, gS, nullptr, nullptr, nullptr, "");
-        Param* wT = conv_weight(nm + "_T", {3, 1, 1, planes, planes});
+        Param* wT = wd_weight(nm + "_T", {3, 1, 1, planes, planes});
         Param* bT = conv_weight(nm + "_T_bias", {planes});
         GN* gT = add_gn(planes);
         Act* yT = conv(B + "convT", st == 'B' ? z1 : zS, wT, bT, kT, one, planes, nullptr, "");
@@ -165,12 +165,12 @@
         if (st == 'A') stout = gn_apply(B + "gnT", 0, yT, gT, nullptr, nullptr, nullptr, B + "st");
         else if (st == 'B') stout = gn_apply(B + "gnST", 3, yT, gT, yS, gS, nullptr, B + "st");      // relu(gn(T)) + relu(gn(S))
         else stout = gn_apply(B + "gnT", 4, yT, gT, zS, nullptr, nullptr, B + "st");
-        Param* w3 = conv_weight("conv3_" + sid + "_3", {1, 1, 1, planes, planes * 4});
+        Param* w3 = wd_weight("conv3_" + sid + "_3", {1, 1, 1, planes, planes * 4});
         GN* g3 = add_gn(planes * 4);
         Act* y3 = conv(B + "conv3", stout, w3, nullptr, one, one, planes * 4, nullptr, "");
         Act* res = x;
         if (first) {
-            Param* wp = conv_weight("dw3d_" + sid, {1, 1, 1, inplanes, planes * 4});
+            Param* wp = wd_weight("dw3d_" + sid, {1, 1, 1, inplanes, planes * 4});
             GN* gp = add_gn(planes * 4);
             Act* yp = conv(B + "proj", x, wp, nullptr, one, s, planes * 4, nullptr, "");
             res = gn_apply(B + "gnp", 5, yp, gp, nullptr, nullptr, nullptr, "");
@@ -190,7 +190,7 @@
         x_in = new_act("x", B, T, H, W, 3, false);
         const int k177[3] = {1, 7, 7}, s122[3] = {1, 2, 2}, k233[3] = {2, 3, 3}, s222[3] = {2, 2, 2};
         const int k211[3] = {2, 1, 1}, s211[3] = {2, 1, 1};
-        Param* w0 = conv_weight("firstconv1", {1, 7, 7, 3, b});
+        Param* w0 = wd_weight("firstconv1", {1, 7, 7, 3, b});
         GN* g0 = add_gn(b);
         Act* c1 = conv("stem/conv", x_in, w0, nullptr, k177, s122, b, nullptr, "conv1_custom", true);
         Act* a1 = gn_apply("stem/gn", 0, c1, g0, nullptr, nullptr, nullptr, "conv1_custom_bn_relu");
@@ -210,11 +210,14 @@
             pools[stage] = cur;
         }
     }
-    // tf.layers.conv3d / conv3d_transpose + GNReLU (gn/p3d_gn.py:14-22,49-51), optionally into a concat slice
+    // tf.layers.conv3d / conv3d_transpose + GNReLU (gn/p3d_gn.py:14-22,49-51), optionally into a concat slice.  l2_layers: the
+    // decoder-block head's conv3d_layers / deconv3d_layers, whose kernels carry kernel_regularizer=l2_reg() (gn/p3d_gn.py:11-21)
+    bool l2_layers = false;
     Act* gn_layer(const char* name, bool up, Act* x, int filters, const int* k, const int* s, Act* out,
                   const std::string& out_name, bool dropout = false) {
         Param* kern = up ? conv_weight(std::string(name) + "/kernel", {k[0], k[1], k[2], filters, x->C})
                          : conv_weight(std::string(name) + "/kernel", {k[0], k[1], k[2], x->C, filters});
+        if (l2_layers) kern->reg = P3D_REG_L2;
         Param* bi = add_param(std::string(name) + "/bias", {filters}, true, INIT_ZEROS);
         GN* g = add_gn(filters);
         Act* y = up ? deconv(name, x, kern, bi, k, s, filters, nullptr, "") : conv(name, x, kern, bi, k, s, filters, nullptr, "");
@@ -249,6 +252,7 @@
         const int B = cfg.batch, T = cfg.frames, H = cfg.height, W = cfg.width, b = cfg.base;
         if (b % 16) throw P3dError("the decoder-block head needs base to be a multiple of 16");
         var_prefix = "P3D/";
+        l2_layers = true;
         const int k333[3] = {3, 3, 3}, k233[3] = {2, 3, 3}, k133[3] = {1, 3, 3};
         const int s111[3] = {1, 1, 1}, s222[3] = {2, 2, 2}, s444[3] = {4, 4, 4};
         Act* cat = new_act("concatenator", B, T / 4, H / 4, W / 4, 14 * b);   // [deconv_pool2 2b | deconv_pool3 4b | deconv_pool4 8b]
@@ -266,6 +270,7 @@
         z = gn_layer("decoder2_deconv", true, z, b / 2, k333, s222, nullptr, "decoder2_deconv");
         z = gn_layer("decoder2_conv2", false, z, b / 4, k333, s111, nullptr, "decoder2_conv2", /*dropout=*/true);
         Param* kp = conv_weight("results/kernel", {3, 3, 3, b / 4, 1});
+        kp->reg = P3D_REG_L2;                 // tf.layers.conv3d(..., kernel_regularizer=l2_reg(), name='results') (gn/p3d_gn.py:538)
         Param* bp = add_param("results/bias", {1}, true, INIT_ZEROS);
         head(z, kp, bp, /*with_sigmoid=*/false, /*transpose=*/false);
     }

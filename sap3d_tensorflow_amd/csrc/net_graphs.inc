@@ -2,6 +2,13 @@
 // heads with attention(), the output head (p3d.py:30-221,226-397; utils/network.py:157-192).
     // ---- the reference graph -------------------------------------------------------------------
     Param* conv_weight(const std::string& name, std::vector<int64_t> shape) { return add_param(name, shape, true, INIT_XAVIER); }
+    // get_conv_weight with wd != 0 (p3d.py:10-16, gn/p3d_gn.py:54-60): its l2_loss goes to 'weightdecay_losses'.  conv_weight()
+    // also makes the convS/convT biases (wd = 0) and the head and attention kernels, which are not in that collection.
+    Param* wd_weight(const std::string& name, std::vector<int64_t> shape) {
+        Param* w = conv_weight(name, shape);
+        w->reg = P3D_REG_WEIGHT_DECAY;
+        return w;
+    }
 
     // Bottleneck.infer, p3d.py:83-136 (3-D branch only; the 2-D branch is unreachable, SURVEY fact 7)
     // per bottleneck: input / output tensors and the [first, last) range of its ops, for p3d_block_forward
@@ -24,7 +31,7 @@
         // variable creation order matters for BN auto-naming (SURVEY Appendix D)
         // BatchNorm fusion (ConvFuse): bn1, bnS, bnT and their ReLUs ride on the operand paths of the convs around them;
         // only bn3 (+ residual) keeps a pass of its own.  Every bn_apply below marked fused_site runs only with fusion off.
-        Param* w1 = conv_weight("conv3_" + sid + "_1", {1, 1, 1, inplanes, planes});
+        Param* w1 = wd_weight("conv3_" + sid + "_1", {1, 1, 1, inplanes, planes});
         BN* bn1 = add_bn("", planes, false);
         const ConvGeo g1 = make_geo(x->D, x->H, x->W, one, s);
         const bool fz = (int64_t)x->N * g1.O[0] * g1.O[1] * g1.O[2] <= fuse_max_rows;      // this bottleneck is built fusable
@@ -35,14 +42,14 @@
         Act* stout = nullptr;
         ConvFuse f3;                 // conv3's view of the ST output
         if (st == 'A') {          // p3d.py:56-63
-            Param* wS = conv_weight(nm + "_S", {1, 3, 3, planes, planes});
+            Param* wS = wd_weight(nm + "_S", {1, 3, 3, planes, planes});
             Param* bS = conv_weight(nm + "_S_bias", {planes});
             BN* bnS = add_bn("", planes, false);
             ConvFuse fS; fS.at = P3D_AT_RELU1; fS.src[0] = {y1, bn1, 1}; fS.ngate = 1; fS.gate[0] = {y1, bn1, 0}; fS.out_bn = bnS;
             if (!fz) fS = ConvFuse();
             Act* yS = conv(B + "convS", z1, wS, bS, kS, one, planes, bnS, "", false, false, 0, &fS);
             Act* zS = bn_apply(B + "bnS", 0, yS, bnS, nullptr, nullptr, nullptr, "", false, fz);
-            Param* wT = conv_weight(nm + "_T", {3, 1, 1, planes, planes});
+            Param* wT = wd_weight(nm + "_T", {3, 1, 1, planes, planes});
             Param* bT = conv_weight(nm + "_T_bias", {planes});
             BN* bnT = add_bn("", planes, false);
             ConvFuse fT; fT.at = P3D_AT_RELU1; fT.src[0] = {yS, bnS, 1}; fT.ngate = 1; fT.gate[0] = {yS, bnS, 0}; fT.out_bn = bnT;
@@ -51,7 +58,7 @@
             stout = bn_apply(B + "bnT", 0, yT, bnT, nullptr, nullptr, nullptr, B + "st", false, fz);
             f3.at = P3D_AT_RELU1; f3.src[0] = {yT, bnT, 1}; f3.ngate = 1; f3.gate[0] = {yT, bnT, 0};
         } else if (st == 'B') {   // p3d.py:65-72
-            Param* wS = conv_weight(nm + "_S", {1, 3, 3, planes, planes});
+            Param* wS = wd_weight(nm + "_S", {1, 3, 3, planes, planes});
             Param* bS = conv_weight(nm + "_S_bias", {planes});
             BN* bnS = add_bn("", planes, false);
             // z1 feeds both siblings: convS (registered first, so last in backward) folds and publishes bn1 in the forward and,
@@ -59,7 +66,7 @@
             ConvFuse fS; fS.at = P3D_AT_RELU1; fS.src[0] = {y1, bn1, 1}; fS.ngate = 1; fS.gate[0] = {y1, bn1, 0}; fS.accum_in = true; fS.out_bn = bnS;
             if (!fz) fS = ConvFuse();
             Act* yS = conv(B + "convS", z1, wS, bS, kS, one, planes, bnS, "", false, false, /*sibling=*/1, &fS);
-            Param* wT = conv_weight(nm + "_T", {3, 1, 1, planes, planes});
+            Param* wT = wd_weight(nm + "_T", {3, 1, 1, planes, planes});
             Param* bT = conv_weight(nm + "_T_bias", {planes});
             BN* bnT = add_bn("", planes, false);
             ConvFuse fT; fT.at = P3D_AT_RELU1; fT.src[0] = {y1, bn1, 2}; fT.out_bn = bnT;
@@ -69,14 +76,14 @@
             f3.at = P3D_AT_RELU2; f3.src[0] = {yS, bnS, 1}; f3.src[1] = {yT, bnT, 1};
             f3.ngate = 2; f3.gate[0] = {yS, bnS, 0}; f3.gate[1] = {yT, bnT, 0};
         } else {                  // p3d.py:74-81
-            Param* wS = conv_weight(nm + "_S", {1, 3, 3, planes, planes});
+            Param* wS = wd_weight(nm + "_S", {1, 3, 3, planes, planes});
             Param* bS = conv_weight(nm + "_S_bias", {planes});
             BN* bnS = add_bn("", planes, false);
             ConvFuse fS; fS.at = P3D_AT_RELU1; fS.src[0] = {y1, bn1, 1}; fS.ngate = 1; fS.gate[0] = {y1, bn1, 0}; fS.out_bn = bnS;
             if (!fz) fS = ConvFuse();
             Act* yS = conv(B + "convS", z1, wS, bS, kS, one, planes, bnS, "", false, false, 0, &fS);
             Act* zS = bn_apply(B + "bnS", 0, yS, bnS, nullptr, nullptr, nullptr, "", false, fz);
-            Param* wT = conv_weight(nm + "_T", {3, 1, 1, planes, planes});
+            Param* wT = wd_weight(nm + "_T", {3, 1, 1, planes, planes});
             Param* bT = conv_weight(nm + "_T_bias", {planes});
             BN* bnT = add_bn("", planes, false);
             // zS also reaches conv3 through the skip: conv3's input gradient leaves its raw result in zS->g, convT's adds its
@@ -89,11 +96,11 @@
             f3.ngate = 1; f3.gate[0] = {yT, bnT, 0}; f3.raw = zS; f3.raw_flag = zS->last_flag;      // the flag of bnT's skip read
         }
         if (!fz) f3 = ConvFuse();
-        Param* w3 = conv_weight("conv3_" + sid + "_3", {1, 1, 1, planes, planes * 4});
+        Param* w3 = wd_weight("conv3_" + sid + "_3", {1, 1, 1, planes, planes * 4});
         BN* bn3 = add_bn("", planes * 4, false);
         Act* y3 = conv(B + "conv3", stout, w3, nullptr, one, one, planes * 4, bn3, "", false, false, 0, &f3);
         if (first) {              // p3d.py:124-127
-            Param* wp = conv_weight("dw3d_" + sid, {1, 1, 1, inplanes, planes * 4});
+            Param* wp = wd_weight("dw3d_" + sid, {1, 1, 1, inplanes, planes * 4});
             BN* bnp = add_bn("", planes * 4, false);
             Act* yp = conv(B + "proj", x, wp, nullptr, one, s, planes * 4, bnp, "");
             return bn_apply(B + "bn3", 2, y3, bn3, yp, bnp, nullptr, B + "out");
@@ -111,7 +118,7 @@
         x_in = new_act("x", B, T, H, W, 3, /*with_grad=*/false);
         // p3d.py:172-177
         const int k177[3] = {1, 7, 7}, s122[3] = {1, 2, 2};
-        Param* w0 = conv_weight("firstconv1", {1, 7, 7, 3, b});
+        Param* w0 = wd_weight("firstconv1", {1, 7, 7, 3, b});
         BN* bn0 = add_bn("", b, true);
         Act* c1 = conv("stem/conv", x_in, w0, nullptr, k177, s122, b, bn0, "conv1_custom", /*stem=*/true);
         Act* a1 = bn_apply("stem/bn", 0, c1, bn0, nullptr, nullptr, nullptr, "conv1_custom_bn_relu");

@@ -238,12 +238,112 @@
         if (hi <= lo) return;
         static const bool skip = p3d_tune_env("P3D_TUNE_SKIP_ADAM") != nullptr;      // timing diagnostic (tuning build; the weights stay put)
         if (skip) return;
+        if (reg_terms) return decay_range(c, lo, hi, true);
         const float lr_t = cur_lr_t;
         launch(c, "adam_kernel", 0, 28.0 * (hi - lo), [&]() {
             return p3d_adam(flat_p + lo, flat_g + lo, flat_m + lo, flat_v + lo, hi - lo, lr_t, c.lr_dev, b1, b2, eps, c.s);
         });
     }
     void run_adam(const Ctx& c) { adam_begin(c); adam_range(c, 0, n_train); }
+
+    // ---- regularisation (p3d_set_regularization) ---------------------------------------------------
+    // The flat range is cut into tiles of one coefficient each: every trainable's slot is cut at REG_TILE, a decayed variable's
+    // slot padding is a tile of its own with c = 0.  Every range adam_range is called with starts at a variable's offset, so at
+    // a tile.  Each tile's 0.5 c sum(w^2) lands in d_reg_part[tile]; the range that starts at 0, always the last one launched on
+    // the stream, folds all of them in tile order into d_reg: the term does not depend on the optimiser split.
+    static constexpr int64_t REG_TILE = 8192;
+    int reg_terms = 0;
+    double reg_wd = 0.0, reg_l2 = 0.0;
+    std::vector<P3dRegTile> reg_tiles;
+    std::vector<int64_t> reg_decayed;        // elements with c != 0 in tiles [0, k)
+    P3dRegTile* d_reg_tiles = nullptr;
+    double* d_reg_part = nullptr;
+    double* d_reg = nullptr;
+    unsigned* d_reg_cnt = nullptr;
+    bool gn_net() const {
+        return cfg.structure == P3D_STRUCTURE_GN_P3D || cfg.structure == P3D_STRUCTURE_GN_P3D_CONCAT ||
+               cfg.structure == P3D_STRUCTURE_GN_P3D_DECODER;
+    }
+    int reg_count(int cls) const {
+        int k = 0;
+        for (const Param* p : porder) k += p->trainable && p->reg == cls;
+        return k;
+    }
+    // the float32 coefficient of one term on one variable under the current settings
+    double reg_coef64(const Param* p, int term) const {
+        if (!(reg_terms & term) || p->reg != term) return 0.0;
+        return (term == P3D_REG_WEIGHT_DECAY ? reg_wd : reg_l2) / reg_count(term);
+    }
+    void set_regularization(int terms, float wd, float l2) {
+        if (terms & ~(P3D_REG_WEIGHT_DECAY | P3D_REG_L2))
+            throw P3dError("regularisation terms are a mask of 1 (weight decay) and 2 (l2), not " + std::to_string(terms));
+        if ((terms & P3D_REG_L2) && reg_count(P3D_REG_L2) == 0)
+            throw P3dError("l2: this net has no kernel_regularizer variables under scope P3D (only gn_p3d_decoder has); the "
+                           "reference's mean over an empty collection is NaN");
+        if ((terms & P3D_REG_WEIGHT_DECAY) && reg_count(P3D_REG_WEIGHT_DECAY) == 0) throw P3dError("weight decay: no decayed variable");
+        std::vector<const Param*> tr;
+        for (const Param* p : porder) if (p->trainable) tr.push_back(p);
+        std::sort(tr.begin(), tr.end(), [](const Param* a, const Param* b) { return a->off < b->off; });
+        const int saved = reg_terms;
+        reg_terms = terms;
+        reg_wd = wd > 0.f ? (double)wd : (gn_net() ? 0.0005 : 0.001);
+        reg_l2 = l2 > 0.f ? (double)l2 : 0.0005;
+        std::vector<P3dRegTile> tiles;
+        auto cut = [&](int64_t a, int64_t b, float c) {
+            for (; a < b; a += REG_TILE) tiles.push_back({(long long)a, (int)std::min(REG_TILE, b - a), c});
+        };
+        for (size_t i = 0; i < tr.size(); ++i) {
+            const int64_t end = i + 1 < tr.size() ? tr[i + 1]->off : n_train;
+            const float c = (float)(reg_coef64(tr[i], P3D_REG_WEIGHT_DECAY) + reg_coef64(tr[i], P3D_REG_L2));
+            if (!tr[i]->reg) { cut(tr[i]->off, end, 0.f); continue; }      // (the cut does not depend on the settings)
+            cut(tr[i]->off, tr[i]->off + tr[i]->count, c);
+            cut(tr[i]->off + tr[i]->count, end, 0.f);
+        }
+        if (tiles.empty() || tiles[0].off != 0) { reg_terms = saved; throw P3dError("regularisation: no trainable variable at offset 0"); }
+        HIPCHECK(hipStreamSynchronize(stream));      // the table may be in use by queued work
+        if (!d_reg_tiles) {
+            d_reg_tiles = dalloc<P3dRegTile>((int64_t)tiles.size());
+            d_reg_part = dalloc<double>((int64_t)tiles.size());
+            d_reg = dalloc<double>(1);
+            d_reg_cnt = dalloc<unsigned>(1);
+            HIPCHECK(fill_async(d_reg, 0, sizeof(double), stream, "regularisation"));
+            HIPCHECK(fill_async(d_reg_cnt, 0, sizeof(unsigned), stream, "regularisation"));
+        }
+        HIPCHECK(copy_now(d_reg_tiles, tiles.data(), tiles.size() * sizeof(P3dRegTile), hipMemcpyHostToDevice, stream));
+        reg_tiles = std::move(tiles);
+        reg_decayed.assign(reg_tiles.size() + 1, 0);
+        for (size_t k = 0; k < reg_tiles.size(); ++k) reg_decayed[k + 1] = reg_decayed[k] + (reg_tiles[k].c != 0.f ? reg_tiles[k].len : 0);
+        drop_step_graph();
+    }
+    // decay (+ Adam when update) of the variables in [lo, hi): adam_range's launch when a term is on, and the gradient-only
+    // launch of p3d_backward.  Per decayed element: 2 operations for g + c w, 2 for the term; 4 bytes more than Adam's 28 (the
+    // gradient written back), 12 without the update.
+    void decay_range(const Ctx& c, int64_t lo, int64_t hi, bool update) {
+        if (hi <= lo) return;
+        auto at = [&](int64_t off) {
+            return (int)(std::lower_bound(reg_tiles.begin(), reg_tiles.end(), off,
+                                          [](const P3dRegTile& t, int64_t o) { return t.off < o; }) - reg_tiles.begin());
+        };
+        const int t0 = at(lo), t1 = at(hi);
+        if (t0 >= (int)reg_tiles.size() || reg_tiles[t0].off != lo || t1 <= t0 || reg_tiles[t1 - 1].off + reg_tiles[t1 - 1].len != hi)
+            throw P3dError("regularisation: range is not on tile boundaries");
+        const double nd = (double)(reg_decayed[t1] - reg_decayed[t0]);
+        const bool fold = lo == 0;
+        const float lr_t = cur_lr_t;
+        launch(c, update ? "adam_decay_kernel" : "decay_grad_kernel", 4.0 * nd,
+               (update ? 28.0 * (hi - lo) + 4.0 * nd : 12.0 * nd) + 8.0 * (t1 - t0), [&]() {
+            return p3d_adam_decay(flat_p + lo, flat_g + lo, flat_m + lo, flat_v + lo, hi - lo, d_reg_tiles + t0, t1 - t0, lo, lr_t,
+                                  c.lr_dev, b1, b2, eps, update ? 1 : 0, d_reg_part + t0, d_reg_part, fold ? (int)reg_tiles.size() : 0,
+                                  d_reg_cnt, d_reg, c.s);
+        });
+    }
+    double read_regularization() {
+        double r = 0.0;
+        if (!reg_terms) return r;
+        HIPCHECK(hipMemcpyAsync(&r, d_reg, sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIPCHECK(hipStreamSynchronize(stream));
+        return r;
+    }
 
     // ---- captured train step (opt-in: P3D_GRAPH=1) ---------------------------------------------------
     // One train step is ~1000 dependent launches on three streams.  The launch list is static, so it CAN be captured
@@ -256,6 +356,7 @@
     hipGraph_t step_graph = nullptr;
     hipGraphExec_t step_exec = nullptr;
     float graph_drop = -1.f; bool graph_f16 = false; ncclComm_t graph_comm = nullptr; float graph_b1 = 0, graph_b2 = 0, graph_eps = 0;
+    int graph_reg = 0;
     bool graph_disabled = false;
     unsigned long long* d_seed = nullptr; float* d_lr = nullptr;
     void drop_step_graph() {
@@ -284,6 +385,7 @@
         if (const char* dot = p3d_tune_env("P3D_TUNE_GRAPH_DOT")) hipGraphDebugDotPrint(step_graph, dot, hipGraphDebugDotFlagsVerbose);      // tuning build
         HIPCHECK(hipGraphInstantiate(&step_exec, step_graph, nullptr, nullptr, 0));
         graph_drop = drop; graph_f16 = pointwise_f16; graph_comm = comm; graph_b1 = b1; graph_b2 = b2; graph_eps = eps;
+        graph_reg = reg_terms;
     }
     void train_step_device(float drop, uint64_t seed) {
         if (!graphs_enabled()) {
@@ -294,7 +396,7 @@
             return;
         }
         if (!step_exec || graph_drop != drop || graph_f16 != pointwise_f16 || graph_comm != comm || graph_b1 != b1 || graph_b2 != b2 ||
-            graph_eps != eps) {
+            graph_eps != eps || graph_reg != reg_terms) {
             try {
                 capture_step_graph(drop);
             } catch (const std::exception& e) {
@@ -314,11 +416,12 @@
         if (x) HIPCHECK(hipMemcpyAsync(x_in->p, x, (size_t)x_in->rows() * 3 * sizeof(float), hipMemcpyHostToDevice, stream));
         if (y) HIPCHECK(hipMemcpyAsync(d_y, y, (size_t)pred->rows() * sizeof(float), hipMemcpyHostToDevice, stream));
     }
-    float read_loss() {
-        double l = 0;
+    float read_loss() {      // the data loss, plus the regularisation term when one is on
+        double l = 0, r = 0;
         HIPCHECK(hipMemcpyAsync(&l, d_loss, sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (reg_terms) HIPCHECK(hipMemcpyAsync(&r, d_reg, sizeof(double), hipMemcpyDeviceToHost, stream));
         HIPCHECK(hipStreamSynchronize(stream));
-        return (float)l;
+        return reg_terms ? (float)(l + r) : (float)l;
     }
     void download_act(Act* a, float* host) {
         if (a->ld == a->C)

@@ -509,6 +509,21 @@ hipError_t p3d_loss(int kind, const float* logits, const float* pred, const floa
 // p, g, m, v must be 16-byte aligned (hipErrorInvalidValue otherwise): the kernel moves four elements at a time.
 hipError_t p3d_adam(float* p, const float* g, float* m, float* v, long n, float lr_t, const float* lr_dev, float b1, float b2,
                     float eps, hipStream_t s);
+// Regularisation (p3d_set_regularization): the flat range is cut at plan time into tiles, each with ONE float32 coefficient c
+// (0 on undecayed variables and on slot padding).  off is relative to the table's base, len >= 1, tiles ascending and
+// contiguous.
+struct P3dRegTile { long long off; int len; float c; };
+// Fused decay + Adam over n elements from p (one block per tile; tiles[0].off - tile_base == 0, the tiles cover [0, n)):
+// per element g' = g + c*p, written back to g where c != 0, then Adam on g' (update = 1), or nothing more (update = 0: the
+// gradient-only mode of p3d_backward).  Float32 order, no contraction: g' = fadd(g, fmul(c, p)); then Adam as adam_kernel
+// computes it -- on 4-groups that lie whole in [0, n) m = fma(b1, m, (1-b1) g'), v = fma(b2, v, ((1-b2) g') g'), on a partial
+// last group m = (b1 m) + ((1-b1) g'), v = (b2 v) + (((1-b2) g') g'); p -= (lr_t m) / (sqrt(v) + eps) -- so c = 0 gives its
+// bits.  part[k] = 0.5 * c * (sum of p^2 over tile k, in double; fixed order); with nfold > 0 the last block folds
+// fold_part[0 .. nfold) in index order into *term (the whole table's term, whichever ranges wrote it earlier on the stream;
+// *counter zero at launch).  p, g, m, v 16-byte aligned.
+hipError_t p3d_adam_decay(float* p, float* g, float* m, float* v, long n, const P3dRegTile* tiles, int ntile, long long tile_base,
+                          float lr_t, const float* lr_dev, float b1, float b2, float eps, int update, double* part,
+                          const double* fold_part, int nfold, unsigned* counter, double* term, hipStream_t s);
 // per-step scalars of a captured train step: scal[0..1] = dropout seed (64 bit), scal[2] = Adam's bias-corrected step size
 hipError_t p3d_set_step_scalars(unsigned long long* seed_dst, float* lr_dst, unsigned long long seed, float lr_t, hipStream_t s);
 

@@ -272,6 +272,25 @@ def adam(p, g, m, v, t, lr=1e-4, b1=0.9, b2=0.999, eps=1e-8, lr_on_device=False,
     return p, m, v, lr_t.value
 
 
+def adam_decay(p, g, m, v, tiles, t, lr=1e-4, b1=0.9, b2=0.999, eps=1e-8, lr_on_device=False, update=True, offset=0, device=0):
+    """Test hook: one launch of the regularised optimiser step (p3d_debug_adam_decay) on flat float32 arrays.  tiles = [(length,
+    coefficient), ...] cut [0, n) in order; each gets one float32 coefficient c, and g' = g + c p.  With update, p, m, v take
+    Adam's step t on g'; without, only g changes.  Returns (g', p, m, v, the term sum 0.5 c sum(p^2) in double, the float32
+    step size)."""
+    p, g, m, v = (_f32(a).ravel().copy() for a in (p, g, m, v))
+    if not (p.size == g.size == m.size == v.size):
+        raise ValueError("p, g, m, v differ in size")
+    lens = np.array([int(n) for n, _ in tiles], np.int64)
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    cs = np.array([c for _, c in tiles], np.float32)
+    i64 = C.POINTER(C.c_int64)
+    term, lr_t = C.c_double(), C.c_float()
+    check(lib().p3d_debug_adam_decay(device, fptr(p), fptr(g), fptr(m), fptr(v), p.size, int(offset), offs.ctypes.data_as(i64),
+                                     lens.ctypes.data_as(i64), fptr(cs), len(tiles), float(lr), int(t), float(b1), float(b2),
+                                     float(eps), 1 if lr_on_device else 0, 1 if update else 0, C.byref(term), C.byref(lr_t)))
+    return g, p, m, v, term.value, lr_t.value
+
+
 def stat_parts(xshape, fshape, strides, transpose=False):
     """Host-only test hook: (partials the conv's statistics epilogue writes, room the network reserves for them)."""
     w, c = C.c_int(), C.c_int()

@@ -231,6 +231,33 @@ class P3DSession:
             raise ValueError("loss %r: have %s" % (name, sorted(_lib.LOSSES)))
         check(lib().p3d_set_loss(self._h, _lib.LOSSES[name]))
 
+    def set_regularization(self, terms=("weightdecay",), wd=None, l2=None):
+        """Regularisation terms added to the training loss, the reference's two collections that its loss leaves out
+        (train.py:161, gn/train_p3d_gn_dataset.py:188-189): "weightdecay" (mean over the get_conv_weight kernels of
+        wd * l2_loss(w); wd defaults to 0.001 on the BatchNorm nets, 0.0005 on the GroupNorm nets) and "l2" (mean over the
+        kernel_regularizer kernels of scope P3D of 0.0005 * l2_loss(w); gn_p3d_decoder only, refused elsewhere).  terms=() or
+        None switches them off, the default.  The loss train_step / backward report is the data loss plus the term."""
+        names = () if terms is None else ((terms,) if isinstance(terms, str) else tuple(terms))
+        mask = 0
+        for t in names:
+            if t not in _lib.REGULARIZATION:
+                raise ValueError("regularization %r: have %s" % (t, sorted(_lib.REGULARIZATION)))
+            mask |= _lib.REGULARIZATION[t]
+        check(lib().p3d_set_regularization(self._h, mask, float(wd or 0.0), float(l2 or 0.0)))
+
+    def last_regularization(self):
+        """The regularisation term of the last train step or backward, in double (0.0 when off); the reported loss
+        includes it once per rank."""
+        t = C.c_double()
+        check(lib().p3d_last_regularization(self._h, C.byref(t)))
+        return t.value
+
+    def param_regularization(self, name):
+        """(c_wd, c_l2): the float32 coefficients whose sum times the variable the regularisation adds to its gradient."""
+        a, b = C.c_float(), C.c_float()
+        check(lib().p3d_param_regularization(self._h, name.encode(), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def predict_windows(self, x):
         """B windows of gen_pred.py:100-168 at once: row k equals forward(x[k:k+1], training=False) of a batch-1
         session, i.e. every batch-statistics BN normalises each clip by its own statistics."""
