@@ -442,6 +442,113 @@ void gn_pass_backward(const Ctx& c, const GnApplyArgs& a, bool small) {
     launch(c, kb.c_str(), 0, tens * (a.y2 ? 5 : 3), [&]() { return p3d_gn_bwd_apply(a, c.s); });
 }
 
+// A BatchNorm's parameters, moving statistics, [4][C] table of scale, shift, mean, invstd, and the statistics partials.
+BnParams bn_layout(const float* gamma, const float* beta, float* moving_mean, float* moving_var, float* tab, const float* statpart,
+                   int nparts, int C) {
+    BnParams b;
+    b.gamma = gamma; b.beta = beta; b.moving_mean = moving_mean; b.moving_var = moving_var; b.statpart = statpart; b.nparts = nparts;
+    b.scale = tab; b.shift = tab + C; b.mean = tab + 2 * C; b.invstd = tab + 3 * C; b.C = C;
+    return b;
+}
+
+// One BatchNorm normalise / ReLU / add pass (bn_apply in net_ops.inc, and the test hook p3d_debug_bn_pass).  Index 1 of the
+// per-BatchNorm arrays is the second BatchNorm of modes 2 and 3; the kernels' argument structs are built from this, and only here.
+struct BnPass {
+    int mode = 0; int64_t M = 0; int C = 0;
+    const float* y1 = nullptr; int ld1 = 0; const float* y2 = nullptr; int ld2 = 0;
+    float* z = nullptr; int ldz = 0; const float* dz = nullptr; int lddz = 0;
+    float* dy1 = nullptr; int lddy1 = 0; float* dy2 = nullptr; int lddy2 = 0; int acc2 = 0;
+    BnParams bn[2] = {};
+    float* dgamma[2] = {}; float* dbeta[2] = {};
+    float* part[2] = {}; int nparts = 0; float* coef[2] = {};      // backward partial sums [nparts][C][2] and coefficients [C][2]
+    int batch[2] = {};                                              // 1: batch statistics, 0: moving statistics
+    float drop_rate = 0.f, drop_scale = 0.f; unsigned long long seed = 0; const unsigned long long* seed_dev = nullptr;
+    float eps = 1e-3f;
+};
+BnApplyArgs bn_apply_args(const BnPass& p) {
+    BnApplyArgs a;
+    memset(&a, 0, sizeof(a));
+    a.mode = p.mode; a.M = p.M; a.C = p.C;
+    a.y1 = p.y1; a.ld1 = p.ld1; a.scale1 = p.bn[0].scale; a.shift1 = p.bn[0].shift;
+    a.y2 = p.y2; a.ld2 = p.ld2; a.scale2 = p.bn[1].scale; a.shift2 = p.bn[1].shift;
+    a.z = p.z; a.ldz = p.ldz;
+    a.drop_scale = p.drop_scale; a.drop_rate = p.drop_rate; a.seed = p.seed; a.seed_dev = p.seed_dev;
+    return a;
+}
+BnSmallArgs bn_small_args(const BnPass& p, bool update_moving) {
+    BnSmallArgs a;
+    memset(&a, 0, sizeof(a));
+    a.mode = p.mode; a.M = (int)p.M; a.C = p.C;
+    a.y1 = p.y1; a.ld1 = p.ld1; a.y2 = p.y2; a.ld2 = p.ld2;
+    a.bn1 = p.bn[0]; a.bn2 = p.bn[1]; a.batch1 = p.batch[0]; a.batch2 = p.batch[1];
+    a.update_moving = update_moving; a.eps = p.eps;
+    a.z = p.z; a.ldz = p.ldz; a.dz = p.dz; a.lddz = p.lddz;
+    a.dy1 = p.dy1; a.lddy1 = p.lddy1; a.dy2 = p.dy2; a.lddy2 = p.lddy2; a.acc2 = p.acc2;
+    a.dgamma1 = p.dgamma[0]; a.dbeta1 = p.dbeta[0]; a.dgamma2 = p.dgamma[1]; a.dbeta2 = p.dbeta[1];
+    return a;
+}
+BnBwdArgs bn_bwd_args(const BnPass& p) {
+    BnBwdArgs a;
+    memset(&a, 0, sizeof(a));
+    a.mode = p.mode; a.M = p.M; a.C = p.C; a.dz = p.dz; a.lddz = p.lddz;
+    a.y1 = p.y1; a.ld1 = p.ld1; a.scale1 = p.bn[0].scale; a.shift1 = p.bn[0].shift; a.mean1 = p.bn[0].mean; a.invstd1 = p.bn[0].invstd;
+    a.y2 = p.y2; a.ld2 = p.ld2; a.scale2 = p.bn[1].scale; a.shift2 = p.bn[1].shift; a.mean2 = p.bn[1].mean; a.invstd2 = p.bn[1].invstd;
+    a.gamma1 = p.bn[0].gamma; a.gamma2 = p.bn[1].gamma;
+    a.part1 = p.part[0]; a.part2 = p.part[1]; a.nparts = p.nparts; a.coef1 = p.coef[0]; a.coef2 = p.coef[1];
+    a.dgamma1 = p.dgamma[0]; a.dbeta1 = p.dbeta[0]; a.dgamma2 = p.dgamma[1]; a.dbeta2 = p.dbeta[1];
+    a.batch1 = p.batch[0]; a.batch2 = p.batch[1];
+    a.dy1 = p.dy1; a.lddy1 = p.lddy1; a.dy2 = p.dy2; a.lddy2 = p.lddy2; a.acc2 = p.acc2;
+    a.drop_scale = p.drop_scale; a.drop_rate = p.drop_rate; a.seed = p.seed; a.seed_dev = p.seed_dev;
+    return a;
+}
+
+// Which kernels take a BatchNorm pass: the one-launch small-tensor kernels unless the pass drops out; else finalize + apply in
+// one launch when every apply block can fold its own channels' statistics partials (nparts of the batch-statistics BatchNorms,
+// 0 for the others); else finalize, then apply.  The network makes the small-path choice when it builds the graph (a producer
+// whose output takes it writes no statistics partials: stats_target), and its dry runs take finalize + apply.
+enum BnPath { BN_SMALL = 1, BN_FOLD = 2, BN_FINALIZE = 3 };      // (p3d_debug_bn_pass's path numbers)
+BnPath bn_path(int64_t M, int C, bool dropout, int nparts1, int nparts2, float drop_scale) {
+    if (!dropout && p3d_bn_small_ok((long)M, C)) return BN_SMALL;
+    return p3d_bn_fold_apply_ok((long)M, C, nparts1, nparts2, drop_scale) ? BN_FOLD : BN_FINALIZE;
+}
+void bn_pass_forward(const Ctx& c, const BnPass& p, BnPath path, bool update_moving) {
+    const double io = (double)p.M * p.C * 4.0 * (p.y2 ? 3 : 2);
+    const std::string m = "<" + std::to_string(p.mode) + ">";
+    if (path == BN_SMALL) {
+        const BnSmallArgs a = bn_small_args(p, update_moving);
+        launch(c, ("bn_small_fwd_kernel" + m).c_str(), 0, io, [&]() { return p3d_bn_small_fwd(a, c.s); });
+        return;
+    }
+    const BnApplyArgs a = bn_apply_args(p);
+    if (path == BN_FOLD) {
+        launch(c, "bn_fold_apply_kernel", 0, io, [&]() {
+            return p3d_bn_fold_apply(a, p.bn[0], p.bn[1], p.batch[0], p.batch[1], update_moving ? 1 : 0, p.eps, c.s);
+        });
+        return;
+    }
+    for (int q = 0; q < (p.mode == 2 || p.mode == 3 ? 2 : 1); ++q)
+        launch(c, "bn_finalize_kernel", 0, 64.0 * p.C, [&]() {
+            return p3d_bn_finalize(p.bn[q], p.M, p.batch[q], p.batch[q] && update_moving, p.eps, c.s);
+        });
+    launch(c, ("bn_apply_kernel" + m).c_str(), 0, io, [&]() { return p3d_bn_apply(a, c.s); });
+}
+// stem non-null: the pass ends before its apply launch and leaves that launch's arguments there (the stem conv's filter
+// gradient evaluates it on its operand path, stem_wgrad.hip).
+void bn_pass_backward(const Ctx& c, const BnPass& p, bool small, BnBwdArgs* stem = nullptr) {
+    const double tens = (double)p.M * p.C * 4.0;
+    const std::string m = "<" + std::to_string(p.mode) + ">";
+    if (small) {
+        const BnSmallArgs a = bn_small_args(p, false);
+        launch(c, ("bn_small_bwd_kernel" + m).c_str(), 0, tens * (p.y2 ? 5 : 3), [&]() { return p3d_bn_small_bwd(a, c.s); });
+        return;
+    }
+    const BnBwdArgs a = bn_bwd_args(p);
+    launch(c, ("bn_bwd_reduce_kernel" + m).c_str(), 0, tens * (p.y2 ? 3 : 2), [&]() { return p3d_bn_bwd_reduce(a, c.s); });
+    launch(c, "bn_bwd_finalize_kernel", 0, 64.0 * p.C, [&]() { return p3d_bn_bwd_finalize(a, c.s); });
+    if (stem) { *stem = a; return; }
+    launch(c, ("bn_bwd_apply_kernel" + m).c_str(), 0, tens * (p.y2 ? 5 : 3), [&]() { return p3d_bn_bwd_apply(a, c.s); });
+}
+
 // CBAM (cbam() in net_gn.inc, and the test hook p3d_debug_cbam): row chunks per sample of the pooling and backward passes, and the
 // layout of a site's scratch, in floats from its base: part [N][chunks][C][3]; avg, mx, ties, cs, davg, dmx [N][C] each;
 // havg, hmx, dh [N][C/8], [N][C/8], [N][2][C/8] (+ 8); sp [M][2]; ss [M]; dpre [M]; dsp [M][2]; dcs_part [N][chunks][C]; dO [N][C].
@@ -942,14 +1049,11 @@ struct p3d_handle {
         return s;
     }
     // Producers of tensors that the one-launch small-tensor BN will consume need no statistics epilogue.
-    static bool bn_is_small(int64_t rows, int C, bool dropout = false) { return !dropout && p3d_bn_small_ok((long)rows, C); }
+    static bool bn_is_small(int64_t rows, int C, bool dropout = false) { return bn_path(rows, C, dropout, 0, 0, 0.f) == BN_SMALL; }
     BN* stats_target(BN* bn, int64_t rows, int C, bool dropout = false) { return bn_is_small(rows, C, dropout) ? nullptr : bn; }
-    BnParams bn_params(BN* bn) {
-        BnParams b;
-        b.gamma = bn->gamma->p; b.beta = bn->beta->p; b.moving_mean = bn->mm->p; b.moving_var = bn->mv->p;
-        b.statpart = bn->part_off >= 0 ? statpart_arena + bn->part_off : nullptr; b.nparts = bn->nparts; b.scale = bn->scale; b.shift = bn->shift; b.mean = bn->mean; b.invstd = bn->invstd;
-        b.C = bn->C;
-        return b;
+    BnParams bn_params(BN* bn) {      // (add_bn lays scale, shift, mean, invstd out as one [4][C] table)
+        return bn_layout(bn->gamma->p, bn->beta->p, bn->mm->p, bn->mv->p, bn->scale,
+                         bn->part_off >= 0 ? statpart_arena + bn->part_off : nullptr, bn->nparts, bn->C);
     }
 
     // ---- deferred, grouped weight gradients -------------------------------------------------------

@@ -827,11 +827,11 @@ int p3d_debug_stem_wgrad_through_bn(int device, const float* x, const int64_t xs
     DevBuf x4(sg.xrows * sg.Wp * 4), dw4((int64_t)sg.KH * sg.K4 * Cout), spart(p3d_stem_wgrad_part_floats());
     Ctx c;
     HIPCHECK(p3d_stem_pad(dx.p, x4.p, sg.xrows, g.I[2], sg.Wp, g.pad[2], c.s));
-    BnBwdArgs a;
-    memset(&a, 0, sizeof(a));
-    a.mode = 0; a.M = rows; a.C = Cout; a.dz = dzb.p; a.lddz = Cout; a.y1 = dyb.p; a.ld1 = Cout;
-    a.scale1 = tb.p; a.shift1 = tb.p + Cout; a.mean1 = tb.p + 2 * Cout; a.invstd1 = tb.p + 3 * Cout; a.gamma1 = tb.p + 4 * Cout;
-    a.coef1 = cf.p; a.batch1 = batch ? 1 : 0; a.dy1 = dyo.p; a.lddy1 = Cout;
+    BnPass p;
+    p.mode = 0; p.M = rows; p.C = Cout; p.dz = dzb.p; p.lddz = Cout; p.y1 = dyb.p; p.ld1 = Cout; p.dy1 = dyo.p; p.lddy1 = Cout;
+    p.bn[0] = bn_layout(tb.p + 4 * Cout, nullptr, nullptr, nullptr, tb.p, nullptr, 0, Cout);
+    p.coef[0] = cf.p; p.batch[0] = batch ? 1 : 0;
+    const BnBwdArgs a = bn_bwd_args(p);
     stem_filter_gradient(c, g, (int)xs[0], sg.Wp, x4.p, nullptr, Cout, Cout, dw4.p, dw1.p, nullptr, false, spart.p, &a);       // fused
     HIPCHECK(p3d_bn_bwd_apply(a, c.s));                                                                                           // two launches
     stem_filter_gradient(c, g, (int)xs[0], sg.Wp, x4.p, dyo.p, Cout, Cout, dw4.p, dw2.p, nullptr, false, spart.p, nullptr);
@@ -959,12 +959,8 @@ int p3d_debug_conv_bn_stats(int device, const float* x, const int64_t xs[5], con
             HIPCHECK(p3d_bn_stats(q ? dy2.p : dy.p, C, (long)rows, C, pq, c.s));
             np[q] = p3d_bn_stats_parts((long)rows, C);
         }
-        BnParams b;
-        float* t = tab.p + (int64_t)q * 4 * C;
         float* m = mv.p + (int64_t)q * 2 * C;
-        b.gamma = gamma.p; b.beta = beta.p; b.moving_mean = m; b.moving_var = m + C;
-        b.statpart = pq; b.nparts = np[q]; b.scale = t; b.shift = t + C; b.mean = t + 2 * C; b.invstd = t + 3 * C; b.C = C;
-        HIPCHECK(p3d_bn_finalize(b, (long)rows, 1, 1, 1e-3f, c.s));
+        HIPCHECK(p3d_bn_finalize(bn_layout(gamma.p, beta.p, m, m + C, tab.p + (int64_t)q * 4 * C, pq, np[q], C), (long)rows, 1, 1, 1e-3f, c.s));
         nparts[q] = small ? 0 : np[q];
     }
     dy.get(y, ny);
@@ -974,9 +970,9 @@ int p3d_debug_conv_bn_stats(int device, const float* x, const int64_t xs[5], con
     API_END
 }
 
-// One normalise / ReLU / add pass of bn_apply (net_ops.inc) on raw inputs, forward and backward.  The launches and their
-// arguments are a literal transcription of bn_apply's forward and backward closures (those read Act / BN objects of a handle,
-// so the argument setup is not shared); the statistics of the non-small paths come from p3d_bn_stats.
+// One normalise / ReLU / add pass of bn_apply (net_ops.inc) on raw inputs, forward and then backward, through the path rule and
+// launch sequences the network itself calls (bn_path, bn_pass_forward / bn_pass_backward, net.hip).  The statistics of the
+// non-small paths come from p3d_bn_stats, standing in for the producer's epilogue.
 int p3d_debug_bn_pass(int device, int mode, int64_t M, int C, const float* y1, const float* y2, const float* params, int batch1,
                       int batch2, int update_moving, const float* dz, int acc2, int path, float* z, float* dy1, float* dy2,
                       float* grads, float* moving, int* info) {
@@ -993,77 +989,26 @@ int p3d_debug_bn_pass(int device, int mode, int64_t M, int C, const float* y1, c
     DevBuf prm(2 * (int64_t)C * nbn, params), mv(2 * (int64_t)C * nbn, moving), tab(4 * (int64_t)C * nbn), grd(2 * (int64_t)C * nbn);
     const int sparts = p3d_bn_stats_parts((long)M, C), bparts = p3d_bn_bwd_parts((long)M, C);
     DevBuf spart((int64_t)sparts * 2 * C * nbn), bpart((int64_t)bparts * 2 * C * nbn), coef(2 * (int64_t)C * nbn);
-    BnParams bp[2];
-    for (int q = 0; q < nbn; ++q) {
-        float* t = tab.p + (int64_t)q * 4 * C;
-        bp[q].gamma = prm.p + (int64_t)q * 2 * C; bp[q].beta = bp[q].gamma + C;
-        bp[q].moving_mean = mv.p + (int64_t)q * 2 * C; bp[q].moving_var = bp[q].moving_mean + C;
-        bp[q].statpart = spart.p + (int64_t)q * sparts * 2 * C; bp[q].nparts = sparts;
-        bp[q].scale = t; bp[q].shift = t + C; bp[q].mean = t + 2 * C; bp[q].invstd = t + 3 * C; bp[q].C = C;
-    }
-    if (!two) bp[1] = BnParams{};
+    // the network's rule, or the forced path -- which must be one the kernels take
+    const int taken = path ? path : bn_path(M, C, false, b1 ? sparts : 0, b2 ? sparts : 0, 0.f);
+    if (taken == BN_SMALL && !p3d_bn_small_ok((long)M, C)) throw P3dError("bn_pass: the small-tensor path does not take this shape");
+    if (taken == BN_FOLD && !p3d_bn_fold_apply_ok((long)M, C, b1 ? sparts : 0, b2 ? sparts : 0, 0.f))
+        throw P3dError("bn_pass: the fold-apply path does not take this shape");
     Ctx c;
-    // the network's rule (bn_is_small, then p3d_bn_fold_apply_ok), or the forced path -- which must be one the kernels take
-    const bool small_ok = p3d_bn_small_ok((long)M, C);
-    const bool fold_ok = p3d_bn_fold_apply_ok((long)M, C, b1 ? sparts : 0, b2 ? sparts : 0, 0.f);
-    const int taken = path ? path : (small_ok ? 1 : (fold_ok ? 2 : 3));
-    if (taken == 1 && !small_ok) throw P3dError("bn_pass: the small-tensor path does not take this shape");
-    if (taken == 2 && !fold_ok) throw P3dError("bn_pass: the fold-apply path does not take this shape");
-    if (taken == 1) {
-        BnSmallArgs a;      // small_args (net_ops.inc)
-        memset(&a, 0, sizeof(a));
-        a.mode = mode; a.M = (int)M; a.C = C;
-        a.y1 = dy1b.p; a.ld1 = C;
-        if (has2) { a.y2 = dy2b.p; a.ld2 = C; }
-        a.bn1 = bp[0];
-        if (two) a.bn2 = bp[1];
-        a.update_moving = update_moving; a.eps = 1e-3f;
-        a.z = zb.p; a.ldz = C;
-        a.dz = dzb.p; a.lddz = C;
-        a.dy1 = g1.p; a.lddy1 = C;
-        if (has2) { a.dy2 = g2.p; a.lddy2 = C; a.acc2 = acc2 ? 1 : 0; }
-        a.dgamma1 = grd.p; a.dbeta1 = grd.p + C;
-        if (two) { a.dgamma2 = grd.p + 2 * C; a.dbeta2 = grd.p + 3 * C; }
-        a.batch1 = b1; a.batch2 = b2;
-        HIPCHECK(p3d_bn_small_fwd(a, c.s));
-        HIPCHECK(p3d_bn_small_bwd(a, c.s));
-    } else {
-        const float* yin[2] = {dy1b.p, dy2b.p};
-        for (int q = 0; q < nbn; ++q)
-            if (q ? b2 : b1) HIPCHECK(p3d_bn_stats(yin[q], C, (long)M, C, spart.p + (int64_t)q * sparts * 2 * C, c.s));
-        BnApplyArgs a;
-        memset(&a, 0, sizeof(a));
-        a.mode = mode; a.M = M; a.C = C;
-        a.y1 = dy1b.p; a.ld1 = C; a.scale1 = bp[0].scale; a.shift1 = bp[0].shift;
-        if (has2) { a.y2 = dy2b.p; a.ld2 = C; }
-        if (two) { a.scale2 = bp[1].scale; a.shift2 = bp[1].shift; }
-        a.z = zb.p; a.ldz = C;
-        if (taken == 2) {
-            HIPCHECK(p3d_bn_fold_apply(a, bp[0], bp[1], b1, b2, update_moving ? 1 : 0, 1e-3f, c.s));
-        } else {
-            HIPCHECK(p3d_bn_finalize(bp[0], (long)M, b1, b1 && update_moving, 1e-3f, c.s));
-            if (two) HIPCHECK(p3d_bn_finalize(bp[1], (long)M, b2, b2 && update_moving, 1e-3f, c.s));
-            HIPCHECK(p3d_bn_apply(a, c.s));
-        }
-        BnBwdArgs g;      // op.bwd (net_ops.inc): reduce, finalize, apply
-        memset(&g, 0, sizeof(g));
-        g.mode = mode; g.M = M; g.C = C;
-        g.dz = dzb.p; g.lddz = C;
-        g.y1 = dy1b.p; g.ld1 = C; g.scale1 = bp[0].scale; g.shift1 = bp[0].shift; g.mean1 = bp[0].mean; g.invstd1 = bp[0].invstd;
-        g.gamma1 = bp[0].gamma; g.dgamma1 = grd.p; g.dbeta1 = grd.p + C; g.batch1 = b1;
-        g.part1 = bpart.p; g.nparts = bparts; g.coef1 = coef.p;
-        g.dy1 = g1.p; g.lddy1 = C; g.acc1 = 0;
-        if (has2) { g.y2 = dy2b.p; g.ld2 = C; g.dy2 = g2.p; g.lddy2 = C; g.acc2 = acc2 ? 1 : 0; }
-        if (two) {
-            g.scale2 = bp[1].scale; g.shift2 = bp[1].shift; g.mean2 = bp[1].mean; g.invstd2 = bp[1].invstd;
-            g.gamma2 = bp[1].gamma; g.dgamma2 = grd.p + 2 * C; g.dbeta2 = grd.p + 3 * C; g.batch2 = b2;
-            g.part2 = bpart.p + (int64_t)bparts * 2 * C; g.coef2 = coef.p + 2 * C;
-        }
-        HIPCHECK(p3d_bn_bwd_reduce(g, c.s));
-        HIPCHECK(p3d_bn_bwd_finalize(g, c.s));
-        HIPCHECK(p3d_bn_bwd_apply(g, c.s));
+    BnPass p;
+    p.mode = mode; p.M = M; p.C = C; p.nparts = bparts;
+    p.y1 = dy1b.p; p.ld1 = C; p.z = zb.p; p.ldz = C; p.dz = dzb.p; p.lddz = C; p.dy1 = g1.p; p.lddy1 = C;
+    if (has2) { p.y2 = dy2b.p; p.ld2 = C; p.dy2 = g2.p; p.lddy2 = C; p.acc2 = acc2 ? 1 : 0; }
+    for (int q = 0; q < nbn; ++q) {
+        const int64_t o = (int64_t)q * 2 * C;
+        p.bn[q] = bn_layout(prm.p + o, prm.p + o + C, mv.p + o, mv.p + o + C, tab.p + 2 * o, spart.p + o * sparts, sparts, C);
+        p.dgamma[q] = grd.p + o; p.dbeta[q] = grd.p + o + C; p.part[q] = bpart.p + o * bparts; p.coef[q] = coef.p + o;
+        p.batch[q] = q ? b2 : b1;
+        if (taken != BN_SMALL && p.batch[q]) HIPCHECK(p3d_bn_stats(q ? p.y2 : p.y1, C, (long)M, C, spart.p + o * sparts, c.s));
     }
-    info[0] = taken; info[1] = taken == 1 ? 0 : sparts; info[2] = taken == 1 ? 0 : bparts;
+    bn_pass_forward(c, p, (BnPath)taken, update_moving != 0);
+    bn_pass_backward(c, p, taken == BN_SMALL);
+    info[0] = taken; info[1] = taken == BN_SMALL ? 0 : sparts; info[2] = taken == BN_SMALL ? 0 : bparts;
     zb.get(z, n);
     g1.get(dy1, n);
     if (has2) g2.get(dy2, n);

@@ -253,11 +253,23 @@
         Op op;
         op.name = opname; op.kind = "bn_apply" + std::to_string(mode);
         const double tens = (double)M * C * 4.0;
-        const std::string kn_apply = "bn_apply_kernel<" + std::to_string(mode) + ">";
-        const std::string kn_red = "bn_bwd_reduce_kernel<" + std::to_string(mode) + ">";
-        const std::string kn_bapply = "bn_bwd_apply_kernel<" + std::to_string(mode) + ">";
         op.flops = 0; op.bytes = tens * (y2 ? 3 : 2);
         op.bflops = 0; op.bbytes = tens * (y2 ? 7 : 5);
+        // the pass on this op's tensors, with the batch flags of the last forward
+        auto mk = [=](const Ctx& c) {
+            BnPass p;
+            p.mode = mode; p.M = M; p.C = C;
+            p.y1 = y1->p; p.ld1 = y1->ld; p.z = out->p; p.ldz = out->ld; p.dz = out->g; p.lddz = out->ld; p.dy1 = y1->g; p.lddy1 = y1->ld;
+            if (y2) { p.y2 = y2->p; p.ld2 = y2->ld; p.dy2 = y2->g; p.lddy2 = y2->ld; p.acc2 = *f2; }
+            BN* const bn[2] = {bn1, bn2};
+            for (int q = 0; q < (two ? 2 : 1); ++q) {
+                p.bn[q] = bn_params(bn[q]); p.dgamma[q] = bn[q]->gamma->g; p.dbeta[q] = bn[q]->beta->g; p.batch[q] = bn[q]->used_batch;
+                p.part[q] = statpart_arena + red_off + (int64_t)q * bwd_parts * 2 * C; p.coef[q] = bnbuf + coef_off + (int64_t)q * 2 * C;
+            }
+            p.nparts = bwd_parts;
+            if (dropout && c.training && c.drop > 0.f) { p.drop_rate = c.drop; p.drop_scale = 1.f / (1.f - c.drop); p.seed = c.seed; p.seed_dev = c.seed_dev; }
+            return p;
+        };
         if (!fused_site) {
             op.owns = {bn1->gamma, bn1->beta};
             if (two) { op.owns.push_back(bn2->gamma); op.owns.push_back(bn2->beta); }
@@ -265,37 +277,11 @@
             if (mode != 0 && mode != 3 && mode != 4) throw P3dError("only the bn -> relu passes inside a bottleneck fuse");
             // reading the (never stored) normalised tensor after a fused forward: the plain apply pass on the published tables
             out->materialize = [=](hipStream_t st) {
-                BnApplyArgs a;
-                memset(&a, 0, sizeof(a));
-                a.mode = mode; a.M = M; a.C = C;
-                a.y1 = y1->p; a.ld1 = y1->ld; a.scale1 = bn1->scale; a.shift1 = bn1->shift;
-                if (y2) { a.y2 = y2->p; a.ld2 = y2->ld; }
-                if (two) { a.scale2 = bn2->scale; a.shift2 = bn2->shift; }
-                a.z = out->p; a.ldz = out->ld;
                 if (mode == 4 && y2->materialize) y2->materialize(st);      // ST_C adds relu(bnS(yS)), itself never stored
-                HIPCHECK(p3d_bn_apply(a, st));
+                HIPCHECK(p3d_bn_apply(bn_apply_args(mk(Ctx())), st));
             };
         }
         const bool small = bn_is_small(M, C, dropout);
-        auto small_args = [=](const Ctx& c) {
-            BnSmallArgs a;
-            memset(&a, 0, sizeof(a));
-            a.mode = mode; a.M = (int)M; a.C = C;
-            a.y1 = y1->p; a.ld1 = y1->ld;
-            if (y2) { a.y2 = y2->p; a.ld2 = y2->ld; }
-            a.bn1 = bn_params(bn1);
-            if (two) a.bn2 = bn_params(bn2);
-            a.update_moving = c.update_moving; a.eps = 1e-3f;
-            a.z = out->p; a.ldz = out->ld;
-            a.dz = out->g; a.lddz = out->ld;
-            a.dy1 = y1->g; a.lddy1 = y1->ld;
-            if (y2) { a.dy2 = y2->g; a.lddy2 = y2->ld; a.acc2 = *f2; }
-            a.dgamma1 = bn1->gamma->g; a.dbeta1 = bn1->beta->g;
-            if (two) { a.dgamma2 = bn2->gamma->g; a.dbeta2 = bn2->beta->g; }
-            return a;
-        };
-        const std::string kn_sf = "bn_small_fwd_kernel<" + std::to_string(mode) + ">";
-        const std::string kn_sb = "bn_small_bwd_kernel<" + std::to_string(mode) + ">";
         const int R = y1->D * y1->H * y1->W;
         op.fwd = [=](const Ctx& c) {
             if (fused_site && c.fuse) return;
@@ -327,106 +313,33 @@
                 launch(c, "gn_apply_kernel(per-sample BN)", 0, tens * (y2 ? 3 : 2), [&]() { return p3d_gn_apply(a, c.s); });
                 return;
             }
-            if (small) {
-                bn1->used_batch = bn1->follows_flag ? c.training : true;
-                if (two) bn2->used_batch = bn2->follows_flag ? c.training : true;
-                BnSmallArgs a = small_args(c);
-                a.batch1 = bn1->used_batch; a.batch2 = two ? bn2->used_batch : 0;
-                launch(c, kn_sf.c_str(), 0, tens * (y2 ? 3 : 2), [&]() { return p3d_bn_small_fwd(a, c.s); });
-                return;
-            }
-            auto fin = [&](BN* bn) {
-                bn->used_batch = bn->follows_flag ? c.training : true;
-                launch(c, "bn_finalize_kernel", 0, 64.0 * bn->C, [&]() {
-                    return p3d_bn_finalize(bn_params(bn), M, bn->used_batch, bn->used_batch && c.update_moving, 1e-3f, c.s);
-                });
-            };
-            BnApplyArgs a;
-            memset(&a, 0, sizeof(a));
-            a.mode = mode; a.M = M; a.C = C;
-            a.y1 = y1->p; a.ld1 = y1->ld; a.scale1 = bn1->scale; a.shift1 = bn1->shift;
-            if (y2) { a.y2 = y2->p; a.ld2 = y2->ld; }
-            if (two) { a.scale2 = bn2->scale; a.shift2 = bn2->shift; }
-            a.z = out->p; a.ldz = out->ld;
-            if (dropout && c.training && c.drop > 0.f) { a.drop_rate = c.drop; a.drop_scale = 1.f / (1.f - c.drop); a.seed = c.seed; a.seed_dev = c.seed_dev; }
-            {   // few statistics partials per channel (stage 2): every apply block folds its own channels' -- one launch, not two or three
-                const bool b1 = bn1->follows_flag ? c.training : true, b2 = two ? (bn2->follows_flag ? c.training : true) : false;
-                if (!c.dry && p3d_bn_fold_apply_ok(M, C, b1 ? bn1->nparts : 0, b2 ? bn2->nparts : 0, a.drop_scale)) {
-                    bn1->used_batch = b1;
-                    if (two) bn2->used_batch = b2;
-                    const BnParams p1 = bn_params(bn1), p2 = two ? bn_params(bn2) : BnParams{};
-                    launch(c, "bn_fold_apply_kernel", 0, tens * (y2 ? 3 : 2), [&]() {
-                        return p3d_bn_fold_apply(a, p1, p2, b1, b2, c.update_moving ? 1 : 0, 1e-3f, c.s);
-                    });
-                    return;
-                }
-            }
-            fin(bn1);
-            if (two) fin(bn2);
-            launch(c, kn_apply.c_str(), 0, tens * (y2 ? 3 : 2), [&]() { return p3d_bn_apply(a, c.s); });
+            bn1->used_batch = bn1->follows_flag ? c.training : true;
+            if (two) bn2->used_batch = bn2->follows_flag ? c.training : true;
+            const BnPass p = mk(c);
+            const BnPath path = small ? BN_SMALL : c.dry ? BN_FINALIZE
+                                      : bn_path(M, C, dropout, p.batch[0] ? p.bn[0].nparts : 0, p.batch[1] ? p.bn[1].nparts : 0, p.drop_scale);
+            bn_pass_forward(c, p, path, c.update_moving);
         };
         {
             auto scope = [](const BN* bn) { const std::string& n = bn->gamma->name; return n.substr(0, n.rfind('/')); };
             op.dec_kind = "bn"; op.dec_name1 = scope(bn1); op.dec_name2 = two ? scope(bn2) : std::string(); op.dec_act = y1;
             op.gates = [=](hipStream_t st, const float* ones, float* o1, float* o2, float* scratch) {
-                if (small) {
-                    BnSmallArgs a;
-                    memset(&a, 0, sizeof(a));
-                    a.mode = mode; a.M = (int)M; a.C = C; a.y1 = y1->p; a.ld1 = y1->ld;
-                    if (y2) { a.y2 = y2->p; a.ld2 = y2->ld; }
-                    a.bn1 = bn_params(bn1);
-                    if (two) a.bn2 = bn_params(bn2);
-                    a.batch1 = 0; a.batch2 = 0; a.eps = 1e-3f;
-                    a.dz = ones; a.lddz = C; a.dy1 = o1; a.lddy1 = C; a.dy2 = o2; a.lddy2 = C; a.acc2 = 0;
-                    a.dgamma1 = scratch; a.dbeta1 = scratch + C; a.dgamma2 = scratch + 2 * C; a.dbeta2 = scratch + 3 * C;
-                    HIPCHECK(p3d_bn_small_bwd(a, st));
-                    return;
-                }
-                BnBwdArgs a;
-                memset(&a, 0, sizeof(a));
-                a.mode = mode; a.M = M; a.C = C; a.dz = ones; a.lddz = C;
-                a.y1 = y1->p; a.ld1 = y1->ld; a.scale1 = bn1->scale; a.shift1 = bn1->shift; a.mean1 = bn1->mean; a.invstd1 = bn1->invstd;
-                a.gamma1 = bn1->gamma->p; a.batch1 = 0; a.dy1 = o1; a.lddy1 = C;
-                if (y2) { a.y2 = y2->p; a.ld2 = y2->ld; a.dy2 = o2; a.lddy2 = C; }
-                if (two) {
-                    a.scale2 = bn2->scale; a.shift2 = bn2->shift; a.mean2 = bn2->mean; a.invstd2 = bn2->invstd;
-                    a.gamma2 = bn2->gamma->p; a.batch2 = 0;
-                }
-                HIPCHECK(p3d_bn_bwd_apply(a, st));       // (dropout sites: the gate alone -- the keep pattern is the tests' own input)
+                BnPass p = mk(Ctx());      // (dropout sites: the gate alone -- the keep pattern is the tests' own input)
+                p.dz = ones; p.lddz = C; p.dy1 = o1; p.lddy1 = C; p.dy2 = o2; p.lddy2 = C; p.acc2 = 0;
+                p.dgamma[0] = scratch; p.dbeta[0] = scratch + C; p.dgamma[1] = scratch + 2 * C; p.dbeta[1] = scratch + 3 * C;
+                p.batch[0] = p.batch[1] = 0;
+                if (small) HIPCHECK(p3d_bn_small_bwd(bn_small_args(p, false), st));
+                else HIPCHECK(p3d_bn_bwd_apply(bn_bwd_args(p), st));
             };
         }
         op.bwd = [=](const Ctx& c) {
             if (fused_site && c.fuse_bwd) return;
-            if (small) {
-                BnSmallArgs sa = small_args(c);
-                sa.batch1 = bn1->used_batch; sa.batch2 = two ? bn2->used_batch : 0;
-                launch(c, kn_sb.c_str(), 0, tens * (y2 ? 5 : 3), [&]() { return p3d_bn_small_bwd(sa, c.s); });
-                return;
-            }
-            BnBwdArgs a;
-            memset(&a, 0, sizeof(a));
-            a.mode = mode; a.M = M; a.C = C;
-            a.dz = out->g; a.lddz = out->ld;
-            a.y1 = y1->p; a.ld1 = y1->ld; a.scale1 = bn1->scale; a.shift1 = bn1->shift; a.mean1 = bn1->mean; a.invstd1 = bn1->invstd;
-            a.gamma1 = bn1->gamma->p; a.dgamma1 = bn1->gamma->g; a.dbeta1 = bn1->beta->g; a.batch1 = bn1->used_batch;
-            a.part1 = statpart_arena + red_off; a.nparts = bwd_parts; a.coef1 = bnbuf + coef_off;
-            a.dy1 = y1->g; a.lddy1 = y1->ld; a.acc1 = 0;
-            if (y2) { a.y2 = y2->p; a.ld2 = y2->ld; a.dy2 = y2->g; a.lddy2 = y2->ld; a.acc2 = *f2; }
-            if (two) {
-                a.scale2 = bn2->scale; a.shift2 = bn2->shift; a.mean2 = bn2->mean; a.invstd2 = bn2->invstd;
-                a.gamma2 = bn2->gamma->p; a.dgamma2 = bn2->gamma->g; a.dbeta2 = bn2->beta->g; a.batch2 = bn2->used_batch;
-                a.part2 = statpart_arena + red_off + (int64_t)bwd_parts * 2 * C; a.coef2 = bnbuf + coef_off + 2 * C;
-            }
-            if (dropout && c.training && c.drop > 0.f) { a.drop_rate = c.drop; a.drop_scale = 1.f / (1.f - c.drop); a.seed = c.seed; a.seed_dev = c.seed_dev; }
-            launch(c, kn_red.c_str(), 0, tens * (y2 ? 3 : 2), [&]() { return p3d_bn_bwd_reduce(a, c.s); });
-            launch(c, "bn_bwd_finalize_kernel", 0, 64.0 * C, [&]() { return p3d_bn_bwd_finalize(a, c.s); });
-            if (mode == 0 && y1->stem_link && y1->stem_link->enabled && !(a.drop_scale > 0.f)) {
-                // the stem: dy is read by the conv's filter gradient only, which evaluates this pass on its operand (stem_wgrad.hip)
-                y1->stem_link->args = a;
-                y1->stem_link->pending = true;
-                return;
-            }
-            launch(c, kn_bapply.c_str(), 0, tens * (y2 ? 5 : 3), [&]() { return p3d_bn_bwd_apply(a, c.s); });
+            const BnPass p = mk(c);
+            // the stem: dy is read by the conv's filter gradient only, which evaluates the apply launch on its operand (stem_wgrad.hip)
+            StemBnLink* stem = y1->stem_link.get();
+            const bool to_stem = stem && stem->enabled && mode == 0 && !small && !(p.drop_scale > 0.f);
+            bn_pass_backward(c, p, small, to_stem ? &stem->args : nullptr);
+            if (to_stem) stem->pending = true;
         };
         ops.push_back(op);
         return out;
