@@ -4,7 +4,8 @@
 Same flags (train.py:21-45), same step semantics (train.py:217-218: dropout 0.5, training=True, Adam lr,
 Smooth-L1 sum), same periodic eval forward (train.py:225-226) and checkpoint cadence (train.py:266-267).  Two flags are
 additions the reference does not have: `--loss bce | l1` trains with sigmoid cross-entropy on the head's logits or the L1
-sum instead of Smooth-L1 (P3DSession.set_loss); `--regularization weightdecay | l2 | both` adds the weight-decay and L2
+sum instead of Smooth-L1, and `--loss kld | kld_cc` with the per-map KL divergence, plus `--cc-weight` times (1 - CC) for
+kld_cc (P3DSession.set_loss); `--regularization weightdecay | l2 | both` adds the weight-decay and L2
 terms the reference builds and leaves commented out of its loss (train.py:161, gn/train_p3d_gn_dataset.py:188-189;
 P3DSession.set_regularization).  The dataset loaders (dataflow.py, tensorpack, cv2) are out of scope
 (SURVEY.md 2.1): clips come either from `--data clips.npz` (arrays x [N,16,112,112,3] already normalised like
@@ -55,9 +56,12 @@ def get_arguments():
     p.add_argument("--steps", type=int, default=20, help="steps per epoch when synthetic")
     p.add_argument("--validclips", type=int, default=4, help="validation batches per validation pass when synthetic")
     # not a reference flag (its flags are train.py:21-45): the loss option of P3DSession.set_loss
-    p.add_argument("--loss", choices=("smooth_l1", "bce", "l1"), default="smooth_l1",
+    p.add_argument("--loss", choices=("smooth_l1", "bce", "l1", "kld", "kld_cc"), default="smooth_l1",
                    help="[addition, no reference flag] training loss: smooth_l1 (the reference's, train.py:159), bce (sigmoid "
-                        "cross-entropy on the head's logits, summed; no reference counterpart) or l1 (L1 sum, train.py:160)")
+                        "cross-entropy on the head's logits, summed; no reference counterpart), l1 (L1 sum, train.py:160), kld "
+                        "(KL divergence of every predicted / ground-truth map, utils/metrics.py:338-361, summed) or kld_cc "
+                        "(kld + cc-weight * (1 - CC), utils/metrics.py:227-250)")
+    p.add_argument("--cc-weight", type=float, default=1.0, help="[addition] weight of the (1 - CC) term of --loss kld_cc")
     # not a reference flag either: the regularisation option of P3DSession.set_regularization
     p.add_argument("--regularization", choices=("none", "weightdecay", "l2", "both"), default="none",
                    help="[addition, no reference flag] terms added to the loss: weightdecay (mean of wd * l2_loss over the "
@@ -135,7 +139,14 @@ def main():
     sess = P3DSession(structure, batch=args.batch, frames=args.videolength, height=args.imagesize[0], width=args.imagesize[1],
                       device=int(args.gpu), seed=0)                                  # graph + global_variables_initializer
     sess.set_adam(args.lr)
-    sess.set_loss(args.loss)
+    try:
+        if args.loss == "kld_cc":
+            sess.set_loss(args.loss, cc_weight=args.cc_weight)
+        else:
+            sess.set_loss(args.loss)
+    except (P3dError, ValueError) as e:
+        sess.close()
+        raise SystemExit("--loss %s: %s" % (args.loss, e))
     terms = {"none": (), "weightdecay": ("weightdecay",), "l2": ("l2",), "both": ("weightdecay", "l2")}[args.regularization]
     try:
         sess.set_regularization(terms, wd=args.wd, l2=args.l2)

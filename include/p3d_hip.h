@@ -131,9 +131,22 @@ int p3d_set_attention_mode(p3d_handle* h, int mode);
  *                       reference counterpart (BASELINE.json configs[2]).  On the heads without a sigmoid (concat and the
  *                       GroupNorm nets) the raw output is taken as the logits, the only meaning the loss can have there;
  *   P3D_LOSS_L1         L1 sum |pred - y| (the reference's commented-out alternative, train.py:160).
+ *   P3D_LOSS_KLD_CC     per-map saliency loss, sum over the B*T maps (one [H, W] frame of one clip each) of
+ *                       w_kld KL_m + w_cc (1 - CC_m) (weights: p3d_set_loss_weights, default 1 and 1).  With s the predicted
+ *                       saliency, p = s / sum s and q = y / sum y (each left as it is when its sum is 0, the reference's
+ *                       `if map.any()`): KL_m = sum q log(eps + q / (p + eps)), eps 2.2204e-16 (utils/metrics.py:338-361, the
+ *                       sum of its `score`), and CC_m the Pearson correlation of s and y (utils/metrics.py:227-250) from
+ *                       centred sums; a map whose s or y is constant has no CC and adds 0 to the CC term and its gradient.
+ *                       Statistics and gradients are float64 on the float32 maps (the reference's KLdiv is float32).  s is
+ *                       the stored pred on the sigmoid heads; on the heads without a sigmoid (concat and the GroupNorm nets)
+ *                       the raw output is read through a sigmoid, s = 1/(1+exp(-z)), as P3D_LOSS_BCE takes it as logits.
  * Any other kind, or a null handle: -1.  Drops a captured step graph; the next step captures anew. */
 enum { P3D_LOSS_SMOOTH_L1 = 0, P3D_LOSS_BCE = 1, P3D_LOSS_L1 = 2 };
+enum { P3D_LOSS_KLD_CC = 3 };
 int p3d_set_loss(p3d_handle* h, int kind);
+/* The weights of P3D_LOSS_KLD_CC (default 1, 1): finite, not negative, not both 0; else -1.  They reach the kernels as launch
+ * arguments: a change drops a captured step graph. */
+int p3d_set_loss_weights(p3d_handle* h, float kld_weight, float cc_weight);
 
 /* Regularisation terms added to the loss of p3d_train_step, p3d_backward, p3d_train_step_device and p3d_profile_step: the two
  * collections the reference builds and leaves out of its loss (train.py:161, gn/train_p3d_gn_dataset.py:188-189), as opt-in.
@@ -334,6 +347,13 @@ int p3d_debug_smooth_l1(int device, const float* pred, const float* target, int6
  * P3D_LOSS_SMOOTH_L1 is p3d_debug_smooth_l1 (logits unused).  *loss is added to. */
 int p3d_debug_loss(int device, int kind, const float* logits, const float* pred, const float* target, int64_t n, int through_sigmoid,
                    int offset, double* loss, float* dlogits, int* info);
+/* Test hook: P3D_LOSS_KLD_CC as the network launches it (its three launches) on `maps` maps of map_elems elements each,
+ * logits, pred and target placed as p3d_debug_loss places them; through_sigmoid: s = pred, else s = sigmoid(logits) (pred
+ * unused).  *loss is added to; per_map [maps][2] = KL_m, CC_m (NaN where CC is undefined); dlogits = dL/dlogits.
+ * info[3] = launches, blocks per map, path taken (1 float4, 2 scalar). */
+int p3d_debug_map_loss(int device, const float* logits, const float* pred, const float* target, int64_t maps, int64_t map_elems,
+                       int through_sigmoid, int offset, float kld_weight, float cc_weight, double* loss, float* dlogits,
+                       double* per_map, int* info);
 /* Test hook: one Adam launch (p3d_adam, as the network's optimiser step launches it) on n elements placed `offset` elements
  * into the device buffers (p3d_adam refuses a base that is not 16-byte aligned).  p, m, v are updated in place from g with
  * the bias-corrected step size of step t (the network's adam_step_size), passed as an argument or, when lr_on_device, through

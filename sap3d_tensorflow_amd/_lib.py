@@ -11,6 +11,9 @@ LIB_PATH = os.environ.get("P3D_LIB") or os.path.join(_HERE, "libp3dhip.so")
 P3D_COMM_ID_BYTES = 128
 # p3d_set_loss kinds (include/p3d_hip.h P3D_LOSS_*)
 LOSSES = {"smooth_l1": 0, "bce": 1, "l1": 2}
+# the per-map loss P3D_LOSS_KLD_CC under its names: (kld_weight, cc_weight) of p3d_set_loss_weights
+P3D_LOSS_KLD_CC = 3
+MAP_LOSSES = {"kld": (1.0, 0.0), "kld_cc": (1.0, 1.0)}
 # p3d_set_regularization terms (include/p3d_hip.h P3D_REG_*)
 REGULARIZATION = {"weightdecay": 1, "l2": 2}
 
@@ -57,6 +60,7 @@ SIGNATURES = {
     "p3d_set_bn_fusion": (C.c_int, [C.c_void_p, C.c_int]),
     "p3d_set_attention_mode": (C.c_int, [C.c_void_p, C.c_int]),
     "p3d_set_loss": (C.c_int, [C.c_void_p, C.c_int]),
+    "p3d_set_loss_weights": (C.c_int, [C.c_void_p, C.c_float, C.c_float]),
     "p3d_set_regularization": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float]),
     "p3d_last_regularization": (C.c_int, [C.c_void_p, _dp]),
     "p3d_param_regularization": (C.c_int, [C.c_void_p, C.c_char_p, _fp, _fp]),
@@ -99,6 +103,8 @@ SIGNATURES = {
                                  C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _ip]),
     "p3d_debug_smooth_l1": (C.c_int, [C.c_int, _fp, _fp, C.c_int64, C.c_int, C.c_int, _dp, _fp, _ip]),
     "p3d_debug_loss": (C.c_int, [C.c_int, C.c_int, _fp, _fp, _fp, C.c_int64, C.c_int, C.c_int, _dp, _fp, _ip]),
+    "p3d_debug_map_loss": (C.c_int, [C.c_int, _fp, _fp, _fp, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_float, _dp,
+                                     _fp, _dp, _ip]),
     "p3d_debug_adam_decay": (C.c_int, [C.c_int, _fp, _fp, _fp, _fp, C.c_int64, C.c_int, _i64p, _i64p, _fp, C.c_int, C.c_float,
                                        C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, _dp, _fp]),
     "p3d_debug_adam": (C.c_int, [C.c_int, _fp, _fp, _fp, _fp, C.c_int64, C.c_int, C.c_float, C.c_int64, C.c_float, C.c_float,

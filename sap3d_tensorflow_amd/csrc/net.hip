@@ -924,6 +924,9 @@ struct p3d_handle {
     float* d_dlogits = nullptr;
     double* d_loss = nullptr;
     int loss_kind = P3D_LOSS_SMOOTH_L1;      // p3d_set_loss
+    float kld_weight = 1.f, cc_weight = 1.f;  // p3d_set_loss_weights (P3D_LOSS_KLD_CC)
+    double* d_map_scratch = nullptr;          // P3D_LOSS_KLD_CC: per-map statistics and block partials, planned in head()
+    unsigned* d_map_cnt = nullptr;            //   and its arrival counters (zero between launches)
     float lr = 1e-4f, b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
     int64_t step = 0;
 

@@ -309,12 +309,25 @@ int p3d_set_attention_mode(p3d_handle* h, int mode) {
 int p3d_set_loss(p3d_handle* h, int kind) {
     API_BEGIN
     if (!h) throw P3dError("null handle");
-    if (kind != P3D_LOSS_SMOOTH_L1 && kind != P3D_LOSS_BCE && kind != P3D_LOSS_L1)
-        throw P3dError("loss kind is 0 (Smooth-L1), 1 (sigmoid cross-entropy on the logits) or 2 (L1 sum), not " +
-                       std::to_string(kind));
+    if (kind != P3D_LOSS_SMOOTH_L1 && kind != P3D_LOSS_BCE && kind != P3D_LOSS_L1 && kind != P3D_LOSS_KLD_CC)
+        throw P3dError("loss kind is 0 (Smooth-L1), 1 (sigmoid cross-entropy on the logits), 2 (L1 sum) or 3 (per-map KL + CC), "
+                       "not " + std::to_string(kind));
     HIPCHECK(hipSetDevice(h->cfg.device));
     h->loss_kind = kind;
     h->drop_step_graph();      // a captured step names the loss kernel it was captured with
+    API_END
+}
+
+int p3d_set_loss_weights(p3d_handle* h, float kld_weight, float cc_weight) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    if (!std::isfinite(kld_weight) || !std::isfinite(cc_weight) || kld_weight < 0.f || cc_weight < 0.f)
+        throw P3dError("loss weights must be finite and not negative");
+    if (kld_weight == 0.f && cc_weight == 0.f) throw P3dError("loss weights: both are 0");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->kld_weight = kld_weight;
+    h->cc_weight = cc_weight;
+    h->drop_step_graph();      // the weights are launch arguments of the captured loss launches
     API_END
 }
 
@@ -1199,6 +1212,7 @@ int p3d_debug_loss(int device, int kind, const float* logits, const float* pred,
                    int offset, double* loss, float* dlogits, int* info) {
     API_BEGIN
     if (kind == P3D_LOSS_SMOOTH_L1) return p3d_debug_smooth_l1(device, pred, target, n, through_sigmoid, offset, loss, dlogits, info);
+    if (kind == P3D_LOSS_KLD_CC) throw P3dError("loss: kind 3 (per-map KL + CC) needs the map geometry: p3d_debug_map_loss");
     if (kind != P3D_LOSS_BCE && kind != P3D_LOSS_L1) throw P3dError("loss: kind is 0, 1 or 2");
     HIPCHECK(hipSetDevice(device));
     if (!logits || !pred || !target || !loss || !dlogits || !info) throw P3dError("null argument");
@@ -1215,6 +1229,46 @@ int p3d_debug_loss(int device, int kind, const float* logits, const float* pred,
     HIPCHECK(copy_now(dlogits, db.p + offset, (size_t)n * 4, hipMemcpyDeviceToHost, nullptr));
     HIPCHECK(copy_now(loss, lb.p, sizeof(double), hipMemcpyDeviceToHost, nullptr));
     info[0] = (int)done[0]; info[1] = (int)done[1];
+    API_END
+}
+
+// The per-map loss (run_map_loss in net_sched.inc) on raw inputs, placed as p3d_debug_loss places them, with scratch sized and
+// zeroed as the handle plans it.
+int p3d_debug_map_loss(int device, const float* logits, const float* pred, const float* target, int64_t maps, int64_t map_elems,
+                       int through_sigmoid, int offset, float kld_weight, float cc_weight, double* loss, float* dlogits,
+                       double* per_map, int* info) {
+    API_BEGIN
+    HIPCHECK(hipSetDevice(device));
+    if (!logits || !target || !loss || !dlogits || !per_map || !info || (through_sigmoid && !pred)) throw P3dError("null argument");
+    if (maps < 1 || map_elems < 1 || offset < 0 || offset > 3) throw P3dError("map loss: bad geometry or offset");
+    if (maps * map_elems > ((int64_t)1 << 31)) throw P3dError("map loss: more than 2^31 elements");
+    const int64_t n = maps * map_elems;
+    size_t md = 0, mc = 0;
+    p3d_map_loss_scratch(maps, map_elems, &md, &mc);
+    DevBuf zb(n + offset), pb(n + offset), tb(n + offset), db(n + offset), lb(2), sb(2 * (int64_t)md), cb((int64_t)mc);
+    HIPCHECK(copy_now(zb.p + offset, logits, (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
+    if (through_sigmoid) HIPCHECK(copy_now(pb.p + offset, pred, (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
+    HIPCHECK(copy_now(tb.p + offset, target, (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
+    HIPCHECK(copy_now(lb.p, loss, sizeof(double), hipMemcpyHostToDevice, nullptr));
+    double* scratch = reinterpret_cast<double*>(sb.p);
+    const MapLossArgs a = p3d_map_loss_args(zb.p + offset, pb.p + offset, tb.p + offset, maps, map_elems, through_sigmoid ? 1 : 0,
+                                            kld_weight, cc_weight, reinterpret_cast<double*>(lb.p), db.p + offset, scratch,
+                                            reinterpret_cast<unsigned*>(cb.p));
+    for (int stage = 0; stage < 3; ++stage) HIPCHECK(p3d_map_loss_launch(stage, a, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    std::vector<double> ms((size_t)maps * P3D_MAP_STATS);
+    HIPCHECK(copy_now(ms.data(), scratch, ms.size() * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    std::vector<unsigned> cnt(mc);
+    HIPCHECK(copy_now(cnt.data(), cb.p, mc * sizeof(unsigned), hipMemcpyDeviceToHost, nullptr));
+    for (unsigned v : cnt)
+        if (v) throw P3dError("map loss: an arrival counter was left nonzero");
+    for (int64_t m = 0; m < maps; ++m) {
+        per_map[2 * m] = ms[(size_t)m * P3D_MAP_STATS + 2];
+        per_map[2 * m + 1] = ms[(size_t)m * P3D_MAP_STATS + 3];
+    }
+    HIPCHECK(copy_now(dlogits, db.p + offset, (size_t)n * 4, hipMemcpyDeviceToHost, nullptr));
+    HIPCHECK(copy_now(loss, lb.p, sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    info[0] = 3; info[1] = a.blocks; info[2] = a.vec4 ? 1 : 2;
     API_END
 }
 

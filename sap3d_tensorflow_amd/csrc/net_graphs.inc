@@ -486,6 +486,13 @@
         d_dlogits = dalloc<float>(pred->rows());
         d_y = dalloc<float>(pred->rows());
         d_loss = dalloc<double>(1);
+        {   // the per-map loss's scratch, sized from the B*T maps of H*W: a step allocates nothing (captured steps stay valid)
+            size_t md = 0, mc = 0;
+            p3d_map_loss_scratch((long long)pred->N * pred->D, (long long)pred->H * pred->W, &md, &mc);
+            d_map_scratch = dalloc<double>((int64_t)md);
+            d_map_cnt = dalloc<unsigned>((int64_t)mc);
+            HIPCHECK(fill_now(d_map_cnt, 0, mc * sizeof(unsigned), stream));
+        }
         char* xflag = consume(x);
         Op op;
         op.name = "results"; op.kind = transpose ? "head_deconv" : "head_conv";

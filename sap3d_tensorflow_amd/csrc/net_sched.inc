@@ -30,6 +30,7 @@
     }
     void run_loss(const Ctx& c) {
         HIPCHECK(fill_async(d_loss, 0, sizeof(double), c.s, "loss"));
+        if (loss_kind == P3D_LOSS_KLD_CC) return run_map_loss(c);
         if (loss_kind != P3D_LOSS_SMOOTH_L1) return run_loss_option(c);
         launch(c, "smooth_l1_kernel", 0, 12.0 * pred->rows(), [&]() { return p3d_smooth_l1(pred->p, d_y, pred->rows(), d_loss, d_dlogits, head_sigmoid ? 1 : 0, c.s); });
     }
@@ -45,6 +46,20 @@
         const double bytes = rows * (bce && ts ? 16.0 : 12.0);
         launch(c, bce ? "sigmoid_ce_kernel" : "l1_loss_kernel", flops, bytes,
                [&]() { return p3d_loss(loss_kind, logits->p, pred->p, d_y, pred->rows(), d_loss, d_dlogits, ts, c.s); });
+    }
+    // P3D_LOSS_KLD_CC (map_loss.hip): w_kld KL + w_cc (1 - CC) per [H, W] map, summed over the B*T maps of this rank, so the
+    // summed gradients under data parallelism are still the global batch's.  Three launches over the same grid; each reads s
+    // (pred, or the raw output through a sigmoid: +3 operations) and the target.  Per element: sums 2 operations; terms ~18
+    // (two double divisions, a log, the centred products); dlogits ~20, and a store.
+    void run_map_loss(const Ctx& c) {
+        const double rows = (double)pred->rows();
+        const int ts = head_sigmoid ? 1 : 0;
+        const double sg = ts ? 0.0 : 3.0;
+        const MapLossArgs a = p3d_map_loss_args(logits->p, pred->p, d_y, (long long)pred->N * pred->D, (long long)pred->H * pred->W, ts,
+                                                kld_weight, cc_weight, d_loss, d_dlogits, d_map_scratch, d_map_cnt);
+        launch(c, "map_loss_sums_kernel", rows * (2.0 + sg), rows * 8.0, [&]() { return p3d_map_loss_launch(0, a, c.s); });
+        launch(c, "map_loss_terms_kernel", rows * (18.0 + sg), rows * 8.0, [&]() { return p3d_map_loss_launch(1, a, c.s); });
+        launch(c, "map_loss_grad_kernel", rows * (20.0 + sg), rows * 12.0, [&]() { return p3d_map_loss_launch(2, a, c.s); });
     }
     // with_adam: the optimiser step is part of the call and split in two -- every variable but the first op's (and those its
     // backward reads, adam_split) is updated while that op's filter gradient (the stem's: the last launch of the pass, alone on

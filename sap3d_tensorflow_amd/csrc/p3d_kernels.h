@@ -504,6 +504,29 @@ hipError_t p3d_smooth_l1(const float* pred, const float* target, long n, double*
 hipError_t p3d_loss(int kind, const float* logits, const float* pred, const float* target, long n, double* loss_out,
                     float* dlogits, int through_sigmoid, hipStream_t s, unsigned* done = nullptr);
 
+// ---- per-map saliency losses (map_loss.hip; p3d_set_loss P3D_LOSS_KLD_CC) ------------------------------------------------
+// `maps` maps of N = map_elems consecutive elements; s = pred (through_sigmoid) or 1/(1+expf(-logits)).  Three stages in
+// order on one stream: 0 sums, 1 terms (+= the weighted loss into *loss_out), 2 dlogits.  Scratch: p3d_map_loss_scratch's
+// doubles and counters, the counters zero before the first launch (every stage leaves them zero).  mstat[m] holds
+// S, Y, KL_m, CC_m (NaN where undefined), sum g p, A, B, C, the map's loss term.
+constexpr int P3D_MAP_STATS = 10;
+constexpr long long P3D_MAP_LOSS_ELEMS_PER_BLOCK = 2048;
+struct MapLossArgs {
+    const float* logits; const float* pred; const float* target;
+    float* dlogits; double* loss_out;
+    long long maps, N;
+    int blocks;                  // per map: p3d_map_loss_blocks(N)
+    int through_sigmoid, vec4;
+    float kld_weight, cc_weight;
+    double* mstat; double* part; unsigned* cnt;
+};
+int p3d_map_loss_blocks(long long map_elems);
+void p3d_map_loss_scratch(long long maps, long long map_elems, size_t* doubles, size_t* counters);
+MapLossArgs p3d_map_loss_args(const float* logits, const float* pred, const float* target, long long maps, long long map_elems,
+                              int through_sigmoid, float kld_weight, float cc_weight, double* loss_out, float* dlogits,
+                              double* scratch, unsigned* counters);
+hipError_t p3d_map_loss_launch(int stage, const MapLossArgs& a, hipStream_t s);
+
 // ---- Adam (tf.train.AdamOptimizer, epsilon-hat form; train.py:168) ------------------------------
 // lr_dev non-null: the bias-corrected step size is read from device memory (captured step graphs), lr_t is ignored.
 // p, g, m, v must be 16-byte aligned (hipErrorInvalidValue otherwise): the kernel moves four elements at a time.

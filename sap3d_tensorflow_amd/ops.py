@@ -259,6 +259,27 @@ def loss(kind, logits, pred, target, through_sigmoid=True, offset=0, loss=0.0, d
     return acc.value, dl, tuple(info)
 
 
+def map_loss(logits, pred, target, maps, map_elems, through_sigmoid=True, offset=0, kld_weight=1.0, cc_weight=1.0, loss=0.0,
+             device=0):
+    """Test hook: the per-map loss P3D_LOSS_KLD_CC as the network launches it (p3d_debug_map_loss) on `maps` maps of map_elems
+    consecutive elements of flat float32 logits / pred / target, placed `offset` elements into the device buffers; s = pred
+    when through_sigmoid, else sigmoid(logits).  Returns (loss + the weighted sum, in double; dL/dlogits; per_map [maps, 2] =
+    KL_m, CC_m (NaN where CC is undefined); (launches, blocks per map, path taken: 1 float4 / 2 scalar))."""
+    z, t = _f32(logits).ravel(), _f32(target).ravel()
+    p = _f32(pred).ravel() if pred is not None else z
+    n = int(maps) * int(map_elems)
+    if not (z.size == p.size == t.size == n):
+        raise ValueError("logits, pred and target must hold maps * map_elems elements")
+    dl = np.empty(n, np.float32)
+    per_map = np.empty((int(maps), 2), np.float64)
+    acc = C.c_double(float(loss))
+    info = (C.c_int * 3)()
+    check(lib().p3d_debug_map_loss(device, fptr(z), fptr(p), fptr(t), int(maps), int(map_elems), 1 if through_sigmoid else 0,
+                                   int(offset), float(kld_weight), float(cc_weight), C.byref(acc), fptr(dl),
+                                   per_map.ctypes.data_as(C.POINTER(C.c_double)), info))
+    return acc.value, dl, per_map, tuple(info)
+
+
 def adam(p, g, m, v, t, lr=1e-4, b1=0.9, b2=0.999, eps=1e-8, lr_on_device=False, offset=0, device=0):
     """Test hook: one launch of the network's Adam kernel (p3d_debug_adam) on flat float32 arrays, step t (1-based).  Returns
     (p, m, v after the step, the float32 step size lr * sqrt(1 - b2^t) / (1 - b1^t) it used)."""

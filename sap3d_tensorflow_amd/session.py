@@ -223,12 +223,30 @@ class P3DSession:
         chip, "auto" picks per block by the size of the score matrix."""
         check(lib().p3d_set_attention_mode(self._h, {"auto": 0, "gemm": 1, "flash": 2}[mode]))
 
-    def set_loss(self, name="smooth_l1"):
+    def set_loss(self, name="smooth_l1", kld_weight=None, cc_weight=None):
         """The training loss of train_step / backward / train_step_device / profile_step: "smooth_l1" (the reference's,
         train.py:159; default), "bce" (sigmoid cross-entropy on the head's logits, summed; no reference counterpart -- on the
-        heads without a sigmoid the raw output is taken as the logits) or "l1" (L1 sum, the reference's train.py:160)."""
+        heads without a sigmoid the raw output is taken as the logits), "l1" (L1 sum, the reference's train.py:160), or the
+        per-map saliency losses "kld" (KL divergence of each [H, W] map, utils/metrics.py:338-361) and "kld_cc" (KL + (1 - CC),
+        utils/metrics.py:227-250), summed over the maps with the weights of _lib.MAP_LOSSES unless kld_weight / cc_weight are
+        given.  The per-map losses read the heads without a sigmoid through one (include/p3d_hip.h P3D_LOSS_KLD_CC)."""
+        if name in _lib.MAP_LOSSES:
+            kw, cw = _lib.MAP_LOSSES[name]
+            kw = kw if kld_weight is None else kld_weight
+            cw = cw if cc_weight is None else cc_weight
+            try:
+                kw, cw = float(kw), float(cw)
+            except (TypeError, ValueError):
+                raise ValueError("loss weights must be numbers, not %r, %r" % (kld_weight, cc_weight))
+            if not (np.isfinite(kw) and np.isfinite(cw)) or kw < 0 or cw < 0 or (kw == 0 and cw == 0):
+                raise ValueError("loss weights must be finite, not negative and not both 0: %r, %r" % (kw, cw))
+            check(lib().p3d_set_loss_weights(self._h, kw, cw))
+            check(lib().p3d_set_loss(self._h, _lib.P3D_LOSS_KLD_CC))
+            return
         if name not in _lib.LOSSES:
-            raise ValueError("loss %r: have %s" % (name, sorted(_lib.LOSSES)))
+            raise ValueError("loss %r: have %s" % (name, sorted(_lib.LOSSES) + sorted(_lib.MAP_LOSSES)))
+        if kld_weight is not None or cc_weight is not None:
+            raise ValueError("loss %r has no weights (they are for %s)" % (name, sorted(_lib.MAP_LOSSES)))
         check(lib().p3d_set_loss(self._h, _lib.LOSSES[name]))
 
     def set_regularization(self, terms=("weightdecay",), wd=None, l2=None):
