@@ -7,8 +7,10 @@ additions the reference does not have: `--loss bce | l1` trains with sigmoid cro
 sum instead of Smooth-L1, and `--loss kld | kld_cc` with the per-map KL divergence, plus `--cc-weight` times (1 - CC) for
 kld_cc (P3DSession.set_loss); `--regularization weightdecay | l2 | both` adds the weight-decay and L2
 terms the reference builds and leaves commented out of its loss (train.py:161, gn/train_p3d_gn_dataset.py:188-189;
-P3DSession.set_regularization).  The dataset loaders (dataflow.py, tensorpack, cv2) are out of scope
-(SURVEY.md 2.1): clips come either from `--data clips.npz` (arrays x [N,16,112,112,3] already normalised like
+P3DSession.set_regularization); `--optimizer momentum | sgd` (with `--momentum`, `--nesterov`) fine-tunes with the
+optimisers the reference's --pretrain help names, and `--optimizer-state` saves and restores the optimiser's slots with the
+checkpoints (P3DSession.set_optimizer, save_checkpoint / restore optimizer_state).  The dataset loaders (dataflow.py,
+tensorpack, cv2) are out of scope: clips come either from `--data clips.npz` (arrays x [N,16,112,112,3] already normalised like
 dataflow.py:204-208, y [N,16,112,112]; raw uint8 frames go through sap3d_tensorflow_amd.dataflow.mapf_frames first) or
 are synthetic with the loader's value law.
 Checkpoints are TensorFlow-1.x V2 bundles `model/<info>/p3d_<step>.ckpt.*` with a `checkpoint` state file, keyed by the
@@ -71,6 +73,16 @@ def get_arguments():
     p.add_argument("--wd", type=float, default=0.0,
                    help="[addition] weight-decay scale; 0 = the reference's (0.001 BatchNorm nets, 0.0005 GroupNorm nets)")
     p.add_argument("--l2", type=float, default=0.0, help="[addition] l2 scale; 0 = the reference's 0.0005")
+    # the optimiser the reference's --pretrain help names ("finetune using SGD", train.py:27; gn/train_p3d_gn_dataset.py:61
+    # prints Momentum) but never builds: P3DSession.set_optimizer
+    p.add_argument("--optimizer", choices=("adam", "momentum", "sgd"), default="adam",
+                   help="[addition] adam (tf.train.AdamOptimizer, the reference's, train.py:168), momentum "
+                        "(tf.train.MomentumOptimizer(lr, --momentum)) or sgd (tf.train.GradientDescentOptimizer(lr))")
+    p.add_argument("--momentum", type=float, default=0.9, help="[addition] momentum of --optimizer momentum")
+    p.add_argument("--nesterov", action="store_true", help="[addition] Nesterov momentum (--optimizer momentum only)")
+    p.add_argument("--optimizer-state", action="store_true",
+                   help="[addition] checkpoints hold the optimiser's slots under their TF names (<var>/Adam, <var>/Adam_1 and "
+                        "beta1_power / beta2_power; <var>/Momentum), and --pretrain restores them: a run resumes its optimiser")
     return p.parse_args()
 
 
@@ -139,6 +151,15 @@ def main():
     sess = P3DSession(structure, batch=args.batch, frames=args.videolength, height=args.imagesize[0], width=args.imagesize[1],
                       device=int(args.gpu), seed=0)                                  # graph + global_variables_initializer
     sess.set_adam(args.lr)
+    if args.nesterov and args.optimizer != "momentum":
+        sess.close()
+        raise SystemExit("--nesterov needs --optimizer momentum")
+    if args.optimizer != "adam":
+        try:
+            sess.set_optimizer(args.optimizer, lr=args.lr, momentum=args.momentum, use_nesterov=args.nesterov)
+        except (P3dError, ValueError) as e:
+            sess.close()
+            raise SystemExit("--optimizer %s: %s" % (args.optimizer, e))
     try:
         if args.loss == "kld_cc":
             sess.set_loss(args.loss, cc_weight=args.cc_weight)
@@ -157,7 +178,7 @@ def main():
     os.makedirs(model_dir, exist_ok=True)
     if args.pretrain:
         print(args.pretrain, "Using this model to retrain...")
-        sess.restore(args.pretrain)                                                 # train.py:204-210
+        sess.restore(args.pretrain, optimizer_state=args.optimizer_state)          # train.py:204-210
     print("Start training")
     step = 0
     for xs, ys in batches(args, np.random.default_rng(0)):
@@ -170,7 +191,7 @@ def main():
         if step % args.validiter == 0:
             validate(sess, args, step)                                              # train.py:243-264
         if step % args.saveiter == 0:
-            sess.save_checkpoint(model_dir, step, keep=10)                          # train.py:180-185,266-267
+            sess.save_checkpoint(model_dir, step, keep=10, optimizer_state=args.optimizer_state)     # train.py:180-185,266-267
     print("Training Finished!")
     sess.close()
 

@@ -171,6 +171,28 @@ int p3d_param_regularization(p3d_handle* h, const char* name, float* c_wd, float
 /* tf.train.AdamOptimizer(lr, beta1, beta2, epsilon) (train.py:168; defaults 1e-4, .9, .999, 1e-8). */
 int p3d_set_adam(p3d_handle* h, float lr, float beta1, float beta2, float eps);
 
+/* The optimiser of the train step: tf.train.AdamOptimizer (P3D_OPT_ADAM, the default), tf.train.MomentumOptimizer(lr, momentum,
+ * use_nesterov) (P3D_OPT_MOMENTUM) or tf.train.GradientDescentOptimizer(lr) (P3D_OPT_SGD).  The reference documents --pretrain
+ * as "finetune using SGD" (train.py:27) and its GroupNorm trainer names Momentum (gn/train_p3d_gn_dataset.py:61).
+ *   Momentum  accum = accum * momentum + g; var -= lr * accum, or with use_nesterov var -= g * lr + accum * momentum * lr
+ *             on the updated accum (TF's ApplyMomentum); SGD var -= lr * g (ApplyGradientDescent).  Float32, every product
+ *             and sum rounded on its own (no fused multiply-add).
+ * Switching kind gives a fresh optimiser: its slots and step count are zeroed, as a newly built TF optimiser has them.  The same
+ * kind with new hyper-parameters keeps the state.  P3D_OPT_ADAM takes lr and keeps beta1, beta2, epsilon from p3d_set_adam
+ * (which is unchanged).  The optimiser still runs as two parts after their all-reduces, and a regularisation term fuses into
+ * it as it does into Adam.  Returns -1 for an unknown kind, a non-finite lr or momentum, or a negative momentum.
+ * p3d_init_params zeroes the slots and the step count of every kind. */
+enum { P3D_OPT_ADAM = 0, P3D_OPT_MOMENTUM = 1, P3D_OPT_SGD = 2 };
+int p3d_set_optimizer(p3d_handle* h, int kind, float lr, float momentum, int use_nesterov);
+/* Optimiser slots of the trainable variable `var`, count = its element count: Adam slot 0 is m (TF's <var>/Adam), slot 1 is
+ * v (<var>/Adam_1); Momentum slot 0 is the accumulator (<var>/Momentum); SGD has none.  -1 for a slot the current kind
+ * lacks, a non-trainable or unknown variable, or a wrong count. */
+int p3d_get_slot(p3d_handle* h, const char* var, int slot, float* host, int64_t count);
+int p3d_set_slot(p3d_handle* h, const char* var, int slot, const float* host, int64_t count);
+/* Completed optimiser steps t (every kind); Adam's next step uses the bias correction of step t + 1.  Setting needs t >= 0. */
+int p3d_get_optimizer_step(p3d_handle* h, int64_t* t);
+int p3d_set_optimizer_step(p3d_handle* h, int64_t t);
+
 /* ---- intermediate tensors (tf fetches of graph tensors; parity/debug taps).  Names:
  *      conv1_custom, conv1_custom_bn_relu, pool1..pool4, block<i>/conv1_bn_relu, block<i>/st,
  *      block<i>/out, deconv3_re, deconv4_conv1, logits, pred. */
@@ -368,6 +390,16 @@ int p3d_debug_adam_decay(int device, float* p, float* g, float* m, float* v, int
                          int lr_on_device, int update, double* term, float* lr_t);
 int p3d_debug_adam(int device, float* p, const float* g, float* m, float* v, int64_t n, int offset, float lr, int64_t t, float b1,
                    float b2, float eps, int lr_on_device, float* lr_t);
+/* Test hooks: one Momentum or SGD launch (kind P3D_OPT_MOMENTUM / P3D_OPT_SGD, as the network's optimiser step launches it) on
+ * n elements placed `offset` (0..3) elements into the device buffers; m is the accumulator (untouched by SGD).  The step size
+ * lr is passed as an argument or, when lr_on_device, through device memory as a captured train step passes it.  The decay
+ * variant is p3d_debug_adam_decay's launch with this update: g becomes g + c*p per tile, and with update p (and m) take the
+ * step on it; *term as there. */
+int p3d_debug_optimizer(int device, int kind, float* p, float* g, float* m, int64_t n, int offset, float lr, float momentum,
+                        int use_nesterov, int lr_on_device);
+int p3d_debug_optimizer_decay(int device, int kind, float* p, float* g, float* m, int64_t n, int offset, const int64_t* tile_off,
+                              const int64_t* tile_len, const float* tile_c, int ntile, float lr, float momentum, int use_nesterov,
+                              int lr_on_device, int update, double* term);
 int p3d_debug_stat_parts(const int64_t xshape[5], const int64_t wshape[5], const int s[3], int transpose, int* written, int* cap);
 int p3d_debug_igemm_groupable(const int64_t xshape[5], const int64_t wshape[5], const int s[3]);
 int p3d_op_max_pool3d(int device, const float* x, const int64_t xshape[5], const int ksize[3], const int s[3], float* y);

@@ -16,6 +16,9 @@ P3D_LOSS_KLD_CC = 3
 MAP_LOSSES = {"kld": (1.0, 0.0), "kld_cc": (1.0, 1.0)}
 # p3d_set_regularization terms (include/p3d_hip.h P3D_REG_*)
 REGULARIZATION = {"weightdecay": 1, "l2": 2}
+# p3d_set_optimizer kinds (include/p3d_hip.h P3D_OPT_*) and the TF slot names of each kind's slots 0, 1 (<var>/<suffix>)
+OPTIMIZERS = {"adam": 0, "momentum": 1, "sgd": 2}
+SLOT_NAMES = {"adam": ("Adam", "Adam_1"), "momentum": ("Momentum",), "sgd": ()}
 
 
 class P3dConfig(C.Structure):
@@ -73,6 +76,11 @@ SIGNATURES = {
     "p3d_train_step": (C.c_int, [C.c_void_p, _fp, _fp, C.c_float, C.c_uint64, _fp]),
     "p3d_backward": (C.c_int, [C.c_void_p, _fp, _fp, C.c_float, C.c_uint64, _fp, _fp]),
     "p3d_set_adam": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float]),
+    "p3d_set_optimizer": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int]),
+    "p3d_get_slot": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, _fp, C.c_int64]),
+    "p3d_set_slot": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, _fp, C.c_int64]),
+    "p3d_get_optimizer_step": (C.c_int, [C.c_void_p, _i64p]),
+    "p3d_set_optimizer_step": (C.c_int, [C.c_void_p, C.c_int64]),
     "p3d_activation_info": (C.c_int, [C.c_void_p, C.c_char_p, _i64p]),
     "p3d_get_activation": (C.c_int, [C.c_void_p, C.c_char_p, _fp, C.c_int64]),
     "p3d_upload_inputs": (C.c_int, [C.c_void_p, _fp, _fp]),
@@ -107,6 +115,9 @@ SIGNATURES = {
                                      _fp, _dp, _ip]),
     "p3d_debug_adam_decay": (C.c_int, [C.c_int, _fp, _fp, _fp, _fp, C.c_int64, C.c_int, _i64p, _i64p, _fp, C.c_int, C.c_float,
                                        C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, _dp, _fp]),
+    "p3d_debug_optimizer": (C.c_int, [C.c_int, C.c_int, _fp, _fp, _fp, C.c_int64, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int]),
+    "p3d_debug_optimizer_decay": (C.c_int, [C.c_int, C.c_int, _fp, _fp, _fp, C.c_int64, C.c_int, _i64p, _i64p, _fp, C.c_int, C.c_float,
+                                            C.c_float, C.c_int, C.c_int, C.c_int, _dp]),
     "p3d_debug_adam": (C.c_int, [C.c_int, _fp, _fp, _fp, _fp, C.c_int64, C.c_int, C.c_float, C.c_int64, C.c_float, C.c_float,
                                  C.c_float, C.c_int, _fp]),
     "p3d_debug_stat_parts": (C.c_int, [_i64p, _i64p, _ip, C.c_int, _ip, _ip]),

@@ -612,6 +612,71 @@ __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, flo
     }
 }
 
+// tf.train.MomentumOptimizer / GradientDescentOptimizer (p3d_set_optimizer): TF's ApplyMomentum and ApplyGradientDescent with
+// every rounding written out -- contraction off and no fma anywhere, so that a numpy float32 replay is bit-exact:
+//   momentum  a = (a * mom) + g;  p = p - (lr * a)
+//   nesterov  a = (a * mom) + g;  p = p - ((g * lr) + ((a * mom) * lr))      (the updated a)
+//   sgd       p = p - (lr * g)
+// The same arithmetic on whole 4-groups and on the scalar tail of a range.
+enum { UPD_NONE = -1, UPD_ADAM = 0, UPD_MOMENTUM = 1, UPD_SGD = 2 };      // the update kinds: P3D_OPT_* of include/p3d_hip.h
+template <int KIND>      // UPD_MOMENTUM or UPD_SGD
+__device__ __forceinline__ void opt_elem(float& p, float& a, float g, float lr_t, float mom, int nesterov) {
+#pragma clang fp contract(off)
+    if (KIND == UPD_SGD) {
+        p = p - lr_t * g;
+        return;
+    }
+    a = a * mom + g;
+    if (nesterov) p = p - (g * lr_t + (a * mom) * lr_t);
+    else p = p - lr_t * a;
+}
+
+// float4 grid-stride pass shaped like adam_kernel (n4 groups of four from element `head`, the last group cut at n); the `head`
+// (0..3) elements before the buffers' first 16-byte boundary go one by one in block 0.  SGD never touches m.
+template <int KIND>
+__device__ __forceinline__ void opt_body(float* p, const float* g, float* m, long long n4, long long n, int head, float lr_t,
+                                         float mom, int nesterov) {
+    if (blockIdx.x == 0 && (int)threadIdx.x < head) {
+        const int q = threadIdx.x;
+        float pq = p[q], mq = KIND == UPD_MOMENTUM ? m[q] : 0.f;
+        opt_elem<KIND>(pq, mq, g[q], lr_t, mom, nesterov);
+        if (KIND == UPD_MOMENTUM) m[q] = mq;
+        p[q] = pq;
+    }
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+        const long long e = head + (i << 2);
+        if (e + 3 < n) {
+            const float4 gg = ld4(g + e), pp = ld4(p + e);
+            const float gs[4] = {gg.x, gg.y, gg.z, gg.w};
+            float ps[4] = {pp.x, pp.y, pp.z, pp.w}, ms[4] = {0.f, 0.f, 0.f, 0.f};
+            if (KIND == UPD_MOMENTUM) {
+                const float4 mm = ld4(m + e);
+                ms[0] = mm.x; ms[1] = mm.y; ms[2] = mm.z; ms[3] = mm.w;
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) opt_elem<KIND>(ps[q], ms[q], gs[q], lr_t, mom, nesterov);
+            if (KIND == UPD_MOMENTUM) st4(m + e, make_float4(ms[0], ms[1], ms[2], ms[3]));
+            st4(p + e, make_float4(ps[0], ps[1], ps[2], ps[3]));
+        } else {
+            for (long long q = e; q < n; ++q) {
+                float pq = p[q], mq = KIND == UPD_MOMENTUM ? m[q] : 0.f;
+                opt_elem<KIND>(pq, mq, g[q], lr_t, mom, nesterov);
+                if (KIND == UPD_MOMENTUM) m[q] = mq;
+                p[q] = pq;
+            }
+        }
+    }
+}
+// one kernel per kind: the launch lists and the profiles name them
+__global__ __launch_bounds__(256) void momentum_kernel(float* p, const float* g, float* m, long long n4, long long n, int head,
+                                                       float lr_arg, const float* lr_dev, float mom, int use_nesterov) {
+    opt_body<UPD_MOMENTUM>(p, g, m, n4, n, head, lr_dev ? *lr_dev : lr_arg, mom, use_nesterov);
+}
+__global__ __launch_bounds__(256) void sgd_kernel(float* p, const float* g, long long n4, long long n, int head, float lr_arg,
+                                                  const float* lr_dev) {
+    opt_body<UPD_SGD>(p, g, nullptr, n4, n, head, lr_dev ? *lr_dev : lr_arg, 0.f, 0);
+}
+
 // Regularisation (p3d_adam_decay).  Every rounding is explicit, so that a numpy float32 replay is bit-exact: contraction is
 // off and the two fused multiply-adds are fmaf.  adam_kernel's own arithmetic, as this compiler contracts it: on a whole
 // float4 group m and v are single fmas over the rounded (1-b) g terms; on the scalar tail of a range nothing is fused.
@@ -632,11 +697,14 @@ __device__ __forceinline__ void adam_elem(float& p, float& m, float& v, float g,
 // One block per tile of uniform coefficient c: g' = g + c p (written back where c != 0), Adam on g' when UPDATE, and the tile's
 // 0.5 c sum(p^2) in double from the parameters before the update.  Elements of a 4-group shared with the neighbouring tile
 // (variables whose length is not a multiple of 4 end mid-group) go one by one, with the arithmetic of the group they are in.
-template <bool UPDATE>
+// KIND: the update on g', UPD_NONE for the gradient-only mode; Momentum keeps its accumulator in m, v is Adam's alone.
+template <int KIND>
 __device__ __forceinline__ void decay_body(float* p, float* g, float* m, float* v, long long n, const P3dRegTile* tiles,
                                            long long tile_base, float lr_arg, const float* lr_dev, float b1, float b2, float eps,
-                                           double* part, const double* fold_part, int nfold, unsigned* counter, double* term) {
+                                           double* part, const double* fold_part, int nfold, unsigned* counter, double* term,
+                                           float mom = 0.f, int nesterov = 0) {
 #pragma clang fp contract(off)
+    constexpr bool UPDATE = KIND != UPD_NONE, ADAM = KIND == UPD_ADAM;
     __shared__ double wsum[4];
     __shared__ int last_flag;
     const P3dRegTile t = tiles[blockIdx.x];
@@ -657,13 +725,23 @@ __device__ __forceinline__ void decay_body(float* p, float* g, float* m, float* 
                 }
                 st4(g + e, make_float4(gs[0], gs[1], gs[2], gs[3]));
             }
-            if (UPDATE) {
+            if (ADAM) {
                 const float4 mm = ld4(m + e), vv = ld4(v + e);
                 float ms[4] = {mm.x, mm.y, mm.z, mm.w}, vs[4] = {vv.x, vv.y, vv.z, vv.w};
 #pragma unroll
                 for (int q = 0; q < 4; ++q) adam_elem(ps[q], ms[q], vs[q], gs[q], lr_t, b1, b2, eps, true);
                 st4(m + e, make_float4(ms[0], ms[1], ms[2], ms[3]));
                 st4(v + e, make_float4(vs[0], vs[1], vs[2], vs[3]));
+                st4(p + e, make_float4(ps[0], ps[1], ps[2], ps[3]));
+            } else if (UPDATE) {
+                float ms[4] = {0.f, 0.f, 0.f, 0.f};
+                if (KIND == UPD_MOMENTUM) {
+                    const float4 mm = ld4(m + e);
+                    ms[0] = mm.x; ms[1] = mm.y; ms[2] = mm.z; ms[3] = mm.w;
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) opt_elem<KIND>(ps[q], ms[q], gs[q], lr_t, mom, nesterov);
+                if (KIND == UPD_MOMENTUM) st4(m + e, make_float4(ms[0], ms[1], ms[2], ms[3]));
                 st4(p + e, make_float4(ps[0], ps[1], ps[2], ps[3]));
             }
         }
@@ -676,10 +754,15 @@ __device__ __forceinline__ void decay_body(float* p, float* g, float* m, float* 
                     ge = ge + c * pe;
                     g[e] = ge;
                 }
-                if (UPDATE) {
+                if (ADAM) {
                     float me = m[e], ve = v[e];
                     adam_elem(pe, me, ve, ge, lr_t, b1, b2, eps, (e & ~3LL) + 3 < n);
                     m[e] = me; v[e] = ve; p[e] = pe;
+                } else if (UPDATE) {
+                    float me = KIND == UPD_MOMENTUM ? m[e] : 0.f;
+                    opt_elem<KIND>(pe, me, ge, lr_t, mom, nesterov);
+                    if (KIND == UPD_MOMENTUM) m[e] = me;
+                    p[e] = pe;
                 }
             }
         }
@@ -703,12 +786,24 @@ __global__ __launch_bounds__(256) void adam_decay_kernel(float* p, float* g, flo
                                                          long long tile_base, float lr_arg, const float* lr_dev, float b1, float b2,
                                                          float eps, double* part, const double* fold_part, int nfold,
                                                          unsigned* counter, double* term) {
-    decay_body<true>(p, g, m, v, n, tiles, tile_base, lr_arg, lr_dev, b1, b2, eps, part, fold_part, nfold, counter, term);
+    decay_body<UPD_ADAM>(p, g, m, v, n, tiles, tile_base, lr_arg, lr_dev, b1, b2, eps, part, fold_part, nfold, counter, term);
+}
+__global__ __launch_bounds__(256) void momentum_decay_kernel(float* p, float* g, float* m, long long n, const P3dRegTile* tiles,
+                                                             long long tile_base, float lr_arg, const float* lr_dev, float mom,
+                                                             int use_nesterov, double* part, const double* fold_part, int nfold,
+                                                             unsigned* counter, double* term) {
+    decay_body<UPD_MOMENTUM>(p, g, m, nullptr, n, tiles, tile_base, lr_arg, lr_dev, 0.f, 0.f, 0.f, part, fold_part, nfold, counter, term, mom,
+                  use_nesterov);
+}
+__global__ __launch_bounds__(256) void sgd_decay_kernel(float* p, float* g, long long n, const P3dRegTile* tiles, long long tile_base,
+                                                        float lr_arg, const float* lr_dev, double* part, const double* fold_part,
+                                                        int nfold, unsigned* counter, double* term) {
+    decay_body<UPD_SGD>(p, g, nullptr, nullptr, n, tiles, tile_base, lr_arg, lr_dev, 0.f, 0.f, 0.f, part, fold_part, nfold, counter, term);
 }
 __global__ __launch_bounds__(256) void decay_grad_kernel(float* p, float* g, long long n, const P3dRegTile* tiles, long long tile_base,
                                                          double* part, const double* fold_part, int nfold, unsigned* counter,
                                                          double* term) {
-    decay_body<false>(p, g, nullptr, nullptr, n, tiles, tile_base, 0.f, nullptr, 0.f, 0.f, 0.f, part, fold_part, nfold, counter, term);
+    decay_body<UPD_NONE>(p, g, nullptr, nullptr, n, tiles, tile_base, 0.f, nullptr, 0.f, 0.f, 0.f, part, fold_part, nfold, counter, term);
 }
 
 __global__ __launch_bounds__(256) void add_inplace_kernel(float* dst, int lddst, const float* src, int ldsrc, long long M, int C, int copy) {
@@ -1156,6 +1251,40 @@ hipError_t p3d_adam(float* p, const float* g, float* m, float* v, long n, float 
         return hipErrorInvalidValue;
     const long long n4 = ((long long)n + 3) / 4;
     hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n4)), dim3(256), 0, s, p, g, m, v, n4, (long long)n, lr_t, lr_dev, b1, b2, eps);
+    return hipGetLastError();
+}
+
+hipError_t p3d_optimizer(int kind, float* p, const float* g, float* m, long n, float lr, const float* lr_dev, float momentum,
+                         int use_nesterov, hipStream_t s) {
+    // p, g, m float-aligned and at the same place in a 16-byte line: the elements before the first 16-byte boundary go one by one
+    const uintptr_t r = reinterpret_cast<uintptr_t>(p) & 15;
+    if (n < 1 || (kind != 1 && kind != 2) || (kind == 1 && !m) || (r & 3) || (reinterpret_cast<uintptr_t>(g) & 15) != r ||
+        (kind == 1 && (reinterpret_cast<uintptr_t>(m) & 15) != r))
+        return hipErrorInvalidValue;
+    const int head = (int)std::min<long long>((long long)((16 - r) & 15) / 4, (long long)n);
+    const long long n4 = ((long long)n - head + 3) / 4;
+    const unsigned grid = n4 > 0 ? grid_for(n4) : 1u;
+    if (kind == 1)
+        hipLaunchKernelGGL(momentum_kernel, dim3(grid), dim3(256), 0, s, p, g, m, n4, (long long)n, head, lr, lr_dev, momentum,
+                           use_nesterov ? 1 : 0);
+    else
+        hipLaunchKernelGGL(sgd_kernel, dim3(grid), dim3(256), 0, s, p, g, n4, (long long)n, head, lr, lr_dev);
+    return hipGetLastError();
+}
+
+hipError_t p3d_optimizer_decay(int kind, float* p, float* g, float* m, long n, const P3dRegTile* tiles, int ntile, long long tile_base,
+                               float lr, const float* lr_dev, float momentum, int use_nesterov, double* part, const double* fold_part,
+                               int nfold, unsigned* counter, double* term, hipStream_t s) {
+    if (n < 1 || ntile < 1 || !tiles || !part || (kind != 1 && kind != 2) || (kind == 1 && !m) ||
+        (nfold > 0 && (!fold_part || !counter || !term)) ||
+        ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(kind == 1 ? m : p)) & 15))
+        return hipErrorInvalidValue;
+    if (kind == 1)
+        hipLaunchKernelGGL(momentum_decay_kernel, dim3(ntile), dim3(256), 0, s, p, g, m, (long long)n, tiles, tile_base, lr, lr_dev,
+                           momentum, use_nesterov ? 1 : 0, part, fold_part, nfold, counter, term);
+    else
+        hipLaunchKernelGGL(sgd_decay_kernel, dim3(ntile), dim3(256), 0, s, p, g, (long long)n, tiles, tile_base, lr, lr_dev, part,
+                           fold_part, nfold, counter, term);
     return hipGetLastError();
 }
 

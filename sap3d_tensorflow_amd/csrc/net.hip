@@ -928,7 +928,9 @@ struct p3d_handle {
     double* d_map_scratch = nullptr;          // P3D_LOSS_KLD_CC: per-map statistics and block partials, planned in head()
     unsigned* d_map_cnt = nullptr;            //   and its arrival counters (zero between launches)
     float lr = 1e-4f, b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
-    int64_t step = 0;
+    int64_t step = 0;                         // completed optimiser steps (every kind)
+    int opt_kind = P3D_OPT_ADAM;              // p3d_set_optimizer: Momentum keeps its accumulator in flat_m
+    float momentum = 0.9f; int use_nesterov = 0;
 
     ncclComm_t comm = nullptr;
     hipEvent_t ev_bucket = nullptr, ev_comm_done = nullptr;

@@ -463,6 +463,76 @@ int p3d_set_adam(p3d_handle* h, float lr, float beta1, float beta2, float eps) {
     API_END
 }
 
+int p3d_set_optimizer(p3d_handle* h, int kind, float lr, float momentum, int use_nesterov) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    if (kind != P3D_OPT_ADAM && kind != P3D_OPT_MOMENTUM && kind != P3D_OPT_SGD)
+        throw P3dError("optimizer kind " + std::to_string(kind) + ": have 0 (adam), 1 (momentum), 2 (sgd)");
+    if (!std::isfinite(lr) || !std::isfinite(momentum) || momentum < 0.f)
+        throw P3dError("optimizer: lr and momentum must be finite and momentum not negative");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    if (kind != h->opt_kind) {      // a fresh optimiser: zero slots, step 0
+        HIPCHECK(hipStreamSynchronize(h->stream));
+        HIPCHECK(hipStreamSynchronize(h->side_stream));
+        HIPCHECK(hipStreamSynchronize(h->comm_stream));
+        HIPCHECK(hipMemsetAsync(h->flat_m, 0, (size_t)h->n_train * 4, h->stream));
+        HIPCHECK(hipMemsetAsync(h->flat_v, 0, (size_t)h->n_train * 4, h->stream));
+        HIPCHECK(hipStreamSynchronize(h->stream));
+        h->step = 0;
+    }
+    h->opt_kind = kind;
+    h->lr = lr;
+    h->momentum = momentum;
+    h->use_nesterov = use_nesterov ? 1 : 0;
+    API_END
+}
+
+// an optimiser slot of a trainable variable: its range of flat_m (slot 0) or flat_v (slot 1)
+static float* slot_ptr(p3d_handle* h, const char* var, int slot, int64_t count) {
+    Param* p = find_param(h, var, count);
+    if (!p->trainable) throw P3dError(std::string(var) + " is not trainable: it has no optimiser slots");
+    const int nslots = h->opt_kind == P3D_OPT_ADAM ? 2 : h->opt_kind == P3D_OPT_MOMENTUM ? 1 : 0;
+    if (slot < 0 || slot >= nslots)
+        throw P3dError("slot " + std::to_string(slot) + ": the current optimiser has " + std::to_string(nslots) + " slot(s)");
+    return (slot == 0 ? h->flat_m : h->flat_v) + p->off;
+}
+
+int p3d_get_slot(p3d_handle* h, const char* var, int slot, float* host, int64_t count) {
+    API_BEGIN
+    if (!host) throw P3dError("null argument");
+    float* d = slot_ptr(h, var, slot, count);
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    HIPCHECK(copy_now(host, d, (size_t)count * 4, hipMemcpyDeviceToHost, h->stream));
+    API_END
+}
+
+int p3d_set_slot(p3d_handle* h, const char* var, int slot, const float* host, int64_t count) {
+    API_BEGIN
+    if (!host) throw P3dError("null argument");
+    float* d = slot_ptr(h, var, slot, count);
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    HIPCHECK(hipStreamSynchronize(h->stream));      // as p3d_set_param: nothing else orders this copy after a running step
+    HIPCHECK(hipStreamSynchronize(h->side_stream));
+    HIPCHECK(hipStreamSynchronize(h->comm_stream));
+    HIPCHECK(copy_now(d, host, (size_t)count * 4, hipMemcpyHostToDevice, h->stream));
+    API_END
+}
+
+int p3d_get_optimizer_step(p3d_handle* h, int64_t* t) {
+    API_BEGIN
+    if (!h || !t) throw P3dError("null argument");
+    *t = h->step;
+    API_END
+}
+
+int p3d_set_optimizer_step(p3d_handle* h, int64_t t) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    if (t < 0) throw P3dError("optimizer step " + std::to_string(t) + " is negative");
+    h->step = t;
+    API_END
+}
+
 int p3d_activation_info(p3d_handle* h, const char* name, int64_t shape[5]) {
     API_BEGIN
     if (!h || !name) throw P3dError("null argument");
@@ -1294,6 +1364,68 @@ int p3d_debug_adam(int device, float* p, const float* g, float* m, float* v, int
     float* outd[3] = {pb.p, mb.p, vb.p};
     for (int q = 0; q < 3; ++q) HIPCHECK(copy_now(out[q], outd[q] + offset, (size_t)n * 4, hipMemcpyDeviceToHost, nullptr));
     *lr_t = step;
+    API_END
+}
+
+// One Momentum / SGD launch (adam_range in net_sched.inc under those kinds), placed as p3d_debug_adam places its buffers.
+int p3d_debug_optimizer(int device, int kind, float* p, float* g, float* m, int64_t n, int offset, float lr, float momentum,
+                        int use_nesterov, int lr_on_device) {
+    API_BEGIN
+    HIPCHECK(hipSetDevice(device));
+    if (!p || !g || !m) throw P3dError("null argument");
+    if (kind != P3D_OPT_MOMENTUM && kind != P3D_OPT_SGD) throw P3dError("optimizer: kind 1 (momentum) or 2 (sgd); Adam has p3d_debug_adam");
+    if (n < 1 || offset < 0 || offset > 3) throw P3dError("optimizer: bad length or offset");
+    DevBuf pb(n + offset), gb(n + offset), mb(n + offset), lrb(1);
+    float* host[3] = {p, g, m};
+    float* dev[3] = {pb.p, gb.p, mb.p};
+    for (int q = 0; q < 3; ++q) HIPCHECK(copy_now(dev[q] + offset, host[q], (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
+    if (lr_on_device) HIPCHECK(p3d_set_step_scalars(nullptr, lrb.p, 0, lr, nullptr));
+    // from device memory the argument must not matter (as p3d_debug_adam)
+    HIPCHECK(p3d_optimizer(kind, pb.p + offset, gb.p + offset, mb.p + offset, (long)n, lr_on_device ? NAN : lr,
+                           lr_on_device ? lrb.p : nullptr, momentum, use_nesterov, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    for (int q = 0; q < 3; ++q) HIPCHECK(copy_now(host[q], dev[q] + offset, (size_t)n * 4, hipMemcpyDeviceToHost, nullptr));
+    API_END
+}
+
+// p3d_debug_adam_decay with Momentum / SGD as the update (decay_range under those kinds; update = 0 is the gradient-only launch).
+int p3d_debug_optimizer_decay(int device, int kind, float* p, float* g, float* m, int64_t n, int offset, const int64_t* tile_off,
+                              const int64_t* tile_len, const float* tile_c, int ntile, float lr, float momentum, int use_nesterov,
+                              int lr_on_device, int update, double* term) {
+    API_BEGIN
+    HIPCHECK(hipSetDevice(device));
+    if (!p || !g || !m || !tile_off || !tile_len || !tile_c || !term) throw P3dError("null argument");
+    if (kind != P3D_OPT_MOMENTUM && kind != P3D_OPT_SGD)
+        throw P3dError("optimizer_decay: kind 1 (momentum) or 2 (sgd); Adam has p3d_debug_adam_decay");
+    if (n < 1 || offset < 0 || offset > 3 || ntile < 1) throw P3dError("optimizer_decay: bad length, offset or tile count");
+    std::vector<P3dRegTile> tiles((size_t)ntile);
+    int64_t at = 0;
+    for (int k = 0; k < ntile; ++k) {
+        if (tile_off[k] != at || tile_len[k] < 1 || tile_len[k] > (1 << 30)) throw P3dError("optimizer_decay: tiles must cover [0, n) in order");
+        tiles[k] = {(long long)tile_off[k], (int)tile_len[k], tile_c[k]};
+        at += tile_len[k];
+    }
+    if (at != n) throw P3dError("optimizer_decay: tiles must cover [0, n) in order");
+    DevBuf pb(n + offset), gb(n + offset), mb(n + offset), lrb(1), tb(4 * (int64_t)ntile), part(2 * (int64_t)ntile), scal(4);
+    float* host[3] = {p, g, m};
+    float* dev[3] = {pb.p, gb.p, mb.p};
+    for (int q = 0; q < 3; ++q) HIPCHECK(copy_now(dev[q] + offset, host[q], (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
+    HIPCHECK(copy_now(tb.p, tiles.data(), tiles.size() * sizeof(P3dRegTile), hipMemcpyHostToDevice, nullptr));
+    // scal (zeroed): [0..1] the term, [2] the fold's counter
+    if (lr_on_device) HIPCHECK(p3d_set_step_scalars(nullptr, lrb.p, 0, lr, nullptr));
+    double* dterm = reinterpret_cast<double*>(scal.p);
+    double* dpart = reinterpret_cast<double*>(part.p);
+    P3dRegTile* dt = reinterpret_cast<P3dRegTile*>(tb.p);
+    unsigned* cnt = reinterpret_cast<unsigned*>(scal.p + 2);
+    if (update)
+        HIPCHECK(p3d_optimizer_decay(kind, pb.p + offset, gb.p + offset, mb.p + offset, (long)n, dt, ntile, 0, lr_on_device ? NAN : lr,
+                                     lr_on_device ? lrb.p : nullptr, momentum, use_nesterov, dpart, dpart, ntile, cnt, dterm, nullptr));
+    else      // the gradient-only launch is the same under every kind
+        HIPCHECK(p3d_adam_decay(pb.p + offset, gb.p + offset, mb.p + offset, mb.p + offset, (long)n, dt, ntile, 0, 0.f, nullptr, 0.f,
+                                0.f, 0.f, 0, dpart, dpart, ntile, cnt, dterm, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    for (int q = 0; q < 3; ++q) HIPCHECK(copy_now(host[q], dev[q] + offset, (size_t)n * 4, hipMemcpyDeviceToHost, nullptr));
+    HIPCHECK(copy_now(term, dterm, sizeof(double), hipMemcpyDeviceToHost, nullptr));
     API_END
 }
 

@@ -246,8 +246,11 @@
     float cur_lr_t = 0.f;
     int64_t adam_split = 0;              // flat offset below which only the first op's variables live (0: no split)
     hipEvent_t ev_side_early = nullptr, ev_comm_early = nullptr;
+    // The optimiser (p3d_set_optimizer) runs as the same two parts under every kind; only the kernel differs.  Its step size
+    // for step t: Adam's bias-corrected one, the constant lr for Momentum and SGD.
+    float opt_step_size(int64_t t) const { return opt_kind == P3D_OPT_ADAM ? adam_step_size(lr, b1, b2, t) : lr; }
     void adam_begin(const Ctx& c) {      // c.lr_dev set: the step size comes from device memory (graph replay), `step` is the caller's
-        cur_lr_t = c.lr_dev ? 0.f : adam_step_size(lr, b1, b2, ++step);
+        cur_lr_t = c.lr_dev ? 0.f : opt_step_size(++step);
     }
     void adam_range(const Ctx& c, int64_t lo, int64_t hi) {
         if (hi <= lo) return;
@@ -255,6 +258,13 @@
         if (skip) return;
         if (reg_terms) return decay_range(c, lo, hi, true);
         const float lr_t = cur_lr_t;
+        if (opt_kind != P3D_OPT_ADAM) {      // Momentum: g, a, p read, a, p written (20 bytes); SGD: g, p read, p written (12)
+            launch(c, opt_kind == P3D_OPT_MOMENTUM ? "momentum_kernel" : "sgd_kernel", 0,
+                   (opt_kind == P3D_OPT_MOMENTUM ? 20.0 : 12.0) * (hi - lo), [&]() {
+                return p3d_optimizer(opt_kind, flat_p + lo, flat_g + lo, flat_m + lo, hi - lo, lr_t, c.lr_dev, momentum, use_nesterov, c.s);
+            });
+            return;
+        }
         launch(c, "adam_kernel", 0, 28.0 * (hi - lo), [&]() {
             return p3d_adam(flat_p + lo, flat_g + lo, flat_m + lo, flat_v + lo, hi - lo, lr_t, c.lr_dev, b1, b2, eps, c.s);
         });
@@ -345,6 +355,15 @@
         const double nd = (double)(reg_decayed[t1] - reg_decayed[t0]);
         const bool fold = lo == 0;
         const float lr_t = cur_lr_t;
+        if (update && opt_kind != P3D_OPT_ADAM) {      // the update's bytes as in adam_range, plus the gradient written back
+            launch(c, opt_kind == P3D_OPT_MOMENTUM ? "momentum_decay_kernel" : "sgd_decay_kernel", 4.0 * nd,
+                   (opt_kind == P3D_OPT_MOMENTUM ? 20.0 : 12.0) * (hi - lo) + 4.0 * nd + 8.0 * (t1 - t0), [&]() {
+                return p3d_optimizer_decay(opt_kind, flat_p + lo, flat_g + lo, flat_m + lo, hi - lo, d_reg_tiles + t0, t1 - t0, lo, lr_t,
+                                           c.lr_dev, momentum, use_nesterov, d_reg_part + t0, d_reg_part,
+                                           fold ? (int)reg_tiles.size() : 0, d_reg_cnt, d_reg, c.s);
+            });
+            return;
+        }
         launch(c, update ? "adam_decay_kernel" : "decay_grad_kernel", 4.0 * nd,
                (update ? 28.0 * (hi - lo) + 4.0 * nd : 12.0 * nd) + 8.0 * (t1 - t0), [&]() {
             return p3d_adam_decay(flat_p + lo, flat_g + lo, flat_m + lo, flat_v + lo, hi - lo, d_reg_tiles + t0, t1 - t0, lo, lr_t,
@@ -372,6 +391,7 @@
     hipGraphExec_t step_exec = nullptr;
     float graph_drop = -1.f; bool graph_f16 = false; ncclComm_t graph_comm = nullptr; float graph_b1 = 0, graph_b2 = 0, graph_eps = 0;
     int graph_reg = 0;
+    int graph_kind = P3D_OPT_ADAM; float graph_mom = 0.f; int graph_nesterov = 0;      // the optimiser the graph launches
     bool graph_disabled = false;
     unsigned long long* d_seed = nullptr; float* d_lr = nullptr;
     void drop_step_graph() {
@@ -401,6 +421,7 @@
         HIPCHECK(hipGraphInstantiate(&step_exec, step_graph, nullptr, nullptr, 0));
         graph_drop = drop; graph_f16 = pointwise_f16; graph_comm = comm; graph_b1 = b1; graph_b2 = b2; graph_eps = eps;
         graph_reg = reg_terms;
+        graph_kind = opt_kind; graph_mom = momentum; graph_nesterov = use_nesterov;
     }
     void train_step_device(float drop, uint64_t seed) {
         if (!graphs_enabled()) {
@@ -411,7 +432,8 @@
             return;
         }
         if (!step_exec || graph_drop != drop || graph_f16 != pointwise_f16 || graph_comm != comm || graph_b1 != b1 || graph_b2 != b2 ||
-            graph_eps != eps || graph_reg != reg_terms) {
+            graph_eps != eps || graph_reg != reg_terms || graph_kind != opt_kind || graph_mom != momentum ||
+            graph_nesterov != use_nesterov) {
             try {
                 capture_step_graph(drop);
             } catch (const std::exception& e) {
@@ -423,7 +445,7 @@
                 return;
             }
         }
-        HIPCHECK(p3d_set_step_scalars(d_seed, d_lr, seed, adam_step_size(lr, b1, b2, ++step), stream));
+        HIPCHECK(p3d_set_step_scalars(d_seed, d_lr, seed, opt_step_size(++step), stream));
         HIPCHECK(hipGraphLaunch(step_exec, stream));
     }
 

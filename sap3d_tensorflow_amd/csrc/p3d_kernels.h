@@ -547,6 +547,18 @@ struct P3dRegTile { long long off; int len; float c; };
 hipError_t p3d_adam_decay(float* p, float* g, float* m, float* v, long n, const P3dRegTile* tiles, int ntile, long long tile_base,
                           float lr_t, const float* lr_dev, float b1, float b2, float eps, int update, double* part,
                           const double* fold_part, int nfold, unsigned* counter, double* term, hipStream_t s);
+// ---- Momentum and SGD (tf.train.MomentumOptimizer / GradientDescentOptimizer; p3d_set_optimizer) ---------------------
+// kind 1 (P3D_OPT_MOMENTUM): m is the accumulator, a = (a mom) + g, then p -= lr a, or with use_nesterov
+// p -= (g lr) + ((a mom) lr) on the updated a; kind 2 (P3D_OPT_SGD): p -= lr g, m unused (may be null).  No contraction, no fma.
+// lr_dev non-null: the step size is read from device memory (captured step graphs), lr is ignored.  p, g, m float-aligned at
+// the same place in a 16-byte line (the elements before the first 16-byte boundary go one by one).
+hipError_t p3d_optimizer(int kind, float* p, const float* g, float* m, long n, float lr, const float* lr_dev, float momentum,
+                         int use_nesterov, hipStream_t s);
+// p3d_adam_decay with Momentum or SGD as the update on g' = g + c*p (always applied: the gradient-only mode is p3d_adam_decay's);
+// p, g, m 16-byte aligned, as there.
+hipError_t p3d_optimizer_decay(int kind, float* p, float* g, float* m, long n, const P3dRegTile* tiles, int ntile, long long tile_base,
+                               float lr, const float* lr_dev, float momentum, int use_nesterov, double* part, const double* fold_part,
+                               int nfold, unsigned* counter, double* term, hipStream_t s);
 // per-step scalars of a captured train step: scal[0..1] = dropout seed (64 bit), scal[2] = Adam's bias-corrected step size
 hipError_t p3d_set_step_scalars(unsigned long long* seed_dst, float* lr_dst, unsigned long long seed, float lr_t, hipStream_t s);
 

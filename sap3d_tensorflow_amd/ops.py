@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import LOSSES, check, fptr, lib
+from ._lib import LOSSES, OPTIMIZERS, check, fptr, lib
 
 
 def _f32(a):
@@ -310,6 +310,44 @@ def adam_decay(p, g, m, v, tiles, t, lr=1e-4, b1=0.9, b2=0.999, eps=1e-8, lr_on_
                                      lens.ctypes.data_as(i64), fptr(cs), len(tiles), float(lr), int(t), float(b1), float(b2),
                                      float(eps), 1 if lr_on_device else 0, 1 if update else 0, C.byref(term), C.byref(lr_t)))
     return g, p, m, v, term.value, lr_t.value
+
+
+def _opt_kind(kind):
+    k = OPTIMIZERS[kind] if isinstance(kind, str) else int(kind)
+    if k not in (OPTIMIZERS["momentum"], OPTIMIZERS["sgd"]):
+        raise ValueError("optimizer %r: the hooks take momentum or sgd (Adam has adam / adam_decay)" % (kind,))
+    return k
+
+
+def optimizer(kind, p, g, m, lr=1e-4, momentum=0.9, use_nesterov=False, lr_on_device=False, offset=0, device=0):
+    """Test hook: one launch of the Momentum or SGD step (p3d_debug_optimizer, kind "momentum" | "sgd") on flat float32 arrays
+    placed `offset` elements into the device buffers; m is Momentum's accumulator.  Returns (p, m) after the step."""
+    k = _opt_kind(kind)
+    p, g, m = (_f32(a).ravel().copy() for a in (p, g, m))
+    if not (p.size == g.size == m.size):
+        raise ValueError("p, g, m differ in size")
+    check(lib().p3d_debug_optimizer(device, k, fptr(p), fptr(g), fptr(m), p.size, int(offset), float(lr), float(momentum),
+                                    1 if use_nesterov else 0, 1 if lr_on_device else 0))
+    return p, m
+
+
+def optimizer_decay(kind, p, g, m, tiles, lr=1e-4, momentum=0.9, use_nesterov=False, lr_on_device=False, update=True, offset=0,
+                    device=0):
+    """Test hook: adam_decay's launch with Momentum or SGD as the update (p3d_debug_optimizer_decay).  tiles = [(length,
+    coefficient), ...] cut [0, n) in order, g' = g + c p.  Returns (g', p, m, the term sum 0.5 c sum(p^2) in double)."""
+    k = _opt_kind(kind)
+    p, g, m = (_f32(a).ravel().copy() for a in (p, g, m))
+    if not (p.size == g.size == m.size):
+        raise ValueError("p, g, m differ in size")
+    lens = np.array([int(n) for n, _ in tiles], np.int64)
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    cs = np.array([c for _, c in tiles], np.float32)
+    i64 = C.POINTER(C.c_int64)
+    term = C.c_double()
+    check(lib().p3d_debug_optimizer_decay(device, k, fptr(p), fptr(g), fptr(m), p.size, int(offset), offs.ctypes.data_as(i64),
+                                          lens.ctypes.data_as(i64), fptr(cs), len(tiles), float(lr), float(momentum),
+                                          1 if use_nesterov else 0, 1 if lr_on_device else 0, 1 if update else 0, C.byref(term)))
+    return g, p, m, term.value
 
 
 def stat_parts(xshape, fshape, strides, transpose=False):

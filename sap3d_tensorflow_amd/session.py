@@ -14,6 +14,35 @@ STRUCTURES = {"unet": 0, "concat": 1, "gn_p3d": 2,     # train.py:149-154 --stru
               "unet++ds": 6}                             # p3d.py:340 p3d_unetplusplus_ds (unet++ with self attention)
 
 
+def slot_names(variables, optimizer):
+    """{TF slot name: (variable, slot index)} of `optimizer` ("adam" | "momentum" | "sgd") over the trainables of
+    [(name, shape, trainable)]: <var>/Adam, <var>/Adam_1 (slots 0, 1) or <var>/Momentum (slot 0), as a tf.train.Saver names them."""
+    out = {}
+    for n, _, tr in variables:
+        if tr:
+            for k, suffix in enumerate(_lib.SLOT_NAMES[optimizer]):
+                out["%s/%s" % (n, suffix)] = (n, k)
+    return out
+
+
+def adam_step_from_powers(beta1_power, beta2_power, beta1=0.9, beta2=0.999):
+    """Completed Adam steps t of TF's beta1_power / beta2_power (b^(t+1) as float32): the integer nearest to
+    log(beta2_power) / log(beta2) - 1, checked against beta1_power (relative 1e-3, or within float32's smallest normal where
+    the running product underflows).  Raises ValueError for powers that fit no step."""
+    b1p, b2p = float(np.float32(beta1_power)), float(np.float32(beta2_power))
+    lb1, lb2 = np.log(np.float64(np.float32(beta1))), np.log(np.float64(np.float32(beta2)))
+    if not (0.0 < b2p <= 1.0) or not (lb2 < 0.0) or not (lb1 < 0.0):
+        raise ValueError("beta2_power %r with beta2 %r fits no Adam step" % (b2p, beta2))
+    t = int(np.rint(np.log(b2p) / lb2 - 1.0))
+    if t < 0:
+        raise ValueError("beta2_power %r is above beta2 %r: no Adam step" % (b2p, beta2))
+    want = float(np.float32(np.float64(np.float32(beta1)) ** (t + 1)))
+    if abs(b1p - want) > 1e-3 * abs(want) + float(np.finfo(np.float32).tiny):
+        raise ValueError("beta1_power %r does not fit step %d of beta2_power %r (expected %r): not this optimiser's state"
+                         % (b1p, t, b2p, want))
+    return t
+
+
 class P3DSession:
     """sess = P3DSession(batch=2)  ~  building the graph + tf.Session() in train.py:143-201."""
 
@@ -36,6 +65,8 @@ class P3DSession:
         self.y_shape = (batch, frames, height, width)
         self.pred_shape = (batch, frames, height, width, 1)
         self._info = None
+        self._opt = "adam"               # p3d_set_optimizer's kind, and set_adam's betas (the beta*_power of optimizer_state)
+        self._betas = (0.9, 0.999)
         if seed is not None:
             self.init_params(seed)
 
@@ -95,10 +126,11 @@ class P3DSession:
         for n in names:
             self.set_param(n, params[n])
 
-    def restore(self, path):
+    def restore(self, path, optimizer_state=False):
         """saver.restore (train.py:204-210, gen_pred.py:57-64): `path` is a TF-1.x checkpoint prefix (`.../p3d_1000.ckpt`),
         a directory holding a `checkpoint` state file (the newest bundle is taken), or an .npz keyed by variable names.
-        Variables the checkpoint lacks raise; extra ones (e.g. Adam slots of another trainer) are ignored."""
+        Variables the checkpoint lacks raise; extra ones (e.g. Adam slots of another trainer) are ignored.  With
+        optimizer_state the current optimiser's slots (and Adam's beta*_power) come back too (load_optimizer_state)."""
         import os
         from . import tf_checkpoint as tfc
         if os.path.isdir(path):
@@ -106,19 +138,31 @@ class P3DSession:
             if latest is None:
                 raise FileNotFoundError("no `checkpoint` state file in %s" % path)
             path = latest
+        names = set(n for n, _, _ in self.variables())
+        if optimizer_state:
+            names |= set(self._slot_names()) | ({"beta1_power", "beta2_power"} if self._opt == "adam" else set())
         if path.endswith(".npz"):
-            self.load(dict(np.load(path)))
+            d = dict(np.load(path))
         else:
-            self.load(tfc.read_checkpoint(path, names=set(n for n, _, _ in self.variables())))
+            d = tfc.read_checkpoint(path, names=names)
+        if optimizer_state:
+            self._parse_optimizer_state(d)      # refuses a checkpoint without this optimiser's state before anything is set
+        self.load(d)
+        if optimizer_state:
+            self.load_optimizer_state(d)
         return path
 
-    def save_checkpoint(self, directory, step, keep=10):
+    def save_checkpoint(self, directory, step, keep=10, optimizer_state=False):
         """saver.save(sess, '<dir>/p3d_<step>.ckpt') with max_to_keep (train.py:180-185,266-267): writes a TF V2 bundle and
-        updates the directory's `checkpoint` state file.  Returns the prefix."""
+        updates the directory's `checkpoint` state file.  With optimizer_state the bundle also holds the optimiser's slots
+        under their TF names (optimizer_state()), as a default tf.train.Saver writes them.  Returns the prefix."""
         import os
         from . import tf_checkpoint as tfc
         prefix = os.path.join(directory, "p3d_%d.ckpt" % step)
-        tfc.write_checkpoint(prefix, self.save())
+        variables = self.save()
+        if optimizer_state:
+            variables.update(self.optimizer_state())
+        tfc.write_checkpoint(prefix, variables)
         tfc.update_checkpoint_state(directory, prefix, keep)
         return prefix
 
@@ -372,6 +416,68 @@ class P3DSession:
 
     def set_adam(self, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8):
         check(lib().p3d_set_adam(self._h, lr, beta1, beta2, eps))
+        self._betas = (beta1, beta2)
+
+    # ---- optimiser (p3d_set_optimizer) and its state -------------------------------------------------
+    def set_optimizer(self, name="adam", lr=1e-4, momentum=0.9, use_nesterov=False):
+        """The train step's optimiser: "adam" (tf.train.AdamOptimizer; beta1, beta2, eps stay as set_adam left them),
+        "momentum" (tf.train.MomentumOptimizer(lr, momentum, use_nesterov)) or "sgd" (tf.train.GradientDescentOptimizer(lr)).
+        Switching kind starts a fresh optimiser (zero slots, step 0); the same kind with new values keeps its state."""
+        if name not in _lib.OPTIMIZERS:
+            raise ValueError("optimizer %r: have %s" % (name, sorted(_lib.OPTIMIZERS)))
+        check(lib().p3d_set_optimizer(self._h, _lib.OPTIMIZERS[name], float(lr), float(momentum), 1 if use_nesterov else 0))
+        self._opt = name
+
+    def optimizer_step(self):
+        """Completed optimiser steps."""
+        t = C.c_int64()
+        check(lib().p3d_get_optimizer_step(self._h, C.byref(t)))
+        return t.value
+
+    def _slot_names(self):
+        return slot_names(self.variables(), self._opt)
+
+    def get_slot(self, name, slot):
+        shape = dict((n, s) for n, s, _ in self.variables())[name]
+        a = np.empty(shape, np.float32)
+        check(lib().p3d_get_slot(self._h, name.encode(), int(slot), fptr(a), a.size))
+        return a
+
+    def set_slot(self, name, slot, value):
+        a = np.ascontiguousarray(value, dtype=np.float32)
+        check(lib().p3d_set_slot(self._h, name.encode(), int(slot), fptr(a), a.size))
+
+    def optimizer_state(self):
+        """{TF name: array} of the optimiser's state, as a default tf.train.Saver stores it: <var>/Adam and <var>/Adam_1 (m, v)
+        with the float32 scalars beta1_power and beta2_power for Adam -- TF keeps b^(t+1) after t completed steps (the
+        variables start at b and are multiplied after each step) --, <var>/Momentum for Momentum, nothing for SGD."""
+        out = dict((k, self.get_slot(n, i)) for k, (n, i) in self._slot_names().items())
+        if self._opt == "adam":
+            t = self.optimizer_step()
+            for key, b in zip(("beta1_power", "beta2_power"), self._betas):
+                out[key] = np.array(np.float64(np.float32(b)) ** (t + 1), np.float32)
+        return out
+
+    def _parse_optimizer_state(self, d):
+        slots = self._slot_names()
+        missing = sorted(k for k in slots if k not in d)
+        if self._opt == "adam":
+            missing += [k for k in ("beta1_power", "beta2_power") if k not in d]
+        if missing:
+            raise KeyError("checkpoint lacks %d %s slots, e.g. %s" % (len(missing), self._opt, missing[:3]))
+        t = adam_step_from_powers(d["beta1_power"], d["beta2_power"], *self._betas) if self._opt == "adam" else None
+        return slots, t
+
+    def load_optimizer_state(self, d):
+        """Set the current optimiser's slots from {TF name: array} (optimizer_state()'s form; extra names are ignored).  For
+        Adam the completed steps t are the integer nearest to log(beta2_power) / log(beta2) - 1; a beta1_power that does not
+        fit that t (relative 1e-3, beyond float32's smallest normal) refuses the checkpoint: TF's running float32 product
+        drifts, so the powers are not compared bit for bit."""
+        slots, t = self._parse_optimizer_state(d)
+        for k, (n, i) in slots.items():
+            self.set_slot(n, i, d[k])
+        if t is not None:
+            check(lib().p3d_set_optimizer_step(self._h, int(t)))
 
     def activation(self, name):
         shape = (C.c_int64 * 5)()
