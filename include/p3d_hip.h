@@ -359,7 +359,7 @@ int p3d_debug_cbam(int device, int N, int D, int H, int W, int C, const float* x
 int p3d_debug_head(int device, int transpose, int N, int D, int H, int W, int C, const float* x, const float* k, const float* bias,
                    int sigmoid, const float* dlogits, int fwd_path, int filter_path, float* logits, float* pred, float* dx, float* dk,
                    float* dbias, int* info);
-/* Test hook: the Smooth-L1 loss and dL/dlogits (p3d_smooth_l1, as the network's loss launches it) on n elements placed
+/* Test hook: the Smooth-L1 loss and dL/dlogits (p3d_loss, as the network's loss launches it) on n elements placed
  * `offset` (0-3) elements into the device buffers: offsets 1-3 misalign them and force the scalar path.  through_sigmoid:
  * dlogits = dL/dpred * pred * (1 - pred).  *loss is added to.  info[2] = path taken (1 float4, 2 scalar), blocks. */
 int p3d_debug_smooth_l1(int device, const float* pred, const float* target, int64_t n, int through_sigmoid, int offset, double* loss,
@@ -376,11 +376,11 @@ int p3d_debug_loss(int device, int kind, const float* logits, const float* pred,
 int p3d_debug_map_loss(int device, const float* logits, const float* pred, const float* target, int64_t maps, int64_t map_elems,
                        int through_sigmoid, int offset, float kld_weight, float cc_weight, double* loss, float* dlogits,
                        double* per_map, int* info);
-/* Test hook: one Adam launch (p3d_adam, as the network's optimiser step launches it) on n elements placed `offset` elements
- * into the device buffers (p3d_adam refuses a base that is not 16-byte aligned).  p, m, v are updated in place from g with
+/* Test hook: one Adam launch (p3d_opt_step, as the network's optimiser step launches it) on n elements placed `offset` elements
+ * into the device buffers (Adam refuses a base that is not 16-byte aligned).  p, m, v are updated in place from g with
  * the bias-corrected step size of step t (the network's adam_step_size), passed as an argument or, when lr_on_device, through
  * device memory as a captured train step passes it.  *lr_t = that step size. */
-/* Test hook: one launch of the regularised optimiser step (p3d_adam_decay, as adam_range launches it when a term is on) on n
+/* Test hook: one launch of the regularised optimiser step (p3d_opt_step, as adam_range launches it when a term is on) on n
  * elements placed `offset` (0..3) elements into the device buffers.  Tiles k = 0..ntile-1 cover [0, n) in order:
  * [tile_off[k], tile_off[k] + tile_len[k]) with coefficient tile_c[k].  g becomes g + c*p; with update, p, m, v take the Adam
  * step of step t on it (step size as p3d_debug_adam: argument or device memory), without it they stay as they are.

@@ -466,51 +466,12 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(PoolArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void smooth_l1_kernel(const float* pred, const float* target, long long n,
-                                                        double* loss_out, float* dl, int through_sigmoid, int vec4, double* part,
-                                                        unsigned* counter) {
-    P3D_CHAIN_PRIO();
-    __shared__ double wsum[4];
-    __shared__ int last_flag;
-    double acc = 0.0;
-    auto one = [&](float p, float t, float& g) {
-        const float d = p - t;
-        const float ad = fabsf(d);
-        acc += ad < 1.f ? 0.5f * d * d : ad - 0.5f;
-        g = ad < 1.f ? d : (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f));
-        if (through_sigmoid) g *= p * (1.f - p);
-    };
-    const long long gtid = (long long)blockIdx.x * blockDim.x + threadIdx.x, gsz = (long long)gridDim.x * blockDim.x;
-    if (vec4) {
-        // 16 bytes per lane and tensor (the scalar form ran at 0.86 TB/s: 22 us for 19 MB on the main stream)
-        const long long n4 = n >> 2;
-        for (long long i = gtid; i < n4; i += gsz) {
-            const float4 p = ld4(pred + 4 * i), t = ld4(target + 4 * i);
-            float4 g;
-            one(p.x, t.x, g.x); one(p.y, t.y, g.y); one(p.z, t.z, g.z); one(p.w, t.w, g.w);
-            st4(dl + 4 * i, g);
-        }
-    } else {
-        for (long long i = gtid; i < n; i += gsz) one(pred[i], target[i], dl[i]);
-    }
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    // per-block partial, then the last arriving block adds the partials in block order (no atomics: the loss is
-    // bit-reproducible)
-    if (threadIdx.x == 0) p3d_store_wt(part, blockIdx.x, wsum[0] + wsum[1] + wsum[2] + wsum[3]);
-    if (!p3d_last_block_wt(counter, gridDim.x, &last_flag)) return;
-    double t = 0.0;
-    for (unsigned b = threadIdx.x; b < gridDim.x; b += 256) t += part[b];
-    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = t;
-    __syncthreads();
-    if (threadIdx.x == 0) *loss_out += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
-
-// The loss options beside Smooth-L1 (p3d_set_loss), with smooth_l1_kernel's lanes, grid and block-order fold.  z = logits,
-// p = pred (sigmoid(z) on a sigmoid head, z on a raw one), t = target.
+// The losses of p3d_set_loss kinds 0-2 (LossArgs in p3d_kernels.h), one grid-stride pass: 16 bytes per lane and tensor when
+// vec4 (the scalar form ran at 0.86 TB/s: 22 us for 19 MB on the main stream), double accumulation, and the block-order fold of
+// det_reduce.h (no atomics: the loss is bit-reproducible).  z = logits, p = pred (sigmoid(z) on a sigmoid head, z on a raw
+// one), t = target.
+//   KIND 0, Smooth-L1 sum: 0.5 d^2 where |d| < 1, |d| - 0.5 elsewhere, d = p - t; dL/dp = d or sign(d), times p (1 - p)
+//     through the sigmoid.  Reads p and t.
 //   KIND 1, sigmoid cross-entropy on logits (tf.nn.sigmoid_cross_entropy_with_logits): max(z,0) - z t + log1p(exp(-|z|)),
 //     finite for every finite z; dL/dz = sigmoid(z) - t, where sigmoid(z) is the stored pred on a sigmoid head (the loss
 //     and the saliency map agree bit for bit) and the head's own 1/(1+expf(-z)) (head.hip) on a raw one.  Reads z, t and,
@@ -524,9 +485,11 @@ __device__ __forceinline__ float loss_term(float z, float p, float t, int throug
         return fmaxf(z, 0.f) - z * t + log1pf(expf(-fabsf(z)));
     }
     const float d = p - t;
-    g = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+    const float ad = fabsf(d);
+    const bool quad = KIND == 0 && ad < 1.f;
+    g = quad ? d : (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f));
     if (through_sigmoid) g *= p * (1.f - p);
-    return fabsf(d);
+    return KIND == 2 ? ad : (quad ? 0.5f * d * d : ad - 0.5f);
 }
 
 template <int KIND>
@@ -536,7 +499,7 @@ __device__ __forceinline__ void loss_body(const float* logits, const float* pred
     __shared__ double wsum[4];
     __shared__ int last_flag;
     double acc = 0.0;
-    const bool need_z = KIND == 1, need_p = KIND == 2 || through_sigmoid;
+    const bool need_z = KIND == 1, need_p = KIND != 1 || through_sigmoid;
     const long long gtid = (long long)blockIdx.x * blockDim.x + threadIdx.x, gsz = (long long)gridDim.x * blockDim.x;
     if (vec4) {
         const long long n4 = n >> 2;
@@ -557,6 +520,7 @@ __device__ __forceinline__ void loss_body(const float* logits, const float* pred
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
     __syncthreads();
+    // per-block partial, then the last arriving block adds the partials in block order
     if (threadIdx.x == 0) p3d_store_wt(part, blockIdx.x, wsum[0] + wsum[1] + wsum[2] + wsum[3]);
     if (!p3d_last_block_wt(counter, gridDim.x, &last_flag)) return;
     double t = 0.0;
@@ -568,6 +532,12 @@ __device__ __forceinline__ void loss_body(const float* logits, const float* pred
     if (threadIdx.x == 0) *loss_out += wsum[0] + wsum[1] + wsum[2] + wsum[3];
 }
 // one kernel per kind: the launch lists and the profiles name the loss
+__global__ __launch_bounds__(256) void smooth_l1_kernel(const float* pred, const float* target, long long n,
+                                                        double* loss_out, float* dl, int through_sigmoid, int vec4, double* part,
+                                                        unsigned* counter) {
+    P3D_CHAIN_PRIO();
+    loss_body<0>(nullptr, pred, target, n, loss_out, dl, through_sigmoid, vec4, part, counter);
+}
 __global__ __launch_bounds__(256) void sigmoid_ce_kernel(const float* logits, const float* pred, const float* target, long long n,
                                                          double* loss_out, float* dl, int through_sigmoid, int vec4, double* part,
                                                          unsigned* counter) {
@@ -618,7 +588,6 @@ __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, flo
 //   nesterov  a = (a * mom) + g;  p = p - ((g * lr) + ((a * mom) * lr))      (the updated a)
 //   sgd       p = p - (lr * g)
 // The same arithmetic on whole 4-groups and on the scalar tail of a range.
-enum { UPD_NONE = -1, UPD_ADAM = 0, UPD_MOMENTUM = 1, UPD_SGD = 2 };      // the update kinds: P3D_OPT_* of include/p3d_hip.h
 template <int KIND>      // UPD_MOMENTUM or UPD_SGD
 __device__ __forceinline__ void opt_elem(float& p, float& a, float g, float lr_t, float mom, int nesterov) {
 #pragma clang fp contract(off)
@@ -677,7 +646,7 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* p, const float* g, long
     opt_body<UPD_SGD>(p, g, nullptr, n4, n, head, lr_dev ? *lr_dev : lr_arg, 0.f, 0);
 }
 
-// Regularisation (p3d_adam_decay).  Every rounding is explicit, so that a numpy float32 replay is bit-exact: contraction is
+// Regularisation (the decay part of OptArgs).  Every rounding is explicit, so that a numpy float32 replay is bit-exact: contraction is
 // off and the two fused multiply-adds are fmaf.  adam_kernel's own arithmetic, as this compiler contracts it: on a whole
 // float4 group m and v are single fmas over the rounded (1-b) g terms; on the scalar tail of a range nothing is fused.
 __device__ __forceinline__ void adam_elem(float& p, float& m, float& v, float g, float lr_t, float b1, float b2, float eps,
@@ -1189,102 +1158,87 @@ hipError_t p3d_maxpool_bwd_disjoint(const PoolArgs& a, int accumulate, hipStream
 }
 
 
-hipError_t p3d_smooth_l1(const float* pred, const float* target, long n, double* loss_out, float* dlogits,
-                         int through_sigmoid, hipStream_t s, unsigned* done) {
-    if (n < 1) return hipErrorInvalidValue;
-    const unsigned g = grid_for(n, 256, 1024);
-    // 16 bytes per lane when every operand is 16-byte aligned and n % 4 == 0, else one element per lane
-    const int vec4 = (n & 3) == 0 &&
-                     ((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(target) | reinterpret_cast<uintptr_t>(dlogits)) & 15) == 0;
-    float* slab = nullptr; unsigned* cnt = nullptr;
-    const hipError_t e = p3d_stream_scratch(s, 2 * (size_t)g, 1, &slab, &cnt);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(smooth_l1_kernel, dim3(g), dim3(256), 0, s, pred, target, (long long)n, loss_out, dlogits, through_sigmoid,
-                       vec4, reinterpret_cast<double*>(slab), cnt);
-    if (done) { done[0] = vec4 ? 1 : 2; done[1] = g; }
-    return hipGetLastError();
+static uintptr_t low4(const void* q) { return reinterpret_cast<uintptr_t>(q) & 15; }      // place in a 16-byte line
+
+LaunchDesc p3d_loss_desc(const LossArgs& a) {
+    // per element: pred (BCE: the logits, and pred on a sigmoid head) and the target read, dlogits written; BCE ~8 operations
+    // (+3 for the sigmoid of a raw head), L1 3 (+3 through the sigmoid)
+    const double n = (double)a.n;      // kinds: P3D_LOSS_* of include/p3d_hip.h
+    const bool ts = a.through_sigmoid != 0;
+    if (a.kind == 1) return {"sigmoid_ce_kernel", n * (ts ? 8.0 : 11.0), n * (ts ? 16.0 : 12.0)};
+    if (a.kind == 2) return {"l1_loss_kernel", n * (ts ? 6.0 : 3.0), n * 12.0};
+    return {"smooth_l1_kernel", 0, 12.0 * n};
 }
 
-hipError_t p3d_loss(int kind, const float* logits, const float* pred, const float* target, long n, double* loss_out,
-                    float* dlogits, int through_sigmoid, hipStream_t s, unsigned* done) {
-    if (n < 1 || (kind != 1 && kind != 2)) return hipErrorInvalidValue;
-    const unsigned g = grid_for(n, 256, 1024);
-    const int vec4 = (n & 3) == 0 &&
-                     ((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(target) |
-                       reinterpret_cast<uintptr_t>(dlogits)) & 15) == 0;
+hipError_t p3d_loss(const LossArgs& a, hipStream_t s, unsigned* done) {
+    if (a.n < 1 || a.kind < 0 || a.kind > 2) return hipErrorInvalidValue;
+    const unsigned g = grid_for(a.n, 256, 1024);
+    // 16 bytes per lane when every operand of the kind is 16-byte aligned and n % 4 == 0, else one element per lane
+    const int vec4 = (a.n & 3) == 0 &&
+                     ((a.kind == 0 ? 0 : low4(a.logits)) | low4(a.pred) | low4(a.target) | low4(a.dlogits)) == 0;
     float* slab = nullptr; unsigned* cnt = nullptr;
     const hipError_t e = p3d_stream_scratch(s, 2 * (size_t)g, 1, &slab, &cnt);
     if (e != hipSuccess) return e;
-    const int ts = through_sigmoid ? 1 : 0;
+    const int ts = a.through_sigmoid ? 1 : 0;
     double* part = reinterpret_cast<double*>(slab);
-    if (kind == 1)
-        hipLaunchKernelGGL(sigmoid_ce_kernel, dim3(g), dim3(256), 0, s, logits, pred, target, (long long)n, loss_out, dlogits, ts, vec4,
-                           part, cnt);
+    const long long n = a.n;
+    if (a.kind == 0)
+        hipLaunchKernelGGL(smooth_l1_kernel, dim3(g), dim3(256), 0, s, a.pred, a.target, n, a.loss_out, a.dlogits, ts, vec4, part, cnt);
     else
-        hipLaunchKernelGGL(l1_loss_kernel, dim3(g), dim3(256), 0, s, logits, pred, target, (long long)n, loss_out, dlogits, ts, vec4,
-                           part, cnt);
+        hipLaunchKernelGGL(a.kind == 1 ? sigmoid_ce_kernel : l1_loss_kernel, dim3(g), dim3(256), 0, s, a.logits, a.pred,
+                           a.target, n, a.loss_out, a.dlogits, ts, vec4, part, cnt);
     if (done) { done[0] = vec4 ? 1 : 2; done[1] = g; }
     return hipGetLastError();
 }
 
-hipError_t p3d_adam_decay(float* p, float* g, float* m, float* v, long n, const P3dRegTile* tiles, int ntile, long long tile_base,
-                          float lr_t, const float* lr_dev, float b1, float b2, float eps, int update, double* part,
-                          const double* fold_part, int nfold, unsigned* counter, double* term, hipStream_t s) {
-    if (n < 1 || ntile < 1 || !tiles || !part || (nfold > 0 && (!fold_part || !counter || !term)) ||
-        ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
-          reinterpret_cast<uintptr_t>(v)) & 15))
-        return hipErrorInvalidValue;
-    if (update)
-        hipLaunchKernelGGL(adam_decay_kernel, dim3(ntile), dim3(256), 0, s, p, g, m, v, (long long)n, tiles, tile_base, lr_t, lr_dev,
-                           b1, b2, eps, part, fold_part, nfold, counter, term);
-    else
-        hipLaunchKernelGGL(decay_grad_kernel, dim3(ntile), dim3(256), 0, s, p, g, (long long)n, tiles, tile_base, part, fold_part,
-                           nfold, counter, term);
-    return hipGetLastError();
+LaunchDesc p3d_opt_desc(const OptArgs& a, double decayed_elems) {
+    // per element Adam reads g, m, v, p and writes m, v, p (28 bytes); Momentum g, a, p and a, p (20); SGD g, p and p (12).  A
+    // decayed element adds 2 operations for g + c w, 2 for the term and the gradient written back (12 bytes alone without an
+    // update); a tile is 8 bytes of table and partial.
+    static const char* const name[2][4] = {{nullptr, "adam_kernel", "momentum_kernel", "sgd_kernel"},
+                                           {"decay_grad_kernel", "adam_decay_kernel", "momentum_decay_kernel", "sgd_decay_kernel"}};
+    const double upd = (a.update == UPD_ADAM ? 28.0 : a.update == UPD_MOMENTUM ? 20.0 : 12.0) * a.n, nd = decayed_elems;
+    if (!a.ntile) return {name[0][a.update + 1], 0, upd};
+    return {name[1][a.update + 1], 4.0 * nd, (a.update == UPD_NONE ? 12.0 * nd : upd + 4.0 * nd) + 8.0 * a.ntile};
 }
 
-hipError_t p3d_adam(float* p, const float* g, float* m, float* v, long n, float lr_t, const float* lr_dev, float b1, float b2,
-                    float eps, hipStream_t s) {
-    // the kernel reads and writes four elements from every 4-aligned offset as one float4
-    if (n < 1 || ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
-                   reinterpret_cast<uintptr_t>(v)) & 15))
-        return hipErrorInvalidValue;
-    const long long n4 = ((long long)n + 3) / 4;
-    hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n4)), dim3(256), 0, s, p, g, m, v, n4, (long long)n, lr_t, lr_dev, b1, b2, eps);
-    return hipGetLastError();
-}
-
-hipError_t p3d_optimizer(int kind, float* p, const float* g, float* m, long n, float lr, const float* lr_dev, float momentum,
-                         int use_nesterov, hipStream_t s) {
-    // p, g, m float-aligned and at the same place in a 16-byte line: the elements before the first 16-byte boundary go one by one
-    const uintptr_t r = reinterpret_cast<uintptr_t>(p) & 15;
-    if (n < 1 || (kind != 1 && kind != 2) || (kind == 1 && !m) || (r & 3) || (reinterpret_cast<uintptr_t>(g) & 15) != r ||
-        (kind == 1 && (reinterpret_cast<uintptr_t>(m) & 15) != r))
-        return hipErrorInvalidValue;
-    const int head = (int)std::min<long long>((long long)((16 - r) & 15) / 4, (long long)n);
-    const long long n4 = ((long long)n - head + 3) / 4;
-    const unsigned grid = n4 > 0 ? grid_for(n4) : 1u;
-    if (kind == 1)
-        hipLaunchKernelGGL(momentum_kernel, dim3(grid), dim3(256), 0, s, p, g, m, n4, (long long)n, head, lr, lr_dev, momentum,
-                           use_nesterov ? 1 : 0);
+hipError_t p3d_opt_step(const OptArgs& a, hipStream_t s) {
+    const bool adam = a.update == UPD_ADAM, mom = a.update == UPD_MOMENTUM;
+    if (a.n < 1 || a.ntile < 0 || a.update < UPD_NONE || a.update > UPD_SGD || (mom && !a.m)) return hipErrorInvalidValue;
+    const long long n = a.n;
+    const int nesterov = a.nesterov ? 1 : 0;
+    const uintptr_t r = low4(a.p);
+    if (!a.ntile && !adam) {
+        // p, g, m float-aligned and at the same place in a 16-byte line: the elements before the first 16-byte boundary go one by one
+        if (a.update == UPD_NONE || (r & 3) || low4(a.g) != r || (mom && low4(a.m) != r)) return hipErrorInvalidValue;
+        const int head = (int)std::min<long long>((long long)((16 - r) & 15) / 4, n);
+        const long long n4 = (n - head + 3) / 4;
+        const dim3 grid(n4 > 0 ? grid_for(n4) : 1u);
+        if (mom) hipLaunchKernelGGL(momentum_kernel, grid, dim3(256), 0, s, a.p, a.g, a.m, n4, n, head, a.lr, a.lr_dev, a.momentum, nesterov);
+        else hipLaunchKernelGGL(sgd_kernel, grid, dim3(256), 0, s, a.p, a.g, n4, n, head, a.lr, a.lr_dev);
+        return hipGetLastError();
+    }
+    // every other kernel reads and writes four elements from every 4-aligned offset as one float4
+    if (r | low4(a.g) | (adam || mom ? low4(a.m) : 0) | (adam ? low4(a.v) : 0)) return hipErrorInvalidValue;
+    if (!a.ntile) {
+        const long long n4 = (n + 3) / 4;
+        hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n4)), dim3(256), 0, s, a.p, a.g, a.m, a.v, n4, n, a.lr, a.lr_dev, a.b1, a.b2, a.eps);
+        return hipGetLastError();
+    }
+    if (!a.tiles || !a.part || (a.nfold > 0 && (!a.fold_part || !a.counter || !a.term))) return hipErrorInvalidValue;
+    const dim3 grid(a.ntile), block(256);
+    if (adam)
+        hipLaunchKernelGGL(adam_decay_kernel, grid, block, 0, s, a.p, a.g, a.m, a.v, n, a.tiles, a.tile_base, a.lr, a.lr_dev, a.b1, a.b2,
+                           a.eps, a.part, a.fold_part, a.nfold, a.counter, a.term);
+    else if (mom)
+        hipLaunchKernelGGL(momentum_decay_kernel, grid, block, 0, s, a.p, a.g, a.m, n, a.tiles, a.tile_base, a.lr, a.lr_dev, a.momentum,
+                           nesterov, a.part, a.fold_part, a.nfold, a.counter, a.term);
+    else if (a.update == UPD_SGD)
+        hipLaunchKernelGGL(sgd_decay_kernel, grid, block, 0, s, a.p, a.g, n, a.tiles, a.tile_base, a.lr, a.lr_dev, a.part, a.fold_part,
+                           a.nfold, a.counter, a.term);
     else
-        hipLaunchKernelGGL(sgd_kernel, dim3(grid), dim3(256), 0, s, p, g, n4, (long long)n, head, lr, lr_dev);
-    return hipGetLastError();
-}
-
-hipError_t p3d_optimizer_decay(int kind, float* p, float* g, float* m, long n, const P3dRegTile* tiles, int ntile, long long tile_base,
-                               float lr, const float* lr_dev, float momentum, int use_nesterov, double* part, const double* fold_part,
-                               int nfold, unsigned* counter, double* term, hipStream_t s) {
-    if (n < 1 || ntile < 1 || !tiles || !part || (kind != 1 && kind != 2) || (kind == 1 && !m) ||
-        (nfold > 0 && (!fold_part || !counter || !term)) ||
-        ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(kind == 1 ? m : p)) & 15))
-        return hipErrorInvalidValue;
-    if (kind == 1)
-        hipLaunchKernelGGL(momentum_decay_kernel, dim3(ntile), dim3(256), 0, s, p, g, m, (long long)n, tiles, tile_base, lr, lr_dev,
-                           momentum, use_nesterov ? 1 : 0, part, fold_part, nfold, counter, term);
-    else
-        hipLaunchKernelGGL(sgd_decay_kernel, dim3(ntile), dim3(256), 0, s, p, g, (long long)n, tiles, tile_base, lr, lr_dev, part,
-                           fold_part, nfold, counter, term);
+        hipLaunchKernelGGL(decay_grad_kernel, grid, block, 0, s, a.p, a.g, n, a.tiles, a.tile_base, a.part, a.fold_part, a.nfold,
+                           a.counter, a.term);
     return hipGetLastError();
 }
 

@@ -387,7 +387,7 @@ int p3d_backward(p3d_handle* h, const float* x, const float* y, float dropout_ra
     h->run_forward(c);
     h->run_loss(c);
     h->run_backward(c, false);
-    if (h->reg_terms) h->decay_range(c, 0, h->n_train, false);      // the regularisation's gradient, after the backward's
+    if (h->reg_terms) h->adam_range(c, 0, h->n_train, false);      // the regularisation's gradient, after the backward's
     const float l = h->read_loss();
     if (loss) *loss = l;
     if (pred) h->download_act(h->pred, pred);
@@ -1256,49 +1256,106 @@ int p3d_debug_head(int device, int transpose, int N, int D, int H, int W, int C,
     API_END
 }
 
-// The loss (run_loss in net_sched.inc) on raw inputs, `offset` elements into the device buffers.
+// ---- the loss and optimiser hooks: the launches run_loss and adam_range (net_sched.inc) issue, on raw inputs -------------------
+namespace {
+// n floats placed `offset` elements into a zeroed device buffer, uploaded from `host` when given
+struct StagedBuf : DevBuf {
+    int64_t n; int offset;
+    StagedBuf(int64_t n_, int offset_, const float* host = nullptr) : DevBuf(n_ + offset_), n(n_), offset(offset_) {
+        if (host) HIPCHECK(copy_now(at(), host, (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
+    }
+    float* at() const { return p + offset; }
+    void back(float* host) const { if (host) HIPCHECK(copy_now(host, at(), (size_t)n * 4, hipMemcpyDeviceToHost, nullptr)); }
+};
+// a double the launch adds into or writes: up from *host, and back
+struct StagedDouble : DevBuf {
+    explicit StagedDouble(const double* host) : DevBuf(2) { HIPCHECK(copy_now(p, host, sizeof(double), hipMemcpyHostToDevice, nullptr)); }
+    double* at() const { return reinterpret_cast<double*>(p); }
+    void back(double* host) const { HIPCHECK(copy_now(host, p, sizeof(double), hipMemcpyDeviceToHost, nullptr)); }
+};
+
+// p3d_loss under kind 0, 1 or 2 (logits may be null under kind 0, which never reads them)
+void debug_loss(int device, int kind, const float* logits, const float* pred, const float* target, int64_t n, int through_sigmoid,
+                int offset, double* loss, float* dlogits, int* info, const char* what) {
+    HIPCHECK(hipSetDevice(device));
+    if ((kind != P3D_LOSS_SMOOTH_L1 && !logits) || !pred || !target || !loss || !dlogits || !info) throw P3dError("null argument");
+    if (n < 1 || offset < 0 || offset > 3) throw P3dError(std::string(what) + ": bad length or offset");
+    StagedBuf zb(n, offset, logits), pb(n, offset, pred), tb(n, offset, target), db(n, offset);
+    StagedDouble lb(loss);
+    const LossArgs a{kind, zb.at(), pb.at(), tb.at(), (long)n, through_sigmoid ? 1 : 0, lb.at(), db.at()};
+    unsigned done[2] = {0, 0};
+    HIPCHECK(p3d_loss(a, nullptr, done));
+    HIPCHECK(hipDeviceSynchronize());
+    db.back(dlogits);
+    lb.back(loss);
+    info[0] = (int)done[0]; info[1] = (int)done[1];
+}
+
+// the tile table of a decay hook: tiles must cover [0, n) in order
+std::vector<P3dRegTile> host_tiles(const int64_t* tile_off, const int64_t* tile_len, const float* tile_c, int ntile, int64_t n,
+                                   const char* what) {
+    std::vector<P3dRegTile> tiles((size_t)ntile);
+    int64_t at = 0;
+    bool ok = true;
+    for (int k = 0; k < ntile && ok; ++k) {
+        ok = tile_off[k] == at && tile_len[k] >= 1 && tile_len[k] <= (1 << 30);
+        tiles[k] = {(long long)tile_off[k], (int)tile_len[k], tile_c[k]};
+        at += tile_len[k];
+    }
+    if (!ok || at != n) throw P3dError(std::string(what) + ": tiles must cover [0, n) in order");
+    return tiles;
+}
+
+// p3d_opt_step: `a` brings the update and its hyper-parameters; p, g, m, v are the host's arrays (null: a zeroed buffer, not
+// copied back; g_out null: the gradient is not copied back), n elements each, `offset` elements into the device buffers.  step: the
+// step size, as an argument or (lr_on_device) through device memory as a captured step reads it.  tiles: the decay part, with
+// the whole table folded into *term.
+void debug_opt_step(OptArgs a, float* p, const float* g, float* g_out, float* m, float* v, int64_t n, int offset,
+                    float step, int lr_on_device, const std::vector<P3dRegTile>& tiles = {}, double* term = nullptr) {
+    const int64_t ntile = (int64_t)tiles.size();
+    StagedBuf pb(n, offset, p), gb(n, offset, g), mb(n, offset, m), vb(n, offset, v);
+    DevBuf lrb(1), tb(4 * ntile), part(2 * ntile), scal(4);      // scal (zeroed): [0..1] the term, [2] the fold's counter
+    a.p = pb.at(); a.g = gb.at(); a.m = mb.at(); a.v = vb.at(); a.n = (long)n;
+    if (lr_on_device) HIPCHECK(p3d_set_step_scalars(nullptr, lrb.p, 0, step, nullptr));
+    // from device memory the argument must not matter: NaN would show in every element if the kernel read it
+    a.lr = lr_on_device ? NAN : step;
+    a.lr_dev = lr_on_device ? lrb.p : nullptr;
+    if (ntile) {
+        HIPCHECK(copy_now(tb.p, tiles.data(), tiles.size() * sizeof(P3dRegTile), hipMemcpyHostToDevice, nullptr));
+        a.tiles = reinterpret_cast<P3dRegTile*>(tb.p); a.ntile = (int)ntile; a.tile_base = 0;
+        a.part = reinterpret_cast<double*>(part.p); a.fold_part = a.part; a.nfold = (int)ntile;
+        a.counter = reinterpret_cast<unsigned*>(scal.p + 2); a.term = reinterpret_cast<double*>(scal.p);
+    }
+    HIPCHECK(p3d_opt_step(a, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    pb.back(p); gb.back(g_out); mb.back(m); vb.back(v);
+    if (term) HIPCHECK(copy_now(term, scal.p, sizeof(double), hipMemcpyDeviceToHost, nullptr));
+}
+OptArgs adam_update(float b1, float b2, float eps, int update = 1) {
+    OptArgs a;
+    a.update = update ? UPD_ADAM : UPD_NONE; a.b1 = b1; a.b2 = b2; a.eps = eps;
+    return a;
+}
+OptArgs momentum_update(int kind, float momentum, int use_nesterov, int update = 1) {
+    OptArgs a;
+    a.update = update ? kind : UPD_NONE; a.momentum = momentum; a.nesterov = use_nesterov;      // the gradient-only launch is the same under every kind
+    return a;
+}
+}  // namespace
+
 int p3d_debug_smooth_l1(int device, const float* pred, const float* target, int64_t n, int through_sigmoid, int offset, double* loss,
                         float* dlogits, int* info) {
     API_BEGIN
-    HIPCHECK(hipSetDevice(device));
-    if (!pred || !target || !loss || !dlogits || !info) throw P3dError("null argument");
-    if (n < 1 || offset < 0 || offset > 3) throw P3dError("smooth_l1: bad length or offset");
-    DevBuf pb(n + offset), tb(n + offset), db(n + offset), lb(2);
-    HIPCHECK(copy_now(pb.p + offset, pred, (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
-    HIPCHECK(copy_now(tb.p + offset, target, (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
-    HIPCHECK(copy_now(lb.p, loss, sizeof(double), hipMemcpyHostToDevice, nullptr));
-    unsigned done[2] = {0, 0};
-    HIPCHECK(p3d_smooth_l1(pb.p + offset, tb.p + offset, (long)n, reinterpret_cast<double*>(lb.p), db.p + offset,
-                           through_sigmoid ? 1 : 0, nullptr, done));
-    HIPCHECK(hipDeviceSynchronize());
-    HIPCHECK(copy_now(dlogits, db.p + offset, (size_t)n * 4, hipMemcpyDeviceToHost, nullptr));
-    HIPCHECK(copy_now(loss, lb.p, sizeof(double), hipMemcpyDeviceToHost, nullptr));
-    info[0] = (int)done[0]; info[1] = (int)done[1];
+    debug_loss(device, P3D_LOSS_SMOOTH_L1, nullptr, pred, target, n, through_sigmoid, offset, loss, dlogits, info, "smooth_l1");
     API_END
 }
 
-// The selectable loss (run_loss / run_loss_option in net_sched.inc) on raw inputs, placed as p3d_debug_smooth_l1 places them.
 int p3d_debug_loss(int device, int kind, const float* logits, const float* pred, const float* target, int64_t n, int through_sigmoid,
                    int offset, double* loss, float* dlogits, int* info) {
     API_BEGIN
-    if (kind == P3D_LOSS_SMOOTH_L1) return p3d_debug_smooth_l1(device, pred, target, n, through_sigmoid, offset, loss, dlogits, info);
     if (kind == P3D_LOSS_KLD_CC) throw P3dError("loss: kind 3 (per-map KL + CC) needs the map geometry: p3d_debug_map_loss");
-    if (kind != P3D_LOSS_BCE && kind != P3D_LOSS_L1) throw P3dError("loss: kind is 0, 1 or 2");
-    HIPCHECK(hipSetDevice(device));
-    if (!logits || !pred || !target || !loss || !dlogits || !info) throw P3dError("null argument");
-    if (n < 1 || offset < 0 || offset > 3) throw P3dError("loss: bad length or offset");
-    DevBuf zb(n + offset), pb(n + offset), tb(n + offset), db(n + offset), lb(2);
-    HIPCHECK(copy_now(zb.p + offset, logits, (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
-    HIPCHECK(copy_now(pb.p + offset, pred, (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
-    HIPCHECK(copy_now(tb.p + offset, target, (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
-    HIPCHECK(copy_now(lb.p, loss, sizeof(double), hipMemcpyHostToDevice, nullptr));
-    unsigned done[2] = {0, 0};
-    HIPCHECK(p3d_loss(kind, zb.p + offset, pb.p + offset, tb.p + offset, (long)n, reinterpret_cast<double*>(lb.p), db.p + offset,
-                      through_sigmoid ? 1 : 0, nullptr, done));
-    HIPCHECK(hipDeviceSynchronize());
-    HIPCHECK(copy_now(dlogits, db.p + offset, (size_t)n * 4, hipMemcpyDeviceToHost, nullptr));
-    HIPCHECK(copy_now(loss, lb.p, sizeof(double), hipMemcpyDeviceToHost, nullptr));
-    info[0] = (int)done[0]; info[1] = (int)done[1];
+    if (kind != P3D_LOSS_SMOOTH_L1 && kind != P3D_LOSS_BCE && kind != P3D_LOSS_L1) throw P3dError("loss: kind is 0, 1 or 2");
+    debug_loss(device, kind, logits, pred, target, n, through_sigmoid, offset, loss, dlogits, info, kind ? "loss" : "smooth_l1");
     API_END
 }
 
@@ -1315,15 +1372,12 @@ int p3d_debug_map_loss(int device, const float* logits, const float* pred, const
     const int64_t n = maps * map_elems;
     size_t md = 0, mc = 0;
     p3d_map_loss_scratch(maps, map_elems, &md, &mc);
-    DevBuf zb(n + offset), pb(n + offset), tb(n + offset), db(n + offset), lb(2), sb(2 * (int64_t)md), cb((int64_t)mc);
-    HIPCHECK(copy_now(zb.p + offset, logits, (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
-    if (through_sigmoid) HIPCHECK(copy_now(pb.p + offset, pred, (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
-    HIPCHECK(copy_now(tb.p + offset, target, (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
-    HIPCHECK(copy_now(lb.p, loss, sizeof(double), hipMemcpyHostToDevice, nullptr));
+    StagedBuf zb(n, offset, logits), pb(n, offset, through_sigmoid ? pred : nullptr), tb(n, offset, target), db(n, offset);
+    StagedDouble lb(loss);
+    DevBuf sb(2 * (int64_t)md), cb((int64_t)mc);
     double* scratch = reinterpret_cast<double*>(sb.p);
-    const MapLossArgs a = p3d_map_loss_args(zb.p + offset, pb.p + offset, tb.p + offset, maps, map_elems, through_sigmoid ? 1 : 0,
-                                            kld_weight, cc_weight, reinterpret_cast<double*>(lb.p), db.p + offset, scratch,
-                                            reinterpret_cast<unsigned*>(cb.p));
+    const MapLossArgs a = p3d_map_loss_args(zb.at(), pb.at(), tb.at(), maps, map_elems, through_sigmoid ? 1 : 0, kld_weight, cc_weight,
+                                            lb.at(), db.at(), scratch, reinterpret_cast<unsigned*>(cb.p));
     for (int stage = 0; stage < 3; ++stage) HIPCHECK(p3d_map_loss_launch(stage, a, nullptr));
     HIPCHECK(hipDeviceSynchronize());
     std::vector<double> ms((size_t)maps * P3D_MAP_STATS);
@@ -1336,38 +1390,26 @@ int p3d_debug_map_loss(int device, const float* logits, const float* pred, const
         per_map[2 * m] = ms[(size_t)m * P3D_MAP_STATS + 2];
         per_map[2 * m + 1] = ms[(size_t)m * P3D_MAP_STATS + 3];
     }
-    HIPCHECK(copy_now(dlogits, db.p + offset, (size_t)n * 4, hipMemcpyDeviceToHost, nullptr));
-    HIPCHECK(copy_now(loss, lb.p, sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    db.back(dlogits);
+    lb.back(loss);
     info[0] = 3; info[1] = a.blocks; info[2] = a.vec4 ? 1 : 2;
     API_END
 }
 
-// One optimiser launch (adam_range in net_sched.inc) on raw inputs, `offset` elements into the device buffers; the step size
-// for step t comes from adam_step_size, as an argument or (lr_on_device) through device memory as a captured step reads it.
+// Adam: the step size for step t comes from adam_step_size, and is returned in *lr_t.
 int p3d_debug_adam(int device, float* p, const float* g, float* m, float* v, int64_t n, int offset, float lr, int64_t t, float b1,
                    float b2, float eps, int lr_on_device, float* lr_t) {
     API_BEGIN
     HIPCHECK(hipSetDevice(device));
     if (!p || !g || !m || !v || !lr_t) throw P3dError("null argument");
     if (n < 1 || t < 1 || offset < 0 || offset > 3) throw P3dError("adam: bad length, step or offset");
-    DevBuf pb(n + offset), gb(n + offset), mb(n + offset), vb(n + offset), lrb(1);
-    const float* host[4] = {p, g, m, v};
-    float* dev[4] = {pb.p, gb.p, mb.p, vb.p};
-    for (int q = 0; q < 4; ++q) HIPCHECK(copy_now(dev[q] + offset, host[q], (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
     const float step = adam_step_size(lr, b1, b2, t);
-    if (lr_on_device) HIPCHECK(p3d_set_step_scalars(nullptr, lrb.p, 0, step, nullptr));
-    // from device memory the argument must not matter: NaN would show in every element if the kernel read it
-    HIPCHECK(p3d_adam(pb.p + offset, gb.p + offset, mb.p + offset, vb.p + offset, (long)n, lr_on_device ? NAN : step,
-                      lr_on_device ? lrb.p : nullptr, b1, b2, eps, nullptr));
-    HIPCHECK(hipDeviceSynchronize());
-    float* out[3] = {p, m, v};
-    float* outd[3] = {pb.p, mb.p, vb.p};
-    for (int q = 0; q < 3; ++q) HIPCHECK(copy_now(out[q], outd[q] + offset, (size_t)n * 4, hipMemcpyDeviceToHost, nullptr));
+    debug_opt_step(adam_update(b1, b2, eps), p, g, nullptr, m, v, n, offset, step, lr_on_device);
     *lr_t = step;
     API_END
 }
 
-// One Momentum / SGD launch (adam_range in net_sched.inc under those kinds), placed as p3d_debug_adam places its buffers.
+// Momentum / SGD, placed as p3d_debug_adam places its buffers.
 int p3d_debug_optimizer(int device, int kind, float* p, float* g, float* m, int64_t n, int offset, float lr, float momentum,
                         int use_nesterov, int lr_on_device) {
     API_BEGIN
@@ -1375,20 +1417,11 @@ int p3d_debug_optimizer(int device, int kind, float* p, float* g, float* m, int6
     if (!p || !g || !m) throw P3dError("null argument");
     if (kind != P3D_OPT_MOMENTUM && kind != P3D_OPT_SGD) throw P3dError("optimizer: kind 1 (momentum) or 2 (sgd); Adam has p3d_debug_adam");
     if (n < 1 || offset < 0 || offset > 3) throw P3dError("optimizer: bad length or offset");
-    DevBuf pb(n + offset), gb(n + offset), mb(n + offset), lrb(1);
-    float* host[3] = {p, g, m};
-    float* dev[3] = {pb.p, gb.p, mb.p};
-    for (int q = 0; q < 3; ++q) HIPCHECK(copy_now(dev[q] + offset, host[q], (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
-    if (lr_on_device) HIPCHECK(p3d_set_step_scalars(nullptr, lrb.p, 0, lr, nullptr));
-    // from device memory the argument must not matter (as p3d_debug_adam)
-    HIPCHECK(p3d_optimizer(kind, pb.p + offset, gb.p + offset, mb.p + offset, (long)n, lr_on_device ? NAN : lr,
-                           lr_on_device ? lrb.p : nullptr, momentum, use_nesterov, nullptr));
-    HIPCHECK(hipDeviceSynchronize());
-    for (int q = 0; q < 3; ++q) HIPCHECK(copy_now(host[q], dev[q] + offset, (size_t)n * 4, hipMemcpyDeviceToHost, nullptr));
+    debug_opt_step(momentum_update(kind, momentum, use_nesterov), p, g, g, m, nullptr, n, offset, lr, lr_on_device);
     API_END
 }
 
-// p3d_debug_adam_decay with Momentum / SGD as the update (decay_range under those kinds; update = 0 is the gradient-only launch).
+// p3d_debug_adam_decay with Momentum / SGD as the update (update = 0 is the gradient-only launch).
 int p3d_debug_optimizer_decay(int device, int kind, float* p, float* g, float* m, int64_t n, int offset, const int64_t* tile_off,
                               const int64_t* tile_len, const float* tile_c, int ntile, float lr, float momentum, int use_nesterov,
                               int lr_on_device, int update, double* term) {
@@ -1398,38 +1431,12 @@ int p3d_debug_optimizer_decay(int device, int kind, float* p, float* g, float* m
     if (kind != P3D_OPT_MOMENTUM && kind != P3D_OPT_SGD)
         throw P3dError("optimizer_decay: kind 1 (momentum) or 2 (sgd); Adam has p3d_debug_adam_decay");
     if (n < 1 || offset < 0 || offset > 3 || ntile < 1) throw P3dError("optimizer_decay: bad length, offset or tile count");
-    std::vector<P3dRegTile> tiles((size_t)ntile);
-    int64_t at = 0;
-    for (int k = 0; k < ntile; ++k) {
-        if (tile_off[k] != at || tile_len[k] < 1 || tile_len[k] > (1 << 30)) throw P3dError("optimizer_decay: tiles must cover [0, n) in order");
-        tiles[k] = {(long long)tile_off[k], (int)tile_len[k], tile_c[k]};
-        at += tile_len[k];
-    }
-    if (at != n) throw P3dError("optimizer_decay: tiles must cover [0, n) in order");
-    DevBuf pb(n + offset), gb(n + offset), mb(n + offset), lrb(1), tb(4 * (int64_t)ntile), part(2 * (int64_t)ntile), scal(4);
-    float* host[3] = {p, g, m};
-    float* dev[3] = {pb.p, gb.p, mb.p};
-    for (int q = 0; q < 3; ++q) HIPCHECK(copy_now(dev[q] + offset, host[q], (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
-    HIPCHECK(copy_now(tb.p, tiles.data(), tiles.size() * sizeof(P3dRegTile), hipMemcpyHostToDevice, nullptr));
-    // scal (zeroed): [0..1] the term, [2] the fold's counter
-    if (lr_on_device) HIPCHECK(p3d_set_step_scalars(nullptr, lrb.p, 0, lr, nullptr));
-    double* dterm = reinterpret_cast<double*>(scal.p);
-    double* dpart = reinterpret_cast<double*>(part.p);
-    P3dRegTile* dt = reinterpret_cast<P3dRegTile*>(tb.p);
-    unsigned* cnt = reinterpret_cast<unsigned*>(scal.p + 2);
-    if (update)
-        HIPCHECK(p3d_optimizer_decay(kind, pb.p + offset, gb.p + offset, mb.p + offset, (long)n, dt, ntile, 0, lr_on_device ? NAN : lr,
-                                     lr_on_device ? lrb.p : nullptr, momentum, use_nesterov, dpart, dpart, ntile, cnt, dterm, nullptr));
-    else      // the gradient-only launch is the same under every kind
-        HIPCHECK(p3d_adam_decay(pb.p + offset, gb.p + offset, mb.p + offset, mb.p + offset, (long)n, dt, ntile, 0, 0.f, nullptr, 0.f,
-                                0.f, 0.f, 0, dpart, dpart, ntile, cnt, dterm, nullptr));
-    HIPCHECK(hipDeviceSynchronize());
-    for (int q = 0; q < 3; ++q) HIPCHECK(copy_now(host[q], dev[q] + offset, (size_t)n * 4, hipMemcpyDeviceToHost, nullptr));
-    HIPCHECK(copy_now(term, dterm, sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    debug_opt_step(momentum_update(kind, momentum, use_nesterov, update), p, g, g, m, nullptr, n, offset, lr, lr_on_device,
+                   host_tiles(tile_off, tile_len, tile_c, ntile, n, "optimizer_decay"), term);
     API_END
 }
 
-// One regularised optimiser launch (decay_range in net_sched.inc) on raw inputs and a tile table, placed as p3d_debug_adam places them.
+// The regularised launch on a tile table, placed as p3d_debug_adam places its buffers (update = 0 is the gradient-only launch).
 int p3d_debug_adam_decay(int device, float* p, float* g, float* m, float* v, int64_t n, int offset, const int64_t* tile_off,
                          const int64_t* tile_len, const float* tile_c, int ntile, float lr, int64_t t, float b1, float b2, float eps,
                          int lr_on_device, int update, double* term, float* lr_t) {
@@ -1437,32 +1444,9 @@ int p3d_debug_adam_decay(int device, float* p, float* g, float* m, float* v, int
     HIPCHECK(hipSetDevice(device));
     if (!p || !g || !m || !v || !tile_off || !tile_len || !tile_c || !term || !lr_t) throw P3dError("null argument");
     if (n < 1 || t < 1 || offset < 0 || offset > 3 || ntile < 1) throw P3dError("adam_decay: bad length, step, offset or tile count");
-    std::vector<P3dRegTile> tiles((size_t)ntile);
-    int64_t at = 0;
-    for (int k = 0; k < ntile; ++k) {
-        if (tile_off[k] != at || tile_len[k] < 1 || tile_len[k] > (1 << 30)) throw P3dError("adam_decay: tiles must cover [0, n) in order");
-        tiles[k] = {(long long)tile_off[k], (int)tile_len[k], tile_c[k]};
-        at += tile_len[k];
-    }
-    if (at != n) throw P3dError("adam_decay: tiles must cover [0, n) in order");
-    DevBuf pb(n + offset), gb(n + offset), mb(n + offset), vb(n + offset), lrb(1), tb(4 * (int64_t)ntile), part(2 * (int64_t)ntile),
-        scal(4);
-    float* host[4] = {p, g, m, v};
-    float* dev[4] = {pb.p, gb.p, mb.p, vb.p};
-    for (int q = 0; q < 4; ++q) HIPCHECK(copy_now(dev[q] + offset, host[q], (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
-    HIPCHECK(copy_now(tb.p, tiles.data(), tiles.size() * sizeof(P3dRegTile), hipMemcpyHostToDevice, nullptr));
-    // scal (zeroed): [0..1] the term, [2] the fold's counter
+    const std::vector<P3dRegTile> tiles = host_tiles(tile_off, tile_len, tile_c, ntile, n, "adam_decay");
     const float step = adam_step_size(lr, b1, b2, t);
-    if (lr_on_device) HIPCHECK(p3d_set_step_scalars(nullptr, lrb.p, 0, step, nullptr));
-    double* dterm = reinterpret_cast<double*>(scal.p);
-    double* dpart = reinterpret_cast<double*>(part.p);
-    // from device memory the argument must not matter (as p3d_debug_adam)
-    HIPCHECK(p3d_adam_decay(pb.p + offset, gb.p + offset, mb.p + offset, vb.p + offset, (long)n, reinterpret_cast<P3dRegTile*>(tb.p), ntile,
-                            0, lr_on_device ? NAN : step, lr_on_device ? lrb.p : nullptr, b1, b2, eps, update ? 1 : 0, dpart, dpart,
-                            ntile, reinterpret_cast<unsigned*>(scal.p + 2), dterm, nullptr));
-    HIPCHECK(hipDeviceSynchronize());
-    for (int q = 0; q < 4; ++q) HIPCHECK(copy_now(host[q], dev[q] + offset, (size_t)n * 4, hipMemcpyDeviceToHost, nullptr));
-    HIPCHECK(copy_now(term, dterm, sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    debug_opt_step(adam_update(b1, b2, eps, update), p, g, g, m, v, n, offset, step, lr_on_device, tiles, term);
     *lr_t = step;
     API_END
 }

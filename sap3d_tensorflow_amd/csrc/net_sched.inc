@@ -28,24 +28,17 @@
             debug_sync("fwd", op, c);
         }
     }
+    // p3d_set_loss's kinds 0-2 into d_loss / d_dlogits.  Each rank's loss is a sum over its own clips, so under data parallelism
+    // the summed gradients are still the global batch's.
+    LossArgs loss_args() const {
+        return {loss_kind, logits->p, pred->p, d_y, (long)pred->rows(), head_sigmoid ? 1 : 0, d_loss, d_dlogits};
+    }
     void run_loss(const Ctx& c) {
         HIPCHECK(fill_async(d_loss, 0, sizeof(double), c.s, "loss"));
         if (loss_kind == P3D_LOSS_KLD_CC) return run_map_loss(c);
-        if (loss_kind != P3D_LOSS_SMOOTH_L1) return run_loss_option(c);
-        launch(c, "smooth_l1_kernel", 0, 12.0 * pred->rows(), [&]() { return p3d_smooth_l1(pred->p, d_y, pred->rows(), d_loss, d_dlogits, head_sigmoid ? 1 : 0, c.s); });
-    }
-    // p3d_set_loss's options, into the same d_loss / d_dlogits.  Each rank's loss is a sum over its own clips, so under data
-    // parallelism the summed gradients are still the global batch's, as for Smooth-L1.  Per element: BCE reads the logits, the
-    // target and (sigmoid head) pred and writes dlogits, ~8 operations (+3 for the sigmoid of a raw head); L1 reads pred and
-    // the target, 3 operations (+3 through the sigmoid).
-    void run_loss_option(const Ctx& c) {
-        const double rows = (double)pred->rows();
-        const int ts = head_sigmoid ? 1 : 0;
-        const bool bce = loss_kind == P3D_LOSS_BCE;
-        const double flops = rows * (bce ? (ts ? 8.0 : 11.0) : (ts ? 6.0 : 3.0));
-        const double bytes = rows * (bce && ts ? 16.0 : 12.0);
-        launch(c, bce ? "sigmoid_ce_kernel" : "l1_loss_kernel", flops, bytes,
-               [&]() { return p3d_loss(loss_kind, logits->p, pred->p, d_y, pred->rows(), d_loss, d_dlogits, ts, c.s); });
+        const LossArgs a = loss_args();
+        const LaunchDesc d = p3d_loss_desc(a);
+        launch(c, d.kernel, d.flops, d.bytes, [&]() { return p3d_loss(a, c.s); });
     }
     // P3D_LOSS_KLD_CC (map_loss.hip): w_kld KL + w_cc (1 - CC) per [H, W] map, summed over the B*T maps of this rank, so the
     // summed gradients under data parallelism are still the global batch's.  Three launches over the same grid; each reads s
@@ -252,22 +245,16 @@
     void adam_begin(const Ctx& c) {      // c.lr_dev set: the step size comes from device memory (graph replay), `step` is the caller's
         cur_lr_t = c.lr_dev ? 0.f : opt_step_size(++step);
     }
-    void adam_range(const Ctx& c, int64_t lo, int64_t hi) {
+    // One optimiser launch over the variables in [lo, hi): the update of the current kind, on g + c w when a regularisation term
+    // is on; update = false is the gradient-only launch of p3d_backward.
+    void adam_range(const Ctx& c, int64_t lo, int64_t hi, bool update = true) {
         if (hi <= lo) return;
         static const bool skip = p3d_tune_env("P3D_TUNE_SKIP_ADAM") != nullptr;      // timing diagnostic (tuning build; the weights stay put)
-        if (skip) return;
-        if (reg_terms) return decay_range(c, lo, hi, true);
-        const float lr_t = cur_lr_t;
-        if (opt_kind != P3D_OPT_ADAM) {      // Momentum: g, a, p read, a, p written (20 bytes); SGD: g, p read, p written (12)
-            launch(c, opt_kind == P3D_OPT_MOMENTUM ? "momentum_kernel" : "sgd_kernel", 0,
-                   (opt_kind == P3D_OPT_MOMENTUM ? 20.0 : 12.0) * (hi - lo), [&]() {
-                return p3d_optimizer(opt_kind, flat_p + lo, flat_g + lo, flat_m + lo, hi - lo, lr_t, c.lr_dev, momentum, use_nesterov, c.s);
-            });
-            return;
-        }
-        launch(c, "adam_kernel", 0, 28.0 * (hi - lo), [&]() {
-            return p3d_adam(flat_p + lo, flat_g + lo, flat_m + lo, flat_v + lo, hi - lo, lr_t, c.lr_dev, b1, b2, eps, c.s);
-        });
+        if (skip && update) return;
+        double decayed = 0.0;
+        const OptArgs a = opt_args(lo, hi, update, cur_lr_t, c.lr_dev, &decayed);
+        const LaunchDesc d = p3d_opt_desc(a, decayed);
+        launch(c, d.kernel, d.flops, d.bytes, [&]() { return p3d_opt_step(a, c.s); });
     }
     void run_adam(const Ctx& c) { adam_begin(c); adam_range(c, 0, n_train); }
 
@@ -340,11 +327,15 @@
         for (size_t k = 0; k < reg_tiles.size(); ++k) reg_decayed[k + 1] = reg_decayed[k] + (reg_tiles[k].c != 0.f ? reg_tiles[k].len : 0);
         drop_step_graph();
     }
-    // decay (+ Adam when update) of the variables in [lo, hi): adam_range's launch when a term is on, and the gradient-only
-    // launch of p3d_backward.  Per decayed element: 2 operations for g + c w, 2 for the term; 4 bytes more than Adam's 28 (the
-    // gradient written back), 12 without the update.
-    void decay_range(const Ctx& c, int64_t lo, int64_t hi, bool update) {
-        if (hi <= lo) return;
+    // adam_range's launch, from the handle: P3D_OPT_* are the UPD_* of p3d_kernels.h; with a term on, the tiles of [lo, hi), which
+    // must start and end on tile boundaries, and *decayed = its elements with c != 0.
+    OptArgs opt_args(int64_t lo, int64_t hi, bool update, float lr_t, const float* lr_dev, double* decayed) const {
+        OptArgs a;
+        a.update = update ? opt_kind : UPD_NONE;
+        a.p = flat_p + lo; a.g = flat_g + lo; a.m = flat_m + lo; a.v = flat_v + lo; a.n = (long)(hi - lo);
+        a.lr = lr_t; a.lr_dev = lr_dev;
+        a.b1 = b1; a.b2 = b2; a.eps = eps; a.momentum = momentum; a.nesterov = use_nesterov;
+        if (!reg_terms) return a;
         auto at = [&](int64_t off) {
             return (int)(std::lower_bound(reg_tiles.begin(), reg_tiles.end(), off,
                                           [](const P3dRegTile& t, int64_t o) { return t.off < o; }) - reg_tiles.begin());
@@ -352,24 +343,11 @@
         const int t0 = at(lo), t1 = at(hi);
         if (t0 >= (int)reg_tiles.size() || reg_tiles[t0].off != lo || t1 <= t0 || reg_tiles[t1 - 1].off + reg_tiles[t1 - 1].len != hi)
             throw P3dError("regularisation: range is not on tile boundaries");
-        const double nd = (double)(reg_decayed[t1] - reg_decayed[t0]);
-        const bool fold = lo == 0;
-        const float lr_t = cur_lr_t;
-        if (update && opt_kind != P3D_OPT_ADAM) {      // the update's bytes as in adam_range, plus the gradient written back
-            launch(c, opt_kind == P3D_OPT_MOMENTUM ? "momentum_decay_kernel" : "sgd_decay_kernel", 4.0 * nd,
-                   (opt_kind == P3D_OPT_MOMENTUM ? 20.0 : 12.0) * (hi - lo) + 4.0 * nd + 8.0 * (t1 - t0), [&]() {
-                return p3d_optimizer_decay(opt_kind, flat_p + lo, flat_g + lo, flat_m + lo, hi - lo, d_reg_tiles + t0, t1 - t0, lo, lr_t,
-                                           c.lr_dev, momentum, use_nesterov, d_reg_part + t0, d_reg_part,
-                                           fold ? (int)reg_tiles.size() : 0, d_reg_cnt, d_reg, c.s);
-            });
-            return;
-        }
-        launch(c, update ? "adam_decay_kernel" : "decay_grad_kernel", 4.0 * nd,
-               (update ? 28.0 * (hi - lo) + 4.0 * nd : 12.0 * nd) + 8.0 * (t1 - t0), [&]() {
-            return p3d_adam_decay(flat_p + lo, flat_g + lo, flat_m + lo, flat_v + lo, hi - lo, d_reg_tiles + t0, t1 - t0, lo, lr_t,
-                                  c.lr_dev, b1, b2, eps, update ? 1 : 0, d_reg_part + t0, d_reg_part, fold ? (int)reg_tiles.size() : 0,
-                                  d_reg_cnt, d_reg, c.s);
-        });
+        *decayed = (double)(reg_decayed[t1] - reg_decayed[t0]);
+        a.tiles = d_reg_tiles + t0; a.ntile = t1 - t0; a.tile_base = lo;
+        a.part = d_reg_part + t0; a.fold_part = d_reg_part; a.nfold = lo == 0 ? (int)reg_tiles.size() : 0;
+        a.counter = d_reg_cnt; a.term = d_reg;
+        return a;
     }
     double read_regularization() {
         double r = 0.0;

@@ -493,16 +493,25 @@ hipError_t p3d_headc_fwd(const HeadArgs& a, hipStream_t s, HeadLaunch* done = nu
 hipError_t p3d_headc_bwd_input(const HeadArgs& a, hipStream_t s);
 hipError_t p3d_headc_bwd_filter(const HeadArgs& a, hipStream_t s, HeadLaunch* done = nullptr);
 
-// ---- loss: Smooth-L1 sum (utils/network.py:49-62, train.py:159) fused with sigmoid backward ---
-// *loss_out += the loss (a double accumulator; the network zeroes it first).  dlogits = dL/dpred * pred*(1-pred).
-// done (optional): [0] = 1 float4 path (n % 4 == 0, every operand 16-byte aligned), 2 scalar path; [1] = blocks
-hipError_t p3d_smooth_l1(const float* pred, const float* target, long n, double* loss_out,
-                         float* dlogits, int through_sigmoid, hipStream_t s, unsigned* done = nullptr);
-// The loss options beside it (p3d_set_loss; same lanes, grid, fold and `done`): kind 1 sigmoid cross-entropy on the logits,
-// dlogits = sigmoid(z) - target (the stored pred when through_sigmoid); kind 2 L1 sum, dlogits = sign(pred - target), times
-// pred*(1-pred) when through_sigmoid.  Any other kind: hipErrorInvalidValue.
-hipError_t p3d_loss(int kind, const float* logits, const float* pred, const float* target, long n, double* loss_out,
-                    float* dlogits, int through_sigmoid, hipStream_t s, unsigned* done = nullptr);
+// What a launch list row says about one launch: the kernel's name and its flop / byte figures (bench.py's roofline).
+struct LaunchDesc { const char* kernel; double flops, bytes; };
+
+// ---- loss (p3d_set_loss kinds 0, 1, 2), fused with the gradient at the logits ----------------------------------
+// *loss_out += the loss (a double accumulator; the network zeroes it first).  z = logits, p = pred, t = target:
+//   kind 0, Smooth-L1 sum (utils/network.py:49-62, train.py:159): dlogits = dL/dpred, times pred*(1-pred) when through_sigmoid
+//   kind 1, sigmoid cross-entropy on the logits: dlogits = sigmoid(z) - t (the stored pred when through_sigmoid)
+//   kind 2, L1 sum (train.py:160): dlogits = sign(p - t), times pred*(1-pred) when through_sigmoid
+// Smooth-L1 never reads the logits.  Any other kind: hipErrorInvalidValue.
+struct LossArgs {
+    int kind;
+    const float* logits; const float* pred; const float* target;
+    long n;
+    int through_sigmoid;
+    double* loss_out; float* dlogits;
+};
+LaunchDesc p3d_loss_desc(const LossArgs& a);
+// done (optional): [0] = 1 float4 path (n % 4 == 0, every operand the kind uses 16-byte aligned), 2 scalar path; [1] = blocks
+hipError_t p3d_loss(const LossArgs& a, hipStream_t s, unsigned* done = nullptr);
 
 // ---- per-map saliency losses (map_loss.hip; p3d_set_loss P3D_LOSS_KLD_CC) ------------------------------------------------
 // `maps` maps of N = map_elems consecutive elements; s = pred (through_sigmoid) or 1/(1+expf(-logits)).  Three stages in
@@ -527,39 +536,41 @@ MapLossArgs p3d_map_loss_args(const float* logits, const float* pred, const floa
                               double* scratch, unsigned* counters);
 hipError_t p3d_map_loss_launch(int stage, const MapLossArgs& a, hipStream_t s);
 
-// ---- Adam (tf.train.AdamOptimizer, epsilon-hat form; train.py:168) ------------------------------
-// lr_dev non-null: the bias-corrected step size is read from device memory (captured step graphs), lr_t is ignored.
-// p, g, m, v must be 16-byte aligned (hipErrorInvalidValue otherwise): the kernel moves four elements at a time.
-hipError_t p3d_adam(float* p, const float* g, float* m, float* v, long n, float lr_t, const float* lr_dev, float b1, float b2,
-                    float eps, hipStream_t s);
-// Regularisation (p3d_set_regularization): the flat range is cut at plan time into tiles, each with ONE float32 coefficient c
-// (0 on undecayed variables and on slot padding).  off is relative to the table's base, len >= 1, tiles ascending and
-// contiguous.
+// ---- the optimiser step (p3d_set_optimizer), with or without regularisation (p3d_set_regularization) ---------------
+// Regularisation: the flat range is cut at plan time into tiles, each with ONE float32 coefficient c (0 on undecayed variables
+// and on slot padding).  off is relative to the table's base, len >= 1, tiles ascending and contiguous.
 struct P3dRegTile { long long off; int len; float c; };
-// Fused decay + Adam over n elements from p (one block per tile; tiles[0].off - tile_base == 0, the tiles cover [0, n)):
-// per element g' = g + c*p, written back to g where c != 0, then Adam on g' (update = 1), or nothing more (update = 0: the
-// gradient-only mode of p3d_backward).  Float32 order, no contraction: g' = fadd(g, fmul(c, p)); then Adam as adam_kernel
-// computes it -- on 4-groups that lie whole in [0, n) m = fma(b1, m, (1-b1) g'), v = fma(b2, v, ((1-b2) g') g'), on a partial
-// last group m = (b1 m) + ((1-b1) g'), v = (b2 v) + (((1-b2) g') g'); p -= (lr_t m) / (sqrt(v) + eps) -- so c = 0 gives its
-// bits.  part[k] = 0.5 * c * (sum of p^2 over tile k, in double; fixed order); with nfold > 0 the last block folds
+enum { UPD_NONE = -1, UPD_ADAM = 0, UPD_MOMENTUM = 1, UPD_SGD = 2 };      // the update kinds: P3D_OPT_* of include/p3d_hip.h
+// One launch over [p, p + n).  lr_dev non-null: the step size is read from device memory (captured step graphs), lr is ignored.
+//   UPD_ADAM (tf.train.AdamOptimizer, epsilon-hat form; train.py:168): lr is the bias-corrected step size; m, v its slots.
+//   UPD_MOMENTUM (tf.train.MomentumOptimizer): m is the accumulator, a = (a mom) + g, then p -= lr a, or with nesterov
+//     p -= (g lr) + ((a mom) lr) on the updated a.  UPD_SGD (GradientDescentOptimizer): p -= lr g.  No contraction, no fma.
+//   SGD never reads m, only Adam reads v.
+// ntile > 0, the decay part: one block per tile (tiles[0].off - tile_base == 0, the tiles cover [0, n)); per element
+// g' = g + c*p, written back to g where c != 0, then the update on g', or nothing more under UPD_NONE (the gradient-only mode
+// of p3d_backward, the same under every optimiser).  Float32 order, no contraction: g' = fadd(g, fmul(c, p)); then Adam as
+// adam_kernel computes it -- on 4-groups that lie whole in [0, n) m = fma(b1, m, (1-b1) g'), v = fma(b2, v, ((1-b2) g') g'), on
+// a partial last group m = (b1 m) + ((1-b1) g'), v = (b2 v) + (((1-b2) g') g'); p -= (lr m) / (sqrt(v) + eps) -- so c = 0
+// gives its bits.  part[k] = 0.5 * c * (sum of p^2 over tile k, in double; fixed order); with nfold > 0 the last block folds
 // fold_part[0 .. nfold) in index order into *term (the whole table's term, whichever ranges wrote it earlier on the stream;
-// *counter zero at launch).  p, g, m, v 16-byte aligned.
-hipError_t p3d_adam_decay(float* p, float* g, float* m, float* v, long n, const P3dRegTile* tiles, int ntile, long long tile_base,
-                          float lr_t, const float* lr_dev, float b1, float b2, float eps, int update, double* part,
-                          const double* fold_part, int nfold, unsigned* counter, double* term, hipStream_t s);
-// ---- Momentum and SGD (tf.train.MomentumOptimizer / GradientDescentOptimizer; p3d_set_optimizer) ---------------------
-// kind 1 (P3D_OPT_MOMENTUM): m is the accumulator, a = (a mom) + g, then p -= lr a, or with use_nesterov
-// p -= (g lr) + ((a mom) lr) on the updated a; kind 2 (P3D_OPT_SGD): p -= lr g, m unused (may be null).  No contraction, no fma.
-// lr_dev non-null: the step size is read from device memory (captured step graphs), lr is ignored.  p, g, m float-aligned at
-// the same place in a 16-byte line (the elements before the first 16-byte boundary go one by one).
-hipError_t p3d_optimizer(int kind, float* p, const float* g, float* m, long n, float lr, const float* lr_dev, float momentum,
-                         int use_nesterov, hipStream_t s);
-// p3d_adam_decay with Momentum or SGD as the update on g' = g + c*p (always applied: the gradient-only mode is p3d_adam_decay's);
-// p, g, m 16-byte aligned, as there.
-hipError_t p3d_optimizer_decay(int kind, float* p, float* g, float* m, long n, const P3dRegTile* tiles, int ntile, long long tile_base,
-                               float lr, const float* lr_dev, float momentum, int use_nesterov, double* part, const double* fold_part,
-                               int nfold, unsigned* counter, double* term, hipStream_t s);
-// per-step scalars of a captured train step: scal[0..1] = dropout seed (64 bit), scal[2] = Adam's bias-corrected step size
+// *counter zero at launch).
+// Refused (hipErrorInvalidValue): Adam and every decay form unless each pointer the kernel uses is 16-byte aligned (they move
+// four elements at a time); Momentum / SGD without decay unless p, g, m are float-aligned at the same place in a 16-byte line
+// (the elements before the first 16-byte boundary go one by one); UPD_NONE without a decay part.
+struct OptArgs {
+    int update = UPD_ADAM;
+    float* p = nullptr; float* g = nullptr; float* m = nullptr; float* v = nullptr;
+    long n = 0;
+    float lr = 0.f; const float* lr_dev = nullptr;
+    float b1 = 0.f, b2 = 0.f, eps = 0.f;             // Adam
+    float momentum = 0.f; int nesterov = 0;          // Momentum
+    const P3dRegTile* tiles = nullptr; int ntile = 0; long long tile_base = 0;      // the decay part (ntile == 0: none)
+    double* part = nullptr; const double* fold_part = nullptr; int nfold = 0; unsigned* counter = nullptr; double* term = nullptr;
+};
+// decayed_elems: the elements of [p, p + n) whose tile has c != 0 (they cost 4 operations and the gradient written back)
+LaunchDesc p3d_opt_desc(const OptArgs& a, double decayed_elems);
+hipError_t p3d_opt_step(const OptArgs& a, hipStream_t s);
+// per-step scalars of a captured train step: scal[0..1] = dropout seed (64 bit), scal[2] = the optimiser's step size (opt_step_size)
 hipError_t p3d_set_step_scalars(unsigned long long* seed_dst, float* lr_dst, unsigned long long seed, float lr_t, hipStream_t s);
 
 // ---- saliency metrics + frame pre-processing (metrics.hip; utils/metrics.py:25-287, dataflow.py:187-216) ------
