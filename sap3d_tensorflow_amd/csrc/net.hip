@@ -317,6 +317,14 @@ int bn_part_cap(int64_t rows, int C) {
     return (int)std::max<int64_t>({rows / 64 + 80, (int64_t)p3d_bn_stats_parts((long)rows, C), (int64_t)p3d_pw_stream_max_blocks(rows, C)});
 }
 
+// One grouped launch of `v` (conv_igemm2.hip, igemm2_group_kernel) with the summed work of its members.
+void launch_igemm_group(const Ctx& c, std::vector<IgemmArgs>& v, const P3dIgemmPlan& pl, const char* suffix) {
+    double fl = 0, by = 0;
+    for (auto& a : v) { double f1, b1; igemm_work(a, f1, b1); fl += f1; by += b1; }
+    const std::string kn = "igemm2_group_kernel<" + std::to_string(pl.bm) + "," + std::to_string(pl.bn) + ">" + suffix;
+    launch(c, kn.c_str(), fl, by, [&]() { return p3d_launch_igemm2_group(v.data(), (int)v.size(), pl, c.s); });
+}
+
 // A group of implicit-GEMM launches that together produce one output tensor (one conv forward,
 // or the residue classes of an input gradient / transposed conv).  Small problems slice K across blocks;
 // the slices are folded in a fixed order by the last arriving block (conv_igemm2.hip), so the output needs no
@@ -324,9 +332,8 @@ int bn_part_cap(int64_t rows, int C) {
 // fork / join non-null: the launches are independent (residue classes of a transposed conv write disjoint output
 // positions) and each of them leaves CUs idle (196 blocks of 128x128 on 256 CUs): odd ones go to the side stream so that
 // two classes run at a time.
-void run_igemm_group(const Ctx& c, std::vector<IgemmArgs>& v, float* out, int ld, int64_t rows, int C, bool accumulate,
-                     const StatSink* stats, hipEvent_t fork = nullptr, hipEvent_t join = nullptr) {
-    (void)out; (void)ld; (void)rows; (void)C;
+void run_igemm_group(const Ctx& c, std::vector<IgemmArgs>& v, bool accumulate, const StatSink* stats, hipEvent_t fork = nullptr,
+                     hipEvent_t join = nullptr) {
     int base = 0;
     for (auto& a : v) {
         a.accum = accumulate ? 1 : 0;
@@ -345,10 +352,7 @@ void run_igemm_group(const Ctx& c, std::vector<IgemmArgs>& v, float* out, int ld
     if (v.size() >= 2 && !c.dry) {
         const P3dIgemmPlan pl = p3d_igemm2_plan(v[0], 1);
         if (p3d_igemm2_groupable(v.data(), (int)v.size(), pl)) {
-            double fl = 0, by = 0;
-            for (auto& a : v) { double f1, b1; igemm_work(a, f1, b1); fl += f1; by += b1; }
-            const char* name = pl.bm == 128 ? (pl.bn == 128 ? "igemm2_group_kernel<128,128>" : "igemm2_group_kernel<128,64>") : "igemm2_group_kernel<64,64>";
-            launch(c, name, fl, by, [&]() { return p3d_launch_igemm2_group(v.data(), (int)v.size(), pl, c.s); });
+            launch_igemm_group(c, v, pl, "");
             if (stats && stats->nparts) *stats->nparts = base;
             return;
         }
@@ -372,22 +376,21 @@ void run_igemm_group(const Ctx& c, std::vector<IgemmArgs>& v, float* out, int ld
     if (stats && stats->nparts) *stats->nparts = base;
 }
 
-// Sibling convs on one input (ST_B, net_ops.inc conv()): each writes its statistics partials into its own BatchNorm's slot
-// from partial 0 ...
-void attach_sibling_stats(IgemmArgs& a, const StatSink& sink) {
+// Sibling convs on one input (ST_B, net_ops.inc conv()): each is a fresh launch that writes its statistics partials into its
+// own BatchNorm's slot from partial 0 (unlike a residue-class group, which stacks its bases) ...
+void sibling_prepare(IgemmArgs& a, const StatSink* sink) {
+    a.zeros = g_zero_page; a.accum = 0; a.statpart = nullptr; a.stat_base = 0;
+    if (!sink) return;
     const int mt = p3d_igemm2_mtiles(a, p3d_igemm2_plan(a, 1));
-    if (mt > sink.cap) throw P3dError("statistics partials overflow their arena slot");
-    a.statpart = sink.part; *sink.nparts = mt;
+    if (mt > sink->cap) throw P3dError("statistics partials overflow their arena slot");
+    a.statpart = sink->part; *sink->nparts = mt;
 }
 // ... and the pair goes out as ONE grouped launch when the plan allows it (either alone leaves most CUs idle), else as one
 // launch each.  Returns whether it was grouped.
 bool launch_siblings(const Ctx& c, std::vector<IgemmArgs>& v) {
     const P3dIgemmPlan pl = p3d_igemm2_plan(v[0], 1);
     if (p3d_igemm2_groupable(v.data(), (int)v.size(), pl)) {
-        double fl = 0, by = 0;
-        for (auto& q : v) { double f1, b1; igemm_work(q, f1, b1); fl += f1; by += b1; }
-        const std::string kn = std::string("igemm2_group_kernel<") + std::to_string(pl.bm) + "," + std::to_string(pl.bn) + ">(siblings)";
-        launch(c, kn.c_str(), fl, by, [&]() { return p3d_launch_igemm2_group(v.data(), (int)v.size(), pl, c.s); });
+        launch_igemm_group(c, v, pl, "(siblings)");
         return true;
     }
     for (auto& q : v) launch_igemm(c, q, 1);
@@ -659,35 +662,83 @@ ConvGeo make_geo(int Di, int Hi, int Wi, const int k[3], const int s[3]) {
     return g;
 }
 
+// tf.nn.max_pool3d SAME over an [N, g.I, C] tensor with row strides ldx / ldy (input / output, and their gradients): all of
+// PoolArgs but the pointers
+PoolArgs pool_args(const ConvGeo& g, int N, int C, int ldx, int ldy) {
+    PoolArgs a;
+    memset(&a, 0, sizeof(a));
+    a.N = N; a.Di = g.I[0]; a.Hi = g.I[1]; a.Wi = g.I[2]; a.C = C; a.ldx = a.lddx = ldx;
+    a.Do = g.O[0]; a.Ho = g.O[1]; a.Wo = g.O[2]; a.ldy = a.lddy = ldy;
+    a.kd = g.k[0]; a.kh = g.k[1]; a.kw = g.k[2]; a.sd = g.s[0]; a.sh = g.s[1]; a.sw = g.s[2];
+    a.pd = g.pad[0]; a.ph = g.pad[1]; a.pw = g.pad[2];
+    return a;
+}
+
 inline int pmod(int a, int m) { int r = a % m; return r < 0 ? r + m : r; }
 
 // firstconv1 (p3d.py:172) on its packed form: the clip is copied to 4 channels with the SAME padding of the W axis written out
 // (x4 [rows][Wp][4]), so that a kernel ROW is one tap of K = kw*4 contiguous floats (7 taps of K = 28 instead of 49 of K = 3).
-struct StemGeo { int Wp, K4, KH; int64_t xrows; };
-StemGeo stem_geo(const ConvGeo& g, int N) {
+// This describes the packed problem -- buffer sizes in floats and the packing launches -- and allocates nothing: the network
+// keeps the buffers in its arena, the op entry points in DevBufs.
+struct StemGeo {
+    ConvGeo g; int N, Cout, Wp, K4, KH; int64_t xrows;
+    int64_t x4_floats, w4_floats;      // x4; w4 and the packed filter gradient dw4 [kh][kw*4][Cout]
+    int64_t part_floats;               // scratch of the one-pass filter gradient (stem_wgrad.hip); 0: that kernel does not take the shape
+};
+StemGeo stem_geo(const ConvGeo& g, int N, int Cout) {
     if (g.k[0] != 1) throw P3dError("stem mode needs kd == 1");
     StemGeo sg;
     const int pad_total = std::max((g.O[2] - 1) * g.s[2] + g.k[2] - g.I[2], 0);
+    sg.g = g; sg.N = N; sg.Cout = Cout;
     sg.Wp = g.I[2] + pad_total; sg.K4 = g.k[2] * 4; sg.KH = g.k[1];
     sg.xrows = (int64_t)N * g.I[0] * g.I[1];
+    sg.x4_floats = sg.xrows * sg.Wp * 4; sg.w4_floats = (int64_t)sg.KH * sg.K4 * Cout;
+    sg.part_floats = p3d_stem_wgrad_ok(g.k[0], g.k[1], g.k[2], 3, Cout, g.s[0], g.s[1], g.s[2], g.O[2]) ? p3d_stem_wgrad_part_floats() : 0;
     return sg;
 }
-IgemmArgs stem_forward_args(const ConvGeo& g, int N, const StemGeo& sg, const float* x4, const float* w4, float* y, int ldy, int Cout,
-                            const float* bias) {
+// x -> x4 (whose padding columns the owner zeroed once) and, with w, the [kh*kw][3][Cout] filter -> w4
+void stem_pack(const Ctx& c, const StemGeo& sg, const float* x, float* x4, const float* w = nullptr, float* w4 = nullptr) {
+    const ConvGeo& g = sg.g;
+    launch(c, "stem_pad_kernel", 0, 28.0 * (sg.xrows * g.I[2]), [&]() { return p3d_stem_pad(x, x4, sg.xrows, g.I[2], sg.Wp, g.pad[2], c.s); });
+    if (w) launch(c, "stem_pack_w_kernel", 0, 8.0 * sg.KH * sg.K4 * sg.Cout, [&]() { return p3d_stem_pack_w(w, w4, sg.KH * g.k[2], sg.Cout, c.s); });
+}
+
+// ---- tap tables: the filter taps of a dense SAME conv in [kd][kh][kw] order, and the stem's kernel rows on its packed form;
+//      the forward and the filter gradient walk the same list.  Return the tap count.
+int conv_taps(const ConvGeo& g, P3dTap* taps) {
+    int t = 0;
+    for (int kd = 0; kd < g.k[0]; ++kd)
+        for (int kh = 0; kh < g.k[1]; ++kh)
+            for (int kw = 0; kw < g.k[2]; ++kw) {
+                if (t >= P3D_MAX_TAPS) throw P3dError("kernel has too many taps");
+                taps[t].dd = (int16_t)(kd - g.pad[0]);
+                taps[t].dh = (int16_t)(kh - g.pad[1]);
+                taps[t].dw = (int16_t)(kw - g.pad[2]);
+                taps[t].widx = (int16_t)((kd * g.k[1] + kh) * g.k[2] + kw);
+                ++t;
+            }
+    return t;
+}
+int stem_row_taps(const StemGeo& sg, P3dTap* taps) {
+    for (int kh = 0; kh < sg.KH; ++kh) { taps[kh].dd = 0; taps[kh].dh = (int16_t)(kh - sg.g.pad[1]); taps[kh].dw = 0; taps[kh].widx = (int16_t)kh; }
+    return sg.KH;
+}
+
+IgemmArgs stem_forward_args(const StemGeo& sg, const float* x4, const float* w4, float* y, int ldy, const float* bias) {
+    const ConvGeo& g = sg.g;
     IgemmArgs a;
     memset(&a, 0, sizeof(a));
-    a.N = N; a.Di = g.I[0]; a.Hi = g.I[1]; a.Wi = sg.Wp; a.ldx = 4; a.K = sg.K4;
+    a.N = sg.N; a.Di = g.I[0]; a.Hi = g.I[1]; a.Wi = sg.Wp; a.ldx = 4; a.K = sg.K4;
     a.Gd = g.O[0]; a.Gh = g.O[1]; a.Gw = g.O[2]; a.isd = g.s[0]; a.ish = g.s[1]; a.isw = g.s[2];
-    a.ntaps = sg.KH;
-    for (int kh = 0; kh < sg.KH; ++kh) { a.taps[kh].dd = 0; a.taps[kh].dh = (int16_t)(kh - g.pad[1]); a.taps[kh].dw = 0; a.taps[kh].widx = (int16_t)kh; }
-    a.x = x4; a.y = y; a.Do = g.O[0]; a.Ho = g.O[1]; a.Wo = g.O[2]; a.ldy = ldy; a.Nc = Cout;
+    a.ntaps = stem_row_taps(sg, a.taps);
+    a.x = x4; a.y = y; a.Do = g.O[0]; a.Ho = g.O[1]; a.Wo = g.O[2]; a.ldy = ldy; a.Nc = sg.Cout;
     a.osd = a.osh = a.osw = 1; a.w = w4; a.bias = bias;
     return a;
 }
 
 // ---- launch-argument builders on the shared geometry ---------------------------------------------
 IgemmArgs igemm_conv_forward(const ConvGeo& g, int N, const float* x, int ldx, int Cin, float* y, int ldy, int Cout,
-                             const float* w, const float* bias, int accum, bool stem = false) {
+                             const float* w, const float* bias, int accum) {
     IgemmArgs a;
     memset(&a, 0, sizeof(a));
     a.x = x; a.N = N; a.Di = g.I[0]; a.Hi = g.I[1]; a.Wi = g.I[2]; a.ldx = ldx; a.K = Cin;
@@ -696,19 +747,7 @@ IgemmArgs igemm_conv_forward(const ConvGeo& g, int N, const float* x, int ldx, i
     a.y = y; a.Do = g.O[0]; a.Ho = g.O[1]; a.Wo = g.O[2]; a.ldy = ldy; a.Nc = Cout;
     a.osd = a.osh = a.osw = 1;
     a.w = w; a.wT = 0; a.bias = bias; a.accum = accum;
-    if (stem) throw P3dError("the 3-channel stem runs on its packed form (stem_forward_args)");
-    int t = 0;
-    for (int kd = 0; kd < g.k[0]; ++kd)
-        for (int kh = 0; kh < g.k[1]; ++kh)
-            for (int kw = 0; kw < g.k[2]; ++kw) {
-                if (t >= P3D_MAX_TAPS) throw P3dError("kernel has too many taps");
-                a.taps[t].dd = (int16_t)(kd - g.pad[0]);
-                a.taps[t].dh = (int16_t)(kh - g.pad[1]);
-                a.taps[t].dw = (int16_t)(kw - g.pad[2]);
-                a.taps[t].widx = (int16_t)((kd * g.k[1] + kh) * g.k[2] + kw);
-                ++t;
-            }
-    a.ntaps = t;
+    a.ntaps = conv_taps(g, a.taps);
     return a;
 }
 
@@ -764,10 +803,11 @@ std::vector<IgemmArgs> igemm_conv_input_side(const ConvGeo& g, int N, const floa
 
 // Filter gradient of the [1,kh,kw,3,Cout] stem conv on its packed form (conv(): "stem"): x4 is the 4-channel, W-padded copy
 // of the clip ([rows][Wp][4]), dw4 the packed gradient [kh][kw*4][Cout] (zeroed here); dw += its three real channels.
-void stem_filter_gradient(const Ctx& c, const ConvGeo& g, int N, int Wp, const float* x4, const float* dy, int ldy, int Cout, float* dw4,
-                          float* dw, float* dbias, bool greedy, float* onepass_part = nullptr, const BnBwdArgs* through_bn = nullptr) {
-    const int KH = g.k[1], K4 = g.k[2] * 4;
-    if (onepass_part && !dbias && p3d_stem_wgrad_ok(g.k[0], g.k[1], g.k[2], 3, Cout, g.s[0], g.s[1], g.s[2], g.O[2])) {
+void stem_filter_gradient(const Ctx& c, const StemGeo& sg, const float* x4, const float* dy, int ldy, float* dw4, float* dw, float* dbias,
+                          bool greedy, float* onepass_part = nullptr, const BnBwdArgs* through_bn = nullptr) {
+    const ConvGeo& g = sg.g;
+    const int N = sg.N, Wp = sg.Wp, Cout = sg.Cout, KH = sg.KH, K4 = sg.K4;
+    if (onepass_part && !dbias && sg.part_floats) {
         // one pass over the output gradient (stem_wgrad.hip); through_bn: that gradient is the BatchNorm + ReLU OUTPUT's and
         // the normalisation's backward apply pass runs on this kernel's operand path
         StemWgradArgs a;
@@ -794,8 +834,7 @@ void stem_filter_gradient(const Ctx& c, const ConvGeo& g, int N, int Wp, const f
     wa.x = x4; wa.N = N; wa.Di = g.I[0]; wa.Hi = g.I[1]; wa.Wi = Wp; wa.ldx = 4; wa.K = K4;
     wa.Gd = g.O[0]; wa.Gh = g.O[1]; wa.Gw = g.O[2]; wa.isd = g.s[0]; wa.ish = g.s[1]; wa.isw = g.s[2];
     wa.dy = dy; wa.ldy = ldy; wa.Nc = Cout; wa.dw = dw4; wa.dbias = dbias; wa.ksplit = 1;
-    wa.ntaps = KH;
-    for (int kh = 0; kh < KH; ++kh) { wa.taps[kh].dd = 0; wa.taps[kh].dh = (int16_t)(kh - g.pad[1]); wa.taps[kh].dw = 0; wa.taps[kh].widx = (int16_t)kh; }
+    wa.ntaps = stem_row_taps(sg, wa.taps);
     wa.greedy = greedy ? 1 : 0;
     wa.pair = K4 <= 32 ? 1 : 0;            // 28 floats per kernel row: two rows of the 7x7 kernel per 64-row tile
     launch_wgrad(c, wa);
@@ -803,26 +842,14 @@ void stem_filter_gradient(const Ctx& c, const ConvGeo& g, int N, int Wp, const f
 }
 
 WgradArgs wgrad_conv(const ConvGeo& g, int N, const float* x, int ldx, int Cin, const float* dy, int ldy, int Cout,
-                     float* dw, float* dbias, bool stem = false) {
+                     float* dw, float* dbias) {
     WgradArgs a;
     memset(&a, 0, sizeof(a));
     a.x = x; a.N = N; a.Di = g.I[0]; a.Hi = g.I[1]; a.Wi = g.I[2]; a.ldx = ldx; a.K = Cin;
     a.Gd = g.O[0]; a.Gh = g.O[1]; a.Gw = g.O[2];
     a.isd = g.s[0]; a.ish = g.s[1]; a.isw = g.s[2];
     a.dy = dy; a.ldy = ldy; a.Nc = Cout; a.dw = dw; a.dbias = dbias; a.ksplit = 1;
-    if (stem) throw P3dError("the 3-channel stem's filter gradient runs on its packed form (stem_filter_gradient)");
-    int t = 0;
-    for (int kd = 0; kd < g.k[0]; ++kd)
-        for (int kh = 0; kh < g.k[1]; ++kh)
-            for (int kw = 0; kw < g.k[2]; ++kw) {
-                if (t >= P3D_MAX_TAPS) throw P3dError("kernel has too many taps");
-                a.taps[t].dd = (int16_t)(kd - g.pad[0]);
-                a.taps[t].dh = (int16_t)(kh - g.pad[1]);
-                a.taps[t].dw = (int16_t)(kw - g.pad[2]);
-                a.taps[t].widx = (int16_t)((kd * g.k[1] + kh) * g.k[2] + kw);
-                ++t;
-            }
-    a.ntaps = t;
+    a.ntaps = conv_taps(g, a.taps);
     return a;
 }
 
@@ -1056,6 +1083,13 @@ struct p3d_handle {
     // Producers of tensors that the one-launch small-tensor BN will consume need no statistics epilogue.
     static bool bn_is_small(int64_t rows, int C, bool dropout = false) { return bn_path(rows, C, dropout, 0, 0, 0.f) == BN_SMALL; }
     BN* stats_target(BN* bn, int64_t rows, int C, bool dropout = false) { return bn_is_small(rows, C, dropout) ? nullptr : bn; }
+    // The BatchNorm whose slot a producer's epilogue statistics fill, as that launch's sink (held in `sink`); null: the launch writes
+    // none.  fused: a fused BatchNorm behind the conv always needs the tile partials (the one-launch small-tensor BN does not).
+    const StatSink* epilogue_sink(StatSink& sink, BN* bn, int64_t rows, int C, bool dropout, bool fused = false) {
+        if (!bn || !(fused || stats_target(bn, rows, C, dropout))) return nullptr;
+        sink = bn_sink(bn);
+        return &sink;
+    }
     BnParams bn_params(BN* bn) {      // (add_bn lays scale, shift, mean, invstd out as one [4][C] table)
         return bn_layout(bn->gamma->p, bn->beta->p, bn->mm->p, bn->mv->p, bn->scale,
                          bn->part_off >= 0 ? statpart_arena + bn->part_off : nullptr, bn->nparts, bn->C);

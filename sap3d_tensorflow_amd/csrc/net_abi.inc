@@ -763,6 +763,37 @@ struct DevBuf {
 };
 int64_t prod5(const int64_t s[5]) { return s[0] * s[1] * s[2] * s[3] * s[4]; }
 bool is_stem_shape(const int64_t xs[5], const int64_t ws[5]) { return xs[4] % 4 != 0 && ws[0] == 1; }
+// One conv on dense tensors of the given shapes, described the way conv() / deconv() describe theirs: geometry, channel counts, rows
+// of the conv's output and its forward launches.  transpose: xs is the input of tf.layers.conv3d_transpose and ws its kernel
+// [kd,kh,kw,Cout,Cin].  The stem ([1,kh,kw,3,C]) runs on its packed form `sg` and reads the packed copies x4 / w4 (stem_pack).
+struct ConvProblem {
+    ConvGeo g; int N = 0, Cin = 0, Cout = 0; int64_t rows = 0; bool transpose = false, stem = false; StemGeo sg{};
+    int64_t ny() const { return rows * Cout; }
+    std::vector<IgemmArgs> forward(const float* x, const float* w, float* y, const float* bias, const float* x4 = nullptr,
+                                   const float* w4 = nullptr) const {
+        if (transpose) return igemm_conv_input_side(g, N, x, Cin, Cin, y, Cout, Cout, w, bias, 0, true);
+        if (stem) return {stem_forward_args(sg, x4, w4, y, Cout, bias)};
+        return {igemm_conv_forward(g, N, x, Cin, Cin, y, Cout, Cout, w, bias, 0)};
+    }
+};
+ConvProblem conv_problem(const int64_t xs[5], const int64_t ws[5], const int s[3], int transpose) {
+    ConvProblem r;
+    const int k[3] = {(int)ws[0], (int)ws[1], (int)ws[2]};
+    r.N = (int)xs[0]; r.Cin = (int)xs[4]; r.transpose = transpose != 0;
+    if (transpose) {
+        r.Cout = (int)ws[3];
+        if (ws[4] != r.Cin) throw P3dError("kernel Cin mismatch");
+        r.g = make_geo((int)xs[1] * s[0], (int)xs[2] * s[1], (int)xs[3] * s[2], k, s);      // the conv whose input is the output
+        r.rows = xs[0] * r.g.I[0] * r.g.I[1] * r.g.I[2];
+        return r;
+    }
+    r.Cout = (int)ws[4];
+    r.g = make_geo((int)xs[1], (int)xs[2], (int)xs[3], k, s);
+    r.rows = xs[0] * r.g.O[0] * r.g.O[1] * r.g.O[2];
+    r.stem = is_stem_shape(xs, ws);
+    if (r.stem) r.sg = stem_geo(r.g, r.N, r.Cout);
+    return r;
+}
 }  // namespace
 
 // ---- decisions of the last forward (test hook, include/p3d_hip.h) ---------------------------------------------------------
@@ -816,27 +847,18 @@ int p3d_op_conv3d(int device, const float* x, const int64_t xs[5], const float* 
                   const float* bias, float* y) {
     API_BEGIN
     HIPCHECK(hipSetDevice(device));
-    const int k[3] = {(int)ws[0], (int)ws[1], (int)ws[2]};
-    const ConvGeo g = make_geo((int)xs[1], (int)xs[2], (int)xs[3], k, s);
-    const int Cin = (int)xs[4], Cout = (int)ws[4];
-    const int64_t ny = xs[0] * g.O[0] * g.O[1] * g.O[2] * Cout;
-    DevBuf dx(prod5(xs), x), dw(prod5(ws), w), dy(ny), db(Cout, bias);
+    const ConvProblem p = conv_problem(xs, ws, s, 0);
+    DevBuf dx(prod5(xs), x), dw(prod5(ws), w), dy(p.ny()), db(p.Cout, bias), x4(p.sg.x4_floats), w4(p.sg.w4_floats);
     ensure_zero_page();
     Ctx c;
-    if (is_stem_shape(xs, ws)) {          // [1,kh,kw,3,Cout] on its packed form, like the network's stem
-        if (Cin != 3) throw P3dError("conv3d: channel counts that are not multiples of 4 are supported for the 3-channel stem only");
-        const StemGeo sg = stem_geo(g, (int)xs[0]);
-        DevBuf x4(sg.xrows * sg.Wp * 4), w4((int64_t)sg.KH * sg.K4 * Cout);
-        HIPCHECK(p3d_stem_pad(dx.p, x4.p, sg.xrows, g.I[2], sg.Wp, g.pad[2], c.s));
-        HIPCHECK(p3d_stem_pack_w(dw.p, w4.p, sg.KH * g.k[2], Cout, c.s));
-        std::vector<IgemmArgs> v{stem_forward_args(g, (int)xs[0], sg, x4.p, w4.p, dy.p, Cout, Cout, bias ? db.p : nullptr)};
-        run_igemm_group(c, v, dy.p, Cout, ny / Cout, Cout, false, nullptr);
-        HIPCHECK(hipDeviceSynchronize());
-    } else {
-        std::vector<IgemmArgs> v{igemm_conv_forward(g, (int)xs[0], dx.p, Cin, Cin, dy.p, Cout, Cout, dw.p, bias ? db.p : nullptr, 0, false)};
-        run_igemm_group(c, v, dy.p, Cout, ny / Cout, Cout, false, nullptr);
+    if (p.stem) {          // [1,kh,kw,3,Cout] on its packed form, like the network's stem
+        if (p.Cin != 3) throw P3dError("conv3d: channel counts that are not multiples of 4 are supported for the 3-channel stem only");
+        stem_pack(c, p.sg, dx.p, x4.p, dw.p, w4.p);
     }
-    dy.get(y, ny);
+    auto v = p.forward(dx.p, dw.p, dy.p, bias ? db.p : nullptr, x4.p, w4.p);
+    run_igemm_group(c, v, false, nullptr);
+    if (p.stem) HIPCHECK(hipDeviceSynchronize());
+    dy.get(y, p.ny());
     API_END
 }
 
@@ -844,14 +866,11 @@ int p3d_op_conv3d_backprop_input(int device, const float* dyh, const float* w, c
                                  const int64_t xs[5], float* dxh) {
     API_BEGIN
     HIPCHECK(hipSetDevice(device));
-    const int k[3] = {(int)ws[0], (int)ws[1], (int)ws[2]};
-    const ConvGeo g = make_geo((int)xs[1], (int)xs[2], (int)xs[3], k, s);
-    const int Cin = (int)xs[4], Cout = (int)ws[4];
-    const int64_t ny = xs[0] * g.O[0] * g.O[1] * g.O[2] * Cout;
-    DevBuf dy(ny, dyh), dw(prod5(ws), w), dx(prod5(xs));
-    auto v = igemm_conv_input_side(g, (int)xs[0], dy.p, Cout, Cout, dx.p, Cin, Cin, dw.p, nullptr, 0, true);
+    const ConvProblem p = conv_problem(xs, ws, s, 0);
+    DevBuf dy(p.ny(), dyh), dw(prod5(ws), w), dx(prod5(xs));
+    auto v = igemm_conv_input_side(p.g, p.N, dy.p, p.Cout, p.Cout, dx.p, p.Cin, p.Cin, dw.p, nullptr, 0, true);
     ensure_zero_page();
-    { Ctx c; run_igemm_group(c, v, dx.p, Cin, prod5(xs) / Cin, Cin, false, nullptr); }
+    { Ctx c; run_igemm_group(c, v, false, nullptr); }
     dx.get(dxh, prod5(xs));
     API_END
 }
@@ -860,29 +879,23 @@ int p3d_op_conv3d_backprop_filter(int device, const float* x, const int64_t xs[5
                                   const int s[3], float* dwh, float* dbh) {
     API_BEGIN
     HIPCHECK(hipSetDevice(device));
-    const int k[3] = {(int)ws[0], (int)ws[1], (int)ws[2]};
-    const ConvGeo g = make_geo((int)xs[1], (int)xs[2], (int)xs[3], k, s);
-    const int Cin = (int)xs[4], Cout = (int)ws[4];
-    const int64_t ny = xs[0] * g.O[0] * g.O[1] * g.O[2] * Cout;
-    DevBuf dx(prod5(xs), x), dy(ny, dyh), dw(prod5(ws)), db(Cout);
+    const ConvProblem p = conv_problem(xs, ws, s, 0);
+    const int Cin = p.Cin, Cout = p.Cout;
+    DevBuf dx(prod5(xs), x), dy(p.ny(), dyh), dw(prod5(ws)), db(Cout);
     ensure_zero_page();
-    if (is_stem_shape(xs, ws)) {          // [1,kh,kw,3,Cout] on its packed form, like the network's stem (no atomics anywhere)
+    Ctx c;
+    if (p.stem) {          // [1,kh,kw,3,Cout] on its packed form, like the network's stem (no atomics anywhere)
         if (Cin != 3) throw P3dError("conv3d_backprop_filter: channel counts that are not multiples of 4 are supported for the 3-channel stem only");
-        const StemGeo sg = stem_geo(g, (int)xs[0]);
-        const int Wp = sg.Wp;
-        const int64_t xrows = sg.xrows;
-        DevBuf x4(xrows * Wp * 4), dw4((int64_t)sg.KH * sg.K4 * Cout), spart(p3d_stem_wgrad_part_floats());
-        Ctx c;
-        HIPCHECK(p3d_stem_pad(dx.p, x4.p, xrows, g.I[2], Wp, g.pad[2], c.s));
-        if (p3d_stem_wgrad_ok(k[0], k[1], k[2], Cin, Cout, s[0], s[1], s[2], g.O[2])) {      // the network's stem: one pass (stem_wgrad.hip)
-            stem_filter_gradient(c, g, (int)xs[0], Wp, x4.p, dy.p, Cout, Cout, dw4.p, dw.p, nullptr, false, spart.p);
-            if (dbh) HIPCHECK(p3d_colsum(dy.p, Cout, ny / Cout, Cout, db.p, c.s));
+        DevBuf x4(p.sg.x4_floats), dw4(p.sg.w4_floats), spart(p.sg.part_floats);
+        stem_pack(c, p.sg, dx.p, x4.p);
+        if (p.sg.part_floats) {      // the network's stem: one pass (stem_wgrad.hip)
+            stem_filter_gradient(c, p.sg, x4.p, dy.p, Cout, dw4.p, dw.p, nullptr, false, spart.p);
+            if (dbh) HIPCHECK(p3d_colsum(dy.p, Cout, p.rows, Cout, db.p, c.s));
         } else
-        stem_filter_gradient(c, g, (int)xs[0], Wp, x4.p, dy.p, Cout, Cout, dw4.p, dw.p, dbh ? db.p : nullptr, false);
+        stem_filter_gradient(c, p.sg, x4.p, dy.p, Cout, dw4.p, dw.p, dbh ? db.p : nullptr, false);
         HIPCHECK(hipDeviceSynchronize());
     } else {
-        WgradArgs a = wgrad_conv(g, (int)xs[0], dx.p, Cin, Cin, dy.p, Cout, Cout, dw.p, dbh ? db.p : nullptr, false);
-        Ctx c; launch_wgrad(c, a);
+        launch_wgrad(c, wgrad_conv(p.g, p.N, dx.p, Cin, Cin, dy.p, Cout, Cout, dw.p, dbh ? db.p : nullptr));
     }
     dw.get(dwh, prod5(ws));
     if (dbh) db.get(dbh, Cout);
@@ -898,26 +911,26 @@ int p3d_debug_stem_wgrad_through_bn(int device, const float* x, const int64_t xs
     API_BEGIN
     HIPCHECK(hipSetDevice(device));
     if (!x || !y || !dz || !tab || !coef || !dw_fused || !dw_two_launches) throw P3dError("null argument");
-    const int k[3] = {1, 7, 7}, s[3] = {1, 2, 2};
-    const int Cout = 64;
-    const ConvGeo g = make_geo((int)xs[1], (int)xs[2], (int)xs[3], k, s);
-    if (xs[4] != 3 || !p3d_stem_wgrad_ok(1, 7, 7, 3, Cout, 1, 2, 2, g.O[2])) throw P3dError("not a stem shape the one-pass kernel takes");
-    const int64_t rows = xs[0] * g.O[0] * g.O[1] * g.O[2], ny = rows * Cout;
-    const int64_t nw = 7 * 7 * 3 * Cout;
+    const int64_t ws[5] = {1, 7, 7, 3, 64};
+    const int s[3] = {1, 2, 2};
+    const ConvProblem cp = conv_problem(xs, ws, s, 0);
+    const StemGeo& sg = cp.sg;
+    if (xs[4] != 3 || !sg.part_floats) throw P3dError("not a stem shape the one-pass kernel takes");
+    const int Cout = cp.Cout;
+    const int64_t rows = cp.rows, ny = cp.ny(), nw = prod5(ws);
     DevBuf dx(prod5(xs), x), dyb(ny, y), dzb(ny, dz), tb(5 * Cout, tab), cf(2 * Cout, coef), dyo(ny), dw1(nw), dw2(nw);
     ensure_zero_page();
-    const StemGeo sg = stem_geo(g, (int)xs[0]);
-    DevBuf x4(sg.xrows * sg.Wp * 4), dw4((int64_t)sg.KH * sg.K4 * Cout), spart(p3d_stem_wgrad_part_floats());
+    DevBuf x4(sg.x4_floats), dw4(sg.w4_floats), spart(sg.part_floats);
     Ctx c;
-    HIPCHECK(p3d_stem_pad(dx.p, x4.p, sg.xrows, g.I[2], sg.Wp, g.pad[2], c.s));
+    stem_pack(c, sg, dx.p, x4.p);
     BnPass p;
     p.mode = 0; p.M = rows; p.C = Cout; p.dz = dzb.p; p.lddz = Cout; p.y1 = dyb.p; p.ld1 = Cout; p.dy1 = dyo.p; p.lddy1 = Cout;
     p.bn[0] = bn_layout(tb.p + 4 * Cout, nullptr, nullptr, nullptr, tb.p, nullptr, 0, Cout);
     p.coef[0] = cf.p; p.batch[0] = batch ? 1 : 0;
     const BnBwdArgs a = bn_bwd_args(p);
-    stem_filter_gradient(c, g, (int)xs[0], sg.Wp, x4.p, nullptr, Cout, Cout, dw4.p, dw1.p, nullptr, false, spart.p, &a);       // fused
+    stem_filter_gradient(c, sg, x4.p, nullptr, Cout, dw4.p, dw1.p, nullptr, false, spart.p, &a);       // fused
     HIPCHECK(p3d_bn_bwd_apply(a, c.s));                                                                                           // two launches
-    stem_filter_gradient(c, g, (int)xs[0], sg.Wp, x4.p, dyo.p, Cout, Cout, dw4.p, dw2.p, nullptr, false, spart.p, nullptr);
+    stem_filter_gradient(c, sg, x4.p, dyo.p, Cout, dw4.p, dw2.p, nullptr, false, spart.p, nullptr);
     HIPCHECK(hipDeviceSynchronize());
     dw1.get(dw_fused, nw);
     dw2.get(dw_two_launches, nw);
@@ -926,35 +939,12 @@ int p3d_debug_stem_wgrad_through_bn(int device, const float* x, const int64_t xs
 
 // ---- BatchNorm statistics behind a conv (test hooks, include/p3d_hip.h) ----------------------------------------------------
 namespace {
-// The launches of one conv that feeds a BatchNorm, built the way conv() / deconv() build them.  transpose: xs is the input of
-// tf.layers.conv3d_transpose and ws its kernel [kd,kh,kw,Cout,Cin].  The stem ([1,kh,kw,3,C]) reads its packed copies x4 / w4.
-struct ConvBnGroup { std::vector<IgemmArgs> v; int64_t rows = 0; int C = 0; bool stem = false; ConvGeo g; StemGeo sg{}; };
-ConvBnGroup conv_bn_group(const int64_t xs[5], const int64_t ws[5], const int s[3], int transpose, const float* x, const float* w,
-                          float* y, const float* bias, const float* x4 = nullptr, const float* w4 = nullptr) {
-    ConvBnGroup r;
-    const int k[3] = {(int)ws[0], (int)ws[1], (int)ws[2]};
-    const int Cin = (int)xs[4];
-    if (transpose) {
-        r.C = (int)ws[3];
-        if (ws[4] != Cin) throw P3dError("kernel Cin mismatch");
-        r.g = make_geo((int)xs[1] * s[0], (int)xs[2] * s[1], (int)xs[3] * s[2], k, s);
-        r.rows = xs[0] * r.g.I[0] * r.g.I[1] * r.g.I[2];
-        r.v = igemm_conv_input_side(r.g, (int)xs[0], x, Cin, Cin, y, r.C, r.C, w, bias, 0, true);
-        return r;
-    }
-    r.C = (int)ws[4];
-    if (ws[3] != Cin) throw P3dError("filter Cin mismatch");
-    r.g = make_geo((int)xs[1], (int)xs[2], (int)xs[3], k, s);
-    r.rows = xs[0] * r.g.O[0] * r.g.O[1] * r.g.O[2];
-    if (is_stem_shape(xs, ws)) {
-        if (Cin != 3 || bias) throw P3dError("the stem path is for [1,kh,kw,3,C] kernels without bias");
-        r.stem = true;
-        r.sg = stem_geo(r.g, (int)xs[0]);
-        r.v.push_back(stem_forward_args(r.g, (int)xs[0], r.sg, x4, w4, y, r.C, r.C, nullptr));
-    } else {
-        r.v.push_back(igemm_conv_forward(r.g, (int)xs[0], x, Cin, Cin, y, r.C, r.C, w, bias, 0, false));
-    }
-    return r;
+// A conv that feeds a BatchNorm: what conv() / deconv() refuse is refused here.
+ConvProblem conv_bn_problem(const int64_t xs[5], const int64_t ws[5], const int s[3], int transpose, bool bias) {
+    const ConvProblem p = conv_problem(xs, ws, s, transpose);
+    if (!transpose && ws[3] != p.Cin) throw P3dError("filter Cin mismatch");
+    if (p.stem && (p.Cin != 3 || bias)) throw P3dError("the stem path is for [1,kh,kw,3,C] kernels without bias");
+    return p;
 }
 int group_parts(const std::vector<IgemmArgs>& v) {
     int n = 0;
@@ -966,10 +956,10 @@ int group_parts(const std::vector<IgemmArgs>& v) {
 int p3d_debug_stat_parts(const int64_t xs[5], const int64_t ws[5], const int s[3], int transpose, int* written, int* cap) {
     API_BEGIN
     if (!xs || !ws || !s || !written || !cap) throw P3dError("null argument");
-    const ConvBnGroup r = conv_bn_group(xs, ws, s, transpose, nullptr, nullptr, nullptr, nullptr);
-    const bool small = p3d_bn_small_ok((long)r.rows, r.C);      // (the network's stats_target: no epilogue partials)
-    *written = small ? 0 : group_parts(r.v);
-    *cap = small ? 0 : bn_part_cap(r.rows, r.C);
+    const ConvProblem p = conv_bn_problem(xs, ws, s, transpose, false);
+    const bool small = p3d_bn_small_ok((long)p.rows, p.Cout);      // (the network's stats_target: no epilogue partials)
+    *written = small ? 0 : group_parts(p.forward(nullptr, nullptr, nullptr, nullptr));
+    *cap = small ? 0 : bn_part_cap(p.rows, p.Cout);
     API_END
 }
 
@@ -978,10 +968,9 @@ int p3d_debug_igemm_groupable(const int64_t xs[5], const int64_t ws[5], const in
         if (!xs || !ws || !s) throw P3dError("null argument");
         // two sibling convs of one input, as conv() sends them (ST_B): distinct weights and outputs, shared everything else
         static float dummy[4];
-        ConvBnGroup a = conv_bn_group(xs, ws, s, 0, dummy, dummy, dummy, nullptr);
-        ConvBnGroup b = conv_bn_group(xs, ws, s, 0, dummy, dummy + 1, dummy + 2, nullptr);
-        if (a.stem) throw P3dError("the stem has no sibling");
-        std::vector<IgemmArgs> v{a.v[0], b.v[0]};
+        const ConvProblem p = conv_bn_problem(xs, ws, s, 0, false);
+        if (p.stem) throw P3dError("the stem has no sibling");
+        std::vector<IgemmArgs> v{p.forward(dummy, dummy, dummy, nullptr)[0], p.forward(dummy, dummy + 1, dummy + 2, nullptr)[0]};
         return p3d_igemm2_groupable(v.data(), 2, p3d_igemm2_plan(v[0], 1)) ? 1 : 0;
     } catch (const std::exception& e) {
         g_err = e.what();
@@ -997,41 +986,34 @@ int p3d_debug_conv_bn_stats(int device, const float* x, const int64_t xs[5], con
     if (!x || !w || !xs || !ws || !s || !moving || !y || !stats || !nparts) throw P3dError("null argument");
     if (w2 && (transpose || !y2)) throw P3dError("a sibling pair is two forward convs with two outputs");
     const int64_t nx = prod5(xs), nw = prod5(ws);
-    const ConvBnGroup shape = conv_bn_group(xs, ws, s, transpose, nullptr, nullptr, nullptr, nullptr);
-    const int C = shape.C, npair = w2 ? 2 : 1;
-    const int64_t rows = shape.rows, ny = rows * C;
+    const ConvProblem p = conv_bn_problem(xs, ws, s, transpose, bias != nullptr);
+    const int C = p.Cout, npair = w2 ? 2 : 1;
+    const int64_t rows = p.rows, ny = p.ny();
     DevBuf dx(nx, x), dw(nw, w), dw2(w2 ? nw : 1, w2), dy(ny), dy2(w2 ? ny : 1), db(C, bias);
     std::vector<float> ones((size_t)C, 1.0f);
     DevBuf gamma(C, ones.data()), beta(C), mv(2 * (int64_t)C * npair, moving), tab(4 * (int64_t)C * npair);
     ensure_zero_page();
     Ctx c;
-    DevBuf x4(shape.stem ? shape.sg.xrows * shape.sg.Wp * 4 : 1), w4(shape.stem ? (int64_t)shape.sg.KH * shape.sg.K4 * C : 1);
-    if (shape.stem) {
-        HIPCHECK(p3d_stem_pad(dx.p, x4.p, shape.sg.xrows, shape.g.I[2], shape.sg.Wp, shape.g.pad[2], c.s));
-        HIPCHECK(p3d_stem_pack_w(dw.p, w4.p, shape.sg.KH * shape.g.k[2], C, c.s));
-    }
-    ConvBnGroup r = conv_bn_group(xs, ws, s, transpose, dx.p, dw.p, dy.p, bias ? db.p : nullptr, x4.p, w4.p);
-    ConvBnGroup r2;
-    if (w2) r2 = conv_bn_group(xs, ws, s, 0, dx.p, dw2.p, dy2.p, bias ? db.p : nullptr);
+    DevBuf x4(p.sg.x4_floats), w4(p.sg.w4_floats);
+    if (p.stem) stem_pack(c, p.sg, dx.p, x4.p, dw.p, w4.p);
+    std::vector<IgemmArgs> v = p.forward(dx.p, dw.p, dy.p, bias ? db.p : nullptr, x4.p, w4.p);
     // the network's rule (stats_target): a tensor the one-launch small-tensor BatchNorm consumes gets no epilogue partials --
     // the statistics below then come from p3d_bn_stats
     const bool small = p3d_bn_small_ok((long)rows, C);
     const int cap = bn_part_cap(rows, C);
     DevBuf part((int64_t)cap * C * 2 * npair);
     int np[2] = {0, 0};
-    const P3dIgemmPlan pl = p3d_igemm2_plan(r.v[0], 1);
-    if (kernel) *kernel = r.v.size() == 1 && p3d_igemm2_tail_split(r.v[0], pl) ? "igemm2_group_kernel(tail)" : pl.name;
+    const P3dIgemmPlan pl = p3d_igemm2_plan(v[0], 1);
+    if (kernel) *kernel = v.size() == 1 && p3d_igemm2_tail_split(v[0], pl) ? "igemm2_group_kernel(tail)" : pl.name;
     if (!w2) {
         StatSink sink; sink.part = part.p; sink.cap = cap; sink.nparts = &np[0];
-        run_igemm_group(c, r.v, dy.p, C, rows, C, false, small ? nullptr : &sink, nullptr, nullptr);
+        run_igemm_group(c, v, false, small ? nullptr : &sink);
     } else {
-        // conv()'s sibling pair: sibling_prepare, then launch_siblings
-        std::vector<IgemmArgs> v{r.v[0], r2.v[0]};
+        // conv()'s sibling pair
+        v.push_back(p.forward(dx.p, dw2.p, dy2.p, bias ? db.p : nullptr)[0]);
         for (int q = 0; q < 2; ++q) {
-            IgemmArgs& a = v[q];
-            a.zeros = g_zero_page; a.accum = 0; a.statpart = nullptr; a.stat_base = 0;
             StatSink sink; sink.part = part.p + (int64_t)q * cap * C * 2; sink.cap = cap; sink.nparts = &np[q];
-            if (!small) attach_sibling_stats(a, sink);
+            sibling_prepare(v[q], small ? nullptr : &sink);
         }
         if (launch_siblings(c, v) && kernel) *kernel = "igemm2_group_kernel(siblings)";
     }
@@ -1455,28 +1437,13 @@ int p3d_op_conv3d_transpose(int device, const float* x, const int64_t xs[5], con
                             const int s[3], const float* bias, float* y) {
     API_BEGIN
     HIPCHECK(hipSetDevice(device));
-    const int k[3] = {(int)ks[0], (int)ks[1], (int)ks[2]};
-    const ConvGeo g = make_geo((int)xs[1] * s[0], (int)xs[2] * s[1], (int)xs[3] * s[2], k, s);
-    const int Cin = (int)xs[4], Cout = (int)ks[3];
-    if (ks[4] != Cin) throw P3dError("kernel Cin mismatch");
-    const int64_t ny = xs[0] * g.I[0] * g.I[1] * g.I[2] * Cout;
-    DevBuf dx(prod5(xs), x), dk(prod5(ks), kh), dy(ny), db(Cout, bias);
-    auto v = igemm_conv_input_side(g, (int)xs[0], dx.p, Cin, Cin, dy.p, Cout, Cout, dk.p, bias ? db.p : nullptr, 0, true);
+    const ConvProblem p = conv_problem(xs, ks, s, 1);
+    DevBuf dx(prod5(xs), x), dk(prod5(ks), kh), dy(p.ny()), db(p.Cout, bias);
+    auto v = p.forward(dx.p, dk.p, dy.p, bias ? db.p : nullptr);
     ensure_zero_page();
-    { Ctx c; run_igemm_group(c, v, dy.p, Cout, ny / Cout, Cout, false, nullptr); }
-    dy.get(y, ny);
+    { Ctx c; run_igemm_group(c, v, false, nullptr); }
+    dy.get(y, p.ny());
     API_END
-}
-
-static PoolArgs pool_args(const int64_t xs[5], const int k[3], const int s[3], const ConvGeo& g) {
-    PoolArgs a;
-    memset(&a, 0, sizeof(a));
-    a.N = (int)xs[0]; a.Di = (int)xs[1]; a.Hi = (int)xs[2]; a.Wi = (int)xs[3]; a.C = (int)xs[4]; a.ldx = a.C;
-    a.Do = g.O[0]; a.Ho = g.O[1]; a.Wo = g.O[2]; a.ldy = a.C;
-    a.kd = k[0]; a.kh = k[1]; a.kw = k[2]; a.sd = s[0]; a.sh = s[1]; a.sw = s[2];
-    a.pd = g.pad[0]; a.ph = g.pad[1]; a.pw = g.pad[2];
-    a.lddy = a.C; a.lddx = a.C;
-    return a;
 }
 
 int p3d_op_max_pool3d(int device, const float* x, const int64_t xs[5], const int k[3], const int s[3], float* y) {
@@ -1485,7 +1452,7 @@ int p3d_op_max_pool3d(int device, const float* x, const int64_t xs[5], const int
     const ConvGeo g = make_geo((int)xs[1], (int)xs[2], (int)xs[3], k, s);
     const int64_t ny = xs[0] * g.O[0] * g.O[1] * g.O[2] * xs[4];
     DevBuf dx(prod5(xs), x), dy(ny);
-    PoolArgs a = pool_args(xs, k, s, g);
+    PoolArgs a = pool_args(g, (int)xs[0], (int)xs[4], (int)xs[4], (int)xs[4]);
     a.x = dx.p; a.y = dy.p;
     HIPCHECK(p3d_maxpool_fwd(a, nullptr));
     dy.get(y, ny);
@@ -1500,7 +1467,7 @@ int p3d_op_max_pool3d_grad(int device, const float* x, const int64_t xs[5], cons
     const int64_t ny = xs[0] * g.O[0] * g.O[1] * g.O[2] * xs[4];
     if (xs[4] % 4) throw P3dError("max_pool3d_grad needs a channel count that is a multiple of 4");
     DevBuf dx(prod5(xs), x), dy(ny, dyh), dg(prod5(xs)), yy(ny), tab(ny / 4);
-    PoolArgs a = pool_args(xs, k, s, g);
+    PoolArgs a = pool_args(g, (int)xs[0], (int)xs[4], (int)xs[4], (int)xs[4]);
     a.x = dx.p; a.dy = dy.p; a.dx = dg.p; a.y = yy.p;
     const bool disjoint = p3d_maxpool_disjoint(a);
     if (!disjoint) a.idx = reinterpret_cast<unsigned*>(tab.p);

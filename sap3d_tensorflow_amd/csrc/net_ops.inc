@@ -28,26 +28,20 @@
             // firstconv1 (p3d.py:172) on the pipelined kernels: 4-channel, W-padded copy of the clip, kw*4 contiguous
             // floats per kernel row (elementwise.hip, "stem"); 7 taps of K = 28 instead of 49 taps of K = 3
             if (k[0] != 1 || Cin != 3 || bias) throw P3dError("stem path is for [1,kh,kw,3,C] kernels without bias");
-            const StemGeo sg = stem_geo(g, x->N);
-            const int Wp = sg.Wp, K4 = sg.K4, KH = sg.KH;
-            const int64_t xrows = sg.xrows;
-            float* x4 = dalloc<float>(xrows * Wp * 4);
-            HIPCHECK(fill_async(x4, 0, (size_t)xrows * Wp * 4 * sizeof(float), stream, "stem-padding"));      // (p3d_create synchronises the stream)
-            float* w4 = dalloc<float>((int64_t)KH * K4 * Cout);
-            float* dw4 = dalloc<float>((int64_t)KH * K4 * Cout);
-            const bool onepass = p3d_stem_wgrad_ok(k[0], k[1], k[2], Cin, Cout, s[0], s[1], s[2], g.O[2]);
-            float* spart = onepass ? dalloc<float>(p3d_stem_wgrad_part_floats()) : nullptr;
+            const StemGeo sg = stem_geo(g, x->N, Cout);
+            float* x4 = dalloc<float>(sg.x4_floats);
+            HIPCHECK(fill_async(x4, 0, (size_t)sg.x4_floats * sizeof(float), stream, "stem-padding"));      // (p3d_create synchronises the stream)
+            float* w4 = dalloc<float>(sg.w4_floats);
+            float* dw4 = dalloc<float>(sg.w4_floats);
+            float* spart = sg.part_floats ? dalloc<float>(sg.part_floats) : nullptr;
             auto link = std::make_shared<StemBnLink>();
-            link->enabled = onepass;
+            link->enabled = sg.part_floats != 0;
             y->stem_link = link;
             op.fwd = [=](const Ctx& c) {
-                launch(c, "stem_pad_kernel", 0, 28.0 * x->rows(), [&]() { return p3d_stem_pad(x->p, x4, xrows, g.I[2], Wp, g.pad[2], c.s); });
-                launch(c, "stem_pack_w_kernel", 0, 8.0 * KH * K4 * Cout, [&]() { return p3d_stem_pack_w(w->p, w4, KH * g.k[2], Cout, c.s); });
-                const IgemmArgs a = stem_forward_args(g, x->N, sg, x4, w4, y->p, y->ld, Cout, nullptr);
-                std::vector<IgemmArgs> v{a};
-                BN* sbn = bn ? stats_target(bn, y->rows(), Cout, bn_has_dropout) : nullptr;
-                StatSink sink; if (sbn) sink = bn_sink(sbn);
-                run_igemm_group(c, v, y->p, y->ld, y->rows(), Cout, false, sbn ? &sink : nullptr);
+                stem_pack(c, sg, x->p, x4, w->p, w4);
+                std::vector<IgemmArgs> v{stem_forward_args(sg, x4, w4, y->p, y->ld, nullptr)};
+                StatSink sink;
+                run_igemm_group(c, v, false, epilogue_sink(sink, bn, y->rows(), Cout, bn_has_dropout));
             };
             op.bwd = [=](const Ctx& c) {
                 const bool through_bn = link->pending;      // the BatchNorm's backward (the op before this one) left its apply pass here
@@ -55,48 +49,29 @@
                 link->pending = false;
                 on_side_stream(c, fork_ev, [=](const Ctx& sc) {
                     // greedy: the last launch of the backward pass -- the main stream is done
-                    stem_filter_gradient(sc, g, x->N, Wp, x4, y->g, y->ld, Cout, dw4, w->g, nullptr, /*greedy=*/true, spart,
-                                         through_bn ? &bnargs : nullptr);
+                    stem_filter_gradient(sc, sg, x4, y->g, y->ld, dw4, w->g, nullptr, /*greedy=*/true, spart, through_bn ? &bnargs : nullptr);
                 });
                 if (xflag) throw P3dError("the stem input carries no gradient");
             };
             ops.push_back(op);
             return y;
         }
-        // sibling convs on one input (ST_B: convS and convT both read relu(bn1(.)), p3d.py:65-72): the first one only prepares
-        // its launch, the second sends both out as ONE grouped launch (conv_igemm2.hip, igemm2_group_kernel) -- either alone
-        // leaves most CUs idle, and forking one to the side stream costs ~10 us of cross-stream latency each way
-        auto sibling_prepare = [=](const Ctx& c, IgemmArgs& a) {
-            a.zeros = g_zero_page; a.accum = 0; a.statpart = nullptr; a.stat_base = 0;
-            BN* sbn = bn ? ((c.fuse && cf.out_bn) ? bn : stats_target(bn, y->rows(), Cout, bn_has_dropout)) : nullptr;
-            if (sbn) attach_sibling_stats(a, bn_sink(sbn));
-        };
-        auto fwd_body = [=](const Ctx& c) {
+        const auto f16 = [=] { return ntap == 1 && pointwise_f16; };      // the fp16 option's rule: 1x1x1 convs, forward and input gradient
+        // sibling = 1 / 2: first / second of two convs that read the same input (ST_B: convS and convT both read relu(bn1(.)),
+        // p3d.py:65-72): the first one only prepares its launch, the second sends both out as ONE grouped launch (conv_igemm2.hip,
+        // igemm2_group_kernel) -- either alone leaves most CUs idle, and forking one to the side stream costs ~10 us of cross-stream
+        // latency each way
+        op.fwd = [=](const Ctx& c) {
             const bool fz = c.fuse && cf.at != 0;
+            if (fz) fused_prefinalize(c, cf, cf.src[0].y->rows());      // on the main stream, ahead of a fork
             // fused: the A operand is the raw output of the conv before the BatchNorm (src[0].y), normalised on the fly
             const Act* xs = fz ? cf.src[0].y : x;
-            std::vector<IgemmArgs> v{igemm_conv_forward(g, x->N, xs->p, xs->ld, Cin, y->p, y->ld, Cout, w->p, bias ? bias->p : nullptr,
-                                                        0, stem)};
-            if (fz) {
-                IgemmArgs& a = v[0];
-                a.at_mode = cf.at;
-                a.f1 = bn_fold(cf.src[0], cf.src[0].y->rows(), c);
-                if (cf.at == P3D_AT_RELU2) { a.x2 = cf.src[1].y->p; a.ldx2 = cf.src[1].y->ld; a.f2 = bn_fold(cf.src[1], cf.src[1].y->rows(), c); }
-            }
-            if (ntap == 1 && !stem && pointwise_f16) v[0].f16 = 1;
-            // a fused BatchNorm behind this conv always needs the tile partials (the one-launch small-tensor BN does not)
-            BN* sbn = bn ? ((c.fuse && cf.out_bn) ? bn : stats_target(bn, y->rows(), Cout, bn_has_dropout)) : nullptr;
-            StatSink sink; if (sbn) sink = bn_sink(sbn);
-            run_igemm_group(c, v, y->p, y->ld, y->rows(), Cout, false, sbn ? &sink : nullptr);
-        };
-        // sibling = 1 / 2: first / second of two convs that read the same input (ST_B, p3d.py:65-72)
-        hipEvent_t fork_fwd = nullptr;
-        op.fwd = [=](const Ctx& c) {
-            if (c.fuse && cf.at) fused_prefinalize(c, cf, cf.src[0].y->rows());      // on the main stream, ahead of a fork
-            (void)fork_fwd;
-            if (sibling && !c.dry && !(c.fuse && cf.at) && ntap > 0 && !stem) {
-                IgemmArgs a = igemm_conv_forward(g, x->N, x->p, x->ld, Cin, y->p, y->ld, Cout, w->p, bias ? bias->p : nullptr, 0, false);
-                sibling_prepare(c, a);
+            std::vector<IgemmArgs> v{igemm_conv_forward(g, x->N, xs->p, xs->ld, Cin, y->p, y->ld, Cout, w->p, bias ? bias->p : nullptr, 0)};
+            IgemmArgs& a = v[0];
+            StatSink sink;
+            const StatSink* stats = epilogue_sink(sink, bn, y->rows(), Cout, bn_has_dropout, c.fuse && cf.out_bn);
+            if (sibling && !c.dry && !fz && ntap > 0) {
+                sibling_prepare(a, stats);
                 if (sibling == 1) {       // first of the pair: wait for the second (a stale entry would be a third class of the next pair)
                     if (!sib_pending.empty()) throw P3dError("sibling conv " + opname + ": an earlier pair never sent its launch");
                     sib_pending.push_back(a);
@@ -104,45 +79,47 @@
                 }
                 if (sib_pending.size() != 1) throw P3dError("sibling conv " + opname + " has no first sibling waiting");
                 sib_pending.push_back(a);
-                std::vector<IgemmArgs> v;
-                v.swap(sib_pending);
-                launch_siblings(c, v);
+                std::vector<IgemmArgs> pair;
+                pair.swap(sib_pending);
+                launch_siblings(c, pair);
                 return;
             }
-            fwd_body(c);
+            if (fz) {
+                a.at_mode = cf.at;
+                a.f1 = bn_fold(cf.src[0], cf.src[0].y->rows(), c);
+                if (cf.at == P3D_AT_RELU2) { a.x2 = cf.src[1].y->p; a.ldx2 = cf.src[1].y->ld; a.f2 = bn_fold(cf.src[1], cf.src[1].y->rows(), c); }
+            }
+            if (f16()) a.f16 = 1;
+            run_igemm_group(c, v, false, stats);
         };
-        op.bwd = [=](const Ctx& c) {
-            if (!(c.fuse_bwd && cf.any())) {
-                // BatchNorm's backward as launches of its own.  After a FUSED forward the normalised input was never stored:
-                // the filter gradient reads it as relu(scale*y + shift) on its operand path (scale / shift published by the forward)
-                const bool fin = c.fuse && cf.at != 0;
-                WgradArgs wa = wgrad_conv(g, x->N, (fin ? cf.src[0].y : x)->p, (fin ? cf.src[0].y : x)->ld, Cin, y->g, y->ld, Cout, w->g,
-                                          bias ? bias->g : nullptr, stem);
-                if (fin) {
-                    wa.xt = cf.at == P3D_AT_RELU2 ? 2 : 1;
-                    wa.xs1 = cf.src[0].bn->scale; wa.xt1 = cf.src[0].bn->shift;
-                    if (wa.xt == 2) { wa.x2 = cf.src[1].y->p; wa.ldx2 = cf.src[1].y->ld; wa.xs2 = cf.src[1].bn->scale; wa.xt2 = cf.src[1].bn->shift; }
-                }
-                queue_wgrad(c, wa);
-                if (xflag) {
-                    const int accum = *xflag;
-                    auto v = igemm_conv_input_side(g, x->N, y->g, y->ld, Cout, x->g, x->ld, Cin, w->p, nullptr, accum,
-                                                   /*include_empty=*/!accum);
-                    if (ntap == 1 && !stem && pointwise_f16) for (auto& a : v) a.f16 = 1;
-                    run_igemm_group(c, v, x->g, x->ld, x->rows(), Cin, accum != 0, nullptr);
-                }
-                return;
-            }
-            // ---- fused BatchNorm: y->g holds the GATED gradient of relu(bn(y)) (written by the consumer's input-gradient
-            //      launch), BatchNorm's own backward happens on the operand paths below
-            const bool fin = cf.at != 0;
-            WgradArgs wa = wgrad_conv(g, x->N, (fin ? cf.src[0].y : x)->p, (fin ? cf.src[0].y : x)->ld, Cin, y->g, y->ld, Cout, w->g,
-                                      bias ? bias->g : nullptr, stem);
+        // The filter-gradient arguments.  fin: the normalised input of a FUSED forward was never stored; the filter gradient reads
+        // it as relu(scale*y + shift) on its operand path (scale / shift published by the forward)
+        const auto wgrad_args = [=](bool fin) {
+            const Act* xs = fin ? cf.src[0].y : x;
+            WgradArgs wa = wgrad_conv(g, x->N, xs->p, xs->ld, Cin, y->g, y->ld, Cout, w->g, bias ? bias->g : nullptr);
             if (fin) {
                 wa.xt = cf.at == P3D_AT_RELU2 ? 2 : 1;
                 wa.xs1 = cf.src[0].bn->scale; wa.xt1 = cf.src[0].bn->shift;
                 if (wa.xt == 2) { wa.x2 = cf.src[1].y->p; wa.ldx2 = cf.src[1].y->ld; wa.xs2 = cf.src[1].bn->scale; wa.xt2 = cf.src[1].bn->shift; }
             }
+            return wa;
+        };
+        op.bwd = [=](const Ctx& c) {
+            if (!(c.fuse_bwd && cf.any())) {
+                // BatchNorm's backward as launches of its own (possibly after a fused forward)
+                queue_wgrad(c, wgrad_args(c.fuse && cf.at != 0));
+                if (xflag) {
+                    const int accum = *xflag;
+                    auto v = igemm_conv_input_side(g, x->N, y->g, y->ld, Cout, x->g, x->ld, Cin, w->p, nullptr, accum,
+                                                   /*include_empty=*/!accum);
+                    if (f16()) for (auto& a : v) a.f16 = 1;
+                    run_igemm_group(c, v, accum != 0, nullptr);
+                }
+                return;
+            }
+            // ---- fused BatchNorm: y->g holds the GATED gradient of relu(bn(y)) (written by the consumer's input-gradient
+            //      launch), BatchNorm's own backward happens on the operand paths below
+            WgradArgs wa = wgrad_args(cf.at != 0);
             if (cf.out_bn) { wa.dyt = 1; wa.dy2 = y->p; wa.ldy2 = y->ld; wa.dcoef = cf.out_bn->coef; }
             if (!xflag) throw P3dError("a conv with a fused BatchNorm needs an input gradient launch (it publishes the coefficients)");
             if (cf.out_bn && !c.dry) {
@@ -163,7 +140,7 @@
             auto v = igemm_conv_input_side(g, x->N, y->g, y->ld, Cout, py, pld, Cin, w->p, nullptr, accum, /*include_empty=*/!accum);
             bool first = true;
             for (auto& a : v) {
-                if (ntap == 1 && !stem && pointwise_f16) a.f16 = 1;
+                if (f16()) a.f16 = 1;
                 if (cf.out_bn) {
                     a.at_mode = P3D_AT_GRAD; a.x2 = y->p; a.ldx2 = y->ld;
                     a.gf = bn_grad_fold(cf.out_bn, y->rows(), first);
@@ -183,7 +160,7 @@
                 }
                 first = false;
             }
-            run_igemm_group(c, v, py, pld, x->rows(), Cin, accum != 0, nullptr);
+            run_igemm_group(c, v, accum != 0, nullptr);
             queue_wgrad(c, wa);      // after the input gradient: its block 0 published the coefficients this one reads
         };
         ops.push_back(op);
@@ -211,9 +188,8 @@
         op.fwd = [=](const Ctx& c) {
             auto v = igemm_conv_input_side(g, x->N, x->p, x->ld, Cin, y->p, y->ld, Cout, kern->p, bias ? bias->p : nullptr,
                                            0, true);
-            BN* sbn = bn ? stats_target(bn, y->rows(), Cout, bn_has_dropout) : nullptr;
-            StatSink sink; if (sbn) sink = bn_sink(sbn);
-            run_igemm_group(c, v, y->p, y->ld, y->rows(), Cout, false, sbn ? &sink : nullptr, class_fork, class_join);
+            StatSink sink;
+            run_igemm_group(c, v, false, epilogue_sink(sink, bn, y->rows(), Cout, bn_has_dropout), class_fork, class_join);
         };
         op.bwd = [=](const Ctx& c) {
             // dK[tap][co][ci] = sum dy_big[o][co] * x[i][ci]  (conv wgrad with the roles of x and dy swapped)
@@ -224,7 +200,7 @@
                 });
             if (xflag) {
                 std::vector<IgemmArgs> v{igemm_conv_forward(g, x->N, y->g, y->ld, Cout, x->g, x->ld, Cin, kern->p, nullptr, *xflag)};
-                run_igemm_group(c, v, x->g, x->ld, x->rows(), Cin, *xflag != 0, nullptr);
+                run_igemm_group(c, v, *xflag != 0, nullptr);
             }
         };
         ops.push_back(op);
@@ -363,15 +339,9 @@
         op.bytes = 4.0 * (x->rows() + out->rows()) * x->C;
         op.bbytes = 4.0 * (2.0 * x->rows() + 2.0 * out->rows()) * x->C;
         auto mk = [=]() {
-            PoolArgs a;
-            memset(&a, 0, sizeof(a));
-            a.x = x->p; a.N = x->N; a.Di = x->D; a.Hi = x->H; a.Wi = x->W; a.C = x->C; a.ldx = x->ld;
-            a.y = out->p; a.Do = g.O[0]; a.Ho = g.O[1]; a.Wo = g.O[2]; a.ldy = out->ld;
             // NB: k / s are pointers into the builder's stack; only the by-value geometry is safe here
-            a.kd = g.k[0]; a.kh = g.k[1]; a.kw = g.k[2]; a.sd = g.s[0]; a.sh = g.s[1]; a.sw = g.s[2];
-            a.pd = g.pad[0]; a.ph = g.pad[1]; a.pw = g.pad[2];
-            a.dy = out->g; a.lddy = out->ld; a.dx = x->g; a.lddx = x->ld;
-            a.idx = idx;
+            PoolArgs a = pool_args(g, x->N, x->C, x->ld, out->ld);
+            a.x = x->p; a.y = out->p; a.dy = out->g; a.dx = x->g; a.idx = idx;
             return a;
         };
         const double pool_bytes = op.bytes;
