@@ -408,6 +408,40 @@ int p3d_op_max_pool3d_grad(int device, const float* x, const int64_t xshape[5], 
 /* BiasAddGrad of tf.nn.bias_add (the bias of tf.layers.conv3d / conv3d_transpose, p3d.py:147-150): dbias[c] = sum over
  * rows of dy[row][c]; fixed summation order, bit-identical run to run. */
 int p3d_op_bias_add_grad(int device, const float* dy, int64_t rows, int channels, float* dbias);
+/* Test hooks: the conv launches in the forms the train step uses -- operands that are channel slices of wider rows, results added to
+ * what the output holds, several filter gradients in one launch, the fp16 option -- built from the builders of the graph's conv ops.
+ * Every OUTPUT buffer is in / out at its full extent: the caller decides what the kernels find there, and gets back every float.
+ * A slice is `channels` floats at column `off` of rows of `ld` floats (all multiples of 4, off + channels <= ld).
+ *
+ * p3d_debug_conv_launch: kind 0 = tf.nn.conv3d forward (in = x, out = y), 1 = its input gradient (in = dy, out = dx; xshape is
+ * the shape of x), 2 = tf.layers.conv3d_transpose forward (shapes as p3d_op_conv3d_transpose).  in [rows][ld_in], out
+ * [rows][ld_out].  accum = 1: out += result (kinds 0, 1); the residue classes of a strided conv's input gradient that no tap reaches
+ * are then not launched, and written (zeros; kind 2: the bias) otherwise.  f16 = 1: the fp16 option of p3d_set_pointwise_fp16,
+ * 1x1x1 convs of kinds 0 and 1 only.  bias: kinds 0 and 2, or null.  kernels: the names the launches went out under, joined
+ * with ';' ("(tail)" appended where a single launch sends its last round K-sliced); splits (or null): the smallest and the largest
+ * K-slice count of the launches' plans, which the names do not carry.  The stem shape is refused.
+ *
+ * p3d_debug_wgrad_group: n (1..6) filter gradients as ONE launch, as the step's queue sends them.  Per problem i: x[i] [rows][ldx[i]],
+ * xshape xs[5 i ..], dy[i] [rows][lddy[i]], filter shape ws[5 i ..], strides s[3 i ..]; transpose[i] = 1: the problem is a
+ * transposed conv's (shapes as p3d_op_conv3d_transpose, x its input, dy the gradient of its output).  dw[i] (in / out) and dbias[i]
+ * (in / out, or null) are ADDED to.  polite / greedy: the residency flags of the launch.  kernel: its name; cuts[i]: the cuts of
+ * problem i along the positions (0: the problem has no positions or taps and is dropped); info = slab stride (the largest cut
+ * count), tile rows, tile columns.
+ *
+ * p3d_debug_max_pool3d(_grad), p3d_debug_bias_add_grad: p3d_op_max_pool3d(_grad) / p3d_op_bias_add_grad on slices; y, dx and
+ * dbias in / out; accumulate = 1: dx += the gradient; *kernel = the backward kernel that ran. */
+int p3d_debug_conv_launch(int device, int kind, const float* in, int ld_in, int off_in, const int64_t xshape[5], const float* w,
+                          const int64_t wshape[5], const int s[3], const float* bias, int accum, int f16, float* out, int ld_out,
+                          int off_out, char* kernels, int kernels_cap, int* splits);
+int p3d_debug_wgrad_group(int device, int n, const float* const* x, const int* ldx, const int* offx, const int64_t* xs,
+                          const float* const* dy, const int* lddy, const int* offdy, const int64_t* ws, const int* s, const int* transpose,
+                          float* const* dw, float* const* dbias, int polite, int greedy, char* kernel, int kernel_cap, int* cuts,
+                          int* info);
+int p3d_debug_max_pool3d(int device, const float* x, int ldx, int offx, const int64_t xshape[5], const int ksize[3], const int s[3],
+                         float* y, int ldy, int offy);
+int p3d_debug_max_pool3d_grad(int device, const float* x, int ldx, int offx, const int64_t xshape[5], const int ksize[3], const int s[3],
+                              const float* dy, int ldy, int offy, int accumulate, float* dx, const char** kernel);
+int p3d_debug_bias_add_grad(int device, const float* dy, int64_t rows, int channels, int ld, int off, float* dbias);
 /* The core of attention(), utils/network.py:183-185, on flattened operands:
  *     s = tf.matmul(hw_flatten(g), hw_flatten(f), transpose_b=True); beta = tf.nn.softmax(s); o = tf.matmul(beta, hw_flatten(h))
  * g [batch][n_g][ch/8], f [batch][n_f][ch/8], h [batch][n_f][ch] -> o [batch][n_g][ch], on the kernels that keep the score

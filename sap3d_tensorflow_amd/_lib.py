@@ -128,6 +128,14 @@ SIGNATURES = {
     "p3d_op_max_pool3d": (C.c_int, [C.c_int, _fp, _i64p, _ip, _ip, _fp]),
     "p3d_op_max_pool3d_grad": (C.c_int, [C.c_int, _fp, _i64p, _ip, _ip, _fp, _fp]),
     "p3d_op_bias_add_grad": (C.c_int, [C.c_int, _fp, C.c_int64, C.c_int, _fp]),
+    "p3d_debug_conv_launch": (C.c_int, [C.c_int, C.c_int, _fp, C.c_int, C.c_int, _i64p, _fp, _i64p, _ip, _fp, C.c_int, C.c_int, _fp,
+                                        C.c_int, C.c_int, C.c_char_p, C.c_int, _ip]),
+    "p3d_debug_wgrad_group": (C.c_int, [C.c_int, C.c_int, C.POINTER(_fp), _ip, _ip, _i64p, C.POINTER(_fp), _ip, _ip, _i64p, _ip, _ip,
+                                        C.POINTER(_fp), C.POINTER(_fp), C.c_int, C.c_int, C.c_char_p, C.c_int, _ip, _ip]),
+    "p3d_debug_max_pool3d": (C.c_int, [C.c_int, _fp, C.c_int, C.c_int, _i64p, _ip, _ip, _fp, C.c_int, C.c_int]),
+    "p3d_debug_max_pool3d_grad": (C.c_int, [C.c_int, _fp, C.c_int, C.c_int, _i64p, _ip, _ip, _fp, C.c_int, C.c_int, C.c_int, _fp,
+                                            C.POINTER(C.c_char_p)]),
+    "p3d_debug_bias_add_grad": (C.c_int, [C.c_int, _fp, C.c_int64, C.c_int, C.c_int, C.c_int, _fp]),
     "p3d_op_attention_core": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     "p3d_metric_cc": (C.c_int, [C.c_int, _fp, _fp, C.c_int, C.c_int, _dp]),
     "p3d_metric_sim": (C.c_int, [C.c_int, _fp, _fp, C.c_int, C.c_int, _dp]),

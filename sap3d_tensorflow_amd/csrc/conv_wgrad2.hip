@@ -797,6 +797,14 @@ bool group_takes_rect(const std::vector<const WgradArgs*>& live) {
     return all;
 }
 
+// The problems of a group that launch anything (positions and taps), in order.
+std::vector<const WgradArgs*> live_problems(const WgradArgs* probs, int n) {
+    std::vector<const WgradArgs*> live;
+    for (int i = 0; i < n; ++i)
+        if ((long long)probs[i].N * probs[i].Gd * probs[i].Gh * probs[i].Gw > 0 && probs[i].ntaps > 0) live.push_back(&probs[i]);
+    return live;
+}
+
 }  // namespace
 
 const char* p3d_wgrad2_variant(const WgradArgs& a) {
@@ -806,9 +814,7 @@ const char* p3d_wgrad2_variant(const WgradArgs& a) {
 }
 const char* p3d_wgrad2_group_variant(const WgradArgs* probs, int n, bool fused) {
     if (n == 1) return p3d_wgrad2_variant(probs[0]);
-    std::vector<const WgradArgs*> live;
-    for (int i = 0; i < n; ++i)
-        if ((long long)probs[i].N * probs[i].Gd * probs[i].Gh * probs[i].Gw > 0 && probs[i].ntaps > 0) live.push_back(&probs[i]);
+    const std::vector<const WgradArgs*> live = live_problems(probs, n);
     if (group_takes_rect(live)) return fused ? "wgrad2_kernel<64,128,fused>(grouped)" : "wgrad2_kernel<64,128>(grouped)";
     return fused ? "wgrad2_kernel<64,64,fused>(grouped)" : "wgrad2_kernel<64,64>(grouped)";
 }
@@ -817,24 +823,11 @@ void p3d_wgrad2_force_tile(int tm, int tn) {
     g_force_tm = ok ? tm : 0; g_force_tn = ok ? tn : 0;
 }
 
-// One launch for up to P3D_WGRAD_GROUP problems.  A single problem may take the 128x128 tile; groups use 64x64 (64x128: below).
-hipError_t p3d_launch_wgrad2_group(const WgradArgs* probs, int n, hipStream_t s) {
-    std::vector<const WgradArgs*> live;
-    for (int i = 0; i < n; ++i) {
-        const WgradArgs& a = probs[i];
-        const long long M = (long long)a.N * a.Gd * a.Gh * a.Gw;
-        if (M <= 0 || a.ntaps <= 0) continue;
-        if (!wgrad_ok(a)) return hipErrorInvalidValue;
-        live.push_back(&a);
-    }
-    if (live.empty()) return hipSuccess;
-    if ((int)live.size() > P3D_WGRAD_GROUP) return hipErrorInvalidValue;
-    WGroup g;
-    memset(&g, 0, sizeof(g));
-    g.nprob = (int)live.size();
-    g.zeros = live[0]->zeros;
-    bool fused = false;
-    for (auto* a : live) if (a->xt || a->dyt) fused = true;
+namespace {
+// Tile and cuts per live problem of one grouped launch.  A single problem may take the 128x128 tile; groups use 64x64 (64x128: above).
+struct GroupPlan { int tm, tn; int cuts[P3D_WGRAD_GROUP]; int kstride; };      // kstride: slabs per tile slot, the largest cut count
+GroupPlan group_plan(const std::vector<const WgradArgs*>& live) {
+    GroupPlan gp;
     WPlan solo = live.size() == 1 ? plan(*live[0]) : WPlan{64, 64, 0, 1, 0.0};
     if (live.size() > 1 && group_takes_rect(live)) solo.tn = 128;
     // tuning build: P3D_TUNE_WGRAD_GROUP_TILE = 1 / 2 / 3 puts the groups over few positions (the bottlenecks of stages 2-3) on 64x128 /
@@ -846,11 +839,11 @@ hipError_t p3d_launch_wgrad2_group(const WgradArgs* probs, int n, hipStream_t s)
         for (auto* a : live) ok = ok && !a->pair && a->K % gtm == 0 && a->Nc % gtn == 0 && (long long)a->N * a->Gd * a->Gh * a->Gw <= wtune().polite_rows;
         if (ok) { solo.tm = gtm; solo.tn = gtn; }
     }
-    const int tm = solo.tm, tn = solo.tn;
+    gp.tm = solo.tm; gp.tn = solo.tn;
     long long tiles64_all = 0;
     for (auto* a : live) tiles64_all += tiles_of(*a, 64, 64);
     // cuts per problem (the model of plan(): the launch's tiles on 512-768 slots, blocks of steps / cuts + overhead)
-    int cuts[P3D_WGRAD_GROUP];
+    int* cuts = gp.cuts;
     long long steps_of[P3D_WGRAD_GROUP], shortest = 1ll << 60;
     for (size_t q = 0; q < live.size(); ++q) {
         const WgradArgs& a = *live[q];
@@ -870,8 +863,46 @@ hipError_t p3d_launch_wgrad2_group(const WgradArgs* probs, int n, hipStream_t s)
             const long long cap = std::max<long long>(1, std::min<long long>(steps_of[q] / 4, 64));
             cuts[q] = (int)std::max<long long>(cuts[q], std::min(cap, (steps_of[q] + shortest - 1) / shortest));
         }
+    gp.kstride = 1;
+    for (size_t q = 0; q < live.size(); ++q) gp.kstride = std::max(gp.kstride, cuts[q]);
+    return gp;
+}
+}  // namespace
+
+// Test hook: what p3d_launch_wgrad2_group would make of these problems -- cuts[i] of problem i (0: dropped, no positions or
+// taps), the slab stride between tile slots (the largest cut count) and the tile.  Host only.
+int p3d_wgrad2_group_cuts(const WgradArgs* probs, int n, int* cuts, int* kstride, int* tm, int* tn) {
+    for (int i = 0; i < n; ++i) cuts[i] = 0;
+    *kstride = 1; *tm = *tn = 0;
+    const std::vector<const WgradArgs*> live = live_problems(probs, n);
+    if (live.empty()) return 0;
+    if ((int)live.size() > P3D_WGRAD_GROUP) return -1;
+    for (auto* a : live) if (!wgrad_ok(*a)) return -1;
+    const GroupPlan gp = group_plan(live);
+    for (size_t q = 0; q < live.size(); ++q) cuts[live[q] - probs] = gp.cuts[q];
+    *kstride = gp.kstride;
+    *tm = gp.tm; *tn = gp.tn;
+    return (int)live.size();
+}
+
+// One launch for up to P3D_WGRAD_GROUP problems.
+hipError_t p3d_launch_wgrad2_group(const WgradArgs* probs, int n, hipStream_t s) {
+    const std::vector<const WgradArgs*> live = live_problems(probs, n);
+    for (auto* a : live) if (!wgrad_ok(*a)) return hipErrorInvalidValue;
+    if (live.empty()) return hipSuccess;
+    if ((int)live.size() > P3D_WGRAD_GROUP) return hipErrorInvalidValue;
+    WGroup g;
+    memset(&g, 0, sizeof(g));
+    g.nprob = (int)live.size();
+    g.zeros = live[0]->zeros;
+    bool fused = false;
+    for (auto* a : live) if (a->xt || a->dyt) fused = true;
+    const GroupPlan gp = group_plan(live);
+    const int tm = gp.tm, tn = gp.tn;
+    const int* cuts = gp.cuts;
     long long blocks = 0;
-    int tile0 = 0, kstride = 1;
+    int tile0 = 0;
+    const int kstride = gp.kstride;
     for (size_t q = 0; q < live.size(); ++q) {
         const WgradArgs& a = *live[q];
         WProb& p = g.p[q];
@@ -882,7 +913,6 @@ hipError_t p3d_launch_wgrad2_group(const WgradArgs* probs, int n, hipStream_t s)
         p.tile0 = tile0;
         blocks += tiles * p.ksplit;
         tile0 += (int)tiles;
-        kstride = std::max(kstride, p.ksplit);
     }
     g.kstride = kstride;       // slab of (slot, cut) = slot * kstride + cut: disjoint whatever each problem's cut count
     static const bool trace = p3d_tune_env("P3D_TUNE_WGRAD_TRACE") != nullptr;      // tuning build: what a grouped launch is made of

@@ -619,14 +619,30 @@ void on_side_stream(const Ctx& c, hipEvent_t ev, F&& f) {
     f(sc);
 }
 
-void launch_wgrad(const Ctx& c, const WgradArgs& a0) {
-    WgradArgs a = a0;
+void wgrad_work(const WgradArgs& a, double& flops, double& bytes) {
     const double M = (double)a.N * a.Gd * a.Gh * a.Gw;
     const double side = (double)a.N * a.Di * a.Hi * a.Wi;
-    const double fl = 2.0 * M * a.ntaps * (double)a.K * a.Nc;
-    const double by = 4.0 * (std::min(M * a.ntaps, side) * a.K + M * a.Nc + (double)a.ntaps * a.K * a.Nc);
+    flops = 2.0 * M * a.ntaps * (double)a.K * a.Nc;
+    bytes = 4.0 * (std::min(M * a.ntaps, side) * a.K + M * a.Nc + (double)a.ntaps * a.K * a.Nc);
+}
+
+void launch_wgrad(const Ctx& c, const WgradArgs& a0) {
+    WgradArgs a = a0;
+    double fl, by;
+    wgrad_work(a, fl, by);
     a.zeros = g_zero_page;
     launch(c, p3d_wgrad2_variant(a), fl, by, [&]() { return p3d_launch_wgrad2(a, c.s); });
+}
+
+// One grouped filter-gradient launch of up to P3D_WGRAD_GROUP problems (conv_wgrad2.hip; flush_wgrads, and the test hook
+// p3d_debug_wgrad_group): the label it goes out under, and the launch on c.s with the summed work `fl` / `by` of its members.
+const char* wgrad_group_name(const std::vector<WgradArgs>& probs) {
+    bool any_fused = false;
+    for (auto& pr : probs) any_fused |= pr.xt != 0 || pr.dyt != 0;
+    return p3d_wgrad2_group_variant(probs.data(), (int)probs.size(), any_fused);
+}
+void launch_wgrad_group(const Ctx& c, const std::vector<WgradArgs>& probs, const char* name, double fl, double by) {
+    launch(c, name, fl, by, [&]() { return p3d_launch_wgrad2_group(probs.data(), (int)probs.size(), c.s); });
 }
 
 struct Op {
@@ -1113,12 +1129,9 @@ struct p3d_handle {
         if (c.dry) return;
         WgradArgs a = a0;
         a.zeros = g_zero_page;
-        const double M = (double)a.N * a.Gd * a.Gh * a.Gw;
-        const double side = (double)a.N * a.Di * a.Hi * a.Wi;
         PendingWgrad pw;
         pw.a = a; pw.op = c.prof ? c.prof->cur_op : std::string();
-        pw.flops = 2.0 * M * a.ntaps * (double)a.K * a.Nc;
-        pw.bytes = 4.0 * (std::min(M * a.ntaps, side) * a.K + M * a.Nc + (double)a.ntaps * a.K * a.Nc);
+        wgrad_work(a, pw.flops, pw.bytes);
         static const bool no_group = p3d_tune_env("P3D_NO_WGRAD_GROUP") != nullptr;
         static const int64_t flush_tiles = p3d_tune_env("P3D_WGRAD_FLUSH_TILES") ? atol(p3d_tune_env("P3D_WGRAD_FLUSH_TILES")) : 512;   // tuning: 256 -> 17.25 ms / step, 512 -> 17.0, 1024 with groups of 12 -> 17.1
         const bool alone = no_group || wgrad_tiles64(a) >= 256;      // fills the chip by itself (and may take 128x128 tiles)
@@ -1140,15 +1153,13 @@ struct p3d_handle {
         std::vector<WgradArgs> probs;
         double fl = 0, by = 0;
         for (auto& q : wq) { probs.push_back(q.a); fl += q.flops; by += q.bytes; }
-        bool any_fused = false;
-        for (auto& pr : probs) any_fused |= pr.xt != 0 || pr.dyt != 0;
-        const char* name = p3d_wgrad2_group_variant(probs.data(), (int)probs.size(), any_fused);
+        const char* name = wgrad_group_name(probs);
         if (c.defer) {            // parked: it will run beside the encoder's chain of small launches -- low residency (conv_wgrad2.hip)
             for (auto& pr : probs) pr.polite = 1;
             parked_flops += fl;
         }
         on_side_stream(c, ev, [=](const Ctx& sc) {          // by value: the job may be parked (Ctx::defer)
-            launch(sc, name, fl, by, [&]() { return p3d_launch_wgrad2_group(probs.data(), (int)probs.size(), sc.s); });
+            launch_wgrad_group(sc, probs, name, fl, by);
         });
         wq.clear();
     }

@@ -767,19 +767,33 @@ bool is_stem_shape(const int64_t xs[5], const int64_t ws[5]) { return xs[4] % 4 
 // of the conv's output and its forward launches.  transpose: xs is the input of tf.layers.conv3d_transpose and ws its kernel
 // [kd,kh,kw,Cout,Cin].  The stem ([1,kh,kw,3,C]) runs on its packed form `sg` and reads the packed copies x4 / w4 (stem_pack).
 struct ConvProblem {
-    ConvGeo g; int N = 0, Cin = 0, Cout = 0; int64_t rows = 0; bool transpose = false, stem = false; StemGeo sg{};
+    ConvGeo g; int N = 0, Cin = 0, Cout = 0; int64_t rows = 0, rows_in = 0; bool transpose = false, stem = false; StemGeo sg{};
     int64_t ny() const { return rows * Cout; }
+    // ldx / ldy: floats per row of x and y where they are channel slices of wider rows (0: dense)
     std::vector<IgemmArgs> forward(const float* x, const float* w, float* y, const float* bias, const float* x4 = nullptr,
-                                   const float* w4 = nullptr) const {
-        if (transpose) return igemm_conv_input_side(g, N, x, Cin, Cin, y, Cout, Cout, w, bias, 0, true);
+                                   const float* w4 = nullptr, int ldx = 0, int ldy = 0, int accum = 0) const {
+        if (!ldx) ldx = Cin;
+        if (!ldy) ldy = Cout;
+        if (transpose) return igemm_conv_input_side(g, N, x, ldx, Cin, y, ldy, Cout, w, bias, 0, true);
         if (stem) return {stem_forward_args(sg, x4, w4, y, Cout, bias)};
-        return {igemm_conv_forward(g, N, x, Cin, Cin, y, Cout, Cout, w, bias, 0)};
+        return {igemm_conv_forward(g, N, x, ldx, Cin, y, ldy, Cout, w, bias, accum)};
+    }
+    // the gradient of the conv's input from the gradient of its output, as conv()'s backward sends it: residue classes without
+    // a tap are written (zeros) only when nothing is accumulated
+    std::vector<IgemmArgs> input_gradient(const float* dy, const float* w, float* dx, int lddy = 0, int lddx = 0, int accum = 0) const {
+        return igemm_conv_input_side(g, N, dy, lddy ? lddy : Cout, Cout, dx, lddx ? lddx : Cin, Cin, w, nullptr, accum, /*include_empty=*/!accum);
+    }
+    // the filter gradient as conv() / deconv() queue it (transpose: x is the transposed conv's input, dy the gradient of its output)
+    WgradArgs filter_gradient(const float* x, int ldx, const float* dy, int lddy, float* dw, float* dbias) const {
+        if (transpose) return wgrad_conv(g, N, dy, lddy, Cout, x, ldx, Cin, dw, nullptr);
+        return wgrad_conv(g, N, x, ldx, Cin, dy, lddy, Cout, dw, dbias);
     }
 };
 ConvProblem conv_problem(const int64_t xs[5], const int64_t ws[5], const int s[3], int transpose) {
     ConvProblem r;
     const int k[3] = {(int)ws[0], (int)ws[1], (int)ws[2]};
     r.N = (int)xs[0]; r.Cin = (int)xs[4]; r.transpose = transpose != 0;
+    r.rows_in = xs[0] * xs[1] * xs[2] * xs[3];
     if (transpose) {
         r.Cout = (int)ws[3];
         if (ws[4] != r.Cin) throw P3dError("kernel Cin mismatch");
@@ -868,7 +882,7 @@ int p3d_op_conv3d_backprop_input(int device, const float* dyh, const float* w, c
     HIPCHECK(hipSetDevice(device));
     const ConvProblem p = conv_problem(xs, ws, s, 0);
     DevBuf dy(p.ny(), dyh), dw(prod5(ws), w), dx(prod5(xs));
-    auto v = igemm_conv_input_side(p.g, p.N, dy.p, p.Cout, p.Cout, dx.p, p.Cin, p.Cin, dw.p, nullptr, 0, true);
+    auto v = p.input_gradient(dy.p, dw.p, dx.p);
     ensure_zero_page();
     { Ctx c; run_igemm_group(c, v, false, nullptr); }
     dx.get(dxh, prod5(xs));
@@ -895,7 +909,7 @@ int p3d_op_conv3d_backprop_filter(int device, const float* x, const int64_t xs[5
         stem_filter_gradient(c, p.sg, x4.p, dy.p, Cout, dw4.p, dw.p, dbh ? db.p : nullptr, false);
         HIPCHECK(hipDeviceSynchronize());
     } else {
-        launch_wgrad(c, wgrad_conv(p.g, p.N, dx.p, Cin, Cin, dy.p, Cout, Cout, dw.p, dbh ? db.p : nullptr));
+        launch_wgrad(c, p.filter_gradient(dx.p, Cin, dy.p, Cout, dw.p, dbh ? db.p : nullptr));
     }
     dw.get(dwh, prod5(ws));
     if (dbh) db.get(dbh, Cout);
@@ -1486,6 +1500,180 @@ int p3d_op_bias_add_grad(int device, const float* dyh, int64_t rows, int channel
     HIPCHECK(hipSetDevice(device));
     DevBuf dy(rows * channels, dyh), db(channels);
     if (rows > 0) HIPCHECK(p3d_colsum(dy.p, channels, (long)rows, channels, db.p, nullptr));
+    db.get(dbias, channels);
+    API_END
+}
+
+// ---- launch forms of the train step (test hooks, include/p3d_hip.h) -------------------------------------------------------------
+namespace {
+// a channel slice of `C` floats at column `off` of rows of `ld` floats, as the kernels take it (float4 accesses)
+void check_slice(const char* what, int ld, int off, int C) {
+    if (C < 4 || (C & 3) || (ld & 3) || (off & 3) || off < 0 || ld < off + C)
+        throw P3dError(std::string(what) + ": channels, row length and channel offset are multiples of 4 with offset + channels <= row length");
+}
+// the kernel names launch() was given while `f` ran, joined with ';'
+void traced_kernels(const std::function<void()>& f, std::string& out) {
+    SchedTrace tr;
+    SchedTrace* const before = g_trace;
+    g_trace = &tr;
+    try { f(); } catch (...) { g_trace = before; throw; }
+    g_trace = before;
+    out.clear();
+    for (const std::string& l : tr.lines) {
+        if (l.compare(0, 2, "L ")) continue;
+        const size_t sp = l.find(' ', 2);
+        out += (out.empty() ? "" : ";") + l.substr(sp + 1);
+    }
+}
+void put_string(const std::string& v, char* out, int cap) {
+    if (!out || cap < 1) return;
+    if ((int)v.size() >= cap) throw P3dError("kernel name buffer too small");
+    memcpy(out, v.c_str(), v.size() + 1);
+}
+}  // namespace
+
+int p3d_debug_conv_launch(int device, int kind, const float* in, int ld_in, int off_in, const int64_t xs[5], const float* w,
+                          const int64_t ws[5], const int s[3], const float* bias, int accum, int f16, float* out, int ld_out, int off_out,
+                          char* kernels, int kernels_cap, int* splits) {
+    API_BEGIN
+    HIPCHECK(hipSetDevice(device));
+    if (!in || !xs || !w || !ws || !s || !out) throw P3dError("null argument");
+    if (kind < 0 || kind > 2) throw P3dError("conv_launch: kind is 0 (forward), 1 (input gradient) or 2 (transposed forward)");
+    const ConvProblem p = conv_problem(xs, ws, s, kind == 2);
+    if (p.stem) throw P3dError("conv_launch: the stem shape has its own entry points");
+    if (kind != 2 && ws[3] != p.Cin) throw P3dError("filter Cin mismatch");
+    if (kind == 2 && accum) throw P3dError("conv_launch: a transposed conv's forward never accumulates");
+    if (kind == 1 && bias) throw P3dError("conv_launch: an input gradient has no bias");
+    const int ntap = (int)(ws[0] * ws[1] * ws[2]);
+    if (f16 && (ntap != 1 || kind == 2)) throw P3dError("conv_launch: the fp16 option is for 1x1x1 convs, forward and input gradient");
+    // gathered side / output side: (rows, channels)
+    const int64_t rin = kind == 1 ? p.rows : p.rows_in, rout = kind == 1 ? p.rows_in : p.rows;
+    const int cin = kind == 1 ? p.Cout : p.Cin, cout = kind == 1 ? p.Cin : p.Cout;
+    check_slice("conv_launch (gathered side)", ld_in, off_in, cin);
+    check_slice("conv_launch (output side)", ld_out, off_out, cout);
+    DevBuf din(rin * ld_in, in), dw(prod5(ws), w), dout(rout * ld_out, out), db(cout, bias);
+    ensure_zero_page();
+    const float* bp = bias ? db.p : nullptr;
+    std::vector<IgemmArgs> v = kind == 1 ? p.input_gradient(din.p + off_in, dw.p, dout.p + off_out, ld_in, ld_out, accum ? 1 : 0)
+                                         : p.forward(din.p + off_in, dw.p, dout.p + off_out, bp, nullptr, nullptr, ld_in, ld_out, accum ? 1 : 0);
+    if (f16) for (auto& a : v) a.f16 = 1;      // (conv(): set on the built launches)
+    Ctx c;
+    std::string names;
+    traced_kernels([&]() { run_igemm_group(c, v, accum != 0, nullptr); }, names);
+    // a single launch whose last round goes out K-sliced keeps its tile's name in the step's tables; say so here
+    if (v.size() == 1 && p3d_igemm2_tail_split(v[0], p3d_igemm2_plan(v[0], 1))) names += "(tail)";
+    put_string(names, kernels, kernels_cap);
+    if (splits) {          // K-slices of the launches' plans (the names do not carry them): the smallest and the largest
+        splits[0] = 1 << 30; splits[1] = 0;
+        for (const IgemmArgs& a : v) {
+            const P3dIgemmPlan pl = p3d_igemm2_plan(a, 1);
+            const int sp = pl.stream_blocks > 0 || pl.splits < 1 ? 1 : pl.splits;
+            splits[0] = std::min(splits[0], sp); splits[1] = std::max(splits[1], sp);
+        }
+        if (v.empty()) splits[0] = splits[1] = 0;
+    }
+    dout.get(out, rout * ld_out);
+    API_END
+}
+
+int p3d_debug_wgrad_group(int device, int n, const float* const* x, const int* ldx, const int* offx, const int64_t* xs,
+                          const float* const* dy, const int* lddy, const int* offdy, const int64_t* ws, const int* s, const int* transpose,
+                          float* const* dw, float* const* dbias, int polite, int greedy, char* kernel, int kernel_cap, int* cuts,
+                          int* info) {
+    API_BEGIN
+    HIPCHECK(hipSetDevice(device));
+    if (!x || !ldx || !offx || !xs || !dy || !lddy || !offdy || !ws || !s || !transpose || !dw || !dbias || !cuts || !info)
+        throw P3dError("null argument");
+    if (n < 1 || n > P3D_WGRAD_GROUP) throw P3dError("wgrad_group: 1 to " + std::to_string(P3D_WGRAD_GROUP) + " problems");
+    struct Bufs { std::unique_ptr<DevBuf> x, dy, dw, db; int64_t nw; int nb; };
+    std::vector<Bufs> bufs((size_t)n);
+    std::vector<WgradArgs> probs;
+    ensure_zero_page();
+    double fl = 0, by = 0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t* xsi = xs + 5 * i; const int64_t* wsi = ws + 5 * i;
+        const ConvProblem p = conv_problem(xsi, wsi, s + 3 * i, transpose[i]);
+        if (p.stem) throw P3dError("wgrad_group: the stem shape has its own entry points");
+        if (!transpose[i] && wsi[3] != p.Cin) throw P3dError("filter Cin mismatch");
+        if (transpose[i] && dbias[i]) throw P3dError("wgrad_group: a transposed conv's bias gradient is a column sum of its own");
+        check_slice("wgrad_group (x)", ldx[i], offx[i], p.Cin);
+        check_slice("wgrad_group (dy)", lddy[i], offdy[i], p.Cout);
+        Bufs& b = bufs[(size_t)i];
+        b.nw = prod5(wsi); b.nb = p.Cout;
+        b.x.reset(new DevBuf(p.rows_in * ldx[i], x[i]));
+        b.dy.reset(new DevBuf(p.rows * lddy[i], dy[i]));
+        if (b.nw > 0 && !dw[i]) throw P3dError("null argument");
+        b.dw.reset(new DevBuf(b.nw, dw[i]));
+        if (dbias[i]) b.db.reset(new DevBuf(b.nb, dbias[i]));
+        WgradArgs a = p.filter_gradient(b.x->p + offx[i], ldx[i], b.dy->p + offdy[i], lddy[i], b.dw->p, dbias[i] ? b.db->p : nullptr);
+        a.zeros = g_zero_page;
+        a.polite = polite ? 1 : 0; a.greedy = greedy ? 1 : 0;
+        double f1, b1;
+        wgrad_work(a, f1, b1);
+        fl += f1; by += b1;
+        probs.push_back(a);
+    }
+    info[1] = info[2] = 0;
+    if (p3d_wgrad2_group_cuts(probs.data(), n, cuts, &info[0], &info[1], &info[2]) < 0) throw P3dError("wgrad_group: a problem the kernel does not take");
+    const char* name = wgrad_group_name(probs);
+    put_string(name, kernel, kernel_cap);
+    Ctx c;
+    launch_wgrad_group(c, probs, name, fl, by);
+    for (int i = 0; i < n; ++i) {
+        if (bufs[(size_t)i].nw > 0) bufs[(size_t)i].dw->get(dw[i], bufs[(size_t)i].nw);
+        if (dbias[i]) bufs[(size_t)i].db->get(dbias[i], bufs[(size_t)i].nb);
+    }
+    API_END
+}
+
+int p3d_debug_max_pool3d(int device, const float* x, int ldx, int offx, const int64_t xs[5], const int k[3], const int s[3], float* y,
+                         int ldy, int offy) {
+    API_BEGIN
+    HIPCHECK(hipSetDevice(device));
+    if (!x || !xs || !k || !s || !y) throw P3dError("null argument");
+    const ConvGeo g = make_geo((int)xs[1], (int)xs[2], (int)xs[3], k, s);
+    const int C = (int)xs[4];
+    check_slice("max_pool3d (x)", ldx, offx, C);
+    check_slice("max_pool3d (y)", ldy, offy, C);
+    const int64_t rin = xs[0] * xs[1] * xs[2] * xs[3], rout = xs[0] * g.O[0] * g.O[1] * g.O[2];
+    DevBuf dx(rin * ldx, x), dy(rout * ldy, y);
+    PoolArgs a = pool_args(g, (int)xs[0], C, ldx, ldy);
+    a.x = dx.p + offx; a.y = dy.p + offy;
+    HIPCHECK(p3d_maxpool_fwd(a, nullptr));
+    dy.get(y, rout * ldy);
+    API_END
+}
+
+int p3d_debug_max_pool3d_grad(int device, const float* x, int ldx, int offx, const int64_t xs[5], const int k[3], const int s[3],
+                              const float* dyh, int ldy, int offy, int accumulate, float* dxh, const char** kernel) {
+    API_BEGIN
+    HIPCHECK(hipSetDevice(device));
+    if (!x || !xs || !k || !s || !dyh || !dxh) throw P3dError("null argument");
+    const ConvGeo g = make_geo((int)xs[1], (int)xs[2], (int)xs[3], k, s);
+    const int C = (int)xs[4];
+    check_slice("max_pool3d_grad (x, dx)", ldx, offx, C);
+    check_slice("max_pool3d_grad (y, dy)", ldy, offy, C);
+    const int64_t rin = xs[0] * xs[1] * xs[2] * xs[3], rout = xs[0] * g.O[0] * g.O[1] * g.O[2];
+    DevBuf dx(rin * ldx, x), dy(rout * ldy, dyh), dg(rin * ldx, dxh), yy(rout * ldy), tab(rout * (C / 4));
+    PoolArgs a = pool_args(g, (int)xs[0], C, ldx, ldy);
+    a.x = dx.p + offx; a.dy = dy.p + offy; a.dx = dg.p + offx; a.y = yy.p + offy;
+    const bool disjoint = p3d_maxpool_disjoint(a);
+    if (!disjoint) a.idx = reinterpret_cast<unsigned*>(tab.p);
+    HIPCHECK(p3d_maxpool_fwd(a, nullptr));
+    if (disjoint) HIPCHECK(p3d_maxpool_bwd_disjoint(a, accumulate ? 1 : 0, nullptr));
+    else HIPCHECK(p3d_maxpool_bwd_gather(a, accumulate ? 1 : 0, nullptr));
+    if (kernel) *kernel = disjoint ? "maxpool_bwd_disjoint_kernel" : "maxpool_bwd_gather_kernel";
+    dg.get(dxh, rin * ldx);
+    API_END
+}
+
+int p3d_debug_bias_add_grad(int device, const float* dyh, int64_t rows, int channels, int ld, int off, float* dbias) {
+    API_BEGIN
+    if (!dyh || !dbias) throw P3dError("null argument");
+    if (rows < 0 || channels < 1 || off < 0 || ld < off + channels) throw P3dError("bias_add_grad needs rows >= 0, channels >= 1 and offset + channels <= row length");
+    HIPCHECK(hipSetDevice(device));
+    DevBuf dy(rows * ld, dyh), db(channels, dbias);
+    if (rows > 0) HIPCHECK(p3d_colsum(dy.p + off, ld, (long)rows, channels, db.p, nullptr));
     db.get(dbias, channels);
     API_END
 }

@@ -270,6 +270,8 @@ hipError_t p3d_launch_wgrad2(const WgradArgs& a, hipStream_t s);
 hipError_t p3d_launch_wgrad2_group(const WgradArgs* probs, int n, hipStream_t s);   // up to P3D_WGRAD_GROUP problems, one launch
 const char* p3d_wgrad2_variant(const WgradArgs& a);
 const char* p3d_wgrad2_group_variant(const WgradArgs* probs, int n, bool fused);      // the label of a grouped launch (its tile)
+// test hook (host only): cuts[i] of problem i in that launch (0: dropped), the slab stride, the tile; returns the live problems or -1
+int p3d_wgrad2_group_cuts(const WgradArgs* probs, int n, int* cuts, int* kstride, int* tm, int* tn);
 void p3d_wgrad2_force_tile(int tm, int tn);      // test hook: tile of single-problem launches (64 / 128 each); 0, 0 = the plan's choice
 
 // ---- BatchNorm (tf.layers.batch_normalization, rank-5, eps 1e-3) ------------------------------

@@ -207,6 +207,138 @@ def cbam(x, k0, b0, k1, b1, k7, dout, chunks=0, dx=None, pgrads=None, ld=None, p
             dxs[:, C_:])
 
 
+def _embed(a, ld, offset, fill):
+    """[rows, C] -> [rows, ld] float32 holding `a` in columns offset .. offset + C and `fill` in every other column."""
+    a = _f32(a)
+    out = np.full((a.shape[0], int(ld)), fill, np.float32)
+    out[:, offset:offset + a.shape[1]] = a
+    return out
+
+
+def _outside(buf, C_, offset):
+    """The columns of [rows, ld] `buf` that are not in the slice offset .. offset + C (left of it, then right of it)."""
+    return np.concatenate([buf[:, :offset], buf[:, offset + C_:]], axis=1)
+
+
+CONV_KINDS = {"forward": 0, "input_grad": 1, "transpose": 2}
+
+
+def conv_launch(kind, inp, filter, strides, input_sizes=None, bias=None, accum=False, f16=False, ld=(None, None), offset=(0, 0),
+                pad=np.nan, prior=np.nan, device=0):
+    """Test hook: one conv of the network in the launch form the train step uses (p3d_debug_conv_launch).  kind "forward"
+    (inp = x), "input_grad" (inp = dy, input_sizes = shape of x) or "transpose" (tf.layers.conv3d_transpose, filter
+    [kd,kh,kw,Cout,Cin]).  ld = (row length of the gathered operand, of the output), None for its channel count; offset = the
+    channel offsets of the two slices; every column outside a slice holds `pad`.  prior: what the output slice holds before the
+    launch (scalar or array of the output's shape); accum: the launch adds to it.  f16: the fp16 option (1x1x1 only).  Returns
+    (the output slice, everything outside it [rows, ld - C], the kernel names joined with ';'); conv_launch.last_splits = the
+    (smallest, largest) K-slice count of the launches' plans."""
+    x, w = _f32(inp), _f32(filter)
+    s = _strides3(strides)
+    kd = CONV_KINDS[kind]
+    if kd == 0:
+        xshape = x.shape
+        oshape = (x.shape[0],) + tuple(_same_out(x.shape[1 + i], s[i]) for i in range(3)) + (w.shape[4],)
+    elif kd == 1:
+        xshape = tuple(int(v) for v in input_sizes)
+        oshape = xshape
+    else:
+        xshape = x.shape
+        oshape = (x.shape[0], x.shape[1] * s[0], x.shape[2] * s[1], x.shape[3] * s[2], w.shape[3])
+    ci, co = x.shape[4], oshape[4]
+    l_in, l_out = (c if v is None else int(v) for v, c in zip(ld, (ci, co)))
+    o_in, o_out = (int(v) for v in offset)
+    xin = _embed(x.reshape(-1, ci), l_in, o_in, pad)
+    rows_out = int(np.prod(oshape[:4]))
+    pr = np.broadcast_to(np.asarray(prior, np.float32), oshape).reshape(rows_out, co)
+    out = _embed(pr, l_out, o_out, pad)
+    b = _f32(bias) if bias is not None else None
+    names = C.create_string_buffer(16384)
+    splits = (C.c_int * 2)()
+    check(lib().p3d_debug_conv_launch(device, kd, fptr(xin), l_in, o_in, _shape5(xshape), fptr(w), _shape5(w.shape), _i3(s), fptr(b),
+                                      1 if accum else 0, 1 if f16 else 0, fptr(out), l_out, o_out, names, len(names), splits))
+    conv_launch.last_splits = (splits[0], splits[1])
+    return out[:, o_out:o_out + co].reshape(oshape).copy(), _outside(out, co, o_out), names.value.decode()
+
+
+def wgrad_group(problems, polite=False, greedy=False, pad=np.nan, device=0):
+    """Test hook: up to 6 filter gradients as ONE launch, the way the train step's queue sends them (p3d_debug_wgrad_group).
+    Each problem is a dict: x, dy, filter_sizes, strides, and optionally ld = (row length of x, of dy), offset = (channel offset
+    of x, of dy), dw / dbias = what the gradients hold before (dw default zeros; dbias None: no bias gradient), transpose (a
+    transposed conv's problem: x its input, dy the gradient of its output, filter_sizes [kd,kh,kw,Cout,Cin]).  Columns outside the
+    slices hold `pad`.  Returns ([(dw, dbias or None), ...], kernel name, cuts per problem (0: dropped), (slab stride, tile rows,
+    tile columns))."""
+    n = len(problems)
+    xs, dys, dws, dbs, keep = [], [], [], [], []
+    ldx, offx, lddy, offdy, tr = [], [], [], [], []
+    xsh, wsh, st = [], [], []
+    for pr in problems:
+        x, dy = _f32(pr["x"]), _f32(pr["dy"])
+        fs = tuple(int(v) for v in pr["filter_sizes"])
+        l = pr.get("ld", (None, None))
+        o = pr.get("offset", (0, 0))
+        lx, ly = (c if v is None else int(v) for v, c in zip(l, (x.shape[4], dy.shape[4])))
+        xs.append(_embed(x.reshape(-1, x.shape[4]), lx, int(o[0]), pad))
+        dys.append(_embed(dy.reshape(-1, dy.shape[4]), ly, int(o[1]), pad))
+        dws.append(np.zeros(fs, np.float32) if pr.get("dw") is None else _f32(np.asarray(pr["dw"]).reshape(fs)).copy())
+        dbs.append(None if pr.get("dbias") is None else _f32(np.asarray(pr["dbias"]).reshape(fs[3] if pr.get("transpose") else fs[4])).copy())
+        ldx.append(lx); offx.append(int(o[0])); lddy.append(ly); offdy.append(int(o[1])); tr.append(1 if pr.get("transpose") else 0)
+        xsh += [int(v) for v in x.shape]
+        wsh += list(fs)
+        st += [int(v) for v in _strides3(pr["strides"])]
+    fpp = type(fptr(dws[0]))
+    arr = lambda v: (fpp * n)(*[fptr(a) for a in v])
+    ints = lambda v: (C.c_int * len(v))(*v)
+    name = C.create_string_buffer(256)
+    cuts, info = (C.c_int * n)(), (C.c_int * 3)()
+    check(lib().p3d_debug_wgrad_group(device, n, arr(xs), ints(ldx), ints(offx), (C.c_int64 * len(xsh))(*xsh), arr(dys), ints(lddy),
+                                      ints(offdy), (C.c_int64 * len(wsh))(*wsh), ints(st), ints(tr), arr(dws), arr(dbs),
+                                      1 if polite else 0, 1 if greedy else 0, name, len(name), cuts, info))
+    return list(zip(dws, dbs)), name.value.decode(), list(cuts), tuple(info)
+
+
+def max_pool3d_launch(x, ksize, strides, ld=(None, None), offset=(0, 0), pad=np.nan, prior=np.nan, device=0):
+    """Test hook: tf.nn.max_pool3d SAME with x and y as channel slices (p3d_debug_max_pool3d); ld / offset = (of x, of y).
+    Returns (y, what its buffer holds outside the slice)."""
+    x = _f32(x)
+    k, s = _strides3(ksize), _strides3(strides)
+    C_ = x.shape[4]
+    oshape = (x.shape[0],) + tuple(_same_out(x.shape[1 + i], s[i]) for i in range(3)) + (C_,)
+    lx, ly = (C_ if v is None else int(v) for v in ld)
+    xin = _embed(x.reshape(-1, C_), lx, offset[0], pad)
+    rows = int(np.prod(oshape[:4]))
+    y = _embed(np.broadcast_to(np.asarray(prior, np.float32), oshape).reshape(rows, C_), ly, offset[1], pad)
+    check(lib().p3d_debug_max_pool3d(device, fptr(xin), lx, int(offset[0]), _shape5(x.shape), _i3(k), _i3(s), fptr(y), ly, int(offset[1])))
+    return y[:, offset[1]:offset[1] + C_].reshape(oshape).copy(), _outside(y, C_, offset[1])
+
+
+def max_pool3d_grad_launch(x, ksize, strides, grad, accumulate=False, ld=(None, None), offset=(0, 0), pad=np.nan, prior=np.nan, device=0):
+    """Test hook: the gradient of max_pool3d_launch (p3d_debug_max_pool3d_grad); ld / offset = (of x and dx, of y and dy).  prior:
+    what dx holds before; accumulate: the kernel adds to it.  Returns (dx, what its buffer holds outside the slice, kernel)."""
+    x, g = _f32(x), _f32(grad)
+    k, s = _strides3(ksize), _strides3(strides)
+    C_ = x.shape[4]
+    lx, ly = (C_ if v is None else int(v) for v in ld)
+    rows = int(np.prod(x.shape[:4]))
+    xin = _embed(x.reshape(rows, C_), lx, offset[0], pad)
+    gin = _embed(g.reshape(-1, C_), ly, offset[1], pad)
+    dx = _embed(np.broadcast_to(np.asarray(prior, np.float32), x.shape).reshape(rows, C_), lx, offset[0], pad)
+    kernel = C.c_char_p()
+    check(lib().p3d_debug_max_pool3d_grad(device, fptr(xin), lx, int(offset[0]), _shape5(x.shape), _i3(k), _i3(s), fptr(gin), ly,
+                                          int(offset[1]), 1 if accumulate else 0, fptr(dx), C.byref(kernel)))
+    return dx[:, offset[0]:offset[0] + C_].reshape(x.shape).copy(), _outside(dx, C_, offset[0]), kernel.value.decode()
+
+
+def bias_add_grad_launch(dy, ld=None, offset=0, pad=np.nan, prior=0.0, device=0):
+    """Test hook: BiasAddGrad on a channel slice of rows of `ld` floats, ADDED to `prior` (p3d_debug_bias_add_grad)."""
+    g = _f32(dy)
+    c = g.shape[-1]
+    l = c if ld is None else int(ld)
+    gin = _embed(g.reshape(-1, c), l, offset, pad)
+    out = np.broadcast_to(np.asarray(prior, np.float32), (c,)).copy()
+    check(lib().p3d_debug_bias_add_grad(device, fptr(gin), gin.shape[0], c, l, int(offset), fptr(out)))
+    return out
+
+
 def head(x, k, bias, dlogits, transpose=True, sigmoid=True, dk=None, dbias=None, fwd_path=0, filter_path=0, device=0):
     """Test hook: the network's output head (include/p3d_hip.h p3d_debug_head) on x [N, D, H, W, C]: transpose = the
     conv3d_transpose(x, 1, 3, 2) head, else the stride-1 conv3d(x, 1, 3, 1).  k: 27 * C floats ([3, 3, 3, 1, C] or

@@ -1,6 +1,10 @@
 """Op-level parity of the HIP kernels (through the C ABI's p3d_op_* entry points) against the
 oracle in float64.  Tolerance: 2e-5 of the result's max magnitude (fp32 sums of up to ~7k terms;
-the north-star tolerance for the path is 1e-3 relative)."""
+the north-star tolerance for the path is 1e-3 relative).
+
+The entry points used here launch every conv dense (ld == channels), without accumulation, one filter gradient per launch,
+into outputs they zero-fill first.  The forms the train step launches -- channel slices, accum = 1, NaN-prefilled outputs,
+grouped filter gradients, the fp16 option -- are tested in tests/test_gpu_conv_launch.py."""
 import numpy as np
 import pytest
 
