@@ -448,6 +448,32 @@ int p3d_debug_bias_add_grad(int device, const float* dy, int64_t rows, int chann
  * matrix on chip (ch in {32, 64, 128, 256}).  With d_o (the gradient of o) it also writes dg, df, dh. */
 int p3d_op_attention_core(int device, int batch, int n_g, int n_f, int ch, const float* g, const float* f, const float* h,
                           float* o, const float* d_o, float* dg, float* df, float* dh);
+/* Test hooks: the self-attention block's kernels as the train step launches them (tests/test_gpu_attention.py).
+ *
+ * p3d_debug_attention_core: p3d_op_attention_core in either execution of p3d_set_attention_mode.  mode 1: the stored-score
+ * sequence of the graph op (row padding of f and h to a multiple of 4 keys, per-clip GEMMs on the conv kernels, softmax rows,
+ * filter-gradient launches for df and dh) on buffers of its own; any ch that is a multiple of 32.  mode 2: the kernels that keep
+ * the scores on chip; ch in {32, 64, 128, 256}, anything else is refused.  Every output buffer, the stored scores and every scratch
+ * buffer holds NaNs before the launches.
+ * p3d_debug_attention_splits (host only): K-slices the plan gives the four row-major products of mode 1 at this shape, in launch
+ * order: g f^T, beta h, d_o h^T, ds f (1: not sliced).
+ *
+ * p3d_debug_softmax_rows: softmax over the first `cols` floats of rows of `ld` floats, in place (backward = 0: s becomes the
+ * attention map, columns [cols, ld) zero), or its gradient (backward = 1: s = the attention map, d = its gradient on entry and the
+ * gradient of the scores on return, columns [cols, ld) zero).  s and d are [rows + guard_rows][ld], copied in and back whole: the
+ * guard rows after the last row must come back as they went in.
+ *
+ * p3d_debug_attn_mix: z = r * gamma + x over M rows of C channels (utils/network.py:191), with the block's dropout of rate
+ * drop_rate (0: none) keyed by seed -- passed as an argument, or read from device memory when seed_dev -- and, with dz, the
+ * backward pass.  r / dr are C channels at column offr of rows of ldr floats, x / dx at offx of ldx, z / dz at offz of ldz.  z, dr
+ * and dx are in / out at their full extent [M][ld]; accx = 1: dx += the gradient; dgamma[1] is added to. */
+int p3d_debug_attention_core(int device, int mode, int batch, int n_g, int n_f, int ch, const float* g, const float* f, const float* h,
+                             float* o, const float* d_o, float* dg, float* df, float* dh);
+int p3d_debug_attention_splits(int batch, int n_g, int n_f, int ch, int splits[4]);
+int p3d_debug_softmax_rows(int device, int backward, int64_t rows, int cols, int ld, float* s, float* d, int guard_rows);
+int p3d_debug_attn_mix(int device, int64_t M, int C, const float* r, int ldr, int offr, const float* x, int ldx, int offx, float gamma,
+                       float drop_rate, uint64_t seed, int seed_dev, float* z, int ldz, int offz, const float* dz, int accx, float* dr,
+                       float* dx, float* dgamma);
 
 /* ---- validation metrics and frame pre-processing: the steps either side of the path.
  *      Host arrays in and out, float64 results.  Maps are float32 [n_maps][n_pix] of ONE shape (the reference's

@@ -137,6 +137,11 @@ SIGNATURES = {
                                             C.POINTER(C.c_char_p)]),
     "p3d_debug_bias_add_grad": (C.c_int, [C.c_int, _fp, C.c_int64, C.c_int, C.c_int, C.c_int, _fp]),
     "p3d_op_attention_core": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "p3d_debug_attention_core": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "p3d_debug_attention_splits": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _ip]),
+    "p3d_debug_softmax_rows": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _fp, _fp, C.c_int]),
+    "p3d_debug_attn_mix": (C.c_int, [C.c_int, C.c_int64, C.c_int, _fp, C.c_int, C.c_int, _fp, C.c_int, C.c_int, C.c_float, C.c_float,
+                                     C.c_uint64, C.c_int, _fp, C.c_int, C.c_int, _fp, C.c_int, _fp, _fp, _fp]),
     "p3d_metric_cc": (C.c_int, [C.c_int, _fp, _fp, C.c_int, C.c_int, _dp]),
     "p3d_metric_sim": (C.c_int, [C.c_int, _fp, _fp, C.c_int, C.c_int, _dp]),
     "p3d_metric_nss": (C.c_int, [C.c_int, _fp, _fp, C.c_int, C.c_int, _dp]),

@@ -58,7 +58,8 @@ __device__ __forceinline__ float group_sum(float v, float* red) {
 }
 
 // TPR threads per row (64: one wave per row, 4 rows per block; 256: one block per row); a row is kept in registers
-// when it fits EPT elements per thread, otherwise it is re-read (three passes).
+// when it fits EPT elements per thread, otherwise it is re-read (three passes).  "Fits" is decided on ld, not cols: the
+// register path writes columns below TPR * EPT only, and the padded columns [cols, ld) are part of what it owes.
 constexpr int EPT = 16;
 
 template <int TPR>
@@ -71,7 +72,7 @@ __global__ __launch_bounds__(256) void softmax_fwd_kernel(float* s, long long ro
         const long long r = r0 + threadIdx.x / TPR;
         const bool live = r < rows;
         float* row = s + (live ? r : 0) * ld;
-        if (cols <= TPR * EPT) {
+        if (ld <= TPR * EPT) {
             float v[EPT];
             float m = -INFINITY;
 #pragma unroll
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(256) void softmax_bwd_kernel(const float* beta, flo
         const bool live = r < rows;
         const float* b = beta + (live ? r : 0) * ld;
         float* g = d + (live ? r : 0) * ld;
-        if (cols <= TPR * EPT) {
+        if (ld <= TPR * EPT) {
             float bv[EPT], gv[EPT];
             float dot = 0.f;
 #pragma unroll

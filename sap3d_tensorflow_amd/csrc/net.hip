@@ -903,6 +903,72 @@ void zero_strided(const Ctx& c, float* p, int ld, int64_t rows, int C) {
     else HIPCHECK(hipMemset2DAsync(p, (size_t)ld * sizeof(float), 0, (size_t)C * sizeof(float), (size_t)rows, c.s));
 }
 
+// The stored-score execution of the attention core  o = softmax(g f^T) h  (utils/network.py:183-185) and of its four gradients:
+// three GEMMs per direction and clip around a stored [Ng x Nfp] score matrix, Nfp = Nf rounded up to 4 (key / value rows are
+// padded with zero rows first; the softmax masks the padded columns).  Described once, on plain pointers, for the graph op
+// (attn_run) and the test hook (p3d_debug_attention_core).  f, h, df, dh are dense ([B][Nf][ch/8], [B][Nf][ch]); g / dg and
+// o / d_o are rows of ldg and ldo floats.  sbuf, dsbuf: [B][Ng][Nfp]; the four pad buffers ([B][Nfp][ch/8 or ch]) only when
+// Nfp != Nf.  (gD, gH, gW) is the lattice the Ng queries of a clip come from (each extent below 1024: packed coordinates).
+struct AttnCore {
+    int B = 0, Ng = 0, Nf = 0, ch = 0, gD = 1, gH = 1, gW = 1;
+    const float* g = nullptr; int ldg = 0;
+    const float* f = nullptr; const float* h = nullptr;
+    float* o = nullptr; int ldo = 0;
+    const float* d_o = nullptr;
+    float *dg = nullptr, *df = nullptr, *dh = nullptr;
+    float *sbuf = nullptr, *dsbuf = nullptr, *fpad = nullptr, *hpad = nullptr, *dfpad = nullptr, *dhpad = nullptr;
+    int ci() const { return ch / 8; }
+    int Nfp() const { return (Nf + 3) / 4 * 4; }
+    bool pad() const { return Nfp() != Nf; }
+    const float* F() const { return pad() ? fpad : f; }
+    const float* H() const { return pad() ? hpad : h; }
+    // the four row-major products of clip b: scores = g f^T, o = beta h, d beta = d o h^T, d g = d s f
+    enum Product { SCORES = 0, OUT = 1, DBETA = 2, DG = 3 };
+    IgemmArgs product(int which, int b) const {
+        const int64_t sb = (int64_t)b * Ng * Nfp(), fb = (int64_t)b * Nfp() * ci(), hb = (int64_t)b * Nfp() * ch;
+        switch (which) {
+            case SCORES: return gemm_rows(gD, gH, gW, g + (int64_t)b * Ng * ldg, ldg, ci(), F() + fb, 1, sbuf + sb, Nfp(), Nfp());
+            case OUT: return gemm_rows(gD, gH, gW, sbuf + sb, Nfp(), Nfp(), H() + hb, 0, o + (int64_t)b * Ng * ldo, ldo, ch);
+            case DBETA: return gemm_rows(gD, gH, gW, d_o + (int64_t)b * Ng * ldo, ldo, ch, H() + hb, 1, dsbuf + sb, Nfp(), Nfp());
+            default: return gemm_rows(gD, gH, gW, dsbuf + sb, Nfp(), Nfp(), F() + fb, 0, dg + (int64_t)b * Ng * ldg, ldg, ci());
+        }
+    }
+    int splits(int which) const { return std::max(1, p3d_igemm2_plan(product(which, 0), 1).splits); }
+    // one GEMM per clip; if the planner slices K (few rows), the whole output is zeroed once and the launches add
+    void gemm_each(const Ctx& c, int which, float* out, int ld, int Nc) const {
+        const bool split = splits(which) > 1;
+        if (split) zero_strided(c, out, ld, (int64_t)B * Ng, Nc);
+        for (int b = 0; b < B; ++b) launch_igemm(c, product(which, b), split ? 1 : 0);
+    }
+    void forward(const Ctx& c) const {
+        const int Np = Nfp(), k = ci();
+        if (pad()) {
+            launch(c, "pad_rows_kernel", 0, 8.0 * B * Np * k, [&]() { return p3d_pad_rows(f, fpad, B, Nf, Np, k, c.s); });
+            launch(c, "pad_rows_kernel", 0, 8.0 * B * Np * ch, [&]() { return p3d_pad_rows(h, hpad, B, Nf, Np, ch, c.s); });
+        }
+        gemm_each(c, SCORES, sbuf, Np, Np);
+        launch(c, "softmax_fwd_kernel", 0, 8.0 * B * Ng * Np, [&]() { return p3d_softmax_rows(sbuf, (long long)B * Ng, Nf, Np, c.s); });
+        gemm_each(c, OUT, o, ldo, ch);
+    }
+    void backward(const Ctx& c) const {
+        const int Np = Nfp(), k = ci();
+        float* dF = pad() ? dfpad : df; float* dH = pad() ? dhpad : dh;
+        gemm_each(c, DBETA, dsbuf, Np, Np);                                                        // d beta = d o * h^T
+        zero_strided(c, dH, ch, (int64_t)B * Np, ch);
+        for (int b = 0; b < B; ++b)                                                                // d h = beta^T * d o
+            launch_wgrad(c, gemm_tn(gD, gH, gW, sbuf + (int64_t)b * Ng * Np, Np, Np, d_o + (int64_t)b * Ng * ldo, ldo, ch, dH + (int64_t)b * Np * ch));
+        launch(c, "softmax_bwd_kernel", 0, 12.0 * B * Ng * Np, [&]() { return p3d_softmax_rows_bwd(sbuf, dsbuf, (long long)B * Ng, Nf, Np, c.s); });
+        gemm_each(c, DG, dg, ldg, k);                                                              // d g = d s * f
+        zero_strided(c, dF, k, (int64_t)B * Np, k);
+        for (int b = 0; b < B; ++b)                                                                // d f = d s^T * g
+            launch_wgrad(c, gemm_tn(gD, gH, gW, dsbuf + (int64_t)b * Ng * Np, Np, Np, g + (int64_t)b * Ng * ldg, ldg, k, dF + (int64_t)b * Np * k));
+        if (pad()) {
+            launch(c, "unpad_rows_kernel", 0, 8.0 * B * Nf * k, [&]() { return p3d_unpad_rows(dfpad, df, B, Nf, Np, k, c.s); });
+            launch(c, "unpad_rows_kernel", 0, 8.0 * B * Nf * ch, [&]() { return p3d_unpad_rows(dhpad, dh, B, Nf, Np, ch, c.s); });
+        }
+    }
+};
+
 }  // namespace
 
 namespace {

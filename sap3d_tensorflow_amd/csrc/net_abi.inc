@@ -1678,29 +1678,146 @@ int p3d_debug_bias_add_grad(int device, const float* dyh, int64_t rows, int chan
     API_END
 }
 
-int p3d_op_attention_core(int device, int batch, int n_g, int n_f, int ch, const float* gh, const float* fh, const float* hh,
-                          float* o, const float* d_o, float* dg, float* df, float* dh) {
-    API_BEGIN
+namespace {
+// a device buffer whose every float is a NaN (all bits set) until a launch writes it
+struct NanBuf : DevBuf {
+    explicit NanBuf(int64_t n) : DevBuf(n) { HIPCHECK(fill_now(p, 0xFF, (size_t)(n > 0 ? n : 1) * 4, nullptr)); }
+};
+// the attention core on dense host operands, mode 1 = stored scores (AttnCore), 2 = the kernels that keep the scores on chip;
+// nan_fill: every output and scratch buffer holds NaNs before the launches
+void attention_core_on_host_arrays(const char* who, int device, int mode, bool nan_fill, int batch, int n_g, int n_f, int ch, const float* gh,
+                                   const float* fh, const float* hh, float* o, const float* d_o, float* dg, float* df, float* dh) {
+    const std::string w(who);
     if (!gh || !fh || !hh || !o) throw P3dError("null argument");
-    if (!p3d_flash_attn_ok(ch)) throw P3dError("attention_core: ch must be 32, 64, 128 or 256");
-    if (batch < 1 || n_g < 1 || n_f < 1) throw P3dError("attention_core needs at least one clip, query and key");
-    if (d_o && (!dg || !df || !dh)) throw P3dError("attention_core: the backward pass writes dg, df and dh");
+    if (mode != 1 && mode != 2) throw P3dError(w + ": mode is 1 (stored scores) or 2 (scores on chip)");
+    if (mode == 2 && !p3d_flash_attn_ok(ch)) throw P3dError(w + ": ch must be 32, 64, 128 or 256");
+    if (mode == 1 && (ch < 32 || ch % 32)) throw P3dError(w + ": the stored-score execution takes channel counts that are multiples of 32");
+    if (batch < 1 || n_g < 1 || n_f < 1) throw P3dError(w + " needs at least one clip, query and key");
+    if (d_o && (!dg || !df || !dh)) throw P3dError(w + ": the backward pass writes dg, df and dh");
     HIPCHECK(hipSetDevice(device));
     const int ci = ch / 8;
     const int64_t ng = (int64_t)batch * n_g, nf = (int64_t)batch * n_f;
-    DevBuf g(ng * ci, gh), f(nf * ci, fh), h(nf * ch, hh), out(ng * ch), lse(ng), dsum(ng);
-    FlashAttnArgs a;
+    auto fresh = [&](int64_t n) { return std::unique_ptr<DevBuf>(nan_fill ? new NanBuf(n) : new DevBuf(n)); };
+    DevBuf g(ng * ci, gh), f(nf * ci, fh), h(nf * ch, hh);
+    std::unique_ptr<DevBuf> out = fresh(ng * ch), dout, gg, gf, gv;
+    if (d_o) { dout.reset(new DevBuf(ng * ch, d_o)); gg = fresh(ng * ci); gf = fresh(nf * ci); gv = fresh(nf * ch); }
+    if (mode == 2) {
+        std::unique_ptr<DevBuf> lse = fresh(ng), dsum = fresh(ng);
+        FlashAttnArgs a;
+        memset(&a, 0, sizeof(a));
+        a.B = batch; a.Ng = n_g; a.Nf = n_f; a.ch = ch;
+        a.g = g.p; a.ldg = ci; a.f = f.p; a.ldf = ci; a.h = h.p; a.ldh = ch; a.o = out->p; a.ldo = ch; a.lse = lse->p;
+        HIPCHECK(p3d_flash_attn_fwd(a, nullptr));
+        out->get(o, ng * ch);
+        if (d_o) {
+            a.d_o = dout->p; a.lddo = ch; a.dsum = dsum->p;
+            a.dg = gg->p; a.lddg = ci; a.df = gf->p; a.lddf = ci; a.dh = gv->p; a.lddh = ch;
+            HIPCHECK(p3d_flash_attn_bwd(a, nullptr));
+        }
+    } else {
+        AttnCore a;
+        a.B = batch; a.Ng = n_g; a.Nf = n_f; a.ch = ch;
+        // the queries of a clip as a lattice with every extent below 1024 (the GEMM kernels pack lattice coordinates)
+        int rest = n_g;
+        for (int* e : {&a.gW, &a.gH}) {
+            int d = std::min(rest, 1023);
+            while (rest % d) --d;
+            *e = d; rest /= d;
+        }
+        a.gD = rest;
+        if (a.gD > 1023) throw P3dError(w + ": n_g has no factorisation into three extents below 1024");
+        const int64_t nfp = (int64_t)batch * a.Nfp();
+        std::unique_ptr<DevBuf> sbuf = fresh(ng * a.Nfp()), dsbuf = fresh(ng * a.Nfp()), fpad, hpad, dfpad, dhpad;
+        if (a.pad()) { fpad = fresh(nfp * ci); hpad = fresh(nfp * ch); dfpad = fresh(nfp * ci); dhpad = fresh(nfp * ch); }
+        a.g = g.p; a.ldg = ci; a.f = f.p; a.h = h.p; a.o = out->p; a.ldo = ch;
+        a.sbuf = sbuf->p; a.dsbuf = dsbuf->p;
+        if (a.pad()) { a.fpad = fpad->p; a.hpad = hpad->p; a.dfpad = dfpad->p; a.dhpad = dhpad->p; }
+        ensure_zero_page();
+        Ctx c;
+        a.forward(c);
+        out->get(o, ng * ch);
+        if (d_o) {
+            a.d_o = dout->p; a.dg = gg->p; a.df = gf->p; a.dh = gv->p;
+            a.backward(c);
+        }
+    }
+    if (d_o) { gg->get(dg, ng * ci); gf->get(df, nf * ci); gv->get(dh, nf * ch); }
+}
+}  // namespace
+
+int p3d_op_attention_core(int device, int batch, int n_g, int n_f, int ch, const float* gh, const float* fh, const float* hh,
+                          float* o, const float* d_o, float* dg, float* df, float* dh) {
+    API_BEGIN
+    attention_core_on_host_arrays("attention_core", device, 2, false, batch, n_g, n_f, ch, gh, fh, hh, o, d_o, dg, df, dh);
+    API_END
+}
+
+int p3d_debug_attention_core(int device, int mode, int batch, int n_g, int n_f, int ch, const float* gh, const float* fh, const float* hh,
+                             float* o, const float* d_o, float* dg, float* df, float* dh) {
+    API_BEGIN
+    attention_core_on_host_arrays("debug_attention_core", device, mode, true, batch, n_g, n_f, ch, gh, fh, hh, o, d_o, dg, df, dh);
+    API_END
+}
+
+int p3d_debug_attention_splits(int batch, int n_g, int n_f, int ch, int* splits) {
+    API_BEGIN
+    if (!splits) throw P3dError("null argument");
+    if (batch < 1 || n_g < 1 || n_f < 1 || ch < 32 || ch % 32) throw P3dError("debug_attention_splits: bad shape");
+    // host only: the plans are a function of the shapes (AttnCore::splits never reads an operand)
+    AttnCore a;
+    a.B = batch; a.Ng = n_g; a.Nf = n_f; a.ch = ch; a.gW = n_g; a.ldg = ch / 8; a.ldo = ch;
+    for (int k = 0; k < 4; ++k) splits[k] = a.splits(k);
+    API_END
+}
+
+int p3d_debug_softmax_rows(int device, int backward, int64_t rows, int cols, int ld, float* s, float* d, int guard_rows) {
+    API_BEGIN
+    if (!s || (backward && !d)) throw P3dError("null argument");
+    if (rows < 1 || cols < 1 || ld < cols || guard_rows < 0) throw P3dError("debug_softmax_rows needs rows >= 1, 1 <= cols <= ld and guard_rows >= 0");
+    HIPCHECK(hipSetDevice(device));
+    const int64_t n = (rows + guard_rows) * ld;
+    DevBuf ds(n, s);
+    if (!backward) {
+        HIPCHECK(p3d_softmax_rows(ds.p, (long long)rows, cols, ld, nullptr));
+        ds.get(s, n);
+    } else {
+        DevBuf dd(n, d);
+        HIPCHECK(p3d_softmax_rows_bwd(ds.p, dd.p, (long long)rows, cols, ld, nullptr));
+        dd.get(d, n);
+    }
+    API_END
+}
+
+int p3d_debug_attn_mix(int device, int64_t M, int C, const float* r, int ldr, int offr, const float* x, int ldx, int offx, float gamma,
+                       float drop_rate, uint64_t seed, int seed_dev, float* z, int ldz, int offz, const float* dz, int accx, float* dr,
+                       float* dx, float* dgamma) {
+    API_BEGIN
+    if (!r || !x || !z) throw P3dError("null argument");
+    if (dz && (!dr || !dx || !dgamma)) throw P3dError("debug_attn_mix: the backward pass writes dr, dx and dgamma");
+    if (M < 1) throw P3dError("debug_attn_mix needs at least one row");
+    if (!(drop_rate >= 0.f && drop_rate < 1.f)) throw P3dError("debug_attn_mix: drop_rate in [0, 1)");
+    check_slice("debug_attn_mix (r, dr)", ldr, offr, C);
+    check_slice("debug_attn_mix (x, dx)", ldx, offx, C);
+    check_slice("debug_attn_mix (z, dz)", ldz, offz, C);
+    HIPCHECK(hipSetDevice(device));
+    DevBuf dr_in(M * ldr, r), dx_in(M * ldx, x), dzz(M * ldz, z), dgm(1, &gamma);
+    DevBuf dseed(2);
+    HIPCHECK(copy_now(dseed.p, &seed, sizeof(seed), hipMemcpyHostToDevice, nullptr));
+    AttnMixArgs a;
     memset(&a, 0, sizeof(a));
-    a.B = batch; a.Ng = n_g; a.Nf = n_f; a.ch = ch;
-    a.g = g.p; a.ldg = ci; a.f = f.p; a.ldf = ci; a.h = h.p; a.ldh = ch; a.o = out.p; a.ldo = ch; a.lse = lse.p;
-    HIPCHECK(p3d_flash_attn_fwd(a, nullptr));
-    out.get(o, ng * ch);
-    if (d_o) {
-        DevBuf dout(ng * ch, d_o), gg(ng * ci), gf(nf * ci), gv(nf * ch);
-        a.d_o = dout.p; a.lddo = ch; a.dsum = dsum.p;
-        a.dg = gg.p; a.lddg = ci; a.df = gf.p; a.lddf = ci; a.dh = gv.p; a.lddh = ch;
-        HIPCHECK(p3d_flash_attn_bwd(a, nullptr));
-        gg.get(dg, ng * ci); gf.get(df, nf * ci); gv.get(dh, nf * ch);
+    a.M = M; a.C = C; a.r = dr_in.p + offr; a.ldr = ldr; a.x = dx_in.p + offx; a.ldx = ldx; a.gamma = dgm.p;
+    a.z = dzz.p + offz; a.ldz = ldz;
+    if (drop_rate > 0.f) {         // (attn_run: the block's dropout, with the step's seed as an argument or in device memory)
+        a.drop_rate = drop_rate; a.drop_scale = 1.f / (1.f - drop_rate);
+        if (seed_dev) a.seed_dev = reinterpret_cast<const unsigned long long*>(dseed.p); else a.seed = seed;
+    }
+    HIPCHECK(p3d_attn_mix_fwd(a, nullptr));
+    dzz.get(z, M * ldz);
+    if (dz) {
+        DevBuf g_z(M * ldz, dz), g_r(M * ldr, dr), g_x(M * ldx, dx), g_gm(1, dgamma);
+        a.dz = g_z.p + offz; a.dr = g_r.p + offr; a.dx = g_x.p + offx; a.accx = accx ? 1 : 0; a.dgamma = g_gm.p;
+        HIPCHECK(p3d_attn_mix_bwd(a, nullptr));      // (part and counter: the launcher's, from the stream's scratch)
+        g_r.get(dr, M * ldr); g_x.get(dx, M * ldx); g_gm.get(dgamma, 1);
     }
     API_END
 }

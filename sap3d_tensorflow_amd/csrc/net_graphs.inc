@@ -295,13 +295,14 @@
             op.flops = 2.0 * B * (double)Ng * Nf * (ci + ch);
             op.bytes = 4.0 * B * ((double)Ng * Nfp * 4 + (double)Ng * (ci + ch) + (double)Nf * (ci + ch));
             op.bflops = 2 * op.flops; op.bbytes = 2 * op.bytes;
-            const int gD = gq->D, gH = gq->H, gW = gq->W;
-            // one GEMM per clip; if the planner slices K (few rows), the whole output is zeroed once and the launches add
-            auto gemm_each = [=](const Ctx& c, float* out, int ldo, int Nc, std::function<IgemmArgs(int)> mk) {
-                IgemmArgs t = mk(0);
-                const bool split = p3d_igemm2_plan(t, 1).splits > 1;
-                if (split) zero_strided(c, out, ldo, (int64_t)B * Ng, Nc);
-                for (int b = 0; b < B; ++b) launch_igemm(c, mk(b), split ? 1 : 0);
+            // the stored-score execution on this site's tensors, as they stand when the op runs (AttnCore, net.hip)
+            auto core = [=]() {
+                AttnCore a;
+                a.B = B; a.Ng = Ng; a.Nf = Nf; a.ch = ch; a.gD = gq->D; a.gH = gq->H; a.gW = gq->W;
+                a.g = gq->p; a.ldg = gq->ld; a.f = f->p; a.h = h->p; a.o = o->p; a.ldo = o->ld;
+                a.d_o = o->g; a.dg = gq->g; a.df = f->g; a.dh = h->g;
+                a.sbuf = gb->sbuf; a.dsbuf = gb->dsbuf; a.fpad = gb->fpad; a.hpad = gb->hpad; a.dfpad = gb->dfpad; a.dhpad = gb->dhpad;
+                return a;
             };
             const double pair_flops = 2.0 * B * (double)Ng * Nf * (ci + ch);
             const double operand_bytes = 4.0 * B * ((double)Ng * (ci + ch) + (double)Nf * (ci + ch));
@@ -312,22 +313,7 @@
                     return;
                 }
                 if (!gb->sbuf) throw P3dError("attention GEMM path without its score buffers (p3d_set_attention_mode allocates them)");
-                float* const sbuf = gb->sbuf; float* const fpad = gb->fpad; float* const hpad = gb->hpad;
-                const float* F = f->p; const float* H = h->p;
-                if (pad) {
-                    launch(c, "pad_rows_kernel", 0, 8.0 * B * Nfp * ci, [&]() { return p3d_pad_rows(f->p, fpad, B, Nf, Nfp, ci, c.s); });
-                    launch(c, "pad_rows_kernel", 0, 8.0 * B * Nfp * ch, [&]() { return p3d_pad_rows(h->p, hpad, B, Nf, Nfp, ch, c.s); });
-                    F = fpad; H = hpad;
-                }
-                gemm_each(c, sbuf, Nfp, Nfp, [=](int b) {
-                    return gemm_rows(gD, gH, gW, gq->p + (int64_t)b * Ng * gq->ld, gq->ld, ci, F + (int64_t)b * Nfp * ci, 1,
-                                     sbuf + (int64_t)b * Ng * Nfp, Nfp, Nfp);
-                });
-                launch(c, "softmax_fwd_kernel", 0, 8.0 * B * Ng * Nfp, [&]() { return p3d_softmax_rows(sbuf, (long long)B * Ng, Nf, Nfp, c.s); });
-                gemm_each(c, o->p, o->ld, ch, [=](int b) {
-                    return gemm_rows(gD, gH, gW, sbuf + (int64_t)b * Ng * Nfp, Nfp, Nfp, H + (int64_t)b * Nfp * ch, 0,
-                                     o->p + (int64_t)b * Ng * o->ld, o->ld, ch);
-                });
+                core().forward(c);
             };
             op.bwd = [=](const Ctx& c) {
                 if (*flg || *flf || *flh) throw P3dError("attention operands have one consumer each");
@@ -338,31 +324,7 @@
                     launch(c, "flash_bwd(rowdot + q + k kernels)", 3.2 * pair_flops, 3 * operand_bytes, [&]() { return p3d_flash_attn_bwd(a, c.s); });
                     return;
                 }
-                float* const sbuf = gb->sbuf; float* const dsbuf = gb->dsbuf;
-                float* const fpad = gb->fpad; float* const hpad = gb->hpad; float* const dfpad = gb->dfpad; float* const dhpad = gb->dhpad;
-                const float* F = pad ? fpad : f->p; const float* H = pad ? hpad : h->p;
-                float* dF = pad ? dfpad : f->g; float* dH = pad ? dhpad : h->g;
-                gemm_each(c, dsbuf, Nfp, Nfp, [=](int b) {          // d beta = d o * h^T
-                    return gemm_rows(gD, gH, gW, o->g + (int64_t)b * Ng * o->ld, o->ld, ch, H + (int64_t)b * Nfp * ch, 1,
-                                     dsbuf + (int64_t)b * Ng * Nfp, Nfp, Nfp);
-                });
-                zero_strided(c, dH, ch, (int64_t)B * Nfp, ch);
-                for (int b = 0; b < B; ++b)                        // d h = beta^T * d o
-                    launch_wgrad(c, gemm_tn(gD, gH, gW, sbuf + (int64_t)b * Ng * Nfp, Nfp, Nfp, o->g + (int64_t)b * Ng * o->ld, o->ld, ch,
-                                            dH + (int64_t)b * Nfp * ch));
-                launch(c, "softmax_bwd_kernel", 0, 12.0 * B * Ng * Nfp, [&]() { return p3d_softmax_rows_bwd(sbuf, dsbuf, (long long)B * Ng, Nf, Nfp, c.s); });
-                gemm_each(c, gq->g, gq->ld, ci, [=](int b) {        // d g = d s * f
-                    return gemm_rows(gD, gH, gW, dsbuf + (int64_t)b * Ng * Nfp, Nfp, Nfp, F + (int64_t)b * Nfp * ci, 0,
-                                     gq->g + (int64_t)b * Ng * gq->ld, gq->ld, ci);
-                });
-                zero_strided(c, dF, ci, (int64_t)B * Nfp, ci);
-                for (int b = 0; b < B; ++b)                        // d f = d s^T * g
-                    launch_wgrad(c, gemm_tn(gD, gH, gW, dsbuf + (int64_t)b * Ng * Nfp, Nfp, Nfp, gq->p + (int64_t)b * Ng * gq->ld, gq->ld, ci,
-                                            dF + (int64_t)b * Nfp * ci));
-                if (pad) {
-                    launch(c, "unpad_rows_kernel", 0, 8.0 * B * Nf * ci, [&]() { return p3d_unpad_rows(dfpad, f->g, B, Nf, Nfp, ci, c.s); });
-                    launch(c, "unpad_rows_kernel", 0, 8.0 * B * Nf * ch, [&]() { return p3d_unpad_rows(dhpad, h->g, B, Nf, Nfp, ch, c.s); });
-                }
+                core().backward(c);
             };
             ops.push_back(op);
         }

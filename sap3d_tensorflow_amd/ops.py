@@ -526,6 +526,79 @@ def attention_core(g, f, h, d_o=None, device=0):
     return o, dg, df, dh
 
 
+ATTENTION_MODES = {"stored": 1, "flash": 2}
+
+
+def attention_core_launch(mode, g, f, h, d_o=None, device=0):
+    """Test hook (p3d_debug_attention_core): attention_core in the execution `mode` -- "stored": the graph op's launch sequence
+    around a stored score matrix (any ch that is a multiple of 32), "flash": the kernels of attention_core.  Outputs and scratch
+    hold NaNs before the launches."""
+    g, f, h = _f32(g), _f32(f), _f32(h)
+    B, ng, ci = g.shape
+    nf, ch = h.shape[1], h.shape[2]
+    if f.shape != (B, nf, ci) or h.shape[0] != B or ci * 8 != ch:
+        raise ValueError("attention_core_launch: g [B,Ng,ch/8], f [B,Nf,ch/8], h [B,Nf,ch]")
+    m = ATTENTION_MODES[mode]
+    o = np.empty((B, ng, ch), np.float32)
+    if d_o is None:
+        check(lib().p3d_debug_attention_core(device, m, B, ng, nf, ch, fptr(g), fptr(f), fptr(h), fptr(o), None, None, None, None))
+        return o
+    d = _f32(d_o)
+    if d.shape != o.shape:
+        raise ValueError("attention_core_launch: d_o has the shape of o")
+    dg, df, dh = np.empty_like(g), np.empty_like(f), np.empty_like(h)
+    check(lib().p3d_debug_attention_core(device, m, B, ng, nf, ch, fptr(g), fptr(f), fptr(h), fptr(o), fptr(d), fptr(dg), fptr(df),
+                                         fptr(dh)))
+    return o, dg, df, dh
+
+
+def attention_splits(B, ng, nf, ch):
+    """Host-only test hook: K-slices of the four row-major products of the stored-score execution (g f^T, beta h, d_o h^T, ds f)."""
+    sp = (C.c_int * 4)()
+    check(lib().p3d_debug_attention_splits(B, ng, nf, ch, sp))
+    return tuple(sp)
+
+
+def softmax_rows_launch(s, cols, d=None, guard_rows=0, device=0):
+    """Test hook (p3d_debug_softmax_rows) on whole buffers [rows + guard_rows, ld]: the softmax over the first `cols` columns of the
+    first `rows` rows of `s` (d = None; returns the buffer after the launch), or its gradient from the attention map `s` and the
+    map's gradient `d` (returns d's buffer after the launch)."""
+    s = _f32(s).copy()
+    rows, ld = s.shape[0] - guard_rows, s.shape[1]
+    if d is None:
+        check(lib().p3d_debug_softmax_rows(device, 0, rows, cols, ld, fptr(s), None, guard_rows))
+        return s
+    d = _f32(d).copy()
+    if d.shape != s.shape:
+        raise ValueError("softmax_rows_launch: d has the shape of s")
+    check(lib().p3d_debug_softmax_rows(device, 1, rows, cols, ld, fptr(s), fptr(d), guard_rows))
+    return d
+
+
+def attn_mix(r, x, gamma, C_, offset=(0, 0, 0), drop_rate=0.0, seed=0, seed_dev=False, z=None, dz=None, accx=False, dr=None, dx=None,
+             dgamma=0.0, device=0):
+    """Test hook (p3d_debug_attn_mix): z = r * gamma + x on `C_` channels at the column offsets (of r, of x, of z) of the wide
+    buffers r [M, ldr], x [M, ldx], z [M, ldz] (what z holds before the launch; default: dense, NaN), the block's dropout, and with dz
+    [M, ldz] the backward pass into dr [M, ldr] and dx [M, ldx] (what they hold before; accx: dx is added to) and dgamma (added
+    to).  Returns the z buffer, or (z, dr, dx, dgamma) buffers."""
+    r, x = _f32(r), _f32(x)
+    M = r.shape[0]
+    z = np.full((M, int(C_)), np.nan, np.float32) if z is None else _f32(z).copy()
+    args = (device, M, int(C_), fptr(r), r.shape[1], int(offset[0]), fptr(x), x.shape[1], int(offset[1]), float(gamma), float(drop_rate),
+            int(seed), 1 if seed_dev else 0, fptr(z), z.shape[1], int(offset[2]))
+    if dz is None:
+        check(lib().p3d_debug_attn_mix(*args, None, 0, None, None, None))
+        return z
+    dz = _f32(dz)
+    dr = np.full(r.shape, np.nan, np.float32) if dr is None else _f32(dr).copy()
+    dx = np.full(x.shape, np.nan, np.float32) if dx is None else _f32(dx).copy()
+    dgm = np.array([dgamma], np.float32)
+    if dz.shape != z.shape or dr.shape != r.shape or dx.shape != x.shape:
+        raise ValueError("attn_mix: dz, dr, dx have the shapes of z, r, x")
+    check(lib().p3d_debug_attn_mix(*args, fptr(dz), 1 if accx else 0, fptr(dr), fptr(dx), fptr(dgm)))
+    return z, dr, dx, dgm[0]
+
+
 def max_pool3d(x, ksize, strides, padding="SAME", device=0):
     """tf.nn.max_pool3d(x, [1,kd,kh,kw,1], [1,sd,sh,sw,1], 'SAME')."""
     x = _f32(x)

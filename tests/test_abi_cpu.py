@@ -21,9 +21,21 @@ def test_library_exports_every_declared_symbol():
     lib = _lib.lib()
     names = declared_symbols()
     assert len(names) >= 30
+    # the hooks of the attention block (tests/test_gpu_attention.py) are declared, exported and bound like every other symbol
+    assert {"p3d_debug_attention_core", "p3d_debug_attention_splits", "p3d_debug_softmax_rows", "p3d_debug_attn_mix"} <= set(names)
     for n in names:
         assert hasattr(lib, n), n
         assert n in _lib.SIGNATURES, "ctypes signature missing for " + n
+
+
+def test_attention_plan_hook_needs_no_device():
+    """p3d_debug_attention_splits is host only: the K-slice plans of the stored-score products are a function of the shapes."""
+    from sap3d_tensorflow_amd import ops, P3dError
+    assert ops.attention_splits(2, 300, 77, 32) == (1, 1, 1, 1)
+    sp = ops.attention_splits(1, 8, 1024, 32)
+    assert sp[0] == 1 and sp[1] > 1 and sp[2] == 1 and sp[3] > 1
+    with pytest.raises(P3dError):
+        ops.attention_splits(1, 8, 1024, 40)
 
 
 def test_default_config_is_the_reference_architecture():

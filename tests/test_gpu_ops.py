@@ -261,7 +261,8 @@ ATTN_CASES = [
 @pytest.mark.parametrize("B,ng,nf,ch", ATTN_CASES)
 def test_attention_core_forward_and_grads(B, ng, nf, ch):
     """softmax(g f^T) h (utils/network.py:183-185) on the kernels that keep the scores on chip, against float64 numpy:
-    forward, and dg / df / dh for a random gradient of o.  Scores of a few units, so the softmax is neither flat nor one-hot."""
+    forward, and dg / df / dh for a random gradient of o.  Scores of a few units, so the softmax is neither flat nor one-hot; flat,
+    steep and offset scores, more shapes and the stored-score execution of the same core are in tests/test_gpu_attention.py."""
     from sap3d_tensorflow_amd import ops
     rng = np.random.default_rng(ch * 1000 + ng)
     ci = ch // 8
