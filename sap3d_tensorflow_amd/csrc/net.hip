@@ -404,12 +404,44 @@ float adam_step_size(float lr, float b1, float b2, int64_t t_step) {
     return (float)(lr * std::sqrt(1.0 - std::pow((double)b2, t)) / (1.0 - std::pow((double)b1, t)));
 }
 
-// One GroupNorm pass (gn_apply in net_gn.inc, and the test hook p3d_debug_gn_pass): which kernels take it, and their launches.
-// A (sample, group) slab that fits one block goes to the one-launch small-tensor kernels unless the pass drops out; everything
-// else runs statistics -> finalize -> apply forward and reduce -> finalize (+ parameter gradients) -> apply backward.
-bool gn_small_rule(int R, int C, int G, bool dropout) {
+// The dropout fields of a launch's arguments (every struct names them alike): left zero unless the site drops out and the pass trains.
+template <typename Args>
+void set_dropout(Args& a, const Ctx& c, bool dropout) {
+    if (dropout && c.training && c.drop > 0.f) { a.drop_rate = c.drop; a.drop_scale = 1.f / (1.f - c.drop); a.seed = c.seed; a.seed_dev = c.seed_dev; }
+}
+
+// A GroupNorm's parameters, sums [N][C][2] and table: scale, shift, mean, invstd [N][C] each, then coef [N][C][3] (only here).
+GnParams gn_layout(const float* gamma, const float* beta, double* sums, float* tab, int N, int C, int G) {
+    GnParams p;
+    const int64_t nc = (int64_t)N * C;
+    p.gamma = gamma; p.beta = beta; p.sums = sums; p.C = C; p.G = G;
+    p.scale = tab; p.shift = tab + nc; p.mean = tab + 2 * nc; p.invstd = tab + 3 * nc; p.coef = tab + 4 * nc;
+    return p;
+}
+// One operand of a GroupNorm pass: values, where their gradient goes and, if it is normalised, its GroupNorm's layout (forward or
+// backward sums) and parameter gradients.  With them, the kernels' arguments (gn_apply in net_gn.inc, the hook p3d_debug_gn_pass).
+struct GnOperand {
+    const float* y = nullptr; int ld = 0; float* dy = nullptr; int lddy = 0;
+    GnParams g = {}; float* dgamma = nullptr; float* dbeta = nullptr;
+};
+GnApplyArgs gn_apply_args(int mode, int64_t M, int R, int C, float eps, const GnOperand& o1, const GnOperand& o2, int acc2,
+                          const float* cs, const float* ss, float* z, int ldz, const float* dz, const Ctx& c, bool dropout) {
+    GnApplyArgs a;
+    memset(&a, 0, sizeof(a));
+    a.mode = mode; a.M = M; a.R = R; a.C = C;
+    a.y1 = o1.y; a.ld1 = o1.ld; a.g1 = o1.g; a.dy1 = o1.dy; a.lddy1 = o1.lddy; a.dgamma1 = o1.dgamma; a.dbeta1 = o1.dbeta;
+    a.y2 = o2.y; a.ld2 = o2.ld; a.g2 = o2.g; a.dy2 = o2.dy; a.lddy2 = o2.lddy; a.dgamma2 = o2.dgamma; a.dbeta2 = o2.dbeta; a.acc2 = acc2;
+    a.cs = cs; a.ss = ss; a.z = z; a.ldz = ldz; a.dz = dz; a.eps = eps;
+    set_dropout(a, c, dropout);
+    return a;
+}
+
+// One GroupNorm pass: which kernels take it, and their launches.  A (sample, group) slab that fits one block goes to the one-launch
+// small-tensor kernels unless the pass drops out, its two GroupNorms (G2 != 0) group differently or it is mode 2 (per-sample
+// BatchNorm); everything else runs statistics -> finalize -> apply forward and reduce -> finalize (+ parameter gradients) -> apply backward.
+bool gn_small_rule(int mode, int R, int C, int G1, int G2, bool dropout) {
     static const bool no_small = p3d_tune_env("P3D_NO_GN_SMALL") != nullptr;
-    return !no_small && !dropout && p3d_gn_small_ok(R, C, G);
+    return !no_small && mode != 2 && !dropout && p3d_gn_small_ok(R, C, G1) && (!G2 || G2 == G1);
 }
 void gn_pass_forward(const Ctx& c, const GnApplyArgs& a, bool small) {
     const double tens = (double)a.M * a.C * 4.0;
@@ -590,6 +622,22 @@ void cbam_scratch_args(CbamArgs& a, float* b, int64_t M) {
     a.dO = b + L.dO;
 }
 
+// CbamArgs on raw pointers (x and dx: rows of ld floats; w, dw: k0, b0, k1, b1, k7 and their gradients), and the two launches.
+CbamArgs cbam_args(int N, int D, int H, int W, int C, const float* x, int ld, const float* const w[5], int chunks, float* scratch,
+                   const float* dout, float* dx, int accx, float* const dw[5]) {
+    CbamArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x; a.ld = ld; a.N = N; a.D = D; a.H = H; a.W = W; a.C = C; a.Ch = C / 8;
+    a.k0 = w[0]; a.b0 = w[1]; a.k1 = w[2]; a.b1 = w[3]; a.k7 = w[4];
+    a.chunks = chunks; a.dout = dout; a.dx = dx; a.lddx = ld; a.accx = accx;
+    cbam_scratch_args(a, scratch, (int64_t)N * D * H * W);
+    a.dk0 = dw[0]; a.db0 = dw[1]; a.dk1 = dw[2]; a.db1 = dw[3]; a.dk7 = dw[4];
+    return a;
+}
+double cbam_elems(const CbamArgs& a) { return (double)a.N * a.D * a.H * a.W * a.C; }
+void cbam_pass_forward(const Ctx& c, const CbamArgs& a) { launch(c, "cbam_forward(5 kernels)", 0, 8.0 * cbam_elems(a), [&]() { return p3d_cbam_forward(a, c.s); }); }
+void cbam_pass_backward(const Ctx& c, const CbamArgs& a) { launch(c, "cbam_backward(6 kernels)", 0, 28.0 * cbam_elems(a), [&]() { return p3d_cbam_backward(a, c.s); }); }
+
 // Runs `f(side_ctx)` on the side stream after everything queued so far on the main stream.
 template <typename F>
 void on_side_stream(const Ctx& c, hipEvent_t ev, F&& f) {
@@ -689,6 +737,62 @@ PoolArgs pool_args(const ConvGeo& g, int N, int C, int ldx, int ldy) {
     a.pd = g.pad[0]; a.ph = g.pad[1]; a.pw = g.pad[2];
     return a;
 }
+
+// The pool's launches (maxpool() in net_ops.inc, and the max_pool3d entry points).  The backward reads the forward's output (disjoint
+// windows: the first cell equal to the maximum) or its arg-max table (overlapping windows: a gather); returns the kernel it launched.
+double pool_bytes(const PoolArgs& a) { return 4.0 * ((int64_t)a.N * a.Di * a.Hi * a.Wi + (int64_t)a.N * a.Do * a.Ho * a.Wo) * a.C; }
+void pool_forward(const Ctx& c, const PoolArgs& a) { launch(c, "maxpool_fwd_kernel", 0, pool_bytes(a), [&]() { return p3d_maxpool_fwd(a, c.s); }); }
+const char* pool_backward(const Ctx& c, const PoolArgs& a, int accumulate) {
+    if (p3d_maxpool_disjoint(a)) {
+        launch(c, "maxpool_bwd_disjoint_kernel", 0, pool_bytes(a) * 2, [&]() { return p3d_maxpool_bwd_disjoint(a, accumulate, c.s); });
+        return "maxpool_bwd_disjoint_kernel";
+    }
+    if (!a.idx) throw P3dError("max-pool with overlapping windows was built without its arg-max table");
+    launch(c, "maxpool_bwd_gather_kernel", 0, pool_bytes(a) * 2, [&]() { return p3d_maxpool_bwd_gather(a, accumulate, c.s); });
+    return "maxpool_bwd_gather_kernel";
+}
+
+// The output head (head() in net_graphs.inc, and the test hook p3d_debug_head): HeadArgs on raw pointers, and the three launches.
+// transpose: the stride-2 conv3d_transpose head (p3d_head_*), else the stride-1 conv (p3d_headc_*); path, done: as the launchers'.
+HeadArgs head_args(const float* x, int N, int D, int H, int W, int C, const float* k, const float* bias, float* logits, float* pred,
+                   int sigmoid, const float* dlogits, float* dx, float* dk, float* dbias) {
+    HeadArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x; a.N = N; a.D = D; a.H = H; a.W = W; a.C = C;
+    a.k = k; a.bias = bias; a.logits = logits; a.pred = pred; a.sigmoid = sigmoid;
+    a.dlogits = dlogits; a.dx = dx; a.dk = dk; a.dbias = dbias;
+    return a;
+}
+LaunchDesc head_desc(const HeadArgs& a, bool transpose, const char* kernel, const char* kernel_stride1) {
+    const int64_t rows = (int64_t)a.N * a.D * a.H * a.W, out_rows = transpose ? 8 * rows : rows;
+    return {transpose ? kernel : kernel_stride1, 2.0 * rows * 27 * a.C, 4.0 * (rows * (double)a.C + 2.0 * out_rows)};
+}
+void head_forward(const Ctx& c, const HeadArgs& a, bool transpose, int path = P3D_HEAD_RULE, HeadLaunch* done = nullptr) {
+    const LaunchDesc d = head_desc(a, transpose, "head_fwd_kernel", "headc_fwd_kernel");
+    launch(c, d.kernel, d.flops, d.bytes, [&]() { return transpose ? p3d_head_fwd(a, c.s, path, done) : p3d_headc_fwd(a, c.s, done); });
+}
+void head_filter_gradient(const Ctx& c, const HeadArgs& a, bool transpose, int path = P3D_HEAD_RULE, HeadLaunch* done = nullptr) {
+    const LaunchDesc d = head_desc(a, transpose, "head_bwd_filter_kernel", "headc_bwd_filter_kernel");
+    launch(c, d.kernel, d.flops, d.bytes, [&]() { return transpose ? p3d_head_bwd_filter(a, c.s, path, done) : p3d_headc_bwd_filter(a, c.s, done); });
+}
+void head_input_gradient(const Ctx& c, const HeadArgs& a, bool transpose) {      // (one kernel each: nothing to force or report)
+    const LaunchDesc d = head_desc(a, transpose, "head_bwd_input_kernel", "headc_bwd_input_kernel");
+    launch(c, d.kernel, d.flops, d.bytes, [&]() { return transpose ? p3d_head_bwd_input(a, c.s) : p3d_headc_bwd_input(a, c.s); });
+}
+
+// The attention block's mixing pass (attn_run in net_graphs.inc, and the test hook p3d_debug_attn_mix): AttnMixArgs on raw pointers
+// (z / dz, r / dr and x / dx share their row strides), and the launches.
+AttnMixArgs attn_mix_args(int64_t M, int C, const float* r, int ldr, const float* x, int ldx, const float* gamma, float* z, int ldz,
+                          const float* dz, float* dr, float* dx, int accx, float* dgamma, const Ctx& c, bool dropout) {
+    AttnMixArgs a;
+    memset(&a, 0, sizeof(a));
+    a.M = M; a.C = C; a.r = r; a.ldr = ldr; a.x = x; a.ldx = ldx; a.gamma = gamma;
+    a.z = z; a.ldz = ldz; a.dz = dz; a.dr = dr; a.dx = dx; a.accx = accx; a.dgamma = dgamma;
+    set_dropout(a, c, dropout);
+    return a;
+}
+void attn_mix_forward(const Ctx& c, const AttnMixArgs& a) { launch(c, "mix_fwd_kernel", 0, 4.0 * 3 * a.M * a.C, [&]() { return p3d_attn_mix_fwd(a, c.s); }); }
+void attn_mix_backward(const Ctx& c, const AttnMixArgs& a) { launch(c, "mix_bwd_kernel", 0, 4.0 * 5 * a.M * a.C, [&]() { return p3d_attn_mix_bwd(a, c.s); }); }
 
 inline int pmod(int a, int m) { int r = a % m; return r < 0 ? r + m : r; }
 

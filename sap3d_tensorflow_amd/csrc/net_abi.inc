@@ -1117,48 +1117,33 @@ int p3d_debug_gn_pass(int device, int mode, int N, int R, int C, int G, float ep
     if (!(drop_rate >= 0.f && drop_rate < 1.f)) throw P3dError("gn_pass: dropout rate must be in [0, 1)");
     const int64_t M = (int64_t)N * R, nc = (int64_t)N * C;
     const bool dropout = drop_rate > 0.f;
-    // the network's rule (gn_small_rule; mode 2, the per-sample BatchNorm of p3d_predict_windows, never takes the small
-    // kernels), or the forced path -- which must be one the kernels take
+    // the network's rule, or the forced path -- which must be one the kernels take
     const bool small_ok = mode != 2 && !dropout && p3d_gn_small_ok(R, C, G);
-    const int taken = path ? path : ((mode != 2 && gn_small_rule(R, C, G, dropout)) ? 1 : 2);
+    const int taken = path ? path : (gn_small_rule(mode, R, C, G, two ? G : 0, dropout) ? 1 : 2);
     if (taken == 1 && !small_ok) throw P3dError("gn_pass: the small-tensor path does not take this shape");
     DevBuf y1b(M * ld1, y1), y2b(has2 ? M * ld2 : 1, has2 ? y2 : nullptr), zb(M * ldz, z), dzb(bwd ? M * ldz : 1, bwd ? dz : nullptr);
     DevBuf g1b(M * ld1, dy1), g2b(bwd && d2 ? M * ld2 : 1, bwd && d2 ? dy2 : nullptr);
     DevBuf prm(2 * (int64_t)C * ngn, params), grd(2 * (int64_t)C * ngn, grads), tab(7 * nc * ngn);
     DevBuf csb(mode == 6 ? nc : 1, mode == 6 ? cs : nullptr), ssb(mode == 6 ? M : 1, mode == 6 ? ss : nullptr);
     DevBuf fsums(4 * nc * ngn), bsums(4 * nc * ngn);           // [gn][N][C][2] doubles each: forward, backward (as the arenas)
-    auto params_of = [&](int q, bool backward) {
-        GnParams p;
-        memset(&p, 0, sizeof(p));
-        p.gamma = prm.p + (int64_t)q * 2 * C; p.beta = p.gamma + C;
-        p.sums = reinterpret_cast<double*>(backward ? bsums.p : fsums.p) + (int64_t)q * 2 * nc;
-        float* t = tab.p + (int64_t)q * 7 * nc;
-        p.scale = t; p.shift = t + nc; p.mean = t + 2 * nc; p.invstd = t + 3 * nc; p.coef = t + 4 * nc;
-        p.C = C; p.G = G;
-        return p;
-    };
-    GnApplyArgs a;      // as gn_apply's mk (net_gn.inc) builds it
-    memset(&a, 0, sizeof(a));
-    a.mode = mode; a.M = M; a.R = R; a.C = C;
-    a.y1 = y1b.p; a.ld1 = ld1; a.g1 = params_of(0, false);
-    if (has2) { a.y2 = y2b.p; a.ld2 = ld2; }
-    if (two) a.g2 = params_of(1, false);
-    if (mode == 6) { a.cs = csb.p; a.ss = ssb.p; }
-    a.z = zb.p; a.ldz = ldz; a.dz = dzb.p;
-    a.dy1 = g1b.p; a.lddy1 = ld1;
-    if (d2) { a.dy2 = g2b.p; a.lddy2 = ld2; a.acc2 = acc2 ? 1 : 0; }
-    if (dropout) { a.drop_rate = drop_rate; a.drop_scale = 1.f / (1.f - drop_rate); a.seed = seed; }
-    a.eps = eps;
-    a.dgamma1 = grd.p; a.dbeta1 = grd.p + C;
-    if (two) { a.dgamma2 = grd.p + 2 * C; a.dbeta2 = grd.p + 3 * C; }
     Ctx c;
-    gn_pass_forward(c, a, taken == 1);
-    if (bwd) {
-        GnApplyArgs b = a;
-        b.g1 = params_of(0, true);
-        if (two) b.g2 = params_of(1, true);
-        gn_pass_backward(c, b, taken == 1);
-    }
+    c.training = true; c.drop = drop_rate; c.seed = seed;
+    auto args = [&](bool backward) {
+        GnOperand o[2];
+        o[0].y = y1b.p; o[0].ld = ld1; o[0].dy = g1b.p; o[0].lddy = ld1;
+        if (has2) { o[1].y = y2b.p; o[1].ld = ld2; }
+        if (d2) { o[1].dy = g2b.p; o[1].lddy = ld2; }
+        for (int q = 0; q < ngn; ++q) {
+            float* const w = prm.p + (int64_t)q * 2 * C; float* const dw = grd.p + (int64_t)q * 2 * C;
+            double* const sums = reinterpret_cast<double*>(backward ? bsums.p : fsums.p) + (int64_t)q * 2 * nc;
+            o[q].g = gn_layout(w, w + C, sums, tab.p + (int64_t)q * 7 * nc, N, C, G);
+            o[q].dgamma = dw; o[q].dbeta = dw + C;
+        }
+        return gn_apply_args(mode, M, R, C, eps, o[0], o[1], (d2 && acc2) ? 1 : 0, mode == 6 ? csb.p : nullptr, mode == 6 ? ssb.p : nullptr,
+                             zb.p, ldz, dzb.p, c, dropout);
+    };
+    gn_pass_forward(c, args(false), taken == 1);
+    if (bwd) gn_pass_backward(c, args(true), taken == 1);
     info[0] = taken;
     zb.get(z, M * ldz);
     if (bwd) {
@@ -1172,8 +1157,8 @@ int p3d_debug_gn_pass(int device, int mode, int N, int R, int C, int G, float ep
     API_END
 }
 
-// CBAM forward and backward (cbam() in net_gn.inc) on raw inputs: p3d_cbam_forward / p3d_cbam_backward on a scratch laid out by
-// cbam_scratch_args, with the network's chunk rule unless chunks > 0.
+// CBAM forward and backward on raw inputs, through the argument builder and the launches cbam() (net_gn.inc) itself uses, with the
+// network's chunk rule unless chunks > 0.
 int p3d_debug_cbam(int device, int N, int D, int H, int W, int C, const float* x, int ld, const float* k0, const float* b0,
                    const float* k1, const float* b1, const float* k7, int chunks, const float* dout, int accx, float* cs, float* sp,
                    float* ss, float* dx, float* pgrads, int* info) {
@@ -1186,22 +1171,17 @@ int p3d_debug_cbam(int device, int N, int D, int H, int W, int C, const float* x
     const int R = D * H * W, Ch = C / 8;
     const int64_t M = (int64_t)N * R, nc = (int64_t)N * C;
     const int64_t ng = (int64_t)C * Ch * 2 + Ch + C + 686;      // dk0, db0, dk1, db1, dk7
-    CbamArgs a;
-    memset(&a, 0, sizeof(a));
-    a.N = N; a.D = D; a.H = H; a.W = W; a.C = C; a.Ch = Ch;
-    a.chunks = chunks ? chunks : cbam_chunks(R);
-    const CbamLayout L = cbam_layout(N, M, C, a.chunks);
+    const int nchunks = chunks ? chunks : cbam_chunks(R);
+    const CbamLayout L = cbam_layout(N, M, C, nchunks);
     DevBuf xb(M * ld, x), k0b((int64_t)C * Ch, k0), b0b(Ch, b0), k1b((int64_t)Ch * C, k1), b1b(C, b1), k7b(686, k7);
     DevBuf doutb(M * C, dout), dxb(M * ld, dx), grd(ng, pgrads), scratch(L.total);
-    a.x = xb.p; a.ld = ld;
-    a.k0 = k0b.p; a.b0 = b0b.p; a.k1 = k1b.p; a.b1 = b1b.p; a.k7 = k7b.p;
-    cbam_scratch_args(a, scratch.p, M);
-    a.dout = doutb.p;
-    a.dx = dxb.p; a.lddx = ld; a.accx = accx ? 1 : 0;
-    a.dk0 = grd.p; a.db0 = a.dk0 + (int64_t)C * Ch; a.dk1 = a.db0 + Ch; a.db1 = a.dk1 + (int64_t)Ch * C; a.dk7 = a.db1 + C;
+    const float* const w[5] = {k0b.p, b0b.p, k1b.p, b1b.p, k7b.p};
+    float* const dk0 = grd.p; float* const db0 = dk0 + (int64_t)C * Ch; float* const dk1 = db0 + Ch; float* const db1 = dk1 + (int64_t)Ch * C;
+    float* const dw[5] = {dk0, db0, dk1, db1, db1 + C};
+    const CbamArgs a = cbam_args(N, D, H, W, C, xb.p, ld, w, nchunks, scratch.p, doutb.p, dxb.p, accx ? 1 : 0, dw);
     Ctx c;
-    HIPCHECK(p3d_cbam_forward(a, c.s));
-    HIPCHECK(p3d_cbam_backward(a, c.s));
+    cbam_pass_forward(c, a);
+    cbam_pass_backward(c, a);
     std::vector<float> h((size_t)L.total);
     scratch.get(h.data(), L.total);
     std::copy(h.begin() + L.cs, h.begin() + L.cs + nc, cs);
@@ -1213,8 +1193,8 @@ int p3d_debug_cbam(int device, int N, int D, int H, int W, int C, const float* x
     API_END
 }
 
-// The output head (head() in net_graphs.inc) on raw inputs: forward, input gradient and filter gradient through the launchers the
-// network calls, on their rule or on a forced kernel.
+// The output head on raw inputs: forward, filter gradient and input gradient through the argument builder and the launches head()
+// (net_graphs.inc) itself uses, on their rule or on a forced kernel.
 int p3d_debug_head(int device, int transpose, int N, int D, int H, int W, int C, const float* x, const float* k, const float* bias,
                    int sigmoid, const float* dlogits, int fwd_path, int filter_path, float* logits, float* pred, float* dx, float* dk,
                    float* dbias, int* info) {
@@ -1227,22 +1207,12 @@ int p3d_debug_head(int device, int transpose, int N, int D, int H, int W, int C,
     const int64_t M = (int64_t)N * D * H * W, Mo = M * up * up * up;
     DevBuf xb(M * C, x), kb(27 * (int64_t)C, k), bb(1, bias), lb(Mo), pb(Mo), dlb(Mo, dlogits), dxb(M * C), dkb(27 * (int64_t)C, dk),
         dbb(1, dbias);
-    HeadArgs a;         // as head()'s mk builds it
-    memset(&a, 0, sizeof(a));
-    a.x = xb.p; a.N = N; a.D = D; a.H = H; a.W = W; a.C = C;
-    a.k = kb.p; a.bias = bb.p; a.logits = lb.p; a.pred = pb.p; a.sigmoid = sigmoid ? 1 : 0;
-    a.dlogits = dlb.p; a.dx = dxb.p; a.dk = dkb.p; a.dbias = dbb.p;
+    const HeadArgs a = head_args(xb.p, N, D, H, W, C, kb.p, bb.p, lb.p, pb.p, sigmoid ? 1 : 0, dlb.p, dxb.p, dkb.p, dbb.p);
     HeadLaunch f{0, 0}, w{0, 0};
-    hipStream_t s = nullptr;
-    if (transpose) {
-        HIPCHECK(p3d_head_fwd(a, s, fwd_path, &f));
-        HIPCHECK(p3d_head_bwd_filter(a, s, filter_path, &w));
-        HIPCHECK(p3d_head_bwd_input(a, s));
-    } else {
-        HIPCHECK(p3d_headc_fwd(a, s, &f));
-        HIPCHECK(p3d_headc_bwd_filter(a, s, &w));
-        HIPCHECK(p3d_headc_bwd_input(a, s));
-    }
+    Ctx c;
+    head_forward(c, a, transpose != 0, fwd_path, &f);
+    head_filter_gradient(c, a, transpose != 0, filter_path, &w);
+    head_input_gradient(c, a, transpose != 0);
     lb.get(logits, Mo);
     pb.get(pred, Mo);
     dxb.get(dx, M * C);
@@ -1460,16 +1430,45 @@ int p3d_op_conv3d_transpose(int device, const float* x, const int64_t xs[5], con
     API_END
 }
 
+namespace {
+// tf.nn.max_pool3d SAME and its gradient on host arrays whose rows of ldx / ldy floats hold the xs[4] channels at column offx / offy,
+// through maxpool()'s launches (net_ops.inc).  y0 / dx0: what the output rows hold before (null: zeros; a slice keeps its other columns).
+void max_pool3d_on_host_arrays(const float* x, int ldx, int offx, const int64_t xs[5], const int k[3], const int s[3], const float* y0,
+                               float* y, int ldy, int offy) {
+    const ConvGeo g = make_geo((int)xs[1], (int)xs[2], (int)xs[3], k, s);
+    const int64_t rin = xs[0] * xs[1] * xs[2] * xs[3], rout = xs[0] * g.O[0] * g.O[1] * g.O[2];
+    DevBuf dx(rin * ldx, x), dy(rout * ldy, y0);
+    PoolArgs a = pool_args(g, (int)xs[0], (int)xs[4], ldx, ldy);
+    a.x = dx.p + offx; a.y = dy.p + offy;
+    pool_forward(Ctx(), a);
+    dy.get(y, rout * ldy);
+}
+const char* max_pool3d_grad_on_host_arrays(const float* x, int ldx, int offx, const int64_t xs[5], const int k[3], const int s[3],
+                                           const float* dyh, int ldy, int offy, int accumulate, const float* dx0, float* dxh) {
+    const ConvGeo g = make_geo((int)xs[1], (int)xs[2], (int)xs[3], k, s);
+    const int C = (int)xs[4];
+    const int64_t rin = xs[0] * xs[1] * xs[2] * xs[3], rout = xs[0] * g.O[0] * g.O[1] * g.O[2];
+    DevBuf dx(rin * ldx, x), dy(rout * ldy, dyh), dg(rin * ldx, dx0), yy(rout * ldy), tab(rout * (C / 4));
+    PoolArgs a = pool_args(g, (int)xs[0], C, ldx, ldy);
+    a.x = dx.p + offx; a.dy = dy.p + offy; a.dx = dg.p + offx; a.y = yy.p + offy;
+    if (!p3d_maxpool_disjoint(a)) a.idx = reinterpret_cast<unsigned*>(tab.p);
+    pool_forward(Ctx(), a);
+    const char* const kernel = pool_backward(Ctx(), a, accumulate);
+    dg.get(dxh, rin * ldx);
+    return kernel;
+}
+// tf.nn.bias_add's gradient: dbias = db0 (null: zeros) + the column sums of `channels` columns at column `off` of rows of ld floats
+void bias_add_grad_on_host_arrays(const float* dyh, int64_t rows, int channels, int ld, int off, const float* db0, float* dbias) {
+    DevBuf dy(rows * ld, dyh), db(channels, db0);
+    if (rows > 0) HIPCHECK(p3d_colsum(dy.p + off, ld, (long)rows, channels, db.p, nullptr));
+    db.get(dbias, channels);
+}
+}  // namespace
+
 int p3d_op_max_pool3d(int device, const float* x, const int64_t xs[5], const int k[3], const int s[3], float* y) {
     API_BEGIN
     HIPCHECK(hipSetDevice(device));
-    const ConvGeo g = make_geo((int)xs[1], (int)xs[2], (int)xs[3], k, s);
-    const int64_t ny = xs[0] * g.O[0] * g.O[1] * g.O[2] * xs[4];
-    DevBuf dx(prod5(xs), x), dy(ny);
-    PoolArgs a = pool_args(g, (int)xs[0], (int)xs[4], (int)xs[4], (int)xs[4]);
-    a.x = dx.p; a.y = dy.p;
-    HIPCHECK(p3d_maxpool_fwd(a, nullptr));
-    dy.get(y, ny);
+    max_pool3d_on_host_arrays(x, (int)xs[4], 0, xs, k, s, nullptr, y, (int)xs[4], 0);
     API_END
 }
 
@@ -1477,19 +1476,8 @@ int p3d_op_max_pool3d_grad(int device, const float* x, const int64_t xs[5], cons
                            float* dxh) {
     API_BEGIN
     HIPCHECK(hipSetDevice(device));
-    const ConvGeo g = make_geo((int)xs[1], (int)xs[2], (int)xs[3], k, s);
-    const int64_t ny = xs[0] * g.O[0] * g.O[1] * g.O[2] * xs[4];
     if (xs[4] % 4) throw P3dError("max_pool3d_grad needs a channel count that is a multiple of 4");
-    DevBuf dx(prod5(xs), x), dy(ny, dyh), dg(prod5(xs)), yy(ny), tab(ny / 4);
-    PoolArgs a = pool_args(g, (int)xs[0], (int)xs[4], (int)xs[4], (int)xs[4]);
-    a.x = dx.p; a.dy = dy.p; a.dx = dg.p; a.y = yy.p;
-    const bool disjoint = p3d_maxpool_disjoint(a);
-    if (!disjoint) a.idx = reinterpret_cast<unsigned*>(tab.p);
-    HIPCHECK(p3d_maxpool_fwd(a, nullptr));       // the backward kernels read the forward's output (disjoint windows: the first
-                                                 // cell equal to the maximum) or its arg-max table (overlapping windows: a gather)
-    if (disjoint) HIPCHECK(p3d_maxpool_bwd_disjoint(a, 0, nullptr));
-    else HIPCHECK(p3d_maxpool_bwd_gather(a, 0, nullptr));
-    dg.get(dxh, prod5(xs));
+    max_pool3d_grad_on_host_arrays(x, (int)xs[4], 0, xs, k, s, dyh, (int)xs[4], 0, 0, nullptr, dxh);
     API_END
 }
 
@@ -1498,9 +1486,7 @@ int p3d_op_bias_add_grad(int device, const float* dyh, int64_t rows, int channel
     if (!dyh || !dbias) throw P3dError("null argument");
     if (rows < 0 || channels < 1) throw P3dError("bias_add_grad needs rows >= 0 and channels >= 1");
     HIPCHECK(hipSetDevice(device));
-    DevBuf dy(rows * channels, dyh), db(channels);
-    if (rows > 0) HIPCHECK(p3d_colsum(dy.p, channels, (long)rows, channels, db.p, nullptr));
-    db.get(dbias, channels);
+    bias_add_grad_on_host_arrays(dyh, rows, channels, channels, 0, nullptr, dbias);
     API_END
 }
 
@@ -1631,16 +1617,9 @@ int p3d_debug_max_pool3d(int device, const float* x, int ldx, int offx, const in
     API_BEGIN
     HIPCHECK(hipSetDevice(device));
     if (!x || !xs || !k || !s || !y) throw P3dError("null argument");
-    const ConvGeo g = make_geo((int)xs[1], (int)xs[2], (int)xs[3], k, s);
-    const int C = (int)xs[4];
-    check_slice("max_pool3d (x)", ldx, offx, C);
-    check_slice("max_pool3d (y)", ldy, offy, C);
-    const int64_t rin = xs[0] * xs[1] * xs[2] * xs[3], rout = xs[0] * g.O[0] * g.O[1] * g.O[2];
-    DevBuf dx(rin * ldx, x), dy(rout * ldy, y);
-    PoolArgs a = pool_args(g, (int)xs[0], C, ldx, ldy);
-    a.x = dx.p + offx; a.y = dy.p + offy;
-    HIPCHECK(p3d_maxpool_fwd(a, nullptr));
-    dy.get(y, rout * ldy);
+    check_slice("max_pool3d (x)", ldx, offx, (int)xs[4]);
+    check_slice("max_pool3d (y)", ldy, offy, (int)xs[4]);
+    max_pool3d_on_host_arrays(x, ldx, offx, xs, k, s, y, y, ldy, offy);
     API_END
 }
 
@@ -1649,21 +1628,10 @@ int p3d_debug_max_pool3d_grad(int device, const float* x, int ldx, int offx, con
     API_BEGIN
     HIPCHECK(hipSetDevice(device));
     if (!x || !xs || !k || !s || !dyh || !dxh) throw P3dError("null argument");
-    const ConvGeo g = make_geo((int)xs[1], (int)xs[2], (int)xs[3], k, s);
-    const int C = (int)xs[4];
-    check_slice("max_pool3d_grad (x, dx)", ldx, offx, C);
-    check_slice("max_pool3d_grad (y, dy)", ldy, offy, C);
-    const int64_t rin = xs[0] * xs[1] * xs[2] * xs[3], rout = xs[0] * g.O[0] * g.O[1] * g.O[2];
-    DevBuf dx(rin * ldx, x), dy(rout * ldy, dyh), dg(rin * ldx, dxh), yy(rout * ldy), tab(rout * (C / 4));
-    PoolArgs a = pool_args(g, (int)xs[0], C, ldx, ldy);
-    a.x = dx.p + offx; a.dy = dy.p + offy; a.dx = dg.p + offx; a.y = yy.p + offy;
-    const bool disjoint = p3d_maxpool_disjoint(a);
-    if (!disjoint) a.idx = reinterpret_cast<unsigned*>(tab.p);
-    HIPCHECK(p3d_maxpool_fwd(a, nullptr));
-    if (disjoint) HIPCHECK(p3d_maxpool_bwd_disjoint(a, accumulate ? 1 : 0, nullptr));
-    else HIPCHECK(p3d_maxpool_bwd_gather(a, accumulate ? 1 : 0, nullptr));
-    if (kernel) *kernel = disjoint ? "maxpool_bwd_disjoint_kernel" : "maxpool_bwd_gather_kernel";
-    dg.get(dxh, rin * ldx);
+    check_slice("max_pool3d_grad (x, dx)", ldx, offx, (int)xs[4]);
+    check_slice("max_pool3d_grad (y, dy)", ldy, offy, (int)xs[4]);
+    const char* const ran = max_pool3d_grad_on_host_arrays(x, ldx, offx, xs, k, s, dyh, ldy, offy, accumulate ? 1 : 0, dxh, dxh);
+    if (kernel) *kernel = ran;
     API_END
 }
 
@@ -1672,9 +1640,7 @@ int p3d_debug_bias_add_grad(int device, const float* dyh, int64_t rows, int chan
     if (!dyh || !dbias) throw P3dError("null argument");
     if (rows < 0 || channels < 1 || off < 0 || ld < off + channels) throw P3dError("bias_add_grad needs rows >= 0, channels >= 1 and offset + channels <= row length");
     HIPCHECK(hipSetDevice(device));
-    DevBuf dy(rows * ld, dyh), db(channels, dbias);
-    if (rows > 0) HIPCHECK(p3d_colsum(dy.p + off, ld, (long)rows, channels, db.p, nullptr));
-    db.get(dbias, channels);
+    bias_add_grad_on_host_arrays(dyh, rows, channels, ld, off, dbias, dbias);
     API_END
 }
 
@@ -1803,20 +1769,17 @@ int p3d_debug_attn_mix(int device, int64_t M, int C, const float* r, int ldr, in
     DevBuf dr_in(M * ldr, r), dx_in(M * ldx, x), dzz(M * ldz, z), dgm(1, &gamma);
     DevBuf dseed(2);
     HIPCHECK(copy_now(dseed.p, &seed, sizeof(seed), hipMemcpyHostToDevice, nullptr));
-    AttnMixArgs a;
-    memset(&a, 0, sizeof(a));
-    a.M = M; a.C = C; a.r = dr_in.p + offr; a.ldr = ldr; a.x = dx_in.p + offx; a.ldx = ldx; a.gamma = dgm.p;
-    a.z = dzz.p + offz; a.ldz = ldz;
-    if (drop_rate > 0.f) {         // (attn_run: the block's dropout, with the step's seed as an argument or in device memory)
-        a.drop_rate = drop_rate; a.drop_scale = 1.f / (1.f - drop_rate);
-        if (seed_dev) a.seed_dev = reinterpret_cast<const unsigned long long*>(dseed.p); else a.seed = seed;
-    }
-    HIPCHECK(p3d_attn_mix_fwd(a, nullptr));
+    Ctx c;         // (attn_run: the block's dropout, with the step's seed as an argument or in device memory)
+    c.training = true; c.drop = drop_rate;
+    if (seed_dev) c.seed_dev = reinterpret_cast<const unsigned long long*>(dseed.p); else c.seed = seed;
+    auto args = [&](const float* g_z, float* g_r, float* g_x, float* g_gm) {
+        return attn_mix_args(M, C, dr_in.p + offr, ldr, dx_in.p + offx, ldx, dgm.p, dzz.p + offz, ldz, g_z, g_r, g_x, accx ? 1 : 0, g_gm, c, true);
+    };
+    attn_mix_forward(c, args(nullptr, nullptr, nullptr, nullptr));
     dzz.get(z, M * ldz);
     if (dz) {
         DevBuf g_z(M * ldz, dz), g_r(M * ldr, dr), g_x(M * ldx, dx), g_gm(1, dgamma);
-        a.dz = g_z.p + offz; a.dr = g_r.p + offr; a.dx = g_x.p + offx; a.accx = accx ? 1 : 0; a.dgamma = g_gm.p;
-        HIPCHECK(p3d_attn_mix_bwd(a, nullptr));      // (part and counter: the launcher's, from the stream's scratch)
+        attn_mix_backward(c, args(g_z.p + offz, g_r.p + offr, g_x.p + offx, g_gm.p));      // (part and counter: the launcher's, from the stream's scratch)
         g_r.get(dr, M * ldr); g_x.get(dx, M * ldx); g_gm.get(dgamma, 1);
     }
     API_END

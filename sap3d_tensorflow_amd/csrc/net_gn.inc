@@ -15,14 +15,8 @@
         return g;
     }
     GnParams gn_params(GN* g, bool bwd) {
-        GnParams p;
-        const int64_t nc = (int64_t)g->N * g->C;
-        p.gamma = g->gamma->p; p.beta = g->beta->p;
-        p.sums = bwd ? red_arena + g->bsums_off : stats_arena + g->sums_off;
-        float* t = bnbuf + g->tab_off;
-        p.scale = t; p.shift = t + nc; p.mean = t + 2 * nc; p.invstd = t + 3 * nc; p.coef = t + 4 * nc;
-        p.C = g->C; p.G = g->G;
-        return p;
+        return gn_layout(g->gamma->p, g->beta->p, bwd ? red_arena + g->bsums_off : stats_arena + g->sums_off, bnbuf + g->tab_off,
+                         g->N, g->C, g->G);
     }
 
     // GroupNorm + fused activation pass (modes in gn.hip).  cb != null: mode 6, y2 is the CBAM input.
@@ -42,25 +36,16 @@
         op.owns = {g1->gamma, g1->beta};
         if (g2) { op.owns.push_back(g2->gamma); op.owns.push_back(g2->beta); }
         auto mk = [=](const Ctx& c, bool bwd) {
-            GnApplyArgs a;
-            memset(&a, 0, sizeof(a));
-            a.mode = mode; a.M = M; a.R = R; a.C = C;
-            a.y1 = y1->p; a.ld1 = y1->ld; a.g1 = gn_params(g1, bwd);
-            if (y2) { a.y2 = y2->p; a.ld2 = y2->ld; }
-            if (g2) a.g2 = gn_params(g2, bwd);
-            if (cb) { a.cs = bnbuf + cb->buf_off + cbam_cs_off(cb); a.ss = bnbuf + cb->buf_off + cbam_ss_off(cb); }
-            a.z = out->p; a.ldz = out->ld; a.dz = out->g;
-            a.dy1 = y1->g; a.lddy1 = y1->ld;
-            if (mode == 6) { a.dy2 = cb->dout; a.lddy2 = C; a.acc2 = 0; }
-            else if (y2) { a.dy2 = y2->g; a.lddy2 = y2->ld; a.acc2 = *f2; }
-            if (dropout && c.training && c.drop > 0.f) { a.drop_rate = c.drop; a.drop_scale = 1.f / (1.f - c.drop); a.seed = c.seed; a.seed_dev = c.seed_dev; }
-            a.eps = 1e-5f;
-            a.dgamma1 = g1->gamma->g; a.dbeta1 = g1->beta->g;
-            if (g2) { a.dgamma2 = g2->gamma->g; a.dbeta2 = g2->beta->g; }
-            return a;
+            const GnOperand o1{y1->p, y1->ld, y1->g, y1->ld, gn_params(g1, bwd), g1->gamma->g, g1->beta->g};
+            GnOperand o2;
+            if (y2) { o2.y = y2->p; o2.ld = y2->ld; o2.dy = y2->g; o2.lddy = y2->ld; }
+            if (mode == 6) { o2.dy = cb->dout; o2.lddy = C; }
+            if (g2) { o2.g = gn_params(g2, bwd); o2.dgamma = g2->gamma->g; o2.dbeta = g2->beta->g; }
+            const CbamArgs ca = cb ? cbam_site_args(cb) : CbamArgs();      // (its channel and spatial scales)
+            return gn_apply_args(mode, M, R, C, 1e-5f, o1, o2, f2 ? *f2 : 0, ca.cs, ca.ss, out->p, out->ld, out->g, c, dropout);
         };
         // small tensors (every GroupNorm of stage 3): one launch each way, see gn.hip
-        const bool small = gn_small_rule(R, C, g1->G, dropout) && (!g2 || g2->G == g1->G);
+        const bool small = gn_small_rule(mode, R, C, g1->G, g2 ? g2->G : 0, dropout);
         if (mode != 5) {
             // decisions of the last forward (p3d_debug_decision_*): the backward apply kernel on dz = 1 with a coefficient table
             // (k, c1, c2) = (1, 0, 0) -- what it writes is the gate itself.  scratch: 2 x [N][C][3] floats + the kernel's own needs
@@ -86,24 +71,12 @@
         return out;
     }
 
-    // scratch layout of one CBAM site inside bnbuf: cbam_layout (net.hip)
-    CbamLayout cbam_site_layout(CbamSite* cb) { return cbam_layout(cb->x->N, cb->x->rows(), cb->x->C, cb->chunks); }
-    int64_t cbam_cs_off(CbamSite* cb) { return cbam_site_layout(cb).cs; }
-    int64_t cbam_ss_off(CbamSite* cb) { return cbam_site_layout(cb).ss; }
-    int64_t cbam_total(CbamSite* cb) { return cbam_site_layout(cb).total; }
-
-    CbamArgs cbam_args(CbamSite* cb) {
-        CbamArgs a;
-        memset(&a, 0, sizeof(a));
+    CbamArgs cbam_site_args(CbamSite* cb) {
         Act* x = cb->x;
-        a.x = x->p; a.ld = x->ld; a.N = x->N; a.D = x->D; a.H = x->H; a.W = x->W; a.C = x->C; a.Ch = x->C / 8;
-        a.k0 = cb->k0->p; a.b0 = cb->b0->p; a.k1 = cb->k1->p; a.b1 = cb->b1->p; a.k7 = cb->k7->p;
-        a.chunks = cb->chunks;
-        cbam_scratch_args(a, bnbuf + cb->buf_off, x->rows());
-        a.dout = cb->dout;
-        a.dx = x->g; a.lddx = x->ld; a.accx = cb->xflag ? *cb->xflag : 0;
-        a.dk0 = cb->k0->g; a.db0 = cb->b0->g; a.dk1 = cb->k1->g; a.db1 = cb->b1->g; a.dk7 = cb->k7->g;
-        return a;
+        const float* const w[5] = {cb->k0->p, cb->b0->p, cb->k1->p, cb->b1->p, cb->k7->p};
+        float* const dw[5] = {cb->k0->g, cb->b0->g, cb->k1->g, cb->b1->g, cb->k7->g};
+        return cbam_args(x->N, x->D, x->H, x->W, x->C, x->p, x->ld, w, cb->chunks, bnbuf + cb->buf_off, cb->dout, x->g,
+                         cb->xflag ? *cb->xflag : 0, dw);
     }
 
     // residual = cbam_block(residual, 'cbam_<id>')  (gn/p3d_gn.py:175)
@@ -121,14 +94,14 @@
         cb->x = x;
         cb->chunks = cbam_chunks(x->D * x->H * x->W);
         cb->dout = dalloc<float>(x->rows() * C);
-        cb->buf_off = bnbuf_count; bnbuf_count += cbam_total(cb);
+        cb->buf_off = bnbuf_count; bnbuf_count += cbam_layout(x->N, x->rows(), C, cb->chunks).total;      // (net.hip)
         cb->xflag = consume(x);
         Op op;
         op.name = "block" + std::to_string(id) + "/cbam"; op.kind = "cbam";
         op.bytes = 4.0 * 2 * x->rows() * C; op.bbytes = 4.0 * 7 * x->rows() * C;
         op.owns = {cb->k0, cb->b0, cb->k1, cb->b1, cb->k7};
-        op.fwd = [=](const Ctx& c) { launch(c, "cbam_forward(5 kernels)", 0, 8.0 * x->rows() * C, [&]() { return p3d_cbam_forward(cbam_args(cb), c.s); }); };
-        op.bwd = [=](const Ctx& c) { launch(c, "cbam_backward(6 kernels)", 0, 28.0 * x->rows() * C, [&]() { return p3d_cbam_backward(cbam_args(cb), c.s); }); };
+        op.fwd = [=](const Ctx& c) { cbam_pass_forward(c, cbam_site_args(cb)); };
+        op.bwd = [=](const Ctx& c) { cbam_pass_backward(c, cbam_site_args(cb)); };
         ops.push_back(op);
         return cb;
     }

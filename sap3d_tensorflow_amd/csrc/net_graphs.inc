@@ -338,19 +338,11 @@
             op.bytes = 4.0 * 3 * x->rows() * ch; op.bbytes = 4.0 * 5 * x->rows() * ch;
             op.owns = {ap.gamma};
             Param* gamma = ap.gamma;
-            auto mk = [=](const Ctx& c) {
-                AttnMixArgs a;
-                memset(&a, 0, sizeof(a));
-                a.M = x->rows(); a.C = ch; a.r = r->p; a.ldr = r->ld; a.x = x->p; a.ldx = x->ld; a.gamma = gamma->p;
-                a.z = z->p; a.ldz = z->ld; a.dz = z->g; a.dr = r->g; a.dx = x->g; a.accx = *flx; a.dgamma = gamma->g;
-                if (dropout && c.training && c.drop > 0.f) { a.drop_rate = c.drop; a.drop_scale = 1.f / (1.f - c.drop); a.seed = c.seed; a.seed_dev = c.seed_dev; }
-                return a;
-            };
-            const double fb = op.bytes, bb = op.bbytes;
-            op.fwd = [=](const Ctx& c) { launch(c, "mix_fwd_kernel", 0, fb, [&]() { return p3d_attn_mix_fwd(mk(c), c.s); }); };
+            auto mk = [=](const Ctx& c) { return attn_mix_args(x->rows(), ch, r->p, r->ld, x->p, x->ld, gamma->p, z->p, z->ld, z->g, r->g, x->g, *flx, gamma->g, c, dropout); };
+            op.fwd = [=](const Ctx& c) { attn_mix_forward(c, mk(c)); };
             op.bwd = [=](const Ctx& c) {
                 if (*flr) throw P3dError("attention branch has one consumer");
-                launch(c, "mix_bwd_kernel", 0, bb, [&]() { return p3d_attn_mix_bwd(mk(c), c.s); });
+                attn_mix_backward(c, mk(c));
             };
             ops.push_back(op);
         }
@@ -462,29 +454,14 @@
         op.bytes = 4.0 * (x->rows() * (double)x->C + 2.0 * pred->rows());
         op.bflops = 2 * op.flops; op.bbytes = 4.0 * (3.0 * x->rows() * (double)x->C + 2.0 * pred->rows());
         op.owns = {k, bias};
-        auto mk = [=]() {
-            HeadArgs a;
-            memset(&a, 0, sizeof(a));
-            a.x = x->p; a.N = x->N; a.D = x->D; a.H = x->H; a.W = x->W; a.C = x->C;
-            a.k = k->p; a.bias = bias->p; a.logits = logits->p; a.pred = pred->p; a.sigmoid = with_sigmoid;
-            a.dlogits = d_dlogits; a.dx = x->g; a.dk = k->g; a.dbias = bias->g;
-            return a;
-        };
-        const double hf = op.flops, hb = op.bytes;
+        auto mk = [=]() { return head_args(x->p, x->N, x->D, x->H, x->W, x->C, k->p, bias->p, logits->p, pred->p, with_sigmoid, d_dlogits, x->g, k->g, bias->g); };
         hipEvent_t head_fork = new_fork_event();
-        op.fwd = [=](const Ctx& c) {
-            if (transpose) launch(c, "head_fwd_kernel", hf, hb, [&]() { return p3d_head_fwd(mk(), c.s); });
-            else launch(c, "headc_fwd_kernel", hf, hb, [&]() { return p3d_headc_fwd(mk(), c.s); });
-        };
+        op.fwd = [=](const Ctx& c) { head_forward(c, mk(), transpose); };
         op.bwd = [=](const Ctx& c) {
             if (*xflag) throw P3dError("head input gradient must be the first writer");
             // the filter gradient is a weight gradient like any other: side stream, off the critical path
-            on_side_stream(c, head_fork, [=](const Ctx& sc) {
-                if (transpose) launch(sc, "head_bwd_filter_kernel", hf, hb, [&]() { return p3d_head_bwd_filter(mk(), sc.s); });
-                else launch(sc, "headc_bwd_filter_kernel", hf, hb, [&]() { return p3d_headc_bwd_filter(mk(), sc.s); });
-            });
-            if (transpose) launch(c, "head_bwd_input_kernel", hf, hb, [&]() { return p3d_head_bwd_input(mk(), c.s); });
-            else launch(c, "headc_bwd_input_kernel", hf, hb, [&]() { return p3d_headc_bwd_input(mk(), c.s); });
+            on_side_stream(c, head_fork, [=](const Ctx& sc) { head_filter_gradient(sc, mk(), transpose); });
+            head_input_gradient(c, mk(), transpose);
         };
         ops.push_back(op);
     }

@@ -243,7 +243,7 @@
                 p.part[q] = statpart_arena + red_off + (int64_t)q * bwd_parts * 2 * C; p.coef[q] = bnbuf + coef_off + (int64_t)q * 2 * C;
             }
             p.nparts = bwd_parts;
-            if (dropout && c.training && c.drop > 0.f) { p.drop_rate = c.drop; p.drop_scale = 1.f / (1.f - c.drop); p.seed = c.seed; p.seed_dev = c.seed_dev; }
+            set_dropout(p, c, dropout);
             return p;
         };
         if (!fused_site) {
@@ -267,25 +267,20 @@
                 if (c.training || c.update_moving || dropout) throw P3dError("per-sample BatchNorm is an inference path");
                 ensure_per_sample_scratch();
                 auto norm = [&](BN* bn, Act* y, int slot) {
-                    GnParams p;
-                    memset(&p, 0, sizeof(p));
                     const int64_t nc = (int64_t)y->N * C;
-                    p.gamma = bn->gamma->p; p.beta = bn->beta->p; p.C = C; p.G = C;
-                    p.sums = ps_sums + (int64_t)slot * 2 * ps_nc;
-                    float* t = ps_tab + (int64_t)slot * 4 * ps_nc;
-                    p.scale = t; p.shift = t + nc; p.mean = t + 2 * nc; p.invstd = t + 3 * nc;
+                    GnParams p = gn_layout(bn->gamma->p, bn->beta->p, ps_sums + (int64_t)slot * 2 * ps_nc, ps_tab + (int64_t)slot * 4 * ps_nc,
+                                           y->N, C, C);
+                    p.coef = nullptr;      // a forward-only table: scale, shift, mean, invstd
                     if (!c.dry) HIPCHECK(hipMemsetAsync(p.sums, 0, (size_t)nc * 2 * sizeof(double), c.s));
                     launch(c, "gn_stats_kernel", 0, tens, [&]() { return p3d_gn_stats(y->p, y->ld, y->N, R, C, p.sums, c.s); });
                     launch(c, "gn_finalize_kernel", 0, 32.0 * nc, [&]() { return p3d_gn_finalize(p, y->N, R, 1e-3f, c.s); });
                     return p;
                 };
-                GnApplyArgs a;
-                memset(&a, 0, sizeof(a));
-                a.mode = mode; a.M = M; a.R = R; a.C = C;
-                a.y1 = y1->p; a.ld1 = y1->ld; a.g1 = norm(bn1, y1, 0);
-                if (y2) { a.y2 = y2->p; a.ld2 = y2->ld; }
-                if (two) a.g2 = norm(bn2, y2, 1);
-                a.z = out->p; a.ldz = out->ld;
+                GnOperand o1, o2;
+                o1.y = y1->p; o1.ld = y1->ld; o1.g = norm(bn1, y1, 0);
+                if (y2) { o2.y = y2->p; o2.ld = y2->ld; }
+                if (two) o2.g = norm(bn2, y2, 1);
+                const GnApplyArgs a = gn_apply_args(mode, M, R, C, 1e-3f, o1, o2, 0, nullptr, nullptr, out->p, out->ld, nullptr, c, false);
                 launch(c, "gn_apply_kernel(per-sample BN)", 0, tens * (y2 ? 3 : 2), [&]() { return p3d_gn_apply(a, c.s); });
                 return;
             }
@@ -329,11 +324,7 @@
         char* xflag = consume(x);
         // overlapping windows (pool1): the forward keeps the arg-max tap of every output so that the backward can gather
         unsigned* idx = nullptr;
-        {
-            const bool disjoint = g.k[0] == g.s[0] && g.k[1] == g.s[1] && g.k[2] == g.s[2] && !g.pad[0] && !g.pad[1] && !g.pad[2] &&
-                                  g.O[0] * g.s[0] == g.I[0] && g.O[1] * g.s[1] == g.I[1] && g.O[2] * g.s[2] == g.I[2];
-            if (!disjoint) idx = (unsigned*)dalloc<float>(out->rows() * (x->C / 4));
-        }
+        if (!p3d_maxpool_disjoint(pool_args(g, x->N, x->C, x->ld, out->ld))) idx = (unsigned*)dalloc<float>(out->rows() * (x->C / 4));
         Op op;
         op.name = opname; op.kind = "maxpool";
         op.bytes = 4.0 * (x->rows() + out->rows()) * x->C;
@@ -344,21 +335,9 @@
             a.x = x->p; a.y = out->p; a.dy = out->g; a.dx = x->g; a.idx = idx;
             return a;
         };
-        const double pool_bytes = op.bytes;
         op.dec_kind = "pool"; op.dec_act = x;
-        op.fwd = [=](const Ctx& c) { launch(c, "maxpool_fwd_kernel", 0, pool_bytes, [&]() { return p3d_maxpool_fwd(mk(), c.s); }); };
-        op.bwd = [=](const Ctx& c) {
-            const PoolArgs pa = mk();
-            if (p3d_maxpool_disjoint(pa)) {
-                launch(c, "maxpool_bwd_disjoint_kernel", 0, pool_bytes * 2, [&]() { return p3d_maxpool_bwd_disjoint(pa, *xflag, c.s); });
-                return;
-            }
-            if (pa.idx) {
-                launch(c, "maxpool_bwd_gather_kernel", 0, pool_bytes * 2, [&]() { return p3d_maxpool_bwd_gather(pa, *xflag, c.s); });
-                return;
-            }
-            throw P3dError("max-pool with overlapping windows was built without its arg-max table");
-        };
+        op.fwd = [=](const Ctx& c) { pool_forward(c, mk()); };
+        op.bwd = [=](const Ctx& c) { pool_backward(c, mk(), *xflag); };
         ops.push_back(op);
         return out;
     }

@@ -1,7 +1,8 @@
 """Every loss (smooth_l1, bce, l1, kld_cc) x optimiser (adam, momentum, momentum+nesterov, sgd) x regularisation (off, weight
-decay) on unet at the bench size (8 clips of 16x112x112), plus gn_p3d_decoder with L2 (the only net with L2 variables): three
-device-resident train steps from the same seed each, then one line with the combination, repr of the last loss and a SHA-256
-over every variable and optimiser slot.  Two builds of the library (P3D_LIB=<path>) that compute the same print the same lines."""
+decay) on unet at the bench size (8 clips of 16x112x112), plus gn_p3d_decoder with L2 (the only net with L2 variables), unet++ds
+(the attention blocks' mixing pass, the transposed head) and gn_p3d (every GroupNorm mode, CBAM): three device-resident train
+steps from the same seed each, then one line with the combination, repr of the last loss and a SHA-256 over every variable and
+optimiser slot.  Two builds of the library (P3D_LIB=<path>) that compute the same print the same lines."""
 import hashlib
 import os
 import sys
@@ -39,6 +40,8 @@ def main():
             for terms in ((), ("weightdecay",)):
                 run("unet", loss, opt, nesterov, terms)
     run("gn_p3d_decoder", "smooth_l1", "adam", False, ("l2",))
+    run("unet++ds", "smooth_l1", "adam", False, ())
+    run("gn_p3d", "smooth_l1", "adam", False, ())
 
 
 if __name__ == "__main__":
