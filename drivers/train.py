@@ -9,7 +9,9 @@ kld_cc (P3DSession.set_loss); `--regularization weightdecay | l2 | both` adds th
 terms the reference builds and leaves commented out of its loss (train.py:161, gn/train_p3d_gn_dataset.py:188-189;
 P3DSession.set_regularization); `--optimizer momentum | sgd` (with `--momentum`, `--nesterov`) fine-tunes with the
 optimisers the reference's --pretrain help names, and `--optimizer-state` saves and restores the optimiser's slots with the
-checkpoints (P3DSession.set_optimizer, save_checkpoint / restore optimizer_state).  The dataset loaders (dataflow.py,
+checkpoints (P3DSession.set_optimizer, save_checkpoint / restore optimizer_state); `--clip-norm X` clips every step's
+gradients by their global norm, as tf.clip_by_global_norm does, and prints the norm and the scale with the step
+(P3DSession.set_grad_clip).  The dataset loaders (dataflow.py,
 tensorpack, cv2) are out of scope: clips come either from `--data clips.npz` (arrays x [N,16,112,112,3] already normalised like
 dataflow.py:204-208, y [N,16,112,112]; raw uint8 frames go through sap3d_tensorflow_amd.dataflow.mapf_frames first) or
 are synthetic with the loader's value law.
@@ -83,6 +85,10 @@ def get_arguments():
     p.add_argument("--optimizer-state", action="store_true",
                    help="[addition] checkpoints hold the optimiser's slots under their TF names (<var>/Adam, <var>/Adam_1 and "
                         "beta1_power / beta2_power; <var>/Momentum), and --pretrain restores them: a run resumes its optimiser")
+    # Momentum and SGD multiply the raw gradient of a SUM loss by lr; TF-1 trainers pair them with tf.clip_by_global_norm
+    p.add_argument("--clip-norm", type=float, default=0.0,
+                   help="[addition] clip the gradients by their global norm to this value before the optimiser applies them "
+                        "(tf.clip_by_global_norm); inf reports the norm without clipping; 0 = off")
     return p.parse_args()
 
 
@@ -174,6 +180,12 @@ def main():
     except P3dError as e:
         sess.close()
         raise SystemExit("--regularization %s: %s" % (args.regularization, e))
+    if args.clip_norm != 0.0:
+        try:
+            sess.set_grad_clip(args.clip_norm)
+        except (P3dError, ValueError) as e:
+            sess.close()
+            raise SystemExit("--clip-norm %s: %s" % (args.clip_norm, e))
     model_dir = os.path.join("model", args.info)
     os.makedirs(model_dir, exist_ok=True)
     if args.pretrain:
@@ -184,10 +196,13 @@ def main():
     for xs, ys in batches(args, np.random.default_rng(0)):
         step += 1
         loss = sess.train_step(xs, ys, dropout=0.5, seed=step)                      # train.py:217-218
+        if args.clip_norm != 0.0:
+            gn_, sc_ = sess.last_grad_norm()
         if step < 10 or step % args.plotiter == 0:
+            clip = ("gnorm", "%.9g" % gn_, "scale", "%.9g" % sc_) if args.clip_norm != 0.0 else ()
             image = sess.forward(xs, dropout=0.0, training=False)                   # train.py:225-226
             print("Datetime", datetime.datetime.now().isoformat()[:-7], "Training step:", step,
-                  float(np.sum(image[0, -1]) * 255.0), float(np.sum(ys[0][-1]) * 255.0), "Training Loss", loss)
+                  float(np.sum(image[0, -1]) * 255.0), float(np.sum(ys[0][-1]) * 255.0), "Training Loss", loss, *clip)
         if step % args.validiter == 0:
             validate(sess, args, step)                                              # train.py:243-264
         if step % args.saveiter == 0:

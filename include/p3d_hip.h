@@ -193,6 +193,28 @@ int p3d_set_slot(p3d_handle* h, const char* var, int slot, const float* host, in
 int p3d_get_optimizer_step(p3d_handle* h, int64_t* t);
 int p3d_set_optimizer_step(p3d_handle* h, int64_t t);
 
+/* Gradient clipping by the global norm, as tf.clip_by_global_norm does it ahead of apply_gradients (an addition: the reference
+ * trains with Adam alone, which does not see the gradient's scale; its loss is a SUM over every output element, so Momentum
+ * and SGD see a gradient that grows with the batch and the clip size).  clip_norm = 0: off, the default; > 0: on; +inf:
+ * measure only; negative or NaN: -1.  With the option on, every train step computes, after the all-reduces and before any
+ * optimiser launch,
+ *   sumsq = sum g'^2 over every element of every trainable variable, g' the gradient the optimiser is about to apply (with a
+ *           regularisation term on, g' = fadd(g, fmul(c, w)) in float32); each square exact in double, the sum in double in a
+ *           fixed order (the same bits on every run, however the step cuts the range into launches);
+ *   norm  = sqrt(sumsq) in double;
+ *   scale = (float)(clip_norm / max(norm, (double)clip_norm)): exactly 1.0f while norm <= clip_norm; 1.0f under +inf; NaN when
+ *           norm is NaN or inf (the step then poisons the weights as the unclipped step would).
+ * The optimiser's update then runs on fmul(g', scale), rounded once, and is otherwise the chosen optimiser's arithmetic: a
+ * threshold that is not reached gives the bits of the unclipped step.  The gradient buffer is not rewritten: p3d_get_grad
+ * returns what it returns without clipping.  The first optimiser part no longer overlaps the stem's filter gradient (no update
+ * may start before the norm is known); that slot takes the first range of the sum instead.  p3d_backward computes the three
+ * values and scales nothing.  Drops a captured step graph.
+ * p3d_get_grad_norm: the values of the last train step or p3d_backward (any pointer may be NULL); -1 while the option is off or
+ * before the first step or backward since it was set.  Under data parallelism the norm is taken after the all-reduce, so every
+ * rank computes the same scale. */
+int p3d_set_grad_clip(p3d_handle* h, float clip_norm);
+int p3d_get_grad_norm(p3d_handle* h, double* sumsq, double* norm, float* scale);
+
 /* ---- intermediate tensors (tf fetches of graph tensors; parity/debug taps).  Names:
  *      conv1_custom, conv1_custom_bn_relu, pool1..pool4, block<i>/conv1_bn_relu, block<i>/st,
  *      block<i>/out, deconv3_re, deconv4_conv1, logits, pred. */
@@ -400,6 +422,22 @@ int p3d_debug_optimizer(int device, int kind, float* p, float* g, float* m, int6
 int p3d_debug_optimizer_decay(int device, int kind, float* p, float* g, float* m, int64_t n, int offset, const int64_t* tile_off,
                               const int64_t* tile_len, const float* tile_c, int ntile, float lr, float momentum, int use_nesterov,
                               int lr_on_device, int update, double* term);
+/* Test hook: any of the optimiser launches above with clipping's scale (OptArgs::gscale, read from device memory): kind
+ * P3D_OPT_*, ntile = 0 for the plain kernels (tile pointers and term may be NULL) or a tile table as p3d_debug_adam_decay takes
+ * it; g becomes g + c*p (not scaled), the update runs on fmul(g', gscale).  t and the betas matter under Adam only, momentum
+ * and use_nesterov under Momentum; v is not touched unless Adam.  *lr_t = the step size used. */
+int p3d_debug_opt_scaled(int device, int kind, float* p, float* g, float* m, float* v, int64_t n, int offset, const int64_t* tile_off,
+                         const int64_t* tile_len, const float* tile_c, int ntile, float lr, int64_t t, float b1, float b2, float eps,
+                         float momentum, int use_nesterov, int lr_on_device, float gscale, double* term, float* lr_t);
+/* Test hook: the global-norm reduction of p3d_set_grad_clip (grad_sumsq_kernel, launched from the description the step uses) on
+ * n gradients g and, where a chunk has a coefficient, parameters p (NULL: none), placed `offset` (0..3) elements into the device
+ * buffers.  Chunks k = 0..nchunk-1: [chunk_off[k], chunk_off[k] + chunk_len[k]) with coefficient chunk_c[k], ascending, without
+ * overlap; elements in no chunk (slot padding) are not read.  The ranges [range_lo[r], range_hi[r]) are launched in the order
+ * given, each over the chunks that start inside it, the last one folding; they must take every chunk exactly once.
+ * max_blocks caps the grid (0: the step's cap).  Results as p3d_get_grad_norm's. */
+int p3d_debug_grad_norm(int device, const float* g, const float* p, int64_t n, int offset, const int64_t* chunk_off,
+                        const int64_t* chunk_len, const float* chunk_c, int nchunk, const int64_t* range_lo, const int64_t* range_hi,
+                        int nrange, float clip_norm, int max_blocks, double* sumsq, double* norm, float* scale);
 int p3d_debug_stat_parts(const int64_t xshape[5], const int64_t wshape[5], const int s[3], int transpose, int* written, int* cap);
 int p3d_debug_igemm_groupable(const int64_t xshape[5], const int64_t wshape[5], const int s[3]);
 int p3d_op_max_pool3d(int device, const float* x, const int64_t xshape[5], const int ksize[3], const int s[3], float* y);

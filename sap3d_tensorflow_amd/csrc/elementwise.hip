@@ -551,6 +551,15 @@ __global__ __launch_bounds__(256) void l1_loss_kernel(const float* logits, const
     loss_body<2>(logits, pred, target, n, loss_out, dl, through_sigmoid, vec4, part, counter);
 }
 
+// Gradient clipping (OptArgs::gscale): the update runs on g'' = fmul(g', scale), rounded once and never fused into what
+// follows; the scale is one float in device memory (grad_sumsq_kernel's), read once per block.  SCALED = false is the code of the
+// unscaled kernels, instruction for instruction.
+template <bool SCALED>
+__device__ __forceinline__ float clip_scaled(float g, float s) {
+#pragma clang fp contract(off)
+    return SCALED ? g * s : g;
+}
+
 __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, float* m, float* v, long long n4,
                                                    long long n, float lr_arg, const float* lr_dev, float b1, float b2, float eps) {
     const float lr_t = lr_dev ? *lr_dev : lr_arg;
@@ -581,6 +590,40 @@ __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, flo
         }
     }
 }
+// adam_kernel on clip_scaled(g): a copy, so that adam_kernel itself compiles to what it did before there was one
+__global__ __launch_bounds__(256) void adam_scaled_kernel(float* p, const float* g, float* m, float* v, long long n4,
+                                                          long long n, float lr_arg, const float* lr_dev, float b1, float b2,
+                                                          float eps, const float* gscale) {
+    const float lr_t = lr_dev ? *lr_dev : lr_arg;
+    const float s = *gscale;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+        const long long e = i << 2;
+        if (e + 3 < n) {
+            const float4 gg = ld4(g + e);
+            float4 mm = ld4(m + e), vv = ld4(v + e), pp = ld4(p + e);
+            const float gs[4] = {clip_scaled<true>(gg.x, s), clip_scaled<true>(gg.y, s), clip_scaled<true>(gg.z, s),
+                                 clip_scaled<true>(gg.w, s)};
+            float ms[4] = {mm.x, mm.y, mm.z, mm.w}, vs[4] = {vv.x, vv.y, vv.z, vv.w}, ps[4] = {pp.x, pp.y, pp.z, pp.w};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                ms[q] = b1 * ms[q] + (1.f - b1) * gs[q];
+                vs[q] = b2 * vs[q] + (1.f - b2) * gs[q] * gs[q];
+                ps[q] -= lr_t * ms[q] / (sqrtf(vs[q]) + eps);
+            }
+            st4(m + e, make_float4(ms[0], ms[1], ms[2], ms[3]));
+            st4(v + e, make_float4(vs[0], vs[1], vs[2], vs[3]));
+            st4(p + e, make_float4(ps[0], ps[1], ps[2], ps[3]));
+        } else {
+            for (long long q = e; q < n; ++q) {
+                const float gq = clip_scaled<true>(g[q], s);
+                const float mq = b1 * m[q] + (1.f - b1) * gq;
+                const float vq = b2 * v[q] + (1.f - b2) * gq * gq;
+                m[q] = mq; v[q] = vq;
+                p[q] -= lr_t * mq / (sqrtf(vq) + eps);
+            }
+        }
+    }
+}
 
 // tf.train.MomentumOptimizer / GradientDescentOptimizer (p3d_set_optimizer): TF's ApplyMomentum and ApplyGradientDescent with
 // every rounding written out -- contraction off and no fma anywhere, so that a numpy float32 replay is bit-exact:
@@ -602,13 +645,13 @@ __device__ __forceinline__ void opt_elem(float& p, float& a, float g, float lr_t
 
 // float4 grid-stride pass shaped like adam_kernel (n4 groups of four from element `head`, the last group cut at n); the `head`
 // (0..3) elements before the buffers' first 16-byte boundary go one by one in block 0.  SGD never touches m.
-template <int KIND>
+template <int KIND, bool SCALED = false>
 __device__ __forceinline__ void opt_body(float* p, const float* g, float* m, long long n4, long long n, int head, float lr_t,
-                                         float mom, int nesterov) {
+                                         float mom, int nesterov, float s = 1.f) {
     if (blockIdx.x == 0 && (int)threadIdx.x < head) {
         const int q = threadIdx.x;
         float pq = p[q], mq = KIND == UPD_MOMENTUM ? m[q] : 0.f;
-        opt_elem<KIND>(pq, mq, g[q], lr_t, mom, nesterov);
+        opt_elem<KIND>(pq, mq, clip_scaled<SCALED>(g[q], s), lr_t, mom, nesterov);
         if (KIND == UPD_MOMENTUM) m[q] = mq;
         p[q] = pq;
     }
@@ -623,13 +666,13 @@ __device__ __forceinline__ void opt_body(float* p, const float* g, float* m, lon
                 ms[0] = mm.x; ms[1] = mm.y; ms[2] = mm.z; ms[3] = mm.w;
             }
 #pragma unroll
-            for (int q = 0; q < 4; ++q) opt_elem<KIND>(ps[q], ms[q], gs[q], lr_t, mom, nesterov);
+            for (int q = 0; q < 4; ++q) opt_elem<KIND>(ps[q], ms[q], clip_scaled<SCALED>(gs[q], s), lr_t, mom, nesterov);
             if (KIND == UPD_MOMENTUM) st4(m + e, make_float4(ms[0], ms[1], ms[2], ms[3]));
             st4(p + e, make_float4(ps[0], ps[1], ps[2], ps[3]));
         } else {
             for (long long q = e; q < n; ++q) {
                 float pq = p[q], mq = KIND == UPD_MOMENTUM ? m[q] : 0.f;
-                opt_elem<KIND>(pq, mq, g[q], lr_t, mom, nesterov);
+                opt_elem<KIND>(pq, mq, clip_scaled<SCALED>(g[q], s), lr_t, mom, nesterov);
                 if (KIND == UPD_MOMENTUM) m[q] = mq;
                 p[q] = pq;
             }
@@ -644,6 +687,15 @@ __global__ __launch_bounds__(256) void momentum_kernel(float* p, const float* g,
 __global__ __launch_bounds__(256) void sgd_kernel(float* p, const float* g, long long n4, long long n, int head, float lr_arg,
                                                   const float* lr_dev) {
     opt_body<UPD_SGD>(p, g, nullptr, n4, n, head, lr_dev ? *lr_dev : lr_arg, 0.f, 0);
+}
+__global__ __launch_bounds__(256) void momentum_scaled_kernel(float* p, const float* g, float* m, long long n4, long long n, int head,
+                                                              float lr_arg, const float* lr_dev, float mom, int use_nesterov,
+                                                              const float* gscale) {
+    opt_body<UPD_MOMENTUM, true>(p, g, m, n4, n, head, lr_dev ? *lr_dev : lr_arg, mom, use_nesterov, *gscale);
+}
+__global__ __launch_bounds__(256) void sgd_scaled_kernel(float* p, const float* g, long long n4, long long n, int head, float lr_arg,
+                                                         const float* lr_dev, const float* gscale) {
+    opt_body<UPD_SGD, true>(p, g, nullptr, n4, n, head, lr_dev ? *lr_dev : lr_arg, 0.f, 0, *gscale);
 }
 
 // Regularisation (the decay part of OptArgs).  Every rounding is explicit, so that a numpy float32 replay is bit-exact: contraction is
@@ -667,11 +719,12 @@ __device__ __forceinline__ void adam_elem(float& p, float& m, float& v, float g,
 // 0.5 c sum(p^2) in double from the parameters before the update.  Elements of a 4-group shared with the neighbouring tile
 // (variables whose length is not a multiple of 4 end mid-group) go one by one, with the arithmetic of the group they are in.
 // KIND: the update on g', UPD_NONE for the gradient-only mode; Momentum keeps its accumulator in m, v is Adam's alone.
-template <int KIND>
+// SCALED (clipping): g' is written back as it is; the update takes clip_scaled(g').
+template <int KIND, bool SCALED = false>
 __device__ __forceinline__ void decay_body(float* p, float* g, float* m, float* v, long long n, const P3dRegTile* tiles,
                                            long long tile_base, float lr_arg, const float* lr_dev, float b1, float b2, float eps,
                                            double* part, const double* fold_part, int nfold, unsigned* counter, double* term,
-                                           float mom = 0.f, int nesterov = 0) {
+                                           float mom = 0.f, int nesterov = 0, const float* gscale = nullptr) {
 #pragma clang fp contract(off)
     constexpr bool UPDATE = KIND != UPD_NONE, ADAM = KIND == UPD_ADAM;
     __shared__ double wsum[4];
@@ -680,6 +733,7 @@ __device__ __forceinline__ void decay_body(float* p, float* g, float* m, float* 
     const long long a = t.off - tile_base, b = a + t.len;
     const float c = t.c;
     const float lr_t = UPDATE ? (lr_dev ? *lr_dev : lr_arg) : 0.f;
+    const float gsc = SCALED ? *gscale : 1.f;
     double acc = 0.0;
     if (UPDATE || c != 0.f) {
         const long long a4 = (a + 3) & ~3LL, b4 = max(a4, b & ~3LL);
@@ -698,7 +752,7 @@ __device__ __forceinline__ void decay_body(float* p, float* g, float* m, float* 
                 const float4 mm = ld4(m + e), vv = ld4(v + e);
                 float ms[4] = {mm.x, mm.y, mm.z, mm.w}, vs[4] = {vv.x, vv.y, vv.z, vv.w};
 #pragma unroll
-                for (int q = 0; q < 4; ++q) adam_elem(ps[q], ms[q], vs[q], gs[q], lr_t, b1, b2, eps, true);
+                for (int q = 0; q < 4; ++q) adam_elem(ps[q], ms[q], vs[q], clip_scaled<SCALED>(gs[q], gsc), lr_t, b1, b2, eps, true);
                 st4(m + e, make_float4(ms[0], ms[1], ms[2], ms[3]));
                 st4(v + e, make_float4(vs[0], vs[1], vs[2], vs[3]));
                 st4(p + e, make_float4(ps[0], ps[1], ps[2], ps[3]));
@@ -709,7 +763,7 @@ __device__ __forceinline__ void decay_body(float* p, float* g, float* m, float* 
                     ms[0] = mm.x; ms[1] = mm.y; ms[2] = mm.z; ms[3] = mm.w;
                 }
 #pragma unroll
-                for (int q = 0; q < 4; ++q) opt_elem<KIND>(ps[q], ms[q], gs[q], lr_t, mom, nesterov);
+                for (int q = 0; q < 4; ++q) opt_elem<KIND>(ps[q], ms[q], clip_scaled<SCALED>(gs[q], gsc), lr_t, mom, nesterov);
                 if (KIND == UPD_MOMENTUM) st4(m + e, make_float4(ms[0], ms[1], ms[2], ms[3]));
                 st4(p + e, make_float4(ps[0], ps[1], ps[2], ps[3]));
             }
@@ -725,11 +779,11 @@ __device__ __forceinline__ void decay_body(float* p, float* g, float* m, float* 
                 }
                 if (ADAM) {
                     float me = m[e], ve = v[e];
-                    adam_elem(pe, me, ve, ge, lr_t, b1, b2, eps, (e & ~3LL) + 3 < n);
+                    adam_elem(pe, me, ve, clip_scaled<SCALED>(ge, gsc), lr_t, b1, b2, eps, (e & ~3LL) + 3 < n);
                     m[e] = me; v[e] = ve; p[e] = pe;
                 } else if (UPDATE) {
                     float me = KIND == UPD_MOMENTUM ? m[e] : 0.f;
-                    opt_elem<KIND>(pe, me, ge, lr_t, mom, nesterov);
+                    opt_elem<KIND>(pe, me, clip_scaled<SCALED>(ge, gsc), lr_t, mom, nesterov);
                     if (KIND == UPD_MOMENTUM) m[e] = me;
                     p[e] = pe;
                 }
@@ -769,10 +823,100 @@ __global__ __launch_bounds__(256) void sgd_decay_kernel(float* p, float* g, long
                                                         int nfold, unsigned* counter, double* term) {
     decay_body<UPD_SGD>(p, g, nullptr, nullptr, n, tiles, tile_base, lr_arg, lr_dev, 0.f, 0.f, 0.f, part, fold_part, nfold, counter, term);
 }
+__global__ __launch_bounds__(256) void adam_decay_scaled_kernel(float* p, float* g, float* m, float* v, long long n,
+                                                                const P3dRegTile* tiles, long long tile_base, float lr_arg,
+                                                                const float* lr_dev, float b1, float b2, float eps, double* part,
+                                                                const double* fold_part, int nfold, unsigned* counter, double* term,
+                                                                const float* gscale) {
+    decay_body<UPD_ADAM, true>(p, g, m, v, n, tiles, tile_base, lr_arg, lr_dev, b1, b2, eps, part, fold_part, nfold, counter, term, 0.f, 0,
+                               gscale);
+}
+__global__ __launch_bounds__(256) void momentum_decay_scaled_kernel(float* p, float* g, float* m, long long n, const P3dRegTile* tiles,
+                                                                    long long tile_base, float lr_arg, const float* lr_dev, float mom,
+                                                                    int use_nesterov, double* part, const double* fold_part,
+                                                                    int nfold, unsigned* counter, double* term, const float* gscale) {
+    decay_body<UPD_MOMENTUM, true>(p, g, m, nullptr, n, tiles, tile_base, lr_arg, lr_dev, 0.f, 0.f, 0.f, part, fold_part, nfold, counter,
+                                   term, mom, use_nesterov, gscale);
+}
+__global__ __launch_bounds__(256) void sgd_decay_scaled_kernel(float* p, float* g, long long n, const P3dRegTile* tiles,
+                                                               long long tile_base, float lr_arg, const float* lr_dev, double* part,
+                                                               const double* fold_part, int nfold, unsigned* counter, double* term,
+                                                               const float* gscale) {
+    decay_body<UPD_SGD, true>(p, g, nullptr, nullptr, n, tiles, tile_base, lr_arg, lr_dev, 0.f, 0.f, 0.f, part, fold_part, nfold, counter,
+                              term, 0.f, 0, gscale);
+}
 __global__ __launch_bounds__(256) void decay_grad_kernel(float* p, float* g, long long n, const P3dRegTile* tiles, long long tile_base,
                                                          double* part, const double* fold_part, int nfold, unsigned* counter,
                                                          double* term) {
     decay_body<UPD_NONE>(p, g, nullptr, nullptr, n, tiles, tile_base, 0.f, nullptr, 0.f, 0.f, 0.f, part, fold_part, nfold, counter, term);
+}
+
+// Global gradient norm (p3d_set_grad_clip; SumsqArgs in p3d_kernels.h).  Block b takes chunks k0 + b, k0 + b + gridDim.x, ... of
+// the table; chunk k's sum of g'^2 -- every square exact in double, one double accumulator per lane over a lane-to-element map
+// that depends on the chunk's place in memory alone, lanes folded by the xor butterfly and the four waves in order -- goes to
+// part[k] with a write-through store.  g' = g + c p in decay_body's float32 rounding where c != 0 (p is not read elsewhere).
+// float4 loads from the chunk's first 16-byte boundary, the elements before it and after the last whole group one by one;
+// a chunk whose g and p sit at different places in a 16-byte line goes one by one throughout.  With nfold > 0 the last block
+// to arrive folds part[0 .. nfold) -- the whole table, whichever launches wrote it -- the same way and writes sumsq, norm and
+// scale: the three do not depend on how the table was cut into launches or on the grid.
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* g, const float* p, const P3dRegTile* tiles, long long tile_base,
+                                                         int k0, int k1, double* part, int nfold, unsigned* counter, double* res,
+                                                         float clip) {
+#pragma clang fp contract(off)
+    __shared__ double wsum[4];
+    __shared__ int last_flag;
+    for (int k = k0 + (int)blockIdx.x; k < k1; k += (int)gridDim.x) {
+        const P3dRegTile t = tiles[k];
+        const long long a = t.off - tile_base, b = a + t.len;
+        const float c = t.c;
+        const unsigned long long ga = (unsigned long long)(g + a), pa = (unsigned long long)(p + a);
+        const bool vec = (ga & 3) == 0 && (c == 0.f || ((ga ^ pa) & 15) == 0);
+        const long long a4 = vec ? min(b, a + (long long)(((16 - (ga & 15)) & 15) >> 2)) : b;
+        const long long b4 = a4 + ((b - a4) & ~3LL);
+        double acc = 0.0;
+        for (long long e = a4 + 4 * (long long)threadIdx.x; e < b4; e += 4 * 256) {
+            const float4 gg = ld4(g + e);
+            float gs[4] = {gg.x, gg.y, gg.z, gg.w};
+            if (c != 0.f) {
+                const float4 pp = ld4(p + e);
+                const float ps[4] = {pp.x, pp.y, pp.z, pp.w};
+#pragma unroll
+                for (int q = 0; q < 4; ++q) gs[q] = gs[q] + c * ps[q];
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc += (double)gs[q] * (double)gs[q];
+        }
+        auto one = [&](long long e) {
+            float ge = g[e];
+            if (c != 0.f) ge = ge + c * p[e];
+            acc += (double)ge * (double)ge;
+        };
+        for (long long e = a + threadIdx.x; e < a4; e += 256) one(e);       // under 4 elements each on the float4 path
+        for (long long e = b4 + threadIdx.x; e < b; e += 256) one(e);
+        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+        __syncthreads();      // the previous chunk's wsum has been read
+        if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+        __syncthreads();
+        if (threadIdx.x == 0) p3d_store_wt(part, (size_t)k, ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3]);
+    }
+    if (nfold <= 0) return;
+    if (!p3d_last_block_wt(counter, gridDim.x, &last_flag)) return;
+    double s = 0.0;
+    for (int k = threadIdx.x; k < nfold; k += 256) s += part[k];
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double sumsq = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+        const double norm = sqrt(sumsq), cn = (double)clip;
+        float scale;
+        if (!(norm - norm == 0.0)) scale = __builtin_nanf("");      // NaN or inf
+        else if (cn - cn != 0.0) scale = 1.f;                        // +inf: measure only
+        else scale = (float)(cn / fmax(norm, cn));
+        res[0] = sumsq; res[1] = norm;
+        *reinterpret_cast<float*>(res + 2) = scale;
+    }
 }
 
 __global__ __launch_bounds__(256) void add_inplace_kernel(float* dst, int lddst, const float* src, int ldsrc, long long M, int C, int copy) {
@@ -1194,17 +1338,25 @@ hipError_t p3d_loss(const LossArgs& a, hipStream_t s, unsigned* done) {
 LaunchDesc p3d_opt_desc(const OptArgs& a, double decayed_elems) {
     // per element Adam reads g, m, v, p and writes m, v, p (28 bytes); Momentum g, a, p and a, p (20); SGD g, p and p (12).  A
     // decayed element adds 2 operations for g + c w, 2 for the term and the gradient written back (12 bytes alone without an
-    // update); a tile is 8 bytes of table and partial.
-    static const char* const name[2][4] = {{nullptr, "adam_kernel", "momentum_kernel", "sgd_kernel"},
-                                           {"decay_grad_kernel", "adam_decay_kernel", "momentum_decay_kernel", "sgd_decay_kernel"}};
+    // update); a tile is 8 bytes of table and partial.  Clipping (gscale): one operation per element, 4 bytes read per block.
+    static const char* const name[2][2][4] = {{{nullptr, "adam_kernel", "momentum_kernel", "sgd_kernel"},
+                                               {"decay_grad_kernel", "adam_decay_kernel", "momentum_decay_kernel", "sgd_decay_kernel"}},
+                                              {{nullptr, "adam_scaled_kernel", "momentum_scaled_kernel", "sgd_scaled_kernel"},
+                                               {nullptr, "adam_decay_scaled_kernel", "momentum_decay_scaled_kernel",
+                                                "sgd_decay_scaled_kernel"}}};
     const double upd = (a.update == UPD_ADAM ? 28.0 : a.update == UPD_MOMENTUM ? 20.0 : 12.0) * a.n, nd = decayed_elems;
-    if (!a.ntile) return {name[0][a.update + 1], 0, upd};
-    return {name[1][a.update + 1], 4.0 * nd, (a.update == UPD_NONE ? 12.0 * nd : upd + 4.0 * nd) + 8.0 * a.ntile};
+    const int sc = a.gscale ? 1 : 0;
+    if (!a.ntile) {
+        return {name[sc][0][a.update + 1], sc * (double)a.n, upd + sc * 4.0 * grid_for((a.n + 3) / 4)};
+    }
+    return {name[sc][1][a.update + 1], 4.0 * nd + sc * (double)a.n,
+            (a.update == UPD_NONE ? 12.0 * nd : upd + 4.0 * nd) + (8.0 + sc * 4.0) * a.ntile};
 }
 
 hipError_t p3d_opt_step(const OptArgs& a, hipStream_t s) {
     const bool adam = a.update == UPD_ADAM, mom = a.update == UPD_MOMENTUM;
     if (a.n < 1 || a.ntile < 0 || a.update < UPD_NONE || a.update > UPD_SGD || (mom && !a.m)) return hipErrorInvalidValue;
+    if (a.gscale && a.update == UPD_NONE) return hipErrorInvalidValue;      // the gradient-only launch scales nothing
     const long long n = a.n;
     const int nesterov = a.nesterov ? 1 : 0;
     const uintptr_t r = low4(a.p);
@@ -1214,7 +1366,12 @@ hipError_t p3d_opt_step(const OptArgs& a, hipStream_t s) {
         const int head = (int)std::min<long long>((long long)((16 - r) & 15) / 4, n);
         const long long n4 = (n - head + 3) / 4;
         const dim3 grid(n4 > 0 ? grid_for(n4) : 1u);
-        if (mom) hipLaunchKernelGGL(momentum_kernel, grid, dim3(256), 0, s, a.p, a.g, a.m, n4, n, head, a.lr, a.lr_dev, a.momentum, nesterov);
+        if (a.gscale) {
+            if (mom)
+                hipLaunchKernelGGL(momentum_scaled_kernel, grid, dim3(256), 0, s, a.p, a.g, a.m, n4, n, head, a.lr, a.lr_dev, a.momentum,
+                                   nesterov, a.gscale);
+            else hipLaunchKernelGGL(sgd_scaled_kernel, grid, dim3(256), 0, s, a.p, a.g, n4, n, head, a.lr, a.lr_dev, a.gscale);
+        } else if (mom) hipLaunchKernelGGL(momentum_kernel, grid, dim3(256), 0, s, a.p, a.g, a.m, n4, n, head, a.lr, a.lr_dev, a.momentum, nesterov);
         else hipLaunchKernelGGL(sgd_kernel, grid, dim3(256), 0, s, a.p, a.g, n4, n, head, a.lr, a.lr_dev);
         return hipGetLastError();
     }
@@ -1222,11 +1379,27 @@ hipError_t p3d_opt_step(const OptArgs& a, hipStream_t s) {
     if (r | low4(a.g) | (adam || mom ? low4(a.m) : 0) | (adam ? low4(a.v) : 0)) return hipErrorInvalidValue;
     if (!a.ntile) {
         const long long n4 = (n + 3) / 4;
-        hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n4)), dim3(256), 0, s, a.p, a.g, a.m, a.v, n4, n, a.lr, a.lr_dev, a.b1, a.b2, a.eps);
+        if (a.gscale)
+            hipLaunchKernelGGL(adam_scaled_kernel, dim3(grid_for(n4)), dim3(256), 0, s, a.p, a.g, a.m, a.v, n4, n, a.lr, a.lr_dev, a.b1,
+                               a.b2, a.eps, a.gscale);
+        else
+            hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n4)), dim3(256), 0, s, a.p, a.g, a.m, a.v, n4, n, a.lr, a.lr_dev, a.b1, a.b2, a.eps);
         return hipGetLastError();
     }
     if (!a.tiles || !a.part || (a.nfold > 0 && (!a.fold_part || !a.counter || !a.term))) return hipErrorInvalidValue;
     const dim3 grid(a.ntile), block(256);
+    if (a.gscale) {
+        if (adam)
+            hipLaunchKernelGGL(adam_decay_scaled_kernel, grid, block, 0, s, a.p, a.g, a.m, a.v, n, a.tiles, a.tile_base, a.lr, a.lr_dev,
+                               a.b1, a.b2, a.eps, a.part, a.fold_part, a.nfold, a.counter, a.term, a.gscale);
+        else if (mom)
+            hipLaunchKernelGGL(momentum_decay_scaled_kernel, grid, block, 0, s, a.p, a.g, a.m, n, a.tiles, a.tile_base, a.lr, a.lr_dev,
+                               a.momentum, nesterov, a.part, a.fold_part, a.nfold, a.counter, a.term, a.gscale);
+        else
+            hipLaunchKernelGGL(sgd_decay_scaled_kernel, grid, block, 0, s, a.p, a.g, n, a.tiles, a.tile_base, a.lr, a.lr_dev, a.part,
+                               a.fold_part, a.nfold, a.counter, a.term, a.gscale);
+        return hipGetLastError();
+    }
     if (adam)
         hipLaunchKernelGGL(adam_decay_kernel, grid, block, 0, s, a.p, a.g, a.m, a.v, n, a.tiles, a.tile_base, a.lr, a.lr_dev, a.b1, a.b2,
                            a.eps, a.part, a.fold_part, a.nfold, a.counter, a.term);
@@ -1239,6 +1412,21 @@ hipError_t p3d_opt_step(const OptArgs& a, hipStream_t s) {
     else
         hipLaunchKernelGGL(decay_grad_kernel, grid, block, 0, s, a.p, a.g, n, a.tiles, a.tile_base, a.part, a.fold_part, a.nfold,
                            a.counter, a.term);
+    return hipGetLastError();
+}
+
+LaunchDesc p3d_grad_sumsq_desc(const SumsqArgs& a, double elems, double decayed_elems) {
+    // g read once, p where the chunk's c != 0 (2 operations for g + c w); square and add; a chunk is 16 bytes of table and 8 of partial
+    return {"grad_sumsq_kernel", 2.0 * elems + 2.0 * decayed_elems, 4.0 * (elems + decayed_elems) + 24.0 * (a.k1 - a.k0) + 8.0 * a.nfold};
+}
+
+hipError_t p3d_grad_sumsq(const SumsqArgs& a, hipStream_t s) {
+    if (!a.g || !a.tiles || !a.part || a.k0 < 0 || a.k1 <= a.k0 || a.max_blocks < 0) return hipErrorInvalidValue;
+    if (a.nfold > 0 && (a.nfold < a.k1 || !a.counter || !a.res)) return hipErrorInvalidValue;
+    if (!(a.clip_norm > 0.f)) return hipErrorInvalidValue;      // NaN, 0 and negatives
+    const int chunks = a.k1 - a.k0, cap = a.max_blocks ? a.max_blocks : P3D_SUMSQ_MAX_BLOCKS;
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(std::min(chunks, cap)), dim3(256), 0, s, a.g, a.p, a.tiles, a.tile_base, a.k0, a.k1,
+                       a.part, a.nfold, a.counter, a.res, a.clip_norm);
     return hipGetLastError();
 }
 

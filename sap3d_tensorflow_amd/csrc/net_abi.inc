@@ -358,6 +358,22 @@ int p3d_param_regularization(p3d_handle* h, const char* name, float* c_wd, float
     API_END
 }
 
+int p3d_set_grad_clip(p3d_handle* h, float clip_norm) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->set_grad_clip(clip_norm);
+    API_END
+}
+
+int p3d_get_grad_norm(p3d_handle* h, double* sumsq, double* norm, float* scale) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->read_grad_norm(sumsq, norm, scale);
+    API_END
+}
+
 int p3d_set_bn_fusion(p3d_handle* h, int enable) {
     API_BEGIN
     if (!h) throw P3dError("null handle");
@@ -387,6 +403,7 @@ int p3d_backward(p3d_handle* h, const float* x, const float* y, float dropout_ra
     h->run_forward(c);
     h->run_loss(c);
     h->run_backward(c, false);
+    if (h->clip_on()) h->sumsq_range(c, 0, h->n_train);            // the norm of g + c w, before g is rewritten to it; nothing is scaled
     if (h->reg_terms) h->adam_range(c, 0, h->n_train, false);      // the regularisation's gradient, after the backward's
     const float l = h->read_loss();
     if (loss) *loss = l;
@@ -1277,12 +1294,15 @@ std::vector<P3dRegTile> host_tiles(const int64_t* tile_off, const int64_t* tile_
 // step size, as an argument or (lr_on_device) through device memory as a captured step reads it.  tiles: the decay part, with
 // the whole table folded into *term.
 void debug_opt_step(OptArgs a, float* p, const float* g, float* g_out, float* m, float* v, int64_t n, int offset,
-                    float step, int lr_on_device, const std::vector<P3dRegTile>& tiles = {}, double* term = nullptr) {
+                    float step, int lr_on_device, const std::vector<P3dRegTile>& tiles = {}, double* term = nullptr,
+                    const float* gscale = nullptr) {
     const int64_t ntile = (int64_t)tiles.size();
     StagedBuf pb(n, offset, p), gb(n, offset, g), mb(n, offset, m), vb(n, offset, v);
     DevBuf lrb(1), tb(4 * ntile), part(2 * ntile), scal(4);      // scal (zeroed): [0..1] the term, [2] the fold's counter
     a.p = pb.at(); a.g = gb.at(); a.m = mb.at(); a.v = vb.at(); a.n = (long)n;
     if (lr_on_device) HIPCHECK(p3d_set_step_scalars(nullptr, lrb.p, 0, step, nullptr));
+    DevBuf sc(1, gscale);      // clipping's scale, read from device memory as the step reads it
+    if (gscale) a.gscale = sc.p;
     // from device memory the argument must not matter: NaN would show in every element if the kernel read it
     a.lr = lr_on_device ? NAN : step;
     a.lr_dev = lr_on_device ? lrb.p : nullptr;
@@ -1414,6 +1434,77 @@ int p3d_debug_adam_decay(int device, float* p, float* g, float* m, float* v, int
     const float step = adam_step_size(lr, b1, b2, t);
     debug_opt_step(adam_update(b1, b2, eps, update), p, g, g, m, v, n, offset, step, lr_on_device, tiles, term);
     *lr_t = step;
+    API_END
+}
+
+// Any optimiser launch with clipping's scale (p3d_debug_adam / _adam_decay / _optimizer / _optimizer_decay keep their arguments).
+int p3d_debug_opt_scaled(int device, int kind, float* p, float* g, float* m, float* v, int64_t n, int offset, const int64_t* tile_off,
+                         const int64_t* tile_len, const float* tile_c, int ntile, float lr, int64_t t, float b1, float b2, float eps,
+                         float momentum, int use_nesterov, int lr_on_device, float gscale, double* term, float* lr_t) {
+    API_BEGIN
+    HIPCHECK(hipSetDevice(device));
+    if (!p || !g || !m || !v || !lr_t || (ntile && (!tile_off || !tile_len || !tile_c || !term))) throw P3dError("null argument");
+    if (kind != P3D_OPT_ADAM && kind != P3D_OPT_MOMENTUM && kind != P3D_OPT_SGD) throw P3dError("opt_scaled: kind 0, 1 or 2");
+    if (n < 1 || t < 1 || offset < 0 || offset > 3 || ntile < 0) throw P3dError("opt_scaled: bad length, step, offset or tile count");
+    std::vector<P3dRegTile> tiles;
+    if (ntile) tiles = host_tiles(tile_off, tile_len, tile_c, ntile, n, "opt_scaled");
+    const bool adam = kind == P3D_OPT_ADAM;
+    const float step = adam ? adam_step_size(lr, b1, b2, t) : lr;
+    debug_opt_step(adam ? adam_update(b1, b2, eps) : momentum_update(kind, momentum, use_nesterov), p, g, g, m, adam ? v : nullptr, n,
+                   offset, step, lr_on_device, tiles, term, &gscale);
+    *lr_t = step;
+    API_END
+}
+
+// grad_sumsq_kernel on host arrays, through sumsq launches described as the step describes its own (SumsqArgs): chunks
+// (chunk_off, chunk_len, chunk_c) ascending, gaps allowed (padding: never read); the ranges [range_lo, range_hi) are launched in
+// the order given, the last one folding; together they must take every chunk once.
+int p3d_debug_grad_norm(int device, const float* g, const float* p, int64_t n, int offset, const int64_t* chunk_off,
+                        const int64_t* chunk_len, const float* chunk_c, int nchunk, const int64_t* range_lo, const int64_t* range_hi,
+                        int nrange, float clip_norm, int max_blocks, double* sumsq, double* norm, float* scale) {
+    API_BEGIN
+    HIPCHECK(hipSetDevice(device));
+    if (!g || !chunk_off || !chunk_len || !chunk_c || !range_lo || !range_hi || !sumsq || !norm || !scale) throw P3dError("null argument");
+    if (n < 1 || offset < 0 || offset > 3 || nchunk < 1 || nrange < 1 || max_blocks < 0) throw P3dError("grad_norm: bad length, offset or counts");
+    if (!(clip_norm > 0.f)) throw P3dError("grad_norm: clip_norm must be positive or +inf");
+    std::vector<P3dRegTile> tiles((size_t)nchunk);
+    int64_t at = 0;
+    for (int k = 0; k < nchunk; ++k) {
+        if (chunk_off[k] < at || chunk_len[k] < 1 || chunk_len[k] > (1 << 30) || chunk_off[k] + chunk_len[k] > n)
+            throw P3dError("grad_norm: chunks must ascend without overlap inside [0, n)");
+        if (chunk_c[k] != 0.f && !p) throw P3dError("grad_norm: a chunk has a coefficient but there are no parameters");
+        tiles[(size_t)k] = {(long long)chunk_off[k], (int)chunk_len[k], chunk_c[k]};
+        at = chunk_off[k] + chunk_len[k];
+    }
+    auto first_at = [&](int64_t off) {
+        return (int)(std::lower_bound(tiles.begin(), tiles.end(), off, [](const P3dRegTile& t, int64_t o) { return t.off < o; }) - tiles.begin());
+    };
+    std::vector<int> taken((size_t)nchunk, 0);
+    std::vector<std::pair<int, int>> cuts;
+    for (int r = 0; r < nrange; ++r) {
+        const int k0 = first_at(range_lo[r]), k1 = first_at(range_hi[r]);
+        if (k1 <= k0 || tiles[(size_t)k1 - 1].off + tiles[(size_t)k1 - 1].len > range_hi[r]) throw P3dError("grad_norm: a range is empty or cuts a chunk");
+        for (int k = k0; k < k1; ++k) ++taken[(size_t)k];
+        cuts.push_back({k0, k1});
+    }
+    for (int k : taken) if (k != 1) throw P3dError("grad_norm: the ranges must take every chunk exactly once");
+    StagedBuf gb(n, offset, g), pb(n, offset, p);
+    DevBuf tb(4 * (int64_t)nchunk), part(2 * (int64_t)nchunk), res(8);      // res (zeroed): [0..5] the results, [6] the fold's counter
+    HIPCHECK(copy_now(tb.p, tiles.data(), tiles.size() * sizeof(P3dRegTile), hipMemcpyHostToDevice, nullptr));
+    for (int r = 0; r < nrange; ++r) {
+        SumsqArgs a;
+        a.g = gb.at(); a.p = p ? pb.at() : nullptr; a.tiles = reinterpret_cast<P3dRegTile*>(tb.p); a.tile_base = 0;
+        a.k0 = cuts[(size_t)r].first; a.k1 = cuts[(size_t)r].second;
+        a.part = reinterpret_cast<double*>(part.p); a.nfold = r == nrange - 1 ? nchunk : 0;
+        a.counter = reinterpret_cast<unsigned*>(res.p + 6); a.res = reinterpret_cast<double*>(res.p);
+        a.clip_norm = clip_norm; a.max_blocks = max_blocks;
+        HIPCHECK(p3d_grad_sumsq(a, nullptr));
+    }
+    HIPCHECK(hipDeviceSynchronize());
+    float back[8];
+    HIPCHECK(copy_now(back, res.p, sizeof(back), hipMemcpyDeviceToHost, nullptr));
+    if (reinterpret_cast<unsigned*>(back)[6]) throw P3dError("grad_norm: the arrival counter was left nonzero");
+    memcpy(sumsq, back, 8); memcpy(norm, back + 2, 8); *scale = back[4];
     API_END
 }
 

@@ -161,8 +161,13 @@
                 early_adam = false;
                 HIPCHECK(ev_wait(c.s, ev_side_early));
                 if (early_comm) HIPCHECK(ev_wait(c.s, ev_comm_early));
-                adam_begin(c);
-                adam_range(c, adam_split, n_train);
+                if (clip_on()) {
+                    // clipping: no update before every gradient is final; the slot takes the norm's first range instead
+                    sumsq_range(c, adam_split, n_train);
+                } else {
+                    adam_begin(c);
+                    adam_range(c, adam_split, n_train);
+                }
                 adam_done = true;
             }
             {
@@ -219,6 +224,11 @@
                 HIPCHECK(ev_wait(c.s, ev_comm_done));
             }
         }
+        if (adam_done && clip_on()) {      // the norm's second range folds; then the optimiser's usual two ranges on the scale
+            sumsq_range(c, 0, adam_split);
+            adam_begin(c);
+            adam_range(c, adam_split, n_train);
+        }
         if (adam_done) adam_range(c, 0, adam_split);
         return adam_done;
     }
@@ -256,7 +266,103 @@
         const LaunchDesc d = p3d_opt_desc(a, decayed);
         launch(c, d.kernel, d.flops, d.bytes, [&]() { return p3d_opt_step(a, c.s); });
     }
-    void run_adam(const Ctx& c) { adam_begin(c); adam_range(c, 0, n_train); }
+    void run_adam(const Ctx& c) {
+        if (clip_on()) sumsq_range(c, 0, n_train);
+        adam_begin(c);
+        adam_range(c, 0, n_train);
+    }
+
+    // ---- gradient clipping by the global norm (p3d_set_grad_clip) ----------------------------------
+    // clip_norm > 0: the step's sum of squares over every trainable element's g' (g + c w under a regularisation term), its
+    // norm and scale = clip_norm / max(norm, clip_norm) land in d_clip_res before any optimiser launch, and every optimiser
+    // launch reads the scale (OptArgs::gscale).  +inf measures only.  The chunk table: each trainable's [off, off + count) cut
+    // at REG_TILE with the variable's coefficient.  Slot padding is in no chunk, so it is never read: nothing here depends on
+    // what the filter-gradient kernels leave there.  The cut depends on the flat layout alone, the coefficients on the
+    // regularisation settings (set_regularization rebuilds the table).  Every range sumsq_range is called with starts at a
+    // variable's offset; the range that starts at 0 is the last one launched and folds the whole table.
+    float clip_norm = 0.f;
+    bool clip_have = false;              // a step or a backward has written d_clip_res since the option was set
+    std::vector<P3dRegTile> clip_tiles;
+    std::vector<int64_t> clip_decayed;   // elements with c != 0 in chunks [0, k)
+    std::vector<int64_t> clip_elems;     // elements in chunks [0, k)
+    P3dRegTile* d_clip_tiles = nullptr;
+    double* d_clip_part = nullptr;
+    double* d_clip_res = nullptr;        // sumsq, norm; the float scale at [2]
+    unsigned* d_clip_cnt = nullptr;
+    bool clip_on() const { return clip_norm > 0.f; }
+    const float* clip_scale_dev() const { return reinterpret_cast<const float*>(d_clip_res + 2); }
+    void build_clip_table() {
+        std::vector<const Param*> tr;
+        for (const Param* p : porder) if (p->trainable) tr.push_back(p);
+        std::sort(tr.begin(), tr.end(), [](const Param* a, const Param* b) { return a->off < b->off; });
+        std::vector<P3dRegTile> tiles;
+        for (const Param* p : tr) {
+            const float c = (float)(reg_coef64(p, P3D_REG_WEIGHT_DECAY) + reg_coef64(p, P3D_REG_L2));      // set_regularization's
+            for (int64_t a = p->off, b = p->off + p->count; a < b; a += REG_TILE)
+                tiles.push_back({(long long)a, (int)std::min(REG_TILE, b - a), c});
+        }
+        if (tiles.empty()) throw P3dError("gradient clipping: no trainable variable");
+        HIPCHECK(hipStreamSynchronize(stream));      // the table may be in use by queued work
+        if (!d_clip_tiles) {
+            d_clip_tiles = dalloc<P3dRegTile>((int64_t)tiles.size());
+            d_clip_part = dalloc<double>((int64_t)tiles.size());
+            d_clip_res = dalloc<double>(3);
+            d_clip_cnt = dalloc<unsigned>(1);
+            HIPCHECK(fill_async(d_clip_res, 0, 3 * sizeof(double), stream, "gradient-norm"));
+            HIPCHECK(fill_async(d_clip_cnt, 0, sizeof(unsigned), stream, "gradient-norm"));
+        }
+        HIPCHECK(copy_now(d_clip_tiles, tiles.data(), tiles.size() * sizeof(P3dRegTile), hipMemcpyHostToDevice, stream));
+        clip_tiles = std::move(tiles);
+        clip_decayed.assign(clip_tiles.size() + 1, 0);
+        clip_elems.assign(clip_tiles.size() + 1, 0);
+        for (size_t k = 0; k < clip_tiles.size(); ++k) {
+            clip_elems[k + 1] = clip_elems[k] + clip_tiles[k].len;
+            clip_decayed[k + 1] = clip_decayed[k] + (clip_tiles[k].c != 0.f ? clip_tiles[k].len : 0);
+        }
+    }
+    void set_grad_clip(float cn) {
+        if (!(cn >= 0.f)) throw P3dError("gradient clipping: clip_norm must be 0 (off), positive or +inf, not negative or NaN");
+        HIPCHECK(hipStreamSynchronize(stream));
+        clip_norm = cn;
+        clip_have = false;
+        if (clip_on()) build_clip_table();
+        drop_step_graph();      // the threshold is a launch argument, and the launch list differs
+    }
+    // the launch over the chunks of [lo, hi), which must start and end between variables
+    SumsqArgs sumsq_args(int64_t lo, int64_t hi, double* elems, double* decayed) const {
+        auto at = [&](int64_t off) {
+            return (int)(std::lower_bound(clip_tiles.begin(), clip_tiles.end(), off,
+                                          [](const P3dRegTile& t, int64_t o) { return t.off < o; }) - clip_tiles.begin());
+        };
+        SumsqArgs a;
+        a.k0 = at(lo); a.k1 = at(hi);
+        if (a.k1 <= a.k0 || clip_tiles[a.k0].off < lo || clip_tiles[a.k1 - 1].off + clip_tiles[a.k1 - 1].len > hi)
+            throw P3dError("gradient clipping: range is not on chunk boundaries");
+        *elems = (double)(clip_elems[a.k1] - clip_elems[a.k0]);
+        *decayed = (double)(clip_decayed[a.k1] - clip_decayed[a.k0]);
+        a.g = flat_g; a.p = flat_p; a.tiles = d_clip_tiles; a.tile_base = 0;
+        a.part = d_clip_part; a.nfold = lo == 0 ? (int)clip_tiles.size() : 0;
+        a.counter = d_clip_cnt; a.res = d_clip_res; a.clip_norm = clip_norm;
+        return a;
+    }
+    void sumsq_range(const Ctx& c, int64_t lo, int64_t hi) {
+        if (hi <= lo) return;
+        double elems = 0.0, decayed = 0.0;
+        const SumsqArgs a = sumsq_args(lo, hi, &elems, &decayed);
+        const LaunchDesc d = p3d_grad_sumsq_desc(a, elems, decayed);
+        launch(c, d.kernel, d.flops, d.bytes, [&]() { return p3d_grad_sumsq(a, c.s); });
+        if (!c.dry && lo == 0) clip_have = true;
+    }
+    void read_grad_norm(double* sumsq, double* norm, float* scale) {
+        if (!clip_on()) throw P3dError("gradient norm: clipping is off (p3d_set_grad_clip)");
+        if (!clip_have) throw P3dError("gradient norm: no train step or backward has run since p3d_set_grad_clip");
+        double r[3] = {0, 0, 0};
+        HIPCHECK(hipMemcpyAsync(r, d_clip_res, sizeof(r), hipMemcpyDeviceToHost, stream));
+        HIPCHECK(hipStreamSynchronize(stream));
+        if (sumsq) *sumsq = r[0];
+        if (norm) *norm = r[1];
+        if (scale) memcpy(scale, &r[2], sizeof(float));
+    }
 
     // ---- regularisation (p3d_set_regularization) ---------------------------------------------------
     // The flat range is cut into tiles of one coefficient each: every trainable's slot is cut at REG_TILE, a decayed variable's
@@ -325,6 +431,7 @@
         reg_tiles = std::move(tiles);
         reg_decayed.assign(reg_tiles.size() + 1, 0);
         for (size_t k = 0; k < reg_tiles.size(); ++k) reg_decayed[k + 1] = reg_decayed[k] + (reg_tiles[k].c != 0.f ? reg_tiles[k].len : 0);
+        if (clip_on()) build_clip_table();      // its chunks carry these coefficients
         drop_step_graph();
     }
     // adam_range's launch, from the handle: P3D_OPT_* are the UPD_* of p3d_kernels.h; with a term on, the tiles of [lo, hi), which
@@ -335,6 +442,7 @@
         a.p = flat_p + lo; a.g = flat_g + lo; a.m = flat_m + lo; a.v = flat_v + lo; a.n = (long)(hi - lo);
         a.lr = lr_t; a.lr_dev = lr_dev;
         a.b1 = b1; a.b2 = b2; a.eps = eps; a.momentum = momentum; a.nesterov = use_nesterov;
+        if (update && clip_on()) a.gscale = clip_scale_dev();
         if (!reg_terms) return a;
         auto at = [&](int64_t off) {
             return (int)(std::lower_bound(reg_tiles.begin(), reg_tiles.end(), off,
@@ -369,6 +477,7 @@
     hipGraphExec_t step_exec = nullptr;
     float graph_drop = -1.f; bool graph_f16 = false; ncclComm_t graph_comm = nullptr; float graph_b1 = 0, graph_b2 = 0, graph_eps = 0;
     int graph_reg = 0;
+    float graph_clip = 0.f;
     int graph_kind = P3D_OPT_ADAM; float graph_mom = 0.f; int graph_nesterov = 0;      // the optimiser the graph launches
     bool graph_disabled = false;
     unsigned long long* d_seed = nullptr; float* d_lr = nullptr;
@@ -399,6 +508,7 @@
         HIPCHECK(hipGraphInstantiate(&step_exec, step_graph, nullptr, nullptr, 0));
         graph_drop = drop; graph_f16 = pointwise_f16; graph_comm = comm; graph_b1 = b1; graph_b2 = b2; graph_eps = eps;
         graph_reg = reg_terms;
+        graph_clip = clip_norm;
         graph_kind = opt_kind; graph_mom = momentum; graph_nesterov = use_nesterov;
     }
     void train_step_device(float drop, uint64_t seed) {
@@ -410,7 +520,7 @@
             return;
         }
         if (!step_exec || graph_drop != drop || graph_f16 != pointwise_f16 || graph_comm != comm || graph_b1 != b1 || graph_b2 != b2 ||
-            graph_eps != eps || graph_reg != reg_terms || graph_kind != opt_kind || graph_mom != momentum ||
+            graph_eps != eps || graph_reg != reg_terms || graph_clip != clip_norm || graph_kind != opt_kind || graph_mom != momentum ||
             graph_nesterov != use_nesterov) {
             try {
                 capture_step_graph(drop);

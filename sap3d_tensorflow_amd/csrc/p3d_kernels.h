@@ -568,10 +568,37 @@ struct OptArgs {
     float momentum = 0.f; int nesterov = 0;          // Momentum
     const P3dRegTile* tiles = nullptr; int ntile = 0; long long tile_base = 0;      // the decay part (ntile == 0: none)
     double* part = nullptr; const double* fold_part = nullptr; int nfold = 0; unsigned* counter = nullptr; double* term = nullptr;
+    const float* gscale = nullptr;      // clipping: the *_scaled_kernel forms (below); null launches the kernels above, unchanged
 };
+// gscale non-null (p3d_set_grad_clip): a device float s, read once per block; the update runs on g'' = fmul(g', s) wherever it
+// uses g' above, rounded once and not fused into the update (g' = g without a decay part).  g is still written back as g', never
+// as g''.  fmul(g', 1.0f) == g', so s = 1 gives the unscaled kernels' bits.  Refused under UPD_NONE.
 // decayed_elems: the elements of [p, p + n) whose tile has c != 0 (they cost 4 operations and the gradient written back)
 LaunchDesc p3d_opt_desc(const OptArgs& a, double decayed_elems);
 hipError_t p3d_opt_step(const OptArgs& a, hipStream_t s);
+// ---- global gradient norm (p3d_set_grad_clip): grad_sumsq_kernel ---------------------------------------------------------------
+// A chunk table (P3dRegTile: off relative to tile_base, len >= 1, ascending, not overlapping; elements between chunks -- slot
+// padding -- belong to no chunk and are never read) cuts the gradients into pieces of one coefficient c each.  One launch sums
+// chunks [k0, k1): part[k] = sum over chunk k of (double)g' * (double)g', g' = fadd(g, fmul(c, p)) in float32 without contraction
+// where c != 0 (decay_body's g'), g' = g where c == 0 (p is not read).  Each square is exact in double; the sum runs in a fixed
+// order that depends on the chunk's address alone.  nfold > 0 (the table's length; this launch is the last one on the stream,
+// *counter zero at launch): the last block to arrive folds part[0 .. nfold) in a fixed order and writes
+//   res[0] = sumsq, res[1] = norm = sqrt(sumsq) (double), and the float at res + 2:
+//   scale = NaN where norm is NaN or inf; 1.0f where clip_norm is +inf; else (float)(clip_norm / max(norm, clip_norm)), both
+//   in double -- exactly 1.0f whenever norm <= clip_norm.
+// The three are the same bits however the table is cut into launches and whatever the grid (max_blocks; 0: the default cap).
+constexpr int P3D_SUMSQ_MAX_BLOCKS = 2048;
+struct SumsqArgs {
+    const float* g = nullptr; const float* p = nullptr;      // p may be null when every c is 0
+    const P3dRegTile* tiles = nullptr; long long tile_base = 0;
+    int k0 = 0, k1 = 0;
+    double* part = nullptr;      // the whole table's partials
+    int nfold = 0; unsigned* counter = nullptr; double* res = nullptr;
+    float clip_norm = 0.f;
+    int max_blocks = 0;
+};
+LaunchDesc p3d_grad_sumsq_desc(const SumsqArgs& a, double elems, double decayed_elems);
+hipError_t p3d_grad_sumsq(const SumsqArgs& a, hipStream_t s);
 // per-step scalars of a captured train step: scal[0..1] = dropout seed (64 bit), scal[2] = the optimiser's step size (opt_step_size)
 hipError_t p3d_set_step_scalars(unsigned long long* seed_dst, float* lr_dst, unsigned long long seed, float lr_t, hipStream_t s);
 

@@ -412,27 +412,57 @@ def map_loss(logits, pred, target, maps, map_elems, through_sigmoid=True, offset
     return acc.value, dl, per_map, tuple(info)
 
 
-def adam(p, g, m, v, t, lr=1e-4, b1=0.9, b2=0.999, eps=1e-8, lr_on_device=False, offset=0, device=0):
+def _opt_scaled(kind, p, g, m, v, tiles, t, lr, b1, b2, eps, momentum, use_nesterov, lr_on_device, gscale, offset, device):
+    """p3d_debug_opt_scaled on copies already made: any optimiser launch with clipping's scale.  Returns (term, step size)."""
+    i64 = C.POINTER(C.c_int64)
+    offs = lens = cs = None
+    if tiles is not None:
+        lens = np.array([int(n) for n, _ in tiles], np.int64)
+        offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+        cs = np.array([c for _, c in tiles], np.float32)
+    term, lr_t = C.c_double(), C.c_float()
+    check(lib().p3d_debug_opt_scaled(device, int(kind), fptr(p), fptr(g), fptr(m), fptr(v), p.size, int(offset),
+                                     offs.ctypes.data_as(i64) if tiles is not None else None,
+                                     lens.ctypes.data_as(i64) if tiles is not None else None, fptr(cs),
+                                     len(tiles) if tiles is not None else 0, float(lr), int(t), float(b1), float(b2), float(eps),
+                                     float(momentum), 1 if use_nesterov else 0, 1 if lr_on_device else 0,
+                                     float(np.float32(gscale)), C.byref(term), C.byref(lr_t)))
+    return term.value, lr_t.value
+
+
+def adam(p, g, m, v, t, lr=1e-4, b1=0.9, b2=0.999, eps=1e-8, lr_on_device=False, offset=0, device=0, gscale=None):
     """Test hook: one launch of the network's Adam kernel (p3d_debug_adam) on flat float32 arrays, step t (1-based).  Returns
-    (p, m, v after the step, the float32 step size lr * sqrt(1 - b2^t) / (1 - b1^t) it used)."""
+    (p, m, v after the step, the float32 step size lr * sqrt(1 - b2^t) / (1 - b1^t) it used).  gscale: clipping's float32
+    scale, read from device memory; the step runs on float32(g * gscale) (adam_scaled_kernel)."""
     p, m, v = (_f32(a).ravel().copy() for a in (p, m, v))
     g = _f32(g).ravel()
     if not (p.size == g.size == m.size == v.size):
         raise ValueError("p, g, m, v differ in size")
+    if gscale is not None:
+        _, step = _opt_scaled(OPTIMIZERS["adam"], p, g.copy(), m, v, None, t, lr, b1, b2, eps, 0.0, False, lr_on_device, gscale, offset,
+                              device)
+        return p, m, v, step
     lr_t = C.c_float()
     check(lib().p3d_debug_adam(device, fptr(p), fptr(g), fptr(m), fptr(v), p.size, int(offset), float(lr), int(t), float(b1),
                                float(b2), float(eps), 1 if lr_on_device else 0, C.byref(lr_t)))
     return p, m, v, lr_t.value
 
 
-def adam_decay(p, g, m, v, tiles, t, lr=1e-4, b1=0.9, b2=0.999, eps=1e-8, lr_on_device=False, update=True, offset=0, device=0):
+def adam_decay(p, g, m, v, tiles, t, lr=1e-4, b1=0.9, b2=0.999, eps=1e-8, lr_on_device=False, update=True, offset=0, device=0,
+               gscale=None):
     """Test hook: one launch of the regularised optimiser step (p3d_debug_adam_decay) on flat float32 arrays.  tiles = [(length,
     coefficient), ...] cut [0, n) in order; each gets one float32 coefficient c, and g' = g + c p.  With update, p, m, v take
     Adam's step t on g'; without, only g changes.  Returns (g', p, m, v, the term sum 0.5 c sum(p^2) in double, the float32
-    step size)."""
+    step size).  gscale: clipping's scale; the step runs on float32(g' * gscale), g' comes back unscaled."""
     p, g, m, v = (_f32(a).ravel().copy() for a in (p, g, m, v))
     if not (p.size == g.size == m.size == v.size):
         raise ValueError("p, g, m, v differ in size")
+    if gscale is not None:
+        if not update:
+            raise ValueError("gscale: the gradient-only launch scales nothing")
+        term, step = _opt_scaled(OPTIMIZERS["adam"], p, g, m, v, tiles, t, lr, b1, b2, eps, 0.0, False, lr_on_device, gscale, offset,
+                                 device)
+        return g, p, m, v, term, step
     lens = np.array([int(n) for n, _ in tiles], np.int64)
     offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
     cs = np.array([c for _, c in tiles], np.float32)
@@ -451,26 +481,37 @@ def _opt_kind(kind):
     return k
 
 
-def optimizer(kind, p, g, m, lr=1e-4, momentum=0.9, use_nesterov=False, lr_on_device=False, offset=0, device=0):
+def optimizer(kind, p, g, m, lr=1e-4, momentum=0.9, use_nesterov=False, lr_on_device=False, offset=0, device=0, gscale=None):
     """Test hook: one launch of the Momentum or SGD step (p3d_debug_optimizer, kind "momentum" | "sgd") on flat float32 arrays
-    placed `offset` elements into the device buffers; m is Momentum's accumulator.  Returns (p, m) after the step."""
+    placed `offset` elements into the device buffers; m is Momentum's accumulator.  Returns (p, m) after the step.  gscale:
+    clipping's scale; the step runs on float32(g * gscale)."""
     k = _opt_kind(kind)
     p, g, m = (_f32(a).ravel().copy() for a in (p, g, m))
     if not (p.size == g.size == m.size):
         raise ValueError("p, g, m differ in size")
+    if gscale is not None:
+        _opt_scaled(k, p, g, m, np.zeros_like(p), None, 1, lr, 0.0, 0.0, 0.0, momentum, use_nesterov, lr_on_device, gscale, offset, device)
+        return p, m
     check(lib().p3d_debug_optimizer(device, k, fptr(p), fptr(g), fptr(m), p.size, int(offset), float(lr), float(momentum),
                                     1 if use_nesterov else 0, 1 if lr_on_device else 0))
     return p, m
 
 
 def optimizer_decay(kind, p, g, m, tiles, lr=1e-4, momentum=0.9, use_nesterov=False, lr_on_device=False, update=True, offset=0,
-                    device=0):
+                    device=0, gscale=None):
     """Test hook: adam_decay's launch with Momentum or SGD as the update (p3d_debug_optimizer_decay).  tiles = [(length,
-    coefficient), ...] cut [0, n) in order, g' = g + c p.  Returns (g', p, m, the term sum 0.5 c sum(p^2) in double)."""
+    coefficient), ...] cut [0, n) in order, g' = g + c p.  Returns (g', p, m, the term sum 0.5 c sum(p^2) in double).  gscale:
+    clipping's scale; the step runs on float32(g' * gscale), g' comes back unscaled."""
     k = _opt_kind(kind)
     p, g, m = (_f32(a).ravel().copy() for a in (p, g, m))
     if not (p.size == g.size == m.size):
         raise ValueError("p, g, m differ in size")
+    if gscale is not None:
+        if not update:
+            raise ValueError("gscale: the gradient-only launch scales nothing")
+        term, _ = _opt_scaled(k, p, g, m, np.zeros_like(p), tiles, 1, lr, 0.0, 0.0, 0.0, momentum, use_nesterov, lr_on_device, gscale,
+                              offset, device)
+        return g, p, m, term
     lens = np.array([int(n) for n, _ in tiles], np.int64)
     offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
     cs = np.array([c for _, c in tiles], np.float32)
@@ -480,6 +521,45 @@ def optimizer_decay(kind, p, g, m, tiles, lr=1e-4, momentum=0.9, use_nesterov=Fa
                                           lens.ctypes.data_as(i64), fptr(cs), len(tiles), float(lr), float(momentum),
                                           1 if use_nesterov else 0, 1 if lr_on_device else 0, 1 if update else 0, C.byref(term)))
     return g, p, m, term.value
+
+
+GRAD_NORM_CHUNK = 8192      # the cut of the flat gradient range (REG_TILE of the network)
+
+
+def grad_norm(g, clip_norm, p=None, tiles=None, ranges=None, offset=0, blocks=0, device=0):
+    """Test hook: the global-norm reduction of P3DSession.set_grad_clip (grad_sumsq_kernel, p3d_debug_grad_norm) on a flat
+    float32 gradient placed `offset` (0..3) elements into the device buffer.  tiles = [(length, coefficient), ...] cut [0, n) in
+    order: a tile with a float coefficient c is one chunk on which g' = float32(g + float32(c p)) (p is needed when any c != 0);
+    a tile whose coefficient is None is slot padding, which belongs to no chunk and is never read.  Without tiles, [0, n) is cut
+    every GRAD_NORM_CHUNK elements with c = 0.  ranges = [(lo, hi), ...] are launched in that order, the last one folding
+    (default: one launch over everything); each must start and end between chunks.  blocks caps the grid (0: the step's cap).
+    Returns (sumsq, norm) in float64 and the float32 scale = clip_norm / max(norm, clip_norm) (1 under inf, NaN when the norm is
+    not finite)."""
+    g = _f32(g).ravel()
+    n = g.size
+    if p is not None:
+        p = _f32(p).ravel()
+        if p.size != n:
+            raise ValueError("g and p differ in size")
+    if tiles is None:
+        tiles = [(min(GRAD_NORM_CHUNK, n - a), 0.0) for a in range(0, n, GRAD_NORM_CHUNK)]
+    offs, lens, cs, at = [], [], [], 0
+    for length, c in tiles:
+        if c is not None:
+            offs.append(at); lens.append(int(length)); cs.append(c)
+        at += int(length)
+    if at != n:
+        raise ValueError("tiles must cover [0, n)")
+    offs, lens, cs = np.array(offs, np.int64), np.array(lens, np.int64), np.array(cs, np.float32)
+    ranges = [(0, n)] if ranges is None else list(ranges)
+    lo = np.array([int(a) for a, _ in ranges], np.int64)
+    hi = np.array([int(b) for _, b in ranges], np.int64)
+    i64 = C.POINTER(C.c_int64)
+    ss, nm, sc = C.c_double(), C.c_double(), C.c_float()
+    check(lib().p3d_debug_grad_norm(device, fptr(g), fptr(p), n, int(offset), offs.ctypes.data_as(i64), lens.ctypes.data_as(i64),
+                                    fptr(cs), len(offs), lo.ctypes.data_as(i64), hi.ctypes.data_as(i64), len(ranges),
+                                    float(np.float32(clip_norm)), int(blocks), C.byref(ss), C.byref(nm), C.byref(sc)))
+    return ss.value, nm.value, np.float32(sc.value)
 
 
 def stat_parts(xshape, fshape, strides, transpose=False):

@@ -320,6 +320,26 @@ class P3DSession:
         check(lib().p3d_param_regularization(self._h, name.encode(), C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def set_grad_clip(self, clip_norm):
+        """Clip the gradients of every train step by their global norm, as tf.clip_by_global_norm ahead of apply_gradients
+        (an addition: the reference trains with Adam alone).  The norm is taken over every trainable element of the gradient the
+        optimiser is about to apply (with the regularisation's part when that is on), in double, in a fixed order; the update
+        runs on float32(g * scale), scale = float32(clip_norm / max(norm, clip_norm)), which is exactly 1 while the norm stays
+        under the threshold.  float("inf") measures only; 0 (or None) switches the option off, the default.  last_grad_norm()
+        reads the step's values."""
+        cn = 0.0 if clip_norm is None else float(clip_norm)
+        if not cn >= 0.0:
+            raise ValueError("clip_norm %r: 0 (off), a positive number or inf" % (clip_norm,))
+        check(lib().p3d_set_grad_clip(self._h, cn))
+
+    def last_grad_norm(self, with_sumsq=False):
+        """(norm, scale) of the last train step or backward with set_grad_clip on: the float64 global norm and the float32
+        factor the step applied (backward applies none); (norm, scale, sumsq) with_sumsq.  Raises while the option is off or
+        before the first step."""
+        ss, nm, sc = C.c_double(), C.c_double(), C.c_float()
+        check(lib().p3d_get_grad_norm(self._h, C.byref(ss), C.byref(nm), C.byref(sc)))
+        return (nm.value, sc.value, ss.value) if with_sumsq else (nm.value, sc.value)
+
     def predict_windows(self, x):
         """B windows of gen_pred.py:100-168 at once: row k equals forward(x[k:k+1], training=False) of a batch-1
         session, i.e. every batch-statistics BN normalises each clip by its own statistics."""
