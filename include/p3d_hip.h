@@ -556,6 +556,13 @@ int p3d_metric_auc_shuffled(int device, const float* sal, const float* fix, cons
 int p3d_eval_last_frames(p3d_handle* h, const unsigned char* density, int Hd, int Wd, const unsigned char* fixation, int H, int W,
                          const double* jitter, const int* borji_idx, const int* n_fix, int n_rep, double step_size, double* out,
                          double* stage_ms);
+/* Test hook: the launches of p3d_eval_last_frames (one shared sequence: uploads, float32 resize, density, the metric passes,
+ * read-back, the n_fix check) on maps the caller supplies instead of the handle's prediction.  maps [n_maps][h][w][elem_stride]
+ * float32, channel 0 is scored (elem_stride > 1: how the prediction buffer is addressed); density [n_maps][Hd][Wd], fixation
+ * [n_maps][H][W], jitter, borji_idx, n_fix[n_maps] and out[n_maps][5] as above (tests/test_gpu_eval_maps.py). */
+int p3d_debug_eval_maps(int device, const float* maps, int n_maps, int h, int w, int elem_stride, const unsigned char* density,
+                        int Hd, int Wd, const unsigned char* fixation, int H, int W, const double* jitter, const int* borji_idx,
+                        const int* n_fix, int n_rep, double step_size, double* out);
 
 /* ---- gen_pred.py's write-out (gen_pred.py:154-168): every emitted 112x112 map as an 8-bit image at 1080x960.
  * cv2.imwrite(name, cv2.resize(float64(map * 255.), (W, H))) per map: the float32 product map * scale widened to double,

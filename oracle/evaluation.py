@@ -59,7 +59,8 @@ def test_py_clip_metrics(prediction, density_u8, fixation_u8, jitter=True, n_rep
       * CC and SIM see the clean map; AUC_Judd adds random.rand(H, W) * 1e-7 IN PLACE (utils/metrics.py:54,65: np.array(...,
         copy=False) then +=, a float64 sum rounded once to float32), so AUC_Borji and NSS see the jittered map;
       * draws from `rng` (default numpy's global stream): jitter, then randint(0, H*W, [n_fix, n_rep]) (:139); a clip without
-        fixation draws nothing (both return NaN first, :56-59 and :122-124)."""
+        fixation draws nothing (both return NaN first, :56-59 and :122-124);
+      * `jitter` may be the noise array itself (float64 [H, W], random.rand * 1e-7 already applied): then it is not drawn."""
     from . import dataflow
     H, W = np.shape(fixation_u8)
     src = rng if rng is not None else np.random
@@ -70,8 +71,12 @@ def test_py_clip_metrics(prediction, density_u8, fixation_u8, jitter=True, n_rep
     n_fix = int(np.count_nonzero(fixation > 0.5))
     if n_fix == 0:
         return np.array(out + [np.nan, np.nan, NSS(pred, fixation)])
-    if jitter:
-        pred = (pred.astype(np.float64) + src.rand(H, W) * 1e-7).astype(np.float32)        # numpy's float32 += float64
+    if jitter is not None and not np.isscalar(jitter):
+        noise = np.asarray(jitter, dtype=np.float64).reshape(H, W)
+    else:
+        noise = src.rand(H, W) * 1e-7 if jitter else None
+    if noise is not None:
+        pred = (pred.astype(np.float64) + noise).astype(np.float32)        # numpy's float32 += float64
     out.append(AUC_Judd(pred, fixation))
     out.append(AUC_Borji(pred, fixation, src.randint(0, H * W, [n_fix, n_rep]), step_size)[0])
     out.append(NSS(pred, fixation))

@@ -159,6 +159,8 @@ SIGNATURES = {
     "p3d_metric_auc_shuffled": (C.c_int, [C.c_int, _fp, _fp, _ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _dp]),
     "p3d_eval_last_frames": (C.c_int, [C.c_void_p, C.POINTER(C.c_ubyte), C.c_int, C.c_int, C.POINTER(C.c_ubyte), C.c_int, C.c_int,
                                        _dp, _ip, _ip, C.c_int, C.c_double, _dp, _dp]),
+    "p3d_debug_eval_maps": (C.c_int, [C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ubyte), C.c_int, C.c_int,
+                                      C.POINTER(C.c_ubyte), C.c_int, C.c_int, _dp, _ip, _ip, C.c_int, C.c_double, _dp]),
     "p3d_resize_linear_u8": (C.c_int, [C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_ubyte)]),
     "p3d_pred_maps_u8": (C.c_int, [C.c_void_p, _ip, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_ubyte), _dp]),
     "p3d_crc32c": (C.c_uint32, [C.c_void_p, C.c_size_t, C.c_uint32]),

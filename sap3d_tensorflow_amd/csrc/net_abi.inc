@@ -2030,6 +2030,86 @@ void check_indices(const int* idx, size_t n, long long n_pix, const char* what) 
     for (size_t i = 0; i < n; ++i)
         if (idx[i] < 0 || idx[i] >= n_pix) throw P3dError(std::string(what) + ": random index out of range");
 }
+// Source maps of one evaluation: map m's pixel (y, x) at p[m * map_stride + (y * w + x) * elem_stride] (device memory)
+struct EvalSource { const float* p; long long map_stride; int elem_stride, n_maps, h, w; };
+// The device pass of test.py's per-batch body on stream s, with the scratch of s: everything of p3d_eval_last_frames that does
+// not need the handle, so that p3d_debug_eval_maps runs the same launches on maps of the caller's.  Checks the arguments, lays
+// the buffers out in the stream's scratch, uploads, resizes the source maps (float32) and the density maps (uint8), runs the
+// metric passes, reads out[n_maps][5] back and compares n_fix with the device's counts.  prepare (or null) queues whatever makes
+// the source maps readable; it runs after the uploads, inside the metric stage's time.
+void eval_maps(hipStream_t s, const EvalSource& src, const std::function<void(hipStream_t)>& prepare, const unsigned char* density, int Hd, int Wd, const unsigned char* fixation, int H,
+               int W, const double* jitter, const int* borji_idx, const int* n_fix, int n_rep, double step_size, double* out,
+               double* stage_ms) {
+    if (!src.p || !density || !fixation || !n_fix || !out) throw P3dError("null argument");
+    if (Hd < 1 || Wd < 1 || H < 1 || W < 1) throw P3dError("eval: empty map");
+    if ((long long)H * W > INT32_MAX / 2) throw P3dError("eval: map too large");
+    if (n_rep < 1 || !(step_size > 0.0)) throw P3dError("eval: AUC_Borji needs n_rep >= 1 and a positive step");
+    const int B = src.n_maps;
+    const long long N = (long long)H * W;
+    size_t n_idx = 0;
+    const std::vector<int> meta = full_meta(n_fix, B, n_rep, N, n_idx);
+    if (n_idx > 0 && !borji_idx) throw P3dError("eval: null random indices");
+    check_indices(borji_idx, n_idx, N, "eval");
+    P3dFullMaps a;
+    P3dFullBorji r;
+    a.fix_u8 = 1; a.n_pix = N; a.n_maps = B; a.nblk = p3d_full_blocks(N); a.out = nullptr;
+    r.n_rand = -1; r.n_rep = n_rep; r.step = step_size;
+    float *P = nullptr, *D = nullptr;
+    unsigned char *dens = nullptr, *fixd = nullptr;
+    double *jit = nullptr, *dout = nullptr;
+    int* idx = nullptr;
+    auto layout = [&](Carve& c) {
+        P = c.take<float>((size_t)B * N);
+        D = c.take<float>((size_t)B * N);
+        dens = c.take<unsigned char>((size_t)B * Hd * Wd);
+        fixd = c.take<unsigned char>((size_t)B * N);
+        jit = c.take<double>(jitter ? (size_t)B * N : 0);
+        idx = c.take<int>(n_idx);
+        dout = c.take<double>((size_t)B * 5);
+        carve_full(c, a, r, meta);
+    };
+    Carve c;
+    layout(c);                                 // sizes the scratch
+    float* slab = nullptr;
+    unsigned* counters = nullptr;
+    HIPCHECK(p3d_stream_scratch(s, (c.off + 3) / 4, (size_t)B, &slab, &counters));
+    c = Carve{(char*)slab, 0};
+    layout(c);
+    a.P = P; a.D = D; a.fix = fixd; a.jit = jitter ? jit : nullptr; a.counter = counters; a.out = dout; r.idx = idx;
+
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    if (stage_ms)
+        for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
+    if (stage_ms) HIPCHECK(hipEventRecord(ev[0], s));
+    HIPCHECK(copy_now(dens, density, (size_t)B * Hd * Wd, hipMemcpyHostToDevice, s));
+    HIPCHECK(copy_now(fixd, fixation, (size_t)B * N, hipMemcpyHostToDevice, s));
+    if (jitter) HIPCHECK(copy_now(jit, jitter, (size_t)B * N * sizeof(double), hipMemcpyHostToDevice, s));
+    if (n_idx) HIPCHECK(copy_now(idx, borji_idx, n_idx * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHECK(copy_now((void*)a.meta, meta.data(), meta.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    if (stage_ms) HIPCHECK(hipEventRecord(ev[1], s));
+    if (prepare) prepare(s);
+    HIPCHECK(p3d_resize_f32(src.p, src.map_stride, src.elem_stride, B, src.h, src.w, P, H, W, s));
+    HIPCHECK(p3d_mapf_density(dens, B, Hd, Wd, D, H, W, s));                  // test.py's density: uint8 resize (dataflow.py:236-238)
+    HIPCHECK(p3d_full_moments(a, s));
+    HIPCHECK(p3d_full_rank(a, s));
+    HIPCHECK(p3d_full_borji(a, r, s));
+    if (stage_ms) HIPCHECK(hipEventRecord(ev[2], s));
+    std::vector<double> st((size_t)B * P3D_FULL_STATS);
+    HIPCHECK(copy_now(out, dout, (size_t)B * 5 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHECK(copy_now(st.data(), a.stats, st.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    if (stage_ms) {
+        float t0 = 0, t1 = 0;
+        HIPCHECK(hipEventElapsedTime(&t0, ev[0], ev[1]));
+        HIPCHECK(hipEventElapsedTime(&t1, ev[1], ev[2]));
+        stage_ms[0] = t0; stage_ms[1] = t1;
+        for (auto& e : ev) HIPCHECK(hipEventDestroy(e));
+    }
+    for (int b = 0; b < B; ++b)
+        if ((long long)st[(size_t)b * P3D_FULL_STATS + P3D_FULL_STAT_NFIX] != n_fix[b])
+            throw P3dError("eval: clip " + std::to_string(b) + ": n_fix = " + std::to_string(n_fix[b]) + " but its fixation map has " +
+                           std::to_string((long long)st[(size_t)b * P3D_FULL_STATS + P3D_FULL_STAT_NFIX]) + " fixated pixels");
+}
 }  // namespace
 extern "C" {
 
@@ -2087,80 +2167,29 @@ int p3d_eval_last_frames(p3d_handle* h, const unsigned char* density, int Hd, in
                          const double* jitter, const int* borji_idx, const int* n_fix, int n_rep, double step_size, double* out,
                          double* stage_ms) {
     API_BEGIN
-    if (!h || !density || !fixation || !n_fix || !out) throw P3dError("null argument");
-    if (Hd < 1 || Wd < 1 || H < 1 || W < 1) throw P3dError("eval: empty map");
-    if ((long long)H * W > INT32_MAX / 2) throw P3dError("eval: map too large");
-    if (n_rep < 1 || !(step_size > 0.0)) throw P3dError("eval: AUC_Borji needs n_rep >= 1 and a positive step");
+    if (!h) throw P3dError("null argument");
     HIPCHECK(hipSetDevice(h->cfg.device));
+    // the prediction of the last forward pass, frame T-1 of every clip: [B][T][h][w] with an element stride of ld floats
     Act* pr = h->pred;
-    const int B = pr->N, T = pr->D;
-    const long long N = (long long)H * W;
-    size_t n_idx = 0;
-    const std::vector<int> meta = full_meta(n_fix, B, n_rep, N, n_idx);
-    if (n_idx > 0 && !borji_idx) throw P3dError("eval: null random indices");
-    check_indices(borji_idx, n_idx, N, "eval");
-    P3dFullMaps a;
-    P3dFullBorji r;
-    a.fix_u8 = 1; a.n_pix = N; a.n_maps = B; a.nblk = p3d_full_blocks(N); a.out = nullptr;
-    r.n_rand = -1; r.n_rep = n_rep; r.step = step_size;
-    float *P = nullptr, *D = nullptr;
-    unsigned char *dens = nullptr, *fixd = nullptr;
-    double *jit = nullptr, *dout = nullptr;
-    int* idx = nullptr;
-    auto layout = [&](Carve& c) {
-        P = c.take<float>((size_t)B * N);
-        D = c.take<float>((size_t)B * N);
-        dens = c.take<unsigned char>((size_t)B * Hd * Wd);
-        fixd = c.take<unsigned char>((size_t)B * N);
-        jit = c.take<double>(jitter ? (size_t)B * N : 0);
-        idx = c.take<int>(n_idx);
-        dout = c.take<double>((size_t)B * 5);
-        carve_full(c, a, r, meta);
-    };
-    Carve c;
-    layout(c);                                 // sizes the scratch
-    float* slab = nullptr;
-    unsigned* counters = nullptr;
-    const hipStream_t s = h->stream;
-    HIPCHECK(p3d_stream_scratch(s, (c.off + 3) / 4, (size_t)B, &slab, &counters));
-    c = Carve{(char*)slab, 0};
-    layout(c);
-    a.P = P; a.D = D; a.fix = fixd; a.jit = jitter ? jit : nullptr; a.counter = counters; a.out = dout; r.idx = idx;
-
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    if (stage_ms)
-        for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
-    if (stage_ms) HIPCHECK(hipEventRecord(ev[0], s));
-    HIPCHECK(copy_now(dens, density, (size_t)B * Hd * Wd, hipMemcpyHostToDevice, s));
-    HIPCHECK(copy_now(fixd, fixation, (size_t)B * N, hipMemcpyHostToDevice, s));
-    if (jitter) HIPCHECK(copy_now(jit, jitter, (size_t)B * N * sizeof(double), hipMemcpyHostToDevice, s));
-    if (n_idx) HIPCHECK(copy_now(idx, borji_idx, n_idx * sizeof(int), hipMemcpyHostToDevice, s));
-    HIPCHECK(copy_now((void*)a.meta, meta.data(), meta.size() * sizeof(int), hipMemcpyHostToDevice, s));
-    if (stage_ms) HIPCHECK(hipEventRecord(ev[1], s));
-    // the prediction of the last forward pass, frame T-1 of every clip: [B][T][h][w] with a row stride of ld floats
-    if (pr->materialize && h->last_forward_fused) pr->materialize(s);
+    const int T = pr->D;
     const long long hw = (long long)pr->H * pr->W;
-    HIPCHECK(p3d_resize_f32(pr->p + (size_t)(T - 1) * hw * pr->ld, (long long)T * hw * pr->ld, pr->ld, B, pr->H, pr->W, P, H, W, s));
-    HIPCHECK(p3d_mapf_density(dens, B, Hd, Wd, D, H, W, s));                  // test.py's density: uint8 resize (dataflow.py:236-238)
-    HIPCHECK(p3d_full_moments(a, s));
-    HIPCHECK(p3d_full_rank(a, s));
-    HIPCHECK(p3d_full_borji(a, r, s));
-    if (stage_ms) HIPCHECK(hipEventRecord(ev[2], s));
-    std::vector<double> st((size_t)B * P3D_FULL_STATS);
-    HIPCHECK(copy_now(out, dout, (size_t)B * 5 * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHECK(copy_now(st.data(), a.stats, st.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHECK(hipStreamSynchronize(s));
-    if (stage_ms) {
-        float t0 = 0, t1 = 0;
-        HIPCHECK(hipEventElapsedTime(&t0, ev[0], ev[1]));
-        HIPCHECK(hipEventElapsedTime(&t1, ev[1], ev[2]));
-        stage_ms[0] = t0; stage_ms[1] = t1;
-        for (auto& e : ev) HIPCHECK(hipEventDestroy(e));
-    }
-    for (int b = 0; b < B; ++b)
-        if ((long long)st[(size_t)b * P3D_FULL_STATS + P3D_FULL_STAT_NFIX] != n_fix[b])
-            throw P3dError("eval: clip " + std::to_string(b) + ": n_fix = " + std::to_string(n_fix[b]) + " but its fixation map has " +
-                           std::to_string((long long)st[(size_t)b * P3D_FULL_STATS + P3D_FULL_STAT_NFIX]) + " fixated pixels");
+    std::function<void(hipStream_t)> prepare;
+    if (pr->materialize && h->last_forward_fused) prepare = pr->materialize;
+    eval_maps(h->stream, {pr->p + (size_t)(T - 1) * hw * pr->ld, (long long)T * hw * pr->ld, pr->ld, pr->N, pr->H, pr->W}, prepare,
+              density, Hd, Wd, fixation, H, W, jitter, borji_idx, n_fix, n_rep, step_size, out, stage_ms);
+    API_END
+}
+
+int p3d_debug_eval_maps(int device, const float* maps, int n_maps, int h, int w, int elem_stride, const unsigned char* density,
+                        int Hd, int Wd, const unsigned char* fixation, int H, int W, const double* jitter, const int* borji_idx,
+                        const int* n_fix, int n_rep, double step_size, double* out) {
+    API_BEGIN
+    metric_args(device, maps, maps, n_maps, 1, out);
+    if (h < 1 || w < 1 || elem_stride < 1) throw P3dError("eval: empty map");
+    const long long per_map = (long long)h * w * elem_stride;
+    DevArr<float> src((size_t)n_maps * per_map, maps);
+    eval_maps(nullptr, {src.p, per_map, elem_stride, n_maps, h, w}, nullptr, density, Hd, Wd, fixation, H, W, jitter, borji_idx, n_fix, n_rep,
+              step_size, out, nullptr);
     API_END
 }
 

@@ -135,3 +135,62 @@ def AUC_shuffled(saliency_map, fixation_map, other_map, n_rep=100, step_size=0.1
     check(lib().p3d_metric_auc_shuffled(device, _fp(a), _fp(b), r.ctypes.data_as(C.POINTER(C.c_int)), a.size, n_fix, r.shape[0],
                                         n_rep, float(step_size), _dp(out)))
     return float(np.mean(out))
+
+
+def eval_draws(fixation, jitter, n_rep, rng=None):
+    """The numpy draws of one test.py batch (test.py:166-176), shared by P3DSession.evaluate and evaluate_maps so that their
+    order cannot drift apart.  fixation: uint8 [B, H, W].  Per map, in order: AUC_Judd's random.rand(H, W) * 1e-7 (jitter=True,
+    utils/metrics.py:64-65), then AUC_Borji's random.randint(0, H*W, [n_fix, n_rep]) (:139); a map without fixation draws
+    nothing (:56-59, :122-124).  jitter: True, False / None, or the noise itself (float64 [B, H, W]: no rand draw).
+    -> (n_fix int32 [B], noise float64 [B, H, W] or None, the indices int32, concatenated)."""
+    src = rng if rng is not None else np.random
+    B, H, W = fixation.shape
+    n_fix = np.count_nonzero(fixation.reshape(B, -1) >= 128, axis=1).astype(np.int32)        # / 255. > 0.5
+    flag = jitter is None or np.isscalar(jitter)
+    draw = flag and bool(jitter)
+    if draw:
+        jit = np.zeros((B, H, W), np.float64)
+    elif flag:
+        jit = None
+    else:
+        jit = np.ascontiguousarray(jitter, dtype=np.float64)
+        if jit.shape != (B, H, W):
+            raise ValueError("jitter must have the fixation maps' shape %s" % ((B, H, W),))
+    idx = []
+    for b in range(B):
+        if n_fix[b] == 0:
+            continue
+        if draw:
+            jit[b] = src.rand(H, W) * 1e-7
+        idx.append(src.randint(0, H * W, [int(n_fix[b]), n_rep]).astype(np.int32).ravel())
+    idx = np.ascontiguousarray(np.concatenate(idx) if idx else np.zeros(0, np.int32))
+    return n_fix, jit, idx
+
+
+def evaluate_maps(maps, density, fixation, size=None, jitter=True, n_rep=100, step_size=0.1, rng=None, device=0):
+    """Test hook (p3d_debug_eval_maps): P3DSession.evaluate's device pass on supplied maps instead of a session's prediction ->
+    [n, 5] float64: CC, SIM, AUC_Judd, AUC_Borji, NSS.  maps: float32 [n, h, w], or [n, h, w, c] of which channel 0 is scored
+    (the way the prediction buffer is addressed); density uint8 [n, Hd, Wd]; fixation uint8 [n, H, W] with (H, W) == size
+    (default: the fixation maps' own).  The draws are evaluate's (eval_draws)."""
+    m = np.ascontiguousarray(maps, dtype=np.float32)
+    dens = np.ascontiguousarray(density)
+    fix = np.ascontiguousarray(fixation)
+    if m.ndim not in (3, 4) or m.size == 0:
+        raise ValueError("expected non-empty [n, h, w] or [n, h, w, c] maps")
+    if dens.dtype != np.uint8 or fix.dtype != np.uint8:
+        raise ValueError("density and fixation maps are uint8 images (cv2.IMREAD_GRAYSCALE)")
+    n = m.shape[0]
+    if dens.ndim != 3 or dens.shape[0] != n or fix.ndim != 3 or fix.shape[0] != n:
+        raise ValueError("expected %d density / fixation maps, [n, H, W]" % n)
+    H, W = fix.shape[1:] if size is None else ((size, size) if np.isscalar(size) else tuple(size))
+    if fix.shape[1:] != (H, W):
+        raise ValueError("fixation maps are %s, not %s" % (fix.shape[1:], (H, W)))
+    n_fix, jit, idx = eval_draws(fix, jitter, n_rep, rng)
+    out = np.empty((n, 5), np.float64)
+    u8 = C.POINTER(C.c_ubyte)
+    ip = C.POINTER(C.c_int)
+    check(lib().p3d_debug_eval_maps(device, _fp(m), n, m.shape[1], m.shape[2], m.shape[3] if m.ndim == 4 else 1, dens.ctypes.data_as(u8),
+                                    dens.shape[1], dens.shape[2], fix.ctypes.data_as(u8), int(H), int(W),
+                                    _dp(jit) if jit is not None else None, idx.ctypes.data_as(ip), n_fix.ctypes.data_as(ip),
+                                    int(n_rep), float(step_size), _dp(out)))
+    return out

@@ -6,6 +6,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import P3dConfig, P3dError, P3dOpTime, check, fptr, lib
+from .metrics import eval_draws
 
 STRUCTURES = {"unet": 0, "concat": 1, "gn_p3d": 2,     # train.py:149-154 --structure
               "unet++nonsa": 3,                          # p3d.py:401 p3d_unetplusplus_nonsa
@@ -412,17 +413,7 @@ class P3DSession:
         self.forward_device(training=False)
         self.synchronize()
         t1 = time.perf_counter()
-        src = rng if rng is not None else np.random
-        n_fix = np.count_nonzero(fix.reshape(B, -1) >= 128, axis=1).astype(np.int32)        # / 255. > 0.5
-        jit = np.zeros((B, H, W), np.float64) if jitter else None
-        idx = []
-        for b in range(B):
-            if n_fix[b] == 0:
-                continue
-            if jitter:
-                jit[b] = src.rand(H, W) * 1e-7
-            idx.append(src.randint(0, H * W, [int(n_fix[b]), n_rep]).astype(np.int32).ravel())
-        idx = np.ascontiguousarray(np.concatenate(idx) if idx else np.zeros(0, np.int32))
+        n_fix, jit, idx = eval_draws(fix, bool(jitter), n_rep, rng)
         t2 = time.perf_counter()
         out = np.empty((B, 5), np.float64)
         ms = (C.c_double * 2)()

@@ -7,6 +7,8 @@ import pytest
 from oracle import dataflow as odf
 from oracle import metrics as om
 
+from eval_maps_ref import reference_auc_judd_loop
+
 
 def _maps(seed, n=1, shape=(112, 112), fix_rate=0.02):
     rng = np.random.default_rng(seed)
@@ -44,16 +46,7 @@ def test_oracle_auc_judd_equals_the_reference_loop():
         if quant:
             s = np.floor(s * quant).astype(np.float32) / quant        # many equal values
         f = (rng.random((24, 20)) < 0.1).astype(np.float32)
-        S = s.ravel().astype(np.float64); F = f.ravel() > 0.5
-        S_fix = S[F]; n_fix = len(S_fix); n_pixels = len(S)
-        thresholds = sorted(S_fix, reverse=True)
-        tp = np.zeros(len(thresholds) + 2); fp = np.zeros(len(thresholds) + 2)
-        tp[-1] = 1; fp[-1] = 1
-        for k, thresh in enumerate(thresholds):
-            above_th = np.sum(S >= thresh)
-            tp[k + 1] = (k + 1) / float(n_fix)
-            fp[k + 1] = (above_th - k - 1) / float(n_pixels - n_fix)
-        want = (getattr(np, "trapezoid", None) or np.trapz)(tp, fp)
+        want = reference_auc_judd_loop(s, f)
         assert om.AUC_Judd(s, f) == pytest.approx(want, abs=1e-14)
 
 
