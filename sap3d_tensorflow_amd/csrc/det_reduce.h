@@ -29,6 +29,17 @@ __device__ __forceinline__ void p3d_store_wt(double* base, size_t index, double 
     const p3d_u32x2 u = {(unsigned)b, (unsigned)(b >> 32)};
     __builtin_amdgcn_raw_buffer_store_b64(u, rs, (int)(index * 8), 0, 16);
 }
+// The sum of one double per thread of a 256-thread block, the same bits in every thread: xor butterfly over each wave, lane 0 of
+// each wave to wsum[4], barrier, ((w0 + w1) + w2) + w3.  REUSE: wsum may still be read from an earlier sum -- one more barrier
+// before it is written.
+template <bool REUSE>
+__device__ __forceinline__ double p3d_block_sum(double v, double* wsum) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if (REUSE) __syncthreads();
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
 __device__ __forceinline__ bool p3d_last_block_wt(unsigned* counter, unsigned nblocks, int* lds_flag) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // every storing wave drains its write-through stores
     __syncthreads();

@@ -517,19 +517,14 @@ __device__ __forceinline__ void loss_body(const float* logits, const float* pred
         for (long long i = gtid; i < n; i += gsz)
             acc += loss_term<KIND>(need_z ? logits[i] : 0.f, need_p ? pred[i] : 0.f, target[i], through_sigmoid, dl[i]);
     }
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
     // per-block partial, then the last arriving block adds the partials in block order
-    if (threadIdx.x == 0) p3d_store_wt(part, blockIdx.x, wsum[0] + wsum[1] + wsum[2] + wsum[3]);
+    const double bsum = p3d_block_sum<false>(acc, wsum);
+    if (threadIdx.x == 0) p3d_store_wt(part, blockIdx.x, bsum);
     if (!p3d_last_block_wt(counter, gridDim.x, &last_flag)) return;
     double t = 0.0;
     for (unsigned b = threadIdx.x; b < gridDim.x; b += 256) t += part[b];
-    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = t;
-    __syncthreads();
-    if (threadIdx.x == 0) *loss_out += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    t = p3d_block_sum<true>(t, wsum);
+    if (threadIdx.x == 0) *loss_out += t;
 }
 // one kernel per kind: the launch lists and the profiles name the loss
 __global__ __launch_bounds__(256) void smooth_l1_kernel(const float* pred, const float* target, long long n,
@@ -552,155 +547,21 @@ __global__ __launch_bounds__(256) void l1_loss_kernel(const float* logits, const
 }
 
 // Gradient clipping (OptArgs::gscale): the update runs on g'' = fmul(g', scale), rounded once and never fused into what
-// follows; the scale is one float in device memory (grad_sumsq_kernel's), read once per block.  SCALED = false is the code of the
-// unscaled kernels, instruction for instruction.
+// follows; the scale is one float in device memory (grad_sumsq_kernel's), read once per block.
 template <bool SCALED>
 __device__ __forceinline__ float clip_scaled(float g, float s) {
 #pragma clang fp contract(off)
     return SCALED ? g * s : g;
 }
 
-__global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, float* m, float* v, long long n4,
-                                                   long long n, float lr_arg, const float* lr_dev, float b1, float b2, float eps) {
-    const float lr_t = lr_dev ? *lr_dev : lr_arg;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-        const long long e = i << 2;
-        if (e + 3 < n) {
-            const float4 gg = ld4(g + e);
-            float4 mm = ld4(m + e), vv = ld4(v + e), pp = ld4(p + e);
-            const float gs[4] = {gg.x, gg.y, gg.z, gg.w};
-            float ms[4] = {mm.x, mm.y, mm.z, mm.w}, vs[4] = {vv.x, vv.y, vv.z, vv.w}, ps[4] = {pp.x, pp.y, pp.z, pp.w};
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                ms[q] = b1 * ms[q] + (1.f - b1) * gs[q];
-                vs[q] = b2 * vs[q] + (1.f - b2) * gs[q] * gs[q];
-                ps[q] -= lr_t * ms[q] / (sqrtf(vs[q]) + eps);
-            }
-            st4(m + e, make_float4(ms[0], ms[1], ms[2], ms[3]));
-            st4(v + e, make_float4(vs[0], vs[1], vs[2], vs[3]));
-            st4(p + e, make_float4(ps[0], ps[1], ps[2], ps[3]));
-        } else {
-            for (long long q = e; q < n; ++q) {
-                const float gq = g[q];
-                const float mq = b1 * m[q] + (1.f - b1) * gq;
-                const float vq = b2 * v[q] + (1.f - b2) * gq * gq;
-                m[q] = mq; v[q] = vq;
-                p[q] -= lr_t * mq / (sqrtf(vq) + eps);
-            }
-        }
-    }
-}
-// adam_kernel on clip_scaled(g): a copy, so that adam_kernel itself compiles to what it did before there was one
-__global__ __launch_bounds__(256) void adam_scaled_kernel(float* p, const float* g, float* m, float* v, long long n4,
-                                                          long long n, float lr_arg, const float* lr_dev, float b1, float b2,
-                                                          float eps, const float* gscale) {
-    const float lr_t = lr_dev ? *lr_dev : lr_arg;
-    const float s = *gscale;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-        const long long e = i << 2;
-        if (e + 3 < n) {
-            const float4 gg = ld4(g + e);
-            float4 mm = ld4(m + e), vv = ld4(v + e), pp = ld4(p + e);
-            const float gs[4] = {clip_scaled<true>(gg.x, s), clip_scaled<true>(gg.y, s), clip_scaled<true>(gg.z, s),
-                                 clip_scaled<true>(gg.w, s)};
-            float ms[4] = {mm.x, mm.y, mm.z, mm.w}, vs[4] = {vv.x, vv.y, vv.z, vv.w}, ps[4] = {pp.x, pp.y, pp.z, pp.w};
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                ms[q] = b1 * ms[q] + (1.f - b1) * gs[q];
-                vs[q] = b2 * vs[q] + (1.f - b2) * gs[q] * gs[q];
-                ps[q] -= lr_t * ms[q] / (sqrtf(vs[q]) + eps);
-            }
-            st4(m + e, make_float4(ms[0], ms[1], ms[2], ms[3]));
-            st4(v + e, make_float4(vs[0], vs[1], vs[2], vs[3]));
-            st4(p + e, make_float4(ps[0], ps[1], ps[2], ps[3]));
-        } else {
-            for (long long q = e; q < n; ++q) {
-                const float gq = clip_scaled<true>(g[q], s);
-                const float mq = b1 * m[q] + (1.f - b1) * gq;
-                const float vq = b2 * v[q] + (1.f - b2) * gq * gq;
-                m[q] = mq; v[q] = vq;
-                p[q] -= lr_t * mq / (sqrtf(vq) + eps);
-            }
-        }
-    }
-}
-
-// tf.train.MomentumOptimizer / GradientDescentOptimizer (p3d_set_optimizer): TF's ApplyMomentum and ApplyGradientDescent with
-// every rounding written out -- contraction off and no fma anywhere, so that a numpy float32 replay is bit-exact:
-//   momentum  a = (a * mom) + g;  p = p - (lr * a)
-//   nesterov  a = (a * mom) + g;  p = p - ((g * lr) + ((a * mom) * lr))      (the updated a)
-//   sgd       p = p - (lr * g)
-// The same arithmetic on whole 4-groups and on the scalar tail of a range.
-template <int KIND>      // UPD_MOMENTUM or UPD_SGD
-__device__ __forceinline__ void opt_elem(float& p, float& a, float g, float lr_t, float mom, int nesterov) {
-#pragma clang fp contract(off)
-    if (KIND == UPD_SGD) {
-        p = p - lr_t * g;
-        return;
-    }
-    a = a * mom + g;
-    if (nesterov) p = p - (g * lr_t + (a * mom) * lr_t);
-    else p = p - lr_t * a;
-}
-
-// float4 grid-stride pass shaped like adam_kernel (n4 groups of four from element `head`, the last group cut at n); the `head`
-// (0..3) elements before the buffers' first 16-byte boundary go one by one in block 0.  SGD never touches m.
-template <int KIND, bool SCALED = false>
-__device__ __forceinline__ void opt_body(float* p, const float* g, float* m, long long n4, long long n, int head, float lr_t,
-                                         float mom, int nesterov, float s = 1.f) {
-    if (blockIdx.x == 0 && (int)threadIdx.x < head) {
-        const int q = threadIdx.x;
-        float pq = p[q], mq = KIND == UPD_MOMENTUM ? m[q] : 0.f;
-        opt_elem<KIND>(pq, mq, clip_scaled<SCALED>(g[q], s), lr_t, mom, nesterov);
-        if (KIND == UPD_MOMENTUM) m[q] = mq;
-        p[q] = pq;
-    }
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-        const long long e = head + (i << 2);
-        if (e + 3 < n) {
-            const float4 gg = ld4(g + e), pp = ld4(p + e);
-            const float gs[4] = {gg.x, gg.y, gg.z, gg.w};
-            float ps[4] = {pp.x, pp.y, pp.z, pp.w}, ms[4] = {0.f, 0.f, 0.f, 0.f};
-            if (KIND == UPD_MOMENTUM) {
-                const float4 mm = ld4(m + e);
-                ms[0] = mm.x; ms[1] = mm.y; ms[2] = mm.z; ms[3] = mm.w;
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) opt_elem<KIND>(ps[q], ms[q], clip_scaled<SCALED>(gs[q], s), lr_t, mom, nesterov);
-            if (KIND == UPD_MOMENTUM) st4(m + e, make_float4(ms[0], ms[1], ms[2], ms[3]));
-            st4(p + e, make_float4(ps[0], ps[1], ps[2], ps[3]));
-        } else {
-            for (long long q = e; q < n; ++q) {
-                float pq = p[q], mq = KIND == UPD_MOMENTUM ? m[q] : 0.f;
-                opt_elem<KIND>(pq, mq, clip_scaled<SCALED>(g[q], s), lr_t, mom, nesterov);
-                if (KIND == UPD_MOMENTUM) m[q] = mq;
-                p[q] = pq;
-            }
-        }
-    }
-}
-// one kernel per kind: the launch lists and the profiles name them
-__global__ __launch_bounds__(256) void momentum_kernel(float* p, const float* g, float* m, long long n4, long long n, int head,
-                                                       float lr_arg, const float* lr_dev, float mom, int use_nesterov) {
-    opt_body<UPD_MOMENTUM>(p, g, m, n4, n, head, lr_dev ? *lr_dev : lr_arg, mom, use_nesterov);
-}
-__global__ __launch_bounds__(256) void sgd_kernel(float* p, const float* g, long long n4, long long n, int head, float lr_arg,
-                                                  const float* lr_dev) {
-    opt_body<UPD_SGD>(p, g, nullptr, n4, n, head, lr_dev ? *lr_dev : lr_arg, 0.f, 0);
-}
-__global__ __launch_bounds__(256) void momentum_scaled_kernel(float* p, const float* g, float* m, long long n4, long long n, int head,
-                                                              float lr_arg, const float* lr_dev, float mom, int use_nesterov,
-                                                              const float* gscale) {
-    opt_body<UPD_MOMENTUM, true>(p, g, m, n4, n, head, lr_dev ? *lr_dev : lr_arg, mom, use_nesterov, *gscale);
-}
-__global__ __launch_bounds__(256) void sgd_scaled_kernel(float* p, const float* g, long long n4, long long n, int head, float lr_arg,
-                                                         const float* lr_dev, const float* gscale) {
-    opt_body<UPD_SGD, true>(p, g, nullptr, n4, n, head, lr_dev ? *lr_dev : lr_arg, 0.f, 0, *gscale);
-}
-
-// Regularisation (the decay part of OptArgs).  Every rounding is explicit, so that a numpy float32 replay is bit-exact: contraction is
-// off and the two fused multiply-adds are fmaf.  adam_kernel's own arithmetic, as this compiler contracts it: on a whole
-// float4 group m and v are single fmas over the rounded (1-b) g terms; on the scalar tail of a range nothing is fused.
+// The three updates, every rounding written out -- contraction off, and a fused multiply-add only where fmaf says so -- so that a
+// numpy float32 replay is bit-exact.
+// tf.train.AdamOptimizer (epsilon-hat form), the only place its arithmetic is written.  whole: the element's 4-group lies whole in
+// the launch range; m and v are then single fmas over the rounded (1-b) g terms, on the partial last group of a range nothing is
+// fused:
+//   whole     m = fma(b1, m, (1-b1) g);  v = fma(b2, v, ((1-b2) g) g)
+//   partial   m = (b1 m) + ((1-b1) g);   v = (b2 v) + (((1-b2) g) g)
+//   both      p = p - (lr m) / (sqrt(v) + eps)
 __device__ __forceinline__ void adam_elem(float& p, float& m, float& v, float g, float lr_t, float b1, float b2, float eps,
                                           bool whole) {
 #pragma clang fp contract(off)
@@ -714,142 +575,141 @@ __device__ __forceinline__ void adam_elem(float& p, float& m, float& v, float g,
     }
     p = p - (lr_t * m) / (sqrtf(v) + eps);
 }
-
-// One block per tile of uniform coefficient c: g' = g + c p (written back where c != 0), Adam on g' when UPDATE, and the tile's
-// 0.5 c sum(p^2) in double from the parameters before the update.  Elements of a 4-group shared with the neighbouring tile
-// (variables whose length is not a multiple of 4 end mid-group) go one by one, with the arithmetic of the group they are in.
-// KIND: the update on g', UPD_NONE for the gradient-only mode; Momentum keeps its accumulator in m, v is Adam's alone.
-// SCALED (clipping): g' is written back as it is; the update takes clip_scaled(g').
-template <int KIND, bool SCALED = false>
-__device__ __forceinline__ void decay_body(float* p, float* g, float* m, float* v, long long n, const P3dRegTile* tiles,
-                                           long long tile_base, float lr_arg, const float* lr_dev, float b1, float b2, float eps,
-                                           double* part, const double* fold_part, int nfold, unsigned* counter, double* term,
-                                           float mom = 0.f, int nesterov = 0, const float* gscale = nullptr) {
+// tf.train.MomentumOptimizer / GradientDescentOptimizer (p3d_set_optimizer): TF's ApplyMomentum and ApplyGradientDescent, no fma
+// anywhere and the same arithmetic on whole 4-groups and on the scalar tail of a range:
+//   momentum  a = (a * mom) + g;  p = p - (lr * a)
+//   nesterov  a = (a * mom) + g;  p = p - ((g * lr) + ((a * mom) * lr))      (the updated a)
+//   sgd       p = p - (lr * g)
+template <int KIND>      // UPD_MOMENTUM or UPD_SGD
+__device__ __forceinline__ void opt_elem(float& p, float& a, float g, float lr_t, float mom, int nesterov) {
 #pragma clang fp contract(off)
-    constexpr bool UPDATE = KIND != UPD_NONE, ADAM = KIND == UPD_ADAM;
+    if (KIND == UPD_SGD) {
+        p = p - lr_t * g;
+        return;
+    }
+    a = a * mom + g;
+    if (nesterov) p = p - (g * lr_t + (a * mom) * lr_t);
+    else p = p - lr_t * a;
+}
+// the update KIND on one element: Adam keeps m and v, Momentum its accumulator in m, SGD neither
+template <int KIND>
+__device__ __forceinline__ void upd_elem(const OptArgs& a, float lr_t, float& p, float& m, float& v, float g, bool whole) {
+    if constexpr (KIND == UPD_ADAM) adam_elem(p, m, v, g, lr_t, a.b1, a.b2, a.eps, whole);
+    else opt_elem<KIND>(p, m, g, lr_t, a.momentum, a.nesterov);
+}
+template <int KIND> constexpr bool HAS_M = KIND == UPD_ADAM || KIND == UPD_MOMENTUM;
+template <int KIND> constexpr bool HAS_V = KIND == UPD_ADAM;
+// one element / one float4 group of the update on clip_scaled(g): only the slots the kind has are loaded and stored
+template <int KIND, bool SCALED>
+__device__ __forceinline__ void upd_one(const OptArgs& a, float lr_t, float s, long long e, float g, bool whole) {
+    float pe = a.p[e], me = HAS_M<KIND> ? a.m[e] : 0.f, ve = HAS_V<KIND> ? a.v[e] : 0.f;
+    upd_elem<KIND>(a, lr_t, pe, me, ve, clip_scaled<SCALED>(g, s), whole);
+    if (HAS_M<KIND>) a.m[e] = me;
+    if (HAS_V<KIND>) a.v[e] = ve;
+    a.p[e] = pe;
+}
+template <int KIND, bool SCALED>
+__device__ __forceinline__ void upd_group(const OptArgs& a, float lr_t, float s, long long e, const float* gs, float4 pp) {
+    const float4 mm = HAS_M<KIND> ? ld4(a.m + e) : f4(0.f), vv = HAS_V<KIND> ? ld4(a.v + e) : f4(0.f);
+    float ps[4] = {pp.x, pp.y, pp.z, pp.w}, ms[4] = {mm.x, mm.y, mm.z, mm.w}, vs[4] = {vv.x, vv.y, vv.z, vv.w};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) upd_elem<KIND>(a, lr_t, ps[q], ms[q], vs[q], clip_scaled<SCALED>(gs[q], s), true);
+    if (HAS_M<KIND>) st4(a.m + e, make_float4(ms[0], ms[1], ms[2], ms[3]));
+    if (HAS_V<KIND>) st4(a.v + e, make_float4(vs[0], vs[1], vs[2], vs[3]));
+    st4(a.p + e, make_float4(ps[0], ps[1], ps[2], ps[3]));
+}
+
+// The dense pass: a float4 grid-stride loop over n4 groups of four from element `head`, the last group cut at n and taken one by
+// one; the `head` (0..3) elements before the buffers' first 16-byte boundary go one by one in block 0 (Adam: head = 0).
+template <int KIND, bool SCALED>
+__device__ __forceinline__ void opt_body(const OptArgs& a) {
+    const long long n = a.n;
+    const float lr_t = a.lr_dev ? *a.lr_dev : a.lr;
+    const float s = SCALED ? *a.gscale : 1.f;
+    if (blockIdx.x == 0 && (int)threadIdx.x < a.head) upd_one<KIND, SCALED>(a, lr_t, s, threadIdx.x, a.g[threadIdx.x], false);
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n4; i += (long long)gridDim.x * blockDim.x) {
+        const long long e = a.head + (i << 2);
+        if (e + 3 < n) {
+            const float4 gg = ld4(a.g + e);
+            const float gs[4] = {gg.x, gg.y, gg.z, gg.w};
+            upd_group<KIND, SCALED>(a, lr_t, s, e, gs, ld4(a.p + e));
+        } else {
+            for (long long q = e; q < n; ++q) upd_one<KIND, SCALED>(a, lr_t, s, q, a.g[q], false);
+        }
+    }
+}
+
+// Regularisation (the decay part of OptArgs), one block per tile of uniform coefficient c: g' = g + c p in float32 without
+// contraction (written back where c != 0), the update KIND on g' (UPD_NONE: the gradient-only mode), and the tile's 0.5 c sum(p^2)
+// in double from the parameters before the update.  Elements of a 4-group shared with the neighbouring tile (variables whose
+// length is not a multiple of 4 end mid-group) go one by one, with the arithmetic of the group they are in.
+// SCALED (clipping): g' is written back as it is; the update takes clip_scaled(g').
+template <int KIND, bool SCALED>
+__device__ __forceinline__ void decay_body(const OptArgs& a) {
+#pragma clang fp contract(off)
+    constexpr bool UPDATE = KIND != UPD_NONE;
     __shared__ double wsum[4];
     __shared__ int last_flag;
-    const P3dRegTile t = tiles[blockIdx.x];
-    const long long a = t.off - tile_base, b = a + t.len;
+    const P3dRegTile t = a.tiles[blockIdx.x];
+    const long long ta = t.off - a.tile_base, tb = ta + t.len;
     const float c = t.c;
-    const float lr_t = UPDATE ? (lr_dev ? *lr_dev : lr_arg) : 0.f;
-    const float gsc = SCALED ? *gscale : 1.f;
+    const float lr_t = UPDATE ? (a.lr_dev ? *a.lr_dev : a.lr) : 0.f;
+    const float s = SCALED ? *a.gscale : 1.f;
     double acc = 0.0;
     if (UPDATE || c != 0.f) {
-        const long long a4 = (a + 3) & ~3LL, b4 = max(a4, b & ~3LL);
+        const long long a4 = (ta + 3) & ~3LL, b4 = max(a4, tb & ~3LL);
         for (long long e = a4 + 4 * (long long)threadIdx.x; e < b4; e += 4 * 256) {
-            const float4 gg = ld4(g + e), pp = ld4(p + e);
-            float gs[4] = {gg.x, gg.y, gg.z, gg.w}, ps[4] = {pp.x, pp.y, pp.z, pp.w};
+            const float4 gg = ld4(a.g + e), pp = ld4(a.p + e);
+            float gs[4] = {gg.x, gg.y, gg.z, gg.w};
             if (c != 0.f) {
+                const float ps[4] = {pp.x, pp.y, pp.z, pp.w};
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     acc += (double)ps[q] * (double)ps[q];
                     gs[q] = gs[q] + c * ps[q];
                 }
-                st4(g + e, make_float4(gs[0], gs[1], gs[2], gs[3]));
+                st4(a.g + e, make_float4(gs[0], gs[1], gs[2], gs[3]));
             }
-            if (ADAM) {
-                const float4 mm = ld4(m + e), vv = ld4(v + e);
-                float ms[4] = {mm.x, mm.y, mm.z, mm.w}, vs[4] = {vv.x, vv.y, vv.z, vv.w};
-#pragma unroll
-                for (int q = 0; q < 4; ++q) adam_elem(ps[q], ms[q], vs[q], clip_scaled<SCALED>(gs[q], gsc), lr_t, b1, b2, eps, true);
-                st4(m + e, make_float4(ms[0], ms[1], ms[2], ms[3]));
-                st4(v + e, make_float4(vs[0], vs[1], vs[2], vs[3]));
-                st4(p + e, make_float4(ps[0], ps[1], ps[2], ps[3]));
-            } else if (UPDATE) {
-                float ms[4] = {0.f, 0.f, 0.f, 0.f};
-                if (KIND == UPD_MOMENTUM) {
-                    const float4 mm = ld4(m + e);
-                    ms[0] = mm.x; ms[1] = mm.y; ms[2] = mm.z; ms[3] = mm.w;
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) opt_elem<KIND>(ps[q], ms[q], clip_scaled<SCALED>(gs[q], gsc), lr_t, mom, nesterov);
-                if (KIND == UPD_MOMENTUM) st4(m + e, make_float4(ms[0], ms[1], ms[2], ms[3]));
-                st4(p + e, make_float4(ps[0], ps[1], ps[2], ps[3]));
-            }
+            if constexpr (UPDATE) upd_group<KIND, SCALED>(a, lr_t, s, e, gs, pp);
         }
-        if (threadIdx.x < 8) {      // threads 0-3: [a, a4), the head; 4-7: [b4, b), the tail (each under 4 elements)
-            const long long e = threadIdx.x < 4 ? a + threadIdx.x : b4 + threadIdx.x - 4;
-            if (threadIdx.x < 4 ? e < min(a4, b) : e < b) {
-                float pe = p[e], ge = g[e];
+        if (threadIdx.x < 8) {      // threads 0-3: [ta, a4), the head; 4-7: [b4, tb), the tail (each under 4 elements)
+            const long long e = threadIdx.x < 4 ? ta + threadIdx.x : b4 + threadIdx.x - 4;
+            if (threadIdx.x < 4 ? e < min(a4, tb) : e < tb) {
+                float ge = a.g[e];
                 if (c != 0.f) {
+                    const float pe = a.p[e];
                     acc += (double)pe * (double)pe;
                     ge = ge + c * pe;
-                    g[e] = ge;
+                    a.g[e] = ge;
                 }
-                if (ADAM) {
-                    float me = m[e], ve = v[e];
-                    adam_elem(pe, me, ve, clip_scaled<SCALED>(ge, gsc), lr_t, b1, b2, eps, (e & ~3LL) + 3 < n);
-                    m[e] = me; v[e] = ve; p[e] = pe;
-                } else if (UPDATE) {
-                    float me = KIND == UPD_MOMENTUM ? m[e] : 0.f;
-                    opt_elem<KIND>(pe, me, clip_scaled<SCALED>(ge, gsc), lr_t, mom, nesterov);
-                    if (KIND == UPD_MOMENTUM) m[e] = me;
-                    p[e] = pe;
-                }
+                if constexpr (UPDATE) upd_one<KIND, SCALED>(a, lr_t, s, e, ge, (e & ~3LL) + 3 < a.n);
             }
         }
     }
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) p3d_store_wt(part, blockIdx.x, 0.5 * (double)c * (wsum[0] + wsum[1] + wsum[2] + wsum[3]));
-    if (nfold <= 0) return;
-    if (!p3d_last_block_wt(counter, gridDim.x, &last_flag)) return;
-    double s = 0.0;
-    for (int k = threadIdx.x; k < nfold; k += 256) s += fold_part[k];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) *term = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    acc = p3d_block_sum<false>(acc, wsum);
+    if (threadIdx.x == 0) p3d_store_wt(a.part, blockIdx.x, 0.5 * (double)c * acc);
+    if (a.nfold <= 0) return;
+    if (!p3d_last_block_wt(a.counter, gridDim.x, &last_flag)) return;
+    double f = 0.0;
+    for (int k = threadIdx.x; k < a.nfold; k += 256) f += a.fold_part[k];
+    f = p3d_block_sum<true>(f, wsum);
+    if (threadIdx.x == 0) *a.term = f;
 }
-// one kernel per mode: the launch lists and the profiles name them
-__global__ __launch_bounds__(256) void adam_decay_kernel(float* p, float* g, float* m, float* v, long long n, const P3dRegTile* tiles,
-                                                         long long tile_base, float lr_arg, const float* lr_dev, float b1, float b2,
-                                                         float eps, double* part, const double* fold_part, int nfold,
-                                                         unsigned* counter, double* term) {
-    decay_body<UPD_ADAM>(p, g, m, v, n, tiles, tile_base, lr_arg, lr_dev, b1, b2, eps, part, fold_part, nfold, counter, term);
-}
-__global__ __launch_bounds__(256) void momentum_decay_kernel(float* p, float* g, float* m, long long n, const P3dRegTile* tiles,
-                                                             long long tile_base, float lr_arg, const float* lr_dev, float mom,
-                                                             int use_nesterov, double* part, const double* fold_part, int nfold,
-                                                             unsigned* counter, double* term) {
-    decay_body<UPD_MOMENTUM>(p, g, m, nullptr, n, tiles, tile_base, lr_arg, lr_dev, 0.f, 0.f, 0.f, part, fold_part, nfold, counter, term, mom,
-                  use_nesterov);
-}
-__global__ __launch_bounds__(256) void sgd_decay_kernel(float* p, float* g, long long n, const P3dRegTile* tiles, long long tile_base,
-                                                        float lr_arg, const float* lr_dev, double* part, const double* fold_part,
-                                                        int nfold, unsigned* counter, double* term) {
-    decay_body<UPD_SGD>(p, g, nullptr, nullptr, n, tiles, tile_base, lr_arg, lr_dev, 0.f, 0.f, 0.f, part, fold_part, nfold, counter, term);
-}
-__global__ __launch_bounds__(256) void adam_decay_scaled_kernel(float* p, float* g, float* m, float* v, long long n,
-                                                                const P3dRegTile* tiles, long long tile_base, float lr_arg,
-                                                                const float* lr_dev, float b1, float b2, float eps, double* part,
-                                                                const double* fold_part, int nfold, unsigned* counter, double* term,
-                                                                const float* gscale) {
-    decay_body<UPD_ADAM, true>(p, g, m, v, n, tiles, tile_base, lr_arg, lr_dev, b1, b2, eps, part, fold_part, nfold, counter, term, 0.f, 0,
-                               gscale);
-}
-__global__ __launch_bounds__(256) void momentum_decay_scaled_kernel(float* p, float* g, float* m, long long n, const P3dRegTile* tiles,
-                                                                    long long tile_base, float lr_arg, const float* lr_dev, float mom,
-                                                                    int use_nesterov, double* part, const double* fold_part,
-                                                                    int nfold, unsigned* counter, double* term, const float* gscale) {
-    decay_body<UPD_MOMENTUM, true>(p, g, m, nullptr, n, tiles, tile_base, lr_arg, lr_dev, 0.f, 0.f, 0.f, part, fold_part, nfold, counter,
-                                   term, mom, use_nesterov, gscale);
-}
-__global__ __launch_bounds__(256) void sgd_decay_scaled_kernel(float* p, float* g, long long n, const P3dRegTile* tiles,
-                                                               long long tile_base, float lr_arg, const float* lr_dev, double* part,
-                                                               const double* fold_part, int nfold, unsigned* counter, double* term,
-                                                               const float* gscale) {
-    decay_body<UPD_SGD, true>(p, g, nullptr, nullptr, n, tiles, tile_base, lr_arg, lr_dev, 0.f, 0.f, 0.f, part, fold_part, nfold, counter,
-                              term, 0.f, 0, gscale);
-}
-__global__ __launch_bounds__(256) void decay_grad_kernel(float* p, float* g, long long n, const P3dRegTile* tiles, long long tile_base,
-                                                         double* part, const double* fold_part, int nfold, unsigned* counter,
-                                                         double* term) {
-    decay_body<UPD_NONE>(p, g, nullptr, nullptr, n, tiles, tile_base, 0.f, nullptr, 0.f, 0.f, 0.f, part, fold_part, nfold, counter, term);
-}
+
+// one kernel per update, mode and scaling: the launch lists and the profiles name them (opt_kernels below)
+__global__ __launch_bounds__(256) void adam_kernel(OptArgs a) { opt_body<UPD_ADAM, false>(a); }
+__global__ __launch_bounds__(256) void momentum_kernel(OptArgs a) { opt_body<UPD_MOMENTUM, false>(a); }
+__global__ __launch_bounds__(256) void sgd_kernel(OptArgs a) { opt_body<UPD_SGD, false>(a); }
+__global__ __launch_bounds__(256) void adam_scaled_kernel(OptArgs a) { opt_body<UPD_ADAM, true>(a); }
+__global__ __launch_bounds__(256) void momentum_scaled_kernel(OptArgs a) { opt_body<UPD_MOMENTUM, true>(a); }
+__global__ __launch_bounds__(256) void sgd_scaled_kernel(OptArgs a) { opt_body<UPD_SGD, true>(a); }
+__global__ __launch_bounds__(256) void decay_grad_kernel(OptArgs a) { decay_body<UPD_NONE, false>(a); }
+__global__ __launch_bounds__(256) void adam_decay_kernel(OptArgs a) { decay_body<UPD_ADAM, false>(a); }
+__global__ __launch_bounds__(256) void momentum_decay_kernel(OptArgs a) { decay_body<UPD_MOMENTUM, false>(a); }
+__global__ __launch_bounds__(256) void sgd_decay_kernel(OptArgs a) { decay_body<UPD_SGD, false>(a); }
+__global__ __launch_bounds__(256) void adam_decay_scaled_kernel(OptArgs a) { decay_body<UPD_ADAM, true>(a); }
+__global__ __launch_bounds__(256) void momentum_decay_scaled_kernel(OptArgs a) { decay_body<UPD_MOMENTUM, true>(a); }
+__global__ __launch_bounds__(256) void sgd_decay_scaled_kernel(OptArgs a) { decay_body<UPD_SGD, true>(a); }
 
 // Global gradient norm (p3d_set_grad_clip; SumsqArgs in p3d_kernels.h).  Block b takes chunks k0 + b, k0 + b + gridDim.x, ... of
 // the table; chunk k's sum of g'^2 -- every square exact in double, one double accumulator per lane over a lane-to-element map
@@ -893,22 +753,15 @@ __global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* g, const f
         };
         for (long long e = a + threadIdx.x; e < a4; e += 256) one(e);       // under 4 elements each on the float4 path
         for (long long e = b4 + threadIdx.x; e < b; e += 256) one(e);
-        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-        __syncthreads();      // the previous chunk's wsum has been read
-        if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-        __syncthreads();
-        if (threadIdx.x == 0) p3d_store_wt(part, (size_t)k, ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3]);
+        acc = p3d_block_sum<true>(acc, wsum);      // its first barrier: the previous chunk's wsum has been read
+        if (threadIdx.x == 0) p3d_store_wt(part, (size_t)k, acc);
     }
     if (nfold <= 0) return;
     if (!p3d_last_block_wt(counter, gridDim.x, &last_flag)) return;
     double s = 0.0;
     for (int k = threadIdx.x; k < nfold; k += 256) s += part[k];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
-    __syncthreads();
+    const double sumsq = p3d_block_sum<true>(s, wsum);
     if (threadIdx.x == 0) {
-        const double sumsq = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
         const double norm = sqrt(sumsq), cn = (double)clip;
         float scale;
         if (!(norm - norm == 0.0)) scale = __builtin_nanf("");      // NaN or inf
@@ -1335,83 +1188,55 @@ hipError_t p3d_loss(const LossArgs& a, hipStream_t s, unsigned* done) {
     return hipGetLastError();
 }
 
+// The optimiser kernels by [scaled][decay][update + 1]: the name a launch is listed under and the kernel it runs.  Null: no such launch
+// (UPD_NONE without a decay part, and under clipping -- the gradient-only launch scales nothing).
+struct OptKernel { const char* name; void (*kernel)(OptArgs); };
+#define P3D_OPT_KERNEL(k) {#k, k}
+static const OptKernel opt_kernels[2][2][4] = {
+    {{{nullptr, nullptr}, P3D_OPT_KERNEL(adam_kernel), P3D_OPT_KERNEL(momentum_kernel), P3D_OPT_KERNEL(sgd_kernel)},
+     {P3D_OPT_KERNEL(decay_grad_kernel), P3D_OPT_KERNEL(adam_decay_kernel), P3D_OPT_KERNEL(momentum_decay_kernel),
+      P3D_OPT_KERNEL(sgd_decay_kernel)}},
+    {{{nullptr, nullptr}, P3D_OPT_KERNEL(adam_scaled_kernel), P3D_OPT_KERNEL(momentum_scaled_kernel), P3D_OPT_KERNEL(sgd_scaled_kernel)},
+     {{nullptr, nullptr}, P3D_OPT_KERNEL(adam_decay_scaled_kernel), P3D_OPT_KERNEL(momentum_decay_scaled_kernel),
+      P3D_OPT_KERNEL(sgd_decay_scaled_kernel)}}};
+#undef P3D_OPT_KERNEL
+static const OptKernel& opt_kernel(const OptArgs& a) { return opt_kernels[a.gscale ? 1 : 0][a.ntile ? 1 : 0][a.update + 1]; }
+
 LaunchDesc p3d_opt_desc(const OptArgs& a, double decayed_elems) {
     // per element Adam reads g, m, v, p and writes m, v, p (28 bytes); Momentum g, a, p and a, p (20); SGD g, p and p (12).  A
     // decayed element adds 2 operations for g + c w, 2 for the term and the gradient written back (12 bytes alone without an
     // update); a tile is 8 bytes of table and partial.  Clipping (gscale): one operation per element, 4 bytes read per block.
-    static const char* const name[2][2][4] = {{{nullptr, "adam_kernel", "momentum_kernel", "sgd_kernel"},
-                                               {"decay_grad_kernel", "adam_decay_kernel", "momentum_decay_kernel", "sgd_decay_kernel"}},
-                                              {{nullptr, "adam_scaled_kernel", "momentum_scaled_kernel", "sgd_scaled_kernel"},
-                                               {nullptr, "adam_decay_scaled_kernel", "momentum_decay_scaled_kernel",
-                                                "sgd_decay_scaled_kernel"}}};
     const double upd = (a.update == UPD_ADAM ? 28.0 : a.update == UPD_MOMENTUM ? 20.0 : 12.0) * a.n, nd = decayed_elems;
     const int sc = a.gscale ? 1 : 0;
-    if (!a.ntile) {
-        return {name[sc][0][a.update + 1], sc * (double)a.n, upd + sc * 4.0 * grid_for((a.n + 3) / 4)};
-    }
-    return {name[sc][1][a.update + 1], 4.0 * nd + sc * (double)a.n,
-            (a.update == UPD_NONE ? 12.0 * nd : upd + 4.0 * nd) + (8.0 + sc * 4.0) * a.ntile};
+    const char* name = opt_kernel(a).name;
+    if (!a.ntile) return {name, sc * (double)a.n, upd + sc * 4.0 * grid_for((a.n + 3) / 4)};
+    return {name, 4.0 * nd + sc * (double)a.n, (a.update == UPD_NONE ? 12.0 * nd : upd + 4.0 * nd) + (8.0 + sc * 4.0) * a.ntile};
 }
 
 hipError_t p3d_opt_step(const OptArgs& a, hipStream_t s) {
     const bool adam = a.update == UPD_ADAM, mom = a.update == UPD_MOMENTUM;
     if (a.n < 1 || a.ntile < 0 || a.update < UPD_NONE || a.update > UPD_SGD || (mom && !a.m)) return hipErrorInvalidValue;
-    if (a.gscale && a.update == UPD_NONE) return hipErrorInvalidValue;      // the gradient-only launch scales nothing
-    const long long n = a.n;
-    const int nesterov = a.nesterov ? 1 : 0;
+    const OptKernel& k = opt_kernel(a);
+    if (!k.kernel) return hipErrorInvalidValue;
+    OptArgs ka = a;      // what the kernel gets: a, and the dense pass's n4 and head
+    ka.n4 = 0; ka.head = 0;
+    unsigned grid = a.ntile;      // the decay part: one block per tile
     const uintptr_t r = low4(a.p);
     if (!a.ntile && !adam) {
         // p, g, m float-aligned and at the same place in a 16-byte line: the elements before the first 16-byte boundary go one by one
-        if (a.update == UPD_NONE || (r & 3) || low4(a.g) != r || (mom && low4(a.m) != r)) return hipErrorInvalidValue;
-        const int head = (int)std::min<long long>((long long)((16 - r) & 15) / 4, n);
-        const long long n4 = (n - head + 3) / 4;
-        const dim3 grid(n4 > 0 ? grid_for(n4) : 1u);
-        if (a.gscale) {
-            if (mom)
-                hipLaunchKernelGGL(momentum_scaled_kernel, grid, dim3(256), 0, s, a.p, a.g, a.m, n4, n, head, a.lr, a.lr_dev, a.momentum,
-                                   nesterov, a.gscale);
-            else hipLaunchKernelGGL(sgd_scaled_kernel, grid, dim3(256), 0, s, a.p, a.g, n4, n, head, a.lr, a.lr_dev, a.gscale);
-        } else if (mom) hipLaunchKernelGGL(momentum_kernel, grid, dim3(256), 0, s, a.p, a.g, a.m, n4, n, head, a.lr, a.lr_dev, a.momentum, nesterov);
-        else hipLaunchKernelGGL(sgd_kernel, grid, dim3(256), 0, s, a.p, a.g, n4, n, head, a.lr, a.lr_dev);
-        return hipGetLastError();
+        if ((r & 3) || low4(a.g) != r || (mom && low4(a.m) != r)) return hipErrorInvalidValue;
+        ka.head = (int)std::min<long long>((long long)((16 - r) & 15) / 4, a.n);
+        ka.n4 = (a.n - ka.head + 3) / 4;
+        grid = ka.n4 > 0 ? grid_for(ka.n4) : 1u;
+    } else {
+        // every other kernel reads and writes four elements from every 4-aligned offset as one float4
+        if (r | low4(a.g) | (adam || mom ? low4(a.m) : 0) | (adam ? low4(a.v) : 0)) return hipErrorInvalidValue;
+        if (!a.ntile) {
+            ka.n4 = (a.n + 3) / 4;
+            grid = grid_for(ka.n4);
+        } else if (!a.tiles || !a.part || (a.nfold > 0 && (!a.fold_part || !a.counter || !a.term))) return hipErrorInvalidValue;
     }
-    // every other kernel reads and writes four elements from every 4-aligned offset as one float4
-    if (r | low4(a.g) | (adam || mom ? low4(a.m) : 0) | (adam ? low4(a.v) : 0)) return hipErrorInvalidValue;
-    if (!a.ntile) {
-        const long long n4 = (n + 3) / 4;
-        if (a.gscale)
-            hipLaunchKernelGGL(adam_scaled_kernel, dim3(grid_for(n4)), dim3(256), 0, s, a.p, a.g, a.m, a.v, n4, n, a.lr, a.lr_dev, a.b1,
-                               a.b2, a.eps, a.gscale);
-        else
-            hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n4)), dim3(256), 0, s, a.p, a.g, a.m, a.v, n4, n, a.lr, a.lr_dev, a.b1, a.b2, a.eps);
-        return hipGetLastError();
-    }
-    if (!a.tiles || !a.part || (a.nfold > 0 && (!a.fold_part || !a.counter || !a.term))) return hipErrorInvalidValue;
-    const dim3 grid(a.ntile), block(256);
-    if (a.gscale) {
-        if (adam)
-            hipLaunchKernelGGL(adam_decay_scaled_kernel, grid, block, 0, s, a.p, a.g, a.m, a.v, n, a.tiles, a.tile_base, a.lr, a.lr_dev,
-                               a.b1, a.b2, a.eps, a.part, a.fold_part, a.nfold, a.counter, a.term, a.gscale);
-        else if (mom)
-            hipLaunchKernelGGL(momentum_decay_scaled_kernel, grid, block, 0, s, a.p, a.g, a.m, n, a.tiles, a.tile_base, a.lr, a.lr_dev,
-                               a.momentum, nesterov, a.part, a.fold_part, a.nfold, a.counter, a.term, a.gscale);
-        else
-            hipLaunchKernelGGL(sgd_decay_scaled_kernel, grid, block, 0, s, a.p, a.g, n, a.tiles, a.tile_base, a.lr, a.lr_dev, a.part,
-                               a.fold_part, a.nfold, a.counter, a.term, a.gscale);
-        return hipGetLastError();
-    }
-    if (adam)
-        hipLaunchKernelGGL(adam_decay_kernel, grid, block, 0, s, a.p, a.g, a.m, a.v, n, a.tiles, a.tile_base, a.lr, a.lr_dev, a.b1, a.b2,
-                           a.eps, a.part, a.fold_part, a.nfold, a.counter, a.term);
-    else if (mom)
-        hipLaunchKernelGGL(momentum_decay_kernel, grid, block, 0, s, a.p, a.g, a.m, n, a.tiles, a.tile_base, a.lr, a.lr_dev, a.momentum,
-                           nesterov, a.part, a.fold_part, a.nfold, a.counter, a.term);
-    else if (a.update == UPD_SGD)
-        hipLaunchKernelGGL(sgd_decay_kernel, grid, block, 0, s, a.p, a.g, n, a.tiles, a.tile_base, a.lr, a.lr_dev, a.part, a.fold_part,
-                           a.nfold, a.counter, a.term);
-    else
-        hipLaunchKernelGGL(decay_grad_kernel, grid, block, 0, s, a.p, a.g, n, a.tiles, a.tile_base, a.part, a.fold_part, a.nfold,
-                           a.counter, a.term);
+    hipLaunchKernelGGL(k.kernel, dim3(grid), dim3(256), 0, s, ka);
     return hipGetLastError();
 }
 

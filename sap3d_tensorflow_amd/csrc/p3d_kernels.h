@@ -550,10 +550,11 @@ enum { UPD_NONE = -1, UPD_ADAM = 0, UPD_MOMENTUM = 1, UPD_SGD = 2 };      // the
 //   SGD never reads m, only Adam reads v.
 // ntile > 0, the decay part: one block per tile (tiles[0].off - tile_base == 0, the tiles cover [0, n)); per element
 // g' = g + c*p, written back to g where c != 0, then the update on g', or nothing more under UPD_NONE (the gradient-only mode
-// of p3d_backward, the same under every optimiser).  Float32 order, no contraction: g' = fadd(g, fmul(c, p)); then Adam as
-// adam_kernel computes it -- on 4-groups that lie whole in [0, n) m = fma(b1, m, (1-b1) g'), v = fma(b2, v, ((1-b2) g') g'), on
-// a partial last group m = (b1 m) + ((1-b1) g'), v = (b2 v) + (((1-b2) g') g'); p -= (lr m) / (sqrt(v) + eps) -- so c = 0
-// gives its bits.  part[k] = 0.5 * c * (sum of p^2 over tile k, in double; fixed order); with nfold > 0 the last block folds
+// of p3d_backward, the same under every optimiser).  Float32 order, no contraction: g' = fadd(g, fmul(c, p)), then the update.
+// Adam's float32 arithmetic is defined once (adam_elem), for the launches with and without a decay part: on 4-groups that lie
+// whole in [0, n) m = fma(b1, m, (1-b1) g'), v = fma(b2, v, ((1-b2) g') g'); on a partial last group m = (b1 m) + ((1-b1) g'),
+// v = (b2 v) + (((1-b2) g') g'); p -= (lr m) / (sqrt(v) + eps).  So a tile with c = 0 gives adam_kernel's bits.
+// part[k] = 0.5 * c * (sum of p^2 over tile k, in double; fixed order); with nfold > 0 the last block folds
 // fold_part[0 .. nfold) in index order into *term (the whole table's term, whichever ranges wrote it earlier on the stream;
 // *counter zero at launch).
 // Refused (hipErrorInvalidValue): Adam and every decay form unless each pointer the kernel uses is 16-byte aligned (they move
@@ -568,8 +569,10 @@ struct OptArgs {
     float momentum = 0.f; int nesterov = 0;          // Momentum
     const P3dRegTile* tiles = nullptr; int ntile = 0; long long tile_base = 0;      // the decay part (ntile == 0: none)
     double* part = nullptr; const double* fold_part = nullptr; int nfold = 0; unsigned* counter = nullptr; double* term = nullptr;
-    const float* gscale = nullptr;      // clipping: the *_scaled_kernel forms (below); null launches the kernels above, unchanged
+    const float* gscale = nullptr;      // clipping: the *_scaled_kernel forms (below); null: the kernels above
+    long long n4 = 0; int head = 0;     // the dense pass's float4 groups and leading single elements: p3d_opt_step's, not the caller's
 };
+// Every optimiser kernel takes the struct by value (p3d_opt_step's copy, n4 and head filled in).
 // gscale non-null (p3d_set_grad_clip): a device float s, read once per block; the update runs on g'' = fmul(g', s) wherever it
 // uses g' above, rounded once and not fused into the update (g' = g without a decay part).  g is still written back as g', never
 // as g''.  fmul(g', 1.0f) == g', so s = 1 gives the unscaled kernels' bits.  Refused under UPD_NONE.

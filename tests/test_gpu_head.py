@@ -32,12 +32,16 @@ float32), the division and sqrt(v) + eps add at most 6 eps32 relative, so |dp| <
 |m|) + eps32 |p|.  Over k steps the error of m and v compounds to k times those bounds, with the magnitude sum
 b1 M + (1 - b1) |g| carried along."""
 import math
+import os
+import sys
 
 import numpy as np
 import pytest
 
-from oracle import nn
-from sap3d_tensorflow_amd import P3dError, ops
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from oracle import nn                                   # noqa: E402
+import reg_ref                                          # noqa: E402
+from sap3d_tensorflow_amd import P3dError, ops          # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -369,6 +373,24 @@ def test_adam_elementwise(n, t, lr_on_device):
         err = np.abs(got - want)
         bad = np.flatnonzero(err > tol)
         assert bad.size == 0, (name, n, t, bad[:5], got[bad[:5]], want[bad[:5]])
+
+
+@pytest.mark.parametrize("n", [1, 3, 4, 5, 7, 1021, 2 ** 20 + 3])
+@pytest.mark.parametrize("lr_on_device", [False, True])
+@pytest.mark.parametrize("s", [1.0, 0.37])
+def test_adam_bits_are_the_float32_replay(n, lr_on_device, s):
+    """adam_kernel and adam_scaled_kernel against reg_ref.adam32, bit for bit on p, m and v: tail only, one group, group plus
+    tail, and more groups than one grid pass.  Elements whose 4-group lies whole in [0, n) take the fma form, the tail the
+    unfused one; the scaled kernel runs on float32(g * s), rounded once."""
+    rng = np.random.default_rng(n * 11 + 5)
+    p, g, m, v = adam_inputs(rng, n)
+    whole = (np.arange(n) & ~3) + 3 < n
+    for gscale, gs in ((None, g), (s, (g * np.float32(s)).astype(np.float32))):
+        p1, m1, v1, lr_t = ops.adam(p, g, m, v, 3, F32(1e-3), B1, B2, EPS, lr_on_device=lr_on_device, gscale=gscale)
+        wp, wm, wv = reg_ref.adam32(p, m, v, gs, lr_t, B1, B2, EPS, whole)
+        for name, got, want in (("p", p1, wp), ("m", m1, wm), ("v", v1, wv)):
+            bad = np.flatnonzero(got.view(np.uint32) != want.view(np.uint32))
+            assert bad.size == 0, (name, n, gscale, bad.size, bad[:5], got[bad[:5]], want[bad[:5]])
 
 
 def test_adam_refuses_a_misaligned_base():
