@@ -123,6 +123,8 @@ def parse_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--model", type=str, default="", help="checkpoint: a directory with a TF `checkpoint` state file (gen_pred.py:57-64), "
                    "a TF bundle prefix, or an .npz keyed by TF variable names")
+    p.add_argument("--ema", action="store_true", help="[addition] predict with the moving averages of the checkpoint: every trainable "
+                   "is restored from <var>/ExponentialMovingAverage (train.py --ema-decay; P3DSession.restore ema_as_weights)")
     p.add_argument("--structure", type=str, default="unet++ds",
                    help="graph to build: unet++ds = p3d_unetplusplus_ds, the buildable form of what gen_pred.py:46 constructs; or unet, "
                         "concat, unet++nonsa, gn_p3d, gn_p3d_concat, gn_p3d_decoder")
@@ -175,7 +177,7 @@ def main(argv=None):
     from sap3d_tensorflow_amd import P3DSession
     sess = P3DSession(args.structure, batch=args.batch, device=int(args.gpu), seed=0)
     if args.model:
-        sess.restore(args.model)
+        sess.restore(args.model, ema_as_weights=args.ema)
     run(sess, args)
     sess.close()
 

@@ -90,6 +90,8 @@ def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     p.add_argument("--model", type=str, default="", help="checkpoint: a directory with a TF `checkpoint` state file, a TF bundle "
                    "prefix, or an .npz keyed by TF variable names (test.py:145-150); none: freshly initialised weights")
+    p.add_argument("--ema", action="store_true", help="[addition] score the moving averages of the checkpoint: every trainable is "
+                   "restored from <var>/ExponentialMovingAverage (train.py --ema-decay; P3DSession.restore ema_as_weights)")
     p.add_argument("--structure", type=str, default="unet++",
                    help="unet, concat, unet++ (built as unet++ds, p3d_unetplusplus_ds, the buildable form of test.py:133-138), "
                         "unet++nonsa, gn_p3d, gn_p3d_concat, gn_p3d_decoder")
@@ -116,7 +118,7 @@ def main(argv=None):
     sess = P3DSession(structure, batch=args.batch, frames=x.shape[1], height=x.shape[2], width=x.shape[3], base=args.base,
                       blocks=blocks, device=device, seed=0)
     if args.model:
-        print("loading checkpoint %s" % sess.restore(args.model))
+        print("loading checkpoint %s" % sess.restore(args.model, ema_as_weights=args.ema))
     print("Now using model %s with structure %s" % (args.model or "(initialised)", structure))
     np.random.seed(args.seed)
     sauc_rng = np.random.RandomState(args.seed) if args.sauc else None

@@ -11,7 +11,9 @@ P3DSession.set_regularization); `--optimizer momentum | sgd` (with `--momentum`,
 optimisers the reference's --pretrain help names, and `--optimizer-state` saves and restores the optimiser's slots with the
 checkpoints (P3DSession.set_optimizer, save_checkpoint / restore optimizer_state); `--clip-norm X` clips every step's
 gradients by their global norm, as tf.clip_by_global_norm does, and prints the norm and the scale with the step
-(P3DSession.set_grad_clip).  The dataset loaders (dataflow.py,
+(P3DSession.set_grad_clip); `--ema-decay D` (with `--ema-warmup`) keeps tf.train.ExponentialMovingAverage's shadows of the
+trainables: the checkpoints carry them, --pretrain restores them when present, and the periodic eval forward and the
+validation pass score the averaged weights (P3DSession.set_ema).  The dataset loaders (dataflow.py,
 tensorpack, cv2) are out of scope: clips come either from `--data clips.npz` (arrays x [N,16,112,112,3] already normalised like
 dataflow.py:204-208, y [N,16,112,112]; raw uint8 frames go through sap3d_tensorflow_amd.dataflow.mapf_frames first) or
 are synthetic with the loader's value law.
@@ -89,6 +91,13 @@ def get_arguments():
     p.add_argument("--clip-norm", type=float, default=0.0,
                    help="[addition] clip the gradients by their global norm to this value before the optimiser applies them "
                         "(tf.clip_by_global_norm); inf reports the norm without clipping; 0 = off")
+    # single checkpoints of a batch-2 SUM loss are noisy: the averaged weights are what TF-1 trainers evaluate
+    p.add_argument("--ema-decay", type=float, default=None, metavar="D",
+                   help="[addition] keep an exponential moving average of the trainables with this decay (0 <= D < 1, "
+                        "tf.train.ExponentialMovingAverage); checkpoints carry the shadows, and the eval forward and the validation "
+                        "pass run on them")
+    p.add_argument("--ema-warmup", action="store_true",
+                   help="[addition] TF's num_updates: step t averages with min(D, (1 + t) / (10 + t)) (--ema-decay only)")
     return p.parse_args()
 
 
@@ -141,6 +150,12 @@ def validate(sess, args, step):
     return res
 
 
+def scoring(sess, ema):
+    """The weights an evaluation runs on: the moving averages under --ema-decay, else the session as it is."""
+    import contextlib
+    return sess.averaged() if ema else contextlib.nullcontext(sess)
+
+
 def main():
     args = get_arguments()
     from sap3d_tensorflow_amd import P3dError, P3DSession
@@ -186,11 +201,28 @@ def main():
         except (P3dError, ValueError) as e:
             sess.close()
             raise SystemExit("--clip-norm %s: %s" % (args.clip_norm, e))
+    ema = args.ema_decay is not None
+    if args.ema_warmup and not ema:
+        sess.close()
+        raise SystemExit("--ema-warmup needs --ema-decay")
+    if ema:
+        try:
+            sess.set_ema(args.ema_decay, warmup=args.ema_warmup)
+        except P3dError as e:
+            sess.close()
+            raise SystemExit("--ema-decay %s: %s" % (args.ema_decay, e))
     model_dir = os.path.join("model", args.info)
     os.makedirs(model_dir, exist_ok=True)
     if args.pretrain:
         print(args.pretrain, "Using this model to retrain...")
-        sess.restore(args.pretrain, optimizer_state=args.optimizer_state)          # train.py:204-210
+        try:
+            sess.restore(args.pretrain, optimizer_state=args.optimizer_state, ema=ema)      # train.py:204-210
+        except KeyError as e:
+            if not ema or "moving averages" not in str(e):
+                raise
+            sess.restore(args.pretrain, optimizer_state=args.optimizer_state)          # a checkpoint without shadows:
+            sess.set_ema(None)                                                          # they start from its weights
+            sess.set_ema(args.ema_decay, warmup=args.ema_warmup)
     print("Start training")
     step = 0
     for xs, ys in batches(args, np.random.default_rng(0)):
@@ -200,13 +232,15 @@ def main():
             gn_, sc_ = sess.last_grad_norm()
         if step < 10 or step % args.plotiter == 0:
             clip = ("gnorm", "%.9g" % gn_, "scale", "%.9g" % sc_) if args.clip_norm != 0.0 else ()
-            image = sess.forward(xs, dropout=0.0, training=False)                   # train.py:225-226
+            with scoring(sess, ema):
+                image = sess.forward(xs, dropout=0.0, training=False)               # train.py:225-226
             print("Datetime", datetime.datetime.now().isoformat()[:-7], "Training step:", step,
                   float(np.sum(image[0, -1]) * 255.0), float(np.sum(ys[0][-1]) * 255.0), "Training Loss", loss, *clip)
         if step % args.validiter == 0:
-            validate(sess, args, step)                                              # train.py:243-264
+            with scoring(sess, ema):
+                validate(sess, args, step)                                          # train.py:243-264
         if step % args.saveiter == 0:
-            sess.save_checkpoint(model_dir, step, keep=10, optimizer_state=args.optimizer_state)     # train.py:180-185,266-267
+            sess.save_checkpoint(model_dir, step, keep=10, optimizer_state=args.optimizer_state, ema=ema)     # train.py:180-185,266-267
     print("Training Finished!")
     sess.close()
 

@@ -215,6 +215,38 @@ int p3d_set_optimizer_step(p3d_handle* h, int64_t t);
 int p3d_set_grad_clip(p3d_handle* h, float clip_norm);
 int p3d_get_grad_norm(p3d_handle* h, double* sumsq, double* norm, float* scale);
 
+/* Exponential moving average of the weights, as tf.train.ExponentialMovingAverage(decay[, num_updates]).apply(
+ * tf.trainable_variables()) run after the train op (an addition: the reference scores single checkpoints).  Off by default; off,
+ * a step launches what it launched before the option existed.  decay < 0 (e.g. -1): off; finite with 0 <= decay < 1: on;
+ * anything else (1, above 1, NaN, +inf): -1, nothing changed.  A shadow s exists for every TRAINABLE variable -- BatchNorm's
+ * moving statistics have none.  After the optimiser has updated p in a train step (p3d_backward never touches the shadows),
+ *   s = s - (s - p) * om        float32, every operation rounded on its own, no fused multiply-add
+ * (TF's assign_moving_average).  om:
+ *   warmup == 0   om = (float)(1.0 - decay): the subtraction in double, rounded once, as TF does with a Python float -- which is
+ *                 why decay is a double here: (float)(1.0 - 0.999) is not 1.f - 0.999f.
+ *   warmup != 0   TF's num_updates: t = (float)steps, steps = the completed optimiser steps including this one (what
+ *                 p3d_get_optimizer_step returns after the step); q = (1.f + t) / (10.f + t); d = fminf((float)decay, q);
+ *                 om = 1.f - d, all in float32.
+ * No TensorFlow was available to pin this against: the text above is the contract, and tests/ema_ref.py replays it bit for bit.
+ * The shadows (one float per trainable element, allocated the first time the option is switched on) are seeded with a copy of
+ * the parameters whenever the option goes from off to on, as TF initialises a shadow from its variable, and again by
+ * p3d_init_params while it is on.  A new decay or warm-up flag while on, p3d_set_optimizer and p3d_set_param leave them alone.
+ * Each optimiser launch of the step is followed by one launch of ema_kernel over the same range.  Under data parallelism every
+ * rank holds the same weights after the update, hence the same shadows; nothing is communicated.  Drops a captured step graph.
+ * p3d_get_ema / p3d_set_ema_var: the shadow of `var`; -1 while the option is off, for an unknown or non-trainable variable, or
+ * a wrong count.
+ * p3d_ema_swap exchanges parameters and shadows of every trainable, bit for bit, in one launch, so that p3d_forward,
+ * p3d_predict_windows, p3d_eval_last_frames and p3d_pred_maps_u8 score the averaged weights without a second network; a second
+ * call restores both (-1 while the option is off).  p3d_ema_swapped: 1 while exchanged, else 0.  While exchanged
+ * p3d_train_step*, p3d_backward, p3d_profile_step, p3d_set_param, p3d_init_params and p3d_set_ema return -1 (a forgotten swap
+ * must not average the averages), and p3d_get_param returns what the parameter buffer then holds -- the shadows -- while
+ * p3d_get_ema returns the parameters. */
+int p3d_set_ema(p3d_handle* h, double decay, int warmup);
+int p3d_get_ema(p3d_handle* h, const char* var, float* host, int64_t count);
+int p3d_set_ema_var(p3d_handle* h, const char* var, const float* host, int64_t count);
+int p3d_ema_swap(p3d_handle* h);
+int p3d_ema_swapped(p3d_handle* h);
+
 /* ---- intermediate tensors (tf fetches of graph tensors; parity/debug taps).  Names:
  *      conv1_custom, conv1_custom_bn_relu, pool1..pool4, block<i>/conv1_bn_relu, block<i>/st,
  *      block<i>/out, deconv3_re, deconv4_conv1, logits, pred. */
@@ -422,6 +454,11 @@ int p3d_debug_optimizer(int device, int kind, float* p, float* g, float* m, int6
 int p3d_debug_optimizer_decay(int device, int kind, float* p, float* g, float* m, int64_t n, int offset, const int64_t* tile_off,
                               const int64_t* tile_len, const float* tile_c, int ntile, float lr, float momentum, int use_nesterov,
                               int lr_on_device, int update, double* term);
+/* Test hook: one ema_kernel launch (p3d_set_ema; as the train step launches it) on n shadows s and parameters p placed `offset`
+ * (0..3) elements past a 16-byte boundary of the device buffers; om is passed as an argument or, when om_on_device, through
+ * device memory as a captured step with warm-up passes it.  The hook surrounds both ranges with guard elements and returns -1
+ * if the launch changed one, or changed p. */
+int p3d_debug_ema(int device, float* s, const float* p, int64_t n, int offset, float om, int om_on_device);
 /* Test hook: any of the optimiser launches above with clipping's scale (OptArgs::gscale, read from device memory): kind
  * P3D_OPT_*, ntile = 0 for the plain kernels (tile pointers and term may be NULL) or a tile table as p3d_debug_adam_decay takes
  * it; g becomes g + c*p (not scaled), the update runs on fmul(g', gscale).  t and the betas matter under Adam only, momentum

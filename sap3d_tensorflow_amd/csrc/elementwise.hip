@@ -711,6 +711,40 @@ __global__ __launch_bounds__(256) void adam_decay_scaled_kernel(OptArgs a) { dec
 __global__ __launch_bounds__(256) void momentum_decay_scaled_kernel(OptArgs a) { decay_body<UPD_MOMENTUM, true>(a); }
 __global__ __launch_bounds__(256) void sgd_decay_scaled_kernel(OptArgs a) { decay_body<UPD_SGD, true>(a); }
 
+// Exponential moving average of the weights (p3d_set_ema; EmaArgs in p3d_kernels.h): tf.train.ExponentialMovingAverage's
+// assign_moving_average, s = s - (s - p) * om, every operation rounded on its own.  One dense pass shaped like opt_body: float4
+// groups from the first 16-byte boundary, the `head` elements before it and the cut last group one by one.  Every element takes
+// the same arithmetic, and elements are independent: slot padding inside the range is averaged like anything else and never read.
+__device__ __forceinline__ float ema_elem(float s, float p, float om) {
+#pragma clang fp contract(off)
+    const float d = s - p;
+    const float e = d * om;
+    return s - e;
+}
+__global__ __launch_bounds__(256) void ema_kernel(EmaArgs a) {
+    const long long n = a.n;
+    const float om = a.om_dev ? *a.om_dev : a.om;
+    if (blockIdx.x == 0 && (int)threadIdx.x < a.head) a.s[threadIdx.x] = ema_elem(a.s[threadIdx.x], a.p[threadIdx.x], om);
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n4; i += (long long)gridDim.x * blockDim.x) {
+        const long long e = a.head + (i << 2);
+        if (e + 3 < n) {
+            const float4 ss = ld4(a.s + e), pp = ld4(a.p + e);
+            st4(a.s + e, make_float4(ema_elem(ss.x, pp.x, om), ema_elem(ss.y, pp.y, om), ema_elem(ss.z, pp.z, om),
+                                     ema_elem(ss.w, pp.w, om)));
+        } else {
+            for (long long q = e; q < n; ++q) a.s[q] = ema_elem(a.s[q], a.p[q], om);
+        }
+    }
+}
+// p3d_ema_swap: a and b exchanged bit for bit (16-byte aligned, n a multiple of 4: whole flat buffers)
+__global__ __launch_bounds__(256) void ema_swap_kernel(float* a, float* b, long long n4) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+        const float4 x = ld4(a + (i << 2)), y = ld4(b + (i << 2));
+        st4(a + (i << 2), y);
+        st4(b + (i << 2), x);
+    }
+}
+
 // Global gradient norm (p3d_set_grad_clip; SumsqArgs in p3d_kernels.h).  Block b takes chunks k0 + b, k0 + b + gridDim.x, ... of
 // the table; chunk k's sum of g'^2 -- every square exact in double, one double accumulator per lane over a lane-to-element map
 // that depends on the chunk's place in memory alone, lanes folded by the xor butterfly and the four waves in order -- goes to
@@ -1255,12 +1289,38 @@ hipError_t p3d_grad_sumsq(const SumsqArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-__global__ void set_step_scalars_kernel(unsigned long long* seed_dst, float* lr_dst, unsigned long long seed, float lr_t) {
+LaunchDesc p3d_ema_desc(const EmaArgs& a) {
+    // per element: s and p read, s written (12 bytes); a subtraction, a product, a subtraction
+    return {"ema_kernel", 3.0 * a.n, 12.0 * a.n};
+}
+
+hipError_t p3d_ema_step(const EmaArgs& a, hipStream_t s) {
+    if (!a.s || !a.p || a.n < 1) return hipErrorInvalidValue;
+    // s and p float-aligned and at the same place in a 16-byte line: the elements before the first 16-byte boundary go one by one
+    const uintptr_t r = low4(a.s);
+    if ((r & 3) || low4(a.p) != r) return hipErrorInvalidValue;
+    EmaArgs ka = a;
+    ka.head = (int)std::min<long long>((long long)((16 - r) & 15) / 4, a.n);
+    ka.n4 = (a.n - ka.head + 3) / 4;
+    hipLaunchKernelGGL(ema_kernel, dim3(ka.n4 > 0 ? grid_for(ka.n4) : 1u), dim3(256), 0, s, ka);
+    return hipGetLastError();
+}
+
+hipError_t p3d_ema_swap(float* a, float* b, long long n, hipStream_t s) {
+    if (!a || !b || a == b || n < 4 || (n & 3) || low4(a) || low4(b)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ema_swap_kernel, dim3(grid_for(n >> 2)), dim3(256), 0, s, a, b, n >> 2);
+    return hipGetLastError();
+}
+
+__global__ void set_step_scalars_kernel(unsigned long long* seed_dst, float* lr_dst, float* om_dst, unsigned long long seed, float lr_t,
+                                        float om) {
     if (seed_dst) *seed_dst = seed;
     if (lr_dst) *lr_dst = lr_t;
+    if (om_dst) *om_dst = om;
 }
-hipError_t p3d_set_step_scalars(unsigned long long* seed_dst, float* lr_dst, unsigned long long seed, float lr_t, hipStream_t s) {
-    hipLaunchKernelGGL(set_step_scalars_kernel, dim3(1), dim3(1), 0, s, seed_dst, lr_dst, seed, lr_t);
+hipError_t p3d_set_step_scalars(unsigned long long* seed_dst, float* lr_dst, float* om_dst, unsigned long long seed, float lr_t, float om,
+                                hipStream_t s) {
+    hipLaunchKernelGGL(set_step_scalars_kernel, dim3(1), dim3(1), 0, s, seed_dst, lr_dst, om_dst, seed, lr_t, om);
     return hipGetLastError();
 }
 

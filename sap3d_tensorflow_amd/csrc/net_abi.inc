@@ -188,6 +188,7 @@ static Param* find_param(p3d_handle* h, const char* name, int64_t count) {
 int p3d_set_param(p3d_handle* h, const char* name, const float* host, int64_t count) {
     API_BEGIN
     Param* p = find_param(h, name, count);
+    h->refuse_swapped("p3d_set_param");
     HIPCHECK(hipSetDevice(h->cfg.device));
     // the handle's streams are non-blocking: nothing else orders this copy after a step that is still running
     HIPCHECK(hipStreamSynchronize(h->stream));
@@ -215,6 +216,7 @@ int p3d_get_grad(p3d_handle* h, const char* name, float* host, int64_t count) {
 int p3d_init_params(p3d_handle* h, uint64_t seed) {
     API_BEGIN
     if (!h) throw P3dError("null handle");
+    h->refuse_swapped("p3d_init_params");
     HIPCHECK(hipSetDevice(h->cfg.device));
     uint64_t idx = 0;
     for (Param* p : h->porder) {
@@ -248,6 +250,7 @@ int p3d_init_params(p3d_handle* h, uint64_t seed) {
     HIPCHECK(hipMemsetAsync(h->flat_v, 0, (size_t)h->n_train * 4, h->stream));
     h->step = 0;
     HIPCHECK(hipStreamSynchronize(h->stream));
+    if (h->ema_on) h->ema_seed();      // fresh variables, fresh shadows
     API_END
 }
 
@@ -374,6 +377,43 @@ int p3d_get_grad_norm(p3d_handle* h, double* sumsq, double* norm, float* scale) 
     API_END
 }
 
+int p3d_set_ema(p3d_handle* h, double decay, int warmup) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->set_ema(decay, warmup != 0);
+    API_END
+}
+
+int p3d_get_ema(p3d_handle* h, const char* var, float* host, int64_t count) {
+    API_BEGIN
+    if (!h || !host) throw P3dError("null argument");
+    float* d = h->ema_ptr(var, count);
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    HIPCHECK(copy_now(host, d, (size_t)count * 4, hipMemcpyDeviceToHost, h->stream));
+    API_END
+}
+
+int p3d_set_ema_var(p3d_handle* h, const char* var, const float* host, int64_t count) {
+    API_BEGIN
+    if (!h || !host) throw P3dError("null argument");
+    float* d = h->ema_ptr(var, count);
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->sync_streams();      // as p3d_set_param: nothing else orders this copy after a running step
+    HIPCHECK(copy_now(d, host, (size_t)count * 4, hipMemcpyHostToDevice, h->stream));
+    API_END
+}
+
+int p3d_ema_swap(p3d_handle* h) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->ema_swap();
+    API_END
+}
+
+int p3d_ema_swapped(p3d_handle* h) { return h ? (h->ema_swapped ? 1 : 0) : -1; }
+
 int p3d_set_bn_fusion(p3d_handle* h, int enable) {
     API_BEGIN
     if (!h) throw P3dError("null handle");
@@ -397,6 +437,7 @@ int p3d_predict_windows(p3d_handle* h, const float* x, float* pred) {
 int p3d_backward(p3d_handle* h, const float* x, const float* y, float dropout_rate, uint64_t seed, float* loss, float* pred) {
     API_BEGIN
     if (!h || !x || !y) throw P3dError("null argument");
+    h->refuse_swapped("p3d_backward");
     HIPCHECK(hipSetDevice(h->cfg.device));
     h->upload(x, y);
     Ctx c; c.training = true; c.drop = dropout_rate; c.seed = seed; c.update_moving = false; c.s = h->stream;
@@ -636,6 +677,7 @@ int p3d_block_backward(p3d_handle* h, int block_id, const float* in, int64_t in_
 int p3d_profile_step(p3d_handle* h, float dropout_rate, uint64_t seed, p3d_op_time* out, int cap) {
     if (!h) { g_err = "null handle"; return -1; }
     try {
+        h->refuse_swapped("p3d_profile_step");
         HIPCHECK(hipSetDevice(h->cfg.device));
         Prof prof;
         Ctx c; c.training = true; c.drop = dropout_rate; c.seed = seed; c.update_moving = true; c.s = h->stream; c.prof = &prof;
@@ -1300,7 +1342,7 @@ void debug_opt_step(OptArgs a, float* p, const float* g, float* g_out, float* m,
     StagedBuf pb(n, offset, p), gb(n, offset, g), mb(n, offset, m), vb(n, offset, v);
     DevBuf lrb(1), tb(4 * ntile), part(2 * ntile), scal(4);      // scal (zeroed): [0..1] the term, [2] the fold's counter
     a.p = pb.at(); a.g = gb.at(); a.m = mb.at(); a.v = vb.at(); a.n = (long)n;
-    if (lr_on_device) HIPCHECK(p3d_set_step_scalars(nullptr, lrb.p, 0, step, nullptr));
+    if (lr_on_device) HIPCHECK(p3d_set_step_scalars(nullptr, lrb.p, nullptr, 0, step, 0.f, nullptr));
     DevBuf sc(1, gscale);      // clipping's scale, read from device memory as the step reads it
     if (gscale) a.gscale = sc.p;
     // from device memory the argument must not matter: NaN would show in every element if the kernel read it
@@ -1404,6 +1446,39 @@ int p3d_debug_optimizer(int device, int kind, float* p, float* g, float* m, int6
     if (kind != P3D_OPT_MOMENTUM && kind != P3D_OPT_SGD) throw P3dError("optimizer: kind 1 (momentum) or 2 (sgd); Adam has p3d_debug_adam");
     if (n < 1 || offset < 0 || offset > 3) throw P3dError("optimizer: bad length or offset");
     debug_opt_step(momentum_update(kind, momentum, use_nesterov), p, g, g, m, nullptr, n, offset, lr, lr_on_device);
+    API_END
+}
+
+// ema_kernel from the step's launch description.  The range sits `offset` elements past a 16-byte boundary with one guard element
+// on each side of it in both buffers; a guard that the launch changed is an error.
+int p3d_debug_ema(int device, float* s, const float* p, int64_t n, int offset, float om, int om_on_device) {
+    API_BEGIN
+    HIPCHECK(hipSetDevice(device));
+    if (!s || !p) throw P3dError("null argument");
+    if (n < 1 || offset < 0 || offset > 3) throw P3dError("ema: bad length or offset");
+    const int64_t at = 4 + offset;
+    const uint32_t guard = 0x7fc5a5a5u;      // a NaN no arithmetic here produces
+    std::vector<uint32_t> gs((size_t)(n + 12), guard);
+    DevBuf sb(n + 12, reinterpret_cast<const float*>(gs.data())), pb(n + 12, reinterpret_cast<const float*>(gs.data())), omb(1);
+    HIPCHECK(copy_now(sb.p + at, s, (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
+    HIPCHECK(copy_now(pb.p + at, p, (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
+    if (om_on_device) HIPCHECK(p3d_set_step_scalars(nullptr, nullptr, omb.p, 0, 0.f, om, nullptr));
+    EmaArgs a;
+    a.s = sb.p + at; a.p = pb.p + at; a.n = (long)n;
+    a.om = om_on_device ? NAN : om;      // from device memory the argument must not matter
+    a.om_dev = om_on_device ? omb.p : nullptr;
+    const LaunchDesc d = p3d_ema_desc(a);
+    if (std::string(d.kernel) != "ema_kernel") throw P3dError("ema: launch description names another kernel");
+    HIPCHECK(p3d_ema_step(a, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    std::vector<uint32_t> back((size_t)(n + 12)), pback((size_t)(n + 12));
+    HIPCHECK(copy_now(back.data(), sb.p, back.size() * 4, hipMemcpyDeviceToHost, nullptr));
+    HIPCHECK(copy_now(pback.data(), pb.p, pback.size() * 4, hipMemcpyDeviceToHost, nullptr));
+    for (int64_t i = 0; i < n + 12; ++i)
+        if ((i < at || i >= at + n) && (back[(size_t)i] != guard || pback[(size_t)i] != guard))
+            throw P3dError("ema: the launch wrote outside its range (element " + std::to_string(i - at) + ")");
+    if (memcmp(pback.data() + at, p, (size_t)n * 4) != 0) throw P3dError("ema: the launch changed the parameters");
+    memcpy(s, back.data() + at, (size_t)n * 4);
     API_END
 }
 

@@ -14,6 +14,7 @@
         statpart_arena = dalloc<float>(statpart_count);
         d_seed = dalloc<unsigned long long>(1);
         d_lr = dalloc<float>(1);
+        d_om = dalloc<float>(1);
         red_arena = dalloc<double>(red_count);
         bnbuf = dalloc<float>(bnbuf_count);
         for (auto& f : late_bind) f();

@@ -265,11 +265,85 @@
         const OptArgs a = opt_args(lo, hi, update, cur_lr_t, c.lr_dev, &decayed);
         const LaunchDesc d = p3d_opt_desc(a, decayed);
         launch(c, d.kernel, d.flops, d.bytes, [&]() { return p3d_opt_step(a, c.s); });
+        if (update && ema_on) ema_range(c, lo, hi);      // the shadows follow their parameters, range by range
     }
     void run_adam(const Ctx& c) {
         if (clip_on()) sumsq_range(c, 0, n_train);
         adam_begin(c);
         adam_range(c, 0, n_train);
+    }
+
+    // ---- exponential moving average of the weights (p3d_set_ema) ---------------------------------------
+    // flat_ema shadows flat_p (same offsets; allocated when the option is first switched on).  Every optimiser launch of a train
+    // step is followed on its stream by one ema_kernel over the same range, so the early range still overlaps the stem's filter
+    // gradient; p3d_backward updates nothing.  om (p3d_hip.h): float(1 - decay) in double, or under warm-up 1.f - min(decay,
+    // (1 + t) / (10 + t)) in float32 with t the completed optimiser steps including this one -- a launch argument, or under
+    // warm-up in a captured step the device float d_om (p3d_set_step_scalars).  Ranks hold the same weights after the
+    // all-reduced update, hence the same shadows: nothing is communicated.
+    float* flat_ema = nullptr;
+    bool ema_on = false, ema_warmup = false, ema_swapped = false;
+    double ema_decay = 0.0;
+    float* d_om = nullptr;
+    float ema_om(int64_t t) const {
+        if (!ema_warmup) return (float)(1.0 - ema_decay);
+        const float tf = (float)t;
+        const float q = (1.f + tf) / (10.f + tf);
+        return 1.f - fminf((float)ema_decay, q);
+    }
+    void ema_range(const Ctx& c, int64_t lo, int64_t hi) {
+        if (hi <= lo) return;
+        EmaArgs a;
+        a.s = flat_ema + lo; a.p = flat_p + lo; a.n = (long)(hi - lo);
+        if (c.om_dev && ema_warmup) a.om_dev = c.om_dev;
+        else a.om = ema_om(step);      // (adam_begin has counted this step; a captured step with a constant decay never reads `step`)
+        const LaunchDesc d = p3d_ema_desc(a);
+        launch(c, d.kernel, d.flops, d.bytes, [&]() { return p3d_ema_step(a, c.s); });
+    }
+    void sync_streams() {
+        HIPCHECK(hipStreamSynchronize(stream));
+        HIPCHECK(hipStreamSynchronize(side_stream));
+        HIPCHECK(hipStreamSynchronize(comm_stream));
+    }
+    void ema_seed() {      // TF initialises a shadow from its variable
+        HIPCHECK(hipMemcpyAsync(flat_ema, flat_p, (size_t)n_train * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        HIPCHECK(hipStreamSynchronize(stream));
+    }
+    void refuse_swapped(const char* what) const {
+        if (ema_swapped)
+            throw P3dError(std::string(what) + ": parameters and averaged weights are exchanged (p3d_ema_swap); swap back first");
+    }
+    void set_ema(double decay, bool warmup) {
+        refuse_swapped("p3d_set_ema");
+        if (!(decay < 0.0) && !(std::isfinite(decay) && decay < 1.0))
+            throw P3dError("moving average: decay must be finite with 0 <= decay < 1 (negative: off)");
+        sync_streams();
+        if (decay < 0.0) {
+            ema_on = false;
+        } else {
+            if (!flat_ema) flat_ema = dalloc<float>(n_train);
+            if (!ema_on) ema_seed();
+            ema_on = true; ema_decay = decay; ema_warmup = warmup;
+        }
+        drop_step_graph();      // the launch list differs, and a constant om is a launch argument
+    }
+    float* ema_ptr(const char* var, int64_t count) {
+        if (!ema_on) throw P3dError("moving average: the option is off (p3d_set_ema)");
+        if (!var) throw P3dError("null argument");
+        auto it = pindex.find(var);
+        if (it == pindex.end()) throw P3dError(std::string("no variable named ") + var);
+        const Param* p = it->second;
+        if (!p->trainable) throw P3dError(std::string(var) + " is not trainable: it has no moving average");
+        if (count != p->count)
+            throw P3dError(std::string("size mismatch for ") + var + ": got " + std::to_string(count) + ", variable has " +
+                           std::to_string(p->count));
+        return flat_ema + p->off;
+    }
+    void ema_swap() {
+        if (!ema_on) throw P3dError("moving average: the option is off (p3d_set_ema)");
+        sync_streams();
+        HIPCHECK(p3d_ema_swap(flat_p, flat_ema, (long long)n_train, stream));
+        HIPCHECK(hipStreamSynchronize(stream));
+        ema_swapped = !ema_swapped;
     }
 
     // ---- gradient clipping by the global norm (p3d_set_grad_clip) ----------------------------------
@@ -479,6 +553,7 @@
     int graph_reg = 0;
     float graph_clip = 0.f;
     int graph_kind = P3D_OPT_ADAM; float graph_mom = 0.f; int graph_nesterov = 0;      // the optimiser the graph launches
+    bool graph_ema = false, graph_ema_warmup = false; double graph_ema_decay = 0.0;    // and the moving average
     bool graph_disabled = false;
     unsigned long long* d_seed = nullptr; float* d_lr = nullptr;
     void drop_step_graph() {
@@ -490,7 +565,7 @@
     }
     void capture_step_graph(float drop) {
         drop_step_graph();
-        Ctx c; c.training = true; c.drop = drop; c.seed = 0; c.seed_dev = d_seed; c.lr_dev = d_lr; c.update_moving = true; c.s = stream;
+        Ctx c; c.training = true; c.drop = drop; c.seed = 0; c.seed_dev = d_seed; c.lr_dev = d_lr; c.om_dev = d_om; c.update_moving = true; c.s = stream;
         HIPCHECK(hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed));
         try {
             run_forward(c);
@@ -510,8 +585,10 @@
         graph_reg = reg_terms;
         graph_clip = clip_norm;
         graph_kind = opt_kind; graph_mom = momentum; graph_nesterov = use_nesterov;
+        graph_ema = ema_on; graph_ema_warmup = ema_warmup; graph_ema_decay = ema_decay;
     }
     void train_step_device(float drop, uint64_t seed) {
+        refuse_swapped("train step");
         if (!graphs_enabled()) {
             Ctx c; c.training = true; c.drop = drop; c.seed = seed; c.update_moving = true; c.s = stream;
             zero_early(c);
@@ -521,7 +598,7 @@
         }
         if (!step_exec || graph_drop != drop || graph_f16 != pointwise_f16 || graph_comm != comm || graph_b1 != b1 || graph_b2 != b2 ||
             graph_eps != eps || graph_reg != reg_terms || graph_clip != clip_norm || graph_kind != opt_kind || graph_mom != momentum ||
-            graph_nesterov != use_nesterov) {
+            graph_nesterov != use_nesterov || graph_ema != ema_on || graph_ema_warmup != ema_warmup || graph_ema_decay != ema_decay) {
             try {
                 capture_step_graph(drop);
             } catch (const std::exception& e) {
@@ -533,7 +610,8 @@
                 return;
             }
         }
-        HIPCHECK(p3d_set_step_scalars(d_seed, d_lr, seed, opt_step_size(++step), stream));
+        ++step;
+        HIPCHECK(p3d_set_step_scalars(d_seed, d_lr, ema_on && ema_warmup ? d_om : nullptr, seed, opt_step_size(step), ema_om(step), stream));
         HIPCHECK(hipGraphLaunch(step_exec, stream));
     }
 

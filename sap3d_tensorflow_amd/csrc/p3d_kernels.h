@@ -602,8 +602,25 @@ struct SumsqArgs {
 };
 LaunchDesc p3d_grad_sumsq_desc(const SumsqArgs& a, double elems, double decayed_elems);
 hipError_t p3d_grad_sumsq(const SumsqArgs& a, hipStream_t s);
-// per-step scalars of a captured train step: scal[0..1] = dropout seed (64 bit), scal[2] = the optimiser's step size (opt_step_size)
-hipError_t p3d_set_step_scalars(unsigned long long* seed_dst, float* lr_dst, unsigned long long seed, float lr_t, hipStream_t s);
+// ---- exponential moving average of the weights (p3d_set_ema): ema_kernel -------------------------------------------------------
+// One launch over [s, s + n): s = fsub(s, fmul(fsub(s, p), om)) in float32, no contraction, the same on every element (TF's
+// assign_moving_average with om = 1 - decay).  om_dev non-null: om is read from device memory (a captured step with warm-up, where
+// it changes every step), om is ignored.  12 bytes and 3 operations per element.
+// Refused (hipErrorInvalidValue): s and p not float-aligned at the same place in a 16-byte line, n < 1.
+struct EmaArgs {
+    float* s = nullptr; const float* p = nullptr;
+    long n = 0;
+    float om = 0.f; const float* om_dev = nullptr;
+    long long n4 = 0; int head = 0;     // the dense pass's float4 groups and leading single elements: p3d_ema_step's, not the caller's
+};
+LaunchDesc p3d_ema_desc(const EmaArgs& a);
+hipError_t p3d_ema_step(const EmaArgs& a, hipStream_t s);
+// a and b exchanged bit for bit (p3d_ema_swap): both 16-byte aligned, n a multiple of 4
+hipError_t p3d_ema_swap(float* a, float* b, long long n, hipStream_t s);
+// per-step scalars of a captured train step: scal[0..1] = dropout seed (64 bit), scal[2] = the optimiser's step size (opt_step_size),
+// scal[3] = the moving average's om under warm-up (ema_om); a null destination is skipped
+hipError_t p3d_set_step_scalars(unsigned long long* seed_dst, float* lr_dst, float* om_dst, unsigned long long seed, float lr_t, float om,
+                                hipStream_t s);
 
 // ---- saliency metrics + frame pre-processing (metrics.hip; utils/metrics.py:25-287, dataflow.py:187-216) ------
 hipError_t p3d_metric_cc(const float* a, const float* b, int n_maps, int n_pix, double* out, hipStream_t s);

@@ -497,6 +497,18 @@ def optimizer(kind, p, g, m, lr=1e-4, momentum=0.9, use_nesterov=False, lr_on_de
     return p, m
 
 
+def ema(s, p, om, om_on_device=False, offset=0, device=0):
+    """Test hook: one launch of the moving-average kernel of P3DSession.set_ema (ema_kernel, p3d_debug_ema) on flat float32
+    shadows s and parameters p placed `offset` (0..3) elements past a 16-byte boundary; om is float32(1 - decay), passed as an
+    argument or through device memory.  Returns s - (s - p) * om.  The hook itself guards both sides of the range."""
+    s = _f32(s).ravel().copy()
+    p = _f32(p).ravel()
+    if s.size != p.size:
+        raise ValueError("s and p differ in size")
+    check(lib().p3d_debug_ema(device, fptr(s), fptr(p), s.size, int(offset), float(np.float32(om)), 1 if om_on_device else 0))
+    return s
+
+
 def optimizer_decay(kind, p, g, m, tiles, lr=1e-4, momentum=0.9, use_nesterov=False, lr_on_device=False, update=True, offset=0,
                     device=0, gscale=None):
     """Test hook: adam_decay's launch with Momentum or SGD as the update (p3d_debug_optimizer_decay).  tiles = [(length,

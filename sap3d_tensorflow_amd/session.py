@@ -26,6 +26,14 @@ def slot_names(variables, optimizer):
     return out
 
 
+EMA_SUFFIX = "ExponentialMovingAverage"      # tf.train.ExponentialMovingAverage's shadow of <var>: <var>/ExponentialMovingAverage
+
+
+def ema_names(variables):
+    """{TF shadow name: variable} over the trainables of [(name, shape, trainable)]."""
+    return dict(("%s/%s" % (n, EMA_SUFFIX), n) for n, _, tr in variables if tr)
+
+
 def adam_step_from_powers(beta1_power, beta2_power, beta1=0.9, beta2=0.999):
     """Completed Adam steps t of TF's beta1_power / beta2_power (b^(t+1) as float32): the integer nearest to
     log(beta2_power) / log(beta2) - 1, checked against beta1_power (relative 1e-3, or within float32's smallest normal where
@@ -127,11 +135,14 @@ class P3DSession:
         for n in names:
             self.set_param(n, params[n])
 
-    def restore(self, path, optimizer_state=False):
+    def restore(self, path, optimizer_state=False, ema=False, ema_as_weights=False):
         """saver.restore (train.py:204-210, gen_pred.py:57-64): `path` is a TF-1.x checkpoint prefix (`.../p3d_1000.ckpt`),
         a directory holding a `checkpoint` state file (the newest bundle is taken), or an .npz keyed by variable names.
         Variables the checkpoint lacks raise; extra ones (e.g. Adam slots of another trainer) are ignored.  With
-        optimizer_state the current optimiser's slots (and Adam's beta*_power) come back too (load_optimizer_state)."""
+        optimizer_state the current optimiser's slots (and Adam's beta*_power) come back too (load_optimizer_state).
+        ema (set_ema must be on): the shadows come back from <var>/ExponentialMovingAverage; a checkpoint that lacks any raises,
+        listing them, before anything is set.  ema_as_weights: every trainable is loaded from its shadow entry and the rest as
+        usual, as a Saver over ema.variables_to_restore() does for evaluation; it needs no set_ema."""
         import os
         from . import tf_checkpoint as tfc
         if os.path.isdir(path):
@@ -142,27 +153,45 @@ class P3DSession:
         names = set(n for n, _, _ in self.variables())
         if optimizer_state:
             names |= set(self._slot_names()) | ({"beta1_power", "beta2_power"} if self._opt == "adam" else set())
+        if ema and ema_as_weights:
+            raise ValueError("restore: ema loads the shadows beside the weights, ema_as_weights in their place; choose one")
+        shadows = ema_names(self.variables()) if (ema or ema_as_weights) else {}
+        names |= set(shadows)
         if path.endswith(".npz"):
             d = dict(np.load(path))
         else:
             d = tfc.read_checkpoint(path, names=names)
+        if shadows:
+            missing = sorted(k for k in shadows if k not in d)
+            if missing:
+                raise KeyError("checkpoint lacks %d moving averages, e.g. %s" % (len(missing), missing[:3]))
         if optimizer_state:
             self._parse_optimizer_state(d)      # refuses a checkpoint without this optimiser's state before anything is set
+        if ema_as_weights:
+            d = dict(d)
+            for k, n in shadows.items():
+                d[n] = d[k]
         self.load(d)
         if optimizer_state:
             self.load_optimizer_state(d)
+        if ema:
+            for k, n in shadows.items():
+                self.set_ema_var(n, d[k])
         return path
 
-    def save_checkpoint(self, directory, step, keep=10, optimizer_state=False):
+    def save_checkpoint(self, directory, step, keep=10, optimizer_state=False, ema=False):
         """saver.save(sess, '<dir>/p3d_<step>.ckpt') with max_to_keep (train.py:180-185,266-267): writes a TF V2 bundle and
         updates the directory's `checkpoint` state file.  With optimizer_state the bundle also holds the optimiser's slots
-        under their TF names (optimizer_state()), as a default tf.train.Saver writes them.  Returns the prefix."""
+        under their TF names (optimizer_state()), as a default tf.train.Saver writes them; with ema the moving averages of
+        set_ema under <var>/ExponentialMovingAverage (ema_state()).  Returns the prefix."""
         import os
         from . import tf_checkpoint as tfc
         prefix = os.path.join(directory, "p3d_%d.ckpt" % step)
         variables = self.save()
         if optimizer_state:
             variables.update(self.optimizer_state())
+        if ema:
+            variables.update(self.ema_state())
         tfc.write_checkpoint(prefix, variables)
         tfc.update_checkpoint_state(directory, prefix, keep)
         return prefix
@@ -340,6 +369,52 @@ class P3DSession:
         ss, nm, sc = C.c_double(), C.c_double(), C.c_float()
         check(lib().p3d_get_grad_norm(self._h, C.byref(ss), C.byref(nm), C.byref(sc)))
         return (nm.value, sc.value, ss.value) if with_sumsq else (nm.value, sc.value)
+
+    # ---- moving average of the weights (p3d_set_ema) ---------------------------------------------------
+    def set_ema(self, decay, warmup=False):
+        """Keep an exponential moving average of every trainable variable, as tf.train.ExponentialMovingAverage(decay).apply(
+        tf.trainable_variables()) after the train op (an addition: the reference scores single checkpoints).  After every
+        train step s = s - (s - p) * om in float32, om = float32(1 - decay); warmup is TF's num_updates: the decay of step t is
+        min(decay, (1 + t) / (10 + t)).  0 <= decay < 1; None switches the option off, the default.  Switching it on seeds the
+        shadows with the current weights.  The step's loss and weights do not change; averaged() scores the shadows."""
+        check(lib().p3d_set_ema(self._h, -1.0 if decay is None else float(decay), 1 if warmup else 0))
+
+    def get_ema(self, name):
+        shape = dict((n, s) for n, s, _ in self.variables())[name]
+        a = np.empty(shape, np.float32)
+        check(lib().p3d_get_ema(self._h, name.encode(), fptr(a), a.size))
+        return a
+
+    def set_ema_var(self, name, value):
+        a = np.ascontiguousarray(value, dtype=np.float32)
+        check(lib().p3d_set_ema_var(self._h, name.encode(), fptr(a), a.size))
+
+    def ema_state(self):
+        """{<var>/ExponentialMovingAverage: array}: the shadows under the names a tf.train.Saver stores them."""
+        return dict((k, self.get_ema(n)) for k, n in ema_names(self.variables()).items())
+
+    def ema_swap(self):
+        """Exchange weights and moving averages of every trainable on the device, bit for bit; a second call restores both.
+        While exchanged the session refuses train_step, backward, set_param, init_params and set_ema, and get_param returns
+        the averages."""
+        check(lib().p3d_ema_swap(self._h))
+
+    def ema_swapped(self):
+        return lib().p3d_ema_swapped(self._h) == 1
+
+    def averaged(self):
+        """with sess.averaged(): forward / evaluate / predict_windows / pred_maps_u8 run on the averaged weights; the weights
+        come back on leaving the block, also through an exception."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def scope():
+            self.ema_swap()
+            try:
+                yield self
+            finally:
+                self.ema_swap()
+        return scope()
 
     def predict_windows(self, x):
         """B windows of gen_pred.py:100-168 at once: row k equals forward(x[k:k+1], training=False) of a batch-1
