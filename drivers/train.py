@@ -13,7 +13,9 @@ checkpoints (P3DSession.set_optimizer, save_checkpoint / restore optimizer_state
 gradients by their global norm, as tf.clip_by_global_norm does, and prints the norm and the scale with the step
 (P3DSession.set_grad_clip); `--ema-decay D` (with `--ema-warmup`) keeps tf.train.ExponentialMovingAverage's shadows of the
 trainables: the checkpoints carry them, --pretrain restores them when present, and the periodic eval forward and the
-validation pass score the averaged weights (P3DSession.set_ema).  The dataset loaders (dataflow.py,
+validation pass score the averaged weights (P3DSession.set_ema); `--accum-steps K` sums the gradients of K batches before
+every optimiser update (P3DSession.set_grad_accum): `--saveiter / --validiter / --plotiter` and the printed step then count
+updates, and the printed loss is the sum of the K batches' losses.  The dataset loaders (dataflow.py,
 tensorpack, cv2) are out of scope: clips come either from `--data clips.npz` (arrays x [N,16,112,112,3] already normalised like
 dataflow.py:204-208, y [N,16,112,112]; raw uint8 frames go through sap3d_tensorflow_amd.dataflow.mapf_frames first) or
 are synthetic with the loader's value law.
@@ -98,6 +100,13 @@ def get_arguments():
                         "pass run on them")
     p.add_argument("--ema-warmup", action="store_true",
                    help="[addition] TF's num_updates: step t averages with min(D, (1 + t) / (10 + t)) (--ema-decay only)")
+    # BatchNorm normalises over the batch in the whole backbone: a larger --batch changes the statistics, accumulation does not
+    p.add_argument("--accum-steps", type=int, default=1, metavar="K",
+                   help="[addition] sum the gradients of K batches, each run with its own BatchNorm statistics, before every "
+                        "optimiser update (the loss is a sum over the batch, so this is the gradient of K * batch clips; not "
+                        "averaged: scale --lr for momentum / sgd).  --saveiter, --validiter, --plotiter and the printed step "
+                        "count updates; the printed loss is the sum over the K batches; batches left over at the end of an "
+                        "epoch are dropped.  1 = off")
     return p.parse_args()
 
 
@@ -115,6 +124,13 @@ def batches(args, rng):
         for s in range(args.epoch * args.steps):
             shape = (args.batch, args.videolength, args.imagesize[0], args.imagesize[1])
             yield law.synthetic_clip(s, shape + (3,)), law.synthetic_target(10_000 + s, shape)
+
+
+def batches_per_epoch(args):
+    """How many batches batches() yields per epoch."""
+    if args.data:
+        return len(range(0, len(np.load(args.data)["y"]) - args.batch + 1, args.batch))
+    return args.steps
 
 
 def validation_batches(args):
@@ -211,6 +227,13 @@ def main():
         except P3dError as e:
             sess.close()
             raise SystemExit("--ema-decay %s: %s" % (args.ema_decay, e))
+    accum = args.accum_steps
+    if accum != 1:
+        try:
+            sess.set_grad_accum(accum)
+        except P3dError as e:
+            sess.close()
+            raise SystemExit("--accum-steps %s: %s" % (accum, e))
     model_dir = os.path.join("model", args.info)
     os.makedirs(model_dir, exist_ok=True)
     if args.pretrain:
@@ -224,10 +247,19 @@ def main():
             sess.set_ema(None)                                                          # they start from its weights
             sess.set_ema(args.ema_decay, warmup=args.ema_warmup)
     print("Start training")
-    step = 0
+    step = 0                  # optimiser updates
+    micro = 0                 # batches seen: `step` itself unless --accum-steps
+    per_epoch = batches_per_epoch(args) if accum > 1 else 0
+    loss = 0.0
     for xs, ys in batches(args, np.random.default_rng(0)):
+        micro += 1
+        loss += sess.train_step(xs, ys, dropout=0.5, seed=micro)                    # train.py:217-218
+        if accum > 1 and sess.grad_accum[1] != 0:
+            if micro % per_epoch == 0:      # an incomplete cycle does not cross the epoch (the loaders' remainder=False)
+                sess.set_grad_accum(accum)
+                loss = 0.0
+            continue                        # no update yet: nothing to print, score or save
         step += 1
-        loss = sess.train_step(xs, ys, dropout=0.5, seed=step)                      # train.py:217-218
         if args.clip_norm != 0.0:
             gn_, sc_ = sess.last_grad_norm()
         if step < 10 or step % args.plotiter == 0:
@@ -241,6 +273,9 @@ def main():
                 validate(sess, args, step)                                          # train.py:243-264
         if step % args.saveiter == 0:
             sess.save_checkpoint(model_dir, step, keep=10, optimizer_state=args.optimizer_state, ema=ema)     # train.py:180-185,266-267
+        loss = 0.0
+    if accum > 1:
+        print("Optimiser updates:", step, "from", micro, "batches")
     print("Training Finished!")
     sess.close()
 

@@ -247,6 +247,36 @@ int p3d_set_ema_var(p3d_handle* h, const char* var, const float* host, int64_t c
 int p3d_ema_swap(p3d_handle* h);
 int p3d_ema_swapped(p3d_handle* h);
 
+/* Gradient accumulation over micro-batches: the TF-1 idiom of running the gradients K times into accumulators and calling
+ * apply_gradients once (an addition: the reference applies every batch of 2, train.py:39; with BatchNorm on batch statistics in
+ * the whole backbone a larger batch changes what is normalised, and accumulation is how the effective batch grows without that).
+ * k = 1: off, the default -- a step launches what it launched before the option existed and no memory is allocated; k >= 2: on;
+ * k < 1: -1, nothing changed.  With k >= 2 every call of p3d_train_step, p3d_train_step_device, p3d_profile_step or
+ * p3d_debug_schedule is one MICRO-STEP j = pending of a cycle of k:
+ *   j < k-1   accumulates.  Forward with training on and the moving-statistics updates, loss, backward.  No all-reduce, no
+ *             optimiser, norm or moving-average launch; the optimiser's step count does not move, weights and slots keep their
+ *             bits.  Then acc = g (j = 0: a copy of the bits, -0 stays -0) or acc = fadd(acc, g) (j > 0) in float32 over every
+ *             trainable element.  The returned loss is this micro-batch's data loss alone and p3d_last_regularization gives 0;
+ *             p3d_get_grad returns this micro-batch's gradient; p3d_get_grad_norm keeps the values of the last update.
+ *   j = k-1   applies.  After the backward the gradient buffer becomes fadd(acc, g), and everything downstream runs on it as on
+ *             any gradient, in the usual order: the all-reduce (the sum over ranks of each rank's accumulated sum), the
+ *             regularisation term g + c*w (once per update), the global norm and its scale, the optimiser of the current kind in
+ *             its two parts, the moving average, the step count + 1.  pending returns to 0.  p3d_get_grad returns the
+ *             accumulated (and reduced) gradient; the loss is this micro-batch's data loss plus the regularisation term.
+ * Gradients are SUMMED, not averaged: every loss here is a sum over the batch, and data parallelism sums in the same way, so k
+ * micro-batches of B clips give the gradient of one batch of k*B clips (up to BatchNorm's statistics, which stay per
+ * micro-batch).  Adam does not see the scale; with Momentum or SGD scale lr by 1/k, or clip.  The order is fixed,
+ * ((g0 + g1) + g2) + ... per element with each sum rounded once to float32: the same bits on every run.
+ * The accumulator holds one float per trainable element and is allocated the first time k >= 2 is set.  Any call of
+ * p3d_set_grad_accum (with the same k too) and p3d_init_params discard a partial sum and set pending to 0; p3d_set_param,
+ * p3d_set_optimizer, p3d_set_ema, p3d_ema_swap and p3d_backward leave it alone -- p3d_backward stays the parity hook and neither
+ * reads nor writes the accumulator.  While k >= 2 a captured step (P3D_GRAPH=1) is not used: a cycle has three launch lists, and
+ * the step runs the eager one; the call drops a captured step graph.  Checkpoints do not store a partial sum: save at update
+ * boundaries (pending = 0).
+ * p3d_get_grad_accum: k, and pending = the micro-steps accumulated since the last update, 0 .. k-1 (either pointer may be NULL). */
+int p3d_set_grad_accum(p3d_handle* h, int k);
+int p3d_get_grad_accum(p3d_handle* h, int* k, int* pending);
+
 /* ---- intermediate tensors (tf fetches of graph tensors; parity/debug taps).  Names:
  *      conv1_custom, conv1_custom_bn_relu, pool1..pool4, block<i>/conv1_bn_relu, block<i>/st,
  *      block<i>/out, deconv3_re, deconv4_conv1, logits, pred. */
@@ -459,6 +489,12 @@ int p3d_debug_optimizer_decay(int device, int kind, float* p, float* g, float* m
  * device memory as a captured step with warm-up passes it.  The hook surrounds both ranges with guard elements and returns -1
  * if the launch changed one, or changed p. */
 int p3d_debug_ema(int device, float* s, const float* p, int64_t n, int offset, float om, int om_on_device);
+/* Test hook: one grad_accum_kernel launch (p3d_set_grad_accum; as the train step launches it) on n accumulator elements acc and
+ * gradients g placed `offset` (0..3) elements past a 16-byte boundary of the device buffers.  mode 0 (STORE): acc = g; 1 (ADD):
+ * acc = fadd(acc, g); 2 (FINISH): g = fadd(acc, g).  The operand the mode writes comes back in place.  The hook surrounds both
+ * ranges with guard elements and returns -1 if the launch changed one, or changed the operand its mode must not write (g under
+ * STORE and ADD, acc under FINISH). */
+int p3d_debug_grad_accum(int device, int mode, float* acc, float* g, int64_t n, int offset);
 /* Test hook: any of the optimiser launches above with clipping's scale (OptArgs::gscale, read from device memory): kind
  * P3D_OPT_*, ntile = 0 for the plain kernels (tile pointers and term may be NULL) or a tile table as p3d_debug_adam_decay takes
  * it; g becomes g + c*p (not scaled), the update runs on fmul(g', gscale).  t and the betas matter under Adam only, momentum

@@ -131,6 +131,9 @@ SIGNATURES = {
     "p3d_set_ema_var": (C.c_int, [C.c_void_p, C.c_char_p, _fp, C.c_int64]),
     "p3d_ema_swap": (C.c_int, [C.c_void_p]),
     "p3d_ema_swapped": (C.c_int, [C.c_void_p]),
+    "p3d_set_grad_accum": (C.c_int, [C.c_void_p, C.c_int]),
+    "p3d_get_grad_accum": (C.c_int, [C.c_void_p, _ip, _ip]),
+    "p3d_debug_grad_accum": (C.c_int, [C.c_int, C.c_int, _fp, _fp, C.c_int64, C.c_int]),
     "p3d_debug_ema": (C.c_int, [C.c_int, _fp, _fp, C.c_int64, C.c_int, C.c_float, C.c_int]),
     "p3d_debug_stat_parts": (C.c_int, [_i64p, _i64p, _ip, C.c_int, _ip, _ip]),
     "p3d_debug_igemm_groupable": (C.c_int, [_i64p, _i64p, _ip]),

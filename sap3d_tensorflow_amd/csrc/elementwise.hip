@@ -745,6 +745,36 @@ __global__ __launch_bounds__(256) void ema_swap_kernel(float* a, float* b, long 
     }
 }
 
+// Gradient accumulation over micro-batches (p3d_set_grad_accum; GradAccumArgs in p3d_kernels.h).  One dense pass shaped like
+// ema_kernel: float4 groups from the first 16-byte boundary, the `head` elements before it and the cut last group one by one, the
+// same operation on every element.  GACC_STORE: acc = g, a copy of the bits (-0 stays -0, 8 bytes per element); GACC_ADD:
+// acc = fadd(acc, g); GACC_FINISH: g = fadd(acc, g), acc left alone (12 bytes).  A single add: nothing to contract, and float32
+// adds keep denormals here as ema_kernel's subtractions do.  Slot padding inside the range is summed like anything else.
+template <int MODE>
+__device__ __forceinline__ void gacc_elem(const GradAccumArgs& a, long long q) {
+    if (MODE == GACC_STORE) a.acc[q] = a.g[q];
+    else (MODE == GACC_FINISH ? a.g : a.acc)[q] = a.acc[q] + a.g[q];
+}
+template <int MODE>
+__global__ __launch_bounds__(256) void grad_accum_kernel(GradAccumArgs a) {
+    const long long n = a.n;
+    if (blockIdx.x == 0 && (int)threadIdx.x < a.head) gacc_elem<MODE>(a, threadIdx.x);
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n4; i += (long long)gridDim.x * blockDim.x) {
+        const long long e = a.head + (i << 2);
+        if (e + 3 < n) {
+            const float4 gg = ld4(a.g + e);
+            if (MODE == GACC_STORE) {
+                st4(a.acc + e, gg);
+            } else {
+                const float4 aa = ld4(a.acc + e);
+                st4((MODE == GACC_FINISH ? a.g : a.acc) + e, make_float4(aa.x + gg.x, aa.y + gg.y, aa.z + gg.z, aa.w + gg.w));
+            }
+        } else {
+            for (long long q = e; q < n; ++q) gacc_elem<MODE>(a, q);
+        }
+    }
+}
+
 // Global gradient norm (p3d_set_grad_clip; SumsqArgs in p3d_kernels.h).  Block b takes chunks k0 + b, k0 + b + gridDim.x, ... of
 // the table; chunk k's sum of g'^2 -- every square exact in double, one double accumulator per lane over a lane-to-element map
 // that depends on the chunk's place in memory alone, lanes folded by the xor butterfly and the four waves in order -- goes to
@@ -1303,6 +1333,30 @@ hipError_t p3d_ema_step(const EmaArgs& a, hipStream_t s) {
     ka.head = (int)std::min<long long>((long long)((16 - r) & 15) / 4, a.n);
     ka.n4 = (a.n - ka.head + 3) / 4;
     hipLaunchKernelGGL(ema_kernel, dim3(ka.n4 > 0 ? grid_for(ka.n4) : 1u), dim3(256), 0, s, ka);
+    return hipGetLastError();
+}
+
+LaunchDesc p3d_grad_accum_desc(const GradAccumArgs& a) {
+    // per element: STORE reads g and writes acc (8 bytes, no arithmetic); ADD and FINISH read both and write one (12 bytes, one add)
+    static const char* const names[3] = {"grad_accum_kernel<0>", "grad_accum_kernel<1>", "grad_accum_kernel<2>"};
+    const int m = a.mode >= GACC_STORE && a.mode <= GACC_FINISH ? a.mode : GACC_STORE;
+    return {names[m], m == GACC_STORE ? 0.0 : 1.0 * a.n, (m == GACC_STORE ? 8.0 : 12.0) * a.n};
+}
+
+hipError_t p3d_grad_accum_step(const GradAccumArgs& a, hipStream_t s) {
+    if (!a.acc || !a.g || a.acc == a.g || a.n < 1 || a.mode < GACC_STORE || a.mode > GACC_FINISH) return hipErrorInvalidValue;
+    // acc and g float-aligned and at the same place in a 16-byte line: the elements before the first 16-byte boundary go one by one
+    const uintptr_t r = low4(a.acc);
+    if ((r & 3) || low4(a.g) != r) return hipErrorInvalidValue;
+    GradAccumArgs ka = a;
+    ka.head = (int)std::min<long long>((long long)((16 - r) & 15) / 4, a.n);
+    ka.n4 = (a.n - ka.head + 3) / 4;
+    const dim3 grid(ka.n4 > 0 ? grid_for(ka.n4) : 1u);      // ema_kernel's launch shape: 256 lanes, at most 4096 blocks, grid-stride
+    switch (a.mode) {
+        case GACC_STORE: hipLaunchKernelGGL(grad_accum_kernel<GACC_STORE>, grid, dim3(256), 0, s, ka); break;
+        case GACC_ADD: hipLaunchKernelGGL(grad_accum_kernel<GACC_ADD>, grid, dim3(256), 0, s, ka); break;
+        default: hipLaunchKernelGGL(grad_accum_kernel<GACC_FINISH>, grid, dim3(256), 0, s, ka); break;
+    }
     return hipGetLastError();
 }
 

@@ -154,6 +154,7 @@ struct Ctx {
     const unsigned long long* seed_dev = nullptr;   // captured step graphs: dropout seed and Adam step size live in device memory
     const float* lr_dev = nullptr;
     const float* om_dev = nullptr;    // ... and the moving average's om under warm-up (p3d_set_ema)
+    bool acc_finish = false;          // the applying micro-step of p3d_set_grad_accum: the backward finishes flat_g = acc + g
     bool update_moving = false;
     bool per_sample = false;          // batch-statistics BNs normalise every clip by its own statistics (p3d_predict_windows)
     bool fuse = false;                // BatchNorm fused into the neighbouring convs' operand paths (set by run_forward / run_backward)

@@ -251,6 +251,7 @@ int p3d_init_params(p3d_handle* h, uint64_t seed) {
     h->step = 0;
     HIPCHECK(hipStreamSynchronize(h->stream));
     if (h->ema_on) h->ema_seed();      // fresh variables, fresh shadows
+    h->acc_pending = 0;                // and no partial sum of gradients (p3d_set_grad_accum)
     API_END
 }
 
@@ -374,6 +375,22 @@ int p3d_get_grad_norm(p3d_handle* h, double* sumsq, double* norm, float* scale) 
     if (!h) throw P3dError("null handle");
     HIPCHECK(hipSetDevice(h->cfg.device));
     h->read_grad_norm(sumsq, norm, scale);
+    API_END
+}
+
+int p3d_set_grad_accum(p3d_handle* h, int k) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->set_grad_accum(k);
+    API_END
+}
+
+int p3d_get_grad_accum(p3d_handle* h, int* k, int* pending) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    if (k) *k = h->acc_k;
+    if (pending) *pending = h->acc_pending;
     API_END
 }
 
@@ -685,8 +702,15 @@ int p3d_profile_step(p3d_handle* h, float dropout_rate, uint64_t seed, p3d_op_ti
         prof.cur_op = "loss"; h->run_loss(c);
         // no collective here: bench.py profiles on rank 0 only, after the timed region -- an all-reduce that the
         // other ranks do not enter would never return
-        prof.phase = 1; h->run_backward(c, false);
-        prof.phase = 2; prof.cur_op = "adam"; h->run_adam(c);
+        if (h->acc_accumulating()) {      // a micro-step of p3d_set_grad_accum that only accumulates
+            prof.phase = 1; h->run_backward(c, false);
+            prof.phase = 2; prof.cur_op = "grad_accum"; h->grad_accum_take(c);
+        } else {
+            c.acc_finish = h->acc_k > 1;
+            prof.phase = 1; h->run_backward(c, false);
+            prof.phase = 2; prof.cur_op = "adam"; h->run_adam(c);
+            h->acc_pending = 0;
+        }
         HIPCHECK(hipStreamSynchronize(c.s));
         int w = 0;
         for (auto& r : prof.recs) {
@@ -1479,6 +1503,43 @@ int p3d_debug_ema(int device, float* s, const float* p, int64_t n, int offset, f
             throw P3dError("ema: the launch wrote outside its range (element " + std::to_string(i - at) + ")");
     if (memcmp(pback.data() + at, p, (size_t)n * 4) != 0) throw P3dError("ema: the launch changed the parameters");
     memcpy(s, back.data() + at, (size_t)n * 4);
+    API_END
+}
+
+// One grad_accum_kernel launch from the step's launch description, placed and guarded as p3d_debug_ema's.  The operand the mode
+// writes comes back; the other one must keep its bits.
+int p3d_debug_grad_accum(int device, int mode, float* acc, float* g, int64_t n, int offset) {
+    API_BEGIN
+    HIPCHECK(hipSetDevice(device));
+    if (!acc || !g) throw P3dError("null argument");
+    if (mode < GACC_STORE || mode > GACC_FINISH) throw P3dError("grad_accum: mode is 0 (store), 1 (add) or 2 (finish)");
+    if (n < 1 || offset < 0 || offset > 3) throw P3dError("grad_accum: bad length or offset");
+    const int64_t at = 4 + offset;
+    const uint32_t guard = 0x7fc5a5a5u;      // a NaN no arithmetic here produces
+    std::vector<uint32_t> gs((size_t)(n + 12), guard);
+    DevBuf ab(n + 12, reinterpret_cast<const float*>(gs.data())), gb(n + 12, reinterpret_cast<const float*>(gs.data()));
+    HIPCHECK(copy_now(ab.p + at, acc, (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
+    HIPCHECK(copy_now(gb.p + at, g, (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
+    GradAccumArgs a;
+    a.acc = ab.p + at; a.g = gb.p + at; a.n = (long)n; a.mode = mode;
+    const LaunchDesc d = p3d_grad_accum_desc(a);
+    if (std::string(d.kernel) != "grad_accum_kernel<" + std::to_string(mode) + ">")
+        throw P3dError("grad_accum: launch description names another kernel");
+    HIPCHECK(p3d_grad_accum_step(a, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    std::vector<uint32_t> aback((size_t)(n + 12)), gback((size_t)(n + 12));
+    HIPCHECK(copy_now(aback.data(), ab.p, aback.size() * 4, hipMemcpyDeviceToHost, nullptr));
+    HIPCHECK(copy_now(gback.data(), gb.p, gback.size() * 4, hipMemcpyDeviceToHost, nullptr));
+    for (int64_t i = 0; i < n + 12; ++i)
+        if ((i < at || i >= at + n) && (aback[(size_t)i] != guard || gback[(size_t)i] != guard))
+            throw P3dError("grad_accum: the launch wrote outside its range (element " + std::to_string(i - at) + ")");
+    if (mode == GACC_FINISH) {
+        if (memcmp(aback.data() + at, acc, (size_t)n * 4) != 0) throw P3dError("grad_accum: FINISH changed the accumulator");
+        memcpy(g, gback.data() + at, (size_t)n * 4);
+    } else {
+        if (memcmp(gback.data() + at, g, (size_t)n * 4) != 0) throw P3dError("grad_accum: the launch changed the gradient");
+        memcpy(acc, aback.data() + at, (size_t)n * 4);
+    }
     API_END
 }
 

@@ -108,6 +108,10 @@
         // the chip (32x224x224 clips).
         std::vector<std::pair<hipEvent_t, std::function<void(const Ctx&)>>> parked;
         bool early_adam = false, early_comm = false;
+        // the applying micro-step of p3d_set_grad_accum: flat_g = acc + g, every element once, after its last producer and before
+        // its first reader (all-reduce, sumsq_range, adam_range).  With a communicator reduce_range finishes each bucket on the
+        // comm stream ahead of its collective; without one the main stream does, in the optimiser's two ranges (below)
+        const bool finish_main = c.acc_finish && !(allreduce && comm && !bucket_hook);
         static const bool no_defer = p3d_tune_env("P3D_DEFER_SIDE") && atoi(p3d_tune_env("P3D_DEFER_SIDE")) == 0;
         const bool defer_on = c.side && !no_defer && defer_release_op > 0 && defer_budget > 0;
         parked_flops = 0;
@@ -161,6 +165,7 @@
                 early_adam = false;
                 HIPCHECK(ev_wait(c.s, ev_side_early));
                 if (early_comm) HIPCHECK(ev_wait(c.s, ev_comm_early));
+                if (finish_main) grad_accum_range(c, GACC_FINISH, adam_split, n_train);      // final since ev_side_early
                 if (clip_on()) {
                     // clipping: no update before every gradient is final; the slot takes the norm's first range instead
                     sumsq_range(c, adam_split, n_train);
@@ -224,6 +229,7 @@
                 HIPCHECK(ev_wait(c.s, ev_comm_done));
             }
         }
+        if (finish_main) grad_accum_range(c, GACC_FINISH, 0, adam_done ? adam_split : n_train);      // the rest: the side stream is joined
         if (adam_done && clip_on()) {      // the norm's second range folds; then the optimiser's usual two ranges on the scale
             sumsq_range(c, 0, adam_split);
             adam_begin(c);
@@ -242,6 +248,10 @@
         if (c.side) {       // the bucket's weight gradients were queued on the side stream
             HIPCHECK(ev_record(ev_side_bucket, c.side));
             HIPCHECK(ev_wait(comm_stream, ev_side_bucket));
+        }
+        if (c.acc_finish) {      // p3d_set_grad_accum: each rank's accumulated sum is what the ranks add up
+            Ctx cc = c; cc.s = comm_stream; cc.side = nullptr;
+            grad_accum_range(cc, GACC_FINISH, lo, hi);
         }
         if (g_trace) g_trace->lines.push_back("C " + g_trace->sname(comm_stream) + " allreduce " + std::to_string(lo) + " " + std::to_string(hi));
         NCCLCHECK(ncclAllReduce(flat_g + lo, flat_g + lo, (size_t)(hi - lo), ncclFloat, ncclSum, comm, comm_stream));
@@ -344,6 +354,43 @@
         HIPCHECK(p3d_ema_swap(flat_p, flat_ema, (long long)n_train, stream));
         HIPCHECK(hipStreamSynchronize(stream));
         ema_swapped = !ema_swapped;
+    }
+
+    // ---- gradient accumulation over micro-batches (p3d_set_grad_accum) ---------------------------------
+    // acc_k >= 2: every train step is micro-step j = acc_pending of a cycle of acc_k.  j < acc_k - 1 accumulates: forward (moving
+    // statistics updated), loss, backward without all-reduce or optimiser, then flat_acc = g (j = 0, GACC_STORE) or
+    // flat_acc += g (GACC_ADD) over [0, n_train) on the main stream, which has joined the side stream by then (ev_side_done).
+    // The next call's zero_early forks from the main stream's tail, so its fill of flat_g stays behind this read.  j = acc_k - 1
+    // applies: run_backward (Ctx::acc_finish) writes flat_g = flat_acc + g range by range, and the all-reduce, the
+    // regularisation term, the norm, the optimiser and the moving average run on it as on any gradient.  flat_acc (one float
+    // per trainable element) is allocated the first time acc_k >= 2 is set.  p3d_backward and the audit hook never touch it.
+    float* flat_acc = nullptr;
+    int acc_k = 1, acc_pending = 0;
+    bool acc_accumulating() const { return acc_k > 1 && acc_pending < acc_k - 1; }
+    void grad_accum_range(const Ctx& c, int mode, int64_t lo, int64_t hi) {
+        if (hi <= lo) return;
+        GradAccumArgs a;
+        a.acc = flat_acc + lo; a.g = flat_g + lo; a.n = (long)(hi - lo); a.mode = mode;
+        const LaunchDesc d = p3d_grad_accum_desc(a);
+        if (g_trace && !c.dry)
+            g_trace->lines.push_back("G " + g_trace->sname(c.s) + (mode == GACC_STORE ? " store " : mode == GACC_ADD ? " add " : " finish ") +
+                                     std::to_string(lo) + " " + std::to_string(hi));
+        launch(c, d.kernel, d.flops, d.bytes, [&]() { return p3d_grad_accum_step(a, c.s); });
+    }
+    // the tail of an accumulating micro-step, after its run_backward(c, false, false)
+    void grad_accum_take(const Ctx& c) {
+        grad_accum_range(c, acc_pending == 0 ? GACC_STORE : GACC_ADD, 0, n_train);
+        // no term belongs to this micro-step: the loss read after it is the data loss alone, and p3d_last_regularization gives 0
+        if (reg_terms) HIPCHECK(fill_async(d_reg, 0, sizeof(double), c.s, "regularisation"));
+        ++acc_pending;
+    }
+    void set_grad_accum(int k) {
+        if (k < 1) throw P3dError("gradient accumulation: k must be 1 (off) or larger, not " + std::to_string(k));
+        sync_streams();
+        if (k > 1 && !flat_acc) flat_acc = dalloc<float>(n_train);
+        acc_k = k;
+        acc_pending = 0;          // a partial sum is discarded
+        drop_step_graph();        // the captured step is not used while k >= 2
     }
 
     // ---- gradient clipping by the global norm (p3d_set_grad_clip) ----------------------------------
@@ -589,11 +636,19 @@
     }
     void train_step_device(float drop, uint64_t seed) {
         refuse_swapped("train step");
-        if (!graphs_enabled()) {
+        // accumulation (p3d_set_grad_accum) has three launch lists per cycle and always runs the eager one
+        if (!graphs_enabled() || acc_k > 1) {
             Ctx c; c.training = true; c.drop = drop; c.seed = seed; c.update_moving = true; c.s = stream;
             zero_early(c);
             run_forward(c); run_loss(c);
+            if (acc_accumulating()) {
+                run_backward(c, false, false);
+                grad_accum_take(c);
+                return;
+            }
+            c.acc_finish = acc_k > 1;
             if (!run_backward(c, true, true)) run_adam(c);
+            acc_pending = 0;
             return;
         }
         if (!step_exec || graph_drop != drop || graph_f16 != pointwise_f16 || graph_comm != comm || graph_b1 != b1 || graph_b2 != b2 ||

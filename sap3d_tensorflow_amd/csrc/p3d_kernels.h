@@ -615,6 +615,19 @@ struct EmaArgs {
 };
 LaunchDesc p3d_ema_desc(const EmaArgs& a);
 hipError_t p3d_ema_step(const EmaArgs& a, hipStream_t s);
+// ---- gradient accumulation over micro-batches (p3d_set_grad_accum): grad_accum_kernel<MODE> ------------------------------------
+// One launch over n elements.  GACC_STORE: acc = g, a copy of the bits; GACC_ADD: acc = fadd(acc, g); GACC_FINISH: g = fadd(acc, g)
+// with acc left alone: float32, rounded once, the same on every element.  8 bytes per element for STORE, 12 for the others.
+// Refused (hipErrorInvalidValue): acc and g not float-aligned at the same place in a 16-byte line, acc == g, n < 1, another mode.
+enum { GACC_STORE = 0, GACC_ADD = 1, GACC_FINISH = 2 };
+struct GradAccumArgs {
+    float* acc = nullptr; float* g = nullptr;      // STORE / ADD write acc and read g; FINISH writes g and reads acc
+    long n = 0;
+    int mode = GACC_STORE;
+    long long n4 = 0; int head = 0;     // the dense pass's float4 groups and leading single elements: p3d_grad_accum_step's, not the caller's
+};
+LaunchDesc p3d_grad_accum_desc(const GradAccumArgs& a);
+hipError_t p3d_grad_accum_step(const GradAccumArgs& a, hipStream_t s);
 // a and b exchanged bit for bit (p3d_ema_swap): both 16-byte aligned, n a multiple of 4
 hipError_t p3d_ema_swap(float* a, float* b, long long n, hipStream_t s);
 // per-step scalars of a captured train step: scal[0..1] = dropout seed (64 bit), scal[2] = the optimiser's step size (opt_step_size),

@@ -509,6 +509,23 @@ def ema(s, p, om, om_on_device=False, offset=0, device=0):
     return s
 
 
+GRAD_ACCUM_MODES = {"store": 0, "add": 1, "finish": 2}
+
+
+def grad_accum(acc, g, mode, offset=0, device=0):
+    """Test hook: one launch of the accumulation kernel of P3DSession.set_grad_accum (grad_accum_kernel, p3d_debug_grad_accum)
+    on a flat float32 accumulator acc and gradient g placed `offset` (0..3) elements past a 16-byte boundary.  mode "store":
+    acc = g; "add": acc = acc + g; "finish": g = acc + g.  Returns the operand the mode writes; the inputs are not modified.
+    The hook itself guards both sides of the range and checks that the other operand kept its bits."""
+    acc = _f32(acc).ravel().copy()
+    g = _f32(g).ravel().copy()
+    if acc.size != g.size:
+        raise ValueError("acc and g differ in size")
+    m = GRAD_ACCUM_MODES[mode] if isinstance(mode, str) else int(mode)
+    check(lib().p3d_debug_grad_accum(device, m, fptr(acc), fptr(g), acc.size, int(offset)))
+    return g if m == 2 else acc
+
+
 def optimizer_decay(kind, p, g, m, tiles, lr=1e-4, momentum=0.9, use_nesterov=False, lr_on_device=False, update=True, offset=0,
                     device=0, gscale=None):
     """Test hook: adam_decay's launch with Momentum or SGD as the update (p3d_debug_optimizer_decay).  tiles = [(length,

@@ -370,6 +370,24 @@ class P3DSession:
         check(lib().p3d_get_grad_norm(self._h, C.byref(ss), C.byref(nm), C.byref(sc)))
         return (nm.value, sc.value, ss.value) if with_sumsq else (nm.value, sc.value)
 
+    # ---- gradient accumulation over micro-batches (p3d_set_grad_accum) ----------------------------------
+    def set_grad_accum(self, k):
+        """Accumulate the gradients of k micro-batches before one optimiser update (an addition: the reference updates on every
+        batch of 2).  k = 1 switches the option off, the default.  With k >= 2 every train_step is one micro-step: the first
+        k - 1 of a cycle run forward (moving statistics updated), loss and backward and add the gradient into an accumulator
+        in float32, in the fixed order ((g0 + g1) + g2) + ...; they return the micro-batch's data loss and move neither the
+        weights nor the optimiser's step.  The k-th applies the SUM (not the mean) through the usual all-reduce,
+        regularisation term, clipping, optimiser and moving average.  Any call, also with the same k, discards a partial sum;
+        so does init_params.  Checkpoints hold no partial sum: save when grad_accum[1] == 0."""
+        check(lib().p3d_set_grad_accum(self._h, int(k)))
+
+    @property
+    def grad_accum(self):
+        """(k, pending): the setting, and the micro-steps accumulated since the last update (0 .. k-1)."""
+        k, pending = C.c_int(0), C.c_int(0)
+        check(lib().p3d_get_grad_accum(self._h, C.byref(k), C.byref(pending)))
+        return k.value, pending.value
+
     # ---- moving average of the weights (p3d_set_ema) ---------------------------------------------------
     def set_ema(self, decay, warmup=False):
         """Keep an exponential moving average of every trainable variable, as tf.train.ExponentialMovingAverage(decay).apply(
