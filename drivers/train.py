@@ -5,7 +5,8 @@ Same flags (train.py:21-45), same step semantics (train.py:217-218: dropout 0.5,
 Smooth-L1 sum), same periodic eval forward (train.py:225-226) and checkpoint cadence (train.py:266-267).  Two flags are
 additions the reference does not have: `--loss bce | l1` trains with sigmoid cross-entropy on the head's logits or the L1
 sum instead of Smooth-L1, and `--loss kld | kld_cc` with the per-map KL divergence, plus `--cc-weight` times (1 - CC) for
-kld_cc (P3DSession.set_loss); `--regularization weightdecay | l2 | both` adds the weight-decay and L2
+kld_cc, and `--loss kld_cc_nss | kld_cc_nss_sim` adds `--nss-weight` times -NSS on fixation maps and `--sim-weight` times
+(1 - SIM) (P3DSession.set_loss); `--regularization weightdecay | l2 | both` adds the weight-decay and L2
 terms the reference builds and leaves commented out of its loss (train.py:161, gn/train_p3d_gn_dataset.py:188-189;
 P3DSession.set_regularization); `--optimizer momentum | sgd` (with `--momentum`, `--nesterov`) fine-tunes with the
 optimisers the reference's --pretrain help names, and `--optimizer-state` saves and restores the optimiser's slots with the
@@ -17,8 +18,10 @@ validation pass score the averaged weights (P3DSession.set_ema); `--accum-steps 
 every optimiser update (P3DSession.set_grad_accum): `--saveiter / --validiter / --plotiter` and the printed step then count
 updates, and the printed loss is the sum of the K batches' losses.  The dataset loaders (dataflow.py,
 tensorpack, cv2) are out of scope: clips come either from `--data clips.npz` (arrays x [N,16,112,112,3] already normalised like
-dataflow.py:204-208, y [N,16,112,112]; raw uint8 frames go through sap3d_tensorflow_amd.dataflow.mapf_frames first) or
-are synthetic with the loader's value law.
+dataflow.py:204-208, y [N,16,112,112]; raw uint8 frames go through sap3d_tensorflow_amd.dataflow.mapf_frames first; for the
+losses with an NSS term also fix [N,16,112,112] uint8, fixated where >= 128, or at any other resolution, which
+sap3d_tensorflow_amd.dataflow.fixations_to_grid brings to the grid) or are synthetic with the loader's value law (fixations:
+sap3d_tensorflow_amd.synthetic.synthetic_fixations of the target).
 Checkpoints are TensorFlow-1.x V2 bundles `model/<info>/p3d_<step>.ckpt.*` with a `checkpoint` state file, keyed by the
 TF variable names of train.py:180-185 (trainables + BN moving statistics): the files the reference's Saver writes and
 restores (sap3d_tensorflow_amd/tf_checkpoint.py); `--pretrain` takes such a directory, a bundle prefix, or an .npz.
@@ -64,12 +67,17 @@ def get_arguments():
     p.add_argument("--steps", type=int, default=20, help="steps per epoch when synthetic")
     p.add_argument("--validclips", type=int, default=4, help="validation batches per validation pass when synthetic")
     # not a reference flag (its flags are train.py:21-45): the loss option of P3DSession.set_loss
-    p.add_argument("--loss", choices=("smooth_l1", "bce", "l1", "kld", "kld_cc"), default="smooth_l1",
+    p.add_argument("--loss", choices=("smooth_l1", "bce", "l1", "kld", "kld_cc", "kld_cc_nss", "kld_cc_nss_sim"), default="smooth_l1",
                    help="[addition, no reference flag] training loss: smooth_l1 (the reference's, train.py:159), bce (sigmoid "
                         "cross-entropy on the head's logits, summed; no reference counterpart), l1 (L1 sum, train.py:160), kld "
                         "(KL divergence of every predicted / ground-truth map, utils/metrics.py:338-361, summed) or kld_cc "
-                        "(kld + cc-weight * (1 - CC), utils/metrics.py:227-250)")
-    p.add_argument("--cc-weight", type=float, default=1.0, help="[addition] weight of the (1 - CC) term of --loss kld_cc")
+                        "(kld + cc-weight * (1 - CC), utils/metrics.py:227-250), kld_cc_nss (kld_cc - nss-weight * NSS on the "
+                        "fixation maps, utils/metrics.py:200-224) or kld_cc_nss_sim (that + sim-weight * (1 - SIM), :258-287)")
+    p.add_argument("--cc-weight", type=float, default=1.0, help="[addition] weight of the (1 - CC) term of --loss kld_cc*")
+    p.add_argument("--nss-weight", type=float, default=1.0, help="[addition] weight of the -NSS term of --loss kld_cc_nss*; above 0 "
+                   "the clips need fixation maps (--data with `fix`; synthetic runs draw them from the target)")
+    p.add_argument("--sim-weight", type=float, default=None, help="[addition] weight of the (1 - SIM) term of --loss kld_cc_nss* "
+                   "(default 0 for kld_cc_nss, 1 for kld_cc_nss_sim)")
     # not a reference flag either: the regularisation option of P3DSession.set_regularization
     p.add_argument("--regularization", choices=("none", "weightdecay", "l2", "both"), default="none",
                    help="[addition, no reference flag] terms added to the loss: weightdecay (mean of wd * l2_loss over the "
@@ -110,20 +118,44 @@ def get_arguments():
     return p.parse_args()
 
 
+def with_fixations(args):
+    """Whether the loss reads fixation maps: a loss with an NSS term whose weight is above 0."""
+    return args.loss in ("kld_cc_nss", "kld_cc_nss_sim") and args.nss_weight > 0
+
+
+def grid_fixations(fix, y_shape):
+    """The `fix` array of --data on the clips' grid: uint8 [N,T,H,W] as it is, any other [N,T,H0,W0] through fixations_to_grid."""
+    from sap3d_tensorflow_amd.dataflow import fixations_to_grid
+    fix = np.asarray(fix)
+    if fix.dtype != np.uint8 or fix.ndim != 4 or fix.shape[:2] != tuple(y_shape[:2]):
+        raise SystemExit("--data: fix is %s %s, expected uint8 [N,T,H,W] beside y %s" % (fix.dtype, fix.shape, tuple(y_shape)))
+    if fix.shape == tuple(y_shape):
+        return fix
+    n, t = fix.shape[:2]
+    return fixations_to_grid(fix.reshape((n * t,) + fix.shape[2:]), y_shape[2], y_shape[3]).reshape(tuple(y_shape))
+
+
 def batches(args, rng):
+    """(x, y, fixations) per batch; fixations None unless the loss reads them."""
     from sap3d_tensorflow_amd import synthetic as law
     if args.data:
         d = np.load(args.data)
         x, y = d["x"].astype(np.float32), d["y"].astype(np.float32)
+        fix = None
+        if with_fixations(args):
+            if "fix" not in d:
+                raise SystemExit("--loss %s with --nss-weight %g needs fixation maps: --data has no `fix`" % (args.loss, args.nss_weight))
+            fix = grid_fixations(d["fix"], y.shape)
         for e in range(args.epoch):
             order = rng.permutation(len(x))
             for i in range(0, len(x) - args.batch + 1, args.batch):
                 idx = order[i:i + args.batch]
-                yield x[idx], y[idx]
+                yield x[idx], y[idx], (fix[idx] if fix is not None else None)
     else:
         for s in range(args.epoch * args.steps):
             shape = (args.batch, args.videolength, args.imagesize[0], args.imagesize[1])
-            yield law.synthetic_clip(s, shape + (3,)), law.synthetic_target(10_000 + s, shape)
+            y = law.synthetic_target(10_000 + s, shape)
+            yield law.synthetic_clip(s, shape + (3,)), y, (law.synthetic_fixations(20_000 + s, y) if with_fixations(args) else None)
 
 
 def batches_per_epoch(args):
@@ -197,9 +229,12 @@ def main():
         except (P3dError, ValueError) as e:
             sess.close()
             raise SystemExit("--optimizer %s: %s" % (args.optimizer, e))
+    saliency = args.loss in ("kld_cc_nss", "kld_cc_nss_sim")
     try:
         if args.loss == "kld_cc":
             sess.set_loss(args.loss, cc_weight=args.cc_weight)
+        elif saliency:
+            sess.set_loss(args.loss, cc_weight=args.cc_weight, nss_weight=args.nss_weight, sim_weight=args.sim_weight)
         else:
             sess.set_loss(args.loss)
     except (P3dError, ValueError) as e:
@@ -251,9 +286,9 @@ def main():
     micro = 0                 # batches seen: `step` itself unless --accum-steps
     per_epoch = batches_per_epoch(args) if accum > 1 else 0
     loss = 0.0
-    for xs, ys in batches(args, np.random.default_rng(0)):
+    for xs, ys, fs in batches(args, np.random.default_rng(0)):
         micro += 1
-        loss += sess.train_step(xs, ys, dropout=0.5, seed=micro)                    # train.py:217-218
+        loss += sess.train_step(xs, ys, dropout=0.5, seed=micro, fixations=fs)      # train.py:217-218
         if accum > 1 and sess.grad_accum[1] != 0:
             if micro % per_epoch == 0:      # an incomplete cycle does not cross the epoch (the loaders' remainder=False)
                 sess.set_grad_accum(accum)
@@ -264,6 +299,9 @@ def main():
             gn_, sc_ = sess.last_grad_norm()
         if step < 10 or step % args.plotiter == 0:
             clip = ("gnorm", "%.9g" % gn_, "scale", "%.9g" % sc_) if args.clip_norm != 0.0 else ()
+            if saliency:      # the means over the maps of the last batch where each term is defined
+                t = sess.last_loss_terms()
+                clip += ("KLD", "%.9g" % t["kld"], "CC", "%.9g" % t["cc"], "NSS", "%.9g" % t["nss"], "SIM", "%.9g" % t["sim"])
             with scoring(sess, ema):
                 image = sess.forward(xs, dropout=0.0, training=False)               # train.py:225-226
             print("Datetime", datetime.datetime.now().isoformat()[:-7], "Training step:", step,

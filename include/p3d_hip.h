@@ -140,13 +140,47 @@ int p3d_set_attention_mode(p3d_handle* h, int mode);
  *                       Statistics and gradients are float64 on the float32 maps (the reference's KLdiv is float32).  s is
  *                       the stored pred on the sigmoid heads; on the heads without a sigmoid (concat and the GroupNorm nets)
  *                       the raw output is read through a sigmoid, s = 1/(1+exp(-z)), as P3D_LOSS_BCE takes it as logits.
- * Any other kind, or a null handle: -1.  Drops a captured step graph; the next step captures anew. */
+ *   P3D_LOSS_SALIENCY   the per-map loss with the two remaining differentiable metrics and a fixation map f as a third input
+ *                       (p3d_upload_fixations; one byte per element, fixated <=> byte >= 128, the /255. > 0.5 of
+ *                       p3d_eval_last_frames): sum over the maps of
+ *                         w_kld KL_m + w_cc (1 - CC_m) + w_nss (-NSS_m) + w_sim (1 - SIM_m)
+ *                       (weights: p3d_set_saliency_weights, default 1, 1, 1, 0; p3d_set_loss_weights does not touch them).
+ *                       KL_m, CC_m and s are those of P3D_LOSS_KLD_CC.  With sbar = S/N, A = sum (s - sbar)^2, F the fixated
+ *                       count and S_f the sum of s over the fixated elements, NSS_m = (S_f/F - sbar) / sqrt(A/N)
+ *                       (utils/metrics.py:200-224, numpy's population std), undefined when F = 0 or A = 0.  With
+ *                       u = (s - min s) / (max s - min s), p' = u / sum u and q' likewise from y, SIM_m = sum min(p', q')
+ *                       (utils/metrics.py:258-287), undefined when s or y is constant; its gradient holds min s and max s
+ *                       fixed, dSIM/ds_i = ([p'_i < q'_i] - sum_j [p'_j < q'_j] p'_j) / sum_j (s_j - min s), the exact one
+ *                       touching only the arg-min / arg-max elements and being ambiguous under ties.  An undefined term adds 0
+ *                       to the map's loss and gradient, as CC does.  float64 on the float32 maps.  With w_nss = w_sim = 0 the
+ *                       loss and the gradients are those of P3D_LOSS_KLD_CC under w_kld, w_cc, bit for bit.
+ * Any other kind, or a null handle: -1.  Drops a captured step graph; the next step captures anew.  The first selection of
+ * P3D_LOSS_SALIENCY allocates its per-map scratch. */
 enum { P3D_LOSS_SMOOTH_L1 = 0, P3D_LOSS_BCE = 1, P3D_LOSS_L1 = 2 };
 enum { P3D_LOSS_KLD_CC = 3 };
+enum { P3D_LOSS_SALIENCY = 4 };
 int p3d_set_loss(p3d_handle* h, int kind);
 /* The weights of P3D_LOSS_KLD_CC (default 1, 1): finite, not negative, not both 0; else -1.  They reach the kernels as launch
  * arguments: a change drops a captured step graph. */
 int p3d_set_loss_weights(p3d_handle* h, float kld_weight, float cc_weight);
+/* The weights of P3D_LOSS_SALIENCY (default 1, 1, 1, 0): each finite and not negative, not all four 0; else -1 and nothing
+ * changes.  Launch arguments: a change drops a captured step graph.  Independent of p3d_set_loss_weights. */
+int p3d_set_saliency_weights(p3d_handle* h, float kld, float cc, float nss, float sim);
+/* The fixation maps of the batch for P3D_LOSS_SALIENCY: fix [B,T,H,W] bytes, copied into a device buffer the handle owns
+ * (allocated by the first call; its address then stays, so captured steps remain valid).  Synchronises.
+ * While the kind is P3D_LOSS_SALIENCY and w_nss > 0:
+ *   p3d_train_step and p3d_backward, which bring x and y from the host, need an upload since the previous such call and
+ *     return -1 (p3d_last_error names this function) without one: a stale map must not train silently.  Under
+ *     p3d_set_grad_accum that is one upload per micro-batch;
+ *   p3d_train_step_device, p3d_profile_step and p3d_debug_schedule reuse the buffer as they reuse x and y, and return -1 only
+ *     if nothing was ever uploaded.
+ * With w_nss = 0 fixations are neither needed nor read. */
+int p3d_upload_fixations(p3d_handle* h, const unsigned char* fix);
+/* What a trainer logs under P3D_LOSS_SALIENCY: over this rank's maps of the last step or backward, sums = sum KL_m, sum CC_m,
+ * sum NSS_m, sum SIM_m over the maps where each is defined (in map order, in double) and counts = how many those were (NSS is
+ * undefined everywhere while w_nss = 0: the fixations are not read).  Under p3d_set_grad_accum: the last micro-batch's.
+ * Synchronises.  -1 unless the last step or backward ran P3D_LOSS_SALIENCY. */
+int p3d_last_loss_terms(p3d_handle* h, double sums[4], int64_t counts[4]);
 
 /* Regularisation terms added to the loss of p3d_train_step, p3d_backward, p3d_train_step_device and p3d_profile_step: the two
  * collections the reference builds and leaves out of its loss (train.py:161, gn/train_p3d_gn_dataset.py:188-189), as opt-in.
@@ -460,6 +494,13 @@ int p3d_debug_loss(int device, int kind, const float* logits, const float* pred,
 int p3d_debug_map_loss(int device, const float* logits, const float* pred, const float* target, int64_t maps, int64_t map_elems,
                        int through_sigmoid, int offset, float kld_weight, float cc_weight, double* loss, float* dlogits,
                        double* per_map, int* info);
+/* Test hook: P3D_LOSS_SALIENCY as the network launches it (its three launches), as p3d_debug_map_loss with the fixation bytes
+ * fix [maps * map_elems] placed `offset` bytes into their device buffer (may be null when nss_weight is 0: they are not read)
+ * and the four weights (finite, not negative).  per_map [maps][4] = KL_m, CC_m, NSS_m, SIM_m (NaN where undefined); info as
+ * p3d_debug_map_loss. */
+int p3d_debug_saliency_loss(int device, const float* logits, const float* pred, const float* target, const unsigned char* fix,
+                            int64_t maps, int64_t map_elems, int through_sigmoid, int offset, float kld_weight, float cc_weight,
+                            float nss_weight, float sim_weight, double* loss, float* dlogits, double* per_map, int* info);
 /* Test hook: one Adam launch (p3d_opt_step, as the network's optimiser step launches it) on n elements placed `offset` elements
  * into the device buffers (Adam refuses a base that is not 16-byte aligned).  p, m, v are updated in place from g with
  * the bias-corrected step size of step t (the network's adam_step_size), passed as an argument or, when lr_on_device, through

@@ -14,6 +14,9 @@ LOSSES = {"smooth_l1": 0, "bce": 1, "l1": 2}
 # the per-map loss P3D_LOSS_KLD_CC under its names: (kld_weight, cc_weight) of p3d_set_loss_weights
 P3D_LOSS_KLD_CC = 3
 MAP_LOSSES = {"kld": (1.0, 0.0), "kld_cc": (1.0, 1.0)}
+# the per-map loss with a fixation map, P3D_LOSS_SALIENCY: (kld, cc, nss, sim) of p3d_set_saliency_weights
+P3D_LOSS_SALIENCY = 4
+SALIENCY_LOSSES = {"kld_cc_nss": (1.0, 1.0, 1.0, 0.0), "kld_cc_nss_sim": (1.0, 1.0, 1.0, 1.0)}
 # p3d_set_regularization terms (include/p3d_hip.h P3D_REG_*)
 REGULARIZATION = {"weightdecay": 1, "l2": 2}
 # p3d_set_optimizer kinds (include/p3d_hip.h P3D_OPT_*) and the TF slot names of each kind's slots 0, 1 (<var>/<suffix>)
@@ -41,6 +44,7 @@ _fp = C.POINTER(C.c_float)
 _i64p = C.POINTER(C.c_int64)
 _ip = C.POINTER(C.c_int)
 _dp = C.POINTER(C.c_double)
+_u8p = C.POINTER(C.c_ubyte)
 
 # every symbol include/p3d_hip.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -64,6 +68,9 @@ SIGNATURES = {
     "p3d_set_attention_mode": (C.c_int, [C.c_void_p, C.c_int]),
     "p3d_set_loss": (C.c_int, [C.c_void_p, C.c_int]),
     "p3d_set_loss_weights": (C.c_int, [C.c_void_p, C.c_float, C.c_float]),
+    "p3d_set_saliency_weights": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float]),
+    "p3d_upload_fixations": (C.c_int, [C.c_void_p, _u8p]),
+    "p3d_last_loss_terms": (C.c_int, [C.c_void_p, _dp, _i64p]),
     "p3d_set_regularization": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float]),
     "p3d_last_regularization": (C.c_int, [C.c_void_p, _dp]),
     "p3d_param_regularization": (C.c_int, [C.c_void_p, C.c_char_p, _fp, _fp]),
@@ -113,6 +120,8 @@ SIGNATURES = {
     "p3d_debug_loss": (C.c_int, [C.c_int, C.c_int, _fp, _fp, _fp, C.c_int64, C.c_int, C.c_int, _dp, _fp, _ip]),
     "p3d_debug_map_loss": (C.c_int, [C.c_int, _fp, _fp, _fp, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_float, _dp,
                                      _fp, _dp, _ip]),
+    "p3d_debug_saliency_loss": (C.c_int, [C.c_int, _fp, _fp, _fp, _u8p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_float,
+                                          C.c_float, C.c_float, _dp, _fp, _dp, _ip]),
     "p3d_debug_adam_decay": (C.c_int, [C.c_int, _fp, _fp, _fp, _fp, C.c_int64, C.c_int, _i64p, _i64p, _fp, C.c_int, C.c_float,
                                        C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, _dp, _fp]),
     "p3d_debug_optimizer": (C.c_int, [C.c_int, C.c_int, _fp, _fp, _fp, C.c_int64, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int]),

@@ -1142,6 +1142,14 @@ struct p3d_handle {
     float kld_weight = 1.f, cc_weight = 1.f;  // p3d_set_loss_weights (P3D_LOSS_KLD_CC)
     double* d_map_scratch = nullptr;          // P3D_LOSS_KLD_CC: per-map statistics and block partials, planned in head()
     unsigned* d_map_cnt = nullptr;            //   and its arrival counters (zero between launches)
+    // P3D_LOSS_SALIENCY: p3d_set_saliency_weights, its scratch (allocated when the kind is first selected) and the fixation
+    // bytes [B,T,H,W] of p3d_upload_fixations (allocated by the first upload); nothing of it exists for users of other kinds
+    float sal_kld = 1.f, sal_cc = 1.f, sal_nss = 1.f, sal_sim = 0.f;
+    double* d_sal_scratch = nullptr;
+    unsigned* d_sal_cnt = nullptr;
+    unsigned char* d_fix = nullptr;
+    bool fix_fresh = false;                   // uploaded since the last p3d_train_step / p3d_backward
+    int last_loss_kind = -1;                  // the kind of the last step's or backward's loss launches (p3d_last_loss_terms)
     float lr = 1e-4f, b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
     int64_t step = 0;                         // completed optimiser steps (every kind)
     int opt_kind = P3D_OPT_ADAM;              // p3d_set_optimizer: Momentum keeps its accumulator in flat_m

@@ -313,10 +313,17 @@ int p3d_set_attention_mode(p3d_handle* h, int mode) {
 int p3d_set_loss(p3d_handle* h, int kind) {
     API_BEGIN
     if (!h) throw P3dError("null handle");
-    if (kind != P3D_LOSS_SMOOTH_L1 && kind != P3D_LOSS_BCE && kind != P3D_LOSS_L1 && kind != P3D_LOSS_KLD_CC)
-        throw P3dError("loss kind is 0 (Smooth-L1), 1 (sigmoid cross-entropy on the logits), 2 (L1 sum) or 3 (per-map KL + CC), "
-                       "not " + std::to_string(kind));
+    if (kind != P3D_LOSS_SMOOTH_L1 && kind != P3D_LOSS_BCE && kind != P3D_LOSS_L1 && kind != P3D_LOSS_KLD_CC && kind != P3D_LOSS_SALIENCY)
+        throw P3dError("loss kind is 0 (Smooth-L1), 1 (sigmoid cross-entropy on the logits), 2 (L1 sum), 3 (per-map KL + CC) or "
+                       "4 (per-map KL + CC + NSS + SIM), not " + std::to_string(kind));
     HIPCHECK(hipSetDevice(h->cfg.device));
+    if (kind == P3D_LOSS_SALIENCY && !h->d_sal_scratch) {      // planned once, here: a step allocates nothing
+        size_t md = 0, mc = 0;
+        p3d_saliency_loss_scratch((long long)h->pred->N * h->pred->D, (long long)h->pred->H * h->pred->W, &md, &mc);
+        h->d_sal_scratch = h->dalloc<double>((int64_t)md);
+        h->d_sal_cnt = h->dalloc<unsigned>((int64_t)mc);
+        HIPCHECK(fill_now(h->d_sal_cnt, 0, mc * sizeof(unsigned), h->stream));
+    }
     h->loss_kind = kind;
     h->drop_step_graph();      // a captured step names the loss kernel it was captured with
     API_END
@@ -332,6 +339,48 @@ int p3d_set_loss_weights(p3d_handle* h, float kld_weight, float cc_weight) {
     h->kld_weight = kld_weight;
     h->cc_weight = cc_weight;
     h->drop_step_graph();      // the weights are launch arguments of the captured loss launches
+    API_END
+}
+
+int p3d_set_saliency_weights(p3d_handle* h, float kld, float cc, float nss, float sim) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    for (float w : {kld, cc, nss, sim})
+        if (!std::isfinite(w) || w < 0.f) throw P3dError("saliency loss weights must be finite and not negative");
+    if (kld == 0.f && cc == 0.f && nss == 0.f && sim == 0.f) throw P3dError("saliency loss weights: all four are 0");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->sal_kld = kld; h->sal_cc = cc; h->sal_nss = nss; h->sal_sim = sim;
+    h->drop_step_graph();      // the weights are launch arguments of the captured loss launches
+    API_END
+}
+
+int p3d_upload_fixations(p3d_handle* h, const unsigned char* fix) {
+    API_BEGIN
+    if (!h || !fix) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->upload_fixations(fix);
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    API_END
+}
+
+int p3d_last_loss_terms(p3d_handle* h, double sums[4], int64_t counts[4]) {
+    API_BEGIN
+    if (!h || !sums || !counts) throw P3dError("null argument");
+    if (h->last_loss_kind != P3D_LOSS_SALIENCY)
+        throw P3dError("loss terms: the last step or backward did not run P3D_LOSS_SALIENCY (p3d_set_loss kind 4)");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    const size_t maps = (size_t)h->pred->N * h->pred->D;
+    std::vector<double> st(maps * (P3D_MAP_STATS + P3D_SAL_STATS));
+    HIPCHECK(hipMemcpyAsync(st.data(), h->d_sal_scratch, st.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    const double* ms = st.data();
+    const double* xs = st.data() + maps * P3D_MAP_STATS;
+    for (int k = 0; k < 4; ++k) { sums[k] = 0.0; counts[k] = 0; }
+    for (size_t m = 0; m < maps; ++m) {      // in map order; a term that is undefined on a map (NaN) is left out of its sum and count
+        const double v[4] = {ms[m * P3D_MAP_STATS + 2], ms[m * P3D_MAP_STATS + 3], xs[m * P3D_SAL_STATS + 6], xs[m * P3D_SAL_STATS + 7]};
+        for (int k = 0; k < 4; ++k)
+            if (!std::isnan(v[k])) { sums[k] += v[k]; ++counts[k]; }
+    }
     API_END
 }
 
@@ -456,6 +505,8 @@ int p3d_backward(p3d_handle* h, const float* x, const float* y, float dropout_ra
     if (!h || !x || !y) throw P3dError("null argument");
     h->refuse_swapped("p3d_backward");
     HIPCHECK(hipSetDevice(h->cfg.device));
+    h->check_fixations(true);
+    h->fix_fresh = false;
     h->upload(x, y);
     Ctx c; c.training = true; c.drop = dropout_rate; c.seed = seed; c.update_moving = false; c.s = h->stream;
     h->run_forward(c);
@@ -506,6 +557,9 @@ int p3d_train_step(p3d_handle* h, const float* x, const float* y, float dropout_
     API_BEGIN
     if (!h || !x || !y) throw P3dError("null argument");
     HIPCHECK(hipSetDevice(h->cfg.device));
+    h->refuse_swapped("train step");
+    h->check_fixations(true);
+    h->fix_fresh = false;
     h->upload(x, y);
     h->train_step_device(dropout_rate, seed);
     const float l = h->read_loss();
@@ -1406,6 +1460,7 @@ int p3d_debug_loss(int device, int kind, const float* logits, const float* pred,
                    int offset, double* loss, float* dlogits, int* info) {
     API_BEGIN
     if (kind == P3D_LOSS_KLD_CC) throw P3dError("loss: kind 3 (per-map KL + CC) needs the map geometry: p3d_debug_map_loss");
+    if (kind == P3D_LOSS_SALIENCY) throw P3dError("loss: kind 4 (per-map KL + CC + NSS + SIM) needs the map geometry: p3d_debug_saliency_loss");
     if (kind != P3D_LOSS_SMOOTH_L1 && kind != P3D_LOSS_BCE && kind != P3D_LOSS_L1) throw P3dError("loss: kind is 0, 1 or 2");
     debug_loss(device, kind, logits, pred, target, n, through_sigmoid, offset, loss, dlogits, info, kind ? "loss" : "smooth_l1");
     API_END
@@ -1445,6 +1500,52 @@ int p3d_debug_map_loss(int device, const float* logits, const float* pred, const
     db.back(dlogits);
     lb.back(loss);
     info[0] = 3; info[1] = a.blocks; info[2] = a.vec4 ? 1 : 2;
+    API_END
+}
+
+// The same for P3D_LOSS_SALIENCY (run_saliency_loss): the fixation bytes sit `offset` bytes into their buffer.
+int p3d_debug_saliency_loss(int device, const float* logits, const float* pred, const float* target, const unsigned char* fix,
+                            int64_t maps, int64_t map_elems, int through_sigmoid, int offset, float kld_weight, float cc_weight,
+                            float nss_weight, float sim_weight, double* loss, float* dlogits, double* per_map, int* info) {
+    API_BEGIN
+    HIPCHECK(hipSetDevice(device));
+    if (!logits || !target || !loss || !dlogits || !per_map || !info || (through_sigmoid && !pred) || (nss_weight > 0.f && !fix))
+        throw P3dError("null argument");
+    if (maps < 1 || map_elems < 1 || offset < 0 || offset > 3) throw P3dError("saliency loss: bad geometry or offset");
+    if (maps * map_elems > ((int64_t)1 << 31)) throw P3dError("saliency loss: more than 2^31 elements");
+    for (float w : {kld_weight, cc_weight, nss_weight, sim_weight})
+        if (!std::isfinite(w) || w < 0.f) throw P3dError("saliency loss weights must be finite and not negative");
+    const int64_t n = maps * map_elems;
+    size_t md = 0, mc = 0;
+    p3d_saliency_loss_scratch(maps, map_elems, &md, &mc);
+    StagedBuf zb(n, offset, logits), pb(n, offset, through_sigmoid ? pred : nullptr), tb(n, offset, target), db(n, offset);
+    DevBuf fb((n + offset + 3) / 4 + 1);      // the bytes, in a zeroed buffer of whole words
+    unsigned char* fdev = reinterpret_cast<unsigned char*>(fb.p) + offset;
+    if (fix) HIPCHECK(copy_now(fdev, fix, (size_t)n, hipMemcpyHostToDevice, nullptr));
+    StagedDouble lb(loss);
+    DevBuf sb(2 * (int64_t)md), cb((int64_t)mc);
+    double* scratch = reinterpret_cast<double*>(sb.p);
+    const SaliencyLossArgs a = p3d_saliency_loss_args(zb.at(), pb.at(), tb.at(), fdev, maps, map_elems, through_sigmoid ? 1 : 0, kld_weight,
+                                                      cc_weight, nss_weight, sim_weight, lb.at(), db.at(), scratch,
+                                                      reinterpret_cast<unsigned*>(cb.p));
+    for (int stage = 0; stage < 3; ++stage) HIPCHECK(p3d_saliency_loss_launch(stage, a, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    std::vector<double> st((size_t)maps * (P3D_MAP_STATS + P3D_SAL_STATS));
+    HIPCHECK(copy_now(st.data(), scratch, st.size() * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    std::vector<unsigned> cnt(mc);
+    HIPCHECK(copy_now(cnt.data(), cb.p, mc * sizeof(unsigned), hipMemcpyDeviceToHost, nullptr));
+    for (unsigned v : cnt)
+        if (v) throw P3dError("saliency loss: an arrival counter was left nonzero");
+    const double* xs = st.data() + (size_t)maps * P3D_MAP_STATS;
+    for (int64_t m = 0; m < maps; ++m) {
+        per_map[4 * m] = st[(size_t)m * P3D_MAP_STATS + 2];
+        per_map[4 * m + 1] = st[(size_t)m * P3D_MAP_STATS + 3];
+        per_map[4 * m + 2] = xs[(size_t)m * P3D_SAL_STATS + 6];
+        per_map[4 * m + 3] = xs[(size_t)m * P3D_SAL_STATS + 7];
+    }
+    db.back(dlogits);
+    lb.back(loss);
+    info[0] = 3; info[1] = a.m.blocks; info[2] = a.m.vec4 ? 1 : 2;
     API_END
 }
 

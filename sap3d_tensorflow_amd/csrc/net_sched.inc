@@ -35,7 +35,9 @@
     }
     void run_loss(const Ctx& c) {
         HIPCHECK(fill_async(d_loss, 0, sizeof(double), c.s, "loss"));
+        if (!c.dry) last_loss_kind = loss_kind;
         if (loss_kind == P3D_LOSS_KLD_CC) return run_map_loss(c);
+        if (loss_kind == P3D_LOSS_SALIENCY) return run_saliency_loss(c);
         const LossArgs a = loss_args();
         const LaunchDesc d = p3d_loss_desc(a);
         launch(c, d.kernel, d.flops, d.bytes, [&]() { return p3d_loss(a, c.s); });
@@ -53,6 +55,33 @@
         launch(c, "map_loss_sums_kernel", rows * (2.0 + sg), rows * 8.0, [&]() { return p3d_map_loss_launch(0, a, c.s); });
         launch(c, "map_loss_terms_kernel", rows * (18.0 + sg), rows * 8.0, [&]() { return p3d_map_loss_launch(1, a, c.s); });
         launch(c, "map_loss_grad_kernel", rows * (20.0 + sg), rows * 12.0, [&]() { return p3d_map_loss_launch(2, a, c.s); });
+    }
+    // P3D_LOSS_SALIENCY (map_loss.hip): the same with w_nss (-NSS) + w_sim (1 - SIM) per map and the fixation bytes of
+    // p3d_upload_fixations as a third input, read (a byte per element, in the first and last launch) only when w_nss > 0.  Per
+    // element on top of the above: sums ~6 (two minima, two maxima, the fixated count and sum); terms ~6 (two double divisions,
+    // a compare); dlogits ~12.
+    bool saliency_needs_fixations() const { return loss_kind == P3D_LOSS_SALIENCY && sal_nss > 0.f; }
+    // fresh: the entry point brings new x / y from the host, so the fixations must be new too (a stale map must not train silently)
+    void check_fixations(bool fresh) const {
+        if (!saliency_needs_fixations()) return;
+        if (!d_fix) throw P3dError("the loss has an NSS term (w_nss > 0) and no fixation maps were uploaded: p3d_upload_fixations");
+        if (fresh && !fix_fresh)
+            throw P3dError("the loss has an NSS term (w_nss > 0) and the fixation maps are those of an earlier batch: "
+                           "p3d_upload_fixations before every p3d_train_step / p3d_backward");
+    }
+    SaliencyLossArgs saliency_loss_args() const {
+        return p3d_saliency_loss_args(logits->p, pred->p, d_y, d_fix, (long long)pred->N * pred->D, (long long)pred->H * pred->W,
+                                      head_sigmoid ? 1 : 0, sal_kld, sal_cc, sal_nss, sal_sim, d_loss, d_dlogits, d_sal_scratch, d_sal_cnt);
+    }
+    void run_saliency_loss(const Ctx& c) {
+        check_fixations(false);
+        if (!d_sal_scratch) throw P3dError("saliency loss: scratch was not planned (p3d_set_loss)");
+        const double rows = (double)pred->rows();
+        const double sg = head_sigmoid ? 0.0 : 3.0, fb = sal_nss > 0.f ? 1.0 : 0.0;
+        const SaliencyLossArgs a = saliency_loss_args();
+        launch(c, "saliency_loss_sums_kernel", rows * (8.0 + sg), rows * (8.0 + fb), [&]() { return p3d_saliency_loss_launch(0, a, c.s); });
+        launch(c, "saliency_loss_terms_kernel", rows * (24.0 + sg), rows * 8.0, [&]() { return p3d_saliency_loss_launch(1, a, c.s); });
+        launch(c, "saliency_loss_grad_kernel", rows * (32.0 + sg), rows * (12.0 + fb), [&]() { return p3d_saliency_loss_launch(2, a, c.s); });
     }
     // with_adam: the optimiser step is part of the call and split in two -- every variable but the first op's (and those its
     // backward reads, adam_split) is updated while that op's filter gradient (the stem's: the last launch of the pass, alone on
@@ -636,6 +665,7 @@
     }
     void train_step_device(float drop, uint64_t seed) {
         refuse_swapped("train step");
+        check_fixations(false);      // before a capture: a refusal must not cost the step graph
         // accumulation (p3d_set_grad_accum) has three launch lists per cycle and always runs the eager one
         if (!graphs_enabled() || acc_k > 1) {
             Ctx c; c.training = true; c.drop = drop; c.seed = seed; c.update_moving = true; c.s = stream;
@@ -666,6 +696,7 @@
             }
         }
         ++step;
+        last_loss_kind = loss_kind;
         HIPCHECK(p3d_set_step_scalars(d_seed, d_lr, ema_on && ema_warmup ? d_om : nullptr, seed, opt_step_size(step), ema_om(step), stream));
         HIPCHECK(hipGraphLaunch(step_exec, stream));
     }
@@ -673,6 +704,11 @@
     void upload(const float* x, const float* y) {
         if (x) HIPCHECK(hipMemcpyAsync(x_in->p, x, (size_t)x_in->rows() * 3 * sizeof(float), hipMemcpyHostToDevice, stream));
         if (y) HIPCHECK(hipMemcpyAsync(d_y, y, (size_t)pred->rows() * sizeof(float), hipMemcpyHostToDevice, stream));
+    }
+    void upload_fixations(const unsigned char* fix) {
+        if (!d_fix) d_fix = dalloc<unsigned char>(pred->rows());      // address stable from here on: captured steps name it
+        HIPCHECK(hipMemcpyAsync(d_fix, fix, (size_t)pred->rows(), hipMemcpyHostToDevice, stream));
+        fix_fresh = true;
     }
     float read_loss() {      // the data loss, plus the regularisation term when one is on
         double l = 0, r = 0;

@@ -538,6 +538,29 @@ MapLossArgs p3d_map_loss_args(const float* logits, const float* pred, const floa
                               double* scratch, unsigned* counters);
 hipError_t p3d_map_loss_launch(int stage, const MapLossArgs& a, hipStream_t s);
 
+// ---- the same with NSS and SIM terms and a fixation map (map_loss.hip; p3d_set_loss P3D_LOSS_SALIENCY) ------------------
+// w_kld KL + w_cc (1 - CC) + w_nss (-NSS) + w_sim (1 - SIM) per map, in sibling kernels of the three above over the same grid
+// (the P3D_LOSS_KLD_CC launches are untouched); m carries what they share.  fix: one byte per element, fixated <=> byte >= 128;
+// read only when nss_weight > 0 (use_fix), four bytes at a time on the float4 path.  The KL and CC parts are the expressions of
+// the kernels above, so with nss_weight = sim_weight = 0 loss and dlogits are theirs bit for bit.  Scratch:
+// p3d_saliency_loss_scratch's doubles and counters (counters zero before the first launch, left zero).  m.mstat[m] as above;
+// xstat[m] holds min s, max s, min y, max y, F, S_f, NSS_m, SIM_m (NaN where undefined), sum [p' < q'] p'.
+constexpr int P3D_SAL_STATS = 10;
+constexpr int P3D_SAL_PARTS = 8;      // partials per block: stage 0 writes eight, stage 1 seven
+struct SaliencyLossArgs {
+    MapLossArgs m;
+    const unsigned char* fix;
+    int use_fix;
+    float nss_weight, sim_weight;
+    double* xstat;
+};
+void p3d_saliency_loss_scratch(long long maps, long long map_elems, size_t* doubles, size_t* counters);
+SaliencyLossArgs p3d_saliency_loss_args(const float* logits, const float* pred, const float* target, const unsigned char* fix,
+                                        long long maps, long long map_elems, int through_sigmoid, float kld_weight, float cc_weight,
+                                        float nss_weight, float sim_weight, double* loss_out, float* dlogits, double* scratch,
+                                        unsigned* counters);
+hipError_t p3d_saliency_loss_launch(int stage, const SaliencyLossArgs& a, hipStream_t s);
+
 // ---- the optimiser step (p3d_set_optimizer), with or without regularisation (p3d_set_regularization) ---------------
 // Regularisation: the flat range is cut at plan time into tiles, each with ONE float32 coefficient c (0 on undecayed variables
 // and on slot padding).  off is relative to the table's base, len >= 1, tiles ascending and contiguous.

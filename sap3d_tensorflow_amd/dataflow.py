@@ -71,3 +71,23 @@ def resize_linear_u8(maps, size, scale=255., device=0):
     check(lib().p3d_resize_linear_u8(device, m.ctypes.data_as(C.POINTER(C.c_float)), m.shape[0], m.shape[1], m.shape[2], float(scale),
                                      H, W, out.ctypes.data_as(C.POINTER(C.c_ubyte))))
     return out[0] if single else out
+
+
+def fixations_to_grid(fix_u8, H, W):
+    """Full-resolution fixation maps on the training grid: uint8 [n, H0, W0] -> uint8 [n, H, W] of 0 / 255, for the losses with an
+    NSS term (P3DSession.upload_fixations).  A grid cell is fixated if any source pixel with byte >= 128 maps to it by
+    (r * H // H0, c * W // W0).  Host numpy.  The reference has no counterpart: it uses fixation maps only at 1080x960, to score
+    (test.py:167-176), and never trains on them."""
+    f = np.asarray(fix_u8)
+    if f.ndim == 2:
+        f = f[None]
+    if f.ndim != 3 or f.dtype != np.uint8 or f.size == 0:
+        raise ValueError("expected [n, H0, W0] uint8 fixation maps")
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError("grid %r x %r" % (H, W))
+    n, H0, W0 = f.shape
+    out = np.zeros((n, H, W), np.uint8)
+    k, r, c = np.nonzero(f >= 128)
+    out[k, r * H // H0, c * W // W0] = 255
+    return out

@@ -412,6 +412,33 @@ def map_loss(logits, pred, target, maps, map_elems, through_sigmoid=True, offset
     return acc.value, dl, per_map, tuple(info)
 
 
+def saliency_loss(logits, pred, target, fixations, maps, map_elems, through_sigmoid=True, offset=0, kld_weight=1.0, cc_weight=1.0,
+                  nss_weight=1.0, sim_weight=0.0, loss=0.0, device=0):
+    """Test hook: the per-map loss P3D_LOSS_SALIENCY as the network launches it (p3d_debug_saliency_loss): map_loss with the
+    uint8 fixation bytes `fixations` (fixated where >= 128; None only with nss_weight 0, when they are not read), placed `offset`
+    bytes into their device buffer, and the four weights.  Returns (loss + the weighted sum, in double; dL/dlogits; per_map
+    [maps, 4] = KL_m, CC_m, NSS_m, SIM_m (NaN where undefined); (launches, blocks per map, path taken: 1 float4 / 2 scalar))."""
+    z, t = _f32(logits).ravel(), _f32(target).ravel()
+    p = _f32(pred).ravel() if pred is not None else z
+    n = int(maps) * int(map_elems)
+    if not (z.size == p.size == t.size == n):
+        raise ValueError("logits, pred and target must hold maps * map_elems elements")
+    f = None
+    if fixations is not None:
+        f = np.ascontiguousarray(fixations).ravel()
+        if f.dtype != np.uint8 or f.size != n:
+            raise ValueError("fixations must be maps * map_elems uint8 bytes")
+    dl = np.empty(n, np.float32)
+    per_map = np.empty((int(maps), 4), np.float64)
+    acc = C.c_double(float(loss))
+    info = (C.c_int * 3)()
+    check(lib().p3d_debug_saliency_loss(device, fptr(z), fptr(p), fptr(t), f.ctypes.data_as(C.POINTER(C.c_ubyte)) if f is not None else None,
+                                        int(maps), int(map_elems), 1 if through_sigmoid else 0, int(offset), float(kld_weight),
+                                        float(cc_weight), float(nss_weight), float(sim_weight), C.byref(acc), fptr(dl),
+                                        per_map.ctypes.data_as(C.POINTER(C.c_double)), info))
+    return acc.value, dl, per_map, tuple(info)
+
+
 def _opt_scaled(kind, p, g, m, v, tiles, t, lr, b1, b2, eps, momentum, use_nesterov, lr_on_device, gscale, offset, device):
     """p3d_debug_opt_scaled on copies already made: any optimiser launch with clipping's scale.  Returns (term, step size)."""
     i64 = C.POINTER(C.c_int64)

@@ -297,13 +297,30 @@ class P3DSession:
         chip, "auto" picks per block by the size of the score matrix."""
         check(lib().p3d_set_attention_mode(self._h, {"auto": 0, "gemm": 1, "flash": 2}[mode]))
 
-    def set_loss(self, name="smooth_l1", kld_weight=None, cc_weight=None):
+    def set_loss(self, name="smooth_l1", kld_weight=None, cc_weight=None, nss_weight=None, sim_weight=None):
         """The training loss of train_step / backward / train_step_device / profile_step: "smooth_l1" (the reference's,
         train.py:159; default), "bce" (sigmoid cross-entropy on the head's logits, summed; no reference counterpart -- on the
         heads without a sigmoid the raw output is taken as the logits), "l1" (L1 sum, the reference's train.py:160), or the
         per-map saliency losses "kld" (KL divergence of each [H, W] map, utils/metrics.py:338-361) and "kld_cc" (KL + (1 - CC),
         utils/metrics.py:227-250), summed over the maps with the weights of _lib.MAP_LOSSES unless kld_weight / cc_weight are
-        given.  The per-map losses read the heads without a sigmoid through one (include/p3d_hip.h P3D_LOSS_KLD_CC)."""
+        given.  The per-map losses read the heads without a sigmoid through one (include/p3d_hip.h P3D_LOSS_KLD_CC).
+        "kld_cc_nss" and "kld_cc_nss_sim" (_lib.SALIENCY_LOSSES; include/p3d_hip.h P3D_LOSS_SALIENCY) add -NSS
+        (utils/metrics.py:200-224) and 1 - SIM (:258-287) per map, with nss_weight / sim_weight as further overrides; while the
+        NSS weight is above 0 every train_step / backward needs the batch's fixation maps (fixations=, or upload_fixations)."""
+        if name in _lib.SALIENCY_LOSSES:
+            given = (kld_weight, cc_weight, nss_weight, sim_weight)
+            w = [d if g is None else g for d, g in zip(_lib.SALIENCY_LOSSES[name], given)]
+            try:
+                w = [float(v) for v in w]
+            except (TypeError, ValueError):
+                raise ValueError("loss weights must be numbers, not %r" % (given,))
+            if not all(np.isfinite(v) and v >= 0 for v in w) or not any(w):
+                raise ValueError("loss weights must be finite, not negative and not all 0: %r" % (w,))
+            check(lib().p3d_set_saliency_weights(self._h, *w))
+            check(lib().p3d_set_loss(self._h, _lib.P3D_LOSS_SALIENCY))
+            return
+        if nss_weight is not None or sim_weight is not None:
+            raise ValueError("loss %r has no NSS or SIM weight (they are for %s)" % (name, sorted(_lib.SALIENCY_LOSSES)))
         if name in _lib.MAP_LOSSES:
             kw, cw = _lib.MAP_LOSSES[name]
             kw = kw if kld_weight is None else kld_weight
@@ -318,9 +335,9 @@ class P3DSession:
             check(lib().p3d_set_loss(self._h, _lib.P3D_LOSS_KLD_CC))
             return
         if name not in _lib.LOSSES:
-            raise ValueError("loss %r: have %s" % (name, sorted(_lib.LOSSES) + sorted(_lib.MAP_LOSSES)))
+            raise ValueError("loss %r: have %s" % (name, sorted(_lib.LOSSES) + sorted(_lib.MAP_LOSSES) + sorted(_lib.SALIENCY_LOSSES)))
         if kld_weight is not None or cc_weight is not None:
-            raise ValueError("loss %r has no weights (they are for %s)" % (name, sorted(_lib.MAP_LOSSES)))
+            raise ValueError("loss %r has no weights (they are for %s)" % (name, sorted(_lib.MAP_LOSSES) + sorted(_lib.SALIENCY_LOSSES)))
         check(lib().p3d_set_loss(self._h, _lib.LOSSES[name]))
 
     def set_regularization(self, terms=("weightdecay",), wd=None, l2=None):
@@ -461,16 +478,40 @@ class P3DSession:
         self.last_maps_ms = dict(device=ms[0], d2h=ms[1])
         return out
 
-    def train_step(self, x, y, dropout=0.5, seed=0):
-        """sess.run([train_op, loss], {x, y, dropout, training: True})  (train.py:217-218) -> loss."""
+    def upload_fixations(self, fixations):
+        """The batch's fixation maps for the losses of _lib.SALIENCY_LOSSES: uint8 [B, T, H, W], fixated where the byte is 128 or
+        more (p3d_upload_fixations; dataflow.fixations_to_grid brings full-resolution maps to the grid)."""
+        f = np.ascontiguousarray(fixations)
+        if f.dtype != np.uint8 or f.shape != self.y_shape:
+            raise ValueError("fixations are %s %s, the graph takes uint8 %s" % (f.dtype, f.shape, self.y_shape))
+        check(lib().p3d_upload_fixations(self._h, f.ctypes.data_as(C.POINTER(C.c_ubyte))))
+
+    def last_loss_terms(self):
+        """The four terms of the last train step or backward under a loss of _lib.SALIENCY_LOSSES, as a trainer logs them:
+        {"kld", "cc", "nss", "sim": the mean over this rank's maps where the term is defined (NaN where none is), "counts":
+        {name: how many maps those were}} (p3d_last_loss_terms)."""
+        sums, counts = (C.c_double * 4)(), (C.c_int64 * 4)()
+        check(lib().p3d_last_loss_terms(self._h, sums, counts))
+        names = ("kld", "cc", "nss", "sim")
+        out = dict((k, sums[i] / counts[i] if counts[i] else float("nan")) for i, k in enumerate(names))
+        out["counts"] = dict((k, int(counts[i])) for i, k in enumerate(names))
+        return out
+
+    def train_step(self, x, y, dropout=0.5, seed=0, fixations=None):
+        """sess.run([train_op, loss], {x, y, dropout, training: True})  (train.py:217-218) -> loss.  fixations: uploaded first
+        (upload_fixations)."""
         x, y = self._x(x), self._y(y)
+        if fixations is not None:
+            self.upload_fixations(fixations)
         loss = C.c_float()
         check(lib().p3d_train_step(self._h, fptr(x), fptr(y), float(dropout), seed, C.byref(loss)))
         return loss.value
 
-    def backward(self, x, y, dropout=0.0, seed=0):
-        """Forward + loss + gradients without the update -> (loss, pred)."""
+    def backward(self, x, y, dropout=0.0, seed=0, fixations=None):
+        """Forward + loss + gradients without the update -> (loss, pred).  fixations: uploaded first (upload_fixations)."""
         x, y = self._x(x), self._y(y)
+        if fixations is not None:
+            self.upload_fixations(fixations)
         loss = C.c_float()
         pred = np.empty(self.pred_shape, np.float32)
         check(lib().p3d_backward(self._h, fptr(x), fptr(y), float(dropout), seed, C.byref(loss), fptr(pred)))
@@ -591,8 +632,10 @@ class P3DSession:
         return a
 
     # ---- device-resident stepping (bench) ------------------------------------------------------
-    def upload(self, x, y):
+    def upload(self, x, y, fixations=None):
         check(lib().p3d_upload_inputs(self._h, fptr(self._x(x)), fptr(self._y(y)) if y is not None else None))
+        if fixations is not None:
+            self.upload_fixations(fixations)
 
     def bucket_audit(self, bucket_floats, dropout=0.0, seed=0, cap=4096):
         """Test hook for the bucketed gradient hand-over of data-parallel training (include/p3d_hip.h,

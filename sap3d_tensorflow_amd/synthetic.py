@@ -19,6 +19,19 @@ def synthetic_target(seed, shape):
     return rng.random(size=shape, dtype=np.float32)
 
 
+def synthetic_fixations(seed, target, share=0.02):
+    """Fixation maps drawn from a target [B,T,H,W]: uint8 of the same shape, 255 where a uniform draw falls under
+    share * y / mean(y of the map) -- about `share` of every map, denser where the target is higher -- and at the map's
+    maximum, so that no map is empty."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    y = np.asarray(target, np.float32)
+    flat = y.reshape(y.shape[0], y.shape[1], -1)
+    mean = np.maximum(flat.mean(axis=2, keepdims=True), np.float32(1e-12))
+    f = rng.random(size=flat.shape, dtype=np.float32) < np.float32(share) * flat / mean
+    np.put_along_axis(f, flat.argmax(axis=2)[..., None], True, axis=2)
+    return (f.reshape(y.shape) * np.uint8(255)).astype(np.uint8)
+
+
 def synthetic_test_set(seed, n, size=(1080, 960), density_size=(270, 480), frames=16, crop=112):
     """An evaluation set for drivers/test.py: x [n,frames,crop,crop,3] float32 by the synthetic_clip law; density uint8
     [n, Hd, Wd] uniform bytes; fixation uint8 [n, H, W]: clip i gets 255 at k ~ U{50..999} uniform pixel draws (with
