@@ -16,7 +16,10 @@ gradients by their global norm, as tf.clip_by_global_norm does, and prints the n
 trainables: the checkpoints carry them, --pretrain restores them when present, and the periodic eval forward and the
 validation pass score the averaged weights (P3DSession.set_ema); `--accum-steps K` sums the gradients of K batches before
 every optimiser update (P3DSession.set_grad_accum): `--saveiter / --validiter / --plotiter` and the printed step then count
-updates, and the printed loss is the sum of the K batches' losses.  The dataset loaders (dataflow.py,
+updates, and the printed loss is the sum of the K batches' losses; `--aug-flip / --aug-reverse / --aug-min-scale /
+--aug-contrast / --aug-brightness` augment every training clip on the device (P3DSession.set_augment): one set of decisions per
+clip for frames, density maps and fixation maps, drawn from the step's seed.  The periodic eval forward and the validation pass
+upload their clips again and score them as given, never the augmented ones.  The dataset loaders (dataflow.py,
 tensorpack, cv2) are out of scope: clips come either from `--data clips.npz` (arrays x [N,16,112,112,3] already normalised like
 dataflow.py:204-208, y [N,16,112,112]; raw uint8 frames go through sap3d_tensorflow_amd.dataflow.mapf_frames first; for the
 losses with an NSS term also fix [N,16,112,112] uint8, fixated where >= 128, or at any other resolution, which
@@ -115,7 +118,22 @@ def get_arguments():
                         "averaged: scale --lr for momentum / sgd).  --saveiter, --validiter, --plotiter and the printed step "
                         "count updates; the printed loss is the sum over the K batches; batches left over at the end of an "
                         "epoch are dropped.  1 = off")
+    # the reference's clips overlap in 15 of 16 frames (--overlap) and its loader only resizes (dataflow.py:187-191)
+    p.add_argument("--aug-flip", type=float, default=0.0, metavar="P", help="[addition] flip a training clip horizontally with probability P")
+    p.add_argument("--aug-reverse", type=float, default=0.0, metavar="P", help="[addition] reverse a training clip in time with probability P")
+    p.add_argument("--aug-min-scale", type=float, default=1.0, metavar="S",
+                   help="[addition] scale jitter: crop a random window of S .. 1 of the frame (0 < S <= 1) and resize it back "
+                        "(cv2.INTER_LINEAR; fixation maps by the grid law); 1 = off")
+    p.add_argument("--aug-contrast", type=float, default=0.0, metavar="C", help="[addition] frames * a with a uniform in 1 +- C (0 <= C < 1)")
+    p.add_argument("--aug-brightness", type=float, default=0.0, metavar="B", help="[addition] frames + b with b uniform in +- B (B >= 0)")
     return p.parse_args()
+
+
+def augment_settings(args):
+    """P3DSession.set_augment's arguments from the --aug-* flags, or None when all five are at their neutral values."""
+    cfg = dict(flip=args.aug_flip, reverse=args.aug_reverse, min_scale=args.aug_min_scale, contrast=args.aug_contrast,
+               brightness=args.aug_brightness)
+    return None if cfg == dict(flip=0.0, reverse=0.0, min_scale=1.0, contrast=0.0, brightness=0.0) else cfg
 
 
 def with_fixations(args):
@@ -269,6 +287,13 @@ def main():
         except P3dError as e:
             sess.close()
             raise SystemExit("--accum-steps %s: %s" % (accum, e))
+    aug = augment_settings(args)
+    if aug is not None:
+        try:
+            sess.set_augment(**aug)
+        except P3dError as e:
+            sess.close()
+            raise SystemExit("--aug-*: %s" % e)
     model_dir = os.path.join("model", args.info)
     os.makedirs(model_dir, exist_ok=True)
     if args.pretrain:
@@ -303,7 +328,7 @@ def main():
                 t = sess.last_loss_terms()
                 clip += ("KLD", "%.9g" % t["kld"], "CC", "%.9g" % t["cc"], "NSS", "%.9g" % t["nss"], "SIM", "%.9g" % t["sim"])
             with scoring(sess, ema):
-                image = sess.forward(xs, dropout=0.0, training=False)               # train.py:225-226
+                image = sess.forward(xs, dropout=0.0, training=False)               # train.py:225-226; uploads xs again: the clip as given
             print("Datetime", datetime.datetime.now().isoformat()[:-7], "Training step:", step,
                   float(np.sum(image[0, -1]) * 255.0), float(np.sum(ys[0][-1]) * 255.0), "Training Loss", loss, *clip)
         if step % args.validiter == 0:

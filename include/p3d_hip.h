@@ -311,6 +311,53 @@ int p3d_ema_swapped(p3d_handle* h);
 int p3d_set_grad_accum(p3d_handle* h, int k);
 int p3d_get_grad_accum(p3d_handle* h, int* k, int* pending);
 
+/* Clip augmentation on the device (an addition: the reference's loader only resizes, dataflow.py:187-191, and its clips overlap in
+ * 15 of 16 frames).  Off by default; off, p3d_train_step issues what it issued before the option existed.  The transform acts on
+ * the three staged inputs of a train step -- x [B,T,H,W,3], y [B,T,H,W] and, when the loss reads them (P3D_LOSS_SALIENCY with
+ * w_nss > 0), the fixation bytes [B,T,H,W] -- with ONE set of decisions per clip applied alike to all three, so the maps stay
+ * registered to the frames.  Per clip, in this order:
+ *   1 crop and resize back: the window [y0, y0 + ch) x [x0, x0 + cw) of every frame of x (each channel on its own) and of y is
+ *     resized to H x W by the float32 cv2.INTER_LINEAR law of p3d_resize_linear (same coordinates, float32 weights, horizontal
+ *     pass then vertical, no fused multiply-add).  A fixation cell (h, w) becomes 255 if some byte >= 128 at (r, c) inside the
+ *     window has (r - y0) * H / ch == h and (c - x0) * W / cw == w (integer division), else 0.  A window equal to the whole frame
+ *     is a copy of the bits, of the fixation bytes as well: no arithmetic, NaN, inf and -0 pass through;
+ *   2 horizontal flip, w -> W - 1 - w;   3 temporal reversal, t -> T - 1 - t;   both on x, y and the fixations;
+ *   4 photometric, x only: x' = fadd(fmul(x, a), b) in float32, each operation rounded on its own; a == 1 and b == 0 is a copy
+ *     of the bits.
+ * 1-3 are one gather; every element is written once.  The decisions are drawn on the host from the step's seed and the clip's
+ * GLOBAL index g = rank * B + b, so a run can be replayed and data-parallel ranks draw differently: draw j = 0..6 is
+ *   z = seed ^ 0xA5A5A5A5A5A5A5A5;  z += 0x9E3779B97F4A7C15 * (1 + 8 g + j)   (mod 2^64);
+ *   z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;  z = (z ^ z >> 27) * 0x94D049BB133111EB;  z ^= z >> 31   (SplitMix64's finaliser);
+ *   u = (z >> 11) * 2^-53 in double, and
+ *   j = 0  flip if u < p_flip;                  j = 1  reverse if u < p_reverse;
+ *   j = 2  s = 1 - u (1 - min_scale); ch = clamp(floor(s H + 0.5), 1, H); cw = clamp(floor(s W + 0.5), 1, W);
+ *   j = 3  y0 = floor(u (H - ch + 1));          j = 4  x0 = floor(u (W - cw + 1));
+ *   j = 5  a = (float)(1 + (2u - 1) contrast);  j = 6  b = (float)((2u - 1) brightness)
+ * in double on the float32 settings.  tests/augment_ref.py replays transform and draws bit for bit.
+ * p3d_set_augment: NULL or the neutral values (0, 0, 1, 0, 0) switch the option off.  Probabilities in [0, 1], 0 < min_scale <= 1,
+ * 0 <= contrast < 1, brightness >= 0, all finite; anything else: -1, nothing changes.  The first switch-on allocates the scratch
+ * (a copy each of x, y and the fixations, and the decision table).  The scratch is private and the staged buffers do not move: a
+ * captured step graph stays valid.
+ * While on, p3d_train_step -- the one entry point that takes host inputs and trains -- augments with its own `seed` after it has
+ * brought x and y from the host and before the forward pass; under p3d_set_grad_accum every micro-step is such a call.  The
+ * fixations are transformed exactly when the loss will read them; p3d_train_step already demands a fresh upload for each call
+ * then, so no buffer is transformed twice.  The launches run ahead of the step, outside its launch list and outside a captured
+ * step.  NEVER augmented: p3d_backward (the parity hook), p3d_forward*, p3d_predict_windows, the evaluation entry points,
+ * p3d_train_step_device, p3d_profile_step, p3d_debug_schedule.
+ * p3d_augment_inputs is the explicit form for the device-resident path: it transforms what p3d_upload_inputs (and
+ * p3d_upload_fixations, when the loss reads them) staged, in place through the scratch, once per call; p3d_augment_inputs and then
+ * p3d_train_step_device is p3d_train_step for the same seed.  Synchronises.
+ * p3d_last_augment: the decisions of the last augmentation, geom [B][6] = flip, reverse, y0, x0, ch, cw and photo [B][2] = a, b
+ * (either may be NULL).  p3d_last_augment_ms: the HIP-event time of its launches (synchronises).  While the option is off, and
+ * before the first augmentation since it was switched on, the three return -1.  p3d_get_augment: the settings (neutral while
+ * off) and whether the option is on; either pointer may be NULL.  Checkpoints store nothing of this. */
+typedef struct p3d_augment { float p_flip, p_reverse, min_scale, contrast, brightness; } p3d_augment;
+int p3d_set_augment(p3d_handle* h, const p3d_augment* cfg);
+int p3d_get_augment(p3d_handle* h, p3d_augment* cfg, int* on);
+int p3d_augment_inputs(p3d_handle* h, uint64_t seed);
+int p3d_last_augment(p3d_handle* h, int32_t* geom, float* photo);
+int p3d_last_augment_ms(p3d_handle* h, double* ms);
+
 /* ---- intermediate tensors (tf fetches of graph tensors; parity/debug taps).  Names:
  *      conv1_custom, conv1_custom_bn_relu, pool1..pool4, block<i>/conv1_bn_relu, block<i>/st,
  *      block<i>/out, deconv3_re, deconv4_conv1, logits, pred. */
@@ -536,6 +583,16 @@ int p3d_debug_ema(int device, float* s, const float* p, int64_t n, int offset, f
  * ranges with guard elements and returns -1 if the launch changed one, or changed the operand its mode must not write (g under
  * STORE and ADD, acc under FINISH). */
 int p3d_debug_grad_accum(int device, int mode, float* acc, float* g, int64_t n, int offset);
+/* Test hook: the augmentation launches of p3d_set_augment, as the step sends them, with EXPLICIT per-clip decisions: geom [B][6] =
+ * flip, reverse, y0, x0, ch, cw and photo [B][2] = a, b, on x [B,T,H,W,3], y [B,T,H,W] and fix [B,T,H,W] bytes (NULL: no fixation
+ * launch, fix_out is not written) of any T, H, W >= 1.  Every device buffer sits `offset` (0..3) elements -- bytes for the
+ * fixations -- past a 16-byte boundary; offsets 1-3 force the element-by-element paths.  Guard elements surround every output:
+ * the hook returns -1 if the launches changed one, or an input.  A window that leaves the frame is refused before any launch.
+ * p3d_debug_augment_draw (host only, no HIP call): the decisions p3d_set_augment's settings *cfg give clip g under `seed` on
+ * an H x W grid; -1 for settings p3d_set_augment refuses. */
+int p3d_debug_augment(int device, const float* x, const float* y, const unsigned char* fix, int B, int T, int H, int W, const int32_t* geom,
+                      const float* photo, int offset, float* x_out, float* y_out, unsigned char* fix_out);
+int p3d_debug_augment_draw(uint64_t seed, uint64_t g, int H, int W, const p3d_augment* cfg, int32_t geom[6], float photo[2]);
 /* Test hook: any of the optimiser launches above with clipping's scale (OptArgs::gscale, read from device memory): kind
  * P3D_OPT_*, ntile = 0 for the plain kernels (tile pointers and term may be NULL) or a tile table as p3d_debug_adam_decay takes
  * it; g becomes g + c*p (not scaled), the update runs on fmul(g', gscale).  t and the betas matter under Adam only, momentum

@@ -35,6 +35,11 @@ class P3dOpTime(C.Structure):
                 ("bytes", C.c_double), ("phase", C.c_int)]
 
 
+class P3dAugment(C.Structure):
+    _fields_ = [("p_flip", C.c_float), ("p_reverse", C.c_float), ("min_scale", C.c_float), ("contrast", C.c_float),
+                ("brightness", C.c_float)]
+
+
 class P3dError(RuntimeError):
     pass
 
@@ -144,6 +149,14 @@ SIGNATURES = {
     "p3d_get_grad_accum": (C.c_int, [C.c_void_p, _ip, _ip]),
     "p3d_debug_grad_accum": (C.c_int, [C.c_int, C.c_int, _fp, _fp, C.c_int64, C.c_int]),
     "p3d_debug_ema": (C.c_int, [C.c_int, _fp, _fp, C.c_int64, C.c_int, C.c_float, C.c_int]),
+    "p3d_set_augment": (C.c_int, [C.c_void_p, C.POINTER(P3dAugment)]),
+    "p3d_get_augment": (C.c_int, [C.c_void_p, C.POINTER(P3dAugment), _ip]),
+    "p3d_augment_inputs": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "p3d_last_augment": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), _fp]),
+    "p3d_last_augment_ms": (C.c_int, [C.c_void_p, _dp]),
+    "p3d_debug_augment": (C.c_int, [C.c_int, _fp, _fp, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), _fp, C.c_int,
+                                    _fp, _fp, _u8p]),
+    "p3d_debug_augment_draw": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.POINTER(P3dAugment), C.POINTER(C.c_int32), _fp]),
     "p3d_debug_stat_parts": (C.c_int, [_i64p, _i64p, _ip, C.c_int, _ip, _ip]),
     "p3d_debug_igemm_groupable": (C.c_int, [_i64p, _i64p, _ip]),
     "p3d_op_conv3d_backprop_input": (C.c_int, [C.c_int, _fp, _fp, _i64p, _ip, _i64p, _fp]),

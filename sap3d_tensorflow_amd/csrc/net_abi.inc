@@ -560,10 +560,71 @@ int p3d_train_step(p3d_handle* h, const float* x, const float* y, float dropout_
     h->refuse_swapped("train step");
     h->check_fixations(true);
     h->fix_fresh = false;
-    h->upload(x, y);
+    if (h->aug_on) h->augment_staged(seed, x, y);      // p3d_set_augment: x and y reach the staged buffers through the transform
+    else h->upload(x, y);
     h->train_step_device(dropout_rate, seed);
     const float l = h->read_loss();
     if (loss) *loss = l;
+    API_END
+}
+
+int p3d_set_augment(p3d_handle* h, const p3d_augment* cfg) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->set_augment(cfg);
+    API_END
+}
+
+int p3d_get_augment(p3d_handle* h, p3d_augment* cfg, int* on) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    if (cfg) *cfg = h->aug_cfg;
+    if (on) *on = h->aug_on ? 1 : 0;
+    API_END
+}
+
+int p3d_augment_inputs(p3d_handle* h, uint64_t seed) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->augment_staged(seed, nullptr, nullptr);
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    API_END
+}
+
+int p3d_last_augment(p3d_handle* h, int32_t* geom, float* photo) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    if (!h->aug_on) throw P3dError("augmentation: the option is off (p3d_set_augment)");
+    if (!h->aug_have) throw P3dError("augmentation: nothing was augmented since the option was switched on");
+    for (size_t b = 0; b < h->aug_tab.size(); ++b) {
+        const P3dAugClip& k = h->aug_tab[b];
+        if (geom) { int32_t* g = geom + 6 * b; g[0] = k.flip; g[1] = k.reverse; g[2] = k.y0; g[3] = k.x0; g[4] = k.ch; g[5] = k.cw; }
+        if (photo) { photo[2 * b] = k.a; photo[2 * b + 1] = k.b; }
+    }
+    API_END
+}
+
+int p3d_last_augment_ms(p3d_handle* h, double* ms) {
+    API_BEGIN
+    if (!h || !ms) throw P3dError("null argument");
+    if (!h->aug_on || !h->aug_have) throw P3dError("augmentation: nothing was augmented (p3d_set_augment)");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    HIPCHECK(hipEventSynchronize(h->ev_aug1));
+    float t = 0.f;
+    HIPCHECK(hipEventElapsedTime(&t, h->ev_aug0, h->ev_aug1));
+    *ms = (double)t;
+    API_END
+}
+
+int p3d_debug_augment_draw(uint64_t seed, uint64_t g, int H, int W, const p3d_augment* cfg, int32_t geom[6], float photo[2]) {
+    API_BEGIN
+    if (!cfg || !geom || !photo) throw P3dError("null argument");
+    if (H < 1 || W < 1 || !p3d_handle::aug_cfg_valid(*cfg)) throw P3dError("augment_draw: bad grid or configuration");
+    const P3dAugClip k = p3d_handle::aug_draw(seed, g, H, W, *cfg);
+    geom[0] = k.flip; geom[1] = k.reverse; geom[2] = k.y0; geom[3] = k.x0; geom[4] = k.ch; geom[5] = k.cw;
+    photo[0] = k.a; photo[1] = k.b;
     API_END
 }
 
@@ -1641,6 +1702,73 @@ int p3d_debug_grad_accum(int device, int mode, float* acc, float* g, int64_t n, 
         if (memcmp(gback.data() + at, g, (size_t)n * 4) != 0) throw P3dError("grad_accum: the launch changed the gradient");
         memcpy(acc, aback.data() + at, (size_t)n * 4);
     }
+    API_END
+}
+
+// The augmentation launches of p3d_set_augment from the step's launch builder, on explicit per-clip decisions.  Every buffer sits
+// `offset` elements (bytes for the fixations) past a 16-byte boundary with guard elements on both sides; a guard or an input that
+// the launches changed is an error.
+int p3d_debug_augment(int device, const float* x, const float* y, const unsigned char* fix, int B, int T, int H, int W, const int32_t* geom,
+                      const float* photo, int offset, float* x_out, float* y_out, unsigned char* fix_out) {
+    API_BEGIN
+    HIPCHECK(hipSetDevice(device));
+    if (!x || !y || !geom || !photo || !x_out || !y_out || (fix && !fix_out)) throw P3dError("null argument");
+    if (B < 1 || T < 1 || H < 1 || W < 1 || offset < 0 || offset > 3) throw P3dError("augment: bad shape or offset");
+    const int64_t ne = (int64_t)B * T * H * W;
+    if (ne * 3 > (int64_t)1 << 31) throw P3dError("augment: the hook takes up to 2^31 floats");
+    std::vector<P3dAugClip> tab((size_t)B);
+    for (int b = 0; b < B; ++b) {
+        const int32_t* g = geom + 6 * b;
+        tab[(size_t)b] = {g[0] != 0, g[1] != 0, g[2], g[3], g[4], g[5], photo[2 * b], photo[2 * b + 1]};
+    }
+    const int64_t at = 4 + offset, bat = 16 + offset;      // floats / bytes ahead of the ranges
+    const uint32_t guard = 0x7fc5a5a5u;                    // a NaN no arithmetic here produces; its bytes guard the fixations
+    auto guarded = [&](int64_t n, const float* host) {     // n floats at `at` of a buffer of guards
+        std::vector<uint32_t> gs((size_t)(n + 12), guard);
+        if (host) memcpy(gs.data() + at, host, (size_t)n * 4);
+        return gs;
+    };
+    const int64_t bwords = (ne + 48 + 3) / 4;
+    std::vector<uint32_t> fsrc((size_t)bwords, guard);
+    if (fix) memcpy(reinterpret_cast<unsigned char*>(fsrc.data()) + bat, fix, (size_t)ne);
+    const std::vector<uint32_t> xs = guarded(3 * ne, x), ys = guarded(ne, y), xo = guarded(3 * ne, nullptr), yo = guarded(ne, nullptr);
+    const std::vector<uint32_t> fdst((size_t)bwords, guard);
+    auto as_f = [](const std::vector<uint32_t>& v) { return reinterpret_cast<const float*>(v.data()); };
+    DevBuf xsb(3 * ne + 12, as_f(xs)), ysb(ne + 12, as_f(ys)), xob(3 * ne + 12, as_f(xo)), yob(ne + 12, as_f(yo));
+    DevBuf fsb(bwords, as_f(fsrc)), fob(bwords, as_f(fdst)), tb((int64_t)B * 8, reinterpret_cast<const float*>(tab.data()));
+    static_assert(sizeof(P3dAugClip) == 32, "the table row is eight words");
+    AugArgs a;
+    a.x = xsb.p + at; a.y = ysb.p + at; a.x_out = xob.p + at; a.y_out = yob.p + at;
+    if (fix) { a.fix = reinterpret_cast<unsigned char*>(fsb.p) + bat; a.fix_out = reinterpret_cast<unsigned char*>(fob.p) + bat; }
+    a.tab = reinterpret_cast<const P3dAugClip*>(tb.p); a.tab_host = tab.data();
+    a.B = B; a.T = T; a.H = H; a.W = W;
+    static const char* const names[3] = {"augment_f32_kernel<3>", "augment_f32_kernel<1>", "augment_fix_kernel"};
+    for (int st = 0; st < p3d_augment_stages(a); ++st) {
+        if (std::string(p3d_augment_desc(st, a).kernel) != names[st]) throw P3dError("augment: launch description names another kernel");
+        HIPCHECK(p3d_augment_launch(st, a, nullptr));
+    }
+    HIPCHECK(hipDeviceSynchronize());
+    auto back = [&](const DevBuf& b, int64_t words) {
+        std::vector<uint32_t> v((size_t)words);
+        HIPCHECK(copy_now(v.data(), b.p, (size_t)words * 4, hipMemcpyDeviceToHost, nullptr));
+        return v;
+    };
+    const std::vector<uint32_t> xs2 = back(xsb, 3 * ne + 12), ys2 = back(ysb, ne + 12), fs2 = back(fsb, bwords);
+    if (xs2 != xs || ys2 != ys || fs2 != fsrc) throw P3dError("augment: the launches changed an input");
+    const std::vector<uint32_t> xo2 = back(xob, 3 * ne + 12), yo2 = back(yob, ne + 12), fo2 = back(fob, bwords);
+    auto guards_kept = [&](const std::vector<uint32_t>& v, int64_t n) {
+        for (int64_t i = 0; i < (int64_t)v.size(); ++i)
+            if ((i < at || i >= at + n) && v[(size_t)i] != guard) return false;
+        return true;
+    };
+    if (!guards_kept(xo2, 3 * ne) || !guards_kept(yo2, ne)) throw P3dError("augment: a launch wrote outside its range");
+    const unsigned char* fb = reinterpret_cast<const unsigned char*>(fo2.data());
+    const unsigned char* gb = reinterpret_cast<const unsigned char*>(fdst.data());
+    for (int64_t i = 0; i < bwords * 4; ++i)
+        if ((i < bat || i >= bat + ne || !fix) && fb[i] != gb[i]) throw P3dError("augment: the fixation launch wrote outside its range");
+    memcpy(x_out, xo2.data() + at, (size_t)ne * 12);
+    memcpy(y_out, yo2.data() + at, (size_t)ne * 4);
+    if (fix) memcpy(fix_out, fb + bat, (size_t)ne);
     API_END
 }
 

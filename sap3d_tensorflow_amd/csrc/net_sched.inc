@@ -422,6 +422,93 @@
         drop_step_graph();        // the captured step is not used while k >= 2
     }
 
+    // ---- clip augmentation of the staged inputs (p3d_set_augment) --------------------------------------
+    // Off by default, and off nothing here runs.  On, p3d_train_step brings x and y from the host into the scratch copies aug_x /
+    // aug_y instead of the staged buffers, copies the fixation bytes there when the loss reads them, and augment.hip's launches
+    // write x_in, d_y and d_fix from the scratch -- on the main stream, ahead of the step and outside its launch list: the step
+    // (eager or captured) names the staged buffers, whose addresses never move, and never the scratch.  p3d_augment_inputs does
+    // the same from the staged buffers themselves (device to device) for the device-resident path.  The decisions are drawn on
+    // the host (aug_draw: SplitMix64 of the step's seed and the clip's global index rank * B + b) and reach the kernels as
+    // d_aug_tab.  The main stream runs every transfer and launch in order, and every entry point here ends synchronised, so the
+    // next call may overwrite aug_tab.
+    bool aug_on = false, aug_have = false;
+    p3d_augment aug_cfg{0.f, 0.f, 1.f, 0.f, 0.f};
+    float* aug_x = nullptr; float* aug_y = nullptr; unsigned char* aug_fix = nullptr;
+    P3dAugClip* d_aug_tab = nullptr;
+    std::vector<P3dAugClip> aug_tab;      // the last augmentation's decisions (p3d_last_augment)
+    hipEvent_t ev_aug0 = nullptr, ev_aug1 = nullptr;      // around the last augmentation's launches (p3d_last_augment_ms)
+    static bool aug_cfg_valid(const p3d_augment& c) {
+        for (float v : {c.p_flip, c.p_reverse, c.min_scale, c.contrast, c.brightness}) if (!std::isfinite(v)) return false;
+        return c.p_flip >= 0.f && c.p_flip <= 1.f && c.p_reverse >= 0.f && c.p_reverse <= 1.f && c.min_scale > 0.f && c.min_scale <= 1.f &&
+               c.contrast >= 0.f && c.contrast < 1.f && c.brightness >= 0.f;
+    }
+    static bool aug_cfg_neutral(const p3d_augment& c) {
+        return c.p_flip == 0.f && c.p_reverse == 0.f && c.min_scale == 1.f && c.contrast == 0.f && c.brightness == 0.f;
+    }
+    // draw j of clip g under `seed` (include/p3d_hip.h): SplitMix64's finaliser on seed ^ A5.. + golden * (1 + 8 g + j), 53 bits
+    static double aug_uniform(uint64_t seed, uint64_t g, int j) {
+        uint64_t z = seed ^ 0xA5A5A5A5A5A5A5A5ull;
+        z += 0x9E3779B97F4A7C15ull * (1ull + 8ull * g + (uint64_t)j);
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        z ^= z >> 31;
+        return (double)(z >> 11) * 0x1.0p-53;
+    }
+    static P3dAugClip aug_draw(uint64_t seed, uint64_t g, int H, int W, const p3d_augment& c) {
+#pragma clang fp contract(off)
+        P3dAugClip k;
+        k.flip = aug_uniform(seed, g, 0) < (double)c.p_flip ? 1 : 0;
+        k.reverse = aug_uniform(seed, g, 1) < (double)c.p_reverse ? 1 : 0;
+        const double s = 1.0 - aug_uniform(seed, g, 2) * (1.0 - (double)c.min_scale);
+        k.ch = (int)std::min<double>(std::max<double>(std::floor(s * H + 0.5), 1.0), (double)H);
+        k.cw = (int)std::min<double>(std::max<double>(std::floor(s * W + 0.5), 1.0), (double)W);
+        k.y0 = std::min((int)std::floor(aug_uniform(seed, g, 3) * (double)(H - k.ch + 1)), H - k.ch);      // (u < 1: the cap never binds)
+        k.x0 = std::min((int)std::floor(aug_uniform(seed, g, 4) * (double)(W - k.cw + 1)), W - k.cw);
+        k.a = (float)(1.0 + (2.0 * aug_uniform(seed, g, 5) - 1.0) * (double)c.contrast);
+        k.b = (float)((2.0 * aug_uniform(seed, g, 6) - 1.0) * (double)c.brightness);
+        return k;
+    }
+    void set_augment(const p3d_augment* c) {
+        const p3d_augment neutral{0.f, 0.f, 1.f, 0.f, 0.f};
+        const p3d_augment want = c ? *c : neutral;
+        if (!aug_cfg_valid(want))
+            throw P3dError("augmentation: probabilities in [0, 1], 0 < min_scale <= 1, 0 <= contrast < 1, brightness >= 0, all finite");
+        if (aug_cfg_neutral(want)) { aug_on = false; aug_have = false; aug_cfg = neutral; return; }
+        if (!aug_x) {      // the first switch-on: private scratch, so no captured step names it
+            aug_x = dalloc<float>(x_in->rows() * 3);
+            aug_y = dalloc<float>(pred->rows());
+            aug_fix = dalloc<unsigned char>(pred->rows());
+            d_aug_tab = dalloc<P3dAugClip>(x_in->N);
+            HIPCHECK(hipEventCreate(&ev_aug0));
+            HIPCHECK(hipEventCreate(&ev_aug1));
+        }
+        if (!aug_on) aug_have = false;
+        aug_on = true; aug_cfg = want;
+    }
+    // hx / hy: the host's x and y (p3d_train_step), or null: the staged buffers are the source (p3d_augment_inputs)
+    void augment_staged(uint64_t seed, const float* hx, const float* hy) {
+        if (!aug_on) throw P3dError("augmentation: the option is off (p3d_set_augment)");
+        const int B = x_in->N, T = x_in->D, H = x_in->H, W = x_in->W;
+        const bool with_fix = saliency_needs_fixations();
+        if (with_fix && !d_fix) throw P3dError("the loss has an NSS term (w_nss > 0) and no fixation maps were uploaded: p3d_upload_fixations");
+        aug_tab.resize((size_t)B);
+        for (int b = 0; b < B; ++b) aug_tab[(size_t)b] = aug_draw(seed, (uint64_t)cfg.rank * (uint64_t)B + (uint64_t)b, H, W, aug_cfg);
+        const size_t nx = (size_t)x_in->rows() * 3 * sizeof(float), ny = (size_t)pred->rows() * sizeof(float);
+        HIPCHECK(hipMemcpyAsync(d_aug_tab, aug_tab.data(), (size_t)B * sizeof(P3dAugClip), hipMemcpyHostToDevice, stream));
+        HIPCHECK(hipMemcpyAsync(aug_x, hx ? hx : x_in->p, nx, hx ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, stream));
+        HIPCHECK(hipMemcpyAsync(aug_y, hy ? hy : d_y, ny, hy ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, stream));
+        if (with_fix) HIPCHECK(hipMemcpyAsync(aug_fix, d_fix, (size_t)pred->rows(), hipMemcpyDeviceToDevice, stream));
+        AugArgs a;
+        a.x = aug_x; a.y = aug_y; a.fix = with_fix ? aug_fix : nullptr;
+        a.x_out = x_in->p; a.y_out = d_y; a.fix_out = with_fix ? d_fix : nullptr;
+        a.tab = d_aug_tab; a.tab_host = aug_tab.data();
+        a.B = B; a.T = T; a.H = H; a.W = W;
+        HIPCHECK(hipEventRecord(ev_aug0, stream));
+        for (int st = 0; st < p3d_augment_stages(a); ++st) HIPCHECK(p3d_augment_launch(st, a, stream));
+        HIPCHECK(hipEventRecord(ev_aug1, stream));
+        aug_have = true;
+    }
+
     // ---- gradient clipping by the global norm (p3d_set_grad_clip) ----------------------------------
     // clip_norm > 0: the step's sum of squares over every trainable element's g' (g + c w under a regularisation term), its
     // norm and scale = clip_norm / max(norm, clip_norm) land in d_clip_res before any optimiser launch, and every optimiser
@@ -739,6 +826,8 @@
         if (ev_side_early) hipEventDestroy(ev_side_early);
         if (ev_comm_early) hipEventDestroy(ev_comm_early);
         if (ev_side_bucket) hipEventDestroy(ev_side_bucket);
+        if (ev_aug0) hipEventDestroy(ev_aug0);
+        if (ev_aug1) hipEventDestroy(ev_aug1);
         // the streams go back to the pool (net.hip, "stream pool"); every path here has synchronised the device or never launched
         if (side_stream) { if (side_pooled) give_stream(cfg.device, 1, side_stream); else hipStreamDestroy(side_stream); }
         for (void* p : allocs) hipFree(p);

@@ -657,6 +657,31 @@ hipError_t p3d_ema_swap(float* a, float* b, long long n, hipStream_t s);
 // scal[3] = the moving average's om under warm-up (ema_om); a null destination is skipped
 hipError_t p3d_set_step_scalars(unsigned long long* seed_dst, float* lr_dst, float* om_dst, unsigned long long seed, float lr_t, float om,
                                 hipStream_t s);
+// ---- clip augmentation of the staged inputs (augment.hip; p3d_set_augment) -----------------------------------------------------
+// One row of decisions per clip, applied alike to x [B,T,H,W,3], y [B,T,H,W] and the fixation bytes [B,T,H,W], out of place:
+//   1 the window [y0, y0 + ch) x [x0, x0 + cw) of every frame resized back to H x W: x (each channel on its own) and y by the
+//     float32 cv2.INTER_LINEAR law of resize_f32_kernel (its coordinates, float32 weights, no contraction); a fixation cell (h, w)
+//     becomes 255 if the window's byte at the one (r, c) with (r - y0) * H / ch == h and (c - x0) * W / cw == w is >= 128, else 0
+//     (ch <= H: at most one row and one column reach a cell).  The whole frame as the window copies the bits, bytes included;
+//   2 flip: w -> W - 1 - w;  3 reverse: t -> T - 1 - t;
+//   4 x only: fadd(fmul(v, a), b), each rounded on its own; a == 1 and b == 0 copies the bits.
+// 1-3 are one gather and every destination element is written once.  A clip whose row is all neutral is copied 16 bytes at a time
+// where source and destination of the clip are 16-byte aligned, else element by element; the gathers store element by element
+// (the bytes four at a time where the clip's destination is 4-byte aligned).  Stages: AUG_X, AUG_Y, and AUG_FIX when fix is given.
+// Refused (hipErrorInvalidValue) before anything is launched: a row of tab_host whose window leaves the frame, B > 65535,
+// H or W > 32768, a clip of more than 2^30 elements, a source that is its destination.
+struct P3dAugClip { int flip, reverse, y0, x0, ch, cw; float a, b; };
+enum { AUG_X = 0, AUG_Y = 1, AUG_FIX = 2 };
+struct AugArgs {
+    const float* x = nullptr; const float* y = nullptr; const unsigned char* fix = nullptr;      // fix null: no AUG_FIX stage
+    float* x_out = nullptr; float* y_out = nullptr; unsigned char* fix_out = nullptr;
+    const P3dAugClip* tab = nullptr;           // [B], device memory
+    const P3dAugClip* tab_host = nullptr;      // the same rows on the host, for the checks above
+    int B = 0, T = 0, H = 0, W = 0;
+};
+inline int p3d_augment_stages(const AugArgs& a) { return a.fix ? 3 : 2; }
+LaunchDesc p3d_augment_desc(int stage, const AugArgs& a);
+hipError_t p3d_augment_launch(int stage, const AugArgs& a, hipStream_t s);
 
 // ---- saliency metrics + frame pre-processing (metrics.hip; utils/metrics.py:25-287, dataflow.py:187-216) ------
 hipError_t p3d_metric_cc(const float* a, const float* b, int n_maps, int n_pix, double* out, hipStream_t s);

@@ -553,6 +553,44 @@ def grad_accum(acc, g, mode, offset=0, device=0):
     return g if m == 2 else acc
 
 
+def augment(x, y, fix, decisions, offset=0, device=0):
+    """Test hook: the augmentation launches of P3DSession.set_augment (p3d_debug_augment) with explicit per-clip decisions
+    [(flip, reverse, y0, x0, ch, cw, a, b), ...] on x [B,T,H,W,3], y [B,T,H,W] float32 and fix [B,T,H,W] uint8 (or None), every
+    device buffer `offset` (0..3) elements past a 16-byte boundary.  Returns (x', y', fix' or None); the inputs are not modified.
+    The hook itself guards both sides of every output and checks that the inputs kept their bits."""
+    x, y = _f32(x), _f32(y)
+    if x.ndim != 5 or x.shape[4] != 3 or y.shape != x.shape[:4]:
+        raise ValueError("x is [B,T,H,W,3] and y [B,T,H,W]")
+    B, T, H, W = y.shape
+    u8 = C.POINTER(C.c_ubyte)
+    f = fo = None
+    if fix is not None:
+        f = np.ascontiguousarray(fix)
+        if f.dtype != np.uint8 or f.shape != y.shape:
+            raise ValueError("fix is uint8 [B,T,H,W]")
+        fo = np.empty_like(f)
+    d = list(decisions)
+    if len(d) != B:
+        raise ValueError("one row of decisions per clip")
+    geom = np.ascontiguousarray([[int(v) for v in r[:6]] for r in d], dtype=np.int32)
+    photo = np.ascontiguousarray([[r[6], r[7]] for r in d], dtype=np.float32)
+    xo, yo = np.empty_like(x), np.empty_like(y)
+    check(lib().p3d_debug_augment(device, fptr(x), fptr(y), f.ctypes.data_as(u8) if f is not None else None, B, T, H, W,
+                                  geom.ctypes.data_as(C.POINTER(C.c_int32)), fptr(photo), int(offset), fptr(xo), fptr(yo),
+                                  fo.ctypes.data_as(u8) if fo is not None else None))
+    return xo, yo, fo
+
+
+def augment_draw(seed, g, H, W, flip=0., reverse=0., min_scale=1., contrast=0., brightness=0.):
+    """Host only: the decisions (flip, reverse, y0, x0, ch, cw, a, b) P3DSession.set_augment's settings give clip g (global index)
+    under `seed` on an H x W grid (p3d_debug_augment_draw); a and b are numpy float32."""
+    from ._lib import P3dAugment
+    cfg = P3dAugment(float(flip), float(reverse), float(min_scale), float(contrast), float(brightness))
+    geom, photo = (C.c_int32 * 6)(), (C.c_float * 2)()
+    check(lib().p3d_debug_augment_draw(int(seed), int(g), int(H), int(W), C.byref(cfg), geom, photo))
+    return (bool(geom[0]), bool(geom[1]), geom[2], geom[3], geom[4], geom[5], np.float32(photo[0]), np.float32(photo[1]))
+
+
 def optimizer_decay(kind, p, g, m, tiles, lr=1e-4, momentum=0.9, use_nesterov=False, lr_on_device=False, update=True, offset=0,
                     device=0, gscale=None):
     """Test hook: adam_decay's launch with Momentum or SGD as the update (p3d_debug_optimizer_decay).  tiles = [(length,

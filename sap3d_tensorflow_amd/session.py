@@ -405,6 +405,51 @@ class P3DSession:
         check(lib().p3d_get_grad_accum(self._h, C.byref(k), C.byref(pending)))
         return k.value, pending.value
 
+    # ---- clip augmentation on the device (p3d_set_augment) ----------------------------------------------
+    def set_augment(self, flip=0., reverse=0., min_scale=1., contrast=0., brightness=0.):
+        """Augment every clip of train_step on the device (an addition: the reference's loader only resizes).  Per clip, one set
+        of decisions for x, y and -- when the loss reads them -- the fixation maps: a random window of min_scale .. 1 of the
+        frame resized back to H x W (cv2.INTER_LINEAR in float32; fixations by fixations_to_grid's law), a horizontal flip with
+        probability `flip`, a temporal reversal with probability `reverse`, and on x alone x * a + b with a in 1 +- contrast and
+        b in +- brightness.  The decisions follow from train_step's seed and the clip's global index (include/p3d_hip.h), so a
+        run can be replayed; last_augment() returns them.  set_augment(None), or the defaults, switch the option off.  backward,
+        forward, predict_windows, evaluate, train_step_device and profile_step never augment: forward(x) after a train_step(x, ..)
+        scores the clip as given, not the augmented one; augment_inputs(seed) is the explicit form for uploaded inputs."""
+        if flip is None:
+            check(lib().p3d_set_augment(self._h, None))
+            return
+        cfg = _lib.P3dAugment(float(flip), float(reverse), float(min_scale), float(contrast), float(brightness))
+        check(lib().p3d_set_augment(self._h, C.byref(cfg)))
+
+    @property
+    def augment(self):
+        """None while the option is off, else dict(flip, reverse, min_scale, contrast, brightness) as float32 holds them."""
+        cfg, on = _lib.P3dAugment(), C.c_int(0)
+        check(lib().p3d_get_augment(self._h, C.byref(cfg), C.byref(on)))
+        if not on.value:
+            return None
+        return dict(flip=cfg.p_flip, reverse=cfg.p_reverse, min_scale=cfg.min_scale, contrast=cfg.contrast, brightness=cfg.brightness)
+
+    def last_augment(self):
+        """The decisions of the last augmented train_step / augment_inputs, one dict per clip of this rank: flip, reverse (bool),
+        y0, x0, ch, cw (the window), a, b (x * a + b).  Raises while the option is off or before the first augmentation."""
+        B = self.x_shape[0]
+        geom, photo = np.empty((B, 6), np.int32), np.empty((B, 2), np.float32)
+        check(lib().p3d_last_augment(self._h, geom.ctypes.data_as(C.POINTER(C.c_int32)), fptr(photo)))
+        return [dict(flip=bool(g[0]), reverse=bool(g[1]), y0=int(g[2]), x0=int(g[3]), ch=int(g[4]), cw=int(g[5]), a=p[0], b=p[1])
+                for g, p in zip(geom, photo)]
+
+    def last_augment_ms(self):
+        """HIP-event time of the last augmentation's launches, in milliseconds."""
+        ms = C.c_double()
+        check(lib().p3d_last_augment_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def augment_inputs(self, seed=0):
+        """Transform the uploaded inputs (upload) in place with the decisions of `seed`, once: augment_inputs(seed) followed by
+        train_step_device(.., seed) is train_step(x, y, .., seed)."""
+        check(lib().p3d_augment_inputs(self._h, int(seed)))
+
     # ---- moving average of the weights (p3d_set_ema) ---------------------------------------------------
     def set_ema(self, decay, warmup=False):
         """Keep an exponential moving average of every trainable variable, as tf.train.ExponentialMovingAverage(decay).apply(
