@@ -16,7 +16,8 @@ Output (`--write`):
             resized and quantised on the GPU (P3DSession.pred_maps_u8).  A video whose directory exists is skipped
             (gen_pred.py:83-86).  PNG is lossless: its pixels are exactly those bytes.  JPEG is written by PIL at
             quality 95 (cv2's default); the files are not byte-identical to cv2's encoder.  Files are encoded on `--writers`
-            threads while the GPU runs the next batch."""
+            threads while the GPU runs the next batch.  --blur-sigma / --blur-radius / --normalize (an addition) smooth and
+            normalise every map at `--size` on the GPU before it is quantised (P3DSession.set_postprocess)."""
 import argparse
 import glob
 import os
@@ -137,11 +138,19 @@ def parse_args(argv=None):
                         "(gen_pred.py:154-168), resized and quantised on the GPU.  PNG pixels are exactly the bytes cv2.imwrite "
                         "would encode; JPEG is PIL's encoder at quality 95, not byte-identical to cv2's")
     p.add_argument("--size", type=int, nargs=2, default=(1080, 960), metavar=("H", "W"), help="image size for png / jpg")
+    p.add_argument("--blur-sigma", type=float, default=0., metavar="S", help="[addition] png / jpg: smooth every map at --size with a "
+                   "Gaussian of S pixels before it is quantised (P3DSession.set_postprocess; the resize is then the float32 one)")
+    p.add_argument("--blur-radius", type=int, default=0, metavar="R", help="[addition] the Gaussian's radius in pixels, at most 255; "
+                   "0: cv2's rule, (int(rint(8 S + 1)) | 1) // 2")
+    p.add_argument("--normalize", choices=("none", "max", "range"), default="none",
+                   help="[addition] png / jpg: scale every (smoothed) map by its maximum, or to its range, before it is quantised")
     p.add_argument("--writers", type=int, default=4, help="encoder threads for png / jpg (at most 16)")
     p.add_argument("--time", action="store_true", help="print per-video wall times (png / jpg: also the device stage and the host encode)")
     args = p.parse_args(argv)
     if not 1 <= args.writers <= 16:
         p.error("--writers must be in 1..16")
+    if args.write == "npy" and (args.blur_sigma != 0. or args.blur_radius != 0 or args.normalize != "none"):
+        p.error("--blur-sigma / --blur-radius / --normalize shape the images: they need --write png or jpg (npy stays the raw 112x112 maps)")
     return args
 
 
@@ -178,6 +187,7 @@ def main(argv=None):
     sess = P3DSession(args.structure, batch=args.batch, device=int(args.gpu), seed=0)
     if args.model:
         sess.restore(args.model, ema_as_weights=args.ema)
+    sess.set_postprocess(args.blur_sigma, args.blur_radius, args.normalize)
     run(sess, args)
     sess.close()
 

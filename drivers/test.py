@@ -72,11 +72,16 @@ def metric_line(fmt, index, cols):
 
 
 def shuffled_auc(sess, fixation, lo, m, rng, device=0):
-    """Column 6 for the clips of the batch at `lo`: shuffled AUC of the clean prediction (resized to the fixation size) against
-    the union of the fixations of m other clips of the set, drawn from `rng`."""
+    """Column 6 for the clips of the batch at `lo`: shuffled AUC of the clean prediction (resized to the fixation size, and
+    through the session's postprocess stage when that is on) against the union of the fixations of m other clips of the set,
+    drawn from `rng`."""
     from sap3d_tensorflow_amd import dataflow, metrics
     pred = sess.activation("pred")[:, -1, :, :, 0]
-    full = dataflow.resize_linear(pred, fixation.shape[1:], device=device)
+    post = sess.postprocess
+    if post:
+        full = dataflow.postprocess_maps(pred, fixation.shape[1:], device=device, **post)
+    else:
+        full = dataflow.resize_linear(pred, fixation.shape[1:], device=device)
     out = []
     for k in range(len(pred)):
         i = lo + k
@@ -102,6 +107,12 @@ def main(argv=None):
     p.add_argument("--seed", type=int, default=0, help="seeds numpy's global stream (the metrics' draws) and the synthetic set")
     p.add_argument("--sauc", type=int, default=0, metavar="M", help="add shuffled AUC against the fixations of M other clips")
     p.add_argument("--time", action="store_true", help="print the stage times of every batch")
+    p.add_argument("--blur-sigma", type=float, default=0., metavar="S", help="[addition] smooth every resized prediction with a "
+                   "Gaussian of S pixels before it is scored (P3DSession.set_postprocess)")
+    p.add_argument("--blur-radius", type=int, default=0, metavar="R", help="[addition] the Gaussian's radius in pixels, at most 255; "
+                   "0: cv2's rule, (int(rint(8 S + 1)) | 1) // 2")
+    p.add_argument("--normalize", choices=("none", "max", "range"), default="none",
+                   help="[addition] scale every (smoothed) map by its maximum, or to its range, before it is scored")
     # the reduced graph of the tests (the reference's is base 64, blocks 3/8/36)
     p.add_argument("--base", type=int, default=64, help=argparse.SUPPRESS)
     p.add_argument("--blocks", type=str, default="3,8,36", help=argparse.SUPPRESS)
@@ -120,6 +131,7 @@ def main(argv=None):
     if args.model:
         print("loading checkpoint %s" % sess.restore(args.model, ema_as_weights=args.ema))
     print("Now using model %s with structure %s" % (args.model or "(initialised)", structure))
+    sess.set_postprocess(args.blur_sigma, args.blur_radius, args.normalize)
     np.random.seed(args.seed)
     sauc_rng = np.random.RandomState(args.seed) if args.sauc else None
     cols = [[] for _ in range(6 if args.sauc else 5)]
@@ -137,7 +149,9 @@ def main(argv=None):
             t = sess.last_eval_ms
             print("  batch %d: forward %.3f ms  host draws %.3f ms  host->device %.3f ms  device metrics %.3f ms"
                   % (index, t["forward"], t["draws"], t["h2d"], t["device"]))
-    print(metric_line(ALL_LINE, index, nan_dropped_means(cols)))
+    post = sess.postprocess
+    print(metric_line(ALL_LINE, index, nan_dropped_means(cols)) +
+          ("   postprocess: sigma %g radius %d normalize %s" % (post["sigma"], post["radius"], post["norm"]) if post else ""))
     print("Testing Finished!")
     sess.close()
     return cols

@@ -749,6 +749,59 @@ int p3d_resize_linear_u8(int device, const float* src, int n, int h, int w, floa
  * from the stream pool.  stage_ms[2] (or NULL): device time of the resize / quantise stage and of the device->host copy. */
 int p3d_pred_maps_u8(p3d_handle* h, const int* first_frame, float scale, int H, int W, unsigned char* out, double* stage_ms);
 
+/* ---- Gaussian smoothing and per-map normalisation of predictions at output resolution (an ADDITION: gen_pred.py writes map * 255
+ * and test.py scores the bare resize; the reference's ground-truth densities are smoothed this way, gen_video.py:15, and
+ * utils/metric_utils.py normalises by 'range').  OFF by default; off, every entry point issues what it issued before and returns
+ * the same bits.  PARITY UNPINNED: cv2 is not available to the tests, so this text is the contract and tests/postprocess_ref.py
+ * replays it in numpy bit for bit.  One map of H x W float32 values v goes through:
+ *   RADIUS  radius > 0 is taken as given.  radius == 0 and sigma > 0: cv2's rule for float images,
+ *           ksize = (int)rint(8.0 * sigma + 1.0) | 1, r = ksize / 2, in double on the float32 sigma (sigma 32 -> r 128, 1 -> 4).
+ *           sigma == 0: no blur (r = 0).  r <= P3D_BLUR_MAX_RADIUS.
+ *   TAPS    e_k = exp(-(k - r)^2 / (2 sigma^2)) in double, k = 0 .. 2r;  S = sum of e_k in ascending k, in double;
+ *           w_k = (float)(e_k / S).  p3d_blur_taps returns these 2r + 1 floats and r (host only; cap = room in taps, in floats).
+ *   PASS    along an axis of length n, in float32, no fused multiply-add, every operation rounded on its own:
+ *           acc = fmul(w_r, s[i]);  for d = 1 .. r:  acc = fadd(acc, fmul(w_{r+d}, fadd(s[rho(i - d)], s[rho(i + d)])));
+ *           rho is reflect-101: rho(j) = -j for j < 0, 2 (n - 1) - j for j > n - 1.  Needs r <= n - 1.
+ *   BLUR    the pass along x over the whole map into a temporary, then the pass along y over the temporary.  fadd commutes, so
+ *           the blur commutes bit for bit with a horizontal or a vertical flip.
+ *   NORM    after the blur, with mn and mx the float32 minimum and maximum of the map:
+ *           P3D_NORM_MAX    v' = v / mx when mx > 0, else the map is left as it is;
+ *           P3D_NORM_RANGE  v' = (v - mn) / (mx - mn) when mx > mn, else every element becomes 0;
+ *           float32 subtraction and division, correctly rounded.
+ *   BYTE    where bytes are asked for: saturate_cast<uchar>((double)fmul(v', scale)), p3d_resize_linear_u8's byte law.
+ * Maps that hold NaN or inf propagate them; their results (and the sign of a zero minimum) are NOT pinned.
+ * Refused (-1, p3d_last_error set, nothing changed): sigma negative or not finite; radius < 0 or > P3D_BLUR_MAX_RADIUS (also the
+ * radius that follows from sigma); radius > 0 with sigma == 0; an unknown norm; and, when the stage runs, r > min(H, W) - 1.
+ *
+ * p3d_set_postprocess: the handle's setting; NULL or {0, 0, P3D_NORM_NONE} switch it off.  Nothing is allocated until the stage
+ * first runs (scratch from the stream pool); the train step, a captured step graph and its schedule never see it.  While on:
+ *   p3d_eval_last_frames  the stage runs on the float32 resize of the prediction, in place, before the jitter is added and before
+ *                         every metric: all five metrics score the smoothed, normalised map;
+ *   p3d_pred_maps_u8      every emitted map is resized to H x W by p3d_resize_linear's FLOAT32 law (not the double-precision
+ *                         resize of the option-off path: the chain is the one evaluation uses, and smoothing belongs at output
+ *                         resolution), then BLUR, NORM, BYTE.  Maps are processed 16 at a time: scratch is 2 x 16 x H x W floats
+ *                         (at 1080x960 a first window's 16 maps of 4 MB each, plus the temporary: 133 MB) beside the bytes.
+ * p3d_get_postprocess: the setting (zeros while off) and whether it is on; either pointer may be NULL.
+ * p3d_gaussian_blur: BLUR alone on host maps src [n][H][W] -> dst [n][H][W].
+ * p3d_postprocess_maps: the same launch sequence (resize, BLUR, NORM, BYTE) on host maps [n][h][w][elem_stride], channel 0;
+ * out_f32 [n][H][W] and out_u8 [n][H][W] may each be NULL (scale is read for out_u8 only); cfg NULL or neutral: the float32 resize
+ * alone.  Its outputs sit between guard elements on the device, out_u8 at an odd offset; a guard that changed is an error.
+ * p3d_debug_eval_maps_post: p3d_debug_eval_maps with the stage of cfg (NULL: off) between the resize and the metrics. */
+enum { P3D_NORM_NONE = 0, P3D_NORM_MAX = 1, P3D_NORM_RANGE = 2 };
+#define P3D_BLUR_MAX_RADIUS 255
+typedef struct p3d_postprocess { float sigma; int radius; int norm; } p3d_postprocess;
+int p3d_set_postprocess(p3d_handle* h, const p3d_postprocess* cfg);
+int p3d_get_postprocess(p3d_handle* h, p3d_postprocess* cfg, int* on);
+int p3d_blur_taps(float sigma, int radius, float* taps, int cap, int* r);
+int p3d_gaussian_blur(int device, const float* src, int n, int H, int W, float sigma, int radius, float* dst);
+int p3d_postprocess_maps(int device, const float* maps, int n, int h, int w, int elem_stride, int H, int W,
+                         const p3d_postprocess* cfg, float scale, float* out_f32, unsigned char* out_u8);
+int p3d_debug_eval_maps_post(int device, const float* maps, int n_maps, int h, int w, int elem_stride, const unsigned char* density,
+                             int Hd, int Wd, const unsigned char* fixation, int H, int W, const double* jitter, const int* borji_idx,
+                             const int* n_fix, int n_rep, double step_size, double* out, const p3d_postprocess* cfg);
+/* Host only (no HIP call): the vertical pass's strip for radius r -- columns, output rows and LDS bytes of one block. */
+int p3d_debug_blur_strip(int r, int* cols, int* rows, int* lds_bytes);
+
 /* CRC-32C of a host buffer (host-side helper of the TensorFlow checkpoint reader / writer, sap3d_tensorflow_amd/tf_checkpoint.py:
  * the bundle format of train.py:180-185,266-267 checksums every tensor); crc = running value, 0 to start. */
 uint32_t p3d_crc32c(const void* data, size_t n, uint32_t crc);

@@ -40,6 +40,15 @@ class P3dAugment(C.Structure):
                 ("brightness", C.c_float)]
 
 
+class P3dPostprocess(C.Structure):
+    _fields_ = [("sigma", C.c_float), ("radius", C.c_int), ("norm", C.c_int)]
+
+
+# p3d_set_postprocess normalisations (include/p3d_hip.h P3D_NORM_*)
+NORMS = {"none": 0, "max": 1, "range": 2}
+P3D_BLUR_MAX_RADIUS = 255
+
+
 class P3dError(RuntimeError):
     pass
 
@@ -194,6 +203,16 @@ SIGNATURES = {
                                       C.POINTER(C.c_ubyte), C.c_int, C.c_int, _dp, _ip, _ip, C.c_int, C.c_double, _dp]),
     "p3d_resize_linear_u8": (C.c_int, [C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_ubyte)]),
     "p3d_pred_maps_u8": (C.c_int, [C.c_void_p, _ip, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_ubyte), _dp]),
+    "p3d_set_postprocess": (C.c_int, [C.c_void_p, C.POINTER(P3dPostprocess)]),
+    "p3d_get_postprocess": (C.c_int, [C.c_void_p, C.POINTER(P3dPostprocess), _ip]),
+    "p3d_blur_taps": (C.c_int, [C.c_float, C.c_int, _fp, C.c_int, _ip]),
+    "p3d_debug_blur_strip": (C.c_int, [C.c_int, _ip, _ip, _ip]),
+    "p3d_gaussian_blur": (C.c_int, [C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _fp]),
+    "p3d_postprocess_maps": (C.c_int, [C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(P3dPostprocess),
+                                       C.c_float, _fp, _u8p]),
+    "p3d_debug_eval_maps_post": (C.c_int, [C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ubyte), C.c_int, C.c_int,
+                                           C.POINTER(C.c_ubyte), C.c_int, C.c_int, _dp, _ip, _ip, C.c_int, C.c_double, _dp,
+                                           C.POINTER(P3dPostprocess)]),
     "p3d_crc32c": (C.c_uint32, [C.c_void_p, C.c_size_t, C.c_uint32]),
     "p3d_shutdown": (C.c_int, []),
 }

@@ -121,11 +121,7 @@ __global__ __launch_bounds__(TPB) void resize_f32_kernel(const float* src, long 
 // saturate_cast<uchar>(double) as cv2.imwrite's conversion to CV_8U does it on x86: cvRound (round half to even) to int32,
 // then clamp to [0, 255].  NaN and a rounded value outside int32 (cvtsd2si's integer-indefinite INT_MIN) give 0.  Spelled
 // out rather than left to the hardware's saturating convert, whose out-of-range results differ from x86's.
-__device__ __forceinline__ unsigned sat_u8(double v) {
-    const double r = rint(v);                                  // NaN stays NaN and fails both range tests below
-    if (!(r >= -2147483648.0 && r <= 2147483647.0)) return 0u;
-    return r <= 0.0 ? 0u : r >= 255.0 ? 255u : (unsigned)r;
-}
+__device__ __forceinline__ unsigned sat_u8(double v) { return p3d_sat_u8(v); }      // p3d_kernels.h: shared with postprocess.hip
 // one pixel: the source is float32(p * scale) widened exactly to double (numpy's float32 product); cv2's CV_64F INTER_LINEAR
 // has float32 weights widened to double and double sums, horizontal pass then vertical.  Same size: cv2.resize copies.
 __device__ __forceinline__ unsigned resize_u8_px(const float* f0, int elem_stride, int h, int w, int y, int x, double sy, double sx,

@@ -2395,6 +2395,65 @@ void check_indices(const int* idx, size_t n, long long n_pix, const char* what) 
     for (size_t i = 0; i < n; ++i)
         if (idx[i] < 0 || idx[i] >= n_pix) throw P3dError(std::string(what) + ": random index out of range");
 }
+// ---- the smoothing / normalisation stage of p3d_set_postprocess (postprocess.hip), one launch sequence for every caller ------
+// What a setting asks for: the effective radius, its weights, the normalisation.  Built on the host, no HIP call.
+struct PostPlan {
+    bool on = false; int r = 0, norm = P3D_NORM_NONE; std::vector<float> taps;
+    PostPlan() {}
+    explicit PostPlan(const p3d_postprocess* cfg) {
+        if (!cfg) return;
+        r = p3d_handle::post_radius(*cfg);
+        norm = cfg->norm;
+        on = !p3d_handle::post_neutral(*cfg);
+        if (r > 0) taps = p3d_handle::post_taps(cfg->sigma, r);
+    }
+    void fits(int H, int W) const {
+        if (r > std::min(H, W) - 1)
+            throw P3dError("postprocess: radius " + std::to_string(r) + " exceeds min(H, W) - 1 = " + std::to_string(std::min(H, W) - 1));
+    }
+};
+// Device scratch of the stage for `chunk` maps of N pixels at a time; own_maps: the maps live here too (no float32 output)
+struct PostScratch { float* maps = nullptr; float* tmp = nullptr; float* taps = nullptr; float* part = nullptr; float* mnmx = nullptr; };
+void post_carve(Carve& c, PostScratch& ps, const PostPlan& pl, int chunk, long long N, bool own_maps) {
+    ps.maps = own_maps ? c.take<float>((size_t)chunk * N) : nullptr;
+    ps.tmp = pl.r > 0 ? c.take<float>((size_t)chunk * N) : nullptr;
+    ps.taps = pl.r > 0 ? c.take<float>((size_t)2 * pl.r + 1) : nullptr;
+    ps.part = pl.norm != P3D_NORM_NONE ? c.take<float>((size_t)chunk * p3d_post_blocks(N) * 2) : nullptr;
+    ps.mnmx = pl.norm != P3D_NORM_NONE ? c.take<float>((size_t)chunk * 2) : nullptr;
+}
+// n maps of one source: map m's pixel (y, x) at p[m * map_stride + (y * w + x) * elem_stride] (device memory)
+struct PostRun { const float* p; long long map_stride; int elem_stride, n; };
+// resize -> blur -> normalise (-> quantise) of `total` maps on stream s, at most `chunk` maps per pass through the stages.
+// runs: the sources, resized (float32) to H x W -- their n add up to total; empty: f32 already holds the maps.  f32 [total][H][W]
+// (device) receives the float32 result, or null: the maps pass through ps.maps.  u8 (device, 4-byte aligned) or null: map k's
+// bytes at u8_off + k * H * W.  counters: `chunk` zeroed arrival counters.  Queues only (after one synchronising upload of the taps).
+void post_sequence(hipStream_t s, const std::vector<PostRun>& runs, int total, int h, int w, int H, int W, const PostPlan& pl,
+                   const PostScratch& ps, unsigned* counters, int chunk, float* f32, unsigned char* u8, long long u8_off, float scale) {
+    pl.fits(H, W);
+    const long long N = (long long)H * W;
+    if (pl.r > 0) HIPCHECK(copy_now(ps.taps, pl.taps.data(), pl.taps.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    size_t ri = 0;
+    int rdone = 0;
+    for (int done = 0; done < total; done += chunk) {
+        const int cn = std::min(chunk, total - done);
+        float* maps = f32 ? f32 + (size_t)done * N : ps.maps;
+        for (int filled = 0; filled < cn && !runs.empty();) {
+            while (runs[ri].n == rdone) { ++ri; rdone = 0; }
+            const PostRun& R = runs[ri];
+            const int take = std::min(R.n - rdone, cn - filled);
+            PostArgs a;
+            a.src = R.p + (size_t)rdone * R.map_stride; a.map_stride = R.map_stride; a.elem_stride = R.elem_stride; a.h = h; a.w = w;
+            a.n = take; a.H = H; a.W = W; a.maps = maps + (size_t)filled * N;
+            HIPCHECK(p3d_post_launch(POST_RESIZE, a, s));
+            filled += take; rdone += take;
+        }
+        PostArgs a;
+        a.n = cn; a.H = H; a.W = W; a.maps = maps; a.tmp = ps.tmp; a.taps = ps.taps; a.r = pl.r; a.norm = pl.norm;
+        a.part = ps.part; a.mnmx = ps.mnmx; a.counter = counters; a.nblk = p3d_post_blocks(N);
+        a.u8 = u8; a.u8_off = u8_off + (long long)done * N; a.scale = scale;
+        for (int st = POST_BLUR_H; st < POST_STAGES; ++st) HIPCHECK(p3d_post_launch(st, a, s));
+    }
+}
 // Source maps of one evaluation: map m's pixel (y, x) at p[m * map_stride + (y * w + x) * elem_stride] (device memory)
 struct EvalSource { const float* p; long long map_stride; int elem_stride, n_maps, h, w; };
 // The device pass of test.py's per-batch body on stream s, with the scratch of s: everything of p3d_eval_last_frames that does
@@ -2404,11 +2463,13 @@ struct EvalSource { const float* p; long long map_stride; int elem_stride, n_map
 // the source maps readable; it runs after the uploads, inside the metric stage's time.
 void eval_maps(hipStream_t s, const EvalSource& src, const std::function<void(hipStream_t)>& prepare, const unsigned char* density, int Hd, int Wd, const unsigned char* fixation, int H,
                int W, const double* jitter, const int* borji_idx, const int* n_fix, int n_rep, double step_size, double* out,
-               double* stage_ms) {
+               double* stage_ms, const p3d_postprocess* post = nullptr) {
+    const PostPlan plan(post);                 // p3d_set_postprocess: between the resize and the metrics, in place on P
     if (!src.p || !density || !fixation || !n_fix || !out) throw P3dError("null argument");
     if (Hd < 1 || Wd < 1 || H < 1 || W < 1) throw P3dError("eval: empty map");
     if ((long long)H * W > INT32_MAX / 2) throw P3dError("eval: map too large");
     if (n_rep < 1 || !(step_size > 0.0)) throw P3dError("eval: AUC_Borji needs n_rep >= 1 and a positive step");
+    if (plan.on) plan.fits(H, W);
     const int B = src.n_maps;
     const long long N = (long long)H * W;
     size_t n_idx = 0;
@@ -2423,6 +2484,8 @@ void eval_maps(hipStream_t s, const EvalSource& src, const std::function<void(hi
     unsigned char *dens = nullptr, *fixd = nullptr;
     double *jit = nullptr, *dout = nullptr;
     int* idx = nullptr;
+    PostScratch post_scratch;
+    const int post_chunk = std::min(B, P3D_POST_CHUNK);
     auto layout = [&](Carve& c) {
         P = c.take<float>((size_t)B * N);
         D = c.take<float>((size_t)B * N);
@@ -2432,6 +2495,7 @@ void eval_maps(hipStream_t s, const EvalSource& src, const std::function<void(hi
         idx = c.take<int>(n_idx);
         dout = c.take<double>((size_t)B * 5);
         carve_full(c, a, r, meta);
+        if (plan.on) post_carve(c, post_scratch, plan, post_chunk, N, false);
     };
     Carve c;
     layout(c);                                 // sizes the scratch
@@ -2453,7 +2517,11 @@ void eval_maps(hipStream_t s, const EvalSource& src, const std::function<void(hi
     HIPCHECK(copy_now((void*)a.meta, meta.data(), meta.size() * sizeof(int), hipMemcpyHostToDevice, s));
     if (stage_ms) HIPCHECK(hipEventRecord(ev[1], s));
     if (prepare) prepare(s);
-    HIPCHECK(p3d_resize_f32(src.p, src.map_stride, src.elem_stride, B, src.h, src.w, P, H, W, s));
+    if (plan.on)
+        post_sequence(s, {{src.p, src.map_stride, src.elem_stride, B}}, B, src.h, src.w, H, W, plan, post_scratch, counters, post_chunk, P,
+                      nullptr, 0, 0.f);
+    else
+        HIPCHECK(p3d_resize_f32(src.p, src.map_stride, src.elem_stride, B, src.h, src.w, P, H, W, s));
     HIPCHECK(p3d_mapf_density(dens, B, Hd, Wd, D, H, W, s));                  // test.py's density: uint8 resize (dataflow.py:236-238)
     HIPCHECK(p3d_full_moments(a, s));
     HIPCHECK(p3d_full_rank(a, s));
@@ -2541,7 +2609,8 @@ int p3d_eval_last_frames(p3d_handle* h, const unsigned char* density, int Hd, in
     std::function<void(hipStream_t)> prepare;
     if (pr->materialize && h->last_forward_fused) prepare = pr->materialize;
     eval_maps(h->stream, {pr->p + (size_t)(T - 1) * hw * pr->ld, (long long)T * hw * pr->ld, pr->ld, pr->N, pr->H, pr->W}, prepare,
-              density, Hd, Wd, fixation, H, W, jitter, borji_idx, n_fix, n_rep, step_size, out, stage_ms);
+              density, Hd, Wd, fixation, H, W, jitter, borji_idx, n_fix, n_rep, step_size, out, stage_ms,
+              h->post_on ? &h->post_cfg : nullptr);
     API_END
 }
 
@@ -2555,6 +2624,19 @@ int p3d_debug_eval_maps(int device, const float* maps, int n_maps, int h, int w,
     DevArr<float> src((size_t)n_maps * per_map, maps);
     eval_maps(nullptr, {src.p, per_map, elem_stride, n_maps, h, w}, nullptr, density, Hd, Wd, fixation, H, W, jitter, borji_idx, n_fix, n_rep,
               step_size, out, nullptr);
+    API_END
+}
+
+int p3d_debug_eval_maps_post(int device, const float* maps, int n_maps, int h, int w, int elem_stride, const unsigned char* density,
+                             int Hd, int Wd, const unsigned char* fixation, int H, int W, const double* jitter, const int* borji_idx,
+                             const int* n_fix, int n_rep, double step_size, double* out, const p3d_postprocess* cfg) {
+    API_BEGIN
+    metric_args(device, maps, maps, n_maps, 1, out);
+    if (h < 1 || w < 1 || elem_stride < 1) throw P3dError("eval: empty map");
+    const long long per_map = (long long)h * w * elem_stride;
+    DevArr<float> src((size_t)n_maps * per_map, maps);
+    eval_maps(nullptr, {src.p, per_map, elem_stride, n_maps, h, w}, nullptr, density, Hd, Wd, fixation, H, W, jitter, borji_idx, n_fix, n_rep,
+              step_size, out, nullptr, cfg);
     API_END
 }
 
@@ -2592,8 +2674,19 @@ int p3d_pred_maps_u8(p3d_handle* h, const int* first_frame, float scale, int H, 
     const hipStream_t s = h->stream;
     float* slab = nullptr;
     unsigned* counters = nullptr;
-    HIPCHECK(p3d_stream_scratch(s, (size_t)(bytes + 3) / 4, 0, &slab, &counters));
-    unsigned char* d = (unsigned char*)slab;
+    // p3d_set_postprocess: the float32 chain resize -> blur -> normalise -> bytes, P3D_POST_CHUNK maps at a time; its scratch
+    // follows the bytes in the slab.  Off: the double-precision resize below, as before.
+    const PostPlan plan(h->post_on ? &h->post_cfg : nullptr);
+    if (plan.on) plan.fits(H, W);
+    const int post_chunk = (int)std::min<long long>(maps, P3D_POST_CHUNK);
+    PostScratch post_scratch;
+    Carve c;
+    c.take<unsigned char>((size_t)bytes);
+    if (plan.on) post_carve(c, post_scratch, plan, post_chunk, hw, true);
+    HIPCHECK(p3d_stream_scratch(s, plan.on ? (c.off + 3) / 4 : (size_t)(bytes + 3) / 4, plan.on ? (size_t)post_chunk : 0, &slab, &counters));
+    c = Carve{(char*)slab, 0};
+    unsigned char* d = c.take<unsigned char>((size_t)bytes);
+    if (plan.on) post_carve(c, post_scratch, plan, post_chunk, hw, true);
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     if (stage_ms)
         for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
@@ -2603,12 +2696,15 @@ int p3d_pred_maps_u8(p3d_handle* h, const int* first_frame, float scale, int H, 
     if (pr->materialize && h->last_forward_fused) pr->materialize(s);
     const long long phw = (long long)pr->H * pr->W;
     long long off = 0;
+    std::vector<PostRun> runs;
     for (int b = 0; b < B; ++b) {
         const int f0 = first_frame[b], n = T - f0;
         if (n == 0) continue;
+        if (plan.on) { runs.push_back({pr->p + ((size_t)b * T + f0) * phw * pr->ld, phw * pr->ld, pr->ld, n}); continue; }
         HIPCHECK(p3d_resize_u8(pr->p + ((size_t)b * T + f0) * phw * pr->ld, phw * pr->ld, pr->ld, n, pr->H, pr->W, scale, d, off, H, W, s));
         off += n * hw;
     }
+    if (plan.on) post_sequence(s, runs, (int)maps, pr->H, pr->W, H, W, plan, post_scratch, counters, post_chunk, nullptr, d, 0, scale);
     if (stage_ms) HIPCHECK(hipEventRecord(ev[1], s));
     HIPCHECK(hipMemcpyAsync(out, d, (size_t)bytes, hipMemcpyDeviceToHost, s));
     if (stage_ms) HIPCHECK(hipEventRecord(ev[2], s));
@@ -2620,6 +2716,113 @@ int p3d_pred_maps_u8(p3d_handle* h, const int* first_frame, float scale, int H, 
         stage_ms[0] = t0; stage_ms[1] = t1;
         for (auto& e : ev) HIPCHECK(hipEventDestroy(e));
     }
+    API_END
+}
+
+// ---- p3d_set_postprocess and the op-level entry points of its stage ----------------------------------------------------------
+int p3d_set_postprocess(p3d_handle* h, const p3d_postprocess* cfg) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    h->set_postprocess(cfg);
+    API_END
+}
+
+int p3d_get_postprocess(p3d_handle* h, p3d_postprocess* cfg, int* on) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    if (cfg) *cfg = h->post_cfg;
+    if (on) *on = h->post_on ? 1 : 0;
+    API_END
+}
+
+int p3d_blur_taps(float sigma, int radius, float* taps, int cap, int* r) {
+    API_BEGIN
+    const p3d_postprocess cfg{sigma, radius, P3D_NORM_NONE};
+    const PostPlan plan(&cfg);
+    if (plan.r > 0) {
+        if (!taps || cap < 2 * plan.r + 1) throw P3dError("blur_taps: room for " + std::to_string(2 * plan.r + 1) + " floats is needed");
+        memcpy(taps, plan.taps.data(), plan.taps.size() * sizeof(float));
+    }
+    if (r) *r = plan.r;
+    API_END
+}
+
+int p3d_debug_blur_strip(int r, int* cols, int* rows, int* lds_bytes) {
+    API_BEGIN
+    if (r < 0 || r > P3D_BLUR_MAX_RADIUS || !cols || !rows || !lds_bytes) throw P3dError("blur_strip: radius in [0, 255] and three results");
+    const PostStrip st = p3d_post_strip(r);
+    *cols = st.cols; *rows = st.rows; *lds_bytes = st.lds_bytes;
+    API_END
+}
+
+int p3d_gaussian_blur(int device, const float* src, int n, int H, int W, float sigma, int radius, float* dst) {
+    API_BEGIN
+    const p3d_postprocess cfg{sigma, radius, P3D_NORM_NONE};
+    const PostPlan plan(&cfg);
+    metric_args(device, src, src, 1, 1, dst);
+    if (n < 1 || H < 1 || W < 1) throw P3dError("gaussian_blur: empty map");
+    if ((long long)H * W > INT32_MAX) throw P3dError("gaussian_blur: H * W exceeds the kernels' int32 in-map offsets");
+    plan.fits(H, W);
+    const long long N = (long long)H * W;
+    const int chunk = std::min(n, P3D_POST_CHUNK);
+    DevArr<float> maps((size_t)n * N, src);
+    PostScratch ps;
+    Carve c;
+    post_carve(c, ps, plan, chunk, N, false);
+    float* slab = nullptr;
+    unsigned* counters = nullptr;
+    HIPCHECK(p3d_stream_scratch(nullptr, (c.off + 3) / 4, (size_t)chunk, &slab, &counters));
+    c = Carve{(char*)slab, 0};
+    post_carve(c, ps, plan, chunk, N, false);
+    post_sequence(nullptr, {}, n, H, W, H, W, plan, ps, counters, chunk, maps.p, nullptr, 0, 0.f);
+    maps.get(dst, (size_t)n * N);
+    API_END
+}
+
+int p3d_postprocess_maps(int device, const float* maps, int n, int h, int w, int elem_stride, int H, int W,
+                         const p3d_postprocess* cfg, float scale, float* out_f32, unsigned char* out_u8) {
+    API_BEGIN
+    const PostPlan plan(cfg);
+    metric_args(device, maps, maps, 1, 1, maps);
+    if (n < 1 || h < 1 || w < 1 || elem_stride < 1 || H < 1 || W < 1) throw P3dError("postprocess_maps: empty map");
+    if ((long long)H * W > INT32_MAX) throw P3dError("postprocess_maps: H * W exceeds the kernels' int32 in-map offsets");
+    plan.fits(H, W);
+    const long long N = (long long)H * W, per_map = (long long)h * w * elem_stride, ne = (long long)n * N;
+    const int chunk = std::min(n, P3D_POST_CHUNK);
+    DevArr<float> src((size_t)n * per_map, maps);
+    // the outputs between guards: 8 floats either side of out_f32; out_u8 at byte 19 of a buffer of guard words
+    const uint32_t guard = 0x7fc5a5a5u;                    // a NaN no arithmetic here produces
+    const long long fat = 8, bat = 19, bwords = (ne + bat + 16 + 3) / 4;
+    const std::vector<uint32_t> fg((size_t)(out_f32 ? ne + 2 * fat : 1), guard), bg((size_t)(out_u8 ? bwords : 1), guard);
+    DevArr<uint32_t> fbuf(fg.size(), fg.data()), bbuf(bg.size(), bg.data());
+    PostScratch ps;
+    Carve c;
+    post_carve(c, ps, plan, chunk, N, !out_f32);
+    float* slab = nullptr;
+    unsigned* counters = nullptr;
+    HIPCHECK(p3d_stream_scratch(nullptr, (c.off + 3) / 4, (size_t)chunk, &slab, &counters));
+    c = Carve{(char*)slab, 0};
+    post_carve(c, ps, plan, chunk, N, !out_f32);
+    post_sequence(nullptr, {{src.p, per_map, elem_stride, n}}, n, h, w, H, W, plan, ps, counters, chunk,
+                  out_f32 ? reinterpret_cast<float*>(fbuf.p) + fat : nullptr, out_u8 ? reinterpret_cast<unsigned char*>(bbuf.p) : nullptr, bat,
+                  scale);
+    if (out_f32) {
+        std::vector<uint32_t> back(fg.size());
+        fbuf.get(back.data(), back.size());
+        for (long long i = 0; i < (long long)back.size(); ++i)
+            if ((i < fat || i >= fat + ne) && back[(size_t)i] != guard) throw P3dError("postprocess_maps: a launch wrote outside the float maps");
+        memcpy(out_f32, back.data() + fat, (size_t)ne * 4);
+    }
+    if (out_u8) {
+        std::vector<uint32_t> back(bg.size());
+        bbuf.get(back.data(), back.size());
+        const unsigned char* got = reinterpret_cast<const unsigned char*>(back.data());
+        const unsigned char* was = reinterpret_cast<const unsigned char*>(bg.data());
+        for (long long i = 0; i < bwords * 4; ++i)
+            if ((i < bat || i >= bat + ne) && got[i] != was[i]) throw P3dError("postprocess_maps: a launch wrote outside the byte maps");
+        memcpy(out_u8, got + bat, (size_t)ne);
+    }
+    if (!out_f32 && !out_u8) HIPCHECK(hipDeviceSynchronize());
     API_END
 }
 

@@ -509,6 +509,48 @@
         aug_have = true;
     }
 
+    // ---- smoothing and normalisation of output maps (p3d_set_postprocess) ------------------------------
+    // Off by default, and off nothing here runs.  The setting is three numbers: the stage itself (postprocess.hip) is issued by
+    // the two users of the handle's prediction, p3d_eval_last_frames and p3d_pred_maps_u8 (net_abi.inc: post_sequence), with
+    // scratch from the stream pool at first use.  No step, launch list or captured graph ever names it.
+    bool post_on = false;
+    p3d_postprocess post_cfg{0.f, 0, P3D_NORM_NONE};
+    // the effective radius (include/p3d_hip.h, RADIUS); throws on a setting the header refuses
+    static int post_radius(const p3d_postprocess& c) {
+        if (!std::isfinite(c.sigma) || c.sigma < 0.f) throw P3dError("postprocess: sigma must be finite and >= 0");
+        if (c.radius < 0 || c.radius > P3D_BLUR_MAX_RADIUS) throw P3dError("postprocess: radius must be in [0, " + std::to_string(P3D_BLUR_MAX_RADIUS) + "]");
+        if (c.radius > 0 && c.sigma == 0.f) throw P3dError("postprocess: a radius needs sigma > 0");
+        if (c.norm != P3D_NORM_NONE && c.norm != P3D_NORM_MAX && c.norm != P3D_NORM_RANGE) throw P3dError("postprocess: unknown norm " + std::to_string(c.norm));
+        if (c.radius > 0 || c.sigma == 0.f) return c.radius;
+        const double k = std::rint(8.0 * (double)c.sigma + 1.0);
+        if (k > 2.0 * P3D_BLUR_MAX_RADIUS + 1.0)
+            throw P3dError("postprocess: sigma asks for a radius above " + std::to_string(P3D_BLUR_MAX_RADIUS) + "; give a radius");
+        return ((int)k | 1) / 2;
+    }
+    static bool post_neutral(const p3d_postprocess& c) { return c.sigma == 0.f && c.radius == 0 && c.norm == P3D_NORM_NONE; }
+    // the 2r + 1 weights (include/p3d_hip.h, TAPS), r >= 1
+    static std::vector<float> post_taps(float sigma, int r) {
+#pragma clang fp contract(off)
+        std::vector<double> e((size_t)(2 * r + 1));
+        const double s2 = 2.0 * ((double)sigma * (double)sigma);
+        double S = 0.0;
+        for (int k = 0; k <= 2 * r; ++k) {
+            const double d = (double)(k - r);
+            e[(size_t)k] = std::exp(-(d * d) / s2);
+            S += e[(size_t)k];
+        }
+        std::vector<float> w(e.size());
+        for (size_t k = 0; k < e.size(); ++k) w[k] = (float)(e[k] / S);
+        return w;
+    }
+    void set_postprocess(const p3d_postprocess* c) {
+        const p3d_postprocess neutral{0.f, 0, P3D_NORM_NONE};
+        const p3d_postprocess want = c ? *c : neutral;
+        post_radius(want);                     // refuses before anything changes
+        post_on = !post_neutral(want);
+        post_cfg = post_on ? want : neutral;
+    }
+
     // ---- gradient clipping by the global norm (p3d_set_grad_clip) ----------------------------------
     // clip_norm > 0: the step's sum of squares over every trainable element's g' (g + c w under a regularisation term), its
     // norm and scale = clip_norm / max(norm, clip_norm) land in d_clip_res before any optimiser launch, and every optimiser

@@ -705,6 +705,13 @@ hipError_t p3d_resize_f32(const float* src, long long map_stride, int elem_strid
 // Writes bytes off .. off + n*H*W - 1 of dst (dst 4-byte aligned); needs H * W <= INT32_MAX.
 hipError_t p3d_resize_u8(const float* src, long long map_stride, int elem_stride, int n, int h, int w, float scale, unsigned char* dst,
                          long long off, int H, int W, hipStream_t s);
+// saturate_cast<uchar>(double) as cv2.imwrite's conversion to CV_8U does it on x86 (the byte law of resize_u8_kernel and of
+// postprocess.hip's apply pass): round half to even, clamp to [0, 255]; NaN and a rounded value outside int32 give 0.
+__device__ __forceinline__ unsigned p3d_sat_u8(double v) {
+    const double r = rint(v);                                  // NaN stays NaN and fails both range tests below
+    if (!(r >= -2147483648.0 && r <= 2147483647.0)) return 0u;
+    return r <= 0.0 ? 0u : r >= 255.0 ? 255u : (unsigned)r;
+}
 struct P3dFullMaps {
     const float* P = nullptr;        // [n_maps][n_pix] saliency maps (clean)
     const float* D = nullptr;        // [n_maps][n_pix] density maps as float32(v / 255.) of the uint8 resize, or null (no CC / SIM)
@@ -736,6 +743,40 @@ int p3d_full_blocks(long long n_pix);
 hipError_t p3d_full_moments(const P3dFullMaps& a, hipStream_t s);        // stats, CC, NSS, the fixated values
 hipError_t p3d_full_rank(const P3dFullMaps& a, hipStream_t s);           // thresholds sorted; SIM, AUC_Judd
 hipError_t p3d_full_borji(const P3dFullMaps& a, const P3dFullBorji& r, hipStream_t s);
+
+// ---- smoothing and normalisation of output maps (postprocess.hip; p3d_set_postprocess, the contract in include/p3d_hip.h) -----
+// One launch sequence on n maps of H x W floats, every stage optional:
+//   POST_RESIZE  src given: resize_f32_kernel's float32 cv2.INTER_LINEAR law, src [n] maps of h x w -> maps;
+//   POST_BLUR_H  r > 0: the horizontal pass, maps -> tmp;      POST_BLUR_V  r > 0: the vertical pass, tmp -> maps;
+//   POST_MINMAX  norm != 0: float32 min and max of every map -> mnmx[n][2], partials folded by the last arriving block;
+//   POST_APPLY   norm != 0 or u8 given: v' by `norm` stored back to maps, and sat_u8((double)fmul(v', scale)) to byte u8_off + i of
+//                u8 when given (u8 4-byte aligned, u8_off arbitrary: whole words where aligned, as resize_u8_kernel).
+// taps: the 2r + 1 weights in device memory (p3d_post_taps makes them on the host).  No contraction; each output element is
+// computed by one lane in the header's order, whatever the tiling.  Refused (hipErrorInvalidValue) before anything is launched:
+// r outside [0, P3D_POST_MAX_RADIUS] or above min(H, W) - 1, H * W above INT32_MAX, n above 65535, a missing buffer.
+constexpr int P3D_POST_MAX_RADIUS = 255;
+constexpr int P3D_POST_CHUNK = 16;            // maps per launch sequence of the chunked callers (scratch: 2 * 16 maps)
+enum { POST_RESIZE = 0, POST_BLUR_H = 1, POST_BLUR_V = 2, POST_MINMAX = 3, POST_APPLY = 4, POST_STAGES = 5 };
+struct PostArgs {
+    const float* src = nullptr; long long map_stride = 0; int elem_stride = 1, h = 0, w = 0;      // src null: no POST_RESIZE
+    int n = 0, H = 0, W = 0;
+    float* maps = nullptr;                    // [n][H][W]
+    float* tmp = nullptr;                     // [n][H][W], r > 0
+    const float* taps = nullptr;              // [2r + 1], r > 0
+    int r = 0, norm = 0;                      // norm: P3D_NORM_*
+    float* part = nullptr;                    // [n][nblk][2], norm != 0
+    float* mnmx = nullptr;                    // [n][2], norm != 0
+    unsigned* counter = nullptr;              // [n] arrival counters, zero at launch (and after), norm != 0
+    int nblk = 0;                             // p3d_post_blocks(H * W)
+    unsigned char* u8 = nullptr; long long u8_off = 0; float scale = 0.f;
+};
+// the vertical pass's strip for radius r: cols columns x rows output rows per block, (rows + 2r) x cols floats + r + 1 taps of LDS
+struct PostStrip { int cols, rows, lds_bytes; };
+PostStrip p3d_post_strip(int r);              // host only; lds_bytes <= 65536 for every r in [0, P3D_POST_MAX_RADIUS]
+int p3d_post_blocks(long long n_pix);
+bool p3d_post_has(int stage, const PostArgs& a);
+LaunchDesc p3d_post_desc(int stage, const PostArgs& a);
+hipError_t p3d_post_launch(int stage, const PostArgs& a, hipStream_t s);      // a stage the arguments do not ask for: nothing, success
 
 // ---- misc ---------------------------------------------------------------------------------------
 hipError_t p3d_add_inplace(float* dst, int lddst, const float* src, int ldsrc, long M, int C, hipStream_t s);

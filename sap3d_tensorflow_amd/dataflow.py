@@ -73,6 +73,82 @@ def resize_linear_u8(maps, size, scale=255., device=0):
     return out[0] if single else out
 
 
+def _post_cfg(sigma, radius, norm):
+    from . import _lib
+    if norm not in _lib.NORMS:
+        raise ValueError("normalisation %r: have %s" % (norm, sorted(_lib.NORMS)))
+    return _lib.P3dPostprocess(float(sigma), int(radius), _lib.NORMS[norm])
+
+
+def blur_taps(sigma, radius=0):
+    """The weights of the Gaussian of P3DSession.set_postprocess (p3d_blur_taps, host only): float32 [2 r + 1] with
+    r = radius, or cv2's rule for float images when radius is 0 (r = (int(rint(8 sigma + 1)) | 1) // 2); w_k = float32(e_k / sum e),
+    e_k = exp(-(k - r)^2 / (2 sigma^2)) in float64.  sigma == 0: the empty array (no blur)."""
+    from . import _lib
+    taps = np.empty(2 * _lib.P3D_BLUR_MAX_RADIUS + 1, np.float32)
+    r = C.c_int(0)
+    check(lib().p3d_blur_taps(float(sigma), int(radius), taps.ctypes.data_as(C.POINTER(C.c_float)), taps.size, C.byref(r)))
+    return taps[:2 * r.value + 1].copy() if r.value > 0 else np.zeros(0, np.float32)
+
+
+def blur_strip(radius):
+    """(columns, rows, LDS bytes) of one block of the blur's vertical pass at this radius (p3d_debug_blur_strip, host only)."""
+    c, r, b = C.c_int(0), C.c_int(0), C.c_int(0)
+    check(lib().p3d_debug_blur_strip(int(radius), C.byref(c), C.byref(r), C.byref(b)))
+    return c.value, r.value, b.value
+
+
+def gaussian_blur(maps, sigma, radius=0, device=0):
+    """The separable Gaussian of include/p3d_hip.h on float32 maps [n, H, W] or [H, W], same shape out: blur_taps' weights, a
+    horizontal then a vertical float32 pass with reflect-101 borders (csrc/postprocess.hip).  Needs r <= min(H, W) - 1."""
+    m = np.ascontiguousarray(maps, dtype=np.float32)
+    single = m.ndim == 2
+    if single:
+        m = m[None]
+    if m.ndim != 3 or m.size == 0:
+        raise ValueError("expected [n, H, W] or [H, W] float32 maps")
+    out = np.empty_like(m)
+    fp = C.POINTER(C.c_float)
+    check(lib().p3d_gaussian_blur(device, m.ctypes.data_as(fp), m.shape[0], m.shape[1], m.shape[2], float(sigma), int(radius),
+                                  out.ctypes.data_as(fp)))
+    return out[0] if single else out
+
+
+def postprocess_maps(maps, size, sigma=0., radius=0, norm="none", scale=None, device=0):
+    """The output stage of P3DSession.set_postprocess on supplied maps (p3d_postprocess_maps): float32 [n, h, w], [h, w], or
+    [n, h, w, c] of which channel 0 is taken -> resize_linear to size = (H, W), gaussian_blur, then each map divided by its
+    maximum (norm="max") or brought to its range (norm="range").  -> float32 [n, H, W]; with `scale`, the uint8 images
+    saturate_cast(float32(v * scale)) instead."""
+    m = np.ascontiguousarray(maps, dtype=np.float32)
+    single = m.ndim == 2
+    if single:
+        m = m[None]
+    if m.ndim not in (3, 4) or m.size == 0:
+        raise ValueError("expected [n, h, w], [h, w] or [n, h, w, c] float32 maps")
+    H, W = (size, size) if np.isscalar(size) else size
+    cfg = _post_cfg(sigma, radius, norm)
+    out = np.empty((m.shape[0], H, W), np.float32 if scale is None else np.uint8)
+    fp, u8 = C.POINTER(C.c_float), C.POINTER(C.c_ubyte)
+    check(lib().p3d_postprocess_maps(device, m.ctypes.data_as(fp), m.shape[0], m.shape[1], m.shape[2], m.shape[3] if m.ndim == 4 else 1,
+                                     int(H), int(W), C.byref(cfg), 0.0 if scale is None else float(scale),
+                                     out.ctypes.data_as(fp) if scale is None else None, out.ctypes.data_as(u8) if scale is not None else None))
+    return out[0] if single else out
+
+
+def postprocess_maps_both(maps, size, sigma=0., radius=0, norm="none", scale=255., device=0):
+    """postprocess_maps with both outputs of one call -> (float32 [n, H, W], uint8 [n, H, W])."""
+    m = np.ascontiguousarray(maps, dtype=np.float32)
+    if m.ndim not in (3, 4) or m.size == 0:
+        raise ValueError("expected [n, h, w] or [n, h, w, c] float32 maps")
+    H, W = (size, size) if np.isscalar(size) else size
+    cfg = _post_cfg(sigma, radius, norm)
+    f, b = np.empty((m.shape[0], H, W), np.float32), np.empty((m.shape[0], H, W), np.uint8)
+    fp, u8 = C.POINTER(C.c_float), C.POINTER(C.c_ubyte)
+    check(lib().p3d_postprocess_maps(device, m.ctypes.data_as(fp), m.shape[0], m.shape[1], m.shape[2], m.shape[3] if m.ndim == 4 else 1,
+                                     int(H), int(W), C.byref(cfg), float(scale), f.ctypes.data_as(fp), b.ctypes.data_as(u8)))
+    return f, b
+
+
 def fixations_to_grid(fix_u8, H, W):
     """Full-resolution fixation maps on the training grid: uint8 [n, H0, W0] -> uint8 [n, H, W] of 0 / 255, for the losses with an
     NSS term (P3DSession.upload_fixations).  A grid cell is fixated if any source pixel with byte >= 128 maps to it by

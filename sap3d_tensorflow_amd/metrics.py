@@ -167,11 +167,13 @@ def eval_draws(fixation, jitter, n_rep, rng=None):
     return n_fix, jit, idx
 
 
-def evaluate_maps(maps, density, fixation, size=None, jitter=True, n_rep=100, step_size=0.1, rng=None, device=0):
+def evaluate_maps(maps, density, fixation, size=None, jitter=True, n_rep=100, step_size=0.1, rng=None, device=0, postprocess=None):
     """Test hook (p3d_debug_eval_maps): P3DSession.evaluate's device pass on supplied maps instead of a session's prediction ->
     [n, 5] float64: CC, SIM, AUC_Judd, AUC_Borji, NSS.  maps: float32 [n, h, w], or [n, h, w, c] of which channel 0 is scored
     (the way the prediction buffer is addressed); density uint8 [n, Hd, Wd]; fixation uint8 [n, H, W] with (H, W) == size
-    (default: the fixation maps' own).  The draws are evaluate's (eval_draws)."""
+    (default: the fixation maps' own).  The draws are evaluate's (eval_draws).  postprocess: dict(sigma, radius, norm) as
+    P3DSession.set_postprocess takes them -- the smoothing / normalisation stage runs between the resize and the metrics
+    (p3d_debug_eval_maps_post)."""
     m = np.ascontiguousarray(maps, dtype=np.float32)
     dens = np.ascontiguousarray(density)
     fix = np.ascontiguousarray(fixation)
@@ -189,8 +191,14 @@ def evaluate_maps(maps, density, fixation, size=None, jitter=True, n_rep=100, st
     out = np.empty((n, 5), np.float64)
     u8 = C.POINTER(C.c_ubyte)
     ip = C.POINTER(C.c_int)
-    check(lib().p3d_debug_eval_maps(device, _fp(m), n, m.shape[1], m.shape[2], m.shape[3] if m.ndim == 4 else 1, dens.ctypes.data_as(u8),
-                                    dens.shape[1], dens.shape[2], fix.ctypes.data_as(u8), int(H), int(W),
-                                    _dp(jit) if jit is not None else None, idx.ctypes.data_as(ip), n_fix.ctypes.data_as(ip),
-                                    int(n_rep), float(step_size), _dp(out)))
+    args = (device, _fp(m), n, m.shape[1], m.shape[2], m.shape[3] if m.ndim == 4 else 1, dens.ctypes.data_as(u8),
+            dens.shape[1], dens.shape[2], fix.ctypes.data_as(u8), int(H), int(W),
+            _dp(jit) if jit is not None else None, idx.ctypes.data_as(ip), n_fix.ctypes.data_as(ip),
+            int(n_rep), float(step_size), _dp(out))
+    if postprocess is None:
+        check(lib().p3d_debug_eval_maps(*args))
+    else:
+        from .dataflow import _post_cfg
+        cfg = _post_cfg(postprocess.get("sigma", 0.), postprocess.get("radius", 0), postprocess.get("norm", "none"))
+        check(lib().p3d_debug_eval_maps_post(*(args + (C.byref(cfg),))))
     return out

@@ -450,6 +450,31 @@ class P3DSession:
         train_step_device(.., seed) is train_step(x, y, .., seed)."""
         check(lib().p3d_augment_inputs(self._h, int(seed)))
 
+    # ---- smoothing and normalisation of the output maps (p3d_set_postprocess) ---------------------------
+    def set_postprocess(self, sigma=0., radius=0, norm="none"):
+        """Smooth and normalise every map that evaluate scores and pred_maps_u8 writes, at output resolution on the device (an
+        addition: gen_pred.py writes map * 255 and test.py scores the bare resize).  The float32 resize, then a Gaussian of
+        `sigma` pixels -- radius 0 follows cv2's rule, (int(rint(8 sigma + 1)) | 1) // 2, at most 255 -- with reflect-101 borders,
+        then per map norm="max" (v / max) or "range" ((v - min) / (max - min)); include/p3d_hip.h holds the exact arithmetic and
+        dataflow.postprocess_maps runs it on supplied maps.  While on, pred_maps_u8 resizes in float32 (not float64) before it
+        smooths.  set_postprocess(None), or the defaults, switch the option off.  Training never sees it."""
+        if sigma is None:
+            check(lib().p3d_set_postprocess(self._h, None))
+            return
+        if norm not in _lib.NORMS:
+            raise ValueError("normalisation %r: have %s" % (norm, sorted(_lib.NORMS)))
+        cfg = _lib.P3dPostprocess(float(sigma), int(radius), _lib.NORMS[norm])
+        check(lib().p3d_set_postprocess(self._h, C.byref(cfg)))
+
+    @property
+    def postprocess(self):
+        """None while the option is off, else dict(sigma, radius, norm) as set."""
+        cfg, on = _lib.P3dPostprocess(), C.c_int(0)
+        check(lib().p3d_get_postprocess(self._h, C.byref(cfg), C.byref(on)))
+        if not on.value:
+            return None
+        return dict(sigma=cfg.sigma, radius=cfg.radius, norm=[k for k, v in _lib.NORMS.items() if v == cfg.norm][0])
+
     # ---- moving average of the weights (p3d_set_ema) ---------------------------------------------------
     def set_ema(self, decay, warmup=False):
         """Keep an exponential moving average of every trainable variable, as tf.train.ExponentialMovingAverage(decay).apply(
@@ -508,7 +533,8 @@ class P3DSession:
         """gen_pred.py:154-168's 8-bit images of the last prediction (predict_windows / forward), resized on the device:
         clip b gives frames first_frame[b] .. T-1 (0: the first window's 16 maps, 15: a later window's newest map, T: none)
         -> uint8 [sum(T - first_frame), H, W], in clip then frame order.  Each map is cv2.imwrite's byte image of
-        cv2.resize(float64(map * scale), (W, H)) (dataflow.resize_linear_u8).  Device times of the call are left in
+        cv2.resize(float64(map * scale), (W, H)) (dataflow.resize_linear_u8); under set_postprocess it is
+        dataflow.postprocess_maps(map, size, ..., scale=scale) instead.  Device times of the call are left in
         `last_maps_ms` (device = resize / quantise, d2h = the copy back; milliseconds)."""
         H, W = (size, size) if np.isscalar(size) else tuple(size)
         B, T = self.x_shape[0], self.x_shape[1]
