@@ -17,7 +17,13 @@ Output (`--write`):
             (gen_pred.py:83-86).  PNG is lossless: its pixels are exactly those bytes.  JPEG is written by PIL at
             quality 95 (cv2's default); the files are not byte-identical to cv2's encoder.  Files are encoded on `--writers`
             threads while the GPU runs the next batch.  --blur-sigma / --blur-radius / --normalize (an addition) smooth and
-            normalise every map at `--size` on the GPU before it is quantised (P3DSession.set_postprocess)."""
+            normalise every map at `--size` on the GPU before it is quantised (P3DSession.set_postprocess).
+
+`--resident` (an addition) keeps a video on the device instead: the uint8 frames are normalised straight into a frame store
+(P3DSession.video_put_u8), windows are cut there (video_predict) and the maps are read once per video.  `--stride N` places a
+window every N frames, and a last one at F - 16 so that every frame is covered; `--overlap newest` gives a frame the map of the
+first window that holds it (at stride 1 the reference's rule: the npy files hold the default path's bytes), `--overlap mean` the
+mean of every window that predicted it.  A stride other than 1 and `--overlap mean` imply `--resident`."""
 import argparse
 import glob
 import os
@@ -70,6 +76,70 @@ def predict_video_images(sess, frames, batch, size=(1080, 960), scale=255.):
         first = [0 if s == 0 else 15 for s in chunk] + [16] * (batch - len(chunk))
         maps = sess.pred_maps_u8(first, size=size, scale=scale)
         yield [s + t for s, f0 in zip(chunk, first) for t in range(f0, 16)], maps
+
+
+def window_starts(F, stride):
+    """Window starts 0, stride, 2 stride, ... and a last window at F - 16, so that every frame is covered."""
+    starts = list(range(0, F - 15, stride))
+    if starts[-1] != F - 16:
+        starts.append(F - 16)
+    return starts
+
+
+PUT_CHUNK = 64      # frames per upload of the resident path
+
+
+def predict_video_resident(sess, video_u8, batch, stride=1, overlap="newest", times=None):
+    """video_u8 [F,H0,W0,3] uint8 RGB -> the open video on the device, every window predicted (P3DSession.open_video /
+    video_put_u8 / video_predict); read it with sess.video_maps / video_maps_u8.  times (a dict or None) collects the HIP-event
+    milliseconds of the window cuts and map folds."""
+    F = len(video_u8)
+    if F < 16:
+        raise ValueError("need at least 16 frames")
+    sess.open_video(F, overlap)
+    for i in range(0, F, PUT_CHUNK):
+        sess.video_put_u8(i, video_u8[i:i + PUT_CHUNK, ..., ::-1])       # the kernel takes cv2's BGR order
+    starts = window_starts(F, stride)
+    for i in range(0, len(starts), batch):
+        sess.video_predict(starts[i:i + batch])
+        if times is not None:
+            ms = sess.video_last_ms()
+            times["gather"] = times.get("gather", 0.0) + ms["gather"]
+            times["scatter"] = times.get("scatter", 0.0) + ms["scatter"]
+            times["batches"] = times.get("batches", 0) + 1
+    return F
+
+
+def write_video_images_resident(sess, F, video_dir, ext, size=(1080, 960), writers=4):
+    """write_video_images for the open video: its maps leave the device 16 at a time (video_maps_u8) while the previous 16 are
+    encoded.  Returns the same dict; gpu is the wall time of the map stages alone."""
+    import threading
+    from concurrent.futures import ThreadPoolExecutor
+    t = dict(gpu=0.0, device=0.0, d2h=0.0, encode=0.0, files=0)
+    lock = threading.Lock()
+
+    def write(f, m):
+        t0 = time.perf_counter()
+        save_image(os.path.join(video_dir, "frame_%d.%s" % (f + 1, ext)), m, ext)
+        with lock:
+            t["encode"] += (time.perf_counter() - t0) * 1e3
+
+    held = []
+    with ThreadPoolExecutor(max_workers=writers) as pool:
+        for first in range(0, F, 16):
+            n = min(16, F - first)
+            t0 = time.perf_counter()
+            maps = sess.video_maps_u8(first, n, size=size)
+            t["gpu"] += (time.perf_counter() - t0) * 1e3
+            t["device"] += sess.last_maps_ms["device"]
+            t["d2h"] += sess.last_maps_ms["d2h"]
+            for fut in held:
+                fut.result()
+            held = [pool.submit(write, first + k, m) for k, m in enumerate(maps)]
+            t["files"] += n
+        for fut in held:
+            fut.result()
+    return t
 
 
 def save_image(path, m, ext):
@@ -145,10 +215,22 @@ def parse_args(argv=None):
     p.add_argument("--normalize", choices=("none", "max", "range"), default="none",
                    help="[addition] png / jpg: scale every (smoothed) map by its maximum, or to its range, before it is quantised")
     p.add_argument("--writers", type=int, default=4, help="encoder threads for png / jpg (at most 16)")
+    p.add_argument("--resident", action="store_true", help="[addition] keep every video on the device: frames go up once as uint8, "
+                   "windows are cut there and the maps are read once per video (P3DSession.open_video)")
+    p.add_argument("--stride", type=int, default=1, metavar="N", help="[addition] a window every N frames (and a last one at F - 16); "
+                   "1 is the reference's.  Other values imply --resident")
+    p.add_argument("--overlap", choices=("newest", "mean"), default="newest", help="[addition] a frame's map: that of the first window "
+                   "that holds it (at stride 1 the reference's rule), or the mean of every window that predicted it (implies --resident)")
+    p.add_argument("--base", type=int, default=64, help=argparse.SUPPRESS)
+    p.add_argument("--blocks", type=str, default="3,8,36", help=argparse.SUPPRESS)
     p.add_argument("--time", action="store_true", help="print per-video wall times (png / jpg: also the device stage and the host encode)")
     args = p.parse_args(argv)
     if not 1 <= args.writers <= 16:
         p.error("--writers must be in 1..16")
+    if args.stride < 1:
+        p.error("--stride must be at least 1")
+    if args.stride != 1 or args.overlap != "newest":
+        args.resident = True
     if args.write == "npy" and (args.blur_sigma != 0. or args.blur_radius != 0 or args.normalize != "none"):
         p.error("--blur-sigma / --blur-radius / --normalize shape the images: they need --write png or jpg (npy stays the raw 112x112 maps)")
     return args
@@ -157,6 +239,9 @@ def parse_args(argv=None):
 def run(sess, args):
     os.makedirs(args.out, exist_ok=True)
     for path in sorted(glob.glob(os.path.join(args.videos, "*.npy"))):
+        if args.resident:
+            run_resident(sess, args, path)
+            continue
         if args.write == "npy":
             t0 = time.perf_counter()
             sal = predict_video(sess, preprocess(np.load(path)), args.batch)
@@ -181,10 +266,41 @@ def run(sess, args):
                   "thread time on %d writers" % (name, wall, t["gpu"], t["device"], t["d2h"], t["encode"], args.writers))
 
 
+def run_resident(sess, args, path):
+    """One video of run() on the resident path."""
+    name = os.path.splitext(os.path.basename(path))[0]
+    video_dir = os.path.join(args.out, name)
+    if args.write != "npy":
+        if os.path.exists(video_dir):                 # gen_pred.py:83-86: a video already written is skipped
+            print(name, "skipped: %s exists" % video_dir)
+            return
+        os.mkdir(video_dir)
+    t0 = time.perf_counter()
+    times = {}
+    F = predict_video_resident(sess, np.load(path), args.batch, args.stride, args.overlap, times)
+    t1 = time.perf_counter()
+    if args.write == "npy":
+        sal = sess.video_maps(0, F)
+        np.save(os.path.join(args.out, os.path.basename(path)), sal)
+        print(os.path.basename(path), sal.shape, float(sal.mean()))
+    else:
+        t = write_video_images_resident(sess, F, video_dir, args.write, size=tuple(args.size), writers=args.writers)
+        print(name, "%d %s files in %s" % (t["files"], args.write, video_dir))
+    sess.close_video()
+    if args.time:
+        print("  %s: wall %.1f ms | resident, stride %d, overlap %s: %d forward passes in %.1f ms (window cuts %.3f ms, map folds %.3f ms "
+              "on the device)" % (os.path.basename(path), (time.perf_counter() - t0) * 1e3, args.stride, args.overlap, times["batches"],
+                                  (t1 - t0) * 1e3, times["gather"], times["scatter"]))
+        if args.write != "npy":
+            print("  %s: maps %.1f ms (device resize/quantise %.2f ms, d2h %.2f ms) | encode %.1f ms thread time on %d writers"
+                  % (name, t["gpu"], t["device"], t["d2h"], t["encode"], args.writers))
+
+
 def main(argv=None):
     args = parse_args(argv)
     from sap3d_tensorflow_amd import P3DSession
-    sess = P3DSession(args.structure, batch=args.batch, device=int(args.gpu), seed=0)
+    blocks = tuple(int(v) for v in args.blocks.split(","))
+    sess = P3DSession(args.structure, batch=args.batch, device=int(args.gpu), seed=0, base=args.base, blocks=blocks)
     if args.model:
         sess.restore(args.model, ema_as_weights=args.ema)
     sess.set_postprocess(args.blur_sigma, args.blur_radius, args.normalize)

@@ -802,6 +802,76 @@ int p3d_debug_eval_maps_post(int device, const float* maps, int n_maps, int h, i
 /* Host only (no HIP call): the vertical pass's strip for radius r -- columns, output rows and LDS bytes of one block. */
 int p3d_debug_blur_strip(int r, int* cols, int* rows, int* lds_bytes);
 
+/* ---- Resident video inference (an ADDITION beside p3d_predict_windows: gen_pred.py slides a 16-frame queue by one frame and keeps
+ * nothing on the device).  A video's normalised frames go up once, windows are cut where the frames are, and every frame's map is
+ * kept on the device until it is read.  OFF until p3d_video_open: while no video is open every other entry point issues what it
+ * issued before and returns the same bits, and nothing is allocated.  Open and close do not drop a captured step graph; the staged
+ * input keeps its address and is only overwritten, as p3d_upload_inputs overwrites it.  Works under p3d_ema_swap as
+ * p3d_predict_windows does; with world_size > 1 it is local to the rank.  PARITY: P3D_VIDEO_NEWEST with starts 0, 1, 2, ... is the
+ * reference's rule (gen_pred.py:154-168: the first window writes all T maps, every later one its newest frame).  Other strides and
+ * P3D_VIDEO_MEAN are UNPINNED: this text is their contract and tests/video_ref.py replays it in numpy bit for bit.
+ * T, H, W, B below are the handle's frames, height, width and batch; F the open video's frames.
+ *
+ * p3d_video_open   allocates, on the handle's device, a frame store [F][H][W][3] float32, a map store [F][H][W] float32 and a
+ *                  contribution count per frame, all 0; no frame counts as put and last_start = -1.  Opening again replaces the
+ *                  video; the allocation is reused when it is large enough.  Refused (-1, nothing changed): frames < T, a mode that
+ *                  is neither of the two, a store the device cannot hold.
+ * p3d_video_close  frees the stores.  p3d_video_info: F, the mode and the last start accepted since the open (-1: none); any pointer
+ *                  may be NULL; refused while no video is open, like every call below.
+ * p3d_video_put_frames     copies n normalised frames x [n][H][W][3] to frames first .. first + n - 1.
+ * p3d_video_put_frames_u8  uploads n decoded frames bgr [n][H0][W0][3] and normalises them straight into the store: the stored
+ *                  floats are, bit for bit, what p3d_mapf_frames returns for those frames.  Frames may arrive in any order and in
+ *                  several calls; a range outside [0, F) is refused.
+ * p3d_video_predict  n_windows in 1 .. B; starts strictly ascending, every start greater than last_start and inside [0, F - T], and
+ *                  every frame of every window put.  Anything else: -1, p3d_last_error names the first offending window or
+ *                  frame, nothing is launched and nothing changes.  Then:
+ *     GATHER   one launch: clip k of the staged input = frames starts[k] .. starts[k] + T - 1 of the store, a copy of the bits.
+ *              Clips n_windows .. B - 1 are copies of the last window (they keep the per-clip BatchNorm statistics finite and
+ *              contribute nothing below).
+ *     FORWARD  p3d_predict_windows's pass (per-clip statistics, not training, no dropout): the prediction of clip k equals, bit
+ *              for bit, what p3d_predict_windows returns for clip k on the same windows stacked and padded by the host.
+ *              p3d_pred_maps_u8 keeps working on the batch.
+ *     SCATTER  one launch, no atomics.  For k ascending and t = 0 .. T - 1, with f = starts[k] + t:
+ *              P3D_VIDEO_NEWEST  if count[f] == 0: map[f] = pred[k][t], a copy of the bits, and count[f] = 1; else frame f is left
+ *                                alone (every frame comes from the first window that holds it);
+ *              P3D_VIDEO_MEAN    if count[f] == 0: sum[f] = pred[k][t], a copy of the bits (-0 stays -0); else
+ *                                sum[f] = fadd(sum[f], pred[k][t]) in float32; then count[f] += 1.  The ascending rule fixes the
+ *                                order ((p_s0 + p_s1) + p_s2) + ..., so the bits do not depend on the run or the batching.
+ *     last_start = starts[n_windows - 1].  The call returns synchronised.
+ * p3d_video_get_maps  frames first .. first + n - 1 -> maps [n][H][W]: the stored map under NEWEST; under MEAN
+ *                  __fdiv_rn(sum, (float)count) per element (a count of 1 returns the sum's bits), computed into scratch: the sums
+ *                  are not rewritten, so more windows can follow.  counts (or NULL) [n] receives the frames' counts.  A frame
+ *                  with count 0 is refused and the error names it.
+ * p3d_video_maps_u8   p3d_pred_maps_u8's chain on those maps (MEAN: finalised into scratch first) -> out [n][H][W] bytes: the
+ *                  double-precision p3d_resize_linear_u8 law, or under p3d_set_postprocess the float32 resize / BLUR / NORM / BYTE
+ *                  sequence, 16 maps at a time.  stage_ms as p3d_pred_maps_u8's.
+ * p3d_video_last_ms   HIP-event time of the last p3d_video_predict's gather (ms[0]) and scatter (ms[1]) launches, milliseconds. */
+enum { P3D_VIDEO_NEWEST = 0, P3D_VIDEO_MEAN = 1 };
+int p3d_video_open(p3d_handle* h, int frames, int mode);
+int p3d_video_close(p3d_handle* h);
+int p3d_video_info(p3d_handle* h, int* frames, int* mode, int* last_start);
+int p3d_video_put_frames(p3d_handle* h, int first, const float* x, int n);
+int p3d_video_put_frames_u8(p3d_handle* h, int first, const unsigned char* bgr, int n, int H0, int W0, const float mean_rgb[3]);
+int p3d_video_predict(p3d_handle* h, const int* starts, int n_windows);
+int p3d_video_get_maps(p3d_handle* h, int first, int n, float* maps, int32_t* counts /* may be NULL */);
+int p3d_video_maps_u8(p3d_handle* h, int first, int n, float scale, int H, int W, unsigned char* out, double* stage_ms);
+int p3d_video_last_ms(p3d_handle* h, double ms[2]);
+/* Test hooks: the three launches from the launch descriptions the entry points use, on host arrays.  Every device buffer sits
+ * `offset` (0 .. 3) elements past a 16-byte boundary between guard elements; -1 if a guard or an input changed.
+ *   gather   store [F][frame_elems], starts [n_windows] each in [0, F - T] -> x [B][T][frame_elems] (padded as GATHER above);
+ *   scatter  pred [B][T][hw][ld] (channel 0 is the map), validated as p3d_video_predict validates (every frame counts as put);
+ *            store [F][hw] and count [F] are updated in place, and the counts the device wrote must equal the plan's;
+ *   mean     sum [n][hw], count [n] (each >= 1) -> out [n][hw];
+ *   plan     host only, no HIP call: validates as p3d_video_predict does and returns the counts after the call in count_out [F]
+ *            (untouched after a refusal). */
+int p3d_debug_video_gather(int device, const float* store, int F, int T, int64_t frame_elems, const int* starts, int n_windows, int B,
+                           int offset, float* x);
+int p3d_debug_video_scatter(int device, int mode, const float* pred, int B, int T, int64_t hw, int ld, const int* starts, int n_windows,
+                            int F, int last_start, float* store /* in/out [F][hw] */, int32_t* count /* in/out [F] */, int offset);
+int p3d_debug_video_mean(int device, const float* sum, const int32_t* count, int n, int64_t hw, int offset, float* out);
+int p3d_debug_video_plan(int mode, int F, int T, int B, int last_start, const int32_t* count_in, const int* starts, int n_windows,
+                         int32_t* count_out);
+
 /* CRC-32C of a host buffer (host-side helper of the TensorFlow checkpoint reader / writer, sap3d_tensorflow_amd/tf_checkpoint.py:
  * the bundle format of train.py:180-185,266-267 checksums every tensor); crc = running value, 0 to start. */
 uint32_t p3d_crc32c(const void* data, size_t n, uint32_t crc);

@@ -47,6 +47,8 @@ class P3dPostprocess(C.Structure):
 # p3d_set_postprocess normalisations (include/p3d_hip.h P3D_NORM_*)
 NORMS = {"none": 0, "max": 1, "range": 2}
 P3D_BLUR_MAX_RADIUS = 255
+# p3d_video_open modes (include/p3d_hip.h P3D_VIDEO_*)
+VIDEO_MODES = {"newest": 0, "mean": 1}
 
 
 class P3dError(RuntimeError):
@@ -213,6 +215,21 @@ SIGNATURES = {
     "p3d_debug_eval_maps_post": (C.c_int, [C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ubyte), C.c_int, C.c_int,
                                            C.POINTER(C.c_ubyte), C.c_int, C.c_int, _dp, _ip, _ip, C.c_int, C.c_double, _dp,
                                            C.POINTER(P3dPostprocess)]),
+    "p3d_video_open": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "p3d_video_close": (C.c_int, [C.c_void_p]),
+    "p3d_video_info": (C.c_int, [C.c_void_p, _ip, _ip, _ip]),
+    "p3d_video_put_frames": (C.c_int, [C.c_void_p, C.c_int, _fp, C.c_int]),
+    "p3d_video_put_frames_u8": (C.c_int, [C.c_void_p, C.c_int, _u8p, C.c_int, C.c_int, C.c_int, _fp]),
+    "p3d_video_predict": (C.c_int, [C.c_void_p, _ip, C.c_int]),
+    "p3d_video_get_maps": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _fp, C.POINTER(C.c_int32)]),
+    "p3d_video_maps_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, _u8p, _dp]),
+    "p3d_video_last_ms": (C.c_int, [C.c_void_p, _dp]),
+    "p3d_debug_video_gather": (C.c_int, [C.c_int, _fp, C.c_int, C.c_int, C.c_int64, _ip, C.c_int, C.c_int, C.c_int, _fp]),
+    "p3d_debug_video_scatter": (C.c_int, [C.c_int, C.c_int, _fp, C.c_int, C.c_int, C.c_int64, C.c_int, _ip, C.c_int, C.c_int, C.c_int,
+                                          _fp, C.POINTER(C.c_int32), C.c_int]),
+    "p3d_debug_video_mean": (C.c_int, [C.c_int, _fp, C.POINTER(C.c_int32), C.c_int, C.c_int64, C.c_int, _fp]),
+    "p3d_debug_video_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), _ip, C.c_int,
+                                       C.POINTER(C.c_int32)]),
     "p3d_crc32c": (C.c_uint32, [C.c_void_p, C.c_size_t, C.c_uint32]),
     "p3d_shutdown": (C.c_int, []),
 }

@@ -2652,6 +2652,63 @@ int p3d_resize_linear_u8(int device, const float* src, int n, int h, int w, floa
     API_END
 }
 
+}  // extern "C"
+namespace {
+// gen_pred.py's write-out of `maps` maps that live on the device, for p3d_pred_maps_u8 and p3d_video_maps_u8: the bytes, the
+// scratch of p3d_set_postprocess's stage and `extra` floats of the caller's share one slab of the stream's scratch.  sources runs
+// inside the device stage's time: it queues whatever makes the maps readable and names them as runs of maps of ph x pw pixels.
+// Off: one double-precision p3d_resize_u8 per run; on: the float32 resize / blur / normalise / byte sequence, P3D_POST_CHUNK maps
+// at a time.  Ends synchronised; stage_ms as p3d_pred_maps_u8's.
+void maps_u8_chain(p3d_handle* h, long long maps, int ph, int pw, float scale, int H, int W, unsigned char* out, double* stage_ms,
+                   size_t extra, const std::function<void(hipStream_t, float*, std::vector<PostRun>&)>& sources) {
+    const long long hw = (long long)H * W, bytes = maps * hw;
+    const hipStream_t s = h->stream;
+    float* slab = nullptr;
+    unsigned* counters = nullptr;
+    // p3d_set_postprocess: the float32 chain resize -> blur -> normalise -> bytes, P3D_POST_CHUNK maps at a time; its scratch
+    // follows the bytes in the slab.  Off: the double-precision resize below, as before.
+    const PostPlan plan(h->post_on ? &h->post_cfg : nullptr);
+    if (plan.on) plan.fits(H, W);
+    const int post_chunk = (int)std::min<long long>(maps, P3D_POST_CHUNK);
+    PostScratch post_scratch;
+    Carve c;
+    c.take<unsigned char>((size_t)bytes);
+    if (plan.on) post_carve(c, post_scratch, plan, post_chunk, hw, true);
+    if (extra) c.take<float>(extra);
+    HIPCHECK(p3d_stream_scratch(s, plan.on || extra ? (c.off + 3) / 4 : (size_t)(bytes + 3) / 4, plan.on ? (size_t)post_chunk : 0, &slab, &counters));
+    c = Carve{(char*)slab, 0};
+    unsigned char* d = c.take<unsigned char>((size_t)bytes);
+    if (plan.on) post_carve(c, post_scratch, plan, post_chunk, hw, true);
+    float* ex = extra ? c.take<float>(extra) : nullptr;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    if (stage_ms)
+        for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
+    if (stage_ms) HIPCHECK(hipEventRecord(ev[0], s));
+    std::vector<PostRun> runs;
+    sources(s, ex, runs);
+    if (plan.on) post_sequence(s, runs, (int)maps, ph, pw, H, W, plan, post_scratch, counters, post_chunk, nullptr, d, 0, scale);
+    else {
+        long long off = 0;
+        for (const PostRun& r : runs) {
+            HIPCHECK(p3d_resize_u8(r.p, r.map_stride, r.elem_stride, r.n, ph, pw, scale, d, off, H, W, s));
+            off += r.n * hw;
+        }
+    }
+    if (stage_ms) HIPCHECK(hipEventRecord(ev[1], s));
+    HIPCHECK(hipMemcpyAsync(out, d, (size_t)bytes, hipMemcpyDeviceToHost, s));
+    if (stage_ms) HIPCHECK(hipEventRecord(ev[2], s));
+    HIPCHECK(hipStreamSynchronize(s));
+    if (stage_ms) {
+        float t0 = 0, t1 = 0;
+        HIPCHECK(hipEventElapsedTime(&t0, ev[0], ev[1]));
+        HIPCHECK(hipEventElapsedTime(&t1, ev[1], ev[2]));
+        stage_ms[0] = t0; stage_ms[1] = t1;
+        for (auto& e : ev) HIPCHECK(hipEventDestroy(e));
+    }
+}
+}  // namespace
+extern "C" {
+
 int p3d_pred_maps_u8(p3d_handle* h, const int* first_frame, float scale, int H, int W, unsigned char* out, double* stage_ms) {
     API_BEGIN
     if (!h || !first_frame || !out) throw P3dError("null argument");
@@ -2667,55 +2724,19 @@ int p3d_pred_maps_u8(p3d_handle* h, const int* first_frame, float scale, int H, 
                            " is outside [0, " + std::to_string(T) + "]");
         maps += T - first_frame[b];
     }
-    const long long hw = (long long)H * W, bytes = maps * hw;
     if (stage_ms) stage_ms[0] = stage_ms[1] = 0.0;
-    if (bytes == 0) return 0;
+    if (maps == 0) return 0;
     HIPCHECK(hipSetDevice(h->cfg.device));
-    const hipStream_t s = h->stream;
-    float* slab = nullptr;
-    unsigned* counters = nullptr;
-    // p3d_set_postprocess: the float32 chain resize -> blur -> normalise -> bytes, P3D_POST_CHUNK maps at a time; its scratch
-    // follows the bytes in the slab.  Off: the double-precision resize below, as before.
-    const PostPlan plan(h->post_on ? &h->post_cfg : nullptr);
-    if (plan.on) plan.fits(H, W);
-    const int post_chunk = (int)std::min<long long>(maps, P3D_POST_CHUNK);
-    PostScratch post_scratch;
-    Carve c;
-    c.take<unsigned char>((size_t)bytes);
-    if (plan.on) post_carve(c, post_scratch, plan, post_chunk, hw, true);
-    HIPCHECK(p3d_stream_scratch(s, plan.on ? (c.off + 3) / 4 : (size_t)(bytes + 3) / 4, plan.on ? (size_t)post_chunk : 0, &slab, &counters));
-    c = Carve{(char*)slab, 0};
-    unsigned char* d = c.take<unsigned char>((size_t)bytes);
-    if (plan.on) post_carve(c, post_scratch, plan, post_chunk, hw, true);
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    if (stage_ms)
-        for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
-    if (stage_ms) HIPCHECK(hipEventRecord(ev[0], s));
     // the prediction of the last forward pass: [B][T][h][w] with an element stride of ld floats; clip b's frames
     // first_frame[b] .. T-1, packed after the maps of the clips before it
-    if (pr->materialize && h->last_forward_fused) pr->materialize(s);
-    const long long phw = (long long)pr->H * pr->W;
-    long long off = 0;
-    std::vector<PostRun> runs;
-    for (int b = 0; b < B; ++b) {
-        const int f0 = first_frame[b], n = T - f0;
-        if (n == 0) continue;
-        if (plan.on) { runs.push_back({pr->p + ((size_t)b * T + f0) * phw * pr->ld, phw * pr->ld, pr->ld, n}); continue; }
-        HIPCHECK(p3d_resize_u8(pr->p + ((size_t)b * T + f0) * phw * pr->ld, phw * pr->ld, pr->ld, n, pr->H, pr->W, scale, d, off, H, W, s));
-        off += n * hw;
-    }
-    if (plan.on) post_sequence(s, runs, (int)maps, pr->H, pr->W, H, W, plan, post_scratch, counters, post_chunk, nullptr, d, 0, scale);
-    if (stage_ms) HIPCHECK(hipEventRecord(ev[1], s));
-    HIPCHECK(hipMemcpyAsync(out, d, (size_t)bytes, hipMemcpyDeviceToHost, s));
-    if (stage_ms) HIPCHECK(hipEventRecord(ev[2], s));
-    HIPCHECK(hipStreamSynchronize(s));
-    if (stage_ms) {
-        float t0 = 0, t1 = 0;
-        HIPCHECK(hipEventElapsedTime(&t0, ev[0], ev[1]));
-        HIPCHECK(hipEventElapsedTime(&t1, ev[1], ev[2]));
-        stage_ms[0] = t0; stage_ms[1] = t1;
-        for (auto& e : ev) HIPCHECK(hipEventDestroy(e));
-    }
+    maps_u8_chain(h, maps, pr->H, pr->W, scale, H, W, out, stage_ms, 0, [&](hipStream_t s, float*, std::vector<PostRun>& runs) {
+        if (pr->materialize && h->last_forward_fused) pr->materialize(s);
+        const long long phw = (long long)pr->H * pr->W;
+        for (int b = 0; b < B; ++b) {
+            const int f0 = first_frame[b], n = T - f0;
+            if (n > 0) runs.push_back({pr->p + ((size_t)b * T + f0) * phw * pr->ld, phw * pr->ld, pr->ld, n});
+        }
+    });
     API_END
 }
 
@@ -2823,6 +2844,224 @@ int p3d_postprocess_maps(int device, const float* maps, int n, int h, int w, int
         memcpy(out_u8, got + bat, (size_t)ne);
     }
     if (!out_f32 && !out_u8) HIPCHECK(hipDeviceSynchronize());
+    API_END
+}
+
+// ---- resident video inference (include/p3d_hip.h; the handle's part in net_sched.inc, the kernels in video.hip) --------------
+int p3d_video_open(p3d_handle* h, int frames, int mode) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->video_open(frames, mode);
+    API_END
+}
+
+int p3d_video_close(p3d_handle* h) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->video_close();
+    API_END
+}
+
+int p3d_video_info(p3d_handle* h, int* frames, int* mode, int* last_start) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    h->video_need_open("video_info");
+    if (frames) *frames = h->vid_F;
+    if (mode) *mode = h->vid_mode;
+    if (last_start) *last_start = h->vid_last;
+    API_END
+}
+
+int p3d_video_put_frames(p3d_handle* h, int first, const float* x, int n) {
+    API_BEGIN
+    if (!h || !x) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->video_put_frames(first, x, n);
+    API_END
+}
+
+int p3d_video_put_frames_u8(p3d_handle* h, int first, const unsigned char* bgr, int n, int H0, int W0, const float mean_rgb[3]) {
+    API_BEGIN
+    if (!h || !bgr || !mean_rgb) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->video_put_frames_u8(first, bgr, n, H0, W0, mean_rgb);
+    API_END
+}
+
+int p3d_video_predict(p3d_handle* h, const int* starts, int n_windows) {
+    API_BEGIN
+    if (!h || !starts) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->video_predict(starts, n_windows);
+    API_END
+}
+
+int p3d_video_last_ms(p3d_handle* h, double ms[2]) {
+    API_BEGIN
+    if (!h || !ms) throw P3dError("null argument");
+    if (!h->vid_is_open || !h->vid_timed) throw P3dError("video_last_ms: no p3d_video_predict has run on the open video");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    float g = 0.f, sc = 0.f;
+    HIPCHECK(hipEventElapsedTime(&g, h->ev_vid[0], h->ev_vid[1]));
+    HIPCHECK(hipEventElapsedTime(&sc, h->ev_vid[2], h->ev_vid[3]));
+    ms[0] = (double)g; ms[1] = (double)sc;
+    API_END
+}
+
+int p3d_video_get_maps(p3d_handle* h, int first, int n, float* maps, int32_t* counts) {
+    API_BEGIN
+    if (!h || !maps) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->video_need_open("video_get_maps");
+    h->video_range("video_get_maps", first, n);
+    const hipStream_t s = h->stream;
+    const size_t ne = (size_t)n * (size_t)h->vid_hw();
+    float* slab = nullptr;
+    unsigned* counters = nullptr;
+    if (h->vid_mode == VIDEO_MEAN) HIPCHECK(p3d_stream_scratch(s, ne, 0, &slab, &counters));
+    const float* src = h->video_finalize("video_get_maps", first, n, slab, s);
+    HIPCHECK(copy_now(maps, src, ne * 4, hipMemcpyDeviceToHost, s));
+    if (counts) memcpy(counts, h->vid_count.data() + first, (size_t)n * sizeof(int32_t));
+    API_END
+}
+
+int p3d_video_maps_u8(p3d_handle* h, int first, int n, float scale, int H, int W, unsigned char* out, double* stage_ms) {
+    API_BEGIN
+    if (!h || !out) throw P3dError("null argument");
+    if (H < 1 || W < 1) throw P3dError("video_maps_u8: empty map");
+    if ((long long)H * W > INT32_MAX) throw P3dError("video_maps_u8: H * W exceeds the kernel's int32 in-map offsets");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->video_need_open("video_maps_u8");
+    h->video_range("video_maps_u8", first, n);
+    for (int f = first; f < first + n; ++f)      // (before the scratch is asked for: a refusal changes nothing)
+        if (h->vid_count[(size_t)f] == 0) throw P3dError("video_maps_u8: frame " + std::to_string(f) + " has no prediction yet (count 0)");
+    if (stage_ms) stage_ms[0] = stage_ms[1] = 0.0;
+    const long long phw = h->vid_hw();
+    maps_u8_chain(h, n, h->pred->H, h->pred->W, scale, H, W, out, stage_ms, h->vid_mode == VIDEO_MEAN ? (size_t)n * (size_t)phw : 0,
+                  [&](hipStream_t s, float* scratch, std::vector<PostRun>& runs) {
+                      runs.push_back({h->video_finalize("video_maps_u8", first, n, scratch, s), phw, 1, n});
+                  });
+    API_END
+}
+
+// The three launches of video.hip from their launch descriptions, on host arrays.  Every device buffer sits `offset` elements past
+// a 16-byte boundary between guard elements; a guard or an input that a launch changed is an error.
+}  // extern "C"
+namespace {
+constexpr uint32_t VID_GUARD = 0x7fc5a5a5u;      // a NaN no arithmetic here produces
+struct GuardedBuf {                               // n floats at element `at` of a device buffer of guards
+    int64_t n, at; std::vector<uint32_t> host; DevArr<uint32_t> dev;
+    static std::vector<uint32_t> fill(int64_t n, int64_t at, const void* src) {
+        std::vector<uint32_t> v((size_t)(n + 12), VID_GUARD);
+        if (src) memcpy(v.data() + at, src, (size_t)n * 4);
+        return v;
+    }
+    GuardedBuf(int64_t n_, int offset, const void* src) : n(n_), at(4 + offset), host(fill(n_, 4 + offset, src)), dev(host.size(), host.data()) {}
+    float* p() { return reinterpret_cast<float*>(dev.p) + at; }
+    std::vector<uint32_t> back() { std::vector<uint32_t> v(host.size()); dev.get(v.data(), v.size()); return v; }
+    static bool guards_kept(const std::vector<uint32_t>& v, int64_t at, int64_t n) {
+        for (int64_t i = 0; i < (int64_t)v.size(); ++i)
+            if ((i < at || i >= at + n) && v[(size_t)i] != VID_GUARD) return false;
+        return true;
+    }
+};
+void video_hook_device(int device, int offset) {
+    int ndev = 0;
+    HIPCHECK(hipGetDeviceCount(&ndev));
+    if (ndev <= 0) throw P3dError("no HIP device: libp3dhip has no CPU fallback");
+    if (device < 0 || device >= ndev) throw P3dError("bad device ordinal");
+    if (offset < 0 || offset > 3) throw P3dError("video hook: offset is 0 .. 3");
+    HIPCHECK(hipSetDevice(device));
+}
+}  // namespace
+extern "C" {
+
+int p3d_debug_video_gather(int device, const float* store, int F, int T, int64_t frame_elems, const int* starts, int n_windows, int B,
+                           int offset, float* x) {
+    API_BEGIN
+    if (!store || !starts || !x) throw P3dError("null argument");
+    if (T < 1 || F < T || frame_elems < 1 || B < 1 || n_windows < 1 || n_windows > B) throw P3dError("video_gather: bad shape");
+    if ((int64_t)F * frame_elems > (int64_t)1 << 31 || (int64_t)B * T * frame_elems > (int64_t)1 << 31) throw P3dError("video_gather: the hook takes up to 2^31 floats");
+    video_hook_device(device, offset);
+    std::vector<int> padded(starts, starts + n_windows);
+    padded.resize((size_t)B, starts[n_windows - 1]);
+    const int64_t ns = (int64_t)F * frame_elems, nx = (int64_t)B * T * frame_elems;
+    GuardedBuf sb(ns, offset, store), xb(nx, offset, nullptr);
+    DevArr<int> tab((size_t)B, padded.data());
+    VideoGatherArgs a;
+    a.store = sb.p(); a.x = xb.p(); a.starts = tab.p; a.starts_host = padded.data(); a.B = B; a.T = T; a.F = F; a.frame_elems = frame_elems;
+    if (std::string(p3d_video_gather_desc(a).kernel) != "video_gather_kernel") throw P3dError("video_gather: launch description names another kernel");
+    HIPCHECK(p3d_video_gather(a, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    if (sb.back() != sb.host) throw P3dError("video_gather: the launch changed the frame store");
+    const std::vector<uint32_t> xo = xb.back();
+    if (!GuardedBuf::guards_kept(xo, xb.at, nx)) throw P3dError("video_gather: the launch wrote outside its range");
+    memcpy(x, xo.data() + xb.at, (size_t)nx * 4);
+    API_END
+}
+
+int p3d_debug_video_scatter(int device, int mode, const float* pred, int B, int T, int64_t hw, int ld, const int* starts, int n_windows,
+                            int F, int last_start, float* store, int32_t* count, int offset) {
+    API_BEGIN
+    if (!pred || !starts || !store || !count) throw P3dError("null argument");
+    if (hw < 1 || ld < 1) throw P3dError("video_scatter: bad shape");
+    const p3d_handle::VideoPlan p = p3d_handle::video_plan(mode, F, T, B, last_start, count, nullptr, starts, n_windows);
+    const int64_t np = (int64_t)B * T * hw * ld, ns = (int64_t)F * hw;
+    if (np > (int64_t)1 << 31 || ns > (int64_t)1 << 31) throw P3dError("video_scatter: the hook takes up to 2^31 floats");
+    video_hook_device(device, offset);
+    GuardedBuf pb(np, offset, pred), sb(ns, offset, store), cb(F, 0, count);
+    if (!p.dst.empty()) {
+        DevArr<P3dVideoDst> dst(p.dst.size(), p.dst.data());
+        DevArr<int> src(p.src.size(), p.src.data());
+        VideoScatterArgs a;
+        a.mode = mode; a.pred = pb.p(); a.ld = ld; a.maps = B * T; a.hw = hw;
+        a.store = sb.p(); a.count = reinterpret_cast<int32_t*>(cb.p()); a.F = F;
+        a.dst = dst.p; a.src = src.p; a.dst_host = p.dst.data(); a.src_host = p.src.data();
+        a.ndst = (int)p.dst.size(); a.nsrc = (int)p.src.size();
+        if (std::string(p3d_video_scatter_desc(a).kernel) != "video_scatter_kernel<" + std::to_string(mode) + ">")
+            throw P3dError("video_scatter: launch description names another kernel");
+        HIPCHECK(p3d_video_scatter(a, nullptr));
+        HIPCHECK(hipDeviceSynchronize());
+    }
+    if (pb.back() != pb.host) throw P3dError("video_scatter: the launch changed the prediction");
+    const std::vector<uint32_t> so = sb.back(), co = cb.back();
+    if (!GuardedBuf::guards_kept(so, sb.at, ns) || !GuardedBuf::guards_kept(co, cb.at, F)) throw P3dError("video_scatter: the launch wrote outside its range");
+    if (memcmp(co.data() + cb.at, p.count.data(), (size_t)F * 4) != 0) throw P3dError("video_scatter: the device's counts differ from the plan's");
+    memcpy(store, so.data() + sb.at, (size_t)ns * 4);
+    memcpy(count, p.count.data(), (size_t)F * 4);
+    API_END
+}
+
+int p3d_debug_video_mean(int device, const float* sum, const int32_t* count, int n, int64_t hw, int offset, float* out) {
+    API_BEGIN
+    if (!sum || !count || !out) throw P3dError("null argument");
+    if (n < 1 || hw < 1 || (int64_t)n * hw > (int64_t)1 << 31) throw P3dError("video_mean: bad shape");
+    for (int i = 0; i < n; ++i)
+        if (count[i] < 1) throw P3dError("video_mean: frame " + std::to_string(i) + " has count " + std::to_string(count[i]));
+    video_hook_device(device, offset);
+    const int64_t ne = (int64_t)n * hw;
+    GuardedBuf sb(ne, offset, sum), ob(ne, offset, nullptr);
+    DevArr<int32_t> cb((size_t)n, count);
+    VideoMeanArgs a;
+    a.sum = sb.p(); a.count = cb.p; a.out = ob.p(); a.n = n; a.hw = hw;
+    if (std::string(p3d_video_mean_desc(a).kernel) != "video_mean_kernel") throw P3dError("video_mean: launch description names another kernel");
+    HIPCHECK(p3d_video_mean(a, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    if (sb.back() != sb.host) throw P3dError("video_mean: the launch changed the sums");
+    const std::vector<uint32_t> oo = ob.back();
+    if (!GuardedBuf::guards_kept(oo, ob.at, ne)) throw P3dError("video_mean: the launch wrote outside its range");
+    memcpy(out, oo.data() + ob.at, (size_t)ne * 4);
+    API_END
+}
+
+int p3d_debug_video_plan(int mode, int F, int T, int B, int last_start, const int32_t* count_in, const int* starts, int n_windows,
+                         int32_t* count_out) {
+    API_BEGIN
+    if (!count_out) throw P3dError("null argument");
+    const p3d_handle::VideoPlan p = p3d_handle::video_plan(mode, F, T, B, last_start, count_in, nullptr, starts, n_windows);
+    memcpy(count_out, p.count.data(), (size_t)F * sizeof(int32_t));
     API_END
 }
 

@@ -551,6 +551,194 @@
         post_cfg = post_on ? want : neutral;
     }
 
+    // ---- resident video inference (p3d_video_*; video.hip) ---------------------------------------------
+    // Nothing exists before the first p3d_video_open and nothing here runs while no video is open.  The stores are private
+    // allocations (freed by p3d_video_close, not part of `allocs`): no step, launch list or captured graph names them.  The gather
+    // writes the staged x_in, whose address never moves, as an upload does.  The host keeps the authoritative counts and which
+    // frames were put; the device's copy of the counts follows the scatter launches.  Every entry point ends synchronised, so
+    // the next call may overwrite the host tables.
+    bool vid_is_open = false;
+    int vid_F = 0, vid_mode = VIDEO_NEWEST, vid_last = -1;
+    int64_t vid_cap = 0;                       // frames the allocation holds
+    float* vid_frames = nullptr; float* vid_maps = nullptr; int32_t* vid_count_dev = nullptr;
+    unsigned char* vid_u8 = nullptr; size_t vid_u8_bytes = 0;      // staging of p3d_video_put_frames_u8's bytes
+    P3dVideoDst* d_vid_dst = nullptr; int* d_vid_src = nullptr; int* d_vid_starts = nullptr;      // the per-call tables, [B*T], [B*T], [B]
+    std::vector<int32_t> vid_count; std::vector<unsigned char> vid_put;
+    hipEvent_t ev_vid[4] = {nullptr, nullptr, nullptr, nullptr};      // around the last call's gather and scatter (p3d_video_last_ms)
+    bool vid_timed = false;
+    int64_t vid_frame_elems() const { return (int64_t)x_in->H * x_in->W * 3; }
+    int64_t vid_hw() const { return (int64_t)pred->H * pred->W; }
+
+    // What one p3d_video_predict does to the stores, from host state alone (no HIP call): validates as the header says -- the
+    // message names the first offending window or frame -- and builds the padded starts, the scatter table and the counts after
+    // the call.  put (or null: every frame counts as put) has F entries.
+    struct VideoPlan { std::vector<int> starts; std::vector<P3dVideoDst> dst; std::vector<int> src; std::vector<int32_t> count; };
+    static VideoPlan video_plan(int mode, int F, int T, int B, int last_start, const int32_t* count, const unsigned char* put,
+                                const int* starts, int n_windows) {
+        if (mode != VIDEO_NEWEST && mode != VIDEO_MEAN) throw P3dError("video: mode " + std::to_string(mode) + " is neither P3D_VIDEO_NEWEST (0) nor P3D_VIDEO_MEAN (1)");
+        if (T < 1 || B < 1 || F < T) throw P3dError("video: needs at least T = " + std::to_string(T) + " frames, has " + std::to_string(F));
+        if (!starts || !count) throw P3dError("null argument");
+        if (n_windows < 1 || n_windows > B) throw P3dError("video: n_windows = " + std::to_string(n_windows) + " is outside 1 .. batch = " + std::to_string(B));
+        for (int k = 0; k < n_windows; ++k) {
+            const int prev = k ? starts[k - 1] : last_start;
+            const std::string w = "video: window " + std::to_string(k) + " starts at " + std::to_string(starts[k]);
+            if (starts[k] < 0 || starts[k] > F - T) throw P3dError(w + ", outside [0, F - T = " + std::to_string(F - T) + "]");
+            if (starts[k] <= prev)
+                throw P3dError(w + (k ? ", not after window " + std::to_string(k - 1) + "'s " : ", not after the last start accepted, ") + std::to_string(prev));
+            for (int t = 0; put && t < T; ++t)
+                if (!put[starts[k] + t]) throw P3dError(w + " and holds frame " + std::to_string(starts[k] + t) + ", which was never put");
+        }
+        VideoPlan p;
+        p.starts.assign(starts, starts + n_windows);
+        p.starts.resize((size_t)B, starts[n_windows - 1]);      // the padding clips repeat the last window
+        p.count.assign(count, count + F);
+        const int f0 = starts[0], span = starts[n_windows - 1] + T - f0;
+        std::vector<int> n((size_t)span, 0), row((size_t)span, -1);
+        for (int k = 0; k < n_windows; ++k)
+            for (int t = 0; t < T; ++t) ++n[(size_t)(starts[k] + t - f0)];
+        int nsrc = 0;
+        for (int i = 0; i < span; ++i) {      // rows ascending by frame; NEWEST: only frames nothing has written, their first contributor
+            const int before = count[f0 + i];
+            if (n[(size_t)i] == 0 || (mode == VIDEO_NEWEST && before != 0)) continue;
+            const int take = mode == VIDEO_MEAN ? n[(size_t)i] : 1;
+            row[(size_t)i] = (int)p.dst.size();
+            p.dst.push_back({f0 + i, before, nsrc, 0});
+            nsrc += take;
+            p.count[(size_t)(f0 + i)] = mode == VIDEO_MEAN ? before + take : 1;
+        }
+        p.src.assign((size_t)nsrc, 0);
+        for (int k = 0; k < n_windows; ++k)      // ascending k within every frame
+            for (int t = 0; t < T; ++t) {
+                const int r = row[(size_t)(starts[k] + t - f0)];
+                if (r < 0) continue;
+                P3dVideoDst& d = p.dst[(size_t)r];
+                if (mode == VIDEO_NEWEST && d.n == 1) continue;
+                p.src[(size_t)(d.first + d.n++)] = k * T + t;
+            }
+        return p;
+    }
+
+    void video_need_open(const char* who) const {
+        if (!vid_is_open) throw P3dError(std::string(who) + ": no video is open (p3d_video_open)");
+    }
+    void video_range(const char* who, int first, int n) const {
+        if (n < 1 || first < 0 || first > vid_F - n)
+            throw P3dError(std::string(who) + ": frames " + std::to_string(first) + " .. " + std::to_string((int64_t)first + n - 1) +
+                           " are outside [0, " + std::to_string(vid_F) + ")");
+    }
+    void video_free() {
+        for (void* p : {(void*)vid_frames, (void*)vid_maps, (void*)vid_count_dev, (void*)vid_u8, (void*)d_vid_dst, (void*)d_vid_src, (void*)d_vid_starts})
+            if (p) hipFree(p);
+        vid_frames = vid_maps = nullptr; vid_count_dev = nullptr; vid_u8 = nullptr; vid_u8_bytes = 0;
+        d_vid_dst = nullptr; d_vid_src = nullptr; d_vid_starts = nullptr;
+        vid_cap = 0;
+    }
+    void video_open(int frames, int mode) {
+        const int T = x_in->D, B = x_in->N;
+        if (mode != VIDEO_NEWEST && mode != VIDEO_MEAN) throw P3dError("video_open: mode " + std::to_string(mode) + " is neither P3D_VIDEO_NEWEST (0) nor P3D_VIDEO_MEAN (1)");
+        if (frames < T) throw P3dError("video_open: " + std::to_string(frames) + " frames, a window needs " + std::to_string(T));
+        if ((int64_t)frames > INT64_MAX / 4 / vid_frame_elems()) throw P3dError("video_open: the frame store is not addressable");
+        sync_streams();
+        if (frames > vid_cap) {      // the new stores first: a failed allocation changes nothing
+            float *nf = nullptr, *nm = nullptr; int32_t* nc = nullptr;
+            const hipError_t e0 = hipMalloc((void**)&nf, (size_t)frames * vid_frame_elems() * 4);
+            const hipError_t e1 = e0 == hipSuccess ? hipMalloc((void**)&nm, (size_t)frames * vid_hw() * 4) : e0;
+            const hipError_t e2 = e1 == hipSuccess ? hipMalloc((void**)&nc, (size_t)frames * 4) : e1;
+            if (e2 != hipSuccess) {
+                if (nf) hipFree(nf);
+                if (nm) hipFree(nm);
+                (void)hipGetLastError();
+                throw P3dError("video_open: no device memory for " + std::to_string(frames) + " frames (" + hipGetErrorString(e2) + ")");
+            }
+            for (void* p : {(void*)vid_frames, (void*)vid_maps, (void*)vid_count_dev}) if (p) hipFree(p);
+            vid_frames = nf; vid_maps = nm; vid_count_dev = nc; vid_cap = frames;
+        }
+        if (!d_vid_dst) {
+            HIPCHECK(hipMalloc((void**)&d_vid_dst, (size_t)B * T * sizeof(P3dVideoDst)));
+            HIPCHECK(hipMalloc((void**)&d_vid_src, (size_t)B * T * sizeof(int)));
+            HIPCHECK(hipMalloc((void**)&d_vid_starts, (size_t)B * sizeof(int)));
+        }
+        if (!ev_vid[0]) for (auto& e : ev_vid) HIPCHECK(hipEventCreate(&e));
+        HIPCHECK(fill_now(vid_count_dev, 0, (size_t)frames * 4, stream));
+        vid_count.assign((size_t)frames, 0);
+        vid_put.assign((size_t)frames, 0);
+        vid_F = frames; vid_mode = mode; vid_last = -1; vid_is_open = true; vid_timed = false;
+    }
+    void video_close() {
+        sync_streams();
+        video_free();
+        vid_count.clear(); vid_put.clear();
+        vid_is_open = false; vid_F = 0; vid_last = -1; vid_timed = false;
+    }
+    void video_put_frames(int first, const float* x, int n) {
+        video_need_open("video_put_frames");
+        video_range("video_put_frames", first, n);
+        HIPCHECK(copy_now(vid_frames + (int64_t)first * vid_frame_elems(), x, (size_t)n * vid_frame_elems() * 4, hipMemcpyHostToDevice, stream));
+        std::fill(vid_put.begin() + first, vid_put.begin() + first + n, (unsigned char)1);
+    }
+    void video_put_frames_u8(int first, const unsigned char* bgr, int n, int H0, int W0, const float mean_rgb[3]) {
+        video_need_open("video_put_frames_u8");
+        video_range("video_put_frames_u8", first, n);
+        if (H0 < 1 || W0 < 1) throw P3dError("video_put_frames_u8: empty frame");
+        const size_t bytes = (size_t)n * H0 * W0 * 3;
+        if (bytes > vid_u8_bytes) {
+            HIPCHECK(hipStreamSynchronize(stream));
+            if (vid_u8) hipFree(vid_u8);
+            vid_u8 = nullptr; vid_u8_bytes = 0;
+            HIPCHECK(hipMalloc((void**)&vid_u8, bytes));
+            vid_u8_bytes = bytes;
+        }
+        HIPCHECK(hipMemcpyAsync(vid_u8, bgr, bytes, hipMemcpyHostToDevice, stream));
+        HIPCHECK(p3d_mapf_frames(vid_u8, n, H0, W0, vid_frames + (int64_t)first * vid_frame_elems(), x_in->H, x_in->W, mean_rgb, stream));
+        HIPCHECK(hipStreamSynchronize(stream));
+        std::fill(vid_put.begin() + first, vid_put.begin() + first + n, (unsigned char)1);
+    }
+    void video_predict(const int* starts, int n_windows) {
+        video_need_open("video_predict");
+        const int B = x_in->N, T = x_in->D;
+        const VideoPlan p = video_plan(vid_mode, vid_F, T, B, vid_last, vid_count.data(), vid_put.data(), starts, n_windows);
+        VideoGatherArgs g;
+        g.store = vid_frames; g.x = x_in->p; g.starts = d_vid_starts; g.starts_host = p.starts.data();
+        g.B = B; g.T = T; g.F = vid_F; g.frame_elems = vid_frame_elems();
+        VideoScatterArgs sc;
+        sc.mode = vid_mode; sc.pred = pred->p; sc.ld = pred->ld; sc.maps = B * T; sc.hw = vid_hw();
+        sc.store = vid_maps; sc.count = vid_count_dev; sc.F = vid_F;
+        sc.dst = d_vid_dst; sc.src = d_vid_src; sc.dst_host = p.dst.data(); sc.src_host = p.src.data();
+        sc.ndst = (int)p.dst.size(); sc.nsrc = (int)p.src.size();
+        HIPCHECK(hipMemcpyAsync(d_vid_starts, p.starts.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, stream));
+        if (sc.ndst) HIPCHECK(hipMemcpyAsync(d_vid_dst, p.dst.data(), p.dst.size() * sizeof(P3dVideoDst), hipMemcpyHostToDevice, stream));
+        if (sc.ndst) HIPCHECK(hipMemcpyAsync(d_vid_src, p.src.data(), p.src.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+        HIPCHECK(hipEventRecord(ev_vid[0], stream));
+        HIPCHECK(p3d_video_gather(g, stream));
+        HIPCHECK(hipEventRecord(ev_vid[1], stream));
+        Ctx c; c.training = false; c.drop = 0.f; c.update_moving = false; c.per_sample = true; c.s = stream;      // p3d_predict_windows's pass
+        run_forward(c);
+        if (pred->materialize && last_forward_fused) pred->materialize(stream);
+        HIPCHECK(hipEventRecord(ev_vid[2], stream));
+        if (sc.ndst) HIPCHECK(p3d_video_scatter(sc, stream));
+        HIPCHECK(hipEventRecord(ev_vid[3], stream));
+        HIPCHECK(hipStreamSynchronize(stream));
+        vid_count = p.count;
+        vid_last = starts[n_windows - 1];
+        vid_timed = true;
+    }
+    // frames first .. first + n - 1 as the read-out returns them: the map store itself under NEWEST; under MEAN `scratch`
+    // ([n][hw], not the store) after the division launches queued here.  Refuses a frame with count 0.
+    const float* video_finalize(const char* who, int first, int n, float* scratch, hipStream_t s) {
+        video_need_open(who);
+        video_range(who, first, n);
+        for (int f = first; f < first + n; ++f)
+            if (vid_count[(size_t)f] == 0) throw P3dError(std::string(who) + ": frame " + std::to_string(f) + " has no prediction yet (count 0)");
+        if (vid_mode == VIDEO_NEWEST) return vid_maps + (int64_t)first * vid_hw();
+        for (int done = 0; done < n; done += 32768) {
+            VideoMeanArgs a;
+            a.sum = vid_maps + (int64_t)(first + done) * vid_hw(); a.count = vid_count_dev + first + done;
+            a.out = scratch + (int64_t)done * vid_hw(); a.n = std::min(32768, n - done); a.hw = vid_hw();
+            HIPCHECK(p3d_video_mean(a, s));
+        }
+        return scratch;
+    }
+
     // ---- gradient clipping by the global norm (p3d_set_grad_clip) ----------------------------------
     // clip_norm > 0: the step's sum of squares over every trainable element's g' (g + c w under a regularisation term), its
     // norm and scale = clip_norm / max(norm, clip_norm) land in d_clip_res before any optimiser launch, and every optimiser
@@ -870,6 +1058,8 @@
         if (ev_side_bucket) hipEventDestroy(ev_side_bucket);
         if (ev_aug0) hipEventDestroy(ev_aug0);
         if (ev_aug1) hipEventDestroy(ev_aug1);
+        for (hipEvent_t e : ev_vid) if (e) hipEventDestroy(e);
+        video_free();
         // the streams go back to the pool (net.hip, "stream pool"); every path here has synchronised the device or never launched
         if (side_stream) { if (side_pooled) give_stream(cfg.device, 1, side_stream); else hipStreamDestroy(side_stream); }
         for (void* p : allocs) hipFree(p);

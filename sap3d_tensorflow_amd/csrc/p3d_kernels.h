@@ -683,6 +683,41 @@ inline int p3d_augment_stages(const AugArgs& a) { return a.fix ? 3 : 2; }
 LaunchDesc p3d_augment_desc(int stage, const AugArgs& a);
 hipError_t p3d_augment_launch(int stage, const AugArgs& a, hipStream_t s);
 
+// ---- resident video inference (video.hip; p3d_video_*, the contract in include/p3d_hip.h) -----------------------------------------
+// A frame store [F][frame_elems] and a map store [F][hw] with a contribution count per frame.  Three launches, each described once
+// for the handle and for the hooks.  Every table reaches its kernel in device memory; the launcher checks the same rows on the
+// host first (a row that leaves a buffer: hipErrorInvalidValue, nothing launched), because the kernels trust them.
+//   gather   clip b of x [B][T][frame_elems] = frames starts[b] .. starts[b] + T - 1 of the store, a copy of the bits (the caller
+//            pads starts to B rows with its last window).
+//   scatter  one table row per destination frame, ascending by frame: `before` = the frame's count before the call and its
+//            contributors src[first .. first + n), each the index k * T + t of a map of pred [maps][hw] (element stride ld),
+//            ascending in k.  VIDEO_NEWEST (rows only for frames with before == 0): map = the first contributor's bits, count = 1.
+//            VIDEO_MEAN: sum = before == 0 ? the first contributor's bits : the stored sum, then fadd of the others in order;
+//            count = before + n.  Frames without a row keep their bits.
+//   mean     out[i][hw] = __fdiv_rn(sum[i], (float)count[i]) for n frames; count 1 copies the bits.  sum != out.
+enum { VIDEO_NEWEST = 0, VIDEO_MEAN = 1 };
+struct P3dVideoDst { int frame, before, first, n; };
+struct VideoGatherArgs {
+    const float* store = nullptr; float* x = nullptr;
+    const int* starts = nullptr; const int* starts_host = nullptr;      // [B], device memory / the same rows on the host
+    int B = 0, T = 0, F = 0; long long frame_elems = 0;
+};
+struct VideoScatterArgs {
+    int mode = VIDEO_NEWEST;
+    const float* pred = nullptr; int ld = 1, maps = 0; long long hw = 0;
+    float* store = nullptr; int32_t* count = nullptr; int F = 0;
+    const P3dVideoDst* dst = nullptr; const int* src = nullptr;           // device memory
+    const P3dVideoDst* dst_host = nullptr; const int* src_host = nullptr; // the same rows on the host
+    int ndst = 0, nsrc = 0;
+};
+struct VideoMeanArgs { const float* sum = nullptr; const int32_t* count = nullptr; float* out = nullptr; int n = 0; long long hw = 0; };
+LaunchDesc p3d_video_gather_desc(const VideoGatherArgs& a);
+hipError_t p3d_video_gather(const VideoGatherArgs& a, hipStream_t s);
+LaunchDesc p3d_video_scatter_desc(const VideoScatterArgs& a);
+hipError_t p3d_video_scatter(const VideoScatterArgs& a, hipStream_t s);
+LaunchDesc p3d_video_mean_desc(const VideoMeanArgs& a);
+hipError_t p3d_video_mean(const VideoMeanArgs& a, hipStream_t s);
+
 // ---- saliency metrics + frame pre-processing (metrics.hip; utils/metrics.py:25-287, dataflow.py:187-216) ------
 hipError_t p3d_metric_cc(const float* a, const float* b, int n_maps, int n_pix, double* out, hipStream_t s);
 hipError_t p3d_metric_sim(const float* a, const float* b, int n_maps, int n_pix, double* out, hipStream_t s);

@@ -549,6 +549,79 @@ class P3DSession:
         self.last_maps_ms = dict(device=ms[0], d2h=ms[1])
         return out
 
+    # ---- resident video inference (p3d_video_*) -------------------------------------------------------------
+    def open_video(self, frames, mode="newest"):
+        """Keep a video of `frames` frames on the device (an addition: gen_pred.py keeps nothing there): its normalised frames
+        go up once (video_put / video_put_u8), video_predict cuts windows where they are, and every frame's map stays on the
+        device until video_maps / video_maps_u8 read it.  mode "newest": a frame's map comes from the first window that holds
+        it (with starts 0, 1, 2, .. the reference's write-out rule); "mean": the float32 mean of every window that predicted it,
+        summed in ascending window order.  Opening again replaces the video.  include/p3d_hip.h holds the exact rules."""
+        if mode not in _lib.VIDEO_MODES:
+            raise ValueError("video mode %r: have %s" % (mode, sorted(_lib.VIDEO_MODES)))
+        check(lib().p3d_video_open(self._h, int(frames), _lib.VIDEO_MODES[mode]))
+
+    def close_video(self):
+        check(lib().p3d_video_close(self._h))
+
+    def video_info(self):
+        """dict(frames, mode, last_start) of the open video; last_start is -1 before the first video_predict."""
+        f, m, l = C.c_int(), C.c_int(), C.c_int()
+        check(lib().p3d_video_info(self._h, C.byref(f), C.byref(m), C.byref(l)))
+        return dict(frames=f.value, mode=[k for k, v in _lib.VIDEO_MODES.items() if v == m.value][0], last_start=l.value)
+
+    def video_put(self, first, frames):
+        """Normalised float32 frames [n, H, W, 3] -> frames first .. first + n - 1 of the open video."""
+        a = np.ascontiguousarray(frames, dtype=np.float32)
+        if a.ndim != 4 or a.shape[1:] != self.x_shape[2:]:
+            raise ValueError("frames are %s, the video takes [n, %d, %d, 3]" % (a.shape, self.x_shape[2], self.x_shape[3]))
+        check(lib().p3d_video_put_frames(self._h, int(first), fptr(a), len(a)))
+
+    def video_put_u8(self, first, bgr, mean_rgb=(90., 102., 98.)):
+        """Decoded uint8 frames [n, H0, W0, 3] in cv2's BGR order, normalised on the device straight into the open video: what
+        dataflow.mapf_frames(bgr, (H, W), mean_rgb) returns, bit for bit, without the trip back to the host."""
+        a = np.ascontiguousarray(bgr)
+        if a.dtype != np.uint8 or a.ndim != 4 or a.shape[3] != 3:
+            raise ValueError("frames are %s %s, expected uint8 [n, H0, W0, 3]" % (a.dtype, a.shape))
+        mean = np.ascontiguousarray(mean_rgb, dtype=np.float32)
+        if mean.shape != (3,):
+            raise ValueError("mean_rgb needs three values")
+        check(lib().p3d_video_put_frames_u8(self._h, int(first), a.ctypes.data_as(_lib._u8p), a.shape[0], a.shape[1], a.shape[2], fptr(mean)))
+
+    def video_predict(self, starts):
+        """One forward pass on the windows that start at `starts` (1 .. batch of them, strictly ascending and after every start of
+        an earlier call): cut on the device, predicted as predict_windows predicts them, folded into the video's maps."""
+        st = np.ascontiguousarray(starts, dtype=np.int32)
+        if st.ndim != 1:
+            raise ValueError("starts is a list of window starts")
+        check(lib().p3d_video_predict(self._h, st.ctypes.data_as(_lib._ip), len(st)))
+
+    def video_last_ms(self):
+        """HIP-event times of the last video_predict's window cut and map fold: dict(gather, scatter), milliseconds."""
+        ms = (C.c_double * 2)()
+        check(lib().p3d_video_last_ms(self._h, ms))
+        return dict(gather=ms[0], scatter=ms[1])
+
+    def video_maps(self, first, n, with_counts=False):
+        """Maps of frames first .. first + n - 1, float32 [n, H, W] (mode "mean": sum / count); with_counts: also how many
+        windows contributed to each.  A frame no window has predicted yet is refused."""
+        n = max(int(n), 0)
+        maps = np.empty((n,) + self.y_shape[2:], np.float32)
+        counts = np.zeros(n, np.int32)
+        check(lib().p3d_video_get_maps(self._h, int(first), n, fptr(maps), counts.ctypes.data_as(C.POINTER(C.c_int32))))
+        return (maps, counts) if with_counts else maps
+
+    def video_maps_u8(self, first, n, size=(1080, 960), scale=255.):
+        """pred_maps_u8's 8-bit images of frames first .. first + n - 1 of the open video -> uint8 [n, H, W]; under
+        set_postprocess the smoothed, normalised ones.  Device times are left in `last_maps_ms`."""
+        H, W = (size, size) if np.isscalar(size) else tuple(size)
+        n = max(int(n), 0)
+        valid = H >= 1 and W >= 1 and H * W <= 2 ** 31 - 1
+        out = np.empty((n, H, W) if valid else (0,), np.uint8)     # (the library refuses the rest)
+        ms = (C.c_double * 2)()
+        check(lib().p3d_video_maps_u8(self._h, int(first), n, float(scale), int(H), int(W), out.ctypes.data_as(_lib._u8p), ms))
+        self.last_maps_ms = dict(device=ms[0], d2h=ms[1])
+        return out
+
     def upload_fixations(self, fixations):
         """The batch's fixation maps for the losses of _lib.SALIENCY_LOSSES: uint8 [B, T, H, W], fixated where the byte is 128 or
         more (p3d_upload_fixations; dataflow.fixations_to_grid brings full-resolution maps to the grid)."""
