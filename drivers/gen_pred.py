@@ -214,6 +214,10 @@ def parse_args(argv=None):
                    "0: cv2's rule, (int(rint(8 S + 1)) | 1) // 2")
     p.add_argument("--normalize", choices=("none", "max", "range"), default="none",
                    help="[addition] png / jpg: scale every (smoothed) map by its maximum, or to its range, before it is quantised")
+    p.add_argument("--match-hist", type=str, default="", metavar="FILE.npz", help="[addition] png / jpg: match the histogram of every "
+                   "(smoothed) map to the table of FILE.npz (`cdf`, `bin_centers`) before it is normalised and quantised "
+                   "(utils/metric_utils.py match_hist; P3DSession.set_hist_match)")
+    p.add_argument("--match-bins", type=int, default=256, metavar="N", help="[addition] bins of --match-hist's histograms, 2 .. 1024")
     p.add_argument("--writers", type=int, default=4, help="encoder threads for png / jpg (at most 16)")
     p.add_argument("--resident", action="store_true", help="[addition] keep every video on the device: frames go up once as uint8, "
                    "windows are cut there and the maps are read once per video (P3DSession.open_video)")
@@ -233,7 +237,21 @@ def parse_args(argv=None):
         args.resident = True
     if args.write == "npy" and (args.blur_sigma != 0. or args.blur_radius != 0 or args.normalize != "none"):
         p.error("--blur-sigma / --blur-radius / --normalize shape the images: they need --write png or jpg (npy stays the raw 112x112 maps)")
+    if args.write == "npy" and args.match_hist:
+        p.error("--match-hist shapes the images: it needs --write png or jpg (npy stays the raw 112x112 maps)")
+    if args.match_hist == "density":
+        p.error("--match-hist density needs a ground truth: it belongs to drivers/test.py; here it takes FILE.npz")
+    if not 2 <= args.match_bins <= 1024:
+        p.error("--match-bins must be in 2..1024")
     return args
+
+
+def match_target(args):
+    """What --match-hist asks for, as P3DSession.set_hist_match takes it: "off", or the table of an .npz."""
+    if not args.match_hist:
+        return "off"
+    from sap3d_tensorflow_amd import dataflow
+    return dataflow.load_match_table(args.match_hist)
 
 
 def run(sess, args):
@@ -304,6 +322,7 @@ def main(argv=None):
     if args.model:
         sess.restore(args.model, ema_as_weights=args.ema)
     sess.set_postprocess(args.blur_sigma, args.blur_radius, args.normalize)
+    sess.set_hist_match(match_target(args), args.match_bins)
     run(sess, args)
     sess.close()
 

@@ -78,7 +78,13 @@ def shuffled_auc(sess, fixation, lo, m, rng, device=0):
     from sap3d_tensorflow_amd import dataflow, metrics
     pred = sess.activation("pred")[:, -1, :, :, 0]
     post = sess.postprocess
-    if post:
+    match = sess.hist_match
+    if match and match["mode"] == "density":
+        raise ValueError("--sauc scores the clean map against other clips' fixations: it takes --match-hist FILE.npz, not density")
+    if match:
+        full = dataflow.postprocess_maps(pred, fixation.shape[1:], device=device, hist_match=(match["cdf"], match["bin_centers"]),
+                                         nbins=match["nbins"], **(post or {}))
+    elif post:
         full = dataflow.postprocess_maps(pred, fixation.shape[1:], device=device, **post)
     else:
         full = dataflow.resize_linear(pred, fixation.shape[1:], device=device)
@@ -91,7 +97,17 @@ def shuffled_auc(sess, fixation, lo, m, rng, device=0):
     return out
 
 
-def main(argv=None):
+def match_target(args):
+    """What --match-hist asks for, as P3DSession.set_hist_match takes it: "off", "density", or the table of an .npz."""
+    if not args.match_hist:
+        return "off"
+    if args.match_hist == "density":
+        return "density"
+    from sap3d_tensorflow_amd import dataflow
+    return dataflow.load_match_table(args.match_hist)
+
+
+def parse_args(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     p.add_argument("--model", type=str, default="", help="checkpoint: a directory with a TF `checkpoint` state file, a TF bundle "
                    "prefix, or an .npz keyed by TF variable names (test.py:145-150); none: freshly initialised weights")
@@ -115,9 +131,20 @@ def main(argv=None):
                    help="[addition] scale every (smoothed) map by its maximum, or to its range, before it is scored")
     # the reduced graph of the tests (the reference's is base 64, blocks 3/8/36)
     p.add_argument("--base", type=int, default=64, help=argparse.SUPPRESS)
+    p.add_argument("--match-hist", type=str, default="", metavar="density|FILE.npz", help="[addition] match the histogram of every "
+                   "(smoothed) prediction before it is normalised and scored (utils/metric_utils.py match_hist; "
+                   "P3DSession.set_hist_match): `density` -- to its own ground-truth density map; or an .npz with `cdf` and "
+                   "`bin_centers` -- one target table for every map")
+    p.add_argument("--match-bins", type=int, default=256, metavar="N", help="[addition] bins of --match-hist's histograms, 2 .. 1024")
     p.add_argument("--blocks", type=str, default="3,8,36", help=argparse.SUPPRESS)
     args = p.parse_args(argv)
+    if not 2 <= args.match_bins <= 1024:
+        p.error("--match-bins must be in 2..1024")
+    return args
 
+
+def main(argv=None):
+    args = parse_args(argv)
     from sap3d_tensorflow_amd import P3DSession, synthetic
     device = int(args.gpu)
     if args.data:
@@ -132,6 +159,7 @@ def main(argv=None):
         print("loading checkpoint %s" % sess.restore(args.model, ema_as_weights=args.ema))
     print("Now using model %s with structure %s" % (args.model or "(initialised)", structure))
     sess.set_postprocess(args.blur_sigma, args.blur_radius, args.normalize)
+    sess.set_hist_match(match_target(args), args.match_bins)
     np.random.seed(args.seed)
     sauc_rng = np.random.RandomState(args.seed) if args.sauc else None
     cols = [[] for _ in range(6 if args.sauc else 5)]
@@ -151,7 +179,8 @@ def main(argv=None):
                   % (index, t["forward"], t["draws"], t["h2d"], t["device"]))
     post = sess.postprocess
     print(metric_line(ALL_LINE, index, nan_dropped_means(cols)) +
-          ("   postprocess: sigma %g radius %d normalize %s" % (post["sigma"], post["radius"], post["norm"]) if post else ""))
+          ("   postprocess: sigma %g radius %d normalize %s" % (post["sigma"], post["radius"], post["norm"]) if post else "") +
+          ("   match-hist: %s, %d bins" % (args.match_hist, args.match_bins) if args.match_hist else ""))
     print("Testing Finished!")
     sess.close()
     return cols

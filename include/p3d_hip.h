@@ -802,6 +802,66 @@ int p3d_debug_eval_maps_post(int device, const float* maps, int n_maps, int h, i
 /* Host only (no HIP call): the vertical pass's strip for radius r -- columns, output rows and LDS bytes of one block. */
 int p3d_debug_blur_strip(int r, int* cols, int* rows, int* lds_bytes);
 
+/* ---- Histogram matching of predictions at output resolution (utils/metric_utils.py:56-84 match_hist(image, cdf, bin_centers,
+ * nbins=256), on tables made by skimage's exposure.cumulative_distribution; the reference's recipe, :321, is
+ * match_hist(map1, *exposure.cumulative_distribution(map2))).  It remaps a map so that its histogram follows a target's.  OFF by
+ * default; off, every entry point issues what it issued before and returns the same bits.  PARITY UNPINNED: skimage is not
+ * available to the tests, so this text is the contract; it is np.histogram plus np.interp, tests/hist_match_ref.py replays it in
+ * numpy bit for bit, and tests/test_hist_match_cpu.py holds that replay to numpy's own two functions.
+ * Everything is float64 on the float32 inputs, no fused multiply-add, every operation rounded on its own.  nb is the bin count,
+ * 2 <= nb <= P3D_HIST_MAX_BINS, 256 where a default applies.
+ *   CDF     of one map a of N values (np.histogram(a, nb), cumsum, / N):  mn, mx the map's minimum and maximum; if mn == mx they
+ *           become mn - 0.5 and mx + 0.5.  step = (mx - mn) / nb;  edge[k] = mn + k * step for k < nb, edge[nb] = mx;
+ *           norm = nb / (mx - mn).  The bin of v, in this order:  i = (int)((v - mn) * norm);  if i == nb: i = nb - 1;
+ *           if v < edge[i]: i -= 1;  else if v >= edge[i + 1] and i != nb - 1: i += 1.  count[k] is an integer;
+ *           centre[k] = (edge[k] + edge[k + 1]) / 2;  cdf[k] = (double)(count[0] + ... + count[k]) / (double)N, the running sum
+ *           kept in integers.
+ *   INTERP  interp(x, xp, fp) over n entries, xp non-decreasing (np.interp):  x < xp[0]: fp[0];  x >= xp[n - 1]: fp[n - 1];  else
+ *           with j the largest index with xp[j] <= x:  fp[j] if x == xp[j], otherwise
+ *           ((fp[j + 1] - fp[j]) / (xp[j + 1] - xp[j])) * (x - xp[j]) + fp[j].
+ *   MATCH   of a source map against a target table (cdf_t, centre_t) of nt entries:  new[k] = interp(cdf_s[k], cdf_t, centre_t)
+ *           for k < nb;  out = (float)interp((double)v, centre_s, new) per pixel, rounded to float32 once.
+ * Maps that hold NaN or inf are NOT pinned (they stay inside every buffer).  Supplied tables are checked on the host.
+ * Refused (-1, p3d_last_error set, nothing changed): nbins or nt outside [2, P3D_HIST_MAX_BINS]; a table that is not finite and
+ * non-decreasing (cdf and centres both); an unknown mode; NULL tables under P3D_MATCH_TABLE.
+ *
+ * p3d_cumulative_distribution  CDF on host maps [n][H][W] -> cdf [n][nbins], centres [n][nbins], and the counts [n][nbins] as
+ *                      int64 unless counts is NULL.
+ * p3d_match_hist       the reference's function: MATCH of maps [n][H][W] against n_tables (1, or n: one per map) tables of nt
+ *                      entries, cdf_t / centre_t [n_tables][nt] -> out [n][H][W].
+ * p3d_match_hist_maps  the reference's recipe: every map matched to the table of its own target image targets [n][H][W], both
+ *                      tables built on the device (nt = nbins).
+ * p3d_set_hist_match   the handle's setting, separate from p3d_set_postprocess; NULL or mode P3D_MATCH_OFF switch it off.  The
+ *                      tables are copied at set time.  Nothing is allocated until the stage first runs (scratch from the stream
+ *                      pool); the train step, a captured step graph and its schedule never see it.  The stage sits between BLUR
+ *                      and NORM of p3d_set_postprocess's chain: resize -> BLUR -> MATCH -> NORM -> BYTE.
+ *     P3D_MATCH_TABLE    one supplied table for every map, in p3d_eval_last_frames, p3d_pred_maps_u8 and p3d_video_maps_u8.
+ *                        With p3d_set_postprocess off, the two byte writers take the float32-resize chain, as they do for the blur.
+ *     P3D_MATCH_DENSITY  evaluation only: each prediction is matched to the table of its own ground-truth density at H x W, the
+ *                        doubles b / 255. of the resized bytes b that the metrics use, before the jitter is added and before
+ *                        every metric.  p3d_pred_maps_u8 and p3d_video_maps_u8 refuse while this mode is set.
+ * p3d_get_hist_match   mode, nbins (0 while off), nt and pointers to the handle's copy of the table (NULL without one; valid
+ *                      until the next p3d_set_hist_match or p3d_destroy).
+ * p3d_postprocess_maps_match  p3d_postprocess_maps with the stage of `match` (NULL: off; P3D_MATCH_DENSITY is refused).
+ * p3d_debug_eval_maps_match   p3d_debug_eval_maps_post with the stage of `match` (NULL: off). */
+enum { P3D_MATCH_OFF = 0, P3D_MATCH_TABLE = 1, P3D_MATCH_DENSITY = 2 };
+#define P3D_HIST_MAX_BINS 1024
+typedef struct p3d_hist_match { int mode; int nbins; int nt; const double* cdf; const double* centres; } p3d_hist_match;
+int p3d_cumulative_distribution(int device, const float* maps, int n, int H, int W, int nbins, int64_t* counts /* may be NULL */,
+                                double* cdf, double* centres);
+int p3d_match_hist(int device, const float* maps, int n, int H, int W, int nbins, const double* cdf_t, const double* centre_t,
+                   int n_tables, int nt, float* out);
+int p3d_match_hist_maps(int device, const float* maps, const float* targets, int n, int H, int W, int nbins, float* out);
+int p3d_set_hist_match(p3d_handle* h, const p3d_hist_match* cfg);
+int p3d_get_hist_match(p3d_handle* h, p3d_hist_match* cfg);
+int p3d_postprocess_maps_match(int device, const float* maps, int n, int h, int w, int elem_stride, int H, int W,
+                               const p3d_postprocess* cfg, const p3d_hist_match* match, float scale, float* out_f32,
+                               unsigned char* out_u8);
+int p3d_debug_eval_maps_match(int device, const float* maps, int n_maps, int h, int w, int elem_stride, const unsigned char* density,
+                              int Hd, int Wd, const unsigned char* fixation, int H, int W, const double* jitter, const int* borji_idx,
+                              const int* n_fix, int n_rep, double step_size, double* out, const p3d_postprocess* cfg,
+                              const p3d_hist_match* match);
+
 /* ---- Resident video inference (an ADDITION beside p3d_predict_windows: gen_pred.py slides a 16-frame queue by one frame and keeps
  * nothing on the device).  A video's normalised frames go up once, windows are cut where the frames are, and every frame's map is
  * kept on the device until it is read.  OFF until p3d_video_open: while no video is open every other entry point issues what it

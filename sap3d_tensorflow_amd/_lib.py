@@ -47,6 +47,15 @@ class P3dPostprocess(C.Structure):
 # p3d_set_postprocess normalisations (include/p3d_hip.h P3D_NORM_*)
 NORMS = {"none": 0, "max": 1, "range": 2}
 P3D_BLUR_MAX_RADIUS = 255
+
+
+class P3dHistMatch(C.Structure):
+    _fields_ = [("mode", C.c_int), ("nbins", C.c_int), ("nt", C.c_int), ("cdf", C.POINTER(C.c_double)), ("centres", C.POINTER(C.c_double))]
+
+
+# p3d_set_hist_match modes (include/p3d_hip.h P3D_MATCH_*)
+MATCH_MODES = {"off": 0, "table": 1, "density": 2}
+P3D_HIST_MAX_BINS = 1024
 # p3d_video_open modes (include/p3d_hip.h P3D_VIDEO_*)
 VIDEO_MODES = {"newest": 0, "mean": 1}
 
@@ -215,6 +224,16 @@ SIGNATURES = {
     "p3d_debug_eval_maps_post": (C.c_int, [C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ubyte), C.c_int, C.c_int,
                                            C.POINTER(C.c_ubyte), C.c_int, C.c_int, _dp, _ip, _ip, C.c_int, C.c_double, _dp,
                                            C.POINTER(P3dPostprocess)]),
+    "p3d_cumulative_distribution": (C.c_int, [C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _i64p, _dp, _dp]),
+    "p3d_match_hist": (C.c_int, [C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _fp]),
+    "p3d_match_hist_maps": (C.c_int, [C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    "p3d_set_hist_match": (C.c_int, [C.c_void_p, C.POINTER(P3dHistMatch)]),
+    "p3d_get_hist_match": (C.c_int, [C.c_void_p, C.POINTER(P3dHistMatch)]),
+    "p3d_postprocess_maps_match": (C.c_int, [C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(P3dPostprocess),
+                                             C.POINTER(P3dHistMatch), C.c_float, _fp, _u8p]),
+    "p3d_debug_eval_maps_match": (C.c_int, [C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ubyte), C.c_int, C.c_int,
+                                            C.POINTER(C.c_ubyte), C.c_int, C.c_int, _dp, _ip, _ip, C.c_int, C.c_double, _dp,
+                                            C.POINTER(P3dPostprocess), C.POINTER(P3dHistMatch)]),
     "p3d_video_open": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "p3d_video_close": (C.c_int, [C.c_void_p]),
     "p3d_video_info": (C.c_int, [C.c_void_p, _ip, _ip, _ip]),

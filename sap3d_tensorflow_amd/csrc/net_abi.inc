@@ -2421,17 +2421,46 @@ void post_carve(Carve& c, PostScratch& ps, const PostPlan& pl, int chunk, long l
     ps.part = pl.norm != P3D_NORM_NONE ? c.take<float>((size_t)chunk * p3d_post_blocks(N) * 2) : nullptr;
     ps.mnmx = pl.norm != P3D_NORM_NONE ? c.take<float>((size_t)chunk * 2) : nullptr;
 }
+// Device scratch of the histogram-matching stage (p3d_set_hist_match) for `chunk` maps of N pixels at a time
+using MatchPlan = p3d_handle::MatchCfg;
+struct MatchScratch {
+    float* part = nullptr; float* mnmx = nullptr; int* cnt = nullptr; double* cdf = nullptr; double* centre = nullptr; double* newv = nullptr;
+    double* tcdf = nullptr; double* tcentre = nullptr;      // TABLE: the uploaded table; DENSITY: the targets' tables [chunk][nb]
+    float* tpart = nullptr; float* tmnmx = nullptr;         // DENSITY: the targets' min / max
+};
+void match_carve(Carve& c, MatchScratch& ms, const MatchPlan& mp, int chunk, long long N) {
+    if (!mp.on()) return;
+    const size_t k = (size_t)chunk * mp.nb;
+    const bool dens = mp.mode == P3D_MATCH_DENSITY;
+    ms.part = c.take<float>((size_t)chunk * p3d_post_blocks(N) * 2);
+    ms.mnmx = c.take<float>((size_t)chunk * 2);
+    ms.cnt = c.take<int>(k);
+    ms.cdf = c.take<double>(k); ms.centre = c.take<double>(k); ms.newv = c.take<double>(k);
+    ms.tcdf = c.take<double>(dens ? k : mp.cdf.size());
+    ms.tcentre = c.take<double>(dens ? k : mp.centres.size());
+    ms.tpart = dens ? c.take<float>((size_t)chunk * p3d_post_blocks(N) * 2) : nullptr;
+    ms.tmnmx = dens ? c.take<float>((size_t)chunk * 2) : nullptr;
+}
 // n maps of one source: map m's pixel (y, x) at p[m * map_stride + (y * w + x) * elem_stride] (device memory)
 struct PostRun { const float* p; long long map_stride; int elem_stride, n; };
 // resize -> blur -> normalise (-> quantise) of `total` maps on stream s, at most `chunk` maps per pass through the stages.
 // runs: the sources, resized (float32) to H x W -- their n add up to total; empty: f32 already holds the maps.  f32 [total][H][W]
 // (device) receives the float32 result, or null: the maps pass through ps.maps.  u8 (device, 4-byte aligned) or null: map k's
 // bytes at u8_off + k * H * W.  counters: `chunk` zeroed arrival counters.  Queues only (after one synchronising upload of the taps).
+// mp / ms: p3d_set_hist_match's stage between the blur and the normalisation (null or off: not issued); density [total][H][W]
+// (device): under P3D_MATCH_DENSITY map k's target, evaluation's float32(b / 255.) density.
 void post_sequence(hipStream_t s, const std::vector<PostRun>& runs, int total, int h, int w, int H, int W, const PostPlan& pl,
-                   const PostScratch& ps, unsigned* counters, int chunk, float* f32, unsigned char* u8, long long u8_off, float scale) {
+                   const PostScratch& ps, unsigned* counters, int chunk, float* f32, unsigned char* u8, long long u8_off, float scale,
+                   const MatchPlan* mp = nullptr, const MatchScratch* ms = nullptr, const float* density = nullptr) {
     pl.fits(H, W);
     const long long N = (long long)H * W;
     if (pl.r > 0) HIPCHECK(copy_now(ps.taps, pl.taps.data(), pl.taps.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    const bool match = mp && mp->on();
+    if (match && mp->mode == P3D_MATCH_DENSITY && !density) throw P3dError("hist_match: P3D_MATCH_DENSITY needs a ground-truth density (evaluation only)");
+    if (match && mp->mode == P3D_MATCH_TABLE) {
+        HIPCHECK(copy_now(ms->tcdf, mp->cdf.data(), mp->cdf.size() * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHECK(copy_now(ms->tcentre, mp->centres.data(), mp->centres.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    }
     size_t ri = 0;
     int rdone = 0;
     for (int done = 0; done < total; done += chunk) {
@@ -2451,6 +2480,22 @@ void post_sequence(hipStream_t s, const std::vector<PostRun>& runs, int total, i
         a.n = cn; a.H = H; a.W = W; a.maps = maps; a.tmp = ps.tmp; a.taps = ps.taps; a.r = pl.r; a.norm = pl.norm;
         a.part = ps.part; a.mnmx = ps.mnmx; a.counter = counters; a.nblk = p3d_post_blocks(N);
         a.u8 = u8; a.u8_off = u8_off + (long long)done * N; a.scale = scale;
+        HistChain hc;
+        if (match) {
+            HistArgs& q = hc.source;           // (its maps are a's: p3d_post_launch fills them in)
+            q.nb = mp->nb; q.part = ms->part; q.mnmx = ms->mnmx; q.counter = counters; q.nblk = p3d_post_blocks(N);
+            q.cnt = ms->cnt; q.cdf = ms->cdf; q.centre = ms->centre; q.newv = ms->newv; q.tcdf = ms->tcdf; q.tcentre = ms->tcentre;
+            q.nt = mp->mode == P3D_MATCH_DENSITY ? mp->nb : (int)mp->cdf.size();
+            q.t_stride = mp->mode == P3D_MATCH_DENSITY ? mp->nb : 0;
+            if (mp->mode == P3D_MATCH_DENSITY) {
+                HistArgs& t = hc.target;
+                hc.has_target = true;
+                t.maps = density + (size_t)done * N; t.kind = HIST_DENSITY; t.n = cn; t.H = H; t.W = W; t.nb = mp->nb;
+                t.part = ms->tpart; t.mnmx = ms->tmnmx; t.counter = counters; t.nblk = q.nblk;
+                t.cnt = ms->cnt; t.cdf = ms->tcdf; t.centre = ms->tcentre;      // (the integer tables are zeroed before every count)
+            }
+            a.match = &hc;
+        }
         for (int st = POST_BLUR_H; st < POST_STAGES; ++st) HIPCHECK(p3d_post_launch(st, a, s));
     }
 }
@@ -2463,8 +2508,10 @@ struct EvalSource { const float* p; long long map_stride; int elem_stride, n_map
 // the source maps readable; it runs after the uploads, inside the metric stage's time.
 void eval_maps(hipStream_t s, const EvalSource& src, const std::function<void(hipStream_t)>& prepare, const unsigned char* density, int Hd, int Wd, const unsigned char* fixation, int H,
                int W, const double* jitter, const int* borji_idx, const int* n_fix, int n_rep, double step_size, double* out,
-               double* stage_ms, const p3d_postprocess* post = nullptr) {
+               double* stage_ms, const p3d_postprocess* post = nullptr, const MatchPlan* matchp = nullptr) {
     const PostPlan plan(post);                 // p3d_set_postprocess: between the resize and the metrics, in place on P
+    const MatchPlan match = matchp ? *matchp : MatchPlan();      // p3d_set_hist_match: after the blur, before the normalisation
+    const bool chain = plan.on || match.on();
     if (!src.p || !density || !fixation || !n_fix || !out) throw P3dError("null argument");
     if (Hd < 1 || Wd < 1 || H < 1 || W < 1) throw P3dError("eval: empty map");
     if ((long long)H * W > INT32_MAX / 2) throw P3dError("eval: map too large");
@@ -2485,6 +2532,7 @@ void eval_maps(hipStream_t s, const EvalSource& src, const std::function<void(hi
     double *jit = nullptr, *dout = nullptr;
     int* idx = nullptr;
     PostScratch post_scratch;
+    MatchScratch match_scratch;
     const int post_chunk = std::min(B, P3D_POST_CHUNK);
     auto layout = [&](Carve& c) {
         P = c.take<float>((size_t)B * N);
@@ -2496,6 +2544,7 @@ void eval_maps(hipStream_t s, const EvalSource& src, const std::function<void(hi
         dout = c.take<double>((size_t)B * 5);
         carve_full(c, a, r, meta);
         if (plan.on) post_carve(c, post_scratch, plan, post_chunk, N, false);
+        match_carve(c, match_scratch, match, post_chunk, N);
     };
     Carve c;
     layout(c);                                 // sizes the scratch
@@ -2517,12 +2566,14 @@ void eval_maps(hipStream_t s, const EvalSource& src, const std::function<void(hi
     HIPCHECK(copy_now((void*)a.meta, meta.data(), meta.size() * sizeof(int), hipMemcpyHostToDevice, s));
     if (stage_ms) HIPCHECK(hipEventRecord(ev[1], s));
     if (prepare) prepare(s);
-    if (plan.on)
+    const bool density_first = match.mode == P3D_MATCH_DENSITY;              // the stage reads D: the same launch, issued earlier
+    if (density_first) HIPCHECK(p3d_mapf_density(dens, B, Hd, Wd, D, H, W, s));
+    if (chain)
         post_sequence(s, {{src.p, src.map_stride, src.elem_stride, B}}, B, src.h, src.w, H, W, plan, post_scratch, counters, post_chunk, P,
-                      nullptr, 0, 0.f);
+                      nullptr, 0, 0.f, &match, &match_scratch, D);
     else
         HIPCHECK(p3d_resize_f32(src.p, src.map_stride, src.elem_stride, B, src.h, src.w, P, H, W, s));
-    HIPCHECK(p3d_mapf_density(dens, B, Hd, Wd, D, H, W, s));                  // test.py's density: uint8 resize (dataflow.py:236-238)
+    if (!density_first) HIPCHECK(p3d_mapf_density(dens, B, Hd, Wd, D, H, W, s));      // test.py's density: uint8 resize (dataflow.py:236-238)
     HIPCHECK(p3d_full_moments(a, s));
     HIPCHECK(p3d_full_rank(a, s));
     HIPCHECK(p3d_full_borji(a, r, s));
@@ -2610,7 +2661,7 @@ int p3d_eval_last_frames(p3d_handle* h, const unsigned char* density, int Hd, in
     if (pr->materialize && h->last_forward_fused) prepare = pr->materialize;
     eval_maps(h->stream, {pr->p + (size_t)(T - 1) * hw * pr->ld, (long long)T * hw * pr->ld, pr->ld, pr->N, pr->H, pr->W}, prepare,
               density, Hd, Wd, fixation, H, W, jitter, borji_idx, n_fix, n_rep, step_size, out, stage_ms,
-              h->post_on ? &h->post_cfg : nullptr);
+              h->post_on ? &h->post_cfg : nullptr, h->match_cfg.on() ? &h->match_cfg : nullptr);
     API_END
 }
 
@@ -2637,6 +2688,21 @@ int p3d_debug_eval_maps_post(int device, const float* maps, int n_maps, int h, i
     DevArr<float> src((size_t)n_maps * per_map, maps);
     eval_maps(nullptr, {src.p, per_map, elem_stride, n_maps, h, w}, nullptr, density, Hd, Wd, fixation, H, W, jitter, borji_idx, n_fix, n_rep,
               step_size, out, nullptr, cfg);
+    API_END
+}
+
+int p3d_debug_eval_maps_match(int device, const float* maps, int n_maps, int h, int w, int elem_stride, const unsigned char* density,
+                              int Hd, int Wd, const unsigned char* fixation, int H, int W, const double* jitter, const int* borji_idx,
+                              const int* n_fix, int n_rep, double step_size, double* out, const p3d_postprocess* cfg,
+                              const p3d_hist_match* match) {
+    API_BEGIN
+    const MatchPlan mp = p3d_handle::match_parse(match);
+    metric_args(device, maps, maps, n_maps, 1, out);
+    if (h < 1 || w < 1 || elem_stride < 1) throw P3dError("eval: empty map");
+    const long long per_map = (long long)h * w * elem_stride;
+    DevArr<float> src((size_t)n_maps * per_map, maps);
+    eval_maps(nullptr, {src.p, per_map, elem_stride, n_maps, h, w}, nullptr, density, Hd, Wd, fixation, H, W, jitter, borji_idx, n_fix, n_rep,
+              step_size, out, nullptr, cfg, &mp);
     API_END
 }
 
@@ -2669,16 +2735,24 @@ void maps_u8_chain(p3d_handle* h, long long maps, int ph, int pw, float scale, i
     // follows the bytes in the slab.  Off: the double-precision resize below, as before.
     const PostPlan plan(h->post_on ? &h->post_cfg : nullptr);
     if (plan.on) plan.fits(H, W);
+    // p3d_set_hist_match: a table takes the same float32 chain, with its stage after the blur; the density mode has no target here
+    const MatchPlan& match = h->match_cfg;
+    if (match.mode == P3D_MATCH_DENSITY)
+        throw P3dError("hist_match: P3D_MATCH_DENSITY matches to a ground-truth density and runs in p3d_eval_last_frames only; written maps take P3D_MATCH_TABLE");
+    const bool chain = plan.on || match.on();
     const int post_chunk = (int)std::min<long long>(maps, P3D_POST_CHUNK);
     PostScratch post_scratch;
+    MatchScratch match_scratch;
     Carve c;
     c.take<unsigned char>((size_t)bytes);
-    if (plan.on) post_carve(c, post_scratch, plan, post_chunk, hw, true);
+    if (chain) post_carve(c, post_scratch, plan, post_chunk, hw, true);
+    match_carve(c, match_scratch, match, post_chunk, hw);
     if (extra) c.take<float>(extra);
-    HIPCHECK(p3d_stream_scratch(s, plan.on || extra ? (c.off + 3) / 4 : (size_t)(bytes + 3) / 4, plan.on ? (size_t)post_chunk : 0, &slab, &counters));
+    HIPCHECK(p3d_stream_scratch(s, chain || extra ? (c.off + 3) / 4 : (size_t)(bytes + 3) / 4, chain ? (size_t)post_chunk : 0, &slab, &counters));
     c = Carve{(char*)slab, 0};
     unsigned char* d = c.take<unsigned char>((size_t)bytes);
-    if (plan.on) post_carve(c, post_scratch, plan, post_chunk, hw, true);
+    if (chain) post_carve(c, post_scratch, plan, post_chunk, hw, true);
+    match_carve(c, match_scratch, match, post_chunk, hw);
     float* ex = extra ? c.take<float>(extra) : nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     if (stage_ms)
@@ -2686,7 +2760,7 @@ void maps_u8_chain(p3d_handle* h, long long maps, int ph, int pw, float scale, i
     if (stage_ms) HIPCHECK(hipEventRecord(ev[0], s));
     std::vector<PostRun> runs;
     sources(s, ex, runs);
-    if (plan.on) post_sequence(s, runs, (int)maps, ph, pw, H, W, plan, post_scratch, counters, post_chunk, nullptr, d, 0, scale);
+    if (chain) post_sequence(s, runs, (int)maps, ph, pw, H, W, plan, post_scratch, counters, post_chunk, nullptr, d, 0, scale, &match, &match_scratch);
     else {
         long long off = 0;
         for (const PostRun& r : runs) {
@@ -2800,10 +2874,13 @@ int p3d_gaussian_blur(int device, const float* src, int n, int H, int W, float s
     API_END
 }
 
-int p3d_postprocess_maps(int device, const float* maps, int n, int h, int w, int elem_stride, int H, int W,
-                         const p3d_postprocess* cfg, float scale, float* out_f32, unsigned char* out_u8) {
-    API_BEGIN
+}  // extern "C"
+namespace {
+void postprocess_maps(int device, const float* maps, int n, int h, int w, int elem_stride, int H, int W, const p3d_postprocess* cfg,
+                      const p3d_hist_match* match, float scale, float* out_f32, unsigned char* out_u8) {
     const PostPlan plan(cfg);
+    const MatchPlan mp = p3d_handle::match_parse(match);
+    if (mp.mode == P3D_MATCH_DENSITY) throw P3dError("hist_match: P3D_MATCH_DENSITY runs in evaluation only; supplied maps take P3D_MATCH_TABLE");
     metric_args(device, maps, maps, 1, 1, maps);
     if (n < 1 || h < 1 || w < 1 || elem_stride < 1 || H < 1 || W < 1) throw P3dError("postprocess_maps: empty map");
     if ((long long)H * W > INT32_MAX) throw P3dError("postprocess_maps: H * W exceeds the kernels' int32 in-map offsets");
@@ -2817,16 +2894,19 @@ int p3d_postprocess_maps(int device, const float* maps, int n, int h, int w, int
     const std::vector<uint32_t> fg((size_t)(out_f32 ? ne + 2 * fat : 1), guard), bg((size_t)(out_u8 ? bwords : 1), guard);
     DevArr<uint32_t> fbuf(fg.size(), fg.data()), bbuf(bg.size(), bg.data());
     PostScratch ps;
+    MatchScratch ms;
     Carve c;
     post_carve(c, ps, plan, chunk, N, !out_f32);
+    match_carve(c, ms, mp, chunk, N);
     float* slab = nullptr;
     unsigned* counters = nullptr;
     HIPCHECK(p3d_stream_scratch(nullptr, (c.off + 3) / 4, (size_t)chunk, &slab, &counters));
     c = Carve{(char*)slab, 0};
     post_carve(c, ps, plan, chunk, N, !out_f32);
+    match_carve(c, ms, mp, chunk, N);
     post_sequence(nullptr, {{src.p, per_map, elem_stride, n}}, n, h, w, H, W, plan, ps, counters, chunk,
                   out_f32 ? reinterpret_cast<float*>(fbuf.p) + fat : nullptr, out_u8 ? reinterpret_cast<unsigned char*>(bbuf.p) : nullptr, bat,
-                  scale);
+                  scale, &mp, &ms);
     if (out_f32) {
         std::vector<uint32_t> back(fg.size());
         fbuf.get(back.data(), back.size());
@@ -2844,6 +2924,115 @@ int p3d_postprocess_maps(int device, const float* maps, int n, int h, int w, int
         memcpy(out_u8, got + bat, (size_t)ne);
     }
     if (!out_f32 && !out_u8) HIPCHECK(hipDeviceSynchronize());
+}
+
+// Device buffers of one op-level launch sequence of hist_match.hip on n maps (no stream scratch: private allocations)
+struct HistBufs {
+    DevArr<float> part, mnmx; DevArr<unsigned> counter; DevArr<int> cnt; DevArr<long long> counts; DevArr<double> cdf, centre, newv;
+    static std::vector<unsigned> zeros(int n) { return std::vector<unsigned>((size_t)n, 0u); }
+    HistBufs(int n, long long N, int nb)
+        : part((size_t)n * p3d_post_blocks(N) * 2), mnmx((size_t)n * 2), counter((size_t)n, zeros(n).data()), cnt((size_t)n * nb),
+          counts((size_t)n * nb), cdf((size_t)n * nb), centre((size_t)n * nb), newv((size_t)n * nb) {}
+    HistArgs args(const float* maps, int n, int H, int W, int nb) {
+        HistArgs a;
+        a.maps = maps; a.n = n; a.H = H; a.W = W; a.nb = nb; a.part = part.p; a.mnmx = mnmx.p; a.counter = counter.p;
+        a.nblk = p3d_post_blocks((long long)H * W); a.cnt = cnt.p; a.counts = counts.p; a.cdf = cdf.p; a.centre = centre.p; a.newv = newv.p;
+        return a;
+    }
+};
+void hist_shape(const char* what, const void* maps, const void* out, int n, int H, int W, int nbins) {
+    p3d_handle::match_bins(what, nbins);
+    if (!maps || !out) throw P3dError(std::string(what) + ": null argument");
+    if (n < 1 || n > 65535 || H < 1 || W < 1) throw P3dError(std::string(what) + ": 1 .. 65535 maps of at least one pixel");
+    if ((long long)H * W > INT32_MAX) throw P3dError(std::string(what) + ": H * W exceeds the kernels' int32 in-map offsets");
+}
+}  // namespace
+extern "C" {
+
+int p3d_postprocess_maps(int device, const float* maps, int n, int h, int w, int elem_stride, int H, int W,
+                         const p3d_postprocess* cfg, float scale, float* out_f32, unsigned char* out_u8) {
+    API_BEGIN
+    postprocess_maps(device, maps, n, h, w, elem_stride, H, W, cfg, nullptr, scale, out_f32, out_u8);
+    API_END
+}
+
+int p3d_postprocess_maps_match(int device, const float* maps, int n, int h, int w, int elem_stride, int H, int W,
+                               const p3d_postprocess* cfg, const p3d_hist_match* match, float scale, float* out_f32, unsigned char* out_u8) {
+    API_BEGIN
+    postprocess_maps(device, maps, n, h, w, elem_stride, H, W, cfg, match, scale, out_f32, out_u8);
+    API_END
+}
+
+// ---- p3d_set_hist_match and the op-level entry points of its stage (hist_match.hip) ------------------------------------------
+int p3d_set_hist_match(p3d_handle* h, const p3d_hist_match* cfg) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    h->set_hist_match(cfg);
+    API_END
+}
+
+int p3d_get_hist_match(p3d_handle* h, p3d_hist_match* cfg) {
+    API_BEGIN
+    if (!h || !cfg) throw P3dError("null argument");
+    const p3d_handle::MatchCfg& m = h->match_cfg;
+    cfg->mode = m.mode; cfg->nbins = m.on() ? m.nb : 0; cfg->nt = (int)m.cdf.size();
+    cfg->cdf = m.cdf.empty() ? nullptr : m.cdf.data();
+    cfg->centres = m.centres.empty() ? nullptr : m.centres.data();
+    API_END
+}
+
+int p3d_cumulative_distribution(int device, const float* maps, int n, int H, int W, int nbins, int64_t* counts, double* cdf, double* centres) {
+    API_BEGIN
+    hist_shape("cumulative_distribution", maps, cdf, n, H, W, nbins);
+    if (!centres) throw P3dError("cumulative_distribution: null argument");
+    metric_args(device, maps, maps, 1, 1, cdf);
+    const long long N = (long long)H * W;
+    DevArr<float> src((size_t)n * N, maps);
+    HistBufs b(n, N, nbins);
+    const HistArgs a = b.args(src.p, n, H, W, nbins);
+    for (int st = 0; st < HIST_STAGES; ++st) HIPCHECK(p3d_hist_launch(st, a, nullptr));
+    b.cdf.get(cdf, (size_t)n * nbins);
+    b.centre.get(centres, (size_t)n * nbins);
+    if (counts) {
+        static_assert(sizeof(long long) == sizeof(int64_t), "counts are int64");
+        b.counts.get(reinterpret_cast<long long*>(counts), (size_t)n * nbins);
+    }
+    API_END
+}
+
+int p3d_match_hist(int device, const float* maps, int n, int H, int W, int nbins, const double* cdf_t, const double* centre_t, int n_tables,
+                   int nt, float* out) {
+    API_BEGIN
+    hist_shape("match_hist", maps, out, n, H, W, nbins);
+    if (n_tables != 1 && n_tables != n) throw P3dError("match_hist: one table, or one per map");
+    p3d_handle::match_table("match_hist", cdf_t, centre_t, nt, n_tables);
+    metric_args(device, maps, maps, 1, 1, out);
+    const long long N = (long long)H * W;
+    DevArr<float> src((size_t)n * N, maps), dst((size_t)n * N);
+    DevArr<double> tc((size_t)n_tables * nt, cdf_t), tx((size_t)n_tables * nt, centre_t);
+    HistBufs b(n, N, nbins);
+    HistArgs a = b.args(src.p, n, H, W, nbins);
+    a.tcdf = tc.p; a.tcentre = tx.p; a.nt = nt; a.t_stride = n_tables == 1 ? 0 : nt; a.out = dst.p;
+    for (int st = 0; st < HIST_STAGES; ++st) HIPCHECK(p3d_hist_launch(st, a, nullptr));
+    dst.get(out, (size_t)n * N);
+    API_END
+}
+
+int p3d_match_hist_maps(int device, const float* maps, const float* targets, int n, int H, int W, int nbins, float* out) {
+    API_BEGIN
+    hist_shape("match_hist_maps", maps, out, n, H, W, nbins);
+    if (!targets) throw P3dError("match_hist_maps: null argument");
+    metric_args(device, maps, maps, 1, 1, out);
+    const long long N = (long long)H * W;
+    DevArr<float> src((size_t)n * N, maps), tgt((size_t)n * N, targets), dst((size_t)n * N);
+    HistBufs bt(n, N, nbins), bs(n, N, nbins);
+    HistChain c;
+    c.has_target = true;
+    c.target = bt.args(tgt.p, n, H, W, nbins);
+    c.source = bs.args(src.p, n, H, W, nbins);
+    c.source.tcdf = bt.cdf.p; c.source.tcentre = bt.centre.p; c.source.nt = nbins; c.source.t_stride = nbins; c.source.out = dst.p;
+    HIPCHECK(p3d_hist_chain_launch(c, nullptr));
+    dst.get(out, (size_t)n * N);
     API_END
 }
 

@@ -551,6 +551,49 @@
         post_cfg = post_on ? want : neutral;
     }
 
+    // ---- histogram matching of output maps (p3d_set_hist_match; hist_match.hip) ---------------------------
+    // Off by default, and off nothing here runs.  The setting is a mode, a bin count and (P3D_MATCH_TABLE) a copy of the caller's
+    // table; the stage is issued by post_sequence (net_abi.inc) between the blur and the normalisation, with scratch from the
+    // stream pool at first use.  No step, launch list or captured graph ever names it.
+    struct MatchCfg {
+        int mode = P3D_MATCH_OFF, nb = 256;
+        std::vector<double> cdf, centres;      // P3D_MATCH_TABLE: nt entries each
+        bool on() const { return mode != P3D_MATCH_OFF; }
+    };
+    MatchCfg match_cfg;
+    static void match_bins(const char* what, int nb) {
+        if (nb < 2 || nb > P3D_HIST_MAX_BINS)
+            throw P3dError(std::string(what) + ": nbins must be in [2, " + std::to_string(P3D_HIST_MAX_BINS) + "], not " + std::to_string(nb));
+    }
+    // a supplied table as the header asks for it: 2 <= nt <= P3D_HIST_MAX_BINS, finite, non-decreasing (n_tables of them)
+    static void match_table(const char* what, const double* cdf, const double* centres, int nt, int n_tables = 1) {
+        if (nt < 2 || nt > P3D_HIST_MAX_BINS)
+            throw P3dError(std::string(what) + ": nt must be in [2, " + std::to_string(P3D_HIST_MAX_BINS) + "], not " + std::to_string(nt));
+        if (!cdf || !centres) throw P3dError(std::string(what) + ": a table needs cdf and centres");
+        for (int t = 0; t < n_tables; ++t)
+            for (int k = 0; k < nt; ++k) {
+                const double *a = cdf + (size_t)t * nt, *b = centres + (size_t)t * nt;
+                if (!std::isfinite(a[k]) || !std::isfinite(b[k])) throw P3dError(std::string(what) + ": the table must be finite (entry " + std::to_string(k) + ")");
+                if (k > 0 && (a[k] < a[k - 1] || b[k] < b[k - 1]))
+                    throw P3dError(std::string(what) + ": the table must be non-decreasing (entry " + std::to_string(k) + ")");
+            }
+    }
+    // what a p3d_hist_match asks for; throws on a setting the header refuses
+    static MatchCfg match_parse(const p3d_hist_match* c) {
+        MatchCfg m;
+        if (!c || c->mode == P3D_MATCH_OFF) return m;
+        if (c->mode != P3D_MATCH_TABLE && c->mode != P3D_MATCH_DENSITY) throw P3dError("hist_match: unknown mode " + std::to_string(c->mode));
+        match_bins("hist_match", c->nbins);
+        m.mode = c->mode; m.nb = c->nbins;
+        if (c->mode == P3D_MATCH_TABLE) {
+            match_table("hist_match", c->cdf, c->centres, c->nt);
+            m.cdf.assign(c->cdf, c->cdf + c->nt);
+            m.centres.assign(c->centres, c->centres + c->nt);
+        }
+        return m;
+    }
+    void set_hist_match(const p3d_hist_match* c) { match_cfg = match_parse(c); }      // (parsed first: a refusal changes nothing)
+
     // ---- resident video inference (p3d_video_*; video.hip) ---------------------------------------------
     // Nothing exists before the first p3d_video_open and nothing here runs while no video is open.  The stores are private
     // allocations (freed by p3d_video_close, not part of `allocs`): no step, launch list or captured graph names them.  The gather

@@ -783,6 +783,7 @@ hipError_t p3d_full_borji(const P3dFullMaps& a, const P3dFullBorji& r, hipStream
 // One launch sequence on n maps of H x W floats, every stage optional:
 //   POST_RESIZE  src given: resize_f32_kernel's float32 cv2.INTER_LINEAR law, src [n] maps of h x w -> maps;
 //   POST_BLUR_H  r > 0: the horizontal pass, maps -> tmp;      POST_BLUR_V  r > 0: the vertical pass, tmp -> maps;
+//   POST_MATCH   match given: histogram matching of every map, in place (hist_match.hip: p3d_hist_chain_launch on *match);
 //   POST_MINMAX  norm != 0: float32 min and max of every map -> mnmx[n][2], partials folded by the last arriving block;
 //   POST_APPLY   norm != 0 or u8 given: v' by `norm` stored back to maps, and sat_u8((double)fmul(v', scale)) to byte u8_off + i of
 //                u8 when given (u8 4-byte aligned, u8_off arbitrary: whole words where aligned, as resize_u8_kernel).
@@ -791,7 +792,8 @@ hipError_t p3d_full_borji(const P3dFullMaps& a, const P3dFullBorji& r, hipStream
 // r outside [0, P3D_POST_MAX_RADIUS] or above min(H, W) - 1, H * W above INT32_MAX, n above 65535, a missing buffer.
 constexpr int P3D_POST_MAX_RADIUS = 255;
 constexpr int P3D_POST_CHUNK = 16;            // maps per launch sequence of the chunked callers (scratch: 2 * 16 maps)
-enum { POST_RESIZE = 0, POST_BLUR_H = 1, POST_BLUR_V = 2, POST_MINMAX = 3, POST_APPLY = 4, POST_STAGES = 5 };
+enum { POST_RESIZE = 0, POST_BLUR_H = 1, POST_BLUR_V = 2, POST_MATCH = 3, POST_MINMAX = 4, POST_APPLY = 5, POST_STAGES = 6 };
+struct HistChain;
 struct PostArgs {
     const float* src = nullptr; long long map_stride = 0; int elem_stride = 1, h = 0, w = 0;      // src null: no POST_RESIZE
     int n = 0, H = 0, W = 0;
@@ -804,6 +806,7 @@ struct PostArgs {
     unsigned* counter = nullptr;              // [n] arrival counters, zero at launch (and after), norm != 0
     int nblk = 0;                             // p3d_post_blocks(H * W)
     unsigned char* u8 = nullptr; long long u8_off = 0; float scale = 0.f;
+    const HistChain* match = nullptr;         // POST_MATCH: its source is these n maps, remapped in place
 };
 // the vertical pass's strip for radius r: cols columns x rows output rows per block, (rows + 2r) x cols floats + r + 1 taps of LDS
 struct PostStrip { int cols, rows, lds_bytes; };
@@ -812,6 +815,40 @@ int p3d_post_blocks(long long n_pix);
 bool p3d_post_has(int stage, const PostArgs& a);
 LaunchDesc p3d_post_desc(int stage, const PostArgs& a);
 hipError_t p3d_post_launch(int stage, const PostArgs& a, hipStream_t s);      // a stage the arguments do not ask for: nothing, success
+
+// ---- histogram matching of output maps (hist_match.hip; p3d_set_hist_match / p3d_match_hist, the law in include/p3d_hip.h) ----
+// One launch sequence on n maps of H x W floats:
+//   HIST_MINMAX  minmax_kernel of postprocess.hip -> mnmx[n][2] (this stage's own buffers: POST_MINMAX's are not touched);
+//   HIST_COUNT   the tables cnt[n][nb] zeroed in stream order, then hist_count_kernel<kind>: counts (and counts[n][nb] as
+//                int64 when given), centre[n][nb], cdf[n][nb]; with tcdf / tcentre (map m's target table of nt entries at
+//                m * t_stride; t_stride 0: one table for all) also newv[n][nb] = interp(cdf, tcdf, tcentre);
+//   HIST_REMAP   out given: out = (float)interp((double)v, centre, newv) per pixel; out may be maps.
+// kind HIST_DENSITY: maps are evaluation's density maps, float32(b / 255.) of bytes b, counted as the doubles b / 255..
+// Refused (hipErrorInvalidValue) before anything is launched: nb or nt outside [2, P3D_HIST_BINS_CAP], H * W above INT32_MAX, n
+// above 65535, a missing buffer, a remap without a target table or of density maps.
+constexpr int P3D_HIST_BINS_CAP = 1024;
+enum { HIST_MINMAX = 0, HIST_COUNT = 1, HIST_REMAP = 2, HIST_STAGES = 3 };
+enum { HIST_F32 = 0, HIST_DENSITY = 1 };
+struct HistArgs {
+    const float* maps = nullptr;              // [n][H][W]
+    int kind = HIST_F32, n = 0, H = 0, W = 0, nb = 0;
+    float* part = nullptr;                    // [n][nblk][2]
+    float* mnmx = nullptr;                    // [n][2]
+    unsigned* counter = nullptr;              // [n] arrival counters, zero at launch (and after)
+    int nblk = 0;                             // p3d_post_blocks(H * W)
+    int* cnt = nullptr;                       // [n][nb] the integer tables
+    long long* counts = nullptr;              // [n][nb] or null
+    double* cdf = nullptr; double* centre = nullptr;      // [n][nb]
+    const double* tcdf = nullptr; const double* tcentre = nullptr; int nt = 0; long long t_stride = 0;
+    double* newv = nullptr;                   // [n][nb], with a target table
+    float* out = nullptr;                     // [n][H][W] or null: no HIST_REMAP
+};
+// match `source` against the table of `target` (has_target: built first, by HIST_MINMAX and HIST_COUNT on it) or a supplied one
+struct HistChain { bool has_target = false; HistArgs target, source; };
+bool p3d_hist_has(int stage, const HistArgs& a);
+LaunchDesc p3d_hist_desc(int stage, const HistArgs& a);
+hipError_t p3d_hist_launch(int stage, const HistArgs& a, hipStream_t s);         // a stage the arguments do not ask for: nothing, success
+hipError_t p3d_hist_chain_launch(const HistChain& c, hipStream_t s);
 
 // ---- misc ---------------------------------------------------------------------------------------
 hipError_t p3d_add_inplace(float* dst, int lddst, const float* src, int ldsrc, long M, int C, hipStream_t s);

@@ -10,6 +10,7 @@
 //  one lane, one order, every operation rounded on its own -- the result does not depend on the tiling, the grid or alignment.
 //  * minmax_kernel: float32 min / max of every map, split over nblk blocks; det_reduce.h's write-through partials and
 //    last-arriver fold (min and max do not depend on the order; no floating-point atomics).
+//  * POST_MATCH, between the blur and the normalisation: hist_match.hip's launch sequence, when asked for.
 //  * apply_kernel: v / mx, or (v - mn) / (mx - mn), correctly rounded, stored back; bytes when asked, whole words where aligned.
 #include "p3d_kernels.h"
 #include "det_reduce.h"
@@ -185,6 +186,7 @@ bool p3d_post_has(int stage, const PostArgs& a) {
     switch (stage) {
         case POST_RESIZE: return a.src != nullptr;
         case POST_BLUR_H: case POST_BLUR_V: return a.r > 0;
+        case POST_MATCH: return a.match != nullptr;
         case POST_MINMAX: return a.norm != P3D_NORM_NONE;
         case POST_APPLY: return a.norm != P3D_NORM_NONE || a.u8 != nullptr;
         default: return false;
@@ -197,6 +199,7 @@ LaunchDesc p3d_post_desc(int stage, const PostArgs& a) {
         case POST_RESIZE: return {"resize_f32_kernel", e * 9.0, e * 8.0};
         case POST_BLUR_H: return {"blur_h_kernel", e * (1.5 * t + 0.5), e * 8.0};      // r + 1 products, 2r sums; one read, one write
         case POST_BLUR_V: return {"blur_v_kernel", e * (1.5 * t + 0.5), e * 8.0};
+        case POST_MATCH: return {"hist_count_kernel+hist_remap_kernel", e * 14.0, e * 16.0};      // min / max, count, remap: hist_match.hip
         case POST_MINMAX: return {"minmax_kernel", e * 2.0, e * 4.0};
         default: return {"apply_kernel", e * 3.0, e * (a.norm != P3D_NORM_NONE ? 8.0 : 4.0) + (a.u8 ? e : 0.0)};
     }
@@ -217,6 +220,11 @@ hipError_t p3d_post_launch(int stage, const PostArgs& a, hipStream_t s) {
             hipLaunchKernelGGL(blur_v_kernel, dim3((a.W + st.cols - 1) / st.cols, (a.H + st.rows - 1) / st.rows, a.n), dim3(TPB),
                                (size_t)st.lds_bytes, s, a.tmp, a.maps, a.taps, a.r, a.H, a.W, st.cols, st.rows);
             break;
+        }
+        case POST_MATCH: {
+            HistChain c = *a.match;                        // the source: these maps, remapped in place
+            c.source.maps = a.maps; c.source.out = a.maps; c.source.n = a.n; c.source.H = a.H; c.source.W = a.W;
+            return p3d_hist_chain_launch(c, s);
         }
         case POST_MINMAX:
             hipLaunchKernelGGL(minmax_kernel, dim3(a.nblk, a.n), dim3(TPB), 0, s, a.maps, n_pix, a.nblk, a.part, a.counter, a.mnmx);

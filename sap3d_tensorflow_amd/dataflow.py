@@ -114,11 +114,100 @@ def gaussian_blur(maps, sigma, radius=0, device=0):
     return out[0] if single else out
 
 
-def postprocess_maps(maps, size, sigma=0., radius=0, norm="none", scale=None, device=0):
+def _match_cfg(hist_match, nbins=256):
+    """(P3dHistMatch, the arrays it points to) of what P3DSession.set_hist_match takes: None / "off", "density", or a table
+    (cdf, bin_centers) of float64 [nt] each."""
+    from . import _lib
+    if hist_match is None or (isinstance(hist_match, str) and hist_match == "off"):
+        return _lib.P3dHistMatch(_lib.MATCH_MODES["off"], int(nbins), 0, None, None), ()
+    if isinstance(hist_match, str):
+        if hist_match != "density":
+            raise ValueError("hist_match %r: 'off', 'density' or a table (cdf, bin_centers)" % (hist_match,))
+        return _lib.P3dHistMatch(_lib.MATCH_MODES["density"], int(nbins), 0, None, None), ()
+    cdf, centres = hist_match
+    cdf = np.ascontiguousarray(cdf, dtype=np.float64)
+    centres = np.ascontiguousarray(centres, dtype=np.float64)
+    if cdf.ndim != 1 or cdf.shape != centres.shape:
+        raise ValueError("a table is (cdf, bin_centers), float64 [nt] each")
+    dp = C.POINTER(C.c_double)
+    return _lib.P3dHistMatch(_lib.MATCH_MODES["table"], int(nbins), cdf.size, cdf.ctypes.data_as(dp), centres.ctypes.data_as(dp)), (cdf, centres)
+
+
+def load_match_table(path):
+    """(cdf, bin_centers), float64 [nt] each, of an .npz that holds `cdf` and `bin_centers` (the --match-hist FILE of the drivers);
+    one map's cumulative_distribution output, or tables pooled over a dataset on the host."""
+    with np.load(path) as d:
+        if "cdf" not in d or "bin_centers" not in d:
+            raise ValueError("%s: a match table holds `cdf` and `bin_centers`" % path)
+        cdf, centres = np.asarray(d["cdf"], np.float64), np.asarray(d["bin_centers"], np.float64)
+    if cdf.ndim != 1 or cdf.shape != centres.shape or cdf.size < 2:
+        raise ValueError("%s: cdf and bin_centers are float64 [nt] each, nt >= 2" % path)
+    return cdf, centres
+
+
+def _maps3(maps):
+    m = np.ascontiguousarray(maps, dtype=np.float32)
+    single = m.ndim == 2
+    if single:
+        m = m[None]
+    if m.ndim != 3 or m.size == 0:
+        raise ValueError("expected [n, H, W] or [H, W] float32 maps")
+    return m, single
+
+
+def cumulative_distribution(maps, nbins=256, with_counts=False, device=0):
+    """skimage.exposure.cumulative_distribution(map, nbins) of float32 maps [n, H, W] or [H, W] on the GPU (csrc/hist_match.hip;
+    the law, np.histogram then cumsum / N in float64, is in include/p3d_hip.h) -> (cdf, bin_centers), float64 [n, nbins] /
+    [nbins] each; with_counts: (cdf, bin_centers, counts int64) -- np.histogram(map.astype(float64), nbins)[0]."""
+    m, single = _maps3(maps)
+    n, nb = m.shape[0], int(nbins)
+    if not 2 <= nb <= 1024:
+        raise ValueError("nbins must be in [2, 1024]")
+    cdf, centres, counts = np.empty((n, nb), np.float64), np.empty((n, nb), np.float64), np.empty((n, nb), np.int64)
+    dp = C.POINTER(C.c_double)
+    check(lib().p3d_cumulative_distribution(device, m.ctypes.data_as(C.POINTER(C.c_float)), n, m.shape[1], m.shape[2], nb,
+                                            counts.ctypes.data_as(C.POINTER(C.c_int64)) if with_counts else None,
+                                            cdf.ctypes.data_as(dp), centres.ctypes.data_as(dp)))
+    out = (cdf, centres, counts) if with_counts else (cdf, centres)
+    return tuple(a[0] for a in out) if single else out
+
+
+def match_hist(maps, cdf, bin_centers, nbins=256, device=0):
+    """The reference's utils/metric_utils.py:56-84 match_hist(image, cdf, bin_centers, nbins) on the GPU: float32 maps [n, H, W] or
+    [H, W] remapped so that their histogram follows the target table's -> the same shape, float32.  cdf / bin_centers: float64
+    [nt] (one table for every map) or [n, nt] (one per map), finite and non-decreasing."""
+    m, single = _maps3(maps)
+    c = np.ascontiguousarray(cdf, dtype=np.float64)
+    x = np.ascontiguousarray(bin_centers, dtype=np.float64)
+    if c.shape != x.shape or c.ndim not in (1, 2) or (c.ndim == 2 and c.shape[0] != m.shape[0]):
+        raise ValueError("cdf and bin_centers are float64 [nt], or [n, nt] with one table per map")
+    out = np.empty_like(m)
+    fp, dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
+    check(lib().p3d_match_hist(device, m.ctypes.data_as(fp), m.shape[0], m.shape[1], m.shape[2], int(nbins), c.ctypes.data_as(dp),
+                               x.ctypes.data_as(dp), 1 if c.ndim == 1 else c.shape[0], c.shape[-1], out.ctypes.data_as(fp)))
+    return out[0] if single else out
+
+
+def match_hist_maps(maps, targets, nbins=256, device=0):
+    """match_hist(map, *cumulative_distribution(target, nbins), nbins) for every map and its own target image (the reference's
+    recipe, utils/metric_utils.py:321), both tables built on the device.  maps, targets: float32 [n, H, W] or [H, W]."""
+    m, single = _maps3(maps)
+    t, _ = _maps3(targets)
+    if t.shape != m.shape:
+        raise ValueError("targets must have the maps' shape %s" % (m.shape,))
+    out = np.empty_like(m)
+    fp = C.POINTER(C.c_float)
+    check(lib().p3d_match_hist_maps(device, m.ctypes.data_as(fp), t.ctypes.data_as(fp), m.shape[0], m.shape[1], m.shape[2], int(nbins),
+                                    out.ctypes.data_as(fp)))
+    return out[0] if single else out
+
+
+def postprocess_maps(maps, size, sigma=0., radius=0, norm="none", scale=None, device=0, hist_match=None, nbins=256):
     """The output stage of P3DSession.set_postprocess on supplied maps (p3d_postprocess_maps): float32 [n, h, w], [h, w], or
     [n, h, w, c] of which channel 0 is taken -> resize_linear to size = (H, W), gaussian_blur, then each map divided by its
     maximum (norm="max") or brought to its range (norm="range").  -> float32 [n, H, W]; with `scale`, the uint8 images
-    saturate_cast(float32(v * scale)) instead."""
+    saturate_cast(float32(v * scale)) instead.  hist_match: a table (cdf, bin_centers) as P3DSession.set_hist_match takes it --
+    every map is matched to it (match_hist with `nbins`) after the blur and before the normalisation."""
     m = np.ascontiguousarray(maps, dtype=np.float32)
     single = m.ndim == 2
     if single:
@@ -129,9 +218,14 @@ def postprocess_maps(maps, size, sigma=0., radius=0, norm="none", scale=None, de
     cfg = _post_cfg(sigma, radius, norm)
     out = np.empty((m.shape[0], H, W), np.float32 if scale is None else np.uint8)
     fp, u8 = C.POINTER(C.c_float), C.POINTER(C.c_ubyte)
-    check(lib().p3d_postprocess_maps(device, m.ctypes.data_as(fp), m.shape[0], m.shape[1], m.shape[2], m.shape[3] if m.ndim == 4 else 1,
-                                     int(H), int(W), C.byref(cfg), 0.0 if scale is None else float(scale),
-                                     out.ctypes.data_as(fp) if scale is None else None, out.ctypes.data_as(u8) if scale is not None else None))
+    args = (device, m.ctypes.data_as(fp), m.shape[0], m.shape[1], m.shape[2], m.shape[3] if m.ndim == 4 else 1, int(H), int(W), C.byref(cfg))
+    outs = (0.0 if scale is None else float(scale), out.ctypes.data_as(fp) if scale is None else None,
+            out.ctypes.data_as(u8) if scale is not None else None)
+    if hist_match is None:
+        check(lib().p3d_postprocess_maps(*(args + outs)))
+    else:
+        mc, keep = _match_cfg(hist_match, nbins)
+        check(lib().p3d_postprocess_maps_match(*(args + (C.byref(mc),) + outs)))
     return out[0] if single else out
 
 

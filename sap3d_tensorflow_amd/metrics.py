@@ -167,13 +167,15 @@ def eval_draws(fixation, jitter, n_rep, rng=None):
     return n_fix, jit, idx
 
 
-def evaluate_maps(maps, density, fixation, size=None, jitter=True, n_rep=100, step_size=0.1, rng=None, device=0, postprocess=None):
+def evaluate_maps(maps, density, fixation, size=None, jitter=True, n_rep=100, step_size=0.1, rng=None, device=0, postprocess=None,
+                  hist_match=None, nbins=256):
     """Test hook (p3d_debug_eval_maps): P3DSession.evaluate's device pass on supplied maps instead of a session's prediction ->
     [n, 5] float64: CC, SIM, AUC_Judd, AUC_Borji, NSS.  maps: float32 [n, h, w], or [n, h, w, c] of which channel 0 is scored
     (the way the prediction buffer is addressed); density uint8 [n, Hd, Wd]; fixation uint8 [n, H, W] with (H, W) == size
     (default: the fixation maps' own).  The draws are evaluate's (eval_draws).  postprocess: dict(sigma, radius, norm) as
     P3DSession.set_postprocess takes them -- the smoothing / normalisation stage runs between the resize and the metrics
-    (p3d_debug_eval_maps_post)."""
+    (p3d_debug_eval_maps_post).  hist_match: "density" or a table (cdf, bin_centers) as P3DSession.set_hist_match takes them, with
+    `nbins` -- the histogram-matching stage runs after the blur and before the normalisation (p3d_debug_eval_maps_match)."""
     m = np.ascontiguousarray(maps, dtype=np.float32)
     dens = np.ascontiguousarray(density)
     fix = np.ascontiguousarray(fixation)
@@ -195,7 +197,13 @@ def evaluate_maps(maps, density, fixation, size=None, jitter=True, n_rep=100, st
             dens.shape[1], dens.shape[2], fix.ctypes.data_as(u8), int(H), int(W),
             _dp(jit) if jit is not None else None, idx.ctypes.data_as(ip), n_fix.ctypes.data_as(ip),
             int(n_rep), float(step_size), _dp(out))
-    if postprocess is None:
+    if hist_match is not None:
+        from .dataflow import _match_cfg, _post_cfg
+        post = postprocess or {}
+        cfg = _post_cfg(post.get("sigma", 0.), post.get("radius", 0), post.get("norm", "none"))
+        mc, keep = _match_cfg(hist_match, nbins)
+        check(lib().p3d_debug_eval_maps_match(*(args + (C.byref(cfg), C.byref(mc)))))
+    elif postprocess is None:
         check(lib().p3d_debug_eval_maps(*args))
     else:
         from .dataflow import _post_cfg

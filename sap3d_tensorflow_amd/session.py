@@ -475,6 +475,32 @@ class P3DSession:
             return None
         return dict(sigma=cfg.sigma, radius=cfg.radius, norm=[k for k, v in _lib.NORMS.items() if v == cfg.norm][0])
 
+    # ---- histogram matching of the output maps (p3d_set_hist_match) -------------------------------------
+    def set_hist_match(self, target="off", nbins=256):
+        """Match the histogram of every map that evaluate scores and pred_maps_u8 / video_maps_u8 write to a target's, at output
+        resolution on the device (the reference's utils/metric_utils.py match_hist; include/p3d_hip.h holds the exact arithmetic,
+        dataflow.match_hist runs it on supplied maps).  target: "off" (or None); a table (cdf, bin_centers) of float64 [nt] each,
+        e.g. dataflow.cumulative_distribution of a map or a pooled dataset table -- every map is matched to it; or "density":
+        evaluate only, each prediction is matched to its own ground-truth density map (pred_maps_u8 and video_maps_u8 refuse
+        while it is set).  `nbins` bins of the map's own histogram, 2 .. 1024.  The stage runs after set_postprocess's blur and
+        before its normalisation; separate from that setting.  Training never sees it."""
+        from .dataflow import _match_cfg
+        cfg, keep = _match_cfg(target, nbins)
+        check(lib().p3d_set_hist_match(self._h, C.byref(cfg)))
+
+    @property
+    def hist_match(self):
+        """None while the option is off, else dict(mode="density" | "table", nbins) and, for a table, cdf and bin_centers."""
+        cfg = _lib.P3dHistMatch()
+        check(lib().p3d_get_hist_match(self._h, C.byref(cfg)))
+        if cfg.mode == _lib.MATCH_MODES["off"]:
+            return None
+        out = dict(mode=[k for k, v in _lib.MATCH_MODES.items() if v == cfg.mode][0], nbins=cfg.nbins)
+        if cfg.nt:
+            out["cdf"] = np.array(cfg.cdf[:cfg.nt], np.float64)
+            out["bin_centers"] = np.array(cfg.centres[:cfg.nt], np.float64)
+        return out
+
     # ---- moving average of the weights (p3d_set_ema) ---------------------------------------------------
     def set_ema(self, decay, warmup=False):
         """Keep an exponential moving average of every trainable variable, as tf.train.ExponentialMovingAverage(decay).apply(
