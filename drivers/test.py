@@ -18,7 +18,10 @@ Without --data, a synthetic set (sap3d_tensorflow_amd.synthetic.synthetic_test_s
 
 --sauc M adds a sixth column, shuffled AUC (utils/metrics.py:157-197) of the clean full-resolution prediction against the
 union of the fixations of M other clips (Borji's M = 10).  It draws from its own np.random.RandomState(seed): the five
-reference columns are identical with and without it.  --time prints per batch: forward, host random draws, host->device
+reference columns are identical with and without it.  --kldiv and --info-gain BASELINE.npy add KL divergence
+(utils/metrics.py:338-362) and information gain over the baseline map (float32 [H, W] at the fixation maps' size) of the same
+scored map, computed on the GPU in the same pass (P3DSession.set_eval_extra); their NaN-dropped means follow the other columns
+on both lines, and the five reference columns are identical with and without them.  --time prints per batch: forward, host random draws, host->device
 copy and the device metric stage."""
 import argparse
 import os
@@ -62,13 +65,31 @@ def nan_dropped_means(cols):
     return [float(np.mean(np.asarray(c)[~np.isnan(c)])) for c in cols]
 
 
-def metric_line(fmt, index, cols):
-    """cols in evaluate's order (CC, SIM, AUC_Judd, AUC_Borji, NSS [, sAUC]); the reference prints CC SIM NSS Judd Borji."""
+def metric_line(fmt, index, cols, extra=()):
+    """cols in evaluate's order (CC, SIM, AUC_Judd, AUC_Borji, NSS [, sAUC]); the reference prints CC SIM NSS Judd Borji.
+    extra: (label, value) of --kldiv / --info-gain, after everything else."""
     cc, sim, judd, borji, nss = cols[:5]
     line = fmt % (index, cc, sim, nss, judd, borji)
     if len(cols) > 5:
         line += "   sAUC: %.3f" % cols[5]
+    for label, value in extra:
+        line += "   %s: %.3f" % (label, value)
     return line
+
+
+def nan_dropped_mean(c):
+    """The mean of a list without its NaNs; NaN for a list that holds nothing else (the progress line's before the first batch)."""
+    c = np.asarray(c, np.float64)
+    c = c[~np.isnan(c)]
+    return float(np.mean(c)) if c.size else float("nan")
+
+
+def load_baseline(path, size):
+    """--info-gain's map: float32 [H, W] of an .npy, of the fixation maps' size."""
+    base = np.asarray(np.load(path), np.float32)
+    if base.shape != tuple(size):
+        raise ValueError("--info-gain: the baseline %s is %s, the fixation maps are %s" % (path, base.shape, tuple(size)))
+    return base
 
 
 def shuffled_auc(sess, fixation, lo, m, rng, device=0):
@@ -123,6 +144,10 @@ def parse_args(argv=None):
     p.add_argument("--seed", type=int, default=0, help="seeds numpy's global stream (the metrics' draws) and the synthetic set")
     p.add_argument("--sauc", type=int, default=0, metavar="M", help="add shuffled AUC against the fixations of M other clips")
     p.add_argument("--time", action="store_true", help="print the stage times of every batch")
+    p.add_argument("--kldiv", action="store_true", help="add KL divergence of the density from the scored map (utils/metrics.py KLdiv; "
+                   "P3DSession.set_eval_extra)")
+    p.add_argument("--info-gain", type=str, default="", metavar="BASELINE.npy", help="[addition] add information gain over the baseline "
+                   "map of this .npy, float32 [H, W] at the fixation maps' size (the MIT benchmark's InfoGain)")
     p.add_argument("--blur-sigma", type=float, default=0., metavar="S", help="[addition] smooth every resized prediction with a "
                    "Gaussian of S pixels before it is scored (P3DSession.set_postprocess)")
     p.add_argument("--blur-radius", type=int, default=0, metavar="R", help="[addition] the Gaussian's radius in pixels, at most 255; "
@@ -151,6 +176,7 @@ def main(argv=None):
         x, density, fixation = load_set(args.data, device)
     else:
         x, density, fixation = synthetic.synthetic_test_set(args.seed, args.clips)
+    baseline = load_baseline(args.info_gain, fixation.shape[1:]) if args.info_gain else None      # refused before anything runs
     structure = "unet++ds" if args.structure == "unet++" else args.structure
     blocks = tuple(int(v) for v in args.blocks.split(","))
     sess = P3DSession(structure, batch=args.batch, frames=x.shape[1], height=x.shape[2], width=x.shape[3], base=args.base,
@@ -160,6 +186,14 @@ def main(argv=None):
     print("Now using model %s with structure %s" % (args.model or "(initialised)", structure))
     sess.set_postprocess(args.blur_sigma, args.blur_radius, args.normalize)
     sess.set_hist_match(match_target(args), args.match_bins)
+    extra_on = args.kldiv or baseline is not None
+    if extra_on:
+        sess.set_eval_extra(kldiv=args.kldiv, info_gain=baseline is not None, baseline=baseline)
+    extra_cols = [[] for _ in range(2)]                                   # KL, IG
+    labels = [(k, name) for k, name, on in ((0, "KLdiv", args.kldiv), (1, "IG", baseline is not None)) if on]
+
+    def extras():
+        return [(name, nan_dropped_mean(extra_cols[k])) for k, name in labels]
     np.random.seed(args.seed)
     sauc_rng = np.random.RandomState(args.seed) if args.sauc else None
     cols = [[] for _ in range(6 if args.sauc else 5)]
@@ -167,10 +201,14 @@ def main(argv=None):
     for lo, hi in batches(len(x), args.batch):
         index += 1
         if index % 100 == 0:
-            print(metric_line(STEP_LINE, index, [np.mean(c) for c in cols]))
+            print(metric_line(STEP_LINE, index, [np.mean(c) for c in cols], extras()))
         m = sess.evaluate(x[lo:hi], density[lo:hi], fixation[lo:hi], size=fixation.shape[1:])
         for k in range(5):
             cols[k].extend(m[:, k].tolist())
+        if extra_on:
+            e = sess.last_eval_extra()
+            for k in range(2):
+                extra_cols[k].extend(e[:, k].tolist())
         if args.sauc:
             cols[5].extend(shuffled_auc(sess, fixation, lo, args.sauc, sauc_rng, device))
         if args.time:
@@ -178,12 +216,12 @@ def main(argv=None):
             print("  batch %d: forward %.3f ms  host draws %.3f ms  host->device %.3f ms  device metrics %.3f ms"
                   % (index, t["forward"], t["draws"], t["h2d"], t["device"]))
     post = sess.postprocess
-    print(metric_line(ALL_LINE, index, nan_dropped_means(cols)) +
+    print(metric_line(ALL_LINE, index, nan_dropped_means(cols), extras()) +
           ("   postprocess: sigma %g radius %d normalize %s" % (post["sigma"], post["radius"], post["norm"]) if post else "") +
           ("   match-hist: %s, %d bins" % (args.match_hist, args.match_bins) if args.match_hist else ""))
     print("Testing Finished!")
     sess.close()
-    return cols
+    return cols + [extra_cols[k] for k, _ in labels]
 
 
 if __name__ == "__main__":

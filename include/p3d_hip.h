@@ -862,6 +862,61 @@ int p3d_debug_eval_maps_match(int device, const float* maps, int n_maps, int h, 
                               const int* n_fix, int n_rep, double step_size, double* out, const p3d_postprocess* cfg,
                               const p3d_hist_match* match);
 
+/* ---- KL divergence and information gain at scoring resolution (utils/metrics.py:338-362 KLdiv, the one function of that file
+ * the evaluation pass did not have; and the MIT saliency benchmark's InfoGain(saliencyMap, fixationMap, baselineMap), an ADDITION
+ * without a reference counterpart).  OFF by default; off, every entry point issues what it issued before and returns the same
+ * bits; on, the five columns of p3d_eval_last_frames are still bit for bit what they are off.  PARITY UNPINNED: neither scipy nor
+ * the MIT code is available to the tests, and the reference computes KLdiv in float32 with numpy's pairwise sum, which is not
+ * reproduced: this text is the contract and tests/kl_ig_ref.py replays it in numpy float64; the kernels are held to that replay.
+ * Per map of n = H * W elements, all arithmetic in float64, no fused multiply-add:
+ *   s_i  the evaluation pass's CLEAN prediction widened to double: the float32 map after the resize and the optional BLUR / MATCH /
+ *        NORM stages, before AUC_Judd's jitter -- the map CC and SIM see.
+ *   y_i  the density: in the evaluation pass rint(q * 255) / 255 of the float32 density q, i.e. byte / 255. in double, what CC and
+ *        SIM use; in the op-level entry points the supplied float32 widened to double.
+ *   f_i  fixated <=> byte >= 128 (evaluation), fix > 0.5f (op level).
+ *   eps  = 2.2204e-16, the reference's literal (not DBL_EPSILON).
+ *   KLDIV      (utils/metrics.py:338-362; its scipy.misc.imresize to the other map's shape is taken as the identity on maps of
+ *              one shape, and imresize's byte quantisation is deliberately not reproduced.)
+ *              S1 = sum of s_i,  S2 = sum of y_i;   p_i = s_i / S1 if any s_i != 0, else s_i;   q_i = y_i / S2 if any y_i != 0,
+ *              else y_i;   KL = sum of q_i * log(eps + q_i / (p_i + eps)).
+ *              Nothing else is special-cased: an all-zero density gives 0, a NaN anywhere gives NaN, a negative p_i + eps gives
+ *              NaN through log as in numpy.
+ *   INFO GAIN  the baseline b is ONE float32 map [H][W] shared by all maps of a call (a centre prior, the mean training density).
+ *              u_i = (s_i - min s) / (max s - min s);   P_i = u_i / U with U = (S1 - n * min s) / (max s - min s), the way the
+ *              per-map loss forms its range sums;   B_i from b in the same way;
+ *              IG = (1 / F) * sum over fixated i of (log2(eps + P_i) - log2(eps + B_i)),  F = the number of fixated elements.
+ *              NaN when F = 0, when s or b is constant, or when either holds a NaN (the cases in which NSS and SIM are NaN).
+ *   ORDER      every sum (S1, S2, the sums of b, KL's and IG's terms, F) is formed in full_pass_a's order: the map is cut into
+ *              p3d_full_blocks(n) equal chunks, one per block; lane t of a block's 256 adds elements t, t + 256, ... of its chunk in
+ *              ascending order; the 256 lane sums go through the block's halving tree (lane t += lane t + 128, then + 64, ...); the
+ *              last arriving block adds the blocks' sums, lane t taking blocks t, t + 256, ..., then the same tree.  Minima and
+ *              maxima likewise.  No floating-point atomics: the same bits on every run.
+ * p3d_set_eval_extra   the handle's setting: flags = P3D_EVAL_KLDIV | P3D_EVAL_INFO_GAIN.  The baseline [H][W] is required if and
+ *                      only if P3D_EVAL_INFO_GAIN is set; it is checked on the host (finite, not constant), copied to the device,
+ *                      and its minimum, maximum and sum are taken there by one launch, once.  flags = 0 switches off and frees.
+ *                      Refused (-1, p3d_last_error set, nothing changed): unknown flags, a missing or a superfluous baseline, a
+ *                      baseline that is not finite or constant.  The train step, a captured step graph and its schedule never see it.
+ *                      While on, p3d_eval_last_frames issues ONE more launch after pass A, on the scored map.
+ * p3d_get_eval_extra   the flags, a pointer to the handle's copy of the baseline (NULL without one; valid until the next
+ *                      p3d_set_eval_extra or p3d_destroy) and its size; every pointer may be NULL.
+ * p3d_last_eval_extra  out[B][2] = KL, IG of the last p3d_eval_last_frames; a metric that is off reports NaN.  cap = room in out, in
+ *                      doubles.  Refused: the option is off; no evaluation has run since it was set; the last evaluation's H x W
+ *                      is not the baseline's (that evaluation ran without the launch; its five columns are unaffected).
+ * p3d_debug_eval_maps_extra  p3d_debug_eval_maps_match with the launch of `flags` and a baseline [H][W] (NULL without
+ *                      P3D_EVAL_INFO_GAIN); extra[n_maps][2] = KL, IG (may be NULL when flags = 0).
+ * p3d_metric_kldiv     KLDIV of host maps [n_maps][n_pix], map1 the saliency map and map2 the density; beside p3d_metric_cc.
+ * p3d_metric_info_gain INFO GAIN of host maps sal, fix [n_maps][n_pix] against baseline [n_pix]. */
+enum { P3D_EVAL_KLDIV = 1, P3D_EVAL_INFO_GAIN = 2 };
+int p3d_set_eval_extra(p3d_handle* h, int flags, const float* baseline, int H, int W);
+int p3d_get_eval_extra(p3d_handle* h, int* flags, const float** baseline, int* H, int* W);
+int p3d_last_eval_extra(p3d_handle* h, double* out /* [B][2]: KL, IG */, int64_t cap);
+int p3d_debug_eval_maps_extra(int device, const float* maps, int n_maps, int h, int w, int elem_stride, const unsigned char* density,
+                              int Hd, int Wd, const unsigned char* fixation, int H, int W, const double* jitter, const int* borji_idx,
+                              const int* n_fix, int n_rep, double step_size, double* out, const p3d_postprocess* cfg,
+                              const p3d_hist_match* match, int flags, const float* baseline, double* extra);
+int p3d_metric_kldiv(int device, const float* map1, const float* map2, int n_maps, int n_pix, double* out);
+int p3d_metric_info_gain(int device, const float* sal, const float* fix, const float* baseline, int n_maps, int n_pix, double* out);
+
 /* ---- Resident video inference (an ADDITION beside p3d_predict_windows: gen_pred.py slides a 16-frame queue by one frame and keeps
  * nothing on the device).  A video's normalised frames go up once, windows are cut where the frames are, and every frame's map is
  * kept on the device until it is read.  OFF until p3d_video_open: while no video is open every other entry point issues what it

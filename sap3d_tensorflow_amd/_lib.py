@@ -56,6 +56,8 @@ class P3dHistMatch(C.Structure):
 # p3d_set_hist_match modes (include/p3d_hip.h P3D_MATCH_*)
 MATCH_MODES = {"off": 0, "table": 1, "density": 2}
 P3D_HIST_MAX_BINS = 1024
+# p3d_set_eval_extra flags (include/p3d_hip.h P3D_EVAL_*)
+EVAL_EXTRA = {"kldiv": 1, "info_gain": 2}
 # p3d_video_open modes (include/p3d_hip.h P3D_VIDEO_*)
 VIDEO_MODES = {"newest": 0, "mean": 1}
 
@@ -234,6 +236,14 @@ SIGNATURES = {
     "p3d_debug_eval_maps_match": (C.c_int, [C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ubyte), C.c_int, C.c_int,
                                             C.POINTER(C.c_ubyte), C.c_int, C.c_int, _dp, _ip, _ip, C.c_int, C.c_double, _dp,
                                             C.POINTER(P3dPostprocess), C.POINTER(P3dHistMatch)]),
+    "p3d_set_eval_extra": (C.c_int, [C.c_void_p, C.c_int, _fp, C.c_int, C.c_int]),
+    "p3d_get_eval_extra": (C.c_int, [C.c_void_p, _ip, C.POINTER(_fp), _ip, _ip]),
+    "p3d_last_eval_extra": (C.c_int, [C.c_void_p, _dp, C.c_int64]),
+    "p3d_debug_eval_maps_extra": (C.c_int, [C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ubyte), C.c_int, C.c_int,
+                                            C.POINTER(C.c_ubyte), C.c_int, C.c_int, _dp, _ip, _ip, C.c_int, C.c_double, _dp,
+                                            C.POINTER(P3dPostprocess), C.POINTER(P3dHistMatch), C.c_int, _fp, _dp]),
+    "p3d_metric_kldiv": (C.c_int, [C.c_int, _fp, _fp, C.c_int, C.c_int, _dp]),
+    "p3d_metric_info_gain": (C.c_int, [C.c_int, _fp, _fp, _fp, C.c_int, C.c_int, _dp]),
     "p3d_video_open": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "p3d_video_close": (C.c_int, [C.c_void_p]),
     "p3d_video_info": (C.c_int, [C.c_void_p, _ip, _ip, _ip]),

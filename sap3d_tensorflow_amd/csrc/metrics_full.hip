@@ -33,6 +33,8 @@ constexpr int SORT_TPB = 1024;
 constexpr int LCAP = 4096;         // AUC-Judd thresholds + counters held in LDS up to this many fixations (32 KB)
 constexpr int NA = 11;             // pass A partials per block
 constexpr int NB = 8;              // pass B partials per block
+constexpr int NS = P3D_FULL_STATS3_PARTS;      // full_stats3 partials per block: min, max, sum, NaN seen
+constexpr int NK = P3D_FULL_EXTRA_PARTS;       // full_pass_kl partials per block: KL terms, IG terms, fixated pixels
 enum { S_MP, S_MD, S_MNP, S_MXP, S_MND, S_MXD, S_MJ, S_MNJ, S_MXJ, S_NFIX, S_SA, S_SB, S_COUNT };
 static_assert(S_COUNT == P3D_FULL_STATS && S_NFIX == P3D_FULL_STAT_NFIX, "p3d_kernels.h names the stats layout");
 
@@ -465,6 +467,88 @@ __global__ __launch_bounds__(TPB) void full_borji(P3dFullMaps a, P3dFullBorji r)
     if (tid == 0) a.out[b * 5 + 3] = sum / r.n_rep;
 }
 
+// ---- KL divergence and information gain (p3d_set_eval_extra; the law in include/p3d_hip.h) ---------------------------------
+// Minimum, maximum and sum of every map, in double on the float32 values: full_pass_a's order (per-lane strided accumulation
+// over block_range's chunk, the block tree, the last arriver's fold over blocks) and its NaN rule (a NaN anywhere makes both
+// extrema NaN), so that a map gets the bits pass A gives it as P.  The baseline of the information gain, once when it is set.
+__global__ __launch_bounds__(TPB) void full_stats3(P3dFullStats3 q) {
+    __shared__ double red[TPB];
+    __shared__ int last;
+    const int b = blockIdx.y;
+    const float* m = q.maps + (size_t)b * q.n_pix;
+    const long long chunk = (q.n_pix + q.nblk - 1) / q.nblk;
+    const long long i0 = (long long)blockIdx.x * chunk, i1 = min((long long)q.n_pix, i0 + chunk);
+    double sp = 0, nan = 0, mn = INFINITY, mx = -INFINITY;
+    for (long long i = i0 + threadIdx.x; i < i1; i += TPB) {
+        const double x = m[i];
+        if (x != x) nan = 1;
+        sp += x; mn = fmin(mn, x); mx = fmax(mx, x);
+    }
+    const double v[NS] = {block_min(mn, red), block_max(mx, red), block_sum(sp, red), block_max(nan, red)};
+    double* part = q.part + (size_t)b * q.nblk * NS;
+    if (threadIdx.x < NS) p3d_store_wt(part, (size_t)blockIdx.x * NS + threadIdx.x, v[threadIdx.x]);
+    if (!p3d_last_block_wt(q.counter + b, q.nblk, &last)) return;
+    const double anynan = fold_max(part, q.nblk, NS, 3, red);
+    const double s[3] = {fold_min(part, q.nblk, NS, 0, red), fold_max(part, q.nblk, NS, 1, red), fold_sum(part, q.nblk, NS, 2, red)};
+    if (threadIdx.x < 3) q.out[(size_t)b * 3 + threadIdx.x] = (threadIdx.x < 2 && anynan > 0.0) ? NAN : s[threadIdx.x];
+}
+
+// KL = sum q_i log(eps + q_i / (p_i + eps)) and IG = (1 / F) sum over fixated i of (log2(eps + P_i) - log2(eps + B_i)) of every
+// map, after pass A.  S1 and S2 are the law's raw sums, not mean * n (S / n * n is not S): pass A's per-block sums still lie in
+// partA (no later pass writes it), and every block folds them again in pass A's order -- the double pass A divided by n.  "Any
+// element nonzero" is min != 0 or max != 0 (a NaN extremum counts as nonzero, as numpy's any() does).  Op level (e.sstat given):
+// the statistics come from full_stats3 and the density is the supplied float32 widened, not density()'s byte.
+// F is counted here, in pass A's order (integers: the same double as stats[S_NFIX]).  Each flag is a block-uniform branch: a call
+// with KL alone reads neither fixations nor baseline; the baseline's pixel i is e.base[i], one map for all.
+__global__ __launch_bounds__(TPB) void full_pass_kl(P3dFullMaps a, P3dFullExtra e) {
+    __shared__ double red[TPB];
+    __shared__ int last;
+    const int b = blockIdx.y;
+    const size_t base = (size_t)b * a.n_pix;
+    const bool kl = (e.flags & P3D_EXTRA_KLDIV) != 0, ig = (e.flags & P3D_EXTRA_INFO_GAIN) != 0;
+    const double n = (double)a.n_pix, eps = 2.2204e-16;
+    double mns, mxs, S1, mny = 0, mxy = 0, S2 = 0;
+    if (e.sstat) {
+        mns = e.sstat[b * 3 + 0]; mxs = e.sstat[b * 3 + 1]; S1 = e.sstat[b * 3 + 2];
+        if (kl) { mny = e.ystat[b * 3 + 0]; mxy = e.ystat[b * 3 + 1]; S2 = e.ystat[b * 3 + 2]; }
+    } else {
+        const double* st = a.stats + (size_t)b * S_COUNT;
+        const double* partA = a.partA + (size_t)b * a.nblk * NA;
+        mns = st[S_MNP]; mxs = st[S_MXP]; mny = st[S_MND]; mxy = st[S_MXD];
+        S1 = fold_sum(partA, a.nblk, NA, 0, red);
+        S2 = fold_sum(partA, a.nblk, NA, 1, red);
+    }
+    const bool any_s = !(mns == 0.0 && mxs == 0.0), any_y = !(mny == 0.0 && mxy == 0.0);
+    const double rs = mxs - mns, su = (S1 - n * mns) / rs;
+    double mnb = 0, rb = 0, bu = 0;
+    if (ig) { mnb = e.bstat[0]; rb = e.bstat[1] - e.bstat[0]; bu = (e.bstat[2] - n * mnb) / rb; }
+    long long i0, i1;
+    block_range(a, i0, i1);
+    double akl = 0, aig = 0, nf = 0;
+    for (long long i = i0 + threadIdx.x; i < i1; i += TPB) {
+        const double s = a.P[base + i];
+        if (kl) {
+            const double y = e.sstat ? (double)a.D[base + i] : density(a.D[base + i]);
+            const double p = any_s ? s / S1 : s, q = any_y ? y / S2 : y;
+            akl += q * log(eps + q / (p + eps));
+        }
+        if (ig && fixated(a, base + i)) {
+            const double Pi = (s - mns) / rs / su, Bi = ((double)e.base[i] - mnb) / rb / bu;
+            aig += log2(eps + Pi) - log2(eps + Bi);
+            nf += 1.0;
+        }
+    }
+    const double v[NK] = {block_sum(akl, red), block_sum(aig, red), block_sum(nf, red)};
+    double* part = e.part + (size_t)b * a.nblk * NK;
+    if (threadIdx.x < NK) p3d_store_wt(part, (size_t)blockIdx.x * NK + threadIdx.x, v[threadIdx.x]);
+    if (!p3d_last_block_wt(a.counter + b, a.nblk, &last)) return;
+    const double KL = fold_sum(part, a.nblk, NK, 0, red), IG = fold_sum(part, a.nblk, NK, 1, red), F = fold_sum(part, a.nblk, NK, 2, red);
+    if (threadIdx.x == 0) {
+        e.out[b * 2 + 0] = kl ? KL : NAN;
+        e.out[b * 2 + 1] = ig ? IG / F : NAN;          // 0 / 0 = NaN: no fixation; a constant or NaN map made every term NaN
+    }
+}
+
 unsigned grid_for(long long total) { return (unsigned)std::min<long long>((total + TPB - 1) / TPB, 65535); }
 
 }  // namespace
@@ -496,5 +580,21 @@ hipError_t p3d_full_rank(const P3dFullMaps& a, hipStream_t s) {
 }
 hipError_t p3d_full_borji(const P3dFullMaps& a, const P3dFullBorji& r, hipStream_t s) {
     hipLaunchKernelGGL(full_borji, dim3(r.n_rep, a.n_maps), dim3(TPB), 0, s, a, r);
+    return hipGetLastError();
+}
+hipError_t p3d_full_stats3(const P3dFullStats3& q, hipStream_t s) {
+    if (!q.maps || !q.part || !q.counter || !q.out || q.n_maps < 1 || q.n_maps > 65535 || q.n_pix < 1 || q.nblk != p3d_full_blocks(q.n_pix))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(full_stats3, dim3(q.nblk, q.n_maps), dim3(TPB), 0, s, q);
+    return hipGetLastError();
+}
+hipError_t p3d_full_extra(const P3dFullMaps& a, const P3dFullExtra& e, hipStream_t s) {
+    const bool kl = (e.flags & P3D_EXTRA_KLDIV) != 0, ig = (e.flags & P3D_EXTRA_INFO_GAIN) != 0;
+    if ((!kl && !ig) || (e.flags & ~(P3D_EXTRA_KLDIV | P3D_EXTRA_INFO_GAIN)) || !a.P || !a.counter || !e.part || !e.out || a.n_maps < 1 ||
+        a.n_maps > 65535 || a.n_pix < 1 || a.nblk != p3d_full_blocks(a.n_pix))
+        return hipErrorInvalidValue;
+    if ((kl && !a.D) || (ig && (!a.fix || !e.base || !e.bstat))) return hipErrorInvalidValue;
+    if (e.sstat ? (kl && !e.ystat) : (!a.stats || !a.partA)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(full_pass_kl, dim3(a.nblk, a.n_maps), dim3(TPB), 0, s, a, e);
     return hipGetLastError();
 }

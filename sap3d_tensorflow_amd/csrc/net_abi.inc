@@ -2501,6 +2501,10 @@ void post_sequence(hipStream_t s, const std::vector<PostRun>& runs, int total, i
 }
 // Source maps of one evaluation: map m's pixel (y, x) at p[m * map_stride + (y * w + x) * elem_stride] (device memory)
 struct EvalSource { const float* p; long long map_stride; int elem_stride, n_maps, h, w; };
+// p3d_set_eval_extra's launch for one evaluation: the flags, the baseline of H x W floats and its statistics (device memory, IG
+// only), and where the [n_maps][2] values go on the host
+static_assert(P3D_EVAL_KLDIV == P3D_EXTRA_KLDIV && P3D_EVAL_INFO_GAIN == P3D_EXTRA_INFO_GAIN, "p3d_kernels.h names the header's flags");
+struct EvalExtra { int flags; const float* base; const double* bstat; int H, W; double* out; };
 // The device pass of test.py's per-batch body on stream s, with the scratch of s: everything of p3d_eval_last_frames that does
 // not need the handle, so that p3d_debug_eval_maps runs the same launches on maps of the caller's.  Checks the arguments, lays
 // the buffers out in the stream's scratch, uploads, resizes the source maps (float32) and the density maps (uint8), runs the
@@ -2508,7 +2512,7 @@ struct EvalSource { const float* p; long long map_stride; int elem_stride, n_map
 // the source maps readable; it runs after the uploads, inside the metric stage's time.
 void eval_maps(hipStream_t s, const EvalSource& src, const std::function<void(hipStream_t)>& prepare, const unsigned char* density, int Hd, int Wd, const unsigned char* fixation, int H,
                int W, const double* jitter, const int* borji_idx, const int* n_fix, int n_rep, double step_size, double* out,
-               double* stage_ms, const p3d_postprocess* post = nullptr, const MatchPlan* matchp = nullptr) {
+               double* stage_ms, const p3d_postprocess* post = nullptr, const MatchPlan* matchp = nullptr, const EvalExtra* extra = nullptr) {
     const PostPlan plan(post);                 // p3d_set_postprocess: between the resize and the metrics, in place on P
     const MatchPlan match = matchp ? *matchp : MatchPlan();      // p3d_set_hist_match: after the blur, before the normalisation
     const bool chain = plan.on || match.on();
@@ -2517,6 +2521,11 @@ void eval_maps(hipStream_t s, const EvalSource& src, const std::function<void(hi
     if ((long long)H * W > INT32_MAX / 2) throw P3dError("eval: map too large");
     if (n_rep < 1 || !(step_size > 0.0)) throw P3dError("eval: AUC_Borji needs n_rep >= 1 and a positive step");
     if (plan.on) plan.fits(H, W);
+    const bool xon = extra && extra->flags != 0;                 // p3d_set_eval_extra: one launch after pass A, on the scored map
+    if (xon && !extra->out) throw P3dError("null argument");
+    if (xon && (extra->flags & P3D_EVAL_INFO_GAIN) && (!extra->base || !extra->bstat || extra->H != H || extra->W != W))
+        throw P3dError("eval_extra: the baseline is " + std::to_string(extra->H) + " x " + std::to_string(extra->W) + ", the evaluation " +
+                       std::to_string(H) + " x " + std::to_string(W));
     const int B = src.n_maps;
     const long long N = (long long)H * W;
     size_t n_idx = 0;
@@ -2533,6 +2542,7 @@ void eval_maps(hipStream_t s, const EvalSource& src, const std::function<void(hi
     int* idx = nullptr;
     PostScratch post_scratch;
     MatchScratch match_scratch;
+    P3dFullExtra x;
     const int post_chunk = std::min(B, P3D_POST_CHUNK);
     auto layout = [&](Carve& c) {
         P = c.take<float>((size_t)B * N);
@@ -2545,6 +2555,7 @@ void eval_maps(hipStream_t s, const EvalSource& src, const std::function<void(hi
         carve_full(c, a, r, meta);
         if (plan.on) post_carve(c, post_scratch, plan, post_chunk, N, false);
         match_carve(c, match_scratch, match, post_chunk, N);
+        if (xon) { x.part = c.take<double>((size_t)B * a.nblk * P3D_FULL_EXTRA_PARTS); x.out = c.take<double>((size_t)B * 2); }
     };
     Carve c;
     layout(c);                                 // sizes the scratch
@@ -2575,11 +2586,16 @@ void eval_maps(hipStream_t s, const EvalSource& src, const std::function<void(hi
         HIPCHECK(p3d_resize_f32(src.p, src.map_stride, src.elem_stride, B, src.h, src.w, P, H, W, s));
     if (!density_first) HIPCHECK(p3d_mapf_density(dens, B, Hd, Wd, D, H, W, s));      // test.py's density: uint8 resize (dataflow.py:236-238)
     HIPCHECK(p3d_full_moments(a, s));
+    if (xon) {
+        x.flags = extra->flags; x.base = extra->base; x.bstat = extra->bstat;
+        HIPCHECK(p3d_full_extra(a, x, s));
+    }
     HIPCHECK(p3d_full_rank(a, s));
     HIPCHECK(p3d_full_borji(a, r, s));
     if (stage_ms) HIPCHECK(hipEventRecord(ev[2], s));
     std::vector<double> st((size_t)B * P3D_FULL_STATS);
     HIPCHECK(copy_now(out, dout, (size_t)B * 5 * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (xon) HIPCHECK(copy_now(extra->out, x.out, (size_t)B * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHECK(copy_now(st.data(), a.stats, st.size() * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHECK(hipStreamSynchronize(s));
     if (stage_ms) {
@@ -2659,9 +2675,20 @@ int p3d_eval_last_frames(p3d_handle* h, const unsigned char* density, int Hd, in
     const long long hw = (long long)pr->H * pr->W;
     std::function<void(hipStream_t)> prepare;
     if (pr->materialize && h->last_forward_fused) prepare = pr->materialize;
+    // p3d_set_eval_extra: its launch joins the sequence; an evaluation of another size than the baseline's runs without it and
+    // p3d_last_eval_extra says so
+    EvalExtra extra{h->extra_flags, h->extra_base, h->extra_bstat, h->extra_H, h->extra_W, nullptr};
+    const bool fits = !(extra.flags & P3D_EVAL_INFO_GAIN) || (extra.H == H && extra.W == W);
+    std::vector<double> xv((size_t)pr->N * 2);
+    extra.out = xv.data();
+    if (extra.flags) { h->extra_state = p3d_handle::EXTRA_NONE; h->extra_eval_H = H; h->extra_eval_W = W; }
     eval_maps(h->stream, {pr->p + (size_t)(T - 1) * hw * pr->ld, (long long)T * hw * pr->ld, pr->ld, pr->N, pr->H, pr->W}, prepare,
               density, Hd, Wd, fixation, H, W, jitter, borji_idx, n_fix, n_rep, step_size, out, stage_ms,
-              h->post_on ? &h->post_cfg : nullptr, h->match_cfg.on() ? &h->match_cfg : nullptr);
+              h->post_on ? &h->post_cfg : nullptr, h->match_cfg.on() ? &h->match_cfg : nullptr, extra.flags && fits ? &extra : nullptr);
+    if (extra.flags) {
+        h->extra_state = fits ? p3d_handle::EXTRA_HAVE : p3d_handle::EXTRA_SHAPE;
+        if (fits) h->extra_last.swap(xv);
+    }
     API_END
 }
 
@@ -2703,6 +2730,109 @@ int p3d_debug_eval_maps_match(int device, const float* maps, int n_maps, int h, 
     DevArr<float> src((size_t)n_maps * per_map, maps);
     eval_maps(nullptr, {src.p, per_map, elem_stride, n_maps, h, w}, nullptr, density, Hd, Wd, fixation, H, W, jitter, borji_idx, n_fix, n_rep,
               step_size, out, nullptr, cfg, &mp);
+    API_END
+}
+
+int p3d_debug_eval_maps_extra(int device, const float* maps, int n_maps, int h, int w, int elem_stride, const unsigned char* density,
+                              int Hd, int Wd, const unsigned char* fixation, int H, int W, const double* jitter, const int* borji_idx,
+                              const int* n_fix, int n_rep, double step_size, double* out, const p3d_postprocess* cfg,
+                              const p3d_hist_match* match, int flags, const float* baseline, double* extra) {
+    API_BEGIN
+    const MatchPlan mp = p3d_handle::match_parse(match);
+    metric_args(device, maps, maps, n_maps, 1, out);
+    if (h < 1 || w < 1 || elem_stride < 1) throw P3dError("eval: empty map");
+    if (flags && !extra) throw P3dError("null argument");
+    p3d_handle::eval_extra_check(flags, baseline, H, W);           // (the baseline of the hook has the evaluation's size)
+    const long long per_map = (long long)h * w * elem_stride;
+    DevArr<float> src((size_t)n_maps * per_map, maps), base(baseline ? (size_t)H * W : 1);
+    DevArr<double> bstat(3);
+    if (baseline) p3d_handle::eval_extra_upload(baseline, H, W, base.p, bstat.p, nullptr);
+    const EvalExtra x{flags, baseline ? base.p : nullptr, baseline ? bstat.p : nullptr, H, W, extra};
+    eval_maps(nullptr, {src.p, per_map, elem_stride, n_maps, h, w}, nullptr, density, Hd, Wd, fixation, H, W, jitter, borji_idx, n_fix, n_rep,
+              step_size, out, nullptr, cfg, &mp, &x);
+    API_END
+}
+
+// ---- p3d_set_eval_extra: KL divergence and information gain (full_pass_kl, metrics_full.hip) -----------------------------------
+int p3d_set_eval_extra(p3d_handle* h, int flags, const float* baseline, int H, int W) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->set_eval_extra(flags, baseline, H, W);
+    API_END
+}
+
+int p3d_get_eval_extra(p3d_handle* h, int* flags, const float** baseline, int* H, int* W) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    if (flags) *flags = h->extra_flags;
+    if (baseline) *baseline = h->extra_base_host.empty() ? nullptr : h->extra_base_host.data();
+    if (H) *H = h->extra_H;
+    if (W) *W = h->extra_W;
+    API_END
+}
+
+int p3d_last_eval_extra(p3d_handle* h, double* out, int64_t cap) {
+    API_BEGIN
+    if (!h || !out) throw P3dError("null argument");
+    if (!h->extra_flags) throw P3dError("last_eval_extra: the option is off (p3d_set_eval_extra)");
+    if (h->extra_state == p3d_handle::EXTRA_SHAPE)
+        throw P3dError("last_eval_extra: the baseline is " + std::to_string(h->extra_H) + " x " + std::to_string(h->extra_W) +
+                       ", the last evaluation scored " + std::to_string(h->extra_eval_H) + " x " + std::to_string(h->extra_eval_W) + " maps");
+    if (h->extra_state != p3d_handle::EXTRA_HAVE) throw P3dError("last_eval_extra: no evaluation has run since the option was set");
+    if (cap < (int64_t)h->extra_last.size())
+        throw P3dError("last_eval_extra: room for " + std::to_string(cap) + " doubles, " + std::to_string(h->extra_last.size()) + " needed");
+    std::copy(h->extra_last.begin(), h->extra_last.end(), out);
+    API_END
+}
+
+}  // extern "C"
+namespace {
+// op level: the statistics of n maps by full_stats3 (private scratch), then full_pass_kl with them
+struct Stats3 {
+    DevArr<double> part, out; DevArr<unsigned> counter;
+    Stats3(int n, long long N) : part((size_t)n * p3d_full_blocks(N) * P3D_FULL_STATS3_PARTS), out((size_t)n * 3),
+                                 counter((size_t)n, std::vector<unsigned>((size_t)n, 0u).data()) {}
+    void run(const float* maps, int n, long long N) {
+        P3dFullStats3 q;
+        q.maps = maps; q.n_pix = N; q.n_maps = n; q.nblk = p3d_full_blocks(N); q.part = part.p; q.counter = counter.p; q.out = out.p;
+        HIPCHECK(p3d_full_stats3(q, nullptr));
+    }
+};
+void metric_extra(int device, int flags, const float* map1, const float* map2, const float* baseline, int n_maps, int n_pix, double* out) {
+    metric_args(device, map1, map2, n_maps, n_pix, out);
+    if (n_maps > 65535) throw P3dError("at most 65535 maps per call");
+    const bool ig = flags == P3D_EVAL_INFO_GAIN;
+    if (ig) p3d_handle::eval_extra_check(flags, baseline, 1, n_pix);
+    const size_t n = (size_t)n_maps * n_pix;
+    DevArr<float> d1(n, map1), d2(n, map2), base(ig ? n_pix : 1, ig ? baseline : nullptr);
+    Stats3 s1(n_maps, n_pix), s2(n_maps, n_pix), sb(1, n_pix);
+    s1.run(d1.p, n_maps, n_pix);
+    if (ig) sb.run(base.p, 1, n_pix); else s2.run(d2.p, n_maps, n_pix);
+    P3dFullMaps a;
+    P3dFullExtra x;
+    a.P = d1.p; a.n_pix = n_pix; a.n_maps = n_maps; a.nblk = p3d_full_blocks(n_pix); a.counter = s1.counter.p;
+    if (ig) { a.fix = d2.p; a.fix_u8 = 0; x.base = base.p; x.bstat = sb.out.p; } else { a.D = d2.p; x.ystat = s2.out.p; }
+    DevArr<double> part((size_t)n_maps * a.nblk * P3D_FULL_EXTRA_PARTS), res((size_t)n_maps * 2);
+    x.flags = flags; x.sstat = s1.out.p; x.part = part.p; x.out = res.p;
+    HIPCHECK(p3d_full_extra(a, x, nullptr));
+    std::vector<double> both((size_t)n_maps * 2);
+    res.get(both.data(), both.size());
+    for (int b = 0; b < n_maps; ++b) out[b] = both[(size_t)b * 2 + (ig ? 1 : 0)];
+}
+}  // namespace
+extern "C" {
+
+int p3d_metric_kldiv(int device, const float* map1, const float* map2, int n_maps, int n_pix, double* out) {
+    API_BEGIN
+    metric_extra(device, P3D_EVAL_KLDIV, map1, map2, nullptr, n_maps, n_pix, out);
+    API_END
+}
+
+int p3d_metric_info_gain(int device, const float* sal, const float* fix, const float* baseline, int n_maps, int n_pix, double* out) {
+    API_BEGIN
+    if (!baseline) throw P3dError("null argument");
+    metric_extra(device, P3D_EVAL_INFO_GAIN, sal, fix, baseline, n_maps, n_pix, out);
     API_END
 }
 

@@ -594,6 +594,71 @@
     }
     void set_hist_match(const p3d_hist_match* c) { match_cfg = match_parse(c); }      // (parsed first: a refusal changes nothing)
 
+    // ---- KL divergence and information gain of the evaluation pass (p3d_set_eval_extra; metrics_full.hip) ----
+    // Off by default, and off nothing here runs or exists.  The baseline, its three statistics and the scratch of their one launch
+    // are private allocations (freed when the option goes off and by the destructor, not part of `allocs`): no step, launch list
+    // or captured graph names them.  The values of the last p3d_eval_last_frames stay on the host until p3d_last_eval_extra.
+    int extra_flags = 0, extra_H = 0, extra_W = 0;
+    float* extra_base = nullptr; double* extra_bstat = nullptr;
+    std::vector<float> extra_base_host;        // p3d_get_eval_extra hands the baseline back
+    std::vector<double> extra_last;            // [B][2] of the last evaluation
+    enum { EXTRA_NONE = 0, EXTRA_HAVE = 1, EXTRA_SHAPE = 2 };
+    int extra_state = EXTRA_NONE, extra_eval_H = 0, extra_eval_W = 0;
+    void eval_extra_free() {
+        for (void* p : {(void*)extra_base, (void*)extra_bstat}) if (p) hipFree(p);
+        extra_base = nullptr; extra_bstat = nullptr;
+        extra_base_host.clear(); extra_last.clear();
+        extra_flags = 0; extra_H = extra_W = 0; extra_state = EXTRA_NONE;
+    }
+    // what the header asks of a setting; throws before anything changes
+    static void eval_extra_check(int flags, const float* baseline, int H, int W) {
+        if (flags & ~(P3D_EVAL_KLDIV | P3D_EVAL_INFO_GAIN)) throw P3dError("eval_extra: unknown flags " + std::to_string(flags));
+        const bool ig = (flags & P3D_EVAL_INFO_GAIN) != 0;
+        if (ig != (baseline != nullptr)) throw P3dError(ig ? "eval_extra: P3D_EVAL_INFO_GAIN needs a baseline" : "eval_extra: a baseline is given without P3D_EVAL_INFO_GAIN");
+        if (!ig) return;
+        if (H < 1 || W < 1 || (long long)H * W > INT32_MAX / 2) throw P3dError("eval_extra: the baseline is H x W floats, 1 <= H * W <= 2^30");
+        const size_t n = (size_t)H * W;
+        bool varies = false;
+        for (size_t i = 0; i < n; ++i) {
+            if (!std::isfinite(baseline[i])) throw P3dError("eval_extra: the baseline must be finite (element " + std::to_string(i) + ")");
+            varies = varies || baseline[i] != baseline[0];
+        }
+        if (!varies) throw P3dError("eval_extra: the baseline must not be constant");
+    }
+    // a baseline on the device with its statistics, one launch on stream s (synchronised on return): base [H * W], bstat [3]
+    static void eval_extra_upload(const float* baseline, int H, int W, float* base, double* bstat, hipStream_t s) {
+        const long long N = (long long)H * W;
+        P3dFullStats3 q;
+        q.maps = base; q.n_pix = N; q.n_maps = 1; q.nblk = p3d_full_blocks(N); q.out = bstat;
+        HIPCHECK(hipMalloc((void**)&q.part, (size_t)q.nblk * P3D_FULL_STATS3_PARTS * sizeof(double)));
+        hipError_t e = hipMalloc((void**)&q.counter, sizeof(unsigned));
+        if (e == hipSuccess) e = copy_now(base, baseline, (size_t)N * sizeof(float), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = fill_now(q.counter, 0, sizeof(unsigned), s);
+        if (e == hipSuccess) e = p3d_full_stats3(q, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        hipFree(q.part);
+        if (q.counter) hipFree(q.counter);
+        HIPCHECK(e);
+    }
+    void set_eval_extra(int flags, const float* baseline, int H, int W) {
+        eval_extra_check(flags, baseline, H, W);
+        float* nb = nullptr; double* ns = nullptr;
+        if (baseline) {                        // the new copy first: a failure changes nothing
+            try {
+                HIPCHECK(hipMalloc((void**)&nb, (size_t)H * W * sizeof(float)));
+                HIPCHECK(hipMalloc((void**)&ns, 3 * sizeof(double)));
+                eval_extra_upload(baseline, H, W, nb, ns, stream);
+            } catch (...) {
+                if (nb) hipFree(nb);
+                if (ns) hipFree(ns);
+                throw;
+            }
+        }
+        eval_extra_free();
+        extra_flags = flags; extra_base = nb; extra_bstat = ns;
+        if (baseline) { extra_H = H; extra_W = W; extra_base_host.assign(baseline, baseline + (size_t)H * W); }
+    }
+
     // ---- resident video inference (p3d_video_*; video.hip) ---------------------------------------------
     // Nothing exists before the first p3d_video_open and nothing here runs while no video is open.  The stores are private
     // allocations (freed by p3d_video_close, not part of `allocs`): no step, launch list or captured graph names them.  The gather
@@ -1103,6 +1168,7 @@
         if (ev_aug1) hipEventDestroy(ev_aug1);
         for (hipEvent_t e : ev_vid) if (e) hipEventDestroy(e);
         video_free();
+        eval_extra_free();
         // the streams go back to the pool (net.hip, "stream pool"); every path here has synchronised the device or never launched
         if (side_stream) { if (side_pooled) give_stream(cfg.device, 1, side_stream); else hipStreamDestroy(side_stream); }
         for (void* p : allocs) hipFree(p);

@@ -778,6 +778,29 @@ int p3d_full_blocks(long long n_pix);
 hipError_t p3d_full_moments(const P3dFullMaps& a, hipStream_t s);        // stats, CC, NSS, the fixated values
 hipError_t p3d_full_rank(const P3dFullMaps& a, hipStream_t s);           // thresholds sorted; SIM, AUC_Judd
 hipError_t p3d_full_borji(const P3dFullMaps& a, const P3dFullBorji& r, hipStream_t s);
+// KL divergence and information gain of the same maps (p3d_set_eval_extra; the law in include/p3d_hip.h), one launch after
+// p3d_full_moments: it reads pass A's stats and per-block sums (partA), P, and by flag D (KL) or fix and the baseline (IG).
+enum { P3D_EXTRA_KLDIV = 1, P3D_EXTRA_INFO_GAIN = 2 };
+constexpr int P3D_FULL_STATS3_PARTS = 4, P3D_FULL_EXTRA_PARTS = 3;
+struct P3dFullStats3 {               // min, max, sum of n_maps maps of n_pix floats -> out[n_maps][3], pass A's order and NaN rule
+    const float* maps = nullptr;
+    long long n_pix = 0;
+    int n_maps = 0, nblk = 0;        // nblk = p3d_full_blocks(n_pix)
+    double* part = nullptr;          // [n_maps][nblk][P3D_FULL_STATS3_PARTS]
+    unsigned* counter = nullptr;     // [n_maps] arrival counters, zero at launch (and after)
+    double* out = nullptr;
+};
+struct P3dFullExtra {
+    int flags = 0;                   // P3D_EXTRA_*
+    const float* base = nullptr;     // IG: the baseline, ONE map [n_pix] for all maps
+    const double* bstat = nullptr;   // IG: its min, max, sum (p3d_full_stats3)
+    const double* sstat = nullptr;   // op level: [n_maps][3] of P by p3d_full_stats3 instead of pass A's; D is then read as it is
+    const double* ystat = nullptr;   // op level with KL: [n_maps][3] of D
+    double* part = nullptr;          // [n_maps][nblk][P3D_FULL_EXTRA_PARTS]
+    double* out = nullptr;           // [n_maps][2]: KL, IG; NaN for a metric that is off
+};
+hipError_t p3d_full_stats3(const P3dFullStats3& q, hipStream_t s);
+hipError_t p3d_full_extra(const P3dFullMaps& a, const P3dFullExtra& e, hipStream_t s);      // uses a.counter like the passes
 
 // ---- smoothing and normalisation of output maps (postprocess.hip; p3d_set_postprocess, the contract in include/p3d_hip.h) -----
 // One launch sequence on n maps of H x W floats, every stage optional:

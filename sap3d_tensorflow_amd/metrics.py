@@ -63,6 +63,50 @@ def NSS_batch(saliency_maps, fixation_maps, device=0):
     return _two_map(lib().p3d_metric_nss, saliency_maps, np.asarray(fixation_maps, dtype=np.float32), True, device)
 
 
+def KLdiv(saliency_map, fixation_map, device=0):
+    """KL divergence of the density `fixation_map` from `saliency_map`, each scaled to sum 1 (utils/metrics.py:338-362 with its
+    resize taken as the identity; float64, eps = 2.2204e-16 -- include/p3d_hip.h, KLDIV)."""
+    return _two_map(lib().p3d_metric_kldiv, saliency_map, fixation_map, False, device)
+
+
+def KLdiv_batch(saliency_maps, density_maps, device=0):
+    return _two_map(lib().p3d_metric_kldiv, saliency_maps, density_maps, True, device)
+
+
+def _info_gain(sal, fix, baseline, batched, device):
+    a, b = _maps(sal, np.asarray(fix, dtype=np.float32))
+    n = a.shape[0] if batched else 1
+    base = np.ascontiguousarray(baseline, dtype=np.float32)
+    if base.shape != a.shape[-2:] and base.shape != (a.size // n,):
+        raise ValueError("the baseline is one map of the maps' shape %s, not %s" % (a.shape[-2:], base.shape))
+    out = np.empty(n, np.float64)
+    check(lib().p3d_metric_info_gain(device, _fp(a), _fp(b), _fp(base), n, a.size // n, _dp(out)))
+    return out if batched else float(out[0])
+
+
+def InfoGain(saliency_map, fixation_map, baseline_map, device=0):
+    """Information gain of `saliency_map` over `baseline_map` at the fixated pixels (fixation_map > 0.5), in bits: the MIT
+    saliency benchmark's InfoGain (include/p3d_hip.h, INFO GAIN).  NaN when nothing is fixated or a map is constant."""
+    return _info_gain(saliency_map, fixation_map, baseline_map, False, device)
+
+
+def InfoGain_batch(saliency_maps, fixation_maps, baseline_map, device=0):
+    """[n, H, W] maps against ONE baseline [H, W]."""
+    return _info_gain(saliency_maps, fixation_maps, baseline_map, True, device)
+
+
+def eval_extra_flags(extra):
+    """P3D_EVAL_* flags of `extra`: a name ("kldiv", "info_gain") or a collection of names."""
+    from ._lib import EVAL_EXTRA
+    names = [extra] if isinstance(extra, str) else list(extra)
+    flags = 0
+    for k in names:
+        if k not in EVAL_EXTRA:
+            raise ValueError("extra metric %r: have %s" % (k, sorted(EVAL_EXTRA)))
+        flags |= EVAL_EXTRA[k]
+    return flags
+
+
 def _judd(sal, fix, jitter, batched, device, rng):
     a, b = _maps(sal, np.asarray(fix, dtype=np.float32))
     n = a.shape[0] if batched else 1
@@ -168,14 +212,17 @@ def eval_draws(fixation, jitter, n_rep, rng=None):
 
 
 def evaluate_maps(maps, density, fixation, size=None, jitter=True, n_rep=100, step_size=0.1, rng=None, device=0, postprocess=None,
-                  hist_match=None, nbins=256):
+                  hist_match=None, nbins=256, extra=None, baseline=None):
     """Test hook (p3d_debug_eval_maps): P3DSession.evaluate's device pass on supplied maps instead of a session's prediction ->
     [n, 5] float64: CC, SIM, AUC_Judd, AUC_Borji, NSS.  maps: float32 [n, h, w], or [n, h, w, c] of which channel 0 is scored
     (the way the prediction buffer is addressed); density uint8 [n, Hd, Wd]; fixation uint8 [n, H, W] with (H, W) == size
     (default: the fixation maps' own).  The draws are evaluate's (eval_draws).  postprocess: dict(sigma, radius, norm) as
     P3DSession.set_postprocess takes them -- the smoothing / normalisation stage runs between the resize and the metrics
     (p3d_debug_eval_maps_post).  hist_match: "density" or a table (cdf, bin_centers) as P3DSession.set_hist_match takes them, with
-    `nbins` -- the histogram-matching stage runs after the blur and before the normalisation (p3d_debug_eval_maps_match)."""
+    `nbins` -- the histogram-matching stage runs after the blur and before the normalisation (p3d_debug_eval_maps_match).
+    extra: "kldiv", "info_gain" or both in a collection, as P3DSession.set_eval_extra's launch (p3d_debug_eval_maps_extra), with
+    `baseline` float32 [H, W] for the information gain; the result is then (the [n, 5] array, [n, 2] float64: KL, IG -- NaN for
+    the one that is off)."""
     m = np.ascontiguousarray(maps, dtype=np.float32)
     dens = np.ascontiguousarray(density)
     fix = np.ascontiguousarray(fixation)
@@ -197,6 +244,21 @@ def evaluate_maps(maps, density, fixation, size=None, jitter=True, n_rep=100, st
             dens.shape[1], dens.shape[2], fix.ctypes.data_as(u8), int(H), int(W),
             _dp(jit) if jit is not None else None, idx.ctypes.data_as(ip), n_fix.ctypes.data_as(ip),
             int(n_rep), float(step_size), _dp(out))
+    if extra is not None:
+        from .dataflow import _match_cfg, _post_cfg
+        flags = eval_extra_flags(extra)
+        base = None
+        if baseline is not None:
+            base = np.ascontiguousarray(baseline, dtype=np.float32)
+            if base.shape != (H, W):
+                raise ValueError("the baseline is %s, the fixation maps %s" % (base.shape, (H, W)))
+        post = postprocess or {}
+        cfg = _post_cfg(post.get("sigma", 0.), post.get("radius", 0), post.get("norm", "none"))
+        mc, keep = _match_cfg(hist_match if hist_match is not None else "off", nbins)
+        xout = np.empty((n, 2), np.float64)
+        check(lib().p3d_debug_eval_maps_extra(*(args + (C.byref(cfg), C.byref(mc), flags, _fp(base) if base is not None else None,
+                                                        _dp(xout)))))
+        return out, xout
     if hist_match is not None:
         from .dataflow import _match_cfg, _post_cfg
         post = postprocess or {}

@@ -501,6 +501,42 @@ class P3DSession:
             out["bin_centers"] = np.array(cfg.centres[:cfg.nt], np.float64)
         return out
 
+    # ---- KL divergence and information gain of the evaluation pass (p3d_set_eval_extra) -----------------
+    def set_eval_extra(self, kldiv=True, info_gain=False, baseline=None):
+        """Score KL divergence (the reference's utils/metrics.py KLdiv) and / or information gain over `baseline` (the MIT
+        benchmark's InfoGain; float32 [H, W] at the fixation maps' size, e.g. a centre prior or the mean training density) in
+        every evaluate, at scoring resolution on the device: one more launch on the map the other metrics score
+        (include/p3d_hip.h holds the arithmetic).  evaluate returns what it returns; last_eval_extra() has the two numbers per
+        clip.  set_eval_extra(False) switches the option off, the default.  Training never sees it."""
+        flags = (_lib.EVAL_EXTRA["kldiv"] if kldiv else 0) | (_lib.EVAL_EXTRA["info_gain"] if info_gain else 0)
+        base, H, W = None, 0, 0
+        if baseline is not None:
+            base = np.ascontiguousarray(baseline, dtype=np.float32)
+            if base.ndim != 2:
+                raise ValueError("the baseline is one [H, W] map")
+            H, W = base.shape
+        check(lib().p3d_set_eval_extra(self._h, flags, fptr(base) if base is not None else None, H, W))
+
+    @property
+    def eval_extra(self):
+        """None while the option is off, else dict(kldiv, info_gain, baseline: float32 [H, W] or None)."""
+        flags, H, W = C.c_int(0), C.c_int(0), C.c_int(0)
+        p = C.POINTER(C.c_float)()
+        check(lib().p3d_get_eval_extra(self._h, C.byref(flags), C.byref(p), C.byref(H), C.byref(W)))
+        if not flags.value:
+            return None
+        base = np.ctypeslib.as_array(p, shape=(H.value, W.value)).copy() if p else None
+        return dict(kldiv=bool(flags.value & _lib.EVAL_EXTRA["kldiv"]), info_gain=bool(flags.value & _lib.EVAL_EXTRA["info_gain"]),
+                    baseline=base)
+
+    def last_eval_extra(self):
+        """[B, 2] float64: KL divergence and information gain of every clip of the last evaluate (NaN for the one that is off).
+        Raises while the option is off, before an evaluate has run with it, and after an evaluate at another size than the
+        baseline's."""
+        out = np.empty((self.x_shape[0], 2), np.float64)
+        check(lib().p3d_last_eval_extra(self._h, out.ctypes.data_as(_lib._dp), out.size))
+        return out
+
     # ---- moving average of the weights (p3d_set_ema) ---------------------------------------------------
     def set_ema(self, decay, warmup=False):
         """Keep an exponential moving average of every trainable variable, as tf.train.ExponentialMovingAverage(decay).apply(
