@@ -646,6 +646,74 @@ int p3d_debug_wgrad_group(int device, int n, const float* const* x, const int* l
                           const float* const* dy, const int* lddy, const int* offdy, const int64_t* ws, const int* s, const int* transpose,
                           float* const* dw, float* const* dbias, int polite, int greedy, char* kernel, int kernel_cap, int* cuts,
                           int* info);
+/* Test hooks: the fused-BatchNorm launches of the bottleneck convs (p3d_set_bn_fusion) -- operand transforms, coefficient folds,
+ * gated epilogues, finalize launches -- built by the builders conv() uses, on host arrays.  Slices as above.  Every array a launch
+ * may WRITE is in / out at its full extent: the caller prefills it and gets every float back, touched or not.
+ *
+ * p3d_fused_bn: one BatchNorm source of a RELU1 / RELU2 operand.  y [rows of the conv's input][ld], the raw tensor the BatchNorm
+ * normalises, `channels of the conv's input` floats at column off (two sources that name the SAME y pointer share one device
+ * buffer).  partials [nparts][C][2] (sum, sum of squares) over `rows` rows, or null: the launch reads scale / shift as given.
+ * With partials: publish = 1 makes block 0 of slice 0 (or, above P3D_FOLD_MAX = 32 partials, a bn_finalize_kernel launch) write
+ * scale, shift, mean, invstd [C] and, with update_moving, the moving statistics; publish = 0 writes none of them.
+ *
+ * p3d_fused_bn_grad: the BatchNorm a GRAD operand differentiates through.  y [rows of the conv's output][ld]: the BatchNorm's input
+ * (the conv's own output); gamma, mean, invstd [Cout].  partials [nparts][Cout][2] (sum g, sum g*xhat) over `rows` rows with
+ * publish (coef [3][Cout], dgamma, dbeta [Cout] written; above 32 partials by a bn_grad_finalize_kernel launch), or null: coef read.
+ *
+ * p3d_fused_gate: one gate of the epilogue.  y [rows of the conv's input][ld_y] and scale, shift, mean, invstd [Cin] are read;
+ * out [rows][ld_out] receives the gated gradient; part [part_rows][Cin][2] the per-tile-row (sum g, sum g*xhat): the launch must
+ * need at most part_rows rows (checked before it goes out).
+ *
+ * p3d_fused_conv: kind 0 = forward with at = 1 (RELU1) or 2 (RELU2) on src[]; out = the conv's output.  kind 1 = input gradient:
+ * g [rows of the conv's output][ld_g] the gradient of that output, out = the raw result buffer (written when there is no gate or
+ * raw_store = 1, read when accum = 1), grad = 1: the GRAD transform of g by gbn; ngate gates.  xshape = shape of the conv's input.
+ * Returned in the struct: gpart_rows = rows of gradient partials every gate received.  kernels / splits as p3d_debug_conv_launch.
+ *
+ * p3d_debug_fused_wgrad: as p3d_debug_wgrad_group; per problem i additionally xt[i] = 0 / 1 / 2 with xs1 / xt1 [Cin] (and x2 with
+ * ldx2 / offx2, xs2, xt2 for xt = 2), dyt[i] = 0 / 1 with dy2 [rows][lddy2] at offdy2 and dcoef [3][Cout].
+ *
+ * p3d_debug_fused_reject: the launcher's answer (a hipError_t; *validator: the filter gradient validator's, 1 = takes it) to malformed
+ * fused launches, which must never go out.  which: 0 / 1 RELU1 with 0 / 33 partials, 2 / 3 GRAD with 0 / 33, 4 a gate beside a
+ * statistics sink, 5 RELU1 with transposed weights, 6 RELU2 with a second row length that is no multiple of 4, 7 xt with pair,
+ * 8 xt = 2 with such a row length, 9 dyt with pair. */
+typedef struct p3d_fused_bn {
+    const float* y; int ld, off;
+    const float* gamma; const float* beta;
+    const float* partials; int nparts; int64_t rows; int publish, update_moving;
+    float* scale; float* shift; float* mean; float* invstd;
+    float* moving_mean; float* moving_var;
+} p3d_fused_bn;
+typedef struct p3d_fused_bn_grad {
+    const float* y; int ld, off;
+    const float* gamma; const float* mean; const float* invstd;
+    const float* partials; int nparts; int64_t rows; int publish;
+    float* coef; float* dgamma; float* dbeta;
+} p3d_fused_bn_grad;
+typedef struct p3d_fused_gate {
+    const float* y; int ld_y, off_y;
+    const float* scale; const float* shift; const float* mean; const float* invstd;
+    float* out; int ld_out, off_out;
+    float* part; int part_rows;
+} p3d_fused_gate;
+typedef struct p3d_fused_conv {
+    int kind;
+    int64_t xshape[5]; int64_t wshape[5]; int stride[3];
+    const float* w; const float* bias; int f16;
+    int at; p3d_fused_bn src[2];
+    const float* g; int ld_g, off_g;
+    int grad; p3d_fused_bn_grad gbn;
+    int ngate; p3d_fused_gate gate[2]; int raw_store, accum;
+    float* out; int ld_out, off_out;
+    int gpart_rows;
+} p3d_fused_conv;
+int p3d_debug_fused_conv(int device, p3d_fused_conv* a, char* kernels, int kernels_cap, int* splits);
+int p3d_debug_fused_wgrad(int device, int n, const float* const* x, const int* ldx, const int* offx, const int64_t* xs,
+                          const float* const* dy, const int* lddy, const int* offdy, const int64_t* ws, const int* s,
+                          const int* xt, const float* const* x2, const int* ldx2, const int* offx2, const float* const* xs1,
+                          const float* const* xt1, const float* const* xs2, const float* const* xt2, const int* dyt,
+                          const float* const* dy2, const int* lddy2, const int* offdy2, const float* const* dcoef,
+                          float* const* dw, float* const* dbias, char* kernel, int kernel_cap, int* cuts, int* info);
+int p3d_debug_fused_reject(int device, int which, int* error, int* validator);
 int p3d_debug_max_pool3d(int device, const float* x, int ldx, int offx, const int64_t xshape[5], const int ksize[3], const int s[3],
                          float* y, int ldy, int offy);
 int p3d_debug_max_pool3d_grad(int device, const float* x, int ldx, int offx, const int64_t xshape[5], const int ksize[3], const int s[3],

@@ -62,6 +62,34 @@ EVAL_EXTRA = {"kldiv": 1, "info_gain": 2}
 VIDEO_MODES = {"newest": 0, "mean": 1}
 
 
+# the descriptors of p3d_debug_fused_conv (include/p3d_hip.h)
+_FP = C.POINTER(C.c_float)
+
+
+class P3dFusedBn(C.Structure):
+    _fields_ = [("y", _FP), ("ld", C.c_int), ("off", C.c_int), ("gamma", _FP), ("beta", _FP), ("partials", _FP), ("nparts", C.c_int),
+                ("rows", C.c_int64), ("publish", C.c_int), ("update_moving", C.c_int), ("scale", _FP), ("shift", _FP), ("mean", _FP),
+                ("invstd", _FP), ("moving_mean", _FP), ("moving_var", _FP)]
+
+
+class P3dFusedBnGrad(C.Structure):
+    _fields_ = [("y", _FP), ("ld", C.c_int), ("off", C.c_int), ("gamma", _FP), ("mean", _FP), ("invstd", _FP), ("partials", _FP),
+                ("nparts", C.c_int), ("rows", C.c_int64), ("publish", C.c_int), ("coef", _FP), ("dgamma", _FP), ("dbeta", _FP)]
+
+
+class P3dFusedGate(C.Structure):
+    _fields_ = [("y", _FP), ("ld_y", C.c_int), ("off_y", C.c_int), ("scale", _FP), ("shift", _FP), ("mean", _FP), ("invstd", _FP),
+                ("out", _FP), ("ld_out", C.c_int), ("off_out", C.c_int), ("part", _FP), ("part_rows", C.c_int)]
+
+
+class P3dFusedConv(C.Structure):
+    _fields_ = [("kind", C.c_int), ("xshape", C.c_int64 * 5), ("wshape", C.c_int64 * 5), ("stride", C.c_int * 3), ("w", _FP),
+                ("bias", _FP), ("f16", C.c_int), ("at", C.c_int), ("src", P3dFusedBn * 2), ("g", _FP), ("ld_g", C.c_int),
+                ("off_g", C.c_int), ("grad", C.c_int), ("gbn", P3dFusedBnGrad), ("ngate", C.c_int), ("gate", P3dFusedGate * 2),
+                ("raw_store", C.c_int), ("accum", C.c_int), ("out", _FP), ("ld_out", C.c_int), ("off_out", C.c_int),
+                ("gpart_rows", C.c_int)]
+
+
 class P3dError(RuntimeError):
     pass
 
@@ -189,6 +217,12 @@ SIGNATURES = {
     "p3d_op_bias_add_grad": (C.c_int, [C.c_int, _fp, C.c_int64, C.c_int, _fp]),
     "p3d_debug_conv_launch": (C.c_int, [C.c_int, C.c_int, _fp, C.c_int, C.c_int, _i64p, _fp, _i64p, _ip, _fp, C.c_int, C.c_int, _fp,
                                         C.c_int, C.c_int, C.c_char_p, C.c_int, _ip]),
+    "p3d_debug_fused_conv": (C.c_int, [C.c_int, C.POINTER(P3dFusedConv), C.c_char_p, C.c_int, _ip]),
+    "p3d_debug_fused_wgrad": (C.c_int, [C.c_int, C.c_int, C.POINTER(_fp), _ip, _ip, _i64p, C.POINTER(_fp), _ip, _ip, _i64p, _ip,
+                                        _ip, C.POINTER(_fp), _ip, _ip, C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), _ip,
+                                        C.POINTER(_fp), _ip, _ip, C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.c_char_p, C.c_int, _ip,
+                                        _ip]),
+    "p3d_debug_fused_reject": (C.c_int, [C.c_int, C.c_int, _ip, _ip]),
     "p3d_debug_wgrad_group": (C.c_int, [C.c_int, C.c_int, C.POINTER(_fp), _ip, _ip, _i64p, C.POINTER(_fp), _ip, _ip, _i64p, _ip, _ip,
                                         C.POINTER(_fp), C.POINTER(_fp), C.c_int, C.c_int, C.c_char_p, C.c_int, _ip, _ip]),
     "p3d_debug_max_pool3d": (C.c_int, [C.c_int, _fp, C.c_int, C.c_int, _i64p, _ip, _ip, _fp, C.c_int, C.c_int]),

@@ -695,6 +695,108 @@ void launch_wgrad_group(const Ctx& c, const std::vector<WgradArgs>& probs, const
     launch(c, name, fl, by, [&]() { return p3d_launch_wgrad2_group(probs.data(), (int)probs.size(), c.s); });
 }
 
+// ---- BatchNorm fused into the convs' operand paths: the launches, on plain descriptors ------------------------------------------
+// conv() (net_ops.inc) and the test hooks p3d_debug_fused_conv / p3d_debug_fused_wgrad build their fused launches with these:
+// device pointers, row strides, channel counts, partial pointers and counts, rows and publish / update-moving flags in; the
+// fields of IgemmArgs / WgradArgs (and the finalize launches) out.  Nothing here knows an Act or a BN.
+struct FusedBn {               // forward: the BatchNorm of one source of a RELU1 / RELU2 operand
+    const float* gamma = nullptr; const float* beta = nullptr; int C = 0;
+    float *scale = nullptr, *shift = nullptr, *mean = nullptr, *invstd = nullptr;      // the published values
+    float *moving_mean = nullptr, *moving_var = nullptr;
+    const float* part = nullptr; int nparts = 0;      // the producer's (sum, sumsq) partials [nparts][C][2]
+    int64_t rows = 0;                                 // rows of the normalised tensor
+    int pub = 0;                                      // 0: read the published scale / shift, 1: fold the partials and publish, 2: fold only
+    bool update_moving = false;
+};
+struct FusedBnGrad {           // backward: the BatchNorm a GRAD operand / a dyt filter gradient differentiates through
+    const float* gamma = nullptr; const float* mean = nullptr; const float* invstd = nullptr; int C = 0;
+    float *coef = nullptr, *dgamma = nullptr, *dbeta = nullptr;      // published k1 / k2 / k3 [3][C] and the parameter gradients
+    const float* part = nullptr; int nparts = 0;      // the gating launch's (sum g, sum g*xhat) partials [nparts][C][2]
+    int64_t rows = 0;
+};
+// THE rule: up to P3D_FOLD_MAX partials a consuming launch folds in its own prologue; more go through a finalize launch, and
+// every consumer then reads the published values.
+inline bool fused_needs_finalize(int nparts) { return nparts > P3D_FOLD_MAX; }
+// forward: the finalize launch of a publishing source with many partials; true when it went out (the values are then complete)
+bool fused_bn_prefinalize(const Ctx& c, const FusedBn& d) {
+    if (d.pub != 1 || !fused_needs_finalize(d.nparts)) return false;
+    BnParams bp;
+    memset(&bp, 0, sizeof(bp));
+    bp.gamma = d.gamma; bp.beta = d.beta; bp.moving_mean = d.moving_mean; bp.moving_var = d.moving_var;
+    bp.statpart = d.part; bp.nparts = d.nparts; bp.scale = d.scale; bp.shift = d.shift; bp.mean = d.mean; bp.invstd = d.invstd; bp.C = d.C;
+    launch(c, "bn_finalize_kernel", 0, 64.0 * d.C, [&]() { return p3d_bn_finalize(bp, (long)d.rows, 1, d.update_moving ? 1 : 0, 1e-3f, c.s); });
+    return true;
+}
+BnFold fused_bn_fold(const FusedBn& d, bool finalized) {
+    BnFold f;
+    memset(&f, 0, sizeof(f));
+    f.gamma = d.gamma; f.beta = d.beta; f.C = d.C;
+    f.scale = d.scale; f.shift = d.shift; f.mean = d.mean; f.invstd = d.invstd;
+    f.moving_mean = d.moving_mean; f.moving_var = d.moving_var;
+    f.inv_m = 1.0 / (double)d.rows; f.eps = 1e-3f;
+    const bool fold = d.pub != 0 && !finalized;
+    if (fold) { f.part = d.part; f.nparts = d.nparts; }
+    f.publish = (fold && d.pub == 1) ? 1 : 0;
+    f.update_moving = d.update_moving ? 1 : 0;
+    return f;
+}
+// RELU1 / RELU2 on a forward launch whose gathered operand `a.x` is the raw tensor of source 0; y2 / ld2: the raw tensor of source 1
+void fused_forward_operand(IgemmArgs& a, int at, const FusedBn& s1, bool fin1, const float* y2, int ld2, const FusedBn* s2, bool fin2) {
+    if (at != P3D_AT_RELU1 && at != P3D_AT_RELU2) throw P3dError("a fused forward operand is RELU1 or RELU2");
+    a.at_mode = at;
+    a.f1 = fused_bn_fold(s1, fin1);
+    if (at == P3D_AT_RELU2) {
+        if (!s2) throw P3dError("RELU2 needs its second source");
+        a.x2 = y2; a.ldx2 = ld2; a.f2 = fused_bn_fold(*s2, fin2);
+    }
+}
+BnGradFold fused_bn_grad_fold(const FusedBnGrad& d, bool finalized, bool publish) {
+    BnGradFold f;
+    memset(&f, 0, sizeof(f));
+    f.gamma = d.gamma; f.mean = d.mean; f.invstd = d.invstd; f.C = d.C;
+    f.coef = d.coef; f.dgamma = d.dgamma; f.dbeta = d.dbeta;
+    f.inv_m = 1.0 / (double)d.rows;
+    const bool fold = !finalized;
+    if (fold) { f.part = d.part; f.nparts = d.nparts; }
+    f.publish = (fold && publish) ? 1 : 0;
+    return f;
+}
+// backward: the finalize launch for many gradient partials; true when it went out
+bool fused_bn_grad_prefinalize(const Ctx& c, const FusedBnGrad& d) {
+    if (!fused_needs_finalize(d.nparts)) return false;
+    const BnGradFold gf = fused_bn_grad_fold(d, false, true);
+    launch(c, "bn_grad_finalize_kernel", 0, 64.0 * d.C, [&]() { return p3d_bn_grad_finalize(gf, c.s); });
+    return true;
+}
+// GRAD on an input-gradient launch whose gathered operand `a.x` is the gated gradient; y / ldy: the BatchNorm's input there
+void fused_grad_operand(IgemmArgs& a, const float* y, int ldy, const FusedBnGrad& d, bool finalized, bool publish) {
+    a.at_mode = P3D_AT_GRAD; a.x2 = y; a.ldx2 = ldy;
+    a.gf = fused_bn_grad_fold(d, finalized, publish);
+}
+// the gated epilogue belongs to stride-1 convs whose input gradient is ONE launch
+void fused_gate_check(const int s[3], int ngate) {
+    if (ngate && (s[0] != 1 || s[1] != 1 || s[2] != 1)) throw P3dError("gated input gradients need a stride-1 conv");
+}
+// ngate gates on the launches `v` of an input gradient; returns the rows of (sum g, sum g*xhat) partials every gate gets (one per
+// output-tile row of the launch's plan; 0 when `plan_rows` is off -- a planning pass)
+int fused_gated_epilogue(std::vector<IgemmArgs>& v, int ngate, const BnGate* gate, bool raw_store, bool plan_rows) {
+    if (ngate < 1 || ngate > 2) throw P3dError("a gated epilogue has one or two gates");
+    if (v.size() != 1) throw P3dError("gated input gradient with more than one residue class");
+    IgemmArgs& a = v[0];
+    a.ngate = ngate; a.raw_store = raw_store ? 1 : 0;
+    for (int q = 0; q < ngate; ++q) a.gate[q] = gate[q];
+    if (!plan_rows) return 0;
+    IgemmArgs t = a; t.zeros = g_zero_page;
+    return p3d_igemm2_mtiles(t, p3d_igemm2_plan(t, 1));
+}
+// filter gradients: relu(scale*y + shift) (one or two sources) on the gathered side, k1*g + k2*y + k3 on the dense side
+void fused_wgrad_x(WgradArgs& wa, int xt, const float* xs1, const float* xt1, const float* x2, int ldx2, const float* xs2, const float* xt2) {
+    if (xt != 1 && xt != 2) throw P3dError("a fused filter-gradient operand has one or two sources");
+    wa.xt = xt; wa.xs1 = xs1; wa.xt1 = xt1;
+    if (xt == 2) { wa.x2 = x2; wa.ldx2 = ldx2; wa.xs2 = xs2; wa.xt2 = xt2; }
+}
+void fused_wgrad_dy(WgradArgs& wa, const float* y, int ldy, const float* coef) { wa.dyt = 1; wa.dy2 = y; wa.ldy2 = ldy; wa.dcoef = coef; }
+
 struct Op {
     std::string name, kind;
     double flops = 0, bytes = 0;            // forward algorithmic work
@@ -1362,7 +1464,6 @@ struct p3d_handle {
     // HBM speed and the convs are throughput-bound, so per-step operand work costs more than the passes it removes
     // (measured per stage).  P3D_FUSE_MAX_ROWS (read once, at p3d_create) overrides it for A/B runs.
     int64_t fuse_max_rows = 2048;
-    static constexpr int FOLD_MAX = P3D_FOLD_MAX;      // up to this many partials per channel a consumer folds in its own prologue; beyond, a finalize launch
     struct FuseSrc { Act* y = nullptr; BN* bn = nullptr; int pub = 0; };   // pub: 0 read the published scale / shift, 1 fold the partials and publish, 2 fold only
     struct ConvFuse {
         int at = 0;                          // P3D_AT_RELU1 / P3D_AT_RELU2 on the conv's input
@@ -1385,43 +1486,32 @@ struct p3d_handle {
     }
     // forward: many partials -> one finalize launch that every consumer then reads (must precede a fork to the side stream)
     std::map<BN*, bool> fwd_finalized, grad_finalized;      // per pass: the published values are complete
+    // the plain descriptors of the launch builders above (fused_bn_fold, fused_bn_grad_fold, ...)
+    FusedBn fused_bn_desc(const FuseSrc& s, int64_t rows, const Ctx& c) {
+        BN* bn = s.bn;
+        FusedBn d;
+        d.gamma = bn->gamma->p; d.beta = bn->beta->p; d.C = bn->C;
+        d.scale = bn->scale; d.shift = bn->shift; d.mean = bn->mean; d.invstd = bn->invstd;
+        d.moving_mean = bn->mm->p; d.moving_var = bn->mv->p;
+        d.part = statpart_arena + bn->part_off; d.nparts = bn->nparts;
+        d.rows = rows; d.pub = s.pub; d.update_moving = c.update_moving;
+        return d;
+    }
+    FusedBnGrad fused_grad_desc(BN* bn, int64_t rows) {
+        FusedBnGrad d;
+        d.gamma = bn->gamma->p; d.mean = bn->mean; d.invstd = bn->invstd; d.C = bn->C;
+        d.coef = bn->coef; d.dgamma = bn->gamma->g; d.dbeta = bn->beta->g;
+        d.part = statpart_arena + bn->gpart_off; d.nparts = bn->gnparts; d.rows = rows;
+        return d;
+    }
     void fused_prefinalize(const Ctx& c, const ConvFuse& cf, int64_t rows) {
         if (c.dry) return;
         for (int q = 0; q < (cf.at == P3D_AT_RELU2 ? 2 : 1); ++q) {
             BN* bn = cf.src[q].bn;
             if (cf.src[q].pub != 1) continue;
-            fwd_finalized[bn] = false;
             bn->used_batch = true;
-            if (bn->nparts > FOLD_MAX) {
-                launch(c, "bn_finalize_kernel", 0, 64.0 * bn->C, [&]() { return p3d_bn_finalize(bn_params(bn), (long)rows, 1, c.update_moving ? 1 : 0, 1e-3f, c.s); });
-                fwd_finalized[bn] = true;
-            }
+            fwd_finalized[bn] = fused_bn_prefinalize(c, fused_bn_desc(cf.src[q], rows, c));
         }
-    }
-    BnFold bn_fold(const FuseSrc& s, int64_t rows, const Ctx& c) {
-        BN* bn = s.bn;
-        BnFold f;
-        memset(&f, 0, sizeof(f));
-        f.gamma = bn->gamma->p; f.beta = bn->beta->p; f.C = bn->C;
-        f.scale = bn->scale; f.shift = bn->shift; f.mean = bn->mean; f.invstd = bn->invstd;
-        f.moving_mean = bn->mm->p; f.moving_var = bn->mv->p;
-        f.inv_m = 1.0 / (double)rows; f.eps = 1e-3f;
-        const bool fold = s.pub != 0 && !fwd_finalized[bn];
-        if (fold) { f.part = statpart_arena + bn->part_off; f.nparts = bn->nparts; }
-        f.publish = (fold && s.pub == 1) ? 1 : 0;
-        f.update_moving = c.update_moving ? 1 : 0;
-        return f;
-    }
-    BnGradFold bn_grad_fold(BN* bn, int64_t rows, bool publish) {
-        BnGradFold f;
-        memset(&f, 0, sizeof(f));
-        f.gamma = bn->gamma->p; f.mean = bn->mean; f.invstd = bn->invstd; f.C = bn->C;
-        f.coef = bn->coef; f.dgamma = bn->gamma->g; f.dbeta = bn->beta->g;
-        f.inv_m = 1.0 / (double)rows;
-        const bool fold = !grad_finalized[bn];
-        if (fold) { f.part = statpart_arena + bn->gpart_off; f.nparts = bn->gnparts; }
-        f.publish = (fold && publish) ? 1 : 0;
-        return f;
     }
     BnGate bn_gate(const FuseSrc& s) {
         BnGate g;

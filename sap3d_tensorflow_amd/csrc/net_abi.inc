@@ -2068,6 +2068,291 @@ int p3d_debug_wgrad_group(int device, int n, const float* const* x, const int* l
     API_END
 }
 
+// ---- fused-BatchNorm launches (test hooks, include/p3d_hip.h): the builders of conv() on host arrays --------------------------------
+namespace {
+// a host array that a launch may write: on the device for the launch, back in the caller's array afterwards (null: absent)
+struct InOut {
+    std::unique_ptr<DevBuf> d; float* host = nullptr; int64_t n = 0;
+    void put(float* h, int64_t count) { host = h; n = count; if (h) d.reset(new DevBuf(count, h)); }
+    float* p() const { return d ? d->p : nullptr; }
+    void back() { if (d) d->get(host, n); }
+};
+std::unique_ptr<DevBuf> dev_copy(const float* h, int64_t n) { return std::unique_ptr<DevBuf>(h ? new DevBuf(n, h) : nullptr); }
+void report_splits(const std::vector<IgemmArgs>& v, int* splits) {
+    if (!splits) return;
+    splits[0] = 1 << 30; splits[1] = 0;
+    for (const IgemmArgs& a : v) {
+        const P3dIgemmPlan pl = p3d_igemm2_plan(a, 1);
+        const int sp = pl.stream_blocks > 0 || pl.splits < 1 ? 1 : pl.splits;
+        splits[0] = std::min(splits[0], sp); splits[1] = std::max(splits[1], sp);
+    }
+    if (v.empty()) splits[0] = splits[1] = 0;
+}
+}  // namespace
+
+int p3d_debug_fused_conv(int device, p3d_fused_conv* fc, char* kernels, int kernels_cap, int* splits) {
+    API_BEGIN
+    HIPCHECK(hipSetDevice(device));
+    if (!fc || !fc->w || !fc->out) throw P3dError("null argument");
+    if (fc->kind != 0 && fc->kind != 1) throw P3dError("fused_conv: kind is 0 (forward) or 1 (input gradient)");
+    const ConvProblem p = conv_problem(fc->xshape, fc->wshape, fc->stride, 0);
+    if (p.stem) throw P3dError("fused_conv: the stem shape has its own entry points");
+    if (fc->wshape[3] != p.Cin) throw P3dError("filter Cin mismatch");
+    const int ntap = (int)(fc->wshape[0] * fc->wshape[1] * fc->wshape[2]);
+    if (fc->f16 && ntap != 1) throw P3dError("fused_conv: the fp16 option is for 1x1x1 convs");
+    ensure_zero_page();
+    DevBuf dw(prod5(fc->wshape), fc->w);
+    Ctx c;
+    std::string names;
+    std::vector<IgemmArgs> v;
+    fc->gpart_rows = 0;
+    if (fc->kind == 0) {
+        if (fc->at != P3D_AT_RELU1 && fc->at != P3D_AT_RELU2) throw P3dError("fused_conv: a forward launch has at = 1 (RELU1) or 2 (RELU2)");
+        check_slice("fused_conv (output)", fc->ld_out, fc->off_out, p.Cout);
+        std::unique_ptr<DevBuf> y[2], gamma[2], beta[2], part[2], db = dev_copy(fc->bias, p.Cout);
+        InOut pub[2][6];
+        FusedBn d[2];
+        const float* yp[2] = {nullptr, nullptr};
+        for (int q = 0; q < fc->at; ++q) {
+            const p3d_fused_bn& b = fc->src[q];
+            if (!b.y || !b.scale || !b.shift || !b.mean || !b.invstd) throw P3dError("null argument");
+            check_slice("fused_conv (source)", b.ld, b.off, p.Cin);
+            if (q == 1 && b.y == fc->src[0].y && b.ld == fc->src[0].ld) yp[1] = y[0]->p + b.off;      // two slices of ONE buffer
+            else { y[q].reset(new DevBuf(p.rows_in * b.ld, b.y)); yp[q] = y[q]->p + b.off; }
+            float* const arr[6] = {b.scale, b.shift, b.mean, b.invstd, b.moving_mean, b.moving_var};
+            for (int j = 0; j < 6; ++j) pub[q][j].put(arr[j], p.Cin);
+            d[q].C = p.Cin; d[q].rows = b.rows;
+            d[q].scale = pub[q][0].p(); d[q].shift = pub[q][1].p(); d[q].mean = pub[q][2].p(); d[q].invstd = pub[q][3].p();
+            d[q].moving_mean = pub[q][4].p(); d[q].moving_var = pub[q][5].p();
+            d[q].update_moving = b.update_moving != 0;
+            if (b.partials) {
+                if (!b.gamma || !b.beta) throw P3dError("null argument");
+                if (b.nparts < 1 || b.rows < 1) throw P3dError("fused_conv: partials need nparts >= 1 and rows >= 1");
+                if (b.publish && b.update_moving && (!b.moving_mean || !b.moving_var)) throw P3dError("null argument");
+                gamma[q] = dev_copy(b.gamma, p.Cin); beta[q] = dev_copy(b.beta, p.Cin);
+                part[q] = dev_copy(b.partials, (int64_t)b.nparts * p.Cin * 2);
+                d[q].gamma = gamma[q]->p; d[q].beta = beta[q]->p; d[q].part = part[q]->p; d[q].nparts = b.nparts;
+                d[q].pub = b.publish ? 1 : 2;
+            } else d[q].rows = 1;
+        }
+        v = p.forward(yp[0], dw.p, nullptr, db ? db->p : nullptr, nullptr, nullptr, fc->src[0].ld, fc->ld_out, 0);
+        DevBuf dout(p.rows * fc->ld_out, fc->out);
+        v[0].y = dout.p + fc->off_out;
+        traced_kernels([&]() {
+            bool fin[2] = {false, false};
+            for (int q = 0; q < fc->at; ++q) fin[q] = fused_bn_prefinalize(c, d[q]);      // (conv(): ahead of the launch, on its stream)
+            fused_forward_operand(v[0], fc->at, d[0], fin[0], yp[1], fc->src[1].ld, fc->at == P3D_AT_RELU2 ? &d[1] : nullptr, fin[1]);
+            if (fc->f16) v[0].f16 = 1;
+            run_igemm_group(c, v, false, nullptr);
+        }, names);
+        dout.get(fc->out, p.rows * fc->ld_out);
+        for (int q = 0; q < fc->at; ++q) for (int j = 0; j < 6; ++j) pub[q][j].back();
+    } else {
+        if (!fc->g) throw P3dError("null argument");
+        if (fc->bias) throw P3dError("fused_conv: an input gradient has no bias");
+        if (fc->ngate < 0 || fc->ngate > 2) throw P3dError("fused_conv: 0, 1 or 2 gates");
+        fused_gate_check(fc->stride, fc->ngate);
+        check_slice("fused_conv (gradient)", fc->ld_g, fc->off_g, p.Cout);
+        check_slice("fused_conv (raw result)", fc->ld_out, fc->off_out, p.Cin);
+        DevBuf dg(p.rows * fc->ld_g, fc->g), dout(p.rows_in * fc->ld_out, fc->out);
+        const int accum = fc->accum ? 1 : 0;
+        v = p.input_gradient(dg.p + fc->off_g, dw.p, dout.p + fc->off_out, fc->ld_g, fc->ld_out, accum);
+        if (fc->f16) for (auto& a : v) a.f16 = 1;
+        // GRAD operand
+        std::unique_ptr<DevBuf> gy, ggamma, gmean, ginv, gpart;
+        InOut gout[3];
+        FusedBnGrad gd;
+        if (fc->grad) {
+            const p3d_fused_bn_grad& b = fc->gbn;
+            if (!b.y || !b.coef) throw P3dError("null argument");
+            check_slice("fused_conv (BatchNorm input)", b.ld, b.off, p.Cout);
+            gy.reset(new DevBuf(p.rows * b.ld, b.y));
+            gout[0].put(b.coef, 3 * (int64_t)p.Cout); gout[1].put(b.dgamma, p.Cout); gout[2].put(b.dbeta, p.Cout);
+            gd.C = p.Cout; gd.rows = 1; gd.coef = gout[0].p(); gd.dgamma = gout[1].p(); gd.dbeta = gout[2].p();
+            if (b.partials) {
+                if (!b.gamma || !b.mean || !b.invstd) throw P3dError("null argument");
+                if (b.nparts < 1 || b.rows < 1) throw P3dError("fused_conv: partials need nparts >= 1 and rows >= 1");
+                if (b.publish && (!b.dgamma || !b.dbeta)) throw P3dError("null argument");
+                if (!b.publish && fused_needs_finalize(b.nparts)) throw P3dError("fused_conv: that many partials go through the finalize launch, which publishes");
+                ggamma = dev_copy(b.gamma, p.Cout); gmean = dev_copy(b.mean, p.Cout); ginv = dev_copy(b.invstd, p.Cout);
+                gpart = dev_copy(b.partials, (int64_t)b.nparts * p.Cout * 2);
+                gd.gamma = ggamma->p; gd.mean = gmean->p; gd.invstd = ginv->p; gd.part = gpart->p; gd.nparts = b.nparts; gd.rows = b.rows;
+            }
+        }
+        // gates
+        std::unique_ptr<DevBuf> qy[2], qtab[2][4];
+        InOut qout[2], qpart[2];
+        BnGate gates[2];
+        for (int q = 0; q < fc->ngate; ++q) {
+            const p3d_fused_gate& b = fc->gate[q];
+            if (!b.y || !b.scale || !b.shift || !b.mean || !b.invstd || !b.out || !b.part) throw P3dError("null argument");
+            if (b.part_rows < 1) throw P3dError("fused_conv: a gate needs room for its partials");
+            check_slice("fused_conv (gate input)", b.ld_y, b.off_y, p.Cin);
+            check_slice("fused_conv (gated gradient)", b.ld_out, b.off_out, p.Cin);
+            qy[q].reset(new DevBuf(p.rows_in * b.ld_y, b.y));
+            const float* const tabs[4] = {b.scale, b.shift, b.mean, b.invstd};
+            for (int j = 0; j < 4; ++j) qtab[q][j] = dev_copy(tabs[j], p.Cin);
+            qout[q].put(b.out, p.rows_in * b.ld_out);
+            qpart[q].put(b.part, (int64_t)b.part_rows * p.Cin * 2);
+            memset(&gates[q], 0, sizeof(BnGate));
+            gates[q].y = qy[q]->p + b.off_y; gates[q].ldy = b.ld_y;
+            gates[q].scale = qtab[q][0]->p; gates[q].shift = qtab[q][1]->p; gates[q].mean = qtab[q][2]->p; gates[q].invstd = qtab[q][3]->p;
+            gates[q].out = qout[q].p() + b.off_out; gates[q].ldo = b.ld_out;
+            gates[q].part = qpart[q].p();
+        }
+        traced_kernels([&]() {
+            if (fc->grad) {
+                const bool fin = fc->gbn.partials ? fused_bn_grad_prefinalize(c, gd) : true;      // published coefficients: nothing to fold
+                bool first = true;
+                for (auto& a : v) { fused_grad_operand(a, gy->p + fc->gbn.off, fc->gbn.ld, gd, fin, first && fc->gbn.publish); first = false; }
+            }
+            if (fc->ngate) {
+                const int mt = fused_gated_epilogue(v, fc->ngate, gates, fc->raw_store != 0, true);
+                for (int q = 0; q < fc->ngate; ++q)
+                    if (mt > fc->gate[q].part_rows) throw P3dError("gradient partials overflow their buffer");
+                fc->gpart_rows = mt;
+            }
+            run_igemm_group(c, v, accum != 0, nullptr);
+        }, names);
+        dout.get(fc->out, p.rows_in * fc->ld_out);
+        for (int j = 0; j < 3; ++j) gout[j].back();
+        for (int q = 0; q < fc->ngate; ++q) { qout[q].back(); qpart[q].back(); }
+    }
+    put_string(names, kernels, kernels_cap);
+    report_splits(v, splits);
+    API_END
+}
+
+int p3d_debug_fused_wgrad(int device, int n, const float* const* x, const int* ldx, const int* offx, const int64_t* xs,
+                          const float* const* dy, const int* lddy, const int* offdy, const int64_t* ws, const int* s,
+                          const int* xt, const float* const* x2, const int* ldx2, const int* offx2, const float* const* xs1,
+                          const float* const* xt1, const float* const* xs2, const float* const* xt2, const int* dyt,
+                          const float* const* dy2, const int* lddy2, const int* offdy2, const float* const* dcoef,
+                          float* const* dw, float* const* dbias, char* kernel, int kernel_cap, int* cuts, int* info) {
+    API_BEGIN
+    HIPCHECK(hipSetDevice(device));
+    if (!x || !ldx || !offx || !xs || !dy || !lddy || !offdy || !ws || !s || !xt || !x2 || !ldx2 || !offx2 || !xs1 || !xt1 || !xs2 || !xt2 ||
+        !dyt || !dy2 || !lddy2 || !offdy2 || !dcoef || !dw || !dbias || !cuts || !info)
+        throw P3dError("null argument");
+    if (n < 1 || n > P3D_WGRAD_GROUP) throw P3dError("fused_wgrad: 1 to " + std::to_string(P3D_WGRAD_GROUP) + " problems");
+    struct Bufs { std::unique_ptr<DevBuf> x, x2, dy, dy2, s1, t1, s2, t2, coef, dw, db; int64_t nw; int nb; };
+    std::vector<Bufs> bufs((size_t)n);
+    std::vector<WgradArgs> probs;
+    ensure_zero_page();
+    double fl = 0, by = 0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t* xsi = xs + 5 * i; const int64_t* wsi = ws + 5 * i;
+        const ConvProblem p = conv_problem(xsi, wsi, s + 3 * i, 0);
+        if (p.stem) throw P3dError("fused_wgrad: the stem shape has its own entry points");
+        if (wsi[3] != p.Cin) throw P3dError("filter Cin mismatch");
+        if (!x[i] || !dy[i]) throw P3dError("null argument");
+        check_slice("fused_wgrad (x)", ldx[i], offx[i], p.Cin);
+        check_slice("fused_wgrad (dy)", lddy[i], offdy[i], p.Cout);
+        Bufs& b = bufs[(size_t)i];
+        b.nw = prod5(wsi); b.nb = p.Cout;
+        b.x.reset(new DevBuf(p.rows_in * ldx[i], x[i]));
+        b.dy.reset(new DevBuf(p.rows * lddy[i], dy[i]));
+        if (b.nw > 0 && !dw[i]) throw P3dError("null argument");
+        b.dw.reset(new DevBuf(b.nw, dw[i]));
+        if (dbias[i]) b.db.reset(new DevBuf(b.nb, dbias[i]));
+        WgradArgs a = p.filter_gradient(b.x->p + offx[i], ldx[i], b.dy->p + offdy[i], lddy[i], b.dw->p, dbias[i] ? b.db->p : nullptr);
+        a.zeros = g_zero_page;
+        if (xt[i]) {
+            if (xt[i] != 1 && xt[i] != 2) throw P3dError("fused_wgrad: xt is 0, 1 or 2");
+            if (!xs1[i] || !xt1[i]) throw P3dError("null argument");
+            b.s1 = dev_copy(xs1[i], p.Cin); b.t1 = dev_copy(xt1[i], p.Cin);
+            const float* x2p = nullptr;
+            if (xt[i] == 2) {
+                if (!x2[i] || !xs2[i] || !xt2[i]) throw P3dError("null argument");
+                check_slice("fused_wgrad (x2)", ldx2[i], offx2[i], p.Cin);
+                b.s2 = dev_copy(xs2[i], p.Cin); b.t2 = dev_copy(xt2[i], p.Cin);
+                if (x2[i] == x[i] && ldx2[i] == ldx[i]) x2p = b.x->p + offx2[i];      // two slices of ONE buffer
+                else { b.x2.reset(new DevBuf(p.rows_in * ldx2[i], x2[i])); x2p = b.x2->p + offx2[i]; }
+            }
+            fused_wgrad_x(a, xt[i], b.s1->p, b.t1->p, x2p, ldx2[i], b.s2 ? b.s2->p : nullptr, b.t2 ? b.t2->p : nullptr);
+        }
+        if (dyt[i]) {
+            if (!dy2[i] || !dcoef[i]) throw P3dError("null argument");
+            check_slice("fused_wgrad (dy2)", lddy2[i], offdy2[i], p.Cout);
+            b.dy2.reset(new DevBuf(p.rows * lddy2[i], dy2[i]));
+            b.coef = dev_copy(dcoef[i], 3 * (int64_t)p.Cout);
+            fused_wgrad_dy(a, b.dy2->p + offdy2[i], lddy2[i], b.coef->p);
+        }
+        double f1, b1;
+        wgrad_work(a, f1, b1);
+        fl += f1; by += b1;
+        probs.push_back(a);
+    }
+    info[1] = info[2] = 0;
+    if (p3d_wgrad2_group_cuts(probs.data(), n, cuts, &info[0], &info[1], &info[2]) < 0) throw P3dError("fused_wgrad: a problem the kernel does not take");
+    const char* name = wgrad_group_name(probs);
+    put_string(name, kernel, kernel_cap);
+    Ctx c;
+    launch_wgrad_group(c, probs, name, fl, by);
+    for (int i = 0; i < n; ++i) {
+        if (bufs[(size_t)i].nw > 0) bufs[(size_t)i].dw->get(dw[i], bufs[(size_t)i].nw);
+        if (dbias[i]) bufs[(size_t)i].db->get(dbias[i], bufs[(size_t)i].nb);
+    }
+    API_END
+}
+
+int p3d_debug_fused_reject(int device, int which, int* error, int* validator) {
+    API_BEGIN
+    if (!error || !validator) throw P3dError("null argument");
+    if (which < 0 || which > 9) throw P3dError("fused_reject: cases 0 to 9");
+    // Every pointer names real memory, on the device where there is one: a launch that a broken check lets through writes into
+    // this page and nowhere else.  Without a device the checks under test, which run ahead of any HIP call, answer all the same.
+    int ndev = 0;
+    const bool dev = hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;
+    if (!dev) (void)hipGetLastError();
+    static float host_page[16384];
+    std::unique_ptr<DevBuf> page;
+    float* b = host_page;
+    if (dev) { HIPCHECK(hipSetDevice(device)); page.reset(new DevBuf(16384)); b = page->p; }
+    const int64_t xs[5] = {1, 1, 2, 2, 8}, ws[5] = {1, 1, 1, 8, 8};
+    const int st[3] = {1, 1, 1};
+    const ConvProblem p = conv_problem(xs, ws, st, 0);
+    float *x = b, *w = b + 1024, *y = b + 2048, *tab = b + 4096, *part = b + 8192, *zeros = b + 12288;
+    *error = 0; *validator = 1;
+    if (which <= 6) {
+        IgemmArgs a = p.forward(x, w, y, nullptr)[0];
+        a.zeros = zeros;
+        FusedBn d;
+        d.gamma = tab; d.beta = tab + 8; d.C = 8; d.scale = tab + 16; d.shift = tab + 24; d.mean = tab + 32; d.invstd = tab + 40;
+        d.moving_mean = tab + 48; d.moving_var = tab + 56; d.part = part; d.rows = 4; d.pub = 2;
+        FusedBnGrad gd;
+        gd.gamma = tab; gd.mean = tab + 32; gd.invstd = tab + 40; gd.C = 8; gd.coef = tab + 64; gd.dgamma = tab + 96; gd.dbeta = tab + 104;
+        gd.part = part; gd.rows = 4;
+        if (which == 0 || which == 1) { d.nparts = which ? P3D_FOLD_MAX + 1 : 0; fused_forward_operand(a, P3D_AT_RELU1, d, false, nullptr, 0, nullptr, false); }
+        if (which == 2 || which == 3) { a.wT = 1; gd.nparts = which == 3 ? P3D_FOLD_MAX + 1 : 0; fused_grad_operand(a, y, 8, gd, false, false); }
+        if (which == 4) {
+            BnGate g;
+            memset(&g, 0, sizeof(g));
+            g.y = x; g.ldy = 8; g.scale = tab + 16; g.shift = tab + 24; g.mean = tab + 32; g.invstd = tab + 40; g.out = y + 512; g.ldo = 8; g.part = part;
+            std::vector<IgemmArgs> v{a};
+            fused_gated_epilogue(v, 1, &g, false, false);
+            a = v[0];
+            a.statpart = part + 4096;
+        }
+        if (which == 5) { d.pub = 0; fused_forward_operand(a, P3D_AT_RELU1, d, false, nullptr, 0, nullptr, false); a.wT = 1; }
+        if (which == 6) { d.pub = 0; fused_forward_operand(a, P3D_AT_RELU2, d, false, x, 10, &d, false); }
+        P3dIgemmPlan pl;
+        pl.bm = 64; pl.bn = 64; pl.splits = 1; pl.name = "igemm2_kernel<64,64>";
+        *error = (int)p3d_launch_igemm2(a, pl, nullptr);
+    } else {
+        WgradArgs a = p.filter_gradient(x, 8, y, 8, w, nullptr);
+        a.zeros = zeros;
+        if (which == 7) { fused_wgrad_x(a, 1, tab + 16, tab + 24, nullptr, 0, nullptr, nullptr); a.pair = 1; }
+        if (which == 8) fused_wgrad_x(a, 2, tab + 16, tab + 24, x, 10, tab + 16, tab + 24);
+        if (which == 9) { fused_wgrad_dy(a, y, 8, tab + 64); a.pair = 1; }
+        int cuts[1], ks = 0, tm = 0, tn = 0;
+        *validator = p3d_wgrad2_group_cuts(&a, 1, cuts, &ks, &tm, &tn) < 0 ? 0 : 1;
+        *error = (int)p3d_launch_wgrad2_group(&a, 1, nullptr);
+    }
+    if (dev) HIPCHECK(hipDeviceSynchronize());
+    API_END
+}
+
 int p3d_debug_max_pool3d(int device, const float* x, int ldx, int offx, const int64_t xs[5], const int k[3], const int s[3], float* y,
                          int ldy, int offy) {
     API_BEGIN

@@ -10,7 +10,7 @@
         if (bn && stats_target(bn, y->rows(), Cout, bn_has_dropout)) reserve_stat_parts(bn, y->rows());
         const ConvFuse cf = fuse ? *fuse : ConvFuse();
         if (cf.out_bn) { if (cf.out_bn != bn) throw P3dError("fused output BatchNorm must be the conv's own"); make_fusable(bn, y->rows()); }
-        if (cf.ngate && (s[0] != 1 || s[1] != 1 || s[2] != 1)) throw P3dError("gated input gradients need a stride-1 conv");
+        fused_gate_check(s, cf.ngate);
         char* xflag = x->g ? consume(x) : nullptr;
         const int Cin = x->C;
         const int ntap = k[0] * k[1] * k[2];
@@ -85,9 +85,11 @@
                 return;
             }
             if (fz) {
-                a.at_mode = cf.at;
-                a.f1 = bn_fold(cf.src[0], cf.src[0].y->rows(), c);
-                if (cf.at == P3D_AT_RELU2) { a.x2 = cf.src[1].y->p; a.ldx2 = cf.src[1].y->ld; a.f2 = bn_fold(cf.src[1], cf.src[1].y->rows(), c); }
+                const bool two = cf.at == P3D_AT_RELU2;
+                const FusedBn s1 = fused_bn_desc(cf.src[0], cf.src[0].y->rows(), c);
+                const FusedBn s2 = two ? fused_bn_desc(cf.src[1], cf.src[1].y->rows(), c) : FusedBn();
+                fused_forward_operand(a, cf.at, s1, fwd_finalized[cf.src[0].bn], two ? cf.src[1].y->p : nullptr, two ? cf.src[1].y->ld : 0,
+                                      two ? &s2 : nullptr, two && fwd_finalized[cf.src[1].bn]);
             }
             if (f16()) a.f16 = 1;
             run_igemm_group(c, v, false, stats);
@@ -98,9 +100,9 @@
             const Act* xs = fin ? cf.src[0].y : x;
             WgradArgs wa = wgrad_conv(g, x->N, xs->p, xs->ld, Cin, y->g, y->ld, Cout, w->g, bias ? bias->g : nullptr);
             if (fin) {
-                wa.xt = cf.at == P3D_AT_RELU2 ? 2 : 1;
-                wa.xs1 = cf.src[0].bn->scale; wa.xt1 = cf.src[0].bn->shift;
-                if (wa.xt == 2) { wa.x2 = cf.src[1].y->p; wa.ldx2 = cf.src[1].y->ld; wa.xs2 = cf.src[1].bn->scale; wa.xt2 = cf.src[1].bn->shift; }
+                const bool two = cf.at == P3D_AT_RELU2;
+                fused_wgrad_x(wa, two ? 2 : 1, cf.src[0].bn->scale, cf.src[0].bn->shift, two ? cf.src[1].y->p : nullptr, two ? cf.src[1].y->ld : 0,
+                              two ? cf.src[1].bn->scale : nullptr, two ? cf.src[1].bn->shift : nullptr);
             }
             return wa;
         };
@@ -120,16 +122,9 @@
             // ---- fused BatchNorm: y->g holds the GATED gradient of relu(bn(y)) (written by the consumer's input-gradient
             //      launch), BatchNorm's own backward happens on the operand paths below
             WgradArgs wa = wgrad_args(cf.at != 0);
-            if (cf.out_bn) { wa.dyt = 1; wa.dy2 = y->p; wa.ldy2 = y->ld; wa.dcoef = cf.out_bn->coef; }
+            if (cf.out_bn) fused_wgrad_dy(wa, y->p, y->ld, cf.out_bn->coef);
             if (!xflag) throw P3dError("a conv with a fused BatchNorm needs an input gradient launch (it publishes the coefficients)");
-            if (cf.out_bn && !c.dry) {
-                grad_finalized[cf.out_bn] = false;
-                if (cf.out_bn->gnparts > FOLD_MAX) {
-                    const BnGradFold gf = bn_grad_fold(cf.out_bn, y->rows(), true);
-                    launch(c, "bn_grad_finalize_kernel", 0, 64.0 * cf.out_bn->C, [&]() { return p3d_bn_grad_finalize(gf, c.s); });
-                    grad_finalized[cf.out_bn] = true;
-                }
-            }
+            if (cf.out_bn && !c.dry) grad_finalized[cf.out_bn] = fused_bn_grad_prefinalize(c, fused_grad_desc(cf.out_bn, y->rows()));
             // where the input gradient goes: plain inputs and ungated launches write / add to x->g; gated launches send the
             // gated result to the gate's own buffers and use x->g (or cf.raw) for raw partial results only
             float* py = x->g; int pld = x->ld; int accum = *xflag;
@@ -141,24 +136,17 @@
             bool first = true;
             for (auto& a : v) {
                 if (f16()) a.f16 = 1;
-                if (cf.out_bn) {
-                    a.at_mode = P3D_AT_GRAD; a.x2 = y->p; a.ldx2 = y->ld;
-                    a.gf = bn_grad_fold(cf.out_bn, y->rows(), first);
-                }
-                if (cf.ngate) {
-                    if (v.size() != 1) throw P3dError("gated input gradient with more than one residue class");
-                    a.ngate = cf.ngate; a.raw_store = cf.raw ? 1 : 0;
-                    for (int q = 0; q < cf.ngate; ++q) a.gate[q] = bn_gate(cf.gate[q]);
-                    if (!c.dry) {
-                        IgemmArgs t = a; t.zeros = g_zero_page;
-                        const int mt = p3d_igemm2_mtiles(t, p3d_igemm2_plan(t, 1));
-                        for (int q = 0; q < cf.ngate; ++q) {
-                            if (mt > cf.gate[q].bn->gpart_cap) throw P3dError("gradient partials overflow their arena slot");
-                            cf.gate[q].bn->gnparts = mt;
-                        }
-                    }
-                }
+                if (cf.out_bn) fused_grad_operand(a, y->p, y->ld, fused_grad_desc(cf.out_bn, y->rows()), grad_finalized[cf.out_bn], first);
                 first = false;
+            }
+            if (cf.ngate) {
+                BnGate gates[2];
+                for (int q = 0; q < cf.ngate; ++q) gates[q] = bn_gate(cf.gate[q]);
+                const int mt = fused_gated_epilogue(v, cf.ngate, gates, cf.raw != nullptr, !c.dry);
+                for (int q = 0; q < cf.ngate && !c.dry; ++q) {
+                    if (mt > cf.gate[q].bn->gpart_cap) throw P3dError("gradient partials overflow their arena slot");
+                    cf.gate[q].bn->gnparts = mt;
+                }
             }
             run_igemm_group(c, v, accum != 0, nullptr);
             queue_wgrad(c, wa);      // after the input gradient: its block 0 published the coefficients this one reads

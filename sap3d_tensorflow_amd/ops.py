@@ -296,6 +296,149 @@ def wgrad_group(problems, polite=False, greedy=False, pad=np.nan, device=0):
     return list(zip(dws, dbs)), name.value.decode(), list(cuts), tuple(info)
 
 
+def _own(a, shape=None):
+    """A private float32 copy of an in / out array (None stays None)."""
+    if a is None:
+        return None
+    a = np.array(a, dtype=np.float32, order="C", copy=True)
+    return a if shape is None else a.reshape(shape)
+
+
+def fused_conv(kind, input_sizes, filter, strides, out, ld_out=None, off_out=0, bias=None, f16=False, src=(), g=None, ld_g=None,
+               off_g=0, grad=None, gates=(), raw_store=False, accum=False, device=0):
+    """Test hook: one fused-BatchNorm conv launch (p3d_debug_fused_conv), built by the builders of the graph's conv op.
+    kind "forward": src = one (RELU1) or two (RELU2) dicts {y [rows, ld], off, and either scale / shift (published) or gamma,
+    beta, partials [nparts, C, 2], rows, publish, update_moving, moving_mean, moving_var}; scale, shift, mean, invstd are what
+    the published arrays hold before.  kind "input_grad": g [rows, ld_g] the gradient of the conv's output; grad = dict {y
+    [rows, ld], off, coef [3, Cout] and either nothing more (published) or gamma, mean, invstd, partials [nparts, Cout, 2], rows,
+    publish, dgamma, dbeta}; gates = up to two dicts {y [rows, ld], off_y, scale, shift, mean, invstd, out [rows, ld_out], off_out,
+    part [part_rows, Cin, 2]}.  out [rows, ld_out]: what the output / raw-result buffer holds before.  Two sources that pass the
+    same array object as y share one device buffer.  Nothing passed in is modified; returns a dict: out, kernels, splits, src
+    (list of dicts scale, shift, mean, invstd, moving_mean, moving_var), grad (coef, dgamma, dbeta), gates (list of out, part),
+    gpart_rows."""
+    from ._lib import P3dFusedConv
+    kd = CONV_KINDS[kind]
+    if kd > 1:
+        raise ValueError("fused_conv: forward or input_grad")
+    w = _f32(filter)
+    a = P3dFusedConv()
+    keep = [w]
+    a.kind = kd
+    a.xshape = _shape5(input_sizes)
+    a.wshape = _shape5(w.shape)
+    a.stride = _i3(_strides3(strides))
+    a.w = fptr(w)
+    b = _f32(bias) if bias is not None else None
+    keep.append(b)
+    a.bias = fptr(b)
+    a.f16 = 1 if f16 else 0
+    res = {"src": [], "grad": None, "gates": []}
+    o = _own(out)
+    a.out, a.ld_out, a.off_out = fptr(o), int(o.shape[1] if ld_out is None else ld_out), int(off_out)
+    ro = lambda v: None if v is None else _f32(v)
+    if kd == 0:
+        a.at = len(src)
+        shared = {}
+        for q, sd in enumerate(src):
+            f = a.src[q]
+            y = shared.setdefault(id(sd["y"]), _f32(sd["y"]))
+            arrs = {k: ro(sd.get(k)) for k in ("gamma", "beta", "partials")}
+            outs = {k: _own(sd.get(k)) for k in ("scale", "shift", "mean", "invstd", "moving_mean", "moving_var")}
+            keep += [y, arrs, outs]
+            f.y, f.ld, f.off = fptr(y), y.shape[1], int(sd.get("off", 0))
+            f.gamma, f.beta, f.partials = fptr(arrs["gamma"]), fptr(arrs["beta"]), fptr(arrs["partials"])
+            f.nparts = 0 if arrs["partials"] is None else arrs["partials"].shape[0]
+            f.rows = int(sd.get("rows", 0))
+            f.publish, f.update_moving = (1 if sd.get("publish") else 0), (1 if sd.get("update_moving") else 0)
+            f.scale, f.shift, f.mean, f.invstd = (fptr(outs[k]) for k in ("scale", "shift", "mean", "invstd"))
+            f.moving_mean, f.moving_var = fptr(outs["moving_mean"]), fptr(outs["moving_var"])
+            res["src"].append(outs)
+    else:
+        gg = _f32(g)
+        keep.append(gg)
+        a.g, a.ld_g, a.off_g = fptr(gg), int(gg.shape[1] if ld_g is None else ld_g), int(off_g)
+        if grad is not None:
+            a.grad = 1
+            f = a.gbn
+            y = _f32(grad["y"])
+            arrs = {k: ro(grad.get(k)) for k in ("gamma", "mean", "invstd", "partials")}
+            outs = {k: _own(grad.get(k)) for k in ("coef", "dgamma", "dbeta")}
+            keep += [y, arrs, outs]
+            f.y, f.ld, f.off = fptr(y), y.shape[1], int(grad.get("off", 0))
+            f.gamma, f.mean, f.invstd, f.partials = (fptr(arrs[k]) for k in ("gamma", "mean", "invstd", "partials"))
+            f.nparts = 0 if arrs["partials"] is None else arrs["partials"].shape[0]
+            f.rows = int(grad.get("rows", 0))
+            f.publish = 1 if grad.get("publish") else 0
+            f.coef, f.dgamma, f.dbeta = fptr(outs["coef"]), fptr(outs["dgamma"]), fptr(outs["dbeta"])
+            res["grad"] = outs
+        a.ngate = len(gates)
+        for q, gd in enumerate(gates):
+            f = a.gate[q]
+            y = _f32(gd["y"])
+            tabs = {k: _f32(gd[k]) for k in ("scale", "shift", "mean", "invstd")}
+            outs = {"out": _own(gd["out"]), "part": _own(gd["part"])}
+            keep += [y, tabs, outs]
+            f.y, f.ld_y, f.off_y = fptr(y), y.shape[1], int(gd.get("off_y", 0))
+            f.scale, f.shift, f.mean, f.invstd = (fptr(tabs[k]) for k in ("scale", "shift", "mean", "invstd"))
+            f.out, f.ld_out, f.off_out = fptr(outs["out"]), outs["out"].shape[1], int(gd.get("off_out", 0))
+            f.part, f.part_rows = fptr(outs["part"]), outs["part"].shape[0]
+            res["gates"].append(outs)
+        a.raw_store, a.accum = (1 if raw_store else 0), (1 if accum else 0)
+    names = C.create_string_buffer(16384)
+    splits = (C.c_int * 2)()
+    check(lib().p3d_debug_fused_conv(device, C.byref(a), names, len(names), splits))
+    res.update(out=o, kernels=names.value.decode(), splits=(splits[0], splits[1]), gpart_rows=int(a.gpart_rows))
+    return res
+
+
+def fused_wgrad(problems, device=0):
+    """Test hook: up to 6 filter gradients of fused-BatchNorm convs as ONE launch (p3d_debug_fused_wgrad).  Each problem is a dict:
+    x [rows, ldx], offx, dy [rows, lddy], offdy, input_sizes, filter_sizes, strides, dw (what the gradient holds before; it is added
+    to), dbias (or None), and optionally xt = 1 / 2 with xs1, xt1 (and x2 [rows, ldx2], offx2, xs2, xt2; the same array object as x
+    shares its device buffer), dyt = 1 with dy2 [rows, lddy2], offdy2, dcoef [3, Cout].  Returns ([(dw, dbias or None), ...], kernel
+    name, cuts, (slab stride, tile rows, tile columns))."""
+    n = len(problems)
+    cols = {k: [] for k in ("x", "dy", "x2", "xs1", "xt1", "xs2", "xt2", "dy2", "dcoef", "dw", "dbias")}
+    ints = {k: [] for k in ("ldx", "offx", "lddy", "offdy", "xt", "ldx2", "offx2", "dyt", "lddy2", "offdy2")}
+    xsh, wsh, st = [], [], []
+    for pr in problems:
+        fs = tuple(int(v) for v in pr["filter_sizes"])
+        x, dy = _f32(pr["x"]), _f32(pr["dy"])
+        x2 = x if pr.get("x2") is pr["x"] else (None if pr.get("x2") is None else _f32(pr["x2"]))
+        dy2 = None if pr.get("dy2") is None else _f32(pr["dy2"])
+        cols["x"].append(x); cols["dy"].append(dy); cols["x2"].append(x2); cols["dy2"].append(dy2)
+        for k in ("xs1", "xt1", "xs2", "xt2", "dcoef"):
+            cols[k].append(None if pr.get(k) is None else _f32(pr[k]))
+        cols["dw"].append(_own(pr["dw"], fs))
+        cols["dbias"].append(_own(pr.get("dbias")))
+        ints["ldx"].append(x.shape[1]); ints["offx"].append(int(pr.get("offx", 0)))
+        ints["lddy"].append(dy.shape[1]); ints["offdy"].append(int(pr.get("offdy", 0)))
+        ints["xt"].append(int(pr.get("xt", 0))); ints["dyt"].append(int(pr.get("dyt", 0)))
+        ints["ldx2"].append(0 if x2 is None else x2.shape[1]); ints["offx2"].append(int(pr.get("offx2", 0)))
+        ints["lddy2"].append(0 if dy2 is None else dy2.shape[1]); ints["offdy2"].append(int(pr.get("offdy2", 0)))
+        xsh += [int(v) for v in pr["input_sizes"]]
+        wsh += list(fs)
+        st += [int(v) for v in _strides3(pr["strides"])]
+    fpp = type(fptr(cols["dw"][0]))
+    arr = lambda k: (fpp * n)(*[fptr(v) for v in cols[k]])
+    iv = lambda k: (C.c_int * n)(*ints[k])
+    name = C.create_string_buffer(256)
+    cuts, info = (C.c_int * n)(), (C.c_int * 3)()
+    check(lib().p3d_debug_fused_wgrad(device, n, arr("x"), iv("ldx"), iv("offx"), (C.c_int64 * len(xsh))(*xsh), arr("dy"), iv("lddy"),
+                                      iv("offdy"), (C.c_int64 * len(wsh))(*wsh), (C.c_int * len(st))(*st), iv("xt"), arr("x2"),
+                                      iv("ldx2"), iv("offx2"), arr("xs1"), arr("xt1"), arr("xs2"), arr("xt2"), iv("dyt"), arr("dy2"),
+                                      iv("lddy2"), iv("offdy2"), arr("dcoef"), arr("dw"), arr("dbias"), name, len(name), cuts, info))
+    return list(zip(cols["dw"], cols["dbias"])), name.value.decode(), list(cuts), tuple(info)
+
+
+def fused_reject(which, device=0):
+    """Test hook (p3d_debug_fused_reject): (the launcher's hipError_t, whether the filter-gradient validator takes it) for malformed
+    fused launch number `which`; hipErrorInvalidValue is 1."""
+    err, ok = C.c_int(-1), C.c_int(-1)
+    check(lib().p3d_debug_fused_reject(device, int(which), C.byref(err), C.byref(ok)))
+    return err.value, bool(ok.value)
+
+
 def max_pool3d_launch(x, ksize, strides, ld=(None, None), offset=(0, 0), pad=np.nan, prior=np.nan, device=0):
     """Test hook: tf.nn.max_pool3d SAME with x and y as channel slices (p3d_debug_max_pool3d); ld / offset = (of x, of y).
     Returns (y, what its buffer holds outside the slice)."""

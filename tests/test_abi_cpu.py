@@ -23,9 +23,21 @@ def test_library_exports_every_declared_symbol():
     assert len(names) >= 30
     # the hooks of the attention block (tests/test_gpu_attention.py) are declared, exported and bound like every other symbol
     assert {"p3d_debug_attention_core", "p3d_debug_attention_splits", "p3d_debug_softmax_rows", "p3d_debug_attn_mix"} <= set(names)
+    # ... and so are the hooks of the fused-BatchNorm launches (tests/test_gpu_fused_ops.py)
+    assert {"p3d_debug_fused_conv", "p3d_debug_fused_wgrad", "p3d_debug_fused_reject"} <= set(names)
     for n in names:
         assert hasattr(lib, n), n
         assert n in _lib.SIGNATURES, "ctypes signature missing for " + n
+
+
+def test_malformed_fused_launches_are_refused_ahead_of_any_device_call():
+    """p3d_debug_fused_reject: the launchers' argument checks run before the first HIP call, so they answer without a device too --
+    hipErrorInvalidValue (1) for every malformed fused launch, and `false` from the filter-gradient validator for its three."""
+    from sap3d_tensorflow_amd import ops
+    for which in range(10):
+        err, ok = ops.fused_reject(which)
+        assert err == 1, (which, err)
+        assert ok == (which < 7), which
 
 
 def test_attention_plan_hook_needs_no_device():

@@ -16,8 +16,10 @@ gradient per launch; the step does none of that (net_ops.inc conv() / deconv(), 
 Tolerance: TOL = 2e-5 of the expected result's max magnitude (tests/test_gpu_ops.py), for accumulating cases of max |prior +
 result|.  Every case that is about a path asserts the kernel name the hook reports.
 
-Not covered here: the BatchNorm-fusion operand transforms and gated epilogues (at_mode, ngate, xt / dyt; off by default), the
-attention GEMMs, RCCL."""
+The BatchNorm-fusion operand transforms and gated epilogues (at_mode, ngate, xt / dyt; off by default) have a file of their own:
+  * tests/test_gpu_fused_ops.py, through the hooks p3d_debug_fused_conv / p3d_debug_fused_wgrad, against tests/fused_bn_ref.py:
+    results at TOL, folded coefficients at 16 eps32 of their terms' magnitudes, gate partials at the float32 summation bound.
+Not covered here: the attention GEMMs (tests/test_gpu_attention.py), RCCL."""
 import os
 import sys
 
