@@ -218,6 +218,11 @@ def parse_args(argv=None):
                    "(smoothed) map to the table of FILE.npz (`cdf`, `bin_centers`) before it is normalised and quantised "
                    "(utils/metric_utils.py match_hist; P3DSession.set_hist_match)")
     p.add_argument("--match-bins", type=int, default=256, metavar="N", help="[addition] bins of --match-hist's histograms, 2 .. 1024")
+    p.add_argument("--prior", type=str, default="", metavar="FILE.npy", help="[addition] png / jpg: combine every (smoothed) map at --size "
+                   "with the prior map of this .npy, float32 [H, W] at --size, before it is matched, normalised and quantised "
+                   "(P3DSession.set_prior_stage; drivers/test.py builds such a map from fixations)")
+    p.add_argument("--prior-mode", choices=("mul", "mix"), default="mul", help="[addition] v ((1 - A) g + A), or (1 - A) v + A g")
+    p.add_argument("--prior-weight", type=float, default=0., metavar="A", help="[addition] the weight A in [0, 1]")
     p.add_argument("--writers", type=int, default=4, help="encoder threads for png / jpg (at most 16)")
     p.add_argument("--resident", action="store_true", help="[addition] keep every video on the device: frames go up once as uint8, "
                    "windows are cut there and the maps are read once per video (P3DSession.open_video)")
@@ -244,6 +249,27 @@ def parse_args(argv=None):
     if not 2 <= args.match_bins <= 1024:
         p.error("--match-bins must be in 2..1024")
     return args
+
+
+def prior_stage_args(args):
+    """(file, mode, weight) of --prior, or None without it.  Exits on flags that cannot be served, before anything runs."""
+    if not args.prior:
+        if args.prior_mode != "mul" or args.prior_weight != 0.:
+            raise SystemExit("--prior-mode / --prior-weight need --prior FILE.npy")
+        return None
+    if args.write == "npy":
+        raise SystemExit("--prior shapes the images: it needs --write png or jpg (npy stays the raw 112x112 maps)")
+    if not 0. <= args.prior_weight <= 1.:
+        raise SystemExit("--prior-weight: the weight must be in [0, 1]")
+    return args.prior, args.prior_mode, float(args.prior_weight)
+
+
+def load_prior(path, size):
+    """--prior's map: float32 [H, W] of an .npy, of the images' size."""
+    g = np.asarray(np.load(path), np.float32)
+    if g.shape != tuple(size):
+        raise ValueError("--prior: the map %s is %s, the images are %s" % (path, g.shape, tuple(size)))
+    return g
 
 
 def match_target(args):
@@ -316,6 +342,8 @@ def run_resident(sess, args, path):
 
 def main(argv=None):
     args = parse_args(argv)
+    stage = prior_stage_args(args)                                          # refused before anything runs
+    prior = load_prior(stage[0], args.size) if stage else None
     from sap3d_tensorflow_amd import P3DSession
     blocks = tuple(int(v) for v in args.blocks.split(","))
     sess = P3DSession(args.structure, batch=args.batch, device=int(args.gpu), seed=0, base=args.base, blocks=blocks)
@@ -323,6 +351,9 @@ def main(argv=None):
         sess.restore(args.model, ema_as_weights=args.ema)
     sess.set_postprocess(args.blur_sigma, args.blur_radius, args.normalize)
     sess.set_hist_match(match_target(args), args.match_bins)
+    if stage:
+        sess.set_prior_map(prior)
+        sess.set_prior_stage(stage[1], stage[2])
     run(sess, args)
     sess.close()
 

@@ -102,7 +102,12 @@ def shuffled_auc(sess, fixation, lo, m, rng, device=0):
     match = sess.hist_match
     if match and match["mode"] == "density":
         raise ValueError("--sauc scores the clean map against other clips' fixations: it takes --match-hist FILE.npz, not density")
-    if match:
+    stage = sess.prior_stage
+    if stage:
+        table = (match["cdf"], match["bin_centers"]) if match else None
+        full = dataflow.postprocess_maps(pred, fixation.shape[1:], device=device, hist_match=table, nbins=match["nbins"] if match else 256,
+                                         prior=sess.prior_map, prior_mode=stage["mode"], prior_weight=stage["weight"], **(post or {}))
+    elif match:
         full = dataflow.postprocess_maps(pred, fixation.shape[1:], device=device, hist_match=(match["cdf"], match["bin_centers"]),
                                          nbins=match["nbins"], **(post or {}))
     elif post:
@@ -128,6 +133,35 @@ def match_target(args):
     return dataflow.load_match_table(args.match_hist)
 
 
+def prior_plan(args):
+    """What the --prior* flags and --info-gain prior ask for, or None when no prior is built: dict(source: "set" (the set's own
+    fixation array) or the .npz of --prior-from, leave_out, sigma, radius, mode, weight, baseline: "prior" or None).  Exits on a
+    combination that cannot be served, before anything runs."""
+    ig = args.info_gain == "prior"
+    stage = args.prior != "off"
+    if not ig and not stage:
+        for flag, given in (("--prior-from", bool(args.prior_from)), ("--prior-sigma", args.prior_sigma != 0.), ("--prior-radius", args.prior_radius != 0)):
+            if given:
+                raise SystemExit("%s builds a prior that nothing uses: add --info-gain prior or --prior mul|mix" % flag)
+        if args.prior_weight != 0.:
+            raise SystemExit("--prior-weight needs --prior mul|mix")
+        if args.prior_leave_out:
+            raise SystemExit("--prior-leave-out needs --info-gain prior")
+        return None
+    if args.prior_weight != 0. and not stage:
+        raise SystemExit("--prior-weight needs --prior mul|mix")
+    if not 0. <= args.prior_weight <= 1.:
+        raise SystemExit("--prior-weight: the weight must be in [0, 1]")
+    if not args.prior_sigma >= 0. or args.prior_radius < 0 or args.prior_radius > 255:
+        raise SystemExit("--prior-sigma must be >= 0 and --prior-radius in 0..255")
+    if args.prior_leave_out and not ig:
+        raise SystemExit("--prior-leave-out needs --info-gain prior")
+    if args.prior_leave_out and args.prior_from:
+        raise SystemExit("--prior-leave-out takes a batch's clips out of the set's own prior: it does not go with --prior-from")
+    return dict(source=args.prior_from or "set", leave_out=bool(args.prior_leave_out), sigma=float(args.prior_sigma), radius=int(args.prior_radius),
+                mode=args.prior, weight=float(args.prior_weight), baseline="prior" if ig else None)
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     p.add_argument("--model", type=str, default="", help="checkpoint: a directory with a TF `checkpoint` state file, a TF bundle "
@@ -146,8 +180,18 @@ def parse_args(argv=None):
     p.add_argument("--time", action="store_true", help="print the stage times of every batch")
     p.add_argument("--kldiv", action="store_true", help="add KL divergence of the density from the scored map (utils/metrics.py KLdiv; "
                    "P3DSession.set_eval_extra)")
-    p.add_argument("--info-gain", type=str, default="", metavar="BASELINE.npy", help="[addition] add information gain over the baseline "
-                   "map of this .npy, float32 [H, W] at the fixation maps' size (the MIT benchmark's InfoGain)")
+    p.add_argument("--info-gain", type=str, default="", metavar="BASELINE.npy|prior", help="[addition] add information gain over the "
+                   "baseline map of this .npy, float32 [H, W] at the fixation maps' size (the MIT benchmark's InfoGain); `prior`: "
+                   "over a fixation prior built on the device from the set's own fixation maps (P3DSession.open_prior)")
+    p.add_argument("--prior-from", type=str, default="", metavar="OTHER.npz", help="[addition] build the prior from the `fixation` array "
+                   "of another set instead")
+    p.add_argument("--prior-sigma", type=float, default=0., metavar="S", help="[addition] the Gaussian that smooths the summed fixations")
+    p.add_argument("--prior-radius", type=int, default=0, metavar="R", help="[addition] its radius, as --blur-radius")
+    p.add_argument("--prior-leave-out", action="store_true", help="[addition] with --info-gain prior: every batch is scored against "
+                   "the prior of the other clips (its own are taken out of the counts, and put back)")
+    p.add_argument("--prior", choices=("off", "mul", "mix"), default="off", help="[addition] combine every (smoothed) prediction with the "
+                   "prior before it is matched, normalised and scored (P3DSession.set_prior_stage): v ((1 - A) g + A), or (1 - A) v + A g")
+    p.add_argument("--prior-weight", type=float, default=0., metavar="A", help="[addition] the weight A in [0, 1]")
     p.add_argument("--blur-sigma", type=float, default=0., metavar="S", help="[addition] smooth every resized prediction with a "
                    "Gaussian of S pixels before it is scored (P3DSession.set_postprocess)")
     p.add_argument("--blur-radius", type=int, default=0, metavar="R", help="[addition] the Gaussian's radius in pixels, at most 255; "
@@ -176,7 +220,13 @@ def main(argv=None):
         x, density, fixation = load_set(args.data, device)
     else:
         x, density, fixation = synthetic.synthetic_test_set(args.seed, args.clips)
-    baseline = load_baseline(args.info_gain, fixation.shape[1:]) if args.info_gain else None      # refused before anything runs
+    plan = prior_plan(args)                                                                       # refused before anything runs
+    baseline = load_baseline(args.info_gain, fixation.shape[1:]) if args.info_gain and args.info_gain != "prior" else None
+    prior_fix = fixation
+    if plan and plan["source"] != "set":
+        prior_fix = last_frame(np.load(plan["source"])["fixation"])
+        if prior_fix.dtype != np.uint8 or prior_fix.shape[1:] != fixation.shape[1:]:
+            raise ValueError("--prior-from: %s holds %s %s fixation maps, the set's are uint8 %s" % (plan["source"], prior_fix.dtype, prior_fix.shape[1:], fixation.shape[1:]))
     structure = "unet++ds" if args.structure == "unet++" else args.structure
     blocks = tuple(int(v) for v in args.blocks.split(","))
     sess = P3DSession(structure, batch=args.batch, frames=x.shape[1], height=x.shape[2], width=x.shape[3], base=args.base,
@@ -186,11 +236,20 @@ def main(argv=None):
     print("Now using model %s with structure %s" % (args.model or "(initialised)", structure))
     sess.set_postprocess(args.blur_sigma, args.blur_radius, args.normalize)
     sess.set_hist_match(match_target(args), args.match_bins)
-    extra_on = args.kldiv or baseline is not None
-    if extra_on:
+    ig_prior = bool(plan and plan["baseline"])
+    if plan:
+        sess.open_prior(fixation.shape[1:], "fixations")
+        sess.prior_add(prior_fix)
+        sess.finish_prior(plan["sigma"], plan["radius"])
+        if plan["mode"] != "off":
+            sess.set_prior_stage(plan["mode"], plan["weight"])
+    extra_on = args.kldiv or baseline is not None or ig_prior
+    if ig_prior:
+        sess.set_eval_extra(kldiv=args.kldiv, baseline="prior")
+    elif extra_on:
         sess.set_eval_extra(kldiv=args.kldiv, info_gain=baseline is not None, baseline=baseline)
     extra_cols = [[] for _ in range(2)]                                   # KL, IG
-    labels = [(k, name) for k, name, on in ((0, "KLdiv", args.kldiv), (1, "IG", baseline is not None)) if on]
+    labels = [(k, name) for k, name, on in ((0, "KLdiv", args.kldiv), (1, "IG", baseline is not None or ig_prior)) if on]
 
     def extras():
         return [(name, nan_dropped_mean(extra_cols[k])) for k, name in labels]
@@ -202,7 +261,13 @@ def main(argv=None):
         index += 1
         if index % 100 == 0:
             print(metric_line(STEP_LINE, index, [np.mean(c) for c in cols], extras()))
+        if plan and plan["leave_out"]:                                    # the baseline of the other clips
+            sess.prior_add(fixation[lo:hi], -1)
+            sess.finish_prior(plan["sigma"], plan["radius"])
+            sess.set_eval_extra(kldiv=args.kldiv, baseline="prior")
         m = sess.evaluate(x[lo:hi], density[lo:hi], fixation[lo:hi], size=fixation.shape[1:])
+        if plan and plan["leave_out"]:
+            sess.prior_add(fixation[lo:hi], 1)
         for k in range(5):
             cols[k].extend(m[:, k].tolist())
         if extra_on:
@@ -218,7 +283,8 @@ def main(argv=None):
     post = sess.postprocess
     print(metric_line(ALL_LINE, index, nan_dropped_means(cols), extras()) +
           ("   postprocess: sigma %g radius %d normalize %s" % (post["sigma"], post["radius"], post["norm"]) if post else "") +
-          ("   match-hist: %s, %d bins" % (args.match_hist, args.match_bins) if args.match_hist else ""))
+          ("   match-hist: %s, %d bins" % (args.match_hist, args.match_bins) if args.match_hist else "") +
+          ("   prior: %s %g" % (plan["mode"], plan["weight"]) if plan and plan["mode"] != "off" else ""))
     print("Testing Finished!")
     sess.close()
     return cols + [extra_cols[k] for k, _ in labels]

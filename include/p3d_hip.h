@@ -902,7 +902,8 @@ int p3d_debug_blur_strip(int r, int* cols, int* rows, int* lds_bytes);
  * p3d_set_hist_match   the handle's setting, separate from p3d_set_postprocess; NULL or mode P3D_MATCH_OFF switch it off.  The
  *                      tables are copied at set time.  Nothing is allocated until the stage first runs (scratch from the stream
  *                      pool); the train step, a captured step graph and its schedule never see it.  The stage sits between BLUR
- *                      and NORM of p3d_set_postprocess's chain: resize -> BLUR -> MATCH -> NORM -> BYTE.
+ *                      and NORM of p3d_set_postprocess's chain: resize -> BLUR -> MATCH -> NORM -> BYTE (p3d_set_prior_stage's
+ *                      stage, further down, goes between BLUR and MATCH).
  *     P3D_MATCH_TABLE    one supplied table for every map, in p3d_eval_last_frames, p3d_pred_maps_u8 and p3d_video_maps_u8.
  *                        With p3d_set_postprocess off, the two byte writers take the float32-resize chain, as they do for the blur.
  *     P3D_MATCH_DENSITY  evaluation only: each prediction is matched to the table of its own ground-truth density at H x W, the
@@ -984,6 +985,92 @@ int p3d_debug_eval_maps_extra(int device, const float* maps, int n_maps, int h, 
                               const p3d_hist_match* match, int flags, const float* baseline, double* extra);
 int p3d_metric_kldiv(int device, const float* map1, const float* map2, int n_maps, int n_pix, double* out);
 int p3d_metric_info_gain(int device, const float* sal, const float* fix, const float* baseline, int n_maps, int n_pix, double* out);
+
+/* ---- Fixation priors built on the device (an ADDITION without a reference counterpart: the MIT benchmark's information-gain
+ * baseline is the fixation maps of the other images of a set, summed and smoothed, and gen_video.py:15 only names the sigma32
+ * densities that were made this way).  The same map is the usual centre-bias correction of a saliency model.  OFF by default; off,
+ * every entry point issues what it issued before and returns the same bits, and nothing is allocated.  The train step, a captured
+ * step graph and its schedule never see any of it.  PARITY UNPINNED: this text is the contract and tests/prior_ref.py replays it in
+ * numpy; the kernels are held to that replay bit for bit.
+ *   COUNT   one accumulator per handle: count[H][W] of uint32 and the number of maps in it.  A map of H x W bytes adds, per pixel,
+ *           1 where the byte is >= 128 (P3D_PRIOR_FIXATIONS, the evaluation pass's "fixated" rule) or the byte itself
+ *           (P3D_PRIOR_BYTES, for 8-bit densities), times sign: +1 adds maps, -1 takes them out again (a leave-one-out baseline).
+ *           Integer arithmetic: the words do not depend on how the maps are cut into calls or launches, and adding then
+ *           subtracting the same maps restores them exactly.  A subtraction that would take any count below zero sets a flag on
+ *           the device and does not fault; p3d_prior_counts and p3d_prior_finish refuse from then on, until p3d_prior_open.
+ *           At most P3D_PRIOR_MAX_MAPS maps in all, so that 255 * maps fits a uint32.
+ *   FINISH  c_i = (float)count_i, rounded to nearest even (exact below 2^24); then BLUR of the section above with (sigma, radius)
+ *           -- RADIUS, TAPS and PASS exactly as there -- then NORM P3D_NORM_MAX.  The result is the handle's prior [H][W], float32,
+ *           resident on the device; 1 at the peak.
+ *   APPLY   the stage of p3d_set_prior_stage on a map v with the prior g and a weight 0 <= a <= 1, b = (float)(1.0 - (double)a),
+ *           float32, no fused multiply-add, every operation rounded once:
+ *           P3D_PRIOR_MUL  v' = fmul(v, fadd(fmul(b, g_i), a))      a gain of a where nothing was ever fixated, 1 at the peak;
+ *           P3D_PRIOR_MIX  v' = fadd(fmul(b, v), fmul(a, g_i)).
+ *           Maps that hold NaN or inf propagate them and are NOT pinned.
+ * p3d_prior_open     a zeroed accumulator of H x W counts of `kind` (an open one is replaced; the flag is cleared).  Refused: an
+ *                    unknown kind, H * W outside [1, 2^30].
+ * p3d_prior_add      maps [n][H][W] of bytes on the host, sign +1 or -1.  Refused on the host before any launch: no accumulator,
+ *                    another sign, n < 1, more than P3D_PRIOR_MAX_MAPS maps in all, more maps taken out than are in.
+ * p3d_prior_counts   the counts [H][W] and the number of maps (n_maps may be NULL).  Refused: no accumulator, the underflow flag.
+ * p3d_prior_info     size, kind and number of maps of the open accumulator; every pointer may be NULL.
+ * p3d_prior_finish   FINISH into the handle's prior (the previous one is replaced only on success), and to out [H][W] unless NULL.
+ *                    Refused, nothing changed: no accumulator or no maps in it; the underflow flag; every count zero; the blur's
+ *                    own refusals (sigma, radius, radius > min(H, W) - 1).
+ * p3d_prior_close    frees the accumulator; the finished prior stays.
+ * p3d_prior_last_ms  HIP-event times, in ms: [0] the count launches of the last p3d_prior_add, [1] the last p3d_prior_finish's
+ *                    launches and the read-back of the maximum.
+ * p3d_set_prior_map  a prior [H][W] from the host instead, checked like a baseline: finite and not constant.  NULL drops the
+ *                    handle's prior.
+ * p3d_get_prior_map  the prior's size (0 x 0 without one) and, unless out is NULL, its H * W floats (cap = room in out, in floats).
+ * p3d_set_prior_stage  mode P3D_PRIOR_OFF / P3D_PRIOR_MUL / P3D_PRIOR_MIX and the weight a.  A setting of its own, separate from
+ *                    p3d_set_postprocess and p3d_set_hist_match.  The stage sits between BLUR and MATCH of the shared chain:
+ *                    resize -> BLUR -> PRIOR -> MATCH -> NORM -> BYTE, in p3d_eval_last_frames (on the scored map, before the
+ *                    jitter and every metric), p3d_pred_maps_u8 and p3d_video_maps_u8.  With p3d_set_postprocess off, the two byte
+ *                    writers take the float32-resize chain, as they do for MATCH.  Refused: an unknown mode, a outside [0, 1], no
+ *                    prior; and, when the stage runs, no prior any more or a prior whose size is not the maps' H x W.
+ * p3d_get_prior_stage  the mode and the weight (0 while off); either pointer may be NULL.
+ * p3d_set_eval_extra_prior  p3d_set_eval_extra with the handle's prior as the baseline, copied device to device (a later
+ *                    p3d_prior_finish does not change it); its minimum, maximum and sum are taken by the same one launch.  flags must
+ *                    hold P3D_EVAL_INFO_GAIN.  Refused without a prior; an evaluation of another size than the prior's runs without
+ *                    the launch and p3d_last_eval_extra says so, as for a supplied baseline.
+ * TEST HOOKS (tests/test_gpu_prior.py); device buffers sit between guard elements, a guard that changed is an error:
+ * p3d_debug_prior_count  COUNT of maps [n][H][W] into counts_in [H][W] (NULL: zeros) -> counts_out, flag_out (0 / 1); the maps start
+ *                    `offset` (0 .. 3) bytes past a 4-byte boundary.
+ * p3d_debug_prior_count_plan  host only: the cut the launcher takes for n maps of H x W at that offset -- four-pixel word lanes,
+ *                    one-pixel byte lanes, map slices (more than one: integer atomic adds).
+ * p3d_debug_prior_apply  APPLY of maps [n][H][W] against prior [H][W] -> out; the maps start (offset & 3), the prior
+ *                    ((offset >> 2) & 3) floats past a 16-byte boundary.
+ * p3d_postprocess_maps_prior  p3d_postprocess_maps_match with the stage (prior [H][W]; ignored and may be NULL when mode is off).
+ * p3d_debug_eval_maps_prior   p3d_debug_eval_maps_extra with the stage; with P3D_EVAL_INFO_GAIN and a NULL baseline the prior is
+ *                    the baseline, copied device to device. */
+enum { P3D_PRIOR_FIXATIONS = 0, P3D_PRIOR_BYTES = 1 };
+enum { P3D_PRIOR_OFF = 0, P3D_PRIOR_MUL = 1, P3D_PRIOR_MIX = 2 };
+#define P3D_PRIOR_MAX_MAPS 16000000
+int p3d_prior_open(p3d_handle* h, int H, int W, int kind);
+int p3d_prior_add(p3d_handle* h, const unsigned char* maps, int64_t n, int sign);
+int p3d_prior_counts(p3d_handle* h, uint32_t* out, int64_t* n_maps);
+int p3d_prior_info(p3d_handle* h, int* H, int* W, int* kind, int64_t* n_maps);
+int p3d_prior_finish(p3d_handle* h, float sigma, int radius, float* out /* may be NULL */);
+int p3d_prior_close(p3d_handle* h);
+int p3d_prior_last_ms(p3d_handle* h, double ms[2]);
+int p3d_set_prior_map(p3d_handle* h, const float* map, int H, int W);
+int p3d_get_prior_map(p3d_handle* h, float* out /* may be NULL */, int64_t cap, int* H, int* W);
+int p3d_set_prior_stage(p3d_handle* h, int mode, float a);
+int p3d_get_prior_stage(p3d_handle* h, int* mode, float* a);
+int p3d_set_eval_extra_prior(p3d_handle* h, int flags);
+int p3d_debug_prior_count(int device, int kind, const unsigned char* maps, int64_t n, int H, int W, int sign, const uint32_t* counts_in,
+                          int offset, uint32_t* counts_out, int* flag_out);
+int p3d_debug_prior_count_plan(int64_t n, int H, int W, int offset, int64_t* words, int64_t* singles, int* slices);
+int p3d_debug_prior_apply(int device, int mode, float a, const float* maps, int n, int H, int W, const float* prior, int offset,
+                          float* out);
+int p3d_postprocess_maps_prior(int device, const float* maps, int n, int h, int w, int elem_stride, int H, int W,
+                               const p3d_postprocess* cfg, const p3d_hist_match* match, const float* prior, int mode, float a,
+                               float scale, float* out_f32, unsigned char* out_u8);
+int p3d_debug_eval_maps_prior(int device, const float* maps, int n_maps, int h, int w, int elem_stride, const unsigned char* density,
+                              int Hd, int Wd, const unsigned char* fixation, int H, int W, const double* jitter, const int* borji_idx,
+                              const int* n_fix, int n_rep, double step_size, double* out, const p3d_postprocess* cfg,
+                              const p3d_hist_match* match, int flags, const float* baseline, double* extra, const float* prior,
+                              int mode, float a);
 
 /* ---- Resident video inference (an ADDITION beside p3d_predict_windows: gen_pred.py slides a 16-frame queue by one frame and keeps
  * nothing on the device).  A video's normalised frames go up once, windows are cut where the frames are, and every frame's map is

@@ -60,6 +60,10 @@ P3D_HIST_MAX_BINS = 1024
 EVAL_EXTRA = {"kldiv": 1, "info_gain": 2}
 # p3d_video_open modes (include/p3d_hip.h P3D_VIDEO_*)
 VIDEO_MODES = {"newest": 0, "mean": 1}
+# P3D_PRIOR_* of include/p3d_hip.h: what a map adds to the accumulator, and how the stage combines a map with the prior
+PRIOR_KINDS = {"fixations": 0, "bytes": 1}
+PRIOR_MODES = {"off": 0, "mul": 1, "mix": 2}
+P3D_PRIOR_MAX_MAPS = 16000000
 
 
 # the descriptors of p3d_debug_fused_conv (include/p3d_hip.h)
@@ -278,6 +282,27 @@ SIGNATURES = {
                                             C.POINTER(P3dPostprocess), C.POINTER(P3dHistMatch), C.c_int, _fp, _dp]),
     "p3d_metric_kldiv": (C.c_int, [C.c_int, _fp, _fp, C.c_int, C.c_int, _dp]),
     "p3d_metric_info_gain": (C.c_int, [C.c_int, _fp, _fp, _fp, C.c_int, C.c_int, _dp]),
+    "p3d_prior_open": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "p3d_prior_add": (C.c_int, [C.c_void_p, _u8p, C.c_int64, C.c_int]),
+    "p3d_prior_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), _i64p]),
+    "p3d_prior_info": (C.c_int, [C.c_void_p, _ip, _ip, _ip, _i64p]),
+    "p3d_prior_finish": (C.c_int, [C.c_void_p, C.c_float, C.c_int, _fp]),
+    "p3d_prior_close": (C.c_int, [C.c_void_p]),
+    "p3d_prior_last_ms": (C.c_int, [C.c_void_p, _dp]),
+    "p3d_set_prior_map": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int]),
+    "p3d_get_prior_map": (C.c_int, [C.c_void_p, _fp, C.c_int64, _ip, _ip]),
+    "p3d_set_prior_stage": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
+    "p3d_get_prior_stage": (C.c_int, [C.c_void_p, _ip, _fp]),
+    "p3d_set_eval_extra_prior": (C.c_int, [C.c_void_p, C.c_int]),
+    "p3d_debug_prior_count": (C.c_int, [C.c_int, C.c_int, _u8p, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_int,
+                                        C.POINTER(C.c_uint32), _ip]),
+    "p3d_debug_prior_count_plan": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, _i64p, _i64p, _ip]),
+    "p3d_debug_prior_apply": (C.c_int, [C.c_int, C.c_int, C.c_float, _fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp]),
+    "p3d_postprocess_maps_prior": (C.c_int, [C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(P3dPostprocess),
+                                             C.POINTER(P3dHistMatch), _fp, C.c_int, C.c_float, C.c_float, _fp, _u8p]),
+    "p3d_debug_eval_maps_prior": (C.c_int, [C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ubyte), C.c_int, C.c_int,
+                                            C.POINTER(C.c_ubyte), C.c_int, C.c_int, _dp, _ip, _ip, C.c_int, C.c_double, _dp,
+                                            C.POINTER(P3dPostprocess), C.POINTER(P3dHistMatch), C.c_int, _fp, _dp, _fp, C.c_int, C.c_float]),
     "p3d_video_open": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "p3d_video_close": (C.c_int, [C.c_void_p]),
     "p3d_video_info": (C.c_int, [C.c_void_p, _ip, _ip, _ip]),

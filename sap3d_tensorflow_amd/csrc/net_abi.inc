@@ -2726,6 +2726,19 @@ void match_carve(Carve& c, MatchScratch& ms, const MatchPlan& mp, int chunk, lon
     ms.tpart = dens ? c.take<float>((size_t)chunk * p3d_post_blocks(N) * 2) : nullptr;
     ms.tmnmx = dens ? c.take<float>((size_t)chunk * 2) : nullptr;
 }
+// p3d_set_prior_stage's stage for one launch sequence: the mode, the weight and the prior map (device memory) with its size
+struct PriorStage {
+    int mode = P3D_PRIOR_OFF; float a = 0.f; const float* map = nullptr; int H = 0, W = 0;
+    bool on() const { return mode != P3D_PRIOR_OFF; }
+    // refused when the stage runs: no prior, or a prior of another size than the stage's
+    void fits(int sH, int sW) const {
+        if (!on()) return;
+        if (!map) throw P3dError("prior_stage: the handle has no prior (p3d_prior_finish or p3d_set_prior_map)");
+        if (H != sH || W != sW)
+            throw P3dError("prior_stage: the prior is " + std::to_string(H) + " x " + std::to_string(W) + ", the maps " + std::to_string(sH) + " x " + std::to_string(sW));
+    }
+};
+PriorStage prior_stage_of(const p3d_handle* h) { return PriorStage{h->prior_mode, h->prior_a, h->prior_map, h->prior_H, h->prior_W}; }
 // n maps of one source: map m's pixel (y, x) at p[m * map_stride + (y * w + x) * elem_stride] (device memory)
 struct PostRun { const float* p; long long map_stride; int elem_stride, n; };
 // resize -> blur -> normalise (-> quantise) of `total` maps on stream s, at most `chunk` maps per pass through the stages.
@@ -2733,11 +2746,14 @@ struct PostRun { const float* p; long long map_stride; int elem_stride, n; };
 // (device) receives the float32 result, or null: the maps pass through ps.maps.  u8 (device, 4-byte aligned) or null: map k's
 // bytes at u8_off + k * H * W.  counters: `chunk` zeroed arrival counters.  Queues only (after one synchronising upload of the taps).
 // mp / ms: p3d_set_hist_match's stage between the blur and the normalisation (null or off: not issued); density [total][H][W]
-// (device): under P3D_MATCH_DENSITY map k's target, evaluation's float32(b / 255.) density.
+// (device): under P3D_MATCH_DENSITY map k's target, evaluation's float32(b / 255.) density.  pr: p3d_set_prior_stage's stage
+// after the blur (null or off: not issued).
 void post_sequence(hipStream_t s, const std::vector<PostRun>& runs, int total, int h, int w, int H, int W, const PostPlan& pl,
                    const PostScratch& ps, unsigned* counters, int chunk, float* f32, unsigned char* u8, long long u8_off, float scale,
-                   const MatchPlan* mp = nullptr, const MatchScratch* ms = nullptr, const float* density = nullptr) {
+                   const MatchPlan* mp = nullptr, const MatchScratch* ms = nullptr, const float* density = nullptr,
+                   const PriorStage* pr = nullptr) {
     pl.fits(H, W);
+    if (pr) pr->fits(H, W);
     const long long N = (long long)H * W;
     if (pl.r > 0) HIPCHECK(copy_now(ps.taps, pl.taps.data(), pl.taps.size() * sizeof(float), hipMemcpyHostToDevice, s));
     const bool match = mp && mp->on();
@@ -2765,6 +2781,7 @@ void post_sequence(hipStream_t s, const std::vector<PostRun>& runs, int total, i
         a.n = cn; a.H = H; a.W = W; a.maps = maps; a.tmp = ps.tmp; a.taps = ps.taps; a.r = pl.r; a.norm = pl.norm;
         a.part = ps.part; a.mnmx = ps.mnmx; a.counter = counters; a.nblk = p3d_post_blocks(N);
         a.u8 = u8; a.u8_off = u8_off + (long long)done * N; a.scale = scale;
+        if (pr && pr->on()) { a.prior = pr->map; a.prior_mode = pr->mode; a.prior_a = pr->a; a.prior_b = (float)(1.0 - (double)pr->a); }
         HistChain hc;
         if (match) {
             HistArgs& q = hc.source;           // (its maps are a's: p3d_post_launch fills them in)
@@ -2797,15 +2814,18 @@ struct EvalExtra { int flags; const float* base; const double* bstat; int H, W; 
 // the source maps readable; it runs after the uploads, inside the metric stage's time.
 void eval_maps(hipStream_t s, const EvalSource& src, const std::function<void(hipStream_t)>& prepare, const unsigned char* density, int Hd, int Wd, const unsigned char* fixation, int H,
                int W, const double* jitter, const int* borji_idx, const int* n_fix, int n_rep, double step_size, double* out,
-               double* stage_ms, const p3d_postprocess* post = nullptr, const MatchPlan* matchp = nullptr, const EvalExtra* extra = nullptr) {
+               double* stage_ms, const p3d_postprocess* post = nullptr, const MatchPlan* matchp = nullptr, const EvalExtra* extra = nullptr,
+               const PriorStage* priorp = nullptr) {
     const PostPlan plan(post);                 // p3d_set_postprocess: between the resize and the metrics, in place on P
     const MatchPlan match = matchp ? *matchp : MatchPlan();      // p3d_set_hist_match: after the blur, before the normalisation
-    const bool chain = plan.on || match.on();
+    const PriorStage prior = priorp ? *priorp : PriorStage();    // p3d_set_prior_stage: after the blur, before the matching
+    const bool chain = plan.on || match.on() || prior.on();
     if (!src.p || !density || !fixation || !n_fix || !out) throw P3dError("null argument");
     if (Hd < 1 || Wd < 1 || H < 1 || W < 1) throw P3dError("eval: empty map");
     if ((long long)H * W > INT32_MAX / 2) throw P3dError("eval: map too large");
     if (n_rep < 1 || !(step_size > 0.0)) throw P3dError("eval: AUC_Borji needs n_rep >= 1 and a positive step");
     if (plan.on) plan.fits(H, W);
+    prior.fits(H, W);
     const bool xon = extra && extra->flags != 0;                 // p3d_set_eval_extra: one launch after pass A, on the scored map
     if (xon && !extra->out) throw P3dError("null argument");
     if (xon && (extra->flags & P3D_EVAL_INFO_GAIN) && (!extra->base || !extra->bstat || extra->H != H || extra->W != W))
@@ -2866,7 +2886,7 @@ void eval_maps(hipStream_t s, const EvalSource& src, const std::function<void(hi
     if (density_first) HIPCHECK(p3d_mapf_density(dens, B, Hd, Wd, D, H, W, s));
     if (chain)
         post_sequence(s, {{src.p, src.map_stride, src.elem_stride, B}}, B, src.h, src.w, H, W, plan, post_scratch, counters, post_chunk, P,
-                      nullptr, 0, 0.f, &match, &match_scratch, D);
+                      nullptr, 0, 0.f, &match, &match_scratch, D, &prior);
     else
         HIPCHECK(p3d_resize_f32(src.p, src.map_stride, src.elem_stride, B, src.h, src.w, P, H, W, s));
     if (!density_first) HIPCHECK(p3d_mapf_density(dens, B, Hd, Wd, D, H, W, s));      // test.py's density: uint8 resize (dataflow.py:236-238)
@@ -2967,9 +2987,11 @@ int p3d_eval_last_frames(p3d_handle* h, const unsigned char* density, int Hd, in
     std::vector<double> xv((size_t)pr->N * 2);
     extra.out = xv.data();
     if (extra.flags) { h->extra_state = p3d_handle::EXTRA_NONE; h->extra_eval_H = H; h->extra_eval_W = W; }
+    const PriorStage hprior = prior_stage_of(h);
     eval_maps(h->stream, {pr->p + (size_t)(T - 1) * hw * pr->ld, (long long)T * hw * pr->ld, pr->ld, pr->N, pr->H, pr->W}, prepare,
               density, Hd, Wd, fixation, H, W, jitter, borji_idx, n_fix, n_rep, step_size, out, stage_ms,
-              h->post_on ? &h->post_cfg : nullptr, h->match_cfg.on() ? &h->match_cfg : nullptr, extra.flags && fits ? &extra : nullptr);
+              h->post_on ? &h->post_cfg : nullptr, h->match_cfg.on() ? &h->match_cfg : nullptr, extra.flags && fits ? &extra : nullptr,
+              h->prior_mode != P3D_PRIOR_OFF ? &hprior : nullptr);
     if (extra.flags) {
         h->extra_state = fits ? p3d_handle::EXTRA_HAVE : p3d_handle::EXTRA_SHAPE;
         if (fits) h->extra_last.swap(xv);
@@ -3154,7 +3176,10 @@ void maps_u8_chain(p3d_handle* h, long long maps, int ph, int pw, float scale, i
     const MatchPlan& match = h->match_cfg;
     if (match.mode == P3D_MATCH_DENSITY)
         throw P3dError("hist_match: P3D_MATCH_DENSITY matches to a ground-truth density and runs in p3d_eval_last_frames only; written maps take P3D_MATCH_TABLE");
-    const bool chain = plan.on || match.on();
+    // p3d_set_prior_stage: the same float32 chain, with its stage after the blur
+    const PriorStage prior = prior_stage_of(h);
+    prior.fits(H, W);
+    const bool chain = plan.on || match.on() || prior.on();
     const int post_chunk = (int)std::min<long long>(maps, P3D_POST_CHUNK);
     PostScratch post_scratch;
     MatchScratch match_scratch;
@@ -3175,7 +3200,7 @@ void maps_u8_chain(p3d_handle* h, long long maps, int ph, int pw, float scale, i
     if (stage_ms) HIPCHECK(hipEventRecord(ev[0], s));
     std::vector<PostRun> runs;
     sources(s, ex, runs);
-    if (chain) post_sequence(s, runs, (int)maps, ph, pw, H, W, plan, post_scratch, counters, post_chunk, nullptr, d, 0, scale, &match, &match_scratch);
+    if (chain) post_sequence(s, runs, (int)maps, ph, pw, H, W, plan, post_scratch, counters, post_chunk, nullptr, d, 0, scale, &match, &match_scratch, nullptr, &prior);
     else {
         long long off = 0;
         for (const PostRun& r : runs) {
@@ -3292,9 +3317,12 @@ int p3d_gaussian_blur(int device, const float* src, int n, int H, int W, float s
 }  // extern "C"
 namespace {
 void postprocess_maps(int device, const float* maps, int n, int h, int w, int elem_stride, int H, int W, const p3d_postprocess* cfg,
-                      const p3d_hist_match* match, float scale, float* out_f32, unsigned char* out_u8) {
+                      const p3d_hist_match* match, float scale, float* out_f32, unsigned char* out_u8, const float* prior = nullptr,
+                      int prior_mode = P3D_PRIOR_OFF, float prior_a = 0.f) {
     const PostPlan plan(cfg);
     const MatchPlan mp = p3d_handle::match_parse(match);
+    p3d_handle::prior_stage_check(prior_mode, prior_a);
+    if (prior_mode != P3D_PRIOR_OFF) p3d_handle::prior_map_check(prior, H, W);      // (the prior of the hook has the stage's size)
     if (mp.mode == P3D_MATCH_DENSITY) throw P3dError("hist_match: P3D_MATCH_DENSITY runs in evaluation only; supplied maps take P3D_MATCH_TABLE");
     metric_args(device, maps, maps, 1, 1, maps);
     if (n < 1 || h < 1 || w < 1 || elem_stride < 1 || H < 1 || W < 1) throw P3dError("postprocess_maps: empty map");
@@ -3302,7 +3330,8 @@ void postprocess_maps(int device, const float* maps, int n, int h, int w, int el
     plan.fits(H, W);
     const long long N = (long long)H * W, per_map = (long long)h * w * elem_stride, ne = (long long)n * N;
     const int chunk = std::min(n, P3D_POST_CHUNK);
-    DevArr<float> src((size_t)n * per_map, maps);
+    DevArr<float> src((size_t)n * per_map, maps), dprior(prior_mode != P3D_PRIOR_OFF ? (size_t)N : 1, prior_mode != P3D_PRIOR_OFF ? prior : nullptr);
+    const PriorStage pst{prior_mode, prior_a, dprior.p, H, W};
     // the outputs between guards: 8 floats either side of out_f32; out_u8 at byte 19 of a buffer of guard words
     const uint32_t guard = 0x7fc5a5a5u;                    // a NaN no arithmetic here produces
     const long long fat = 8, bat = 19, bwords = (ne + bat + 16 + 3) / 4;
@@ -3321,7 +3350,7 @@ void postprocess_maps(int device, const float* maps, int n, int h, int w, int el
     match_carve(c, ms, mp, chunk, N);
     post_sequence(nullptr, {{src.p, per_map, elem_stride, n}}, n, h, w, H, W, plan, ps, counters, chunk,
                   out_f32 ? reinterpret_cast<float*>(fbuf.p) + fat : nullptr, out_u8 ? reinterpret_cast<unsigned char*>(bbuf.p) : nullptr, bat,
-                  scale, &mp, &ms);
+                  scale, &mp, &ms, nullptr, &pst);
     if (out_f32) {
         std::vector<uint32_t> back(fg.size());
         fbuf.get(back.data(), back.size());
@@ -3448,6 +3477,295 @@ int p3d_match_hist_maps(int device, const float* maps, const float* targets, int
     c.source.tcdf = bt.cdf.p; c.source.tcentre = bt.centre.p; c.source.nt = nbins; c.source.t_stride = nbins; c.source.out = dst.p;
     HIPCHECK(p3d_hist_chain_launch(c, nullptr));
     dst.get(out, (size_t)n * N);
+    API_END
+}
+
+}  // extern "C"
+namespace {
+// ---- fixation priors (include/p3d_hip.h; the handle's part in net_sched.inc, the kernels in prior.hip) -------------------------
+// Counts -> float32 -> BLUR -> NORM (max) on stream s: the conversion, then the shared launch sequence on one map, in place on
+// `map` [H * W] (device).  Returns the float32 maximum of the blurred counts (0: every count was zero, the map is left unscaled).
+float prior_finish_launches(hipStream_t s, const unsigned* count, int H, int W, const PostPlan& plan, float* map) {
+    const long long N = (long long)H * W;
+    PostScratch ps;
+    Carve c;
+    post_carve(c, ps, plan, 1, N, false);
+    float* slab = nullptr;
+    unsigned* counters = nullptr;
+    HIPCHECK(p3d_stream_scratch(s, (c.off + 3) / 4, 1, &slab, &counters));
+    c = Carve{(char*)slab, 0};
+    post_carve(c, ps, plan, 1, N, false);
+    HIPCHECK(p3d_prior_float(count, map, N, s));
+    post_sequence(s, {}, 1, H, W, H, W, plan, ps, counters, 1, map, nullptr, 0, 0.f);
+    float mnmx[2] = {0.f, 0.f};
+    HIPCHECK(copy_now(mnmx, ps.mnmx, sizeof(mnmx), hipMemcpyDeviceToHost, s));
+    return mnmx[1];
+}
+PostPlan prior_plan(float sigma, int radius, int H, int W) {
+    const p3d_postprocess cfg{sigma, radius, P3D_NORM_MAX};
+    const PostPlan plan(&cfg);                 // the blur's own refusals
+    plan.fits(H, W);
+    return plan;
+}
+void prior_finish(p3d_handle* h, float sigma, int radius, float* out) {
+    h->prior_need_open("prior_finish");
+    const int H = h->prior_acc_H, W = h->prior_acc_W;
+    const PostPlan plan = prior_plan(sigma, radius, H, W);
+    if (h->prior_n_maps < 1) throw P3dError("prior_finish: the accumulator holds no maps");
+    if (h->prior_underflowed()) throw P3dError("prior_finish: a subtraction took a count below zero (maps were taken out that were never added); open the accumulator again");
+    const hipStream_t s = h->stream;
+    float* map = nullptr;
+    HIPCHECK(hipMalloc((void**)&map, (size_t)H * W * sizeof(float)));
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    try {
+        for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
+        HIPCHECK(hipEventRecord(ev[0], s));
+        const float mx = prior_finish_launches(s, h->prior_count, H, W, plan, map);
+        HIPCHECK(hipEventRecord(ev[1], s));
+        HIPCHECK(hipStreamSynchronize(s));
+        if (!(mx > 0.f)) throw P3dError("prior_finish: every count is zero");
+        float t = 0.f;
+        HIPCHECK(hipEventElapsedTime(&t, ev[0], ev[1]));
+        h->prior_ms[1] = t;
+        if (out) HIPCHECK(copy_now(out, map, (size_t)H * W * sizeof(float), hipMemcpyDeviceToHost, s));
+    } catch (...) {
+        for (auto& e : ev) if (e) hipEventDestroy(e);
+        hipFree(map);
+        throw;
+    }
+    for (auto& e : ev) hipEventDestroy(e);
+    h->prior_map_take(map, H, W);
+}
+// op level: a device array of `n` elements between `guard` elements of guard words on either side, the data `shift` elements in
+template <typename T>
+struct Guarded {
+    static constexpr uint32_t WORD = 0x7fc5a5a5u;          // a NaN no arithmetic here produces
+    size_t n, at, total; std::vector<T> init; DevArr<T> dev;
+    static std::vector<T> fill(size_t total) {
+        std::vector<T> v(total);
+        const unsigned char pat[4] = {0xa5, 0xa5, 0xc5, 0x7f};
+        unsigned char* b = reinterpret_cast<unsigned char*>(v.data());
+        for (size_t i = 0; i < total * sizeof(T); ++i) b[i] = pat[i & 3];
+        return v;
+    }
+    Guarded(size_t n_, size_t guard, size_t shift, const T* host)
+        : n(n_), at(guard + shift), total(n_ + 2 * guard + shift), init(fill(total)), dev(total) {
+        if (host) std::copy(host, host + n, init.begin() + at); else std::fill(init.begin() + at, init.begin() + at + n, T());
+        HIPCHECK(copy_now(dev.p, init.data(), total * sizeof(T), hipMemcpyHostToDevice, nullptr));
+    }
+    T* data() { return dev.p + at; }
+    // the data into out (or nowhere); throws if anything outside it changed
+    void back(T* out, const char* what) {
+        std::vector<T> got(total);
+        dev.get(got.data(), total);
+        if (memcmp(got.data(), init.data(), at * sizeof(T)) || memcmp(got.data() + at + n, init.data() + at + n, (total - at - n) * sizeof(T)))
+            throw P3dError(std::string(what) + ": a launch wrote outside its buffer");
+        if (out) memcpy(out, got.data() + at, n * sizeof(T));
+    }
+    void unchanged(const char* what) {
+        std::vector<T> got(total);
+        dev.get(got.data(), total);
+        if (memcmp(got.data(), init.data(), total * sizeof(T))) throw P3dError(std::string(what) + ": a launch wrote to a read-only buffer");
+    }
+};
+}  // namespace
+extern "C" {
+
+int p3d_prior_open(p3d_handle* h, int H, int W, int kind) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->prior_open(H, W, kind);
+    API_END
+}
+
+int p3d_prior_close(p3d_handle* h) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->prior_close();
+    API_END
+}
+
+int p3d_prior_info(p3d_handle* h, int* H, int* W, int* kind, int64_t* n_maps) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    h->prior_need_open("prior_info");
+    if (H) *H = h->prior_acc_H;
+    if (W) *W = h->prior_acc_W;
+    if (kind) *kind = h->prior_kind;
+    if (n_maps) *n_maps = h->prior_n_maps;
+    API_END
+}
+
+int p3d_prior_add(p3d_handle* h, const unsigned char* maps, int64_t n, int sign) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->prior_add(maps, n, sign);
+    API_END
+}
+
+int p3d_prior_counts(p3d_handle* h, uint32_t* out, int64_t* n_maps) {
+    API_BEGIN
+    if (!h || !out) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->prior_need_open("prior_counts");
+    if (h->prior_underflowed()) throw P3dError("prior_counts: a subtraction took a count below zero (maps were taken out that were never added); open the accumulator again");
+    HIPCHECK(copy_now(out, h->prior_count, (size_t)h->prior_acc_H * h->prior_acc_W * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (n_maps) *n_maps = h->prior_n_maps;
+    API_END
+}
+
+int p3d_prior_finish(p3d_handle* h, float sigma, int radius, float* out) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    prior_finish(h, sigma, radius, out);
+    API_END
+}
+
+int p3d_prior_last_ms(p3d_handle* h, double ms[2]) {
+    API_BEGIN
+    if (!h || !ms) throw P3dError("null argument");
+    ms[0] = h->prior_ms[0]; ms[1] = h->prior_ms[1];
+    API_END
+}
+
+int p3d_set_prior_map(p3d_handle* h, const float* map, int H, int W) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->set_prior_map(map, H, W);
+    API_END
+}
+
+int p3d_get_prior_map(p3d_handle* h, float* out, int64_t cap, int* H, int* W) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    if (H) *H = h->prior_H;
+    if (W) *W = h->prior_W;
+    if (out) {
+        if (!h->prior_map) throw P3dError("get_prior_map: the handle has no prior (p3d_prior_finish or p3d_set_prior_map)");
+        const int64_t n = (int64_t)h->prior_H * h->prior_W;
+        if (cap < n) throw P3dError("get_prior_map: room for " + std::to_string(cap) + " floats, " + std::to_string(n) + " needed");
+        HIPCHECK(hipSetDevice(h->cfg.device));
+        HIPCHECK(copy_now(out, h->prior_map, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    }
+    API_END
+}
+
+int p3d_set_prior_stage(p3d_handle* h, int mode, float a) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    h->set_prior_stage(mode, a);
+    API_END
+}
+
+int p3d_get_prior_stage(p3d_handle* h, int* mode, float* a) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    if (mode) *mode = h->prior_mode;
+    if (a) *a = h->prior_a;
+    API_END
+}
+
+int p3d_set_eval_extra_prior(p3d_handle* h, int flags) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->set_eval_extra_prior(flags);
+    API_END
+}
+
+int p3d_debug_prior_count(int device, int kind, const unsigned char* maps, int64_t n, int H, int W, int sign, const uint32_t* counts_in,
+                          int offset, uint32_t* counts_out, int* flag_out) {
+    API_BEGIN
+    metric_args(device, maps, maps, 1, 1, counts_out);
+    if (!flag_out) throw P3dError("null argument");
+    if (H < 1 || W < 1 || (long long)H * W > INT32_MAX / 2) throw P3dError("prior_count: maps are H x W bytes, 1 <= H * W <= 2^30");
+    if (n < 1 || n > P3D_PRIOR_MAX_MAPS) throw P3dError("prior_count: 1 .. P3D_PRIOR_MAX_MAPS maps");
+    if (kind != P3D_PRIOR_FIXATIONS && kind != P3D_PRIOR_BYTES) throw P3dError("prior_count: unknown kind " + std::to_string(kind));
+    if (sign != 1 && sign != -1) throw P3dError("prior_count: sign must be +1 or -1");
+    if (offset < 0 || offset > 3) throw P3dError("prior_count: offset in [0, 3]");
+    const size_t N = (size_t)H * W;
+    Guarded<unsigned char> src((size_t)n * N, 16, (size_t)offset, maps);
+    Guarded<uint32_t> cnt(N, 8, 0, counts_in), flag(1, 2, 0, nullptr);
+    PriorCountArgs a;
+    a.maps = src.data(); a.n = n; a.n_pix = (long long)N; a.kind = kind; a.sign = sign; a.count = cnt.data(); a.flag = flag.data();
+    HIPCHECK(p3d_prior_count_launch(a, nullptr));
+    uint32_t f = 0;
+    cnt.back(counts_out, "prior_count");
+    flag.back(&f, "prior_count");
+    src.unchanged("prior_count");
+    if (f > 1) throw P3dError("prior_count: the flag holds " + std::to_string(f));
+    *flag_out = (int)f;
+    API_END
+}
+
+int p3d_debug_prior_count_plan(int64_t n, int H, int W, int offset, int64_t* words, int64_t* singles, int* slices) {
+    API_BEGIN
+    if (!words || !singles || !slices) throw P3dError("null argument");
+    unsigned dummy[2];
+    PriorCountArgs a;
+    a.maps = reinterpret_cast<const unsigned char*>((uintptr_t)256 + (uintptr_t)(offset & 3)); a.n = n; a.n_pix = (long long)H * W;
+    a.count = dummy; a.flag = dummy + 1;
+    if (H < 1 || W < 1 || !p3d_prior_count_plan(a)) throw P3dError("prior_count_plan: arguments the launcher refuses");
+    *words = a.words; *singles = a.singles; *slices = a.slices;
+    API_END
+}
+
+int p3d_debug_prior_apply(int device, int mode, float a, const float* maps, int n, int H, int W, const float* prior, int offset, float* out) {
+    API_BEGIN
+    metric_args(device, maps, prior, 1, 1, out);
+    if (n < 1 || n > 65535 || H < 1 || W < 1 || (long long)H * W > INT32_MAX / 2) throw P3dError("prior_apply: 1 .. 65535 maps of H x W floats, 1 <= H * W <= 2^30");
+    p3d_handle::prior_stage_check(mode, a);
+    if (mode == P3D_PRIOR_OFF) throw P3dError("prior_apply: the mode is P3D_PRIOR_MUL or P3D_PRIOR_MIX");
+    if (offset < 0 || offset > 15) throw P3dError("prior_apply: offset in [0, 15]");
+    const size_t N = (size_t)H * W;
+    Guarded<float> v((size_t)n * N, 8, (size_t)(offset & 3), maps), g(N, 8, (size_t)((offset >> 2) & 3), prior);
+    PriorApplyArgs q;
+    q.maps = v.data(); q.prior = g.data(); q.n = n; q.n_pix = (int)N; q.mode = mode; q.nblk = p3d_post_blocks((long long)N);
+    q.a = a; q.b = (float)(1.0 - (double)a);
+    HIPCHECK(p3d_prior_apply_launch(q, nullptr));
+    v.back(out, "prior_apply");
+    g.unchanged("prior_apply");
+    API_END
+}
+
+int p3d_postprocess_maps_prior(int device, const float* maps, int n, int h, int w, int elem_stride, int H, int W, const p3d_postprocess* cfg,
+                               const p3d_hist_match* match, const float* prior, int mode, float a, float scale, float* out_f32,
+                               unsigned char* out_u8) {
+    API_BEGIN
+    postprocess_maps(device, maps, n, h, w, elem_stride, H, W, cfg, match, scale, out_f32, out_u8, prior, mode, a);
+    API_END
+}
+
+int p3d_debug_eval_maps_prior(int device, const float* maps, int n_maps, int h, int w, int elem_stride, const unsigned char* density,
+                              int Hd, int Wd, const unsigned char* fixation, int H, int W, const double* jitter, const int* borji_idx,
+                              const int* n_fix, int n_rep, double step_size, double* out, const p3d_postprocess* cfg,
+                              const p3d_hist_match* match, int flags, const float* baseline, double* extra, const float* prior, int mode,
+                              float a) {
+    API_BEGIN
+    const MatchPlan mp = p3d_handle::match_parse(match);
+    metric_args(device, maps, maps, n_maps, 1, out);
+    if (h < 1 || w < 1 || elem_stride < 1) throw P3dError("eval: empty map");
+    if (flags && !extra) throw P3dError("null argument");
+    p3d_handle::prior_stage_check(mode, a);
+    const bool from_prior = (flags & P3D_EVAL_INFO_GAIN) && !baseline;       // the prior is the baseline, copied device to device
+    if (mode != P3D_PRIOR_OFF || from_prior || prior) p3d_handle::prior_map_check(prior, H, W);
+    if (!from_prior) p3d_handle::eval_extra_check(flags, baseline, H, W);
+    else if (flags & ~(P3D_EVAL_KLDIV | P3D_EVAL_INFO_GAIN)) throw P3dError("eval_extra: unknown flags " + std::to_string(flags));
+    const long long per_map = (long long)h * w * elem_stride;
+    const bool ig = (flags & P3D_EVAL_INFO_GAIN) != 0;
+    DevArr<float> src((size_t)n_maps * per_map, maps), base(ig ? (size_t)H * W : 1), dprior(prior ? (size_t)H * W : 1, prior);
+    DevArr<double> bstat(3);
+    if (ig) p3d_handle::eval_extra_upload(from_prior ? dprior.p : baseline, H, W, base.p, bstat.p, nullptr,
+                                          from_prior ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice);
+    const EvalExtra x{flags, ig ? base.p : nullptr, ig ? bstat.p : nullptr, H, W, extra};
+    const PriorStage pst{mode, a, dprior.p, H, W};
+    eval_maps(nullptr, {src.p, per_map, elem_stride, n_maps, h, w}, nullptr, density, Hd, Wd, fixation, H, W, jitter, borji_idx, n_fix, n_rep,
+              step_size, out, nullptr, cfg, &mp, &x, &pst);
     API_END
 }
 

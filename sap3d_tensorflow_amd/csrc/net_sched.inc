@@ -626,13 +626,14 @@
         if (!varies) throw P3dError("eval_extra: the baseline must not be constant");
     }
     // a baseline on the device with its statistics, one launch on stream s (synchronised on return): base [H * W], bstat [3]
-    static void eval_extra_upload(const float* baseline, int H, int W, float* base, double* bstat, hipStream_t s) {
+    static void eval_extra_upload(const float* baseline, int H, int W, float* base, double* bstat, hipStream_t s,
+                                  hipMemcpyKind kind = hipMemcpyHostToDevice) {
         const long long N = (long long)H * W;
         P3dFullStats3 q;
         q.maps = base; q.n_pix = N; q.n_maps = 1; q.nblk = p3d_full_blocks(N); q.out = bstat;
         HIPCHECK(hipMalloc((void**)&q.part, (size_t)q.nblk * P3D_FULL_STATS3_PARTS * sizeof(double)));
         hipError_t e = hipMalloc((void**)&q.counter, sizeof(unsigned));
-        if (e == hipSuccess) e = copy_now(base, baseline, (size_t)N * sizeof(float), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = copy_now(base, baseline, (size_t)N * sizeof(float), kind, s);
         if (e == hipSuccess) e = fill_now(q.counter, 0, sizeof(unsigned), s);
         if (e == hipSuccess) e = p3d_full_stats3(q, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -657,6 +658,153 @@
         eval_extra_free();
         extra_flags = flags; extra_base = nb; extra_bstat = ns;
         if (baseline) { extra_H = H; extra_W = W; extra_base_host.assign(baseline, baseline + (size_t)H * W); }
+    }
+
+    // p3d_set_eval_extra_prior: set_eval_extra with the handle's prior as the baseline, copied device to device; its statistics
+    // come from the same one launch
+    void set_eval_extra_prior(int flags) {
+        if (flags & ~(P3D_EVAL_KLDIV | P3D_EVAL_INFO_GAIN)) throw P3dError("eval_extra: unknown flags " + std::to_string(flags));
+        if (!(flags & P3D_EVAL_INFO_GAIN)) throw P3dError("eval_extra: a baseline is given without P3D_EVAL_INFO_GAIN");
+        if (!prior_map) throw P3dError("eval_extra: the handle has no prior (p3d_prior_finish or p3d_set_prior_map)");
+        const int H = prior_H, W = prior_W;
+        float* nb = nullptr; double* ns = nullptr;
+        std::vector<float> host((size_t)H * W);
+        try {                                  // the new copy first: a failure changes nothing
+            HIPCHECK(hipMalloc((void**)&nb, host.size() * sizeof(float)));
+            HIPCHECK(hipMalloc((void**)&ns, 3 * sizeof(double)));
+            eval_extra_upload(prior_map, H, W, nb, ns, stream, hipMemcpyDeviceToDevice);
+            HIPCHECK(copy_now(host.data(), nb, host.size() * sizeof(float), hipMemcpyDeviceToHost, stream));
+        } catch (...) {
+            if (nb) hipFree(nb);
+            if (ns) hipFree(ns);
+            throw;
+        }
+        eval_extra_free();
+        extra_flags = flags; extra_base = nb; extra_bstat = ns; extra_H = H; extra_W = W;
+        extra_base_host.swap(host);
+    }
+
+    // ---- fixation priors (p3d_prior_*, p3d_set_prior_map, p3d_set_prior_stage; prior.hip) -------------------
+    // Nothing exists before p3d_prior_open or p3d_set_prior_map, and off nothing here runs.  The accumulator (uint32 counts, the
+    // underflow flag, a staging buffer for uploaded maps) and the finished prior map are private allocations (freed by
+    // p3d_prior_close / when the map is replaced, and by the destructor; not part of `allocs`): no step, launch list or captured
+    // graph names them.  The stage is issued by post_sequence (net_abi.inc) after the blur.  The operations that need that
+    // sequence (finish) live in net_abi.inc.
+    bool prior_is_open = false;
+    int prior_kind = P3D_PRIOR_FIXATIONS, prior_acc_H = 0, prior_acc_W = 0;
+    int64_t prior_n_maps = 0;
+    unsigned* prior_count = nullptr; unsigned* prior_flag = nullptr;
+    unsigned char* prior_staging = nullptr; size_t prior_staging_bytes = 0;
+    float* prior_map = nullptr; int prior_H = 0, prior_W = 0;
+    int prior_mode = P3D_PRIOR_OFF; float prior_a = 0.f;
+    double prior_ms[2] = {0.0, 0.0};           // the count launches of the last p3d_prior_add; the last p3d_prior_finish's launches
+    void prior_need_open(const char* what) const {
+        if (!prior_is_open) throw P3dError(std::string(what) + ": no accumulator is open (p3d_prior_open)");
+    }
+    void prior_close() {
+        for (void* p : {(void*)prior_count, (void*)prior_flag, (void*)prior_staging}) if (p) hipFree(p);
+        prior_count = nullptr; prior_flag = nullptr; prior_staging = nullptr; prior_staging_bytes = 0;
+        prior_is_open = false; prior_n_maps = 0; prior_acc_H = prior_acc_W = 0;
+    }
+    void prior_open(int H, int W, int kind) {
+        if (kind != P3D_PRIOR_FIXATIONS && kind != P3D_PRIOR_BYTES) throw P3dError("prior: kind " + std::to_string(kind) + " is neither P3D_PRIOR_FIXATIONS (0) nor P3D_PRIOR_BYTES (1)");
+        if (H < 1 || W < 1 || (long long)H * W > INT32_MAX / 2) throw P3dError("prior: maps are H x W bytes, 1 <= H * W <= 2^30");
+        unsigned* nc = nullptr; unsigned* nf = nullptr;
+        try {                                  // the new accumulator first: a failure changes nothing
+            HIPCHECK(hipMalloc((void**)&nc, (size_t)H * W * sizeof(unsigned)));
+            HIPCHECK(hipMalloc((void**)&nf, sizeof(unsigned)));
+            HIPCHECK(fill_now(nc, 0, (size_t)H * W * sizeof(unsigned), stream));
+            HIPCHECK(fill_now(nf, 0, sizeof(unsigned), stream));
+        } catch (...) {
+            if (nc) hipFree(nc);
+            if (nf) hipFree(nf);
+            throw;
+        }
+        prior_close();
+        prior_count = nc; prior_flag = nf; prior_is_open = true; prior_kind = kind; prior_acc_H = H; prior_acc_W = W;
+    }
+    bool prior_underflowed() {
+        unsigned f = 0;
+        HIPCHECK(copy_now(&f, prior_flag, sizeof(f), hipMemcpyDeviceToHost, stream));
+        return f != 0;
+    }
+    // maps [n][H][W] from the host, in uploads of at most 256 MB; sign +1 adds, -1 takes maps out again
+    void prior_add(const unsigned char* maps, int64_t n, int sign) {
+        prior_need_open("prior_add");
+        if (!maps) throw P3dError("null argument");
+        if (sign != 1 && sign != -1) throw P3dError("prior_add: sign must be +1 or -1, not " + std::to_string(sign));
+        if (n < 1) throw P3dError("prior_add: at least one map");
+        if (sign > 0 && (n > P3D_PRIOR_MAX_MAPS || prior_n_maps + n > P3D_PRIOR_MAX_MAPS))
+            throw P3dError("prior_add: " + std::to_string(prior_n_maps) + " + " + std::to_string(n) + " maps exceed P3D_PRIOR_MAX_MAPS = " + std::to_string((long long)P3D_PRIOR_MAX_MAPS));
+        if (sign < 0 && n > prior_n_maps)
+            throw P3dError("prior_add: " + std::to_string(n) + " maps cannot leave an accumulator of " + std::to_string(prior_n_maps));
+        const size_t N = (size_t)prior_acc_H * prior_acc_W;
+        const int64_t per = std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / N));
+        const size_t want = (size_t)std::min(n, per) * N;
+        if (want > prior_staging_bytes) {
+            unsigned char* p = nullptr;
+            HIPCHECK(hipMalloc((void**)&p, want));
+            if (prior_staging) hipFree(prior_staging);
+            prior_staging = p; prior_staging_bytes = want;
+        }
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
+        double ms = 0.0;
+        hipError_t err = hipSuccess;
+        for (int64_t done = 0; done < n && err == hipSuccess; done += per) {
+            const int64_t cn = std::min(per, n - done);
+            PriorCountArgs a;
+            a.maps = prior_staging; a.n = cn; a.n_pix = (long long)N; a.kind = prior_kind; a.sign = sign; a.count = prior_count; a.flag = prior_flag;
+            err = copy_now(prior_staging, maps + (size_t)done * N, (size_t)cn * N, hipMemcpyHostToDevice, stream);
+            if (err == hipSuccess) err = hipEventRecord(ev[0], stream);
+            if (err == hipSuccess) err = p3d_prior_count_launch(a, stream);
+            if (err == hipSuccess) err = hipEventRecord(ev[1], stream);
+            if (err == hipSuccess) err = hipStreamSynchronize(stream);
+            float t = 0.f;
+            if (err == hipSuccess) err = hipEventElapsedTime(&t, ev[0], ev[1]);
+            ms += t;
+            if (err == hipSuccess) prior_n_maps += sign * cn;
+        }
+        for (auto& e : ev) hipEventDestroy(e);
+        HIPCHECK(err);
+        prior_ms[0] = ms;
+    }
+    // a prior as the header asks for it: finite, not constant, 1 <= H * W <= 2^30
+    static void prior_map_check(const float* map, int H, int W) {
+        if (!map) throw P3dError("null argument");
+        if (H < 1 || W < 1 || (long long)H * W > INT32_MAX / 2) throw P3dError("prior: the map is H x W floats, 1 <= H * W <= 2^30");
+        const size_t n = (size_t)H * W;
+        bool varies = false;
+        for (size_t i = 0; i < n; ++i) {
+            if (!std::isfinite(map[i])) throw P3dError("prior: the map must be finite (element " + std::to_string(i) + ")");
+            varies = varies || map[i] != map[0];
+        }
+        if (!varies) throw P3dError("prior: the map must not be constant");
+    }
+    void prior_map_take(float* dev, int H, int W) {      // dev: a private allocation, owned from here on
+        if (prior_map) hipFree(prior_map);
+        prior_map = dev; prior_H = dev ? H : 0; prior_W = dev ? W : 0;
+    }
+    void set_prior_map(const float* map, int H, int W) {
+        if (!map) {                            // dropped; a stage that is on refuses when it next runs
+            prior_map_take(nullptr, 0, 0);
+            return;
+        }
+        prior_map_check(map, H, W);
+        float* p = nullptr;
+        HIPCHECK(hipMalloc((void**)&p, (size_t)H * W * sizeof(float)));
+        const hipError_t e = copy_now(p, map, (size_t)H * W * sizeof(float), hipMemcpyHostToDevice, stream);
+        if (e != hipSuccess) { hipFree(p); HIPCHECK(e); }
+        prior_map_take(p, H, W);
+    }
+    static void prior_stage_check(int mode, float a) {
+        if (mode != P3D_PRIOR_OFF && mode != P3D_PRIOR_MUL && mode != P3D_PRIOR_MIX) throw P3dError("prior_stage: unknown mode " + std::to_string(mode));
+        if (mode != P3D_PRIOR_OFF && !(a >= 0.f && a <= 1.f)) throw P3dError("prior_stage: the weight must be in [0, 1]");
+    }
+    void set_prior_stage(int mode, float a) {
+        prior_stage_check(mode, a);
+        if (mode != P3D_PRIOR_OFF && !prior_map) throw P3dError("prior_stage: the handle has no prior (p3d_prior_finish or p3d_set_prior_map)");
+        prior_mode = mode; prior_a = mode != P3D_PRIOR_OFF ? a : 0.f;
     }
 
     // ---- resident video inference (p3d_video_*; video.hip) ---------------------------------------------
@@ -1169,6 +1317,8 @@
         for (hipEvent_t e : ev_vid) if (e) hipEventDestroy(e);
         video_free();
         eval_extra_free();
+        prior_close();
+        prior_map_take(nullptr, 0, 0);
         // the streams go back to the pool (net.hip, "stream pool"); every path here has synchronised the device or never launched
         if (side_stream) { if (side_pooled) give_stream(cfg.device, 1, side_stream); else hipStreamDestroy(side_stream); }
         for (void* p : allocs) hipFree(p);

@@ -806,6 +806,7 @@ hipError_t p3d_full_extra(const P3dFullMaps& a, const P3dFullExtra& e, hipStream
 // One launch sequence on n maps of H x W floats, every stage optional:
 //   POST_RESIZE  src given: resize_f32_kernel's float32 cv2.INTER_LINEAR law, src [n] maps of h x w -> maps;
 //   POST_BLUR_H  r > 0: the horizontal pass, maps -> tmp;      POST_BLUR_V  r > 0: the vertical pass, tmp -> maps;
+//   POST_PRIOR   prior given: every map multiplied by or mixed with one prior map of H x W floats, in place (prior.hip);
 //   POST_MATCH   match given: histogram matching of every map, in place (hist_match.hip: p3d_hist_chain_launch on *match);
 //   POST_MINMAX  norm != 0: float32 min and max of every map -> mnmx[n][2], partials folded by the last arriving block;
 //   POST_APPLY   norm != 0 or u8 given: v' by `norm` stored back to maps, and sat_u8((double)fmul(v', scale)) to byte u8_off + i of
@@ -815,7 +816,7 @@ hipError_t p3d_full_extra(const P3dFullMaps& a, const P3dFullExtra& e, hipStream
 // r outside [0, P3D_POST_MAX_RADIUS] or above min(H, W) - 1, H * W above INT32_MAX, n above 65535, a missing buffer.
 constexpr int P3D_POST_MAX_RADIUS = 255;
 constexpr int P3D_POST_CHUNK = 16;            // maps per launch sequence of the chunked callers (scratch: 2 * 16 maps)
-enum { POST_RESIZE = 0, POST_BLUR_H = 1, POST_BLUR_V = 2, POST_MATCH = 3, POST_MINMAX = 4, POST_APPLY = 5, POST_STAGES = 6 };
+enum { POST_RESIZE = 0, POST_BLUR_H = 1, POST_BLUR_V = 2, POST_PRIOR = 3, POST_MATCH = 4, POST_MINMAX = 5, POST_APPLY = 6, POST_STAGES = 7 };
 struct HistChain;
 struct PostArgs {
     const float* src = nullptr; long long map_stride = 0; int elem_stride = 1, h = 0, w = 0;      // src null: no POST_RESIZE
@@ -830,6 +831,7 @@ struct PostArgs {
     int nblk = 0;                             // p3d_post_blocks(H * W)
     unsigned char* u8 = nullptr; long long u8_off = 0; float scale = 0.f;
     const HistChain* match = nullptr;         // POST_MATCH: its source is these n maps, remapped in place
+    const float* prior = nullptr; int prior_mode = 0; float prior_a = 0.f, prior_b = 0.f;      // POST_PRIOR: PriorApplyArgs' map, mode, a, b
 };
 // the vertical pass's strip for radius r: cols columns x rows output rows per block, (rows + 2r) x cols floats + r + 1 taps of LDS
 struct PostStrip { int cols, rows, lds_bytes; };
@@ -872,6 +874,40 @@ bool p3d_hist_has(int stage, const HistArgs& a);
 LaunchDesc p3d_hist_desc(int stage, const HistArgs& a);
 hipError_t p3d_hist_launch(int stage, const HistArgs& a, hipStream_t s);         // a stage the arguments do not ask for: nothing, success
 hipError_t p3d_hist_chain_launch(const HistChain& c, hipStream_t s);
+
+// ---- fixation priors (prior.hip; p3d_prior_* / p3d_set_prior_stage, the law in include/p3d_hip.h) ------------------------------
+// Count: n maps [n][n_pix] of bytes into count[n_pix], +1 per byte >= 128 (FIXATIONS) or + the byte (BYTES), times sign.  Integer
+// sums modulo 2^32: one launch on n maps leaves the words of any split into several.  A subtraction below zero stores 1 to *flag
+// and does not fault.  The launcher plans the cut (p3d_prior_count_plan fills the fields below the line) and refuses
+// (hipErrorInvalidValue) before anything is launched: a null or misaligned count / flag, n outside [1, P3D_PRIOR_MAPS_CAP],
+// n_pix outside [1, INT32_MAX], an unknown kind, a sign that is not +1 or -1.  maps may start at any byte.
+constexpr long long P3D_PRIOR_MAPS_CAP = 16000000;        // 255 * maps fits a uint32
+enum { P3D_PRIOR_KIND_FIXATIONS = 0, P3D_PRIOR_KIND_BYTES = 1 };
+enum { P3D_PRIOR_STAGE_OFF = 0, P3D_PRIOR_STAGE_MUL = 1, P3D_PRIOR_STAGE_MIX = 2 };
+struct PriorCountArgs {
+    const unsigned char* maps = nullptr;      // [n][n_pix]
+    long long n = 0, n_pix = 0;
+    int kind = P3D_PRIOR_KIND_FIXATIONS, sign = 1;
+    unsigned* count = nullptr;                // [n_pix], added to
+    unsigned* flag = nullptr;                 // one word: set to 1 by a subtraction below zero, never cleared here
+    // ---- the launcher's plan
+    long long head = 0, words = 0, singles = 0;      // pixels ahead of the first aligned word; four-pixel word lanes; one-pixel byte lanes
+    long long per_slice = 0; int slices = 1;         // maps per blockIdx.y; more than one slice: integer atomic adds
+};
+bool p3d_prior_count_plan(PriorCountArgs& a);
+LaunchDesc p3d_prior_count_desc(const PriorCountArgs& a);       // of a planned launch
+hipError_t p3d_prior_count_launch(const PriorCountArgs& a, hipStream_t s);
+hipError_t p3d_prior_float(const unsigned* count, float* out, long long n_pix, hipStream_t s);      // out_i = (float)count_i, RNE
+// Apply (POST_PRIOR): maps [n][n_pix] in place against prior [n_pix], b = (float)(1.0 - (double)a) formed by the caller:
+//   MUL  v' = fmul(v, fadd(fmul(b, g), a));      MIX  v' = fadd(fmul(b, v), fmul(a, g)).      No contraction.
+// Refused (hipErrorInvalidValue): a or b outside [0, 1], an unknown mode, n above 65535, nblk != p3d_post_blocks(n_pix).
+struct PriorApplyArgs {
+    float* maps = nullptr; const float* prior = nullptr;
+    int n = 0, n_pix = 0, mode = P3D_PRIOR_STAGE_OFF, nblk = 0;
+    float a = 0.f, b = 1.f;
+};
+LaunchDesc p3d_prior_apply_desc(const PriorApplyArgs& q);
+hipError_t p3d_prior_apply_launch(const PriorApplyArgs& q, hipStream_t s);
 
 // ---- misc ---------------------------------------------------------------------------------------
 hipError_t p3d_add_inplace(float* dst, int lddst, const float* src, int ldsrc, long M, int C, hipStream_t s);

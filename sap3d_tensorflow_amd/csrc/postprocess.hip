@@ -10,6 +10,7 @@
 //  one lane, one order, every operation rounded on its own -- the result does not depend on the tiling, the grid or alignment.
 //  * minmax_kernel: float32 min / max of every map, split over nblk blocks; det_reduce.h's write-through partials and
 //    last-arriver fold (min and max do not depend on the order; no floating-point atomics).
+//  * POST_PRIOR, after the blur: prior.hip's prior_apply_kernel, when asked for.
 //  * POST_MATCH, between the blur and the normalisation: hist_match.hip's launch sequence, when asked for.
 //  * apply_kernel: v / mx, or (v - mn) / (mx - mn), correctly rounded, stored back; bytes when asked, whole words where aligned.
 #include "p3d_kernels.h"
@@ -169,6 +170,13 @@ bool args_ok(const PostArgs& a) {
     return true;
 }
 
+PriorApplyArgs prior_args(const PostArgs& a) {
+    PriorApplyArgs q;
+    q.maps = a.maps; q.prior = a.prior; q.n = a.n; q.n_pix = a.H * a.W; q.mode = a.prior_mode; q.nblk = p3d_post_blocks((long long)a.H * a.W);
+    q.a = a.prior_a; q.b = a.prior_b;
+    return q;
+}
+
 }  // namespace
 
 // The widest strip whose rows + 2r staged rows fit the LDS cap, rows = max(2r, 64) where that fits (the halo is then read at most
@@ -186,6 +194,7 @@ bool p3d_post_has(int stage, const PostArgs& a) {
     switch (stage) {
         case POST_RESIZE: return a.src != nullptr;
         case POST_BLUR_H: case POST_BLUR_V: return a.r > 0;
+        case POST_PRIOR: return a.prior != nullptr;
         case POST_MATCH: return a.match != nullptr;
         case POST_MINMAX: return a.norm != P3D_NORM_NONE;
         case POST_APPLY: return a.norm != P3D_NORM_NONE || a.u8 != nullptr;
@@ -199,6 +208,7 @@ LaunchDesc p3d_post_desc(int stage, const PostArgs& a) {
         case POST_RESIZE: return {"resize_f32_kernel", e * 9.0, e * 8.0};
         case POST_BLUR_H: return {"blur_h_kernel", e * (1.5 * t + 0.5), e * 8.0};      // r + 1 products, 2r sums; one read, one write
         case POST_BLUR_V: return {"blur_v_kernel", e * (1.5 * t + 0.5), e * 8.0};
+        case POST_PRIOR: return p3d_prior_apply_desc(prior_args(a));
         case POST_MATCH: return {"hist_count_kernel+hist_remap_kernel", e * 14.0, e * 16.0};      // min / max, count, remap: hist_match.hip
         case POST_MINMAX: return {"minmax_kernel", e * 2.0, e * 4.0};
         default: return {"apply_kernel", e * 3.0, e * (a.norm != P3D_NORM_NONE ? 8.0 : 4.0) + (a.u8 ? e : 0.0)};
@@ -221,6 +231,8 @@ hipError_t p3d_post_launch(int stage, const PostArgs& a, hipStream_t s) {
                                (size_t)st.lds_bytes, s, a.tmp, a.maps, a.taps, a.r, a.H, a.W, st.cols, st.rows);
             break;
         }
+        case POST_PRIOR:
+            return p3d_prior_apply_launch(prior_args(a), s);
         case POST_MATCH: {
             HistChain c = *a.match;                        // the source: these maps, remapped in place
             c.source.maps = a.maps; c.source.out = a.maps; c.source.n = a.n; c.source.H = a.H; c.source.W = a.W;

@@ -202,12 +202,15 @@ def match_hist_maps(maps, targets, nbins=256, device=0):
     return out[0] if single else out
 
 
-def postprocess_maps(maps, size, sigma=0., radius=0, norm="none", scale=None, device=0, hist_match=None, nbins=256):
+def postprocess_maps(maps, size, sigma=0., radius=0, norm="none", scale=None, device=0, hist_match=None, nbins=256, prior=None,
+                     prior_mode="off", prior_weight=0.):
     """The output stage of P3DSession.set_postprocess on supplied maps (p3d_postprocess_maps): float32 [n, h, w], [h, w], or
     [n, h, w, c] of which channel 0 is taken -> resize_linear to size = (H, W), gaussian_blur, then each map divided by its
     maximum (norm="max") or brought to its range (norm="range").  -> float32 [n, H, W]; with `scale`, the uint8 images
     saturate_cast(float32(v * scale)) instead.  hist_match: a table (cdf, bin_centers) as P3DSession.set_hist_match takes it --
-    every map is matched to it (match_hist with `nbins`) after the blur and before the normalisation."""
+    every map is matched to it (match_hist with `nbins`) after the blur and before the normalisation.  prior (float32 [H, W]),
+    prior_mode ("mul" / "mix") and prior_weight: P3DSession.set_prior_stage's stage, after the blur and before the matching
+    (p3d_postprocess_maps_prior)."""
     m = np.ascontiguousarray(maps, dtype=np.float32)
     single = m.ndim == 2
     if single:
@@ -221,11 +224,95 @@ def postprocess_maps(maps, size, sigma=0., radius=0, norm="none", scale=None, de
     args = (device, m.ctypes.data_as(fp), m.shape[0], m.shape[1], m.shape[2], m.shape[3] if m.ndim == 4 else 1, int(H), int(W), C.byref(cfg))
     outs = (0.0 if scale is None else float(scale), out.ctypes.data_as(fp) if scale is None else None,
             out.ctypes.data_as(u8) if scale is not None else None)
-    if hist_match is None:
+    if prior is not None or prior_mode != "off":
+        md = _prior_mode(prior_mode, prior_weight)
+        g = None if prior is None else np.ascontiguousarray(prior, dtype=np.float32)
+        if g is not None and g.shape != (H, W):
+            raise ValueError("the prior is %s, the output %s" % (g.shape, (H, W)))
+        mc, keep = _match_cfg(hist_match if hist_match is not None else "off", nbins)
+        check(lib().p3d_postprocess_maps_prior(*(args + (C.byref(mc), g.ctypes.data_as(fp) if g is not None else None, md,
+                                                         float(prior_weight)) + outs)))
+    elif hist_match is None:
         check(lib().p3d_postprocess_maps(*(args + outs)))
     else:
         mc, keep = _match_cfg(hist_match, nbins)
         check(lib().p3d_postprocess_maps_match(*(args + (C.byref(mc),) + outs)))
+    return out[0] if single else out
+
+
+def _u8_maps3(maps):
+    m = np.asarray(maps)
+    if m.dtype != np.uint8:
+        raise ValueError("prior maps are uint8 images")
+    m = np.ascontiguousarray(m[None] if m.ndim == 2 else m)
+    if m.ndim != 3 or m.size == 0:
+        raise ValueError("expected [n, H, W] or [H, W] uint8 maps")
+    return m
+
+
+def _prior_kind(kind):
+    from . import _lib
+    if kind not in _lib.PRIOR_KINDS:
+        raise ValueError("prior kind %r: have %s" % (kind, sorted(_lib.PRIOR_KINDS)))
+    return _lib.PRIOR_KINDS[kind]
+
+
+def _prior_mode(mode, a):
+    from . import _lib
+    if mode not in _lib.PRIOR_MODES:
+        raise ValueError("prior mode %r: have %s" % (mode, sorted(_lib.PRIOR_MODES)))
+    if mode != "off" and not 0. <= float(a) <= 1.:
+        raise ValueError("the prior weight must be in [0, 1]")
+    return _lib.PRIOR_MODES[mode]
+
+
+def prior_count(maps, kind="fixations", sign=1, counts=None, offset=0, device=0):
+    """Test hook (p3d_debug_prior_count): uint8 maps [n, H, W] counted into `counts` (uint32 [H, W]; None: zeros) by
+    csrc/prior.hip's prior_count_kernel, the maps `offset` bytes past a 4-byte boundary -> (uint32 [H, W], underflow flag)."""
+    m = _u8_maps3(maps)
+    n, H, W = m.shape
+    cin = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
+    if cin is not None and cin.shape != (H, W):
+        raise ValueError("counts are uint32 %s" % ((H, W),))
+    out, flag = np.empty((H, W), np.uint32), C.c_int(0)
+    u32 = C.POINTER(C.c_uint32)
+    check(lib().p3d_debug_prior_count(device, _prior_kind(kind), m.ctypes.data_as(C.POINTER(C.c_ubyte)), n, H, W, int(sign),
+                                      cin.ctypes.data_as(u32) if cin is not None else None, int(offset), out.ctypes.data_as(u32),
+                                      C.byref(flag)))
+    return out, bool(flag.value)
+
+
+def prior_count_plan(n, H, W, offset=0):
+    """(four-pixel word lanes, one-pixel byte lanes, map slices) of the count launch on n maps of H x W bytes (host only)."""
+    w, s1, sl = C.c_int64(0), C.c_int64(0), C.c_int(0)
+    check(lib().p3d_debug_prior_count_plan(int(n), int(H), int(W), int(offset), C.byref(w), C.byref(s1), C.byref(sl)))
+    return w.value, s1.value, sl.value
+
+
+def fixation_prior(maps, kind="fixations", sigma=0., radius=0, device=0):
+    """A fixation prior from uint8 maps [n, H, W] on the GPU, without a session: the counts (csrc/prior.hip), float32, the Gaussian
+    of gaussian_blur, then / max -> float32 [H, W], 1 at the peak (P3DSession.finish_prior's law, include/p3d_hip.h)."""
+    counts, flag = prior_count(maps, kind, device=device)
+    if not counts.any():
+        raise ValueError("every count is zero")
+    return postprocess_maps(counts.astype(np.float32), counts.shape, sigma=sigma, radius=radius, norm="max", device=device)
+
+
+def apply_prior(maps, prior, mode="mul", a=0., offset=0, device=0):
+    """P3DSession.set_prior_stage's stage on supplied maps (p3d_debug_prior_apply): float32 [n, H, W] or [H, W] combined with
+    prior float32 [H, W] -- "mul": v * ((1 - a) g + a); "mix": (1 - a) v + a g, in float32 -> the same shape.  offset (test
+    hook): the maps start (offset & 3), the prior ((offset >> 2) & 3) floats past a 16-byte boundary on the device."""
+    m, single = _maps3(maps)
+    g = np.ascontiguousarray(prior, dtype=np.float32)
+    if g.shape != m.shape[1:]:
+        raise ValueError("the prior is %s, the maps %s" % (g.shape, m.shape[1:]))
+    md = _prior_mode(mode, a)
+    if mode == "off":
+        raise ValueError("apply_prior: mode 'mul' or 'mix'")
+    out = np.empty_like(m)
+    fp = C.POINTER(C.c_float)
+    check(lib().p3d_debug_prior_apply(device, md, float(a), m.ctypes.data_as(fp), m.shape[0], m.shape[1], m.shape[2], g.ctypes.data_as(fp),
+                                      int(offset), out.ctypes.data_as(fp)))
     return out[0] if single else out
 
 

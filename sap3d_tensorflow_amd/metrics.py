@@ -212,7 +212,7 @@ def eval_draws(fixation, jitter, n_rep, rng=None):
 
 
 def evaluate_maps(maps, density, fixation, size=None, jitter=True, n_rep=100, step_size=0.1, rng=None, device=0, postprocess=None,
-                  hist_match=None, nbins=256, extra=None, baseline=None):
+                  hist_match=None, nbins=256, extra=None, baseline=None, prior=None, prior_mode="off", prior_weight=0.):
     """Test hook (p3d_debug_eval_maps): P3DSession.evaluate's device pass on supplied maps instead of a session's prediction ->
     [n, 5] float64: CC, SIM, AUC_Judd, AUC_Borji, NSS.  maps: float32 [n, h, w], or [n, h, w, c] of which channel 0 is scored
     (the way the prediction buffer is addressed); density uint8 [n, Hd, Wd]; fixation uint8 [n, H, W] with (H, W) == size
@@ -222,7 +222,9 @@ def evaluate_maps(maps, density, fixation, size=None, jitter=True, n_rep=100, st
     `nbins` -- the histogram-matching stage runs after the blur and before the normalisation (p3d_debug_eval_maps_match).
     extra: "kldiv", "info_gain" or both in a collection, as P3DSession.set_eval_extra's launch (p3d_debug_eval_maps_extra), with
     `baseline` float32 [H, W] for the information gain; the result is then (the [n, 5] array, [n, 2] float64: KL, IG -- NaN for
-    the one that is off)."""
+    the one that is off).  prior (float32 [H, W]), prior_mode and prior_weight: P3DSession.set_prior_stage's stage after the
+    blur (p3d_debug_eval_maps_prior); baseline="prior" scores the information gain over that prior, copied on the device.  With
+    a prior the result is always the pair."""
     m = np.ascontiguousarray(maps, dtype=np.float32)
     dens = np.ascontiguousarray(density)
     fix = np.ascontiguousarray(fixation)
@@ -244,6 +246,27 @@ def evaluate_maps(maps, density, fixation, size=None, jitter=True, n_rep=100, st
             dens.shape[1], dens.shape[2], fix.ctypes.data_as(u8), int(H), int(W),
             _dp(jit) if jit is not None else None, idx.ctypes.data_as(ip), n_fix.ctypes.data_as(ip),
             int(n_rep), float(step_size), _dp(out))
+    if prior is not None:
+        from .dataflow import _match_cfg, _post_cfg, _prior_mode
+        flags = eval_extra_flags(extra) if extra is not None else 0
+        g = np.ascontiguousarray(prior, dtype=np.float32)
+        if g.shape != (H, W):
+            raise ValueError("the prior is %s, the fixation maps %s" % (g.shape, (H, W)))
+        base = None
+        if baseline is not None and not isinstance(baseline, str):
+            base = np.ascontiguousarray(baseline, dtype=np.float32)
+            if base.shape != (H, W):
+                raise ValueError("the baseline is %s, the fixation maps %s" % (base.shape, (H, W)))
+        elif baseline is not None and baseline != "prior":
+            raise ValueError("baseline %r: a [H, W] map or 'prior'" % (baseline,))
+        post = postprocess or {}
+        cfg = _post_cfg(post.get("sigma", 0.), post.get("radius", 0), post.get("norm", "none"))
+        mc, keep = _match_cfg(hist_match if hist_match is not None else "off", nbins)
+        xout = np.full((n, 2), np.nan, np.float64)
+        check(lib().p3d_debug_eval_maps_prior(*(args + (C.byref(cfg), C.byref(mc), flags, _fp(base) if base is not None else None,
+                                                        _dp(xout), _fp(g), _prior_mode(prior_mode, prior_weight),
+                                                        float(prior_weight)))))
+        return out, xout
     if extra is not None:
         from .dataflow import _match_cfg, _post_cfg
         flags = eval_extra_flags(extra)

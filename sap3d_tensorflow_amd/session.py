@@ -506,8 +506,14 @@ class P3DSession:
         """Score KL divergence (the reference's utils/metrics.py KLdiv) and / or information gain over `baseline` (the MIT
         benchmark's InfoGain; float32 [H, W] at the fixation maps' size, e.g. a centre prior or the mean training density) in
         every evaluate, at scoring resolution on the device: one more launch on the map the other metrics score
-        (include/p3d_hip.h holds the arithmetic).  evaluate returns what it returns; last_eval_extra() has the two numbers per
-        clip.  set_eval_extra(False) switches the option off, the default.  Training never sees it."""
+        (include/p3d_hip.h holds the arithmetic).  baseline="prior": the session's own prior (finish_prior / set_prior_map),
+        copied on the device; information gain is then on.  evaluate returns what it returns; last_eval_extra() has the two
+        numbers per clip.  set_eval_extra(False) switches the option off, the default.  Training never sees it."""
+        if isinstance(baseline, str):
+            if baseline != "prior":
+                raise ValueError("baseline %r: a [H, W] map or 'prior'" % (baseline,))
+            check(lib().p3d_set_eval_extra_prior(self._h, (_lib.EVAL_EXTRA["kldiv"] if kldiv else 0) | _lib.EVAL_EXTRA["info_gain"]))
+            return
         flags = (_lib.EVAL_EXTRA["kldiv"] if kldiv else 0) | (_lib.EVAL_EXTRA["info_gain"] if info_gain else 0)
         base, H, W = None, 0, 0
         if baseline is not None:
@@ -536,6 +542,103 @@ class P3DSession:
         out = np.empty((self.x_shape[0], 2), np.float64)
         check(lib().p3d_last_eval_extra(self._h, out.ctypes.data_as(_lib._dp), out.size))
         return out
+
+    # ---- fixation priors (p3d_prior_*, p3d_set_prior_stage) ---------------------------------------------
+    def open_prior(self, size, kind="fixations"):
+        """A zeroed accumulator of size = (H, W) counts on the device (an addition: the MIT benchmark's information-gain baseline,
+        the other images' fixation maps summed and smoothed).  kind "fixations": a map adds 1 where its byte is >= 128;
+        "bytes": it adds the byte, for 8-bit densities.  include/p3d_hip.h holds the arithmetic.  Training never sees it."""
+        if kind not in _lib.PRIOR_KINDS:
+            raise ValueError("prior kind %r: have %s" % (kind, sorted(_lib.PRIOR_KINDS)))
+        H, W = (size, size) if np.isscalar(size) else tuple(size)
+        check(lib().p3d_prior_open(self._h, int(H), int(W), _lib.PRIOR_KINDS[kind]))
+
+    def close_prior(self):
+        """Free the accumulator; a finished prior stays."""
+        check(lib().p3d_prior_close(self._h))
+
+    def prior_info(self):
+        """dict(size=(H, W), kind, n_maps) of the open accumulator."""
+        H, W, k, n = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int64(0)
+        check(lib().p3d_prior_info(self._h, C.byref(H), C.byref(W), C.byref(k), C.byref(n)))
+        return dict(size=(H.value, W.value), kind=[q for q, v in _lib.PRIOR_KINDS.items() if v == k.value][0], n_maps=n.value)
+
+    def prior_add(self, maps, sign=1):
+        """Count uint8 maps [n, H, W] or [H, W] into the accumulator; sign=-1 takes maps out again (a leave-one-out baseline)."""
+        m = np.asarray(maps)
+        if m.dtype != np.uint8:
+            raise ValueError("prior maps are uint8 images")
+        m = np.ascontiguousarray(m[None] if m.ndim == 2 else m)
+        if m.ndim != 3 or m.size == 0:
+            raise ValueError("expected [n, H, W] or [H, W] uint8 maps")
+        if m.shape[1:] != self.prior_info()["size"]:
+            raise ValueError("the maps are %s, the accumulator %s" % (m.shape[1:], self.prior_info()["size"]))
+        if sign not in (1, -1):
+            raise ValueError("sign is +1 or -1")
+        check(lib().p3d_prior_add(self._h, m.ctypes.data_as(_lib._u8p), m.shape[0], int(sign)))
+
+    def prior_counts(self):
+        """(uint32 [H, W] counts, the number of maps in them)."""
+        H, W = self.prior_info()["size"]
+        out, n = np.empty((H, W), np.uint32), C.c_int64(0)
+        check(lib().p3d_prior_counts(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(n)))
+        return out, n.value
+
+    def finish_prior(self, sigma=0., radius=0):
+        """Turn the counts into the session's prior: float32(count), set_postprocess's Gaussian (sigma, radius), then / max ->
+        float32 [H, W], 1 at the peak; it stays on the device for set_prior_stage and set_eval_extra(baseline="prior")."""
+        H, W = self.prior_info()["size"]
+        out = np.empty((H, W), np.float32)
+        check(lib().p3d_prior_finish(self._h, float(sigma), int(radius), fptr(out)))
+        return out
+
+    def prior_last_ms(self):
+        """(ms of the last prior_add's count launches, ms of the last finish_prior's launches), by HIP events."""
+        ms = (C.c_double * 2)()
+        check(lib().p3d_prior_last_ms(self._h, ms))
+        return ms[0], ms[1]
+
+    def set_prior_map(self, prior):
+        """Supply the prior from the host instead: float32 [H, W], finite and not constant.  None drops it."""
+        if prior is None:
+            check(lib().p3d_set_prior_map(self._h, None, 0, 0))
+            return
+        g = np.ascontiguousarray(prior, dtype=np.float32)
+        if g.ndim != 2:
+            raise ValueError("the prior is one [H, W] map")
+        check(lib().p3d_set_prior_map(self._h, fptr(g), g.shape[0], g.shape[1]))
+
+    @property
+    def prior_map(self):
+        """The session's prior, float32 [H, W], or None."""
+        H, W = C.c_int(0), C.c_int(0)
+        check(lib().p3d_get_prior_map(self._h, None, 0, C.byref(H), C.byref(W)))
+        if H.value == 0:
+            return None
+        out = np.empty((H.value, W.value), np.float32)
+        check(lib().p3d_get_prior_map(self._h, fptr(out), out.size, None, None))
+        return out
+
+    def set_prior_stage(self, mode="off", weight=0.):
+        """Combine every map that evaluate scores and pred_maps_u8 / video_maps_u8 write with the session's prior g, at output
+        resolution on the device, after set_postprocess's blur and before set_hist_match's stage.  mode "mul": v * ((1 - a) g + a)
+        -- a gain of a where nothing was ever fixated, 1 at the peak; "mix": (1 - a) v + a g; a = weight in [0, 1].  "off" (or
+        None) switches the stage off, the default.  Training never sees it."""
+        mode = "off" if mode is None else mode
+        if mode not in _lib.PRIOR_MODES:
+            raise ValueError("prior mode %r: have %s" % (mode, sorted(_lib.PRIOR_MODES)))
+        if mode != "off" and not 0. <= float(weight) <= 1.:
+            raise ValueError("the prior weight must be in [0, 1]")
+        check(lib().p3d_set_prior_stage(self._h, _lib.PRIOR_MODES[mode], float(weight)))
+
+    @property
+    def prior_stage(self):
+        """None while the stage is off, else dict(mode, weight)."""
+        m, a = C.c_int(0), C.c_float(0)
+        check(lib().p3d_get_prior_stage(self._h, C.byref(m), C.byref(a)))
+        if m.value == _lib.PRIOR_MODES["off"]:
+            return None
+        return dict(mode=[k for k, v in _lib.PRIOR_MODES.items() if v == m.value][0], weight=a.value)
 
     # ---- moving average of the weights (p3d_set_ema) ---------------------------------------------------
     def set_ema(self, decay, warmup=False):
