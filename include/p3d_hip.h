@@ -367,9 +367,31 @@ int p3d_get_activation(p3d_handle* h, const char* name, float* host, int64_t cou
 /* ---- schedule of one train step (TEST HOOK, tests/test_gpu_schedule.py): runs p3d_train_step_device once and writes every stream
  *      operation it issued, in host issue order, one per line: "L <stream> <kernel> [@op]" (launch), "M <stream> <what>" (async
  *      fill), "R <stream> e<k>" (event record), "W <stream> e<k>" (stream waits for event), "C <stream> allreduce <lo> <hi>".
+ *      Under p3d_set_grad_accum, "G <stream> store|add|finish <lo> <hi>" ahead of a launch of the accumulator is a note, not a
+ *      stream operation.  A side-stream job that the walk parked until it reached the encoder carries the tag of the op that
+ *      released it, not of the op whose backward queued it.
  *      Streams: main, side (filter gradients), comm (all-reduce).  `needed` receives the size of the text; call with a buffer
  *      at least that large (a first call with text = NULL runs the step, too).  Synchronises. */
 int p3d_debug_schedule(p3d_handle* h, float dropout_rate, uint64_t seed, char* text, int64_t cap, int64_t* needed);
+
+/* ---- schedule perturbation (TEST HOOK, tests/test_gpu_stream_hazards.py): the step is bit-reproducible, so a correct schedule gives
+ *      the same bits however its three streams drift against each other.
+ *      mode 0: off.  1: serial -- the issuing stream is synchronised after every launch / fill / all-reduce (host issue order).
+ *      2: slow -- a bounded delay kernel of delay_us goes onto `stream` (0 main, 1 side, 2 comm) ahead of every launch, fill and
+ *      all-reduce issued on it.  Stays until changed, for the calls the calling thread makes; only this handle's streams are
+ *      touched.  Refused (-1) when P3D_GRAPH is set, as p3d_debug_schedule is; ignored in dry and profiling passes.  delay_us in
+ *      [1, 2000].  The delay kernel is one block whose lane 0 polls the 100 MHz wall clock between sleeps and leaves when the time
+ *      is up or after a fixed number of polls (about 10x the delay); it reads and writes no memory and is not part of the
+ *      p3d_debug_schedule trace.
+ *      p3d_debug_perturb_count: the delay kernels and synchronisations inserted since the last call to p3d_debug_perturb.
+ *      p3d_debug_perturb_selftest shows that the hook can see a missing wait.  Two pooled streams A and B, two buffers of 4096
+ *      floats: buf = 1.0 (complete); on A a launch overwrites buf with 2.0 and an event is recorded; B waits for it only if
+ *      with_wait; on B a launch copies buf to out[4096]; both are synchronised.  All through the launch / event funnel of the
+ *      step, under `mode` (2: `slow` 0 holds back A, the producer's stream, 1 holds back B, the consumer's).  Every value read
+ *      is a valid float in allocated memory. */
+int p3d_debug_perturb(p3d_handle* h, int mode, int stream, int delay_us);
+int p3d_debug_perturb_count(p3d_handle* h, int64_t* delays, int64_t* syncs);
+int p3d_debug_perturb_selftest(int device, int mode, int slow, int delay_us, int with_wait, float* out);
 
 /* ---- decisions of the last forward (TEST HOOK, tests/test_gpu_pinned.py): the ReLU gates and max-pool choices the backward pass of
  *      this handle will use -- so that the oracle can differentiate the SAME piecewise-linear branch (a float32 forward takes

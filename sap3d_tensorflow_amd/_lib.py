@@ -136,6 +136,9 @@ SIGNATURES = {
     "p3d_debug_dirty_counters": (C.c_int64, []),
     "p3d_debug_force_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "p3d_debug_schedule": (C.c_int, [C.c_void_p, C.c_float, C.c_uint64, C.c_char_p, C.c_int64, _i64p]),
+    "p3d_debug_perturb": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "p3d_debug_perturb_count": (C.c_int, [C.c_void_p, _i64p, _i64p]),
+    "p3d_debug_perturb_selftest": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     "p3d_debug_decision_count": (C.c_int, [C.c_void_p]),
     "p3d_debug_decision_info": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), _i64p]),
     "p3d_debug_decision_get": (C.c_int, [C.c_void_p, C.c_int, _fp, _fp, C.c_int64]),

@@ -1392,6 +1392,20 @@ hipError_t p3d_copy_strided(float* dst, int lddst, const float* src, int ldsrc, 
     return hipGetLastError();
 }
 
+// p3d_debug_perturb's delay (test hook): holds its stream for delay_us and touches no memory.  Lane 0 polls the 100 MHz wall clock
+// between sleeps of 32 x 64 cycles (about a microsecond at the top clock) and leaves when the time is up or after 10 polls per
+// microsecond asked for, whichever comes first: about ten times the delay at the most, whatever the clocks do.
+__global__ __launch_bounds__(64) void delay_kernel(long long ticks, int max_polls) {
+    if (threadIdx.x != 0) return;
+    const long long t0 = wall_clock64();
+    for (int i = 0; i < max_polls && wall_clock64() - t0 < ticks; ++i) __builtin_amdgcn_s_sleep(32);
+}
+hipError_t p3d_delay(int delay_us, hipStream_t s) {
+    if (delay_us < 1 || delay_us > 2000) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(delay_kernel, dim3(1), dim3(64), 0, s, (long long)delay_us * 100, delay_us * 10);
+    return hipGetLastError();
+}
+
 hipError_t p3d_fill_uniform(float* p, long n, float lo, float hi, unsigned long long seed, hipStream_t s) {
     hipLaunchKernelGGL(fill_uniform_kernel, dim3(grid_for(n)), dim3(256), 0, s, p, (long long)n, lo, hi, seed);
     return hipGetLastError();

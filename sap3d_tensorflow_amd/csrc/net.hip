@@ -195,6 +195,36 @@ struct SchedTrace {
     }
 };
 thread_local SchedTrace* g_trace = nullptr;
+// ---- schedule perturbation (test hook p3d_debug_perturb, tests/test_gpu_stream_hazards.py): the step is bit-reproducible by design,
+//      so a correct schedule gives the same bits however its streams drift against each other.  serial: the issuing stream is
+//      synchronised after every launch, fill and all-reduce -- the host's issue order, one legal order.  slow: a bounded delay
+//      kernel (elementwise.hip, p3d_delay) goes onto ONE stream ahead of everything issued there, so the others run ahead as far
+//      as the events allow: a slow producer shows a consumer that lacks its wait, a slow consumer a buffer that is reused under
+//      it.  Only the three streams of the handle the hook was set on are touched; the delay kernels are not traced.  Set per
+//      calling thread, like g_trace; off (the default), launch() pays one thread-local null check.
+struct Perturb {
+    int mode = 0;                              // 0 off, 1 serial, 2 slow
+    hipStream_t streams[3] = {nullptr, nullptr, nullptr};      // main, side, comm
+    hipStream_t target = nullptr;              // slow: the stream that is held back
+    int delay_us = 0;
+    int64_t delays = 0, syncs = 0;             // inserted since the hook was last set
+    hipError_t before(hipStream_t s) {
+        if (mode != 2 || s != target) return hipSuccess;
+        ++delays;
+        return p3d_delay(delay_us, s);
+    }
+    hipError_t after(hipStream_t s) {
+        if (mode != 1 || (s != streams[0] && s != streams[1] && s != streams[2])) return hipSuccess;
+        ++syncs;
+        return hipStreamSynchronize(s);
+    }
+};
+thread_local Perturb* g_perturb = nullptr;
+struct PerturbPause {                          // profiling passes time single launches: the hook stays out of them
+    Perturb* const saved = g_perturb;
+    PerturbPause() { g_perturb = nullptr; }
+    ~PerturbPause() { g_perturb = saved; }
+};
 inline hipError_t ev_record(hipEvent_t e, hipStream_t s) {
     if (g_trace) g_trace->lines.push_back("R " + g_trace->sname(s) + " e" + std::to_string(g_trace->eid(e)));
     return hipEventRecord(e, s);
@@ -218,7 +248,11 @@ inline hipError_t copy_now(void* dst, const void* src, size_t bytes, hipMemcpyKi
 }
 inline hipError_t fill_async(void* p, int v, size_t bytes, hipStream_t s, const char* what) {
     if (g_trace) g_trace->lines.push_back("M " + g_trace->sname(s) + " " + what);
-    return hipMemsetAsync(p, v, bytes, s);
+    Perturb* const pt = g_perturb;
+    if (!pt) return hipMemsetAsync(p, v, bytes, s);
+    hipError_t e = pt->before(s);
+    if (e == hipSuccess) e = hipMemsetAsync(p, v, bytes, s);
+    return e != hipSuccess ? e : pt->after(s);
 }
 
 template <typename F>
@@ -226,7 +260,10 @@ void launch(const Ctx& c, const char* kernel, double flops, double bytes, F&& f)
     if (c.dry) return;
     if (g_trace) g_trace->lines.push_back("L " + g_trace->sname(c.s) + " " + kernel + (c.bwd_op ? std::string(" @") + c.bwd_op : std::string()));
     if (!c.prof) {
+        Perturb* const pt = g_perturb;
+        if (pt) HIPCHECK(pt->before(c.s));
         HIPCHECK(f());
+        if (pt) HIPCHECK(pt->after(c.s));
         return;
     }
     ProfRec r;
@@ -1211,6 +1248,7 @@ struct p3d_handle {
         return e;
     }
     std::vector<void*> allocs;
+    Perturb perturb;                          // p3d_debug_perturb: g_perturb points here while the hook is on
 
     std::deque<Param> params;                 // stable addresses
     std::map<std::string, Param*> pindex;

@@ -157,6 +157,7 @@ void p3d_destroy(p3d_handle* h) {
     if (!h) return;
     hipSetDevice(h->cfg.device);
     hipDeviceSynchronize();
+    if (g_perturb == &h->perturb) g_perturb = nullptr;
     delete h;
     --g_live_handles;
 }
@@ -553,6 +554,31 @@ int p3d_debug_schedule(p3d_handle* h, float dropout_rate, uint64_t seed, char* t
     API_END
 }
 
+int p3d_debug_perturb(p3d_handle* h, int mode, int stream, int delay_us) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    if (mode < 0 || mode > 2) throw P3dError("perturb: mode is 0 (off), 1 (serial) or 2 (slow)");
+    if (mode == 2 && (stream < 0 || stream > 2)) throw P3dError("perturb: stream is 0 (main), 1 (side) or 2 (comm)");
+    if (mode == 2 && (delay_us < 1 || delay_us > 2000)) throw P3dError("perturb: delay_us must be in [1, 2000]");
+    if (h->graphs_enabled()) throw P3dError("the perturbation follows the eager launch list (P3D_GRAPH is set)");
+    Perturb& p = h->perturb;
+    p = Perturb();
+    p.mode = mode;
+    p.streams[0] = h->stream; p.streams[1] = h->side_stream; p.streams[2] = h->comm_stream;
+    if (mode == 2) { p.target = p.streams[stream]; p.delay_us = delay_us; }
+    if (mode) g_perturb = &p;
+    else if (g_perturb == &p) g_perturb = nullptr;
+    API_END
+}
+
+int p3d_debug_perturb_count(p3d_handle* h, int64_t* delays, int64_t* syncs) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    if (delays) *delays = h->perturb.delays;
+    if (syncs) *syncs = h->perturb.syncs;
+    API_END
+}
+
 int p3d_train_step(p3d_handle* h, const float* x, const float* y, float dropout_rate, uint64_t seed, float* loss) {
     API_BEGIN
     if (!h || !x || !y) throw P3dError("null argument");
@@ -811,6 +837,7 @@ int p3d_profile_step(p3d_handle* h, float dropout_rate, uint64_t seed, p3d_op_ti
     try {
         h->refuse_swapped("p3d_profile_step");
         HIPCHECK(hipSetDevice(h->cfg.device));
+        PerturbPause unperturbed;
         Prof prof;
         Ctx c; c.training = true; c.drop = dropout_rate; c.seed = seed; c.update_moving = true; c.s = h->stream; c.prof = &prof;
         prof.phase = 0; h->run_forward(c);
@@ -1973,6 +2000,54 @@ void put_string(const std::string& v, char* out, int cap) {
     memcpy(out, v.c_str(), v.size() + 1);
 }
 }  // namespace
+
+int p3d_debug_perturb_selftest(int device, int mode, int slow, int delay_us, int with_wait, float* out) {
+    API_BEGIN
+    if (!out) throw P3dError("null argument");
+    if (mode < 0 || mode > 2) throw P3dError("perturb: mode is 0 (off), 1 (serial) or 2 (slow)");
+    if (mode == 2 && (slow < 0 || slow > 1)) throw P3dError("perturb self-test: slow is 0 (the producer's stream) or 1 (the consumer's)");
+    if (mode == 2 && (delay_us < 1 || delay_us > 2000)) throw P3dError("perturb: delay_us must be in [1, 2000]");
+    HIPCHECK(hipSetDevice(device));
+    const int n = 4096;
+    struct Streams {      // two pooled streams and the event between them, given back on every path
+        int device; hipStream_t a = nullptr, b = nullptr; hipEvent_t ev = nullptr;
+        explicit Streams(int d) : device(d) {
+            a = take_stream(d, 0); b = take_stream(d, 0);
+            HIPCHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        }
+        ~Streams() {
+            hipStreamSynchronize(a); hipStreamSynchronize(b);
+            if (ev) hipEventDestroy(ev);
+            give_stream(device, 0, a); give_stream(device, 0, b);
+        }
+    } st(device);
+    DevBuf buf(n), res(n);
+    // buf = 1.0, and every kernel used below has run once (a first launch may load its code, which would hold the host back by
+    // more than the delay under test): all complete before anything below is issued
+    HIPCHECK(p3d_fill_uniform(buf.p, n, 1.f, 1.f, 0, st.a));
+    HIPCHECK(p3d_delay(1, st.a));
+    HIPCHECK(hipStreamSynchronize(st.a));
+    HIPCHECK(p3d_copy_strided(res.p, 4, buf.p, 4, n / 4, 4, st.b));
+    HIPCHECK(hipStreamSynchronize(st.b));
+    HIPCHECK(fill_now(res.p, 0, (size_t)n * 4, st.b));
+    Perturb pt;
+    pt.mode = mode; pt.streams[0] = st.a; pt.streams[1] = st.b;
+    if (mode == 2) { pt.target = slow ? st.b : st.a; pt.delay_us = delay_us; }
+    Perturb* const before = g_perturb;
+    g_perturb = mode ? &pt : nullptr;
+    try {
+        Ctx ca, cb; ca.s = st.a; cb.s = st.b;
+        launch(ca, "fill_uniform_kernel", 0, 4.0 * n, [&]() { return p3d_fill_uniform(buf.p, n, 2.f, 2.f, 0, ca.s); });
+        HIPCHECK(ev_record(st.ev, st.a));
+        if (with_wait) HIPCHECK(ev_wait(st.b, st.ev));
+        launch(cb, "add_inplace_kernel", 0, 8.0 * n, [&]() { return p3d_copy_strided(res.p, 4, buf.p, 4, n / 4, 4, cb.s); });
+        HIPCHECK(hipStreamSynchronize(st.a));
+        HIPCHECK(hipStreamSynchronize(st.b));
+    } catch (...) { g_perturb = before; throw; }
+    g_perturb = before;
+    res.get(out, n);
+    API_END
+}
 
 int p3d_debug_conv_launch(int device, int kind, const float* in, int ld_in, int off_in, const int64_t xs[5], const float* w,
                           const int64_t ws[5], const int s[3], const float* bias, int accum, int f16, float* out, int ld_out, int off_out,

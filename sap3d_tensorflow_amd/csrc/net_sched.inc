@@ -283,7 +283,10 @@
             grad_accum_range(cc, GACC_FINISH, lo, hi);
         }
         if (g_trace) g_trace->lines.push_back("C " + g_trace->sname(comm_stream) + " allreduce " + std::to_string(lo) + " " + std::to_string(hi));
+        Perturb* const pt = g_perturb;
+        if (pt) HIPCHECK(pt->before(comm_stream));
         NCCLCHECK(ncclAllReduce(flat_g + lo, flat_g + lo, (size_t)(hi - lo), ncclFloat, ncclSum, comm, comm_stream));
+        if (pt) HIPCHECK(pt->after(comm_stream));
     }
     float cur_lr_t = 0.f;
     int64_t adam_split = 0;              // flat offset below which only the first op's variables live (0: no split)

@@ -913,6 +913,8 @@ hipError_t p3d_prior_apply_launch(const PriorApplyArgs& q, hipStream_t s);
 hipError_t p3d_add_inplace(float* dst, int lddst, const float* src, int ldsrc, long M, int C, hipStream_t s);
 hipError_t p3d_copy_strided(float* dst, int lddst, const float* src, int ldsrc, long M, int C, hipStream_t s);
 hipError_t p3d_fill_uniform(float* p, long n, float lo, float hi, unsigned long long seed, hipStream_t s);
+// one block that holds stream `s` for delay_us (1 .. 2000) microseconds, bounded, and touches no memory (p3d_debug_perturb)
+hipError_t p3d_delay(int delay_us, hipStream_t s);
 hipError_t p3d_fill_trunc_normal(float* p, long n, float stddev, unsigned long long seed, hipStream_t s);   // N(0, stddev) within 2 stddev
 hipError_t p3d_colsum(const float* dy, int ld, long M, int C, float* out, hipStream_t s);   // out += column sums
 // stem re-layout (elementwise.hip): 3-channel input -> 4-channel rows with the W padding written out; packed weights

@@ -439,6 +439,16 @@ def fused_reject(which, device=0):
     return err.value, bool(ok.value)
 
 
+def perturb_selftest(mode="off", slow="producer", delay_us=200, with_wait=True, device=0):
+    """Test hook (p3d_debug_perturb_selftest): a producer on one stream overwrites a buffer of 1.0 with 2.0, a consumer on another
+    copies it out, with or without the wait between them, under P3DSession.perturb's `mode` ("slow": `slow` names whose stream is
+    held back, "producer" | "consumer").  Returns the 4096 floats the consumer read."""
+    out = np.empty(4096, np.float32)
+    check(lib().p3d_debug_perturb_selftest(device, {"off": 0, "serial": 1, "slow": 2}[mode], {"producer": 0, "consumer": 1}[slow],
+                                           int(delay_us), 1 if with_wait else 0, fptr(out)))
+    return out
+
+
 def max_pool3d_launch(x, ksize, strides, ld=(None, None), offset=(0, 0), pad=np.nan, prior=np.nan, device=0):
     """Test hook: tf.nn.max_pool3d SAME with x and y as channel slices (p3d_debug_max_pool3d); ld / offset = (of x, of y).
     Returns (y, what its buffer holds outside the slice)."""

@@ -259,6 +259,26 @@ class P3DSession:
             raise P3dError("schedule text of %d bytes does not fit" % need.value)
         return buf.value.decode().splitlines()
 
+    PERTURB_MODES = {"off": 0, "serial": 1, "slow": 2}
+    PERTURB_STREAMS = {"main": 0, "side": 1, "comm": 2}
+
+    def perturb(self, mode="off", stream=None, delay_us=200):
+        """Perturb the schedule of every later call of this thread on this session (p3d_debug_perturb; tests): "serial"
+        synchronises the issuing stream after every launch, fill and all-reduce; "slow" puts a bounded delay kernel of delay_us
+        microseconds onto `stream` ("main" | "side" | "comm") ahead of everything issued there; "off" ends it.  Results must not
+        change by a bit (tests/test_gpu_stream_hazards.py)."""
+        if mode not in self.PERTURB_MODES:
+            raise ValueError("perturb mode %r: have %s" % (mode, sorted(self.PERTURB_MODES)))
+        if mode == "slow" and stream not in self.PERTURB_STREAMS:
+            raise ValueError("perturb stream %r: have %s" % (stream, sorted(self.PERTURB_STREAMS)))
+        check(lib().p3d_debug_perturb(self._h, self.PERTURB_MODES[mode], self.PERTURB_STREAMS.get(stream, 0), int(delay_us)))
+
+    def perturb_count(self):
+        """(delays, syncs) inserted since the last perturb()."""
+        d, s = C.c_int64(0), C.c_int64(0)
+        check(lib().p3d_debug_perturb_count(self._h, C.byref(d), C.byref(s)))
+        return d.value, s.value
+
     def decisions(self):
         """The ReLU gates and max-pool inputs of the last forward pass, as the backward pass of this session uses them
         (p3d_debug_decision_*; tests): {'relu': {BatchNorm scope: bool array [N,D,H,W,C]}, 'pool': [float32 arrays]} -- the `pins`
