@@ -23,7 +23,11 @@ Output (`--write`):
 (P3DSession.video_put_u8), windows are cut there (video_predict) and the maps are read once per video.  `--stride N` places a
 window every N frames, and a last one at F - 16 so that every frame is covered; `--overlap newest` gives a frame the map of the
 first window that holds it (at stride 1 the reference's rule: the npy files hold the default path's bytes), `--overlap mean` the
-mean of every window that predicted it.  A stride other than 1 and `--overlap mean` imply `--resident`."""
+mean of every window that predicted it.  A stride other than 1 and `--overlap mean` imply `--resident`.  `--temporal gauss|ema`
+(an addition, implies `--resident`) smooths the maps along the frame axis on the device as they are read
+(P3DSession.set_video_temporal): a Gaussian of `--temporal-sigma` frames (radius `--temporal-radius`, at most 24; 0: cv2's rule)
+with reflected ends, or the causal moving average m_f = A m_{f-1} + (1 - A) v_f of `--temporal-alpha`; npy files then hold the
+filtered maps, png / jpg the images of the filtered maps."""
 import argparse
 import glob
 import os
@@ -230,6 +234,14 @@ def parse_args(argv=None):
                    "1 is the reference's.  Other values imply --resident")
     p.add_argument("--overlap", choices=("newest", "mean"), default="newest", help="[addition] a frame's map: that of the first window "
                    "that holds it (at stride 1 the reference's rule), or the mean of every window that predicted it (implies --resident)")
+    p.add_argument("--temporal", choices=("off", "gauss", "ema"), default="off", help="[addition] smooth the maps along the frame axis on "
+                   "the device as they are read (P3DSession.set_video_temporal): a Gaussian over the whole video with reflected ends, or "
+                   "the causal moving average (implies --resident)")
+    p.add_argument("--temporal-sigma", type=float, default=0., metavar="S", help="[addition] --temporal gauss: the Gaussian's sigma in frames, > 0")
+    p.add_argument("--temporal-radius", type=int, default=0, metavar="R", help="[addition] --temporal gauss: the radius in frames, at most "
+                   "24 and at most F - 1; 0: cv2's rule, (int(rint(8 S + 1)) | 1) // 2")
+    p.add_argument("--temporal-alpha", type=float, default=0., metavar="A", help="[addition] --temporal ema: m_f = A m_{f-1} + (1 - A) v_f, "
+                   "A in [0, 1)")
     p.add_argument("--base", type=int, default=64, help=argparse.SUPPRESS)
     p.add_argument("--blocks", type=str, default="3,8,36", help=argparse.SUPPRESS)
     p.add_argument("--time", action="store_true", help="print per-video wall times (png / jpg: also the device stage and the host encode)")
@@ -240,6 +252,9 @@ def parse_args(argv=None):
         p.error("--stride must be at least 1")
     if args.stride != 1 or args.overlap != "newest":
         args.resident = True
+    temporal_args(args, p.error)
+    if args.temporal != "off":
+        args.resident = True
     if args.write == "npy" and (args.blur_sigma != 0. or args.blur_radius != 0 or args.normalize != "none"):
         p.error("--blur-sigma / --blur-radius / --normalize shape the images: they need --write png or jpg (npy stays the raw 112x112 maps)")
     if args.write == "npy" and args.match_hist:
@@ -249,6 +264,37 @@ def parse_args(argv=None):
     if not 2 <= args.match_bins <= 1024:
         p.error("--match-bins must be in 2..1024")
     return args
+
+
+TEMPORAL_MAX_RADIUS = 24
+
+
+def temporal_args(args, error):
+    """Checks --temporal and its values as P3DSession.set_video_temporal would refuse them, before anything runs; error(message)
+    does not return."""
+    import math
+    s, r, a = args.temporal_sigma, args.temporal_radius, args.temporal_alpha
+    if args.temporal == "off":
+        if s != 0. or r != 0 or a != 0.:
+            error("--temporal-sigma / --temporal-radius / --temporal-alpha need --temporal gauss or ema")
+    elif args.temporal == "gauss":
+        if a != 0.:
+            error("--temporal-alpha belongs to --temporal ema")
+        if not (math.isfinite(s) and s > 0.):
+            error("--temporal gauss needs --temporal-sigma S with S > 0")
+        if not 0 <= r <= TEMPORAL_MAX_RADIUS:
+            error("--temporal-radius must be in 0..%d" % TEMPORAL_MAX_RADIUS)
+        if r == 0:
+            k = round(8. * float(np.float32(s)) + 1.)               # (rint: round half to even, as Python's round)
+            if k > 2 * TEMPORAL_MAX_RADIUS + 1:
+                error("--temporal-sigma %g asks for a radius above %d; give --temporal-radius" % (s, TEMPORAL_MAX_RADIUS))
+            if (int(k) | 1) // 2 < 1:
+                error("--temporal-sigma %g asks for radius 0; give --temporal-radius" % s)
+    else:
+        if s != 0. or r != 0:
+            error("--temporal-sigma / --temporal-radius belong to --temporal gauss")
+        if not (math.isfinite(a) and 0. <= a < 1.):
+            error("--temporal-alpha must be in [0, 1)")
 
 
 def prior_stage_args(args):
@@ -330,11 +376,14 @@ def run_resident(sess, args, path):
     else:
         t = write_video_images_resident(sess, F, video_dir, args.write, size=tuple(args.size), writers=args.writers)
         print(name, "%d %s files in %s" % (t["files"], args.write, video_dir))
+    temporal_ms = sess.video_temporal_last_ms() if args.temporal != "off" and args.time else None
     sess.close_video()
     if args.time:
         print("  %s: wall %.1f ms | resident, stride %d, overlap %s: %d forward passes in %.1f ms (window cuts %.3f ms, map folds %.3f ms "
               "on the device)" % (os.path.basename(path), (time.perf_counter() - t0) * 1e3, args.stride, args.overlap, times["batches"],
                                   (t1 - t0) * 1e3, times["gather"], times["scatter"]))
+        if temporal_ms is not None:
+            print("  %s: temporal %s: %.3f ms on the device in the last read-out" % (name, args.temporal, temporal_ms))
         if args.write != "npy":
             print("  %s: maps %.1f ms (device resize/quantise %.2f ms, d2h %.2f ms) | encode %.1f ms thread time on %d writers"
                   % (name, t["gpu"], t["device"], t["d2h"], t["encode"], args.writers))
@@ -351,6 +400,7 @@ def main(argv=None):
         sess.restore(args.model, ema_as_weights=args.ema)
     sess.set_postprocess(args.blur_sigma, args.blur_radius, args.normalize)
     sess.set_hist_match(match_target(args), args.match_bins)
+    sess.set_video_temporal(args.temporal, args.temporal_sigma, args.temporal_radius, args.temporal_alpha)
     if stage:
         sess.set_prior_map(prior)
         sess.set_prior_stage(stage[1], stage[2])

@@ -1164,6 +1164,63 @@ int p3d_debug_video_mean(int device, const float* sum, const int32_t* count, int
 int p3d_debug_video_plan(int mode, int F, int T, int B, int last_start, const int32_t* count_in, const int* starts, int n_windows,
                          int32_t* count_out);
 
+/* ---- Temporal smoothing of the open video's maps at read-out (an ADDITION: overlapping 16-frame windows flicker from frame to
+ * frame, and every other output stage works on one map in space).  OFF by default; off, every entry point issues what it issued
+ * before and returns the same bits.  Nothing is allocated until the stage first runs (scratch from the stream pool); the train
+ * step, a captured step graph and its schedule never see it.  PARITY UNPINNED: the reference has no such stage, so this text is
+ * the contract and tests/temporal_ref.py replays it in numpy bit for bit.  The stage filters along the frame axis into scratch:
+ * the stores are never rewritten, so more windows can follow a filtered read.  One launch per read-out call.
+ *   INPUT   v_f, the input of frame f, per element: under P3D_VIDEO_NEWEST the stored map; under P3D_VIDEO_MEAN
+ *           __fdiv_rn(sum_f, (float)count_f), a count of 1 giving the sum's bits: what p3d_video_get_maps returns with the stage
+ *           off.  The division happens as the temporal kernel loads the frame; no finalised copy of the video is written.
+ *   GAUSS   P3D_TEMPORAL_GAUSS: radius and taps follow RADIUS and TAPS of the postprocess section (p3d_blur_taps(sigma, radius)),
+ *           with sigma > 0, the resulting r in 1 .. P3D_TEMPORAL_MAX_RADIUS, and r <= F - 1.  The output is that section's PASS
+ *           along the frame axis of the WHOLE video (n = F): float32, no fused multiply-add, reflect-101 at frames 0 and F - 1:
+ *           acc = fmul(w_r, v_f);  for d = 1 .. r:  acc = fadd(acc, fmul(w_{r+d}, fadd(v_{rho(f-d)}, v_{rho(f+d)}))).
+ *           fadd commutes, so the filter commutes bit for bit with reversing the video in time.  A read of frames
+ *           first .. first + n - 1 needs frames max(0, first - r) .. min(F - 1, first + n - 1 + r).
+ *   EMA     P3D_TEMPORAL_EMA (causal): alpha finite and in [0, 1);  b = fsub(1.0f, alpha);  m_0 = v_0, a copy of the bits;
+ *           m_f = fadd(fmul(alpha, m_{f-1}), fmul(b, v_f));  the output of frame f is m_f.  A read of first .. first + n - 1 needs
+ *           frames 0 .. first + n - 1 and recomputes from frame 0 in every call (no carry is kept): the bits of a partial read
+ *           are the slice of a full read.
+ * Maps that hold NaN or inf propagate them; their results are NOT pinned.
+ * Refused (-1, p3d_last_error set, nothing launched, nothing changed) at set time: an unknown kind; GAUSS with sigma not finite or
+ * not > 0, radius < 0 or > P3D_TEMPORAL_MAX_RADIUS (also the radius that follows from sigma), or a resulting r of 0; EMA with alpha
+ * not finite or outside [0, 1).  (sigma and radius are not read under EMA, alpha not under GAUSS.)  At read-out time: r > F - 1; a
+ * needed frame whose count is 0 -- the error names the first such frame.
+ *
+ * p3d_set_video_temporal  the handle's setting; NULL or kind P3D_TEMPORAL_OFF switch it off; needs no open video and outlives it.
+ * p3d_get_video_temporal  the setting (zeros while off) and whether it is on; either pointer may be NULL.
+ * While on:
+ *   p3d_video_get_maps  returns the filtered maps; counts are the frames' own counts, as before.
+ *   p3d_video_maps_u8   filters first, then its chain runs on the filtered maps, 16 at a time: the double-precision
+ *                       p3d_resize_linear_u8 law, or under p3d_set_postprocess / p3d_set_hist_match / p3d_set_prior_stage the
+ *                       float32 resize, BLUR, prior, match, NORM, BYTE.
+ * p3d_video_temporal_last_ms  HIP-event time of the temporal launch of the last read-out that ran the stage, milliseconds.
+ * p3d_temporal_filter  the stage alone on host maps [F][hw] (every count 1) -> out [n][hw], frames first .. first + n - 1.
+ * Test hooks.  p3d_debug_video_temporal: the launch from the launch description the read-outs use, on a host store [F][hw] and
+ * counts [F] under `mode`; every device buffer sits `offset` (0 .. 3) elements past a 16-byte boundary between guard elements;
+ * -1 if a guard, the store or the counts changed.  Its refusals are decided before the first HIP call.
+ * p3d_debug_video_temporal_plan (host only, no HIP call): for GAUSS of radius r on hw pixels and a read of n frames, the pixels and
+ * the consecutive output frames one block owns (block (x, y) takes pixels from x * pixels_per_block and frames from
+ * first + y * frames_per_block) and its LDS bytes, at most 65536; for EMA (r is not read) the pixels of one block with 16-byte
+ * aligned bases, n, and 0.
+ * p3d_debug_video_temporal_desc (host only): the launch description of a read-out of frames first .. first + n - 1 of F frames of
+ * hw pixels under `mode` -- the kernel's name (cap = room in kernel, in bytes), and the float operations and the bytes it claims:
+ * every input frame once per block run that loads it, every output frame once. */
+enum { P3D_TEMPORAL_OFF = 0, P3D_TEMPORAL_GAUSS = 1, P3D_TEMPORAL_EMA = 2 };
+#define P3D_TEMPORAL_MAX_RADIUS 24
+typedef struct p3d_video_temporal { int kind; float sigma; int radius; float alpha; } p3d_video_temporal;
+int p3d_set_video_temporal(p3d_handle* h, const p3d_video_temporal* cfg);
+int p3d_get_video_temporal(p3d_handle* h, p3d_video_temporal* cfg, int* on);
+int p3d_video_temporal_last_ms(p3d_handle* h, double* ms);
+int p3d_temporal_filter(int device, const p3d_video_temporal* cfg, const float* maps, int F, int64_t hw, int first, int n, float* out);
+int p3d_debug_video_temporal(int device, int mode, const p3d_video_temporal* cfg, const float* store, const int32_t* count, int F,
+                             int64_t hw, int first, int n, int offset, float* out);
+int p3d_debug_video_temporal_plan(int kind, int r, int64_t hw, int n, int* pixels_per_block, int* frames_per_block, int* lds_bytes);
+int p3d_debug_video_temporal_desc(int mode, const p3d_video_temporal* cfg, int F, int64_t hw, int first, int n, char* kernel, int cap,
+                                  double* flops, double* bytes);
+
 /* CRC-32C of a host buffer (host-side helper of the TensorFlow checkpoint reader / writer, sap3d_tensorflow_amd/tf_checkpoint.py:
  * the bundle format of train.py:180-185,266-267 checksums every tensor); crc = running value, 0 to start. */
 uint32_t p3d_crc32c(const void* data, size_t n, uint32_t crc);

@@ -44,6 +44,10 @@ class P3dPostprocess(C.Structure):
     _fields_ = [("sigma", C.c_float), ("radius", C.c_int), ("norm", C.c_int)]
 
 
+class P3dVideoTemporal(C.Structure):
+    _fields_ = [("kind", C.c_int), ("sigma", C.c_float), ("radius", C.c_int), ("alpha", C.c_float)]
+
+
 # p3d_set_postprocess normalisations (include/p3d_hip.h P3D_NORM_*)
 NORMS = {"none": 0, "max": 1, "range": 2}
 P3D_BLUR_MAX_RADIUS = 255
@@ -60,6 +64,9 @@ P3D_HIST_MAX_BINS = 1024
 EVAL_EXTRA = {"kldiv": 1, "info_gain": 2}
 # p3d_video_open modes (include/p3d_hip.h P3D_VIDEO_*)
 VIDEO_MODES = {"newest": 0, "mean": 1}
+# p3d_set_video_temporal kinds (include/p3d_hip.h P3D_TEMPORAL_*)
+TEMPORAL_KINDS = {"off": 0, "gauss": 1, "ema": 2}
+P3D_TEMPORAL_MAX_RADIUS = 24
 # P3D_PRIOR_* of include/p3d_hip.h: what a map adds to the accumulator, and how the stage combines a map with the prior
 PRIOR_KINDS = {"fixations": 0, "bytes": 1}
 PRIOR_MODES = {"off": 0, "mul": 1, "mix": 2}
@@ -321,6 +328,15 @@ SIGNATURES = {
     "p3d_debug_video_mean": (C.c_int, [C.c_int, _fp, C.POINTER(C.c_int32), C.c_int, C.c_int64, C.c_int, _fp]),
     "p3d_debug_video_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), _ip, C.c_int,
                                        C.POINTER(C.c_int32)]),
+    "p3d_set_video_temporal": (C.c_int, [C.c_void_p, C.POINTER(P3dVideoTemporal)]),
+    "p3d_get_video_temporal": (C.c_int, [C.c_void_p, C.POINTER(P3dVideoTemporal), _ip]),
+    "p3d_video_temporal_last_ms": (C.c_int, [C.c_void_p, _dp]),
+    "p3d_temporal_filter": (C.c_int, [C.c_int, C.POINTER(P3dVideoTemporal), _fp, C.c_int, C.c_int64, C.c_int, C.c_int, _fp]),
+    "p3d_debug_video_temporal": (C.c_int, [C.c_int, C.c_int, C.POINTER(P3dVideoTemporal), _fp, C.POINTER(C.c_int32), C.c_int, C.c_int64,
+                                           C.c_int, C.c_int, C.c_int, _fp]),
+    "p3d_debug_video_temporal_plan": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int, _ip, _ip, _ip]),
+    "p3d_debug_video_temporal_desc": (C.c_int, [C.c_int, C.POINTER(P3dVideoTemporal), C.c_int, C.c_int64, C.c_int, C.c_int, C.c_char_p, C.c_int,
+                                                _dp, _dp]),
     "p3d_crc32c": (C.c_uint32, [C.c_void_p, C.c_size_t, C.c_uint32]),
     "p3d_shutdown": (C.c_int, []),
 }

@@ -3917,8 +3917,10 @@ int p3d_video_get_maps(p3d_handle* h, int first, int n, float* maps, int32_t* co
     const size_t ne = (size_t)n * (size_t)h->vid_hw();
     float* slab = nullptr;
     unsigned* counters = nullptr;
-    if (h->vid_mode == VIDEO_MEAN) HIPCHECK(p3d_stream_scratch(s, ne, 0, &slab, &counters));
-    const float* src = h->video_finalize("video_get_maps", first, n, slab, s);
+    const bool temporal = h->temporal_cfg.on();      // p3d_set_video_temporal: the filtered maps, into scratch under either mode
+    if (temporal) h->video_temporal_check("video_get_maps", first, n);      // (before the scratch is asked for: a refusal changes nothing)
+    if (temporal || h->vid_mode == VIDEO_MEAN) HIPCHECK(p3d_stream_scratch(s, ne, 0, &slab, &counters));
+    const float* src = temporal ? h->video_temporal("video_get_maps", first, n, slab, s) : h->video_finalize("video_get_maps", first, n, slab, s);
     HIPCHECK(copy_now(maps, src, ne * 4, hipMemcpyDeviceToHost, s));
     if (counts) memcpy(counts, h->vid_count.data() + first, (size_t)n * sizeof(int32_t));
     API_END
@@ -3932,13 +3934,16 @@ int p3d_video_maps_u8(p3d_handle* h, int first, int n, float scale, int H, int W
     HIPCHECK(hipSetDevice(h->cfg.device));
     h->video_need_open("video_maps_u8");
     h->video_range("video_maps_u8", first, n);
-    for (int f = first; f < first + n; ++f)      // (before the scratch is asked for: a refusal changes nothing)
+    const bool temporal = h->temporal_cfg.on();      // p3d_set_video_temporal: the chain runs on the filtered maps
+    if (temporal) h->video_temporal_check("video_maps_u8", first, n);      // (before the scratch is asked for: a refusal changes nothing)
+    for (int f = first; f < first + n; ++f)
         if (h->vid_count[(size_t)f] == 0) throw P3dError("video_maps_u8: frame " + std::to_string(f) + " has no prediction yet (count 0)");
     if (stage_ms) stage_ms[0] = stage_ms[1] = 0.0;
     const long long phw = h->vid_hw();
-    maps_u8_chain(h, n, h->pred->H, h->pred->W, scale, H, W, out, stage_ms, h->vid_mode == VIDEO_MEAN ? (size_t)n * (size_t)phw : 0,
+    maps_u8_chain(h, n, h->pred->H, h->pred->W, scale, H, W, out, stage_ms, temporal || h->vid_mode == VIDEO_MEAN ? (size_t)n * (size_t)phw : 0,
                   [&](hipStream_t s, float* scratch, std::vector<PostRun>& runs) {
-                      runs.push_back({h->video_finalize("video_maps_u8", first, n, scratch, s), phw, 1, n});
+                      runs.push_back({temporal ? h->video_temporal("video_maps_u8", first, n, scratch, s)
+                                               : h->video_finalize("video_maps_u8", first, n, scratch, s), phw, 1, n});
                   });
     API_END
 }
@@ -4059,6 +4064,112 @@ int p3d_debug_video_plan(int mode, int F, int T, int B, int last_start, const in
     if (!count_out) throw P3dError("null argument");
     const p3d_handle::VideoPlan p = p3d_handle::video_plan(mode, F, T, B, last_start, count_in, nullptr, starts, n_windows);
     memcpy(count_out, p.count.data(), (size_t)F * sizeof(int32_t));
+    API_END
+}
+
+// ---- temporal smoothing of the video's maps at read-out (include/p3d_hip.h; the handle's part in net_sched.inc, temporal.hip) --
+int p3d_set_video_temporal(p3d_handle* h, const p3d_video_temporal* cfg) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    h->set_video_temporal(cfg);
+    API_END
+}
+
+int p3d_get_video_temporal(p3d_handle* h, p3d_video_temporal* cfg, int* on) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    if (cfg) *cfg = h->temporal_cfg.set;
+    if (on) *on = h->temporal_cfg.on() ? 1 : 0;
+    API_END
+}
+
+int p3d_video_temporal_last_ms(p3d_handle* h, double* ms) {
+    API_BEGIN
+    if (!h || !ms) throw P3dError("null argument");
+    if (!h->temporal_timed) throw P3dError("video_temporal_last_ms: no read-out has run the temporal stage");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    float t = 0.f;
+    HIPCHECK(hipEventElapsedTime(&t, h->ev_temporal[0], h->ev_temporal[1]));
+    *ms = (double)t;
+    API_END
+}
+
+}  // extern "C"
+namespace {
+// One temporal launch from its launch description on host arrays: store [F][hw], count [F] (null: every count 1) under `mode`,
+// frames first .. first + n - 1 -> out [n][hw].  Every refusal is decided before the first HIP call.
+void temporal_on_host(int device, int mode, const p3d_video_temporal* cfg, const float* store, const int32_t* count, int F, int64_t hw,
+                      int first, int n, int offset, float* out) {
+    if (!store || !out) throw P3dError("null argument");
+    if (mode != VIDEO_NEWEST && mode != VIDEO_MEAN) throw P3dError("video_temporal: mode " + std::to_string(mode) + " is neither P3D_VIDEO_NEWEST (0) nor P3D_VIDEO_MEAN (1)");
+    const p3d_handle::TemporalCfg t = p3d_handle::temporal_parse(cfg);
+    if (!t.on()) throw P3dError("video_temporal: the hook needs a kind (GAUSS or EMA)");
+    if (F < 1 || hw < 1 || (int64_t)F * hw > (int64_t)1 << 31) throw P3dError("video_temporal: bad shape");
+    std::vector<int32_t> ones;
+    if (!count) { ones.assign((size_t)F, 1); count = ones.data(); }
+    p3d_handle::temporal_check("video_temporal", t, F, first, n, count);
+    video_hook_device(device, offset);
+    const int64_t ns = (int64_t)F * hw, no = (int64_t)n * hw;
+    GuardedBuf sb(ns, offset, store), cb(F, 0, count), ob(no, offset, nullptr);
+    const VideoTemporalArgs a = p3d_handle::temporal_args(t, sb.p(), mode == VIDEO_MEAN ? reinterpret_cast<const int32_t*>(cb.p()) : nullptr,
+                                                          ob.p(), F, hw, first, n);
+    const std::string want = std::string(t.set.kind == P3D_TEMPORAL_GAUSS ? "video_temporal_gauss_kernel<" : "video_temporal_ema_kernel<") +
+                             (mode == VIDEO_MEAN ? "1>" : "0>");
+    if (std::string(p3d_video_temporal_desc(a).kernel) != want) throw P3dError("video_temporal: launch description names another kernel");
+    HIPCHECK(p3d_video_temporal_launch(a, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    if (sb.back() != sb.host) throw P3dError("video_temporal: the launch changed the store");
+    if (cb.back() != cb.host) throw P3dError("video_temporal: the launch changed the counts");
+    const std::vector<uint32_t> oo = ob.back();
+    if (!GuardedBuf::guards_kept(oo, ob.at, no)) throw P3dError("video_temporal: the launch wrote outside its range");
+    memcpy(out, oo.data() + ob.at, (size_t)no * 4);
+}
+}  // namespace
+extern "C" {
+
+int p3d_temporal_filter(int device, const p3d_video_temporal* cfg, const float* maps, int F, int64_t hw, int first, int n, float* out) {
+    API_BEGIN
+    temporal_on_host(device, VIDEO_NEWEST, cfg, maps, nullptr, F, hw, first, n, 0, out);
+    API_END
+}
+
+int p3d_debug_video_temporal(int device, int mode, const p3d_video_temporal* cfg, const float* store, const int32_t* count, int F,
+                             int64_t hw, int first, int n, int offset, float* out) {
+    API_BEGIN
+    if (!count) throw P3dError("null argument");
+    if (offset < 0 || offset > 3) throw P3dError("video hook: offset is 0 .. 3");
+    temporal_on_host(device, mode, cfg, store, count, F, hw, first, n, offset, out);
+    API_END
+}
+
+int p3d_debug_video_temporal_desc(int mode, const p3d_video_temporal* cfg, int F, int64_t hw, int first, int n, char* kernel, int cap,
+                                  double* flops, double* bytes) {
+    API_BEGIN
+    if (!kernel || cap < 1 || !flops || !bytes) throw P3dError("null argument");
+    if (mode != VIDEO_NEWEST && mode != VIDEO_MEAN) throw P3dError("video_temporal: mode " + std::to_string(mode) + " is neither P3D_VIDEO_NEWEST (0) nor P3D_VIDEO_MEAN (1)");
+    const p3d_handle::TemporalCfg t = p3d_handle::temporal_parse(cfg);
+    if (!t.on()) throw P3dError("video_temporal: the hook needs a kind (GAUSS or EMA)");
+    if (F < 1 || hw < 1) throw P3dError("video_temporal: bad shape");
+    const std::vector<int32_t> ones((size_t)F, 1);
+    p3d_handle::temporal_check("video_temporal", t, F, first, n, ones.data());
+    // (the description reads no memory: the pointers only say which is there)
+    const float* some = reinterpret_cast<const float*>(kernel);
+    const VideoTemporalArgs a = p3d_handle::temporal_args(t, some, mode == VIDEO_MEAN ? ones.data() : nullptr, nullptr, F, hw, first, n);
+    const LaunchDesc d = p3d_video_temporal_desc(a);
+    snprintf(kernel, (size_t)cap, "%s", d.kernel);
+    *flops = d.flops; *bytes = d.bytes;
+    API_END
+}
+
+int p3d_debug_video_temporal_plan(int kind, int r, int64_t hw, int n, int* pixels_per_block, int* frames_per_block, int* lds_bytes) {
+    API_BEGIN
+    if (!pixels_per_block || !frames_per_block || !lds_bytes) throw P3dError("null argument");
+    if (kind != P3D_TEMPORAL_GAUSS && kind != P3D_TEMPORAL_EMA) throw P3dError("video_temporal_plan: the kind is GAUSS (1) or EMA (2)");
+    if (kind == P3D_TEMPORAL_GAUSS && (r < 1 || r > P3D_TEMPORAL_MAX_RADIUS))
+        throw P3dError("video_temporal_plan: radius must be in [1, " + std::to_string(P3D_TEMPORAL_MAX_RADIUS) + "]");
+    if (hw < 1 || n < 1) throw P3dError("video_temporal_plan: at least one pixel and one frame");
+    const VideoTemporalPlan p = p3d_video_temporal_plan(kind, r, hw, n);
+    *pixels_per_block = p.pixels_per_block; *frames_per_block = p.frames_per_block; *lds_bytes = p.lds_bytes;
     API_END
 }
 

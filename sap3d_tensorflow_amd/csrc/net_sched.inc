@@ -998,6 +998,88 @@
         return scratch;
     }
 
+    // ---- temporal smoothing of the video's maps at read-out (p3d_set_video_temporal; temporal.hip) -------
+    // Off by default, and off nothing here runs.  The setting is a kind with its radius and taps, or its alpha; the stage is one
+    // launch issued by the two read-outs in place of video_finalize, into scratch from the stream pool.  The events exist from the
+    // first run on.  No step, launch list or captured graph ever names it.
+    struct TemporalCfg {
+        p3d_video_temporal set{P3D_TEMPORAL_OFF, 0.f, 0, 0.f};      // as given
+        int r = 0; std::vector<float> w;                            // GAUSS: the effective radius and w_r .. w_2r
+        bool on() const { return set.kind != P3D_TEMPORAL_OFF; }
+    };
+    TemporalCfg temporal_cfg;
+    hipEvent_t ev_temporal[2] = {nullptr, nullptr};
+    bool temporal_timed = false;
+    // what a setting asks for (include/p3d_hip.h); throws on a setting the header refuses.  Host only.
+    static TemporalCfg temporal_parse(const p3d_video_temporal* c) {
+        TemporalCfg t;
+        if (!c || c->kind == P3D_TEMPORAL_OFF) return t;
+        if (c->kind == P3D_TEMPORAL_GAUSS) {
+            if (!std::isfinite(c->sigma) || !(c->sigma > 0.f)) throw P3dError("video_temporal: GAUSS needs a finite sigma > 0");
+            if (c->radius < 0 || c->radius > P3D_TEMPORAL_MAX_RADIUS)
+                throw P3dError("video_temporal: radius must be in [0, " + std::to_string(P3D_TEMPORAL_MAX_RADIUS) + "]");
+            int r = c->radius;
+            if (r == 0) {      // RADIUS of the postprocess section
+                const double k = std::rint(8.0 * (double)c->sigma + 1.0);
+                if (k > 2.0 * P3D_TEMPORAL_MAX_RADIUS + 1.0)
+                    throw P3dError("video_temporal: sigma asks for a radius above " + std::to_string(P3D_TEMPORAL_MAX_RADIUS) + "; give a radius");
+                r = ((int)k | 1) / 2;
+            }
+            if (r < 1) throw P3dError("video_temporal: sigma asks for radius 0; give a radius");
+            const std::vector<float> taps = post_taps(c->sigma, r);
+            t.r = r;
+            t.w.assign(taps.begin() + r, taps.end());
+            t.set = p3d_video_temporal{P3D_TEMPORAL_GAUSS, c->sigma, c->radius, 0.f};
+        } else if (c->kind == P3D_TEMPORAL_EMA) {
+            if (!std::isfinite(c->alpha) || !(c->alpha >= 0.f && c->alpha < 1.f)) throw P3dError("video_temporal: EMA needs alpha in [0, 1)");
+            t.set = p3d_video_temporal{P3D_TEMPORAL_EMA, 0.f, 0, c->alpha};
+        } else {
+            throw P3dError("video_temporal: kind " + std::to_string(c->kind) + " is none of P3D_TEMPORAL_OFF (0), GAUSS (1), EMA (2)");
+        }
+        return t;
+    }
+    // the read-out's refusals for frames first .. first + n - 1 of F (count [F], host): r > F - 1, a needed frame of count 0
+    static void temporal_check(const char* who, const TemporalCfg& t, int F, int first, int n, const int32_t* count) {
+        if (n < 1 || first < 0 || first > F - n)
+            throw P3dError(std::string(who) + ": frames " + std::to_string(first) + " .. " + std::to_string((int64_t)first + n - 1) +
+                           " are outside [0, " + std::to_string(F) + ")");
+        int lo = 0, hi = first + n - 1;
+        if (t.set.kind == P3D_TEMPORAL_GAUSS) {
+            if (t.r > F - 1)
+                throw P3dError(std::string(who) + ": the temporal radius " + std::to_string(t.r) + " exceeds F - 1 = " + std::to_string(F - 1));
+            lo = std::max(0, first - t.r);
+            hi = std::min(F - 1, first + n - 1 + t.r);
+        }
+        for (int f = lo; f <= hi; ++f)
+            if (count[f] < 1)
+                throw P3dError(std::string(who) + ": the temporal filter needs frame " + std::to_string(f) + ", which has no prediction yet (count 0)");
+    }
+    static VideoTemporalArgs temporal_args(const TemporalCfg& t, const float* store, const int32_t* count_dev, float* out, int F, int64_t hw,
+                                           int first, int n) {
+        VideoTemporalArgs a;
+        a.kind = t.set.kind; a.store = store; a.count = count_dev; a.out = out; a.F = F; a.hw = hw; a.first = first; a.n = n;
+        a.r = t.r; a.alpha = t.set.alpha;
+        for (size_t d = 0; d < t.w.size() && d <= (size_t)TEMPORAL_MAX_RADIUS; ++d) a.w[d] = t.w[d];
+        return a;
+    }
+    void set_video_temporal(const p3d_video_temporal* c) { temporal_cfg = temporal_parse(c); }      // (refuses before anything changes)
+    void video_temporal_check(const char* who, int first, int n) const {
+        video_need_open(who);
+        temporal_check(who, temporal_cfg, vid_F, first, n, vid_count.data());
+    }
+    // the filtered frames first .. first + n - 1 in `scratch` [n][hw]: one launch between the stage's events
+    const float* video_temporal(const char* who, int first, int n, float* scratch, hipStream_t s) {
+        video_temporal_check(who, first, n);
+        if (!ev_temporal[0]) for (auto& e : ev_temporal) HIPCHECK(hipEventCreate(&e));
+        const VideoTemporalArgs a = temporal_args(temporal_cfg, vid_maps, vid_mode == VIDEO_MEAN ? vid_count_dev : nullptr, scratch, vid_F,
+                                                  vid_hw(), first, n);
+        HIPCHECK(hipEventRecord(ev_temporal[0], s));
+        HIPCHECK(p3d_video_temporal_launch(a, s));
+        HIPCHECK(hipEventRecord(ev_temporal[1], s));
+        temporal_timed = true;
+        return scratch;
+    }
+
     // ---- gradient clipping by the global norm (p3d_set_grad_clip) ----------------------------------
     // clip_norm > 0: the step's sum of squares over every trainable element's g' (g + c w under a regularisation term), its
     // norm and scale = clip_norm / max(norm, clip_norm) land in d_clip_res before any optimiser launch, and every optimiser
@@ -1318,6 +1400,7 @@
         if (ev_aug0) hipEventDestroy(ev_aug0);
         if (ev_aug1) hipEventDestroy(ev_aug1);
         for (hipEvent_t e : ev_vid) if (e) hipEventDestroy(e);
+        for (hipEvent_t e : ev_temporal) if (e) hipEventDestroy(e);
         video_free();
         eval_extra_free();
         prior_close();

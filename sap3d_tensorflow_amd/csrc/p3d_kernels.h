@@ -717,6 +717,29 @@ LaunchDesc p3d_video_scatter_desc(const VideoScatterArgs& a);
 hipError_t p3d_video_scatter(const VideoScatterArgs& a, hipStream_t s);
 LaunchDesc p3d_video_mean_desc(const VideoMeanArgs& a);
 hipError_t p3d_video_mean(const VideoMeanArgs& a, hipStream_t s);
+// ---- temporal smoothing of the maps at read-out (temporal.hip; p3d_set_video_temporal, the contract in include/p3d_hip.h) -------
+// One launch: frames first .. first + n - 1 of store [F][hw], filtered along the frame axis of the whole video, -> out [n][hw]
+// (not the store, which is only read).  count null: a frame's input is the stored map; else [F] in device memory and the input is
+// __fdiv_rn(sum, (float)count), divided as the frame is loaded (a count of 1 keeps the bits).  The caller has checked that every
+// frame the read needs has a count >= 1.
+//   TEMPORAL_GAUSS  w[d] = the tap w_{r+d} of p3d_blur_taps, d = 0 .. r; the PASS law with reflect-101 at frames 0 and F - 1.
+//   TEMPORAL_EMA    m_0 = v_0, m_f = fadd(fmul(alpha, m_{f-1}), fmul(fsub(1, alpha), v_f)), recomputed from frame 0.
+// Refused (hipErrorInvalidValue, nothing launched): a range outside [0, F), r outside 1 .. min(TEMPORAL_MAX_RADIUS, F - 1), alpha
+// outside [0, 1), store == out.  The plan is a function of its four arguments alone, so a test can aim at the seams: a GAUSS block
+// owns pixels_per_block pixels and frames_per_block consecutive output frames, and holds lds_bytes of LDS (at most 64 KB).
+enum { TEMPORAL_OFF = 0, TEMPORAL_GAUSS = 1, TEMPORAL_EMA = 2 };
+constexpr int TEMPORAL_MAX_RADIUS = 24;
+struct VideoTemporalArgs {
+    int kind = TEMPORAL_OFF;
+    const float* store = nullptr; const int32_t* count = nullptr; float* out = nullptr;
+    int F = 0; long long hw = 0; int first = 0, n = 0;
+    int r = 0; float w[TEMPORAL_MAX_RADIUS + 1] = {};
+    float alpha = 0.f;
+};
+struct VideoTemporalPlan { int threads = 0, pixels_per_block = 0, frames_per_block = 0, lds_bytes = 0; };
+VideoTemporalPlan p3d_video_temporal_plan(int kind, int r, long long hw, int n);
+LaunchDesc p3d_video_temporal_desc(const VideoTemporalArgs& a);
+hipError_t p3d_video_temporal_launch(const VideoTemporalArgs& a, hipStream_t s);
 
 // ---- saliency metrics + frame pre-processing (metrics.hip; utils/metrics.py:25-287, dataflow.py:187-216) ------
 hipError_t p3d_metric_cc(const float* a, const float* b, int n_maps, int n_pix, double* out, hipStream_t s);

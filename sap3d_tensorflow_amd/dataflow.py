@@ -114,6 +114,56 @@ def gaussian_blur(maps, sigma, radius=0, device=0):
     return out[0] if single else out
 
 
+def _temporal_cfg(kind, sigma, radius, alpha):
+    from . import _lib
+    if kind not in _lib.TEMPORAL_KINDS:
+        raise ValueError("temporal kind %r: have %s" % (kind, sorted(_lib.TEMPORAL_KINDS)))
+    return _lib.P3dVideoTemporal(_lib.TEMPORAL_KINDS[kind], float(sigma), int(radius), float(alpha))
+
+
+def temporal_filter(maps, kind, sigma=0., radius=0, alpha=0., first=0, n=None, device=0):
+    """The temporal stage of P3DSession.set_video_temporal on supplied maps (p3d_temporal_filter): maps [F, ...] float32, one per
+    frame, trailing axes flattened to pixels and every count 1.  kind "gauss": the Gaussian of blur_taps(sigma, radius) along
+    the frame axis with reflect-101 at the first and last frame, r in 1 .. 24 and r <= F - 1; "ema": m_f = alpha m_{f-1} +
+    (1 - alpha) v_f from m_0 = v_0.  Returns frames first .. first + n - 1 (all by default), [n, ...]."""
+    m = np.ascontiguousarray(maps, dtype=np.float32)
+    if m.ndim < 1 or m.size == 0:
+        raise ValueError("expected [F, ...] float32 maps")
+    F = m.shape[0]
+    n = F - int(first) if n is None else int(n)
+    cfg = _temporal_cfg(kind, sigma, radius, alpha)
+    out = np.empty((max(n, 0),) + m.shape[1:], np.float32)
+    fp = C.POINTER(C.c_float)
+    check(lib().p3d_temporal_filter(device, C.byref(cfg), m.ctypes.data_as(fp), F, m.size // F, int(first), n, out.ctypes.data_as(fp)))
+    return out
+
+
+def temporal_plan(kind, radius, hw, n):
+    """(pixels, consecutive output frames, LDS bytes) of one block of the temporal launch for a read of n frames of hw pixels
+    (p3d_debug_video_temporal_plan, host only); kind "gauss" with its effective radius, or "ema"."""
+    from . import _lib
+    if kind not in ("gauss", "ema"):
+        raise ValueError("temporal kind %r: have ['ema', 'gauss']" % (kind,))
+    p, f, b = C.c_int(0), C.c_int(0), C.c_int(0)
+    check(lib().p3d_debug_video_temporal_plan(_lib.TEMPORAL_KINDS[kind], int(radius), int(hw), int(n), C.byref(p), C.byref(f), C.byref(b)))
+    return p.value, f.value, b.value
+
+
+def temporal_desc(kind, F, hw, first=0, n=None, sigma=0., radius=0, alpha=0., mode="newest"):
+    """dict(kernel, flops, bytes): what the temporal launch of a read-out of frames first .. first + n - 1 of F frames of hw pixels
+    claims (p3d_debug_video_temporal_desc, host only)."""
+    from . import _lib
+    if mode not in _lib.VIDEO_MODES:
+        raise ValueError("video mode %r: have %s" % (mode, sorted(_lib.VIDEO_MODES)))
+    cfg = _temporal_cfg(kind, sigma, radius, alpha)
+    n = int(F) - int(first) if n is None else int(n)
+    name = C.create_string_buffer(64)
+    flops, nbytes = C.c_double(0.), C.c_double(0.)
+    check(lib().p3d_debug_video_temporal_desc(_lib.VIDEO_MODES[mode], C.byref(cfg), int(F), int(hw), int(first), n, name, 64, C.byref(flops),
+                                              C.byref(nbytes)))
+    return dict(kernel=name.value.decode(), flops=flops.value, bytes=nbytes.value)
+
+
 def _match_cfg(hist_match, nbins=256):
     """(P3dHistMatch, the arrays it points to) of what P3DSession.set_hist_match takes: None / "off", "density", or a table
     (cdf, bin_centers) of float64 [nt] each."""

@@ -786,9 +786,40 @@ class P3DSession:
         check(lib().p3d_video_last_ms(self._h, ms))
         return dict(gather=ms[0], scatter=ms[1])
 
+    def set_video_temporal(self, kind="off", sigma=0., radius=0, alpha=0.):
+        """Smooth the open video's maps along the frame axis when they are read (an addition: overlapping 16-frame windows flicker
+        from frame to frame).  kind "gauss": a Gaussian of `sigma` frames over the whole video -- radius 0 follows cv2's rule,
+        (int(rint(8 sigma + 1)) | 1) // 2; at most 24, and at most frames - 1 -- with reflect-101 at the first and last frame;
+        "ema": the causal m_f = alpha m_{f-1} + (1 - alpha) v_f from m_0 = v_0, alpha in [0, 1).  Under mode "mean" the input is
+        sum / count.  video_maps returns the filtered maps and video_maps_u8 runs its chain on them; the stores are never
+        rewritten, so more windows can follow.  include/p3d_hip.h holds the exact arithmetic and dataflow.temporal_filter runs
+        it on supplied maps.  set_video_temporal("off"), None or the defaults switch it off.  Needs no open video."""
+        if kind is None:
+            kind = "off"
+        if kind not in _lib.TEMPORAL_KINDS:
+            raise ValueError("temporal kind %r: have %s" % (kind, sorted(_lib.TEMPORAL_KINDS)))
+        cfg = _lib.P3dVideoTemporal(_lib.TEMPORAL_KINDS[kind], float(sigma), int(radius), float(alpha))
+        check(lib().p3d_set_video_temporal(self._h, C.byref(cfg)))
+
+    def get_video_temporal(self):
+        """None while the option is off, else dict(kind, sigma, radius, alpha) as set."""
+        cfg, on = _lib.P3dVideoTemporal(), C.c_int(0)
+        check(lib().p3d_get_video_temporal(self._h, C.byref(cfg), C.byref(on)))
+        if not on.value:
+            return None
+        return dict(kind=[k for k, v in _lib.TEMPORAL_KINDS.items() if v == cfg.kind][0], sigma=cfg.sigma, radius=cfg.radius, alpha=cfg.alpha)
+
+    def video_temporal_last_ms(self):
+        """HIP-event time of the temporal launch of the last video_maps / video_maps_u8 that ran the stage, milliseconds."""
+        ms = C.c_double(0.)
+        check(lib().p3d_video_temporal_last_ms(self._h, C.byref(ms)))
+        return ms.value
+
     def video_maps(self, first, n, with_counts=False):
         """Maps of frames first .. first + n - 1, float32 [n, H, W] (mode "mean": sum / count); with_counts: also how many
-        windows contributed to each.  A frame no window has predicted yet is refused."""
+        windows contributed to each.  A frame no window has predicted yet is refused.  Under set_video_temporal the maps are
+        filtered along the frame axis of the whole video (the counts stay the frames' own), and every frame the filter needs --
+        up to its radius either side, or every earlier frame for "ema" -- must have been predicted."""
         n = max(int(n), 0)
         maps = np.empty((n,) + self.y_shape[2:], np.float32)
         counts = np.zeros(n, np.int32)
@@ -797,7 +828,8 @@ class P3DSession:
 
     def video_maps_u8(self, first, n, size=(1080, 960), scale=255.):
         """pred_maps_u8's 8-bit images of frames first .. first + n - 1 of the open video -> uint8 [n, H, W]; under
-        set_postprocess the smoothed, normalised ones.  Device times are left in `last_maps_ms`."""
+        set_postprocess the smoothed, normalised ones.  Under set_video_temporal the maps are filtered along the frame axis first
+        and the chain runs on the filtered maps.  Device times are left in `last_maps_ms`."""
         H, W = (size, size) if np.isscalar(size) else tuple(size)
         n = max(int(n), 0)
         valid = H >= 1 and W >= 1 and H * W <= 2 ** 31 - 1
