@@ -18,7 +18,15 @@ Without --data, a synthetic set (sap3d_tensorflow_amd.synthetic.synthetic_test_s
 
 --sauc M adds a sixth column, shuffled AUC (utils/metrics.py:157-197) of the clean full-resolution prediction against the
 union of the fixations of M other clips (Borji's M = 10).  It draws from its own np.random.RandomState(seed): the five
-reference columns are identical with and without it.  --kldiv and --info-gain BASELINE.npy add KL divergence
+reference columns are identical with and without it.  With --sauc-device the column is computed inside the evaluation pass
+(P3DSession.evaluate(shuffled=...); include/p3d_hip.h, "Shuffled AUC in the evaluation pass"): the set's fixation maps go into a
+pool on the device once, one bit per pixel, and per batch the draws from RandomState(seed) are, in this order: for each clip of the
+batch in clip order rng.choice(np.delete(arange(n), i), size=min(M, n - 1), replace=False); the union is taken on the device and
+the clips' n_other come back; then for each clip in clip order, nothing when it has no fixation, else n_rep times
+rng.permutation(n_other)[:n_fix].  (Without the flag the host path interleaves choice and permutations clip by clip: the two
+orders coincide at --batch 1, where the sixth column is the same number, and differ in the draws -- not in the law -- above it.)
+The scored map is the CLEAN map after the resize and every optional stage, so with --sauc-device --match-hist density is allowed:
+each clip's map is the one matched to its own density, scored against the other clips' fixations.  --kldiv and --info-gain BASELINE.npy add KL divergence
 (utils/metrics.py:338-362) and information gain over the baseline map (float32 [H, W] at the fixation maps' size) of the same
 scored map, computed on the GPU in the same pass (P3DSession.set_eval_extra); their NaN-dropped means follow the other columns
 on both lines, and the five reference columns are identical with and without them.  --time prints per batch: forward, host random draws, host->device
@@ -123,6 +131,12 @@ def shuffled_auc(sess, fixation, lo, m, rng, device=0):
     return out
 
 
+def sauc_others(n, lo, hi, m, rng):
+    """--sauc-device: the other clips of every clip of the batch [lo, hi), int32 [hi - lo, min(m, n - 1)], drawn clip by clip as
+    shuffled_auc draws them."""
+    return np.asarray([rng.choice(np.delete(np.arange(n), i), size=min(m, n - 1), replace=False) for i in range(lo, hi)], np.int32)
+
+
 def match_target(args):
     """What --match-hist asks for, as P3DSession.set_hist_match takes it: "off", "density", or the table of an .npz."""
     if not args.match_hist:
@@ -177,6 +191,8 @@ def parse_args(argv=None):
     p.add_argument("--gpu", type=str, default="0")
     p.add_argument("--seed", type=int, default=0, help="seeds numpy's global stream (the metrics' draws) and the synthetic set")
     p.add_argument("--sauc", type=int, default=0, metavar="M", help="add shuffled AUC against the fixations of M other clips")
+    p.add_argument("--sauc-device", action="store_true", help="[addition] compute --sauc's column inside the evaluation pass, from a "
+                   "fixation pool kept on the device (P3DSession.open_fixation_pool)")
     p.add_argument("--time", action="store_true", help="print the stage times of every batch")
     p.add_argument("--kldiv", action="store_true", help="add KL divergence of the density from the scored map (utils/metrics.py KLdiv; "
                    "P3DSession.set_eval_extra)")
@@ -209,6 +225,10 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if not 2 <= args.match_bins <= 1024:
         p.error("--match-bins must be in 2..1024")
+    if args.sauc_device and not args.sauc:
+        p.error("--sauc-device needs --sauc M")
+    if args.sauc_device and args.sauc > 64:
+        p.error("--sauc-device takes M <= 64")
     return args
 
 
@@ -255,6 +275,11 @@ def main(argv=None):
         return [(name, nan_dropped_mean(extra_cols[k])) for k, name in labels]
     np.random.seed(args.seed)
     sauc_rng = np.random.RandomState(args.seed) if args.sauc else None
+    if args.sauc_device:
+        if len(fixation) < 2:
+            raise SystemExit("--sauc-device needs at least two clips")
+        sess.open_fixation_pool(fixation.shape[1:], len(fixation))
+        sess.fixation_pool_put(0, fixation)
     cols = [[] for _ in range(6 if args.sauc else 5)]
     index = 0
     for lo, hi in batches(len(x), args.batch):
@@ -265,7 +290,11 @@ def main(argv=None):
             sess.prior_add(fixation[lo:hi], -1)
             sess.finish_prior(plan["sigma"], plan["radius"])
             sess.set_eval_extra(kldiv=args.kldiv, baseline="prior")
-        m = sess.evaluate(x[lo:hi], density[lo:hi], fixation[lo:hi], size=fixation.shape[1:])
+        shuffled = None
+        if args.sauc_device:                                              # the docstring's draw order
+            shuffled = dict(others=sauc_others(len(fixation), lo, hi, args.sauc, sauc_rng), rng=sauc_rng)
+            shuffled["n_other"] = sess.shuffled_begin(shuffled["others"])
+        m = sess.evaluate(x[lo:hi], density[lo:hi], fixation[lo:hi], size=fixation.shape[1:], shuffled=shuffled)
         if plan and plan["leave_out"]:
             sess.prior_add(fixation[lo:hi], 1)
         for k in range(5):
@@ -274,7 +303,9 @@ def main(argv=None):
             e = sess.last_eval_extra()
             for k in range(2):
                 extra_cols[k].extend(e[:, k].tolist())
-        if args.sauc:
+        if args.sauc_device:
+            cols[5].extend(sess.last_eval_shuffled()[0].tolist())
+        elif args.sauc:
             cols[5].extend(shuffled_auc(sess, fixation, lo, args.sauc, sauc_rng, device))
         if args.time:
             t = sess.last_eval_ms

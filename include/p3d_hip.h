@@ -1094,6 +1094,85 @@ int p3d_debug_eval_maps_prior(int device, const float* maps, int n_maps, int h, 
                               const p3d_hist_match* match, int flags, const float* baseline, double* extra, const float* prior,
                               int mode, float a);
 
+/* ---- Shuffled AUC in the evaluation pass, from a fixation pool on the device (utils/metrics.py:157-197 AUC_shuffled: AUC_Borji
+ * whose random locations are fixations of OTHER images, the usual centre-bias-discounting column of video-saliency results; an
+ * ADDITION to test.py, which does not call it).  OFF by default: until p3d_eval_shuffled_draws arms an evaluation, every entry point
+ * issues exactly the launches it issued before and returns the same bits, and nothing is allocated before p3d_fixpool_open.  The
+ * train step, a captured step graph and its schedule never see any of it.  PARITY UNPINNED (the reference's AUC_shuffled takes a
+ * ready other_map): this text is the contract, tests/sauc_ref.py replays it in numpy and is itself held to
+ * oracle.evaluation.AUC_shuffled; every integer result of the kernels is held to that replay with tolerance 0.
+ *   STORE   one pool per handle: words[capacity][nw] of uint64, nw = ceil(H * W / 64), one bit per pixel.  Bit j of word k of a slot
+ *           is set exactly when byte 64k + j of its map is >= 128 (the evaluation pass's "fixated" rule); the unused high bits of
+ *           the last word are 0.  In numpy: np.packbits(map.ravel() >= 128, bitorder="little"), padded to a multiple of 8 bytes,
+ *           viewed as little-endian uint64.  A 1080 x 960 map takes 129 600 bytes.  The host keeps which slots were filled.
+ *   UNION   for clip b of a batch and its row ids[b][0 .. M) of filled slots, 1 <= M <= 64 (repeats allowed): uni[b][k] = the OR of
+ *           words[ids[b][m]][k]; n_other[b] = the number of set bits; an exclusive uint32 prefix of the words' bit counts, kept in
+ *           two levels (within scan blocks of 256 words, and over the blocks).  np.any over the M maps.
+ *   SELECT  for a rank 0 <= q < n_other[b]: the pixel index of the q-th set bit of uni[b] in ascending pixel order, an int32:
+ *           np.nonzero(other.ravel())[0][q], exactly.
+ *   DRAW ORDER  the host draws; the device never does.  Python's metrics.shuffled_draws is the one place: per clip in clip order,
+ *           nothing for a clip with n_fix = 0, else for each of the n_rep splits in order rng.permutation(n_other_b)[:n_fix_b];
+ *           clip b's ranks are the transposed rows [min(n_fix_b, n_other_b)][n_rep], row-major, clips concatenated.  A driver that
+ *           also draws the other clips from the same stream draws all rows of ids for the batch first (clip order), calls
+ *           p3d_eval_shuffled_begin, then draws the permutations (clip order): drivers/test.py --sauc-device.
+ *   SCORE   the armed p3d_eval_last_frames, after all its launches (unedited, in their order): SELECT of every rank; then pass A and
+ *           pass B of the evaluation (p3d_full_moments) on the CLEAN scored map P -- after the resize and the optional BLUR / PRIOR /
+ *           MATCH / NORM stages, WITHOUT AUC_Judd's jitter (with P3D_MATCH_DENSITY that is the map matched to its own density) --
+ *           with statistics and scratch of their own; then the AUC_Borji kernel with clip b's n_rows[b] rows of selected pixels.
+ *           The false-positive rate divides by n_fix also when n_other < n_fix (utils/metrics.py:151-152); with n_other = 0 the
+ *           curve closes at (1, 1); a clip without fixation gives NaN for every split.  These are the launches and inputs of
+ *           p3d_metric_auc_shuffled on that map: the same bits.  The mean over the splits is the host's (np.mean).  out[B][5], KL
+ *           and IG are bit for bit what they are unarmed.
+ * p3d_fixpool_open   a pool of `capacity` slots for maps of H x W bytes (an open one is replaced, with the union held for it).
+ *                    Refused: H * W outside [1, 2^30], capacity outside [1, 2^31 - 1].
+ * p3d_fixpool_put    maps [n][H][W] of bytes on the host into slots first .. first + n - 1, through a staging buffer of at most
+ *                    256 MB.  Refused before any launch: no pool, n < 1, a slot outside [0, capacity).
+ * p3d_fixpool_info   size, capacity, words per map and number of filled slots; every pointer may be NULL.
+ * p3d_fixpool_get    the words [n][nw] of filled slots first .. first + n - 1 (for tests).  Refused: an unfilled slot, a slot outside.
+ * p3d_fixpool_close  frees the pool, its staging buffer and the union.
+ * p3d_fixpool_last_ms  HIP-event times, in ms: [0] the pack launches of the last p3d_fixpool_put, [1] the union + scan launch of the
+ *                    last p3d_eval_shuffled_begin, [2] the select and [3] the clean moments + borji of the last armed evaluation.
+ * p3d_eval_shuffled_begin  UNION for the handle's batch: ids [B][M] on the host, checked row by row before any launch (every id a
+ *                    filled slot, 1 <= M <= 64); n_other_out[B] comes back after one synchronisation; the union and its scan stay
+ *                    in buffers of the handle.  Independent of the prediction: before or after the forward pass.  Disarms.
+ * p3d_eval_shuffled_draws  the host's ranks, [n_rows[b]][n_rep] per clip, concatenated, and the threshold step of the curve.  Refused
+ *                    before anything is kept: no union held, n_rows[b] > n_other[b], a rank outside [0, n_other[b]), n_rep < 1, a
+ *                    step that is not positive.  Arms exactly ONE evaluation: the next p3d_eval_last_frames, whatever becomes of it.
+ *                    That evaluation refuses, before any launch, a pool of another size than its H x W, a batch of another size
+ *                    than the union's, and n_rows[b] != min(n_fix[b], n_other[b]) (n_fix itself is held to the device's count
+ *                    as always).
+ * p3d_last_eval_shuffled  per_rep[B][n_rep] of the last armed evaluation that succeeded (cap = room in doubles).  An evaluation
+ *                    that was not armed clears nothing and adds nothing.
+ * TEST HOOKS (tests/test_gpu_sauc_device.py); device buffers sit between guard elements, a guard that changed is an error:
+ * p3d_debug_fix_pack     STORE of maps [n][H][W] -> words [n][nw]; the maps start `offset` (0 .. 3) bytes past a 16-byte boundary.
+ * p3d_debug_fix_union    UNION over a pool of packed words [capacity][nw] -> uni [B][nw], the exclusive prefix over the whole map
+ *                    [B][nw] (block sum + block-local prefix; may be NULL), n_other [B].
+ * p3d_debug_fix_select   UNION, then SELECT of ranks ([n_rows[b]][n_rep] per row, concatenated) -> out, int32, the same layout.
+ * p3d_debug_eval_maps_shuffled  p3d_debug_eval_maps_prior (a supplied baseline only) with the whole armed sequence on caller-supplied
+ *                    maps: pool_maps [capacity][H][W] are packed, the union taken, n_other [B] returned, and the evaluation scored
+ *                    with the given ranks -> per_rep [n_maps][sh_n_rep]. */
+#define P3D_FIX_SCAN_BLOCK 256
+int p3d_fixpool_open(p3d_handle* h, int H, int W, int64_t capacity);
+int p3d_fixpool_put(p3d_handle* h, int64_t first, const unsigned char* maps, int64_t n);
+int p3d_fixpool_info(p3d_handle* h, int* H, int* W, int64_t* capacity, int64_t* words_per_map, int64_t* n_filled);
+int p3d_fixpool_get(p3d_handle* h, int64_t first, int64_t n, uint64_t* words);
+int p3d_fixpool_close(p3d_handle* h);
+int p3d_fixpool_last_ms(p3d_handle* h, double ms[4]);
+int p3d_eval_shuffled_begin(p3d_handle* h, const int* ids, int M, uint32_t* n_other_out);
+int p3d_eval_shuffled_draws(p3d_handle* h, const int* ranks, const int* n_rows, int n_rep, double step);
+int p3d_last_eval_shuffled(p3d_handle* h, double* per_rep, int64_t cap);
+int p3d_debug_fix_pack(int device, const unsigned char* maps, int n, int H, int W, int offset, uint64_t* words);
+int p3d_debug_fix_union(int device, const uint64_t* pool, int capacity, int H, int W, const int* ids, int B, int M, uint64_t* uni,
+                        uint32_t* prefix /* may be NULL */, uint32_t* n_other);
+int p3d_debug_fix_select(int device, const uint64_t* pool, int capacity, int H, int W, const int* ids, int B, int M, const int* ranks,
+                         const int* n_rows, int n_rep, int* out);
+int p3d_debug_eval_maps_shuffled(int device, const float* maps, int n_maps, int h, int w, int elem_stride, const unsigned char* density,
+                                 int Hd, int Wd, const unsigned char* fixation, int H, int W, const double* jitter, const int* borji_idx,
+                                 const int* n_fix, int n_rep, double step_size, double* out, const p3d_postprocess* cfg,
+                                 const p3d_hist_match* match, int flags, const float* baseline, double* extra, const float* prior,
+                                 int mode, float a, const unsigned char* pool_maps, int capacity, const int* ids, int M,
+                                 const int* ranks, const int* n_rows, int sh_n_rep, double sh_step, uint32_t* n_other, double* per_rep);
+
 /* ---- Resident video inference (an ADDITION beside p3d_predict_windows: gen_pred.py slides a 16-frame queue by one frame and keeps
  * nothing on the device).  A video's normalised frames go up once, windows are cut where the frames are, and every frame's map is
  * kept on the device until it is read.  OFF until p3d_video_open: while no video is open every other entry point issues what it

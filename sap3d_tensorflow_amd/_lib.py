@@ -313,6 +313,23 @@ SIGNATURES = {
     "p3d_debug_eval_maps_prior": (C.c_int, [C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ubyte), C.c_int, C.c_int,
                                             C.POINTER(C.c_ubyte), C.c_int, C.c_int, _dp, _ip, _ip, C.c_int, C.c_double, _dp,
                                             C.POINTER(P3dPostprocess), C.POINTER(P3dHistMatch), C.c_int, _fp, _dp, _fp, C.c_int, C.c_float]),
+    "p3d_fixpool_open": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64]),
+    "p3d_fixpool_put": (C.c_int, [C.c_void_p, C.c_int64, _u8p, C.c_int64]),
+    "p3d_fixpool_info": (C.c_int, [C.c_void_p, _ip, _ip, _i64p, _i64p, _i64p]),
+    "p3d_fixpool_get": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_uint64)]),
+    "p3d_fixpool_close": (C.c_int, [C.c_void_p]),
+    "p3d_fixpool_last_ms": (C.c_int, [C.c_void_p, _dp]),
+    "p3d_eval_shuffled_begin": (C.c_int, [C.c_void_p, _ip, C.c_int, C.POINTER(C.c_uint32)]),
+    "p3d_eval_shuffled_draws": (C.c_int, [C.c_void_p, _ip, _ip, C.c_int, C.c_double]),
+    "p3d_last_eval_shuffled": (C.c_int, [C.c_void_p, _dp, C.c_int64]),
+    "p3d_debug_fix_pack": (C.c_int, [C.c_int, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
+    "p3d_debug_fix_union": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.POINTER(C.c_uint64),
+                                      C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "p3d_debug_fix_select": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_int, _ip, C.c_int, C.c_int, _ip, _ip, C.c_int, _ip]),
+    "p3d_debug_eval_maps_shuffled": (C.c_int, [C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int,
+                                               _dp, _ip, _ip, C.c_int, C.c_double, _dp, C.POINTER(P3dPostprocess), C.POINTER(P3dHistMatch),
+                                               C.c_int, _fp, _dp, _fp, C.c_int, C.c_float, _u8p, C.c_int, _ip, C.c_int, _ip, _ip, C.c_int,
+                                               C.c_double, C.POINTER(C.c_uint32), _dp]),
     "p3d_video_open": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "p3d_video_close": (C.c_int, [C.c_void_p]),
     "p3d_video_info": (C.c_int, [C.c_void_p, _ip, _ip, _ip]),

@@ -417,7 +417,8 @@ __global__ __launch_bounds__(TPB) void full_pass_c(P3dFullMaps a) {
 // S = J scaled to [0,1] by the map's min / max (pass A); S_fix = the compacted fixated values; S_rand[:, rep] = S at the
 // caller's pixel indices r[n_rand][n_rep].  Thresholds arange(0, max(S_fix, S_rand[:, rep]), step) from the top; tp = share
 // of S_fix >= thr, fp = #{S_rand >= thr} / n_fix (utils/metrics.py:146-153: also for shuffled AUC's shorter rows, :151-152).
-// AUC-Borji: n_rand = n_fix, r = randint(0, n_pix, [n_fix, n_rep]) (:139).  Shuffled AUC: n_rand = min(n_fix, n_other).
+// AUC-Borji: n_rand = n_fix, r = randint(0, n_pix, [n_fix, n_rep]) (:139).  Shuffled AUC: n_rand = min(n_fix, n_other); n_rand_map gives
+// every map its own row count (the evaluation pass's shuffled AUC, where n_other differs from clip to clip).
 __global__ __launch_bounds__(TPB) void full_borji(P3dFullMaps a, P3dFullBorji r) {
     __shared__ double red[TPB];
     __shared__ int last;
@@ -428,7 +429,7 @@ __global__ __launch_bounds__(TPB) void full_borji(P3dFullMaps a, P3dFullBorji r)
         if (tid == 0 && rep == 0 && a.out) a.out[b * 5 + 3] = NAN;
         return;
     }
-    const int nrand = r.n_rand < 0 ? nfix : r.n_rand;
+    const int nrand = r.n_rand_map ? r.n_rand_map[b] : (r.n_rand < 0 ? nfix : r.n_rand);
     const size_t base = (size_t)b * a.n_pix;
     const double* st = a.stats + (size_t)b * S_COUNT;
     const double mn = st[S_MNJ], rng = st[S_MXJ] - st[S_MNJ];

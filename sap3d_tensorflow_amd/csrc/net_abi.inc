@@ -2882,6 +2882,13 @@ struct EvalSource { const float* p; long long map_stride; int elem_stride, n_map
 // only), and where the [n_maps][2] values go on the host
 static_assert(P3D_EVAL_KLDIV == P3D_EXTRA_KLDIV && P3D_EVAL_INFO_GAIN == P3D_EXTRA_INFO_GAIN, "p3d_kernels.h names the header's flags");
 struct EvalExtra { int flags; const float* base; const double* bstat; int H, W; double* out; };
+// p3d_eval_shuffled_*'s part of one evaluation: the union of every clip's other fixations with its scan (device memory, fixpool.hip),
+// the counts on the host, the pool's size, the host's ranks [n_rows[b]][n_rep] per clip, and where the [n_maps][n_rep] areas and the
+// two HIP-event times (select; clean moments + borji) go on the host
+struct ShuffledEval {
+    const unsigned long long* uni; const unsigned* prefix; const unsigned* bsum; const unsigned* n_other_dev; const unsigned* n_other;
+    long long nw; int H, W; const int* ranks; const int* n_rows; int n_rep; double step; double* per_rep; double* ms;
+};
 // The device pass of test.py's per-batch body on stream s, with the scratch of s: everything of p3d_eval_last_frames that does
 // not need the handle, so that p3d_debug_eval_maps runs the same launches on maps of the caller's.  Checks the arguments, lays
 // the buffers out in the stream's scratch, uploads, resizes the source maps (float32) and the density maps (uint8), runs the
@@ -2890,7 +2897,7 @@ struct EvalExtra { int flags; const float* base; const double* bstat; int H, W; 
 void eval_maps(hipStream_t s, const EvalSource& src, const std::function<void(hipStream_t)>& prepare, const unsigned char* density, int Hd, int Wd, const unsigned char* fixation, int H,
                int W, const double* jitter, const int* borji_idx, const int* n_fix, int n_rep, double step_size, double* out,
                double* stage_ms, const p3d_postprocess* post = nullptr, const MatchPlan* matchp = nullptr, const EvalExtra* extra = nullptr,
-               const PriorStage* priorp = nullptr) {
+               const PriorStage* priorp = nullptr, const ShuffledEval* sh = nullptr) {
     const PostPlan plan(post);                 // p3d_set_postprocess: between the resize and the metrics, in place on P
     const MatchPlan match = matchp ? *matchp : MatchPlan();      // p3d_set_hist_match: after the blur, before the normalisation
     const PriorStage prior = priorp ? *priorp : PriorStage();    // p3d_set_prior_stage: after the blur, before the matching
@@ -2912,10 +2919,37 @@ void eval_maps(hipStream_t s, const EvalSource& src, const std::function<void(hi
     const std::vector<int> meta = full_meta(n_fix, B, n_rep, N, n_idx);
     if (n_idx > 0 && !borji_idx) throw P3dError("eval: null random indices");
     check_indices(borji_idx, n_idx, N, "eval");
-    P3dFullMaps a;
-    P3dFullBorji r;
+    // shuffled AUC (p3d_eval_shuffled_draws armed it): a second, clean P3dFullMaps on the same P with rows of its own per map
+    std::vector<int> meta2;
+    size_t n_idx2 = 0;
+    int max_rows = 0;
+    if (sh) {
+        if (sh->H != H || sh->W != W)
+            throw P3dError("eval_shuffled: the fixation pool is " + std::to_string(sh->H) + " x " + std::to_string(sh->W) + ", the evaluation " +
+                           std::to_string(H) + " x " + std::to_string(W));
+        if (!sh->per_rep) throw P3dError("null argument");
+        p3d_handle::shuffled_check_draws("eval_shuffled", sh->ranks, sh->n_rows, sh->n_other, B, sh->n_rep, sh->step);
+        for (int b = 0; b < B; ++b) {
+            const long long want = std::min<long long>(n_fix[b], sh->n_other[b]);
+            if (sh->n_rows[b] != want)
+                throw P3dError("eval_shuffled: clip " + std::to_string(b) + ": " + std::to_string(sh->n_rows[b]) + " rows of ranks, but min(n_fix, n_other) = " +
+                               std::to_string(want));
+            max_rows = std::max(max_rows, sh->n_rows[b]);
+        }
+        meta2 = full_meta(n_fix, B, 0, N, n_idx2);
+        long long at = 0;
+        for (int b = 0; b < B; ++b) { meta2[b * 3 + 2] = (int)at; at += (long long)sh->n_rows[b] * sh->n_rep; }
+        n_idx2 = (size_t)at;
+    }
+    P3dFullMaps a, a2;
+    P3dFullBorji r, r2;
+    int *ranks2 = nullptr, *idx2 = nullptr, *rows2 = nullptr;
     a.fix_u8 = 1; a.n_pix = N; a.n_maps = B; a.nblk = p3d_full_blocks(N); a.out = nullptr;
     r.n_rand = -1; r.n_rep = n_rep; r.step = step_size;
+    if (sh) {
+        a2.fix_u8 = 1; a2.n_pix = N; a2.n_maps = B; a2.nblk = a.nblk; a2.out = nullptr;
+        r2.n_rep = sh->n_rep; r2.step = sh->step;
+    }
     float *P = nullptr, *D = nullptr;
     unsigned char *dens = nullptr, *fixd = nullptr;
     double *jit = nullptr, *dout = nullptr;
@@ -2936,6 +2970,10 @@ void eval_maps(hipStream_t s, const EvalSource& src, const std::function<void(hi
         if (plan.on) post_carve(c, post_scratch, plan, post_chunk, N, false);
         match_carve(c, match_scratch, match, post_chunk, N);
         if (xon) { x.part = c.take<double>((size_t)B * a.nblk * P3D_FULL_EXTRA_PARTS); x.out = c.take<double>((size_t)B * 2); }
+        if (sh) {
+            ranks2 = c.take<int>(n_idx2); idx2 = c.take<int>(n_idx2); rows2 = c.take<int>((size_t)B);
+            carve_full(c, a2, r2, meta2);
+        }
     };
     Carve c;
     layout(c);                                 // sizes the scratch
@@ -2945,6 +2983,7 @@ void eval_maps(hipStream_t s, const EvalSource& src, const std::function<void(hi
     c = Carve{(char*)slab, 0};
     layout(c);
     a.P = P; a.D = D; a.fix = fixd; a.jit = jitter ? jit : nullptr; a.counter = counters; a.out = dout; r.idx = idx;
+    if (sh) { a2.P = P; a2.fix = fixd; a2.counter = counters; r2.idx = idx2; r2.n_rand_map = rows2; }
 
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     if (stage_ms)
@@ -2972,6 +3011,32 @@ void eval_maps(hipStream_t s, const EvalSource& src, const std::function<void(hi
     }
     HIPCHECK(p3d_full_rank(a, s));
     HIPCHECK(p3d_full_borji(a, r, s));
+    if (sh) {                                  // after every launch of the plain evaluation: select, then the clean map's moments and borji
+        hipEvent_t e2[3] = {nullptr, nullptr, nullptr};
+        if (n_idx2) HIPCHECK(copy_now(ranks2, sh->ranks, n_idx2 * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHECK(copy_now(rows2, sh->n_rows, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHECK(copy_now((void*)a2.meta, meta2.data(), meta2.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        for (auto& e : e2) HIPCHECK(hipEventCreate(&e));
+        hipError_t err = hipEventRecord(e2[0], s);
+        if (err == hipSuccess && n_idx2) {
+            FixSelectArgs q;
+            q.uni = sh->uni; q.prefix = sh->prefix; q.bsum = sh->bsum; q.n_other = sh->n_other_dev; q.nw = sh->nw; q.B = B;
+            q.nsb = p3d_fix_scan_blocks(sh->nw); q.n_rep = sh->n_rep; q.max_rows = max_rows; q.meta = a2.meta; q.n_rows = rows2; q.ranks = ranks2;
+            q.out = idx2;
+            err = p3d_fix_select_launch(q, s);
+        }
+        if (err == hipSuccess) err = hipEventRecord(e2[1], s);
+        if (err == hipSuccess) err = p3d_full_moments(a2, s);
+        if (err == hipSuccess) err = p3d_full_borji(a2, r2, s);
+        if (err == hipSuccess) err = hipEventRecord(e2[2], s);
+        if (err == hipSuccess) err = copy_now(sh->per_rep, r2.per_rep, (size_t)B * sh->n_rep * sizeof(double), hipMemcpyDeviceToHost, s);
+        float t0 = 0.f, t1 = 0.f;
+        if (err == hipSuccess) err = hipEventElapsedTime(&t0, e2[0], e2[1]);
+        if (err == hipSuccess) err = hipEventElapsedTime(&t1, e2[1], e2[2]);
+        for (auto& e : e2) hipEventDestroy(e);
+        HIPCHECK(err);
+        if (sh->ms) { sh->ms[0] = t0; sh->ms[1] = t1; }
+    }
     if (stage_ms) HIPCHECK(hipEventRecord(ev[2], s));
     std::vector<double> st((size_t)B * P3D_FULL_STATS);
     HIPCHECK(copy_now(out, dout, (size_t)B * 5 * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -3063,10 +3128,23 @@ int p3d_eval_last_frames(p3d_handle* h, const unsigned char* density, int Hd, in
     extra.out = xv.data();
     if (extra.flags) { h->extra_state = p3d_handle::EXTRA_NONE; h->extra_eval_H = H; h->extra_eval_W = W; }
     const PriorStage hprior = prior_stage_of(h);
+    // p3d_eval_shuffled_draws armed this one evaluation: whatever becomes of it, the next one is plain again
+    const bool armed = h->sh_armed;
+    h->sh_armed = false;
+    std::vector<double> sv;
+    ShuffledEval sh{};
+    if (armed) {
+        if ((int)h->sh_n_other.size() != pr->N) throw P3dError("eval_shuffled: the union was taken for " + std::to_string(h->sh_n_other.size()) + " clips, the batch has " + std::to_string(pr->N));
+        sv.assign((size_t)pr->N * h->sh_n_rep, 0.0);
+        h->sh_have = false;
+        sh = ShuffledEval{h->sh_uni, h->sh_prefix, h->sh_bsum, h->sh_n_other_dev, h->sh_n_other.data(), h->fp_nw, h->fp_H, h->fp_W,
+                          h->sh_ranks.data(), h->sh_n_rows.data(), h->sh_n_rep, h->sh_step, sv.data(), h->fp_score_ms};
+    }
     eval_maps(h->stream, {pr->p + (size_t)(T - 1) * hw * pr->ld, (long long)T * hw * pr->ld, pr->ld, pr->N, pr->H, pr->W}, prepare,
               density, Hd, Wd, fixation, H, W, jitter, borji_idx, n_fix, n_rep, step_size, out, stage_ms,
               h->post_on ? &h->post_cfg : nullptr, h->match_cfg.on() ? &h->match_cfg : nullptr, extra.flags && fits ? &extra : nullptr,
-              h->prior_mode != P3D_PRIOR_OFF ? &hprior : nullptr);
+              h->prior_mode != P3D_PRIOR_OFF ? &hprior : nullptr, armed ? &sh : nullptr);
+    if (armed) { h->sh_last.swap(sv); h->sh_have = true; }
     if (extra.flags) {
         h->extra_state = fits ? p3d_handle::EXTRA_HAVE : p3d_handle::EXTRA_SHAPE;
         if (fits) h->extra_last.swap(xv);
@@ -3841,6 +3919,235 @@ int p3d_debug_eval_maps_prior(int device, const float* maps, int n_maps, int h, 
     const PriorStage pst{mode, a, dprior.p, H, W};
     eval_maps(nullptr, {src.p, per_map, elem_stride, n_maps, h, w}, nullptr, density, Hd, Wd, fixation, H, W, jitter, borji_idx, n_fix, n_rep,
               step_size, out, nullptr, cfg, &mp, &x, &pst);
+    API_END
+}
+
+// ---- fixation pool and shuffled AUC in the evaluation pass (include/p3d_hip.h; the handle's part in net_sched.inc, fixpool.hip) ----
+int p3d_fixpool_open(p3d_handle* h, int H, int W, int64_t capacity) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->fixpool_open(H, W, capacity);
+    API_END
+}
+
+int p3d_fixpool_close(p3d_handle* h) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->fixpool_close();
+    API_END
+}
+
+int p3d_fixpool_info(p3d_handle* h, int* H, int* W, int64_t* capacity, int64_t* words_per_map, int64_t* n_filled) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    h->fixpool_need_open("fixpool_info");
+    if (H) *H = h->fp_H;
+    if (W) *W = h->fp_W;
+    if (capacity) *capacity = h->fp_cap;
+    if (words_per_map) *words_per_map = h->fp_nw;
+    if (n_filled) *n_filled = (int64_t)std::count(h->fp_filled.begin(), h->fp_filled.end(), (char)1);
+    API_END
+}
+
+int p3d_fixpool_put(p3d_handle* h, int64_t first, const unsigned char* maps, int64_t n) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->fixpool_put(first, maps, n);
+    API_END
+}
+
+int p3d_fixpool_get(p3d_handle* h, int64_t first, int64_t n, uint64_t* words) {
+    API_BEGIN
+    if (!h || !words) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->fixpool_need_open("fixpool_get");
+    if (n < 1 || first < 0 || first > h->fp_cap - n)
+        throw P3dError("fixpool_get: slots " + std::to_string(first) + " .. " + std::to_string(first + n - 1) + " are not inside [0, " + std::to_string(h->fp_cap) + ")");
+    for (int64_t i = first; i < first + n; ++i)
+        if (!h->fp_filled[(size_t)i]) throw P3dError("fixpool_get: slot " + std::to_string(i) + " was never filled (p3d_fixpool_put)");
+    HIPCHECK(copy_now(words, h->fp_words + first * h->fp_nw, (size_t)n * h->fp_nw * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    API_END
+}
+
+int p3d_fixpool_last_ms(p3d_handle* h, double ms[4]) {
+    API_BEGIN
+    if (!h || !ms) throw P3dError("null argument");
+    ms[0] = h->fp_pack_ms; ms[1] = h->fp_union_ms; ms[2] = h->fp_score_ms[0]; ms[3] = h->fp_score_ms[1];
+    API_END
+}
+
+int p3d_eval_shuffled_begin(p3d_handle* h, const int* ids, int M, uint32_t* n_other_out) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->shuffled_begin(ids, h->pred->N, M, n_other_out);
+    API_END
+}
+
+int p3d_eval_shuffled_draws(p3d_handle* h, const int* ranks, const int* n_rows, int n_rep, double step) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    h->shuffled_draws(ranks, n_rows, n_rep, step);
+    API_END
+}
+
+int p3d_last_eval_shuffled(p3d_handle* h, double* per_rep, int64_t cap) {
+    API_BEGIN
+    if (!h || !per_rep) throw P3dError("null argument");
+    if (!h->sh_have) throw P3dError("last_eval_shuffled: no evaluation has run armed (p3d_eval_shuffled_draws)");
+    if (cap < (int64_t)h->sh_last.size())
+        throw P3dError("last_eval_shuffled: room for " + std::to_string(cap) + " doubles, " + std::to_string(h->sh_last.size()) + " needed");
+    std::copy(h->sh_last.begin(), h->sh_last.end(), per_rep);
+    API_END
+}
+
+}  // extern "C"
+namespace {
+void fix_shape(const char* what, int H, int W) {
+    if (H < 1 || W < 1 || (long long)H * W > INT32_MAX / 2) throw P3dError(std::string(what) + ": maps are H x W bytes, 1 <= H * W <= 2^30");
+}
+// op level: the union of B rows of M slots of a pool of `cap` packed maps, every device buffer between guard words
+struct FixUnionRun {
+    long long nw; int nsb, B;
+    Guarded<unsigned long long> pool, uni; Guarded<unsigned> prefix, bsum, n_other, counter; Guarded<int> ids;
+    FixUnionArgs a;
+    FixUnionRun(const uint64_t* words, int cap, int H, int W, const int* idv, int B_, int M)
+        : nw(p3d_fix_words((long long)H * W)), nsb(p3d_fix_scan_blocks(nw)), B(B_),
+          pool((size_t)cap * nw, 4, 0, reinterpret_cast<const unsigned long long*>(words)), uni((size_t)B_ * nw, 4, 0, nullptr),
+          prefix((size_t)B_ * nw, 8, 0, nullptr), bsum((size_t)B_ * nsb, 8, 0, nullptr), n_other((size_t)B_, 8, 0, nullptr),
+          counter((size_t)B_, 8, 0, nullptr), ids((size_t)B_ * M, 8, 0, idv) {
+        a.pool = pool.data(); a.nw = nw; a.ids = ids.data(); a.B = B; a.M = M; a.nsb = nsb;
+        a.uni = uni.data(); a.prefix = prefix.data(); a.bsum = bsum.data(); a.n_other = n_other.data(); a.counter = counter.data();
+        HIPCHECK(p3d_fix_union_launch(a, nullptr));
+    }
+    // uni [B][nw], the exclusive prefix over the whole map [B][nw] (block sum + block-local prefix), n_other [B]; guards intact
+    void back(uint64_t* uni_out, uint32_t* prefix_out, uint32_t* n_other_out, const char* what) {
+        std::vector<unsigned> local((size_t)B * nw), bs((size_t)B * nsb), zero((size_t)B, 1u);
+        uni.back(reinterpret_cast<unsigned long long*>(uni_out), what);
+        prefix.back(local.data(), what);
+        bsum.back(bs.data(), what);
+        n_other.back(n_other_out, what);
+        counter.back(zero.data(), what);
+        pool.unchanged(what);
+        ids.unchanged(what);
+        for (unsigned z : zero) if (z != 0u) throw P3dError(std::string(what) + ": an arrival counter was left at " + std::to_string(z));
+        if (prefix_out)
+            for (int b = 0; b < B; ++b)
+                for (long long k = 0; k < nw; ++k) prefix_out[(size_t)b * nw + k] = bs[(size_t)b * nsb + k / P3D_FIX_SCAN_WORDS] + local[(size_t)b * nw + k];
+    }
+};
+void fix_ids_check(const char* what, const int* ids, int cap, int B, int M) {
+    if (!ids) throw P3dError("null argument");
+    if (cap < 1 || B < 1 || B > 65535) throw P3dError(std::string(what) + ": 1 .. 65535 rows over a pool of at least one map");
+    if (M < 1 || M > 64) throw P3dError(std::string(what) + ": 1 .. 64 other maps per clip, not " + std::to_string(M));
+    for (size_t i = 0; i < (size_t)B * M; ++i)
+        if (ids[i] < 0 || ids[i] >= cap) throw P3dError(std::string(what) + ": slot " + std::to_string(ids[i]) + " is outside [0, " + std::to_string(cap) + ")");
+}
+}  // namespace
+extern "C" {
+
+int p3d_debug_fix_pack(int device, const unsigned char* maps, int n, int H, int W, int offset, uint64_t* words) {
+    API_BEGIN
+    metric_args(device, maps, maps, 1, 1, words);
+    fix_shape("fix_pack", H, W);
+    if (n < 1 || n > 65535) throw P3dError("fix_pack: 1 .. 65535 maps");
+    if (offset < 0 || offset > 3) throw P3dError("fix_pack: offset in [0, 3]");
+    const size_t N = (size_t)H * W, nw = (size_t)p3d_fix_words((long long)N);
+    Guarded<unsigned char> src((size_t)n * N, 16, (size_t)offset, maps);
+    Guarded<unsigned long long> dst((size_t)n * nw, 4, 0, nullptr);
+    FixPackArgs a;
+    a.maps = src.data(); a.n = n; a.n_pix = (long long)N; a.words = dst.data();
+    HIPCHECK(p3d_fix_pack_launch(a, nullptr));
+    dst.back(reinterpret_cast<unsigned long long*>(words), "fix_pack");
+    src.unchanged("fix_pack");
+    API_END
+}
+
+int p3d_debug_fix_union(int device, const uint64_t* pool, int capacity, int H, int W, const int* ids, int B, int M, uint64_t* uni,
+                        uint32_t* prefix, uint32_t* n_other) {
+    API_BEGIN
+    metric_args(device, pool, pool, 1, 1, uni);
+    if (!n_other) throw P3dError("null argument");
+    fix_shape("fix_union", H, W);
+    fix_ids_check("fix_union", ids, capacity, B, M);
+    FixUnionRun u(pool, capacity, H, W, ids, B, M);
+    u.back(uni, prefix, n_other, "fix_union");
+    API_END
+}
+
+int p3d_debug_fix_select(int device, const uint64_t* pool, int capacity, int H, int W, const int* ids, int B, int M, const int* ranks,
+                         const int* n_rows, int n_rep, int* out) {
+    API_BEGIN
+    metric_args(device, pool, pool, 1, 1, out);
+    fix_shape("fix_select", H, W);
+    fix_ids_check("fix_select", ids, capacity, B, M);
+    FixUnionRun u(pool, capacity, H, W, ids, B, M);
+    std::vector<uint32_t> n_other((size_t)B);
+    std::vector<uint64_t> uni((size_t)B * u.nw);
+    u.back(uni.data(), nullptr, n_other.data(), "fix_select");
+    p3d_handle::shuffled_check_draws("fix_select", ranks, n_rows, n_other.data(), B, n_rep, 1.0);
+    std::vector<int> meta((size_t)B * 3, 0);
+    long long at = 0;
+    int max_rows = 0;
+    for (int b = 0; b < B; ++b) { meta[b * 3 + 2] = (int)at; at += (long long)n_rows[b] * n_rep; max_rows = std::max(max_rows, n_rows[b]); }
+    if (at < 1) throw P3dError("fix_select: no rank to select");
+    Guarded<int> dranks((size_t)at, 8, 0, ranks), dout((size_t)at, 8, 0, nullptr), dmeta(meta.size(), 8, 0, meta.data()), drows((size_t)B, 8, 0, n_rows);
+    FixSelectArgs q;
+    q.uni = u.a.uni; q.prefix = u.a.prefix; q.bsum = u.a.bsum; q.n_other = u.a.n_other; q.nw = u.nw; q.B = B; q.nsb = u.nsb; q.n_rep = n_rep;
+    q.max_rows = max_rows; q.meta = dmeta.data(); q.n_rows = drows.data(); q.ranks = dranks.data(); q.out = dout.data();
+    HIPCHECK(p3d_fix_select_launch(q, nullptr));
+    dout.back(out, "fix_select");
+    dranks.unchanged("fix_select"); dmeta.unchanged("fix_select"); drows.unchanged("fix_select");
+    std::vector<uint64_t> uni2(uni.size());
+    std::vector<uint32_t> n2((size_t)B);
+    u.back(uni2.data(), nullptr, n2.data(), "fix_select");      // the select reads the union: same words, guards intact
+    if (uni2 != uni || n2 != n_other) throw P3dError("fix_select: a launch wrote to a read-only buffer");
+    API_END
+}
+
+int p3d_debug_eval_maps_shuffled(int device, const float* maps, int n_maps, int h, int w, int elem_stride, const unsigned char* density,
+                                 int Hd, int Wd, const unsigned char* fixation, int H, int W, const double* jitter, const int* borji_idx,
+                                 const int* n_fix, int n_rep, double step_size, double* out, const p3d_postprocess* cfg,
+                                 const p3d_hist_match* match, int flags, const float* baseline, double* extra, const float* prior, int mode,
+                                 float a, const unsigned char* pool_maps, int capacity, const int* ids, int M, const int* ranks,
+                                 const int* n_rows, int sh_n_rep, double sh_step, uint32_t* n_other, double* per_rep) {
+    API_BEGIN
+    const MatchPlan mp = p3d_handle::match_parse(match);
+    metric_args(device, maps, maps, n_maps, 1, out);
+    if (h < 1 || w < 1 || elem_stride < 1) throw P3dError("eval: empty map");
+    if (flags && !extra) throw P3dError("null argument");
+    if (!pool_maps || !n_other || !per_rep) throw P3dError("null argument");
+    fix_shape("eval_shuffled", H, W);
+    if (capacity < 1 || capacity > 65535) throw P3dError("eval_shuffled: 1 .. 65535 pool maps");
+    fix_ids_check("eval_shuffled", ids, capacity, n_maps, M);
+    p3d_handle::prior_stage_check(mode, a);
+    if (mode != P3D_PRIOR_OFF || prior) p3d_handle::prior_map_check(prior, H, W);
+    p3d_handle::eval_extra_check(flags, baseline, H, W);
+    const long long per_map = (long long)h * w * elem_stride;
+    const bool ig = (flags & P3D_EVAL_INFO_GAIN) != 0;
+    DevArr<float> src((size_t)n_maps * per_map, maps), base(ig ? (size_t)H * W : 1), dprior(prior ? (size_t)H * W : 1, prior);
+    DevArr<double> bstat(3);
+    if (ig) p3d_handle::eval_extra_upload(baseline, H, W, base.p, bstat.p, nullptr, hipMemcpyHostToDevice);
+    const EvalExtra x{flags, ig ? base.p : nullptr, ig ? bstat.p : nullptr, H, W, extra};
+    const PriorStage pst{mode, a, dprior.p, H, W};
+    // the pool packed here, then the union: the launches the handle issues, on private buffers
+    const size_t N = (size_t)H * W, nw = (size_t)p3d_fix_words((long long)N);
+    DevArr<unsigned char> pm((size_t)capacity * N, pool_maps);
+    DevArr<unsigned long long> words((size_t)capacity * nw);
+    FixPackArgs pk;
+    pk.maps = pm.p; pk.n = capacity; pk.n_pix = (long long)N; pk.words = words.p;
+    HIPCHECK(p3d_fix_pack_launch(pk, nullptr));
+    std::vector<uint64_t> packed((size_t)capacity * nw);
+    words.get(reinterpret_cast<unsigned long long*>(packed.data()), packed.size());
+    FixUnionRun u(packed.data(), capacity, H, W, ids, n_maps, M);
+    std::vector<uint64_t> uni((size_t)n_maps * nw);
+    u.back(uni.data(), nullptr, n_other, "eval_shuffled");
+    const ShuffledEval sh{u.a.uni, u.a.prefix, u.a.bsum, u.a.n_other, n_other, (long long)nw, H, W, ranks, n_rows, sh_n_rep, sh_step, per_rep, nullptr};
+    eval_maps(nullptr, {src.p, per_map, elem_stride, n_maps, h, w}, nullptr, density, Hd, Wd, fixation, H, W, jitter, borji_idx, n_fix, n_rep,
+              step_size, out, nullptr, cfg, &mp, &x, &pst, &sh);
     API_END
 }
 

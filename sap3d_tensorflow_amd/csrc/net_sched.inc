@@ -810,6 +810,170 @@
         prior_mode = mode; prior_a = mode != P3D_PRIOR_OFF ? a : 0.f;
     }
 
+    // ---- fixation pool and shuffled AUC in the evaluation pass (p3d_fixpool_*, p3d_eval_shuffled_*; fixpool.hip) ---------------
+    // Nothing exists before p3d_fixpool_open, and while no p3d_eval_shuffled_draws has armed it an evaluation issues what it always
+    // issued.  The pool (one bit per pixel and slot), its staging buffer and the union's buffers of one batch are private
+    // allocations (freed by p3d_fixpool_close and the destructor; not part of `allocs`): no step, launch list or captured graph
+    // names them.  The host keeps which slots are filled.  The evaluation's part (select, clean moments, borji) is issued by
+    // eval_maps (net_abi.inc).
+    bool fp_is_open = false;
+    int fp_H = 0, fp_W = 0;
+    int64_t fp_cap = 0, fp_nw = 0;
+    unsigned long long* fp_words = nullptr;
+    std::vector<char> fp_filled;
+    unsigned char* fp_staging = nullptr; size_t fp_staging_bytes = 0;
+    double fp_pack_ms = 0.0, fp_union_ms = 0.0, fp_score_ms[2] = {0.0, 0.0};      // HIP events: last put's packs; last begin; last armed evaluation's select, moments + borji
+    // one batch's union (p3d_eval_shuffled_begin) and the draws that arm the next evaluation
+    int sh_B = 0, sh_M = 0; size_t sh_room = 0;
+    unsigned long long* sh_uni = nullptr; unsigned* sh_prefix = nullptr; unsigned* sh_bsum = nullptr; unsigned* sh_n_other_dev = nullptr;
+    unsigned* sh_counter = nullptr; int* sh_ids = nullptr;
+    bool sh_begun = false, sh_armed = false, sh_have = false;
+    std::vector<unsigned> sh_n_other;
+    std::vector<int> sh_ranks, sh_n_rows;
+    int sh_n_rep = 0; double sh_step = 0.1;
+    std::vector<double> sh_last;
+    void fixpool_need_open(const char* what) const {
+        if (!fp_is_open) throw P3dError(std::string(what) + ": no fixation pool is open (p3d_fixpool_open)");
+    }
+    void shuffled_free() {
+        for (void* p : {(void*)sh_uni, (void*)sh_prefix, (void*)sh_bsum, (void*)sh_n_other_dev, (void*)sh_counter, (void*)sh_ids}) if (p) hipFree(p);
+        sh_uni = nullptr; sh_prefix = nullptr; sh_bsum = nullptr; sh_n_other_dev = nullptr; sh_counter = nullptr; sh_ids = nullptr;
+        sh_room = 0; sh_B = sh_M = 0; sh_begun = sh_armed = sh_have = false;
+    }
+    void fixpool_close() {
+        for (void* p : {(void*)fp_words, (void*)fp_staging}) if (p) hipFree(p);
+        fp_words = nullptr; fp_staging = nullptr; fp_staging_bytes = 0; fp_filled.clear();
+        fp_is_open = false; fp_H = fp_W = 0; fp_cap = fp_nw = 0;
+        shuffled_free();
+    }
+    void fixpool_open(int H, int W, int64_t capacity) {
+        if (H < 1 || W < 1 || (long long)H * W > INT32_MAX / 2) throw P3dError("fixpool: maps are H x W bytes, 1 <= H * W <= 2^30");
+        if (capacity < 1 || capacity > INT32_MAX) throw P3dError("fixpool: a capacity of 1 .. 2^31 - 1 maps");
+        const int64_t nw = p3d_fix_words((long long)H * W);
+        unsigned long long* w = nullptr;
+        HIPCHECK(hipMalloc((void**)&w, (size_t)capacity * nw * sizeof(unsigned long long)));      // the new pool first: a failure changes nothing
+        fixpool_close();
+        fp_words = w; fp_is_open = true; fp_H = H; fp_W = W; fp_cap = capacity; fp_nw = nw;
+        fp_filled.assign((size_t)capacity, 0);
+    }
+    // maps [n][H][W] from the host into slots first .. first + n - 1, in uploads of at most 256 MB
+    void fixpool_put(int64_t first, const unsigned char* maps, int64_t n) {
+        fixpool_need_open("fixpool_put");
+        if (!maps) throw P3dError("null argument");
+        if (n < 1 || first < 0 || first > fp_cap - n)
+            throw P3dError("fixpool_put: slots " + std::to_string(first) + " .. " + std::to_string(first + n - 1) + " are not inside [0, " + std::to_string(fp_cap) + ")");
+        const size_t N = (size_t)fp_H * fp_W;
+        const int64_t per = std::min<int64_t>(65535, std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / N)));
+        const size_t want = (size_t)std::min(n, per) * N;
+        if (want > fp_staging_bytes) {
+            unsigned char* p = nullptr;
+            HIPCHECK(hipMalloc((void**)&p, want));
+            if (fp_staging) hipFree(fp_staging);
+            fp_staging = p; fp_staging_bytes = want;
+        }
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
+        double ms = 0.0;
+        hipError_t err = hipSuccess;
+        for (int64_t done = 0; done < n && err == hipSuccess; done += per) {
+            const int64_t cn = std::min(per, n - done);
+            FixPackArgs a;
+            a.maps = fp_staging; a.n = cn; a.n_pix = (long long)N; a.words = fp_words + (first + done) * fp_nw;
+            err = copy_now(fp_staging, maps + (size_t)done * N, (size_t)cn * N, hipMemcpyHostToDevice, stream);
+            if (err == hipSuccess) err = hipEventRecord(ev[0], stream);
+            if (err == hipSuccess) err = p3d_fix_pack_launch(a, stream);
+            if (err == hipSuccess) err = hipEventRecord(ev[1], stream);
+            if (err == hipSuccess) err = hipStreamSynchronize(stream);
+            float t = 0.f;
+            if (err == hipSuccess) err = hipEventElapsedTime(&t, ev[0], ev[1]);
+            ms += t;
+            if (err == hipSuccess) std::fill(fp_filled.begin() + (first + done), fp_filled.begin() + (first + done + cn), 1);
+        }
+        for (auto& e : ev) hipEventDestroy(e);
+        HIPCHECK(err);
+        fp_pack_ms = ms;
+    }
+    // ids [B][M]: every id a filled slot; 1 <= M <= 64
+    void fixpool_check_ids(const char* what, const int* ids, int B, int M) const {
+        fixpool_need_open(what);
+        if (!ids) throw P3dError("null argument");
+        if (M < 1 || M > 64) throw P3dError(std::string(what) + ": 1 .. 64 other maps per clip, not " + std::to_string(M));
+        for (int b = 0; b < B; ++b)
+            for (int m = 0; m < M; ++m) {
+                const int id = ids[(size_t)b * M + m];
+                if (id < 0 || id >= fp_cap) throw P3dError(std::string(what) + ": clip " + std::to_string(b) + ": slot " + std::to_string(id) + " is outside [0, " + std::to_string(fp_cap) + ")");
+                if (!fp_filled[(size_t)id]) throw P3dError(std::string(what) + ": clip " + std::to_string(b) + ": slot " + std::to_string(id) + " was never filled (p3d_fixpool_put)");
+            }
+    }
+    // the union, counts and scan of B rows of M slots into the handle's buffers; n_other_out [B]
+    void shuffled_begin(const int* ids, int B, int M, uint32_t* n_other_out) {
+        if (!n_other_out) throw P3dError("null argument");
+        fixpool_check_ids("eval_shuffled_begin", ids, B, M);
+        sh_begun = sh_armed = false;
+        const int nsb = p3d_fix_scan_blocks(fp_nw);
+        const size_t room = (size_t)B * fp_nw;
+        if (room > sh_room || B > sh_B || M > sh_M) {
+            const int nB = std::max(B, sh_B), nM = std::max(M, sh_M);
+            const size_t nroom = std::max(room, sh_room);
+            shuffled_free();
+            HIPCHECK(hipMalloc((void**)&sh_uni, nroom * sizeof(unsigned long long)));
+            HIPCHECK(hipMalloc((void**)&sh_prefix, nroom * sizeof(unsigned)));
+            HIPCHECK(hipMalloc((void**)&sh_bsum, (size_t)nB * nsb * sizeof(unsigned)));
+            HIPCHECK(hipMalloc((void**)&sh_n_other_dev, (size_t)nB * sizeof(unsigned)));
+            HIPCHECK(hipMalloc((void**)&sh_counter, (size_t)nB * sizeof(unsigned)));
+            HIPCHECK(hipMalloc((void**)&sh_ids, (size_t)nB * nM * sizeof(int)));
+            HIPCHECK(fill_now(sh_counter, 0, (size_t)nB * sizeof(unsigned), stream));
+            sh_room = nroom; sh_B = nB; sh_M = nM;
+        }
+        HIPCHECK(copy_now(sh_ids, ids, (size_t)B * M * sizeof(int), hipMemcpyHostToDevice, stream));
+        FixUnionArgs a;
+        a.pool = fp_words; a.nw = fp_nw; a.ids = sh_ids; a.B = B; a.M = M; a.nsb = nsb;
+        a.uni = sh_uni; a.prefix = sh_prefix; a.bsum = sh_bsum; a.n_other = sh_n_other_dev; a.counter = sh_counter;
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
+        hipError_t err = hipEventRecord(ev[0], stream);
+        if (err == hipSuccess) err = p3d_fix_union_launch(a, stream);
+        if (err == hipSuccess) err = hipEventRecord(ev[1], stream);
+        sh_n_other.assign((size_t)B, 0u);
+        if (err == hipSuccess) err = copy_now(sh_n_other.data(), sh_n_other_dev, (size_t)B * sizeof(unsigned), hipMemcpyDeviceToHost, stream);      // the one synchronisation
+        float t = 0.f;
+        if (err == hipSuccess) err = hipEventElapsedTime(&t, ev[0], ev[1]);
+        for (auto& e : ev) hipEventDestroy(e);
+        HIPCHECK(err);
+        fp_union_ms = t;
+        std::copy(sh_n_other.begin(), sh_n_other.end(), n_other_out);
+        sh_begun = true;
+    }
+    // ranks [sum n_rows[b]][n_rep]: refused before anything is kept when a row count or a rank exceeds the clip's n_other
+    static void shuffled_check_draws(const char* what, const int* ranks, const int* n_rows, const unsigned* n_other, int B, int n_rep, double step) {
+        if (!n_rows) throw P3dError("null argument");
+        if (n_rep < 1 || !(step > 0.0)) throw P3dError(std::string(what) + ": n_rep >= 1 and a positive step");
+        size_t at = 0;
+        for (int b = 0; b < B; ++b) {
+            if (n_rows[b] < 0 || (unsigned)n_rows[b] > n_other[b])
+                throw P3dError(std::string(what) + ": clip " + std::to_string(b) + ": " + std::to_string(n_rows[b]) + " rows, but the union holds " + std::to_string(n_other[b]) + " fixations");
+            const size_t n = (size_t)n_rows[b] * n_rep;
+            if (n > 0 && !ranks) throw P3dError("null argument");
+            for (size_t i = 0; i < n; ++i)
+                if (ranks[at + i] < 0 || (unsigned)ranks[at + i] >= n_other[b])
+                    throw P3dError(std::string(what) + ": clip " + std::to_string(b) + ": rank " + std::to_string(ranks[at + i]) + " is outside [0, " + std::to_string(n_other[b]) + ")");
+            at += n;
+            if (at > (size_t)INT32_MAX) throw P3dError(std::string(what) + ": too many ranks");
+        }
+    }
+    void shuffled_draws(const int* ranks, const int* n_rows, int n_rep, double step) {
+        fixpool_need_open("eval_shuffled_draws");
+        if (!sh_begun) throw P3dError("eval_shuffled_draws: no union is held (p3d_eval_shuffled_begin)");
+        const int B = (int)sh_n_other.size();
+        sh_armed = false;
+        shuffled_check_draws("eval_shuffled_draws", ranks, n_rows, sh_n_other.data(), B, n_rep, step);
+        size_t n = 0;
+        for (int b = 0; b < B; ++b) n += (size_t)n_rows[b] * n_rep;
+        sh_ranks.assign(ranks, ranks + n);
+        sh_n_rows.assign(n_rows, n_rows + B);
+        sh_n_rep = n_rep; sh_step = step; sh_armed = true;
+    }
+
     // ---- resident video inference (p3d_video_*; video.hip) ---------------------------------------------
     // Nothing exists before the first p3d_video_open and nothing here runs while no video is open.  The stores are private
     // allocations (freed by p3d_video_close, not part of `allocs`): no step, launch list or captured graph names them.  The gather
@@ -1405,6 +1569,7 @@
         eval_extra_free();
         prior_close();
         prior_map_take(nullptr, 0, 0);
+        fixpool_close();
         // the streams go back to the pool (net.hip, "stream pool"); every path here has synchronised the device or never launched
         if (side_stream) { if (side_pooled) give_stream(cfg.device, 1, side_stream); else hipStreamDestroy(side_stream); }
         for (void* p : allocs) hipFree(p);

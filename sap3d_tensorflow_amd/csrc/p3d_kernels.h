@@ -791,6 +791,7 @@ struct P3dFullMaps {
 struct P3dFullBorji {
     const int* idx = nullptr;        // random pixel indices [n_rand][n_rep] per map (at meta[b][2])
     int n_rand = -1;                 // -1: n_fix rows (AUC_Borji)
+    const int* n_rand_map = nullptr; // [n_maps] rows of every map instead of n_rand (device memory), or null
     int n_rep = 0;
     double step = 0.1;
     double* per_rep = nullptr;       // [n_maps][n_rep]
@@ -931,6 +932,53 @@ struct PriorApplyArgs {
 };
 LaunchDesc p3d_prior_apply_desc(const PriorApplyArgs& q);
 hipError_t p3d_prior_apply_launch(const PriorApplyArgs& q, hipStream_t s);
+
+// ---- fixation pool and shuffled AUC's sampling (fixpool.hip; p3d_fixpool_* / p3d_eval_shuffled_*, the law in include/p3d_hip.h) ---
+// Pack: n maps [n][n_pix] of bytes -> words [n][nw], nw = ceil(n_pix / 64): bit j of word k is set exactly when byte 64k + j of the
+// map is >= 128, the high bits of a map's last word are 0.  Every word has one writer and is stored whole.  maps may start at any
+// byte.  Refused (hipErrorInvalidValue): a null or misaligned buffer, n outside [1, 65535], n_pix outside [1, 2^30].
+constexpr int P3D_FIX_SCAN_WORDS = 256;                   // words per block of the union's scan: block seams at multiples of it
+struct FixPackArgs {
+    const unsigned char* maps = nullptr;      // [n][n_pix]
+    long long n = 0, n_pix = 0;
+    unsigned long long* words = nullptr;      // [n][nw]
+};
+__host__ __device__ inline long long p3d_fix_words(long long n_pix) { return (n_pix + 63) / 64; }
+LaunchDesc p3d_fix_pack_desc(const FixPackArgs& a);
+hipError_t p3d_fix_pack_launch(const FixPackArgs& a, hipStream_t s);
+// Union: uni[b][k] = OR over m < M of pool[ids[b][m]][k]; prefix[b][k] = the set bits of uni[b] in the words before k of k's scan
+// block (P3D_FIX_SCAN_WORDS words); bsum[b][j] = the set bits in the scan blocks before j; n_other[b] = all of them.  uint32
+// integer sums.  The last arriving block of a map (det_reduce.h's ticket on counter[b], zero at launch and after) scans the block
+// sums.  Refused: a missing buffer, B outside [1, 65535], M outside [1, 64], nsb != ceil(nw / P3D_FIX_SCAN_WORDS).  The ids are
+// the caller's to check.
+struct FixUnionArgs {
+    const unsigned long long* pool = nullptr; // [capacity][nw]
+    long long nw = 0;
+    const int* ids = nullptr;                 // [B][M] pool slots (device memory)
+    int B = 0, M = 0, nsb = 0;
+    unsigned long long* uni = nullptr;        // [B][nw]
+    unsigned* prefix = nullptr;               // [B][nw]
+    unsigned* bsum = nullptr;                 // [B][nsb]
+    unsigned* n_other = nullptr;              // [B]
+    unsigned* counter = nullptr;              // [B]
+};
+inline int p3d_fix_scan_blocks(long long nw) { return (int)((nw + P3D_FIX_SCAN_WORDS - 1) / P3D_FIX_SCAN_WORDS); }
+LaunchDesc p3d_fix_union_desc(const FixUnionArgs& a);
+hipError_t p3d_fix_union_launch(const FixUnionArgs& a, hipStream_t s);
+// Select: map b has n_rows[b] * n_rep ranks at ranks[meta[b][2] ..), row-major [n_rows][n_rep] (P3dFullMaps' meta: the random-index
+// offset); out[i] = the pixel index of the ranks[i]-th set bit of uni[b], np.nonzero(other)[0][rank].  A rank outside
+// [0, n_other[b]) is the caller's to refuse; the kernel writes 0 for it.
+struct FixSelectArgs {
+    const unsigned long long* uni = nullptr; const unsigned* prefix = nullptr; const unsigned* bsum = nullptr; const unsigned* n_other = nullptr;
+    long long nw = 0;
+    int B = 0, nsb = 0, n_rep = 0, max_rows = 0;          // max_rows: the largest n_rows (sizes the grid)
+    const int* meta = nullptr;                // [B][3]
+    const int* n_rows = nullptr;              // [B] (device memory)
+    const int* ranks = nullptr;
+    int* out = nullptr;
+};
+LaunchDesc p3d_fix_select_desc(const FixSelectArgs& a);
+hipError_t p3d_fix_select_launch(const FixSelectArgs& a, hipStream_t s);
 
 // ---- misc ---------------------------------------------------------------------------------------
 hipError_t p3d_add_inplace(float* dst, int lddst, const float* src, int ldsrc, long M, int C, hipStream_t s);

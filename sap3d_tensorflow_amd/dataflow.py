@@ -366,6 +366,60 @@ def apply_prior(maps, prior, mode="mul", a=0., offset=0, device=0):
     return out[0] if single else out
 
 
+def fixation_words(H, W):
+    """Words per packed fixation map: ceil(H * W / 64) (include/p3d_hip.h, STORE)."""
+    return (int(H) * int(W) + 63) // 64
+
+
+def pack_fixations(maps, offset=0, device=0):
+    """Test hook (p3d_debug_fix_pack): uint8 maps [n, H, W] or [H, W] -> uint64 [n, ceil(H W / 64)], bit j of word k set where byte
+    64 k + j is >= 128 (csrc/fixpool.hip's fix_pack_kernel); the maps start `offset` bytes past a 16-byte boundary."""
+    m = _u8_maps3(maps)
+    n, H, W = m.shape
+    out = np.empty((n, fixation_words(H, W)), np.uint64)
+    check(lib().p3d_debug_fix_pack(device, m.ctypes.data_as(C.POINTER(C.c_ubyte)), n, H, W, int(offset), out.ctypes.data_as(C.POINTER(C.c_uint64))))
+    return out
+
+
+def _pool_ids(words, size, others):
+    w = np.ascontiguousarray(words, dtype=np.uint64)
+    H, W = (size, size) if np.isscalar(size) else tuple(size)
+    if w.ndim != 2 or w.shape[1] != fixation_words(H, W):
+        raise ValueError("packed maps are uint64 [capacity, %d] for %d x %d maps" % (fixation_words(H, W), H, W))
+    ids = np.ascontiguousarray(others, dtype=np.int32)
+    if ids.ndim != 2:
+        raise ValueError("others is int [B, M]")
+    return w, int(H), int(W), ids
+
+
+def union_fixations(words, size, others, device=0):
+    """Test hook (p3d_debug_fix_union): for every row of others [B, M] (slots of the packed pool `words`, uint64 [capacity, nw]) the
+    OR of its maps -> (uni uint64 [B, nw], the exclusive prefix of the words' bit counts uint32 [B, nw], n_other uint32 [B])."""
+    w, H, W, ids = _pool_ids(words, size, others)
+    B, M = ids.shape
+    uni, prefix, n_other = np.empty((B, w.shape[1]), np.uint64), np.empty((B, w.shape[1]), np.uint32), np.empty(B, np.uint32)
+    u64, u32 = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+    check(lib().p3d_debug_fix_union(device, w.ctypes.data_as(u64), w.shape[0], H, W, ids.ctypes.data_as(C.POINTER(C.c_int)), B, M,
+                                    uni.ctypes.data_as(u64), prefix.ctypes.data_as(u32), n_other.ctypes.data_as(u32)))
+    return uni, prefix, n_other
+
+
+def select_fixations(words, size, others, ranks, n_rows, n_rep, device=0):
+    """Test hook (p3d_debug_fix_select): the union of every row of others, then the pixel index of every rank's set bit --
+    np.nonzero(other.ravel())[0][ranks].  ranks: int32, [n_rows[b], n_rep] per row, concatenated -> int32 of the same layout."""
+    w, H, W, ids = _pool_ids(words, size, others)
+    B, M = ids.shape
+    r = np.ascontiguousarray(ranks, dtype=np.int32).ravel()
+    rows = np.ascontiguousarray(n_rows, dtype=np.int32)
+    if rows.shape != (B,) or r.size != int(np.sum(rows.astype(np.int64))) * int(n_rep):
+        raise ValueError("ranks hold sum(n_rows) * n_rep entries, n_rows one per row of others")
+    out = np.empty(r.size, np.int32)
+    ip = C.POINTER(C.c_int)
+    check(lib().p3d_debug_fix_select(device, w.ctypes.data_as(C.POINTER(C.c_uint64)), w.shape[0], H, W, ids.ctypes.data_as(ip), B, M,
+                                     r.ctypes.data_as(ip), rows.ctypes.data_as(ip), int(n_rep), out.ctypes.data_as(ip)))
+    return out
+
+
 def postprocess_maps_both(maps, size, sigma=0., radius=0, norm="none", scale=255., device=0):
     """postprocess_maps with both outputs of one call -> (float32 [n, H, W], uint8 [n, H, W])."""
     m = np.ascontiguousarray(maps, dtype=np.float32)

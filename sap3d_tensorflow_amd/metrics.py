@@ -211,8 +211,30 @@ def eval_draws(fixation, jitter, n_rep, rng=None):
     return n_fix, jit, idx
 
 
+def shuffled_draws(n_fix, n_other, n_rep, rng=None):
+    """The numpy draws of shuffled AUC for one batch (include/p3d_hip.h, DRAW ORDER), the one place that makes them: per clip in
+    clip order, nothing for a clip with n_fix = 0, else for each of the n_rep splits in order rng.permutation(n_other)[:n_fix]
+    (utils/metrics.py:190), transposed to [min(n_fix, n_other), n_rep] (:191).
+    -> (ranks int32, the clips' rows concatenated row-major; n_rows int32 [B])."""
+    src = rng if rng is not None else np.random
+    n_fix = np.asarray(n_fix, dtype=np.int64).ravel()
+    n_other = np.asarray(n_other, dtype=np.int64).ravel()
+    if n_fix.shape != n_other.shape:
+        raise ValueError("one n_fix and one n_other per clip")
+    ranks, n_rows = [], np.zeros(len(n_fix), np.int32)
+    for b in range(len(n_fix)):
+        if n_fix[b] == 0:
+            continue
+        rows = [src.permutation(int(n_other[b]))[:int(n_fix[b])] for _ in range(n_rep)]
+        r = np.asarray(rows, dtype=np.int64).reshape(n_rep, -1).T
+        n_rows[b] = r.shape[0]
+        ranks.append(np.ascontiguousarray(r, dtype=np.int32).ravel())
+    ranks = np.ascontiguousarray(np.concatenate(ranks) if ranks else np.zeros(0, np.int32))
+    return ranks, n_rows
+
+
 def evaluate_maps(maps, density, fixation, size=None, jitter=True, n_rep=100, step_size=0.1, rng=None, device=0, postprocess=None,
-                  hist_match=None, nbins=256, extra=None, baseline=None, prior=None, prior_mode="off", prior_weight=0.):
+                  hist_match=None, nbins=256, extra=None, baseline=None, prior=None, prior_mode="off", prior_weight=0., shuffled=None):
     """Test hook (p3d_debug_eval_maps): P3DSession.evaluate's device pass on supplied maps instead of a session's prediction ->
     [n, 5] float64: CC, SIM, AUC_Judd, AUC_Borji, NSS.  maps: float32 [n, h, w], or [n, h, w, c] of which channel 0 is scored
     (the way the prediction buffer is addressed); density uint8 [n, Hd, Wd]; fixation uint8 [n, H, W] with (H, W) == size
@@ -224,7 +246,10 @@ def evaluate_maps(maps, density, fixation, size=None, jitter=True, n_rep=100, st
     `baseline` float32 [H, W] for the information gain; the result is then (the [n, 5] array, [n, 2] float64: KL, IG -- NaN for
     the one that is off).  prior (float32 [H, W]), prior_mode and prior_weight: P3DSession.set_prior_stage's stage after the
     blur (p3d_debug_eval_maps_prior); baseline="prior" scores the information gain over that prior, copied on the device.  With
-    a prior the result is always the pair."""
+    a prior the result is always the pair.  shuffled: dict(pool=uint8 [capacity, H, W] fixation maps, others=int [n, M] slots of it,
+    rng=..., n_rep=100, step_size=0.1[, n_other=...]) -- shuffled AUC of the clean scored map by the armed sequence
+    (p3d_debug_eval_maps_shuffled; shuffled_draws draws from `rng` after n_other is known: given, or taken by
+    dataflow.union_fixations); the result is then (out, xout, per_rep float64 [n, n_rep]), xout NaN where nothing is on."""
     m = np.ascontiguousarray(maps, dtype=np.float32)
     dens = np.ascontiguousarray(density)
     fix = np.ascontiguousarray(fixation)
@@ -246,6 +271,37 @@ def evaluate_maps(maps, density, fixation, size=None, jitter=True, n_rep=100, st
             dens.shape[1], dens.shape[2], fix.ctypes.data_as(u8), int(H), int(W),
             _dp(jit) if jit is not None else None, idx.ctypes.data_as(ip), n_fix.ctypes.data_as(ip),
             int(n_rep), float(step_size), _dp(out))
+    if shuffled is not None:
+        from . import dataflow
+        from .dataflow import _match_cfg, _post_cfg, _prior_mode
+        pool = np.ascontiguousarray(shuffled["pool"])
+        if pool.dtype != np.uint8 or pool.ndim != 3 or pool.shape[1:] != (H, W):
+            raise ValueError("the pool is uint8 [capacity, %d, %d]" % (H, W))
+        ids = np.ascontiguousarray(shuffled["others"], dtype=np.int32)
+        if ids.ndim != 2 or ids.shape[0] != n:
+            raise ValueError("others is int [%d, M]" % n)
+        s_rep, s_step = int(shuffled.get("n_rep", 100)), float(shuffled.get("step_size", 0.1))
+        n_other = shuffled.get("n_other")
+        if n_other is None:
+            n_other = dataflow.union_fixations(dataflow.pack_fixations(pool, device=device), (H, W), ids, device=device)[2]
+        if "ranks" in shuffled:                 # (tests of the refusals: ranks of the caller's, nothing drawn)
+            ranks, n_rows = (np.ascontiguousarray(v, dtype=np.int32) for v in (shuffled["ranks"], shuffled["n_rows"]))
+        else:
+            ranks, n_rows = shuffled_draws(n_fix, n_other, s_rep, shuffled.get("rng"))
+        flags = eval_extra_flags(extra) if extra is not None else 0
+        g = None if prior is None else np.ascontiguousarray(prior, dtype=np.float32)
+        base = None if baseline is None else np.ascontiguousarray(baseline, dtype=np.float32)
+        post = postprocess or {}
+        cfg = _post_cfg(post.get("sigma", 0.), post.get("radius", 0), post.get("norm", "none"))
+        mc, keep = _match_cfg(hist_match if hist_match is not None else "off", nbins)
+        xout = np.full((n, 2), np.nan, np.float64)
+        got_other, per_rep = np.empty(n, np.uint32), np.empty((n, s_rep), np.float64)
+        check(lib().p3d_debug_eval_maps_shuffled(*(args + (C.byref(cfg), C.byref(mc), flags, _fp(base) if base is not None else None,
+                                                           _dp(xout), _fp(g) if g is not None else None, _prior_mode(prior_mode, prior_weight),
+                                                           float(prior_weight), pool.ctypes.data_as(u8), pool.shape[0], ids.ctypes.data_as(ip),
+                                                           ids.shape[1], ranks.ctypes.data_as(ip), n_rows.ctypes.data_as(ip), s_rep, s_step,
+                                                           got_other.ctypes.data_as(C.POINTER(C.c_uint32)), _dp(per_rep)))))
+        return out, xout, per_rep
     if prior is not None:
         from .dataflow import _match_cfg, _post_cfg, _prior_mode
         flags = eval_extra_flags(extra) if extra is not None else 0

@@ -660,6 +660,66 @@ class P3DSession:
             return None
         return dict(mode=[k for k, v in _lib.PRIOR_MODES.items() if v == m.value][0], weight=a.value)
 
+    # ---- fixation pool and shuffled AUC in the evaluation pass (p3d_fixpool_*, p3d_eval_shuffled_*) ----------
+    def open_fixation_pool(self, size, capacity):
+        """A pool of `capacity` fixation maps of size = (H, W) on the device, one bit per pixel (an addition: the other clips'
+        fixations that shuffled AUC samples from -- evaluate(shuffled=...)).  include/p3d_hip.h holds the layout.  Training never
+        sees it."""
+        H, W = (size, size) if np.isscalar(size) else tuple(size)
+        check(lib().p3d_fixpool_open(self._h, int(H), int(W), int(capacity)))
+
+    def close_fixation_pool(self):
+        check(lib().p3d_fixpool_close(self._h))
+
+    def fixation_pool_info(self):
+        """dict(size=(H, W), capacity, words, filled) of the open pool."""
+        H, W = C.c_int(0), C.c_int(0)
+        cap, nw, nf = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        check(lib().p3d_fixpool_info(self._h, C.byref(H), C.byref(W), C.byref(cap), C.byref(nw), C.byref(nf)))
+        return dict(size=(H.value, W.value), capacity=cap.value, words=nw.value, filled=nf.value)
+
+    def fixation_pool_put(self, first, maps):
+        """uint8 fixation maps [n, H, W] or [H, W] (fixated where the byte is >= 128) into slots first .. first + n - 1."""
+        m = np.asarray(maps)
+        if m.dtype != np.uint8:
+            raise ValueError("fixation maps are uint8 images")
+        m = np.ascontiguousarray(m[None] if m.ndim == 2 else m)
+        if m.ndim != 3 or m.size == 0:
+            raise ValueError("expected [n, H, W] or [H, W] uint8 maps")
+        if m.shape[1:] != self.fixation_pool_info()["size"]:
+            raise ValueError("the maps are %s, the pool %s" % (m.shape[1:], self.fixation_pool_info()["size"]))
+        check(lib().p3d_fixpool_put(self._h, int(first), m.ctypes.data_as(_lib._u8p), m.shape[0]))
+
+    def fixation_pool_get(self, first, n):
+        """The packed words of slots first .. first + n - 1, uint64 [n, words] (for tests)."""
+        out = np.empty((max(int(n), 0), self.fixation_pool_info()["words"]), np.uint64)
+        check(lib().p3d_fixpool_get(self._h, int(first), int(n), out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out
+
+    def fixation_pool_last_ms(self):
+        """HIP-event times, ms: dict(pack: the last fixation_pool_put's launches, union: the last shuffled_begin's launch, select and
+        score: the select and the clean moments + borji of the last evaluate(shuffled=...))."""
+        ms = (C.c_double * 4)()
+        check(lib().p3d_fixpool_last_ms(self._h, ms))
+        return dict(pack=ms[0], union=ms[1], select=ms[2], score=ms[3])
+
+    def shuffled_begin(self, others):
+        """The union of the pool's maps others[b] (int [B, M], 1 <= M <= 64) for every clip of the batch, counted and scanned on the
+        device -> n_other uint32 [B], the only thing that comes back.  Does not depend on the prediction."""
+        ids = np.ascontiguousarray(others, dtype=np.int32)
+        if ids.ndim != 2 or ids.shape[0] != self.x_shape[0]:
+            raise ValueError("others is int [%d, M]" % self.x_shape[0])
+        n_other = np.empty(ids.shape[0], np.uint32)
+        check(lib().p3d_eval_shuffled_begin(self._h, ids.ctypes.data_as(_lib._ip), ids.shape[1], n_other.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return n_other
+
+    def last_eval_shuffled(self):
+        """(the means float64 [B] -- np.mean over the splits, as metrics.AUC_shuffled takes it --, the per-split areas [B, n_rep]) of
+        the last evaluate(shuffled=...)."""
+        out = np.empty((self.x_shape[0], getattr(self, "_shuffled_rep", 100)), np.float64)
+        check(lib().p3d_last_eval_shuffled(self._h, out.ctypes.data_as(_lib._dp), out.size))
+        return np.asarray([float(np.mean(r)) for r in out]), out
+
     # ---- moving average of the weights (p3d_set_ema) ---------------------------------------------------
     def set_ema(self, decay, warmup=False):
         """Keep an exponential moving average of every trainable variable, as tf.train.ExponentialMovingAverage(decay).apply(
@@ -878,7 +938,7 @@ class P3DSession:
         check(lib().p3d_backward(self._h, fptr(x), fptr(y), float(dropout), seed, C.byref(loss), fptr(pred)))
         return loss.value, pred
 
-    def evaluate(self, x, density, fixation, size=(1080, 960), jitter=True, n_rep=100, step_size=0.1, rng=None):
+    def evaluate(self, x, density, fixation, size=(1080, 960), jitter=True, n_rep=100, step_size=0.1, rng=None, shuffled=None):
         """The per-batch body of test.py (test.py:160-176) -> [B, 5] float64: CC, SIM, AUC_Judd, AUC_Borji, NSS of the last
         frame of every clip, scored at the fixation maps' resolution.  One plain batched forward with training False (:160:
         the backbone BatchNorm couples the clips of a batch, as in the reference), then one device pass that resizes the
@@ -888,7 +948,11 @@ class P3DSession:
         frame is used (:167-169).  numpy's stream (`rng`, default np.random, as utils/metrics.py draws) is consumed per clip
         in the reference's order: AUC_Judd's random.rand(H, W) (jitter=True, :64-65), then AUC_Borji's
         random.randint(0, H*W, [n_fix, n_rep]) (:139); a clip without fixation draws nothing (:56-59, :122-124).
-        Stage times of the call are left in `last_eval_ms` (forward, draws, h2d, device; milliseconds)."""
+        Stage times of the call are left in `last_eval_ms` (forward, draws, h2d, device; milliseconds).
+        shuffled (default None: nothing changes): dict(others=int [B, M] slots of the open fixation pool, rng=a RandomState of its
+        own, n_rep=100, step_size=0.1) adds shuffled AUC of the clean scored map in the same device pass: the union is taken
+        (shuffled_begin; skipped when the dict carries the n_other a caller's own shuffled_begin returned), metrics.shuffled_draws
+        draws from `rng`, and last_eval_shuffled() returns the result.  The five columns are the same bits either way."""
         import time
         H, W = (size, size) if np.isscalar(size) else tuple(size)
         B = self.x_shape[0]
@@ -909,6 +973,17 @@ class P3DSession:
         self.synchronize()
         t1 = time.perf_counter()
         n_fix, jit, idx = eval_draws(fix, bool(jitter), n_rep, rng)
+        if shuffled is not None:
+            from .metrics import shuffled_draws
+            n_other = shuffled["n_other"] if shuffled.get("n_other") is not None else self.shuffled_begin(shuffled["others"])
+            s_rep = int(shuffled.get("n_rep", 100))
+            if "ranks" in shuffled:             # (tests of the refusals: ranks of the caller's, nothing drawn)
+                ranks, n_rows = (np.ascontiguousarray(v, dtype=np.int32) for v in (shuffled["ranks"], shuffled["n_rows"]))
+            else:
+                ranks, n_rows = shuffled_draws(n_fix, n_other, s_rep, shuffled.get("rng"))
+            check(lib().p3d_eval_shuffled_draws(self._h, ranks.ctypes.data_as(_lib._ip), n_rows.ctypes.data_as(_lib._ip), s_rep,
+                                                float(shuffled.get("step_size", 0.1))))
+            self._shuffled_rep = s_rep
         t2 = time.perf_counter()
         out = np.empty((B, 5), np.float64)
         ms = (C.c_double * 2)()
