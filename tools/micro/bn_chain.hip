@@ -1,7 +1,8 @@
 // Micro-benchmark of the one-launch small-tensor BatchNorm (bn_small.hip) in the setting of a stage-3 bottleneck: NL
 // layers with their own tensors (cold: 300+ MB in rotation), each launch behind a small producer kernel that has just
 // written its input (as the conv / input-gradient kernel does in the net).  Prints us per BN launch = chain with BN
-// minus chain without.   P3D_BN_CB=4|8|16 ./bn_chain    (not part of the product or the tests)
+// minus chain without, and the grid of the BN launch.   P3D_BN_CB=4|8|16 P3D_BN_SPLIT=0|1 P3D_BN_XCD=0|1 ./bn_chain   (needs a -DP3D_TUNING build of
+// bn_small.hip for the three switches; not part of the product or the tests)
 #include "../../sap3d_tensorflow_amd/csrc/p3d_kernels.h"
 #include <cstdio>
 #include <cstdlib>
@@ -17,6 +18,9 @@ struct Layer { float *y1, *y2, *z, *dz, *dy1, *dy2, *par; };
 
 int main() {
     const int M = 784, NL = 96;
+    const int cb = getenv("P3D_BN_CB") ? atoi(getenv("P3D_BN_CB")) : 0;
+    const bool identity = getenv("P3D_BN_XCD") && atoi(getenv("P3D_BN_XCD")) == 0;
+    const bool split = !getenv("P3D_BN_SPLIT") || atoi(getenv("P3D_BN_SPLIT")) != 0;
     hipStream_t s; CK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     for (int C : {256, 1024}) {
@@ -44,7 +48,7 @@ int main() {
             a.dgamma1 = l.par + 8 * C + 4 * C; a.dbeta1 = a.dgamma1 + C; a.dgamma2 = a.dbeta1 + C; a.dbeta2 = a.dgamma2 + C;
             return a;
         };
-        for (int mode : {0, 1}) {
+        for (int mode : {0, 1, 3, 4}) {
             for (int bwd = 0; bwd < 2; ++bwd) {
                 float ms[2] = {0, 0};
                 for (int with_bn = 0; with_bn < 2; ++with_bn) {
@@ -59,8 +63,11 @@ int main() {
                         CK(hipEventElapsedTime(&ms[with_bn], e0, e1));
                     }
                 }
-                printf("C=%4d mode %d %s: %.2f us per BN launch (producer-only chain %.2f us per launch)\n", C, mode, bwd ? "bwd" : "fwd",
-                       (ms[1] - ms[0]) * 1e3 / NL, ms[0] * 1e3 / NL);
+                char grid[32] = "rule";
+                const int w = (cb == 4 || cb == 8 || cb == 16) ? cb : (C >= 512 && mode != 3 && mode != 2) ? 16 : 8;      // dispatch()'s slab
+                snprintf(grid, sizeof(grid), "%d (order of %d-channel slabs)", C / (split ? 4 : w), w);
+                printf("C=%4d mode %d %s slabs %s grid %s: %.2f us per BN launch (producer-only chain %.2f us per launch)\n", C, mode,
+                       bwd ? "bwd" : "fwd", identity ? "identity" : "xcd", grid, (ms[1] - ms[0]) * 1e3 / NL, ms[0] * 1e3 / NL);
             }
         }
         for (auto& l : L) for (float* p : {l.y1, l.y2, l.z, l.dz, l.dy1, l.dy2, l.par}) CK(hipFree(p));
