@@ -28,6 +28,13 @@ sap3d_tensorflow_amd.synthetic.synthetic_fixations of the target).
 Checkpoints are TensorFlow-1.x V2 bundles `model/<info>/p3d_<step>.ckpt.*` with a `checkpoint` state file, keyed by the
 TF variable names of train.py:180-185 (trainables + BN moving statistics): the files the reference's Saver writes and
 restores (sap3d_tensorflow_amd/tf_checkpoint.py); `--pretrain` takes such a directory, a bundle prefix, or an .npz.
+`--video-data set.npz` [addition] trains from whole videos kept on the device instead of pre-cut clips (P3DSession.open_trainset):
+arrays frames uint8 [sum F,H0,W0,3] RGB, density uint8 [sum F,Hd,Wd], optionally fix uint8 [sum F,Hf,Wf], and video_frames int [V].  The
+clip list is VideoDataset.setup_video_dataset_p3d's (dataflow.py:39-62; sap3d_tensorflow_amd.dataflow.clip_tuples / split_clips):
+`--videolength`, `--overlap`, `--trainingprops` mean what they mean there and `--skip-head` is its skip_head; every epoch is a fresh
+permutation of the training tuples; training runs through P3DSession.trainset_step, the eval forward and the validation pass over
+the held-out tuples through trainset_forward.  `--trainset-format u8 | f32` picks the frame store (default: u8 for frames
+already at --imagesize, else f32).
 Every `--validiter` steps the validation pass of train.py:243-264 runs: eval forward over the validation clips, CC / SIM /
 AUC_Judd of the LAST frame of every clip (GPU kernels, sap3d_tensorflow_amd.metrics), NaNs dropped, means printed."""
 import argparse
@@ -67,6 +74,14 @@ def get_arguments():
     p.add_argument("--overlap", type=int, default=15)
     p.add_argument("--imagesize", type=int, nargs=2, default=(112, 112), help="clip height width (train.py:34)")
     p.add_argument("--data", type=str, default="", help="npz with x, y; empty = synthetic clips")
+    p.add_argument("--video-data", type=str, default="",
+                   help="[addition] npz of whole videos kept on the device (P3DSession.open_trainset): frames uint8 [sum F,H0,W0,3] RGB, "
+                        "density uint8 [sum F,Hd,Wd], optional fix uint8 [sum F,Hf,Wf], video_frames int [V]; clips are cut there by "
+                        "--videolength / --overlap / --skip-head / --trainingprops (dataflow.py:39-62).  Not with --data")
+    p.add_argument("--skip-head", type=int, default=11, help="[--video-data] first frame of a video's first clip (dataflow.py:39 skip_head)")
+    p.add_argument("--trainset-format", choices=("u8", "f32"), default=None,
+                   help="[--video-data] frame store: u8 (3 bytes per pixel; frames already at --imagesize) or f32 (normalised floats, "
+                        "any source size); default u8 where it applies")
     p.add_argument("--steps", type=int, default=20, help="steps per epoch when synthetic")
     p.add_argument("--validclips", type=int, default=4, help="validation batches per validation pass when synthetic")
     # not a reference flag (its flags are train.py:21-45): the loss option of P3DSession.set_loss
@@ -198,13 +213,99 @@ def validation_batches(args):
             yield law.synthetic_clip(500_000 + s, shape + (3,)), law.synthetic_target(600_000 + s, shape)
 
 
-def validate(sess, args, step):
+PUT_CHUNK = 256      # frames per put of --video-data
+
+
+def video_clips(args, video_frames, rng):
+    """The training and validation tuples of --video-data: dataflow.py:39-62 with --videolength, --overlap, --skip-head and
+    --trainingprops, shuffled from `rng`."""
+    from sap3d_tensorflow_amd import dataflow
+    tuples = dataflow.clip_tuples([int(f) for f in video_frames], args.videolength, args.overlap, args.skip_head)
+    return dataflow.split_clips(tuples, args.trainingprops, rng)
+
+
+def video_batches(train, args, rng):
+    """A list of --batch (video, start) tuples per batch: every epoch a fresh permutation of the training tuples from `rng`, the
+    remainder dropped."""
+    for e in range(args.epoch):
+        order = rng.permutation(len(train))
+        for i in range(0, len(train) - args.batch + 1, args.batch):
+            yield [train[j] for j in order[i:i + args.batch]]
+
+
+class VideoData:
+    """--video-data: the set on the session's device and the clip lists.  `rng` is the driver's: the split draws from it first,
+    then every epoch's permutation."""
+
+    def __init__(self, sess, args, rng):
+        from sap3d_tensorflow_amd import dataflow
+        d = np.load(args.video_data)
+        for k in ("frames", "density", "video_frames"):
+            if k not in d:
+                raise SystemExit("--video-data: no `%s` array" % k)
+        frames, density, counts = d["frames"], d["density"], [int(f) for f in d["video_frames"]]
+        H, W = args.imagesize
+        total = sum(counts)
+        if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[3] != 3 or len(frames) != total:
+            raise SystemExit("--video-data: frames are %s %s, expected uint8 [%d,H0,W0,3]" % (frames.dtype, frames.shape, total))
+        if density.dtype != np.uint8 or density.ndim != 3 or len(density) != total:
+            raise SystemExit("--video-data: density is %s %s, expected uint8 [%d,Hd,Wd]" % (density.dtype, density.shape, total))
+        grid = frames.shape[1:3] == (H, W)
+        fmt = args.trainset_format or ("u8" if grid else "f32")
+        if fmt == "u8" and not grid:
+            raise SystemExit("--trainset-format u8 takes frames already at --imagesize %d %d, not %d x %d" % ((H, W) + frames.shape[1:3]))
+        fix = None
+        if with_fixations(args):
+            if "fix" not in d:
+                raise SystemExit("--loss %s with --nss-weight %g needs fixation maps: --video-data has no `fix`" % (args.loss, args.nss_weight))
+            fix = d["fix"]
+            if fix.dtype != np.uint8 or fix.ndim != 3 or len(fix) != total:
+                raise SystemExit("--video-data: fix is %s %s, expected uint8 [%d,Hf,Wf]" % (fix.dtype, fix.shape, total))
+        self.sess, self.args, self.density, self.size = sess, args, density, (H, W)
+        self.base = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        sess.open_trainset(counts, frame_format=fmt, fixations=fix is not None)
+        for v, n in enumerate(counts):
+            for i in range(0, n, PUT_CHUNK):
+                a, b = int(self.base[v]) + i, int(self.base[v]) + min(i + PUT_CHUNK, n)
+                sess.trainset_put_frames_u8(v, i, frames[a:b, ..., ::-1])          # the set takes cv2's BGR order, the npz is RGB
+                sess.trainset_put_density_u8(v, i, density[a:b])
+                if fix is not None:
+                    f = fix[a:b]
+                    sess.trainset_put_fixations(v, i, f if f.shape[1:] == (H, W) else dataflow.fixations_to_grid(f, H, W))
+        self.train, self.valid = video_clips(args, counts, rng)
+        self.per_epoch = len(range(0, len(self.train) - args.batch + 1, args.batch))
+        info = sess.trainset_info()
+        print("Training set on the device:", info["videos"], "videos,", info["total_frames"], "frames,", info["frame_format"], "frames,",
+              info["bytes"], "bytes;", len(self.train), "training clips,", len(self.valid), "validation clips")
+
+    def batches(self, rng):
+        """(clips, None, None) per batch, in batches()'s shape."""
+        for clips in video_batches(self.train, self.args, rng):
+            yield clips, None, None
+
+    def last_density(self, clips):
+        """The ground truth of the last frame of every clip, float32 [n,H,W] (dataflow.py:210-214)."""
+        from sap3d_tensorflow_amd import dataflow
+        at = [int(self.base[v]) + s + self.args.videolength - 1 for v, s in clips]
+        return dataflow.mapf_density(self.density[at], self.size, device=int(self.args.gpu))
+
+    def validation_batches(self):
+        """(prediction, ground truth) of the last frames per batch of held-out tuples, the remainder dropped."""
+        for i in range(0, len(self.valid) - self.args.batch + 1, self.args.batch):
+            clips = self.valid[i:i + self.args.batch]
+            yield self.sess.trainset_forward(clips)[:, -1, ..., 0], self.last_density(clips)
+
+
+def validate(sess, args, step, video=None):
     """train.py:243-264: CC, SIM, AUC_Judd between the last predicted frame and the last ground-truth frame of every
-    validation clip; NaNs (no fixation, flat map) are dropped before averaging."""
+    validation clip; NaNs (no fixation, flat map) are dropped before averaging.  video: the --video-data set, whose held-out
+    tuples are scored instead."""
     from sap3d_tensorflow_amd import metrics
     print("Doing validation...")
     preds, gts = [], []
-    for xs, ys in validation_batches(args):
+    for p_, g_ in (video.validation_batches() if video is not None else ()):
+        preds.append(p_); gts.append(g_)
+    for xs, ys in (validation_batches(args) if video is None else ()):
         image0 = sess.forward(xs, dropout=0.0, training=False)[..., 0]              # train.py:250-251
         preds.append(image0[:, -1]); gts.append(ys[:, -1])                          # prediction[-1], ground_truth[-1]
     if not preds:
@@ -225,6 +326,8 @@ def scoring(sess, ema):
 def main():
     args = get_arguments()
     from sap3d_tensorflow_amd import P3dError, P3DSession
+    if args.video_data and args.data:
+        raise SystemExit("--video-data and --data exclude each other")
     gn_nets = {"P3D": "gn_p3d", "P3D_CONCAT": "gn_p3d_concat", "P3D_DECODER": "gn_p3d_decoder"}     # gn/train_p3d_gn_dataset.py:169-180
     gn = args.normalization.lower() == "gn"
     if gn and args.net not in gn_nets:
@@ -309,11 +412,22 @@ def main():
     print("Start training")
     step = 0                  # optimiser updates
     micro = 0                 # batches seen: `step` itself unless --accum-steps
-    per_epoch = batches_per_epoch(args) if accum > 1 else 0
+    rng = np.random.default_rng(0)
+    video = None
+    if args.video_data:
+        try:
+            video = VideoData(sess, args, rng)
+        except (P3dError, ValueError) as e:
+            sess.close()
+            raise SystemExit("--video-data: %s" % e)
+    per_epoch = (video.per_epoch if video else batches_per_epoch(args)) if accum > 1 else 0
     loss = 0.0
-    for xs, ys, fs in batches(args, np.random.default_rng(0)):
+    for xs, ys, fs in (video.batches(rng) if video else batches(args, rng)):
         micro += 1
-        loss += sess.train_step(xs, ys, dropout=0.5, seed=micro, fixations=fs)      # train.py:217-218
+        if video:
+            loss += sess.trainset_step(xs, dropout=0.5, seed=micro)                 # xs: the batch's (video, start) tuples
+        else:
+            loss += sess.train_step(xs, ys, dropout=0.5, seed=micro, fixations=fs)  # train.py:217-218
         if accum > 1 and sess.grad_accum[1] != 0:
             if micro % per_epoch == 0:      # an incomplete cycle does not cross the epoch (the loaders' remainder=False)
                 sess.set_grad_accum(accum)
@@ -328,12 +442,15 @@ def main():
                 t = sess.last_loss_terms()
                 clip += ("KLD", "%.9g" % t["kld"], "CC", "%.9g" % t["cc"], "NSS", "%.9g" % t["nss"], "SIM", "%.9g" % t["sim"])
             with scoring(sess, ema):
-                image = sess.forward(xs, dropout=0.0, training=False)               # train.py:225-226; uploads xs again: the clip as given
+                if video:
+                    image, truth = sess.trainset_forward(xs), video.last_density(xs[:1])[0]      # cut again: the clip as stored
+                else:
+                    image, truth = sess.forward(xs, dropout=0.0, training=False), ys[0][-1]     # train.py:225-226; uploads xs again: the clip as given
             print("Datetime", datetime.datetime.now().isoformat()[:-7], "Training step:", step,
-                  float(np.sum(image[0, -1]) * 255.0), float(np.sum(ys[0][-1]) * 255.0), "Training Loss", loss, *clip)
+                  float(np.sum(image[0, -1]) * 255.0), float(np.sum(truth) * 255.0), "Training Loss", loss, *clip)
         if step % args.validiter == 0:
             with scoring(sess, ema):
-                validate(sess, args, step)                                          # train.py:243-264
+                validate(sess, args, step, video)                                   # train.py:243-264
         if step % args.saveiter == 0:
             sess.save_checkpoint(model_dir, step, keep=10, optimizer_state=args.optimizer_state, ema=ema)     # train.py:180-185,266-267
         loss = 0.0

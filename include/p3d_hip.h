@@ -1300,6 +1300,83 @@ int p3d_debug_video_temporal_plan(int kind, int r, int64_t hw, int n, int* pixel
 int p3d_debug_video_temporal_desc(int mode, const p3d_video_temporal* cfg, int F, int64_t hw, int first, int n, char* kernel, int cap,
                                   double* flops, double* bytes);
 
+/* ---- Resident training set (an ADDITION beside p3d_upload_inputs: the reference's loader, dataflow.py:39-62, cuts clips that
+ * share overlap of video_length frames on the host and keeps nothing on the device).  The decoded frames, density maps and fixation
+ * maps of V videos go up once; a batch of B clips, each a (video, start) pair, is cut where they are, into the staged x, y and
+ * fixation buffers a train step reads, normalising on the way.  OFF until p3d_trainset_open: while no set is open every other entry
+ * point issues what it issued before and returns the same bits, and nothing is allocated.  No step, launch list or captured graph
+ * names the stores, a captured step graph survives every call here, checkpoints store nothing of the set, a resident video and a
+ * training set may be open together, and with world_size > 1 the set is local to the rank.
+ * T, H, W, B below are the handle's frames, height, width and batch; F_v is video v's frames; the videos are concatenated, video v's
+ * frames at base[v] = F_0 + .. + F_{v-1}.
+ *
+ * STORES (tests/trainset_ref.py replays every rule below in numpy bit for bit):
+ *   frames     one format per set.  P3D_TRAINSET_FRAMES_U8: 3 bytes per grid pixel, the decoded bytes as put; takes only frames decoded
+ *              at H x W.  P3D_TRAINSET_FRAMES_F32: the floats p3d_mapf_frames returns, for any source size.
+ *   density    one byte per grid pixel: the byte v of p3d_mapf_density's 8-bit resize (a copy when the sizes agree), y = v / 255.
+ *   fixations  one byte per grid pixel; exists only in a set opened with P3D_TRAINSET_FIXATIONS.
+ *   and a put flag per frame and tensor, on the host.
+ *
+ * p3d_trainset_open   allocates the stores for n_videos videos of frames[v] >= 1 frames each on the handle's device and clears every
+ *                     put flag.  mean_rgb: the channel means every frame is normalised with.  Opening again replaces the set; an
+ *                     allocation that is large enough is reused.  Refused (-1, nothing changed): no video, a video without frames,
+ *                     more than 2^31 - 1 frames, an unknown format or flag, a mean that is not finite, no device memory.
+ * p3d_trainset_close  frees the stores.
+ * p3d_trainset_info   V, the frames of all videos, the format, the flags and the bytes of the stores; any pointer may be NULL; refused
+ *                     while no set is open, like every call below.  p3d_trainset_video_info: F_v and how many of its frames were put,
+ *                     per tensor.
+ * p3d_trainset_put_frames_u8   n decoded frames bgr [n][H0][W0][3] (cv2's order) -> frames first .. first + n - 1 of `video`.  U8 sets
+ *                     keep the bytes (H0 x W0 must be H x W); F32 sets keep p3d_mapf_frames(bgr, H0, W0, mean_rgb, H, W).
+ * p3d_trainset_put_frames      F32 sets only: n normalised frames x [n][H][W][3], a copy.
+ * p3d_trainset_put_density_u8  n grey maps [n][H0][W0] -> the bytes of p3d_mapf_density's resize to H x W.
+ * p3d_trainset_put_fixations   n maps [n][H][W] on the grid, a copy of the bytes (fixated where >= 128, as p3d_upload_fixations).
+ *                     A put outside its video, or one the set's format or flags exclude, is refused with nothing changed.
+ * p3d_trainset_stage  clip k = frames start[k] .. start[k] + T - 1 of video[k], k < n == B:
+ *                       staged x   = p3d_mapf_frames of the clip's frames, bit for bit (U8 sets, per channel c of RGB:
+ *                                    __fdiv_rn(__fsub_rn((float)bgr[2 - c], mean_rgb[c]), 255.f), which is that kernel at equal sizes)
+ *                       staged y   = p3d_mapf_density of the clip's maps: (float)((double)v / 255.0)
+ *                       staged fixations = the bytes, exactly when the set has them; that counts as the p3d_upload_fixations
+ *                                    p3d_train_step_device asks for, and allocates that buffer on first use as the first upload does.
+ *                     Validated first: n == B, every video in [0, V), every start in [0, F_v - T], every frame of every clip put in
+ *                     every tensor the call writes.  Else -1, p3d_last_error names the first offending clip or frame, nothing is
+ *                     launched and nothing changes.  One launch; the staged buffers keep their addresses; returns synchronised.  Each
+ *                     call overwrites the staged input, as p3d_upload_inputs does.
+ * p3d_trainset_step   p3d_trainset_stage, p3d_augment_inputs(seed) under p3d_set_augment, p3d_train_step_device(dropout, seed),
+ *                     p3d_last_loss: the loss and every weight, slot, moving statistic and shadow equal those after p3d_train_step (with
+ *                     p3d_upload_fixations where the loss reads them) on host clips built through p3d_mapf_frames / p3d_mapf_density.
+ *                     Under p3d_set_grad_accum each call is one micro-step.  Refused with nothing changed when the loss reads fixations
+ *                     (P3D_LOSS_SALIENCY with w_nss > 0) and the set has none, and wherever the stage or p3d_train_step refuses.
+ * p3d_trainset_forward  stages x only (density and fixations need not be put), then p3d_forward's pass with training off and
+ *                     dropout 0 -> pred, as p3d_forward returns it for the host-built clips.
+ * p3d_trainset_get_staged  reads the staged buffers back: x [B][T][H][W][3], y [B][T][H][W], fix [B][T][H][W]; any may be NULL.
+ * p3d_trainset_last_ms  HIP-event time of the last stage's launch (p3d_trainset_stage / _step / _forward), milliseconds.
+ *
+ * Test hook.  p3d_debug_trainset_gather: the launch from the launch description the handle uses, on host stores of n_videos videos
+ * (frames_store: bytes for format U8, floats for F32; density_store / fix_store [sum F][hw] bytes, either may be NULL with its
+ * output) -> x [B][T][hw][3], y, fix.  Every device buffer sits `offset` (0 .. 3) elements past a 16-byte boundary between guard
+ * elements; -1 if a guard or a store changed, or if the launch wrapper refused the table (a row outside its video).  first: NULL,
+ * or the rows' first frames in the concatenation as the caller computed them (the wrapper refuses a row that is not
+ * base[video] + start). */
+enum { P3D_TRAINSET_FRAMES_U8 = 0, P3D_TRAINSET_FRAMES_F32 = 1 };
+#define P3D_TRAINSET_FIXATIONS 1
+int p3d_trainset_open(p3d_handle* h, int n_videos, const int* frames, int frame_format, int flags, const float mean_rgb[3]);
+int p3d_trainset_close(p3d_handle* h);
+int p3d_trainset_info(p3d_handle* h, int* n_videos, int64_t* total_frames, int* frame_format, int* flags, int64_t* bytes);
+int p3d_trainset_video_info(p3d_handle* h, int video, int* frames, int* put_frames, int* put_density, int* put_fixations);
+int p3d_trainset_put_frames_u8(p3d_handle* h, int video, int first, const unsigned char* bgr, int n, int H0, int W0);
+int p3d_trainset_put_frames(p3d_handle* h, int video, int first, const float* x, int n);
+int p3d_trainset_put_density_u8(p3d_handle* h, int video, int first, const unsigned char* grey, int n, int H0, int W0);
+int p3d_trainset_put_fixations(p3d_handle* h, int video, int first, const unsigned char* fix, int n);
+int p3d_trainset_stage(p3d_handle* h, const int* video, const int* start, int n);
+int p3d_trainset_step(p3d_handle* h, const int* video, const int* start, int n, float dropout_rate, uint64_t seed, float* loss);
+int p3d_trainset_forward(p3d_handle* h, const int* video, const int* start, int n, float* pred);
+int p3d_trainset_get_staged(p3d_handle* h, float* x, float* y, unsigned char* fix);
+int p3d_trainset_last_ms(p3d_handle* h, double* ms);
+int p3d_debug_trainset_gather(int device, int frame_format, const void* frames_store, const unsigned char* density_store,
+                              const unsigned char* fix_store, int n_videos, const int* frames, int T, int64_t hw, const float mean_rgb[3],
+                              const int* video, const int* start, const int* first, int B, int offset, float* x, float* y,
+                              unsigned char* fix);
+
 /* CRC-32C of a host buffer (host-side helper of the TensorFlow checkpoint reader / writer, sap3d_tensorflow_amd/tf_checkpoint.py:
  * the bundle format of train.py:180-185,266-267 checksums every tensor); crc = running value, 0 to start. */
 uint32_t p3d_crc32c(const void* data, size_t n, uint32_t crc);

@@ -64,6 +64,9 @@ P3D_HIST_MAX_BINS = 1024
 EVAL_EXTRA = {"kldiv": 1, "info_gain": 2}
 # p3d_video_open modes (include/p3d_hip.h P3D_VIDEO_*)
 VIDEO_MODES = {"newest": 0, "mean": 1}
+# p3d_trainset_open frame formats and flags (include/p3d_hip.h P3D_TRAINSET_*)
+TRAINSET_FORMATS = {"u8": 0, "f32": 1}
+P3D_TRAINSET_FIXATIONS = 1
 # p3d_set_video_temporal kinds (include/p3d_hip.h P3D_TEMPORAL_*)
 TEMPORAL_KINDS = {"off": 0, "gauss": 1, "ema": 2}
 P3D_TEMPORAL_MAX_RADIUS = 24
@@ -354,6 +357,21 @@ SIGNATURES = {
     "p3d_debug_video_temporal_plan": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int, _ip, _ip, _ip]),
     "p3d_debug_video_temporal_desc": (C.c_int, [C.c_int, C.POINTER(P3dVideoTemporal), C.c_int, C.c_int64, C.c_int, C.c_int, C.c_char_p, C.c_int,
                                                 _dp, _dp]),
+    "p3d_trainset_open": (C.c_int, [C.c_void_p, C.c_int, _ip, C.c_int, C.c_int, _fp]),
+    "p3d_trainset_close": (C.c_int, [C.c_void_p]),
+    "p3d_trainset_info": (C.c_int, [C.c_void_p, _ip, _i64p, _ip, _ip, _i64p]),
+    "p3d_trainset_video_info": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip, _ip, _ip]),
+    "p3d_trainset_put_frames_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, C.c_int]),
+    "p3d_trainset_put_frames": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _fp, C.c_int]),
+    "p3d_trainset_put_density_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, C.c_int]),
+    "p3d_trainset_put_fixations": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _u8p, C.c_int]),
+    "p3d_trainset_stage": (C.c_int, [C.c_void_p, _ip, _ip, C.c_int]),
+    "p3d_trainset_step": (C.c_int, [C.c_void_p, _ip, _ip, C.c_int, C.c_float, C.c_uint64, _fp]),
+    "p3d_trainset_forward": (C.c_int, [C.c_void_p, _ip, _ip, C.c_int, _fp]),
+    "p3d_trainset_get_staged": (C.c_int, [C.c_void_p, _fp, _fp, _u8p]),
+    "p3d_trainset_last_ms": (C.c_int, [C.c_void_p, _dp]),
+    "p3d_debug_trainset_gather": (C.c_int, [C.c_int, C.c_int, C.c_void_p, _u8p, _u8p, C.c_int, _ip, C.c_int, C.c_int64, _fp, _ip, _ip, _ip,
+                                            C.c_int, C.c_int, _fp, _fp, _u8p]),
     "p3d_crc32c": (C.c_uint32, [C.c_void_p, C.c_size_t, C.c_uint32]),
     "p3d_shutdown": (C.c_int, []),
 }

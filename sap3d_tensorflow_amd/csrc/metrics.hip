@@ -327,7 +327,9 @@ __device__ __forceinline__ void lin_coef_u8(int d, double scale, int extent, boo
     w1 = __float2int_rn(__fmul_rn(f, 2048.f));
     s0 = min(max(sx, 0), extent - 1); s1 = min(max(sx + 1, 0), extent - 1);
 }
-__global__ __launch_bounds__(TPB) void mapf_density_kernel(const unsigned char* src, int n_frames, int H0, int W0, float* dst, int H, int W) {
+// OUT float: y = v / 255.; OUT unsigned char: the byte v itself (the training set's density store, trainset.hip divides at the gather)
+template <typename OUT>
+__global__ __launch_bounds__(TPB) void mapf_density_kernel(const unsigned char* src, int n_frames, int H0, int W0, OUT* dst, int H, int W) {
     const double sx = (double)W0 / W, sy = (double)H0 / H;
     const bool same = H0 == H && W0 == W;                 // cv::resize copies when the sizes agree
     const long long total = (long long)n_frames * H * W;
@@ -348,7 +350,8 @@ __global__ __launch_bounds__(TPB) void mapf_density_kernel(const unsigned char* 
             v = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2;
             v = min(max(v, 0), 255);
         }
-        dst[i] = (float)((double)v / 255.0);              // numpy: uint8 / 255. is float64, then fed as float32
+        if constexpr (sizeof(OUT) == 1) dst[i] = (OUT)v;
+        else dst[i] = (float)((double)v / 255.0);         // numpy: uint8 / 255. is float64, then fed as float32
     }
 }
 
@@ -392,6 +395,12 @@ hipError_t p3d_mapf_frames(const unsigned char* bgr, int n_frames, int H0, int W
 hipError_t p3d_mapf_density(const unsigned char* grey, int n_frames, int H0, int W0, float* dst, int H, int W, hipStream_t s) {
     const long long total = (long long)n_frames * H * W;
     const unsigned grid = (unsigned)((total + TPB - 1) / TPB > 65535 ? 65535 : (total + TPB - 1) / TPB);
-    hipLaunchKernelGGL(mapf_density_kernel, dim3(grid), dim3(TPB), 0, s, grey, n_frames, H0, W0, dst, H, W);
+    hipLaunchKernelGGL(mapf_density_kernel<float>, dim3(grid), dim3(TPB), 0, s, grey, n_frames, H0, W0, dst, H, W);
+    return hipGetLastError();
+}
+hipError_t p3d_mapf_density_u8(const unsigned char* grey, int n_frames, int H0, int W0, unsigned char* dst, int H, int W, hipStream_t s) {
+    const long long total = (long long)n_frames * H * W;
+    const unsigned grid = (unsigned)((total + TPB - 1) / TPB > 65535 ? 65535 : (total + TPB - 1) / TPB);
+    hipLaunchKernelGGL(mapf_density_kernel<unsigned char>, dim3(grid), dim3(TPB), 0, s, grey, n_frames, H0, W0, dst, H, W);
     return hipGetLastError();
 }

@@ -4510,6 +4510,220 @@ uint32_t p3d_crc32c(const void* data, size_t n, uint32_t crc) {
     return c ^ 0xFFFFFFFFu;
 }
 
+// ---- resident training set (include/p3d_hip.h; the handle's part in net_sched.inc, the kernel in trainset.hip) ------------------
+int p3d_trainset_open(p3d_handle* h, int n_videos, const int* frames, int frame_format, int flags, const float mean_rgb[3]) {
+    API_BEGIN
+    if (!h || !frames || !mean_rgb) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->trainset_open(n_videos, frames, frame_format, flags, mean_rgb);
+    API_END
+}
+
+int p3d_trainset_close(p3d_handle* h) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->trainset_close();
+    API_END
+}
+
+int p3d_trainset_info(p3d_handle* h, int* n_videos, int64_t* total_frames, int* frame_format, int* flags, int64_t* bytes) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    h->trainset_need_open("trainset_info");
+    if (n_videos) *n_videos = (int)h->ts_frames.size();
+    if (total_frames) *total_frames = h->ts_total();
+    if (frame_format) *frame_format = h->ts_format;
+    if (flags) *flags = h->ts_flags;
+    if (bytes) *bytes = (int64_t)(h->ts_fr_bytes + h->ts_den_bytes + h->ts_fix_bytes);
+    API_END
+}
+
+int p3d_trainset_video_info(p3d_handle* h, int video, int* frames, int* put_frames, int* put_density, int* put_fixations) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    h->trainset_need_open("trainset_video_info");
+    if (video < 0 || video >= (int)h->ts_frames.size())
+        throw P3dError("trainset_video_info: video " + std::to_string(video) + " is outside [0, " + std::to_string(h->ts_frames.size()) + ")");
+    const int F = h->ts_frames[(size_t)video];
+    int* out[3] = {put_frames, put_density, put_fixations};
+    for (int t = 0; t < 3; ++t) {
+        if (!out[t]) continue;
+        const unsigned char* p = h->ts_put[t].data() + h->ts_base[(size_t)video];
+        *out[t] = (int)std::count(p, p + F, (unsigned char)1);
+    }
+    if (frames) *frames = F;
+    API_END
+}
+
+int p3d_trainset_put_frames_u8(p3d_handle* h, int video, int first, const unsigned char* bgr, int n, int H0, int W0) {
+    API_BEGIN
+    if (!h || !bgr) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->trainset_put_frames_u8(video, first, bgr, n, H0, W0);
+    API_END
+}
+
+int p3d_trainset_put_frames(p3d_handle* h, int video, int first, const float* x, int n) {
+    API_BEGIN
+    if (!h || !x) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->trainset_put_frames(video, first, x, n);
+    API_END
+}
+
+int p3d_trainset_put_density_u8(p3d_handle* h, int video, int first, const unsigned char* grey, int n, int H0, int W0) {
+    API_BEGIN
+    if (!h || !grey) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->trainset_put_density_u8(video, first, grey, n, H0, W0);
+    API_END
+}
+
+int p3d_trainset_put_fixations(p3d_handle* h, int video, int first, const unsigned char* fix, int n) {
+    API_BEGIN
+    if (!h || !fix) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->trainset_put_fixations(video, first, fix, n);
+    API_END
+}
+
+int p3d_trainset_stage(p3d_handle* h, const int* video, const int* start, int n) {
+    API_BEGIN
+    if (!h || !video || !start) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->trainset_gather("trainset_stage", video, start, n, true);
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    API_END
+}
+
+int p3d_trainset_step(p3d_handle* h, const int* video, const int* start, int n, float dropout_rate, uint64_t seed, float* loss) {
+    API_BEGIN
+    if (!h || !video || !start) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->trainset_step_check();
+    h->trainset_gather("trainset_step", video, start, n, true);
+    h->check_fixations(true);
+    h->fix_fresh = false;
+    if (h->aug_on) h->augment_staged(seed, nullptr, nullptr);      // p3d_augment_inputs: from the staged buffers themselves
+    h->train_step_device(dropout_rate, seed);
+    const float l = h->read_loss();
+    if (loss) *loss = l;
+    API_END
+}
+
+int p3d_trainset_forward(p3d_handle* h, const int* video, const int* start, int n, float* pred) {
+    API_BEGIN
+    if (!h || !video || !start || !pred) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->trainset_gather("trainset_forward", video, start, n, false);
+    Ctx c; c.training = false; c.drop = 0.f; c.seed = 0; c.update_moving = false; c.s = h->stream;      // p3d_forward's pass
+    h->run_forward(c);
+    h->download_act(h->pred, pred);
+    API_END
+}
+
+int p3d_trainset_get_staged(p3d_handle* h, float* x, float* y, unsigned char* fix) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->trainset_need_open("trainset_get_staged");
+    if (fix && !h->d_fix) throw P3dError("trainset_get_staged: no fixation maps were ever staged");
+    const hipStream_t s = h->stream;
+    if (x) HIPCHECK(hipMemcpyAsync(x, h->x_in->p, (size_t)h->x_in->rows() * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (y) HIPCHECK(hipMemcpyAsync(y, h->d_y, (size_t)h->pred->rows() * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (fix) HIPCHECK(hipMemcpyAsync(fix, h->d_fix, (size_t)h->pred->rows(), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    API_END
+}
+
+int p3d_trainset_last_ms(p3d_handle* h, double* ms) {
+    API_BEGIN
+    if (!h || !ms) throw P3dError("null argument");
+    h->trainset_need_open("trainset_last_ms");
+    if (!h->ts_timed) throw P3dError("trainset_last_ms: nothing was staged from the open training set");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    float t = 0.f;
+    HIPCHECK(hipEventElapsedTime(&t, h->ev_ts[0], h->ev_ts[1]));
+    *ms = (double)t;
+    API_END
+}
+
+// The launch of trainset.hip from its launch description, on host arrays.  Every device buffer sits `offset` elements past a 16-byte
+// boundary between guard elements; a guard or a store that the launch changed is an error.
+}  // extern "C"
+namespace {
+template <typename T>
+struct GuardedArr {                               // n elements at element `at` of a device buffer of guard bytes
+    static constexpr unsigned char GUARD = 0xa5;
+    int64_t n, at; std::vector<unsigned char> host; DevArr<unsigned char> dev;
+    static std::vector<unsigned char> fill(int64_t n, int64_t at, const void* src) {
+        std::vector<unsigned char> v((size_t)(n + 32) * sizeof(T), GUARD);
+        if (src) memcpy(v.data() + at * sizeof(T), src, (size_t)n * sizeof(T));
+        return v;
+    }
+    GuardedArr(int64_t n_, int offset, const void* src) : n(n_), at(16 + offset), host(fill(n_, 16 + offset, src)), dev(host.size(), host.data()) {}
+    T* p() { return reinterpret_cast<T*>(dev.p) + at; }
+    std::vector<unsigned char> back() { std::vector<unsigned char> v(host.size()); dev.get(v.data(), v.size()); return v; }
+    bool guards_kept(const std::vector<unsigned char>& v) const {
+        for (size_t i = 0; i < v.size(); ++i)
+            if ((i < (size_t)at * sizeof(T) || i >= (size_t)(at + n) * sizeof(T)) && v[i] != GUARD) return false;
+        return true;
+    }
+    void take(const std::vector<unsigned char>& v, void* out) const { memcpy(out, v.data() + at * sizeof(T), (size_t)n * sizeof(T)); }
+};
+}  // namespace
+extern "C" {
+
+int p3d_debug_trainset_gather(int device, int frame_format, const void* frames_store, const unsigned char* density_store,
+                              const unsigned char* fix_store, int n_videos, const int* frames, int T, int64_t hw, const float mean_rgb[3],
+                              const int* video, const int* start, const int* first, int B, int offset, float* x, float* y,
+                              unsigned char* fix) {
+    API_BEGIN
+    if (!frames_store || !frames || !mean_rgb || !video || !start || !x) throw P3dError("null argument");
+    if ((y != nullptr) != (density_store != nullptr) || (fix != nullptr) != (fix_store != nullptr))
+        throw P3dError("trainset_gather: a store and its output come together");
+    if (frame_format != P3D_TRAINSET_FRAMES_U8 && frame_format != P3D_TRAINSET_FRAMES_F32) throw P3dError("trainset_gather: unknown frame format");
+    if (n_videos < 1 || T < 1 || hw < 1 || B < 1) throw P3dError("trainset_gather: bad shape");
+    int64_t total = 0;
+    std::vector<int64_t> base((size_t)n_videos, 0);
+    for (int v = 0; v < n_videos; ++v) {
+        if (frames[v] < 1) throw P3dError("trainset_gather: a video without frames");
+        base[(size_t)v] = total;
+        total += frames[v];
+    }
+    if (total * hw * 3 > (int64_t)1 << 28 || (int64_t)B * T * hw * 3 > (int64_t)1 << 28) throw P3dError("trainset_gather: the hook takes up to 2^28 elements");
+    video_hook_device(device, offset);
+    std::vector<int> fr((size_t)B, 0);      // a row the wrapper will refuse keeps 0 here: it is never dereferenced
+    for (int k = 0; k < B; ++k)
+        fr[(size_t)k] = first ? first[k] : (video[k] >= 0 && video[k] < n_videos ? (int)(base[(size_t)video[k]] + start[k]) : 0);
+    const bool f32 = frame_format == P3D_TRAINSET_FRAMES_F32;
+    const int64_t npx = total * hw, nout = (int64_t)B * T * hw;
+    GuardedArr<float> sf(f32 ? npx * 3 : 0, offset, f32 ? frames_store : nullptr), xb(nout * 3, offset, nullptr), yb(y ? nout : 0, offset, nullptr);
+    GuardedArr<unsigned char> su(f32 ? 0 : npx * 3, offset, f32 ? nullptr : frames_store), sd(y ? npx : 0, offset, density_store),
+        sx(fix ? npx : 0, offset, fix_store), fb(fix ? nout : 0, offset, nullptr);
+    DevArr<int> tab((size_t)B, fr.data());
+    TrainsetGatherArgs a;
+    a.format = f32 ? TRAINSET_F32 : TRAINSET_U8;
+    a.frames = f32 ? (const void*)sf.p() : (const void*)su.p();
+    a.density = y ? sd.p() : nullptr; a.fixations = fix ? sx.p() : nullptr;
+    a.x = xb.p(); a.y = y ? yb.p() : nullptr; a.fix = fix ? fb.p() : nullptr;
+    a.first = tab.p; a.first_host = fr.data(); a.video_host = video; a.start_host = start; a.frames_host = frames; a.n_videos = n_videos;
+    a.B = B; a.T = T; a.hw = hw;
+    for (int c = 0; c < 3; ++c) a.mean[c] = mean_rgb[c];
+    if (std::string(p3d_trainset_gather_desc(a).kernel) != "trainset_gather_kernel<" + std::to_string(a.format) + ">")
+        throw P3dError("trainset_gather: launch description names another kernel");
+    HIPCHECK(p3d_trainset_gather(a, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    if (sf.back() != sf.host || su.back() != su.host || sd.back() != sd.host || sx.back() != sx.host) throw P3dError("trainset_gather: the launch changed a store");
+    const std::vector<unsigned char> xo = xb.back(), yo = yb.back(), fo = fb.back();
+    if (!xb.guards_kept(xo) || !yb.guards_kept(yo) || !fb.guards_kept(fo)) throw P3dError("trainset_gather: the launch wrote outside its range");
+    xb.take(xo, x);
+    if (y) yb.take(yo, y);
+    if (fix) fb.take(fo, fix);
+    API_END
+}
+
 int p3d_shutdown(void) {
     API_BEGIN
     if (g_live_handles.load() > 0)

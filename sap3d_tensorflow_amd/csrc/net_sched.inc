@@ -1162,6 +1162,207 @@
         return scratch;
     }
 
+    // ---- resident training set (p3d_trainset_*; trainset.hip) -------------------------------------------
+    // Nothing exists before the first p3d_trainset_open and nothing here runs while no set is open.  The stores are private
+    // allocations (freed by p3d_trainset_close, not part of `allocs`): no step, launch list or captured graph names them.  The
+    // gather writes the staged x_in, d_y and d_fix, whose addresses never move, as the uploads do; d_fix is allocated by the first
+    // gather that writes it, as by the first p3d_upload_fixations.  The host keeps which frames were put, per tensor.  Every
+    // entry point ends synchronised, so the next call may overwrite the host table.
+    bool ts_is_open = false;
+    int ts_format = P3D_TRAINSET_FRAMES_U8, ts_flags = 0;
+    float ts_mean[3] = {0.f, 0.f, 0.f};
+    std::vector<int> ts_frames;                 // F_v
+    std::vector<int64_t> ts_base;               // base[v] = F_0 + .. + F_{v-1}; [V + 1], the last entry the total
+    void* ts_fr = nullptr; unsigned char* ts_den = nullptr; unsigned char* ts_fix = nullptr;      // the three stores
+    size_t ts_fr_bytes = 0, ts_den_bytes = 0, ts_fix_bytes = 0;                                    // what the allocations hold
+    unsigned char* ts_u8 = nullptr; size_t ts_u8_bytes = 0;      // staging of the puts that run a kernel
+    int* d_ts_first = nullptr;                                   // the per-call table, [B]
+    std::vector<int> ts_first;
+    std::vector<unsigned char> ts_put[3];                        // frames, density, fixations: [total]
+    hipEvent_t ev_ts[2] = {nullptr, nullptr};                    // around the last stage's launch (p3d_trainset_last_ms)
+    bool ts_timed = false;
+    int64_t ts_hw() const { return (int64_t)x_in->H * x_in->W; }
+    int64_t ts_total() const { return ts_base.empty() ? 0 : ts_base.back(); }
+    bool ts_has_fix() const { return (ts_flags & P3D_TRAINSET_FIXATIONS) != 0; }
+    size_t ts_frame_bytes() const { return (size_t)ts_hw() * 3 * (ts_format == P3D_TRAINSET_FRAMES_F32 ? 4 : 1); }
+    static const char* ts_unput(int t) { return t == 0 ? ", which was never put" : t == 1 ? ", whose density map was never put" : ", whose fixation map was never put"; }
+
+    // The global first frame of every clip of a stage, from host state alone (no HIP call): validates as the header says -- the
+    // message names the first offending clip or frame.  put[t] (or null: the tensor is not written by the call) has one flag per
+    // frame of the concatenation.
+    static std::vector<int> trainset_plan(const char* who, const std::vector<int>& frames, const std::vector<int64_t>& base, int T, int B,
+                                          const int* video, const int* start, int n, const unsigned char* const put[3]) {
+        if (!video || !start) throw P3dError("null argument");
+        if (n != B) throw P3dError(std::string(who) + ": " + std::to_string(n) + " clips, the batch is " + std::to_string(B));
+        const int V = (int)frames.size();
+        std::vector<int> first((size_t)B, 0);
+        for (int k = 0; k < n; ++k) {
+            const int v = video[k];
+            if (v < 0 || v >= V)
+                throw P3dError(std::string(who) + ": clip " + std::to_string(k) + " names video " + std::to_string(v) + ", outside [0, " + std::to_string(V) + ")");
+            const std::string c = std::string(who) + ": clip " + std::to_string(k) + " (video " + std::to_string(v) + ") starts at " + std::to_string(start[k]);
+            if (start[k] < 0 || start[k] > frames[(size_t)v] - T)
+                throw P3dError(c + ", outside [0, F - T = " + std::to_string(frames[(size_t)v] - T) + "]");
+            const int64_t f0 = base[(size_t)v] + start[k];
+            for (int t = 0; t < 3; ++t)
+                for (int i = 0; put[t] && i < T; ++i)
+                    if (!put[t][(size_t)(f0 + i)])
+                        throw P3dError(c + " and holds frame " + std::to_string(start[k] + i) + ts_unput(t));
+            first[(size_t)k] = (int)f0;
+        }
+        return first;
+    }
+
+    void trainset_need_open(const char* who) const {
+        if (!ts_is_open) throw P3dError(std::string(who) + ": no training set is open (p3d_trainset_open)");
+    }
+    // frames first .. first + n - 1 of video v -> the first one's index in the concatenation
+    int64_t trainset_range(const char* who, int v, int first, int n) const {
+        if (v < 0 || v >= (int)ts_frames.size())
+            throw P3dError(std::string(who) + ": video " + std::to_string(v) + " is outside [0, " + std::to_string(ts_frames.size()) + ")");
+        if (n < 1 || first < 0 || first > ts_frames[(size_t)v] - n)
+            throw P3dError(std::string(who) + ": frames " + std::to_string(first) + " .. " + std::to_string((int64_t)first + n - 1) +
+                           " are outside video " + std::to_string(v) + "'s [0, " + std::to_string(ts_frames[(size_t)v]) + ")");
+        return ts_base[(size_t)v] + first;
+    }
+    void trainset_free() {
+        for (void* p : {ts_fr, (void*)ts_den, (void*)ts_fix, (void*)ts_u8, (void*)d_ts_first}) if (p) hipFree(p);
+        ts_fr = nullptr; ts_den = ts_fix = ts_u8 = nullptr; d_ts_first = nullptr;
+        ts_fr_bytes = ts_den_bytes = ts_fix_bytes = ts_u8_bytes = 0;
+    }
+    void trainset_open(int n_videos, const int* frames, int format, int flags, const float mean_rgb[3]) {
+        if (format != P3D_TRAINSET_FRAMES_U8 && format != P3D_TRAINSET_FRAMES_F32)
+            throw P3dError("trainset_open: frame format " + std::to_string(format) + " is neither P3D_TRAINSET_FRAMES_U8 (0) nor P3D_TRAINSET_FRAMES_F32 (1)");
+        if (flags & ~P3D_TRAINSET_FIXATIONS) throw P3dError("trainset_open: unknown flags " + std::to_string(flags));
+        if (n_videos < 1) throw P3dError("trainset_open: needs at least one video");
+        for (int c = 0; c < 3; ++c) if (!std::isfinite(mean_rgb[c])) throw P3dError("trainset_open: the channel means must be finite");
+        std::vector<int64_t> base((size_t)n_videos + 1, 0);
+        for (int v = 0; v < n_videos; ++v) {
+            if (frames[v] < 1) throw P3dError("trainset_open: video " + std::to_string(v) + " has " + std::to_string(frames[v]) + " frames");
+            base[(size_t)v + 1] = base[(size_t)v] + frames[v];
+            if (base[(size_t)v + 1] > (int64_t)INT32_MAX) throw P3dError("trainset_open: more than 2^31 - 1 frames");
+        }
+        const int64_t total = base.back();
+        const bool want_fix = (flags & P3D_TRAINSET_FIXATIONS) != 0;
+        const size_t fb = (size_t)total * (size_t)ts_hw() * 3 * (format == P3D_TRAINSET_FRAMES_F32 ? 4 : 1), db = (size_t)total * (size_t)ts_hw();
+        sync_streams();
+        // the new stores first: a failed allocation changes nothing
+        void *nf = nullptr, *nd = nullptr, *nx = nullptr;
+        hipError_t e = hipSuccess;
+        if (fb > ts_fr_bytes) e = hipMalloc(&nf, fb);
+        if (e == hipSuccess && db > ts_den_bytes) e = hipMalloc(&nd, db);
+        if (e == hipSuccess && want_fix && db > ts_fix_bytes) e = hipMalloc(&nx, db);
+        if (e != hipSuccess) {
+            for (void* p : {nf, nd, nx}) if (p) hipFree(p);
+            (void)hipGetLastError();
+            throw P3dError("trainset_open: no device memory for " + std::to_string(total) + " frames (" + hipGetErrorString(e) + ")");
+        }
+        if (nf) { if (ts_fr) hipFree(ts_fr); ts_fr = nf; ts_fr_bytes = fb; }
+        if (nd) { if (ts_den) hipFree(ts_den); ts_den = (unsigned char*)nd; ts_den_bytes = db; }
+        if (nx) { if (ts_fix) hipFree(ts_fix); ts_fix = (unsigned char*)nx; ts_fix_bytes = db; }
+        if (!want_fix && ts_fix) { hipFree(ts_fix); ts_fix = nullptr; ts_fix_bytes = 0; }      // the fixation store exists only for a set that has them
+        if (!d_ts_first) HIPCHECK(hipMalloc((void**)&d_ts_first, (size_t)x_in->N * sizeof(int)));
+        if (!ev_ts[0]) for (auto& ev : ev_ts) HIPCHECK(hipEventCreate(&ev));
+        ts_frames.assign(frames, frames + n_videos);
+        ts_base = base;
+        for (auto& p : ts_put) p.assign((size_t)total, 0);
+        ts_format = format; ts_flags = flags;
+        for (int c = 0; c < 3; ++c) ts_mean[c] = mean_rgb[c];
+        ts_is_open = true; ts_timed = false;
+    }
+    void trainset_close() {
+        sync_streams();
+        trainset_free();
+        ts_frames.clear(); ts_base.clear();
+        for (auto& p : ts_put) p.clear();
+        ts_is_open = false; ts_timed = false; ts_flags = 0;
+    }
+    void trainset_mark(int t, int64_t at, int n) { std::fill(ts_put[t].begin() + at, ts_put[t].begin() + at + n, (unsigned char)1); }
+    // the call's bytes in the staging buffer (queued on the main stream)
+    const unsigned char* trainset_stage_bytes(const unsigned char* src, size_t bytes) {
+        if (bytes > ts_u8_bytes) {
+            HIPCHECK(hipStreamSynchronize(stream));
+            if (ts_u8) hipFree(ts_u8);
+            ts_u8 = nullptr; ts_u8_bytes = 0;
+            HIPCHECK(hipMalloc((void**)&ts_u8, bytes));
+            ts_u8_bytes = bytes;
+        }
+        HIPCHECK(hipMemcpyAsync(ts_u8, src, bytes, hipMemcpyHostToDevice, stream));
+        return ts_u8;
+    }
+    void trainset_put_frames_u8(int v, int first, const unsigned char* bgr, int n, int H0, int W0) {
+        trainset_need_open("trainset_put_frames_u8");
+        const int64_t at = trainset_range("trainset_put_frames_u8", v, first, n);
+        if (H0 < 1 || W0 < 1) throw P3dError("trainset_put_frames_u8: empty frame");
+        if (ts_format == P3D_TRAINSET_FRAMES_U8) {      // the bytes as they are: the gather normalises
+            if (H0 != x_in->H || W0 != x_in->W)
+                throw P3dError("trainset_put_frames_u8: the set keeps 8-bit frames (P3D_TRAINSET_FRAMES_U8), which takes frames decoded at the grid's " +
+                               std::to_string(x_in->H) + " x " + std::to_string(x_in->W) + ", not " + std::to_string(H0) + " x " + std::to_string(W0));
+            HIPCHECK(copy_now((unsigned char*)ts_fr + (size_t)at * ts_frame_bytes(), bgr, (size_t)n * ts_frame_bytes(), hipMemcpyHostToDevice, stream));
+        } else {
+            const unsigned char* src = trainset_stage_bytes(bgr, (size_t)n * H0 * W0 * 3);
+            HIPCHECK(p3d_mapf_frames(src, n, H0, W0, (float*)ts_fr + at * ts_hw() * 3, x_in->H, x_in->W, ts_mean, stream));
+            HIPCHECK(hipStreamSynchronize(stream));
+        }
+        trainset_mark(0, at, n);
+    }
+    void trainset_put_frames(int v, int first, const float* x, int n) {
+        trainset_need_open("trainset_put_frames");
+        const int64_t at = trainset_range("trainset_put_frames", v, first, n);
+        if (ts_format != P3D_TRAINSET_FRAMES_F32)
+            throw P3dError("trainset_put_frames: the set keeps 8-bit frames (P3D_TRAINSET_FRAMES_U8); normalised floats need P3D_TRAINSET_FRAMES_F32");
+        HIPCHECK(copy_now((float*)ts_fr + at * ts_hw() * 3, x, (size_t)n * ts_frame_bytes(), hipMemcpyHostToDevice, stream));
+        trainset_mark(0, at, n);
+    }
+    void trainset_put_density_u8(int v, int first, const unsigned char* grey, int n, int H0, int W0) {
+        trainset_need_open("trainset_put_density_u8");
+        const int64_t at = trainset_range("trainset_put_density_u8", v, first, n);
+        if (H0 < 1 || W0 < 1) throw P3dError("trainset_put_density_u8: empty map");
+        const unsigned char* src = trainset_stage_bytes(grey, (size_t)n * H0 * W0);
+        HIPCHECK(p3d_mapf_density_u8(src, n, H0, W0, ts_den + at * ts_hw(), x_in->H, x_in->W, stream));
+        HIPCHECK(hipStreamSynchronize(stream));
+        trainset_mark(1, at, n);
+    }
+    void trainset_put_fixations(int v, int first, const unsigned char* fix, int n) {
+        trainset_need_open("trainset_put_fixations");
+        const int64_t at = trainset_range("trainset_put_fixations", v, first, n);
+        if (!ts_has_fix()) throw P3dError("trainset_put_fixations: the set was opened without P3D_TRAINSET_FIXATIONS");
+        HIPCHECK(copy_now(ts_fix + at * ts_hw(), fix, (size_t)n * (size_t)ts_hw(), hipMemcpyHostToDevice, stream));
+        trainset_mark(2, at, n);
+    }
+    // validates (nothing launched on a refusal), then queues the table and the one launch between the stage's events.
+    // targets: x alone (p3d_trainset_forward), or x, y and -- when the set has them -- the fixations.
+    void trainset_gather(const char* who, const int* video, const int* start, int n, bool targets) {
+        trainset_need_open(who);
+        const int B = x_in->N, T = x_in->D;
+        const bool with_fix = targets && ts_has_fix();
+        const unsigned char* const put[3] = {ts_put[0].data(), targets ? ts_put[1].data() : nullptr, with_fix ? ts_put[2].data() : nullptr};
+        std::vector<int> first = trainset_plan(who, ts_frames, ts_base, T, B, video, start, n, put);
+        if (with_fix && !d_fix) d_fix = dalloc<unsigned char>(pred->rows());      // address stable from here on: captured steps name it
+        ts_first.swap(first);
+        TrainsetGatherArgs a;
+        a.format = ts_format == P3D_TRAINSET_FRAMES_F32 ? TRAINSET_F32 : TRAINSET_U8;
+        a.frames = ts_fr; a.density = ts_den; a.fixations = ts_fix;
+        a.x = x_in->p; a.y = targets ? d_y : nullptr; a.fix = with_fix ? d_fix : nullptr;
+        a.first = d_ts_first; a.first_host = ts_first.data(); a.video_host = video; a.start_host = start;
+        a.frames_host = ts_frames.data(); a.n_videos = (int)ts_frames.size();
+        a.B = B; a.T = T; a.hw = ts_hw();
+        for (int c = 0; c < 3; ++c) a.mean[c] = ts_mean[c];
+        HIPCHECK(hipMemcpyAsync(d_ts_first, ts_first.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, stream));
+        HIPCHECK(hipEventRecord(ev_ts[0], stream));
+        HIPCHECK(p3d_trainset_gather(a, stream));
+        HIPCHECK(hipEventRecord(ev_ts[1], stream));
+        if (with_fix) fix_fresh = true;      // the gather is the upload p3d_upload_fixations would have been
+        ts_timed = true;
+    }
+    // p3d_trainset_step's refusals that do not depend on the clips, ahead of anything that changes state
+    void trainset_step_check() const {
+        trainset_need_open("trainset_step");
+        refuse_swapped("train step");
+        if (saliency_needs_fixations() && !ts_has_fix())
+            throw P3dError("trainset_step: the loss has an NSS term (w_nss > 0) and the training set was opened without P3D_TRAINSET_FIXATIONS");
+    }
+
     // ---- temporal smoothing of the video's maps at read-out (p3d_set_video_temporal; temporal.hip) -------
     // Off by default, and off nothing here runs.  The setting is a kind with its radius and taps, or its alpha; the stage is one
     // launch issued by the two read-outs in place of video_finalize, into scratch from the stream pool.  The events exist from the
@@ -1566,6 +1767,8 @@
         for (hipEvent_t e : ev_vid) if (e) hipEventDestroy(e);
         for (hipEvent_t e : ev_temporal) if (e) hipEventDestroy(e);
         video_free();
+        for (hipEvent_t e : ev_ts) if (e) hipEventDestroy(e);
+        trainset_free();
         eval_extra_free();
         prior_close();
         prior_map_take(nullptr, 0, 0);

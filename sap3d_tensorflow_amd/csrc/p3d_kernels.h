@@ -717,6 +717,29 @@ LaunchDesc p3d_video_scatter_desc(const VideoScatterArgs& a);
 hipError_t p3d_video_scatter(const VideoScatterArgs& a, hipStream_t s);
 LaunchDesc p3d_video_mean_desc(const VideoMeanArgs& a);
 hipError_t p3d_video_mean(const VideoMeanArgs& a, hipStream_t s);
+// ---- resident training set (trainset.hip; p3d_trainset_*, the contract in include/p3d_hip.h) -------------------------------------
+// V videos concatenated, video v's frames at base[v] = F_0 + .. + F_{v-1}: a frame store (TRAINSET_U8: [sum F][hw][3] bytes in the
+// decoded BGR order; TRAINSET_F32: [sum F][hw][3] normalised floats), a density store [sum F][hw] bytes and a fixation store of the
+// same shape.  One launch cuts clip k = frames first[k] .. first[k] + T - 1 of every tensor the call names into x [B][T][hw][3],
+// y [B][T][hw] and fix [B][T][hw] (y and / or fix null: not written):
+//   x    TRAINSET_U8: x[c] = __fdiv_rn(__fsub_rn((float)bgr[2 - c], mean[c]), 255.f); TRAINSET_F32: a copy of the bits
+//   y    (float)((double)byte / 255.0)
+//   fix  a copy of the bytes
+// first [B] reaches the kernel in device memory; the launcher checks the same rows on the host first (video_host / start_host /
+// first_host against frames_host [V]: a row outside its video is hipErrorInvalidValue, nothing launched): the kernel trusts them.
+enum { TRAINSET_U8 = 0, TRAINSET_F32 = 1 };
+struct TrainsetGatherArgs {
+    int format = TRAINSET_U8;
+    const void* frames = nullptr; const unsigned char* density = nullptr; const unsigned char* fixations = nullptr;      // the stores
+    float* x = nullptr; float* y = nullptr; unsigned char* fix = nullptr;
+    const int* first = nullptr;                                                                  // [B], device memory
+    const int* first_host = nullptr; const int* video_host = nullptr; const int* start_host = nullptr;      // the same rows on the host
+    const int* frames_host = nullptr; int n_videos = 0;                                          // F_v
+    int B = 0, T = 0; long long hw = 0;
+    float mean[3] = {0.f, 0.f, 0.f};
+};
+LaunchDesc p3d_trainset_gather_desc(const TrainsetGatherArgs& a);
+hipError_t p3d_trainset_gather(const TrainsetGatherArgs& a, hipStream_t s);
 // ---- temporal smoothing of the maps at read-out (temporal.hip; p3d_set_video_temporal, the contract in include/p3d_hip.h) -------
 // One launch: frames first .. first + n - 1 of store [F][hw], filtered along the frame axis of the whole video, -> out [n][hw]
 // (not the store, which is only read).  count null: a frame's input is the stored map; else [F] in device memory and the input is
@@ -754,6 +777,8 @@ hipError_t p3d_metric_auc_borji(const float* sal, const float* fix, const int* r
 hipError_t p3d_mapf_frames(const unsigned char* bgr, int n_frames, int H0, int W0, float* dst, int H, int W, const float mean_rgb[3],
                            hipStream_t s);
 hipError_t p3d_mapf_density(const unsigned char* grey, int n_frames, int H0, int W0, float* dst, int H, int W, hipStream_t s);
+// the byte v of the same resize (y = v / 255.): what the training set's density store keeps
+hipError_t p3d_mapf_density_u8(const unsigned char* grey, int n_frames, int H0, int W0, unsigned char* dst, int H, int W, hipStream_t s);
 
 // ---- the same metrics at ground-truth resolution, whole-GPU reductions (metrics_full.hip; test.py:160-183) ------
 // cv2.INTER_LINEAR resize of float32 maps: map m's pixel (y, x) at src[m * map_stride + (y * w + x) * elem_stride]

@@ -40,6 +40,34 @@ def mapf_density(maps_grey, size=112, device=0):
     return out
 
 
+def clip_tuples(frames_per_video, video_length=16, overlap=15, skip_head=11):
+    """The clip list of VideoDataset.setup_video_dataset_p3d (dataflow.py:43-52) before its shuffle: (video, first frame) for
+    first frames skip_head, skip_head + step, .. with step = video_length - overlap, video by video, a video's list ending at
+    the first clip that would leave it (:49-50)."""
+    if not overlap < video_length:
+        raise ValueError("overlap should be smaller than video_length")          # dataflow.py:42
+    step = video_length - overlap
+    out = []
+    for i, total in enumerate(frames_per_video):
+        for j in range(skip_head, int(total), step):
+            if j + video_length > total:
+                break
+            out.append((i, j))
+    return out
+
+
+def split_clips(tuples, props, rng):
+    """dataflow.py:56-60: the shuffled list cut at int(n * props) -> (training tuples, validation tuples).  The reference
+    shuffles with the unseeded global `random`; here the order is rng.permutation(n) of a numpy Generator (or a seed for
+    np.random.default_rng), so a split can be reproduced.  UNPINNED: no run of the reference yields the same split."""
+    if not hasattr(rng, "permutation"):
+        rng = np.random.default_rng(rng)
+    order = rng.permutation(len(tuples))
+    shuffled = [tuple(tuples[i]) for i in order]
+    n = int(len(shuffled) * props)
+    return shuffled[:n], shuffled[n:]
+
+
 def resize_linear(maps, size, device=0):
     """cv2.resize(m, (W, H), interpolation=cv2.INTER_LINEAR) of float32 single-channel maps (test.py:170 resizes every
     112x112 prediction to the 1080x960 fixation map): [n, h, w] or [h, w] -> [n, H, W] / [H, W]; size = (H, W) or an int."""

@@ -899,6 +899,120 @@ class P3DSession:
         self.last_maps_ms = dict(device=ms[0], d2h=ms[1])
         return out
 
+    # ---- resident training set (p3d_trainset_*) -------------------------------------------------------------
+    def open_trainset(self, frames_per_video, frame_format="u8", fixations=False, mean_rgb=(90., 102., 98.)):
+        """Keep a training set on the device (an addition: the reference's loader, dataflow.py:39-62, cuts overlapping clips on
+        the host): videos of frames_per_video[v] frames each, their decoded frames, density maps and -- fixations=True -- fixation
+        maps go up once (trainset_put_*), and trainset_stage / trainset_step / trainset_forward cut a batch of (video, start)
+        clips where they are, into the buffers a train step reads.  frame_format "u8" keeps 3 bytes per pixel and takes only
+        frames decoded at the grid's size; "f32" keeps the floats of dataflow.mapf_frames, for any source size.  The staged x and y
+        are what dataflow.mapf_frames(..., mean_rgb) and dataflow.mapf_density return for the clips' frames, bit for bit.
+        Opening again replaces the set.  include/p3d_hip.h holds the exact rules."""
+        if frame_format not in _lib.TRAINSET_FORMATS:
+            raise ValueError("frame format %r: have %s" % (frame_format, sorted(_lib.TRAINSET_FORMATS)))
+        fr = np.ascontiguousarray(frames_per_video, dtype=np.int32)
+        if fr.ndim != 1:
+            raise ValueError("frames_per_video is a list of frame counts, one per video")
+        mean = np.ascontiguousarray(mean_rgb, dtype=np.float32)
+        if mean.shape != (3,):
+            raise ValueError("mean_rgb needs three values")
+        check(lib().p3d_trainset_open(self._h, len(fr), fr.ctypes.data_as(_lib._ip), _lib.TRAINSET_FORMATS[frame_format],
+                                      _lib.P3D_TRAINSET_FIXATIONS if fixations else 0, fptr(mean)))
+
+    def close_trainset(self):
+        check(lib().p3d_trainset_close(self._h))
+
+    def trainset_info(self):
+        """dict(videos, total_frames, frame_format, fixations, bytes, frames, put) of the open set: `frames` the frames of every
+        video, `put` how many of them were put per video as dict(frames, density, fixations) of lists."""
+        v, t, f, fl, b = C.c_int(), C.c_int64(), C.c_int(), C.c_int(), C.c_int64()
+        check(lib().p3d_trainset_info(self._h, C.byref(v), C.byref(t), C.byref(f), C.byref(fl), C.byref(b)))
+        frames, put = [], dict(frames=[], density=[], fixations=[])
+        for i in range(v.value):
+            n, a, d, x = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+            check(lib().p3d_trainset_video_info(self._h, i, C.byref(n), C.byref(a), C.byref(d), C.byref(x)))
+            frames.append(n.value); put["frames"].append(a.value); put["density"].append(d.value); put["fixations"].append(x.value)
+        return dict(videos=v.value, total_frames=t.value, frame_format=[k for k, c in _lib.TRAINSET_FORMATS.items() if c == f.value][0],
+                    fixations=bool(fl.value & _lib.P3D_TRAINSET_FIXATIONS), bytes=b.value, frames=frames, put=put)
+
+    @staticmethod
+    def _u8_frames(a, ndim, what):
+        a = np.ascontiguousarray(a)
+        if a.dtype != np.uint8 or a.ndim != ndim or (ndim == 4 and a.shape[3] != 3) or a.size == 0:
+            raise ValueError("%s are %s %s, expected uint8 %s" % (what, a.dtype, a.shape, "[n, H0, W0, 3]" if ndim == 4 else "[n, H0, W0]"))
+        return a
+
+    def trainset_put_frames_u8(self, video, first, bgr):
+        """Decoded uint8 frames [n, H0, W0, 3] in cv2's BGR order -> frames first .. first + n - 1 of `video`.  A "u8" set keeps the
+        bytes (H0 x W0 must be the grid); an "f32" set keeps dataflow.mapf_frames(bgr, (H, W), mean_rgb), computed on the device."""
+        a = self._u8_frames(bgr, 4, "frames")
+        check(lib().p3d_trainset_put_frames_u8(self._h, int(video), int(first), a.ctypes.data_as(_lib._u8p), a.shape[0], a.shape[1], a.shape[2]))
+
+    def trainset_put_frames(self, video, first, frames):
+        """Normalised float32 frames [n, H, W, 3] -> frames first .. first + n - 1 of `video` ("f32" sets only)."""
+        a = np.ascontiguousarray(frames, dtype=np.float32)
+        if a.ndim != 4 or a.shape[1:] != self.x_shape[2:] or a.size == 0:
+            raise ValueError("frames are %s, the set takes [n, %d, %d, 3]" % (a.shape, self.x_shape[2], self.x_shape[3]))
+        check(lib().p3d_trainset_put_frames(self._h, int(video), int(first), fptr(a), len(a)))
+
+    def trainset_put_density_u8(self, video, first, grey):
+        """Grey uint8 density maps [n, H0, W0] -> the bytes of dataflow.mapf_density's 8-bit resize to the grid, y = byte / 255."""
+        a = self._u8_frames(grey, 3, "density maps")
+        check(lib().p3d_trainset_put_density_u8(self._h, int(video), int(first), a.ctypes.data_as(_lib._u8p), a.shape[0], a.shape[1], a.shape[2]))
+
+    def trainset_put_fixations(self, video, first, fix):
+        """uint8 fixation maps [n, H, W] on the grid, fixated where the byte is 128 or more (dataflow.fixations_to_grid brings
+        full-resolution maps there); the set must have been opened with fixations=True."""
+        a = np.ascontiguousarray(fix)
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[1:] != self.y_shape[2:] or a.size == 0:
+            raise ValueError("fixation maps are %s %s, the set takes uint8 [n, %d, %d]" % (a.dtype, a.shape, self.y_shape[2], self.y_shape[3]))
+        check(lib().p3d_trainset_put_fixations(self._h, int(video), int(first), a.ctypes.data_as(_lib._u8p), len(a)))
+
+    @staticmethod
+    def _clips(clips):
+        c = np.ascontiguousarray(clips, dtype=np.int32)
+        if c.ndim != 2 or c.shape[1] != 2:
+            raise ValueError("clips is a list of (video, start) pairs")
+        return np.ascontiguousarray(c[:, 0]), np.ascontiguousarray(c[:, 1])
+
+    def trainset_stage(self, clips):
+        """Cut `batch` clips, (video, start) each, out of the open set into the staged x, y and -- when the set has them -- fixation
+        buffers: what upload(x, y, fixations) leaves there for the host-built clips.  Refused with nothing changed when a clip
+        leaves its video or holds a frame that was never put."""
+        v, st = self._clips(clips)
+        check(lib().p3d_trainset_stage(self._h, v.ctypes.data_as(_lib._ip), st.ctypes.data_as(_lib._ip), len(v)))
+
+    def trainset_step(self, clips, dropout=0.5, seed=0):
+        """trainset_stage(clips), the augmentation under set_augment, then the train step -> loss: train_step(x, y, dropout, seed,
+        fixations) on the host-built clips, bit for bit, without the three uploads."""
+        v, st = self._clips(clips)
+        loss = C.c_float()
+        check(lib().p3d_trainset_step(self._h, v.ctypes.data_as(_lib._ip), st.ctypes.data_as(_lib._ip), len(v), float(dropout), seed, C.byref(loss)))
+        return loss.value
+
+    def trainset_forward(self, clips):
+        """forward(x, training=False) on the clips' frames, cut on the device; density and fixation maps need not be put."""
+        v, st = self._clips(clips)
+        pred = np.empty(self.pred_shape, np.float32)
+        check(lib().p3d_trainset_forward(self._h, v.ctypes.data_as(_lib._ip), st.ctypes.data_as(_lib._ip), len(v), fptr(pred)))
+        return pred
+
+    def trainset_staged(self, fixations=None):
+        """The staged inputs read back: (x [B,T,H,W,3], y [B,T,H,W], fix uint8 [B,T,H,W] or None).  fixations: whether to read the
+        fixation buffer (default: when the open set has them)."""
+        if fixations is None:
+            fixations = self.trainset_info()["fixations"]
+        x, y = np.empty(self.x_shape, np.float32), np.empty(self.y_shape, np.float32)
+        f = np.empty(self.y_shape, np.uint8) if fixations else None
+        check(lib().p3d_trainset_get_staged(self._h, fptr(x), fptr(y), f.ctypes.data_as(_lib._u8p) if fixations else None))
+        return x, y, f
+
+    def trainset_last_ms(self):
+        """HIP-event time of the last trainset_stage / trainset_step / trainset_forward's cut, milliseconds."""
+        ms = C.c_double(0.)
+        check(lib().p3d_trainset_last_ms(self._h, C.byref(ms)))
+        return ms.value
+
     def upload_fixations(self, fixations):
         """The batch's fixation maps for the losses of _lib.SALIENCY_LOSSES: uint8 [B, T, H, W], fixated where the byte is 128 or
         more (p3d_upload_fixations; dataflow.fixations_to_grid brings full-resolution maps to the grid)."""
