@@ -1571,3 +1571,4 @@ struct p3d_handle {
 };
 
 #include "net_abi.inc"
+#include "net_readout.inc"

@@ -1,0 +1,2075 @@
+// ---- metrics / pre-processing entry points (metrics.hip) -------------------------------------------------------
+namespace {
+template <typename T>
+struct DevArr {
+    T* p = nullptr;
+    explicit DevArr(size_t n, const T* host = nullptr) {
+        HIPCHECK(hipMalloc((void**)&p, (n > 0 ? n : 1) * sizeof(T)));
+        if (host) HIPCHECK(copy_now(p, host, n * sizeof(T), hipMemcpyHostToDevice, nullptr));
+    }
+    ~DevArr() { hipFree(p); }
+    void get(T* host, size_t n) { HIPCHECK(hipDeviceSynchronize()); HIPCHECK(copy_now(host, p, n * sizeof(T), hipMemcpyDeviceToHost, nullptr)); }
+};
+// op level: a device array of `n` elements between `guard` elements of guard words on either side, the data `shift` elements in
+template <typename T>
+struct Guarded {
+    static constexpr uint32_t WORD = 0x7fc5a5a5u;          // a NaN no arithmetic here produces
+    size_t n, at, total; std::vector<T> init; DevArr<T> dev;
+    static std::vector<T> fill(size_t total) {
+        std::vector<T> v(total);
+        const unsigned char pat[4] = {0xa5, 0xa5, 0xc5, 0x7f};
+        unsigned char* b = reinterpret_cast<unsigned char*>(v.data());
+        for (size_t i = 0; i < total * sizeof(T); ++i) b[i] = pat[i & 3];
+        return v;
+    }
+    Guarded(size_t n_, size_t guard, size_t shift, const T* host)
+        : n(n_), at(guard + shift), total(n_ + 2 * guard + shift), init(fill(total)), dev(total) {
+        if (host) std::copy(host, host + n, init.begin() + at); else std::fill(init.begin() + at, init.begin() + at + n, T());
+        HIPCHECK(copy_now(dev.p, init.data(), total * sizeof(T), hipMemcpyHostToDevice, nullptr));
+    }
+    T* data() { return dev.p + at; }
+    // the data into out (or nowhere); throws if anything outside it changed
+    void back(T* out, const char* what) {
+        std::vector<T> got(total);
+        dev.get(got.data(), total);
+        if (memcmp(got.data(), init.data(), at * sizeof(T)) || memcmp(got.data() + at + n, init.data() + at + n, (total - at - n) * sizeof(T)))
+            throw P3dError(std::string(what) + ": a launch wrote outside its buffer");
+        if (out) memcpy(out, got.data() + at, n * sizeof(T));
+    }
+    void unchanged(const char* what) {
+        std::vector<T> got(total);
+        dev.get(got.data(), total);
+        if (memcmp(got.data(), init.data(), total * sizeof(T))) throw P3dError(std::string(what) + ": a launch wrote to a read-only buffer");
+    }
+};
+void metric_args(int device, const void* a, const void* b, int n_maps, int n_pix, const void* out) {
+    if (!a || !b || !out) throw P3dError("null argument");
+    if (n_maps < 1 || n_pix < 1) throw P3dError("metrics need at least one map and one pixel");
+    int ndev = 0;
+    HIPCHECK(hipGetDeviceCount(&ndev));
+    if (ndev <= 0) throw P3dError("no HIP device: libp3dhip has no CPU fallback");
+    if (device < 0 || device >= ndev) throw P3dError("bad device ordinal");
+    HIPCHECK(hipSetDevice(device));
+}
+}  // namespace
+
+extern "C" {
+
+int p3d_metric_cc(int device, const float* a, const float* b, int n_maps, int n_pix, double* out) {
+    API_BEGIN
+    metric_args(device, a, b, n_maps, n_pix, out);
+    const size_t n = (size_t)n_maps * n_pix;
+    DevArr<float> da(n, a), db(n, b); DevArr<double> dout(n_maps);
+    HIPCHECK(p3d_metric_cc(da.p, db.p, n_maps, n_pix, dout.p, nullptr));
+    dout.get(out, n_maps);
+    API_END
+}
+int p3d_metric_sim(int device, const float* a, const float* b, int n_maps, int n_pix, double* out) {
+    API_BEGIN
+    metric_args(device, a, b, n_maps, n_pix, out);
+    const size_t n = (size_t)n_maps * n_pix;
+    DevArr<float> da(n, a), db(n, b); DevArr<double> dout(n_maps);
+    HIPCHECK(p3d_metric_sim(da.p, db.p, n_maps, n_pix, dout.p, nullptr));
+    dout.get(out, n_maps);
+    API_END
+}
+int p3d_metric_nss(int device, const float* sal, const float* fix, int n_maps, int n_pix, double* out) {
+    API_BEGIN
+    metric_args(device, sal, fix, n_maps, n_pix, out);
+    const size_t n = (size_t)n_maps * n_pix;
+    DevArr<float> da(n, sal), db(n, fix); DevArr<double> dout(n_maps);
+    HIPCHECK(p3d_metric_nss(da.p, db.p, n_maps, n_pix, dout.p, nullptr));
+    dout.get(out, n_maps);
+    API_END
+}
+int p3d_metric_auc_judd(int device, const float* sal, const float* fix, const float* jitter, int n_maps, int n_pix, double* out) {
+    API_BEGIN
+    metric_args(device, sal, fix, n_maps, n_pix, out);
+    const size_t n = (size_t)n_maps * n_pix;
+    const size_t pad = (size_t)p3d_metric_auc_pad(n_pix);
+    DevArr<float> da(n, sal), db(n, fix), dj(jitter ? n : 1, jitter), thr(pad * n_maps);
+    DevArr<int> cnt((pad + 1) * n_maps);
+    DevArr<double> dout(n_maps);
+    HIPCHECK(p3d_metric_auc_judd(da.p, db.p, jitter ? dj.p : nullptr, n_maps, n_pix, thr.p, cnt.p, dout.p, nullptr));
+    dout.get(out, n_maps);
+    API_END
+}
+int p3d_metric_auc_borji(int device, const float* sal, const float* fix, const int* rand_idx, int n_pix, int n_fix, int n_rep,
+                         double step_size, double* out) {
+    API_BEGIN
+    metric_args(device, sal, fix, 1, n_pix, out);
+    if (!rand_idx || n_rep < 1 || !(step_size > 0.0)) throw P3dError("AUC_Borji needs random indices, n_rep >= 1 and a positive step");
+    DevArr<float> da(n_pix, sal), db(n_pix, fix);
+    DevArr<int> fidx(n_pix), fcount(1);
+    HIPCHECK(p3d_metric_fix_index(db.p, n_pix, fidx.p, fcount.p, nullptr));
+    int have = 0;
+    fcount.get(&have, 1);
+    if (have == 0) { for (int i = 0; i < n_rep; ++i) out[i] = NAN; return 0; }      // "no fixation to predict"
+    if (have != n_fix) throw P3dError("AUC_Borji: n_fix = " + std::to_string(n_fix) + " but the fixation map has " + std::to_string(have) + " fixated pixels");
+    for (size_t i = 0; i < (size_t)n_fix * n_rep; ++i)
+        if (rand_idx[i] < 0 || rand_idx[i] >= n_pix) throw P3dError("AUC_Borji: random index out of range");
+    DevArr<int> dr((size_t)n_fix * n_rep, rand_idx);
+    DevArr<double> dout(n_rep);
+    HIPCHECK(p3d_metric_auc_borji(da.p, db.p, dr.p, n_pix, n_fix, n_rep, step_size, fidx.p, dout.p, nullptr));
+    dout.get(out, n_rep);
+    API_END
+}
+int p3d_mapf_frames(int device, const unsigned char* bgr, int n, int H0, int W0, const float mean_rgb[3], int H, int W, float* out) {
+    API_BEGIN
+    metric_args(device, bgr, mean_rgb, 1, 1, out);
+    if (n < 1 || H0 < 1 || W0 < 1 || H < 1 || W < 1) throw P3dError("mapf: empty frame");
+    DevArr<unsigned char> src((size_t)n * H0 * W0 * 3, bgr);
+    DevArr<float> dst((size_t)n * H * W * 3);
+    HIPCHECK(p3d_mapf_frames(src.p, n, H0, W0, dst.p, H, W, mean_rgb, nullptr));
+    dst.get(out, (size_t)n * H * W * 3);
+    API_END
+}
+int p3d_mapf_density(int device, const unsigned char* grey, int n, int H0, int W0, int H, int W, float* out) {
+    API_BEGIN
+    metric_args(device, grey, grey, 1, 1, out);
+    if (n < 1 || H0 < 1 || W0 < 1 || H < 1 || W < 1) throw P3dError("mapf: empty frame");
+    DevArr<unsigned char> src((size_t)n * H0 * W0, grey);
+    DevArr<float> dst((size_t)n * H * W);
+    HIPCHECK(p3d_mapf_density(src.p, n, H0, W0, dst.p, H, W, nullptr));
+    dst.get(out, (size_t)n * H * W);
+    API_END
+}
+
+// ---- ground-truth resolution (metrics_full.hip) ----------------------------------------------------------------------
+}  // extern "C"
+namespace {
+// Byte offsets of the buffers of one full-resolution evaluation inside one allocation (a first pass with base = null sizes it)
+struct Carve {
+    char* base = nullptr;
+    size_t off = 0;
+    template <typename T> T* take(size_t n) {
+        const size_t o = (off + 255) & ~(size_t)255;
+        off = o + (n > 0 ? n : 1) * sizeof(T);
+        return base ? (T*)(base + o) : nullptr;
+    }
+};
+// Buffers in the scratch of stream s.  layout(Carve&) only calls take: it runs once on a null base, which sizes the slab, and once
+// on the slab itself -- one statement list, so the two passes cannot drift apart.  -> the n_counters zeroed arrival counters.
+template <typename Layout>
+unsigned* carve_scratch(hipStream_t s, size_t n_counters, const Layout& layout) {
+    Carve c;
+    layout(c);
+    float* slab = nullptr;
+    unsigned* counters = nullptr;
+    HIPCHECK(p3d_stream_scratch(s, (c.off + 3) / 4, n_counters, &slab, &counters));
+    c = Carve{(char*)slab, 0};
+    layout(c);
+    return counters;
+}
+int next_pow2(int n) { int p = 1; while (p < n) p <<= 1; return p; }
+// every scratch buffer of P3dFullMaps / P3dFullBorji; slot offsets and meta come from n_fix[n_maps]
+void carve_full(Carve& c, P3dFullMaps& a, P3dFullBorji& r, const std::vector<int>& meta) {
+    const int B = a.n_maps;
+    size_t slots = 0;
+    for (int b = 0; b < B; ++b) slots += next_pow2(meta[b * 3]);
+    a.meta = c.take<int>((size_t)B * 3);
+    a.partA = c.take<double>((size_t)B * a.nblk * 11);
+    a.partB = c.take<double>((size_t)B * a.nblk * 8);
+    a.partC = c.take<double>((size_t)B * a.nblk);
+    a.stats = c.take<double>((size_t)B * P3D_FULL_STATS);
+    a.fixv = c.take<float>(slots);
+    a.cnt = c.take<int>(slots + B);
+    r.per_rep = c.take<double>((size_t)B * r.n_rep);
+}
+std::vector<int> full_meta(const int* n_fix, int n_maps, int n_rep, long long n_pix, size_t& n_idx) {
+    std::vector<int> meta((size_t)n_maps * 3);
+    long long slot = 0, idx = 0;
+    for (int b = 0; b < n_maps; ++b) {
+        if (n_fix[b] < 0 || n_fix[b] > n_pix) throw P3dError("n_fix out of range");
+        meta[b * 3 + 0] = n_fix[b];
+        meta[b * 3 + 1] = (int)slot;
+        meta[b * 3 + 2] = (int)idx;
+        slot += next_pow2(n_fix[b]);
+        idx += (long long)n_fix[b] * n_rep;
+        if (slot > INT32_MAX / 2 || idx > INT32_MAX) throw P3dError("too many fixations");
+    }
+    n_idx = (size_t)idx;
+    return meta;
+}
+void check_indices(const int* idx, size_t n, long long n_pix, const char* what) {
+    for (size_t i = 0; i < n; ++i)
+        if (idx[i] < 0 || idx[i] >= n_pix) throw P3dError(std::string(what) + ": random index out of range");
+}
+using StageTimer = p3d_handle::StageTimer;
+// ---- the smoothing / normalisation stage of p3d_set_postprocess (postprocess.hip), one launch sequence for every caller ------
+// What a setting asks for: the effective radius, its weights, the normalisation.  Built on the host, no HIP call.
+struct PostPlan {
+    bool on = false; int r = 0, norm = P3D_NORM_NONE; std::vector<float> taps;
+    PostPlan() {}
+    explicit PostPlan(const p3d_postprocess* cfg) {
+        if (!cfg) return;
+        r = p3d_handle::post_radius(*cfg);
+        norm = cfg->norm;
+        on = !p3d_handle::post_neutral(*cfg);
+        if (r > 0) taps = p3d_handle::post_taps(cfg->sigma, r);
+    }
+    void fits(int H, int W) const {
+        if (r > std::min(H, W) - 1)
+            throw P3dError("postprocess: radius " + std::to_string(r) + " exceeds min(H, W) - 1 = " + std::to_string(std::min(H, W) - 1));
+    }
+};
+using MatchPlan = p3d_handle::MatchCfg;
+// p3d_set_prior_stage's stage for one launch sequence: the mode, the weight and the prior map (device memory) with its size
+struct PriorStage {
+    int mode = P3D_PRIOR_OFF; float a = 0.f; const float* map = nullptr; int H = 0, W = 0;
+    bool on() const { return mode != P3D_PRIOR_OFF; }
+    // refused when the stage runs: no prior, or a prior of another size than the stage's
+    void fits(int sH, int sW) const {
+        if (!on()) return;
+        if (!map) throw P3dError("prior_stage: the handle has no prior (p3d_prior_finish or p3d_set_prior_map)");
+        if (H != sH || W != sW)
+            throw P3dError("prior_stage: the prior is " + std::to_string(H) + " x " + std::to_string(W) + ", the maps " + std::to_string(sH) + " x " + std::to_string(sW));
+    }
+};
+// The stages of one launch sequence between the resize and the read-out: p3d_set_postprocess's blur and normalisation,
+// p3d_set_prior_stage's stage after the blur, p3d_set_hist_match's matching after that and before the normalisation.
+struct Stages {
+    PostPlan post; MatchPlan match; PriorStage prior;
+    Stages() {}
+    // the handle's settings (each was parsed when it was set)
+    explicit Stages(const p3d_handle* h)
+        : post(h->post_on ? &h->post_cfg : nullptr), match(h->match_cfg), prior{h->prior_mode, h->prior_a, h->prior_map, h->prior_H, h->prior_W} {}
+    // a hook's arguments, refused in this order: cfg, match.  prior: H x W floats, or null until the hook has its copy on the device
+    Stages(const p3d_postprocess* cfg, const p3d_hist_match* m, const float* prior_, int mode, float a, int H, int W)
+        : post(cfg), match(p3d_handle::match_parse(m)), prior{mode, a, prior_, H, W} {}
+    bool chain() const { return post.on || match.on() || prior.on(); }
+    void fits(int H, int W) const { post.fits(H, W); prior.fits(H, W); }
+};
+// Device scratch of the stages for `chunk` maps of N pixels at a time
+struct StageScratch {
+    struct Post { float* maps = nullptr; float* tmp = nullptr; float* taps = nullptr; float* part = nullptr; float* mnmx = nullptr; } post;
+    struct Match {
+        float* part = nullptr; float* mnmx = nullptr; int* cnt = nullptr; double* cdf = nullptr; double* centre = nullptr; double* newv = nullptr;
+        double* tcdf = nullptr; double* tcentre = nullptr;      // TABLE: the uploaded table; DENSITY: the targets' tables [chunk][nb]
+        float* tpart = nullptr; float* tmnmx = nullptr;         // DENSITY: the targets' min / max
+    } match;
+    // own_maps: the maps live here too (no float32 output)
+    void carve(Carve& c, const Stages& st, int chunk, long long N, bool own_maps) {
+        const PostPlan& pl = st.post;
+        post.maps = own_maps ? c.take<float>((size_t)chunk * N) : nullptr;
+        post.tmp = pl.r > 0 ? c.take<float>((size_t)chunk * N) : nullptr;
+        post.taps = pl.r > 0 ? c.take<float>((size_t)2 * pl.r + 1) : nullptr;
+        post.part = pl.norm != P3D_NORM_NONE ? c.take<float>((size_t)chunk * p3d_post_blocks(N) * 2) : nullptr;
+        post.mnmx = pl.norm != P3D_NORM_NONE ? c.take<float>((size_t)chunk * 2) : nullptr;
+        const MatchPlan& mp = st.match;
+        if (!mp.on()) return;
+        const size_t k = (size_t)chunk * mp.nb;
+        const bool dens = mp.mode == P3D_MATCH_DENSITY;
+        match.part = c.take<float>((size_t)chunk * p3d_post_blocks(N) * 2);
+        match.mnmx = c.take<float>((size_t)chunk * 2);
+        match.cnt = c.take<int>(k);
+        match.cdf = c.take<double>(k); match.centre = c.take<double>(k); match.newv = c.take<double>(k);
+        match.tcdf = c.take<double>(dens ? k : mp.cdf.size());
+        match.tcentre = c.take<double>(dens ? k : mp.centres.size());
+        match.tpart = dens ? c.take<float>((size_t)chunk * p3d_post_blocks(N) * 2) : nullptr;
+        match.tmnmx = dens ? c.take<float>((size_t)chunk * 2) : nullptr;
+    }
+};
+// n maps of one source: map m's pixel (y, x) at p[m * map_stride + (y * w + x) * elem_stride] (device memory)
+struct PostRun { const float* p; long long map_stride; int elem_stride, n; };
+// One pass of `total` maps through the stages.  runs: the sources of h x w pixels, resized (float32) to H x W -- their n add up to
+// total; empty: f32 already holds the maps.  f32 [total][H][W] (device) receives the float32 result, or null: the maps pass through
+// the scratch's own.  u8 (device, 4-byte aligned) or null: map k's bytes, v * scale saturated, at u8_off + k * H * W.  density
+// [total][H][W] (device): under P3D_MATCH_DENSITY map k's target, evaluation's float32(b / 255.) density.
+struct PostJob {
+    std::vector<PostRun> runs; int total = 0, h = 0, w = 0, H = 0, W = 0;
+    float* f32 = nullptr; unsigned char* u8 = nullptr; long long u8_off = 0; float scale = 0.f;
+    const float* density = nullptr;
+};
+// resize -> blur -> prior -> match -> normalise (-> quantise) of a job's maps on stream s, at most `chunk` maps per pass through the
+// stages; a stage that is off is not issued.  counters: `chunk` zeroed arrival counters.  Queues only (after one synchronising
+// upload of the taps and of a table).
+void post_sequence(hipStream_t s, const Stages& st, const StageScratch& sc, unsigned* counters, int chunk, const PostJob& job) {
+    const PostPlan& pl = st.post;
+    const MatchPlan& mp = st.match;
+    const StageScratch::Post& ps = sc.post;
+    const StageScratch::Match& ms = sc.match;
+    const int H = job.H, W = job.W, total = job.total;
+    const std::vector<PostRun>& runs = job.runs;
+    st.fits(H, W);
+    const long long N = (long long)H * W;
+    if (pl.r > 0) HIPCHECK(copy_now(ps.taps, pl.taps.data(), pl.taps.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    const bool match = mp.on();
+    if (match && mp.mode == P3D_MATCH_DENSITY && !job.density) throw P3dError("hist_match: P3D_MATCH_DENSITY needs a ground-truth density (evaluation only)");
+    if (match && mp.mode == P3D_MATCH_TABLE) {
+        HIPCHECK(copy_now(ms.tcdf, mp.cdf.data(), mp.cdf.size() * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHECK(copy_now(ms.tcentre, mp.centres.data(), mp.centres.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    }
+    size_t ri = 0;
+    int rdone = 0;
+    for (int done = 0; done < total; done += chunk) {
+        const int cn = std::min(chunk, total - done);
+        float* maps = job.f32 ? job.f32 + (size_t)done * N : ps.maps;
+        for (int filled = 0; filled < cn && !runs.empty();) {
+            while (runs[ri].n == rdone) { ++ri; rdone = 0; }
+            const PostRun& R = runs[ri];
+            const int take = std::min(R.n - rdone, cn - filled);
+            PostArgs a;
+            a.src = R.p + (size_t)rdone * R.map_stride; a.map_stride = R.map_stride; a.elem_stride = R.elem_stride; a.h = job.h; a.w = job.w;
+            a.n = take; a.H = H; a.W = W; a.maps = maps + (size_t)filled * N;
+            HIPCHECK(p3d_post_launch(POST_RESIZE, a, s));
+            filled += take; rdone += take;
+        }
+        PostArgs a;
+        a.n = cn; a.H = H; a.W = W; a.maps = maps; a.tmp = ps.tmp; a.taps = ps.taps; a.r = pl.r; a.norm = pl.norm;
+        a.part = ps.part; a.mnmx = ps.mnmx; a.counter = counters; a.nblk = p3d_post_blocks(N);
+        a.u8 = job.u8; a.u8_off = job.u8_off + (long long)done * N; a.scale = job.scale;
+        if (st.prior.on()) { a.prior = st.prior.map; a.prior_mode = st.prior.mode; a.prior_a = st.prior.a; a.prior_b = (float)(1.0 - (double)st.prior.a); }
+        HistChain hc;
+        if (match) {
+            HistArgs& q = hc.source;           // (its maps are a's: p3d_post_launch fills them in)
+            q.nb = mp.nb; q.part = ms.part; q.mnmx = ms.mnmx; q.counter = counters; q.nblk = p3d_post_blocks(N);
+            q.cnt = ms.cnt; q.cdf = ms.cdf; q.centre = ms.centre; q.newv = ms.newv; q.tcdf = ms.tcdf; q.tcentre = ms.tcentre;
+            q.nt = mp.mode == P3D_MATCH_DENSITY ? mp.nb : (int)mp.cdf.size();
+            q.t_stride = mp.mode == P3D_MATCH_DENSITY ? mp.nb : 0;
+            if (mp.mode == P3D_MATCH_DENSITY) {
+                HistArgs& t = hc.target;
+                hc.has_target = true;
+                t.maps = job.density + (size_t)done * N; t.kind = HIST_DENSITY; t.n = cn; t.H = H; t.W = W; t.nb = mp.nb;
+                t.part = ms.tpart; t.mnmx = ms.tmnmx; t.counter = counters; t.nblk = q.nblk;
+                t.cnt = ms.cnt; t.cdf = ms.tcdf; t.centre = ms.tcentre;      // (the integer tables are zeroed before every count)
+            }
+            a.match = &hc;
+        }
+        for (int st_i = POST_BLUR_H; st_i < POST_STAGES; ++st_i) HIPCHECK(p3d_post_launch(st_i, a, s));
+    }
+}
+// Source maps of one evaluation: map m's pixel (y, x) at p[m * map_stride + (y * w + x) * elem_stride] (device memory)
+struct EvalSource { const float* p; long long map_stride; int elem_stride, n_maps, h, w; };
+// p3d_set_eval_extra's launch for one evaluation: the flags, the baseline of H x W floats and its statistics (device memory, IG
+// only), and where the [n_maps][2] values go on the host
+static_assert(P3D_EVAL_KLDIV == P3D_EXTRA_KLDIV && P3D_EVAL_INFO_GAIN == P3D_EXTRA_INFO_GAIN, "p3d_kernels.h names the header's flags");
+struct EvalExtra { int flags; const float* base; const double* bstat; int H, W; double* out; };
+// p3d_eval_shuffled_*'s part of one evaluation: the union of every clip's other fixations with its scan (device memory, fixpool.hip),
+// the counts on the host, the pool's size, the host's ranks [n_rows[b]][n_rep] per clip, and where the [n_maps][n_rep] areas and the
+// two HIP-event times (select; clean moments + borji) go on the host
+struct ShuffledEval {
+    const unsigned long long* uni; const unsigned* prefix; const unsigned* bsum; const unsigned* n_other_dev; const unsigned* n_other;
+    long long nw; int H, W; const int* ranks; const int* n_rows; int n_rep; double step; double* per_rep; double* ms;
+};
+// What every evaluation is given, on the host: density uint8 [n_maps][Hd][Wd]; fixation uint8 [n_maps][H][W]; jitter (or null)
+// float64 [n_maps][H][W]; AUC_Borji's draws borji_idx for n_fix [n_maps] fixations, n_rep and step_size; out [n_maps][5]
+struct EvalInputs {
+    const unsigned char* density; int Hd, Wd; const unsigned char* fixation; int H, W; const double* jitter;
+    const int* borji_idx; const int* n_fix; int n_rep; double step_size; double* out;
+};
+// One evaluation.  src: the source maps; prepare (or empty) queues whatever makes them readable -- it runs after the uploads,
+// inside the metric stage's time.  stage_ms (or null): the HIP-event times of the uploads and of the device pass.  extra, sh: null
+// when off.
+struct EvalRequest {
+    EvalSource src{};
+    std::function<void(hipStream_t)> prepare;
+    EvalInputs in{};
+    double* stage_ms = nullptr;
+    Stages stages;
+    const EvalExtra* extra = nullptr;
+    const ShuffledEval* sh = nullptr;
+};
+// The device pass of test.py's per-batch body on stream s, with the scratch of s: everything of p3d_eval_last_frames that does
+// not need the handle, so that p3d_debug_eval_maps runs the same launches on maps of the caller's.  Checks the arguments, lays
+// the buffers out in the stream's scratch, uploads, resizes the source maps (float32) and the density maps (uint8), runs the
+// metric passes, reads out[n_maps][5] back and compares n_fix with the device's counts.
+void eval_maps(hipStream_t s, const EvalRequest& rq) {
+    const EvalSource& src = rq.src;
+    const Stages& st = rq.stages;
+    const MatchPlan& match = st.match;
+    const EvalExtra* const extra = rq.extra;
+    const ShuffledEval* const sh = rq.sh;
+    const EvalInputs& in = rq.in;
+    const int Hd = in.Hd, Wd = in.Wd, H = in.H, W = in.W, n_rep = in.n_rep;
+    const int* const n_fix = in.n_fix;
+    const double* const jitter = in.jitter;
+    const bool chain = st.chain();
+    if (!src.p || !in.density || !in.fixation || !n_fix || !in.out) throw P3dError("null argument");
+    if (Hd < 1 || Wd < 1 || H < 1 || W < 1) throw P3dError("eval: empty map");
+    if ((long long)H * W > INT32_MAX / 2) throw P3dError("eval: map too large");
+    if (n_rep < 1 || !(in.step_size > 0.0)) throw P3dError("eval: AUC_Borji needs n_rep >= 1 and a positive step");
+    st.fits(H, W);
+    const bool xon = extra && extra->flags != 0;                 // p3d_set_eval_extra: one launch after pass A, on the scored map
+    if (xon && !extra->out) throw P3dError("null argument");
+    if (xon && (extra->flags & P3D_EVAL_INFO_GAIN) && (!extra->base || !extra->bstat || extra->H != H || extra->W != W))
+        throw P3dError("eval_extra: the baseline is " + std::to_string(extra->H) + " x " + std::to_string(extra->W) + ", the evaluation " +
+                       std::to_string(H) + " x " + std::to_string(W));
+    const int B = src.n_maps;
+    const long long N = (long long)H * W;
+    size_t n_idx = 0;
+    const std::vector<int> meta = full_meta(n_fix, B, n_rep, N, n_idx);
+    if (n_idx > 0 && !in.borji_idx) throw P3dError("eval: null random indices");
+    check_indices(in.borji_idx, n_idx, N, "eval");
+    // shuffled AUC (p3d_eval_shuffled_draws armed it): a second, clean P3dFullMaps on the same P with rows of its own per map
+    std::vector<int> meta2;
+    size_t n_idx2 = 0;
+    int max_rows = 0;
+    if (sh) {
+        if (sh->H != H || sh->W != W)
+            throw P3dError("eval_shuffled: the fixation pool is " + std::to_string(sh->H) + " x " + std::to_string(sh->W) + ", the evaluation " +
+                           std::to_string(H) + " x " + std::to_string(W));
+        if (!sh->per_rep) throw P3dError("null argument");
+        p3d_handle::shuffled_check_draws("eval_shuffled", sh->ranks, sh->n_rows, sh->n_other, B, sh->n_rep, sh->step);
+        for (int b = 0; b < B; ++b) {
+            const long long want = std::min<long long>(n_fix[b], sh->n_other[b]);
+            if (sh->n_rows[b] != want)
+                throw P3dError("eval_shuffled: clip " + std::to_string(b) + ": " + std::to_string(sh->n_rows[b]) + " rows of ranks, but min(n_fix, n_other) = " +
+                               std::to_string(want));
+            max_rows = std::max(max_rows, sh->n_rows[b]);
+        }
+        meta2 = full_meta(n_fix, B, 0, N, n_idx2);
+        long long at = 0;
+        for (int b = 0; b < B; ++b) { meta2[b * 3 + 2] = (int)at; at += (long long)sh->n_rows[b] * sh->n_rep; }
+        n_idx2 = (size_t)at;
+    }
+    P3dFullMaps a, a2;
+    P3dFullBorji r, r2;
+    int *ranks2 = nullptr, *idx2 = nullptr, *rows2 = nullptr;
+    a.fix_u8 = 1; a.n_pix = N; a.n_maps = B; a.nblk = p3d_full_blocks(N); a.out = nullptr;
+    r.n_rand = -1; r.n_rep = n_rep; r.step = in.step_size;
+    if (sh) {
+        a2.fix_u8 = 1; a2.n_pix = N; a2.n_maps = B; a2.nblk = a.nblk; a2.out = nullptr;
+        r2.n_rep = sh->n_rep; r2.step = sh->step;
+    }
+    float *P = nullptr, *D = nullptr;
+    unsigned char *dens = nullptr, *fixd = nullptr;
+    double *jit = nullptr, *dout = nullptr;
+    int* idx = nullptr;
+    StageScratch scratch;
+    P3dFullExtra x;
+    const int post_chunk = std::min(B, P3D_POST_CHUNK);
+    unsigned* const counters = carve_scratch(s, (size_t)B, [&](Carve& c) {
+        P = c.take<float>((size_t)B * N);
+        D = c.take<float>((size_t)B * N);
+        dens = c.take<unsigned char>((size_t)B * Hd * Wd);
+        fixd = c.take<unsigned char>((size_t)B * N);
+        jit = c.take<double>(jitter ? (size_t)B * N : 0);
+        idx = c.take<int>(n_idx);
+        dout = c.take<double>((size_t)B * 5);
+        carve_full(c, a, r, meta);
+        scratch.carve(c, st, post_chunk, N, false);
+        if (xon) { x.part = c.take<double>((size_t)B * a.nblk * P3D_FULL_EXTRA_PARTS); x.out = c.take<double>((size_t)B * 2); }
+        if (sh) {
+            ranks2 = c.take<int>(n_idx2); idx2 = c.take<int>(n_idx2); rows2 = c.take<int>((size_t)B);
+            carve_full(c, a2, r2, meta2);
+        }
+    });
+    a.P = P; a.D = D; a.fix = fixd; a.jit = jitter ? jit : nullptr; a.counter = counters; a.out = dout; r.idx = idx;
+    if (sh) { a2.P = P; a2.fix = fixd; a2.counter = counters; r2.idx = idx2; r2.n_rand_map = rows2; }
+
+    StageTimer tm(rq.stage_ms != nullptr, 3);
+    tm.mark(0, s);
+    HIPCHECK(copy_now(dens, in.density, (size_t)B * Hd * Wd, hipMemcpyHostToDevice, s));
+    HIPCHECK(copy_now(fixd, in.fixation, (size_t)B * N, hipMemcpyHostToDevice, s));
+    if (jitter) HIPCHECK(copy_now(jit, jitter, (size_t)B * N * sizeof(double), hipMemcpyHostToDevice, s));
+    if (n_idx) HIPCHECK(copy_now(idx, in.borji_idx, n_idx * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHECK(copy_now((void*)a.meta, meta.data(), meta.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    tm.mark(1, s);
+    if (rq.prepare) rq.prepare(s);
+    const bool density_first = match.mode == P3D_MATCH_DENSITY;              // the stage reads D: the same launch, issued earlier
+    if (density_first) HIPCHECK(p3d_mapf_density(dens, B, Hd, Wd, D, H, W, s));
+    if (chain) {
+        PostJob job;
+        job.runs = {{src.p, src.map_stride, src.elem_stride, B}};
+        job.total = B; job.h = src.h; job.w = src.w; job.H = H; job.W = W; job.f32 = P; job.density = D;
+        post_sequence(s, st, scratch, counters, post_chunk, job);
+    } else
+        HIPCHECK(p3d_resize_f32(src.p, src.map_stride, src.elem_stride, B, src.h, src.w, P, H, W, s));
+    if (!density_first) HIPCHECK(p3d_mapf_density(dens, B, Hd, Wd, D, H, W, s));      // test.py's density: uint8 resize (dataflow.py:236-238)
+    HIPCHECK(p3d_full_moments(a, s));
+    if (xon) {
+        x.flags = extra->flags; x.base = extra->base; x.bstat = extra->bstat;
+        HIPCHECK(p3d_full_extra(a, x, s));
+    }
+    HIPCHECK(p3d_full_rank(a, s));
+    HIPCHECK(p3d_full_borji(a, r, s));
+    if (sh) {                                  // after every launch of the plain evaluation: select, then the clean map's moments and borji
+        if (n_idx2) HIPCHECK(copy_now(ranks2, sh->ranks, n_idx2 * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHECK(copy_now(rows2, sh->n_rows, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHECK(copy_now((void*)a2.meta, meta2.data(), meta2.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        StageTimer t2(true, 3);
+        t2.mark(0, s);
+        if (n_idx2) {
+            FixSelectArgs q;
+            q.uni = sh->uni; q.prefix = sh->prefix; q.bsum = sh->bsum; q.n_other = sh->n_other_dev; q.nw = sh->nw; q.B = B;
+            q.nsb = p3d_fix_scan_blocks(sh->nw); q.n_rep = sh->n_rep; q.max_rows = max_rows; q.meta = a2.meta; q.n_rows = rows2; q.ranks = ranks2;
+            q.out = idx2;
+            HIPCHECK(p3d_fix_select_launch(q, s));
+        }
+        t2.mark(1, s);
+        HIPCHECK(p3d_full_moments(a2, s));
+        HIPCHECK(p3d_full_borji(a2, r2, s));
+        t2.mark(2, s);
+        HIPCHECK(copy_now(sh->per_rep, r2.per_rep, (size_t)B * sh->n_rep * sizeof(double), hipMemcpyDeviceToHost, s));
+        const float t0 = t2.ms(0), t1 = t2.ms(1);
+        if (sh->ms) { sh->ms[0] = t0; sh->ms[1] = t1; }
+    }
+    tm.mark(2, s);
+    std::vector<double> stats((size_t)B * P3D_FULL_STATS);
+    HIPCHECK(copy_now(in.out, dout, (size_t)B * 5 * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (xon) HIPCHECK(copy_now(extra->out, x.out, (size_t)B * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHECK(copy_now(stats.data(), a.stats, stats.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    if (rq.stage_ms) { rq.stage_ms[0] = tm.ms(0); rq.stage_ms[1] = tm.ms(1); }
+    for (int b = 0; b < B; ++b)
+        if ((long long)stats[(size_t)b * P3D_FULL_STATS + P3D_FULL_STAT_NFIX] != n_fix[b])
+            throw P3dError("eval: clip " + std::to_string(b) + ": n_fix = " + std::to_string(n_fix[b]) + " but its fixation map has " +
+                           std::to_string((long long)stats[(size_t)b * P3D_FULL_STATS + P3D_FULL_STAT_NFIX]) + " fixated pixels");
+}
+}  // namespace
+extern "C" {
+
+int p3d_resize_linear(int device, const float* src, int n, int h, int w, int H, int W, float* dst) {
+    API_BEGIN
+    metric_args(device, src, src, 1, 1, dst);
+    if (n < 1 || h < 1 || w < 1 || H < 1 || W < 1) throw P3dError("resize: empty map");
+    DevArr<float> s((size_t)n * h * w, src), d((size_t)n * H * W);
+    HIPCHECK(p3d_resize_f32(s.p, (long long)h * w, 1, n, h, w, d.p, H, W, nullptr));
+    d.get(dst, (size_t)n * H * W);
+    API_END
+}
+
+int p3d_metric_auc_shuffled(int device, const float* sal, const float* fix, const int* other_idx, int n_pix, int n_fix, int n_rand,
+                            int n_rep, double step_size, double* out) {
+    API_BEGIN
+    metric_args(device, sal, fix, 1, n_pix, out);
+    if (n_rep < 1 || !(step_size > 0.0)) throw P3dError("AUC_shuffled needs n_rep >= 1 and a positive step");
+    if (n_rand < 0 || n_rand > n_fix) throw P3dError("AUC_shuffled: n_rand must be in [0, n_fix]");
+    if (n_rand > 0 && !other_idx) throw P3dError("AUC_shuffled: null random indices");
+    check_indices(other_idx, (size_t)n_rand * n_rep, n_pix, "AUC_shuffled");
+    P3dFullMaps a;
+    P3dFullBorji r;
+    a.fix = nullptr; a.fix_u8 = 0; a.n_pix = n_pix; a.n_maps = 1; a.nblk = p3d_full_blocks(n_pix);
+    r.n_rand = n_rand; r.n_rep = n_rep; r.step = step_size;
+    size_t n_idx = 0;
+    const std::vector<int> meta = full_meta(&n_fix, 1, 0, n_pix, n_idx);
+    Carve c;
+    carve_full(c, a, r, meta);
+    DevArr<char> scratch(c.off);
+    c = Carve{scratch.p, 0};
+    carve_full(c, a, r, meta);
+    DevArr<float> dsal(n_pix, sal), dfix(n_pix, fix);
+    DevArr<int> didx((size_t)n_rand * n_rep, other_idx);
+    const unsigned zero = 0;
+    DevArr<unsigned> counter(1, &zero);
+    HIPCHECK(copy_now((void*)a.meta, meta.data(), meta.size() * sizeof(int), hipMemcpyHostToDevice, nullptr));
+    a.P = dsal.p; a.fix = dfix.p; a.counter = counter.p; r.idx = didx.p;
+    HIPCHECK(p3d_full_moments(a, nullptr));
+    double st[P3D_FULL_STATS];
+    HIPCHECK(copy_now(st, a.stats, sizeof(st), hipMemcpyDeviceToHost, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    if ((int)st[P3D_FULL_STAT_NFIX] != n_fix)
+        throw P3dError("AUC_shuffled: n_fix = " + std::to_string(n_fix) + " but the fixation map has " +
+                       std::to_string((long long)st[P3D_FULL_STAT_NFIX]) + " fixated pixels");
+    if (n_fix == 0) { for (int i = 0; i < n_rep; ++i) out[i] = NAN; return 0; }      // "no fixation to predict"
+    HIPCHECK(p3d_full_borji(a, r, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    HIPCHECK(copy_now(out, r.per_rep, (size_t)n_rep * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    API_END
+}
+
+int p3d_eval_last_frames(p3d_handle* h, const unsigned char* density, int Hd, int Wd, const unsigned char* fixation, int H, int W,
+                         const double* jitter, const int* borji_idx, const int* n_fix, int n_rep, double step_size, double* out,
+                         double* stage_ms) {
+    API_BEGIN
+    if (!h) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    // the prediction of the last forward pass, frame T-1 of every clip: [B][T][h][w] with an element stride of ld floats
+    Act* pr = h->pred;
+    const int T = pr->D;
+    const long long hw = (long long)pr->H * pr->W;
+    EvalRequest rq;
+    rq.src = {pr->p + (size_t)(T - 1) * hw * pr->ld, (long long)T * hw * pr->ld, pr->ld, pr->N, pr->H, pr->W};
+    if (pr->materialize && h->last_forward_fused) rq.prepare = pr->materialize;
+    rq.in = {density, Hd, Wd, fixation, H, W, jitter, borji_idx, n_fix, n_rep, step_size, out};
+    rq.stage_ms = stage_ms;
+    rq.stages = Stages(h);
+    // p3d_set_eval_extra: its launch joins the sequence; an evaluation of another size than the baseline's runs without it and
+    // p3d_last_eval_extra says so
+    EvalExtra extra{h->extra_flags, h->extra_base, h->extra_bstat, h->extra_H, h->extra_W, nullptr};
+    const bool fits = !(extra.flags & P3D_EVAL_INFO_GAIN) || (extra.H == H && extra.W == W);
+    std::vector<double> xv((size_t)pr->N * 2);
+    extra.out = xv.data();
+    if (extra.flags) { h->extra_state = p3d_handle::EXTRA_NONE; h->extra_eval_H = H; h->extra_eval_W = W; }
+    // p3d_eval_shuffled_draws armed this one evaluation: whatever becomes of it, the next one is plain again
+    const bool armed = h->sh_armed;
+    h->sh_armed = false;
+    std::vector<double> sv;
+    ShuffledEval sh{};
+    if (armed) {
+        if ((int)h->sh_n_other.size() != pr->N) throw P3dError("eval_shuffled: the union was taken for " + std::to_string(h->sh_n_other.size()) + " clips, the batch has " + std::to_string(pr->N));
+        sv.assign((size_t)pr->N * h->sh_n_rep, 0.0);
+        h->sh_have = false;
+        sh = ShuffledEval{h->sh_uni, h->sh_prefix, h->sh_bsum, h->sh_n_other_dev, h->sh_n_other.data(), h->fp_nw, h->fp_H, h->fp_W,
+                          h->sh_ranks.data(), h->sh_n_rows.data(), h->sh_n_rep, h->sh_step, sv.data(), h->fp_score_ms};
+    }
+    rq.extra = extra.flags && fits ? &extra : nullptr;
+    rq.sh = armed ? &sh : nullptr;
+    eval_maps(h->stream, rq);
+    if (armed) { h->sh_last.swap(sv); h->sh_have = true; }
+    if (extra.flags) {
+        h->extra_state = fits ? p3d_handle::EXTRA_HAVE : p3d_handle::EXTRA_SHAPE;
+        if (fits) h->extra_last.swap(xv);
+    }
+    API_END
+}
+
+// ---- p3d_set_eval_extra: KL divergence and information gain (full_pass_kl, metrics_full.hip) -----------------------------------
+int p3d_set_eval_extra(p3d_handle* h, int flags, const float* baseline, int H, int W) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->set_eval_extra(flags, baseline, H, W);
+    API_END
+}
+
+int p3d_get_eval_extra(p3d_handle* h, int* flags, const float** baseline, int* H, int* W) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    if (flags) *flags = h->extra_flags;
+    if (baseline) *baseline = h->extra_base_host.empty() ? nullptr : h->extra_base_host.data();
+    if (H) *H = h->extra_H;
+    if (W) *W = h->extra_W;
+    API_END
+}
+
+int p3d_last_eval_extra(p3d_handle* h, double* out, int64_t cap) {
+    API_BEGIN
+    if (!h || !out) throw P3dError("null argument");
+    if (!h->extra_flags) throw P3dError("last_eval_extra: the option is off (p3d_set_eval_extra)");
+    if (h->extra_state == p3d_handle::EXTRA_SHAPE)
+        throw P3dError("last_eval_extra: the baseline is " + std::to_string(h->extra_H) + " x " + std::to_string(h->extra_W) +
+                       ", the last evaluation scored " + std::to_string(h->extra_eval_H) + " x " + std::to_string(h->extra_eval_W) + " maps");
+    if (h->extra_state != p3d_handle::EXTRA_HAVE) throw P3dError("last_eval_extra: no evaluation has run since the option was set");
+    if (cap < (int64_t)h->extra_last.size())
+        throw P3dError("last_eval_extra: room for " + std::to_string(cap) + " doubles, " + std::to_string(h->extra_last.size()) + " needed");
+    std::copy(h->extra_last.begin(), h->extra_last.end(), out);
+    API_END
+}
+
+}  // extern "C"
+namespace {
+// op level: the statistics of n maps by full_stats3 (private scratch), then full_pass_kl with them
+struct Stats3 {
+    DevArr<double> part, out; DevArr<unsigned> counter;
+    Stats3(int n, long long N) : part((size_t)n * p3d_full_blocks(N) * P3D_FULL_STATS3_PARTS), out((size_t)n * 3),
+                                 counter((size_t)n, std::vector<unsigned>((size_t)n, 0u).data()) {}
+    void run(const float* maps, int n, long long N) {
+        P3dFullStats3 q;
+        q.maps = maps; q.n_pix = N; q.n_maps = n; q.nblk = p3d_full_blocks(N); q.part = part.p; q.counter = counter.p; q.out = out.p;
+        HIPCHECK(p3d_full_stats3(q, nullptr));
+    }
+};
+void metric_extra(int device, int flags, const float* map1, const float* map2, const float* baseline, int n_maps, int n_pix, double* out) {
+    metric_args(device, map1, map2, n_maps, n_pix, out);
+    if (n_maps > 65535) throw P3dError("at most 65535 maps per call");
+    const bool ig = flags == P3D_EVAL_INFO_GAIN;
+    if (ig) p3d_handle::eval_extra_check(flags, baseline, 1, n_pix);
+    const size_t n = (size_t)n_maps * n_pix;
+    DevArr<float> d1(n, map1), d2(n, map2), base(ig ? n_pix : 1, ig ? baseline : nullptr);
+    Stats3 s1(n_maps, n_pix), s2(n_maps, n_pix), sb(1, n_pix);
+    s1.run(d1.p, n_maps, n_pix);
+    if (ig) sb.run(base.p, 1, n_pix); else s2.run(d2.p, n_maps, n_pix);
+    P3dFullMaps a;
+    P3dFullExtra x;
+    a.P = d1.p; a.n_pix = n_pix; a.n_maps = n_maps; a.nblk = p3d_full_blocks(n_pix); a.counter = s1.counter.p;
+    if (ig) { a.fix = d2.p; a.fix_u8 = 0; x.base = base.p; x.bstat = sb.out.p; } else { a.D = d2.p; x.ystat = s2.out.p; }
+    DevArr<double> part((size_t)n_maps * a.nblk * P3D_FULL_EXTRA_PARTS), res((size_t)n_maps * 2);
+    x.flags = flags; x.sstat = s1.out.p; x.part = part.p; x.out = res.p;
+    HIPCHECK(p3d_full_extra(a, x, nullptr));
+    std::vector<double> both((size_t)n_maps * 2);
+    res.get(both.data(), both.size());
+    for (int b = 0; b < n_maps; ++b) out[b] = both[(size_t)b * 2 + (ig ? 1 : 0)];
+}
+}  // namespace
+extern "C" {
+
+int p3d_metric_kldiv(int device, const float* map1, const float* map2, int n_maps, int n_pix, double* out) {
+    API_BEGIN
+    metric_extra(device, P3D_EVAL_KLDIV, map1, map2, nullptr, n_maps, n_pix, out);
+    API_END
+}
+
+int p3d_metric_info_gain(int device, const float* sal, const float* fix, const float* baseline, int n_maps, int n_pix, double* out) {
+    API_BEGIN
+    if (!baseline) throw P3dError("null argument");
+    metric_extra(device, P3D_EVAL_INFO_GAIN, sal, fix, baseline, n_maps, n_pix, out);
+    API_END
+}
+
+int p3d_resize_linear_u8(int device, const float* src, int n, int h, int w, float scale, int H, int W, unsigned char* dst) {
+    API_BEGIN
+    metric_args(device, src, src, 1, 1, dst);
+    if (n < 1 || h < 1 || w < 1 || H < 1 || W < 1) throw P3dError("resize_u8: empty map");
+    if ((long long)H * W > INT32_MAX) throw P3dError("resize_u8: H * W exceeds the kernel's int32 in-map offsets");
+    DevArr<float> s((size_t)n * h * w, src);
+    DevArr<unsigned char> d((size_t)n * H * W);
+    HIPCHECK(p3d_resize_u8(s.p, (long long)h * w, 1, n, h, w, scale, d.p, 0, H, W, nullptr));
+    d.get(dst, (size_t)n * H * W);
+    API_END
+}
+
+}  // extern "C"
+namespace {
+// gen_pred.py's write-out of `maps` maps that live on the device, for p3d_pred_maps_u8 and p3d_video_maps_u8: the bytes, the
+// scratch of p3d_set_postprocess's stage and `extra` floats of the caller's share one slab of the stream's scratch.  sources runs
+// inside the device stage's time: it queues whatever makes the maps readable and names them as runs of maps of ph x pw pixels.
+// Off: one double-precision p3d_resize_u8 per run; on: the float32 resize / blur / normalise / byte sequence, P3D_POST_CHUNK maps
+// at a time.  Ends synchronised; stage_ms as p3d_pred_maps_u8's.
+void maps_u8_chain(p3d_handle* h, long long maps, int ph, int pw, float scale, int H, int W, unsigned char* out, double* stage_ms,
+                   size_t extra, const std::function<void(hipStream_t, float*, std::vector<PostRun>&)>& sources) {
+    const long long hw = (long long)H * W, bytes = maps * hw;
+    const hipStream_t s = h->stream;
+    // p3d_set_postprocess: the float32 chain resize -> blur -> normalise -> bytes, P3D_POST_CHUNK maps at a time; its scratch
+    // follows the bytes in the slab.  Off: the double-precision resize below, as before.
+    // p3d_set_hist_match: a table takes the same float32 chain, with its stage after the blur; the density mode has no target here
+    // p3d_set_prior_stage: the same float32 chain, with its stage after the blur
+    const Stages st(h);
+    st.post.fits(H, W);
+    if (st.match.mode == P3D_MATCH_DENSITY)
+        throw P3dError("hist_match: P3D_MATCH_DENSITY matches to a ground-truth density and runs in p3d_eval_last_frames only; written maps take P3D_MATCH_TABLE");
+    st.prior.fits(H, W);
+    const bool chain = st.chain();
+    const int post_chunk = (int)std::min<long long>(maps, P3D_POST_CHUNK);
+    StageScratch scratch;
+    unsigned char* d = nullptr;
+    float* ex = nullptr;
+    unsigned* const counters = carve_scratch(s, chain ? (size_t)post_chunk : 0, [&](Carve& c) {
+        d = c.take<unsigned char>((size_t)bytes);      // (the first take starts at offset 0: with nothing else, the slab is the bytes)
+        if (chain) scratch.carve(c, st, post_chunk, hw, true);
+        ex = extra ? c.take<float>(extra) : nullptr;
+    });
+    StageTimer tm(stage_ms != nullptr, 3);
+    tm.mark(0, s);
+    PostJob job;
+    sources(s, ex, job.runs);
+    if (chain) {
+        job.total = (int)maps; job.h = ph; job.w = pw; job.H = H; job.W = W; job.u8 = d; job.scale = scale;
+        post_sequence(s, st, scratch, counters, post_chunk, job);
+    } else {
+        long long off = 0;
+        for (const PostRun& r : job.runs) {
+            HIPCHECK(p3d_resize_u8(r.p, r.map_stride, r.elem_stride, r.n, ph, pw, scale, d, off, H, W, s));
+            off += r.n * hw;
+        }
+    }
+    tm.mark(1, s);
+    HIPCHECK(hipMemcpyAsync(out, d, (size_t)bytes, hipMemcpyDeviceToHost, s));
+    tm.mark(2, s);
+    HIPCHECK(hipStreamSynchronize(s));
+    if (stage_ms) { stage_ms[0] = tm.ms(0); stage_ms[1] = tm.ms(1); }
+}
+}  // namespace
+extern "C" {
+
+int p3d_pred_maps_u8(p3d_handle* h, const int* first_frame, float scale, int H, int W, unsigned char* out, double* stage_ms) {
+    API_BEGIN
+    if (!h || !first_frame || !out) throw P3dError("null argument");
+    if (H < 1 || W < 1) throw P3dError("pred_maps_u8: empty map");
+    if ((long long)H * W > INT32_MAX) throw P3dError("pred_maps_u8: H * W exceeds the kernel's int32 in-map offsets");
+    if (!h->pred_ready) throw P3dError("pred_maps_u8: the handle has no prediction yet (run a forward pass first)");
+    Act* pr = h->pred;
+    const int B = pr->N, T = pr->D;
+    long long maps = 0;
+    for (int b = 0; b < B; ++b) {
+        if (first_frame[b] < 0 || first_frame[b] > T)
+            throw P3dError("pred_maps_u8: first_frame[" + std::to_string(b) + "] = " + std::to_string(first_frame[b]) +
+                           " is outside [0, " + std::to_string(T) + "]");
+        maps += T - first_frame[b];
+    }
+    if (stage_ms) stage_ms[0] = stage_ms[1] = 0.0;
+    if (maps == 0) return 0;
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    // the prediction of the last forward pass: [B][T][h][w] with an element stride of ld floats; clip b's frames
+    // first_frame[b] .. T-1, packed after the maps of the clips before it
+    maps_u8_chain(h, maps, pr->H, pr->W, scale, H, W, out, stage_ms, 0, [&](hipStream_t s, float*, std::vector<PostRun>& runs) {
+        if (pr->materialize && h->last_forward_fused) pr->materialize(s);
+        const long long phw = (long long)pr->H * pr->W;
+        for (int b = 0; b < B; ++b) {
+            const int f0 = first_frame[b], n = T - f0;
+            if (n > 0) runs.push_back({pr->p + ((size_t)b * T + f0) * phw * pr->ld, phw * pr->ld, pr->ld, n});
+        }
+    });
+    API_END
+}
+
+// ---- p3d_set_postprocess and the op-level entry points of its stage ----------------------------------------------------------
+int p3d_set_postprocess(p3d_handle* h, const p3d_postprocess* cfg) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    h->set_postprocess(cfg);
+    API_END
+}
+
+int p3d_get_postprocess(p3d_handle* h, p3d_postprocess* cfg, int* on) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    if (cfg) *cfg = h->post_cfg;
+    if (on) *on = h->post_on ? 1 : 0;
+    API_END
+}
+
+int p3d_blur_taps(float sigma, int radius, float* taps, int cap, int* r) {
+    API_BEGIN
+    const p3d_postprocess cfg{sigma, radius, P3D_NORM_NONE};
+    const PostPlan plan(&cfg);
+    if (plan.r > 0) {
+        if (!taps || cap < 2 * plan.r + 1) throw P3dError("blur_taps: room for " + std::to_string(2 * plan.r + 1) + " floats is needed");
+        memcpy(taps, plan.taps.data(), plan.taps.size() * sizeof(float));
+    }
+    if (r) *r = plan.r;
+    API_END
+}
+
+int p3d_debug_blur_strip(int r, int* cols, int* rows, int* lds_bytes) {
+    API_BEGIN
+    if (r < 0 || r > P3D_BLUR_MAX_RADIUS || !cols || !rows || !lds_bytes) throw P3dError("blur_strip: radius in [0, 255] and three results");
+    const PostStrip st = p3d_post_strip(r);
+    *cols = st.cols; *rows = st.rows; *lds_bytes = st.lds_bytes;
+    API_END
+}
+
+int p3d_gaussian_blur(int device, const float* src, int n, int H, int W, float sigma, int radius, float* dst) {
+    API_BEGIN
+    const p3d_postprocess cfg{sigma, radius, P3D_NORM_NONE};
+    Stages st;
+    st.post = PostPlan(&cfg);
+    metric_args(device, src, src, 1, 1, dst);
+    if (n < 1 || H < 1 || W < 1) throw P3dError("gaussian_blur: empty map");
+    if ((long long)H * W > INT32_MAX) throw P3dError("gaussian_blur: H * W exceeds the kernels' int32 in-map offsets");
+    st.post.fits(H, W);
+    const long long N = (long long)H * W;
+    const int chunk = std::min(n, P3D_POST_CHUNK);
+    DevArr<float> maps((size_t)n * N, src);
+    StageScratch scratch;
+    unsigned* const counters = carve_scratch(nullptr, (size_t)chunk, [&](Carve& c) { scratch.carve(c, st, chunk, N, false); });
+    PostJob job;
+    job.total = n; job.h = H; job.w = W; job.H = H; job.W = W; job.f32 = maps.p;
+    post_sequence(nullptr, st, scratch, counters, chunk, job);
+    maps.get(dst, (size_t)n * N);
+    API_END
+}
+
+}  // extern "C"
+namespace {
+// Everything p3d_postprocess_maps_prior takes; the two hooks below it leave the match and the prior off
+struct PostHook {
+    int device; const float* maps; int n, h, w, elem_stride, H, W; const p3d_postprocess* cfg; const p3d_hist_match* match;
+    const float* prior; int mode; float a; float scale; float* out_f32; unsigned char* out_u8;
+};
+void postprocess_maps(const PostHook& q) {
+    const int n = q.n, H = q.H, W = q.W;
+    Stages st(q.cfg, q.match, nullptr, q.mode, q.a, H, W);
+    p3d_handle::prior_stage_check(q.mode, q.a);
+    if (st.prior.on()) p3d_handle::prior_map_check(q.prior, H, W);      // (the prior of the hook has the stage's size)
+    if (st.match.mode == P3D_MATCH_DENSITY) throw P3dError("hist_match: P3D_MATCH_DENSITY runs in evaluation only; supplied maps take P3D_MATCH_TABLE");
+    metric_args(q.device, q.maps, q.maps, 1, 1, q.maps);
+    if (n < 1 || q.h < 1 || q.w < 1 || q.elem_stride < 1 || H < 1 || W < 1) throw P3dError("postprocess_maps: empty map");
+    if ((long long)H * W > INT32_MAX) throw P3dError("postprocess_maps: H * W exceeds the kernels' int32 in-map offsets");
+    st.post.fits(H, W);
+    const long long N = (long long)H * W, per_map = (long long)q.h * q.w * q.elem_stride, ne = (long long)n * N;
+    const int chunk = std::min(n, P3D_POST_CHUNK);
+    DevArr<float> src((size_t)n * per_map, q.maps), dprior(st.prior.on() ? (size_t)N : 1, st.prior.on() ? q.prior : nullptr);
+    st.prior.map = dprior.p;
+    // the outputs between guards: 8 floats either side of out_f32; out_u8 at byte 19 of its buffer, so that the BYTE kernel's
+    // unaligned head and tail run
+    Guarded<float> fbuf(q.out_f32 ? (size_t)ne : 0, 8, 0, nullptr);
+    Guarded<unsigned char> bbuf(q.out_u8 ? (size_t)ne : 0, 16, 3, nullptr);
+    StageScratch scratch;
+    unsigned* const counters = carve_scratch(nullptr, (size_t)chunk, [&](Carve& c) { scratch.carve(c, st, chunk, N, !q.out_f32); });
+    PostJob job;
+    job.runs = {{src.p, per_map, q.elem_stride, n}};
+    job.total = n; job.h = q.h; job.w = q.w; job.H = H; job.W = W; job.scale = q.scale;
+    job.f32 = q.out_f32 ? fbuf.data() : nullptr;
+    job.u8 = q.out_u8 ? bbuf.dev.p : nullptr; job.u8_off = (long long)bbuf.at;
+    post_sequence(nullptr, st, scratch, counters, chunk, job);
+    if (q.out_f32) fbuf.back(q.out_f32, "postprocess_maps");
+    if (q.out_u8) bbuf.back(q.out_u8, "postprocess_maps");
+    if (!q.out_f32 && !q.out_u8) HIPCHECK(hipDeviceSynchronize());
+}
+
+// Device buffers of one op-level launch sequence of hist_match.hip on n maps (no stream scratch: private allocations)
+struct HistBufs {
+    DevArr<float> part, mnmx; DevArr<unsigned> counter; DevArr<int> cnt; DevArr<long long> counts; DevArr<double> cdf, centre, newv;
+    static std::vector<unsigned> zeros(int n) { return std::vector<unsigned>((size_t)n, 0u); }
+    HistBufs(int n, long long N, int nb)
+        : part((size_t)n * p3d_post_blocks(N) * 2), mnmx((size_t)n * 2), counter((size_t)n, zeros(n).data()), cnt((size_t)n * nb),
+          counts((size_t)n * nb), cdf((size_t)n * nb), centre((size_t)n * nb), newv((size_t)n * nb) {}
+    HistArgs args(const float* maps, int n, int H, int W, int nb) {
+        HistArgs a;
+        a.maps = maps; a.n = n; a.H = H; a.W = W; a.nb = nb; a.part = part.p; a.mnmx = mnmx.p; a.counter = counter.p;
+        a.nblk = p3d_post_blocks((long long)H * W); a.cnt = cnt.p; a.counts = counts.p; a.cdf = cdf.p; a.centre = centre.p; a.newv = newv.p;
+        return a;
+    }
+};
+void hist_shape(const char* what, const void* maps, const void* out, int n, int H, int W, int nbins) {
+    p3d_handle::match_bins(what, nbins);
+    if (!maps || !out) throw P3dError(std::string(what) + ": null argument");
+    if (n < 1 || n > 65535 || H < 1 || W < 1) throw P3dError(std::string(what) + ": 1 .. 65535 maps of at least one pixel");
+    if ((long long)H * W > INT32_MAX) throw P3dError(std::string(what) + ": H * W exceeds the kernels' int32 in-map offsets");
+}
+}  // namespace
+extern "C" {
+
+int p3d_postprocess_maps(int device, const float* maps, int n, int h, int w, int elem_stride, int H, int W,
+                         const p3d_postprocess* cfg, float scale, float* out_f32, unsigned char* out_u8) {
+    API_BEGIN
+    postprocess_maps({device, maps, n, h, w, elem_stride, H, W, cfg, nullptr, nullptr, P3D_PRIOR_OFF, 0.f, scale, out_f32, out_u8});
+    API_END
+}
+
+int p3d_postprocess_maps_match(int device, const float* maps, int n, int h, int w, int elem_stride, int H, int W,
+                               const p3d_postprocess* cfg, const p3d_hist_match* match, float scale, float* out_f32, unsigned char* out_u8) {
+    API_BEGIN
+    postprocess_maps({device, maps, n, h, w, elem_stride, H, W, cfg, match, nullptr, P3D_PRIOR_OFF, 0.f, scale, out_f32, out_u8});
+    API_END
+}
+
+int p3d_postprocess_maps_prior(int device, const float* maps, int n, int h, int w, int elem_stride, int H, int W, const p3d_postprocess* cfg,
+                               const p3d_hist_match* match, const float* prior, int mode, float a, float scale, float* out_f32,
+                               unsigned char* out_u8) {
+    API_BEGIN
+    postprocess_maps({device, maps, n, h, w, elem_stride, H, W, cfg, match, prior, mode, a, scale, out_f32, out_u8});
+    API_END
+}
+
+// ---- p3d_set_hist_match and the op-level entry points of its stage (hist_match.hip) ------------------------------------------
+int p3d_set_hist_match(p3d_handle* h, const p3d_hist_match* cfg) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    h->set_hist_match(cfg);
+    API_END
+}
+
+int p3d_get_hist_match(p3d_handle* h, p3d_hist_match* cfg) {
+    API_BEGIN
+    if (!h || !cfg) throw P3dError("null argument");
+    const p3d_handle::MatchCfg& m = h->match_cfg;
+    cfg->mode = m.mode; cfg->nbins = m.on() ? m.nb : 0; cfg->nt = (int)m.cdf.size();
+    cfg->cdf = m.cdf.empty() ? nullptr : m.cdf.data();
+    cfg->centres = m.centres.empty() ? nullptr : m.centres.data();
+    API_END
+}
+
+int p3d_cumulative_distribution(int device, const float* maps, int n, int H, int W, int nbins, int64_t* counts, double* cdf, double* centres) {
+    API_BEGIN
+    hist_shape("cumulative_distribution", maps, cdf, n, H, W, nbins);
+    if (!centres) throw P3dError("cumulative_distribution: null argument");
+    metric_args(device, maps, maps, 1, 1, cdf);
+    const long long N = (long long)H * W;
+    DevArr<float> src((size_t)n * N, maps);
+    HistBufs b(n, N, nbins);
+    const HistArgs a = b.args(src.p, n, H, W, nbins);
+    for (int st = 0; st < HIST_STAGES; ++st) HIPCHECK(p3d_hist_launch(st, a, nullptr));
+    b.cdf.get(cdf, (size_t)n * nbins);
+    b.centre.get(centres, (size_t)n * nbins);
+    if (counts) {
+        static_assert(sizeof(long long) == sizeof(int64_t), "counts are int64");
+        b.counts.get(reinterpret_cast<long long*>(counts), (size_t)n * nbins);
+    }
+    API_END
+}
+
+int p3d_match_hist(int device, const float* maps, int n, int H, int W, int nbins, const double* cdf_t, const double* centre_t, int n_tables,
+                   int nt, float* out) {
+    API_BEGIN
+    hist_shape("match_hist", maps, out, n, H, W, nbins);
+    if (n_tables != 1 && n_tables != n) throw P3dError("match_hist: one table, or one per map");
+    p3d_handle::match_table("match_hist", cdf_t, centre_t, nt, n_tables);
+    metric_args(device, maps, maps, 1, 1, out);
+    const long long N = (long long)H * W;
+    DevArr<float> src((size_t)n * N, maps), dst((size_t)n * N);
+    DevArr<double> tc((size_t)n_tables * nt, cdf_t), tx((size_t)n_tables * nt, centre_t);
+    HistBufs b(n, N, nbins);
+    HistArgs a = b.args(src.p, n, H, W, nbins);
+    a.tcdf = tc.p; a.tcentre = tx.p; a.nt = nt; a.t_stride = n_tables == 1 ? 0 : nt; a.out = dst.p;
+    for (int st = 0; st < HIST_STAGES; ++st) HIPCHECK(p3d_hist_launch(st, a, nullptr));
+    dst.get(out, (size_t)n * N);
+    API_END
+}
+
+int p3d_match_hist_maps(int device, const float* maps, const float* targets, int n, int H, int W, int nbins, float* out) {
+    API_BEGIN
+    hist_shape("match_hist_maps", maps, out, n, H, W, nbins);
+    if (!targets) throw P3dError("match_hist_maps: null argument");
+    metric_args(device, maps, maps, 1, 1, out);
+    const long long N = (long long)H * W;
+    DevArr<float> src((size_t)n * N, maps), tgt((size_t)n * N, targets), dst((size_t)n * N);
+    HistBufs bt(n, N, nbins), bs(n, N, nbins);
+    HistChain c;
+    c.has_target = true;
+    c.target = bt.args(tgt.p, n, H, W, nbins);
+    c.source = bs.args(src.p, n, H, W, nbins);
+    c.source.tcdf = bt.cdf.p; c.source.tcentre = bt.centre.p; c.source.nt = nbins; c.source.t_stride = nbins; c.source.out = dst.p;
+    HIPCHECK(p3d_hist_chain_launch(c, nullptr));
+    dst.get(out, (size_t)n * N);
+    API_END
+}
+
+}  // extern "C"
+namespace {
+// ---- fixation priors (include/p3d_hip.h; the handle's part in net_sched.inc, the kernels in prior.hip) -------------------------
+// Counts -> float32 -> BLUR -> NORM (max) on stream s: the conversion, then the shared launch sequence on one map, in place on
+// `map` [H * W] (device).  Returns the float32 maximum of the blurred counts (0: every count was zero, the map is left unscaled).
+float prior_finish_launches(hipStream_t s, const unsigned* count, int H, int W, const Stages& st, float* map) {
+    const long long N = (long long)H * W;
+    StageScratch scratch;
+    unsigned* const counters = carve_scratch(s, 1, [&](Carve& c) { scratch.carve(c, st, 1, N, false); });
+    HIPCHECK(p3d_prior_float(count, map, N, s));
+    PostJob job;
+    job.total = 1; job.h = H; job.w = W; job.H = H; job.W = W; job.f32 = map;
+    post_sequence(s, st, scratch, counters, 1, job);
+    float mnmx[2] = {0.f, 0.f};
+    HIPCHECK(copy_now(mnmx, scratch.post.mnmx, sizeof(mnmx), hipMemcpyDeviceToHost, s));
+    return mnmx[1];
+}
+Stages prior_plan(float sigma, int radius, int H, int W) {
+    const p3d_postprocess cfg{sigma, radius, P3D_NORM_MAX};
+    Stages st;
+    st.post = PostPlan(&cfg);                  // the blur's own refusals
+    st.post.fits(H, W);
+    return st;
+}
+void prior_finish(p3d_handle* h, float sigma, int radius, float* out) {
+    h->prior_need_open("prior_finish");
+    const int H = h->prior_acc_H, W = h->prior_acc_W;
+    const Stages plan = prior_plan(sigma, radius, H, W);
+    if (h->prior_n_maps < 1) throw P3dError("prior_finish: the accumulator holds no maps");
+    if (h->prior_underflowed()) throw P3dError("prior_finish: a subtraction took a count below zero (maps were taken out that were never added); open the accumulator again");
+    const hipStream_t s = h->stream;
+    DevArr<float> map((size_t)H * W);          // the handle's from prior_map_take on
+    StageTimer tm(true, 2);
+    tm.mark(0, s);
+    const float mx = prior_finish_launches(s, h->prior_count, H, W, plan, map.p);
+    tm.mark(1, s);
+    HIPCHECK(hipStreamSynchronize(s));
+    if (!(mx > 0.f)) throw P3dError("prior_finish: every count is zero");
+    h->prior_ms[1] = tm.ms(0);
+    if (out) HIPCHECK(copy_now(out, map.p, (size_t)H * W * sizeof(float), hipMemcpyDeviceToHost, s));
+    h->prior_map_take(map.p, H, W);
+    map.p = nullptr;
+}
+}  // namespace
+extern "C" {
+
+int p3d_prior_open(p3d_handle* h, int H, int W, int kind) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->prior_open(H, W, kind);
+    API_END
+}
+
+int p3d_prior_close(p3d_handle* h) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->prior_close();
+    API_END
+}
+
+int p3d_prior_info(p3d_handle* h, int* H, int* W, int* kind, int64_t* n_maps) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    h->prior_need_open("prior_info");
+    if (H) *H = h->prior_acc_H;
+    if (W) *W = h->prior_acc_W;
+    if (kind) *kind = h->prior_kind;
+    if (n_maps) *n_maps = h->prior_n_maps;
+    API_END
+}
+
+int p3d_prior_add(p3d_handle* h, const unsigned char* maps, int64_t n, int sign) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->prior_add(maps, n, sign);
+    API_END
+}
+
+int p3d_prior_counts(p3d_handle* h, uint32_t* out, int64_t* n_maps) {
+    API_BEGIN
+    if (!h || !out) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->prior_need_open("prior_counts");
+    if (h->prior_underflowed()) throw P3dError("prior_counts: a subtraction took a count below zero (maps were taken out that were never added); open the accumulator again");
+    HIPCHECK(copy_now(out, h->prior_count, (size_t)h->prior_acc_H * h->prior_acc_W * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (n_maps) *n_maps = h->prior_n_maps;
+    API_END
+}
+
+int p3d_prior_finish(p3d_handle* h, float sigma, int radius, float* out) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    prior_finish(h, sigma, radius, out);
+    API_END
+}
+
+int p3d_prior_last_ms(p3d_handle* h, double ms[2]) {
+    API_BEGIN
+    if (!h || !ms) throw P3dError("null argument");
+    ms[0] = h->prior_ms[0]; ms[1] = h->prior_ms[1];
+    API_END
+}
+
+int p3d_set_prior_map(p3d_handle* h, const float* map, int H, int W) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->set_prior_map(map, H, W);
+    API_END
+}
+
+int p3d_get_prior_map(p3d_handle* h, float* out, int64_t cap, int* H, int* W) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    if (H) *H = h->prior_H;
+    if (W) *W = h->prior_W;
+    if (out) {
+        if (!h->prior_map) throw P3dError("get_prior_map: the handle has no prior (p3d_prior_finish or p3d_set_prior_map)");
+        const int64_t n = (int64_t)h->prior_H * h->prior_W;
+        if (cap < n) throw P3dError("get_prior_map: room for " + std::to_string(cap) + " floats, " + std::to_string(n) + " needed");
+        HIPCHECK(hipSetDevice(h->cfg.device));
+        HIPCHECK(copy_now(out, h->prior_map, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    }
+    API_END
+}
+
+int p3d_set_prior_stage(p3d_handle* h, int mode, float a) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    h->set_prior_stage(mode, a);
+    API_END
+}
+
+int p3d_get_prior_stage(p3d_handle* h, int* mode, float* a) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    if (mode) *mode = h->prior_mode;
+    if (a) *a = h->prior_a;
+    API_END
+}
+
+int p3d_set_eval_extra_prior(p3d_handle* h, int flags) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->set_eval_extra_prior(flags);
+    API_END
+}
+
+int p3d_debug_prior_count(int device, int kind, const unsigned char* maps, int64_t n, int H, int W, int sign, const uint32_t* counts_in,
+                          int offset, uint32_t* counts_out, int* flag_out) {
+    API_BEGIN
+    metric_args(device, maps, maps, 1, 1, counts_out);
+    if (!flag_out) throw P3dError("null argument");
+    if (H < 1 || W < 1 || (long long)H * W > INT32_MAX / 2) throw P3dError("prior_count: maps are H x W bytes, 1 <= H * W <= 2^30");
+    if (n < 1 || n > P3D_PRIOR_MAX_MAPS) throw P3dError("prior_count: 1 .. P3D_PRIOR_MAX_MAPS maps");
+    if (kind != P3D_PRIOR_FIXATIONS && kind != P3D_PRIOR_BYTES) throw P3dError("prior_count: unknown kind " + std::to_string(kind));
+    if (sign != 1 && sign != -1) throw P3dError("prior_count: sign must be +1 or -1");
+    if (offset < 0 || offset > 3) throw P3dError("prior_count: offset in [0, 3]");
+    const size_t N = (size_t)H * W;
+    Guarded<unsigned char> src((size_t)n * N, 16, (size_t)offset, maps);
+    Guarded<uint32_t> cnt(N, 8, 0, counts_in), flag(1, 2, 0, nullptr);
+    PriorCountArgs a;
+    a.maps = src.data(); a.n = n; a.n_pix = (long long)N; a.kind = kind; a.sign = sign; a.count = cnt.data(); a.flag = flag.data();
+    HIPCHECK(p3d_prior_count_launch(a, nullptr));
+    uint32_t f = 0;
+    cnt.back(counts_out, "prior_count");
+    flag.back(&f, "prior_count");
+    src.unchanged("prior_count");
+    if (f > 1) throw P3dError("prior_count: the flag holds " + std::to_string(f));
+    *flag_out = (int)f;
+    API_END
+}
+
+int p3d_debug_prior_count_plan(int64_t n, int H, int W, int offset, int64_t* words, int64_t* singles, int* slices) {
+    API_BEGIN
+    if (!words || !singles || !slices) throw P3dError("null argument");
+    unsigned dummy[2];
+    PriorCountArgs a;
+    a.maps = reinterpret_cast<const unsigned char*>((uintptr_t)256 + (uintptr_t)(offset & 3)); a.n = n; a.n_pix = (long long)H * W;
+    a.count = dummy; a.flag = dummy + 1;
+    if (H < 1 || W < 1 || !p3d_prior_count_plan(a)) throw P3dError("prior_count_plan: arguments the launcher refuses");
+    *words = a.words; *singles = a.singles; *slices = a.slices;
+    API_END
+}
+
+int p3d_debug_prior_apply(int device, int mode, float a, const float* maps, int n, int H, int W, const float* prior, int offset, float* out) {
+    API_BEGIN
+    metric_args(device, maps, prior, 1, 1, out);
+    if (n < 1 || n > 65535 || H < 1 || W < 1 || (long long)H * W > INT32_MAX / 2) throw P3dError("prior_apply: 1 .. 65535 maps of H x W floats, 1 <= H * W <= 2^30");
+    p3d_handle::prior_stage_check(mode, a);
+    if (mode == P3D_PRIOR_OFF) throw P3dError("prior_apply: the mode is P3D_PRIOR_MUL or P3D_PRIOR_MIX");
+    if (offset < 0 || offset > 15) throw P3dError("prior_apply: offset in [0, 15]");
+    const size_t N = (size_t)H * W;
+    Guarded<float> v((size_t)n * N, 8, (size_t)(offset & 3), maps), g(N, 8, (size_t)((offset >> 2) & 3), prior);
+    PriorApplyArgs q;
+    q.maps = v.data(); q.prior = g.data(); q.n = n; q.n_pix = (int)N; q.mode = mode; q.nblk = p3d_post_blocks((long long)N);
+    q.a = a; q.b = (float)(1.0 - (double)a);
+    HIPCHECK(p3d_prior_apply_launch(q, nullptr));
+    v.back(out, "prior_apply");
+    g.unchanged("prior_apply");
+    API_END
+}
+
+// ---- fixation pool and shuffled AUC in the evaluation pass (include/p3d_hip.h; the handle's part in net_sched.inc, fixpool.hip) ----
+int p3d_fixpool_open(p3d_handle* h, int H, int W, int64_t capacity) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->fixpool_open(H, W, capacity);
+    API_END
+}
+
+int p3d_fixpool_close(p3d_handle* h) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->fixpool_close();
+    API_END
+}
+
+int p3d_fixpool_info(p3d_handle* h, int* H, int* W, int64_t* capacity, int64_t* words_per_map, int64_t* n_filled) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    h->fixpool_need_open("fixpool_info");
+    if (H) *H = h->fp_H;
+    if (W) *W = h->fp_W;
+    if (capacity) *capacity = h->fp_cap;
+    if (words_per_map) *words_per_map = h->fp_nw;
+    if (n_filled) *n_filled = (int64_t)std::count(h->fp_filled.begin(), h->fp_filled.end(), (char)1);
+    API_END
+}
+
+int p3d_fixpool_put(p3d_handle* h, int64_t first, const unsigned char* maps, int64_t n) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->fixpool_put(first, maps, n);
+    API_END
+}
+
+int p3d_fixpool_get(p3d_handle* h, int64_t first, int64_t n, uint64_t* words) {
+    API_BEGIN
+    if (!h || !words) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->fixpool_need_open("fixpool_get");
+    if (n < 1 || first < 0 || first > h->fp_cap - n)
+        throw P3dError("fixpool_get: slots " + std::to_string(first) + " .. " + std::to_string(first + n - 1) + " are not inside [0, " + std::to_string(h->fp_cap) + ")");
+    for (int64_t i = first; i < first + n; ++i)
+        if (!h->fp_filled[(size_t)i]) throw P3dError("fixpool_get: slot " + std::to_string(i) + " was never filled (p3d_fixpool_put)");
+    HIPCHECK(copy_now(words, h->fp_words + first * h->fp_nw, (size_t)n * h->fp_nw * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    API_END
+}
+
+int p3d_fixpool_last_ms(p3d_handle* h, double ms[4]) {
+    API_BEGIN
+    if (!h || !ms) throw P3dError("null argument");
+    ms[0] = h->fp_pack_ms; ms[1] = h->fp_union_ms; ms[2] = h->fp_score_ms[0]; ms[3] = h->fp_score_ms[1];
+    API_END
+}
+
+int p3d_eval_shuffled_begin(p3d_handle* h, const int* ids, int M, uint32_t* n_other_out) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->shuffled_begin(ids, h->pred->N, M, n_other_out);
+    API_END
+}
+
+int p3d_eval_shuffled_draws(p3d_handle* h, const int* ranks, const int* n_rows, int n_rep, double step) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    h->shuffled_draws(ranks, n_rows, n_rep, step);
+    API_END
+}
+
+int p3d_last_eval_shuffled(p3d_handle* h, double* per_rep, int64_t cap) {
+    API_BEGIN
+    if (!h || !per_rep) throw P3dError("null argument");
+    if (!h->sh_have) throw P3dError("last_eval_shuffled: no evaluation has run armed (p3d_eval_shuffled_draws)");
+    if (cap < (int64_t)h->sh_last.size())
+        throw P3dError("last_eval_shuffled: room for " + std::to_string(cap) + " doubles, " + std::to_string(h->sh_last.size()) + " needed");
+    std::copy(h->sh_last.begin(), h->sh_last.end(), per_rep);
+    API_END
+}
+
+}  // extern "C"
+namespace {
+void fix_shape(const char* what, int H, int W) {
+    if (H < 1 || W < 1 || (long long)H * W > INT32_MAX / 2) throw P3dError(std::string(what) + ": maps are H x W bytes, 1 <= H * W <= 2^30");
+}
+// op level: the union of B rows of M slots of a pool of `cap` packed maps, every device buffer between guard words
+struct FixUnionRun {
+    long long nw; int nsb, B;
+    Guarded<unsigned long long> pool, uni; Guarded<unsigned> prefix, bsum, n_other, counter; Guarded<int> ids;
+    FixUnionArgs a;
+    FixUnionRun(const uint64_t* words, int cap, int H, int W, const int* idv, int B_, int M)
+        : nw(p3d_fix_words((long long)H * W)), nsb(p3d_fix_scan_blocks(nw)), B(B_),
+          pool((size_t)cap * nw, 4, 0, reinterpret_cast<const unsigned long long*>(words)), uni((size_t)B_ * nw, 4, 0, nullptr),
+          prefix((size_t)B_ * nw, 8, 0, nullptr), bsum((size_t)B_ * nsb, 8, 0, nullptr), n_other((size_t)B_, 8, 0, nullptr),
+          counter((size_t)B_, 8, 0, nullptr), ids((size_t)B_ * M, 8, 0, idv) {
+        a.pool = pool.data(); a.nw = nw; a.ids = ids.data(); a.B = B; a.M = M; a.nsb = nsb;
+        a.uni = uni.data(); a.prefix = prefix.data(); a.bsum = bsum.data(); a.n_other = n_other.data(); a.counter = counter.data();
+        HIPCHECK(p3d_fix_union_launch(a, nullptr));
+    }
+    // uni [B][nw], the exclusive prefix over the whole map [B][nw] (block sum + block-local prefix), n_other [B]; guards intact
+    void back(uint64_t* uni_out, uint32_t* prefix_out, uint32_t* n_other_out, const char* what) {
+        std::vector<unsigned> local((size_t)B * nw), bs((size_t)B * nsb), zero((size_t)B, 1u);
+        uni.back(reinterpret_cast<unsigned long long*>(uni_out), what);
+        prefix.back(local.data(), what);
+        bsum.back(bs.data(), what);
+        n_other.back(n_other_out, what);
+        counter.back(zero.data(), what);
+        pool.unchanged(what);
+        ids.unchanged(what);
+        for (unsigned z : zero) if (z != 0u) throw P3dError(std::string(what) + ": an arrival counter was left at " + std::to_string(z));
+        if (prefix_out)
+            for (int b = 0; b < B; ++b)
+                for (long long k = 0; k < nw; ++k) prefix_out[(size_t)b * nw + k] = bs[(size_t)b * nsb + k / P3D_FIX_SCAN_WORDS] + local[(size_t)b * nw + k];
+    }
+};
+void fix_ids_check(const char* what, const int* ids, int cap, int B, int M) {
+    if (!ids) throw P3dError("null argument");
+    if (cap < 1 || B < 1 || B > 65535) throw P3dError(std::string(what) + ": 1 .. 65535 rows over a pool of at least one map");
+    if (M < 1 || M > 64) throw P3dError(std::string(what) + ": 1 .. 64 other maps per clip, not " + std::to_string(M));
+    for (size_t i = 0; i < (size_t)B * M; ++i)
+        if (ids[i] < 0 || ids[i] >= cap) throw P3dError(std::string(what) + ": slot " + std::to_string(ids[i]) + " is outside [0, " + std::to_string(cap) + ")");
+}
+}  // namespace
+extern "C" {
+
+int p3d_debug_fix_pack(int device, const unsigned char* maps, int n, int H, int W, int offset, uint64_t* words) {
+    API_BEGIN
+    metric_args(device, maps, maps, 1, 1, words);
+    fix_shape("fix_pack", H, W);
+    if (n < 1 || n > 65535) throw P3dError("fix_pack: 1 .. 65535 maps");
+    if (offset < 0 || offset > 3) throw P3dError("fix_pack: offset in [0, 3]");
+    const size_t N = (size_t)H * W, nw = (size_t)p3d_fix_words((long long)N);
+    Guarded<unsigned char> src((size_t)n * N, 16, (size_t)offset, maps);
+    Guarded<unsigned long long> dst((size_t)n * nw, 4, 0, nullptr);
+    FixPackArgs a;
+    a.maps = src.data(); a.n = n; a.n_pix = (long long)N; a.words = dst.data();
+    HIPCHECK(p3d_fix_pack_launch(a, nullptr));
+    dst.back(reinterpret_cast<unsigned long long*>(words), "fix_pack");
+    src.unchanged("fix_pack");
+    API_END
+}
+
+int p3d_debug_fix_union(int device, const uint64_t* pool, int capacity, int H, int W, const int* ids, int B, int M, uint64_t* uni,
+                        uint32_t* prefix, uint32_t* n_other) {
+    API_BEGIN
+    metric_args(device, pool, pool, 1, 1, uni);
+    if (!n_other) throw P3dError("null argument");
+    fix_shape("fix_union", H, W);
+    fix_ids_check("fix_union", ids, capacity, B, M);
+    FixUnionRun u(pool, capacity, H, W, ids, B, M);
+    u.back(uni, prefix, n_other, "fix_union");
+    API_END
+}
+
+int p3d_debug_fix_select(int device, const uint64_t* pool, int capacity, int H, int W, const int* ids, int B, int M, const int* ranks,
+                         const int* n_rows, int n_rep, int* out) {
+    API_BEGIN
+    metric_args(device, pool, pool, 1, 1, out);
+    fix_shape("fix_select", H, W);
+    fix_ids_check("fix_select", ids, capacity, B, M);
+    FixUnionRun u(pool, capacity, H, W, ids, B, M);
+    std::vector<uint32_t> n_other((size_t)B);
+    std::vector<uint64_t> uni((size_t)B * u.nw);
+    u.back(uni.data(), nullptr, n_other.data(), "fix_select");
+    p3d_handle::shuffled_check_draws("fix_select", ranks, n_rows, n_other.data(), B, n_rep, 1.0);
+    std::vector<int> meta((size_t)B * 3, 0);
+    long long at = 0;
+    int max_rows = 0;
+    for (int b = 0; b < B; ++b) { meta[b * 3 + 2] = (int)at; at += (long long)n_rows[b] * n_rep; max_rows = std::max(max_rows, n_rows[b]); }
+    if (at < 1) throw P3dError("fix_select: no rank to select");
+    Guarded<int> dranks((size_t)at, 8, 0, ranks), dout((size_t)at, 8, 0, nullptr), dmeta(meta.size(), 8, 0, meta.data()), drows((size_t)B, 8, 0, n_rows);
+    FixSelectArgs q;
+    q.uni = u.a.uni; q.prefix = u.a.prefix; q.bsum = u.a.bsum; q.n_other = u.a.n_other; q.nw = u.nw; q.B = B; q.nsb = u.nsb; q.n_rep = n_rep;
+    q.max_rows = max_rows; q.meta = dmeta.data(); q.n_rows = drows.data(); q.ranks = dranks.data(); q.out = dout.data();
+    HIPCHECK(p3d_fix_select_launch(q, nullptr));
+    dout.back(out, "fix_select");
+    dranks.unchanged("fix_select"); dmeta.unchanged("fix_select"); drows.unchanged("fix_select");
+    std::vector<uint64_t> uni2(uni.size());
+    std::vector<uint32_t> n2((size_t)B);
+    u.back(uni2.data(), nullptr, n2.data(), "fix_select");      // the select reads the union: same words, guards intact
+    if (uni2 != uni || n2 != n_other) throw P3dError("fix_select: a launch wrote to a read-only buffer");
+    API_END
+}
+
+// ---- the evaluation hooks: p3d_debug_eval_maps and its five supersets, one body ---------------------------------------------------
+}  // extern "C"
+namespace {
+// Everything the richest hook, p3d_debug_eval_maps_shuffled, takes; a hook that lacks an argument leaves it off / null.  The hooks
+// differ in two more ways than in what they pass, and each is a field: prior_as_baseline and shuffled.
+struct EvalHook {
+    int device; const float* maps; int n_maps, h, w, elem_stride; EvalInputs in;
+    const p3d_postprocess* cfg = nullptr; const p3d_hist_match* match = nullptr;
+    int flags = 0; const float* baseline = nullptr; double* extra = nullptr;
+    const float* prior = nullptr; int mode = P3D_PRIOR_OFF; float a = 0.f;
+    // _prior alone: P3D_EVAL_INFO_GAIN with a null baseline is not refused but scores over the prior, copied device to device (and
+    // the prior is then checked whatever the mode); every other hook leaves that case to eval_extra_check, which refuses it
+    bool prior_as_baseline = false;
+    // _shuffled alone: the pool is packed, the union taken and the armed sequence runs; the ten arguments below are its own
+    bool shuffled = false;
+    const unsigned char* pool_maps = nullptr; int capacity = 0; const int* ids = nullptr; int M = 0; const int* ranks = nullptr;
+    const int* n_rows = nullptr; int sh_n_rep = 0; double sh_step = 0.0; uint32_t* n_other = nullptr; double* per_rep = nullptr;
+};
+void eval_hook(const EvalHook& q) {
+    const EvalInputs& in = q.in;
+    const int H = in.H, W = in.W, n_maps = q.n_maps;
+    EvalRequest rq;
+    Stages& st = rq.stages;
+    st = Stages(nullptr, q.match, nullptr, q.mode, q.a, H, W);      // match_parse: ahead of any device call
+    metric_args(q.device, q.maps, q.maps, n_maps, 1, in.out);
+    if (q.h < 1 || q.w < 1 || q.elem_stride < 1) throw P3dError("eval: empty map");
+    if (q.flags && !q.extra) throw P3dError("null argument");
+    if (q.shuffled) {
+        if (!q.pool_maps || !q.n_other || !q.per_rep) throw P3dError("null argument");
+        fix_shape("eval_shuffled", H, W);
+        if (q.capacity < 1 || q.capacity > 65535) throw P3dError("eval_shuffled: 1 .. 65535 pool maps");
+        fix_ids_check("eval_shuffled", q.ids, q.capacity, n_maps, q.M);
+    }
+    p3d_handle::prior_stage_check(q.mode, q.a);
+    const bool from_prior = q.prior_as_baseline && (q.flags & P3D_EVAL_INFO_GAIN) && !q.baseline;
+    if (q.mode != P3D_PRIOR_OFF || from_prior || q.prior) p3d_handle::prior_map_check(q.prior, H, W);
+    if (!from_prior) p3d_handle::eval_extra_check(q.flags, q.baseline, H, W);           // (the baseline of the hook has the evaluation's size)
+    else if (q.flags & ~(P3D_EVAL_KLDIV | P3D_EVAL_INFO_GAIN)) throw P3dError("eval_extra: unknown flags " + std::to_string(q.flags));
+    const long long per_map = (long long)q.h * q.w * q.elem_stride;
+    const bool ig = (q.flags & P3D_EVAL_INFO_GAIN) != 0;
+    DevArr<float> src((size_t)n_maps * per_map, q.maps), base(ig ? (size_t)H * W : 1), dprior(q.prior ? (size_t)H * W : 1, q.prior);
+    DevArr<double> bstat(3);
+    if (ig) p3d_handle::eval_extra_upload(from_prior ? dprior.p : q.baseline, H, W, base.p, bstat.p, nullptr,
+                                          from_prior ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice);
+    const EvalExtra x{q.flags, ig ? base.p : nullptr, ig ? bstat.p : nullptr, H, W, q.extra};
+    st.prior.map = dprior.p;
+    // the pool packed here, then the union: the launches the handle issues, on private buffers
+    std::unique_ptr<FixUnionRun> u;
+    ShuffledEval sh{};
+    if (q.shuffled) {
+        const size_t N = (size_t)H * W, nw = (size_t)p3d_fix_words((long long)N);
+        DevArr<unsigned char> pm((size_t)q.capacity * N, q.pool_maps);
+        DevArr<unsigned long long> words((size_t)q.capacity * nw);
+        FixPackArgs pk;
+        pk.maps = pm.p; pk.n = q.capacity; pk.n_pix = (long long)N; pk.words = words.p;
+        HIPCHECK(p3d_fix_pack_launch(pk, nullptr));
+        std::vector<uint64_t> packed((size_t)q.capacity * nw);
+        words.get(reinterpret_cast<unsigned long long*>(packed.data()), packed.size());
+        u.reset(new FixUnionRun(packed.data(), q.capacity, H, W, q.ids, n_maps, q.M));
+        std::vector<uint64_t> uni((size_t)n_maps * nw);
+        u->back(uni.data(), nullptr, q.n_other, "eval_shuffled");
+        sh = ShuffledEval{u->a.uni, u->a.prefix, u->a.bsum, u->a.n_other, q.n_other, (long long)nw, H, W, q.ranks, q.n_rows, q.sh_n_rep, q.sh_step,
+                          q.per_rep, nullptr};
+    }
+    st.post = PostPlan(q.cfg);                 // its refusals come last, as they did when eval_maps parsed the setting
+    rq.src = {src.p, per_map, q.elem_stride, n_maps, q.h, q.w};
+    rq.in = in;
+    rq.extra = &x;
+    rq.sh = q.shuffled ? &sh : nullptr;
+    eval_maps(nullptr, rq);
+}
+}  // namespace
+extern "C" {
+
+int p3d_debug_eval_maps(int device, const float* maps, int n_maps, int h, int w, int elem_stride, const unsigned char* density,
+                        int Hd, int Wd, const unsigned char* fixation, int H, int W, const double* jitter, const int* borji_idx,
+                        const int* n_fix, int n_rep, double step_size, double* out) {
+    API_BEGIN
+    eval_hook({device, maps, n_maps, h, w, elem_stride, {density, Hd, Wd, fixation, H, W, jitter, borji_idx, n_fix, n_rep, step_size, out}});
+    API_END
+}
+
+int p3d_debug_eval_maps_post(int device, const float* maps, int n_maps, int h, int w, int elem_stride, const unsigned char* density,
+                             int Hd, int Wd, const unsigned char* fixation, int H, int W, const double* jitter, const int* borji_idx,
+                             const int* n_fix, int n_rep, double step_size, double* out, const p3d_postprocess* cfg) {
+    API_BEGIN
+    EvalHook q{device, maps, n_maps, h, w, elem_stride, {density, Hd, Wd, fixation, H, W, jitter, borji_idx, n_fix, n_rep, step_size, out}};
+    q.cfg = cfg;
+    eval_hook(q);
+    API_END
+}
+
+int p3d_debug_eval_maps_match(int device, const float* maps, int n_maps, int h, int w, int elem_stride, const unsigned char* density,
+                              int Hd, int Wd, const unsigned char* fixation, int H, int W, const double* jitter, const int* borji_idx,
+                              const int* n_fix, int n_rep, double step_size, double* out, const p3d_postprocess* cfg,
+                              const p3d_hist_match* match) {
+    API_BEGIN
+    EvalHook q{device, maps, n_maps, h, w, elem_stride, {density, Hd, Wd, fixation, H, W, jitter, borji_idx, n_fix, n_rep, step_size, out}};
+    q.cfg = cfg; q.match = match;
+    eval_hook(q);
+    API_END
+}
+
+int p3d_debug_eval_maps_extra(int device, const float* maps, int n_maps, int h, int w, int elem_stride, const unsigned char* density,
+                              int Hd, int Wd, const unsigned char* fixation, int H, int W, const double* jitter, const int* borji_idx,
+                              const int* n_fix, int n_rep, double step_size, double* out, const p3d_postprocess* cfg,
+                              const p3d_hist_match* match, int flags, const float* baseline, double* extra) {
+    API_BEGIN
+    EvalHook q{device, maps, n_maps, h, w, elem_stride, {density, Hd, Wd, fixation, H, W, jitter, borji_idx, n_fix, n_rep, step_size, out}};
+    q.cfg = cfg; q.match = match; q.flags = flags; q.baseline = baseline; q.extra = extra;
+    eval_hook(q);
+    API_END
+}
+
+int p3d_debug_eval_maps_prior(int device, const float* maps, int n_maps, int h, int w, int elem_stride, const unsigned char* density,
+                              int Hd, int Wd, const unsigned char* fixation, int H, int W, const double* jitter, const int* borji_idx,
+                              const int* n_fix, int n_rep, double step_size, double* out, const p3d_postprocess* cfg,
+                              const p3d_hist_match* match, int flags, const float* baseline, double* extra, const float* prior, int mode,
+                              float a) {
+    API_BEGIN
+    EvalHook q{device, maps, n_maps, h, w, elem_stride, {density, Hd, Wd, fixation, H, W, jitter, borji_idx, n_fix, n_rep, step_size, out}};
+    q.cfg = cfg; q.match = match; q.flags = flags; q.baseline = baseline; q.extra = extra; q.prior = prior; q.mode = mode; q.a = a;
+    q.prior_as_baseline = true;
+    eval_hook(q);
+    API_END
+}
+
+int p3d_debug_eval_maps_shuffled(int device, const float* maps, int n_maps, int h, int w, int elem_stride, const unsigned char* density,
+                                 int Hd, int Wd, const unsigned char* fixation, int H, int W, const double* jitter, const int* borji_idx,
+                                 const int* n_fix, int n_rep, double step_size, double* out, const p3d_postprocess* cfg,
+                                 const p3d_hist_match* match, int flags, const float* baseline, double* extra, const float* prior, int mode,
+                                 float a, const unsigned char* pool_maps, int capacity, const int* ids, int M, const int* ranks,
+                                 const int* n_rows, int sh_n_rep, double sh_step, uint32_t* n_other, double* per_rep) {
+    API_BEGIN
+    EvalHook q{device, maps, n_maps, h, w, elem_stride, {density, Hd, Wd, fixation, H, W, jitter, borji_idx, n_fix, n_rep, step_size, out}};
+    q.cfg = cfg; q.match = match; q.flags = flags; q.baseline = baseline; q.extra = extra; q.prior = prior; q.mode = mode; q.a = a;
+    q.shuffled = true;
+    q.pool_maps = pool_maps; q.capacity = capacity; q.ids = ids; q.M = M; q.ranks = ranks; q.n_rows = n_rows; q.sh_n_rep = sh_n_rep;
+    q.sh_step = sh_step; q.n_other = n_other; q.per_rep = per_rep;
+    eval_hook(q);
+    API_END
+}
+
+// ---- resident video inference (include/p3d_hip.h; the handle's part in net_sched.inc, the kernels in video.hip) --------------
+int p3d_video_open(p3d_handle* h, int frames, int mode) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->video_open(frames, mode);
+    API_END
+}
+
+int p3d_video_close(p3d_handle* h) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->video_close();
+    API_END
+}
+
+int p3d_video_info(p3d_handle* h, int* frames, int* mode, int* last_start) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    h->video_need_open("video_info");
+    if (frames) *frames = h->vid_F;
+    if (mode) *mode = h->vid_mode;
+    if (last_start) *last_start = h->vid_last;
+    API_END
+}
+
+int p3d_video_put_frames(p3d_handle* h, int first, const float* x, int n) {
+    API_BEGIN
+    if (!h || !x) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->video_put_frames(first, x, n);
+    API_END
+}
+
+int p3d_video_put_frames_u8(p3d_handle* h, int first, const unsigned char* bgr, int n, int H0, int W0, const float mean_rgb[3]) {
+    API_BEGIN
+    if (!h || !bgr || !mean_rgb) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->video_put_frames_u8(first, bgr, n, H0, W0, mean_rgb);
+    API_END
+}
+
+int p3d_video_predict(p3d_handle* h, const int* starts, int n_windows) {
+    API_BEGIN
+    if (!h || !starts) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->video_predict(starts, n_windows);
+    API_END
+}
+
+int p3d_video_last_ms(p3d_handle* h, double ms[2]) {
+    API_BEGIN
+    if (!h || !ms) throw P3dError("null argument");
+    if (!h->vid_is_open || !h->vid_timed) throw P3dError("video_last_ms: no p3d_video_predict has run on the open video");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    float g = 0.f, sc = 0.f;
+    HIPCHECK(hipEventElapsedTime(&g, h->ev_vid[0], h->ev_vid[1]));
+    HIPCHECK(hipEventElapsedTime(&sc, h->ev_vid[2], h->ev_vid[3]));
+    ms[0] = (double)g; ms[1] = (double)sc;
+    API_END
+}
+
+int p3d_video_get_maps(p3d_handle* h, int first, int n, float* maps, int32_t* counts) {
+    API_BEGIN
+    if (!h || !maps) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->video_need_open("video_get_maps");
+    h->video_range("video_get_maps", first, n);
+    const hipStream_t s = h->stream;
+    const size_t ne = (size_t)n * (size_t)h->vid_hw();
+    float* slab = nullptr;
+    unsigned* counters = nullptr;
+    const bool temporal = h->temporal_cfg.on();      // p3d_set_video_temporal: the filtered maps, into scratch under either mode
+    if (temporal) h->video_temporal_check("video_get_maps", first, n);      // (before the scratch is asked for: a refusal changes nothing)
+    if (temporal || h->vid_mode == VIDEO_MEAN) HIPCHECK(p3d_stream_scratch(s, ne, 0, &slab, &counters));
+    const float* src = temporal ? h->video_temporal("video_get_maps", first, n, slab, s) : h->video_finalize("video_get_maps", first, n, slab, s);
+    HIPCHECK(copy_now(maps, src, ne * 4, hipMemcpyDeviceToHost, s));
+    if (counts) memcpy(counts, h->vid_count.data() + first, (size_t)n * sizeof(int32_t));
+    API_END
+}
+
+int p3d_video_maps_u8(p3d_handle* h, int first, int n, float scale, int H, int W, unsigned char* out, double* stage_ms) {
+    API_BEGIN
+    if (!h || !out) throw P3dError("null argument");
+    if (H < 1 || W < 1) throw P3dError("video_maps_u8: empty map");
+    if ((long long)H * W > INT32_MAX) throw P3dError("video_maps_u8: H * W exceeds the kernel's int32 in-map offsets");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->video_need_open("video_maps_u8");
+    h->video_range("video_maps_u8", first, n);
+    const bool temporal = h->temporal_cfg.on();      // p3d_set_video_temporal: the chain runs on the filtered maps
+    if (temporal) h->video_temporal_check("video_maps_u8", first, n);      // (before the scratch is asked for: a refusal changes nothing)
+    for (int f = first; f < first + n; ++f)
+        if (h->vid_count[(size_t)f] == 0) throw P3dError("video_maps_u8: frame " + std::to_string(f) + " has no prediction yet (count 0)");
+    if (stage_ms) stage_ms[0] = stage_ms[1] = 0.0;
+    const long long phw = h->vid_hw();
+    maps_u8_chain(h, n, h->pred->H, h->pred->W, scale, H, W, out, stage_ms, temporal || h->vid_mode == VIDEO_MEAN ? (size_t)n * (size_t)phw : 0,
+                  [&](hipStream_t s, float* scratch, std::vector<PostRun>& runs) {
+                      runs.push_back({temporal ? h->video_temporal("video_maps_u8", first, n, scratch, s)
+                                               : h->video_finalize("video_maps_u8", first, n, scratch, s), phw, 1, n});
+                  });
+    API_END
+}
+
+// The three launches of video.hip from their launch descriptions, on host arrays.  Every device buffer sits `offset` elements past
+// a 16-byte boundary between guard elements; a guard or an input that a launch changed is an error.
+}  // extern "C"
+namespace {
+void video_hook_device(int device, int offset) {
+    int ndev = 0;
+    HIPCHECK(hipGetDeviceCount(&ndev));
+    if (ndev <= 0) throw P3dError("no HIP device: libp3dhip has no CPU fallback");
+    if (device < 0 || device >= ndev) throw P3dError("bad device ordinal");
+    if (offset < 0 || offset > 3) throw P3dError("video hook: offset is 0 .. 3");
+    HIPCHECK(hipSetDevice(device));
+}
+}  // namespace
+extern "C" {
+
+int p3d_debug_video_gather(int device, const float* store, int F, int T, int64_t frame_elems, const int* starts, int n_windows, int B,
+                           int offset, float* x) {
+    API_BEGIN
+    if (!store || !starts || !x) throw P3dError("null argument");
+    if (T < 1 || F < T || frame_elems < 1 || B < 1 || n_windows < 1 || n_windows > B) throw P3dError("video_gather: bad shape");
+    if ((int64_t)F * frame_elems > (int64_t)1 << 31 || (int64_t)B * T * frame_elems > (int64_t)1 << 31) throw P3dError("video_gather: the hook takes up to 2^31 floats");
+    video_hook_device(device, offset);
+    std::vector<int> padded(starts, starts + n_windows);
+    padded.resize((size_t)B, starts[n_windows - 1]);
+    const int64_t ns = (int64_t)F * frame_elems, nx = (int64_t)B * T * frame_elems;
+    Guarded<float> sb((size_t)ns, 8, (size_t)offset, store), xb((size_t)nx, 8, (size_t)offset, nullptr);
+    DevArr<int> tab((size_t)B, padded.data());
+    VideoGatherArgs a;
+    a.store = sb.data(); a.x = xb.data(); a.starts = tab.p; a.starts_host = padded.data(); a.B = B; a.T = T; a.F = F; a.frame_elems = frame_elems;
+    if (std::string(p3d_video_gather_desc(a).kernel) != "video_gather_kernel") throw P3dError("video_gather: launch description names another kernel");
+    HIPCHECK(p3d_video_gather(a, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    sb.unchanged("video_gather");
+    xb.back(x, "video_gather");
+    API_END
+}
+
+int p3d_debug_video_scatter(int device, int mode, const float* pred, int B, int T, int64_t hw, int ld, const int* starts, int n_windows,
+                            int F, int last_start, float* store, int32_t* count, int offset) {
+    API_BEGIN
+    if (!pred || !starts || !store || !count) throw P3dError("null argument");
+    if (hw < 1 || ld < 1) throw P3dError("video_scatter: bad shape");
+    const p3d_handle::VideoPlan p = p3d_handle::video_plan(mode, F, T, B, last_start, count, nullptr, starts, n_windows);
+    const int64_t np = (int64_t)B * T * hw * ld, ns = (int64_t)F * hw;
+    if (np > (int64_t)1 << 31 || ns > (int64_t)1 << 31) throw P3dError("video_scatter: the hook takes up to 2^31 floats");
+    video_hook_device(device, offset);
+    Guarded<float> pb((size_t)np, 8, (size_t)offset, pred), sb((size_t)ns, 8, (size_t)offset, store);
+    Guarded<int32_t> cb((size_t)F, 8, 0, count);
+    if (!p.dst.empty()) {
+        DevArr<P3dVideoDst> dst(p.dst.size(), p.dst.data());
+        DevArr<int> src(p.src.size(), p.src.data());
+        VideoScatterArgs a;
+        a.mode = mode; a.pred = pb.data(); a.ld = ld; a.maps = B * T; a.hw = hw;
+        a.store = sb.data(); a.count = cb.data(); a.F = F;
+        a.dst = dst.p; a.src = src.p; a.dst_host = p.dst.data(); a.src_host = p.src.data();
+        a.ndst = (int)p.dst.size(); a.nsrc = (int)p.src.size();
+        if (std::string(p3d_video_scatter_desc(a).kernel) != "video_scatter_kernel<" + std::to_string(mode) + ">")
+            throw P3dError("video_scatter: launch description names another kernel");
+        HIPCHECK(p3d_video_scatter(a, nullptr));
+        HIPCHECK(hipDeviceSynchronize());
+    }
+    pb.unchanged("video_scatter");
+    std::vector<int32_t> co((size_t)F);
+    cb.back(co.data(), "video_scatter");
+    if (memcmp(co.data(), p.count.data(), (size_t)F * 4) != 0) throw P3dError("video_scatter: the device's counts differ from the plan's");
+    sb.back(store, "video_scatter");
+    memcpy(count, p.count.data(), (size_t)F * 4);
+    API_END
+}
+
+int p3d_debug_video_mean(int device, const float* sum, const int32_t* count, int n, int64_t hw, int offset, float* out) {
+    API_BEGIN
+    if (!sum || !count || !out) throw P3dError("null argument");
+    if (n < 1 || hw < 1 || (int64_t)n * hw > (int64_t)1 << 31) throw P3dError("video_mean: bad shape");
+    for (int i = 0; i < n; ++i)
+        if (count[i] < 1) throw P3dError("video_mean: frame " + std::to_string(i) + " has count " + std::to_string(count[i]));
+    video_hook_device(device, offset);
+    const int64_t ne = (int64_t)n * hw;
+    Guarded<float> sb((size_t)ne, 8, (size_t)offset, sum), ob((size_t)ne, 8, (size_t)offset, nullptr);
+    DevArr<int32_t> cb((size_t)n, count);
+    VideoMeanArgs a;
+    a.sum = sb.data(); a.count = cb.p; a.out = ob.data(); a.n = n; a.hw = hw;
+    if (std::string(p3d_video_mean_desc(a).kernel) != "video_mean_kernel") throw P3dError("video_mean: launch description names another kernel");
+    HIPCHECK(p3d_video_mean(a, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    sb.unchanged("video_mean");
+    ob.back(out, "video_mean");
+    API_END
+}
+
+int p3d_debug_video_plan(int mode, int F, int T, int B, int last_start, const int32_t* count_in, const int* starts, int n_windows,
+                         int32_t* count_out) {
+    API_BEGIN
+    if (!count_out) throw P3dError("null argument");
+    const p3d_handle::VideoPlan p = p3d_handle::video_plan(mode, F, T, B, last_start, count_in, nullptr, starts, n_windows);
+    memcpy(count_out, p.count.data(), (size_t)F * sizeof(int32_t));
+    API_END
+}
+
+// ---- temporal smoothing of the video's maps at read-out (include/p3d_hip.h; the handle's part in net_sched.inc, temporal.hip) --
+int p3d_set_video_temporal(p3d_handle* h, const p3d_video_temporal* cfg) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    h->set_video_temporal(cfg);
+    API_END
+}
+
+int p3d_get_video_temporal(p3d_handle* h, p3d_video_temporal* cfg, int* on) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    if (cfg) *cfg = h->temporal_cfg.set;
+    if (on) *on = h->temporal_cfg.on() ? 1 : 0;
+    API_END
+}
+
+int p3d_video_temporal_last_ms(p3d_handle* h, double* ms) {
+    API_BEGIN
+    if (!h || !ms) throw P3dError("null argument");
+    if (!h->temporal_timed) throw P3dError("video_temporal_last_ms: no read-out has run the temporal stage");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    float t = 0.f;
+    HIPCHECK(hipEventElapsedTime(&t, h->ev_temporal[0], h->ev_temporal[1]));
+    *ms = (double)t;
+    API_END
+}
+
+}  // extern "C"
+namespace {
+// One temporal launch from its launch description on host arrays: store [F][hw], count [F] (null: every count 1) under `mode`,
+// frames first .. first + n - 1 -> out [n][hw].  Every refusal is decided before the first HIP call.
+void temporal_on_host(int device, int mode, const p3d_video_temporal* cfg, const float* store, const int32_t* count, int F, int64_t hw,
+                      int first, int n, int offset, float* out) {
+    if (!store || !out) throw P3dError("null argument");
+    if (mode != VIDEO_NEWEST && mode != VIDEO_MEAN) throw P3dError("video_temporal: mode " + std::to_string(mode) + " is neither P3D_VIDEO_NEWEST (0) nor P3D_VIDEO_MEAN (1)");
+    const p3d_handle::TemporalCfg t = p3d_handle::temporal_parse(cfg);
+    if (!t.on()) throw P3dError("video_temporal: the hook needs a kind (GAUSS or EMA)");
+    if (F < 1 || hw < 1 || (int64_t)F * hw > (int64_t)1 << 31) throw P3dError("video_temporal: bad shape");
+    std::vector<int32_t> ones;
+    if (!count) { ones.assign((size_t)F, 1); count = ones.data(); }
+    p3d_handle::temporal_check("video_temporal", t, F, first, n, count);
+    video_hook_device(device, offset);
+    const int64_t ns = (int64_t)F * hw, no = (int64_t)n * hw;
+    Guarded<float> sb((size_t)ns, 8, (size_t)offset, store), ob((size_t)no, 8, (size_t)offset, nullptr);
+    Guarded<int32_t> cb((size_t)F, 8, 0, count);
+    const VideoTemporalArgs a = p3d_handle::temporal_args(t, sb.data(), mode == VIDEO_MEAN ? cb.data() : nullptr, ob.data(), F, hw, first, n);
+    const std::string want = std::string(t.set.kind == P3D_TEMPORAL_GAUSS ? "video_temporal_gauss_kernel<" : "video_temporal_ema_kernel<") +
+                             (mode == VIDEO_MEAN ? "1>" : "0>");
+    if (std::string(p3d_video_temporal_desc(a).kernel) != want) throw P3dError("video_temporal: launch description names another kernel");
+    HIPCHECK(p3d_video_temporal_launch(a, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    sb.unchanged("video_temporal");
+    cb.unchanged("video_temporal");
+    ob.back(out, "video_temporal");
+}
+}  // namespace
+extern "C" {
+
+int p3d_temporal_filter(int device, const p3d_video_temporal* cfg, const float* maps, int F, int64_t hw, int first, int n, float* out) {
+    API_BEGIN
+    temporal_on_host(device, VIDEO_NEWEST, cfg, maps, nullptr, F, hw, first, n, 0, out);
+    API_END
+}
+
+int p3d_debug_video_temporal(int device, int mode, const p3d_video_temporal* cfg, const float* store, const int32_t* count, int F,
+                             int64_t hw, int first, int n, int offset, float* out) {
+    API_BEGIN
+    if (!count) throw P3dError("null argument");
+    if (offset < 0 || offset > 3) throw P3dError("video hook: offset is 0 .. 3");
+    temporal_on_host(device, mode, cfg, store, count, F, hw, first, n, offset, out);
+    API_END
+}
+
+int p3d_debug_video_temporal_desc(int mode, const p3d_video_temporal* cfg, int F, int64_t hw, int first, int n, char* kernel, int cap,
+                                  double* flops, double* bytes) {
+    API_BEGIN
+    if (!kernel || cap < 1 || !flops || !bytes) throw P3dError("null argument");
+    if (mode != VIDEO_NEWEST && mode != VIDEO_MEAN) throw P3dError("video_temporal: mode " + std::to_string(mode) + " is neither P3D_VIDEO_NEWEST (0) nor P3D_VIDEO_MEAN (1)");
+    const p3d_handle::TemporalCfg t = p3d_handle::temporal_parse(cfg);
+    if (!t.on()) throw P3dError("video_temporal: the hook needs a kind (GAUSS or EMA)");
+    if (F < 1 || hw < 1) throw P3dError("video_temporal: bad shape");
+    const std::vector<int32_t> ones((size_t)F, 1);
+    p3d_handle::temporal_check("video_temporal", t, F, first, n, ones.data());
+    // (the description reads no memory: the pointers only say which is there)
+    const float* some = reinterpret_cast<const float*>(kernel);
+    const VideoTemporalArgs a = p3d_handle::temporal_args(t, some, mode == VIDEO_MEAN ? ones.data() : nullptr, nullptr, F, hw, first, n);
+    const LaunchDesc d = p3d_video_temporal_desc(a);
+    snprintf(kernel, (size_t)cap, "%s", d.kernel);
+    *flops = d.flops; *bytes = d.bytes;
+    API_END
+}
+
+int p3d_debug_video_temporal_plan(int kind, int r, int64_t hw, int n, int* pixels_per_block, int* frames_per_block, int* lds_bytes) {
+    API_BEGIN
+    if (!pixels_per_block || !frames_per_block || !lds_bytes) throw P3dError("null argument");
+    if (kind != P3D_TEMPORAL_GAUSS && kind != P3D_TEMPORAL_EMA) throw P3dError("video_temporal_plan: the kind is GAUSS (1) or EMA (2)");
+    if (kind == P3D_TEMPORAL_GAUSS && (r < 1 || r > P3D_TEMPORAL_MAX_RADIUS))
+        throw P3dError("video_temporal_plan: radius must be in [1, " + std::to_string(P3D_TEMPORAL_MAX_RADIUS) + "]");
+    if (hw < 1 || n < 1) throw P3dError("video_temporal_plan: at least one pixel and one frame");
+    const VideoTemporalPlan p = p3d_video_temporal_plan(kind, r, hw, n);
+    *pixels_per_block = p.pixels_per_block; *frames_per_block = p.frames_per_block; *lds_bytes = p.lds_bytes;
+    API_END
+}
+
+// CRC-32C (Castagnoli) of a host buffer, slicing-by-8: the checksum of TensorFlow's checkpoint bundles
+// (tensorflow/core/lib/hash/crc32c.h), used by the Python reader / writer of sap3d_tensorflow_amd/tf_checkpoint.py on the
+// 248 MB of variables (train.py:180-185, 204-210, 266-267).  `crc` = running value (0 to start).
+uint32_t p3d_crc32c(const void* data, size_t n, uint32_t crc) {
+    static uint32_t T[8][256];
+    static bool ready = false;
+    if (!ready) {
+        for (uint32_t i = 0; i < 256; ++i) {
+            uint32_t c = i;
+            for (int k = 0; k < 8; ++k) c = (c >> 1) ^ ((c & 1) ? 0x82F63B78u : 0u);
+            T[0][i] = c;
+        }
+        for (uint32_t i = 0; i < 256; ++i)
+            for (int t = 1; t < 8; ++t) T[t][i] = (T[t - 1][i] >> 8) ^ T[0][T[t - 1][i] & 0xFF];
+        ready = true;
+    }
+    const unsigned char* p = (const unsigned char*)data;
+    uint32_t c = crc ^ 0xFFFFFFFFu;
+    while (n >= 8) {
+        uint32_t lo, hi;
+        memcpy(&lo, p, 4); memcpy(&hi, p + 4, 4);
+        lo ^= c;
+        c = T[7][lo & 0xFF] ^ T[6][(lo >> 8) & 0xFF] ^ T[5][(lo >> 16) & 0xFF] ^ T[4][lo >> 24] ^
+            T[3][hi & 0xFF] ^ T[2][(hi >> 8) & 0xFF] ^ T[1][(hi >> 16) & 0xFF] ^ T[0][hi >> 24];
+        p += 8; n -= 8;
+    }
+    while (n--) c = T[0][(c ^ *p++) & 0xFF] ^ (c >> 8);
+    return c ^ 0xFFFFFFFFu;
+}
+
+// ---- resident training set (include/p3d_hip.h; the handle's part in net_sched.inc, the kernel in trainset.hip) ------------------
+int p3d_trainset_open(p3d_handle* h, int n_videos, const int* frames, int frame_format, int flags, const float mean_rgb[3]) {
+    API_BEGIN
+    if (!h || !frames || !mean_rgb) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->trainset_open(n_videos, frames, frame_format, flags, mean_rgb);
+    API_END
+}
+
+int p3d_trainset_close(p3d_handle* h) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->trainset_close();
+    API_END
+}
+
+int p3d_trainset_info(p3d_handle* h, int* n_videos, int64_t* total_frames, int* frame_format, int* flags, int64_t* bytes) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    h->trainset_need_open("trainset_info");
+    if (n_videos) *n_videos = (int)h->ts_frames.size();
+    if (total_frames) *total_frames = h->ts_total();
+    if (frame_format) *frame_format = h->ts_format;
+    if (flags) *flags = h->ts_flags;
+    if (bytes) *bytes = (int64_t)(h->ts_fr_bytes + h->ts_den_bytes + h->ts_fix_bytes);
+    API_END
+}
+
+int p3d_trainset_video_info(p3d_handle* h, int video, int* frames, int* put_frames, int* put_density, int* put_fixations) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    h->trainset_need_open("trainset_video_info");
+    if (video < 0 || video >= (int)h->ts_frames.size())
+        throw P3dError("trainset_video_info: video " + std::to_string(video) + " is outside [0, " + std::to_string(h->ts_frames.size()) + ")");
+    const int F = h->ts_frames[(size_t)video];
+    int* out[3] = {put_frames, put_density, put_fixations};
+    for (int t = 0; t < 3; ++t) {
+        if (!out[t]) continue;
+        const unsigned char* p = h->ts_put[t].data() + h->ts_base[(size_t)video];
+        *out[t] = (int)std::count(p, p + F, (unsigned char)1);
+    }
+    if (frames) *frames = F;
+    API_END
+}
+
+int p3d_trainset_put_frames_u8(p3d_handle* h, int video, int first, const unsigned char* bgr, int n, int H0, int W0) {
+    API_BEGIN
+    if (!h || !bgr) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->trainset_put_frames_u8(video, first, bgr, n, H0, W0);
+    API_END
+}
+
+int p3d_trainset_put_frames(p3d_handle* h, int video, int first, const float* x, int n) {
+    API_BEGIN
+    if (!h || !x) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->trainset_put_frames(video, first, x, n);
+    API_END
+}
+
+int p3d_trainset_put_density_u8(p3d_handle* h, int video, int first, const unsigned char* grey, int n, int H0, int W0) {
+    API_BEGIN
+    if (!h || !grey) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->trainset_put_density_u8(video, first, grey, n, H0, W0);
+    API_END
+}
+
+int p3d_trainset_put_fixations(p3d_handle* h, int video, int first, const unsigned char* fix, int n) {
+    API_BEGIN
+    if (!h || !fix) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->trainset_put_fixations(video, first, fix, n);
+    API_END
+}
+
+int p3d_trainset_stage(p3d_handle* h, const int* video, const int* start, int n) {
+    API_BEGIN
+    if (!h || !video || !start) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->trainset_gather("trainset_stage", video, start, n, true);
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    API_END
+}
+
+int p3d_trainset_step(p3d_handle* h, const int* video, const int* start, int n, float dropout_rate, uint64_t seed, float* loss) {
+    API_BEGIN
+    if (!h || !video || !start) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->trainset_step_check();
+    h->trainset_gather("trainset_step", video, start, n, true);
+    h->check_fixations(true);
+    h->fix_fresh = false;
+    if (h->aug_on) h->augment_staged(seed, nullptr, nullptr);      // p3d_augment_inputs: from the staged buffers themselves
+    h->train_step_device(dropout_rate, seed);
+    const float l = h->read_loss();
+    if (loss) *loss = l;
+    API_END
+}
+
+int p3d_trainset_forward(p3d_handle* h, const int* video, const int* start, int n, float* pred) {
+    API_BEGIN
+    if (!h || !video || !start || !pred) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->trainset_gather("trainset_forward", video, start, n, false);
+    Ctx c; c.training = false; c.drop = 0.f; c.seed = 0; c.update_moving = false; c.s = h->stream;      // p3d_forward's pass
+    h->run_forward(c);
+    h->download_act(h->pred, pred);
+    API_END
+}
+
+int p3d_trainset_get_staged(p3d_handle* h, float* x, float* y, unsigned char* fix) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->trainset_need_open("trainset_get_staged");
+    if (fix && !h->d_fix) throw P3dError("trainset_get_staged: no fixation maps were ever staged");
+    const hipStream_t s = h->stream;
+    if (x) HIPCHECK(hipMemcpyAsync(x, h->x_in->p, (size_t)h->x_in->rows() * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (y) HIPCHECK(hipMemcpyAsync(y, h->d_y, (size_t)h->pred->rows() * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (fix) HIPCHECK(hipMemcpyAsync(fix, h->d_fix, (size_t)h->pred->rows(), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    API_END
+}
+
+int p3d_trainset_last_ms(p3d_handle* h, double* ms) {
+    API_BEGIN
+    if (!h || !ms) throw P3dError("null argument");
+    h->trainset_need_open("trainset_last_ms");
+    if (!h->ts_timed) throw P3dError("trainset_last_ms: nothing was staged from the open training set");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    float t = 0.f;
+    HIPCHECK(hipEventElapsedTime(&t, h->ev_ts[0], h->ev_ts[1]));
+    *ms = (double)t;
+    API_END
+}
+
+// The launch of trainset.hip from its launch description, on host arrays.  Every device buffer sits `offset` elements past a 16-byte
+// boundary between guard elements; a guard or a store that the launch changed is an error.
+int p3d_debug_trainset_gather(int device, int frame_format, const void* frames_store, const unsigned char* density_store,
+                              const unsigned char* fix_store, int n_videos, const int* frames, int T, int64_t hw, const float mean_rgb[3],
+                              const int* video, const int* start, const int* first, int B, int offset, float* x, float* y,
+                              unsigned char* fix) {
+    API_BEGIN
+    if (!frames_store || !frames || !mean_rgb || !video || !start || !x) throw P3dError("null argument");
+    if ((y != nullptr) != (density_store != nullptr) || (fix != nullptr) != (fix_store != nullptr))
+        throw P3dError("trainset_gather: a store and its output come together");
+    if (frame_format != P3D_TRAINSET_FRAMES_U8 && frame_format != P3D_TRAINSET_FRAMES_F32) throw P3dError("trainset_gather: unknown frame format");
+    if (n_videos < 1 || T < 1 || hw < 1 || B < 1) throw P3dError("trainset_gather: bad shape");
+    int64_t total = 0;
+    std::vector<int64_t> base((size_t)n_videos, 0);
+    for (int v = 0; v < n_videos; ++v) {
+        if (frames[v] < 1) throw P3dError("trainset_gather: a video without frames");
+        base[(size_t)v] = total;
+        total += frames[v];
+    }
+    if (total * hw * 3 > (int64_t)1 << 28 || (int64_t)B * T * hw * 3 > (int64_t)1 << 28) throw P3dError("trainset_gather: the hook takes up to 2^28 elements");
+    video_hook_device(device, offset);
+    std::vector<int> fr((size_t)B, 0);      // a row the wrapper will refuse keeps 0 here: it is never dereferenced
+    for (int k = 0; k < B; ++k)
+        fr[(size_t)k] = first ? first[k] : (video[k] >= 0 && video[k] < n_videos ? (int)(base[(size_t)video[k]] + start[k]) : 0);
+    const bool f32 = frame_format == P3D_TRAINSET_FRAMES_F32;
+    const int64_t npx = total * hw, nout = (int64_t)B * T * hw;
+    const size_t off = (size_t)offset;
+    Guarded<float> sf(f32 ? (size_t)npx * 3 : 0, 16, off, f32 ? (const float*)frames_store : nullptr), xb((size_t)nout * 3, 16, off, nullptr),
+        yb(y ? (size_t)nout : 0, 16, off, nullptr);
+    Guarded<unsigned char> su(f32 ? 0 : (size_t)npx * 3, 16, off, f32 ? nullptr : (const unsigned char*)frames_store),
+        sd(y ? (size_t)npx : 0, 16, off, density_store), sx(fix ? (size_t)npx : 0, 16, off, fix_store), fb(fix ? (size_t)nout : 0, 16, off, nullptr);
+    DevArr<int> tab((size_t)B, fr.data());
+    TrainsetGatherArgs a;
+    a.format = f32 ? TRAINSET_F32 : TRAINSET_U8;
+    a.frames = f32 ? (const void*)sf.data() : (const void*)su.data();
+    a.density = y ? sd.data() : nullptr; a.fixations = fix ? sx.data() : nullptr;
+    a.x = xb.data(); a.y = y ? yb.data() : nullptr; a.fix = fix ? fb.data() : nullptr;
+    a.first = tab.p; a.first_host = fr.data(); a.video_host = video; a.start_host = start; a.frames_host = frames; a.n_videos = n_videos;
+    a.B = B; a.T = T; a.hw = hw;
+    for (int c = 0; c < 3; ++c) a.mean[c] = mean_rgb[c];
+    if (std::string(p3d_trainset_gather_desc(a).kernel) != "trainset_gather_kernel<" + std::to_string(a.format) + ">")
+        throw P3dError("trainset_gather: launch description names another kernel");
+    HIPCHECK(p3d_trainset_gather(a, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    sf.unchanged("trainset_gather"); su.unchanged("trainset_gather"); sd.unchanged("trainset_gather"); sx.unchanged("trainset_gather");
+    xb.back(x, "trainset_gather");
+    yb.back(y, "trainset_gather");
+    fb.back(fix, "trainset_gather");
+    API_END
+}
+
+}  // extern "C"

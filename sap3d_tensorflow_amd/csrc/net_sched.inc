@@ -514,7 +514,7 @@
 
     // ---- smoothing and normalisation of output maps (p3d_set_postprocess) ------------------------------
     // Off by default, and off nothing here runs.  The setting is three numbers: the stage itself (postprocess.hip) is issued by
-    // the two users of the handle's prediction, p3d_eval_last_frames and p3d_pred_maps_u8 (net_abi.inc: post_sequence), with
+    // the two users of the handle's prediction, p3d_eval_last_frames and p3d_pred_maps_u8 (net_readout.inc: post_sequence), with
     // scratch from the stream pool at first use.  No step, launch list or captured graph ever names it.
     bool post_on = false;
     p3d_postprocess post_cfg{0.f, 0, P3D_NORM_NONE};
@@ -556,7 +556,7 @@
 
     // ---- histogram matching of output maps (p3d_set_hist_match; hist_match.hip) ---------------------------
     // Off by default, and off nothing here runs.  The setting is a mode, a bin count and (P3D_MATCH_TABLE) a copy of the caller's
-    // table; the stage is issued by post_sequence (net_abi.inc) between the blur and the normalisation, with scratch from the
+    // table; the stage is issued by post_sequence (net_readout.inc) between the blur and the normalisation, with scratch from the
     // stream pool at first use.  No step, launch list or captured graph ever names it.
     struct MatchCfg {
         int mode = P3D_MATCH_OFF, nb = 256;
@@ -687,12 +687,31 @@
         extra_base_host.swap(host);
     }
 
+    // ---- HIP-event times of the read-out's stages --------------------------------------------------------
+    // Up to three events of one call: created at once and only when `on`, destroyed with the timer, so a throw between two marks
+    // leaks none.  mark(i, s) records event i on s; ms(i) is the time from event i to event i + 1, both reached.
+    struct StageTimer {
+        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+        explicit StageTimer(bool on, int count) {
+            for (int i = 0; on && i < count; ++i) {
+                const hipError_t e = hipEventCreate(&ev[i]);
+                if (e != hipSuccess) { release(); HIPCHECK(e); }
+            }
+        }
+        StageTimer(const StageTimer&) = delete;
+        StageTimer& operator=(const StageTimer&) = delete;
+        ~StageTimer() { release(); }
+        void release() { for (auto& e : ev) if (e) { hipEventDestroy(e); e = nullptr; } }
+        void mark(int i, hipStream_t s) { if (ev[i]) HIPCHECK(hipEventRecord(ev[i], s)); }
+        float ms(int i) const { float t = 0.f; HIPCHECK(hipEventElapsedTime(&t, ev[i], ev[i + 1])); return t; }
+    };
+
     // ---- fixation priors (p3d_prior_*, p3d_set_prior_map, p3d_set_prior_stage; prior.hip) -------------------
     // Nothing exists before p3d_prior_open or p3d_set_prior_map, and off nothing here runs.  The accumulator (uint32 counts, the
     // underflow flag, a staging buffer for uploaded maps) and the finished prior map are private allocations (freed by
     // p3d_prior_close / when the map is replaced, and by the destructor; not part of `allocs`): no step, launch list or captured
-    // graph names them.  The stage is issued by post_sequence (net_abi.inc) after the blur.  The operations that need that
-    // sequence (finish) live in net_abi.inc.
+    // graph names them.  The stage is issued by post_sequence (net_readout.inc) after the blur.  The operations that need that
+    // sequence (finish) live in net_readout.inc.
     bool prior_is_open = false;
     int prior_kind = P3D_PRIOR_FIXATIONS, prior_acc_H = 0, prior_acc_W = 0;
     int64_t prior_n_maps = 0;
@@ -750,26 +769,20 @@
             if (prior_staging) hipFree(prior_staging);
             prior_staging = p; prior_staging_bytes = want;
         }
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
+        StageTimer tm(true, 2);
         double ms = 0.0;
-        hipError_t err = hipSuccess;
-        for (int64_t done = 0; done < n && err == hipSuccess; done += per) {
+        for (int64_t done = 0; done < n; done += per) {
             const int64_t cn = std::min(per, n - done);
             PriorCountArgs a;
             a.maps = prior_staging; a.n = cn; a.n_pix = (long long)N; a.kind = prior_kind; a.sign = sign; a.count = prior_count; a.flag = prior_flag;
-            err = copy_now(prior_staging, maps + (size_t)done * N, (size_t)cn * N, hipMemcpyHostToDevice, stream);
-            if (err == hipSuccess) err = hipEventRecord(ev[0], stream);
-            if (err == hipSuccess) err = p3d_prior_count_launch(a, stream);
-            if (err == hipSuccess) err = hipEventRecord(ev[1], stream);
-            if (err == hipSuccess) err = hipStreamSynchronize(stream);
-            float t = 0.f;
-            if (err == hipSuccess) err = hipEventElapsedTime(&t, ev[0], ev[1]);
-            ms += t;
-            if (err == hipSuccess) prior_n_maps += sign * cn;
+            HIPCHECK(copy_now(prior_staging, maps + (size_t)done * N, (size_t)cn * N, hipMemcpyHostToDevice, stream));
+            tm.mark(0, stream);
+            HIPCHECK(p3d_prior_count_launch(a, stream));
+            tm.mark(1, stream);
+            HIPCHECK(hipStreamSynchronize(stream));
+            ms += tm.ms(0);
+            prior_n_maps += sign * cn;
         }
-        for (auto& e : ev) hipEventDestroy(e);
-        HIPCHECK(err);
         prior_ms[0] = ms;
     }
     // a prior as the header asks for it: finite, not constant, 1 <= H * W <= 2^30
@@ -815,7 +828,7 @@
     // issued.  The pool (one bit per pixel and slot), its staging buffer and the union's buffers of one batch are private
     // allocations (freed by p3d_fixpool_close and the destructor; not part of `allocs`): no step, launch list or captured graph
     // names them.  The host keeps which slots are filled.  The evaluation's part (select, clean moments, borji) is issued by
-    // eval_maps (net_abi.inc).
+    // eval_maps (net_readout.inc).
     bool fp_is_open = false;
     int fp_H = 0, fp_W = 0;
     int64_t fp_cap = 0, fp_nw = 0;
@@ -871,26 +884,20 @@
             if (fp_staging) hipFree(fp_staging);
             fp_staging = p; fp_staging_bytes = want;
         }
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
+        StageTimer tm(true, 2);
         double ms = 0.0;
-        hipError_t err = hipSuccess;
-        for (int64_t done = 0; done < n && err == hipSuccess; done += per) {
+        for (int64_t done = 0; done < n; done += per) {
             const int64_t cn = std::min(per, n - done);
             FixPackArgs a;
             a.maps = fp_staging; a.n = cn; a.n_pix = (long long)N; a.words = fp_words + (first + done) * fp_nw;
-            err = copy_now(fp_staging, maps + (size_t)done * N, (size_t)cn * N, hipMemcpyHostToDevice, stream);
-            if (err == hipSuccess) err = hipEventRecord(ev[0], stream);
-            if (err == hipSuccess) err = p3d_fix_pack_launch(a, stream);
-            if (err == hipSuccess) err = hipEventRecord(ev[1], stream);
-            if (err == hipSuccess) err = hipStreamSynchronize(stream);
-            float t = 0.f;
-            if (err == hipSuccess) err = hipEventElapsedTime(&t, ev[0], ev[1]);
-            ms += t;
-            if (err == hipSuccess) std::fill(fp_filled.begin() + (first + done), fp_filled.begin() + (first + done + cn), 1);
+            HIPCHECK(copy_now(fp_staging, maps + (size_t)done * N, (size_t)cn * N, hipMemcpyHostToDevice, stream));
+            tm.mark(0, stream);
+            HIPCHECK(p3d_fix_pack_launch(a, stream));
+            tm.mark(1, stream);
+            HIPCHECK(hipStreamSynchronize(stream));
+            ms += tm.ms(0);
+            std::fill(fp_filled.begin() + (first + done), fp_filled.begin() + (first + done + cn), 1);
         }
-        for (auto& e : ev) hipEventDestroy(e);
-        HIPCHECK(err);
         fp_pack_ms = ms;
     }
     // ids [B][M]: every id a filled slot; 1 <= M <= 64
@@ -929,18 +936,13 @@
         FixUnionArgs a;
         a.pool = fp_words; a.nw = fp_nw; a.ids = sh_ids; a.B = B; a.M = M; a.nsb = nsb;
         a.uni = sh_uni; a.prefix = sh_prefix; a.bsum = sh_bsum; a.n_other = sh_n_other_dev; a.counter = sh_counter;
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
-        hipError_t err = hipEventRecord(ev[0], stream);
-        if (err == hipSuccess) err = p3d_fix_union_launch(a, stream);
-        if (err == hipSuccess) err = hipEventRecord(ev[1], stream);
+        StageTimer tm(true, 2);
+        tm.mark(0, stream);
+        HIPCHECK(p3d_fix_union_launch(a, stream));
+        tm.mark(1, stream);
         sh_n_other.assign((size_t)B, 0u);
-        if (err == hipSuccess) err = copy_now(sh_n_other.data(), sh_n_other_dev, (size_t)B * sizeof(unsigned), hipMemcpyDeviceToHost, stream);      // the one synchronisation
-        float t = 0.f;
-        if (err == hipSuccess) err = hipEventElapsedTime(&t, ev[0], ev[1]);
-        for (auto& e : ev) hipEventDestroy(e);
-        HIPCHECK(err);
-        fp_union_ms = t;
+        HIPCHECK(copy_now(sh_n_other.data(), sh_n_other_dev, (size_t)B * sizeof(unsigned), hipMemcpyDeviceToHost, stream));      // the one synchronisation
+        fp_union_ms = tm.ms(0);
         std::copy(sh_n_other.begin(), sh_n_other.end(), n_other_out);
         sh_begun = true;
     }

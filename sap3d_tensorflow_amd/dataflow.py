@@ -302,19 +302,19 @@ def postprocess_maps(maps, size, sigma=0., radius=0, norm="none", scale=None, de
     args = (device, m.ctypes.data_as(fp), m.shape[0], m.shape[1], m.shape[2], m.shape[3] if m.ndim == 4 else 1, int(H), int(W), C.byref(cfg))
     outs = (0.0 if scale is None else float(scale), out.ctypes.data_as(fp) if scale is None else None,
             out.ctypes.data_as(u8) if scale is not None else None)
-    if prior is not None or prior_mode != "off":
+    # the three entry points are supersets of one another: a call takes the lowest that has every argument it was given
+    level = 2 if prior is not None or prior_mode != "off" else 1 if hist_match is not None else 0
+    if level == 2:
         md = _prior_mode(prior_mode, prior_weight)
         g = None if prior is None else np.ascontiguousarray(prior, dtype=np.float32)
         if g is not None and g.shape != (H, W):
             raise ValueError("the prior is %s, the output %s" % (g.shape, (H, W)))
-        mc, keep = _match_cfg(hist_match if hist_match is not None else "off", nbins)
-        check(lib().p3d_postprocess_maps_prior(*(args + (C.byref(mc), g.ctypes.data_as(fp) if g is not None else None, md,
-                                                         float(prior_weight)) + outs)))
-    elif hist_match is None:
-        check(lib().p3d_postprocess_maps(*(args + outs)))
-    else:
-        mc, keep = _match_cfg(hist_match, nbins)
-        check(lib().p3d_postprocess_maps_match(*(args + (C.byref(mc),) + outs)))
+    mc, keep = _match_cfg(hist_match if hist_match is not None else "off", nbins)
+    if level >= 1:
+        args += (C.byref(mc),)
+    if level == 2:
+        args += (g.ctypes.data_as(fp) if g is not None else None, md, float(prior_weight))
+    check(getattr(lib(), "p3d_postprocess_maps" + ("", "_match", "_prior")[level])(*(args + outs)))
     return out[0] if single else out
 
 

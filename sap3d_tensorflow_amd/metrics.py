@@ -271,15 +271,44 @@ def evaluate_maps(maps, density, fixation, size=None, jitter=True, n_rep=100, st
             dens.shape[1], dens.shape[2], fix.ctypes.data_as(u8), int(H), int(W),
             _dp(jit) if jit is not None else None, idx.ctypes.data_as(ip), n_fix.ctypes.data_as(ip),
             int(n_rep), float(step_size), _dp(out))
-    if shuffled is not None:
-        from . import dataflow
-        from .dataflow import _match_cfg, _post_cfg, _prior_mode
+    # the hooks are supersets of one another: a call takes the lowest rung that has every argument it was given
+    from . import dataflow
+    from .dataflow import _match_cfg, _post_cfg, _prior_mode
+    rungs = ("", "_post", "_match", "_extra", "_prior", "_shuffled")
+    level = (5 if shuffled is not None else 4 if prior is not None else 3 if extra is not None else 2 if hist_match is not None
+             else 1 if postprocess is not None else 0)
+    if level == 5:
         pool = np.ascontiguousarray(shuffled["pool"])
         if pool.dtype != np.uint8 or pool.ndim != 3 or pool.shape[1:] != (H, W):
             raise ValueError("the pool is uint8 [capacity, %d, %d]" % (H, W))
         ids = np.ascontiguousarray(shuffled["others"], dtype=np.int32)
         if ids.ndim != 2 or ids.shape[0] != n:
             raise ValueError("others is int [%d, M]" % n)
+    flags = eval_extra_flags(extra) if extra is not None else 0
+    g = None if prior is None else np.ascontiguousarray(prior, dtype=np.float32)
+    if level == 4 and g.shape != (H, W):
+        raise ValueError("the prior is %s, the fixation maps %s" % (g.shape, (H, W)))
+    base = None
+    if level == 4 and isinstance(baseline, str):
+        if baseline != "prior":
+            raise ValueError("baseline %r: a [H, W] map or 'prior'" % (baseline,))
+    elif level >= 3 and baseline is not None:
+        base = np.ascontiguousarray(baseline, dtype=np.float32)
+        if level != 5 and base.shape != (H, W):         # (the shuffled rung leaves the shapes to the library)
+            raise ValueError("the baseline is %s, the fixation maps %s" % (base.shape, (H, W)))
+    post = postprocess or {}
+    cfg = _post_cfg(post.get("sigma", 0.), post.get("radius", 0), post.get("norm", "none"))
+    mc, keep = _match_cfg(hist_match if hist_match is not None else "off", nbins)
+    xout = np.full((n, 2), np.nan, np.float64) if level >= 4 else np.empty((n, 2), np.float64)
+    if level >= 1:
+        args += (C.byref(cfg),)
+    if level >= 2:
+        args += (C.byref(mc),)
+    if level >= 3:
+        args += (flags, _fp(base) if base is not None else None, _dp(xout))
+    if level >= 4:
+        args += (_fp(g) if g is not None else None, _prior_mode(prior_mode, prior_weight), float(prior_weight))
+    if level == 5:
         s_rep, s_step = int(shuffled.get("n_rep", 100)), float(shuffled.get("step_size", 0.1))
         n_other = shuffled.get("n_other")
         if n_other is None:
@@ -288,66 +317,8 @@ def evaluate_maps(maps, density, fixation, size=None, jitter=True, n_rep=100, st
             ranks, n_rows = (np.ascontiguousarray(v, dtype=np.int32) for v in (shuffled["ranks"], shuffled["n_rows"]))
         else:
             ranks, n_rows = shuffled_draws(n_fix, n_other, s_rep, shuffled.get("rng"))
-        flags = eval_extra_flags(extra) if extra is not None else 0
-        g = None if prior is None else np.ascontiguousarray(prior, dtype=np.float32)
-        base = None if baseline is None else np.ascontiguousarray(baseline, dtype=np.float32)
-        post = postprocess or {}
-        cfg = _post_cfg(post.get("sigma", 0.), post.get("radius", 0), post.get("norm", "none"))
-        mc, keep = _match_cfg(hist_match if hist_match is not None else "off", nbins)
-        xout = np.full((n, 2), np.nan, np.float64)
         got_other, per_rep = np.empty(n, np.uint32), np.empty((n, s_rep), np.float64)
-        check(lib().p3d_debug_eval_maps_shuffled(*(args + (C.byref(cfg), C.byref(mc), flags, _fp(base) if base is not None else None,
-                                                           _dp(xout), _fp(g) if g is not None else None, _prior_mode(prior_mode, prior_weight),
-                                                           float(prior_weight), pool.ctypes.data_as(u8), pool.shape[0], ids.ctypes.data_as(ip),
-                                                           ids.shape[1], ranks.ctypes.data_as(ip), n_rows.ctypes.data_as(ip), s_rep, s_step,
-                                                           got_other.ctypes.data_as(C.POINTER(C.c_uint32)), _dp(per_rep)))))
-        return out, xout, per_rep
-    if prior is not None:
-        from .dataflow import _match_cfg, _post_cfg, _prior_mode
-        flags = eval_extra_flags(extra) if extra is not None else 0
-        g = np.ascontiguousarray(prior, dtype=np.float32)
-        if g.shape != (H, W):
-            raise ValueError("the prior is %s, the fixation maps %s" % (g.shape, (H, W)))
-        base = None
-        if baseline is not None and not isinstance(baseline, str):
-            base = np.ascontiguousarray(baseline, dtype=np.float32)
-            if base.shape != (H, W):
-                raise ValueError("the baseline is %s, the fixation maps %s" % (base.shape, (H, W)))
-        elif baseline is not None and baseline != "prior":
-            raise ValueError("baseline %r: a [H, W] map or 'prior'" % (baseline,))
-        post = postprocess or {}
-        cfg = _post_cfg(post.get("sigma", 0.), post.get("radius", 0), post.get("norm", "none"))
-        mc, keep = _match_cfg(hist_match if hist_match is not None else "off", nbins)
-        xout = np.full((n, 2), np.nan, np.float64)
-        check(lib().p3d_debug_eval_maps_prior(*(args + (C.byref(cfg), C.byref(mc), flags, _fp(base) if base is not None else None,
-                                                        _dp(xout), _fp(g), _prior_mode(prior_mode, prior_weight),
-                                                        float(prior_weight)))))
-        return out, xout
-    if extra is not None:
-        from .dataflow import _match_cfg, _post_cfg
-        flags = eval_extra_flags(extra)
-        base = None
-        if baseline is not None:
-            base = np.ascontiguousarray(baseline, dtype=np.float32)
-            if base.shape != (H, W):
-                raise ValueError("the baseline is %s, the fixation maps %s" % (base.shape, (H, W)))
-        post = postprocess or {}
-        cfg = _post_cfg(post.get("sigma", 0.), post.get("radius", 0), post.get("norm", "none"))
-        mc, keep = _match_cfg(hist_match if hist_match is not None else "off", nbins)
-        xout = np.empty((n, 2), np.float64)
-        check(lib().p3d_debug_eval_maps_extra(*(args + (C.byref(cfg), C.byref(mc), flags, _fp(base) if base is not None else None,
-                                                        _dp(xout)))))
-        return out, xout
-    if hist_match is not None:
-        from .dataflow import _match_cfg, _post_cfg
-        post = postprocess or {}
-        cfg = _post_cfg(post.get("sigma", 0.), post.get("radius", 0), post.get("norm", "none"))
-        mc, keep = _match_cfg(hist_match, nbins)
-        check(lib().p3d_debug_eval_maps_match(*(args + (C.byref(cfg), C.byref(mc)))))
-    elif postprocess is None:
-        check(lib().p3d_debug_eval_maps(*args))
-    else:
-        from .dataflow import _post_cfg
-        cfg = _post_cfg(postprocess.get("sigma", 0.), postprocess.get("radius", 0), postprocess.get("norm", "none"))
-        check(lib().p3d_debug_eval_maps_post(*(args + (C.byref(cfg),))))
-    return out
+        args += (pool.ctypes.data_as(u8), pool.shape[0], ids.ctypes.data_as(ip), ids.shape[1], ranks.ctypes.data_as(ip),
+                 n_rows.ctypes.data_as(ip), s_rep, s_step, got_other.ctypes.data_as(C.POINTER(C.c_uint32)), _dp(per_rep))
+    check(getattr(lib(), "p3d_debug_eval_maps" + rungs[level])(*args))
+    return (out, xout, per_rep) if level == 5 else (out, xout) if level >= 3 else out
