@@ -78,7 +78,19 @@ int p3d_init_params(p3d_handle* h, uint64_t seed);
 /* ---- sess.run(pred, {x, dropout: 0, training: False})   train.py:225-226, gen_pred.py:151.
  *      x [B,T,H,W,3] -> pred [B,T,H,W,1].  `training` is the placeholder of train.py:145: it
  *      switches stem/decoder BN and dropout only; backbone BN always uses batch statistics
- *      (p3d.py:140,179,185,191).  Never updates moving statistics (UPDATE_OPS are not fetched). */
+ *      (p3d.py:140,179,185,191).  Never updates moving statistics (UPDATE_OPS are not fetched).
+ *
+ *      THE DROPOUT MASK (with training and dropout_rate in (0, 1); part of the contract, and the same for p3d_train_step,
+ *      p3d_backward and the *_device forms).  The structure's one dropout site holds an activation of `rows` = N*D*H*W rows of
+ *      C channels; its element (row, c) has the dense index e = row * C + c, whatever row stride the buffer has.  In uint64
+ *      arithmetic mod 2^64 (the SplitMix64 finaliser):
+ *          z = seed + 0x9E3779B97F4A7C15 * (e + 1);
+ *          z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;   z = (z ^ (z >> 27)) * 0x94D049BB133111EB;   z = z ^ (z >> 31);
+ *          u01(seed, e) = float32(z >> 40) * 2^-24                      (24 bits, in [0, 1))
+ *          keep(e) = u01(seed, e) >= dropout_rate                        (compared as float32)
+ *      A kept element is multiplied by 1 / (1 - dropout_rate), formed in float32, a dropped one is 0, forward and backward alike.  The
+ *      mask is this function of (seed, e) and nothing else: not of the launch shape, the path a pass takes, whether the seed is an
+ *      argument or read from device memory (captured steps), the replica or the run.  tests/dropout_ref.py replays it. */
 int p3d_forward(p3d_handle* h, const float* x, int training, float dropout_rate, uint64_t seed, float* pred);
 
 /* ---- B sliding windows of gen_pred.py:100-168 in one pass.  The reference runs sess.run(pred, ...) once per
@@ -92,7 +104,8 @@ int p3d_predict_windows(p3d_handle* h, const float* x, float* pred);
 /* ---- sess.run([train_op, loss], {x, y, dropout, training: True})   train.py:217-218.
  *      y [B,T,H,W]; the selected loss, Smooth-L1 by default (SUM, utils/network.py:49-62; p3d_set_loss), Adam on
  *      every trainable (train.py:168), BN moving-average updates (train.py:170-172).  With world_size > 1 the
- *      gradients are summed across replicas (RCCL) before Adam. */
+ *      gradients are summed across replicas (RCCL) before Adam.  The dropout mask is the function of (seed, element)
+ *      defined at p3d_forward. */
 int p3d_train_step(p3d_handle* h, const float* x, const float* y, float dropout_rate, uint64_t seed, float* loss);
 
 /* Parity hook: forward (training=True) + the selected loss (Smooth-L1 by default) + backward, no Adam, no moving-stat update.
@@ -505,16 +518,22 @@ int p3d_debug_conv_bn_stats(int device, const float* x, const int64_t xshape[5],
                             const int s[3], const float* bias, int transpose, float* moving, float* y, float* y2, float* stats,
                             int* nparts, const char** kernel);
 /* Test hook: one BatchNorm normalise / ReLU / add pass (modes of bn_apply: 0 relu(bn1(y1)), 1 relu(bn1(y1) + r),
- * 2 relu(bn1(y1) + bn2(y2)), 3 relu(bn1(y1)) + relu(bn2(y2)), 4 r + relu(bn1(y1))) on [M][C] inputs, forward then backward,
- * launched as the network launches it.  y2 is the second BN input or the residual r (null for mode 0).  params [bns][2][C] =
- * gamma, beta; moving [bns][2][C] = moving (mean, variance), updated in place when update_moving and the BN uses batch
- * statistics (batch1 / batch2).  dz: gradient of z; dy2 (modes 1-4): when acc2, holds the gradient to add to on entry.
- * grads [bns][2][C] = dgamma, dbeta.  path: 0 = the network's rule, 1 = small-tensor kernels, 2 = fold-apply, 3 = finalize +
- * apply (the last two with the three-launch backward); a forced path the kernels cannot take is an error.
- * info[3] = path taken, forward statistics partials per BN, backward partials. */
-int p3d_debug_bn_pass(int device, int mode, int64_t M, int C, const float* y1, const float* y2, const float* params, int batch1,
-                      int batch2, int update_moving, const float* dz, int acc2, int path, float* z, float* dy1, float* dy2,
-                      float* grads, float* moving, int* info);
+ * 2 relu(bn1(y1) + bn2(y2)), 3 relu(bn1(y1)) + relu(bn2(y2)), 4 r + relu(bn1(y1))) on M rows of C channels, forward then
+ * backward, launched as the network launches it.  The operands are channel slices of wider rows: y1 and dy1 [M][ld1] at column
+ * off1, y2 and dy2 [M][ld2] at off2 (y2 is the second BN input or the residual r; null for mode 0), z and dz [M][ldz] at offz;
+ * strides and offsets are multiples of 4 with off + C <= ld.  In/out: z, dy1 and dy2 keep what they held outside their C
+ * columns; dy2 (modes 1-4) holds the gradient to add to when acc2.  The stand-in statistics (p3d_bn_stats) read the slices too.
+ * params [bns][2][C] = gamma, beta; moving [bns][2][C] = moving (mean, variance), updated in place when update_moving and the
+ * BN uses batch statistics (batch1 / batch2).  grads [bns][2][C] = dgamma, dbeta.  drop_rate in [0, 1): the pass is a dropout
+ * site's (mask as defined at p3d_forward, e = row * C + c, scale 1 / (1 - drop_rate)) keyed by seed -- passed as an argument,
+ * or read from device memory when seed_dev; a rate outside [0, 1) is refused.  path: 0 = the network's rule (bn_path: a pass
+ * that drops out takes neither the small-tensor kernels nor fold-apply), 1 = small-tensor kernels, 2 = fold-apply, 3 = finalize
+ * + apply (the last two with the three-launch backward); a forced path the kernels cannot take -- 1 or 2 with drop_rate > 0
+ * among them -- is an error that writes nothing.  info[3] = path taken, forward statistics partials per BN, backward partials. */
+int p3d_debug_bn_pass(int device, int mode, int64_t M, int C, const float* y1, int ld1, int off1, const float* y2, int ld2, int off2,
+                      const float* params, int batch1, int batch2, int update_moving, const float* dz, int acc2, float drop_rate,
+                      uint64_t seed, int seed_dev, int path, float* z, int ldz, int offz, float* dy1, float* dy2, float* grads,
+                      float* moving, int* info);
 /* Test hook: one GroupNorm normalise / ReLU / add pass of the GN network (modes of gn.hip: 0 relu(gn1(y1)), 1 relu(gn1(y1) + r),
  * 2 relu(gn1(y1) + gn2(y2)) (forward only), 3 relu(gn1(y1)) + relu(gn2(y2)), 4 r + relu(gn1(y1)), 5 gn1(y1),
  * 6 relu(gn1(y1) + r * cs[n,c] * ss[row])) on N samples of R rows of C channels, G groups, forward then backward, launched as

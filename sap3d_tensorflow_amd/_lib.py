@@ -179,8 +179,9 @@ SIGNATURES = {
     "p3d_op_conv3d": (C.c_int, [C.c_int, _fp, _i64p, _fp, _i64p, _ip, _fp, _fp]),
     "p3d_debug_conv_bn_stats": (C.c_int, [C.c_int, _fp, _i64p, _fp, _fp, _i64p, _ip, _fp, C.c_int, _fp, _fp, _fp, _fp, _ip,
                                           C.POINTER(C.c_char_p)]),
-    "p3d_debug_bn_pass": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int,
-                                    C.c_int, _fp, _fp, _fp, _fp, _fp, _ip]),
+    "p3d_debug_bn_pass": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int, _fp, C.c_int, C.c_int, _fp, C.c_int, C.c_int, _fp, C.c_int,
+                                    C.c_int, C.c_int, _fp, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int, _fp, C.c_int, C.c_int,
+                                    _fp, _fp, _fp, _fp, _ip]),
     "p3d_debug_gn_pass": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _fp, C.c_int, _fp, C.c_int,
                                     C.c_int, _fp, _fp, _fp, _fp, C.c_int, C.c_float, C.c_uint64, C.c_int, _fp, _fp, _fp, _fp, _fp,
                                     _ip]),

@@ -1275,11 +1275,13 @@ int p3d_debug_conv_bn_stats(int device, const float* x, const int64_t xs[5], con
 }
 
 // One normalise / ReLU / add pass of bn_apply (net_ops.inc) on raw inputs, forward and then backward, through the path rule and
-// launch sequences the network itself calls (bn_path, bn_pass_forward / bn_pass_backward, net.hip).  The statistics of the
-// non-small paths come from p3d_bn_stats, standing in for the producer's epilogue.
-int p3d_debug_bn_pass(int device, int mode, int64_t M, int C, const float* y1, const float* y2, const float* params, int batch1,
-                      int batch2, int update_moving, const float* dz, int acc2, int path, float* z, float* dy1, float* dy2,
-                      float* grads, float* moving, int* info) {
+// launch sequences the network itself calls (bn_path, bn_pass_forward / bn_pass_backward, net.hip).  The operands are C-channel
+// slices of wider rows, as the network's are of its conv outputs and concat buffers, and the pass drops out as a dropout site's
+// does (set_dropout).  The statistics of the non-small paths come from p3d_bn_stats, standing in for the producer's epilogue.
+int p3d_debug_bn_pass(int device, int mode, int64_t M, int C, const float* y1, int ld1, int off1, const float* y2, int ld2, int off2,
+                      const float* params, int batch1, int batch2, int update_moving, const float* dz, int acc2, float drop_rate,
+                      uint64_t seed, int seed_dev, int path, float* z, int ldz, int offz, float* dy1, float* dy2, float* grads,
+                      float* moving, int* info) {
     API_BEGIN
     HIPCHECK(hipSetDevice(device));
     if (mode < 0 || mode > 4) throw P3dError("bn_pass: mode must be 0..4");
@@ -1287,35 +1289,47 @@ int p3d_debug_bn_pass(int device, int mode, int64_t M, int C, const float* y1, c
     const int nbn = two ? 2 : 1;
     if (!y1 || !params || !dz || !z || !dy1 || !grads || !moving || !info || (has2 && (!y2 || !dy2))) throw P3dError("null argument");
     if (M < 1 || C < 4 || C > 1024 || (C & 3) || path < 0 || path > 3) throw P3dError("bn_pass: bad shape or path");
-    const int64_t n = M * C;
+    auto slice_ok = [&](int ld, int off) { return !(ld & 3) && !(off & 3) && off >= 0 && ld >= off + C; };
+    if (!slice_ok(ld1, off1) || !slice_ok(ldz, offz) || (has2 && !slice_ok(ld2, off2)))
+        throw P3dError("bn_pass: row strides and channel offsets are multiples of 4 with offset + C <= stride");
+    if (!(drop_rate >= 0.f && drop_rate < 1.f)) throw P3dError("bn_pass: dropout rate must be in [0, 1)");
+    const bool dropout = drop_rate > 0.f;
+    const float drop_scale = dropout ? 1.f / (1.f - drop_rate) : 0.f;      // (set_dropout's)
     const bool b1 = batch1 != 0, b2 = two && batch2 != 0;
-    DevBuf dy1b(n, y1), dy2b(has2 ? n : 1, has2 ? y2 : nullptr), dzb(n, dz), zb(n), g1(n), g2(has2 ? n : 1, (has2 && acc2) ? dy2 : nullptr);
-    DevBuf prm(2 * (int64_t)C * nbn, params), mv(2 * (int64_t)C * nbn, moving), tab(4 * (int64_t)C * nbn), grd(2 * (int64_t)C * nbn);
     const int sparts = p3d_bn_stats_parts((long)M, C), bparts = p3d_bn_bwd_parts((long)M, C);
+    // the network's rule, or the forced path -- which must be one the kernels take (a pass that drops out takes only finalize + apply)
+    const int taken = path ? path : bn_path(M, C, dropout, b1 ? sparts : 0, b2 ? sparts : 0, drop_scale);
+    if (taken == BN_SMALL && (dropout || !p3d_bn_small_ok((long)M, C)))
+        throw P3dError("bn_pass: the small-tensor path does not take this shape, or a pass that drops out");
+    if (taken == BN_FOLD && !p3d_bn_fold_apply_ok((long)M, C, b1 ? sparts : 0, b2 ? sparts : 0, drop_scale))
+        throw P3dError("bn_pass: the fold-apply path does not take this shape, or a pass that drops out");
+    const int64_t n1 = M * ld1, n2 = has2 ? M * ld2 : 1, nz = M * ldz;
+    DevBuf dy1b(n1, y1), dy2b(n2, has2 ? y2 : nullptr), dzb(nz, dz), zb(nz, z), g1(n1, dy1), g2(n2, has2 ? dy2 : nullptr);
+    DevBuf prm(2 * (int64_t)C * nbn, params), mv(2 * (int64_t)C * nbn, moving), tab(4 * (int64_t)C * nbn), grd(2 * (int64_t)C * nbn);
     DevBuf spart((int64_t)sparts * 2 * C * nbn), bpart((int64_t)bparts * 2 * C * nbn), coef(2 * (int64_t)C * nbn);
-    // the network's rule, or the forced path -- which must be one the kernels take
-    const int taken = path ? path : bn_path(M, C, false, b1 ? sparts : 0, b2 ? sparts : 0, 0.f);
-    if (taken == BN_SMALL && !p3d_bn_small_ok((long)M, C)) throw P3dError("bn_pass: the small-tensor path does not take this shape");
-    if (taken == BN_FOLD && !p3d_bn_fold_apply_ok((long)M, C, b1 ? sparts : 0, b2 ? sparts : 0, 0.f))
-        throw P3dError("bn_pass: the fold-apply path does not take this shape");
-    Ctx c;
+    DevBuf dseed(2);
+    HIPCHECK(copy_now(dseed.p, &seed, sizeof(seed), hipMemcpyHostToDevice, nullptr));
+    Ctx c;         // (bn_apply at a dropout site: the step's seed as an argument or in device memory)
+    c.training = true; c.drop = drop_rate;
+    if (seed_dev) c.seed_dev = reinterpret_cast<const unsigned long long*>(dseed.p); else c.seed = seed;
     BnPass p;
     p.mode = mode; p.M = M; p.C = C; p.nparts = bparts;
-    p.y1 = dy1b.p; p.ld1 = C; p.z = zb.p; p.ldz = C; p.dz = dzb.p; p.lddz = C; p.dy1 = g1.p; p.lddy1 = C;
-    if (has2) { p.y2 = dy2b.p; p.ld2 = C; p.dy2 = g2.p; p.lddy2 = C; p.acc2 = acc2 ? 1 : 0; }
+    p.y1 = dy1b.p + off1; p.ld1 = ld1; p.z = zb.p + offz; p.ldz = ldz; p.dz = dzb.p + offz; p.lddz = ldz; p.dy1 = g1.p + off1; p.lddy1 = ld1;
+    if (has2) { p.y2 = dy2b.p + off2; p.ld2 = ld2; p.dy2 = g2.p + off2; p.lddy2 = ld2; p.acc2 = acc2 ? 1 : 0; }
     for (int q = 0; q < nbn; ++q) {
         const int64_t o = (int64_t)q * 2 * C;
         p.bn[q] = bn_layout(prm.p + o, prm.p + o + C, mv.p + o, mv.p + o + C, tab.p + 2 * o, spart.p + o * sparts, sparts, C);
         p.dgamma[q] = grd.p + o; p.dbeta[q] = grd.p + o + C; p.part[q] = bpart.p + o * bparts; p.coef[q] = coef.p + o;
         p.batch[q] = q ? b2 : b1;
-        if (taken != BN_SMALL && p.batch[q]) HIPCHECK(p3d_bn_stats(q ? p.y2 : p.y1, C, (long)M, C, spart.p + o * sparts, c.s));
+        if (taken != BN_SMALL && p.batch[q]) HIPCHECK(p3d_bn_stats(q ? p.y2 : p.y1, q ? ld2 : ld1, (long)M, C, spart.p + o * sparts, c.s));
     }
+    set_dropout(p, c, dropout);
     bn_pass_forward(c, p, (BnPath)taken, update_moving != 0);
     bn_pass_backward(c, p, taken == BN_SMALL);
     info[0] = taken; info[1] = taken == BN_SMALL ? 0 : sparts; info[2] = taken == BN_SMALL ? 0 : bparts;
-    zb.get(z, n);
-    g1.get(dy1, n);
-    if (has2) g2.get(dy2, n);
+    zb.get(z, nz);
+    g1.get(dy1, n1);
+    if (has2) g2.get(dy2, n2);
     grd.get(grads, 2 * (int64_t)C * nbn);
     mv.get(moving, 2 * (int64_t)C * nbn);
     API_END

@@ -106,24 +106,45 @@ def conv_bn_stats(x, filter, strides, bias=None, transpose=False, filter2=None, 
     return ys, stats[:, 2], stats[:, 3], mv, [nparts[q] for q in range(pairs)], kernel.value.decode()
 
 
-def bn_pass(mode, y1, y2, params, moving, dz, batch=(1, 1), update_moving=1, acc2=None, path=0, device=0):
+def bn_pass(mode, y1, y2, params, moving, dz, batch=(1, 1), update_moving=1, acc2=None, path=0, device=0, C_=None,
+            offset=(0, 0, 0), drop_rate=0.0, seed=0, seed_dev=False, z=None, dy1=None, dy2=None):
     """Test hook: one BatchNorm normalise / ReLU / add pass of the network (mode 0-4, see include/p3d_hip.h) forward and
     backward on [M, C] arrays.  params [bns, 2, C] = gamma, beta; moving [bns, 2, C] moving (mean, variance) before.
     acc2: the gradient of y2 to add to (None: overwrite).  path 0 = the network's rule, 1 small, 2 fold-apply, 3 finalize +
-    apply.  Returns (z, dy1, dy2, grads [bns, 2, C], moving after, (path taken, forward partials, backward partials))."""
+    apply.  Returns (z, dy1, dy2, grads [bns, 2, C], moving after, (path taken, forward partials, backward partials)).
+
+    C_ (default: dense operands, as above): the operands are C_-channel slices of the wide buffers y1 [M, ld1], y2 [M, ld2] and
+    dz [M, ldz] at the column offsets `offset` (of y1 / dy1, of y2 / dy2, of z / dz); z, dy1 and dy2 are then what the wide
+    output buffers hold before the pass (dy2 inside its slice: the gradient to add to when acc2 is not None, whose value is
+    otherwise unused), and the wide buffers are returned.  drop_rate > 0: the pass drops out with the kernels' mask of `seed`,
+    passed as an argument or (seed_dev) read from device memory."""
     y1 = _f32(y1)
-    M, C_ = y1.shape
     bns = 2 if mode in (2, 3) else 1
     y2 = _f32(y2) if mode != 0 else None
+    dz = _f32(dz)
+    if C_ is None:
+        M, C_ = y1.shape
+        z, dy1 = np.empty((M, C_), np.float32), np.empty((M, C_), np.float32)
+        dy2 = (_f32(acc2).copy() if acc2 is not None else np.empty((M, C_), np.float32)) if mode != 0 else None
+    else:
+        M, C_ = y1.shape[0], int(C_)
+        if z is None or dy1 is None or (mode != 0 and dy2 is None):
+            raise ValueError("bn_pass: sliced operands come with the z, dy1 and dy2 buffers")
+        z, dy1 = _f32(z).copy(), _f32(dy1).copy()
+        dy2 = _f32(dy2).copy() if mode != 0 else None
+        if z.shape != dz.shape or dy1.shape != y1.shape or (mode != 0 and dy2.shape != y2.shape):
+            raise ValueError("bn_pass: z, dy1, dy2 have the shapes of dz, y1, y2")
+    if dz.shape[0] != M or (mode != 0 and y2.shape[0] != M):
+        raise ValueError("bn_pass: every operand has M rows")
     prm = _f32(np.asarray(params).reshape(bns, 2, C_))
     mv = np.array(moving, dtype=np.float32).reshape(bns, 2, C_).copy()
-    z, dy1 = np.empty((M, C_), np.float32), np.empty((M, C_), np.float32)
-    dy2 = (_f32(acc2).copy() if acc2 is not None else np.empty((M, C_), np.float32)) if mode != 0 else None
     grads = np.empty((bns, 2, C_), np.float32)
     info = (C.c_int * 3)()
-    check(lib().p3d_debug_bn_pass(device, mode, M, C_, fptr(y1), fptr(y2), fptr(prm), int(batch[0]), int(batch[1]),
-                                  int(update_moving), fptr(_f32(dz)), 1 if acc2 is not None else 0, path, fptr(z), fptr(dy1),
-                                  fptr(dy2), fptr(grads), fptr(mv), info))
+    ld2 = y2.shape[1] if mode != 0 else C_
+    check(lib().p3d_debug_bn_pass(device, mode, M, C_, fptr(y1), y1.shape[1], int(offset[0]), fptr(y2), ld2, int(offset[1]),
+                                  fptr(prm), int(batch[0]), int(batch[1]), int(update_moving), fptr(dz),
+                                  1 if acc2 is not None else 0, float(drop_rate), int(seed), 1 if seed_dev else 0, path, fptr(z),
+                                  z.shape[1], int(offset[2]), fptr(dy1), fptr(dy2), fptr(grads), fptr(mv), info))
     return z, dy1, dy2, grads, mv, tuple(info)
 
 

@@ -25,6 +25,7 @@ pytestmark = pytest.mark.gpu
 # given build it is a fixed number (the kernels are bit-reproducible).  A wrong kernel shows as >= 1e-1, and the conv /
 # deconv / pool kernels are held to 2e-5 at op level (test_gpu_ops.py).
 from gates import grad_gate      # noqa: E402
+import dropout_ref                # noqa: E402
 
 
 def grads_vs_oracles(s, g64, g32):
@@ -231,6 +232,8 @@ def test_unetplusplus_nonsa_dropout_and_train_steps():
     dropped = s.activation('x_1_3')
     keep = np.where(base != 0, dropped != 0, True)
     assert 0.45 < keep[base != 0].mean() < 0.55
+    # where it is observable, the pattern read back is the definition's (include/p3d_hip.h at p3d_forward, tests/dropout_ref.py)
+    assert np.array_equal(keep[base != 0], dropout_ref.keep(11, 0.5, base.size // base.shape[-1], base.shape[-1]).reshape(base.shape)[base != 0])
     l64, pr64, g64, _ = p3d.loss_and_grads(p64, x.astype(np.float64), y.astype(np.float64), 0.5, True, st, cfg,
                                            np.float64, keep_mask=keep.astype(np.float64))
     _, _, g32, _ = p3d.loss_and_grads(dict(p32), x, y, 0.5, True, st, cfg, np.float32, keep_mask=keep.astype(np.float32))
@@ -309,6 +312,8 @@ def test_unetplusplus_ds_self_attention(cfg, shape, mode):
     dropped = s.activation('x_1_3_sa')
     keep = np.where(base != 0, dropped != 0, True)
     assert 0.45 < keep[base != 0].mean() < 0.55
+    # where it is observable, the pattern read back is the definition's (include/p3d_hip.h at p3d_forward, tests/dropout_ref.py)
+    assert np.array_equal(keep[base != 0], dropout_ref.keep(11, 0.5, base.size // base.shape[-1], base.shape[-1]).reshape(base.shape)[base != 0])
     l64, pr64, g64, _ = p3d.loss_and_grads(p64, x.astype(np.float64), y.astype(np.float64), 0.5, True, st, cfg, np.float64,
                                            keep_mask=keep.astype(np.float64))
     _, _, g32, _ = p3d.loss_and_grads(dict(p32), x, y, 0.5, True, st, cfg, np.float32, keep_mask=keep.astype(np.float32))
