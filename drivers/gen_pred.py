@@ -146,6 +146,62 @@ def write_video_images_resident(sess, F, video_dir, ext, size=(1080, 960), write
     return t
 
 
+SCORE_CHUNK = 64     # frames per scoring call of --truth
+SCORE_NAMES = ("cc", "sim", "judd", "kl", "nss")       # the columns of a row of scores, in order
+
+
+def load_truth(truth_dir, name, F, size):
+    """--truth's arrays of one video: <name>_density.npy and <name>_fixation.npy, uint8 [F, H, W] at --size."""
+    out = []
+    for what in ("density", "fixation"):
+        path = os.path.join(truth_dir, "%s_%s.npy" % (name, what))
+        a = np.load(path)
+        if a.dtype != np.uint8 or a.shape != (F,) + tuple(size):
+            raise ValueError("--truth: %s is %s %s, the video needs uint8 %s" % (path, a.dtype, a.shape, (F,) + tuple(size)))
+        out.append(a)
+    return out
+
+
+def nan_means(scores):
+    """Column means of [F, 5] scores with the NaN rows of a column dropped (np.nanmean; a column of NaN stays NaN)."""
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        return np.nanmean(np.asarray(scores, np.float64).reshape(-1, len(SCORE_NAMES)), axis=0)
+
+
+def format_means(means):
+    return ", ".join("%s=%r" % (k, float(v)) for k, v in zip(SCORE_NAMES, means))
+
+
+def score_video_resident(sess, F, density, fixation, size, columns, ties, video_dir=None, ext=None, writers=4):
+    """Scores the open video against its ground truth on the device (P3DSession.video_score), SCORE_CHUNK frames a call ->
+    (scores float64 [F, 5], times).  The 8-bit maps stay on the device unless video_dir asks for the images: then each call also
+    returns its bytes and they are encoded as write_video_images_resident encodes them, while the next call runs."""
+    from concurrent.futures import ThreadPoolExecutor
+    scores = np.full((F, len(SCORE_NAMES)), np.nan, np.float64)
+    t = dict(upload=0.0, device=0.0, score=0.0, files=0)
+    held = []
+    with ThreadPoolExecutor(max_workers=writers) as pool:
+        for first in range(0, F, SCORE_CHUNK):
+            n = min(SCORE_CHUNK, F - first)
+            got = sess.video_score(first, n, density[first:first + n], fixation[first:first + n], size=size, columns=columns, ties=ties,
+                                   with_maps=video_dir is not None)
+            for k in ("upload", "device", "score"):
+                t[k] += sess.last_score_ms[k]
+            if video_dir is not None:
+                got, maps = got
+                for fut in held:
+                    fut.result()
+                held = [pool.submit(save_image, os.path.join(video_dir, "frame_%d.%s" % (first + k + 1, ext)), m, ext)
+                        for k, m in enumerate(maps)]
+                t["files"] += n
+            scores[first:first + n] = got
+        for fut in held:
+            fut.result()
+    return scores, t
+
+
 def save_image(path, m, ext):
     """One 8-bit map with PIL: PNG at compress_level 1 (lossless: the level changes the file size, not the pixels), JPEG at
     quality 95 (cv2.IMWRITE_JPEG_QUALITY's default)."""
@@ -242,6 +298,16 @@ def parse_args(argv=None):
                    "24 and at most F - 1; 0: cv2's rule, (int(rint(8 S + 1)) | 1) // 2")
     p.add_argument("--temporal-alpha", type=float, default=0., metavar="A", help="[addition] --temporal ema: m_f = A m_{f-1} + (1 - A) v_f, "
                    "A in [0, 1)")
+    p.add_argument("--truth", type=str, default="", metavar="DIR", help="[addition] score every frame's 8-bit map at --size on the device "
+                   "against DIR/<name>_density.npy and DIR/<name>_fixation.npy, uint8 [F, H, W] at --size (fixated: byte >= 128): the "
+                   "arithmetic of utils/matlab_metric/metric_video_base.m (P3DSession.video_score).  Writes <out>/<name>_scores.npy, "
+                   "[F, 5]: CC, SIM, AUC_Judd, KL, NSS, and prints the means (implies --resident)")
+    p.add_argument("--score-columns", type=str, nargs="+", default=["cc", "sim", "judd"], choices=("cc", "sim", "judd", "kl", "nss", "matlab"),
+                   metavar="COLUMN", help="[addition] --truth: the columns to compute, of cc sim judd kl nss; the others are NaN.  The "
+                   "default, also spelled matlab, is the .m file's masks")
+    p.add_argument("--score-ties", choices=("reference", "expected"), default="expected", help="[addition] --truth: AUC_Judd on equal bytes: "
+                   "utils/metrics.py with jitter=False, or its mean over every order of the tied pixels (what the default jitter does "
+                   "to an 8-bit map, without a draw)")
     p.add_argument("--base", type=int, default=64, help=argparse.SUPPRESS)
     p.add_argument("--blocks", type=str, default="3,8,36", help=argparse.SUPPRESS)
     p.add_argument("--time", action="store_true", help="print per-video wall times (png / jpg: also the device stage and the host encode)")
@@ -255,9 +321,15 @@ def parse_args(argv=None):
     temporal_args(args, p.error)
     if args.temporal != "off":
         args.resident = True
-    if args.write == "npy" and (args.blur_sigma != 0. or args.blur_radius != 0 or args.normalize != "none"):
+    if args.truth:
+        args.resident = True
+    elif args.score_columns != ["cc", "sim", "judd"] or args.score_ties != "expected":
+        p.error("--score-columns / --score-ties need --truth DIR")
+    if args.truth:
+        pass                                          # the stages below shape the scored maps too: --write npy may have them
+    elif args.write == "npy" and (args.blur_sigma != 0. or args.blur_radius != 0 or args.normalize != "none"):
         p.error("--blur-sigma / --blur-radius / --normalize shape the images: they need --write png or jpg (npy stays the raw 112x112 maps)")
-    if args.write == "npy" and args.match_hist:
+    if args.write == "npy" and args.match_hist and not args.truth:
         p.error("--match-hist shapes the images: it needs --write png or jpg (npy stays the raw 112x112 maps)")
     if args.match_hist == "density":
         p.error("--match-hist density needs a ground truth: it belongs to drivers/test.py; here it takes FILE.npz")
@@ -303,7 +375,7 @@ def prior_stage_args(args):
         if args.prior_mode != "mul" or args.prior_weight != 0.:
             raise SystemExit("--prior-mode / --prior-weight need --prior FILE.npy")
         return None
-    if args.write == "npy":
+    if args.write == "npy" and not args.truth:
         raise SystemExit("--prior shapes the images: it needs --write png or jpg (npy stays the raw 112x112 maps)")
     if not 0. <= args.prior_weight <= 1.:
         raise SystemExit("--prior-weight: the weight must be in [0, 1]")
@@ -328,9 +400,12 @@ def match_target(args):
 
 def run(sess, args):
     os.makedirs(args.out, exist_ok=True)
+    video_means = []
     for path in sorted(glob.glob(os.path.join(args.videos, "*.npy"))):
         if args.resident:
-            run_resident(sess, args, path)
+            means = run_resident(sess, args, path)
+            if means is not None:
+                video_means.append(means)
             continue
         if args.write == "npy":
             t0 = time.perf_counter()
@@ -356,8 +431,12 @@ def run(sess, args):
                   "thread time on %d writers" % (name, wall, t["gpu"], t["device"], t["d2h"], t["encode"], args.writers))
 
 
+    if args.truth and video_means:
+        print("mean over %d videos: %s" % (len(video_means), format_means(nan_means(np.stack(video_means)))))
+
+
 def run_resident(sess, args, path):
-    """One video of run() on the resident path."""
+    """One video of run() on the resident path.  -> the video's column means under --truth, else None."""
     name = os.path.splitext(os.path.basename(path))[0]
     video_dir = os.path.join(args.out, name)
     if args.write != "npy":
@@ -369,10 +448,21 @@ def run_resident(sess, args, path):
     times = {}
     F = predict_video_resident(sess, np.load(path), args.batch, args.stride, args.overlap, times)
     t1 = time.perf_counter()
+    means = ts = None
+    if args.truth:
+        density, fixation = load_truth(args.truth, name, F, args.size)
+        scores, ts = score_video_resident(sess, F, density, fixation, tuple(args.size), tuple(args.score_columns), args.score_ties,
+                                          video_dir if args.write != "npy" else None, args.write, args.writers)
+        np.save(os.path.join(args.out, name + "_scores.npy"), scores)
+        means = nan_means(scores)
+        print("%s scores over %d frames: %s" % (name, F, format_means(means)))
     if args.write == "npy":
         sal = sess.video_maps(0, F)
         np.save(os.path.join(args.out, os.path.basename(path)), sal)
         print(os.path.basename(path), sal.shape, float(sal.mean()))
+    elif ts is not None:
+        t = dict(gpu=ts["upload"] + ts["device"] + ts["score"], device=ts["device"], d2h=0.0, encode=0.0, files=ts["files"])
+        print(name, "%d %s files in %s" % (t["files"], args.write, video_dir))
     else:
         t = write_video_images_resident(sess, F, video_dir, args.write, size=tuple(args.size), writers=args.writers)
         print(name, "%d %s files in %s" % (t["files"], args.write, video_dir))
@@ -384,9 +474,12 @@ def run_resident(sess, args, path):
                                   (t1 - t0) * 1e3, times["gather"], times["scatter"]))
         if temporal_ms is not None:
             print("  %s: temporal %s: %.3f ms on the device in the last read-out" % (name, args.temporal, temporal_ms))
-        if args.write != "npy":
+        if ts is not None:
+            print("  %s: scoring: uploads %.2f ms, maps %.2f ms, scoring launches %.3f ms on the device" % (name, ts["upload"], ts["device"], ts["score"]))
+        if args.write != "npy" and ts is None:
             print("  %s: maps %.1f ms (device resize/quantise %.2f ms, d2h %.2f ms) | encode %.1f ms thread time on %d writers"
                   % (name, t["gpu"], t["device"], t["d2h"], t["encode"], args.writers))
+    return means
 
 
 def main(argv=None):

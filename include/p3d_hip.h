@@ -1396,6 +1396,73 @@ int p3d_debug_trainset_gather(int device, int frame_format, const void* frames_s
                               const int* video, const int* start, const int* first, int B, int offset, float* x, float* y,
                               unsigned char* fix);
 
+/* ---- Scoring 8-bit maps against 8-bit ground truth (an ADDITION: the arithmetic of the reference's
+ * utils/matlab_metric/metric_video_base.m protocol -- every frame's 8-bit map at output resolution against that frame's 8-bit density
+ * and fixation images, CC / SIM / AUC-Judd per frame with KL and NSS behind masks -- with the metric definitions of
+ * utils/metrics.py; the MATLAB toolbox and metric_statistics are not part of this library).  OFF until called: every other entry
+ * point issues what it issued before and returns the same bits.  PARITY UNPINNED beyond utils/metrics.py: this text is the
+ * contract, tests/score_u8_ref.py replays it in numpy and is itself held to oracle/metrics.py.
+ * Per map: saliency s, density d, fixation x, [H][W] bytes of one shape, N = H * W, 1 <= N <= 2^23 (every integer below then fits
+ * a signed 64-bit word: 65025 * 2^46 < 2^63).  A pixel is fixated exactly when its byte x >= 128.
+ *   TABLES  hs[v] = pixels with s = v; hf[v] = fixated pixels with s = v; hd[v] = pixels with d = v; sd = sum s d (uint64).
+ *           Integers: no order can show.  From them, exactly: S1 = sum v hs[v], S2 = sum v^2 hs[v], D1, D2 likewise from hd,
+ *           nf = sum hf[v], F1 = sum v hf[v].
+ *   Everything below is float64, every operation rounded on its own; (double) of an integer is one round-to-nearest-even.
+ *   CC      (double)(N sd - S1 D1) / (sqrt((double)(N S2 - S1^2)) * sqrt((double)(N D2 - D1^2))), the three differences formed as
+ *           integers; NaN when either variance is 0.
+ *   NSS     (double)(N F1 - nf S1) / ((double)nf * sqrt((double)(N S2 - S1^2))); NaN when nf = 0 or the variance is 0.
+ *   AUC_Judd, P3D_SCORE_TIES_REFERENCE  utils/metrics.py:69-85 with jitter=False: walk v = 255 .. 0 with A += hs[v]; for each of
+ *           the hf[v] fixations of that level k += 1 and the point tp = k / nf, fp = (A - k) / (N - nf) is added; with the end
+ *           points (0, 0) and (1, 1) the score is sum (fp_i+1 - fp_i) (tp_i+1 + tp_i) / 2.  Inside a tied level fp runs backwards;
+ *           that is the reference's behaviour.  With G_v = sum_{u > v} hf[u] the sum times 2 (N - nf) nf is the integer
+ *           I = sum_v hs[v] w_v - nf^2, w_v = 2 G_v + 1 where G_v < nf and 2 nf where G_v = nf, and the score is
+ *           (double)I / (double)(2 (N - nf) nf): the sweep's real value, rounded once.
+ *   AUC_Judd, P3D_SCORE_TIES_EXPECTED  the expectation of that curve's score when the pixels inside every level are ordered
+ *           uniformly at random -- what the reference's default jitter does to an 8-bit map, without a draw.  m[v] = hs[v] - hf[v],
+ *           f = (double)hf[v], g = (double)G_v, n = (double)nf:
+ *             e_v = ((g + 0.5) + f / 2) / n                                          where G_v + hf[v] < nf,
+ *             e_v = (((f * (g + 0.5)) / n + (f * (f - 1)) / (2 n)) + 1) / (f + 1)   where G_v + hf[v] = nf;
+ *           t_v = (double)m[v] * e_v, and 0 where m[v] = 0; score = T / (double)(N - nf), T the sum of t_255 .. t_0 in this order:
+ *           with t_255 first, groups of 64 consecutive terms are each folded by six butterfly steps (x_i += x_{i xor o}, o = 32,
+ *           16, 8, 4, 2, 1), then T = ((w0 + w1) + w2) + w3.
+ *           Both laws: NaN when nf = 0, and NaN when nf = N (the reference divides by zero there: not pinned).
+ *   SIM     min_s / max_s the lowest / highest v with hs[v] > 0; u_v = (double)(v - min_s) / (double)(max_s - min_s);
+ *           U_s = sum over v ascending, hs[v] > 0 only, of (double)hs[v] * u_v; us[v] = u_v / U_s; ud from hd likewise.
+ *           SIM = sum over pixels of min(us[s], ud[d]), a NaN on either side kept (a constant map gives NaN).
+ *   KL      ps[v] = (double)v / (double)S1, or 0 for every v when S1 = 0 (the reference's `if map1.any()`); pd from D1 likewise;
+ *           KL = sum over pixels of pd[d] * log(eps + pd[d] / (ps[s] + eps)), eps = 2.2204e-16 (utils/metrics.py:359, the literal).
+ *           The imresize of the reference's KLdiv is the identity on maps of one shape and its byte quantisation is not reproduced.
+ *           The order of the two sums over pixels is the kernel's (lane, then block partials in block order); tests hold them
+ *           to relative 1e-9.
+ * p3d_video_score    scores frames first .. first + n - 1 of the open video.  The scored bytes are, bit for bit, what
+ *                    p3d_video_maps_u8(first, n, scale, H, W) returns under the handle's current settings (MEAN finalisation,
+ *                    p3d_set_video_temporal, p3d_set_postprocess, p3d_set_prior_stage, P3D_MATCH_TABLE); they stay on the device
+ *                    unless maps_out asks for them.  density / fixation [n][H][W] on the host; out [n][5]: CC, SIM, AUC_Judd, KL,
+ *                    NSS, an unselected column NaN.  stage_ms (or NULL) [3]: HIP-event milliseconds of the two uploads, of the
+ *                    maps' chain, of the scoring launches.  Validated as p3d_video_maps_u8 validates, before any launch or
+ *                    upload; also refused: flags outside the five bits or 0, a ties law that is neither value, H * W > 2^23,
+ *                    fixation == NULL with JUDD or NSS selected (without them it may be NULL).
+ * p3d_score_maps_u8  op level, host arrays: n maps sal / density / fixation [n][H][W] -> out [n][5]; n in 1 .. 65535.
+ * TEST HOOKS (tests/test_gpu_score_u8.py):
+ * p3d_debug_score_u8   the same launch descriptions with every device buffer between guard elements: sal starts `offset` bytes
+ *                    (0 .. 15) past a 16-byte boundary, density (2 offset) mod 16 and fixation (3 offset) mod 16 bytes past one, so
+ *                    that offset 0 aligns the three alike and any other offset does not; -1 if a guard or an input changed, or if
+ *                    anything was written for pass B when neither SIM nor KL was selected.  hs / hf / hd [n][256] and sd [n] come
+ *                    back; any of the four may be NULL.
+ * p3d_debug_score_plan host only, no HIP call: pass A's blocks per map, pixels per block (a multiple of 16) and the most products
+ *                    s d a lane adds in its 32-bit accumulator for n maps at that offset (66 051 products of 255 * 255 fit). */
+enum { P3D_SCORE_CC = 1, P3D_SCORE_SIM = 2, P3D_SCORE_JUDD = 4, P3D_SCORE_KL = 8, P3D_SCORE_NSS = 16 };
+#define P3D_SCORE_MATLAB (P3D_SCORE_CC | P3D_SCORE_SIM | P3D_SCORE_JUDD)      /* metric_video_base.m's masks */
+enum { P3D_SCORE_TIES_REFERENCE = 0, P3D_SCORE_TIES_EXPECTED = 1 };
+int p3d_video_score(p3d_handle* h, int first, int n, float scale, int H, int W, const unsigned char* density,
+                    const unsigned char* fixation, int flags, int ties, double* out, unsigned char* maps_out /* may be NULL */,
+                    double* stage_ms /* may be NULL */);
+int p3d_score_maps_u8(int device, const unsigned char* sal, const unsigned char* density, const unsigned char* fixation, int n, int H,
+                      int W, int flags, int ties, double* out);
+int p3d_debug_score_u8(int device, const unsigned char* sal, const unsigned char* density, const unsigned char* fixation, int n, int H,
+                       int W, int flags, int ties, int offset, uint32_t* hs, uint32_t* hf, uint32_t* hd, uint64_t* sd, double* out);
+int p3d_debug_score_plan(int64_t n_pix, int n, int offset, int* blocks_per_map, int* pixels_per_block, int64_t* products_per_lane);
+
 /* CRC-32C of a host buffer (host-side helper of the TensorFlow checkpoint reader / writer, sap3d_tensorflow_amd/tf_checkpoint.py:
  * the bundle format of train.py:180-185,266-267 checksums every tensor); crc = running value, 0 to start. */
 uint32_t p3d_crc32c(const void* data, size_t n, uint32_t crc);

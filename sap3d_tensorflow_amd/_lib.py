@@ -65,6 +65,10 @@ EVAL_EXTRA = {"kldiv": 1, "info_gain": 2}
 # p3d_video_open modes (include/p3d_hip.h P3D_VIDEO_*)
 VIDEO_MODES = {"newest": 0, "mean": 1}
 # p3d_trainset_open frame formats and flags (include/p3d_hip.h P3D_TRAINSET_*)
+# p3d_video_score / p3d_score_maps_u8: the columns' flags (also their order in a row of scores) and the AUC-Judd ties laws
+SCORE_COLUMNS = {"cc": 1, "sim": 2, "judd": 4, "kl": 8, "nss": 16}
+SCORE_MATLAB = ("cc", "sim", "judd")
+SCORE_TIES = {"reference": 0, "expected": 1}
 TRAINSET_FORMATS = {"u8": 0, "f32": 1}
 P3D_TRAINSET_FIXATIONS = 1
 # p3d_set_video_temporal kinds (include/p3d_hip.h P3D_TEMPORAL_*)
@@ -373,6 +377,11 @@ SIGNATURES = {
     "p3d_trainset_last_ms": (C.c_int, [C.c_void_p, _dp]),
     "p3d_debug_trainset_gather": (C.c_int, [C.c_int, C.c_int, C.c_void_p, _u8p, _u8p, C.c_int, _ip, C.c_int, C.c_int64, _fp, _ip, _ip, _ip,
                                             C.c_int, C.c_int, _fp, _fp, _u8p]),
+    "p3d_video_score": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, _u8p, _u8p, C.c_int, C.c_int, _dp, _u8p, _dp]),
+    "p3d_score_maps_u8": (C.c_int, [C.c_int, _u8p, _u8p, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp]),
+    "p3d_debug_score_u8": (C.c_int, [C.c_int, _u8p, _u8p, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32),
+                                     C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), _dp]),
+    "p3d_debug_score_plan": (C.c_int, [C.c_int64, C.c_int, C.c_int, _ip, _ip, _i64p]),
     "p3d_crc32c": (C.c_uint32, [C.c_void_p, C.c_size_t, C.c_uint32]),
     "p3d_shutdown": (C.c_int, []),
 }

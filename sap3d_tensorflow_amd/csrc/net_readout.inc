@@ -718,8 +718,22 @@ namespace {
 // inside the device stage's time: it queues whatever makes the maps readable and names them as runs of maps of ph x pw pixels.
 // Off: one double-precision p3d_resize_u8 per run; on: the float32 resize / blur / normalise / byte sequence, P3D_POST_CHUNK maps
 // at a time.  Ends synchronised; stage_ms as p3d_pred_maps_u8's.
+// A consumer (p3d_video_score) takes the device bytes where they are instead of a copy of the chain: its buffers are carved after
+// the chain's in the same layout, `before` is queued ahead of the sources, `after` behind the chain with the bytes and `counters`
+// zeroed arrival counters of its own, `results` (its copies back to the host) behind that; out may then be NULL (the bytes stay
+// on the device) and ms [3] receives the times of `before`, of the device stage and of `after`.  Without one, nothing here differs
+// from what the two callers issued before.
+struct U8Consumer {
+    size_t counters = 0;
+    std::function<void(Carve&)> carve;
+    std::function<void(hipStream_t)> before;
+    std::function<void(hipStream_t, const unsigned char*, unsigned*)> after;
+    std::function<void(hipStream_t)> results;
+    double* ms = nullptr;
+};
 void maps_u8_chain(p3d_handle* h, long long maps, int ph, int pw, float scale, int H, int W, unsigned char* out, double* stage_ms,
-                   size_t extra, const std::function<void(hipStream_t, float*, std::vector<PostRun>&)>& sources) {
+                   size_t extra, const std::function<void(hipStream_t, float*, std::vector<PostRun>&)>& sources,
+                   const U8Consumer* use = nullptr) {
     const long long hw = (long long)H * W, bytes = maps * hw;
     const hipStream_t s = h->stream;
     // p3d_set_postprocess: the float32 chain resize -> blur -> normalise -> bytes, P3D_POST_CHUNK maps at a time; its scratch
@@ -736,12 +750,16 @@ void maps_u8_chain(p3d_handle* h, long long maps, int ph, int pw, float scale, i
     StageScratch scratch;
     unsigned char* d = nullptr;
     float* ex = nullptr;
-    unsigned* const counters = carve_scratch(s, chain ? (size_t)post_chunk : 0, [&](Carve& c) {
+    const size_t chain_counters = chain ? (size_t)post_chunk : 0;
+    unsigned* const counters = carve_scratch(s, chain_counters + (use ? use->counters : 0), [&](Carve& c) {
         d = c.take<unsigned char>((size_t)bytes);      // (the first take starts at offset 0: with nothing else, the slab is the bytes)
         if (chain) scratch.carve(c, st, post_chunk, hw, true);
         ex = extra ? c.take<float>(extra) : nullptr;
+        if (use) use->carve(c);
     });
-    StageTimer tm(stage_ms != nullptr, 3);
+    StageTimer tm(stage_ms != nullptr || (use && use->ms), 3), ends(use && use->ms, 2);
+    ends.mark(0, s);
+    if (use) use->before(s);
     tm.mark(0, s);
     PostJob job;
     sources(s, ex, job.runs);
@@ -756,10 +774,19 @@ void maps_u8_chain(p3d_handle* h, long long maps, int ph, int pw, float scale, i
         }
     }
     tm.mark(1, s);
-    HIPCHECK(hipMemcpyAsync(out, d, (size_t)bytes, hipMemcpyDeviceToHost, s));
+    if (use) use->after(s, d, counters + chain_counters);
+    ends.mark(1, s);
+    if (use) use->results(s);
+    if (out) HIPCHECK(hipMemcpyAsync(out, d, (size_t)bytes, hipMemcpyDeviceToHost, s));
     tm.mark(2, s);
     HIPCHECK(hipStreamSynchronize(s));
     if (stage_ms) { stage_ms[0] = tm.ms(0); stage_ms[1] = tm.ms(1); }
+    if (use && use->ms) {
+        float up = 0.f, sc = 0.f;
+        HIPCHECK(hipEventElapsedTime(&up, ends.ev[0], tm.ev[0]));
+        HIPCHECK(hipEventElapsedTime(&sc, tm.ev[1], ends.ev[1]));
+        use->ms[0] = (double)up; use->ms[1] = tm.ms(0); use->ms[2] = (double)sc;
+    }
 }
 }  // namespace
 extern "C" {
@@ -1646,6 +1673,146 @@ int p3d_video_maps_u8(p3d_handle* h, int first, int n, float scale, int H, int W
                       runs.push_back({temporal ? h->video_temporal("video_maps_u8", first, n, scratch, s)
                                                : h->video_finalize("video_maps_u8", first, n, scratch, s), phw, 1, n});
                   });
+    API_END
+}
+
+}  // extern "C"
+namespace {
+// ---- scoring 8-bit maps (score_u8.hip; the law in include/p3d_hip.h): one check, one scratch layout and one launch sequence for
+// p3d_video_score, p3d_score_maps_u8 and p3d_debug_score_u8 ----------------------------------------------------------------------
+void score_check(const char* who, const void* density, const void* fixation, int n, int H, int W, int flags, int ties, const void* out) {
+    if (!density || !out) throw P3dError("null argument");
+    if (n < 1 || n > 65535) throw P3dError(std::string(who) + ": 1 .. 65535 maps");
+    if (H < 1 || W < 1) throw P3dError(std::string(who) + ": empty map");
+    if ((long long)H * W > P3D_SCORE_MAX_PIXELS) throw P3dError(std::string(who) + ": H * W exceeds 2^23, the bound of the 64-bit integer sums");
+    if (flags <= 0 || (flags & ~P3D_SCORE_ALL)) throw P3dError(std::string(who) + ": flags are a non-empty set of P3D_SCORE_CC | SIM | JUDD | KL | NSS");
+    if (ties != P3D_SCORE_TIES_REFERENCE && ties != P3D_SCORE_TIES_EXPECTED) throw P3dError(std::string(who) + ": ties is P3D_SCORE_TIES_REFERENCE or P3D_SCORE_TIES_EXPECTED");
+    if (!fixation && (flags & (P3D_SCORE_JUDD | P3D_SCORE_NSS))) throw P3dError(std::string(who) + ": AUC_Judd and NSS need the fixation maps");
+}
+ScoreArgs score_args(int n, long long n_pix, int flags, int ties) {
+    ScoreArgs a;
+    const ScorePlan p = p3d_score_plan(n_pix);
+    a.n = n; a.n_pix = (int)n_pix; a.flags = flags; a.ties = ties; a.nblk = p.nblk; a.chunk = p.chunk;
+    return a;
+}
+void score_carve(Carve& c, ScoreArgs& a) {
+    a.tab = c.take<unsigned>((size_t)a.n * P3D_SCORE_TAB_WORDS);
+    a.lut = c.take<double>((size_t)a.n * 1024);
+    a.part = c.take<double>((size_t)a.n * a.nblk * 2);
+    a.out = c.take<double>((size_t)a.n * 5);
+}
+void score_sequence(const ScoreArgs& a, hipStream_t s) {
+    for (int st = 0; st < SCORE_STAGES; ++st) HIPCHECK(p3d_score_launch(st, a, s));
+}
+}  // namespace
+extern "C" {
+
+int p3d_video_score(p3d_handle* h, int first, int n, float scale, int H, int W, const unsigned char* density, const unsigned char* fixation,
+                    int flags, int ties, double* out, unsigned char* maps_out, double* stage_ms) {
+    API_BEGIN
+    if (!h) throw P3dError("null argument");
+    score_check("video_score", density, fixation, std::max(1, std::min(n, 65535)), H, W, flags, ties, out);
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->video_need_open("video_score");
+    h->video_range("video_score", first, n);
+    if (n > 65535) throw P3dError("video_score: 1 .. 65535 maps");
+    const bool temporal = h->temporal_cfg.on();
+    if (temporal) h->video_temporal_check("video_score", first, n);
+    for (int f = first; f < first + n; ++f)
+        if (h->vid_count[(size_t)f] == 0) throw P3dError("video_score: frame " + std::to_string(f) + " has no prediction yet (count 0)");
+    if (stage_ms) stage_ms[0] = stage_ms[1] = stage_ms[2] = 0.0;
+    const long long phw = h->vid_hw(), N = (long long)H * W;
+    const size_t bytes = (size_t)n * (size_t)N;
+    ScoreArgs a = score_args(n, N, flags, ties);
+    unsigned char* dd = nullptr; unsigned char* dx = nullptr;
+    U8Consumer use;
+    use.counters = (size_t)n * 2;
+    use.ms = stage_ms;
+    use.carve = [&](Carve& c) {
+        dd = c.take<unsigned char>(bytes);
+        dx = fixation ? c.take<unsigned char>(bytes) : nullptr;
+        score_carve(c, a);
+    };
+    use.before = [&](hipStream_t s) {
+        HIPCHECK(hipMemcpyAsync(dd, density, bytes, hipMemcpyHostToDevice, s));
+        if (fixation) HIPCHECK(hipMemcpyAsync(dx, fixation, bytes, hipMemcpyHostToDevice, s));
+    };
+    use.after = [&](hipStream_t s, const unsigned char* d, unsigned* counters) {
+        a.sal = d; a.den = dd; a.fix = dx; a.counter = counters;
+        score_sequence(a, s);
+    };
+    use.results = [&](hipStream_t s) { HIPCHECK(hipMemcpyAsync(out, a.out, (size_t)n * 5 * sizeof(double), hipMemcpyDeviceToHost, s)); };
+    maps_u8_chain(h, n, h->pred->H, h->pred->W, scale, H, W, maps_out, nullptr, temporal || h->vid_mode == VIDEO_MEAN ? (size_t)n * (size_t)phw : 0,
+                  [&](hipStream_t s, float* scratch, std::vector<PostRun>& runs) {
+                      runs.push_back({temporal ? h->video_temporal("video_score", first, n, scratch, s)
+                                               : h->video_finalize("video_score", first, n, scratch, s), phw, 1, n});
+                  }, &use);
+    API_END
+}
+
+int p3d_score_maps_u8(int device, const unsigned char* sal, const unsigned char* density, const unsigned char* fixation, int n, int H, int W,
+                      int flags, int ties, double* out) {
+    API_BEGIN
+    if (!sal) throw P3dError("null argument");
+    score_check("score_maps_u8", density, fixation, n, H, W, flags, ties, out);
+    metric_args(device, sal, density, 1, 1, out);
+    const long long N = (long long)H * W;
+    const size_t bytes = (size_t)n * (size_t)N;
+    DevArr<unsigned char> ds(bytes, sal), dd(bytes, density), dx(fixation ? bytes : 1, fixation);
+    ScoreArgs a = score_args(n, N, flags, ties);
+    a.counter = carve_scratch(nullptr, (size_t)n * 2, [&](Carve& c) { score_carve(c, a); });
+    a.sal = ds.p; a.den = dd.p; a.fix = fixation ? dx.p : nullptr;
+    score_sequence(a, nullptr);
+    HIPCHECK(hipDeviceSynchronize());
+    HIPCHECK(copy_now(out, a.out, (size_t)n * 5 * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    API_END
+}
+
+int p3d_debug_score_u8(int device, const unsigned char* sal, const unsigned char* density, const unsigned char* fixation, int n, int H, int W,
+                       int flags, int ties, int offset, uint32_t* hs, uint32_t* hf, uint32_t* hd, uint64_t* sd, double* out) {
+    API_BEGIN
+    if (!sal) throw P3dError("null argument");
+    score_check("debug_score_u8", density, fixation, n, H, W, flags, ties, out);
+    if (offset < 0 || offset > 15) throw P3dError("debug_score_u8: offset in [0, 15]");
+    metric_args(device, sal, density, 1, 1, out);
+    const long long N = (long long)H * W;
+    const size_t bytes = (size_t)n * (size_t)N;
+    ScoreArgs a = score_args(n, N, flags, ties);
+    // guards of 16 elements keep a 16-byte boundary at the data's start for every element type here; the sources are then shifted
+    Guarded<unsigned char> ds(bytes, 16, (size_t)offset, sal), dd(bytes, 16, (size_t)(2 * offset % 16), density),
+        dx(fixation ? bytes : 0, 16, (size_t)(3 * offset % 16), fixation);
+    Guarded<unsigned> tab((size_t)n * P3D_SCORE_TAB_WORDS, 16, 0, nullptr), counter((size_t)n * 2, 16, 0, nullptr);
+    Guarded<double> lut((size_t)n * 1024, 16, 0, nullptr), part((size_t)n * a.nblk * 2, 16, 0, nullptr), dout((size_t)n * 5, 16, 0, nullptr);
+    a.sal = ds.data(); a.den = dd.data(); a.fix = fixation ? dx.data() : nullptr;
+    a.tab = tab.data(); a.counter = counter.data(); a.lut = lut.data(); a.part = part.data(); a.out = dout.data();
+    score_sequence(a, nullptr);
+    std::vector<unsigned> t((size_t)n * P3D_SCORE_TAB_WORDS), zero((size_t)n * 2, 1u);
+    tab.back(t.data(), "debug_score_u8");
+    counter.back(zero.data(), "debug_score_u8");
+    dout.back(out, "debug_score_u8");
+    if (p3d_score_has(SCORE_TERMS, a)) { lut.back(nullptr, "debug_score_u8"); part.back(nullptr, "debug_score_u8"); }
+    else { lut.unchanged("debug_score_u8"); part.unchanged("debug_score_u8"); }      // no pass B: nothing of its was written
+    ds.unchanged("debug_score_u8"); dd.unchanged("debug_score_u8");
+    if (fixation) dx.unchanged("debug_score_u8");
+    for (unsigned z : zero) if (z != 0u) throw P3dError("debug_score_u8: an arrival counter was left at " + std::to_string(z));
+    for (int m = 0; m < n; ++m) {
+        const unsigned* row = t.data() + (size_t)m * P3D_SCORE_TAB_WORDS;
+        if (hs) std::copy(row, row + 256, hs + (size_t)m * 256);
+        if (hf) std::copy(row + 256, row + 512, hf + (size_t)m * 256);
+        if (hd) std::copy(row + 512, row + 768, hd + (size_t)m * 256);
+        if (sd) sd[m] = (uint64_t)row[768] | ((uint64_t)row[769] << 32);
+    }
+    API_END
+}
+
+int p3d_debug_score_plan(int64_t n_pix, int n, int offset, int* blocks_per_map, int* pixels_per_block, int64_t* products_per_lane) {
+    API_BEGIN
+    if (!blocks_per_map || !pixels_per_block || !products_per_lane) throw P3dError("null argument");
+    if (n_pix < 1 || n_pix > P3D_SCORE_MAX_PIXELS || n < 1 || n > 65535 || offset < 0 || offset > 15)
+        throw P3dError("debug_score_plan: 1 <= n_pix <= 2^23, 1 .. 65535 maps, offset in [0, 15]");
+    const ScorePlan p = p3d_score_plan(n_pix);
+    *blocks_per_map = p.nblk; *pixels_per_block = p.chunk;
+    *products_per_lane = p3d_score_lane_products(n_pix, n, (unsigned)offset, (unsigned)(2 * offset % 16), (unsigned)(3 * offset % 16));
     API_END
 }
 

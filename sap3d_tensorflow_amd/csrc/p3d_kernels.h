@@ -1005,6 +1005,48 @@ struct FixSelectArgs {
 LaunchDesc p3d_fix_select_desc(const FixSelectArgs& a);
 hipError_t p3d_fix_select_launch(const FixSelectArgs& a, hipStream_t s);
 
+// ---- scoring 8-bit maps against 8-bit ground truth (score_u8.hip; p3d_video_score / p3d_score_maps_u8, the law in include/p3d_hip.h) ----
+// One launch sequence on n maps of n_pix bytes, 1 <= n_pix <= 2^23, sal / den / fix [n][n_pix] (fix may be null: nothing is fixated):
+//   SCORE_COUNT  tab[n][P3D_SCORE_TAB_WORDS] zeroed in stream order, then score_count_kernel: hs[256], hf[256], hd[256] and the
+//                64-bit sum of s * d of every map; the last arriving block of a map (counter[m]) writes out[m][0 .. 5) -- CC, NaN,
+//                AUC_Judd, NaN, NSS, an unselected column NaN -- and, with SIM or KL selected, lut[m][4][256]: us, ud, ps, pd;
+//   SCORE_TERMS  with SIM or KL selected only: score_terms_kernel, block partials in part[n][nblk][2], the last arriving block of
+//                a map (counter[n + m]) folds them in block order into out[m][1] and out[m][3].
+// Refused (hipErrorInvalidValue): a missing buffer, n outside [1, 65535], n_pix outside the range, flags outside the five bits, an
+// unknown ties law, JUDD or NSS without fix, nblk / chunk other than p3d_score_plan's.
+constexpr int P3D_SCORE_TAB_WORDS = 770;                  // 3 * 256 counters, then the sum of products as two words (8-byte aligned)
+constexpr int P3D_SCORE_MAX_PIXELS = 1 << 23;             // 65025 * 2^46 < 2^63: every integer of FINALISE fits a signed 64-bit word
+constexpr int P3D_SCORE_ALL = 31;
+enum { SCORE_COUNT = 0, SCORE_TERMS = 1, SCORE_STAGES = 2 };
+struct ScoreArgs {
+    const unsigned char* sal = nullptr; const unsigned char* den = nullptr; const unsigned char* fix = nullptr;
+    int n = 0, n_pix = 0, flags = 0, ties = 0;
+    int nblk = 0, chunk = 0;                  // p3d_score_plan(n_pix)
+    unsigned* tab = nullptr;                  // [n][P3D_SCORE_TAB_WORDS]
+    double* lut = nullptr;                    // [n][4][256]
+    double* part = nullptr;                   // [n][nblk][2]
+    unsigned* counter = nullptr;              // [2 n]
+    double* out = nullptr;                    // [n][5]
+};
+// blocks per map (one per 32768 pixels, at most 256) and pixels per block, a multiple of 16 so that every block of a map starts as
+// far past a 16-byte boundary as the map does
+struct ScorePlan { int nblk = 0, chunk = 0; };
+ScorePlan p3d_score_plan(long long n_pix);
+// How a block cuts its len pixels: `head` single pixels up to the first 16-byte boundary, `words` whole 16-byte words, the rest
+// single.  Sources that are not aligned alike: every pixel single.
+struct ScoreCut { int head, words; };
+__host__ __device__ inline ScoreCut p3d_score_cut(uintptr_t as, uintptr_t ad, uintptr_t ax, int len) {
+    if (((as ^ ad) & 15) || ((as ^ ax) & 15)) return {len, 0};
+    const int head = (int)((16 - (as & 15)) & 15);
+    if (head >= len) return {len, 0};
+    return {head, (len - head) >> 4};
+}
+// the most products s * d any lane of pass A adds, for n maps whose sources start off_s / off_d / off_x bytes past a 16-byte boundary
+long long p3d_score_lane_products(long long n_pix, int n, unsigned off_s, unsigned off_d, unsigned off_x);
+bool p3d_score_has(int stage, const ScoreArgs& a);
+LaunchDesc p3d_score_desc(int stage, const ScoreArgs& a);
+hipError_t p3d_score_launch(int stage, const ScoreArgs& a, hipStream_t s);      // a stage the arguments do not ask for: nothing, success
+
 // ---- misc ---------------------------------------------------------------------------------------
 hipError_t p3d_add_inplace(float* dst, int lddst, const float* src, int ldsrc, long M, int C, hipStream_t s);
 hipError_t p3d_copy_strided(float* dst, int lddst, const float* src, int ldsrc, long M, int C, hipStream_t s);

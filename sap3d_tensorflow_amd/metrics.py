@@ -322,3 +322,65 @@ def evaluate_maps(maps, density, fixation, size=None, jitter=True, n_rep=100, st
                  n_rows.ctypes.data_as(ip), s_rep, s_step, got_other.ctypes.data_as(C.POINTER(C.c_uint32)), _dp(per_rep))
     check(getattr(lib(), "p3d_debug_eval_maps" + rungs[level])(*args))
     return (out, xout, per_rep) if level == 5 else (out, xout) if level >= 3 else out
+
+
+def score_flags(columns):
+    """The flags of p3d_video_score / p3d_score_maps_u8 for column names of _lib.SCORE_COLUMNS ("matlab": cc, sim, judd), or an
+    int that already is such a set."""
+    from ._lib import SCORE_COLUMNS, SCORE_MATLAB
+    if isinstance(columns, (int, np.integer)):
+        return int(columns)
+    if isinstance(columns, str):
+        columns = (columns,)
+    flags = 0
+    for c in columns:
+        for name in (SCORE_MATLAB if c == "matlab" else (c,)):
+            if name not in SCORE_COLUMNS:
+                raise ValueError("score column %r: have %s and 'matlab'" % (name, sorted(SCORE_COLUMNS)))
+            flags |= SCORE_COLUMNS[name]
+    return flags
+
+
+def score_ties(ties):
+    from ._lib import SCORE_TIES
+    if ties not in SCORE_TIES:
+        raise ValueError("ties %r: have %s" % (ties, sorted(SCORE_TIES)))
+    return SCORE_TIES[ties]
+
+
+def score_plan(n_pix, n=1, offset=0):
+    """Test hook (p3d_debug_score_plan, host only): (blocks per map, pixels per block, most products a lane adds) of pass A."""
+    b, c, k = C.c_int(0), C.c_int(0), C.c_int64(0)
+    check(lib().p3d_debug_score_plan(int(n_pix), int(n), int(offset), C.byref(b), C.byref(c), C.byref(k)))
+    return b.value, c.value, k.value
+
+
+def score_bytes(sal, density, fixation, flags=("cc", "sim", "judd", "kl", "nss"), ties="expected", with_tables=False, device=0, offset=0):
+    """8-bit saliency maps scored against 8-bit density and fixation maps (fixated: byte >= 128), all uint8 [n, H, W] or [H, W] of
+    one shape -> float64 [n, 5]: CC, SIM, AUC_Judd, KL, NSS, an unselected column NaN (include/p3d_hip.h, "Scoring 8-bit maps";
+    p3d_score_maps_u8).  ties: how AUC_Judd treats equal bytes, "reference" (utils/metrics.py with jitter=False) or "expected"
+    (the mean over every order of the tied pixels).  fixation may be None when neither judd nor nss is selected.  with_tables
+    (the test hook p3d_debug_score_u8, sources `offset` bytes past a 16-byte boundary): also dict(hs, hf, hd uint32 [n, 256],
+    sd uint64 [n])."""
+    s = np.ascontiguousarray(sal)
+    d = np.ascontiguousarray(density)
+    x = None if fixation is None else np.ascontiguousarray(fixation)
+    for a in (s, d) + (() if x is None else (x,)):
+        if a.dtype != np.uint8 or a.shape != s.shape:
+            raise ValueError("saliency, density and fixation maps are uint8 arrays of one shape")
+    if s.ndim not in (2, 3) or s.size == 0:
+        raise ValueError("expected non-empty [H, W] or [n, H, W] maps")
+    n = s.shape[0] if s.ndim == 3 else 1
+    H, W = s.shape[-2:]
+    u8 = C.POINTER(C.c_ubyte)
+    out = np.empty((n, 5), np.float64)
+    args = (device, s.ctypes.data_as(u8), d.ctypes.data_as(u8), None if x is None else x.ctypes.data_as(u8), n, int(H), int(W),
+            score_flags(flags), score_ties(ties))
+    if not with_tables:
+        check(lib().p3d_score_maps_u8(*args, _dp(out)))
+        return out
+    t = dict(hs=np.empty((n, 256), np.uint32), hf=np.empty((n, 256), np.uint32), hd=np.empty((n, 256), np.uint32), sd=np.empty(n, np.uint64))
+    u32 = C.POINTER(C.c_uint32)
+    check(lib().p3d_debug_score_u8(*args, int(offset), t["hs"].ctypes.data_as(u32), t["hf"].ctypes.data_as(u32), t["hd"].ctypes.data_as(u32),
+                                   t["sd"].ctypes.data_as(C.POINTER(C.c_uint64)), _dp(out)))
+    return out, t

@@ -899,6 +899,34 @@ class P3DSession:
         self.last_maps_ms = dict(device=ms[0], d2h=ms[1])
         return out
 
+    def video_score(self, first, n, density, fixation, size=(1080, 960), scale=255., columns=("cc", "sim", "judd"), ties="expected",
+                    with_maps=False):
+        """Score frames first .. first + n - 1 of the open video on the device (an addition: the arithmetic of the reference's
+        utils/matlab_metric/metric_video_base.m protocol): video_maps_u8's bytes, where they are, against density and fixation,
+        uint8 [n, H, W] at `size` (fixated: byte >= 128) -> float64 [n, 5]: CC, SIM, AUC_Judd, KL, NSS, NaN in the columns not
+        named in `columns` ("cc", "sim", "judd", "kl", "nss"; "matlab" is the first three).  ties: AUC_Judd on equal bytes,
+        "reference" (utils/metrics.py with jitter=False) or "expected" (its mean over every order of the tied pixels, what the
+        default jitter does to an 8-bit map).  fixation may be None when neither judd nor nss is asked for.  with_maps: also the
+        scored bytes, uint8 [n, H, W].  Device times are left in `last_score_ms`.  include/p3d_hip.h holds the exact rules."""
+        from . import metrics
+        H, W = (size, size) if np.isscalar(size) else tuple(size)
+        n = max(int(n), 0)
+        valid = H >= 1 and W >= 1 and H * W <= 2 ** 23
+        dens = np.ascontiguousarray(density)
+        fix = None if fixation is None else np.ascontiguousarray(fixation)
+        for a in (dens,) + (() if fix is None else (fix,)):
+            if a.dtype != np.uint8 or (valid and a.shape != (n, H, W)):
+                raise ValueError("density and fixation maps are uint8 [%d, %d, %d]" % (n, H, W))
+        out = np.full((n, 5), np.nan, np.float64)
+        maps = np.empty((n, H, W) if valid else (0,), np.uint8) if with_maps else None
+        ms = (C.c_double * 3)()
+        check(lib().p3d_video_score(self._h, int(first), n, float(scale), int(H), int(W), dens.ctypes.data_as(_lib._u8p),
+                                    None if fix is None else fix.ctypes.data_as(_lib._u8p), metrics.score_flags(columns),
+                                    metrics.score_ties(ties), out.ctypes.data_as(_lib._dp),
+                                    None if maps is None else maps.ctypes.data_as(_lib._u8p), ms))
+        self.last_score_ms = dict(upload=ms[0], device=ms[1], score=ms[2])
+        return (out, maps) if with_maps else out
+
     # ---- resident training set (p3d_trainset_*) -------------------------------------------------------------
     def open_trainset(self, frames_per_video, frame_format="u8", fixations=False, mean_rgb=(90., 102., 98.)):
         """Keep a training set on the device (an addition: the reference's loader, dataflow.py:39-62, cuts overlapping clips on
