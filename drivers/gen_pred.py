@@ -202,6 +202,78 @@ def score_video_resident(sess, F, density, fixation, size, columns, ties, video_
     return scores, t
 
 
+def sauc_ids(rng, P, c0, c1, M, own):
+    """The pool slots whose union frames c0 .. c1 - 1 sample shuffled AUC's locations from, int32 [c1 - c0, M], drawn row by row in
+    frame order (repeats allowed).  own: the pool is the video's own P fixation maps, slot = frame, and a frame never draws itself:
+    randint over the P - 1 others."""
+    ids = np.empty((c1 - c0, M), np.int32)
+    for f in range(c0, c1):
+        if own:
+            r = rng.randint(0, P - 1, M)
+            ids[f - c0] = r + (r >= f)
+        else:
+            ids[f - c0] = rng.randint(0, P, M)
+    return ids
+
+
+def score_video_resident_auc(sess, F, density, fixation, size, columns, ties, borji, sauc, pool_size, own_pool, n_rep, step, seed,
+                             video_dir=None, ext=None, writers=4):
+    """score_video_resident with AUC-Borji and / or shuffled AUC of the same bytes (P3DSession.video_score_auc; --score-borji,
+    --score-sauc M) -> (scores [F, 5], auc float64 [F, 2]: the Borji and shuffled means per frame, NaN where not asked; times).
+    One RandomState(seed) per video; per chunk of SCORE_CHUNK frames it draws, in this order: the rows of pool slots in frame order
+    (sauc_ids), [video_shuffled_begin], Borji's randint per frame with fixations (metrics.borji_draws_u8), metrics.shuffled_draws.
+    With video_dir the images come from video_maps_u8, one more run of the maps' chain per chunk."""
+    from concurrent.futures import ThreadPoolExecutor
+    from sap3d_tensorflow_amd import metrics
+    scores = np.full((F, len(SCORE_NAMES)), np.nan, np.float64)
+    auc = np.full((F, 2), np.nan, np.float64)
+    t = dict(upload=0.0, device=0.0, score=0.0, auc=0.0, files=0)
+    rng = np.random.RandomState(seed)
+    held = []
+    with ThreadPoolExecutor(max_workers=writers) as pool:
+        for first in range(0, F, SCORE_CHUNK):
+            n = min(SCORE_CHUNK, F - first)
+            fix = fixation[first:first + n]
+            n_other = bidx = ranks = n_rows = None
+            if sauc:
+                n_other = sess.video_shuffled_begin(sauc_ids(rng, pool_size, first, first + n, sauc, own_pool))
+            nf = np.count_nonzero(fix.reshape(n, -1) >= 128, axis=1)
+            if borji:
+                bidx, nf = metrics.borji_draws_u8(fix, n_rep, rng)
+            if sauc:
+                ranks, n_rows = metrics.shuffled_draws(nf, n_other, n_rep, rng)
+            got = sess.video_score_auc(first, n, density[first:first + n], fix, size=size, columns=columns, ties=ties, borji_idx=bidx,
+                                       shuffled_ranks=ranks, n_rows=n_rows, n_rep=n_rep, step_size=step)
+            for k in ("upload", "device", "score", "auc"):
+                t[k] += sess.last_score_ms[k]
+            scores[first:first + n] = got["scores"]
+            if borji:
+                auc[first:first + n, 0] = [np.mean(r) for r in got["borji"]]
+            if sauc:
+                auc[first:first + n, 1] = [np.mean(r) for r in got["shuffled"]]
+            if video_dir is not None:
+                maps = sess.video_maps_u8(first, n, size=size)
+                for fut in held:
+                    fut.result()
+                held = [pool.submit(save_image, os.path.join(video_dir, "frame_%d.%s" % (first + k + 1, ext)), m, ext)
+                        for k, m in enumerate(maps)]
+                t["files"] += n
+        for fut in held:
+            fut.result()
+    return scores, auc, t
+
+
+def auc_means(auc):
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        return np.nanmean(np.asarray(auc, np.float64).reshape(-1, 2), axis=0)
+
+
+def format_auc(means):
+    return "borji=%r, sauc=%r" % (float(means[0]), float(means[1]))
+
+
 def save_image(path, m, ext):
     """One 8-bit map with PIL: PNG at compress_level 1 (lossless: the level changes the file size, not the pixels), JPEG at
     quality 95 (cv2.IMWRITE_JPEG_QUALITY's default)."""
@@ -308,6 +380,18 @@ def parse_args(argv=None):
     p.add_argument("--score-ties", choices=("reference", "expected"), default="expected", help="[addition] --truth: AUC_Judd on equal bytes: "
                    "utils/metrics.py with jitter=False, or its mean over every order of the tied pixels (what the default jitter does "
                    "to an 8-bit map, without a draw)")
+    p.add_argument("--score-borji", action="store_true", help="[addition] --truth: also AUC-Borji of every frame, metric_video_base.m's "
+                   "sixth column, on the device (P3DSession.video_score_auc).  Writes <out>/<name>_auc.npy, [F, 2]: the Borji and "
+                   "shuffled-AUC means per frame, NaN where not asked, and prints their means")
+    p.add_argument("--score-sauc", type=int, default=0, metavar="M", help="[addition] --truth: also shuffled AUC of every frame, its random "
+                   "locations the fixations of M other maps of the pool (1 .. 64)")
+    p.add_argument("--sauc-pool", type=str, default="", metavar="FILE.npy", help="[addition] --score-sauc: uint8 [P, H, W] fixation maps of other "
+                   "videos at --size.  Without it the pool is the video's own frames, and a frame never draws itself")
+    p.add_argument("--score-rep", type=int, default=100, metavar="N", help="[addition] --score-borji / --score-sauc: random splits per frame")
+    p.add_argument("--score-step", type=float, default=0.1, metavar="S", help="[addition] --score-borji / --score-sauc: the threshold step, "
+                   "at most 1024 thresholds")
+    p.add_argument("--score-seed", type=int, default=0, metavar="N", help="[addition] --score-borji / --score-sauc: the seed of every video's "
+                   "numpy RandomState, which makes all draws")
     p.add_argument("--base", type=int, default=64, help=argparse.SUPPRESS)
     p.add_argument("--blocks", type=str, default="3,8,36", help=argparse.SUPPRESS)
     p.add_argument("--time", action="store_true", help="print per-video wall times (png / jpg: also the device stage and the host encode)")
@@ -325,6 +409,15 @@ def parse_args(argv=None):
         args.resident = True
     elif args.score_columns != ["cc", "sim", "judd"] or args.score_ties != "expected":
         p.error("--score-columns / --score-ties need --truth DIR")
+    args.score_auc = bool(args.score_borji or args.score_sauc)
+    if not args.truth and (args.score_auc or args.sauc_pool or args.score_rep != 100 or args.score_step != 0.1 or args.score_seed != 0):
+        p.error("--score-borji / --score-sauc / --sauc-pool / --score-rep / --score-step / --score-seed need --truth DIR")
+    if not 0 <= args.score_sauc <= 64:
+        p.error("--score-sauc takes 1 .. 64 other maps")
+    if args.sauc_pool and not args.score_sauc:
+        p.error("--sauc-pool needs --score-sauc M")
+    if args.score_rep < 1 or not args.score_step > 0. or 1. / args.score_step > 1024:
+        p.error("--score-rep is at least 1, --score-step positive and at least 1 / 1024")
     if args.truth:
         pass                                          # the stages below shape the scored maps too: --write npy may have them
     elif args.write == "npy" and (args.blur_sigma != 0. or args.blur_radius != 0 or args.normalize != "none"):
@@ -401,6 +494,7 @@ def match_target(args):
 def run(sess, args):
     os.makedirs(args.out, exist_ok=True)
     video_means = []
+    args.auc_means = []
     for path in sorted(glob.glob(os.path.join(args.videos, "*.npy"))):
         if args.resident:
             means = run_resident(sess, args, path)
@@ -433,6 +527,8 @@ def run(sess, args):
 
     if args.truth and video_means:
         print("mean over %d videos: %s" % (len(video_means), format_means(nan_means(np.stack(video_means)))))
+    if args.truth and args.auc_means:
+        print("auc mean over %d videos: %s" % (len(args.auc_means), format_auc(auc_means(np.stack(args.auc_means)))))
 
 
 def run_resident(sess, args, path):
@@ -449,7 +545,33 @@ def run_resident(sess, args, path):
     F = predict_video_resident(sess, np.load(path), args.batch, args.stride, args.overlap, times)
     t1 = time.perf_counter()
     means = ts = None
-    if args.truth:
+    if args.truth and args.score_auc:
+        density, fixation = load_truth(args.truth, name, F, args.size)
+        pool_size = 0
+        if args.score_sauc:
+            pool_maps = fixation
+            if args.sauc_pool:
+                pool_maps = np.load(args.sauc_pool)
+                if pool_maps.dtype != np.uint8 or pool_maps.ndim != 3 or pool_maps.shape[1:] != tuple(args.size):
+                    raise ValueError("--sauc-pool: %s is %s %s, not uint8 [P, %d, %d]" % ((args.sauc_pool, pool_maps.dtype, pool_maps.shape) + tuple(args.size)))
+            elif F < 2:
+                raise ValueError("--score-sauc: a video of one frame has no other frame to draw from; give --sauc-pool")
+            pool_size = len(pool_maps)
+            sess.open_fixation_pool(tuple(args.size), pool_size)
+            sess.fixation_pool_put(0, pool_maps)
+        scores, auc, ts = score_video_resident_auc(sess, F, density, fixation, tuple(args.size), tuple(args.score_columns), args.score_ties,
+                                                   args.score_borji, args.score_sauc, pool_size, not args.sauc_pool, args.score_rep,
+                                                   args.score_step, args.score_seed, video_dir if args.write != "npy" else None, args.write,
+                                                   args.writers)
+        if args.score_sauc:
+            sess.close_fixation_pool()
+        np.save(os.path.join(args.out, name + "_scores.npy"), scores)
+        np.save(os.path.join(args.out, name + "_auc.npy"), auc)
+        means = nan_means(scores)
+        print("%s scores over %d frames: %s" % (name, F, format_means(means)))
+        print("%s auc over %d frames: %s" % (name, F, format_auc(auc_means(auc))))
+        args.auc_means.append(auc_means(auc))
+    elif args.truth:
         density, fixation = load_truth(args.truth, name, F, args.size)
         scores, ts = score_video_resident(sess, F, density, fixation, tuple(args.size), tuple(args.score_columns), args.score_ties,
                                           video_dir if args.write != "npy" else None, args.write, args.writers)
@@ -476,6 +598,8 @@ def run_resident(sess, args, path):
             print("  %s: temporal %s: %.3f ms on the device in the last read-out" % (name, args.temporal, temporal_ms))
         if ts is not None:
             print("  %s: scoring: uploads %.2f ms, maps %.2f ms, scoring launches %.3f ms on the device" % (name, ts["upload"], ts["device"], ts["score"]))
+            if "auc" in ts:
+                print("  %s: scoring: select + sweeps %.3f ms on the device" % (name, ts["auc"]))
         if args.write != "npy" and ts is None:
             print("  %s: maps %.1f ms (device resize/quantise %.2f ms, d2h %.2f ms) | encode %.1f ms thread time on %d writers"
                   % (name, t["gpu"], t["device"], t["d2h"], t["encode"], args.writers))

@@ -1463,6 +1463,65 @@ int p3d_debug_score_u8(int device, const unsigned char* sal, const unsigned char
                        int W, int flags, int ties, int offset, uint32_t* hs, uint32_t* hf, uint32_t* hd, uint64_t* sd, double* out);
 int p3d_debug_score_plan(int64_t n_pix, int n, int offset, int* blocks_per_map, int* pixels_per_block, int64_t* products_per_lane);
 
+/* ---- AUC-Borji and shuffled AUC of 8-bit maps (an ADDITION: metric_video_base.m's saliency_score_BOR column, lines 132-135, and
+ * the shuffled AUC that video-saliency tables report beside it, with the definitions of utils/metrics.py:88-197).  OFF until called:
+ * every other entry point issues what it issued before and returns the same bits.  PARITY UNPINNED beyond utils/metrics.py: this
+ * text is the contract, tests/score_auc_ref.py replays it in numpy and is itself held to oracle.metrics.AUC_Borji and
+ * oracle.evaluation.AUC_shuffled (per split, absolute 1e-12: np.trapz adds the same terms in its own order).
+ *   SPLIT SWEEP  Per map: saliency bytes s and fixation bytes x, [H][W] each, N = H * W, 1 <= N <= 2^23; a pixel is fixated exactly
+ *           when x >= 128.  Sample pixel indices idx[n_rows][n_rep], int32, row-major (the reference's [n_fix, n_rep]).
+ *           hs, hf, nf as in TABLES above; lo / hi the lowest / highest v with hs[v] > 0; maxfix the highest v with hf[v] > 0
+ *           (-1 when nf = 0); u_v = (double)(v - lo) / (double)(hi - lo); kmax = (int)ceil(1.0 / step), a step that is not
+ *           positive or gives kmax > 1024 is refused; t_k = (double)k * step; lev[v] = the number of k < kmax with t_k <= u_v,
+ *           for every v in 0 .. 255 (0 for every v on a flat map, hi = lo).
+ *           For split rep: b_i = s[idx[i][rep]]; top = max(maxfix, max_i b_i) (n_rows = 0: maxfix); K = (int)ceil(u_top / step),
+ *           or 0 when u_top = 0 -- len(np.arange(0, u_top, step)).  For k = K - 1 .. 0, in this order: ctp = sum of hf[v] over
+ *           lev[v] > k; cfp = the number of i with lev[b_i] > k (both integers); x = (double)cfp / (double)nf,
+ *           y = (double)ctp / (double)nf; area += (x - px) * (y + py) * 0.5, from (px, py) = (0, 0); then (px, py) = (x, y).  After
+ *           the last k the closing term (1 - px) * (1 + py) * 0.5 is added.  float64, every operation rounded on its own.  The
+ *           false-positive rate divides by nf also when n_rows < nf (utils/metrics.py:151-152).  A split is NaN when nf = 0 or
+ *           hi = lo (the reference fails on a flat map: not pinned).  Results are per split; the mean over the splits is the
+ *           host's (np.mean), as with p3d_last_eval_shuffled.
+ *   AUC-Borji    the sweep with n_rows = nf and idx = randint(0, N, [nf, n_rep]) drawn on the host (utils/metrics.py:139).
+ *   Shuffled AUC the sweep with n_rows = min(nf, n_other) and idx the SELECT of the host's ranks in the UNION of M pool slots
+ *           (STORE / UNION / SELECT / DRAW ORDER of "Shuffled AUC in the evaluation pass" above, unchanged).
+ *   The device never draws.
+ * p3d_score_sweep_u8  op level, host arrays: n maps sal / fixation [n][H][W], idx the maps' rows concatenated (nothing for a map
+ *                    whose n_rows is 0; may be NULL when every n_rows is 0) -> per_rep [n][n_rep].  Refused before the sweep's
+ *                    launch, the outputs untouched: a NULL array, n outside 1 .. 65535, N outside the range, a bad step,
+ *                    n_rep < 1, an index outside [0, N), n_rows[b] < 0 or > nf[b] -- nf the device's count (pass A and the
+ *                    preparation launch have then run), read back once.
+ * p3d_video_shuffled_begin  UNION and its scan for n frames out of the handle's fixation pool (p3d_fixpool_open / p3d_fixpool_put):
+ *                    ids [n][M], n_other_out [n] after one synchronisation.  The union is held in buffers of its own: the state
+ *                    of p3d_eval_shuffled_begin / _draws, armed or not, is neither read nor disturbed.  Refused as
+ *                    p3d_eval_shuffled_begin refuses, and n outside 1 .. 65535; the pool's size is checked at the scoring call.
+ *                    p3d_fixpool_open and p3d_fixpool_close drop the held union.
+ * p3d_video_score_auc  p3d_video_score's maps chain once, then everything asked for on the same bytes (bit for bit
+ *                    p3d_video_maps_u8's under the handle's current settings); pass A runs once per call.  flags != 0: the five
+ *                    columns out [n][5] from p3d_video_score's launch descriptions, the same bits; flags = 0 needs out = NULL, and
+ *                    density may then be NULL (pass A counts neither hd nor the products).  borji_idx (NULL: no AUC-Borji): every
+ *                    frame's [nf][n_rep] indices, concatenated -> borji_per_rep [n][n_rep].  ranks (NULL: no shuffled AUC):
+ *                    [n_rows[b]][n_rep] ranks per frame, concatenated -> shuffled_per_rep [n][n_rep]; n_rows[b] must equal
+ *                    min(nf[b], n_other[b]) of the held union, the union must be for n frames and the pool for H x W, a rank must
+ *                    lie in [0, n_other[b]).  nf is counted from `fixation` on the host and the device's count is held to it.
+ *                    Every refusal comes before any launch or upload and leaves the outputs untouched.  stage_ms (or NULL) [4]:
+ *                    HIP-event milliseconds of the uploads, of the maps' chain, of the five-column scoring launches (pass A
+ *                    included), of the preparation + select + sweeps.
+ * TEST HOOK (tests/test_gpu_score_auc.py):
+ * p3d_debug_score_sweep_u8  p3d_score_sweep_u8's launch descriptions with every device buffer between guard elements: sal starts
+ *                    `offset` bytes (0 .. 15) past a 16-byte boundary and fixation (3 offset) mod 16 bytes past one, as in
+ *                    p3d_debug_score_u8; -1 if a guard or an input changed.  lev_out [n][256], top_out [n][n_rep] (a split's top,
+ *                    -1 where nothing is fixated and no row is given) and per_rep come back. */
+int p3d_score_sweep_u8(int device, const unsigned char* sal, const unsigned char* fixation, int n, int H, int W, const int* idx,
+                       const int* n_rows, int n_rep, double step, double* per_rep);
+int p3d_debug_score_sweep_u8(int device, const unsigned char* sal, const unsigned char* fixation, int n, int H, int W, const int* idx,
+                             const int* n_rows, int n_rep, double step, int offset, int* lev_out, int* top_out, double* per_rep);
+int p3d_video_shuffled_begin(p3d_handle* h, int n, const int* ids, int M, uint32_t* n_other_out);
+int p3d_video_score_auc(p3d_handle* h, int first, int n, float scale, int H, int W, const unsigned char* density /* may be NULL */,
+                        const unsigned char* fixation, int flags, int ties, double* out /* may be NULL */,
+                        const int* borji_idx /* may be NULL */, const int* ranks /* may be NULL */, const int* n_rows, int n_rep,
+                        double step, double* borji_per_rep, double* shuffled_per_rep, double* stage_ms /* may be NULL */);
+
 /* CRC-32C of a host buffer (host-side helper of the TensorFlow checkpoint reader / writer, sap3d_tensorflow_amd/tf_checkpoint.py:
  * the bundle format of train.py:180-185,266-267 checksums every tensor); crc = running value, 0 to start. */
 uint32_t p3d_crc32c(const void* data, size_t n, uint32_t crc);

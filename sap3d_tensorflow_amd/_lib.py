@@ -382,6 +382,11 @@ SIGNATURES = {
     "p3d_debug_score_u8": (C.c_int, [C.c_int, _u8p, _u8p, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32),
                                      C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), _dp]),
     "p3d_debug_score_plan": (C.c_int, [C.c_int64, C.c_int, C.c_int, _ip, _ip, _i64p]),
+    "p3d_score_sweep_u8": (C.c_int, [C.c_int, _u8p, _u8p, C.c_int, C.c_int, C.c_int, _ip, _ip, C.c_int, C.c_double, _dp]),
+    "p3d_debug_score_sweep_u8": (C.c_int, [C.c_int, _u8p, _u8p, C.c_int, C.c_int, C.c_int, _ip, _ip, C.c_int, C.c_double, C.c_int, _ip, _ip, _dp]),
+    "p3d_video_shuffled_begin": (C.c_int, [C.c_void_p, C.c_int, _ip, C.c_int, C.POINTER(C.c_uint32)]),
+    "p3d_video_score_auc": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, _u8p, _u8p, C.c_int, C.c_int, _dp, _ip, _ip, _ip,
+                                      C.c_int, C.c_double, _dp, _dp, _dp]),
     "p3d_crc32c": (C.c_uint32, [C.c_void_p, C.c_size_t, C.c_uint32]),
     "p3d_shutdown": (C.c_int, []),
 }

@@ -1816,6 +1816,293 @@ int p3d_debug_score_plan(int64_t n_pix, int n, int offset, int* blocks_per_map, 
     API_END
 }
 
+}  // extern "C"
+namespace {
+// ---- SPLIT SWEEP on 8-bit maps: AUC-Borji and shuffled AUC (score_auc_u8.hip; the law in include/p3d_hip.h): one check, one
+// scratch layout and one launch sequence for p3d_score_sweep_u8, p3d_debug_score_sweep_u8 and p3d_video_score_auc ---------------
+ScoreSweepArgs sweep_args(const char* who, int n, long long n_pix, int n_rep, double step) {
+    ScoreSweepArgs q;
+    q.kmax = p3d_sweep_kmax(step);
+    if (q.kmax < 1) throw P3dError(std::string(who) + ": the step is positive and gives at most 1024 thresholds (ceil(1 / step))");
+    if (n_rep < 1) throw P3dError(std::string(who) + ": n_rep >= 1");
+    q.n = n; q.n_pix = (int)n_pix; q.n_rep = n_rep; q.step = step; q.cols = p3d_sweep_cols(q.kmax, n_rep);
+    return q;
+}
+void sweep_carve(Carve& c, ScoreSweepArgs& q) {
+    q.lev = c.take<int>((size_t)q.n * 256);
+    q.lad = c.take<unsigned>((size_t)q.n * (q.kmax + 1));
+    q.info = c.take<int>((size_t)q.n * 4);
+}
+// meta [n][2] of maps whose rows are concatenated: the row count, the offset of the first index; -> the number of indices
+std::vector<long long> sweep_meta(const char* who, const int* n_rows, int n, int n_rep, size_t& total) {
+    std::vector<long long> meta((size_t)n * 2);
+    long long at = 0;
+    for (int b = 0; b < n; ++b) {
+        if (n_rows[b] < 0) throw P3dError(std::string(who) + ": map " + std::to_string(b) + ": a negative row count");
+        meta[(size_t)b * 2] = n_rows[b]; meta[(size_t)b * 2 + 1] = at;
+        at += (long long)n_rows[b] * n_rep;
+        if (at > INT32_MAX) throw P3dError(std::string(who) + ": too many indices");
+    }
+    total = (size_t)at;
+    return meta;
+}
+// fixated pixels (byte >= 128) of every map, counted on the host
+std::vector<int> host_n_fix(const unsigned char* fixation, int n, long long n_pix) {
+    std::vector<int> nf((size_t)n);
+    for (int b = 0; b < n; ++b) {
+        const unsigned char* p = fixation + (size_t)b * n_pix;
+        int k = 0;
+        for (long long i = 0; i < n_pix; ++i) k += p[i] >> 7;
+        nf[(size_t)b] = k;
+    }
+    return nf;
+}
+// the op-level sweep's checks that need no device; -> meta
+std::vector<long long> sweep_op_check(const char* who, const void* sal, const void* fixation, int n, int H, int W, const int* idx, const int* n_rows,
+                                      const void* per_rep, int n_rep, size_t& total) {
+    if (!sal || !fixation || !n_rows || !per_rep) throw P3dError("null argument");
+    if (n < 1 || n > 65535) throw P3dError(std::string(who) + ": 1 .. 65535 maps");
+    if (H < 1 || W < 1) throw P3dError(std::string(who) + ": empty map");
+    if ((long long)H * W > P3D_SCORE_MAX_PIXELS) throw P3dError(std::string(who) + ": H * W exceeds 2^23");
+    std::vector<long long> meta = sweep_meta(who, n_rows, n, n_rep, total);
+    if (total > 0 && !idx) throw P3dError("null argument");
+    check_indices(idx, total, (long long)H * W, who);
+    return meta;
+}
+// the device's counts (info[b][0] = nf) against the rows: n_rows[b] <= nf[b]
+void sweep_check_rows(const char* who, const std::vector<int>& info, const int* n_rows, int n) {
+    for (int b = 0; b < n; ++b)
+        if (n_rows[b] > info[(size_t)b * 4])
+            throw P3dError(std::string(who) + ": map " + std::to_string(b) + ": " + std::to_string(n_rows[b]) + " rows, but the map has " +
+                           std::to_string(info[(size_t)b * 4]) + " fixated pixels");
+}
+}  // namespace
+extern "C" {
+
+int p3d_score_sweep_u8(int device, const unsigned char* sal, const unsigned char* fixation, int n, int H, int W, const int* idx,
+                       const int* n_rows, int n_rep, double step, double* per_rep) {
+    API_BEGIN
+    const long long N = (long long)H * W;
+    ScoreSweepArgs q = sweep_args("score_sweep_u8", n, N, n_rep, step);
+    size_t total = 0;
+    const std::vector<long long> meta = sweep_op_check("score_sweep_u8", sal, fixation, n, H, W, idx, n_rows, per_rep, n_rep, total);
+    metric_args(device, sal, fixation, 1, 1, per_rep);
+    const size_t bytes = (size_t)n * (size_t)N;
+    DevArr<unsigned char> ds(bytes, sal), dx(bytes, fixation);
+    DevArr<int> didx(total, total ? idx : nullptr);
+    DevArr<long long> dmeta(meta.size(), meta.data());
+    ScoreArgs a = score_args(n, N, 0, P3D_SCORE_TIES_REFERENCE);
+    a.counter = carve_scratch(nullptr, (size_t)n * 2, [&](Carve& c) {
+        score_carve(c, a);
+        sweep_carve(c, q);
+        q.per_rep = c.take<double>((size_t)n * n_rep);
+    });
+    a.sal = ds.p; a.fix = dx.p;
+    q.sal = ds.p; q.tab = a.tab; q.idx = didx.p; q.meta = dmeta.p;
+    score_sequence(a, nullptr);
+    HIPCHECK(p3d_sweep_launch(SWEEP_PREP, q, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    std::vector<int> info((size_t)n * 4);
+    HIPCHECK(copy_now(info.data(), q.info, info.size() * sizeof(int), hipMemcpyDeviceToHost, nullptr));      // nf, read back once
+    sweep_check_rows("score_sweep_u8", info, n_rows, n);
+    HIPCHECK(p3d_sweep_launch(SWEEP_RUN, q, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    HIPCHECK(copy_now(per_rep, q.per_rep, (size_t)n * n_rep * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    API_END
+}
+
+int p3d_debug_score_sweep_u8(int device, const unsigned char* sal, const unsigned char* fixation, int n, int H, int W, const int* idx,
+                             const int* n_rows, int n_rep, double step, int offset, int* lev_out, int* top_out, double* per_rep) {
+    API_BEGIN
+    const char* who = "debug_score_sweep_u8";
+    const long long N = (long long)H * W;
+    ScoreSweepArgs q = sweep_args(who, n, N, n_rep, step);
+    size_t total = 0;
+    const std::vector<long long> meta = sweep_op_check(who, sal, fixation, n, H, W, idx, n_rows, per_rep, n_rep, total);
+    if (!lev_out || !top_out) throw P3dError("null argument");
+    if (offset < 0 || offset > 15) throw P3dError(std::string(who) + ": offset in [0, 15]");
+    metric_args(device, sal, fixation, 1, 1, per_rep);
+    const size_t bytes = (size_t)n * (size_t)N;
+    ScoreArgs a = score_args(n, N, 0, P3D_SCORE_TIES_REFERENCE);
+    // as p3d_debug_score_u8: guards of 16 elements, the sources shifted off the boundary (no density map here)
+    Guarded<unsigned char> ds(bytes, 16, (size_t)offset, sal), dx(bytes, 16, (size_t)(3 * offset % 16), fixation);
+    Guarded<unsigned> tab((size_t)n * P3D_SCORE_TAB_WORDS, 16, 0, nullptr), counter((size_t)n * 2, 16, 0, nullptr), lad((size_t)n * (q.kmax + 1), 16, 0, nullptr);
+    Guarded<double> lut((size_t)n * 1024, 16, 0, nullptr), part((size_t)n * a.nblk * 2, 16, 0, nullptr), dout((size_t)n * 5, 16, 0, nullptr),
+        dper((size_t)n * n_rep, 16, 0, nullptr);
+    Guarded<int> lev((size_t)n * 256, 16, 0, nullptr), dinfo((size_t)n * 4, 16, 0, nullptr), dtop((size_t)n * n_rep, 16, 0, nullptr),
+        didx(total, 16, 0, total ? idx : nullptr);
+    Guarded<long long> dmeta(meta.size(), 16, 0, meta.data());
+    a.sal = ds.data(); a.fix = dx.data();
+    a.tab = tab.data(); a.counter = counter.data(); a.lut = lut.data(); a.part = part.data(); a.out = dout.data();
+    q.sal = ds.data(); q.tab = tab.data(); q.lev = lev.data(); q.lad = lad.data(); q.info = dinfo.data();
+    q.idx = didx.data(); q.meta = dmeta.data(); q.top = dtop.data(); q.per_rep = dper.data();
+    score_sequence(a, nullptr);
+    HIPCHECK(p3d_sweep_launch(SWEEP_PREP, q, nullptr));
+    std::vector<int> info((size_t)n * 4), levs((size_t)n * 256), tops((size_t)n * n_rep);
+    std::vector<double> per((size_t)n * n_rep);
+    dinfo.back(info.data(), who);
+    sweep_check_rows(who, info, n_rows, n);
+    HIPCHECK(p3d_sweep_launch(SWEEP_RUN, q, nullptr));
+    std::vector<unsigned> zero((size_t)n * 2, 1u);
+    lev.back(levs.data(), who); dtop.back(tops.data(), who); dper.back(per.data(), who);
+    tab.back(nullptr, who); lad.back(nullptr, who); dinfo.back(nullptr, who); dout.back(nullptr, who);
+    counter.back(zero.data(), who);
+    lut.unchanged(who); part.unchanged(who);
+    ds.unchanged(who); dx.unchanged(who); didx.unchanged(who); dmeta.unchanged(who);
+    for (unsigned z : zero) if (z != 0u) throw P3dError(std::string(who) + ": an arrival counter was left at " + std::to_string(z));
+    std::copy(levs.begin(), levs.end(), lev_out);
+    std::copy(tops.begin(), tops.end(), top_out);
+    std::copy(per.begin(), per.end(), per_rep);
+    API_END
+}
+
+int p3d_video_shuffled_begin(p3d_handle* h, int n, const int* ids, int M, uint32_t* n_other_out) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->video_shuffled_begin(ids, n, M, n_other_out);
+    API_END
+}
+
+int p3d_video_score_auc(p3d_handle* h, int first, int n, float scale, int H, int W, const unsigned char* density, const unsigned char* fixation,
+                        int flags, int ties, double* out, const int* borji_idx, const int* ranks, const int* n_rows, int n_rep, double step,
+                        double* borji_per_rep, double* shuffled_per_rep, double* stage_ms) {
+    API_BEGIN
+    const char* who = "video_score_auc";
+    if (!h) throw P3dError("null argument");
+    const bool borji = borji_idx != nullptr, shuf = ranks != nullptr;
+    const int nc = std::max(1, std::min(n, 65535));
+    if (flags != 0) score_check(who, density, fixation, nc, H, W, flags, ties, out);
+    else if (out) throw P3dError(std::string(who) + ": flags = 0 selects no column, so out must be NULL");
+    if (flags == 0 && !borji && !shuf) throw P3dError(std::string(who) + ": nothing is asked for");
+    if (H < 1 || W < 1) throw P3dError(std::string(who) + ": empty map");
+    if ((long long)H * W > P3D_SCORE_MAX_PIXELS) throw P3dError(std::string(who) + ": H * W exceeds 2^23");
+    if ((borji || shuf) && !fixation) throw P3dError(std::string(who) + ": AUC-Borji and shuffled AUC need the fixation maps");
+    if ((borji && !borji_per_rep) || (shuf && (!n_rows || !shuffled_per_rep))) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->video_need_open(who);
+    h->video_range(who, first, n);
+    if (n > 65535) throw P3dError(std::string(who) + ": 1 .. 65535 maps");
+    const bool temporal = h->temporal_cfg.on();
+    if (temporal) h->video_temporal_check(who, first, n);
+    for (int f = first; f < first + n; ++f)
+        if (h->vid_count[(size_t)f] == 0) throw P3dError(std::string(who) + ": frame " + std::to_string(f) + " has no prediction yet (count 0)");
+    const long long phw = h->vid_hw(), N = (long long)H * W;
+    const size_t bytes = (size_t)n * (size_t)N;
+    ScoreArgs a = score_args(n, N, flags, flags ? ties : P3D_SCORE_TIES_REFERENCE);
+    ScoreSweepArgs q, qs;
+    std::vector<int> nf;
+    std::vector<long long> metaB, metaS;
+    std::vector<int> meta3;
+    size_t totB = 0, totS = 0;
+    int max_rows = 0;
+    if (borji || shuf) {
+        q = sweep_args(who, n, N, n_rep, step);
+        nf = host_n_fix(fixation, n, N);
+    }
+    if (borji) {
+        metaB = sweep_meta(who, nf.data(), n, n_rep, totB);
+        check_indices(borji_idx, totB, N, who);
+    }
+    if (shuf) {
+        h->fixpool_need_open(who);
+        if (!h->vu.begun) throw P3dError(std::string(who) + ": no union is held (p3d_video_shuffled_begin)");
+        if (h->fp_H != H || h->fp_W != W)
+            throw P3dError(std::string(who) + ": the fixation pool holds " + std::to_string(h->fp_H) + " x " + std::to_string(h->fp_W) + " maps, the call scores " +
+                           std::to_string(H) + " x " + std::to_string(W));
+        if (h->vu.n != n) throw P3dError(std::string(who) + ": the union was taken for " + std::to_string(h->vu.n) + " frames, the call scores " + std::to_string(n));
+        for (int b = 0; b < n; ++b)
+            if (n_rows[b] != (int)std::min<long long>(nf[(size_t)b], h->vu.n_other[(size_t)b]))
+                throw P3dError(std::string(who) + ": frame " + std::to_string(b) + ": n_rows = " + std::to_string(n_rows[b]) + ", but min(n_fix, n_other) = min(" +
+                               std::to_string(nf[(size_t)b]) + ", " + std::to_string(h->vu.n_other[(size_t)b]) + ")");
+        p3d_handle::shuffled_check_draws(who, ranks, n_rows, h->vu.n_other.data(), n, n_rep, step);
+        metaS = sweep_meta(who, n_rows, n, n_rep, totS);
+        meta3.assign((size_t)n * 3, 0);
+        for (int b = 0; b < n; ++b) { meta3[(size_t)b * 3 + 2] = (int)metaS[(size_t)b * 2 + 1]; max_rows = std::max(max_rows, n_rows[b]); }
+    }
+    if (stage_ms) stage_ms[0] = stage_ms[1] = stage_ms[2] = stage_ms[3] = 0.0;
+    unsigned char* dd = nullptr; unsigned char* dx = nullptr;
+    int* didx = nullptr; int* dranks = nullptr; int* dsel = nullptr; int* dmeta3 = nullptr; int* drows = nullptr;
+    long long* dmetaB = nullptr; long long* dmetaS = nullptr;
+    double* perB = nullptr; double* perS = nullptr;
+    std::vector<int> info((size_t)n * 4, 0);
+    double ms3[3] = {0.0, 0.0, 0.0};
+    StageTimer sweeps(stage_ms != nullptr, 2);
+    U8Consumer use;
+    use.counters = (size_t)n * 2;
+    use.ms = stage_ms ? ms3 : nullptr;
+    use.carve = [&](Carve& c) {
+        dd = density && flags ? c.take<unsigned char>(bytes) : nullptr;
+        dx = fixation ? c.take<unsigned char>(bytes) : nullptr;
+        score_carve(c, a);
+        if (!borji && !shuf) return;
+        sweep_carve(c, q);
+        if (borji) { didx = c.take<int>(totB); dmetaB = c.take<long long>(metaB.size()); perB = c.take<double>((size_t)n * n_rep); }
+        if (shuf) {
+            dranks = c.take<int>(totS); dsel = c.take<int>(totS); dmeta3 = c.take<int>(meta3.size()); drows = c.take<int>((size_t)n);
+            dmetaS = c.take<long long>(metaS.size()); perS = c.take<double>((size_t)n * n_rep);
+        }
+    };
+    use.before = [&](hipStream_t s) {
+        if (dd) HIPCHECK(hipMemcpyAsync(dd, density, bytes, hipMemcpyHostToDevice, s));
+        if (dx) HIPCHECK(hipMemcpyAsync(dx, fixation, bytes, hipMemcpyHostToDevice, s));
+        if (borji) {
+            if (totB) HIPCHECK(hipMemcpyAsync(didx, borji_idx, totB * sizeof(int), hipMemcpyHostToDevice, s));
+            HIPCHECK(hipMemcpyAsync(dmetaB, metaB.data(), metaB.size() * sizeof(long long), hipMemcpyHostToDevice, s));
+        }
+        if (shuf) {
+            if (totS) HIPCHECK(hipMemcpyAsync(dranks, ranks, totS * sizeof(int), hipMemcpyHostToDevice, s));
+            HIPCHECK(hipMemcpyAsync(dmeta3, meta3.data(), meta3.size() * sizeof(int), hipMemcpyHostToDevice, s));
+            HIPCHECK(hipMemcpyAsync(drows, n_rows, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+            HIPCHECK(hipMemcpyAsync(dmetaS, metaS.data(), metaS.size() * sizeof(long long), hipMemcpyHostToDevice, s));
+        }
+    };
+    use.after = [&](hipStream_t s, const unsigned char* d, unsigned* counters) {
+        a.sal = d; a.den = dd; a.fix = dx; a.counter = counters;
+        score_sequence(a, s);                                 // pass A once, for the columns and for the sweeps
+        sweeps.mark(0, s);
+        if (borji || shuf) {
+            q.sal = d; q.tab = a.tab;
+            HIPCHECK(p3d_sweep_launch(SWEEP_PREP, q, s));
+        }
+        if (borji) {
+            q.idx = didx; q.meta = dmetaB; q.per_rep = perB;
+            HIPCHECK(p3d_sweep_launch(SWEEP_RUN, q, s));
+        }
+        if (shuf) {
+            if (totS) {
+                FixSelectArgs e;
+                e.uni = h->vu.uni; e.prefix = h->vu.prefix; e.bsum = h->vu.bsum; e.n_other = h->vu.n_other_dev; e.nw = h->fp_nw; e.B = n;
+                e.nsb = p3d_fix_scan_blocks(h->fp_nw); e.n_rep = n_rep; e.max_rows = max_rows; e.meta = dmeta3; e.n_rows = drows; e.ranks = dranks; e.out = dsel;
+                HIPCHECK(p3d_fix_select_launch(e, s));
+            }
+            qs = q;
+            qs.idx = dsel; qs.meta = dmetaS; qs.per_rep = perS;
+            HIPCHECK(p3d_sweep_launch(SWEEP_RUN, qs, s));
+        }
+        sweeps.mark(1, s);
+    };
+    use.results = [&](hipStream_t s) {
+        if (flags) HIPCHECK(hipMemcpyAsync(out, a.out, (size_t)n * 5 * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (borji) HIPCHECK(hipMemcpyAsync(borji_per_rep, perB, (size_t)n * n_rep * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (shuf) HIPCHECK(hipMemcpyAsync(shuffled_per_rep, perS, (size_t)n * n_rep * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (borji || shuf) HIPCHECK(hipMemcpyAsync(info.data(), q.info, info.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+    };
+    maps_u8_chain(h, n, h->pred->H, h->pred->W, scale, H, W, nullptr, nullptr, temporal || h->vid_mode == VIDEO_MEAN ? (size_t)n * (size_t)phw : 0,
+                  [&](hipStream_t s, float* scratch, std::vector<PostRun>& runs) {
+                      runs.push_back({temporal ? h->video_temporal(who, first, n, scratch, s) : h->video_finalize(who, first, n, scratch, s), phw, 1, n});
+                  }, &use);
+    if (stage_ms) {
+        stage_ms[3] = (double)sweeps.ms(0);
+        stage_ms[0] = ms3[0]; stage_ms[1] = ms3[1]; stage_ms[2] = std::max(0.0, ms3[2] - stage_ms[3]);
+    }
+    for (int b = 0; (borji || shuf) && b < n; ++b)
+        if (info[(size_t)b * 4] != nf[(size_t)b])
+            throw P3dError(std::string(who) + ": frame " + std::to_string(b) + ": the device counted " + std::to_string(info[(size_t)b * 4]) + " fixated pixels, the host " +
+                           std::to_string(nf[(size_t)b]));
+    API_END
+}
+
 // The three launches of video.hip from their launch descriptions, on host arrays.  Every device buffer sits `offset` elements past
 // a 16-byte boundary between guard elements; a guard or an input that a launch changed is an error.
 }  // extern "C"

@@ -858,6 +858,7 @@
         fp_words = nullptr; fp_staging = nullptr; fp_staging_bytes = 0; fp_filled.clear();
         fp_is_open = false; fp_H = fp_W = 0; fp_cap = fp_nw = 0;
         shuffled_free();
+        vu.release();
     }
     void fixpool_open(int H, int W, int64_t capacity) {
         if (H < 1 || W < 1 || (long long)H * W > INT32_MAX / 2) throw P3dError("fixpool: maps are H x W bytes, 1 <= H * W <= 2^30");
@@ -974,6 +975,48 @@
         sh_ranks.assign(ranks, ranks + n);
         sh_n_rows.assign(n_rows, n_rows + B);
         sh_n_rep = n_rep; sh_step = step; sh_armed = true;
+    }
+    // the union p3d_video_shuffled_begin holds for p3d_video_score_auc: n frames' rows of pool slots, in buffers of its own -- the
+    // evaluation pass's union above, armed or not, is neither read nor written.  Freed with the pool.
+    struct VideoUnion {
+        int B = 0, M = 0, n = 0; size_t room = 0; bool begun = false;
+        unsigned long long* uni = nullptr; unsigned* prefix = nullptr; unsigned* bsum = nullptr; unsigned* n_other_dev = nullptr;
+        unsigned* counter = nullptr; int* ids = nullptr;
+        std::vector<unsigned> n_other;
+        void release() {
+            for (void* p : {(void*)uni, (void*)prefix, (void*)bsum, (void*)n_other_dev, (void*)counter, (void*)ids}) if (p) hipFree(p);
+            *this = VideoUnion();
+        }
+    } vu;
+    void video_shuffled_begin(const int* ids, int n, int M, uint32_t* n_other_out) {
+        if (!n_other_out) throw P3dError("null argument");
+        if (n < 1 || n > 65535) throw P3dError("video_shuffled_begin: 1 .. 65535 frames");
+        fixpool_check_ids("video_shuffled_begin", ids, n, M);
+        vu.begun = false;
+        const int nsb = p3d_fix_scan_blocks(fp_nw);
+        const size_t room = (size_t)n * fp_nw;
+        if (room > vu.room || n > vu.B || M > vu.M) {
+            const int nB = std::max(n, vu.B), nM = std::max(M, vu.M);
+            const size_t nroom = std::max(room, vu.room);
+            vu.release();
+            HIPCHECK(hipMalloc((void**)&vu.uni, nroom * sizeof(unsigned long long)));
+            HIPCHECK(hipMalloc((void**)&vu.prefix, nroom * sizeof(unsigned)));
+            HIPCHECK(hipMalloc((void**)&vu.bsum, (size_t)nB * nsb * sizeof(unsigned)));
+            HIPCHECK(hipMalloc((void**)&vu.n_other_dev, (size_t)nB * sizeof(unsigned)));
+            HIPCHECK(hipMalloc((void**)&vu.counter, (size_t)nB * sizeof(unsigned)));
+            HIPCHECK(hipMalloc((void**)&vu.ids, (size_t)nB * nM * sizeof(int)));
+            HIPCHECK(fill_now(vu.counter, 0, (size_t)nB * sizeof(unsigned), stream));
+            vu.room = nroom; vu.B = nB; vu.M = nM;
+        }
+        HIPCHECK(copy_now(vu.ids, ids, (size_t)n * M * sizeof(int), hipMemcpyHostToDevice, stream));
+        FixUnionArgs a;
+        a.pool = fp_words; a.nw = fp_nw; a.ids = vu.ids; a.B = n; a.M = M; a.nsb = nsb;
+        a.uni = vu.uni; a.prefix = vu.prefix; a.bsum = vu.bsum; a.n_other = vu.n_other_dev; a.counter = vu.counter;
+        HIPCHECK(p3d_fix_union_launch(a, stream));
+        vu.n_other.assign((size_t)n, 0u);
+        HIPCHECK(copy_now(vu.n_other.data(), vu.n_other_dev, (size_t)n * sizeof(unsigned), hipMemcpyDeviceToHost, stream));      // the one synchronisation
+        std::copy(vu.n_other.begin(), vu.n_other.end(), n_other_out);
+        vu.n = n; vu.begun = true;
     }
 
     // ---- resident video inference (p3d_video_*; video.hip) ---------------------------------------------

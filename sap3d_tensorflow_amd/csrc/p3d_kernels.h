@@ -1006,7 +1006,8 @@ LaunchDesc p3d_fix_select_desc(const FixSelectArgs& a);
 hipError_t p3d_fix_select_launch(const FixSelectArgs& a, hipStream_t s);
 
 // ---- scoring 8-bit maps against 8-bit ground truth (score_u8.hip; p3d_video_score / p3d_score_maps_u8, the law in include/p3d_hip.h) ----
-// One launch sequence on n maps of n_pix bytes, 1 <= n_pix <= 2^23, sal / den / fix [n][n_pix] (fix may be null: nothing is fixated):
+// One launch sequence on n maps of n_pix bytes, 1 <= n_pix <= 2^23, sal / den / fix [n][n_pix] (fix may be null: nothing is fixated;
+// den may be null when none of CC, SIM and KL is selected: pass A then counts neither hd nor the products, and reads no density):
 //   SCORE_COUNT  tab[n][P3D_SCORE_TAB_WORDS] zeroed in stream order, then score_count_kernel: hs[256], hf[256], hd[256] and the
 //                64-bit sum of s * d of every map; the last arriving block of a map (counter[m]) writes out[m][0 .. 5) -- CC, NaN,
 //                AUC_Judd, NaN, NSS, an unselected column NaN -- and, with SIM or KL selected, lut[m][4][256]: us, ud, ps, pd;
@@ -1046,6 +1047,36 @@ long long p3d_score_lane_products(long long n_pix, int n, unsigned off_s, unsign
 bool p3d_score_has(int stage, const ScoreArgs& a);
 LaunchDesc p3d_score_desc(int stage, const ScoreArgs& a);
 hipError_t p3d_score_launch(int stage, const ScoreArgs& a, hipStream_t s);      // a stage the arguments do not ask for: nothing, success
+
+// ---- AUC-Borji and shuffled AUC of 8-bit maps (score_auc_u8.hip; p3d_score_sweep_u8 / p3d_video_score_auc, the law in
+// include/p3d_hip.h, SPLIT SWEEP) ----
+//   SWEEP_PREP  per map, from pass A's tables tab (SCORE_COUNT, earlier in the stream): lev[n][256], the fixation ladder
+//               lad[n][kmax + 1] (lad[l] = sum of hf[v] over lev[v] >= l) and info[n][4] = {nf, lo, hi, maxfix} (-1: none);
+//   SWEEP_RUN   per (split, map): map m's n_rows = meta[m][0] rows of n_rep pixel indices start at idx[meta[m][1]]; the bytes
+//               sal[m][idx] are gathered and counted per level, per_rep[m][split] is the area (NaN: nf = 0 or a flat map) and,
+//               where top is not null, top[m][split] the split's largest byte or maxfix.  One prep serves any number of runs.
+// Refused (hipErrorInvalidValue): a missing buffer, n outside [1, 65535], n_pix outside the range, kmax other than
+// p3d_sweep_kmax(step) or 0, n_rep < 1, cols other than p3d_sweep_cols'.  Indices outside [0, n_pix) are the caller's to refuse.
+constexpr int P3D_SWEEP_MAX_KMAX = 1024;
+enum { SWEEP_PREP = 0, SWEEP_RUN = 1, SWEEP_STAGES = 2 };
+struct ScoreSweepArgs {
+    const unsigned char* sal = nullptr;       // [n][n_pix]
+    const unsigned* tab = nullptr;            // [n][P3D_SCORE_TAB_WORDS], pass A's
+    int n = 0, n_pix = 0, kmax = 0, n_rep = 0, cols = 0;
+    double step = 0.0;
+    int* lev = nullptr;                       // [n][256]
+    unsigned* lad = nullptr;                  // [n][kmax + 1]
+    int* info = nullptr;                      // [n][4]
+    const int* idx = nullptr;
+    const long long* meta = nullptr;          // [n][2]
+    int* top = nullptr;                       // [n][n_rep], or null
+    double* per_rep = nullptr;                // [n][n_rep]
+};
+int p3d_sweep_kmax(double step);              // (int)ceil(1 / step); 0: not positive, or more than P3D_SWEEP_MAX_KMAX thresholds
+// split columns of a block: a power of two <= 32 whose histograms (kmax + 1 counters a split) fit 48 KB, no wider than n_rep needs
+int p3d_sweep_cols(int kmax, int n_rep);
+LaunchDesc p3d_sweep_desc(int stage, const ScoreSweepArgs& a);
+hipError_t p3d_sweep_launch(int stage, const ScoreSweepArgs& a, hipStream_t s);
 
 // ---- misc ---------------------------------------------------------------------------------------
 hipError_t p3d_add_inplace(float* dst, int lddst, const float* src, int ldsrc, long M, int C, hipStream_t s);

@@ -11,7 +11,8 @@
 //    few and add 1 each.  The products s * d are added per lane in 32 bits: a lane adds at most
 //    2 + 16 * ceil(chunk / 16 / 256) <= 130 products of at most 255 * 255 (chunk <= 2^23 / 256 = 32768 rounded up to 16; the plan
 //    hook reports the exact figure), far below the 66 051 that fit -- the trips are bounded, nothing is added in 64 bits before the
-//    wave's fold.  The copies are folded and flushed with integer atomics to the map's table (zeroed by the launcher in stream
+//    wave's fold.  Without a density map (no column that needs one: the sweeps of score_auc_u8.hip alone) the kernel's other
+//    instantiation counts neither hd nor the products and reads two sources.  The copies are folded and flushed with integer atomics to the map's table (zeroed by the launcher in stream
 //    order), the waves' 64-bit product sums likewise.
 //    The last arriving block of a map (det_reduce.h's ticket) runs FINALISE on the tables alone, thread t on level v = 255 - t:
 //    the moments are integer block sums, the two running sums of AUC-Judd are integer scans, CC / NSS / the REFERENCE-ties AUC are
@@ -52,23 +53,25 @@ __device__ __forceinline__ void count_bin(unsigned* cnt, int b, int lane) {
     if (b >= 0) atomicAdd(&cnt[b], 1u);
 }
 
-// one pixel per lane (on: this lane holds one); -> its product
+// one pixel per lane (on: this lane holds one); -> its product.  DEN false: no density map, hd and the products are not counted
+template <bool DEN>
 __device__ __forceinline__ unsigned count_pixel(unsigned* cnt, bool on, unsigned s, unsigned d, unsigned x, int lane) {
     count_bin(cnt, on ? (int)s : -1, lane);
-    count_bin(cnt + 512, on ? (int)d : -1, lane);
+    if (DEN) count_bin(cnt + 512, on ? (int)d : -1, lane);
     if (on && x >= 128u) atomicAdd(&cnt[256 + s], 1u);
-    return on ? s * d : 0u;
+    return DEN && on ? s * d : 0u;
 }
 
 // pixels [lo, hi) of the block by byte loads, a wave-uniform trip count (the ballots need every lane)
+template <bool DEN>
 __device__ __forceinline__ unsigned count_range(unsigned* cnt, const unsigned char* ps, const unsigned char* pd, const unsigned char* px,
                                                 int lo, int hi, int tid) {
     unsigned acc = 0u;
     for (int at = lo; at < hi; at += TPB) {
         const int i = at + tid;
         const bool on = i < hi;
-        const unsigned s = on ? ps[i] : 0u, d = on ? pd[i] : 0u, x = on && px ? px[i] : 0u;
-        acc += count_pixel(cnt, on, s, d, x, tid & 63);
+        const unsigned s = on ? ps[i] : 0u, d = DEN && on ? pd[i] : 0u, x = on && px ? px[i] : 0u;
+        acc += count_pixel<DEN>(cnt, on, s, d, x, tid & 63);
     }
     return acc;
 }
@@ -178,6 +181,7 @@ __device__ void score_finalise(const ScoreArgs& a, int m, unsigned* th, double* 
     lut[768 + v] = D1 ? (double)v / (double)D1 : 0.0;
 }
 
+template <bool DEN>
 __global__ __launch_bounds__(TPB) void score_count_kernel(ScoreArgs a) {
     __shared__ unsigned cnt[WAVES * TAB];
     __shared__ double uu[512];
@@ -188,11 +192,11 @@ __global__ __launch_bounds__(TPB) void score_count_kernel(ScoreArgs a) {
     const int i0 = (int)min((long long)blockIdx.x * a.chunk, (long long)a.n_pix), i1 = (int)min((long long)i0 + a.chunk, (long long)a.n_pix);
     const int len = i1 - i0;
     const unsigned char* ps = a.sal + (size_t)m * a.n_pix + i0;
-    const unsigned char* pd = a.den + (size_t)m * a.n_pix + i0;
+    const unsigned char* pd = DEN ? a.den + (size_t)m * a.n_pix + i0 : ps;
     const unsigned char* px = a.fix ? a.fix + (size_t)m * a.n_pix + i0 : nullptr;
     unsigned* mine = cnt + (tid >> 6) * TAB;
     const ScoreCut cut = p3d_score_cut((uintptr_t)ps, (uintptr_t)pd, px ? (uintptr_t)px : (uintptr_t)ps, len);      // block-uniform
-    unsigned acc = count_range(mine, ps, pd, px, 0, cut.head, tid);
+    unsigned acc = count_range<DEN>(mine, ps, pd, px, 0, cut.head, tid);
     const uint4* s4 = reinterpret_cast<const uint4*>(ps + cut.head);
     const uint4* d4 = reinterpret_cast<const uint4*>(pd + cut.head);
     const uint4* x4 = reinterpret_cast<const uint4*>(px ? px + cut.head : ps + cut.head);
@@ -200,11 +204,11 @@ __global__ __launch_bounds__(TPB) void score_count_kernel(ScoreArgs a) {
         const int q = at + tid;
         const bool on = q < cut.words;
         uint4 vs = {0u, 0u, 0u, 0u}, vd = vs, vx = vs;
-        if (on) { vs = s4[q]; vd = d4[q]; if (px) vx = x4[q]; }
+        if (on) { vs = s4[q]; if (DEN) vd = d4[q]; if (px) vx = x4[q]; }
 #pragma unroll
-        for (int j = 0; j < 16; ++j) acc += count_pixel(mine, on, byte_of(vs, j), byte_of(vd, j), byte_of(vx, j), lane);
+        for (int j = 0; j < 16; ++j) acc += count_pixel<DEN>(mine, on, byte_of(vs, j), byte_of(vd, j), byte_of(vx, j), lane);
     }
-    acc += count_range(mine, ps, pd, px, cut.head + cut.words * 16, len, tid);
+    acc += count_range<DEN>(mine, ps, pd, px, cut.head + cut.words * 16, len, tid);
     __syncthreads();
     unsigned* table = a.tab + (size_t)m * P3D_SCORE_TAB_WORDS;
     for (int k = tid; k < TAB; k += TPB) {
@@ -258,8 +262,9 @@ __global__ __launch_bounds__(TPB) void score_terms_kernel(ScoreArgs a) {
 }
 
 bool args_ok(const ScoreArgs& a) {
-    if (a.n < 1 || a.n > 65535 || a.n_pix < 1 || a.n_pix > P3D_SCORE_MAX_PIXELS || !a.sal || !a.den) return false;
+    if (a.n < 1 || a.n > 65535 || a.n_pix < 1 || a.n_pix > P3D_SCORE_MAX_PIXELS || !a.sal) return false;
     if (a.flags < 0 || (a.flags & ~P3D_SCORE_ALL)) return false;
+    if (!a.den && (a.flags & (P3D_SCORE_CC | P3D_SCORE_SIM | P3D_SCORE_KL))) return false;
     if (a.ties != P3D_SCORE_TIES_REFERENCE && a.ties != P3D_SCORE_TIES_EXPECTED) return false;
     if (!a.fix && (a.flags & (P3D_SCORE_JUDD | P3D_SCORE_NSS))) return false;
     const ScorePlan p = p3d_score_plan(a.n_pix);
@@ -303,7 +308,7 @@ bool p3d_score_has(int stage, const ScoreArgs& a) {
 
 LaunchDesc p3d_score_desc(int stage, const ScoreArgs& a) {
     const double e = (double)a.n * (double)a.n_pix;
-    if (stage == SCORE_COUNT) return {"score_count_kernel", e * 2.0, e * (a.fix ? 3.0 : 2.0)};      // one read of every source
+    if (stage == SCORE_COUNT) return {"score_count_kernel", e * 2.0, e * ((a.fix ? 2.0 : 1.0) + (a.den ? 1.0 : 0.0))};      // one read of every source
     return {"score_terms_kernel", e * 8.0, e * 2.0};
 }
 
@@ -313,7 +318,8 @@ hipError_t p3d_score_launch(int stage, const ScoreArgs& a, hipStream_t s) {
     if (stage == SCORE_COUNT) {
         const hipError_t e = hipMemsetAsync(a.tab, 0, (size_t)a.n * P3D_SCORE_TAB_WORDS * sizeof(unsigned), s);      // the tables start at zero, in stream order
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(score_count_kernel, dim3(a.nblk, a.n), dim3(TPB), 0, s, a);
+        if (a.den) hipLaunchKernelGGL(score_count_kernel<true>, dim3(a.nblk, a.n), dim3(TPB), 0, s, a);
+        else hipLaunchKernelGGL(score_count_kernel<false>, dim3(a.nblk, a.n), dim3(TPB), 0, s, a);
     } else {
         hipLaunchKernelGGL(score_terms_kernel, dim3(a.nblk, a.n), dim3(TPB), 0, s, a);
     }

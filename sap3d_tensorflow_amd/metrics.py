@@ -384,3 +384,57 @@ def score_bytes(sal, density, fixation, flags=("cc", "sim", "judd", "kl", "nss")
     check(lib().p3d_debug_score_u8(*args, int(offset), t["hs"].ctypes.data_as(u32), t["hf"].ctypes.data_as(u32), t["hd"].ctypes.data_as(u32),
                                    t["sd"].ctypes.data_as(C.POINTER(C.c_uint64)), _dp(out)))
     return out, t
+
+
+def borji_draws_u8(fixation, n_rep, rng=None):
+    """AUC-Borji's draws for byte maps (the draw order of eval_draws without the jitter): fixation uint8 [n, H, W] or [H, W],
+    fixated where the byte is >= 128; per map in map order, nothing for a map without fixation, else
+    randint(0, H * W, [nf, n_rep]) (utils/metrics.py:139).  -> (idx int32, the maps' rows concatenated; nf int32 [n])."""
+    src = rng if rng is not None else np.random
+    f = np.asarray(fixation)
+    f = f[None] if f.ndim == 2 else f
+    nf = np.count_nonzero(f.reshape(f.shape[0], -1) >= 128, axis=1).astype(np.int32)
+    n_pix = int(f.shape[1]) * int(f.shape[2])
+    idx = [src.randint(0, n_pix, [int(k), int(n_rep)]).astype(np.int32).ravel() for k in nf if k]
+    return np.ascontiguousarray(np.concatenate(idx) if idx else np.zeros(0, np.int32)), nf
+
+
+def score_sweep(sal, fixation, idx, n_rows, step_size=0.1, device=0, with_tables=False, offset=0, n_rep=None):
+    """AUC-Borji / shuffled AUC of 8-bit maps from supplied sample locations (include/p3d_hip.h, SPLIT SWEEP; p3d_score_sweep_u8):
+    sal, fixation uint8 [n, H, W] or [H, W]; idx int32, map b's [n_rows[b], n_rep] pixel indices row-major, the maps concatenated;
+    n_rows int [n], each at most the map's number of fixated pixels; n_rep: the splits, by default idx.size / sum(n_rows).  -> the per-split areas float64 [n, n_rep] (the score is
+    np.mean over a row; NaN rows: no fixation, or a flat map).  with_tables (the test hook p3d_debug_score_sweep_u8, sources
+    `offset` bytes past a 16-byte boundary): also dict(lev int32 [n, 256], top int32 [n, n_rep])."""
+    s = np.ascontiguousarray(sal)
+    x = np.ascontiguousarray(fixation)
+    if s.dtype != np.uint8 or x.dtype != np.uint8 or s.shape != x.shape:
+        raise ValueError("saliency and fixation maps are uint8 arrays of one shape")
+    if s.ndim not in (2, 3) or s.size == 0:
+        raise ValueError("expected non-empty [H, W] or [n, H, W] maps")
+    n = s.shape[0] if s.ndim == 3 else 1
+    H, W = s.shape[-2:]
+    rows = np.ascontiguousarray(n_rows, dtype=np.int32).ravel()
+    if rows.size != n:
+        raise ValueError("one row count per map")
+    r = np.ascontiguousarray(idx, dtype=np.int32).ravel()
+    total = int(rows.astype(np.int64).sum())
+    if n_rep is None:            # from idx: sum(n_rows) * n_rep indices; with no row at all, idx of shape [0, n_rep] still says it
+        if total > 0 and r.size and r.size % total == 0:
+            n_rep = r.size // total
+        elif total == 0 and np.ndim(idx) == 2:
+            n_rep = int(np.shape(idx)[1])
+        else:
+            raise ValueError("idx holds sum(n_rows) * n_rep indices")
+    n_rep = int(n_rep)
+    if r.size != total * n_rep:
+        raise ValueError("idx holds sum(n_rows) * n_rep = %d indices, not %d" % (total * n_rep, r.size))
+    ip, u8 = C.POINTER(C.c_int), C.POINTER(C.c_ubyte)
+    out = np.empty((n, n_rep), np.float64)
+    args = (device, s.ctypes.data_as(u8), x.ctypes.data_as(u8), n, int(H), int(W), r.ctypes.data_as(ip) if total else None,
+            rows.ctypes.data_as(ip), n_rep, float(step_size))
+    if not with_tables:
+        check(lib().p3d_score_sweep_u8(*args, _dp(out)))
+        return out
+    t = dict(lev=np.empty((n, 256), np.int32), top=np.empty((n, n_rep), np.int32))
+    check(lib().p3d_debug_score_sweep_u8(*args, int(offset), t["lev"].ctypes.data_as(ip), t["top"].ctypes.data_as(ip), _dp(out)))
+    return out, t

@@ -927,6 +927,58 @@ class P3DSession:
         self.last_score_ms = dict(upload=ms[0], device=ms[1], score=ms[2])
         return (out, maps) if with_maps else out
 
+    def video_shuffled_begin(self, ids):
+        """The union of the fixation pool's maps ids[b] (int [n, M], 1 <= M <= 64) for each of n frames that video_score_auc will
+        score, counted and scanned on the device -> n_other uint32 [n].  Held apart from shuffled_begin's union: an armed
+        evaluate(shuffled=...) is not disturbed."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        if ids.ndim != 2:
+            raise ValueError("ids is int [n, M]")
+        n_other = np.empty(ids.shape[0], np.uint32)
+        check(lib().p3d_video_shuffled_begin(self._h, ids.shape[0], ids.ctypes.data_as(_lib._ip), ids.shape[1],
+                                             n_other.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return n_other
+
+    def video_score_auc(self, first, n, density, fixation, size=(1080, 960), scale=255., columns=("cc", "sim", "judd"), ties="expected",
+                        borji_idx=None, shuffled_ranks=None, n_rows=None, n_rep=100, step_size=0.1):
+        """video_score with AUC-Borji and shuffled AUC of the same bytes (include/p3d_hip.h, SPLIT SWEEP): one maps chain, one
+        pass A, then everything asked for.  columns: as video_score, or () / None for none of the five (density may then be None).
+        borji_idx: every frame's randint(0, H * W, [nf, n_rep]) indices, concatenated (metrics.borji_draws_u8).  shuffled_ranks,
+        n_rows: metrics.shuffled_draws' ranks into the union video_shuffled_begin holds for these n frames.
+        -> dict(scores float64 [n, 5], borji [n, n_rep], shuffled [n, n_rep]; NaN where not asked).  Device times are left in
+        `last_score_ms`: upload, device (the maps' chain), score (the five columns), auc (preparation, select and sweeps)."""
+        from . import metrics
+        H, W = (size, size) if np.isscalar(size) else tuple(size)
+        n = max(int(n), 0)
+        valid = H >= 1 and W >= 1 and H * W <= 2 ** 23
+        flags = metrics.score_flags(columns if columns is not None else ())
+        dens = None if density is None else np.ascontiguousarray(density)
+        fix = None if fixation is None else np.ascontiguousarray(fixation)
+        for a in (dens, fix):
+            if a is not None and (a.dtype != np.uint8 or (valid and a.shape != (n, H, W))):
+                raise ValueError("density and fixation maps are uint8 [%d, %d, %d]" % (n, H, W))
+        n_rep = int(n_rep)
+        res = dict(scores=np.full((n, 5), np.nan, np.float64), borji=np.full((n, max(n_rep, 0)), np.nan, np.float64),
+                   shuffled=np.full((n, max(n_rep, 0)), np.nan, np.float64))
+
+        def ints(a):        # (a one-element array where there is nothing: NULL means "not asked")
+            a = np.ascontiguousarray(a, dtype=np.int32).ravel()
+            return a if a.size else np.zeros(1, np.int32)
+        bi = None if borji_idx is None else ints(borji_idx)
+        rk = None if shuffled_ranks is None else ints(shuffled_ranks)
+        nr = None if n_rows is None else np.ascontiguousarray(n_rows, dtype=np.int32).ravel()
+        if rk is not None and (nr is None or nr.size != n):
+            raise ValueError("n_rows is int [%d], the rows of shuffled_ranks per frame" % n)
+        ptr = lambda a, t: None if a is None else a.ctypes.data_as(t)
+        ms = (C.c_double * 4)()
+        check(lib().p3d_video_score_auc(self._h, int(first), n, float(scale), int(H), int(W), ptr(dens, _lib._u8p), ptr(fix, _lib._u8p), flags,
+                                        metrics.score_ties(ties), ptr(res["scores"], _lib._dp) if flags else None, ptr(bi, _lib._ip),
+                                        ptr(rk, _lib._ip), ptr(nr, _lib._ip), n_rep, float(step_size),
+                                        ptr(res["borji"], _lib._dp) if bi is not None else None,
+                                        ptr(res["shuffled"], _lib._dp) if rk is not None else None, ms))
+        self.last_score_ms = dict(upload=ms[0], device=ms[1], score=ms[2], auc=ms[3])
+        return res
+
     # ---- resident training set (p3d_trainset_*) -------------------------------------------------------------
     def open_trainset(self, frames_per_video, frame_format="u8", fixations=False, mean_rgb=(90., 102., 98.)):
         """Keep a training set on the device (an addition: the reference's loader, dataflow.py:39-62, cuts overlapping clips on
