@@ -114,6 +114,14 @@ def predict_video_resident(sess, video_u8, batch, stride=1, overlap="newest", ti
     return F
 
 
+def hand_over(pool, held, write, first, maps):
+    """Waits for the images in flight (`held`: the previous chunk's, encoded while this one ran on the device), then submits
+    write(frame, map) for this chunk's maps, frames first, first + 1, ... -> the futures now in flight."""
+    for fut in held:
+        fut.result()
+    return [pool.submit(write, first + k, m) for k, m in enumerate(maps)]
+
+
 def write_video_images_resident(sess, F, video_dir, ext, size=(1080, 960), writers=4):
     """write_video_images for the open video: its maps leave the device 16 at a time (video_maps_u8) while the previous 16 are
     encoded.  Returns the same dict; gpu is the wall time of the map stages alone."""
@@ -137,12 +145,9 @@ def write_video_images_resident(sess, F, video_dir, ext, size=(1080, 960), write
             t["gpu"] += (time.perf_counter() - t0) * 1e3
             t["device"] += sess.last_maps_ms["device"]
             t["d2h"] += sess.last_maps_ms["d2h"]
-            for fut in held:
-                fut.result()
-            held = [pool.submit(write, first + k, m) for k, m in enumerate(maps)]
+            held = hand_over(pool, held, write, first, maps)
             t["files"] += n
-        for fut in held:
-            fut.result()
+        hand_over(pool, held, write, F, ())
     return t
 
 
@@ -174,34 +179,6 @@ def format_means(means):
     return ", ".join("%s=%r" % (k, float(v)) for k, v in zip(SCORE_NAMES, means))
 
 
-def score_video_resident(sess, F, density, fixation, size, columns, ties, video_dir=None, ext=None, writers=4):
-    """Scores the open video against its ground truth on the device (P3DSession.video_score), SCORE_CHUNK frames a call ->
-    (scores float64 [F, 5], times).  The 8-bit maps stay on the device unless video_dir asks for the images: then each call also
-    returns its bytes and they are encoded as write_video_images_resident encodes them, while the next call runs."""
-    from concurrent.futures import ThreadPoolExecutor
-    scores = np.full((F, len(SCORE_NAMES)), np.nan, np.float64)
-    t = dict(upload=0.0, device=0.0, score=0.0, files=0)
-    held = []
-    with ThreadPoolExecutor(max_workers=writers) as pool:
-        for first in range(0, F, SCORE_CHUNK):
-            n = min(SCORE_CHUNK, F - first)
-            got = sess.video_score(first, n, density[first:first + n], fixation[first:first + n], size=size, columns=columns, ties=ties,
-                                   with_maps=video_dir is not None)
-            for k in ("upload", "device", "score"):
-                t[k] += sess.last_score_ms[k]
-            if video_dir is not None:
-                got, maps = got
-                for fut in held:
-                    fut.result()
-                held = [pool.submit(save_image, os.path.join(video_dir, "frame_%d.%s" % (first + k + 1, ext)), m, ext)
-                        for k, m in enumerate(maps)]
-                t["files"] += n
-            scores[first:first + n] = got
-        for fut in held:
-            fut.result()
-    return scores, t
-
-
 def sauc_ids(rng, P, c0, c1, M, own):
     """The pool slots whose union frames c0 .. c1 - 1 sample shuffled AUC's locations from, int32 [c1 - c0, M], drawn row by row in
     frame order (repeats allowed).  own: the pool is the video's own P fixation maps, slot = frame, and a frame never draws itself:
@@ -216,51 +193,58 @@ def sauc_ids(rng, P, c0, c1, M, own):
     return ids
 
 
-def score_video_resident_auc(sess, F, density, fixation, size, columns, ties, borji, sauc, pool_size, own_pool, n_rep, step, seed,
-                             video_dir=None, ext=None, writers=4):
-    """score_video_resident with AUC-Borji and / or shuffled AUC of the same bytes (P3DSession.video_score_auc; --score-borji,
-    --score-sauc M) -> (scores [F, 5], auc float64 [F, 2]: the Borji and shuffled means per frame, NaN where not asked; times).
-    One RandomState(seed) per video; per chunk of SCORE_CHUNK frames it draws, in this order: the rows of pool slots in frame order
-    (sauc_ids), [video_shuffled_begin], Borji's randint per frame with fixations (metrics.borji_draws_u8), metrics.shuffled_draws.
-    With video_dir the images come from video_maps_u8, one more run of the maps' chain per chunk."""
+def score_video_resident(sess, F, density, fixation, size, columns, ties, auc=None, video_dir=None, ext=None, writers=4):
+    """Scores the open video against its ground truth on the device, SCORE_CHUNK frames a call -> (scores float64 [F, 5], auc,
+    times).  auc None: P3DSession.video_score; the 8-bit maps stay on the device unless video_dir asks for the images: then each
+    call also returns its bytes and they are encoded as write_video_images_resident encodes them, while the next call runs.
+    auc, a dict(borji, sauc, pool_size, own_pool, n_rep, step, seed): AUC-Borji and / or shuffled AUC of the same bytes as well
+    (P3DSession.video_score_auc; --score-borji, --score-sauc M) -> auc float64 [F, 2]: the Borji and shuffled means per frame, NaN
+    where not asked.  One RandomState(seed) per video; per chunk of SCORE_CHUNK frames it draws, in this order: the rows of pool
+    slots in frame order (sauc_ids), [video_shuffled_begin], Borji's randint per frame with fixations (metrics.borji_draws_u8),
+    metrics.shuffled_draws.  With video_dir the images then come from video_maps_u8, one more run of the maps' chain per chunk."""
     from concurrent.futures import ThreadPoolExecutor
     from sap3d_tensorflow_amd import metrics
     scores = np.full((F, len(SCORE_NAMES)), np.nan, np.float64)
-    auc = np.full((F, 2), np.nan, np.float64)
-    t = dict(upload=0.0, device=0.0, score=0.0, auc=0.0, files=0)
-    rng = np.random.RandomState(seed)
+    means = np.full((F, 2), np.nan, np.float64) if auc else None
+    t = dict(upload=0.0, device=0.0, score=0.0, files=0, **(dict(auc=0.0) if auc else {}))
+    rng = np.random.RandomState(auc["seed"]) if auc else None
+
+    def write(f, m):
+        save_image(os.path.join(video_dir, "frame_%d.%s" % (f + 1, ext)), m, ext)
+
     held = []
     with ThreadPoolExecutor(max_workers=writers) as pool:
         for first in range(0, F, SCORE_CHUNK):
             n = min(SCORE_CHUNK, F - first)
-            fix = fixation[first:first + n]
-            n_other = bidx = ranks = n_rows = None
-            if sauc:
-                n_other = sess.video_shuffled_begin(sauc_ids(rng, pool_size, first, first + n, sauc, own_pool))
-            nf = np.count_nonzero(fix.reshape(n, -1) >= 128, axis=1)
-            if borji:
-                bidx, nf = metrics.borji_draws_u8(fix, n_rep, rng)
-            if sauc:
-                ranks, n_rows = metrics.shuffled_draws(nf, n_other, n_rep, rng)
-            got = sess.video_score_auc(first, n, density[first:first + n], fix, size=size, columns=columns, ties=ties, borji_idx=bidx,
-                                       shuffled_ranks=ranks, n_rows=n_rows, n_rep=n_rep, step_size=step)
-            for k in ("upload", "device", "score", "auc"):
-                t[k] += sess.last_score_ms[k]
-            scores[first:first + n] = got["scores"]
-            if borji:
-                auc[first:first + n, 0] = [np.mean(r) for r in got["borji"]]
-            if sauc:
-                auc[first:first + n, 1] = [np.mean(r) for r in got["shuffled"]]
+            den, fix, maps = density[first:first + n], fixation[first:first + n], None
+            if not auc:
+                got = sess.video_score(first, n, den, fix, size=size, columns=columns, ties=ties, with_maps=video_dir is not None)
+                if video_dir is not None:
+                    got, maps = got
+            else:
+                n_other = bidx = ranks = n_rows = None
+                if auc["sauc"]:
+                    n_other = sess.video_shuffled_begin(sauc_ids(rng, auc["pool_size"], first, first + n, auc["sauc"], auc["own_pool"]))
+                nf = np.count_nonzero(fix.reshape(n, -1) >= 128, axis=1)
+                if auc["borji"]:
+                    bidx, nf = metrics.borji_draws_u8(fix, auc["n_rep"], rng)
+                if auc["sauc"]:
+                    ranks, n_rows = metrics.shuffled_draws(nf, n_other, auc["n_rep"], rng)
+                res = sess.video_score_auc(first, n, den, fix, size=size, columns=columns, ties=ties, borji_idx=bidx, shuffled_ranks=ranks,
+                                           n_rows=n_rows, n_rep=auc["n_rep"], step_size=auc["step"])
+                got = res["scores"]
+                if auc["borji"]:
+                    means[first:first + n, 0] = [np.mean(r) for r in res["borji"]]
+                if auc["sauc"]:
+                    means[first:first + n, 1] = [np.mean(r) for r in res["shuffled"]]
+            for k, ms in sess.last_score_ms.items():
+                t[k] += ms
+            scores[first:first + n] = got
             if video_dir is not None:
-                maps = sess.video_maps_u8(first, n, size=size)
-                for fut in held:
-                    fut.result()
-                held = [pool.submit(save_image, os.path.join(video_dir, "frame_%d.%s" % (first + k + 1, ext)), m, ext)
-                        for k, m in enumerate(maps)]
+                held = hand_over(pool, held, write, first, sess.video_maps_u8(first, n, size=size) if auc else maps)
                 t["files"] += n
-        for fut in held:
-            fut.result()
-    return scores, auc, t
+        hand_over(pool, held, write, F, ())
+    return scores, means, t
 
 
 def auc_means(auc):
@@ -545,9 +529,12 @@ def run_resident(sess, args, path):
     F = predict_video_resident(sess, np.load(path), args.batch, args.stride, args.overlap, times)
     t1 = time.perf_counter()
     means = ts = None
-    if args.truth and args.score_auc:
+    if args.truth:
         density, fixation = load_truth(args.truth, name, F, args.size)
-        pool_size = 0
+        auc = None
+        if args.score_auc:
+            auc = dict(borji=args.score_borji, sauc=args.score_sauc, pool_size=0, own_pool=not args.sauc_pool, n_rep=args.score_rep,
+                       step=args.score_step, seed=args.score_seed)
         if args.score_sauc:
             pool_maps = fixation
             if args.sauc_pool:
@@ -556,28 +543,21 @@ def run_resident(sess, args, path):
                     raise ValueError("--sauc-pool: %s is %s %s, not uint8 [P, %d, %d]" % ((args.sauc_pool, pool_maps.dtype, pool_maps.shape) + tuple(args.size)))
             elif F < 2:
                 raise ValueError("--score-sauc: a video of one frame has no other frame to draw from; give --sauc-pool")
-            pool_size = len(pool_maps)
-            sess.open_fixation_pool(tuple(args.size), pool_size)
+            auc["pool_size"] = len(pool_maps)
+            sess.open_fixation_pool(tuple(args.size), len(pool_maps))
             sess.fixation_pool_put(0, pool_maps)
-        scores, auc, ts = score_video_resident_auc(sess, F, density, fixation, tuple(args.size), tuple(args.score_columns), args.score_ties,
-                                                   args.score_borji, args.score_sauc, pool_size, not args.sauc_pool, args.score_rep,
-                                                   args.score_step, args.score_seed, video_dir if args.write != "npy" else None, args.write,
-                                                   args.writers)
+        scores, auc, ts = score_video_resident(sess, F, density, fixation, tuple(args.size), tuple(args.score_columns), args.score_ties, auc,
+                                               video_dir if args.write != "npy" else None, args.write, args.writers)
         if args.score_sauc:
             sess.close_fixation_pool()
         np.save(os.path.join(args.out, name + "_scores.npy"), scores)
-        np.save(os.path.join(args.out, name + "_auc.npy"), auc)
+        if auc is not None:
+            np.save(os.path.join(args.out, name + "_auc.npy"), auc)
         means = nan_means(scores)
         print("%s scores over %d frames: %s" % (name, F, format_means(means)))
-        print("%s auc over %d frames: %s" % (name, F, format_auc(auc_means(auc))))
-        args.auc_means.append(auc_means(auc))
-    elif args.truth:
-        density, fixation = load_truth(args.truth, name, F, args.size)
-        scores, ts = score_video_resident(sess, F, density, fixation, tuple(args.size), tuple(args.score_columns), args.score_ties,
-                                          video_dir if args.write != "npy" else None, args.write, args.writers)
-        np.save(os.path.join(args.out, name + "_scores.npy"), scores)
-        means = nan_means(scores)
-        print("%s scores over %d frames: %s" % (name, F, format_means(means)))
+        if auc is not None:
+            print("%s auc over %d frames: %s" % (name, F, format_auc(auc_means(auc))))
+            args.auc_means.append(auc_means(auc))
     if args.write == "npy":
         sal = sess.video_maps(0, F)
         np.save(os.path.join(args.out, os.path.basename(path)), sal)

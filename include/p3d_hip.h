@@ -1506,7 +1506,7 @@ int p3d_debug_score_plan(int64_t n_pix, int n, int offset, int* blocks_per_map, 
  *                    lie in [0, n_other[b]).  nf is counted from `fixation` on the host and the device's count is held to it.
  *                    Every refusal comes before any launch or upload and leaves the outputs untouched.  stage_ms (or NULL) [4]:
  *                    HIP-event milliseconds of the uploads, of the maps' chain, of the five-column scoring launches (pass A
- *                    included), of the preparation + select + sweeps.
+ *                    included), of the preparation + select + sweeps (0 where no sweep is asked for: nothing is timed).
  * TEST HOOK (tests/test_gpu_score_auc.py):
  * p3d_debug_score_sweep_u8  p3d_score_sweep_u8's launch descriptions with every device buffer between guard elements: sal starts
  *                    `offset` bytes (0 .. 15) past a 16-byte boundary and fixation (3 offset) mod 16 bytes past one, as in

@@ -718,22 +718,50 @@ namespace {
 // inside the device stage's time: it queues whatever makes the maps readable and names them as runs of maps of ph x pw pixels.
 // Off: one double-precision p3d_resize_u8 per run; on: the float32 resize / blur / normalise / byte sequence, P3D_POST_CHUNK maps
 // at a time.  Ends synchronised; stage_ms as p3d_pred_maps_u8's.
-// A consumer (p3d_video_score) takes the device bytes where they are instead of a copy of the chain: its buffers are carved after
-// the chain's in the same layout, `before` is queued ahead of the sources, `after` behind the chain with the bytes and `counters`
-// zeroed arrival counters of its own, `results` (its copies back to the host) behind that; out may then be NULL (the bytes stay
-// on the device) and ms [3] receives the times of `before`, of the device stage and of `after`.  Without one, nothing here differs
-// from what the two callers issued before.
-struct U8Consumer {
-    size_t counters = 0;
-    std::function<void(Carve&)> carve;
-    std::function<void(hipStream_t)> before;
-    std::function<void(hipStream_t, const unsigned char*, unsigned*)> after;
-    std::function<void(hipStream_t)> results;
-    double* ms = nullptr;
+// A score stage (p3d_video_score, p3d_video_score_auc) takes the device bytes where they are instead of a copy of the chain: its
+// buffers are carved after the chain's in the same layout, its upload is queued ahead of the sources, its launches behind the chain
+// with the bytes and counters() zeroed arrival counters of its own, its results (the copies back to the host) behind that; out may
+// then be NULL (the bytes stay on the device) and, timed, its ms [3] receives the times of the upload, of the device stage and of
+// the launches.  Without one, nothing here differs from what the two callers issued before.
+// What one scoring of n maps of H x W bytes asks for; every pointer is host memory.  Whatever is not asked for is not issued.
+struct ScoreRequest {
+    const char* who; int n, H, W;
+    int flags = 0, ties = P3D_SCORE_TIES_REFERENCE;      // the columns -> out [n][5]; 0: none, and the density is not read
+    const unsigned char* density = nullptr; const unsigned char* fixation = nullptr; double* out = nullptr;
+    // AUC-Borji -> borji [n][n_rep] (null: not asked for): map b's idx_rows[b] x n_rep indices (null: its fixated pixels, counted here)
+    const int* idx = nullptr; const int* idx_rows = nullptr; double* borji = nullptr;
+    // shuffled AUC -> shuffled [n][n_rep] (null: not asked for): ranks of n_rows[b] x n_rep draws into the union that `pool` holds
+    const int* ranks = nullptr; const int* n_rows = nullptr; const p3d_handle* pool = nullptr; double* shuffled = nullptr;
+    int n_rep = 0; double step = 0.0;
+    bool timed = false;                                   // events around the stage's moments (ms) and around the sweeps (sweep_ms)
+};
+// The launches of score_u8.hip and score_auc_u8.hip behind some device bytes: the launch arguments, the tables of the host and the
+// device buffers, carved from a caller's scratch.  The constructor refuses what the request's arrays get wrong and queues nothing.
+struct ScoreStage {
+    const ScoreRequest r; const size_t bytes;
+    ScoreArgs a; ScoreSweepArgs q;
+    std::vector<int> nf, meta3, info; std::vector<long long> metaB, metaS;
+    size_t totB = 0, totS = 0; int max_rows = 0;
+    unsigned char* dd = nullptr; unsigned char* dx = nullptr;
+    int* didx = nullptr; int* dranks = nullptr; int* dsel = nullptr; int* dmeta3 = nullptr; int* drows = nullptr;
+    long long* dmetaB = nullptr; long long* dmetaS = nullptr; double* perB = nullptr; double* perS = nullptr;
+    StageTimer sweeps; double ms[3] = {0.0, 0.0, 0.0};
+    explicit ScoreStage(const ScoreRequest& r);
+    bool sweep() const { return r.borji || r.shuffled; }
+    size_t counters() const;
+    void carve(Carve& c);
+    void upload(hipStream_t s);
+    // pass A and the columns, then the sweeps' preparation (q.info: the device's counts); sweep_rest: the sweeps themselves
+    void prepare(hipStream_t s, const unsigned char* sal, unsigned* counters);
+    void sweep_rest(hipStream_t s);
+    void launch(hipStream_t s, const unsigned char* sal, unsigned* counters) { prepare(s, sal, counters); sweep_rest(s); }
+    void results(hipStream_t s);
+    void check_counts() const;                            // after the results have arrived: the device's counts against nf
+    double sweep_ms() const { return sweeps.ev[0] ? (double)sweeps.ms(0) : 0.0; }
 };
 void maps_u8_chain(p3d_handle* h, long long maps, int ph, int pw, float scale, int H, int W, unsigned char* out, double* stage_ms,
                    size_t extra, const std::function<void(hipStream_t, float*, std::vector<PostRun>&)>& sources,
-                   const U8Consumer* use = nullptr) {
+                   ScoreStage* use = nullptr) {
     const long long hw = (long long)H * W, bytes = maps * hw;
     const hipStream_t s = h->stream;
     // p3d_set_postprocess: the float32 chain resize -> blur -> normalise -> bytes, P3D_POST_CHUNK maps at a time; its scratch
@@ -751,15 +779,16 @@ void maps_u8_chain(p3d_handle* h, long long maps, int ph, int pw, float scale, i
     unsigned char* d = nullptr;
     float* ex = nullptr;
     const size_t chain_counters = chain ? (size_t)post_chunk : 0;
-    unsigned* const counters = carve_scratch(s, chain_counters + (use ? use->counters : 0), [&](Carve& c) {
+    unsigned* const counters = carve_scratch(s, chain_counters + (use ? use->counters() : 0), [&](Carve& c) {
         d = c.take<unsigned char>((size_t)bytes);      // (the first take starts at offset 0: with nothing else, the slab is the bytes)
         if (chain) scratch.carve(c, st, post_chunk, hw, true);
         ex = extra ? c.take<float>(extra) : nullptr;
         if (use) use->carve(c);
     });
-    StageTimer tm(stage_ms != nullptr || (use && use->ms), 3), ends(use && use->ms, 2);
+    const bool use_timed = use && use->r.timed;
+    StageTimer tm(stage_ms != nullptr || use_timed, 3), ends(use_timed, 2);
     ends.mark(0, s);
-    if (use) use->before(s);
+    if (use) use->upload(s);
     tm.mark(0, s);
     PostJob job;
     sources(s, ex, job.runs);
@@ -774,14 +803,14 @@ void maps_u8_chain(p3d_handle* h, long long maps, int ph, int pw, float scale, i
         }
     }
     tm.mark(1, s);
-    if (use) use->after(s, d, counters + chain_counters);
+    if (use) use->launch(s, d, counters + chain_counters);
     ends.mark(1, s);
     if (use) use->results(s);
     if (out) HIPCHECK(hipMemcpyAsync(out, d, (size_t)bytes, hipMemcpyDeviceToHost, s));
     tm.mark(2, s);
     HIPCHECK(hipStreamSynchronize(s));
     if (stage_ms) { stage_ms[0] = tm.ms(0); stage_ms[1] = tm.ms(1); }
-    if (use && use->ms) {
+    if (use_timed) {
         float up = 0.f, sc = 0.f;
         HIPCHECK(hipEventElapsedTime(&up, ends.ev[0], tm.ev[0]));
         HIPCHECK(hipEventElapsedTime(&sc, tm.ev[1], ends.ev[1]));
@@ -1635,21 +1664,42 @@ int p3d_video_last_ms(p3d_handle* h, double ms[2]) {
     API_END
 }
 
+}  // extern "C"
+namespace {
+// Frames first .. first + n - 1 of the open video as a read-out's source.  Refused here, in this order and before any scratch is
+// asked for (a refusal changes nothing): no open video, the range, more than `most` frames, what p3d_set_video_temporal's filter
+// needs and, where `predicted` is asked for, a frame without a prediction.
+struct VideoSource {
+    p3d_handle* h; const char* who; int first, n; bool temporal;
+    VideoSource(p3d_handle* h_, const char* who_, int first_, int n_, bool predicted = true, int most = INT32_MAX)
+        : h(h_), who(who_), first(first_), n(n_), temporal(h_->temporal_cfg.on()) {
+        h->video_need_open(who);
+        h->video_range(who, first, n);
+        if (n > most) throw P3dError(std::string(who) + ": 1 .. " + std::to_string(most) + " maps");
+        if (temporal) h->video_temporal_check(who, first, n);
+        if (predicted) h->video_need_predicted(who, first, n);
+    }
+    // floats of scratch the maps need: the filtered maps under either mode, the divided sums under MEAN
+    size_t extra() const { return temporal || h->vid_mode == VIDEO_MEAN ? (size_t)n * (size_t)h->vid_hw() : 0; }
+    // queues whatever makes the maps readable; -> the maps [n][hw]
+    const float* queue(hipStream_t s, float* scratch) const {
+        return temporal ? h->video_temporal(who, first, n, scratch, s) : h->video_finalize(who, first, n, scratch, s);
+    }
+    void operator()(hipStream_t s, float* scratch, std::vector<PostRun>& runs) const { runs.push_back({queue(s, scratch), h->vid_hw(), 1, n}); }
+};
+}  // namespace
+extern "C" {
+
 int p3d_video_get_maps(p3d_handle* h, int first, int n, float* maps, int32_t* counts) {
     API_BEGIN
     if (!h || !maps) throw P3dError("null argument");
     HIPCHECK(hipSetDevice(h->cfg.device));
-    h->video_need_open("video_get_maps");
-    h->video_range("video_get_maps", first, n);
+    const VideoSource src(h, "video_get_maps", first, n, false);      // (a frame without a prediction: refused by video_finalize)
     const hipStream_t s = h->stream;
-    const size_t ne = (size_t)n * (size_t)h->vid_hw();
     float* slab = nullptr;
     unsigned* counters = nullptr;
-    const bool temporal = h->temporal_cfg.on();      // p3d_set_video_temporal: the filtered maps, into scratch under either mode
-    if (temporal) h->video_temporal_check("video_get_maps", first, n);      // (before the scratch is asked for: a refusal changes nothing)
-    if (temporal || h->vid_mode == VIDEO_MEAN) HIPCHECK(p3d_stream_scratch(s, ne, 0, &slab, &counters));
-    const float* src = temporal ? h->video_temporal("video_get_maps", first, n, slab, s) : h->video_finalize("video_get_maps", first, n, slab, s);
-    HIPCHECK(copy_now(maps, src, ne * 4, hipMemcpyDeviceToHost, s));
+    if (src.extra()) HIPCHECK(p3d_stream_scratch(s, src.extra(), 0, &slab, &counters));
+    HIPCHECK(copy_now(maps, src.queue(s, slab), (size_t)n * (size_t)h->vid_hw() * 4, hipMemcpyDeviceToHost, s));
     if (counts) memcpy(counts, h->vid_count.data() + first, (size_t)n * sizeof(int32_t));
     API_END
 }
@@ -1660,26 +1710,16 @@ int p3d_video_maps_u8(p3d_handle* h, int first, int n, float scale, int H, int W
     if (H < 1 || W < 1) throw P3dError("video_maps_u8: empty map");
     if ((long long)H * W > INT32_MAX) throw P3dError("video_maps_u8: H * W exceeds the kernel's int32 in-map offsets");
     HIPCHECK(hipSetDevice(h->cfg.device));
-    h->video_need_open("video_maps_u8");
-    h->video_range("video_maps_u8", first, n);
-    const bool temporal = h->temporal_cfg.on();      // p3d_set_video_temporal: the chain runs on the filtered maps
-    if (temporal) h->video_temporal_check("video_maps_u8", first, n);      // (before the scratch is asked for: a refusal changes nothing)
-    for (int f = first; f < first + n; ++f)
-        if (h->vid_count[(size_t)f] == 0) throw P3dError("video_maps_u8: frame " + std::to_string(f) + " has no prediction yet (count 0)");
+    const VideoSource src(h, "video_maps_u8", first, n);
     if (stage_ms) stage_ms[0] = stage_ms[1] = 0.0;
-    const long long phw = h->vid_hw();
-    maps_u8_chain(h, n, h->pred->H, h->pred->W, scale, H, W, out, stage_ms, temporal || h->vid_mode == VIDEO_MEAN ? (size_t)n * (size_t)phw : 0,
-                  [&](hipStream_t s, float* scratch, std::vector<PostRun>& runs) {
-                      runs.push_back({temporal ? h->video_temporal("video_maps_u8", first, n, scratch, s)
-                                               : h->video_finalize("video_maps_u8", first, n, scratch, s), phw, 1, n});
-                  });
+    maps_u8_chain(h, n, h->pred->H, h->pred->W, scale, H, W, out, stage_ms, src.extra(), src);
     API_END
 }
 
 }  // extern "C"
 namespace {
-// ---- scoring 8-bit maps (score_u8.hip; the law in include/p3d_hip.h): one check, one scratch layout and one launch sequence for
-// p3d_video_score, p3d_score_maps_u8 and p3d_debug_score_u8 ----------------------------------------------------------------------
+// ---- scoring 8-bit maps (score_u8.hip; the law in include/p3d_hip.h): one check, one table of buffer sizes and one launch
+// sequence for the score stage and p3d_debug_score_u8 ------------------------------------------------------------------------------
 void score_check(const char* who, const void* density, const void* fixation, int n, int H, int W, int flags, int ties, const void* out) {
     if (!density || !out) throw P3dError("null argument");
     if (n < 1 || n > 65535) throw P3dError(std::string(who) + ": 1 .. 65535 maps");
@@ -1695,60 +1735,17 @@ ScoreArgs score_args(int n, long long n_pix, int flags, int ties) {
     a.n = n; a.n_pix = (int)n_pix; a.flags = flags; a.ties = ties; a.nblk = p.nblk; a.chunk = p.chunk;
     return a;
 }
-void score_carve(Carve& c, ScoreArgs& a) {
-    a.tab = c.take<unsigned>((size_t)a.n * P3D_SCORE_TAB_WORDS);
-    a.lut = c.take<double>((size_t)a.n * 1024);
-    a.part = c.take<double>((size_t)a.n * a.nblk * 2);
-    a.out = c.take<double>((size_t)a.n * 5);
-}
+// Elements of the buffers of one scoring: what the stage carves and what the hooks put between guards
+struct ScoreSizes {
+    size_t tab, lut, part, out, counters;
+    explicit ScoreSizes(const ScoreArgs& a)
+        : tab((size_t)a.n * P3D_SCORE_TAB_WORDS), lut((size_t)a.n * 1024), part((size_t)a.n * a.nblk * 2), out((size_t)a.n * 5), counters((size_t)a.n * 2) {}
+};
 void score_sequence(const ScoreArgs& a, hipStream_t s) {
     for (int st = 0; st < SCORE_STAGES; ++st) HIPCHECK(p3d_score_launch(st, a, s));
 }
 }  // namespace
 extern "C" {
-
-int p3d_video_score(p3d_handle* h, int first, int n, float scale, int H, int W, const unsigned char* density, const unsigned char* fixation,
-                    int flags, int ties, double* out, unsigned char* maps_out, double* stage_ms) {
-    API_BEGIN
-    if (!h) throw P3dError("null argument");
-    score_check("video_score", density, fixation, std::max(1, std::min(n, 65535)), H, W, flags, ties, out);
-    HIPCHECK(hipSetDevice(h->cfg.device));
-    h->video_need_open("video_score");
-    h->video_range("video_score", first, n);
-    if (n > 65535) throw P3dError("video_score: 1 .. 65535 maps");
-    const bool temporal = h->temporal_cfg.on();
-    if (temporal) h->video_temporal_check("video_score", first, n);
-    for (int f = first; f < first + n; ++f)
-        if (h->vid_count[(size_t)f] == 0) throw P3dError("video_score: frame " + std::to_string(f) + " has no prediction yet (count 0)");
-    if (stage_ms) stage_ms[0] = stage_ms[1] = stage_ms[2] = 0.0;
-    const long long phw = h->vid_hw(), N = (long long)H * W;
-    const size_t bytes = (size_t)n * (size_t)N;
-    ScoreArgs a = score_args(n, N, flags, ties);
-    unsigned char* dd = nullptr; unsigned char* dx = nullptr;
-    U8Consumer use;
-    use.counters = (size_t)n * 2;
-    use.ms = stage_ms;
-    use.carve = [&](Carve& c) {
-        dd = c.take<unsigned char>(bytes);
-        dx = fixation ? c.take<unsigned char>(bytes) : nullptr;
-        score_carve(c, a);
-    };
-    use.before = [&](hipStream_t s) {
-        HIPCHECK(hipMemcpyAsync(dd, density, bytes, hipMemcpyHostToDevice, s));
-        if (fixation) HIPCHECK(hipMemcpyAsync(dx, fixation, bytes, hipMemcpyHostToDevice, s));
-    };
-    use.after = [&](hipStream_t s, const unsigned char* d, unsigned* counters) {
-        a.sal = d; a.den = dd; a.fix = dx; a.counter = counters;
-        score_sequence(a, s);
-    };
-    use.results = [&](hipStream_t s) { HIPCHECK(hipMemcpyAsync(out, a.out, (size_t)n * 5 * sizeof(double), hipMemcpyDeviceToHost, s)); };
-    maps_u8_chain(h, n, h->pred->H, h->pred->W, scale, H, W, maps_out, nullptr, temporal || h->vid_mode == VIDEO_MEAN ? (size_t)n * (size_t)phw : 0,
-                  [&](hipStream_t s, float* scratch, std::vector<PostRun>& runs) {
-                      runs.push_back({temporal ? h->video_temporal("video_score", first, n, scratch, s)
-                                               : h->video_finalize("video_score", first, n, scratch, s), phw, 1, n});
-                  }, &use);
-    API_END
-}
 
 int p3d_score_maps_u8(int device, const unsigned char* sal, const unsigned char* density, const unsigned char* fixation, int n, int H, int W,
                       int flags, int ties, double* out) {
@@ -1756,15 +1753,15 @@ int p3d_score_maps_u8(int device, const unsigned char* sal, const unsigned char*
     if (!sal) throw P3dError("null argument");
     score_check("score_maps_u8", density, fixation, n, H, W, flags, ties, out);
     metric_args(device, sal, density, 1, 1, out);
-    const long long N = (long long)H * W;
-    const size_t bytes = (size_t)n * (size_t)N;
-    DevArr<unsigned char> ds(bytes, sal), dd(bytes, density), dx(fixation ? bytes : 1, fixation);
-    ScoreArgs a = score_args(n, N, flags, ties);
-    a.counter = carve_scratch(nullptr, (size_t)n * 2, [&](Carve& c) { score_carve(c, a); });
-    a.sal = ds.p; a.den = dd.p; a.fix = fixation ? dx.p : nullptr;
-    score_sequence(a, nullptr);
+    ScoreRequest r{"score_maps_u8", n, H, W};
+    r.flags = flags; r.ties = ties; r.density = density; r.fixation = fixation; r.out = out;
+    ScoreStage stage(r);
+    DevArr<unsigned char> ds(stage.bytes, sal);
+    unsigned* const counters = carve_scratch(nullptr, stage.counters(), [&](Carve& c) { stage.carve(c); });
+    stage.upload(nullptr);
+    stage.launch(nullptr, ds.p, counters);
+    stage.results(nullptr);
     HIPCHECK(hipDeviceSynchronize());
-    HIPCHECK(copy_now(out, a.out, (size_t)n * 5 * sizeof(double), hipMemcpyDeviceToHost, nullptr));
     API_END
 }
 
@@ -1778,15 +1775,16 @@ int p3d_debug_score_u8(int device, const unsigned char* sal, const unsigned char
     const long long N = (long long)H * W;
     const size_t bytes = (size_t)n * (size_t)N;
     ScoreArgs a = score_args(n, N, flags, ties);
+    const ScoreSizes sz(a);
     // guards of 16 elements keep a 16-byte boundary at the data's start for every element type here; the sources are then shifted
     Guarded<unsigned char> ds(bytes, 16, (size_t)offset, sal), dd(bytes, 16, (size_t)(2 * offset % 16), density),
         dx(fixation ? bytes : 0, 16, (size_t)(3 * offset % 16), fixation);
-    Guarded<unsigned> tab((size_t)n * P3D_SCORE_TAB_WORDS, 16, 0, nullptr), counter((size_t)n * 2, 16, 0, nullptr);
-    Guarded<double> lut((size_t)n * 1024, 16, 0, nullptr), part((size_t)n * a.nblk * 2, 16, 0, nullptr), dout((size_t)n * 5, 16, 0, nullptr);
+    Guarded<unsigned> tab(sz.tab, 16, 0, nullptr), counter(sz.counters, 16, 0, nullptr);
+    Guarded<double> lut(sz.lut, 16, 0, nullptr), part(sz.part, 16, 0, nullptr), dout(sz.out, 16, 0, nullptr);
     a.sal = ds.data(); a.den = dd.data(); a.fix = fixation ? dx.data() : nullptr;
     a.tab = tab.data(); a.counter = counter.data(); a.lut = lut.data(); a.part = part.data(); a.out = dout.data();
     score_sequence(a, nullptr);
-    std::vector<unsigned> t((size_t)n * P3D_SCORE_TAB_WORDS), zero((size_t)n * 2, 1u);
+    std::vector<unsigned> t(sz.tab), zero(sz.counters, 1u);
     tab.back(t.data(), "debug_score_u8");
     counter.back(zero.data(), "debug_score_u8");
     dout.back(out, "debug_score_u8");
@@ -1818,8 +1816,8 @@ int p3d_debug_score_plan(int64_t n_pix, int n, int offset, int* blocks_per_map, 
 
 }  // extern "C"
 namespace {
-// ---- SPLIT SWEEP on 8-bit maps: AUC-Borji and shuffled AUC (score_auc_u8.hip; the law in include/p3d_hip.h): one check, one
-// scratch layout and one launch sequence for p3d_score_sweep_u8, p3d_debug_score_sweep_u8 and p3d_video_score_auc ---------------
+// ---- SPLIT SWEEP on 8-bit maps: AUC-Borji and shuffled AUC (score_auc_u8.hip; the law in include/p3d_hip.h): one check, one table
+// of buffer sizes and one launch sequence for the score stage and p3d_debug_score_sweep_u8 ------------------------------------------
 ScoreSweepArgs sweep_args(const char* who, int n, long long n_pix, int n_rep, double step) {
     ScoreSweepArgs q;
     q.kmax = p3d_sweep_kmax(step);
@@ -1828,11 +1826,11 @@ ScoreSweepArgs sweep_args(const char* who, int n, long long n_pix, int n_rep, do
     q.n = n; q.n_pix = (int)n_pix; q.n_rep = n_rep; q.step = step; q.cols = p3d_sweep_cols(q.kmax, n_rep);
     return q;
 }
-void sweep_carve(Carve& c, ScoreSweepArgs& q) {
-    q.lev = c.take<int>((size_t)q.n * 256);
-    q.lad = c.take<unsigned>((size_t)q.n * (q.kmax + 1));
-    q.info = c.take<int>((size_t)q.n * 4);
-}
+struct SweepSizes {
+    size_t lev, lad, info, per_rep;
+    explicit SweepSizes(const ScoreSweepArgs& q)
+        : lev((size_t)q.n * 256), lad((size_t)q.n * (q.kmax + 1)), info((size_t)q.n * 4), per_rep((size_t)q.n * q.n_rep) {}
+};
 // meta [n][2] of maps whose rows are concatenated: the row count, the offset of the first index; -> the number of indices
 std::vector<long long> sweep_meta(const char* who, const int* n_rows, int n, int n_rep, size_t& total) {
     std::vector<long long> meta((size_t)n * 2);
@@ -1857,17 +1855,12 @@ std::vector<int> host_n_fix(const unsigned char* fixation, int n, long long n_pi
     }
     return nf;
 }
-// the op-level sweep's checks that need no device; -> meta
-std::vector<long long> sweep_op_check(const char* who, const void* sal, const void* fixation, int n, int H, int W, const int* idx, const int* n_rows,
-                                      const void* per_rep, int n_rep, size_t& total) {
+// the op-level sweep's checks of its arguments and shapes
+void sweep_op_shape(const char* who, const void* sal, const void* fixation, int n, int H, int W, const int* n_rows, const void* per_rep) {
     if (!sal || !fixation || !n_rows || !per_rep) throw P3dError("null argument");
     if (n < 1 || n > 65535) throw P3dError(std::string(who) + ": 1 .. 65535 maps");
     if (H < 1 || W < 1) throw P3dError(std::string(who) + ": empty map");
     if ((long long)H * W > P3D_SCORE_MAX_PIXELS) throw P3dError(std::string(who) + ": H * W exceeds 2^23");
-    std::vector<long long> meta = sweep_meta(who, n_rows, n, n_rep, total);
-    if (total > 0 && !idx) throw P3dError("null argument");
-    check_indices(idx, total, (long long)H * W, who);
-    return meta;
 }
 // the device's counts (info[b][0] = nf) against the rows: n_rows[b] <= nf[b]
 void sweep_check_rows(const char* who, const std::vector<int>& info, const int* n_rows, int n) {
@@ -1876,38 +1869,151 @@ void sweep_check_rows(const char* who, const std::vector<int>& info, const int* 
             throw P3dError(std::string(who) + ": map " + std::to_string(b) + ": " + std::to_string(n_rows[b]) + " rows, but the map has " +
                            std::to_string(info[(size_t)b * 4]) + " fixated pixels");
 }
+
+// ---- the score stage (declared above maps_u8_chain) -------------------------------------------------------------------------------
+ScoreStage::ScoreStage(const ScoreRequest& r_)
+    : r(r_), bytes((size_t)r_.n * (size_t)r_.H * (size_t)r_.W),
+      a(score_args(r_.n, (long long)r_.H * r_.W, r_.flags, r_.flags ? r_.ties : P3D_SCORE_TIES_REFERENCE)), sweeps(r_.timed && (r_.borji || r_.shuffled), 2) {
+    if (!sweep()) return;
+    const long long N = (long long)r.H * r.W;
+    q = sweep_args(r.who, r.n, N, r.n_rep, r.step);
+    if ((r.borji && !r.idx_rows) || r.shuffled) {
+        nf = host_n_fix(r.fixation, r.n, N);
+        info.assign(SweepSizes(q).info, 0);
+    }
+    if (r.borji) {
+        metaB = sweep_meta(r.who, r.idx_rows ? r.idx_rows : nf.data(), r.n, r.n_rep, totB);
+        if (totB > 0 && !r.idx) throw P3dError("null argument");
+        check_indices(r.idx, totB, N, r.who);
+    }
+    if (r.shuffled) {
+        const p3d_handle* h = r.pool;
+        h->fixpool_need_open(r.who);
+        if (!h->vu.begun) throw P3dError(std::string(r.who) + ": no union is held (p3d_video_shuffled_begin)");
+        if (h->fp_H != r.H || h->fp_W != r.W)
+            throw P3dError(std::string(r.who) + ": the fixation pool holds " + std::to_string(h->fp_H) + " x " + std::to_string(h->fp_W) + " maps, the call scores " +
+                           std::to_string(r.H) + " x " + std::to_string(r.W));
+        if (h->vu.n != r.n) throw P3dError(std::string(r.who) + ": the union was taken for " + std::to_string(h->vu.n) + " frames, the call scores " + std::to_string(r.n));
+        for (int b = 0; b < r.n; ++b)
+            if (r.n_rows[b] != (int)std::min<long long>(nf[(size_t)b], h->vu.n_other[(size_t)b]))
+                throw P3dError(std::string(r.who) + ": frame " + std::to_string(b) + ": n_rows = " + std::to_string(r.n_rows[b]) + ", but min(n_fix, n_other) = min(" +
+                               std::to_string(nf[(size_t)b]) + ", " + std::to_string(h->vu.n_other[(size_t)b]) + ")");
+        p3d_handle::shuffled_check_draws(r.who, r.ranks, r.n_rows, h->vu.n_other.data(), r.n, r.n_rep, r.step);
+        metaS = sweep_meta(r.who, r.n_rows, r.n, r.n_rep, totS);
+        meta3.assign((size_t)r.n * 3, 0);
+        for (int b = 0; b < r.n; ++b) { meta3[(size_t)b * 3 + 2] = (int)metaS[(size_t)b * 2 + 1]; max_rows = std::max(max_rows, r.n_rows[b]); }
+    }
+}
+size_t ScoreStage::counters() const { return ScoreSizes(a).counters; }
+void ScoreStage::carve(Carve& c) {
+    const ScoreSizes z(a);
+    dd = r.density && r.flags ? c.take<unsigned char>(bytes) : nullptr;
+    dx = r.fixation ? c.take<unsigned char>(bytes) : nullptr;
+    a.tab = c.take<unsigned>(z.tab); a.lut = c.take<double>(z.lut); a.part = c.take<double>(z.part); a.out = c.take<double>(z.out);
+    if (!sweep()) return;
+    const SweepSizes w(q);
+    q.lev = c.take<int>(w.lev); q.lad = c.take<unsigned>(w.lad); q.info = c.take<int>(w.info);
+    if (r.borji) { didx = c.take<int>(totB); dmetaB = c.take<long long>(metaB.size()); perB = c.take<double>(w.per_rep); }
+    if (r.shuffled) {
+        dranks = c.take<int>(totS); dsel = c.take<int>(totS); dmeta3 = c.take<int>(meta3.size()); drows = c.take<int>((size_t)r.n);
+        dmetaS = c.take<long long>(metaS.size()); perS = c.take<double>(w.per_rep);
+    }
+}
+void ScoreStage::upload(hipStream_t s) {
+    if (dd) HIPCHECK(hipMemcpyAsync(dd, r.density, bytes, hipMemcpyHostToDevice, s));
+    if (dx) HIPCHECK(hipMemcpyAsync(dx, r.fixation, bytes, hipMemcpyHostToDevice, s));
+    if (r.borji) {
+        if (totB) HIPCHECK(hipMemcpyAsync(didx, r.idx, totB * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHECK(hipMemcpyAsync(dmetaB, metaB.data(), metaB.size() * sizeof(long long), hipMemcpyHostToDevice, s));
+    }
+    if (r.shuffled) {
+        if (totS) HIPCHECK(hipMemcpyAsync(dranks, r.ranks, totS * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHECK(hipMemcpyAsync(dmeta3, meta3.data(), meta3.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHECK(hipMemcpyAsync(drows, r.n_rows, (size_t)r.n * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHECK(hipMemcpyAsync(dmetaS, metaS.data(), metaS.size() * sizeof(long long), hipMemcpyHostToDevice, s));
+    }
+}
+void ScoreStage::prepare(hipStream_t s, const unsigned char* sal, unsigned* counters) {
+    a.sal = sal; a.den = dd; a.fix = dx; a.counter = counters;
+    score_sequence(a, s);                                 // pass A once, for the columns and for the sweeps
+    sweeps.mark(0, s);
+    if (!sweep()) return;
+    q.sal = sal; q.tab = a.tab;
+    HIPCHECK(p3d_sweep_launch(SWEEP_PREP, q, s));
+}
+void ScoreStage::sweep_rest(hipStream_t s) {
+    if (r.borji) {
+        q.idx = didx; q.meta = dmetaB; q.per_rep = perB;
+        HIPCHECK(p3d_sweep_launch(SWEEP_RUN, q, s));
+    }
+    if (r.shuffled) {
+        const p3d_handle* h = r.pool;
+        if (totS) {
+            FixSelectArgs e;
+            e.uni = h->vu.uni; e.prefix = h->vu.prefix; e.bsum = h->vu.bsum; e.n_other = h->vu.n_other_dev; e.nw = h->fp_nw; e.B = r.n;
+            e.nsb = p3d_fix_scan_blocks(h->fp_nw); e.n_rep = r.n_rep; e.max_rows = max_rows; e.meta = dmeta3; e.n_rows = drows; e.ranks = dranks; e.out = dsel;
+            HIPCHECK(p3d_fix_select_launch(e, s));
+        }
+        ScoreSweepArgs qs = q;
+        qs.idx = dsel; qs.meta = dmetaS; qs.per_rep = perS;
+        HIPCHECK(p3d_sweep_launch(SWEEP_RUN, qs, s));
+    }
+    sweeps.mark(1, s);
+}
+void ScoreStage::results(hipStream_t s) {
+    if (r.flags) HIPCHECK(hipMemcpyAsync(r.out, a.out, ScoreSizes(a).out * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (!sweep()) return;
+    const SweepSizes w(q);
+    if (r.borji) HIPCHECK(hipMemcpyAsync(r.borji, perB, w.per_rep * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (r.shuffled) HIPCHECK(hipMemcpyAsync(r.shuffled, perS, w.per_rep * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (!nf.empty()) HIPCHECK(hipMemcpyAsync(info.data(), q.info, info.size() * sizeof(int), hipMemcpyDeviceToHost, s));      // (to hold against the host's)
+}
+void ScoreStage::check_counts() const {
+    for (size_t b = 0; b < nf.size(); ++b)
+        if (info[b * 4] != nf[b])
+            throw P3dError(std::string(r.who) + ": frame " + std::to_string(b) + ": the device counted " + std::to_string(info[b * 4]) + " fixated pixels, the host " +
+                           std::to_string(nf[b]));
+}
+// p3d_video_score and p3d_video_score_auc behind the checks of their arguments: the video's frames through the maps' chain, the
+// stage behind its bytes.  stage_ms (null, or n_ms = 3 or 4 values): uploads, the chain, the launches less the sweeps, the sweeps.
+void video_score_run(p3d_handle* h, int first, float scale, ScoreRequest r, unsigned char* maps_out, double* stage_ms, int n_ms) {
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    const VideoSource src(h, r.who, first, r.n, true, 65535);
+    r.timed = stage_ms != nullptr;
+    ScoreStage stage(r);
+    for (int i = 0; stage_ms && i < n_ms; ++i) stage_ms[i] = 0.0;
+    maps_u8_chain(h, r.n, h->pred->H, h->pred->W, scale, r.H, r.W, maps_out, nullptr, src.extra(), src, &stage);
+    if (stage_ms) {
+        const double sw = stage.sweep_ms();
+        stage_ms[0] = stage.ms[0]; stage_ms[1] = stage.ms[1]; stage_ms[2] = std::max(0.0, stage.ms[2] - sw);
+        if (n_ms > 3) stage_ms[3] = sw;
+    }
+    stage.check_counts();
+}
 }  // namespace
 extern "C" {
 
 int p3d_score_sweep_u8(int device, const unsigned char* sal, const unsigned char* fixation, int n, int H, int W, const int* idx,
                        const int* n_rows, int n_rep, double step, double* per_rep) {
     API_BEGIN
-    const long long N = (long long)H * W;
-    ScoreSweepArgs q = sweep_args("score_sweep_u8", n, N, n_rep, step);
-    size_t total = 0;
-    const std::vector<long long> meta = sweep_op_check("score_sweep_u8", sal, fixation, n, H, W, idx, n_rows, per_rep, n_rep, total);
+    const char* who = "score_sweep_u8";
+    sweep_args(who, n, (long long)H * W, n_rep, step);      // (the step and n_rep are refused first, as in the hook)
+    sweep_op_shape(who, sal, fixation, n, H, W, n_rows, per_rep);
+    ScoreRequest r{who, n, H, W};
+    r.fixation = fixation; r.idx = idx; r.idx_rows = n_rows; r.borji = per_rep; r.n_rep = n_rep; r.step = step;
+    ScoreStage stage(r);
     metric_args(device, sal, fixation, 1, 1, per_rep);
-    const size_t bytes = (size_t)n * (size_t)N;
-    DevArr<unsigned char> ds(bytes, sal), dx(bytes, fixation);
-    DevArr<int> didx(total, total ? idx : nullptr);
-    DevArr<long long> dmeta(meta.size(), meta.data());
-    ScoreArgs a = score_args(n, N, 0, P3D_SCORE_TIES_REFERENCE);
-    a.counter = carve_scratch(nullptr, (size_t)n * 2, [&](Carve& c) {
-        score_carve(c, a);
-        sweep_carve(c, q);
-        q.per_rep = c.take<double>((size_t)n * n_rep);
-    });
-    a.sal = ds.p; a.fix = dx.p;
-    q.sal = ds.p; q.tab = a.tab; q.idx = didx.p; q.meta = dmeta.p;
-    score_sequence(a, nullptr);
-    HIPCHECK(p3d_sweep_launch(SWEEP_PREP, q, nullptr));
+    DevArr<unsigned char> ds(stage.bytes, sal);
+    unsigned* const counters = carve_scratch(nullptr, stage.counters(), [&](Carve& c) { stage.carve(c); });
+    stage.upload(nullptr);
+    stage.prepare(nullptr, ds.p, counters);
     HIPCHECK(hipDeviceSynchronize());
-    std::vector<int> info((size_t)n * 4);
-    HIPCHECK(copy_now(info.data(), q.info, info.size() * sizeof(int), hipMemcpyDeviceToHost, nullptr));      // nf, read back once
-    sweep_check_rows("score_sweep_u8", info, n_rows, n);
-    HIPCHECK(p3d_sweep_launch(SWEEP_RUN, q, nullptr));
+    std::vector<int> info(SweepSizes(stage.q).info);
+    HIPCHECK(copy_now(info.data(), stage.q.info, info.size() * sizeof(int), hipMemcpyDeviceToHost, nullptr));      // nf, read back once
+    sweep_check_rows(who, info, n_rows, n);
+    stage.sweep_rest(nullptr);
+    stage.results(nullptr);
     HIPCHECK(hipDeviceSynchronize());
-    HIPCHECK(copy_now(per_rep, q.per_rep, (size_t)n * n_rep * sizeof(double), hipMemcpyDeviceToHost, nullptr));
     API_END
 }
 
@@ -1918,19 +2024,22 @@ int p3d_debug_score_sweep_u8(int device, const unsigned char* sal, const unsigne
     const long long N = (long long)H * W;
     ScoreSweepArgs q = sweep_args(who, n, N, n_rep, step);
     size_t total = 0;
-    const std::vector<long long> meta = sweep_op_check(who, sal, fixation, n, H, W, idx, n_rows, per_rep, n_rep, total);
+    sweep_op_shape(who, sal, fixation, n, H, W, n_rows, per_rep);
+    const std::vector<long long> meta = sweep_meta(who, n_rows, n, n_rep, total);
+    if (total > 0 && !idx) throw P3dError("null argument");
+    check_indices(idx, total, N, who);
     if (!lev_out || !top_out) throw P3dError("null argument");
     if (offset < 0 || offset > 15) throw P3dError(std::string(who) + ": offset in [0, 15]");
     metric_args(device, sal, fixation, 1, 1, per_rep);
     const size_t bytes = (size_t)n * (size_t)N;
     ScoreArgs a = score_args(n, N, 0, P3D_SCORE_TIES_REFERENCE);
+    const ScoreSizes sz(a);
+    const SweepSizes w(q);
     // as p3d_debug_score_u8: guards of 16 elements, the sources shifted off the boundary (no density map here)
     Guarded<unsigned char> ds(bytes, 16, (size_t)offset, sal), dx(bytes, 16, (size_t)(3 * offset % 16), fixation);
-    Guarded<unsigned> tab((size_t)n * P3D_SCORE_TAB_WORDS, 16, 0, nullptr), counter((size_t)n * 2, 16, 0, nullptr), lad((size_t)n * (q.kmax + 1), 16, 0, nullptr);
-    Guarded<double> lut((size_t)n * 1024, 16, 0, nullptr), part((size_t)n * a.nblk * 2, 16, 0, nullptr), dout((size_t)n * 5, 16, 0, nullptr),
-        dper((size_t)n * n_rep, 16, 0, nullptr);
-    Guarded<int> lev((size_t)n * 256, 16, 0, nullptr), dinfo((size_t)n * 4, 16, 0, nullptr), dtop((size_t)n * n_rep, 16, 0, nullptr),
-        didx(total, 16, 0, total ? idx : nullptr);
+    Guarded<unsigned> tab(sz.tab, 16, 0, nullptr), counter(sz.counters, 16, 0, nullptr), lad(w.lad, 16, 0, nullptr);
+    Guarded<double> lut(sz.lut, 16, 0, nullptr), part(sz.part, 16, 0, nullptr), dout(sz.out, 16, 0, nullptr), dper(w.per_rep, 16, 0, nullptr);
+    Guarded<int> lev(w.lev, 16, 0, nullptr), dinfo(w.info, 16, 0, nullptr), dtop(w.per_rep, 16, 0, nullptr), didx(total, 16, 0, total ? idx : nullptr);
     Guarded<long long> dmeta(meta.size(), 16, 0, meta.data());
     a.sal = ds.data(); a.fix = dx.data();
     a.tab = tab.data(); a.counter = counter.data(); a.lut = lut.data(); a.part = part.data(); a.out = dout.data();
@@ -1938,12 +2047,12 @@ int p3d_debug_score_sweep_u8(int device, const unsigned char* sal, const unsigne
     q.idx = didx.data(); q.meta = dmeta.data(); q.top = dtop.data(); q.per_rep = dper.data();
     score_sequence(a, nullptr);
     HIPCHECK(p3d_sweep_launch(SWEEP_PREP, q, nullptr));
-    std::vector<int> info((size_t)n * 4), levs((size_t)n * 256), tops((size_t)n * n_rep);
-    std::vector<double> per((size_t)n * n_rep);
+    std::vector<int> info(w.info), levs(w.lev), tops(w.per_rep);
+    std::vector<double> per(w.per_rep);
     dinfo.back(info.data(), who);
     sweep_check_rows(who, info, n_rows, n);
     HIPCHECK(p3d_sweep_launch(SWEEP_RUN, q, nullptr));
-    std::vector<unsigned> zero((size_t)n * 2, 1u);
+    std::vector<unsigned> zero(sz.counters, 1u);
     lev.back(levs.data(), who); dtop.back(tops.data(), who); dper.back(per.data(), who);
     tab.back(nullptr, who); lad.back(nullptr, who); dinfo.back(nullptr, who); dout.back(nullptr, who);
     counter.back(zero.data(), who);
@@ -1964,6 +2073,17 @@ int p3d_video_shuffled_begin(p3d_handle* h, int n, const int* ids, int M, uint32
     API_END
 }
 
+int p3d_video_score(p3d_handle* h, int first, int n, float scale, int H, int W, const unsigned char* density, const unsigned char* fixation,
+                    int flags, int ties, double* out, unsigned char* maps_out, double* stage_ms) {
+    API_BEGIN
+    if (!h) throw P3dError("null argument");
+    score_check("video_score", density, fixation, std::max(1, std::min(n, 65535)), H, W, flags, ties, out);
+    ScoreRequest r{"video_score", n, H, W};
+    r.flags = flags; r.ties = ties; r.density = density; r.fixation = fixation; r.out = out;
+    video_score_run(h, first, scale, r, maps_out, stage_ms, 3);
+    API_END
+}
+
 int p3d_video_score_auc(p3d_handle* h, int first, int n, float scale, int H, int W, const unsigned char* density, const unsigned char* fixation,
                         int flags, int ties, double* out, const int* borji_idx, const int* ranks, const int* n_rows, int n_rep, double step,
                         double* borji_per_rep, double* shuffled_per_rep, double* stage_ms) {
@@ -1979,127 +2099,11 @@ int p3d_video_score_auc(p3d_handle* h, int first, int n, float scale, int H, int
     if ((long long)H * W > P3D_SCORE_MAX_PIXELS) throw P3dError(std::string(who) + ": H * W exceeds 2^23");
     if ((borji || shuf) && !fixation) throw P3dError(std::string(who) + ": AUC-Borji and shuffled AUC need the fixation maps");
     if ((borji && !borji_per_rep) || (shuf && (!n_rows || !shuffled_per_rep))) throw P3dError("null argument");
-    HIPCHECK(hipSetDevice(h->cfg.device));
-    h->video_need_open(who);
-    h->video_range(who, first, n);
-    if (n > 65535) throw P3dError(std::string(who) + ": 1 .. 65535 maps");
-    const bool temporal = h->temporal_cfg.on();
-    if (temporal) h->video_temporal_check(who, first, n);
-    for (int f = first; f < first + n; ++f)
-        if (h->vid_count[(size_t)f] == 0) throw P3dError(std::string(who) + ": frame " + std::to_string(f) + " has no prediction yet (count 0)");
-    const long long phw = h->vid_hw(), N = (long long)H * W;
-    const size_t bytes = (size_t)n * (size_t)N;
-    ScoreArgs a = score_args(n, N, flags, flags ? ties : P3D_SCORE_TIES_REFERENCE);
-    ScoreSweepArgs q, qs;
-    std::vector<int> nf;
-    std::vector<long long> metaB, metaS;
-    std::vector<int> meta3;
-    size_t totB = 0, totS = 0;
-    int max_rows = 0;
-    if (borji || shuf) {
-        q = sweep_args(who, n, N, n_rep, step);
-        nf = host_n_fix(fixation, n, N);
-    }
-    if (borji) {
-        metaB = sweep_meta(who, nf.data(), n, n_rep, totB);
-        check_indices(borji_idx, totB, N, who);
-    }
-    if (shuf) {
-        h->fixpool_need_open(who);
-        if (!h->vu.begun) throw P3dError(std::string(who) + ": no union is held (p3d_video_shuffled_begin)");
-        if (h->fp_H != H || h->fp_W != W)
-            throw P3dError(std::string(who) + ": the fixation pool holds " + std::to_string(h->fp_H) + " x " + std::to_string(h->fp_W) + " maps, the call scores " +
-                           std::to_string(H) + " x " + std::to_string(W));
-        if (h->vu.n != n) throw P3dError(std::string(who) + ": the union was taken for " + std::to_string(h->vu.n) + " frames, the call scores " + std::to_string(n));
-        for (int b = 0; b < n; ++b)
-            if (n_rows[b] != (int)std::min<long long>(nf[(size_t)b], h->vu.n_other[(size_t)b]))
-                throw P3dError(std::string(who) + ": frame " + std::to_string(b) + ": n_rows = " + std::to_string(n_rows[b]) + ", but min(n_fix, n_other) = min(" +
-                               std::to_string(nf[(size_t)b]) + ", " + std::to_string(h->vu.n_other[(size_t)b]) + ")");
-        p3d_handle::shuffled_check_draws(who, ranks, n_rows, h->vu.n_other.data(), n, n_rep, step);
-        metaS = sweep_meta(who, n_rows, n, n_rep, totS);
-        meta3.assign((size_t)n * 3, 0);
-        for (int b = 0; b < n; ++b) { meta3[(size_t)b * 3 + 2] = (int)metaS[(size_t)b * 2 + 1]; max_rows = std::max(max_rows, n_rows[b]); }
-    }
-    if (stage_ms) stage_ms[0] = stage_ms[1] = stage_ms[2] = stage_ms[3] = 0.0;
-    unsigned char* dd = nullptr; unsigned char* dx = nullptr;
-    int* didx = nullptr; int* dranks = nullptr; int* dsel = nullptr; int* dmeta3 = nullptr; int* drows = nullptr;
-    long long* dmetaB = nullptr; long long* dmetaS = nullptr;
-    double* perB = nullptr; double* perS = nullptr;
-    std::vector<int> info((size_t)n * 4, 0);
-    double ms3[3] = {0.0, 0.0, 0.0};
-    StageTimer sweeps(stage_ms != nullptr, 2);
-    U8Consumer use;
-    use.counters = (size_t)n * 2;
-    use.ms = stage_ms ? ms3 : nullptr;
-    use.carve = [&](Carve& c) {
-        dd = density && flags ? c.take<unsigned char>(bytes) : nullptr;
-        dx = fixation ? c.take<unsigned char>(bytes) : nullptr;
-        score_carve(c, a);
-        if (!borji && !shuf) return;
-        sweep_carve(c, q);
-        if (borji) { didx = c.take<int>(totB); dmetaB = c.take<long long>(metaB.size()); perB = c.take<double>((size_t)n * n_rep); }
-        if (shuf) {
-            dranks = c.take<int>(totS); dsel = c.take<int>(totS); dmeta3 = c.take<int>(meta3.size()); drows = c.take<int>((size_t)n);
-            dmetaS = c.take<long long>(metaS.size()); perS = c.take<double>((size_t)n * n_rep);
-        }
-    };
-    use.before = [&](hipStream_t s) {
-        if (dd) HIPCHECK(hipMemcpyAsync(dd, density, bytes, hipMemcpyHostToDevice, s));
-        if (dx) HIPCHECK(hipMemcpyAsync(dx, fixation, bytes, hipMemcpyHostToDevice, s));
-        if (borji) {
-            if (totB) HIPCHECK(hipMemcpyAsync(didx, borji_idx, totB * sizeof(int), hipMemcpyHostToDevice, s));
-            HIPCHECK(hipMemcpyAsync(dmetaB, metaB.data(), metaB.size() * sizeof(long long), hipMemcpyHostToDevice, s));
-        }
-        if (shuf) {
-            if (totS) HIPCHECK(hipMemcpyAsync(dranks, ranks, totS * sizeof(int), hipMemcpyHostToDevice, s));
-            HIPCHECK(hipMemcpyAsync(dmeta3, meta3.data(), meta3.size() * sizeof(int), hipMemcpyHostToDevice, s));
-            HIPCHECK(hipMemcpyAsync(drows, n_rows, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
-            HIPCHECK(hipMemcpyAsync(dmetaS, metaS.data(), metaS.size() * sizeof(long long), hipMemcpyHostToDevice, s));
-        }
-    };
-    use.after = [&](hipStream_t s, const unsigned char* d, unsigned* counters) {
-        a.sal = d; a.den = dd; a.fix = dx; a.counter = counters;
-        score_sequence(a, s);                                 // pass A once, for the columns and for the sweeps
-        sweeps.mark(0, s);
-        if (borji || shuf) {
-            q.sal = d; q.tab = a.tab;
-            HIPCHECK(p3d_sweep_launch(SWEEP_PREP, q, s));
-        }
-        if (borji) {
-            q.idx = didx; q.meta = dmetaB; q.per_rep = perB;
-            HIPCHECK(p3d_sweep_launch(SWEEP_RUN, q, s));
-        }
-        if (shuf) {
-            if (totS) {
-                FixSelectArgs e;
-                e.uni = h->vu.uni; e.prefix = h->vu.prefix; e.bsum = h->vu.bsum; e.n_other = h->vu.n_other_dev; e.nw = h->fp_nw; e.B = n;
-                e.nsb = p3d_fix_scan_blocks(h->fp_nw); e.n_rep = n_rep; e.max_rows = max_rows; e.meta = dmeta3; e.n_rows = drows; e.ranks = dranks; e.out = dsel;
-                HIPCHECK(p3d_fix_select_launch(e, s));
-            }
-            qs = q;
-            qs.idx = dsel; qs.meta = dmetaS; qs.per_rep = perS;
-            HIPCHECK(p3d_sweep_launch(SWEEP_RUN, qs, s));
-        }
-        sweeps.mark(1, s);
-    };
-    use.results = [&](hipStream_t s) {
-        if (flags) HIPCHECK(hipMemcpyAsync(out, a.out, (size_t)n * 5 * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (borji) HIPCHECK(hipMemcpyAsync(borji_per_rep, perB, (size_t)n * n_rep * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (shuf) HIPCHECK(hipMemcpyAsync(shuffled_per_rep, perS, (size_t)n * n_rep * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (borji || shuf) HIPCHECK(hipMemcpyAsync(info.data(), q.info, info.size() * sizeof(int), hipMemcpyDeviceToHost, s));
-    };
-    maps_u8_chain(h, n, h->pred->H, h->pred->W, scale, H, W, nullptr, nullptr, temporal || h->vid_mode == VIDEO_MEAN ? (size_t)n * (size_t)phw : 0,
-                  [&](hipStream_t s, float* scratch, std::vector<PostRun>& runs) {
-                      runs.push_back({temporal ? h->video_temporal(who, first, n, scratch, s) : h->video_finalize(who, first, n, scratch, s), phw, 1, n});
-                  }, &use);
-    if (stage_ms) {
-        stage_ms[3] = (double)sweeps.ms(0);
-        stage_ms[0] = ms3[0]; stage_ms[1] = ms3[1]; stage_ms[2] = std::max(0.0, ms3[2] - stage_ms[3]);
-    }
-    for (int b = 0; (borji || shuf) && b < n; ++b)
-        if (info[(size_t)b * 4] != nf[(size_t)b])
-            throw P3dError(std::string(who) + ": frame " + std::to_string(b) + ": the device counted " + std::to_string(info[(size_t)b * 4]) + " fixated pixels, the host " +
-                           std::to_string(nf[(size_t)b]));
+    ScoreRequest r{who, n, H, W};
+    r.flags = flags; r.ties = ties; r.density = density; r.fixation = fixation; r.out = out; r.n_rep = n_rep; r.step = step;
+    if (borji) { r.idx = borji_idx; r.borji = borji_per_rep; }
+    if (shuf) { r.ranks = ranks; r.n_rows = n_rows; r.pool = h; r.shuffled = shuffled_per_rep; }
+    video_score_run(h, first, scale, r, nullptr, stage_ms, 4);
     API_END
 }
 

@@ -1192,11 +1192,14 @@
     }
     // frames first .. first + n - 1 as the read-out returns them: the map store itself under NEWEST; under MEAN `scratch`
     // ([n][hw], not the store) after the division launches queued here.  Refuses a frame with count 0.
+    void video_need_predicted(const char* who, int first, int n) const {
+        for (int f = first; f < first + n; ++f)
+            if (vid_count[(size_t)f] == 0) throw P3dError(std::string(who) + ": frame " + std::to_string(f) + " has no prediction yet (count 0)");
+    }
     const float* video_finalize(const char* who, int first, int n, float* scratch, hipStream_t s) {
         video_need_open(who);
         video_range(who, first, n);
-        for (int f = first; f < first + n; ++f)
-            if (vid_count[(size_t)f] == 0) throw P3dError(std::string(who) + ": frame " + std::to_string(f) + " has no prediction yet (count 0)");
+        video_need_predicted(who, first, n);
         if (vid_mode == VIDEO_NEWEST) return vid_maps + (int64_t)first * vid_hw();
         for (int done = 0; done < n; done += 32768) {
             VideoMeanArgs a;

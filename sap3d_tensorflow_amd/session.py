@@ -52,6 +52,23 @@ def adam_step_from_powers(beta1_power, beta2_power, beta1=0.9, beta2=0.999):
     return t
 
 
+def _ptr(a, t):
+    return None if a is None else a.ctypes.data_as(t)
+
+
+def _score_inputs(n, size, *maps):
+    """What video_score and video_score_auc check of their maps before the library sees them: each is None or uint8 [n, H, W]
+    (the shape only at a size the library takes: it refuses the rest) -> n, H, W, whether the size is one, the maps contiguous."""
+    H, W = (size, size) if np.isscalar(size) else tuple(size)
+    n = max(int(n), 0)
+    valid = H >= 1 and W >= 1 and H * W <= 2 ** 23
+    maps = [None if a is None else np.ascontiguousarray(a) for a in maps]
+    for a in maps:
+        if a is not None and (a.dtype != np.uint8 or (valid and a.shape != (n, H, W))):
+            raise ValueError("density and fixation maps are uint8 [%d, %d, %d]" % (n, H, W))
+    return n, int(H), int(W), valid, maps
+
+
 class P3DSession:
     """sess = P3DSession(batch=2)  ~  building the graph + tf.Session() in train.py:143-201."""
 
@@ -909,21 +926,12 @@ class P3DSession:
         default jitter does to an 8-bit map).  fixation may be None when neither judd nor nss is asked for.  with_maps: also the
         scored bytes, uint8 [n, H, W].  Device times are left in `last_score_ms`.  include/p3d_hip.h holds the exact rules."""
         from . import metrics
-        H, W = (size, size) if np.isscalar(size) else tuple(size)
-        n = max(int(n), 0)
-        valid = H >= 1 and W >= 1 and H * W <= 2 ** 23
-        dens = np.ascontiguousarray(density)
-        fix = None if fixation is None else np.ascontiguousarray(fixation)
-        for a in (dens,) + (() if fix is None else (fix,)):
-            if a.dtype != np.uint8 or (valid and a.shape != (n, H, W)):
-                raise ValueError("density and fixation maps are uint8 [%d, %d, %d]" % (n, H, W))
+        n, H, W, valid, (dens, fix) = _score_inputs(n, size, np.ascontiguousarray(density), fixation)
         out = np.full((n, 5), np.nan, np.float64)
         maps = np.empty((n, H, W) if valid else (0,), np.uint8) if with_maps else None
         ms = (C.c_double * 3)()
-        check(lib().p3d_video_score(self._h, int(first), n, float(scale), int(H), int(W), dens.ctypes.data_as(_lib._u8p),
-                                    None if fix is None else fix.ctypes.data_as(_lib._u8p), metrics.score_flags(columns),
-                                    metrics.score_ties(ties), out.ctypes.data_as(_lib._dp),
-                                    None if maps is None else maps.ctypes.data_as(_lib._u8p), ms))
+        check(lib().p3d_video_score(self._h, int(first), n, float(scale), H, W, _ptr(dens, _lib._u8p), _ptr(fix, _lib._u8p),
+                                    metrics.score_flags(columns), metrics.score_ties(ties), _ptr(out, _lib._dp), _ptr(maps, _lib._u8p), ms))
         self.last_score_ms = dict(upload=ms[0], device=ms[1], score=ms[2])
         return (out, maps) if with_maps else out
 
@@ -948,15 +956,8 @@ class P3DSession:
         -> dict(scores float64 [n, 5], borji [n, n_rep], shuffled [n, n_rep]; NaN where not asked).  Device times are left in
         `last_score_ms`: upload, device (the maps' chain), score (the five columns), auc (preparation, select and sweeps)."""
         from . import metrics
-        H, W = (size, size) if np.isscalar(size) else tuple(size)
-        n = max(int(n), 0)
-        valid = H >= 1 and W >= 1 and H * W <= 2 ** 23
+        n, H, W, _, (dens, fix) = _score_inputs(n, size, density, fixation)
         flags = metrics.score_flags(columns if columns is not None else ())
-        dens = None if density is None else np.ascontiguousarray(density)
-        fix = None if fixation is None else np.ascontiguousarray(fixation)
-        for a in (dens, fix):
-            if a is not None and (a.dtype != np.uint8 or (valid and a.shape != (n, H, W))):
-                raise ValueError("density and fixation maps are uint8 [%d, %d, %d]" % (n, H, W))
         n_rep = int(n_rep)
         res = dict(scores=np.full((n, 5), np.nan, np.float64), borji=np.full((n, max(n_rep, 0)), np.nan, np.float64),
                    shuffled=np.full((n, max(n_rep, 0)), np.nan, np.float64))
@@ -969,13 +970,12 @@ class P3DSession:
         nr = None if n_rows is None else np.ascontiguousarray(n_rows, dtype=np.int32).ravel()
         if rk is not None and (nr is None or nr.size != n):
             raise ValueError("n_rows is int [%d], the rows of shuffled_ranks per frame" % n)
-        ptr = lambda a, t: None if a is None else a.ctypes.data_as(t)
         ms = (C.c_double * 4)()
-        check(lib().p3d_video_score_auc(self._h, int(first), n, float(scale), int(H), int(W), ptr(dens, _lib._u8p), ptr(fix, _lib._u8p), flags,
-                                        metrics.score_ties(ties), ptr(res["scores"], _lib._dp) if flags else None, ptr(bi, _lib._ip),
-                                        ptr(rk, _lib._ip), ptr(nr, _lib._ip), n_rep, float(step_size),
-                                        ptr(res["borji"], _lib._dp) if bi is not None else None,
-                                        ptr(res["shuffled"], _lib._dp) if rk is not None else None, ms))
+        check(lib().p3d_video_score_auc(self._h, int(first), n, float(scale), H, W, _ptr(dens, _lib._u8p), _ptr(fix, _lib._u8p), flags,
+                                        metrics.score_ties(ties), _ptr(res["scores"] if flags else None, _lib._dp), _ptr(bi, _lib._ip),
+                                        _ptr(rk, _lib._ip), _ptr(nr, _lib._ip), n_rep, float(step_size),
+                                        _ptr(res["borji"] if bi is not None else None, _lib._dp),
+                                        _ptr(res["shuffled"] if rk is not None else None, _lib._dp), ms))
         self.last_score_ms = dict(upload=ms[0], device=ms[1], score=ms[2], auc=ms[3])
         return res
 
