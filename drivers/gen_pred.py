@@ -27,7 +27,9 @@ mean of every window that predicted it.  A stride other than 1 and `--overlap me
 (an addition, implies `--resident`) smooths the maps along the frame axis on the device as they are read
 (P3DSession.set_video_temporal): a Gaussian of `--temporal-sigma` frames (radius `--temporal-radius`, at most 24; 0: cv2's rule)
 with reflected ends, or the causal moving average m_f = A m_{f-1} + (1 - A) v_f of `--temporal-alpha`; npy files then hold the
-filtered maps, png / jpg the images of the filtered maps."""
+filtered maps, png / jpg the images of the filtered maps.  `--render DIR` (an addition, needs `--resident`) also keeps the
+decoded frames on the device and writes DIR/<video>/frame_<k>.png: every frame at its own size with its 8-bit map laid over it
+on the device (P3DSession.video_render), whatever `--write` and `--truth` do beside it."""
 import argparse
 import glob
 import os
@@ -93,14 +95,16 @@ def window_starts(F, stride):
 PUT_CHUNK = 64      # frames per upload of the resident path
 
 
-def predict_video_resident(sess, video_u8, batch, stride=1, overlap="newest", times=None):
+def predict_video_resident(sess, video_u8, batch, stride=1, overlap="newest", times=None, keep_source=False):
     """video_u8 [F,H0,W0,3] uint8 RGB -> the open video on the device, every window predicted (P3DSession.open_video /
     video_put_u8 / video_predict); read it with sess.video_maps / video_maps_u8.  times (a dict or None) collects the HIP-event
-    milliseconds of the window cuts and map folds."""
+    milliseconds of the window cuts and map folds.  keep_source: the decoded frames stay on the device too, for video_render."""
     F = len(video_u8)
     if F < 16:
         raise ValueError("need at least 16 frames")
     sess.open_video(F, overlap)
+    if keep_source:
+        sess.video_keep_source(True)
     for i in range(0, F, PUT_CHUNK):
         sess.video_put_u8(i, video_u8[i:i + PUT_CHUNK, ..., ::-1])       # the kernel takes cv2's BGR order
     starts = window_starts(F, stride)
@@ -146,6 +150,37 @@ def write_video_images_resident(sess, F, video_dir, ext, size=(1080, 960), write
             t["device"] += sess.last_maps_ms["device"]
             t["d2h"] += sess.last_maps_ms["d2h"]
             held = hand_over(pool, held, write, first, maps)
+            t["files"] += n
+        hand_over(pool, held, write, F, ())
+    return t
+
+
+def render_video_resident(sess, F, video_dir, render, writers=4):
+    """--render: the open video's frames with their maps laid over them (P3DSession.video_render on the kept source, at the
+    video's own size), 16 at a time while the previous 16 are encoded -> <video_dir>/frame_<k>.png, k = 1..F, colour.  render:
+    the keyword arguments of video_render.  Returns milliseconds: gpu (wall time of the calls), the three device stages, encode
+    (thread time), and the number of files."""
+    import threading
+    from concurrent.futures import ThreadPoolExecutor
+    t = dict(gpu=0.0, upload=0.0, device=0.0, render=0.0, encode=0.0, files=0)
+    lock = threading.Lock()
+
+    def write(f, m):
+        t0 = time.perf_counter()
+        save_color_image(os.path.join(video_dir, "frame_%d.png" % (f + 1)), m)
+        with lock:
+            t["encode"] += (time.perf_counter() - t0) * 1e3
+
+    held = []
+    with ThreadPoolExecutor(max_workers=writers) as pool:
+        for first in range(0, F, 16):
+            n = min(16, F - first)
+            t0 = time.perf_counter()
+            images = sess.video_render(first, n, timed=True, **render)
+            t["gpu"] += (time.perf_counter() - t0) * 1e3
+            for k in ("upload", "device", "render"):
+                t[k] += sess.last_render_ms[k]
+            held = hand_over(pool, held, write, first, images)
             t["files"] += n
         hand_over(pool, held, write, F, ())
     return t
@@ -270,6 +305,14 @@ def save_image(path, m, ext):
         Image.fromarray(m).save(path, format="JPEG", quality=95)
 
 
+def save_color_image(path, bgr):
+    """One rendered frame [H, W, 3] uint8 in B, G, R order as a colour PNG (compress_level 1, lossless)."""
+    from PIL import Image
+    if bgr.dtype != np.uint8 or bgr.ndim != 3 or bgr.shape[2] != 3:
+        raise ValueError("expected a [H, W, 3] uint8 image")
+    Image.fromarray(np.ascontiguousarray(bgr[..., ::-1])).save(path, format="PNG", compress_level=1)
+
+
 def write_video_images(sess, frames, batch, video_dir, ext, size=(1080, 960), writers=4):
     """<video_dir>/frame_<k>.<ext>, k = 1..F (gen_pred.py:159,165).  A batch's files are encoded on a pool of `writers`
     threads (PIL releases the GIL while it compresses) while the device runs the next batch; at most two batches of maps are
@@ -376,6 +419,18 @@ def parse_args(argv=None):
                    "at most 1024 thresholds")
     p.add_argument("--score-seed", type=int, default=0, metavar="N", help="[addition] --score-borji / --score-sauc: the seed of every video's "
                    "numpy RandomState, which makes all draws")
+    p.add_argument("--render", type=str, default="", metavar="DIR", help="[addition] needs --resident: keep every video's decoded frames on "
+                   "the device and write DIR/<video>/frame_<k>.png, the frame at its own size with its 8-bit map laid over it, colour-"
+                   "mapped and blended on the device (every read-out setting the maps follow applies)")
+    p.add_argument("--render-colormap", choices=("grey", "hot", "jet"), default="jet", help="[addition] --render: the colour of a level")
+    p.add_argument("--render-alpha", type=float, default=0.6, metavar="A", help="[addition] --render: the overlay's weight in [0, 1]")
+    p.add_argument("--render-opacity", choices=("ramp", "constant"), default="ramp", help="[addition] --render: a level's opacity, "
+                   "A * level / 255 or A at every level")
+    p.add_argument("--render-gate", type=int, default=0, metavar="LEVEL", help="[addition] --render: levels below it are transparent")
+    p.add_argument("--render-contour", type=int, default=0, metavar="LEVEL", help="[addition] --render: draw the iso-line of this level, "
+                   "1 .. 255 (0: none)")
+    p.add_argument("--render-thickness", type=int, default=1, metavar="T", help="[addition] --render-contour: the line's width, 1 .. 4 pixels")
+    p.add_argument("--render-contour-color", type=str, default="255,255,255", metavar="R,G,B", help="[addition] --render-contour: the line's colour")
     p.add_argument("--base", type=int, default=64, help=argparse.SUPPRESS)
     p.add_argument("--blocks", type=str, default="3,8,36", help=argparse.SUPPRESS)
     p.add_argument("--time", action="store_true", help="print per-video wall times (png / jpg: also the device stage and the host encode)")
@@ -412,7 +467,38 @@ def parse_args(argv=None):
         p.error("--match-hist density needs a ground truth: it belongs to drivers/test.py; here it takes FILE.npz")
     if not 2 <= args.match_bins <= 1024:
         p.error("--match-bins must be in 2..1024")
+    render_args(args, p.error)
     return args
+
+
+def render_args(args, error):
+    """Checks --render and its values as P3DSession.video_render would refuse them, before anything runs; error(message) does not
+    return.  Leaves the keyword arguments of video_render in args.render_kw (None without --render)."""
+    args.render_kw = None
+    shaped = (args.render_colormap != "jet" or args.render_alpha != 0.6 or args.render_opacity != "ramp" or args.render_gate != 0 or
+              args.render_contour != 0 or args.render_thickness != 1 or args.render_contour_color != "255,255,255")
+    if not args.render:
+        if shaped:
+            error("--render-colormap / -alpha / -opacity / -gate / -contour / -thickness / -contour-color need --render DIR")
+        return
+    if not args.resident:
+        error("--render needs --resident: the frames and the maps stay on the device")
+    try:
+        color = tuple(int(v) for v in args.render_contour_color.split(","))
+    except ValueError:
+        color = ()
+    if len(color) != 3 or min(color) < 0 or max(color) > 255:
+        error("--render-contour-color is R,G,B, three bytes")
+    if not 0. <= args.render_alpha <= 1.:
+        error("--render-alpha is in [0, 1]")
+    if not 0 <= args.render_gate <= 256:
+        error("--render-gate is a level, 0 .. 256")
+    if not 0 <= args.render_contour <= 255:
+        error("--render-contour is a level, 1 .. 255 (0: none)")
+    if not 1 <= args.render_thickness <= 4:
+        error("--render-thickness is 1 .. 4")
+    args.render_kw = dict(colormap=args.render_colormap, alpha=args.render_alpha, opacity=args.render_opacity, gate=args.render_gate,
+                          contour=args.render_contour or None, thickness=args.render_thickness, contour_color=color)
 
 
 TEMPORAL_MAX_RADIUS = 24
@@ -524,9 +610,12 @@ def run_resident(sess, args, path):
             print(name, "skipped: %s exists" % video_dir)
             return
         os.mkdir(video_dir)
+    render_dir = os.path.join(args.render, name) if args.render else None
+    if render_dir:
+        os.makedirs(render_dir, exist_ok=True)
     t0 = time.perf_counter()
     times = {}
-    F = predict_video_resident(sess, np.load(path), args.batch, args.stride, args.overlap, times)
+    F = predict_video_resident(sess, np.load(path), args.batch, args.stride, args.overlap, times, keep_source=bool(render_dir))
     t1 = time.perf_counter()
     means = ts = None
     if args.truth:
@@ -568,6 +657,10 @@ def run_resident(sess, args, path):
     else:
         t = write_video_images_resident(sess, F, video_dir, args.write, size=tuple(args.size), writers=args.writers)
         print(name, "%d %s files in %s" % (t["files"], args.write, video_dir))
+    tr = None
+    if render_dir:
+        tr = render_video_resident(sess, F, render_dir, args.render_kw, writers=args.writers)
+        print(name, "%d rendered png files in %s" % (tr["files"], render_dir))
     temporal_ms = sess.video_temporal_last_ms() if args.temporal != "off" and args.time else None
     sess.close_video()
     if args.time:
@@ -583,6 +676,9 @@ def run_resident(sess, args, path):
         if args.write != "npy" and ts is None:
             print("  %s: maps %.1f ms (device resize/quantise %.2f ms, d2h %.2f ms) | encode %.1f ms thread time on %d writers"
                   % (name, t["gpu"], t["device"], t["d2h"], t["encode"], args.writers))
+        if tr is not None:
+            print("  %s: render %.1f ms (uploads %.2f ms, maps %.2f ms, render launches %.3f ms on the device) | encode %.1f ms thread "
+                  "time on %d writers" % (name, tr["gpu"], tr["upload"], tr["device"], tr["render"], tr["encode"], args.writers))
     return means
 
 

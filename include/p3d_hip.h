@@ -1211,7 +1211,8 @@ int p3d_debug_eval_maps_shuffled(int device, const float* maps, int n_maps, int 
  * p3d_video_put_frames     copies n normalised frames x [n][H][W][3] to frames first .. first + n - 1.
  * p3d_video_put_frames_u8  uploads n decoded frames bgr [n][H0][W0][3] and normalises them straight into the store: the stored
  *                  floats are, bit for bit, what p3d_mapf_frames returns for those frames.  Frames may arrive in any order and in
- *                  several calls; a range outside [0, F) is refused.
+ *                  several calls; a range outside [0, F) is refused.  (p3d_video_keep_source, "Rendering 8-bit maps" below, also
+ *                  keeps the bytes; off, this call issues what it always issued.)
  * p3d_video_predict  n_windows in 1 .. B; starts strictly ascending, every start greater than last_start and inside [0, F - T], and
  *                  every frame of every window put.  Anything else: -1, p3d_last_error names the first offending window or
  *                  frame, nothing is launched and nothing changes.  Then:
@@ -1521,6 +1522,61 @@ int p3d_video_score_auc(p3d_handle* h, int first, int n, float scale, int H, int
                         const unsigned char* fixation, int flags, int ties, double* out /* may be NULL */,
                         const int* borji_idx /* may be NULL */, const int* ranks /* may be NULL */, const int* n_rows, int n_rep,
                         double step, double* borji_per_rep, double* shuffled_per_rep, double* stage_ms /* may be NULL */);
+
+/* ---- Rendering 8-bit maps over their frames (an ADDITION: the arithmetic of what the reference's gen_video.py is for -- a written
+ * map laid over the frame it belongs to, colour-mapped, with an iso-line round the salient region; encoding a video container is
+ * not part of this library).  OFF until called: every other entry point issues what it issued before and returns the same bits.
+ * PARITY UNPINNED: cv2 is not part of the build and the reference has no overlay; this text is the contract and tests/render_ref.py
+ * replays it in numpy.  Everything is integer arithmetic, no floating point: no order can show, and every test holds to 0.
+ * Per frame: s [H][W] bytes, the saliency map; frame [H][W][3] bytes in cv2's B, G, R order, or absent; table [256], one uint32_t
+ * per level v packed b | g << 8 | r << 16 | o << 24, o that level's opacity in 0 .. 255; a contour: level L in 0 .. 255 (0: off),
+ * thickness t in 1 .. 4, a colour of three bytes (B, G, R).  -> out [H][W][3] bytes.
+ *   BLEND    (b, g, r, o) = table[s], c = (b, g, r); per channel k: out_k = (frame_k * (255 - o) + c_k * o + 127) / 255, integer
+ *            division; the largest numerator is 65152.  255 is odd, so no tie exists: this is round-to-nearest of the real blend,
+ *            floor(x / 255 + 0.5); o = 255 returns the colour, o = 0 the frame.
+ *   Without a frame  out_k = c_k, o is ignored: a plain heat map.
+ *   CONTOUR  when L > 0, with a(y, x) = (s(y, x) >= L): a pixel is on the contour exactly when a(y, x) holds and some pixel
+ *            (y', x') INSIDE THE MAP with |y' - y| <= t and |x' - x| <= t has a false.  Nothing outside the map counts: a region
+ *            that runs into the border gets no line along the border, a map entirely at or above L gets no contour.  A contour
+ *            pixel's three bytes are the contour colour; it replaces the blend.
+ *   LIMITS   1 <= n <= 65535 maps a call; H, W >= 1; H * W <= 2^28 (3 H W fits int32 inside a map; bases between maps are 64-bit).
+ * p3d_render_u8      op level, host arrays: sal [n][H][W], frames [n][H][W][3] or NULL (the heat map), -> out [n][H][W][3].
+ * p3d_video_keep_source  legal only while a video is open and before the first p3d_video_put_frames_u8 since the open; anything
+ *                    else is refused and changes nothing.  Every p3d_video_open starts with it off.  On: the first
+ *                    p3d_video_put_frames_u8 fixes (H0, W0) and allocates a byte store [F][H0][W0][3] (refused, nothing changed,
+ *                    if the device cannot hold it); a later put of another size is refused.  The upload lands in the store and
+ *                    the normalising launch reads it there, so the stored floats stay, bit for bit, p3d_mapf_frames's.  Frames put
+ *                    as floats (p3d_video_put_frames) have no source.  Off: nothing is allocated and the put issues what it issued
+ *                    before.
+ * p3d_video_source_info  whether the store is on, its frame size (0, 0 until the first put fixes it) and the bytes it holds.
+ * p3d_video_render   renders frames first .. first + n - 1 of the open video at H x W.  The saliency bytes are, bit for bit, what
+ *                    p3d_video_maps_u8(first, n, scale, H, W) returns under the handle's current settings; maps_out (or NULL)
+ *                    receives them.  frames: host [n][H][W][3], uploaded as p3d_video_score uploads its truth, or NULL for the
+ *                    kept source -- then H = H0 and W = W0 are required and every frame of the range must have a source (the
+ *                    refusal names the first without one).  The heat map without frames exists at op level only.  Validated as
+ *                    p3d_video_maps_u8 validates, plus cfg (L in 0 .. 255; with L > 0, t in 1 .. 4) and LIMITS, all before any
+ *                    launch, upload or scratch request: a refusal changes nothing.  stage_ms (or NULL) [3]: HIP-event milliseconds
+ *                    of the frames' upload (0 with the kept source; the table's 1 KB is not counted), of the maps' chain, of the
+ *                    render launch.  Returns synchronised.
+ * TEST HOOKS (tests/test_gpu_render.py):
+ * p3d_debug_render_u8  the same launch description with every device buffer between guards: sal starts `offset` bytes (0 .. 15)
+ *                    past a 16-byte boundary, frames (3 offset) mod 16 and out (5 offset) mod 16 bytes past one, so that offsets 0
+ *                    and 8 align the three alike (frame and out bytes of pixel p start at 3 p) and any other offset does not;
+ *                    -1 if a guard or an input changed.
+ * p3d_debug_render_plan  host only, no HIP call: the block shape of the launch for n maps of H x W with a contour of that thickness
+ *                    (0: none).  cols_per_block = 0 (and rows_per_block = 0): the blocks are flat runs of pixels_per_block pixels;
+ *                    otherwise tiles of rows_per_block x cols_per_block pixels whose first tile starts at (0, 0). */
+typedef struct { uint32_t table[256]; int contour_level, contour_thickness; unsigned char contour_bgr[3]; } p3d_render;
+int p3d_render_u8(int device, const unsigned char* sal, const unsigned char* frames /* may be NULL */, int n, int H, int W,
+                  const p3d_render* cfg, unsigned char* out);
+int p3d_video_keep_source(p3d_handle* h, int on);
+int p3d_video_source_info(p3d_handle* h, int* on, int* H0, int* W0, int64_t* bytes);
+int p3d_video_render(p3d_handle* h, int first, int n, float scale, int H, int W, const unsigned char* frames /* NULL: kept source */,
+                     const p3d_render* cfg, unsigned char* out, unsigned char* maps_out /* may be NULL */, double* stage_ms /* may be NULL */);
+int p3d_debug_render_u8(int device, const unsigned char* sal, const unsigned char* frames, int n, int H, int W, const p3d_render* cfg,
+                        int offset, unsigned char* out);
+int p3d_debug_render_plan(int H, int W, int n, int contour_thickness /* 0: no contour */, int offset,
+                          int* rows_per_block, int* cols_per_block, int64_t* pixels_per_block);
 
 /* CRC-32C of a host buffer (host-side helper of the TensorFlow checkpoint reader / writer, sap3d_tensorflow_amd/tf_checkpoint.py:
  * the bundle format of train.py:180-185,266-267 checksums every tensor); crc = running value, 0 to start. */

@@ -44,6 +44,11 @@ class P3dPostprocess(C.Structure):
     _fields_ = [("sigma", C.c_float), ("radius", C.c_int), ("norm", C.c_int)]
 
 
+class P3dRender(C.Structure):
+    """p3d_render: table[v] = b | g << 8 | r << 16 | o << 24; contour level 0 is off."""
+    _fields_ = [("table", C.c_uint32 * 256), ("contour_level", C.c_int), ("contour_thickness", C.c_int), ("contour_bgr", C.c_ubyte * 3)]
+
+
 class P3dVideoTemporal(C.Structure):
     _fields_ = [("kind", C.c_int), ("sigma", C.c_float), ("radius", C.c_int), ("alpha", C.c_float)]
 
@@ -71,6 +76,9 @@ SCORE_MATLAB = ("cc", "sim", "judd")
 SCORE_TIES = {"reference": 0, "expected": 1}
 TRAINSET_FORMATS = {"u8": 0, "f32": 1}
 P3D_TRAINSET_FIXATIONS = 1
+# dataflow.render_table: this project's own colour maps and the two opacity laws
+RENDER_COLORMAPS = ("grey", "hot", "jet")
+RENDER_OPACITIES = ("constant", "ramp")
 # p3d_set_video_temporal kinds (include/p3d_hip.h P3D_TEMPORAL_*)
 TEMPORAL_KINDS = {"off": 0, "gauss": 1, "ema": 2}
 P3D_TEMPORAL_MAX_RADIUS = 24
@@ -387,6 +395,12 @@ SIGNATURES = {
     "p3d_video_shuffled_begin": (C.c_int, [C.c_void_p, C.c_int, _ip, C.c_int, C.POINTER(C.c_uint32)]),
     "p3d_video_score_auc": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, _u8p, _u8p, C.c_int, C.c_int, _dp, _ip, _ip, _ip,
                                       C.c_int, C.c_double, _dp, _dp, _dp]),
+    "p3d_render_u8": (C.c_int, [C.c_int, _u8p, _u8p, C.c_int, C.c_int, C.c_int, C.POINTER(P3dRender), _u8p]),
+    "p3d_video_keep_source": (C.c_int, [C.c_void_p, C.c_int]),
+    "p3d_video_source_info": (C.c_int, [C.c_void_p, _ip, _ip, _ip, _i64p]),
+    "p3d_video_render": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, _u8p, C.POINTER(P3dRender), _u8p, _u8p, _dp]),
+    "p3d_debug_render_u8": (C.c_int, [C.c_int, _u8p, _u8p, C.c_int, C.c_int, C.c_int, C.POINTER(P3dRender), C.c_int, _u8p]),
+    "p3d_debug_render_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _i64p]),
     "p3d_crc32c": (C.c_uint32, [C.c_void_p, C.c_size_t, C.c_uint32]),
     "p3d_shutdown": (C.c_int, []),
 }

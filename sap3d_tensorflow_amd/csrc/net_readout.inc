@@ -723,6 +723,8 @@ namespace {
 // with the bytes and counters() zeroed arrival counters of its own, its results (the copies back to the host) behind that; out may
 // then be NULL (the bytes stay on the device) and, timed, its ms [3] receives the times of the upload, of the device stage and of
 // the launches.  Without one, nothing here differs from what the two callers issued before.
+// A render stage (p3d_video_render) is a second consumer of the same kind and follows the score stage at each of the four moments;
+// it has no counters.  Without one, nothing here differs from what the callers issued before it existed.
 // What one scoring of n maps of H x W bytes asks for; every pointer is host memory.  Whatever is not asked for is not issued.
 struct ScoreRequest {
     const char* who; int n, H, W;
@@ -759,9 +761,30 @@ struct ScoreStage {
     void check_counts() const;                            // after the results have arrived: the device's counts against nf
     double sweep_ms() const { return sweeps.ev[0] ? (double)sweeps.ms(0) : 0.0; }
 };
+// What one rendering of n maps of H x W bytes asks for: frames on the host (uploaded), or on the device where they are (the kept
+// source), or neither (the heat map); out on the host.
+struct RenderRequest {
+    const char* who; int n, H, W;
+    const p3d_render* cfg = nullptr;
+    const unsigned char* frames = nullptr; const unsigned char* frames_dev = nullptr; unsigned char* out = nullptr;
+    bool timed = false;
+};
+// The launch of render.hip behind some device bytes, with ScoreStage's four moments.  It has no arrival counters: its blocks share
+// nothing.  render_check has passed cfg and the shape before one is built; the constructor queues nothing.
+struct RenderStage {
+    const RenderRequest r; const size_t bytes;
+    RenderArgs a;
+    unsigned char* df = nullptr; unsigned char* dout = nullptr; unsigned* dtab = nullptr;
+    double ms[3] = {0.0, 0.0, 0.0};
+    explicit RenderStage(const RenderRequest& r);
+    void carve(Carve& c);
+    void upload(hipStream_t s);
+    void launch(hipStream_t s, const unsigned char* sal);
+    void results(hipStream_t s);
+};
 void maps_u8_chain(p3d_handle* h, long long maps, int ph, int pw, float scale, int H, int W, unsigned char* out, double* stage_ms,
                    size_t extra, const std::function<void(hipStream_t, float*, std::vector<PostRun>&)>& sources,
-                   ScoreStage* use = nullptr) {
+                   ScoreStage* use = nullptr, RenderStage* paint = nullptr) {
     const long long hw = (long long)H * W, bytes = maps * hw;
     const hipStream_t s = h->stream;
     // p3d_set_postprocess: the float32 chain resize -> blur -> normalise -> bytes, P3D_POST_CHUNK maps at a time; its scratch
@@ -784,11 +807,13 @@ void maps_u8_chain(p3d_handle* h, long long maps, int ph, int pw, float scale, i
         if (chain) scratch.carve(c, st, post_chunk, hw, true);
         ex = extra ? c.take<float>(extra) : nullptr;
         if (use) use->carve(c);
+        if (paint) paint->carve(c);
     });
-    const bool use_timed = use && use->r.timed;
+    const bool use_timed = (use && use->r.timed) || (paint && paint->r.timed);
     StageTimer tm(stage_ms != nullptr || use_timed, 3), ends(use_timed, 2);
     ends.mark(0, s);
     if (use) use->upload(s);
+    if (paint) paint->upload(s);
     tm.mark(0, s);
     PostJob job;
     sources(s, ex, job.runs);
@@ -804,8 +829,10 @@ void maps_u8_chain(p3d_handle* h, long long maps, int ph, int pw, float scale, i
     }
     tm.mark(1, s);
     if (use) use->launch(s, d, counters + chain_counters);
+    if (paint) paint->launch(s, d);
     ends.mark(1, s);
     if (use) use->results(s);
+    if (paint) paint->results(s);
     if (out) HIPCHECK(hipMemcpyAsync(out, d, (size_t)bytes, hipMemcpyDeviceToHost, s));
     tm.mark(2, s);
     HIPCHECK(hipStreamSynchronize(s));
@@ -814,7 +841,8 @@ void maps_u8_chain(p3d_handle* h, long long maps, int ph, int pw, float scale, i
         float up = 0.f, sc = 0.f;
         HIPCHECK(hipEventElapsedTime(&up, ends.ev[0], tm.ev[0]));
         HIPCHECK(hipEventElapsedTime(&sc, tm.ev[1], ends.ev[1]));
-        use->ms[0] = (double)up; use->ms[1] = tm.ms(0); use->ms[2] = (double)sc;
+        double* const ms = use ? use->ms : paint->ms;
+        ms[0] = (double)up; ms[1] = tm.ms(0); ms[2] = (double)sc;
     }
 }
 }  // namespace
@@ -1811,6 +1839,154 @@ int p3d_debug_score_plan(int64_t n_pix, int n, int offset, int* blocks_per_map, 
     const ScorePlan p = p3d_score_plan(n_pix);
     *blocks_per_map = p.nblk; *pixels_per_block = p.chunk;
     *products_per_lane = p3d_score_lane_products(n_pix, n, (unsigned)offset, (unsigned)(2 * offset % 16), (unsigned)(3 * offset % 16));
+    API_END
+}
+
+}  // extern "C"
+namespace {
+// ---- rendering 8-bit maps over their frames (render.hip; the law in include/p3d_hip.h): one check, one table of buffer sizes and
+// one launch description for p3d_render_u8, the render stage and p3d_debug_render_u8 ------------------------------------------------
+void render_check(const char* who, const p3d_render* cfg, int n, int H, int W, const void* out) {
+    if (!cfg || !out) throw P3dError("null argument");
+    if (n < 1 || n > 65535) throw P3dError(std::string(who) + ": 1 .. 65535 maps");
+    if (H < 1 || W < 1) throw P3dError(std::string(who) + ": empty map");
+    if ((long long)H * W > P3D_RENDER_MAX_PIXELS) throw P3dError(std::string(who) + ": H * W exceeds 2^28, the bound of the int32 offsets inside a map");
+    if (cfg->contour_level < 0 || cfg->contour_level > 255) throw P3dError(std::string(who) + ": the contour level is 0 (off) .. 255");
+    if (cfg->contour_level > 0 && (cfg->contour_thickness < 1 || cfg->contour_thickness > P3D_RENDER_MAX_THICKNESS))
+        throw P3dError(std::string(who) + ": the contour thickness is 1 .. 4");
+}
+RenderArgs render_args(const p3d_render& cfg, int n, int H, int W) {
+    RenderArgs a;
+    a.n = n; a.H = H; a.W = W; a.level = cfg.contour_level; a.thick = a.level > 0 ? cfg.contour_thickness : 0;
+    for (int k = 0; k < 3; ++k) a.contour_bgr[k] = cfg.contour_bgr[k];
+    const RenderPlan p = p3d_render_plan(H, W, a.thick);
+    a.rows = p.rows; a.cols = p.cols; a.chunk = p.chunk; a.blocks = p.blocks;
+    return a;
+}
+// Elements of the buffers of one rendering: what the stage carves and what the hook puts between guards
+struct RenderSizes {
+    size_t sal, bgr, table;
+    explicit RenderSizes(const RenderArgs& a) : sal((size_t)a.n * (size_t)a.H * (size_t)a.W), bgr(sal * 3), table(256) {}
+};
+
+// ---- the render stage (declared above maps_u8_chain) ------------------------------------------------------------------------------
+RenderStage::RenderStage(const RenderRequest& r_)
+    : r(r_), bytes((size_t)r_.n * (size_t)r_.H * (size_t)r_.W), a(render_args(*r_.cfg, r_.n, r_.H, r_.W)) {}
+void RenderStage::carve(Carve& c) {
+    const RenderSizes z(a);
+    df = r.frames ? c.take<unsigned char>(z.bgr) : nullptr;
+    dout = c.take<unsigned char>(z.bgr);
+    dtab = c.take<unsigned>(z.table);
+}
+void RenderStage::upload(hipStream_t s) {
+    HIPCHECK(hipMemcpyAsync(dtab, r.cfg->table, 256 * sizeof(unsigned), hipMemcpyHostToDevice, s));
+    if (df) HIPCHECK(hipMemcpyAsync(df, r.frames, RenderSizes(a).bgr, hipMemcpyHostToDevice, s));
+}
+void RenderStage::launch(hipStream_t s, const unsigned char* sal) {
+    a.sal = sal; a.frames = df ? df : r.frames_dev; a.out = dout; a.table = dtab;
+    HIPCHECK(p3d_render_launch(a, s));
+}
+void RenderStage::results(hipStream_t s) {
+    HIPCHECK(hipMemcpyAsync(r.out, dout, RenderSizes(a).bgr, hipMemcpyDeviceToHost, s));
+}
+}  // namespace
+extern "C" {
+
+int p3d_render_u8(int device, const unsigned char* sal, const unsigned char* frames, int n, int H, int W, const p3d_render* cfg,
+                  unsigned char* out) {
+    API_BEGIN
+    if (!sal) throw P3dError("null argument");
+    render_check("render_u8", cfg, n, H, W, out);
+    metric_args(device, sal, cfg, 1, 1, out);
+    RenderRequest r{"render_u8", n, H, W};
+    r.cfg = cfg; r.frames = frames; r.out = out;
+    RenderStage stage(r);
+    DevArr<unsigned char> ds(stage.bytes, sal);
+    carve_scratch(nullptr, 0, [&](Carve& c) { stage.carve(c); });
+    stage.upload(nullptr);
+    stage.launch(nullptr, ds.p);
+    stage.results(nullptr);
+    HIPCHECK(hipDeviceSynchronize());
+    API_END
+}
+
+int p3d_debug_render_u8(int device, const unsigned char* sal, const unsigned char* frames, int n, int H, int W, const p3d_render* cfg,
+                        int offset, unsigned char* out) {
+    API_BEGIN
+    const char* who = "debug_render_u8";
+    if (!sal) throw P3dError("null argument");
+    render_check(who, cfg, n, H, W, out);
+    if (offset < 0 || offset > 15) throw P3dError(std::string(who) + ": offset in [0, 15]");
+    metric_args(device, sal, cfg, 1, 1, out);
+    RenderArgs a = render_args(*cfg, n, H, W);
+    const RenderSizes sz(a);
+    // guards of 16 elements keep a 16-byte boundary at the data's start; the three byte buffers are then shifted
+    Guarded<unsigned char> ds(sz.sal, 16, (size_t)offset, sal), df(frames ? sz.bgr : 0, 16, (size_t)(3 * offset % 16), frames),
+        dout(sz.bgr, 16, (size_t)(5 * offset % 16), nullptr);
+    Guarded<unsigned> tab(sz.table, 16, 0, cfg->table);
+    a.sal = ds.data(); a.frames = frames ? df.data() : nullptr; a.out = dout.data(); a.table = tab.data();
+    HIPCHECK(p3d_render_launch(a, nullptr));
+    dout.back(out, who);
+    ds.unchanged(who); tab.unchanged(who);
+    if (frames) df.unchanged(who);
+    API_END
+}
+
+int p3d_debug_render_plan(int H, int W, int n, int contour_thickness, int offset, int* rows_per_block, int* cols_per_block,
+                          int64_t* pixels_per_block) {
+    API_BEGIN
+    if (!rows_per_block || !cols_per_block || !pixels_per_block) throw P3dError("null argument");
+    if (H < 1 || W < 1 || (long long)H * W > P3D_RENDER_MAX_PIXELS || n < 1 || n > 65535 || contour_thickness < 0 ||
+        contour_thickness > P3D_RENDER_MAX_THICKNESS || offset < 0 || offset > 15)
+        throw P3dError("debug_render_plan: 1 <= H * W <= 2^28, 1 .. 65535 maps, thickness 0 .. 4, offset in [0, 15]");
+    const RenderPlan p = p3d_render_plan(H, W, contour_thickness);
+    *rows_per_block = p.rows; *cols_per_block = p.cols; *pixels_per_block = p.chunk;
+    API_END
+}
+
+int p3d_video_keep_source(p3d_handle* h, int on) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    h->video_keep_source(on);
+    API_END
+}
+
+int p3d_video_source_info(p3d_handle* h, int* on, int* H0, int* W0, int64_t* bytes) {
+    API_BEGIN
+    if (!h) throw P3dError("null handle");
+    h->video_need_open("video_source_info");
+    if (on) *on = h->vid_keep ? 1 : 0;
+    if (H0) *H0 = h->vid_H0;
+    if (W0) *W0 = h->vid_W0;
+    if (bytes) *bytes = (int64_t)h->vid_src_bytes;
+    API_END
+}
+
+int p3d_video_render(p3d_handle* h, int first, int n, float scale, int H, int W, const unsigned char* frames, const p3d_render* cfg,
+                     unsigned char* out, unsigned char* maps_out, double* stage_ms) {
+    API_BEGIN
+    const char* who = "video_render";
+    if (!h) throw P3dError("null argument");
+    h->video_need_open(who);
+    // before the shape: a call that leaves the size to the source has none to name when there is no source
+    if (!frames && !h->vid_src) throw P3dError(std::string(who) + ": no frames are given and the video keeps no source (p3d_video_keep_source before the first p3d_video_put_frames_u8)");
+    render_check(who, cfg, std::max(1, std::min(n, 65535)), H, W, out);
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    const VideoSource src(h, who, first, n, true, 65535);
+    RenderRequest r{who, n, H, W};
+    r.cfg = cfg; r.frames = frames; r.out = out; r.timed = stage_ms != nullptr;
+    if (!frames) {
+        if (H != h->vid_H0 || W != h->vid_W0)
+            throw P3dError(std::string(who) + ": the kept source is " + std::to_string(h->vid_H0) + " x " + std::to_string(h->vid_W0) + ", the call renders " +
+                           std::to_string(H) + " x " + std::to_string(W));
+        for (int f = first; f < first + n; ++f)
+            if (!h->vid_has_src[(size_t)f]) throw P3dError(std::string(who) + ": frame " + std::to_string(f) + " has no source (it was not put with p3d_video_put_frames_u8)");
+        r.frames_dev = h->vid_src + (size_t)first * (size_t)H * (size_t)W * 3;
+    }
+    RenderStage stage(r);
+    for (int i = 0; stage_ms && i < 3; ++i) stage_ms[i] = 0.0;
+    maps_u8_chain(h, n, h->pred->H, h->pred->W, scale, H, W, maps_out, nullptr, src.extra(), src, nullptr, &stage);
+    if (stage_ms) { stage_ms[0] = frames ? stage.ms[0] : 0.0; stage_ms[1] = stage.ms[1]; stage_ms[2] = stage.ms[2]; }
     API_END
 }
 

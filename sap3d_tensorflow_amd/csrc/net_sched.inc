@@ -1030,6 +1030,11 @@
     int64_t vid_cap = 0;                       // frames the allocation holds
     float* vid_frames = nullptr; float* vid_maps = nullptr; int32_t* vid_count_dev = nullptr;
     unsigned char* vid_u8 = nullptr; size_t vid_u8_bytes = 0;      // staging of p3d_video_put_frames_u8's bytes
+    // p3d_video_keep_source: the decoded frames [F][H0][W0][3] as they were put, for p3d_video_render.  Off: nothing of it exists
+    bool vid_keep = false, vid_u8_put = false;                     // vid_u8_put: a p3d_video_put_frames_u8 has run since the open
+    unsigned char* vid_src = nullptr; size_t vid_src_bytes = 0;
+    int vid_H0 = 0, vid_W0 = 0;
+    std::vector<unsigned char> vid_has_src;                        // [F]: the frame's bytes are in the store
     P3dVideoDst* d_vid_dst = nullptr; int* d_vid_src = nullptr; int* d_vid_starts = nullptr;      // the per-call tables, [B*T], [B*T], [B]
     std::vector<int32_t> vid_count; std::vector<unsigned char> vid_put;
     hipEvent_t ev_vid[4] = {nullptr, nullptr, nullptr, nullptr};      // around the last call's gather and scatter (p3d_video_last_ms)
@@ -1097,9 +1102,21 @@
     void video_free() {
         for (void* p : {(void*)vid_frames, (void*)vid_maps, (void*)vid_count_dev, (void*)vid_u8, (void*)d_vid_dst, (void*)d_vid_src, (void*)d_vid_starts})
             if (p) hipFree(p);
+        video_source_drop();
         vid_frames = vid_maps = nullptr; vid_count_dev = nullptr; vid_u8 = nullptr; vid_u8_bytes = 0;
         d_vid_dst = nullptr; d_vid_src = nullptr; d_vid_starts = nullptr;
         vid_cap = 0;
+    }
+    // the source store goes with the video it belongs to
+    void video_source_drop() {
+        if (vid_src) hipFree(vid_src);
+        vid_src = nullptr; vid_src_bytes = 0; vid_H0 = vid_W0 = 0; vid_keep = false; vid_u8_put = false;
+        vid_has_src.clear();
+    }
+    void video_keep_source(int on) {
+        video_need_open("video_keep_source");
+        if (vid_u8_put) throw P3dError("video_keep_source: frames were already put with p3d_video_put_frames_u8; set it right after p3d_video_open");
+        vid_keep = on != 0;
     }
     void video_open(int frames, int mode) {
         const int T = x_in->D, B = x_in->N;
@@ -1130,6 +1147,7 @@
         HIPCHECK(fill_now(vid_count_dev, 0, (size_t)frames * 4, stream));
         vid_count.assign((size_t)frames, 0);
         vid_put.assign((size_t)frames, 0);
+        video_source_drop();
         vid_F = frames; vid_mode = mode; vid_last = -1; vid_is_open = true; vid_timed = false;
     }
     void video_close() {
@@ -1143,22 +1161,47 @@
         video_range("video_put_frames", first, n);
         HIPCHECK(copy_now(vid_frames + (int64_t)first * vid_frame_elems(), x, (size_t)n * vid_frame_elems() * 4, hipMemcpyHostToDevice, stream));
         std::fill(vid_put.begin() + first, vid_put.begin() + first + n, (unsigned char)1);
+        if (!vid_has_src.empty()) std::fill(vid_has_src.begin() + first, vid_has_src.begin() + first + n, (unsigned char)0);      // floats have no source
     }
     void video_put_frames_u8(int first, const unsigned char* bgr, int n, int H0, int W0, const float mean_rgb[3]) {
         video_need_open("video_put_frames_u8");
         video_range("video_put_frames_u8", first, n);
         if (H0 < 1 || W0 < 1) throw P3dError("video_put_frames_u8: empty frame");
         const size_t bytes = (size_t)n * H0 * W0 * 3;
-        if (bytes > vid_u8_bytes) {
+        if (vid_keep) {      // the upload lands in the source store and the normalising launch reads it there
+            const size_t frame = (size_t)H0 * W0 * 3;
+            if (!vid_src) {
+                unsigned char* ns = nullptr;
+                const hipError_t e = hipMalloc((void**)&ns, (size_t)vid_F * frame);
+                if (e != hipSuccess) {
+                    (void)hipGetLastError();
+                    throw P3dError("video_put_frames_u8: no device memory for the source store of " + std::to_string(vid_F) + " frames of " +
+                                   std::to_string(H0) + " x " + std::to_string(W0) + " (" + hipGetErrorString(e) + ")");
+                }
+                vid_src = ns; vid_src_bytes = (size_t)vid_F * frame; vid_H0 = H0; vid_W0 = W0;
+                vid_has_src.assign((size_t)vid_F, 0);
+            } else if (H0 != vid_H0 || W0 != vid_W0) {
+                throw P3dError("video_put_frames_u8: the source store holds " + std::to_string(vid_H0) + " x " + std::to_string(vid_W0) + " frames, the call puts " +
+                               std::to_string(H0) + " x " + std::to_string(W0));
+            }
+            unsigned char* at = vid_src + (size_t)first * frame;
+            HIPCHECK(hipMemcpyAsync(at, bgr, bytes, hipMemcpyHostToDevice, stream));
+            HIPCHECK(p3d_mapf_frames(at, n, H0, W0, vid_frames + (int64_t)first * vid_frame_elems(), x_in->H, x_in->W, mean_rgb, stream));
             HIPCHECK(hipStreamSynchronize(stream));
-            if (vid_u8) hipFree(vid_u8);
-            vid_u8 = nullptr; vid_u8_bytes = 0;
-            HIPCHECK(hipMalloc((void**)&vid_u8, bytes));
-            vid_u8_bytes = bytes;
+            std::fill(vid_has_src.begin() + first, vid_has_src.begin() + first + n, (unsigned char)1);
+        } else {
+            if (bytes > vid_u8_bytes) {
+                HIPCHECK(hipStreamSynchronize(stream));
+                if (vid_u8) hipFree(vid_u8);
+                vid_u8 = nullptr; vid_u8_bytes = 0;
+                HIPCHECK(hipMalloc((void**)&vid_u8, bytes));
+                vid_u8_bytes = bytes;
+            }
+            HIPCHECK(hipMemcpyAsync(vid_u8, bgr, bytes, hipMemcpyHostToDevice, stream));
+            HIPCHECK(p3d_mapf_frames(vid_u8, n, H0, W0, vid_frames + (int64_t)first * vid_frame_elems(), x_in->H, x_in->W, mean_rgb, stream));
+            HIPCHECK(hipStreamSynchronize(stream));
         }
-        HIPCHECK(hipMemcpyAsync(vid_u8, bgr, bytes, hipMemcpyHostToDevice, stream));
-        HIPCHECK(p3d_mapf_frames(vid_u8, n, H0, W0, vid_frames + (int64_t)first * vid_frame_elems(), x_in->H, x_in->W, mean_rgb, stream));
-        HIPCHECK(hipStreamSynchronize(stream));
+        vid_u8_put = true;
         std::fill(vid_put.begin() + first, vid_put.begin() + first + n, (unsigned char)1);
     }
     void video_predict(const int* starts, int n_windows) {

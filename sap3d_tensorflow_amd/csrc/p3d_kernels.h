@@ -1078,6 +1078,39 @@ int p3d_sweep_cols(int kmax, int n_rep);
 LaunchDesc p3d_sweep_desc(int stage, const ScoreSweepArgs& a);
 hipError_t p3d_sweep_launch(int stage, const ScoreSweepArgs& a, hipStream_t s);
 
+// ---- overlays of 8-bit maps on their frames (render.hip; p3d_video_render / p3d_render_u8, the law in include/p3d_hip.h) ----
+// One launch on n maps of H x W bytes: sal [n][H][W], frames [n][H][W][3] (null: the heat map), table [256] in device memory,
+// out [n][H][W][3].  level > 0: the contour of {s >= level}, thick pixels wide, in contour_bgr.  Without a contour the blocks are
+// flat runs of RENDER_CHUNK pixels; with one they are tiles of RENDER_TILE_ROWS x RENDER_TILE_COLS pixels.
+// Refused (hipErrorInvalidValue): a missing buffer, n outside [1, 65535], H * W outside [1, 2^28], level outside [0, 255], with a
+// contour thick outside [1, 4], a plan other than p3d_render_plan's.
+constexpr int P3D_RENDER_MAX_PIXELS = 1 << 28;            // 3 H W fits int32 inside a map
+constexpr int P3D_RENDER_MAX_THICKNESS = 4;
+constexpr int RENDER_CHUNK = 8192;                        // a multiple of 16: every block of a map starts as far past a boundary as the map
+constexpr int RENDER_TILE_ROWS = 16, RENDER_TILE_COLS = 256;
+constexpr int RENDER_GRID_X = 65536;                      // blocks of a map in the grid's x; a map of more folds the rest into z (<= 2^24 / 2^16)
+struct RenderPlan { int rows = 0, cols = 0, chunk = 0; long long blocks = 0; };      // rows = cols = 0: flat runs of chunk pixels
+RenderPlan p3d_render_plan(int H, int W, int thick /* 0: no contour */);
+struct RenderArgs {
+    const unsigned char* sal = nullptr; const unsigned char* frames = nullptr; unsigned char* out = nullptr;
+    const unsigned* table = nullptr;          // [256]: b | g << 8 | r << 16 | o << 24
+    int n = 0, H = 0, W = 0;
+    int level = 0, thick = 0;
+    unsigned char contour_bgr[4] = {0, 0, 0, 0};
+    int rows = 0, cols = 0, chunk = 0; long long blocks = 0;      // p3d_render_plan(H, W, level > 0 ? thick : 0)
+};
+// How a run of len pixels is cut: `head` single pixels up to the first 16-byte boundary of s, `words` groups of 16 pixels, the
+// rest single.  Frame and out bytes of pixel p start 3 p past their base, so the three are aligned alike exactly when the frame
+// and out addresses equal 3 times the s address modulo 16; otherwise every pixel is single.
+struct RenderCut { int head, words; };
+__host__ __device__ inline RenderCut p3d_render_cut(uintptr_t as, uintptr_t af, uintptr_t ao, int len) {
+    if (((af - 3 * as) & 15) || ((ao - 3 * as) & 15)) return {len, 0};
+    const int head = (int)((16 - (as & 15)) & 15);
+    if (head >= len) return {len, 0};
+    return {head, (len - head) >> 4};
+}
+hipError_t p3d_render_launch(const RenderArgs& a, hipStream_t s);
+
 // ---- misc ---------------------------------------------------------------------------------------
 hipError_t p3d_add_inplace(float* dst, int lddst, const float* src, int ldsrc, long M, int C, hipStream_t s);
 hipError_t p3d_copy_strided(float* dst, int lddst, const float* src, int ldsrc, long M, int C, hipStream_t s);

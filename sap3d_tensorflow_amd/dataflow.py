@@ -480,3 +480,85 @@ def fixations_to_grid(fix_u8, H, W):
     k, r, c = np.nonzero(f >= 128)
     out[k, r * H // H0, c * W // W0] = 255
     return out
+
+
+def render_table(colormap="jet", alpha=0.6, opacity="ramp", gate=0):
+    """The colour and opacity table of p3d_render (include/p3d_hip.h, "Rendering 8-bit maps") -> uint32 [256], entry v packed
+    b | g << 8 | r << 16 | o << 24.  Built here in float64 with x = v / 255 and byte(c) = floor(255 c + 0.5).  The colour maps are
+    this project's own, not cv2's: "grey" (v, v, v); "hot" r = clamp(3x), g = clamp(3x - 1), b = clamp(3x - 2); "jet"
+    r = clamp(1.5 - |4x - 3|), g = clamp(1.5 - |4x - 2|), b = clamp(1.5 - |4x - 1|), clamp to [0, 1].  opacity "constant":
+    o = floor(255 alpha + 0.5) at every level; "ramp": o_v = floor(alpha v + 0.5).  Either is 0 below level `gate`."""
+    from ._lib import RENDER_COLORMAPS, RENDER_OPACITIES
+    if colormap not in RENDER_COLORMAPS:
+        raise ValueError("colormap %r: have %s" % (colormap, list(RENDER_COLORMAPS)))
+    if opacity not in RENDER_OPACITIES:
+        raise ValueError("opacity %r: have %s" % (opacity, list(RENDER_OPACITIES)))
+    alpha, gate = float(alpha), int(gate)
+    if not 0. <= alpha <= 1.:
+        raise ValueError("alpha is in [0, 1]")
+    if not 0 <= gate <= 256:
+        raise ValueError("gate is a level, 0 .. 256")
+    v = np.arange(256, dtype=np.float64)
+    x = v / 255.
+
+    def byte(c):
+        return np.floor(255. * np.clip(c, 0., 1.) + 0.5).astype(np.uint32)
+    if colormap == "grey":
+        r = g = b = np.arange(256, dtype=np.uint32)
+    elif colormap == "hot":
+        r, g, b = byte(3. * x), byte(3. * x - 1.), byte(3. * x - 2.)
+    else:
+        r, g, b = byte(1.5 - np.abs(4. * x - 3.)), byte(1.5 - np.abs(4. * x - 2.)), byte(1.5 - np.abs(4. * x - 1.))
+    o = np.floor((alpha * v if opacity == "ramp" else np.full(256, 255. * alpha)) + 0.5).astype(np.uint32)
+    o[:min(gate, 256)] = 0
+    return (b | (g << 8) | (r << 16) | (o << 24)).astype(np.uint32)
+
+
+def render_cfg(table, contour=None, thickness=1, contour_color=(255, 255, 255)):
+    """p3d_render from a uint32 [256] table, a contour level (None or 0: off), its thickness and its colour as (R, G, B)."""
+    from ._lib import P3dRender
+    t = np.ascontiguousarray(table)
+    if t.dtype != np.uint32 or t.shape != (256,):
+        raise ValueError("the table is uint32 [256] (dataflow.render_table)")
+    rgb = tuple(int(c) for c in contour_color)
+    if len(rgb) != 3 or min(rgb) < 0 or max(rgb) > 255:
+        raise ValueError("contour_color is (R, G, B) bytes")
+    cfg = P3dRender()
+    C.memmove(cfg.table, t.ctypes.data, 1024)
+    cfg.contour_level = int(contour) if contour else 0
+    cfg.contour_thickness = int(thickness)
+    cfg.contour_bgr[0], cfg.contour_bgr[1], cfg.contour_bgr[2] = rgb[2], rgb[1], rgb[0]
+    return cfg
+
+
+def render_plan(H, W, n=1, thickness=0, offset=0):
+    """Test hook (p3d_debug_render_plan, host only): (rows, cols, pixels) per block of the render launch; cols 0: flat runs."""
+    r, c, p = C.c_int(0), C.c_int(0), C.c_int64(0)
+    check(lib().p3d_debug_render_plan(int(H), int(W), int(n), int(thickness), int(offset), C.byref(r), C.byref(c), C.byref(p)))
+    return r.value, c.value, p.value
+
+
+def render_overlay(sal, frames, table, contour=None, thickness=1, contour_color=(255, 255, 255), device=0, offset=None):
+    """8-bit saliency maps uint8 [n, H, W] or [H, W] laid over frames uint8 [n, H, W, 3] in B, G, R order (None: the plain heat
+    map) through `table` (render_table) -> uint8 [n, H, W, 3] (include/p3d_hip.h, "Rendering 8-bit maps"; p3d_render_u8).
+    contour: the level whose iso-line is drawn, `thickness` pixels wide (1 .. 4), in contour_color (R, G, B).  offset (0 .. 15):
+    the test hook p3d_debug_render_u8, every device buffer between guards and shifted off a 16-byte boundary."""
+    s = np.ascontiguousarray(sal)
+    if s.dtype != np.uint8 or s.ndim not in (2, 3) or s.size == 0:
+        raise ValueError("saliency maps are non-empty uint8 [H, W] or [n, H, W]")
+    s3 = s[None] if s.ndim == 2 else s
+    f = None
+    if frames is not None:
+        f = np.ascontiguousarray(frames)
+        if f.dtype != np.uint8 or f.shape != s3.shape + (3,) and f.shape != s.shape + (3,):
+            raise ValueError("frames are uint8 %s, the maps' shape with three channels" % (s3.shape + (3,),))
+    cfg = render_cfg(table, contour, thickness, contour_color)
+    n, H, W = s3.shape
+    out = np.empty((n, H, W, 3), np.uint8)
+    u8 = C.POINTER(C.c_ubyte)
+    args = (device, s3.ctypes.data_as(u8), None if f is None else f.ctypes.data_as(u8), n, H, W, C.byref(cfg))
+    if offset is None:
+        check(lib().p3d_render_u8(*args, out.ctypes.data_as(u8)))
+    else:
+        check(lib().p3d_debug_render_u8(*args, int(offset), out.ctypes.data_as(u8)))
+    return out if s.ndim == 3 else out[0]

@@ -935,6 +935,50 @@ class P3DSession:
         self.last_score_ms = dict(upload=ms[0], device=ms[1], score=ms[2])
         return (out, maps) if with_maps else out
 
+    def video_keep_source(self, on=True):
+        """Keep the decoded frames of video_put_u8 on the device as they were put, for video_render (an addition).  Legal only
+        right after open_video, before the first video_put_u8; every open_video starts with it off.  The first video_put_u8 then
+        fixes the frames' size and allocates uint8 [frames, H0, W0, 3]; the normalised floats stay what they were, bit for bit."""
+        check(lib().p3d_video_keep_source(self._h, 1 if on else 0))
+
+    def video_source_info(self):
+        """dict(on, size=(H0, W0) -- (0, 0) until the first video_put_u8 --, bytes) of the open video's source store."""
+        on, h0, w0, b = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int64(0)
+        check(lib().p3d_video_source_info(self._h, C.byref(on), C.byref(h0), C.byref(w0), C.byref(b)))
+        return dict(on=bool(on.value), size=(h0.value, w0.value), bytes=b.value)
+
+    def video_render(self, first, n, frames=None, size=None, scale=255., table=None, colormap="jet", alpha=0.6, opacity="ramp", gate=0,
+                     contour=None, thickness=1, contour_color=(255, 255, 255), with_maps=False, timed=False):
+        """Frames first .. first + n - 1 of the open video with their saliency maps laid over them, on the device (an addition:
+        what the reference's gen_video.py is for) -> uint8 [n, H, W, 3] in B, G, R order.  The maps are video_maps_u8's bytes at
+        `size`, where they are; frames: uint8 [n, H, W, 3] at that size, or None for the source kept by video_keep_source (size
+        then defaults to, and must be, the source's own).  table: uint32 [256] of dataflow.render_table, or None to build it from
+        colormap ("grey", "hot", "jet"), alpha, opacity ("ramp", "constant") and gate.  contour: the level whose iso-line is
+        drawn `thickness` pixels wide in contour_color (R, G, B); None: no line.  with_maps: also the maps, uint8 [n, H, W].
+        timed: HIP-event times are left in `last_render_ms` (upload, device = the maps' chain, render).  include/p3d_hip.h holds
+        the exact rules."""
+        from . import dataflow
+        if size is None:
+            size = self.video_source_info()["size"] if frames is None else np.shape(frames)[1:3]
+        H, W = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
+        n = max(int(n), 0)
+        f = None
+        if frames is not None:
+            f = np.ascontiguousarray(frames)
+            if f.dtype != np.uint8 or f.shape != (n, H, W, 3):
+                raise ValueError("frames are %s %s, expected uint8 %s" % (f.dtype, f.shape, (n, H, W, 3)))
+        cfg = dataflow.render_cfg(dataflow.render_table(colormap, alpha, opacity, gate) if table is None else table, contour, thickness,
+                                  contour_color)
+        valid = H >= 1 and W >= 1 and H * W <= 2 ** 28
+        out = np.empty((n, H, W, 3) if valid else (0,), np.uint8)     # (the library refuses the rest)
+        maps = np.empty((n, H, W) if valid else (0,), np.uint8) if with_maps else None
+        ms = (C.c_double * 3)()
+        check(lib().p3d_video_render(self._h, int(first), n, float(scale), H, W, _ptr(f, _lib._u8p), C.byref(cfg), _ptr(out, _lib._u8p),
+                                     _ptr(maps, _lib._u8p), ms if timed else None))
+        if timed:
+            self.last_render_ms = dict(upload=ms[0], device=ms[1], render=ms[2])
+        return (out, maps) if with_maps else out
+
     def video_shuffled_begin(self, ids):
         """The union of the fixation pool's maps ids[b] (int [n, M], 1 <= M <= 64) for each of n frames that video_score_auc will
         score, counted and scanned on the device -> n_other uint32 [n].  Held apart from shuffled_begin's union: an armed
