@@ -29,7 +29,12 @@ mean of every window that predicted it.  A stride other than 1 and `--overlap me
 with reflected ends, or the causal moving average m_f = A m_{f-1} + (1 - A) v_f of `--temporal-alpha`; npy files then hold the
 filtered maps, png / jpg the images of the filtered maps.  `--render DIR` (an addition, needs `--resident`) also keeps the
 decoded frames on the device and writes DIR/<video>/frame_<k>.png: every frame at its own size with its 8-bit map laid over it
-on the device (P3DSession.video_render), whatever `--write` and `--truth` do beside it."""
+on the device (P3DSession.video_render), whatever `--write` and `--truth` do beside it.  `--reframe DIR` (an addition, needs
+`--resident`, may stand beside `--render`) writes DIR/<video>/frame_<k>.png, every frame cut -- not resized -- to the window of
+`--reframe-size HC WC` or `--reframe-aspect A:B` (width : height; default 9:16) that holds the most saliency at or above
+`--reframe-gate`, on a track averaged over `--reframe-smooth` frames to either side (P3DSession.video_reframe, one call per
+video so that the filter sees all of it), and DIR/<video>/track.npy, int64 [F, 7]: the smoothed (y, x), the raw (y, x), and the
+masses of the best window, of the window taken and of the whole map."""
 import argparse
 import glob
 import os
@@ -183,6 +188,56 @@ def render_video_resident(sess, F, video_dir, render, writers=4):
             held = hand_over(pool, held, write, first, images)
             t["files"] += n
         hand_over(pool, held, write, F, ())
+    return t
+
+
+def aspect_window(H, W, a, b):
+    """--reframe-aspect a:b (width : height): the largest window (hc, wc) of that aspect that fits an H x W frame -- the full width
+    where W / a <= H / b, else the full height, the other side the floor of the exact ratio -- each side rounded down to an even
+    number (a side of one pixel stays one)."""
+    if W * b <= H * a:
+        hc, wc = W * b // a, W
+    else:
+        hc, wc = H, H * a // b
+    return max(hc // 2 * 2, 1), max(wc // 2 * 2, 1)
+
+
+TRACK_COLUMNS = ("y", "x", "raw_y", "raw_x", "mass_best", "mass_smoothed", "mass_total")      # a row of track.npy
+
+
+def reframe_video_resident(sess, F, video_dir, reframe, writers=4):
+    """--reframe: the open video's frames cut to the window that follows their saliency (P3DSession.video_reframe on the kept
+    source, at the video's own size) -> <video_dir>/frame_<k>.png, k = 1..F, colour, and <video_dir>/track.npy, int64 [F, 7] in
+    TRACK_COLUMNS' order.  ONE call for the whole video: the track's filter sees every frame.  reframe: dict(size=(hc, wc) or
+    aspect=(a, b), gate, smooth).  Returns milliseconds: gpu (wall time of the call), the three device stages, encode (thread
+    time), the number of files and the window."""
+    import threading
+    from concurrent.futures import ThreadPoolExecutor
+    t = dict(gpu=0.0, upload=0.0, device=0.0, reframe=0.0, encode=0.0, files=0)
+    lock = threading.Lock()
+    H0, W0 = sess.video_source_info()["size"]
+    crop = tuple(reframe["size"]) if reframe.get("size") else aspect_window(H0, W0, *reframe["aspect"])
+    if not (1 <= crop[0] <= H0 and 1 <= crop[1] <= W0):
+        raise ValueError("--reframe: a %d x %d window does not fit the video's %d x %d frames" % (crop + (H0, W0)))
+
+    def write(f, m):
+        t0 = time.perf_counter()
+        save_color_image(os.path.join(video_dir, "frame_%d.png" % (f + 1)), m)
+        with lock:
+            t["encode"] += (time.perf_counter() - t0) * 1e3
+
+    t0 = time.perf_counter()
+    res = sess.video_reframe(0, F, crop, gate=reframe["gate"], smooth=reframe["smooth"], with_raw=True, with_mass=True, timed=True)
+    t["gpu"] = (time.perf_counter() - t0) * 1e3
+    for k in ("upload", "device", "reframe"):
+        t[k] = sess.last_reframe_ms[k]
+    np.save(os.path.join(video_dir, "track.npy"), np.concatenate([res["track"], res["raw"], res["mass"]], axis=1).astype(np.int64))
+    with ThreadPoolExecutor(max_workers=writers) as pool:
+        held = []
+        for first in range(0, F, 16):
+            held = hand_over(pool, held, write, first, res["crop"][first:first + 16])
+        hand_over(pool, held, write, F, ())
+    t["files"], t["window"] = F, crop
     return t
 
 
@@ -431,6 +486,15 @@ def parse_args(argv=None):
                    "1 .. 255 (0: none)")
     p.add_argument("--render-thickness", type=int, default=1, metavar="T", help="[addition] --render-contour: the line's width, 1 .. 4 pixels")
     p.add_argument("--render-contour-color", type=str, default="255,255,255", metavar="R,G,B", help="[addition] --render-contour: the line's colour")
+    p.add_argument("--reframe", type=str, default="", metavar="DIR", help="[addition] needs --resident: keep every video's decoded frames on "
+                   "the device and write DIR/<video>/frame_<k>.png, the frame cut to the window of the most saliency on a smoothed "
+                   "track (not resized), and DIR/<video>/track.npy; may be given together with --render")
+    p.add_argument("--reframe-size", type=int, nargs=2, default=None, metavar=("HC", "WC"), help="[addition] --reframe: the window's rows and columns")
+    p.add_argument("--reframe-aspect", type=str, default="", metavar="A:B", help="[addition] --reframe: width : height of the window; the largest "
+                   "such window that fits the frame, each side rounded down to an even number (default 9:16)")
+    p.add_argument("--reframe-gate", type=int, default=0, metavar="LEVEL", help="[addition] --reframe: map levels below it weigh nothing, 0 .. 255")
+    p.add_argument("--reframe-smooth", type=int, default=0, metavar="R", help="[addition] --reframe: the track is averaged over R frames to "
+                   "either side, 0 .. 255 (0: the raw track)")
     p.add_argument("--base", type=int, default=64, help=argparse.SUPPRESS)
     p.add_argument("--blocks", type=str, default="3,8,36", help=argparse.SUPPRESS)
     p.add_argument("--time", action="store_true", help="print per-video wall times (png / jpg: also the device stage and the host encode)")
@@ -468,7 +532,41 @@ def parse_args(argv=None):
     if not 2 <= args.match_bins <= 1024:
         p.error("--match-bins must be in 2..1024")
     render_args(args, p.error)
+    reframe_args(args, p.error)
     return args
+
+
+def reframe_args(args, error):
+    """Checks --reframe and its values as P3DSession.video_reframe would refuse them, before anything runs; error(message) does not
+    return.  Leaves dict(size or aspect, gate, smooth) in args.reframe_kw (None without --reframe)."""
+    args.reframe_kw = None
+    shaped = args.reframe_size is not None or args.reframe_aspect or args.reframe_gate != 0 or args.reframe_smooth != 0
+    if not args.reframe:
+        if shaped:
+            error("--reframe-size / -aspect / -gate / -smooth need --reframe DIR")
+        return
+    if not args.resident:
+        error("--reframe needs --resident: the frames and the maps stay on the device")
+    if args.reframe_size is not None and args.reframe_aspect:
+        error("--reframe-size and --reframe-aspect both set the window: give one")
+    kw = dict(size=None, aspect=None, gate=args.reframe_gate, smooth=args.reframe_smooth)
+    if args.reframe_size is not None:
+        if min(args.reframe_size) < 1:
+            error("--reframe-size is HC WC, each at least 1")
+        kw["size"] = tuple(args.reframe_size)
+    else:
+        try:
+            a, b = (int(v) for v in (args.reframe_aspect or "9:16").split(":"))
+        except ValueError:
+            a = b = 0
+        if a < 1 or b < 1:
+            error("--reframe-aspect is A:B, two positive integers (width : height)")
+        kw["aspect"] = (a, b)
+    if not 0 <= args.reframe_gate <= 255:
+        error("--reframe-gate is a level, 0 .. 255")
+    if not 0 <= args.reframe_smooth <= 255:
+        error("--reframe-smooth is 0 .. 255 frames")
+    args.reframe_kw = kw
 
 
 def render_args(args, error):
@@ -615,7 +713,10 @@ def run_resident(sess, args, path):
         os.makedirs(render_dir, exist_ok=True)
     t0 = time.perf_counter()
     times = {}
-    F = predict_video_resident(sess, np.load(path), args.batch, args.stride, args.overlap, times, keep_source=bool(render_dir))
+    reframe_dir = os.path.join(args.reframe, name) if args.reframe else None
+    if reframe_dir:
+        os.makedirs(reframe_dir, exist_ok=True)
+    F = predict_video_resident(sess, np.load(path), args.batch, args.stride, args.overlap, times, keep_source=bool(render_dir or reframe_dir))
     t1 = time.perf_counter()
     means = ts = None
     if args.truth:
@@ -661,6 +762,10 @@ def run_resident(sess, args, path):
     if render_dir:
         tr = render_video_resident(sess, F, render_dir, args.render_kw, writers=args.writers)
         print(name, "%d rendered png files in %s" % (tr["files"], render_dir))
+    tf = None
+    if reframe_dir:
+        tf = reframe_video_resident(sess, F, reframe_dir, args.reframe_kw, writers=args.writers)
+        print(name, "%d reframed %d x %d png files and track.npy in %s" % ((tf["files"],) + tf["window"] + (reframe_dir,)))
     temporal_ms = sess.video_temporal_last_ms() if args.temporal != "off" and args.time else None
     sess.close_video()
     if args.time:
@@ -679,6 +784,9 @@ def run_resident(sess, args, path):
         if tr is not None:
             print("  %s: render %.1f ms (uploads %.2f ms, maps %.2f ms, render launches %.3f ms on the device) | encode %.1f ms thread "
                   "time on %d writers" % (name, tr["gpu"], tr["upload"], tr["device"], tr["render"], tr["encode"], args.writers))
+        if tf is not None:
+            print("  %s: reframe %.1f ms (uploads %.2f ms, maps %.2f ms, reframe launches %.3f ms on the device) | encode %.1f ms thread "
+                  "time on %d writers" % (name, tf["gpu"], tf["upload"], tf["device"], tf["reframe"], tf["encode"], args.writers))
     return means
 
 

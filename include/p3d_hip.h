@@ -1578,6 +1578,61 @@ int p3d_debug_render_u8(int device, const unsigned char* sal, const unsigned cha
 int p3d_debug_render_plan(int H, int W, int n, int contour_thickness /* 0: no contour */, int offset,
                           int* rows_per_block, int* cols_per_block, int64_t* pixels_per_block);
 
+/* ---- Reframing around 8-bit maps (an ADDITION: what a video-saliency model is run for -- a smaller window cut out of every frame
+ * where the viewers look, on a track steady enough to watch: 16:9 to 9:16, thumbnails, region-of-interest crops for an encoder).
+ * OFF until called: every other entry point issues what it issued before and returns the same bits.  PARITY UNPINNED: the reference
+ * has nothing of the kind; this text is the contract and tests/reframe_ref.py replays it in numpy.  Everything is integer
+ * arithmetic, no floating point anywhere: no order can show, and every test holds to 0.
+ * Per frame: s [H][W] bytes, the saliency map; frame [H][W][3] bytes (B, G, R), or absent; a window size hc x wc, 1 <= hc <= H,
+ * 1 <= wc <= W; a gate level g in 0 .. 255; a smoothing radius R in 0 .. 255 frames.
+ *   LIMITS   1 <= n <= 65535 maps a call; H * W <= 2^23.  The largest mass is 255 * 2^23 < 2^31: one unsigned 32-bit word holds it.
+ *   WEIGHT   wt(v) = v where v >= g, else 0; g = 0 weighs every byte by itself.
+ *   MASS     for a window with top-left (y0, x0), 0 <= y0 <= H - hc, 0 <= x0 <= W - wc: M(y0, x0) = the sum of wt(s(y, x)) over the
+ *            window's hc * wc pixels.  T = the same sum over the whole map.
+ *   BEST WINDOW (the raw track)  the window with the largest M; among equals the smallest
+ *            D = |2 y0 - (H - hc)| + |2 x0 - (W - wc)| (nearest the centred window); among those the smallest y0, then the smallest
+ *            x0.  An all-zero map, a map whose bytes all fall below the gate and a constant map therefore give the centred window,
+ *            rounded towards the top-left.
+ *   SMOOTHED TRACK  R = 0: the raw track.  Otherwise, over the n frames OF THE CALL, with c(i) = min(max(i, 0), n - 1), separately
+ *            per coordinate: Y_f = (2 * sum_{k = -R .. R} y_{c(f + k)} + (2 R + 1)) / (2 (2 R + 1)), integer division, the sum in 64
+ *            bits: round-to-nearest, half up, of a box average whose ends repeat the first or last frame.  An average of legal
+ *            positions is legal.  The frames of one call are the whole world of the filter: a caller who wants one track for a video
+ *            asks for the video in one call.
+ *   MASSES   per frame three unsigned 32-bit numbers: M of the best window, M of the window at the smoothed position, T.  Always
+ *            M_smoothed <= M_best <= T.
+ *   CROP     where frames are present: out[f][y][x][k] = frame[f][Y_f + y][X_f + x][k], out [n][hc][wc][3].  The crop is not
+ *            resized: scaling it is the encoder's or the host's job, as video containers are.  Without frames only the tracks and
+ *            masses come back.
+ * p3d_reframe_u8     op level, host arrays: sal [n][H][W], frames [n][H][W][3] or NULL -> track [n][2] (Y, X), raw [n][2] (or NULL),
+ *                    mass [n][3] (or NULL), out [n][hc][wc][3], NULL exactly when frames is.
+ * p3d_video_reframe  reframes frames first .. first + n - 1 of the open video at H x W.  The saliency bytes are, bit for bit, what
+ *                    p3d_video_maps_u8(first, n, scale, H, W) returns under the handle's current settings; maps_out (or NULL)
+ *                    receives them.  out == NULL: tracks and masses only, frames must be NULL too.  Otherwise frames: host
+ *                    [n][H][W][3], uploaded as p3d_video_score uploads its truth, or NULL for the source kept by
+ *                    p3d_video_keep_source -- then H = H0 and W = W0 are required and every frame of the range must have a source
+ *                    (the refusal names the first without one).  Validated as p3d_video_maps_u8 validates, plus cfg, LIMITS, a
+ *                    window larger than the map and track == NULL, all before any launch, upload or scratch request: a refusal
+ *                    changes nothing.  stage_ms (or NULL) [3] as p3d_video_render's: the frames' upload (0 with the kept source or
+ *                    without a crop), the maps' chain, the reframe launches.  Returns synchronised.
+ * TEST HOOKS (tests/test_gpu_reframe.py):
+ * p3d_debug_reframe_u8  the same launch description with every device buffer, the scratch included, between guards: sal starts
+ *                    `offset` bytes (0 .. 15) past a 16-byte boundary, frames (3 offset) mod 16 and out (5 offset) mod 16 bytes past
+ *                    one; -1 if a guard or an input changed.
+ * p3d_debug_reframe_plan  host only, no HIP call: the window positions a block of the search takes, the search's blocks a map, the
+ *                    maps whose summed-area tables are held at a time (a call of more maps runs in chunks of that many) and the bytes
+ *                    of scratch the tables and the blocks' bests take. */
+typedef struct { int crop_h, crop_w, gate, smooth_radius; } p3d_reframe;
+int p3d_reframe_u8(int device, const unsigned char* sal, const unsigned char* frames /* may be NULL */, int n, int H, int W,
+                   const p3d_reframe* cfg, int32_t* track /* [n][2]: Y, X */, int32_t* raw /* [n][2], may be NULL */,
+                   uint32_t* mass /* [n][3], may be NULL */, unsigned char* out /* [n][crop_h][crop_w][3]; NULL exactly when frames is */);
+int p3d_video_reframe(p3d_handle* h, int first, int n, float scale, int H, int W, const unsigned char* frames /* NULL: kept source */,
+                      const p3d_reframe* cfg, int32_t* track, int32_t* raw, uint32_t* mass, unsigned char* out /* may be NULL: tracks only */,
+                      unsigned char* maps_out /* may be NULL */, double* stage_ms /* may be NULL, [3] as p3d_video_render's */);
+int p3d_debug_reframe_u8(int device, const unsigned char* sal, const unsigned char* frames, int n, int H, int W, const p3d_reframe* cfg,
+                         int offset, int32_t* track, int32_t* raw, uint32_t* mass, unsigned char* out);
+int p3d_debug_reframe_plan(int H, int W, int crop_h, int crop_w, int n, int* positions_per_block, int* search_blocks, int* maps_per_chunk,
+                           int64_t* scratch_bytes);
+
 /* CRC-32C of a host buffer (host-side helper of the TensorFlow checkpoint reader / writer, sap3d_tensorflow_amd/tf_checkpoint.py:
  * the bundle format of train.py:180-185,266-267 checksums every tensor); crc = running value, 0 to start. */
 uint32_t p3d_crc32c(const void* data, size_t n, uint32_t crc);

@@ -49,6 +49,11 @@ class P3dRender(C.Structure):
     _fields_ = [("table", C.c_uint32 * 256), ("contour_level", C.c_int), ("contour_thickness", C.c_int), ("contour_bgr", C.c_ubyte * 3)]
 
 
+class P3dReframe(C.Structure):
+    """p3d_reframe: the window, the gate level (0 .. 255) and the smoothing radius in frames (0 .. 255)."""
+    _fields_ = [("crop_h", C.c_int), ("crop_w", C.c_int), ("gate", C.c_int), ("smooth_radius", C.c_int)]
+
+
 class P3dVideoTemporal(C.Structure):
     _fields_ = [("kind", C.c_int), ("sigma", C.c_float), ("radius", C.c_int), ("alpha", C.c_float)]
 
@@ -126,6 +131,8 @@ _i64p = C.POINTER(C.c_int64)
 _ip = C.POINTER(C.c_int)
 _dp = C.POINTER(C.c_double)
 _u8p = C.POINTER(C.c_ubyte)
+_i32p = C.POINTER(C.c_int32)
+_u32p = C.POINTER(C.c_uint32)
 
 # every symbol include/p3d_hip.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -401,6 +408,11 @@ SIGNATURES = {
     "p3d_video_render": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, _u8p, C.POINTER(P3dRender), _u8p, _u8p, _dp]),
     "p3d_debug_render_u8": (C.c_int, [C.c_int, _u8p, _u8p, C.c_int, C.c_int, C.c_int, C.POINTER(P3dRender), C.c_int, _u8p]),
     "p3d_debug_render_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _i64p]),
+    "p3d_reframe_u8": (C.c_int, [C.c_int, _u8p, _u8p, C.c_int, C.c_int, C.c_int, C.POINTER(P3dReframe), _i32p, _i32p, _u32p, _u8p]),
+    "p3d_video_reframe": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, _u8p, C.POINTER(P3dReframe), _i32p, _i32p, _u32p,
+                                    _u8p, _u8p, _dp]),
+    "p3d_debug_reframe_u8": (C.c_int, [C.c_int, _u8p, _u8p, C.c_int, C.c_int, C.c_int, C.POINTER(P3dReframe), C.c_int, _i32p, _i32p, _u32p, _u8p]),
+    "p3d_debug_reframe_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _ip, _i64p]),
     "p3d_crc32c": (C.c_uint32, [C.c_void_p, C.c_size_t, C.c_uint32]),
     "p3d_shutdown": (C.c_int, []),
 }

@@ -725,6 +725,8 @@ namespace {
 // the launches.  Without one, nothing here differs from what the two callers issued before.
 // A render stage (p3d_video_render) is a second consumer of the same kind and follows the score stage at each of the four moments;
 // it has no counters.  Without one, nothing here differs from what the callers issued before it existed.
+// A reframe stage (p3d_video_reframe) is a third, behind the render stage at each moment, with no counters either: its launches
+// hand results to one another from launch to launch.  Without one, nothing here differs from what the callers issued before.
 // What one scoring of n maps of H x W bytes asks for; every pointer is host memory.  Whatever is not asked for is not issued.
 struct ScoreRequest {
     const char* who; int n, H, W;
@@ -782,9 +784,32 @@ struct RenderStage {
     void launch(hipStream_t s, const unsigned char* sal);
     void results(hipStream_t s);
 };
+// What one reframing of n maps of H x W bytes asks for: frames on the host (uploaded), or on the device where they are (the kept
+// source), or neither (tracks and masses only); track, raw, mass and out on the host, whatever is null is not copied back.
+struct ReframeRequest {
+    const char* who; int n, H, W;
+    const p3d_reframe* cfg = nullptr;
+    const unsigned char* frames = nullptr; const unsigned char* frames_dev = nullptr;
+    int32_t* track = nullptr; int32_t* raw = nullptr; uint32_t* mass = nullptr; unsigned char* out = nullptr;
+    bool timed = false;
+};
+// The launches of reframe.hip behind some device bytes, with ScoreStage's four moments and no arrival counters.  reframe_check has
+// passed cfg and the shape before one is built; the constructor queues nothing.
+struct ReframeStage {
+    const ReframeRequest r; const size_t bytes;
+    ReframeArgs a;
+    unsigned char* df = nullptr;
+    double ms[3] = {0.0, 0.0, 0.0};
+    explicit ReframeStage(const ReframeRequest& r);
+    bool crops() const { return r.out != nullptr; }
+    void carve(Carve& c);
+    void upload(hipStream_t s);
+    void launch(hipStream_t s, const unsigned char* sal);
+    void results(hipStream_t s);
+};
 void maps_u8_chain(p3d_handle* h, long long maps, int ph, int pw, float scale, int H, int W, unsigned char* out, double* stage_ms,
                    size_t extra, const std::function<void(hipStream_t, float*, std::vector<PostRun>&)>& sources,
-                   ScoreStage* use = nullptr, RenderStage* paint = nullptr) {
+                   ScoreStage* use = nullptr, RenderStage* paint = nullptr, ReframeStage* cut = nullptr) {
     const long long hw = (long long)H * W, bytes = maps * hw;
     const hipStream_t s = h->stream;
     // p3d_set_postprocess: the float32 chain resize -> blur -> normalise -> bytes, P3D_POST_CHUNK maps at a time; its scratch
@@ -808,12 +833,14 @@ void maps_u8_chain(p3d_handle* h, long long maps, int ph, int pw, float scale, i
         ex = extra ? c.take<float>(extra) : nullptr;
         if (use) use->carve(c);
         if (paint) paint->carve(c);
+        if (cut) cut->carve(c);
     });
-    const bool use_timed = (use && use->r.timed) || (paint && paint->r.timed);
+    const bool use_timed = (use && use->r.timed) || (paint && paint->r.timed) || (cut && cut->r.timed);
     StageTimer tm(stage_ms != nullptr || use_timed, 3), ends(use_timed, 2);
     ends.mark(0, s);
     if (use) use->upload(s);
     if (paint) paint->upload(s);
+    if (cut) cut->upload(s);
     tm.mark(0, s);
     PostJob job;
     sources(s, ex, job.runs);
@@ -830,9 +857,11 @@ void maps_u8_chain(p3d_handle* h, long long maps, int ph, int pw, float scale, i
     tm.mark(1, s);
     if (use) use->launch(s, d, counters + chain_counters);
     if (paint) paint->launch(s, d);
+    if (cut) cut->launch(s, d);
     ends.mark(1, s);
     if (use) use->results(s);
     if (paint) paint->results(s);
+    if (cut) cut->results(s);
     if (out) HIPCHECK(hipMemcpyAsync(out, d, (size_t)bytes, hipMemcpyDeviceToHost, s));
     tm.mark(2, s);
     HIPCHECK(hipStreamSynchronize(s));
@@ -841,7 +870,7 @@ void maps_u8_chain(p3d_handle* h, long long maps, int ph, int pw, float scale, i
         float up = 0.f, sc = 0.f;
         HIPCHECK(hipEventElapsedTime(&up, ends.ev[0], tm.ev[0]));
         HIPCHECK(hipEventElapsedTime(&sc, tm.ev[1], ends.ev[1]));
-        double* const ms = use ? use->ms : paint->ms;
+        double* const ms = use ? use->ms : paint ? paint->ms : cut->ms;
         ms[0] = (double)up; ms[1] = tm.ms(0); ms[2] = (double)sc;
     }
 }
@@ -1986,6 +2015,157 @@ int p3d_video_render(p3d_handle* h, int first, int n, float scale, int H, int W,
     RenderStage stage(r);
     for (int i = 0; stage_ms && i < 3; ++i) stage_ms[i] = 0.0;
     maps_u8_chain(h, n, h->pred->H, h->pred->W, scale, H, W, maps_out, nullptr, src.extra(), src, nullptr, &stage);
+    if (stage_ms) { stage_ms[0] = frames ? stage.ms[0] : 0.0; stage_ms[1] = stage.ms[1]; stage_ms[2] = stage.ms[2]; }
+    API_END
+}
+
+}  // extern "C"
+namespace {
+// ---- reframing around 8-bit maps (reframe.hip; the law in include/p3d_hip.h): one check, one table of buffer sizes and one launch
+// description for p3d_reframe_u8, the reframe stage and p3d_debug_reframe_u8 --------------------------------------------------------
+void reframe_check(const char* who, const p3d_reframe* cfg, int n, int H, int W, const void* track) {
+    if (!cfg || !track) throw P3dError("null argument");
+    if (n < 1 || n > 65535) throw P3dError(std::string(who) + ": 1 .. 65535 maps");
+    if (H < 1 || W < 1) throw P3dError(std::string(who) + ": empty map");
+    if ((long long)H * W > P3D_REFRAME_MAX_PIXELS) throw P3dError(std::string(who) + ": H * W exceeds 2^23, the bound that keeps a mass in 32 bits");
+    if (cfg->crop_h < 1 || cfg->crop_h > H || cfg->crop_w < 1 || cfg->crop_w > W)
+        throw P3dError(std::string(who) + ": the window is " + std::to_string(cfg->crop_h) + " x " + std::to_string(cfg->crop_w) + ", the map " +
+                       std::to_string(H) + " x " + std::to_string(W) + "; 1 <= crop_h <= H and 1 <= crop_w <= W");
+    if (cfg->gate < 0 || cfg->gate > 255) throw P3dError(std::string(who) + ": the gate is a level, 0 .. 255");
+    if (cfg->smooth_radius < 0 || cfg->smooth_radius > 255) throw P3dError(std::string(who) + ": the smoothing radius is 0 .. 255 frames");
+}
+ReframeArgs reframe_args(const p3d_reframe& cfg, int n, int H, int W) {
+    ReframeArgs a;
+    a.n = n; a.H = H; a.W = W; a.hc = cfg.crop_h; a.wc = cfg.crop_w; a.gate = cfg.gate; a.radius = cfg.smooth_radius;
+    const ReframePlan p = p3d_reframe_plan(H, W, a.hc, a.wc, n);
+    a.maps_per_chunk = p.maps_per_chunk; a.search_blocks = p.search_blocks;
+    return a;
+}
+// Elements of the buffers of one reframing: what the stage carves and what the hook puts between guards
+struct ReframeSizes {
+    size_t sal, bgr, crop, pairs, masses, sat, best, part;
+    explicit ReframeSizes(const ReframeArgs& a)
+        : sal((size_t)a.n * (size_t)a.H * (size_t)a.W), bgr(sal * 3), crop((size_t)a.n * (size_t)a.hc * (size_t)a.wc * 3), pairs((size_t)a.n * 2),
+          masses((size_t)a.n * 3) {
+        const ReframePlan p = p3d_reframe_plan(a.H, a.W, a.hc, a.wc, a.n);
+        sat = (size_t)p.sat_elems; best = (size_t)p.best_elems; part = (size_t)p.part_elems;
+    }
+};
+
+// ---- the reframe stage (declared above maps_u8_chain) -----------------------------------------------------------------------------
+ReframeStage::ReframeStage(const ReframeRequest& r_)
+    : r(r_), bytes((size_t)r_.n * (size_t)r_.H * (size_t)r_.W), a(reframe_args(*r_.cfg, r_.n, r_.H, r_.W)) {}
+void ReframeStage::carve(Carve& c) {
+    const ReframeSizes z(a);
+    df = crops() && r.frames ? c.take<unsigned char>(z.bgr) : nullptr;
+    a.out = crops() ? c.take<unsigned char>(z.crop) : nullptr;
+    a.track = c.take<int32_t>(z.pairs);
+    a.raw = c.take<int32_t>(z.pairs);
+    a.mass = c.take<uint32_t>(z.masses);
+    a.sat = c.take<unsigned>(z.sat);
+    a.best = c.take<unsigned>(z.best);
+    a.part = c.take<unsigned>(z.part);
+}
+void ReframeStage::upload(hipStream_t s) {
+    if (df) HIPCHECK(hipMemcpyAsync(df, r.frames, ReframeSizes(a).bgr, hipMemcpyHostToDevice, s));
+}
+void ReframeStage::launch(hipStream_t s, const unsigned char* sal) {
+    a.sal = sal; a.frames = !crops() ? nullptr : df ? df : r.frames_dev;
+    HIPCHECK(p3d_reframe_launch(a, s));
+}
+void ReframeStage::results(hipStream_t s) {
+    const ReframeSizes z(a);
+    HIPCHECK(hipMemcpyAsync(r.track, a.track, z.pairs * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (r.raw) HIPCHECK(hipMemcpyAsync(r.raw, a.raw, z.pairs * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (r.mass) HIPCHECK(hipMemcpyAsync(r.mass, a.mass, z.masses * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (crops()) HIPCHECK(hipMemcpyAsync(r.out, a.out, z.crop, hipMemcpyDeviceToHost, s));
+}
+}  // namespace
+extern "C" {
+
+int p3d_reframe_u8(int device, const unsigned char* sal, const unsigned char* frames, int n, int H, int W, const p3d_reframe* cfg,
+                   int32_t* track, int32_t* raw, uint32_t* mass, unsigned char* out) {
+    API_BEGIN
+    const char* who = "reframe_u8";
+    if (!sal) throw P3dError("null argument");
+    reframe_check(who, cfg, n, H, W, track);
+    if ((frames == nullptr) != (out == nullptr)) throw P3dError(std::string(who) + ": out is given exactly when frames are");
+    metric_args(device, sal, cfg, 1, 1, track);
+    ReframeRequest r{who, n, H, W};
+    r.cfg = cfg; r.frames = frames; r.track = track; r.raw = raw; r.mass = mass; r.out = out;
+    ReframeStage stage(r);
+    DevArr<unsigned char> ds(stage.bytes, sal);
+    carve_scratch(nullptr, 0, [&](Carve& c) { stage.carve(c); });
+    stage.upload(nullptr);
+    stage.launch(nullptr, ds.p);
+    stage.results(nullptr);
+    HIPCHECK(hipDeviceSynchronize());
+    API_END
+}
+
+int p3d_debug_reframe_u8(int device, const unsigned char* sal, const unsigned char* frames, int n, int H, int W, const p3d_reframe* cfg,
+                         int offset, int32_t* track, int32_t* raw, uint32_t* mass, unsigned char* out) {
+    API_BEGIN
+    const char* who = "debug_reframe_u8";
+    if (!sal) throw P3dError("null argument");
+    reframe_check(who, cfg, n, H, W, track);
+    if ((frames == nullptr) != (out == nullptr)) throw P3dError(std::string(who) + ": out is given exactly when frames are");
+    if (offset < 0 || offset > 15) throw P3dError(std::string(who) + ": offset in [0, 15]");
+    metric_args(device, sal, cfg, 1, 1, track);
+    ReframeArgs a = reframe_args(*cfg, n, H, W);
+    const ReframeSizes sz(a);
+    // guards of 16 elements keep a 16-byte boundary at the data's start; the three byte buffers are then shifted
+    Guarded<unsigned char> ds(sz.sal, 16, (size_t)offset, sal), df(frames ? sz.bgr : 0, 16, (size_t)(3 * offset % 16), frames),
+        dout(frames ? sz.crop : 0, 16, (size_t)(5 * offset % 16), nullptr);
+    Guarded<int32_t> dtrack(sz.pairs, 16, 0, nullptr), draw(sz.pairs, 16, 0, nullptr);
+    Guarded<uint32_t> dmass(sz.masses, 16, 0, nullptr), dsat(sz.sat, 16, 0, nullptr), dbest(sz.best, 16, 0, nullptr), dpart(sz.part, 16, 0, nullptr);
+    a.sal = ds.data(); a.frames = frames ? df.data() : nullptr; a.out = frames ? dout.data() : nullptr;
+    a.track = dtrack.data(); a.raw = draw.data(); a.mass = dmass.data(); a.sat = dsat.data(); a.best = dbest.data(); a.part = dpart.data();
+    HIPCHECK(p3d_reframe_launch(a, nullptr));
+    dtrack.back(track, who); draw.back(raw, who); dmass.back(mass, who);
+    dsat.back(nullptr, who); dbest.back(nullptr, who); dpart.back(nullptr, who);
+    if (frames) { dout.back(out, who); df.unchanged(who); }
+    ds.unchanged(who);
+    API_END
+}
+
+int p3d_debug_reframe_plan(int H, int W, int crop_h, int crop_w, int n, int* positions_per_block, int* search_blocks, int* maps_per_chunk,
+                           int64_t* scratch_bytes) {
+    API_BEGIN
+    if (!positions_per_block || !search_blocks || !maps_per_chunk || !scratch_bytes) throw P3dError("null argument");
+    if (H < 1 || W < 1 || (long long)H * W > P3D_REFRAME_MAX_PIXELS || n < 1 || n > 65535 || crop_h < 1 || crop_h > H || crop_w < 1 || crop_w > W)
+        throw P3dError("debug_reframe_plan: 1 <= H * W <= 2^23, 1 .. 65535 maps, a window inside the map");
+    const ReframePlan p = p3d_reframe_plan(H, W, crop_h, crop_w, n);
+    *positions_per_block = p.positions_per_block; *search_blocks = p.search_blocks; *maps_per_chunk = p.maps_per_chunk;
+    *scratch_bytes = (int64_t)p.scratch_bytes;
+    API_END
+}
+
+int p3d_video_reframe(p3d_handle* h, int first, int n, float scale, int H, int W, const unsigned char* frames, const p3d_reframe* cfg,
+                      int32_t* track, int32_t* raw, uint32_t* mass, unsigned char* out, unsigned char* maps_out, double* stage_ms) {
+    API_BEGIN
+    const char* who = "video_reframe";
+    if (!h) throw P3dError("null argument");
+    h->video_need_open(who);
+    if (frames && !out) throw P3dError(std::string(who) + ": frames are given but no out to receive the windows");
+    // before the shape: a call that leaves the size to the source has none to name when there is no source
+    if (out && !frames && !h->vid_src) throw P3dError(std::string(who) + ": no frames are given and the video keeps no source (p3d_video_keep_source before the first p3d_video_put_frames_u8)");
+    reframe_check(who, cfg, std::max(1, std::min(n, 65535)), H, W, track);
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    const VideoSource src(h, who, first, n, true, 65535);
+    ReframeRequest r{who, n, H, W};
+    r.cfg = cfg; r.frames = frames; r.track = track; r.raw = raw; r.mass = mass; r.out = out; r.timed = stage_ms != nullptr;
+    if (out && !frames) {
+        if (H != h->vid_H0 || W != h->vid_W0)
+            throw P3dError(std::string(who) + ": the kept source is " + std::to_string(h->vid_H0) + " x " + std::to_string(h->vid_W0) + ", the call reframes " +
+                           std::to_string(H) + " x " + std::to_string(W));
+        for (int f = first; f < first + n; ++f)
+            if (!h->vid_has_src[(size_t)f]) throw P3dError(std::string(who) + ": frame " + std::to_string(f) + " has no source (it was not put with p3d_video_put_frames_u8)");
+        r.frames_dev = h->vid_src + (size_t)first * (size_t)H * (size_t)W * 3;
+    }
+    ReframeStage stage(r);
+    for (int i = 0; stage_ms && i < 3; ++i) stage_ms[i] = 0.0;
+    maps_u8_chain(h, n, h->pred->H, h->pred->W, scale, H, W, maps_out, nullptr, src.extra(), src, nullptr, nullptr, &stage);
     if (stage_ms) { stage_ms[0] = frames ? stage.ms[0] : 0.0; stage_ms[1] = stage.ms[1]; stage_ms[2] = stage.ms[2]; }
     API_END
 }

@@ -1111,6 +1111,33 @@ __host__ __device__ inline RenderCut p3d_render_cut(uintptr_t as, uintptr_t af, 
 }
 hipError_t p3d_render_launch(const RenderArgs& a, hipStream_t s);
 
+// ---- reframing around 8-bit maps (reframe.hip; p3d_video_reframe / p3d_reframe_u8, the law in include/p3d_hip.h) ----
+// One launch sequence on n maps of H x W bytes: sal [n][H][W], frames [n][H][W][3] (null: tracks and masses only) -> track [n][2]
+// (Y, X), raw [n][2], mass [n][3] (M_best, M_smoothed, T), out [n][hc][wc][3] (null exactly when frames is); every buffer device
+// memory.  sat, best and part are scratch of p3d_reframe_plan's sat_elems, best_elems and part_elems words; sat starts on a 16-byte
+// boundary.  Per chunk of maps_per_chunk maps: the summed-area tables (two launches), the search, the pick; then the track, the
+// masses at the track's positions (two launches) and the crop.
+// Refused (hipErrorInvalidValue): a missing buffer, frames without out or out without frames, n outside [1, 65535], H * W outside
+// [1, 2^23], a window outside [1, H] x [1, W], a gate or radius outside [0, 255], a plan other than p3d_reframe_plan's.
+constexpr int P3D_REFRAME_MAX_PIXELS = 1 << 23;           // 255 * 2^23 < 2^31: a mass fits one unsigned word
+constexpr int P3D_REFRAME_CHUNK = 16;                     // at most this many maps' tables at a time, as P3D_POST_CHUNK
+constexpr long long P3D_REFRAME_SAT_BYTES = 64LL << 20;   // and at most this many bytes of tables (never less than one map's)
+constexpr int REFRAME_POSITIONS = 4096;                   // window positions a block of the search takes
+constexpr int REFRAME_MASS_SLICES = 16;                   // blocks that share the rows of one window when its mass is re-summed
+struct ReframePlan {
+    int maps_per_chunk = 0, positions_per_block = 0, search_blocks = 0;
+    long long sat_elems = 0, best_elems = 0, part_elems = 0, scratch_bytes = 0;
+};
+ReframePlan p3d_reframe_plan(int H, int W, int hc, int wc, int n);
+struct ReframeArgs {
+    const unsigned char* sal = nullptr; const unsigned char* frames = nullptr; unsigned char* out = nullptr;
+    int32_t* track = nullptr; int32_t* raw = nullptr; uint32_t* mass = nullptr;
+    unsigned* sat = nullptr; unsigned* best = nullptr; unsigned* part = nullptr;
+    int n = 0, H = 0, W = 0, hc = 0, wc = 0, gate = 0, radius = 0;
+    int maps_per_chunk = 0, search_blocks = 0;            // p3d_reframe_plan(H, W, hc, wc, n)
+};
+hipError_t p3d_reframe_launch(const ReframeArgs& a, hipStream_t s);
+
 // ---- misc ---------------------------------------------------------------------------------------
 hipError_t p3d_add_inplace(float* dst, int lddst, const float* src, int ldsrc, long M, int C, hipStream_t s);
 hipError_t p3d_copy_strided(float* dst, int lddst, const float* src, int ldsrc, long M, int C, hipStream_t s);

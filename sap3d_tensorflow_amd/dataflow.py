@@ -562,3 +562,101 @@ def render_overlay(sal, frames, table, contour=None, thickness=1, contour_color=
     else:
         check(lib().p3d_debug_render_u8(*args, int(offset), out.ctypes.data_as(u8)))
     return out if s.ndim == 3 else out[0]
+
+
+def _reframe_shape(sal, crop):
+    s = np.ascontiguousarray(sal)
+    if s.dtype != np.uint8 or s.ndim not in (2, 3) or s.size == 0:
+        raise ValueError("saliency maps are non-empty uint8 [H, W] or [n, H, W]")
+    s3 = s[None] if s.ndim == 2 else s
+    hc, wc = (int(crop), int(crop)) if np.isscalar(crop) else (int(crop[0]), int(crop[1]))
+    return s3, hc, wc
+
+
+def reframe_track(sal, crop, gate=0, smooth=0):
+    """The law of include/p3d_hip.h, "Reframing around 8-bit maps", stated in numpy on the host (integers only): saliency maps uint8
+    [n, H, W] (or [H, W]: one frame), crop = (hc, wc), the gate level and the smoothing radius -> (track int32 [n, 2], raw int32
+    [n, 2], mass uint32 [n, 3]): the smoothed and the raw (Y, X) of every frame, and M_best, M_smoothed, T.  The n maps are the
+    whole world of the smoothing filter."""
+    s3, hc, wc = _reframe_shape(sal, crop)
+    n, H, W = s3.shape
+    gate, R = int(gate), int(smooth)
+    if n > 65535 or H * W > 2 ** 23:
+        raise ValueError("1 .. 65535 maps of at most 2^23 pixels")
+    if not (1 <= hc <= H and 1 <= wc <= W):
+        raise ValueError("the window is %d x %d, the map %d x %d" % (hc, wc, H, W))
+    if not 0 <= gate <= 255 or not 0 <= R <= 255:
+        raise ValueError("the gate is a level 0 .. 255, the smoothing radius 0 .. 255 frames")
+    Hp, Wp = H - hc + 1, W - wc + 1
+    D = np.abs(2 * np.arange(Hp, dtype=np.int64) - (H - hc))[:, None] + np.abs(2 * np.arange(Wp, dtype=np.int64) - (W - wc))[None, :]
+    raw = np.empty((n, 2), np.int64)
+    mass = np.empty((n, 3), np.int64)
+    tables = []
+    for f in range(n):
+        w = np.where(s3[f] >= gate, s3[f], 0).astype(np.int64)
+        S = np.zeros((H + 1, W + 1), np.int64)
+        S[1:, 1:] = w.cumsum(0).cumsum(1)
+        M = S[hc:, wc:] - S[:Hp, wc:] - S[hc:, :Wp] + S[:Hp, :Wp]
+        best = M.max()
+        d = np.where(M == best, D, np.iinfo(np.int64).max)
+        y0, x0 = np.unravel_index(np.argmin(d), d.shape)      # the first of the smallest D in row-major order: smallest y0, then x0
+        raw[f] = (y0, x0)
+        mass[f, 0], mass[f, 2] = best, S[H, W]
+        tables.append(M if R else None)
+    if R:
+        idx = np.clip(np.arange(n)[:, None] + np.arange(-R, R + 1)[None, :], 0, n - 1)
+        track = (2 * raw[idx].sum(axis=1) + (2 * R + 1)) // (2 * (2 * R + 1))
+        mass[:, 1] = [tables[f][track[f, 0], track[f, 1]] for f in range(n)]
+    else:
+        track = raw.copy()
+        mass[:, 1] = mass[:, 0]
+    return track.astype(np.int32), raw.astype(np.int32), mass.astype(np.uint32)
+
+
+def reframe_crop(frames, track, crop):
+    """frames uint8 [n, H, W, 3], a track int [n, 2] of (Y, X) and crop = (hc, wc) -> uint8 [n, hc, wc, 3], frame f's window at its
+    track position, not resized (the CROP rule of include/p3d_hip.h, "Reframing around 8-bit maps")."""
+    f = np.asarray(frames)
+    t = np.asarray(track)
+    hc, wc = (int(crop), int(crop)) if np.isscalar(crop) else (int(crop[0]), int(crop[1]))
+    if f.dtype != np.uint8 or f.ndim != 4 or f.shape[3] != 3 or t.shape != (f.shape[0], 2):
+        raise ValueError("frames are uint8 [n, H, W, 3] and the track [n, 2]")
+    if (t < 0).any() or (t[:, 0] + hc > f.shape[1]).any() or (t[:, 1] + wc > f.shape[2]).any():
+        raise ValueError("a window of the track leaves the frame")
+    return np.stack([f[i, y:y + hc, x:x + wc] for i, (y, x) in enumerate(t)])
+
+
+def reframe_plan(H, W, crop, n=1):
+    """Test hook (p3d_debug_reframe_plan, host only): dict(positions_per_block, search_blocks, maps_per_chunk, scratch_bytes) of the
+    reframe launches for n maps of H x W and a window crop = (hc, wc)."""
+    hc, wc = (int(crop), int(crop)) if np.isscalar(crop) else (int(crop[0]), int(crop[1]))
+    p, b, m, s = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int64(0)
+    check(lib().p3d_debug_reframe_plan(int(H), int(W), hc, wc, int(n), C.byref(p), C.byref(b), C.byref(m), C.byref(s)))
+    return dict(positions_per_block=p.value, search_blocks=b.value, maps_per_chunk=m.value, scratch_bytes=s.value)
+
+
+def reframe(sal, frames, crop, gate=0, smooth=0, device=0, offset=None):
+    """reframe_track and reframe_crop on the device (p3d_reframe_u8): saliency maps uint8 [n, H, W], frames uint8 [n, H, W, 3] in
+    B, G, R order or None -> (track, raw, mass, crop or None).  offset (0 .. 15): the test hook p3d_debug_reframe_u8, every device
+    buffer between guards and shifted off a 16-byte boundary."""
+    from ._lib import P3dReframe
+    s3, hc, wc = _reframe_shape(sal, crop)
+    n, H, W = s3.shape
+    f = None
+    if frames is not None:
+        f = np.ascontiguousarray(frames)
+        if f.dtype != np.uint8 or f.shape != s3.shape + (3,):
+            raise ValueError("frames are uint8 %s, the maps' shape with three channels" % (s3.shape + (3,),))
+    cfg = P3dReframe(hc, wc, int(gate), int(smooth))
+    track, raw, mass = np.empty((n, 2), np.int32), np.empty((n, 2), np.int32), np.empty((n, 3), np.uint32)
+    out = None if f is None or not (1 <= hc <= H and 1 <= wc <= W) else np.empty((n, hc, wc, 3), np.uint8)
+    if f is not None and out is None:
+        out = np.empty((1,), np.uint8)                        # (the library refuses the window before it writes)
+    u8, i32, u32 = C.POINTER(C.c_ubyte), C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
+    head = (device, s3.ctypes.data_as(u8), None if f is None else f.ctypes.data_as(u8), n, H, W, C.byref(cfg))
+    tail = (track.ctypes.data_as(i32), raw.ctypes.data_as(i32), mass.ctypes.data_as(u32), None if out is None else out.ctypes.data_as(u8))
+    if offset is None:
+        check(lib().p3d_reframe_u8(*head, *tail))
+    else:
+        check(lib().p3d_debug_reframe_u8(*head, int(offset), *tail))
+    return track, raw, mass, (out if f is not None else None)

@@ -979,6 +979,51 @@ class P3DSession:
             self.last_render_ms = dict(upload=ms[0], device=ms[1], render=ms[2])
         return (out, maps) if with_maps else out
 
+    def video_reframe(self, first, n, crop, frames=None, size=None, scale=255., gate=0, smooth=0, with_raw=False, with_mass=False,
+                      with_maps=False, timed=False):
+        """Frames first .. first + n - 1 of the open video reframed around their saliency, on the device (an addition): per frame
+        the crop = (hc, wc) window of the largest gated saliency mass, the track box-smoothed over `smooth` frames to either side
+        WITHIN THIS CALL (ask for the whole video in one call for one track) -> dict(track int32 [n, 2] (Y, X), crop uint8
+        [n, hc, wc, 3] in B, G, R order or None).  The maps are video_maps_u8's bytes at `size`, where they are.  frames: uint8
+        [n, H, W, 3] at that size, None for the source kept by video_keep_source (size then defaults to, and must be, the
+        source's own), or False for the tracks alone (size is then required).  with_raw / with_mass / with_maps add raw int32
+        [n, 2], mass uint32 [n, 3] (best, smoothed, total) and maps uint8 [n, H, W].  timed: HIP-event times are left in
+        `last_reframe_ms` (upload, device = the maps' chain, reframe).  include/p3d_hip.h holds the exact rules."""
+        tracks_only = frames is False
+        if size is None:
+            if tracks_only:
+                raise ValueError("tracks alone (frames=False) need a size")
+            size = self.video_source_info()["size"] if frames is None else np.shape(frames)[1:3]
+        H, W = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
+        hc, wc = (int(crop), int(crop)) if np.isscalar(crop) else (int(crop[0]), int(crop[1]))
+        n = max(int(n), 0)
+        f = None
+        if frames is not None and not tracks_only:
+            f = np.ascontiguousarray(frames)
+            if f.dtype != np.uint8 or f.shape != (n, H, W, 3):
+                raise ValueError("frames are %s %s, expected uint8 %s" % (f.dtype, f.shape, (n, H, W, 3)))
+        cfg = _lib.P3dReframe(hc, wc, int(gate), int(smooth))
+        valid = H >= 1 and W >= 1 and H * W <= 2 ** 23 and 1 <= hc <= H and 1 <= wc <= W      # (the library refuses the rest)
+        track = np.empty((n, 2), np.int32)
+        raw = np.empty((n, 2), np.int32) if with_raw else None
+        mass = np.empty((n, 3), np.uint32) if with_mass else None
+        out = None if tracks_only else np.empty((n, hc, wc, 3) if valid else (0,), np.uint8)
+        maps = np.empty((n, H, W) if valid else (0,), np.uint8) if with_maps else None
+        ms = (C.c_double * 3)()
+        check(lib().p3d_video_reframe(self._h, int(first), n, float(scale), H, W, _ptr(f, _lib._u8p), C.byref(cfg), _ptr(track, _lib._i32p),
+                                      _ptr(raw, _lib._i32p), _ptr(mass, _lib._u32p), _ptr(out, _lib._u8p), _ptr(maps, _lib._u8p),
+                                      ms if timed else None))
+        if timed:
+            self.last_reframe_ms = dict(upload=ms[0], device=ms[1], reframe=ms[2])
+        res = dict(track=track, crop=out)
+        if with_raw:
+            res["raw"] = raw
+        if with_mass:
+            res["mass"] = mass
+        if with_maps:
+            res["maps"] = maps
+        return res
+
     def video_shuffled_begin(self, ids):
         """The union of the fixation pool's maps ids[b] (int [n, M], 1 <= M <= 64) for each of n frames that video_score_auc will
         score, counted and scanned on the device -> n_other uint32 [n].  Held apart from shuffled_begin's union: an armed
