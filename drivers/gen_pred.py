@@ -123,30 +123,50 @@ def predict_video_resident(sess, video_u8, batch, stride=1, overlap="newest", ti
     return F
 
 
-def hand_over(pool, held, write, first, maps):
-    """Waits for the images in flight (`held`: the previous chunk's, encoded while this one ran on the device), then submits
-    write(frame, map) for this chunk's maps, frames first, first + 1, ... -> the futures now in flight."""
-    for fut in held:
-        fut.result()
-    return [pool.submit(write, first + k, m) for k, m in enumerate(maps)]
+class ChunkWriter:
+    """Encodes chunks of images on `writers` threads (PIL releases the GIL while it compresses) while the device runs the next
+    chunk.  hand_over(frames, images) waits for the chunk in flight, encoded while this one ran on the device, then submits
+    write_one(frame, image) for every pair; leaving the `with` block waits for the last chunk.  So at most two chunks of images
+    are held, and an exception of write_one surfaces in the caller at the next hand_over or at the block's end.  encode_ms: the
+    thread time spent in write_one."""
+
+    def __init__(self, writers, write_one):
+        import threading
+        from concurrent.futures import ThreadPoolExecutor
+        self.pool, self.lock = ThreadPoolExecutor(max_workers=writers), threading.Lock()
+        self.write_one, self.held, self.encode_ms = write_one, [], 0.0
+
+    def _write(self, f, m):
+        t0 = time.perf_counter()
+        self.write_one(f, m)
+        with self.lock:
+            self.encode_ms += (time.perf_counter() - t0) * 1e3
+
+    def wait(self):
+        held, self.held = self.held, []
+        for fut in held:
+            fut.result()
+
+    def hand_over(self, frames, images):
+        self.wait()
+        self.held = [self.pool.submit(self._write, f, m) for f, m in zip(frames, images)]
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, kind, *_):
+        try:
+            if kind is None:
+                self.wait()
+        finally:
+            self.pool.shutdown(wait=True)
 
 
 def write_video_images_resident(sess, F, video_dir, ext, size=(1080, 960), writers=4):
     """write_video_images for the open video: its maps leave the device 16 at a time (video_maps_u8) while the previous 16 are
     encoded.  Returns the same dict; gpu is the wall time of the map stages alone."""
-    import threading
-    from concurrent.futures import ThreadPoolExecutor
     t = dict(gpu=0.0, device=0.0, d2h=0.0, encode=0.0, files=0)
-    lock = threading.Lock()
-
-    def write(f, m):
-        t0 = time.perf_counter()
-        save_image(os.path.join(video_dir, "frame_%d.%s" % (f + 1, ext)), m, ext)
-        with lock:
-            t["encode"] += (time.perf_counter() - t0) * 1e3
-
-    held = []
-    with ThreadPoolExecutor(max_workers=writers) as pool:
+    with ChunkWriter(writers, lambda f, m: save_image(os.path.join(video_dir, "frame_%d.%s" % (f + 1, ext)), m, ext)) as w:
         for first in range(0, F, 16):
             n = min(16, F - first)
             t0 = time.perf_counter()
@@ -154,9 +174,9 @@ def write_video_images_resident(sess, F, video_dir, ext, size=(1080, 960), write
             t["gpu"] += (time.perf_counter() - t0) * 1e3
             t["device"] += sess.last_maps_ms["device"]
             t["d2h"] += sess.last_maps_ms["d2h"]
-            held = hand_over(pool, held, write, first, maps)
+            w.hand_over(range(first, first + n), maps)
             t["files"] += n
-        hand_over(pool, held, write, F, ())
+    t["encode"] = w.encode_ms
     return t
 
 
@@ -165,19 +185,8 @@ def render_video_resident(sess, F, video_dir, render, writers=4):
     video's own size), 16 at a time while the previous 16 are encoded -> <video_dir>/frame_<k>.png, k = 1..F, colour.  render:
     the keyword arguments of video_render.  Returns milliseconds: gpu (wall time of the calls), the three device stages, encode
     (thread time), and the number of files."""
-    import threading
-    from concurrent.futures import ThreadPoolExecutor
     t = dict(gpu=0.0, upload=0.0, device=0.0, render=0.0, encode=0.0, files=0)
-    lock = threading.Lock()
-
-    def write(f, m):
-        t0 = time.perf_counter()
-        save_color_image(os.path.join(video_dir, "frame_%d.png" % (f + 1)), m)
-        with lock:
-            t["encode"] += (time.perf_counter() - t0) * 1e3
-
-    held = []
-    with ThreadPoolExecutor(max_workers=writers) as pool:
+    with ChunkWriter(writers, lambda f, m: save_color_image(os.path.join(video_dir, "frame_%d.png" % (f + 1)), m)) as w:
         for first in range(0, F, 16):
             n = min(16, F - first)
             t0 = time.perf_counter()
@@ -185,9 +194,9 @@ def render_video_resident(sess, F, video_dir, render, writers=4):
             t["gpu"] += (time.perf_counter() - t0) * 1e3
             for k in ("upload", "device", "render"):
                 t[k] += sess.last_render_ms[k]
-            held = hand_over(pool, held, write, first, images)
+            w.hand_over(range(first, first + n), images)
             t["files"] += n
-        hand_over(pool, held, write, F, ())
+    t["encode"] = w.encode_ms
     return t
 
 
@@ -211,20 +220,11 @@ def reframe_video_resident(sess, F, video_dir, reframe, writers=4):
     TRACK_COLUMNS' order.  ONE call for the whole video: the track's filter sees every frame.  reframe: dict(size=(hc, wc) or
     aspect=(a, b), gate, smooth).  Returns milliseconds: gpu (wall time of the call), the three device stages, encode (thread
     time), the number of files and the window."""
-    import threading
-    from concurrent.futures import ThreadPoolExecutor
     t = dict(gpu=0.0, upload=0.0, device=0.0, reframe=0.0, encode=0.0, files=0)
-    lock = threading.Lock()
     H0, W0 = sess.video_source_info()["size"]
     crop = tuple(reframe["size"]) if reframe.get("size") else aspect_window(H0, W0, *reframe["aspect"])
     if not (1 <= crop[0] <= H0 and 1 <= crop[1] <= W0):
         raise ValueError("--reframe: a %d x %d window does not fit the video's %d x %d frames" % (crop + (H0, W0)))
-
-    def write(f, m):
-        t0 = time.perf_counter()
-        save_color_image(os.path.join(video_dir, "frame_%d.png" % (f + 1)), m)
-        with lock:
-            t["encode"] += (time.perf_counter() - t0) * 1e3
 
     t0 = time.perf_counter()
     res = sess.video_reframe(0, F, crop, gate=reframe["gate"], smooth=reframe["smooth"], with_raw=True, with_mass=True, timed=True)
@@ -232,12 +232,10 @@ def reframe_video_resident(sess, F, video_dir, reframe, writers=4):
     for k in ("upload", "device", "reframe"):
         t[k] = sess.last_reframe_ms[k]
     np.save(os.path.join(video_dir, "track.npy"), np.concatenate([res["track"], res["raw"], res["mass"]], axis=1).astype(np.int64))
-    with ThreadPoolExecutor(max_workers=writers) as pool:
-        held = []
+    with ChunkWriter(writers, lambda f, m: save_color_image(os.path.join(video_dir, "frame_%d.png" % (f + 1)), m)) as w:
         for first in range(0, F, 16):
-            held = hand_over(pool, held, write, first, res["crop"][first:first + 16])
-        hand_over(pool, held, write, F, ())
-    t["files"], t["window"] = F, crop
+            w.hand_over(range(first, min(first + 16, F)), res["crop"][first:first + 16])
+    t["encode"], t["files"], t["window"] = w.encode_ms, F, crop
     return t
 
 
@@ -292,18 +290,12 @@ def score_video_resident(sess, F, density, fixation, size, columns, ties, auc=No
     where not asked.  One RandomState(seed) per video; per chunk of SCORE_CHUNK frames it draws, in this order: the rows of pool
     slots in frame order (sauc_ids), [video_shuffled_begin], Borji's randint per frame with fixations (metrics.borji_draws_u8),
     metrics.shuffled_draws.  With video_dir the images then come from video_maps_u8, one more run of the maps' chain per chunk."""
-    from concurrent.futures import ThreadPoolExecutor
     from sap3d_tensorflow_amd import metrics
     scores = np.full((F, len(SCORE_NAMES)), np.nan, np.float64)
     means = np.full((F, 2), np.nan, np.float64) if auc else None
     t = dict(upload=0.0, device=0.0, score=0.0, files=0, **(dict(auc=0.0) if auc else {}))
     rng = np.random.RandomState(auc["seed"]) if auc else None
-
-    def write(f, m):
-        save_image(os.path.join(video_dir, "frame_%d.%s" % (f + 1, ext)), m, ext)
-
-    held = []
-    with ThreadPoolExecutor(max_workers=writers) as pool:
+    with ChunkWriter(writers, lambda f, m: save_image(os.path.join(video_dir, "frame_%d.%s" % (f + 1, ext)), m, ext)) as w:
         for first in range(0, F, SCORE_CHUNK):
             n = min(SCORE_CHUNK, F - first)
             den, fix, maps = density[first:first + n], fixation[first:first + n], None
@@ -331,9 +323,8 @@ def score_video_resident(sess, F, density, fixation, size, columns, ties, auc=No
                 t[k] += ms
             scores[first:first + n] = got
             if video_dir is not None:
-                held = hand_over(pool, held, write, first, sess.video_maps_u8(first, n, size=size) if auc else maps)
+                w.hand_over(range(first, first + n), sess.video_maps_u8(first, n, size=size) if auc else maps)
                 t["files"] += n
-        hand_over(pool, held, write, F, ())
     return scores, means, t
 
 
@@ -373,34 +364,22 @@ def write_video_images(sess, frames, batch, video_dir, ext, size=(1080, 960), wr
     threads (PIL releases the GIL while it compresses) while the device runs the next batch; at most two batches of maps are
     held.  Returns milliseconds: gpu (wall time of the forward passes and map stages), device / d2h (pred_maps_u8's device
     times), encode (thread time spent encoding), and the number of files."""
-    import threading
-    from concurrent.futures import ThreadPoolExecutor
     t = dict(gpu=0.0, device=0.0, d2h=0.0, encode=0.0, files=0)
-    lock = threading.Lock()
-
-    def write(f, m):
-        t0 = time.perf_counter()
-        save_image(os.path.join(video_dir, "frame_%d.%s" % (f + 1, ext)), m, ext)
-        with lock:
-            t["encode"] += (time.perf_counter() - t0) * 1e3
-
-    held = []
-    with ThreadPoolExecutor(max_workers=writers) as pool:
+    with ChunkWriter(writers, lambda f, m: save_image(os.path.join(video_dir, "frame_%d.%s" % (f + 1, ext)), m, ext)) as w:
         batches = predict_video_images(sess, frames, batch, size=size)
         while True:
             t0 = time.perf_counter()
             nxt = next(batches, None)
             t["gpu"] += (time.perf_counter() - t0) * 1e3
-            for fut in held:              # the previous batch, encoded while this one ran on the device
-                fut.result()
             if nxt is None:
                 break
             idx, maps = nxt
             ms = getattr(sess, "last_maps_ms", None) or {}
             t["device"] += ms.get("device", 0.0)
             t["d2h"] += ms.get("d2h", 0.0)
-            held = [pool.submit(write, f, m) for f, m in zip(idx, maps)]
-            t["files"] += len(held)
+            w.hand_over(idx, maps)
+            t["files"] += len(idx)
+    t["encode"] = w.encode_ms
     return t
 
 

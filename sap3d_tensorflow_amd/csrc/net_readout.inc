@@ -713,20 +713,20 @@ int p3d_resize_linear_u8(int device, const float* src, int n, int h, int w, floa
 
 }  // extern "C"
 namespace {
-// gen_pred.py's write-out of `maps` maps that live on the device, for p3d_pred_maps_u8 and p3d_video_maps_u8: the bytes, the
-// scratch of p3d_set_postprocess's stage and `extra` floats of the caller's share one slab of the stream's scratch.  sources runs
-// inside the device stage's time: it queues whatever makes the maps readable and names them as runs of maps of ph x pw pixels.
-// Off: one double-precision p3d_resize_u8 per run; on: the float32 resize / blur / normalise / byte sequence, P3D_POST_CHUNK maps
-// at a time.  Ends synchronised; stage_ms as p3d_pred_maps_u8's.
-// A score stage (p3d_video_score, p3d_video_score_auc) takes the device bytes where they are instead of a copy of the chain: its
-// buffers are carved after the chain's in the same layout, its upload is queued ahead of the sources, its launches behind the chain
-// with the bytes and counters() zeroed arrival counters of its own, its results (the copies back to the host) behind that; out may
-// then be NULL (the bytes stay on the device) and, timed, its ms [3] receives the times of the upload, of the device stage and of
-// the launches.  Without one, nothing here differs from what the two callers issued before.
-// A render stage (p3d_video_render) is a second consumer of the same kind and follows the score stage at each of the four moments;
-// it has no counters.  Without one, nothing here differs from what the callers issued before it existed.
-// A reframe stage (p3d_video_reframe) is a third, behind the render stage at each moment, with no counters either: its launches
-// hand results to one another from launch to launch.  Without one, nothing here differs from what the callers issued before.
+// What runs behind n maps of H x W device bytes, at four moments: carve (its buffers, from a caller's scratch), upload, launch,
+// results.  A constructor refuses what its request gets wrong and queues nothing.
+struct ByteStage {
+    const char* who; int n, H, W;
+    size_t bytes; bool timed; double ms[3] = {0.0, 0.0, 0.0};
+    template <typename Request>
+    explicit ByteStage(const Request& r) : who(r.who), n(r.n), H(r.H), W(r.W), bytes((size_t)r.n * (size_t)r.H * (size_t)r.W), timed(r.timed) {}
+    virtual ~ByteStage() = default;
+    virtual size_t counters() const { return 0; }
+    virtual void carve(Carve& c) = 0;
+    virtual void upload(hipStream_t s) = 0;
+    virtual void launch(hipStream_t s, const unsigned char* sal, unsigned* counters) = 0;
+    virtual void results(hipStream_t s) = 0;
+};
 // What one scoring of n maps of H x W bytes asks for; every pointer is host memory.  Whatever is not asked for is not issued.
 struct ScoreRequest {
     const char* who; int n, H, W;
@@ -741,25 +741,25 @@ struct ScoreRequest {
 };
 // The launches of score_u8.hip and score_auc_u8.hip behind some device bytes: the launch arguments, the tables of the host and the
 // device buffers, carved from a caller's scratch.  The constructor refuses what the request's arrays get wrong and queues nothing.
-struct ScoreStage {
-    const ScoreRequest r; const size_t bytes;
+struct ScoreStage : ByteStage {
+    const ScoreRequest r;
     ScoreArgs a; ScoreSweepArgs q;
     std::vector<int> nf, meta3, info; std::vector<long long> metaB, metaS;
     size_t totB = 0, totS = 0; int max_rows = 0;
     unsigned char* dd = nullptr; unsigned char* dx = nullptr;
     int* didx = nullptr; int* dranks = nullptr; int* dsel = nullptr; int* dmeta3 = nullptr; int* drows = nullptr;
     long long* dmetaB = nullptr; long long* dmetaS = nullptr; double* perB = nullptr; double* perS = nullptr;
-    StageTimer sweeps; double ms[3] = {0.0, 0.0, 0.0};
+    StageTimer sweeps;
     explicit ScoreStage(const ScoreRequest& r);
     bool sweep() const { return r.borji || r.shuffled; }
-    size_t counters() const;
-    void carve(Carve& c);
-    void upload(hipStream_t s);
+    size_t counters() const override;
+    void carve(Carve& c) override;
+    void upload(hipStream_t s) override;
     // pass A and the columns, then the sweeps' preparation (q.info: the device's counts); sweep_rest: the sweeps themselves
     void prepare(hipStream_t s, const unsigned char* sal, unsigned* counters);
     void sweep_rest(hipStream_t s);
-    void launch(hipStream_t s, const unsigned char* sal, unsigned* counters) { prepare(s, sal, counters); sweep_rest(s); }
-    void results(hipStream_t s);
+    void launch(hipStream_t s, const unsigned char* sal, unsigned* counters) override { prepare(s, sal, counters); sweep_rest(s); }
+    void results(hipStream_t s) override;
     void check_counts() const;                            // after the results have arrived: the device's counts against nf
     double sweep_ms() const { return sweeps.ev[0] ? (double)sweeps.ms(0) : 0.0; }
 };
@@ -771,18 +771,17 @@ struct RenderRequest {
     const unsigned char* frames = nullptr; const unsigned char* frames_dev = nullptr; unsigned char* out = nullptr;
     bool timed = false;
 };
-// The launch of render.hip behind some device bytes, with ScoreStage's four moments.  It has no arrival counters: its blocks share
-// nothing.  render_check has passed cfg and the shape before one is built; the constructor queues nothing.
-struct RenderStage {
-    const RenderRequest r; const size_t bytes;
+// The launch of render.hip behind some device bytes.  It has no arrival counters: its blocks share nothing.  render_check has
+// passed cfg and the shape before one is built.
+struct RenderStage : ByteStage {
+    const RenderRequest r;
     RenderArgs a;
     unsigned char* df = nullptr; unsigned char* dout = nullptr; unsigned* dtab = nullptr;
-    double ms[3] = {0.0, 0.0, 0.0};
     explicit RenderStage(const RenderRequest& r);
-    void carve(Carve& c);
-    void upload(hipStream_t s);
-    void launch(hipStream_t s, const unsigned char* sal);
-    void results(hipStream_t s);
+    void carve(Carve& c) override;
+    void upload(hipStream_t s) override;
+    void launch(hipStream_t s, const unsigned char* sal, unsigned*) override;
+    void results(hipStream_t s) override;
 };
 // What one reframing of n maps of H x W bytes asks for: frames on the host (uploaded), or on the device where they are (the kept
 // source), or neither (tracks and masses only); track, raw, mass and out on the host, whatever is null is not copied back.
@@ -793,23 +792,32 @@ struct ReframeRequest {
     int32_t* track = nullptr; int32_t* raw = nullptr; uint32_t* mass = nullptr; unsigned char* out = nullptr;
     bool timed = false;
 };
-// The launches of reframe.hip behind some device bytes, with ScoreStage's four moments and no arrival counters.  reframe_check has
-// passed cfg and the shape before one is built; the constructor queues nothing.
-struct ReframeStage {
-    const ReframeRequest r; const size_t bytes;
+// The launches of reframe.hip behind some device bytes, with no arrival counters: they hand results to one another from launch to
+// launch.  reframe_check has passed cfg and the shape before one is built.
+struct ReframeStage : ByteStage {
+    const ReframeRequest r;
     ReframeArgs a;
     unsigned char* df = nullptr;
-    double ms[3] = {0.0, 0.0, 0.0};
     explicit ReframeStage(const ReframeRequest& r);
     bool crops() const { return r.out != nullptr; }
-    void carve(Carve& c);
-    void upload(hipStream_t s);
-    void launch(hipStream_t s, const unsigned char* sal);
-    void results(hipStream_t s);
+    void carve(Carve& c) override;
+    void upload(hipStream_t s) override;
+    void launch(hipStream_t s, const unsigned char* sal, unsigned*) override;
+    void results(hipStream_t s) override;
 };
+// gen_pred.py's write-out of `maps` maps that live on the device, for p3d_pred_maps_u8 and p3d_video_maps_u8: the bytes, the
+// scratch of p3d_set_postprocess's stage and `extra` floats of the caller's share one slab of the stream's scratch.  sources runs
+// inside the device stage's time: it queues whatever makes the maps readable and names them as runs of maps of ph x pw pixels.
+// Off: one double-precision p3d_resize_u8 per run; on: the float32 resize / blur / normalise / byte sequence, P3D_POST_CHUNK maps
+// at a time.  Ends synchronised; stage_ms as p3d_pred_maps_u8's.
+// A stage (ByteStage: score, render, reframe) takes the device bytes where they are instead of a copy of the chain: its buffers are
+// carved after the chain's in the same layout, its upload is queued ahead of the sources, its launches behind the chain with the
+// bytes and counters() zeroed arrival counters of its own (after the chain's), its results (the copies back to the host) behind
+// that; out may then be NULL (the bytes stay on the device) and, timed, its ms [3] receives the times of the upload, of the device
+// stage and of the launches.  Without one, nothing here differs from what p3d_pred_maps_u8 and p3d_video_maps_u8 issue.
 void maps_u8_chain(p3d_handle* h, long long maps, int ph, int pw, float scale, int H, int W, unsigned char* out, double* stage_ms,
                    size_t extra, const std::function<void(hipStream_t, float*, std::vector<PostRun>&)>& sources,
-                   ScoreStage* use = nullptr, RenderStage* paint = nullptr, ReframeStage* cut = nullptr) {
+                   ByteStage* stage = nullptr) {
     const long long hw = (long long)H * W, bytes = maps * hw;
     const hipStream_t s = h->stream;
     // p3d_set_postprocess: the float32 chain resize -> blur -> normalise -> bytes, P3D_POST_CHUNK maps at a time; its scratch
@@ -827,20 +835,16 @@ void maps_u8_chain(p3d_handle* h, long long maps, int ph, int pw, float scale, i
     unsigned char* d = nullptr;
     float* ex = nullptr;
     const size_t chain_counters = chain ? (size_t)post_chunk : 0;
-    unsigned* const counters = carve_scratch(s, chain_counters + (use ? use->counters() : 0), [&](Carve& c) {
+    unsigned* const counters = carve_scratch(s, chain_counters + (stage ? stage->counters() : 0), [&](Carve& c) {
         d = c.take<unsigned char>((size_t)bytes);      // (the first take starts at offset 0: with nothing else, the slab is the bytes)
         if (chain) scratch.carve(c, st, post_chunk, hw, true);
         ex = extra ? c.take<float>(extra) : nullptr;
-        if (use) use->carve(c);
-        if (paint) paint->carve(c);
-        if (cut) cut->carve(c);
+        if (stage) stage->carve(c);
     });
-    const bool use_timed = (use && use->r.timed) || (paint && paint->r.timed) || (cut && cut->r.timed);
-    StageTimer tm(stage_ms != nullptr || use_timed, 3), ends(use_timed, 2);
+    const bool timed = stage && stage->timed;
+    StageTimer tm(stage_ms != nullptr || timed, 3), ends(timed, 2);
     ends.mark(0, s);
-    if (use) use->upload(s);
-    if (paint) paint->upload(s);
-    if (cut) cut->upload(s);
+    if (stage) stage->upload(s);
     tm.mark(0, s);
     PostJob job;
     sources(s, ex, job.runs);
@@ -855,23 +859,18 @@ void maps_u8_chain(p3d_handle* h, long long maps, int ph, int pw, float scale, i
         }
     }
     tm.mark(1, s);
-    if (use) use->launch(s, d, counters + chain_counters);
-    if (paint) paint->launch(s, d);
-    if (cut) cut->launch(s, d);
+    if (stage) stage->launch(s, d, counters + chain_counters);
     ends.mark(1, s);
-    if (use) use->results(s);
-    if (paint) paint->results(s);
-    if (cut) cut->results(s);
+    if (stage) stage->results(s);
     if (out) HIPCHECK(hipMemcpyAsync(out, d, (size_t)bytes, hipMemcpyDeviceToHost, s));
     tm.mark(2, s);
     HIPCHECK(hipStreamSynchronize(s));
     if (stage_ms) { stage_ms[0] = tm.ms(0); stage_ms[1] = tm.ms(1); }
-    if (use_timed) {
+    if (timed) {
         float up = 0.f, sc = 0.f;
         HIPCHECK(hipEventElapsedTime(&up, ends.ev[0], tm.ev[0]));
         HIPCHECK(hipEventElapsedTime(&sc, tm.ev[1], ends.ev[1]));
-        double* const ms = use ? use->ms : paint ? paint->ms : cut->ms;
-        ms[0] = (double)up; ms[1] = tm.ms(0); ms[2] = (double)sc;
+        stage->ms[0] = (double)up; stage->ms[1] = tm.ms(0); stage->ms[2] = (double)sc;
     }
 }
 }  // namespace
@@ -1775,13 +1774,51 @@ int p3d_video_maps_u8(p3d_handle* h, int first, int n, float scale, int H, int W
 
 }  // extern "C"
 namespace {
+// ---- what every stage's entry points share ----------------------------------------------------------------------------------------
+// The shape every read-out of 8-bit maps takes; bound: what H * W exceeds, in the refusal's words
+void map_shape_check(const char* who, int n, int H, int W, long long max_pixels, const char* bound) {
+    if (n < 1 || n > 65535) throw P3dError(std::string(who) + ": 1 .. 65535 maps");
+    if (H < 1 || W < 1) throw P3dError(std::string(who) + ": empty map");
+    if ((long long)H * W > max_pixels) throw P3dError(std::string(who) + ": H * W exceeds " + bound);
+}
+// op level: the stage behind the host's bytes, on the null stream's scratch.  Ends synchronised.
+void stage_on_host_bytes(ByteStage& stage, const unsigned char* sal) {
+    DevArr<unsigned char> ds(stage.bytes, sal);
+    unsigned* const counters = carve_scratch(nullptr, stage.counters(), [&](Carve& c) { stage.carve(c); });
+    stage.upload(nullptr);
+    stage.launch(nullptr, ds.p, counters);
+    stage.results(nullptr);
+    HIPCHECK(hipDeviceSynchronize());
+}
+// Frames first .. first + n - 1 of the source the open video keeps, for a call that `verb` ("renders", "reframes") H x W frames
+const unsigned char* kept_source(const p3d_handle* h, const char* who, int first, int n, int H, int W, const char* verb) {
+    if (H != h->vid_H0 || W != h->vid_W0)
+        throw P3dError(std::string(who) + ": the kept source is " + std::to_string(h->vid_H0) + " x " + std::to_string(h->vid_W0) + ", the call " + verb + " " +
+                       std::to_string(H) + " x " + std::to_string(W));
+    for (int f = first; f < first + n; ++f)
+        if (!h->vid_has_src[(size_t)f]) throw P3dError(std::string(who) + ": frame " + std::to_string(f) + " has no source (it was not put with p3d_video_put_frames_u8)");
+    return h->vid_src + (size_t)first * (size_t)H * (size_t)W * 3;
+}
+void need_kept_source(const p3d_handle* h, const char* who) {
+    if (!h->vid_src) throw P3dError(std::string(who) + ": no frames are given and the video keeps no source (p3d_video_keep_source before the first p3d_video_put_frames_u8)");
+}
+// p3d_video_score, _score_auc, _render and _reframe behind the checks of their arguments: at most 65535 of the video's frames
+// through the maps' chain, the stage behind its bytes.  make builds the stage once the source has passed, so that what the stage
+// (or the kept source it reads) refuses is refused after it.  stage_ms (null, or n_ms >= 3 values): zeroed, then the stage's ms.
+void video_stage_run(p3d_handle* h, const char* who, int first, int n, float scale, unsigned char* maps_out, double* stage_ms, int n_ms,
+                     const std::function<ByteStage&()>& make) {
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    const VideoSource src(h, who, first, n, true, 65535);
+    ByteStage& stage = make();
+    for (int i = 0; stage_ms && i < n_ms; ++i) stage_ms[i] = 0.0;
+    maps_u8_chain(h, n, h->pred->H, h->pred->W, scale, stage.H, stage.W, maps_out, nullptr, src.extra(), src, &stage);
+    for (int i = 0; stage_ms && i < 3; ++i) stage_ms[i] = stage.ms[i];
+}
 // ---- scoring 8-bit maps (score_u8.hip; the law in include/p3d_hip.h): one check, one table of buffer sizes and one launch
 // sequence for the score stage and p3d_debug_score_u8 ------------------------------------------------------------------------------
 void score_check(const char* who, const void* density, const void* fixation, int n, int H, int W, int flags, int ties, const void* out) {
     if (!density || !out) throw P3dError("null argument");
-    if (n < 1 || n > 65535) throw P3dError(std::string(who) + ": 1 .. 65535 maps");
-    if (H < 1 || W < 1) throw P3dError(std::string(who) + ": empty map");
-    if ((long long)H * W > P3D_SCORE_MAX_PIXELS) throw P3dError(std::string(who) + ": H * W exceeds 2^23, the bound of the 64-bit integer sums");
+    map_shape_check(who, n, H, W, P3D_SCORE_MAX_PIXELS, "2^23, the bound of the 64-bit integer sums");
     if (flags <= 0 || (flags & ~P3D_SCORE_ALL)) throw P3dError(std::string(who) + ": flags are a non-empty set of P3D_SCORE_CC | SIM | JUDD | KL | NSS");
     if (ties != P3D_SCORE_TIES_REFERENCE && ties != P3D_SCORE_TIES_EXPECTED) throw P3dError(std::string(who) + ": ties is P3D_SCORE_TIES_REFERENCE or P3D_SCORE_TIES_EXPECTED");
     if (!fixation && (flags & (P3D_SCORE_JUDD | P3D_SCORE_NSS))) throw P3dError(std::string(who) + ": AUC_Judd and NSS need the fixation maps");
@@ -1813,12 +1850,7 @@ int p3d_score_maps_u8(int device, const unsigned char* sal, const unsigned char*
     ScoreRequest r{"score_maps_u8", n, H, W};
     r.flags = flags; r.ties = ties; r.density = density; r.fixation = fixation; r.out = out;
     ScoreStage stage(r);
-    DevArr<unsigned char> ds(stage.bytes, sal);
-    unsigned* const counters = carve_scratch(nullptr, stage.counters(), [&](Carve& c) { stage.carve(c); });
-    stage.upload(nullptr);
-    stage.launch(nullptr, ds.p, counters);
-    stage.results(nullptr);
-    HIPCHECK(hipDeviceSynchronize());
+    stage_on_host_bytes(stage, sal);
     API_END
 }
 
@@ -1877,9 +1909,7 @@ namespace {
 // one launch description for p3d_render_u8, the render stage and p3d_debug_render_u8 ------------------------------------------------
 void render_check(const char* who, const p3d_render* cfg, int n, int H, int W, const void* out) {
     if (!cfg || !out) throw P3dError("null argument");
-    if (n < 1 || n > 65535) throw P3dError(std::string(who) + ": 1 .. 65535 maps");
-    if (H < 1 || W < 1) throw P3dError(std::string(who) + ": empty map");
-    if ((long long)H * W > P3D_RENDER_MAX_PIXELS) throw P3dError(std::string(who) + ": H * W exceeds 2^28, the bound of the int32 offsets inside a map");
+    map_shape_check(who, n, H, W, P3D_RENDER_MAX_PIXELS, "2^28, the bound of the int32 offsets inside a map");
     if (cfg->contour_level < 0 || cfg->contour_level > 255) throw P3dError(std::string(who) + ": the contour level is 0 (off) .. 255");
     if (cfg->contour_level > 0 && (cfg->contour_thickness < 1 || cfg->contour_thickness > P3D_RENDER_MAX_THICKNESS))
         throw P3dError(std::string(who) + ": the contour thickness is 1 .. 4");
@@ -1899,8 +1929,7 @@ struct RenderSizes {
 };
 
 // ---- the render stage (declared above maps_u8_chain) ------------------------------------------------------------------------------
-RenderStage::RenderStage(const RenderRequest& r_)
-    : r(r_), bytes((size_t)r_.n * (size_t)r_.H * (size_t)r_.W), a(render_args(*r_.cfg, r_.n, r_.H, r_.W)) {}
+RenderStage::RenderStage(const RenderRequest& r_) : ByteStage(r_), r(r_), a(render_args(*r_.cfg, r_.n, r_.H, r_.W)) {}
 void RenderStage::carve(Carve& c) {
     const RenderSizes z(a);
     df = r.frames ? c.take<unsigned char>(z.bgr) : nullptr;
@@ -1911,7 +1940,7 @@ void RenderStage::upload(hipStream_t s) {
     HIPCHECK(hipMemcpyAsync(dtab, r.cfg->table, 256 * sizeof(unsigned), hipMemcpyHostToDevice, s));
     if (df) HIPCHECK(hipMemcpyAsync(df, r.frames, RenderSizes(a).bgr, hipMemcpyHostToDevice, s));
 }
-void RenderStage::launch(hipStream_t s, const unsigned char* sal) {
+void RenderStage::launch(hipStream_t s, const unsigned char* sal, unsigned*) {
     a.sal = sal; a.frames = df ? df : r.frames_dev; a.out = dout; a.table = dtab;
     HIPCHECK(p3d_render_launch(a, s));
 }
@@ -1930,12 +1959,7 @@ int p3d_render_u8(int device, const unsigned char* sal, const unsigned char* fra
     RenderRequest r{"render_u8", n, H, W};
     r.cfg = cfg; r.frames = frames; r.out = out;
     RenderStage stage(r);
-    DevArr<unsigned char> ds(stage.bytes, sal);
-    carve_scratch(nullptr, 0, [&](Carve& c) { stage.carve(c); });
-    stage.upload(nullptr);
-    stage.launch(nullptr, ds.p);
-    stage.results(nullptr);
-    HIPCHECK(hipDeviceSynchronize());
+    stage_on_host_bytes(stage, sal);
     API_END
 }
 
@@ -1998,24 +2022,17 @@ int p3d_video_render(p3d_handle* h, int first, int n, float scale, int H, int W,
     if (!h) throw P3dError("null argument");
     h->video_need_open(who);
     // before the shape: a call that leaves the size to the source has none to name when there is no source
-    if (!frames && !h->vid_src) throw P3dError(std::string(who) + ": no frames are given and the video keeps no source (p3d_video_keep_source before the first p3d_video_put_frames_u8)");
+    if (!frames) need_kept_source(h, who);
     render_check(who, cfg, std::max(1, std::min(n, 65535)), H, W, out);
-    HIPCHECK(hipSetDevice(h->cfg.device));
-    const VideoSource src(h, who, first, n, true, 65535);
     RenderRequest r{who, n, H, W};
     r.cfg = cfg; r.frames = frames; r.out = out; r.timed = stage_ms != nullptr;
-    if (!frames) {
-        if (H != h->vid_H0 || W != h->vid_W0)
-            throw P3dError(std::string(who) + ": the kept source is " + std::to_string(h->vid_H0) + " x " + std::to_string(h->vid_W0) + ", the call renders " +
-                           std::to_string(H) + " x " + std::to_string(W));
-        for (int f = first; f < first + n; ++f)
-            if (!h->vid_has_src[(size_t)f]) throw P3dError(std::string(who) + ": frame " + std::to_string(f) + " has no source (it was not put with p3d_video_put_frames_u8)");
-        r.frames_dev = h->vid_src + (size_t)first * (size_t)H * (size_t)W * 3;
-    }
-    RenderStage stage(r);
-    for (int i = 0; stage_ms && i < 3; ++i) stage_ms[i] = 0.0;
-    maps_u8_chain(h, n, h->pred->H, h->pred->W, scale, H, W, maps_out, nullptr, src.extra(), src, nullptr, &stage);
-    if (stage_ms) { stage_ms[0] = frames ? stage.ms[0] : 0.0; stage_ms[1] = stage.ms[1]; stage_ms[2] = stage.ms[2]; }
+    std::unique_ptr<RenderStage> stage;
+    video_stage_run(h, who, first, n, scale, maps_out, stage_ms, 3, [&]() -> ByteStage& {
+        if (!frames) r.frames_dev = kept_source(h, who, first, n, H, W, "renders");
+        stage.reset(new RenderStage(r));
+        return *stage;
+    });
+    if (stage_ms && !frames) stage_ms[0] = 0.0;      // (nothing but the table went up)
     API_END
 }
 
@@ -2025,9 +2042,7 @@ namespace {
 // description for p3d_reframe_u8, the reframe stage and p3d_debug_reframe_u8 --------------------------------------------------------
 void reframe_check(const char* who, const p3d_reframe* cfg, int n, int H, int W, const void* track) {
     if (!cfg || !track) throw P3dError("null argument");
-    if (n < 1 || n > 65535) throw P3dError(std::string(who) + ": 1 .. 65535 maps");
-    if (H < 1 || W < 1) throw P3dError(std::string(who) + ": empty map");
-    if ((long long)H * W > P3D_REFRAME_MAX_PIXELS) throw P3dError(std::string(who) + ": H * W exceeds 2^23, the bound that keeps a mass in 32 bits");
+    map_shape_check(who, n, H, W, P3D_REFRAME_MAX_PIXELS, "2^23, the bound that keeps a mass in 32 bits");
     if (cfg->crop_h < 1 || cfg->crop_h > H || cfg->crop_w < 1 || cfg->crop_w > W)
         throw P3dError(std::string(who) + ": the window is " + std::to_string(cfg->crop_h) + " x " + std::to_string(cfg->crop_w) + ", the map " +
                        std::to_string(H) + " x " + std::to_string(W) + "; 1 <= crop_h <= H and 1 <= crop_w <= W");
@@ -2053,8 +2068,7 @@ struct ReframeSizes {
 };
 
 // ---- the reframe stage (declared above maps_u8_chain) -----------------------------------------------------------------------------
-ReframeStage::ReframeStage(const ReframeRequest& r_)
-    : r(r_), bytes((size_t)r_.n * (size_t)r_.H * (size_t)r_.W), a(reframe_args(*r_.cfg, r_.n, r_.H, r_.W)) {}
+ReframeStage::ReframeStage(const ReframeRequest& r_) : ByteStage(r_), r(r_), a(reframe_args(*r_.cfg, r_.n, r_.H, r_.W)) {}
 void ReframeStage::carve(Carve& c) {
     const ReframeSizes z(a);
     df = crops() && r.frames ? c.take<unsigned char>(z.bgr) : nullptr;
@@ -2069,7 +2083,7 @@ void ReframeStage::carve(Carve& c) {
 void ReframeStage::upload(hipStream_t s) {
     if (df) HIPCHECK(hipMemcpyAsync(df, r.frames, ReframeSizes(a).bgr, hipMemcpyHostToDevice, s));
 }
-void ReframeStage::launch(hipStream_t s, const unsigned char* sal) {
+void ReframeStage::launch(hipStream_t s, const unsigned char* sal, unsigned*) {
     a.sal = sal; a.frames = !crops() ? nullptr : df ? df : r.frames_dev;
     HIPCHECK(p3d_reframe_launch(a, s));
 }
@@ -2094,12 +2108,7 @@ int p3d_reframe_u8(int device, const unsigned char* sal, const unsigned char* fr
     ReframeRequest r{who, n, H, W};
     r.cfg = cfg; r.frames = frames; r.track = track; r.raw = raw; r.mass = mass; r.out = out;
     ReframeStage stage(r);
-    DevArr<unsigned char> ds(stage.bytes, sal);
-    carve_scratch(nullptr, 0, [&](Carve& c) { stage.carve(c); });
-    stage.upload(nullptr);
-    stage.launch(nullptr, ds.p);
-    stage.results(nullptr);
-    HIPCHECK(hipDeviceSynchronize());
+    stage_on_host_bytes(stage, sal);
     API_END
 }
 
@@ -2149,24 +2158,17 @@ int p3d_video_reframe(p3d_handle* h, int first, int n, float scale, int H, int W
     h->video_need_open(who);
     if (frames && !out) throw P3dError(std::string(who) + ": frames are given but no out to receive the windows");
     // before the shape: a call that leaves the size to the source has none to name when there is no source
-    if (out && !frames && !h->vid_src) throw P3dError(std::string(who) + ": no frames are given and the video keeps no source (p3d_video_keep_source before the first p3d_video_put_frames_u8)");
+    if (out && !frames) need_kept_source(h, who);
     reframe_check(who, cfg, std::max(1, std::min(n, 65535)), H, W, track);
-    HIPCHECK(hipSetDevice(h->cfg.device));
-    const VideoSource src(h, who, first, n, true, 65535);
     ReframeRequest r{who, n, H, W};
     r.cfg = cfg; r.frames = frames; r.track = track; r.raw = raw; r.mass = mass; r.out = out; r.timed = stage_ms != nullptr;
-    if (out && !frames) {
-        if (H != h->vid_H0 || W != h->vid_W0)
-            throw P3dError(std::string(who) + ": the kept source is " + std::to_string(h->vid_H0) + " x " + std::to_string(h->vid_W0) + ", the call reframes " +
-                           std::to_string(H) + " x " + std::to_string(W));
-        for (int f = first; f < first + n; ++f)
-            if (!h->vid_has_src[(size_t)f]) throw P3dError(std::string(who) + ": frame " + std::to_string(f) + " has no source (it was not put with p3d_video_put_frames_u8)");
-        r.frames_dev = h->vid_src + (size_t)first * (size_t)H * (size_t)W * 3;
-    }
-    ReframeStage stage(r);
-    for (int i = 0; stage_ms && i < 3; ++i) stage_ms[i] = 0.0;
-    maps_u8_chain(h, n, h->pred->H, h->pred->W, scale, H, W, maps_out, nullptr, src.extra(), src, nullptr, nullptr, &stage);
-    if (stage_ms) { stage_ms[0] = frames ? stage.ms[0] : 0.0; stage_ms[1] = stage.ms[1]; stage_ms[2] = stage.ms[2]; }
+    std::unique_ptr<ReframeStage> stage;
+    video_stage_run(h, who, first, n, scale, maps_out, stage_ms, 3, [&]() -> ByteStage& {
+        if (out && !frames) r.frames_dev = kept_source(h, who, first, n, H, W, "reframes");
+        stage.reset(new ReframeStage(r));
+        return *stage;
+    });
+    if (stage_ms && !frames) stage_ms[0] = 0.0;      // (nothing went up)
     API_END
 }
 
@@ -2214,9 +2216,7 @@ std::vector<int> host_n_fix(const unsigned char* fixation, int n, long long n_pi
 // the op-level sweep's checks of its arguments and shapes
 void sweep_op_shape(const char* who, const void* sal, const void* fixation, int n, int H, int W, const int* n_rows, const void* per_rep) {
     if (!sal || !fixation || !n_rows || !per_rep) throw P3dError("null argument");
-    if (n < 1 || n > 65535) throw P3dError(std::string(who) + ": 1 .. 65535 maps");
-    if (H < 1 || W < 1) throw P3dError(std::string(who) + ": empty map");
-    if ((long long)H * W > P3D_SCORE_MAX_PIXELS) throw P3dError(std::string(who) + ": H * W exceeds 2^23");
+    map_shape_check(who, n, H, W, P3D_SCORE_MAX_PIXELS, "2^23");
 }
 // the device's counts (info[b][0] = nf) against the rows: n_rows[b] <= nf[b]
 void sweep_check_rows(const char* who, const std::vector<int>& info, const int* n_rows, int n) {
@@ -2228,7 +2228,7 @@ void sweep_check_rows(const char* who, const std::vector<int>& info, const int* 
 
 // ---- the score stage (declared above maps_u8_chain) -------------------------------------------------------------------------------
 ScoreStage::ScoreStage(const ScoreRequest& r_)
-    : r(r_), bytes((size_t)r_.n * (size_t)r_.H * (size_t)r_.W),
+    : ByteStage(r_), r(r_),
       a(score_args(r_.n, (long long)r_.H * r_.W, r_.flags, r_.flags ? r_.ties : P3D_SCORE_TIES_REFERENCE)), sweeps(r_.timed && (r_.borji || r_.shuffled), 2) {
     if (!sweep()) return;
     const long long N = (long long)r.H * r.W;
@@ -2330,21 +2330,18 @@ void ScoreStage::check_counts() const {
             throw P3dError(std::string(r.who) + ": frame " + std::to_string(b) + ": the device counted " + std::to_string(info[b * 4]) + " fixated pixels, the host " +
                            std::to_string(nf[b]));
 }
-// p3d_video_score and p3d_video_score_auc behind the checks of their arguments: the video's frames through the maps' chain, the
-// stage behind its bytes.  stage_ms (null, or n_ms = 3 or 4 values): uploads, the chain, the launches less the sweeps, the sweeps.
+// p3d_video_score and p3d_video_score_auc behind the checks of their arguments.  stage_ms (null, or n_ms = 3 or 4 values): uploads,
+// the chain, the launches less the sweeps, the sweeps.
 void video_score_run(p3d_handle* h, int first, float scale, ScoreRequest r, unsigned char* maps_out, double* stage_ms, int n_ms) {
-    HIPCHECK(hipSetDevice(h->cfg.device));
-    const VideoSource src(h, r.who, first, r.n, true, 65535);
     r.timed = stage_ms != nullptr;
-    ScoreStage stage(r);
-    for (int i = 0; stage_ms && i < n_ms; ++i) stage_ms[i] = 0.0;
-    maps_u8_chain(h, r.n, h->pred->H, h->pred->W, scale, r.H, r.W, maps_out, nullptr, src.extra(), src, &stage);
+    std::unique_ptr<ScoreStage> stage;
+    video_stage_run(h, r.who, first, r.n, scale, maps_out, stage_ms, n_ms, [&]() -> ByteStage& { stage.reset(new ScoreStage(r)); return *stage; });
     if (stage_ms) {
-        const double sw = stage.sweep_ms();
-        stage_ms[0] = stage.ms[0]; stage_ms[1] = stage.ms[1]; stage_ms[2] = std::max(0.0, stage.ms[2] - sw);
+        const double sw = stage->sweep_ms();
+        stage_ms[2] = std::max(0.0, stage_ms[2] - sw);
         if (n_ms > 3) stage_ms[3] = sw;
     }
-    stage.check_counts();
+    stage->check_counts();
 }
 }  // namespace
 extern "C" {
@@ -2451,8 +2448,7 @@ int p3d_video_score_auc(p3d_handle* h, int first, int n, float scale, int H, int
     if (flags != 0) score_check(who, density, fixation, nc, H, W, flags, ties, out);
     else if (out) throw P3dError(std::string(who) + ": flags = 0 selects no column, so out must be NULL");
     if (flags == 0 && !borji && !shuf) throw P3dError(std::string(who) + ": nothing is asked for");
-    if (H < 1 || W < 1) throw P3dError(std::string(who) + ": empty map");
-    if ((long long)H * W > P3D_SCORE_MAX_PIXELS) throw P3dError(std::string(who) + ": H * W exceeds 2^23");
+    map_shape_check(who, nc, H, W, P3D_SCORE_MAX_PIXELS, "2^23");
     if ((borji || shuf) && !fixation) throw P3dError(std::string(who) + ": AUC-Borji and shuffled AUC need the fixation maps");
     if ((borji && !borji_per_rep) || (shuf && (!n_rows || !shuffled_per_rep))) throw P3dError("null argument");
     ScoreRequest r{who, n, H, W};

@@ -69,6 +69,27 @@ def _score_inputs(n, size, *maps):
     return n, int(H), int(W), valid, maps
 
 
+def _frame_inputs(sess, n, size, frames, max_pixels, with_maps, window=None, with_out=True):
+    """What video_render and video_reframe settle before the library sees the call: size (a scalar, a pair, or None for the kept
+    source's or the frames' own) and frames, None or uint8 [n, H, W, 3]; then the arrays the call fills, empty at a size the
+    library refuses -> n, H, W, the frames contiguous, out uint8 [n, H, W, 3] ([n] + window + [3] for a window) or None, maps
+    uint8 [n, H, W] or None."""
+    if size is None:
+        size = sess.video_source_info()["size"] if frames is None else np.shape(frames)[1:3]
+    H, W = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
+    n = max(int(n), 0)
+    f = None
+    if frames is not None:
+        f = np.ascontiguousarray(frames)
+        if f.dtype != np.uint8 or f.shape != (n, H, W, 3):
+            raise ValueError("frames are %s %s, expected uint8 %s" % (f.dtype, f.shape, (n, H, W, 3)))
+    hc, wc = (H, W) if window is None else window
+    valid = H >= 1 and W >= 1 and H * W <= max_pixels and 1 <= hc <= H and 1 <= wc <= W      # (the library refuses the rest)
+    out = np.empty((n, hc, wc, 3) if valid else (0,), np.uint8) if with_out else None
+    maps = np.empty((n, H, W) if valid else (0,), np.uint8) if with_maps else None
+    return n, H, W, f, out, maps
+
+
 class P3DSession:
     """sess = P3DSession(batch=2)  ~  building the graph + tf.Session() in train.py:143-201."""
 
@@ -958,20 +979,9 @@ class P3DSession:
         timed: HIP-event times are left in `last_render_ms` (upload, device = the maps' chain, render).  include/p3d_hip.h holds
         the exact rules."""
         from . import dataflow
-        if size is None:
-            size = self.video_source_info()["size"] if frames is None else np.shape(frames)[1:3]
-        H, W = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
-        n = max(int(n), 0)
-        f = None
-        if frames is not None:
-            f = np.ascontiguousarray(frames)
-            if f.dtype != np.uint8 or f.shape != (n, H, W, 3):
-                raise ValueError("frames are %s %s, expected uint8 %s" % (f.dtype, f.shape, (n, H, W, 3)))
+        n, H, W, f, out, maps = _frame_inputs(self, n, size, frames, 2 ** 28, with_maps)
         cfg = dataflow.render_cfg(dataflow.render_table(colormap, alpha, opacity, gate) if table is None else table, contour, thickness,
                                   contour_color)
-        valid = H >= 1 and W >= 1 and H * W <= 2 ** 28
-        out = np.empty((n, H, W, 3) if valid else (0,), np.uint8)     # (the library refuses the rest)
-        maps = np.empty((n, H, W) if valid else (0,), np.uint8) if with_maps else None
         ms = (C.c_double * 3)()
         check(lib().p3d_video_render(self._h, int(first), n, float(scale), H, W, _ptr(f, _lib._u8p), C.byref(cfg), _ptr(out, _lib._u8p),
                                      _ptr(maps, _lib._u8p), ms if timed else None))
@@ -990,25 +1000,14 @@ class P3DSession:
         [n, 2], mass uint32 [n, 3] (best, smoothed, total) and maps uint8 [n, H, W].  timed: HIP-event times are left in
         `last_reframe_ms` (upload, device = the maps' chain, reframe).  include/p3d_hip.h holds the exact rules."""
         tracks_only = frames is False
-        if size is None:
-            if tracks_only:
-                raise ValueError("tracks alone (frames=False) need a size")
-            size = self.video_source_info()["size"] if frames is None else np.shape(frames)[1:3]
-        H, W = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
+        if tracks_only and size is None:
+            raise ValueError("tracks alone (frames=False) need a size")
         hc, wc = (int(crop), int(crop)) if np.isscalar(crop) else (int(crop[0]), int(crop[1]))
-        n = max(int(n), 0)
-        f = None
-        if frames is not None and not tracks_only:
-            f = np.ascontiguousarray(frames)
-            if f.dtype != np.uint8 or f.shape != (n, H, W, 3):
-                raise ValueError("frames are %s %s, expected uint8 %s" % (f.dtype, f.shape, (n, H, W, 3)))
+        n, H, W, f, out, maps = _frame_inputs(self, n, size, None if tracks_only else frames, 2 ** 23, with_maps, (hc, wc), not tracks_only)
         cfg = _lib.P3dReframe(hc, wc, int(gate), int(smooth))
-        valid = H >= 1 and W >= 1 and H * W <= 2 ** 23 and 1 <= hc <= H and 1 <= wc <= W      # (the library refuses the rest)
         track = np.empty((n, 2), np.int32)
         raw = np.empty((n, 2), np.int32) if with_raw else None
         mass = np.empty((n, 3), np.uint32) if with_mass else None
-        out = None if tracks_only else np.empty((n, hc, wc, 3) if valid else (0,), np.uint8)
-        maps = np.empty((n, H, W) if valid else (0,), np.uint8) if with_maps else None
         ms = (C.c_double * 3)()
         check(lib().p3d_video_reframe(self._h, int(first), n, float(scale), H, W, _ptr(f, _lib._u8p), C.byref(cfg), _ptr(track, _lib._i32p),
                                       _ptr(raw, _lib._i32p), _ptr(mass, _lib._u32p), _ptr(out, _lib._u8p), _ptr(maps, _lib._u8p),
