@@ -11,6 +11,19 @@
  * owned by the caller and copied by value (like feed_dict / fetched numpy arrays); device
  * memory, streams and RCCL state are owned by the opaque handle; one caller thread per handle
  * (like the single thread calling sess.run).  All tensors are float32 NDHWC.
+ *
+ * The Python binding is READ FROM THIS FILE (sap3d_tensorflow_amd/_header.py, at import): a declaration here is bound, and
+ * nothing is written a second time.  The reader accepts this grammar and stops at anything else, naming it:
+ *   block comments; #include, the include guard and the __cplusplus brackets; #define P3D_NAME <integer literal> (a #define
+ *   with any other body is not a constant for Python); enum { A = n, ... }; with an explicit integer for every enumerator;
+ *   typedef struct [tag] { ... } name; with several declarators per declaration (int ld, off; -- not after a pointer), fixed
+ *   arrays, pointer members and earlier structs by value or in arrays; the opaque handle's typedef; function declarations with
+ *   named parameters.
+ * Types: int, float, double, char, unsigned char, size_t, void, [u]int32_t, [u]int64_t, p3d_handle and the structs defined
+ * above their use, with const, up to two levels of pointer, and parameters name[N].  Scalars bind to their ctypes twins, a
+ * void return to None, p3d_handle* and void* to c_void_p, [const] char* to c_char_p, any other T* to POINTER(T), a second
+ * level (T**, T* const*, const char**, p3d_handle**) to POINTER of the first, a parameter T name[N] to POINTER(T), and
+ * struct p3d_some_name to the ctypes.Structure P3dSomeName.
  */
 #ifndef P3D_HIP_H
 #define P3D_HIP_H

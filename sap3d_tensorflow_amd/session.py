@@ -8,11 +8,12 @@ from . import _lib
 from ._lib import P3dConfig, P3dError, P3dOpTime, check, fptr, lib
 from .metrics import eval_draws
 
-STRUCTURES = {"unet": 0, "concat": 1, "gn_p3d": 2,     # train.py:149-154 --structure
-              "unet++nonsa": 3,                          # p3d.py:401 p3d_unetplusplus_nonsa
-              "gn_p3d_decoder": 4,                       # gn/p3d_gn.py:489 inference_p3d_decoder_block (net='P3D_DECODER')
-              "gn_p3d_concat": 5,                        # gn/p3d_gn.py:279 inference_p3d_concat (net='P3D_CONCAT')
-              "unet++ds": 6}                             # p3d.py:340 p3d_unetplusplus_ds (unet++ with self attention)
+STRUCTURES = dict((name, _lib.K["P3D_STRUCTURE_" + h]) for name, h in (
+    ("unet", "UNET"), ("concat", "CONCAT"), ("gn_p3d", "GN_P3D"),     # train.py:149-154 --structure
+    ("unet++nonsa", "UNETPP_NONSA"),                    # p3d.py:401 p3d_unetplusplus_nonsa
+    ("gn_p3d_decoder", "GN_P3D_DECODER"),               # gn/p3d_gn.py:489 inference_p3d_decoder_block (net='P3D_DECODER')
+    ("gn_p3d_concat", "GN_P3D_CONCAT"),                 # gn/p3d_gn.py:279 inference_p3d_concat (net='P3D_CONCAT')
+    ("unet++ds", "UNETPP_DS")))                         # p3d.py:340 p3d_unetplusplus_ds (unet++ with self attention)
 
 
 def slot_names(variables, optimizer):
