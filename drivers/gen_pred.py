@@ -29,7 +29,11 @@ mean of every window that predicted it.  A stride other than 1 and `--overlap me
 with reflected ends, or the causal moving average m_f = A m_{f-1} + (1 - A) v_f of `--temporal-alpha`; npy files then hold the
 filtered maps, png / jpg the images of the filtered maps.  `--render DIR` (an addition, needs `--resident`) also keeps the
 decoded frames on the device and writes DIR/<video>/frame_<k>.png: every frame at its own size with its 8-bit map laid over it
-on the device (P3DSession.video_render), whatever `--write` and `--truth` do beside it.  `--reframe DIR` (an addition, needs
+on the device (P3DSession.video_render), whatever `--write` and `--truth` do beside it.  `--shots detect|FILE.npy` (an addition, needs `--resident`) installs a
+shot table on every video before its maps are read -- the hard cuts found on the device in the decoded frames
+(P3DSession.video_detect_shots, shaped by `--shots-grid`, `-threshold`, `-window`, `-ratio`, `-min-length`), or the starts in FILE.npy
+-- so that `--temporal` filters inside the shots and `--reframe` smooths its track inside them; it writes `<out>/<video>_shots.npy`
+and, under detect, `<out>/<video>_cutsignal.npy`.  `--reframe DIR` (an addition, needs
 `--resident`, may stand beside `--render`) writes DIR/<video>/frame_<k>.png, every frame cut -- not resized -- to the window of
 `--reframe-size HC WC` or `--reframe-aspect A:B` (width : height; default 9:16) that holds the most saliency at or above
 `--reframe-gate`, on a track averaged over `--reframe-smooth` frames to either side (P3DSession.video_reframe, one call per
@@ -474,6 +478,18 @@ def parse_args(argv=None):
     p.add_argument("--reframe-gate", type=int, default=0, metavar="LEVEL", help="[addition] --reframe: map levels below it weigh nothing, 0 .. 255")
     p.add_argument("--reframe-smooth", type=int, default=0, metavar="R", help="[addition] --reframe: the track is averaged over R frames to "
                    "either side, 0 .. 255 (0: the raw track)")
+    p.add_argument("--shots", type=str, default="", metavar="detect|FILE.npy", help="[addition] needs --resident: a shot table for every video, "
+                   "installed before its maps are read (P3DSession.video_set_shots) -- --temporal then filters inside the shots and --reframe "
+                   "smooths its track inside them.  detect: the hard cuts found on the device in the decoded frames "
+                   "(P3DSession.video_detect_shots; the frames are kept on the device); FILE.npy: the shot starts, ascending from 0.  "
+                   "Writes <out>/<video>_shots.npy and, under detect, <out>/<video>_cutsignal.npy")
+    p.add_argument("--shots-grid", type=int, nargs=2, default=None, metavar=("GY", "GX"), help="[addition] --shots detect: cells of histograms a frame, 1 .. 4 each (2 2)")
+    p.add_argument("--shots-threshold", type=int, default=None, metavar="PERMILLE", help="[addition] --shots detect: a cut's distance is at least "
+                   "this many permille of the largest possible, 1 .. 1000 (250)")
+    p.add_argument("--shots-window", type=int, default=None, metavar="FRAMES", help="[addition] --shots detect: the peak rule looks this far to either side, 0 .. 32 (2)")
+    p.add_argument("--shots-ratio", type=int, default=None, metavar="Q8", help="[addition] --shots detect: a cut's distance is at least Q8 / 256 times "
+                   "every other within the window, 256 .. 65535 (512)")
+    p.add_argument("--shots-min-length", type=int, default=None, metavar="FRAMES", help="[addition] --shots detect: the shortest shot, at least 1 (3)")
     p.add_argument("--base", type=int, default=64, help=argparse.SUPPRESS)
     p.add_argument("--blocks", type=str, default="3,8,36", help=argparse.SUPPRESS)
     p.add_argument("--time", action="store_true", help="print per-video wall times (png / jpg: also the device stage and the host encode)")
@@ -512,7 +528,65 @@ def parse_args(argv=None):
         p.error("--match-bins must be in 2..1024")
     render_args(args, p.error)
     reframe_args(args, p.error)
+    shots_args(args, p.error)
     return args
+
+
+SHOTS_DEFAULTS = dict(grid=(2, 2), threshold=250, window=2, ratio=512, min_length=3)
+
+
+def shots_args(args, error):
+    """Checks --shots and its values as P3DSession.video_detect_shots would refuse them, before anything runs; error(message) does not
+    return.  Leaves dict(detect=dict(grid, threshold, window, ratio, min_length) or None, starts=array or None) in args.shots_kw (None
+    without --shots)."""
+    args.shots_kw = None
+    given = dict(grid=args.shots_grid, threshold=args.shots_threshold, window=args.shots_window, ratio=args.shots_ratio, min_length=args.shots_min_length)
+    shaped = any(v is not None for v in given.values())
+    if not args.shots:
+        if shaped:
+            error("--shots-grid / -threshold / -window / -ratio / -min-length need --shots detect")
+        return
+    if not args.resident:
+        error("--shots needs --resident: the table belongs to a video on the device")
+    if args.shots != "detect":
+        if shaped:
+            error("--shots-grid / -threshold / -window / -ratio / -min-length belong to --shots detect")
+        try:
+            starts = np.load(args.shots)
+        except Exception as e:
+            error("--shots %s: %s" % (args.shots, e))
+        if starts.ndim != 1 or starts.size < 1 or starts.dtype.kind not in "iu" or starts[0] != 0 or (np.diff(starts.astype(np.int64)) <= 0).any():
+            error("--shots %s: the shot starts are integers ascending strictly from 0" % args.shots)
+        args.shots_kw = dict(detect=None, starts=starts.astype(np.int32))
+        return
+    kw = dict((k, SHOTS_DEFAULTS[k] if v is None else v) for k, v in given.items())
+    kw["grid"] = tuple(kw["grid"])
+    if not all(1 <= g <= 4 for g in kw["grid"]):
+        error("--shots-grid is GY GX, 1 .. 4 each")
+    if not 1 <= kw["threshold"] <= 1000:
+        error("--shots-threshold is 1 .. 1000 permille")
+    if not 0 <= kw["window"] <= 32:
+        error("--shots-window is 0 .. 32 frames")
+    if not 256 <= kw["ratio"] <= 65535:
+        error("--shots-ratio is 256 .. 65535 (256: equal neighbours pass)")
+    if kw["min_length"] < 1:
+        error("--shots-min-length is at least 1 frame")
+    args.shots_kw = dict(detect=kw, starts=None)
+
+
+def shots_video_resident(sess, F, out_dir, name, shots):
+    """--shots: installs the open video's shot table before any map is read and writes <out>/<name>_shots.npy (and _cutsignal.npy
+    under detect).  -> the starts."""
+    if shots["detect"] is not None:
+        starts, D = sess.video_detect_shots(install=True, with_signal=True, **shots["detect"])
+        np.save(os.path.join(out_dir, name + "_cutsignal.npy"), D)
+    else:
+        starts = shots["starts"]
+        if starts[-1] >= F:
+            raise ValueError("--shots: a shot starts at frame %d, the video has %d frames" % (starts[-1], F))
+        sess.video_set_shots(starts)
+    np.save(os.path.join(out_dir, name + "_shots.npy"), np.asarray(starts, np.int32))
+    return starts
 
 
 def reframe_args(args, error):
@@ -695,7 +769,11 @@ def run_resident(sess, args, path):
     reframe_dir = os.path.join(args.reframe, name) if args.reframe else None
     if reframe_dir:
         os.makedirs(reframe_dir, exist_ok=True)
-    F = predict_video_resident(sess, np.load(path), args.batch, args.stride, args.overlap, times, keep_source=bool(render_dir or reframe_dir))
+    detect = bool(args.shots_kw and args.shots_kw["detect"])
+    F = predict_video_resident(sess, np.load(path), args.batch, args.stride, args.overlap, times, keep_source=bool(render_dir or reframe_dir or detect))
+    if args.shots_kw:
+        starts = shots_video_resident(sess, F, args.out, name, args.shots_kw)
+        print(name, "%d shots, starting at frames %s%s" % (len(starts), " ".join(str(int(v)) for v in starts[:12]), " ..." if len(starts) > 12 else ""))
     t1 = time.perf_counter()
     means = ts = None
     if args.truth:

@@ -1646,6 +1646,85 @@ int p3d_debug_reframe_u8(int device, const unsigned char* sal, const unsigned ch
 int p3d_debug_reframe_plan(int H, int W, int crop_h, int crop_w, int n, int* positions_per_block, int* search_blocks, int* maps_per_chunk,
                            int64_t* scratch_bytes);
 
+/* ---- Shot boundaries of 8-bit frames (an ADDITION: the videos people reframe are edited, and a filter along the frame axis that
+ * runs across a hard cut blends two unrelated scenes; automatic reframing tools find the cuts first).  OFF until called: every other
+ * entry point issues what it issued before and returns the same bits.  PARITY UNPINNED: the reference's clips are single takes and
+ * it has nothing of the kind; this text is the contract and tests/shots_ref.py replays it in numpy.  SIGNAL and DECISION are integer
+ * arithmetic, no floating point anywhere: no order can show, and every test holds to 0.  Hard cuts only: a dissolve or a fade
+ * spreads its change over many frames, none of which is a peak, and is NOT detected.
+ * Per frame: bytes [H][W][3] (B, G, R); a grid of gy x gx cells, 1 <= gy <= min(P3D_SHOTS_MAX_GRID, H), 1 <= gx <= min(.., W).
+ *   LIMITS   1 <= n <= 65535 frames a call; P = H * W <= 2^28, so that 6 P fits 32 bits.
+ *   CELL     pixel (y, x) lies in cell (y * gy / H, x * gx / W), integer division.
+ *   HIST     per cell and channel 64 bins, bin = byte >> 2; counts are unsigned 32-bit.
+ *   DIST     D_0 = 0; for f >= 1, D_f = the sum over cells, channels and bins of |h_f - h_{f-1}|.  0 <= D_f <= 6 P.
+ *   CONFIG   six ints in the order of the P3D_SHOTS_* indices below (an array: `const int cfg[6]`): grid_y, grid_x; threshold_permille
+ *            in 1 .. 1000; window in 0 .. 32; ratio_q8 in 256 .. 65535; min_length >= 1.
+ *   CAND(f)  for 1 <= f <= F - 1, in 64-bit integers: D_f * 1000 >= threshold_permille * 6 * P, and D_f * 256 >= ratio_q8 * N_f,
+ *            where N_f is the largest D_g over g != f, 1 <= g <= F - 1, |g - f| <= window (0 where there is no such g, so also for
+ *            window = 0).  The second test is the peak rule: a flash -- one bright frame, two large distances side by side -- fails
+ *            it at any ratio above 256 times the smaller over the larger.
+ *   ACCEPT   f ascending, last = 0: f starts a shot exactly when CAND(f), f - last >= min_length and F - f >= min_length; then
+ *            last = f.
+ *   RESULT   starts [n_shots], strictly ascending, starts[0] = 0: shot k is frames starts[k] .. starts[k + 1] - 1, the last to F - 1.
+ * p3d_shot_distances_u8  op level, host frames [n][H][W][3] -> D [n].
+ * p3d_shot_cuts          op level, host D [F] and P = H * W of its frames -> the first min(cap, n_shots) starts and n_shots (cap >= 1).
+ *                        The decision runs on the device, one block behind the signal's launches; grid_y and grid_x are not read.
+ * Refused (-1, p3d_last_error set, nothing launched): a null pointer, LIMITS, a grid or a CONFIG value outside its range.
+ * TEST HOOKS (tests/test_gpu_shots.py):
+ * p3d_debug_shot_distances_u8  the same launch description with every device buffer, the scratch included, between guards; the frames
+ *                        start `offset` bytes (0 .. 15) past a 16-byte boundary; ballot 1 counts a wave's equal bins with one add
+ *                        (score_u8.hip's way), 0 adds every byte on its own: the same D.  -1 if a guard or the frames changed.
+ * p3d_debug_shots_plan   host only, no HIP call: the rows a block of the count takes, its blocks a frame, the frames whose tables are
+ *                        held at a time (a call of more frames runs in chunks of that many, each seeded with the last table of the
+ *                        one before) and the bytes of scratch the tables take.
+ * p3d_debug_shots_time   HIP-event milliseconds of `reps` rounds of: the signal's launches without and with ballot, and a
+ *                        device-to-device copy of the same n * H * W * 3 bytes (the roof of a kernel that reads every byte once), in
+ *                        turn, after one untimed round.
+ * THE OPEN VIDEO'S SHOT TABLE.  p3d_video_open starts without one and nothing reads one until it is installed; a refusal changes
+ * nothing and launches nothing.
+ * p3d_video_set_shots     installs starts [n_shots]: starts[0] == 0, strictly ascending, every start < F; NULL removes the table.
+ * p3d_video_get_shots     the first min(cap, n_shots) starts (starts may be NULL) and n_shots, 0 without a table.
+ * p3d_video_detect_shots  SIGNAL and DECISION on the source kept by p3d_video_keep_source, F <= 65535 frames at H0 x W0: refused
+ *                         unless every frame has a source (the error names the first without one).  D_out [F] and starts_out [cap]
+ *                         may be NULL; n_shots receives the number of shots; install != 0 installs the table.
+ * p3d_video_shots_last_ms HIP-event ms [2] of the last detection: the signal's launches, the decision.
+ * While a table is installed, frame f lying in shot [lo, hi], L = hi - lo + 1:
+ *   TEMPORAL  (the stage of p3d_set_video_temporal, while on; float32, each operation rounding on its own: bit for bit)
+ *     GAUSS   the PASS of that section with rho replaced by rho_s(i) = lo + refl(i - lo, L); refl(j, 1) = 0, otherwise with
+ *             m = j mod (2 L - 2), non-negative, refl = m where m < L, else 2 L - 2 - m: periodic reflect-101, so a shot of any
+ *             length is legal and the read-out refusal r > F - 1 does not apply.  A read needs, of every shot it touches in frames
+ *             a .. b, frames max(lo, a - r) .. min(hi, b + r).  One shot and r <= F - 1: the bits without a table.
+ *     EMA     m_lo = v_lo, a copy of the bits: the recurrence restarts at every shot.  A read needs frames lo(first) .. first + n - 1,
+ *             and the bits of a partial read are the slice of a full read.
+ *   REFRAME   p3d_video_reframe's SMOOTHED TRACK takes c(i) = min(max(i, a), b), [a, b] the frame's shot intersected with the frames
+ *             of the call: the ends of a shot repeat and the window may jump at a cut.  BEST WINDOW, MASSES and CROP are unchanged.
+ *   p3d_video_predict's windows still straddle cuts, and p3d_video_score and p3d_video_render do not read the table.
+ * p3d_temporal_filter_shots  the temporal stage alone under a table, on a host store [F][hw] and counts [F] (NULL: every count 1)
+ *                         under `mode`, frames first .. first + n - 1 -> out [n][hw]; every device buffer, the run table included,
+ *                         sits between guards, the floats `offset` (0 .. 3) elements past a 16-byte boundary.
+ * p3d_reframe_shots_u8    p3d_reframe_u8 under a table starts [n_shots] over the n frames of the call; offset -1: the stage on the
+ *                         stream's scratch, as p3d_reframe_u8; 0 .. 15: between guards and shifted, as p3d_debug_reframe_u8. */
+#define P3D_SHOTS_MAX_GRID 4
+enum { P3D_SHOTS_GRID_Y = 0, P3D_SHOTS_GRID_X = 1, P3D_SHOTS_THRESHOLD = 2, P3D_SHOTS_WINDOW = 3, P3D_SHOTS_RATIO = 4, P3D_SHOTS_MIN_LENGTH = 5 };
+int p3d_shot_distances_u8(int device, const unsigned char* frames, int n, int H, int W, int grid_y, int grid_x, uint32_t* D /* [n] */);
+int p3d_shot_cuts(int device, const uint32_t* D, int F, int64_t P, const int cfg[6], int32_t* starts /* [cap] */, int cap, int* n_shots);
+int p3d_debug_shot_distances_u8(int device, const unsigned char* frames, int n, int H, int W, int grid_y, int grid_x, int offset, int ballot,
+                                uint32_t* D);
+int p3d_debug_shots_plan(int H, int W, int grid_y, int grid_x, int n, int* rows_per_block, int* blocks_per_frame, int* frames_per_chunk,
+                         int64_t* scratch_bytes);
+int p3d_debug_shots_time(int device, const unsigned char* frames, int n, int H, int W, int grid_y, int grid_x, int reps,
+                         double* signal_ms /* [reps] */, double* ballot_ms /* [reps] */, double* copy_ms /* [reps] */);
+int p3d_video_set_shots(p3d_handle* h, const int32_t* starts /* NULL: remove */, int n_shots);
+int p3d_video_get_shots(p3d_handle* h, int32_t* starts /* [cap], may be NULL */, int cap, int* n_shots);
+int p3d_video_detect_shots(p3d_handle* h, const int cfg[6], uint32_t* D_out /* [F], may be NULL */, int32_t* starts_out /* [cap], may be NULL */,
+                           int cap, int* n_shots, int install);
+int p3d_video_shots_last_ms(p3d_handle* h, double* ms /* [2] */);
+int p3d_temporal_filter_shots(int device, int mode, const p3d_video_temporal* cfg, const float* store, const int32_t* count /* may be NULL */,
+                              int F, int64_t hw, const int32_t* starts, int n_shots, int first, int n, int offset, float* out);
+int p3d_reframe_shots_u8(int device, const unsigned char* sal, const unsigned char* frames /* may be NULL */, int n, int H, int W,
+                         const p3d_reframe* cfg, const int32_t* starts, int n_shots, int offset /* -1, or 0 .. 15 */, int32_t* track,
+                         int32_t* raw /* may be NULL */, uint32_t* mass /* may be NULL */, unsigned char* out /* NULL exactly when frames is */);
+
 /* CRC-32C of a host buffer (host-side helper of the TensorFlow checkpoint reader / writer, sap3d_tensorflow_amd/tf_checkpoint.py:
  * the bundle format of train.py:180-185,266-267 checksums every tensor); crc = running value, 0 to start. */
 uint32_t p3d_crc32c(const void* data, size_t n, uint32_t crc);

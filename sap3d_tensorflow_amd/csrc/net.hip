@@ -1572,3 +1572,4 @@ struct p3d_handle {
 
 #include "net_abi.inc"
 #include "net_readout.inc"
+#include "net_shots.inc"

@@ -791,6 +791,7 @@ struct ReframeRequest {
     const unsigned char* frames = nullptr; const unsigned char* frames_dev = nullptr;
     int32_t* track = nullptr; int32_t* raw = nullptr; uint32_t* mass = nullptr; unsigned char* out = nullptr;
     bool timed = false;
+    const int32_t* starts = nullptr; int n_shots = 0;      // host: a shot table in frames of the call (shots_table_check has passed it), or none
 };
 // The launches of reframe.hip behind some device bytes, with no arrival counters: they hand results to one another from launch to
 // launch.  reframe_check has passed cfg and the shape before one is built.
@@ -798,6 +799,7 @@ struct ReframeStage : ByteStage {
     const ReframeRequest r;
     ReframeArgs a;
     unsigned char* df = nullptr;
+    int32_t* dstarts = nullptr;
     explicit ReframeStage(const ReframeRequest& r);
     bool crops() const { return r.out != nullptr; }
     void carve(Carve& c) override;
@@ -1736,7 +1738,9 @@ struct VideoSource {
         if (predicted) h->video_need_predicted(who, first, n);
     }
     // floats of scratch the maps need: the filtered maps under either mode, the divided sums under MEAN
-    size_t extra() const { return temporal || h->vid_mode == VIDEO_MEAN ? (size_t)n * (size_t)h->vid_hw() : 0; }
+    size_t extra() const {
+        return temporal || h->vid_mode == VIDEO_MEAN ? (size_t)n * (size_t)h->vid_hw() + (temporal ? h->video_temporal_table(n) : 0) : 0;
+    }
     // queues whatever makes the maps readable; -> the maps [n][hw]
     const float* queue(hipStream_t s, float* scratch) const {
         return temporal ? h->video_temporal(who, first, n, scratch, s) : h->video_finalize(who, first, n, scratch, s);
@@ -2079,12 +2083,15 @@ void ReframeStage::carve(Carve& c) {
     a.sat = c.take<unsigned>(z.sat);
     a.best = c.take<unsigned>(z.best);
     a.part = c.take<unsigned>(z.part);
+    dstarts = r.starts ? c.take<int32_t>((size_t)r.n_shots) : nullptr;
 }
 void ReframeStage::upload(hipStream_t s) {
     if (df) HIPCHECK(hipMemcpyAsync(df, r.frames, ReframeSizes(a).bgr, hipMemcpyHostToDevice, s));
+    if (dstarts) HIPCHECK(hipMemcpyAsync(dstarts, r.starts, (size_t)r.n_shots * sizeof(int32_t), hipMemcpyHostToDevice, s));
 }
 void ReframeStage::launch(hipStream_t s, const unsigned char* sal, unsigned*) {
     a.sal = sal; a.frames = !crops() ? nullptr : df ? df : r.frames_dev;
+    a.starts = dstarts; a.n_shots = dstarts ? r.n_shots : 0;
     HIPCHECK(p3d_reframe_launch(a, s));
 }
 void ReframeStage::results(hipStream_t s) {
@@ -2163,8 +2170,15 @@ int p3d_video_reframe(p3d_handle* h, int first, int n, float scale, int H, int W
     ReframeRequest r{who, n, H, W};
     r.cfg = cfg; r.frames = frames; r.track = track; r.raw = raw; r.mass = mass; r.out = out; r.timed = stage_ms != nullptr;
     std::unique_ptr<ReframeStage> stage;
+    std::vector<int32_t> shots;                            // the installed table in frames of the call: its shots cut the track's filter
     video_stage_run(h, who, first, n, scale, maps_out, stage_ms, 3, [&]() -> ByteStage& {
         if (out && !frames) r.frames_dev = kept_source(h, who, first, n, H, W, "reframes");
+        if (!h->vid_shots.empty()) {
+            shots.push_back(0);
+            for (int32_t st : h->vid_shots)
+                if (st > first && st < first + n) shots.push_back(st - first);
+            r.starts = shots.data(); r.n_shots = (int)shots.size();
+        }
         stage.reset(new ReframeStage(r));
         return *stage;
     });

@@ -1148,12 +1148,13 @@
         vid_count.assign((size_t)frames, 0);
         vid_put.assign((size_t)frames, 0);
         video_source_drop();
+        vid_shots.clear();
         vid_F = frames; vid_mode = mode; vid_last = -1; vid_is_open = true; vid_timed = false;
     }
     void video_close() {
         sync_streams();
         video_free();
-        vid_count.clear(); vid_put.clear();
+        vid_count.clear(); vid_put.clear(); vid_shots.clear();
         vid_is_open = false; vid_F = 0; vid_last = -1; vid_timed = false;
     }
     void video_put_frames(int first, const float* x, int n) {
@@ -1518,17 +1519,58 @@
         for (size_t d = 0; d < t.w.size() && d <= (size_t)TEMPORAL_MAX_RADIUS; ++d) a.w[d] = t.w[d];
         return a;
     }
+    // ---- the shot table of the open video (p3d_video_set_shots, p3d_video_detect_shots; shots.hip) -------
+    // None until installed, and gone with the video it belongs to.  While one is installed the temporal stage filters inside the
+    // shots (the *_shots launches of temporal.hip, from a run table that follows the filtered maps in the scratch) and
+    // p3d_video_reframe smooths its track inside them; nothing else reads it.
+    std::vector<int32_t> vid_shots;                        // the starts, ascending from 0; empty: no table
+    std::vector<int> vid_runs;                             // the host's copy of the last run table (it outlives the asynchronous upload)
+    hipEvent_t ev_shots[3] = {nullptr, nullptr, nullptr};  // around the signal and the decision of the last p3d_video_detect_shots
+    bool shots_timed = false;
+    // the same refusals under a shot table: the reflections stay inside a shot, so r > F - 1 is no refusal, and only frames of the
+    // shots that are read are needed
+    static void temporal_check_shots(const char* who, const TemporalCfg& t, int F, int first, int n, const int32_t* count,
+                                     const int32_t* starts, int n_shots) {
+        if (n < 1 || first < 0 || first > F - n)
+            throw P3dError(std::string(who) + ": frames " + std::to_string(first) + " .. " + std::to_string((int64_t)first + n - 1) +
+                           " are outside [0, " + std::to_string(F) + ")");
+        const int last = first + n - 1;
+        for (int k = 0; k < n_shots; ++k) {
+            const int lo = starts[k], hi = (k + 1 < n_shots ? starts[k + 1] : F) - 1;
+            if (hi < first || lo > last) continue;
+            const int a = std::max(first, lo), b = std::min(last, hi);
+            const int from = t.set.kind == P3D_TEMPORAL_GAUSS ? std::max(lo, a - t.r) : lo, to = t.set.kind == P3D_TEMPORAL_GAUSS ? std::min(hi, b + t.r) : b;
+            for (int f = from; f <= to; ++f)
+                if (count[f] < 1)
+                    throw P3dError(std::string(who) + ": the temporal filter needs frame " + std::to_string(f) + ", which has no prediction yet (count 0)");
+        }
+    }
     void set_video_temporal(const p3d_video_temporal* c) { temporal_cfg = temporal_parse(c); }      // (refuses before anything changes)
     void video_temporal_check(const char* who, int first, int n) const {
         video_need_open(who);
-        temporal_check(who, temporal_cfg, vid_F, first, n, vid_count.data());
+        if (!vid_shots.empty()) temporal_check_shots(who, temporal_cfg, vid_F, first, n, vid_count.data(), vid_shots.data(), (int)vid_shots.size());
+        else temporal_check(who, temporal_cfg, vid_F, first, n, vid_count.data());
     }
+    // floats of scratch behind the n filtered maps that the run table of a read of n frames may take: at most a run a frame and one
+    // more a shot, four ints each
+    size_t video_temporal_table(int n) const { return vid_shots.empty() ? 0 : (size_t)n * 8; }
     // the filtered frames first .. first + n - 1 in `scratch` [n][hw]: one launch between the stage's events
     const float* video_temporal(const char* who, int first, int n, float* scratch, hipStream_t s) {
         video_temporal_check(who, first, n);
         if (!ev_temporal[0]) for (auto& e : ev_temporal) HIPCHECK(hipEventCreate(&e));
         const VideoTemporalArgs a = temporal_args(temporal_cfg, vid_maps, vid_mode == VIDEO_MEAN ? vid_count_dev : nullptr, scratch, vid_F,
                                                   vid_hw(), first, n);
+        if (!vid_shots.empty()) {
+            vid_runs = p3d_video_temporal_runs(a.kind, a.r, a.hw, vid_F, first, n, vid_shots.data(), (int)vid_shots.size());
+            if (vid_runs.size() > video_temporal_table(n)) throw P3dError(std::string(who) + ": the run table outgrew its scratch");
+            int* table = reinterpret_cast<int*>(scratch + (size_t)n * (size_t)vid_hw());
+            HIPCHECK(hipMemcpyAsync(table, vid_runs.data(), vid_runs.size() * sizeof(int), hipMemcpyHostToDevice, s));
+            HIPCHECK(hipEventRecord(ev_temporal[0], s));
+            HIPCHECK(p3d_video_temporal_shots_launch(a, table, (int)(vid_runs.size() / 4), s));
+            HIPCHECK(hipEventRecord(ev_temporal[1], s));
+            temporal_timed = true;
+            return scratch;
+        }
         HIPCHECK(hipEventRecord(ev_temporal[0], s));
         HIPCHECK(p3d_video_temporal_launch(a, s));
         HIPCHECK(hipEventRecord(ev_temporal[1], s));
@@ -1857,6 +1899,7 @@
         if (ev_aug1) hipEventDestroy(ev_aug1);
         for (hipEvent_t e : ev_vid) if (e) hipEventDestroy(e);
         for (hipEvent_t e : ev_temporal) if (e) hipEventDestroy(e);
+        for (hipEvent_t e : ev_shots) if (e) hipEventDestroy(e);
         video_free();
         for (hipEvent_t e : ev_ts) if (e) hipEventDestroy(e);
         trainset_free();

@@ -1,0 +1,301 @@
+// ---- shot boundaries of 8-bit frames (shots.hip; the law in include/p3d_hip.h): one check and one launch description for
+// p3d_shot_distances_u8, p3d_shot_cuts and the hooks --------------------------------------------------------------------------------
+namespace {
+void shots_shape_check(const char* who, int n, int H, int W, int gy, int gx) {
+    if (n < 1 || n > 65535) throw P3dError(std::string(who) + ": 1 .. 65535 frames");
+    if (H < 1 || W < 1) throw P3dError(std::string(who) + ": empty frame");
+    if ((long long)H * W > P3D_SHOTS_MAX_PIXELS) throw P3dError(std::string(who) + ": H * W exceeds 2^28, the bound that keeps a distance in 32 bits");
+    if (gy < 1 || gy > std::min(P3D_SHOTS_MAX_GRID, H) || gx < 1 || gx > std::min(P3D_SHOTS_MAX_GRID, W))
+        throw P3dError(std::string(who) + ": the grid is " + std::to_string(gy) + " x " + std::to_string(gx) + "; 1 <= grid_y <= min(4, H) and 1 <= grid_x <= min(4, W)");
+}
+// the four numbers of the decision (the grid is checked against a frame's shape where there is one)
+void shots_rule_check(const char* who, const int* cfg) {
+    if (cfg[P3D_SHOTS_THRESHOLD] < 1 || cfg[P3D_SHOTS_THRESHOLD] > 1000) throw P3dError(std::string(who) + ": the threshold is 1 .. 1000 permille of 6 H W");
+    if (cfg[P3D_SHOTS_WINDOW] < 0 || cfg[P3D_SHOTS_WINDOW] > 32) throw P3dError(std::string(who) + ": the window is 0 .. 32 frames");
+    if (cfg[P3D_SHOTS_RATIO] < 256 || cfg[P3D_SHOTS_RATIO] > 65535) throw P3dError(std::string(who) + ": the ratio is 256 .. 65535 (q8)");
+    if (cfg[P3D_SHOTS_MIN_LENGTH] < 1) throw P3dError(std::string(who) + ": the minimum length is at least 1 frame");
+}
+// a shot table over F frames: starts[0] == 0, strictly ascending, every start below F
+void shots_table_check(const char* who, const int32_t* starts, int n_shots, int F) {
+    if (n_shots < 1 || n_shots > F) throw P3dError(std::string(who) + ": 1 .. F shots");
+    if (!starts) throw P3dError("null argument");
+    if (starts[0] != 0) throw P3dError(std::string(who) + ": the first shot starts at frame 0, not at " + std::to_string(starts[0]));
+    for (int k = 1; k < n_shots; ++k) {
+        if (starts[k] <= starts[k - 1]) throw P3dError(std::string(who) + ": shot starts ascend strictly; start " + std::to_string(k) + " does not");
+        if (starts[k] >= F) throw P3dError(std::string(who) + ": shot start " + std::to_string(starts[k]) + " is outside [0, " + std::to_string(F) + ")");
+    }
+}
+ShotsArgs shots_args(int n, int H, int W, int gy, int gx, int ballot) {
+    ShotsArgs a;
+    a.n = n; a.H = H; a.W = W; a.gy = gy; a.gx = gx; a.ballot = ballot;
+    const ShotsPlan p = p3d_shots_plan(H, W, gy, gx, n);
+    a.rows_per_block = p.rows_per_block; a.blocks_per_frame = p.blocks_per_frame; a.frames_per_chunk = p.frames_per_chunk;
+    return a;
+}
+size_t shots_tab_words(const ShotsArgs& a) { return (size_t)(p3d_shots_plan(a.H, a.W, a.gy, a.gx, a.n).scratch_bytes / 4); }
+ShotCutArgs shot_cut_args(const int* cfg, int F, long long P, int cap) {
+    ShotCutArgs c;
+    c.F = F; c.P = P; c.cap = cap;
+    c.threshold_permille = cfg[P3D_SHOTS_THRESHOLD]; c.window = cfg[P3D_SHOTS_WINDOW]; c.ratio_q8 = cfg[P3D_SHOTS_RATIO];
+    c.min_length = cfg[P3D_SHOTS_MIN_LENGTH];
+    return c;
+}
+}  // namespace
+extern "C" {
+
+int p3d_shot_distances_u8(int device, const unsigned char* frames, int n, int H, int W, int grid_y, int grid_x, uint32_t* D) {
+    API_BEGIN
+    const char* who = "shot_distances_u8";
+    if (!frames || !D) throw P3dError("null argument");
+    shots_shape_check(who, n, H, W, grid_y, grid_x);
+    metric_args(device, frames, frames, 1, 1, D);
+    ShotsArgs a = shots_args(n, H, W, grid_y, grid_x, P3D_SHOTS_BALLOT);
+    DevArr<unsigned char> df((size_t)n * H * W * 3, frames);
+    DevArr<uint32_t> dD((size_t)n);
+    DevArr<unsigned> tabs(shots_tab_words(a));
+    a.frames = df.p; a.D = dD.p; a.tabs = tabs.p;
+    HIPCHECK(p3d_shots_launch(a, nullptr));
+    dD.get(D, (size_t)n);
+    API_END
+}
+
+int p3d_debug_shot_distances_u8(int device, const unsigned char* frames, int n, int H, int W, int grid_y, int grid_x, int offset, int ballot,
+                                uint32_t* D) {
+    API_BEGIN
+    const char* who = "debug_shot_distances_u8";
+    if (!frames || !D) throw P3dError("null argument");
+    shots_shape_check(who, n, H, W, grid_y, grid_x);
+    if (offset < 0 || offset > 15) throw P3dError(std::string(who) + ": offset in [0, 15]");
+    if (ballot != 0 && ballot != 1) throw P3dError(std::string(who) + ": ballot is 0 or 1");
+    metric_args(device, frames, frames, 1, 1, D);
+    ShotsArgs a = shots_args(n, H, W, grid_y, grid_x, ballot);
+    Guarded<unsigned char> df((size_t)n * H * W * 3, 16, (size_t)offset, frames);
+    Guarded<uint32_t> dD((size_t)n, 16, 0, nullptr);
+    Guarded<unsigned> tabs(shots_tab_words(a), 16, 0, nullptr);
+    a.frames = df.data(); a.D = dD.data(); a.tabs = tabs.data();
+    HIPCHECK(p3d_shots_launch(a, nullptr));
+    dD.back(D, who);
+    tabs.back(nullptr, who);
+    df.unchanged(who);
+    API_END
+}
+
+int p3d_debug_shots_plan(int H, int W, int grid_y, int grid_x, int n, int* rows_per_block, int* blocks_per_frame, int* frames_per_chunk,
+                         int64_t* scratch_bytes) {
+    API_BEGIN
+    if (!rows_per_block || !blocks_per_frame || !frames_per_chunk || !scratch_bytes) throw P3dError("null argument");
+    shots_shape_check("debug_shots_plan", n, H, W, grid_y, grid_x);
+    const ShotsPlan p = p3d_shots_plan(H, W, grid_y, grid_x, n);
+    *rows_per_block = p.rows_per_block; *blocks_per_frame = p.blocks_per_frame; *frames_per_chunk = p.frames_per_chunk;
+    *scratch_bytes = (int64_t)p.scratch_bytes;
+    API_END
+}
+
+int p3d_debug_shots_time(int device, const unsigned char* frames, int n, int H, int W, int grid_y, int grid_x, int reps, double* signal_ms,
+                         double* ballot_ms, double* copy_ms) {
+    API_BEGIN
+    const char* who = "debug_shots_time";
+    if (!frames || !signal_ms || !ballot_ms || !copy_ms) throw P3dError("null argument");
+    shots_shape_check(who, n, H, W, grid_y, grid_x);
+    if (reps < 1 || reps > 1000) throw P3dError(std::string(who) + ": 1 .. 1000 repetitions");
+    metric_args(device, frames, frames, 1, 1, signal_ms);
+    const size_t bytes = (size_t)n * H * W * 3;
+    ShotsArgs a = shots_args(n, H, W, grid_y, grid_x, 0);
+    DevArr<unsigned char> df(bytes, frames), dcopy(bytes);
+    DevArr<uint32_t> dD((size_t)n);
+    DevArr<unsigned> tabs(shots_tab_words(a));
+    a.frames = df.p; a.D = dD.p; a.tabs = tabs.p;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIPCHECK(hipEventCreate(&e0));
+    HIPCHECK(hipEventCreate(&e1));
+    auto timed = [&](const std::function<void()>& work) {
+        float ms = 0.f;
+        HIPCHECK(hipEventRecord(e0, nullptr));
+        work();
+        HIPCHECK(hipEventRecord(e1, nullptr));
+        HIPCHECK(hipEventSynchronize(e1));
+        HIPCHECK(hipEventElapsedTime(&ms, e0, e1));
+        return (double)ms;
+    };
+    // one untimed round warms all three, then they alternate
+    for (int r = -1; r < reps; ++r) {
+        a.ballot = 0;
+        const double t0 = timed([&] { HIPCHECK(p3d_shots_launch(a, nullptr)); });
+        a.ballot = 1;
+        const double t1 = timed([&] { HIPCHECK(p3d_shots_launch(a, nullptr)); });
+        const double t2 = timed([&] { HIPCHECK(hipMemcpyAsync(dcopy.p, df.p, bytes, hipMemcpyDeviceToDevice, nullptr)); });
+        if (r >= 0) { signal_ms[r] = t0; ballot_ms[r] = t1; copy_ms[r] = t2; }
+    }
+    hipEventDestroy(e0);
+    hipEventDestroy(e1);
+    API_END
+}
+
+int p3d_shot_cuts(int device, const uint32_t* D, int F, int64_t P, const int cfg[6], int32_t* starts, int cap, int* n_shots) {
+    API_BEGIN
+    const char* who = "shot_cuts";
+    if (!D || !cfg || !starts || !n_shots) throw P3dError("null argument");
+    if (F < 1 || F > 65535) throw P3dError(std::string(who) + ": 1 .. 65535 frames");
+    if (P < 1 || P > P3D_SHOTS_MAX_PIXELS) throw P3dError(std::string(who) + ": P = H * W is 1 .. 2^28");
+    if (cap < 1) throw P3dError(std::string(who) + ": room for at least one start");
+    shots_rule_check(who, cfg);
+    metric_args(device, D, cfg, 1, 1, starts);
+    ShotCutArgs c = shot_cut_args(cfg, F, (long long)P, cap);
+    Guarded<uint32_t> dD((size_t)F, 16, 0, D);
+    Guarded<unsigned> cand((size_t)F, 16, 0, nullptr);
+    Guarded<int32_t> ds((size_t)cap, 16, 0, nullptr), dn(1, 16, 0, nullptr);
+    c.D = dD.data(); c.cand = cand.data(); c.starts = ds.data(); c.n_shots = dn.data();
+    HIPCHECK(p3d_shot_cuts_launch(c, nullptr));
+    std::vector<int32_t> got((size_t)cap);
+    int32_t count = 0;
+    ds.back(got.data(), who); dn.back(&count, who); cand.back(nullptr, who); dD.unchanged(who);
+    std::copy(got.begin(), got.begin() + std::min(cap, (int)count), starts);
+    *n_shots = (int)count;
+    API_END
+}
+
+int p3d_reframe_shots_u8(int device, const unsigned char* sal, const unsigned char* frames, int n, int H, int W, const p3d_reframe* cfg,
+                         const int32_t* starts, int n_shots, int offset, int32_t* track, int32_t* raw, uint32_t* mass, unsigned char* out) {
+    API_BEGIN
+    const char* who = "reframe_shots_u8";
+    if (!sal) throw P3dError("null argument");
+    reframe_check(who, cfg, n, H, W, track);
+    if ((frames == nullptr) != (out == nullptr)) throw P3dError(std::string(who) + ": out is given exactly when frames are");
+    shots_table_check(who, starts, n_shots, n);
+    if (offset < -1 || offset > 15) throw P3dError(std::string(who) + ": offset in [0, 15], or -1 for the stage on the stream's scratch");
+    metric_args(device, sal, cfg, 1, 1, track);
+    if (offset < 0) {
+        ReframeRequest r{who, n, H, W};
+        r.cfg = cfg; r.frames = frames; r.track = track; r.raw = raw; r.mass = mass; r.out = out; r.starts = starts; r.n_shots = n_shots;
+        ReframeStage stage(r);
+        stage_on_host_bytes(stage, sal);
+        return 0;
+    }
+    ReframeArgs a = reframe_args(*cfg, n, H, W);
+    const ReframeSizes sz(a);
+    Guarded<unsigned char> ds(sz.sal, 16, (size_t)offset, sal), df(frames ? sz.bgr : 0, 16, (size_t)(3 * offset % 16), frames),
+        dout(frames ? sz.crop : 0, 16, (size_t)(5 * offset % 16), nullptr);
+    Guarded<int32_t> dtrack(sz.pairs, 16, 0, nullptr), draw(sz.pairs, 16, 0, nullptr), dst((size_t)n_shots, 16, 0, starts);
+    Guarded<uint32_t> dmass(sz.masses, 16, 0, nullptr), dsat(sz.sat, 16, 0, nullptr), dbest(sz.best, 16, 0, nullptr), dpart(sz.part, 16, 0, nullptr);
+    a.sal = ds.data(); a.frames = frames ? df.data() : nullptr; a.out = frames ? dout.data() : nullptr;
+    a.track = dtrack.data(); a.raw = draw.data(); a.mass = dmass.data(); a.sat = dsat.data(); a.best = dbest.data(); a.part = dpart.data();
+    a.starts = dst.data(); a.n_shots = n_shots;
+    HIPCHECK(p3d_reframe_launch(a, nullptr));
+    dtrack.back(track, who); draw.back(raw, who); dmass.back(mass, who);
+    dsat.back(nullptr, who); dbest.back(nullptr, who); dpart.back(nullptr, who);
+    if (frames) { dout.back(out, who); df.unchanged(who); }
+    ds.unchanged(who); dst.unchanged(who);
+    API_END
+}
+
+int p3d_temporal_filter_shots(int device, int mode, const p3d_video_temporal* cfg, const float* store, const int32_t* count, int F, int64_t hw,
+                              const int32_t* starts, int n_shots, int first, int n, int offset, float* out) {
+    API_BEGIN
+    const char* who = "temporal_filter_shots";
+    if (!store || !out) throw P3dError("null argument");
+    if (mode != VIDEO_NEWEST && mode != VIDEO_MEAN) throw P3dError(std::string(who) + ": mode " + std::to_string(mode) + " is neither P3D_VIDEO_NEWEST (0) nor P3D_VIDEO_MEAN (1)");
+    const p3d_handle::TemporalCfg t = p3d_handle::temporal_parse(cfg);
+    if (!t.on()) throw P3dError(std::string(who) + ": needs a kind (GAUSS or EMA)");
+    if (F < 1 || hw < 1 || (int64_t)F * hw > (int64_t)1 << 31) throw P3dError(std::string(who) + ": bad shape");
+    shots_table_check(who, starts, n_shots, F);
+    std::vector<int32_t> ones;
+    if (!count) { ones.assign((size_t)F, 1); count = ones.data(); }
+    p3d_handle::temporal_check_shots(who, t, F, first, n, count, starts, n_shots);
+    video_hook_device(device, offset);
+    const std::vector<int> runs = p3d_video_temporal_runs(t.set.kind, t.r, hw, F, first, n, starts, n_shots);
+    const int64_t ns = (int64_t)F * hw, no = (int64_t)n * hw;
+    Guarded<float> sb((size_t)ns, 8, (size_t)offset, store), ob((size_t)no, 8, (size_t)offset, nullptr);
+    Guarded<int32_t> cb((size_t)F, 8, 0, count);
+    Guarded<int> rb(runs.size(), 8, 0, runs.data());
+    const VideoTemporalArgs a = p3d_handle::temporal_args(t, sb.data(), mode == VIDEO_MEAN ? cb.data() : nullptr, ob.data(), F, hw, first, n);
+    HIPCHECK(p3d_video_temporal_shots_launch(a, rb.data(), (int)(runs.size() / 4), nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    sb.unchanged(who); cb.unchanged(who); rb.unchanged(who);
+    ob.back(out, who);
+    API_END
+}
+
+// ---- the open video's shot table ----------------------------------------------------------------------------------------------------
+int p3d_video_set_shots(p3d_handle* h, const int32_t* starts, int n_shots) {
+    API_BEGIN
+    const char* who = "video_set_shots";
+    if (!h) throw P3dError("null argument");
+    h->video_need_open(who);
+    if (!starts) { h->vid_shots.clear(); return 0; }
+    shots_table_check(who, starts, n_shots, h->vid_F);
+    h->vid_shots.assign(starts, starts + n_shots);
+    API_END
+}
+
+int p3d_video_get_shots(p3d_handle* h, int32_t* starts, int cap, int* n_shots) {
+    API_BEGIN
+    const char* who = "video_get_shots";
+    if (!h || !n_shots) throw P3dError("null argument");
+    h->video_need_open(who);
+    if (starts && cap < 0) throw P3dError(std::string(who) + ": a negative cap");
+    if (starts) std::copy(h->vid_shots.begin(), h->vid_shots.begin() + std::min((size_t)cap, h->vid_shots.size()), starts);
+    *n_shots = (int)h->vid_shots.size();
+    API_END
+}
+
+int p3d_video_detect_shots(p3d_handle* h, const int cfg[6], uint32_t* D_out, int32_t* starts_out, int cap, int* n_shots, int install) {
+    API_BEGIN
+    const char* who = "video_detect_shots";
+    if (!h || !cfg || !n_shots) throw P3dError("null argument");
+    h->video_need_open(who);
+    need_kept_source(h, who);
+    const int F = h->vid_F, H = h->vid_H0, W = h->vid_W0;
+    shots_shape_check(who, F, H, W, cfg[P3D_SHOTS_GRID_Y], cfg[P3D_SHOTS_GRID_X]);
+    shots_rule_check(who, cfg);
+    if (starts_out && cap < 1) throw P3dError(std::string(who) + ": room for at least one start");
+    kept_source(h, who, 0, F, H, W, "reads");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    const hipStream_t s = h->stream;
+    ShotsArgs a = shots_args(F, H, W, cfg[P3D_SHOTS_GRID_Y], cfg[P3D_SHOTS_GRID_X], P3D_SHOTS_BALLOT);
+    ShotCutArgs c = shot_cut_args(cfg, F, (long long)H * W, F);
+    const size_t words = shots_tab_words(a);
+    unsigned* tabs = nullptr;
+    carve_scratch(s, 0, [&](Carve& cv) {
+        tabs = cv.take<unsigned>(words);
+        a.D = cv.take<uint32_t>((size_t)F);
+        c.cand = cv.take<unsigned>((size_t)F);
+        c.starts = cv.take<int32_t>((size_t)F);
+        c.n_shots = cv.take<int32_t>(1);
+    });
+    a.frames = h->vid_src; a.tabs = tabs; c.D = a.D;
+    if (!h->ev_shots[0]) for (auto& e : h->ev_shots) HIPCHECK(hipEventCreate(&e));
+    HIPCHECK(hipEventRecord(h->ev_shots[0], s));
+    HIPCHECK(p3d_shots_launch(a, s));
+    HIPCHECK(hipEventRecord(h->ev_shots[1], s));
+    HIPCHECK(p3d_shot_cuts_launch(c, s));
+    HIPCHECK(hipEventRecord(h->ev_shots[2], s));
+    h->shots_timed = true;
+    std::vector<int32_t> starts((size_t)F);
+    int32_t count = 0;
+    HIPCHECK(copy_now(&count, c.n_shots, sizeof(count), hipMemcpyDeviceToHost, s));
+    HIPCHECK(copy_now(starts.data(), c.starts, (size_t)F * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (D_out) HIPCHECK(copy_now(D_out, a.D, (size_t)F * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (count < 1 || count > F) throw P3dError(std::string(who) + ": the decision returned no table");
+    starts.resize((size_t)count);
+    if (starts_out) std::copy(starts.begin(), starts.begin() + std::min(cap, (int)count), starts_out);
+    *n_shots = (int)count;
+    if (install) {
+        shots_table_check(who, starts.data(), (int)count, F);
+        h->vid_shots = starts;
+    }
+    API_END
+}
+
+int p3d_video_shots_last_ms(p3d_handle* h, double* ms) {
+    API_BEGIN
+    if (!h || !ms) throw P3dError("null argument");
+    if (!h->shots_timed) throw P3dError("video_shots_last_ms: no p3d_video_detect_shots has run");
+    float t0 = 0.f, t1 = 0.f;
+    HIPCHECK(hipEventSynchronize(h->ev_shots[2]));
+    HIPCHECK(hipEventElapsedTime(&t0, h->ev_shots[0], h->ev_shots[1]));
+    HIPCHECK(hipEventElapsedTime(&t1, h->ev_shots[1], h->ev_shots[2]));
+    ms[0] = t0; ms[1] = t1;
+    API_END
+}
+
+}  // extern "C"

@@ -12,6 +12,7 @@
 // affine output map.  Layout is NDHWC with an explicit row stride (floats per
 // position) so channel slices of concat buffers are addressed in place.
 #pragma once
+#include <vector>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -763,6 +764,12 @@ struct VideoTemporalPlan { int threads = 0, pixels_per_block = 0, frames_per_blo
 VideoTemporalPlan p3d_video_temporal_plan(int kind, int r, long long hw, int n);
 LaunchDesc p3d_video_temporal_desc(const VideoTemporalArgs& a);
 hipError_t p3d_video_temporal_launch(const VideoTemporalArgs& a, hipStream_t s);
+// Under a shot table (starts [n_shots] ascending from 0, host): the runs (f0, f1, lo, hi) of a read of first .. first + n - 1, four
+// ints each -- GAUSS: output frames f0 .. f1 - 1, at most the plan's frames_per_block of them, inside the shot lo .. hi; EMA: the
+// shots from the one `first` lies in, each from its first frame to its last frame that is read.  The launch takes them in device
+// memory and replaces rho by the shot's periodic reflect-101 (r <= F - 1 is not required), restarts the moving average at every lo.
+std::vector<int> p3d_video_temporal_runs(int kind, int r, long long hw, int F, int first, int n, const int32_t* starts, int n_shots);
+hipError_t p3d_video_temporal_shots_launch(const VideoTemporalArgs& a, const int* runs, int n_runs, hipStream_t s);
 
 // ---- saliency metrics + frame pre-processing (metrics.hip; utils/metrics.py:25-287, dataflow.py:187-216) ------
 hipError_t p3d_metric_cc(const float* a, const float* b, int n_maps, int n_pix, double* out, hipStream_t s);
@@ -1118,7 +1125,8 @@ hipError_t p3d_render_launch(const RenderArgs& a, hipStream_t s);
 // boundary.  Per chunk of maps_per_chunk maps: the summed-area tables (two launches), the search, the pick; then the track, the
 // masses at the track's positions (two launches) and the crop.
 // Refused (hipErrorInvalidValue): a missing buffer, frames without out or out without frames, n outside [1, 65535], H * W outside
-// [1, 2^23], a window outside [1, H] x [1, W], a gate or radius outside [0, 255], a plan other than p3d_reframe_plan's.
+// [1, 2^23], a window outside [1, H] x [1, W], a gate or radius outside [0, 255], a plan other than p3d_reframe_plan's, starts
+// without n_shots in 1 .. n or n_shots without starts (the table's values are the caller's to check: they are device memory).
 constexpr int P3D_REFRAME_MAX_PIXELS = 1 << 23;           // 255 * 2^23 < 2^31: a mass fits one unsigned word
 constexpr int P3D_REFRAME_CHUNK = 16;                     // at most this many maps' tables at a time, as P3D_POST_CHUNK
 constexpr long long P3D_REFRAME_SAT_BYTES = 64LL << 20;   // and at most this many bytes of tables (never less than one map's)
@@ -1135,8 +1143,41 @@ struct ReframeArgs {
     unsigned* sat = nullptr; unsigned* best = nullptr; unsigned* part = nullptr;
     int n = 0, H = 0, W = 0, hc = 0, wc = 0, gate = 0, radius = 0;
     int maps_per_chunk = 0, search_blocks = 0;            // p3d_reframe_plan(H, W, hc, wc, n)
+    const int32_t* starts = nullptr; int n_shots = 0;     // a shot table in frames of the call (device; ascending from 0), or none
 };
 hipError_t p3d_reframe_launch(const ReframeArgs& a, hipStream_t s);
+
+// ---- shot boundaries of 8-bit frames (shots.hip; p3d_shot_distances_u8 / p3d_shot_cuts, the law in include/p3d_hip.h) ----
+// The cut signal of n frames [n][H][W][3] of device bytes: D [n] device words, D_0 = 0, D_f the distance of frame f's cell
+// histograms from frame f - 1's.  tabs is scratch of (frames_per_chunk + 1) tables of table_words words on a 16-byte boundary: slot 0
+// holds the last table of the chunk before, slots 1 .. the chunk's frames.  Per chunk: a fill of its slots, the count (grid
+// (blocks_per_frame, frames)), the distances (a block a frame), and a copy of the last slot to slot 0.  ballot: 1 aggregates a wave's
+// equal bins as score_u8.hip's count_bin does, 0 adds every byte on its own (the counts are the same; the time is not).
+// Refused (hipErrorInvalidValue): a missing buffer, n outside [1, 65535], H * W outside [1, 2^28], a grid outside
+// [1, min(4, H)] x [1, min(4, W)], a plan other than p3d_shots_plan's.
+constexpr long long P3D_SHOTS_MAX_PIXELS = 1LL << 28;     // D_f <= 6 P < 2^32
+constexpr int P3D_SHOTS_CHUNK = 64;                       // at most this many frames' tables at a time
+constexpr int SHOTS_BLOCK_BYTES = 64 << 10;               // a block of the count takes whole rows of at most about this many bytes together
+constexpr int P3D_SHOTS_BALLOT = 0;                       // what the entry points count with: plain adds (ballot took 1.4 - 1.8 times as long)
+struct ShotsPlan {
+    int rows_per_block = 0, blocks_per_frame = 0, frames_per_chunk = 0, table_words = 0;
+    long long scratch_bytes = 0;
+};
+ShotsPlan p3d_shots_plan(int H, int W, int gy, int gx, int n);
+struct ShotsArgs {
+    const unsigned char* frames = nullptr; uint32_t* D = nullptr; unsigned* tabs = nullptr;
+    int n = 0, H = 0, W = 0, gy = 0, gx = 0, ballot = 0;
+    int rows_per_block = 0, blocks_per_frame = 0, frames_per_chunk = 0;      // p3d_shots_plan(H, W, gy, gx, n)
+};
+hipError_t p3d_shots_launch(const ShotsArgs& a, hipStream_t s);
+// The cut decision on D [F] device words (one block): cand is scratch of F words; starts [cap] receives the first min(cap, n_shots)
+// shot starts, n_shots [1] their number.  P = H * W of the frames D came from.
+struct ShotCutArgs {
+    const uint32_t* D = nullptr; unsigned* cand = nullptr; int32_t* starts = nullptr; int32_t* n_shots = nullptr;
+    int F = 0, cap = 0; long long P = 0;
+    int threshold_permille = 0, window = 0, ratio_q8 = 0, min_length = 0;
+};
+hipError_t p3d_shot_cuts_launch(const ShotCutArgs& a, hipStream_t s);
 
 // ---- misc ---------------------------------------------------------------------------------------
 hipError_t p3d_add_inplace(float* dst, int lddst, const float* src, int ldsrc, long M, int C, hipStream_t s);

@@ -18,7 +18,8 @@
 //  * reframe_pick: grid (maps), folds the blocks' bests of a map -- a launch of its own in place of an arrival counter: the fold
 //    reads other blocks' stores, and the next launch sees them without any protocol -- and writes the raw track, M_best and T.
 // Then, once over the n maps:
-//  * reframe_track: a thread a frame, the box average of the raw track round frame f (64-bit sums, ends repeated).
+//  * reframe_track: a thread a frame, the box average of the raw track round frame f (64-bit sums, ends repeated); under a shot
+//    table (ReframeArgs::starts) reframe_track_shots in its place: the ends of the frame's shot repeat.
 //  * reframe_mass: grid (REFRAME_MASS_SLICES, n), M of the window at the smoothed position re-summed from the map's bytes (the
 //    table of an earlier chunk is gone by now): a block a slice of the window's rows, a wave a row, in the same words as
 //    reframe_rows; one sum per block to scratch, and reframe_mass_fold, a thread a frame, adds a frame's slices.  (One block a
@@ -207,6 +208,28 @@ __global__ __launch_bounds__(TPB) void reframe_track(ReframeArgs a) {
     a.track[2 * f + 1] = (int)((2 * sx + taps) / (2 * taps));
 }
 
+// The same average inside the frame's shot: starts [n_shots] ascending from 0, in frames of the call; the taps past an end of the
+// shot repeat that end (c(i) = min(max(i, a), b)), so nothing of another shot enters and the window may jump at a cut.
+__global__ __launch_bounds__(TPB) void reframe_track_shots(ReframeArgs a) {
+    const int f = blockIdx.x * TPB + threadIdx.x;
+    if (f >= a.n) return;
+    int k = 0, top = a.n_shots - 1;                         // the last shot that starts at or before f
+    while (k < top) {
+        const int mid = (k + top + 1) >> 1;
+        if (a.starts[mid] <= f) k = mid; else top = mid - 1;
+    }
+    const int lo = a.starts[k], hi = (k + 1 < a.n_shots ? a.starts[k + 1] : a.n) - 1;
+    const int R = a.radius;
+    long long sy = 0, sx = 0;
+    for (int t = -R; t <= R; ++t) {
+        const int i = min(max(f + t, lo), hi);
+        sy += a.raw[2 * i]; sx += a.raw[2 * i + 1];
+    }
+    const long long taps = 2 * R + 1;
+    a.track[2 * f] = (int)((2 * sy + taps) / (2 * taps));
+    a.track[2 * f + 1] = (int)((2 * sx + taps) / (2 * taps));
+}
+
 // M at the smoothed position, from the bytes: block (s, f) sums slice s of the window's rows into part[f][s]
 __global__ __launch_bounds__(TPB) void reframe_mass(ReframeArgs a) {
     __shared__ unsigned wsum[TPB / WAVE];
@@ -292,6 +315,7 @@ __global__ __launch_bounds__(TPB) void reframe_crop(ReframeArgs a) {
 bool args_ok(const ReframeArgs& a) {
     if (!a.sal || !a.track || !a.raw || !a.mass || !a.sat || !a.best || !a.part) return false;
     if ((a.frames == nullptr) != (a.out == nullptr)) return false;
+    if ((a.starts == nullptr) != (a.n_shots == 0) || a.n_shots < 0 || a.n_shots > a.n) return false;
     if (a.n < 1 || a.n > 65535 || a.H < 1 || a.W < 1 || (long long)a.H * a.W > P3D_REFRAME_MAX_PIXELS) return false;
     if (a.hc < 1 || a.hc > a.H || a.wc < 1 || a.wc > a.W || a.gate < 0 || a.gate > 255 || a.radius < 0 || a.radius > 255) return false;
     const ReframePlan p = p3d_reframe_plan(a.H, a.W, a.hc, a.wc, a.n);
@@ -327,7 +351,8 @@ hipError_t p3d_reframe_launch(const ReframeArgs& a, hipStream_t s) {
         if (e != hipSuccess) return e;
     }
     const dim3 frames((unsigned)((a.n + TPB - 1) / TPB));
-    hipLaunchKernelGGL(reframe_track, frames, block, 0, s, a);
+    if (a.starts) hipLaunchKernelGGL(reframe_track_shots, frames, block, 0, s, a);
+    else hipLaunchKernelGGL(reframe_track, frames, block, 0, s, a);
     hipLaunchKernelGGL(reframe_mass, dim3(REFRAME_MASS_SLICES, (unsigned)a.n), block, 0, s, a);
     hipLaunchKernelGGL(reframe_mass_fold, frames, block, 0, s, a);
     if (a.frames) hipLaunchKernelGGL(reframe_crop, dim3((unsigned)((a.hc + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), (unsigned)a.n), block, 0, s, a);

@@ -15,9 +15,13 @@
 //  * video_temporal_ema_kernel<MEAN, V>: one lane per V pixels walks frames 0 .. first + n - 1 and stores from `first`.  The
 //    recurrence is serial along f; the loads are not, and go out EMA_UNROLL frames at a time ahead of it.  Blocks of one wave
 //    spread a small map over as many CUs as it has waves.  V = 4 only where hw is large enough to fill the chip with float4 lanes.
+//  * Under a shot table (p3d_video_set_shots) the two *_shots_kernel twins run the same bodies from a run table (f0, f1, lo, hi) in
+//    scratch (p3d_video_temporal_runs): the reflections bounce at the ends lo and hi of the run's shot, periodically, so a shot
+//    shorter than the radius is legal; the moving average restarts at every shot.  Without a table the launches are the old ones.
 // No atomics, no cross-block state; every operation rounds on its own.
 #include "p3d_kernels.h"
 #include <algorithm>
+#include <vector>
 
 #pragma clang fp contract(off)
 
@@ -60,18 +64,20 @@ template <> struct Pix<4> {
     }
 };
 
-template <bool MEAN, int V>
-__global__ __launch_bounds__(GAUSS_TPB) void video_temporal_gauss_kernel(VideoTemporalArgs a, int fpb) {
+// Output frames f0 .. f1 - 1 of one block, inside the frames lo_b .. hi_b that bound the reflections: the whole video (SHOTS false:
+// 0 and F - 1, r <= F - 1, one bounce at most) or the run's shot (SHOTS true: any length, the walk bounces at either end as often
+// as it must, and stands still in a shot of one frame).
+template <bool MEAN, int V, bool SHOTS>
+__device__ __forceinline__ void gauss_run(const VideoTemporalArgs& a, const int f0, const int f1, const int lo_b, const int hi_b) {
     using P = Pix<V>;
     extern __shared__ float4 ring_raw[];
     P* ring = reinterpret_cast<P*>(ring_raw);      // [2r + 1][GAUSS_TPB]
     constexpr int lanes = GAUSS_TPB;
-    const int tid = threadIdx.x, r = a.r, R = 2 * r + 1, F = a.F;
+    const int tid = threadIdx.x, r = a.r, R = 2 * r + 1;
     const long long p0 = (long long)blockIdx.x * lanes * V;
     const bool vec = V == 4 && (a.hw & 3) == 0 && aligned16(a.store, a.out);
     const long long mine = vec ? p0 + 4ll * tid : p0 + tid;      // V == 4, not vec: pixels mine + k * lanes
     if (mine >= a.hw) return;      // (no barrier below: a lane without pixels may leave)
-    const int f0 = a.first + (int)blockIdx.y * fpb, f1 = min(f0 + fpb, a.first + a.n);
 
     auto load = [&](int g) -> P {
         const float* src = a.store + (long long)g * a.hw;
@@ -94,8 +100,8 @@ __global__ __launch_bounds__(GAUSS_TPB) void video_temporal_gauss_kernel(VideoTe
         return v;
     };
 
-    // the window of the run's first output: frames max(0, f0 - r) .. min(F - 1, f0 + r); frame g lives in slot g mod R
-    const int lo = max(0, f0 - r), hi = min(F - 1, f0 + r);
+    // the window of the run's first output: frames max(lo_b, f0 - r) .. min(hi_b, f0 + r); frame g lives in slot g mod R
+    const int lo = max(lo_b, f0 - r), hi = min(hi_b, f0 + r);
     int slot = lo % R;
     for (int g = lo; g <= hi; g += GAUSS_PRELOAD) {
         P v[GAUSS_PRELOAD];
@@ -113,16 +119,22 @@ __global__ __launch_bounds__(GAUSS_TPB) void video_temporal_gauss_kernel(VideoTe
     for (int f = f0; f < f1; ++f) {
         // frame f + r + 1 joins the window of output f + 1 and takes the slot of frame f - r, which output f still reads
         const int gn = f + r + 1;
-        const bool more = f + 1 < f1 && gn <= F - 1;
+        const bool more = f + 1 < f1 && gn <= hi_b;
         P nxt = P::zero();
         if (more) nxt = load(gn);
         P acc = P::scaled(a.w[0], ring[cs * lanes + tid]);
         int ja = f, jb = f, sa = cs, sb = cs, da = -1, db = 1;      // rho(f - d), rho(f + d) and their slots
+        if (SHOTS && lo_b == hi_b) da = db = 0;
         for (int d = 1; d <= r; ++d) {
-            if (ja == 0) da = 1;
+            if (SHOTS) {
+                if (ja == lo_b && da < 0) da = 1; else if (ja == hi_b && da > 0) da = -1;
+                if (jb == hi_b && db > 0) db = -1; else if (jb == lo_b && db < 0) db = 1;
+            } else {
+                if (ja == lo_b) da = 1;
+                if (jb == hi_b) db = -1;
+            }
             ja += da; sa += da;
             if (sa < 0) sa += R; else if (sa >= R) sa -= R;
-            if (jb == F - 1) db = -1;
             jb += db; sb += db;
             if (sb < 0) sb += R; else if (sb >= R) sb -= R;
             acc.tap(a.w[d], ring[sa * lanes + tid], ring[sb * lanes + tid]);
@@ -146,6 +158,20 @@ __global__ __launch_bounds__(GAUSS_TPB) void video_temporal_gauss_kernel(VideoTe
         }
         if (++cs == R) cs = 0;
     }
+}
+
+template <bool MEAN, int V>
+__global__ __launch_bounds__(GAUSS_TPB) void video_temporal_gauss_kernel(VideoTemporalArgs a, int fpb) {
+    const int f0 = a.first + (int)blockIdx.y * fpb, f1 = min(f0 + fpb, a.first + a.n);
+    gauss_run<MEAN, V, false>(a, f0, f1, 0, a.F - 1);
+}
+
+// Under a shot table: blockIdx.y is a run (f0, f1, lo, hi) of the table in scratch -- output frames f0 .. f1 - 1, all of them in the
+// shot lo .. hi, so that no run straddles a cut and no frame of another shot is ever loaded.
+template <bool MEAN, int V>
+__global__ __launch_bounds__(GAUSS_TPB) void video_temporal_gauss_shots_kernel(VideoTemporalArgs a, const int* runs) {
+    const int* run = runs + 4 * (size_t)blockIdx.y;
+    gauss_run<MEAN, V, true>(a, run[0], run[1], run[2], run[3]);
 }
 
 template <bool MEAN, int V>
@@ -185,14 +211,55 @@ __global__ __launch_bounds__(EMA_TPB) void video_temporal_ema_kernel(VideoTempor
     }
 }
 
+// Under a shot table: the runs are whole shots from their first frame (f0 == lo), the first of them the shot frame `first` lies
+// in; the recurrence restarts with a copy of the bits at every run and nothing before `first` is stored.
+template <bool MEAN, int V>
+__global__ __launch_bounds__(EMA_TPB) void video_temporal_ema_shots_kernel(VideoTemporalArgs a, const int* runs, int n_runs) {
+    using E = Pix<V>;
+    const long long i = ((long long)blockIdx.x * EMA_TPB + threadIdx.x) * V;
+    if (i >= a.hw) return;
+    const float al = a.alpha, b = 1.0f - al;
+    auto load = [&](int g) -> E {
+        E v = E::ld(a.store + (long long)g * a.hw + i);
+        if (MEAN) {
+            const int c = a.count[g];
+            if (c != 1) v.div((float)c);
+        }
+        return v;
+    };
+    auto store = [&](int f, const E& m) {
+        if (f >= a.first) m.st(a.out + (long long)(f - a.first) * a.hw + i);
+    };
+    for (int k = 0; k < n_runs; ++k) {
+        const int begin = runs[4 * k], end = runs[4 * k + 1];
+        E m = load(begin);
+        store(begin, m);
+        int f = begin + 1;
+        for (; f + EMA_UNROLL <= end; f += EMA_UNROLL) {
+            E v[EMA_UNROLL];
+#pragma unroll
+            for (int u = 0; u < EMA_UNROLL; ++u) v[u] = load(f + u);
+#pragma unroll
+            for (int u = 0; u < EMA_UNROLL; ++u) {
+                m.step(al, b, v[u]);
+                store(f + u, m);
+            }
+        }
+        for (; f < end; ++f) {
+            m.step(al, b, load(f));
+            store(f, m);
+        }
+    }
+}
+
 bool ema_vec(const VideoTemporalArgs& a) {
     return a.hw >= EMA_VEC_MIN_HW && (a.hw & 3) == 0 && ((((unsigned long long)a.store | (unsigned long long)a.out)) & 15ull) == 0;
 }
 
-bool temporal_ok(const VideoTemporalArgs& a) {
+bool temporal_ok(const VideoTemporalArgs& a, bool shots = false) {
     if (!a.store || !a.out || a.store == a.out) return false;
     if (a.F < 1 || a.hw < 1 || a.n < 1 || a.first < 0 || a.first > a.F - a.n) return false;
-    if (a.kind == TEMPORAL_GAUSS) return a.r >= 1 && a.r <= TEMPORAL_MAX_RADIUS && a.r <= a.F - 1;      // the reflections stay inside the ring
+    if (a.kind == TEMPORAL_GAUSS) return a.r >= 1 && a.r <= TEMPORAL_MAX_RADIUS && (shots || a.r <= a.F - 1);      // the reflections stay inside the ring
     if (a.kind == TEMPORAL_EMA) return a.alpha >= 0.f && a.alpha < 1.f;
     return false;
 }
@@ -266,5 +333,50 @@ hipError_t p3d_video_temporal_launch(const VideoTemporalArgs& a, hipStream_t s) 
     else if (mean) hipLaunchKernelGGL((video_temporal_gauss_kernel<true, 1>), grid, dim3(GAUSS_TPB), p.lds_bytes, s, a, p.frames_per_block);
     else if (v4) hipLaunchKernelGGL((video_temporal_gauss_kernel<false, 4>), grid, dim3(GAUSS_TPB), p.lds_bytes, s, a, p.frames_per_block);
     else hipLaunchKernelGGL((video_temporal_gauss_kernel<false, 1>), grid, dim3(GAUSS_TPB), p.lds_bytes, s, a, p.frames_per_block);
+    return hipGetLastError();
+}
+
+std::vector<int> p3d_video_temporal_runs(int kind, int r, long long hw, int F, int first, int n, const int32_t* starts, int n_shots) {
+    std::vector<int> runs;
+    const int last = first + n - 1;
+    const int fpb = kind == TEMPORAL_GAUSS ? p3d_video_temporal_plan(kind, r, hw, n).frames_per_block : 0;
+    for (int k = 0; k < n_shots; ++k) {
+        const int lo = starts[k], hi = (k + 1 < n_shots ? starts[k + 1] : F) - 1;
+        if (hi < first || lo > last) continue;
+        if (kind == TEMPORAL_EMA) {
+            runs.insert(runs.end(), {lo, std::min(hi, last) + 1, lo, hi});
+            continue;
+        }
+        for (int f0 = std::max(first, lo); f0 <= std::min(last, hi); f0 += fpb) runs.insert(runs.end(), {f0, std::min(f0 + fpb, std::min(last, hi) + 1), lo, hi});
+    }
+    return runs;
+}
+
+hipError_t p3d_video_temporal_shots_launch(const VideoTemporalArgs& a, const int* runs, int n_runs, hipStream_t s) {
+    if (!temporal_ok(a, true) || !runs || n_runs < 1) return hipErrorInvalidValue;
+    const bool mean = a.count != nullptr;
+    const VideoTemporalPlan p = p3d_video_temporal_plan(a.kind, a.r, a.hw, a.n);
+    if (a.kind == TEMPORAL_EMA) {
+        const bool v4 = ema_vec(a);
+        const long long lanes = v4 ? a.hw / 4 : a.hw, blocks = (lanes + EMA_TPB - 1) / EMA_TPB;
+        if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
+        const dim3 grid((unsigned)blocks);
+        if (mean && v4) hipLaunchKernelGGL((video_temporal_ema_shots_kernel<true, 4>), grid, dim3(EMA_TPB), 0, s, a, runs, n_runs);
+        else if (mean) hipLaunchKernelGGL((video_temporal_ema_shots_kernel<true, 1>), grid, dim3(EMA_TPB), 0, s, a, runs, n_runs);
+        else if (v4) hipLaunchKernelGGL((video_temporal_ema_shots_kernel<false, 4>), grid, dim3(EMA_TPB), 0, s, a, runs, n_runs);
+        else hipLaunchKernelGGL((video_temporal_ema_shots_kernel<false, 1>), grid, dim3(EMA_TPB), 0, s, a, runs, n_runs);
+        return hipGetLastError();
+    }
+    const long long strips = (a.hw + p.pixels_per_block - 1) / p.pixels_per_block;
+    if (strips > 0x7fffffffll || p.lds_bytes > GAUSS_LDS_MAX) return hipErrorInvalidValue;
+    const bool v4 = p.pixels_per_block == 4 * GAUSS_TPB;
+    for (int k0 = 0; k0 < n_runs; k0 += 65535) {            // gridDim.y
+        const dim3 grid((unsigned)strips, (unsigned)std::min(65535, n_runs - k0));
+        const int* at = runs + 4 * (size_t)k0;
+        if (mean && v4) hipLaunchKernelGGL((video_temporal_gauss_shots_kernel<true, 4>), grid, dim3(GAUSS_TPB), p.lds_bytes, s, a, at);
+        else if (mean) hipLaunchKernelGGL((video_temporal_gauss_shots_kernel<true, 1>), grid, dim3(GAUSS_TPB), p.lds_bytes, s, a, at);
+        else if (v4) hipLaunchKernelGGL((video_temporal_gauss_shots_kernel<false, 4>), grid, dim3(GAUSS_TPB), p.lds_bytes, s, a, at);
+        else hipLaunchKernelGGL((video_temporal_gauss_shots_kernel<false, 1>), grid, dim3(GAUSS_TPB), p.lds_bytes, s, a, at);
+    }
     return hipGetLastError();
 }

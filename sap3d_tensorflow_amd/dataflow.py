@@ -149,11 +149,14 @@ def _temporal_cfg(kind, sigma, radius, alpha):
     return _lib.P3dVideoTemporal(_lib.TEMPORAL_KINDS[kind], float(sigma), int(radius), float(alpha))
 
 
-def temporal_filter(maps, kind, sigma=0., radius=0, alpha=0., first=0, n=None, device=0):
+def temporal_filter(maps, kind, sigma=0., radius=0, alpha=0., first=0, n=None, device=0, shots=None, counts=None, mode="newest", offset=0):
     """The temporal stage of P3DSession.set_video_temporal on supplied maps (p3d_temporal_filter): maps [F, ...] float32, one per
     frame, trailing axes flattened to pixels and every count 1.  kind "gauss": the Gaussian of blur_taps(sigma, radius) along
     the frame axis with reflect-101 at the first and last frame, r in 1 .. 24 and r <= F - 1; "ema": m_f = alpha m_{f-1} +
-    (1 - alpha) v_f from m_0 = v_0.  Returns frames first .. first + n - 1 (all by default), [n, ...]."""
+    (1 - alpha) v_f from m_0 = v_0.  Returns frames first .. first + n - 1 (all by default), [n, ...].  shots: the starts of a shot
+    table, ascending from 0 (p3d_temporal_filter_shots): the Gaussian reflects at the ends of every shot, periodically, so any r in
+    1 .. 24 is legal, and the moving average restarts at every shot; then counts [F] (with mode "mean": the maps are sums) and offset
+    (0 .. 3 floats off a 16-byte boundary, every device buffer between guards) are read as well."""
     m = np.ascontiguousarray(maps, dtype=np.float32)
     if m.ndim < 1 or m.size == 0:
         raise ValueError("expected [F, ...] float32 maps")
@@ -162,7 +165,15 @@ def temporal_filter(maps, kind, sigma=0., radius=0, alpha=0., first=0, n=None, d
     cfg = _temporal_cfg(kind, sigma, radius, alpha)
     out = np.empty((max(n, 0),) + m.shape[1:], np.float32)
     fp = C.POINTER(C.c_float)
-    check(lib().p3d_temporal_filter(device, C.byref(cfg), m.ctypes.data_as(fp), F, m.size // F, int(first), n, out.ctypes.data_as(fp)))
+    if shots is None:
+        check(lib().p3d_temporal_filter(device, C.byref(cfg), m.ctypes.data_as(fp), F, m.size // F, int(first), n, out.ctypes.data_as(fp)))
+        return out
+    from . import _lib
+    st = np.ascontiguousarray(shots, np.int32).ravel()
+    cnt = None if counts is None else np.ascontiguousarray(counts, np.int32)
+    i32 = C.POINTER(C.c_int32)
+    check(lib().p3d_temporal_filter_shots(device, _lib.VIDEO_MODES[mode], C.byref(cfg), m.ctypes.data_as(fp), None if cnt is None else cnt.ctypes.data_as(i32),
+                                          F, m.size // F, st.ctypes.data_as(i32), len(st), int(first), n, int(offset), out.ctypes.data_as(fp)))
     return out
 
 
@@ -635,10 +646,11 @@ def reframe_plan(H, W, crop, n=1):
     return dict(positions_per_block=p.value, search_blocks=b.value, maps_per_chunk=m.value, scratch_bytes=s.value)
 
 
-def reframe(sal, frames, crop, gate=0, smooth=0, device=0, offset=None):
+def reframe(sal, frames, crop, gate=0, smooth=0, device=0, offset=None, shots=None):
     """reframe_track and reframe_crop on the device (p3d_reframe_u8): saliency maps uint8 [n, H, W], frames uint8 [n, H, W, 3] in
     B, G, R order or None -> (track, raw, mass, crop or None).  offset (0 .. 15): the test hook p3d_debug_reframe_u8, every device
-    buffer between guards and shifted off a 16-byte boundary."""
+    buffer between guards and shifted off a 16-byte boundary.  shots: the starts of a shot table over the n frames, ascending from
+    0 (p3d_reframe_shots_u8): the track is smoothed inside every shot, whose ends repeat."""
     from ._lib import P3dReframe
     s3, hc, wc = _reframe_shape(sal, crop)
     n, H, W = s3.shape
@@ -655,8 +667,80 @@ def reframe(sal, frames, crop, gate=0, smooth=0, device=0, offset=None):
     u8, i32, u32 = C.POINTER(C.c_ubyte), C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
     head = (device, s3.ctypes.data_as(u8), None if f is None else f.ctypes.data_as(u8), n, H, W, C.byref(cfg))
     tail = (track.ctypes.data_as(i32), raw.ctypes.data_as(i32), mass.ctypes.data_as(u32), None if out is None else out.ctypes.data_as(u8))
-    if offset is None:
+    if shots is not None:
+        st = np.ascontiguousarray(shots, np.int32).ravel()
+        check(lib().p3d_reframe_shots_u8(*head, st.ctypes.data_as(i32), len(st), -1 if offset is None else int(offset), *tail))
+    elif offset is None:
         check(lib().p3d_reframe_u8(*head, *tail))
     else:
         check(lib().p3d_debug_reframe_u8(*head, int(offset), *tail))
     return track, raw, mass, (out if f is not None else None)
+
+
+def _shot_frames(frames):
+    f = np.ascontiguousarray(frames)
+    if f.dtype != np.uint8 or f.ndim != 4 or f.shape[3] != 3 or f.size == 0:
+        raise ValueError("frames are non-empty uint8 [n, H, W, 3] in B, G, R order")
+    return f
+
+
+def shots_cfg(grid=(2, 2), threshold=250, window=2, ratio=512, min_length=3):
+    """The six ints of include/p3d_hip.h's CONFIG ("Shot boundaries of 8-bit frames") in the order of the P3D_SHOTS_* indices:
+    grid = (gy, gx) cells, threshold in permille of 6 H W, window in frames, ratio in 1 / 256, min_length in frames."""
+    from . import _lib
+    gy, gx = (int(grid), int(grid)) if np.isscalar(grid) else (int(grid[0]), int(grid[1]))
+    cfg = (C.c_int * 6)()
+    for k, v in ((_lib.P3D_SHOTS_GRID_Y, gy), (_lib.P3D_SHOTS_GRID_X, gx), (_lib.P3D_SHOTS_THRESHOLD, threshold), (_lib.P3D_SHOTS_WINDOW, window),
+                 (_lib.P3D_SHOTS_RATIO, ratio), (_lib.P3D_SHOTS_MIN_LENGTH, min_length)):
+        cfg[k] = int(v)
+    return cfg
+
+
+def shot_distances(frames, grid=(2, 2), device=0, offset=None, ballot=0):
+    """The cut signal of frames uint8 [n, H, W, 3] on the device (p3d_shot_distances_u8): D uint32 [n], D[0] = 0, D[f] the distance
+    of frame f's gy x gx cell histograms from frame f - 1's.  offset (0 .. 15): the test hook p3d_debug_shot_distances_u8, every
+    device buffer between guards, the frames shifted off a 16-byte boundary, counted with (ballot=1) or without ballot aggregation."""
+    f = _shot_frames(frames)
+    n, H, W, _ = f.shape
+    gy, gx = (int(grid), int(grid)) if np.isscalar(grid) else (int(grid[0]), int(grid[1]))
+    D = np.empty(n, np.uint32)
+    u8, u32 = C.POINTER(C.c_ubyte), C.POINTER(C.c_uint32)
+    if offset is None:
+        check(lib().p3d_shot_distances_u8(device, f.ctypes.data_as(u8), n, H, W, gy, gx, D.ctypes.data_as(u32)))
+    else:
+        check(lib().p3d_debug_shot_distances_u8(device, f.ctypes.data_as(u8), n, H, W, gy, gx, int(offset), int(ballot), D.ctypes.data_as(u32)))
+    return D
+
+
+def shot_cuts(D, P, threshold=250, window=2, ratio=512, min_length=3, device=0):
+    """The cut decision on the device (p3d_shot_cuts): D uint32 [F], P = H * W of the frames it came from -> starts int32
+    [n_shots], strictly ascending from 0."""
+    d = np.ascontiguousarray(D, np.uint32)
+    if d.ndim != 1 or d.size == 0:
+        raise ValueError("D is a non-empty vector")
+    cfg = shots_cfg((1, 1), threshold, window, ratio, min_length)
+    starts, count = np.empty(len(d), np.int32), C.c_int(0)
+    check(lib().p3d_shot_cuts(device, d.ctypes.data_as(C.POINTER(C.c_uint32)), len(d), int(P), cfg, starts.ctypes.data_as(C.POINTER(C.c_int32)),
+                              len(d), C.byref(count)))
+    return starts[:count.value].copy()
+
+
+def shots_plan(H, W, grid=(2, 2), n=1):
+    """Test hook (p3d_debug_shots_plan, host only): dict(rows_per_block, blocks_per_frame, frames_per_chunk, scratch_bytes) of the cut
+    signal's launches for n frames of H x W."""
+    gy, gx = (int(grid), int(grid)) if np.isscalar(grid) else (int(grid[0]), int(grid[1]))
+    r, b, c, s = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int64(0)
+    check(lib().p3d_debug_shots_plan(int(H), int(W), gy, gx, int(n), C.byref(r), C.byref(b), C.byref(c), C.byref(s)))
+    return dict(rows_per_block=r.value, blocks_per_frame=b.value, frames_per_chunk=c.value, scratch_bytes=s.value)
+
+
+def shots_time(frames, grid=(2, 2), reps=20, device=0):
+    """Measurement hook (p3d_debug_shots_time): HIP-event ms of `reps` alternating rounds -> (signal_ms, ballot_ms, copy_ms), float64
+    [reps] each: the cut signal without and with ballot aggregation, and a device-to-device copy of the same bytes."""
+    f = _shot_frames(frames)
+    n, H, W, _ = f.shape
+    gy, gx = (int(grid), int(grid)) if np.isscalar(grid) else (int(grid[0]), int(grid[1]))
+    out = [np.empty(int(reps), np.float64) for _ in range(3)]
+    dp = C.POINTER(C.c_double)
+    check(lib().p3d_debug_shots_time(device, f.ctypes.data_as(C.POINTER(C.c_ubyte)), n, H, W, gy, gx, int(reps), *[o.ctypes.data_as(dp) for o in out]))
+    return tuple(out)

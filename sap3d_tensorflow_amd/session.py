@@ -1024,6 +1024,49 @@ class P3DSession:
             res["maps"] = maps
         return res
 
+    def video_detect_shots(self, grid=(2, 2), threshold=250, window=2, ratio=512, min_length=3, install=True, with_signal=False):
+        """Find the hard cuts of the open video on the device (an addition), from the source kept by video_keep_source: per frame a
+        grid = (gy, gx) of cell histograms of the B, G, R bytes, D_f their distance from the frame before; frame f starts a shot
+        when D_f is at least `threshold` permille of its largest possible value 6 H W, at least ratio / 256 times every other D
+        within `window` frames (a flash fails this), and at least `min_length` frames from the last cut and from the end.  Returns
+        the starts, int32 [n_shots] ascending from 0 (with_signal: also D, uint32 [frames]); install: the table is installed as
+        video_set_shots would.  Dissolves and fades are not detected.  include/p3d_hip.h holds the exact rules."""
+        from . import dataflow
+        F = self.video_info()["frames"]
+        cfg = dataflow.shots_cfg(grid, threshold, window, ratio, min_length)
+        D, starts, count = np.zeros(max(F, 1), np.uint32), np.zeros(max(F, 1), np.int32), C.c_int(0)
+        check(lib().p3d_video_detect_shots(self._h, cfg, _ptr(D, _lib._u32p), _ptr(starts, _lib._i32p), len(starts), C.byref(count),
+                                           1 if install else 0))
+        starts = starts[:count.value].copy()
+        return (starts, D) if with_signal else starts
+
+    def video_set_shots(self, starts):
+        """Install a shot table on the open video: starts ascending from 0, each the first frame of a shot; None removes it.  While
+        one is installed, set_video_temporal's filter runs inside the shots (reflecting at their ends, the moving average restarting)
+        and video_reframe smooths its track inside them; open_video starts without one."""
+        if starts is None:
+            check(lib().p3d_video_set_shots(self._h, None, 0))
+            return
+        st = np.ascontiguousarray(starts, np.int32).ravel()
+        room = st if len(st) else np.zeros(1, np.int32)      # (an empty table is refused by the library, not taken for None)
+        check(lib().p3d_video_set_shots(self._h, _ptr(room, _lib._i32p), len(st)))
+
+    def video_shots(self):
+        """The installed shot table, int32 [n_shots], or None."""
+        count = C.c_int(0)
+        check(lib().p3d_video_get_shots(self._h, None, 0, C.byref(count)))
+        if not count.value:
+            return None
+        st = np.empty(count.value, np.int32)
+        check(lib().p3d_video_get_shots(self._h, _ptr(st, _lib._i32p), len(st), C.byref(count)))
+        return st
+
+    def video_shots_last_ms(self):
+        """HIP-event times of the last video_detect_shots, milliseconds: dict(signal, decision)."""
+        ms = (C.c_double * 2)()
+        check(lib().p3d_video_shots_last_ms(self._h, ms))
+        return dict(signal=ms[0], decision=ms[1])
+
     def video_shuffled_begin(self, ids):
         """The union of the fixation pool's maps ids[b] (int [n, M], 1 <= M <= 64) for each of n frames that video_score_auc will
         score, counted and scanned on the device -> n_other uint32 [n].  Held apart from shuffled_begin's union: an armed
