@@ -121,6 +121,32 @@ int p3d_predict_windows(p3d_handle* h, const float* x, float* pred);
  *      defined at p3d_forward. */
 int p3d_train_step(p3d_handle* h, const float* x, const float* y, float dropout_rate, uint64_t seed, float* loss);
 
+/* ---- Non-finite values (NaN, +inf, -inf) in inputs, activations, gradients and weights.  A corrupt frame must show in the
+ *      loss, not train the network on zeros; tests/test_gpu_nonfinite.py holds every kernel to the six items below.
+ *   1. Forward kernels propagate.  An output is NaN exactly where the float64 reference of the same operation is NaN, and
+ *      nowhere else; the same holds for +inf and for -inf.  The reference is written with propagating primitives:
+ *      relu(v) = v > 0 ? v : (v != v ? v : 0) (numpy's maximum, not fmaxf, which returns the operand that is not NaN), a
+ *      max-pool window -- CBAM's pools over positions and over channels included -- that holds a NaN gives NaN, a variance
+ *      that is NaN stays NaN under its clamp at 0, and every sum is a sum.
+ *   2. Finite values.  Outside that footprint every result is finite, and where the operation couples nothing across the
+ *      poisoned element it has the BITS of the same launch on clean data: the other samples under GroupNorm and CBAM, the
+ *      other channels under BatchNorm, the other maps in the per-map losses, the other elements in the optimisers, the moving
+ *      average and the accumulation kernel, positions outside a convolution's receptive field, the other members of a
+ *      grouped launch.  Every finite value gives the bits it gave before this paragraph existed, and relu(-0.f) is +0.f.
+ *   3. max-pool arg-max: the first NaN tap in (kd, kh, kw) scan order if the window holds one, otherwise the first maximum
+ *      (for a window of nothing but -inf: its first tap inside the tensor).  Both backward kernels send the gradient there.
+ *   4. ReLU gates in the backward pass are selects: pre > 0 ? g : 0, so a NaN pre-activation has a closed gate and passes no
+ *      gradient (references use where(mask, g, 0), never g * mask).  The poison reaches the gradients through the loss, which
+ *      item 1 makes NaN, and through the statistics sums.
+ *   5. The fp16 pointwise mode (p3d_set_pointwise_fp16) is held to the same rule for NaN and +-inf among operands of
+ *      magnitude below 4; finite values that overflow fp16 are not part of this contract.
+ *   6. Infinite weights are outside the contract (SAME padding multiplies zeros by the weight, so 0 * inf at the borders is
+ *      an implementation detail).  NaN weights are inside: a NaN in a tap that lies inside the tensor at every output
+ *      position (the centre tap) makes output channel co NaN at every position.  In the same way the head's filter gradients
+ *      multiply x by the zero gradient of output positions past the border: a NaN or inf x in a border cell also reaches the
+ *      taps of its channel that never read it (that channel's gradient is non-finite either way).
+ *      Not part of the contract: stopping a training run on a non-finite loss (drivers/train.py reports the loss). */
+
 /* Parity hook: forward (training=True) + the selected loss (Smooth-L1 by default) + backward, no Adam, no moving-stat update.
  * pred may be NULL.  Gradients are then readable with p3d_get_grad. */
 int p3d_backward(p3d_handle* h, const float* x, const float* y, float dropout_rate, uint64_t seed,

@@ -292,7 +292,7 @@ def relu(tape, x):
 
     def bwd():
         if out.grad is not None:
-            x.acc(out.grad * (out.data > 0 if mask is None else mask))
+            x.acc(np.where(out.data > 0 if mask is None else mask, out.grad, 0))      # a select: a closed gate passes no NaN
     tape.record(bwd)
     return out
 
@@ -359,7 +359,9 @@ def max_pool3d(tape, x, ksize, strides):
     """tf.nn.max_pool3d(x, [1,kd,kh,kw,1], [1,sd,sh,sw,1], 'SAME') -- Appendix
     A.1/A.6; call sites p3d.py:176,177,183,189,195.  Padded cells are ignored.
     Backward routes dy to the first maximum in (kd,kh,kw) scan order; ties only
-    occur between post-ReLU zeros, whose ReLU gradient is zero anyway."""
+    occur between post-ReLU zeros, whose ReLU gradient is zero anyway.
+    A window that holds a NaN gives NaN, and its arg-max is the first NaN tap in
+    scan order (include/p3d_hip.h, "Non-finite values"); dy goes to that tap alone."""
     xd = x.data
     N, D, H, W, C = xd.shape
     (Do, Ho, Wo), taps = _conv_taps(xd.shape, tuple(ksize) + (C, C), strides)
@@ -369,7 +371,8 @@ def max_pool3d(tape, x, ksize, strides):
         which = np.full((N, Do, Ho, Wo, C), -1, dtype=np.int16)
         for t, (_, osl, isl) in enumerate(taps):
             v = src[isl]
-            better = v > best[osl]
+            # (which == -1: no tap yet -- a window of nothing but -inf keeps its first tap, "the first maximum")
+            better = (v > best[osl]) | (which[osl] == -1) | (np.isnan(v) & ~np.isnan(best[osl]))
             best[osl] = np.where(better, v, best[osl])
             which[osl] = np.where(better, t, which[osl])
         return best, which
@@ -396,7 +399,7 @@ def max_pool3d(tape, x, ksize, strides):
             return
         dx = np.zeros_like(xd)
         for t, (_, osl, isl) in enumerate(taps):
-            dx[isl] += out.grad[osl] * (idx[osl] == t)
+            dx[isl] += np.where(idx[osl] == t, out.grad[osl], 0)      # a select: a NaN dy stays in its own tap
         x.acc(dx)
     tape.record(bwd)
     return out

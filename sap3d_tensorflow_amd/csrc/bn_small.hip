@@ -24,7 +24,9 @@ __device__ __forceinline__ float4 mul4(float4 a, float4 b) { return make_float4(
 __device__ __forceinline__ float4 fma4(float4 a, float4 b, float4 c) {
     return make_float4(fmaf(a.x, b.x, c.x), fmaf(a.y, b.y, c.y), fmaf(a.z, b.z, c.z), fmaf(a.w, b.w, c.w));
 }
-__device__ __forceinline__ float4 relu4(float4 a) { return make_float4(fmaxf(a.x, 0.f), fmaxf(a.y, 0.f), fmaxf(a.z, 0.f), fmaxf(a.w, 0.f)); }
+// relu(NaN) is NaN (fmaxf would return the 0); finite values and -0.f give the bits fmaxf gave
+__device__ __forceinline__ float relu1(float v) { return v > 0.f ? v : (v != v ? v : 0.f); }
+__device__ __forceinline__ float4 relu4(float4 a) { return make_float4(relu1(a.x), relu1(a.y), relu1(a.z), relu1(a.w)); }
 __device__ __forceinline__ float4 gate4(float4 g, float4 pre) {
     return make_float4(pre.x > 0.f ? g.x : 0.f, pre.y > 0.f ? g.y : 0.f, pre.z > 0.f ? g.z : 0.f, pre.w > 0.f ? g.w : 0.f);
 }
@@ -92,9 +94,13 @@ __device__ __forceinline__ void block_sum2(float4& v, float4& w, float4* xch /*[
 // One-pass mean / biased variance of the slab held in registers, shifted by the channel's first row so that
 // E[d^2] - E[d]^2 does not cancel (d = x - x[0]).
 template <int G, int P, int MJ>
-__device__ __forceinline__ void bn_moments(const float4 (&v)[MJ], const float4 shift, int nj, int M, int rowslot, int h, float4* xch,
+__device__ __forceinline__ void bn_moments(const float4 (&v)[MJ], float4 shift, int nj, int M, int rowslot, int h, float4* xch,
                                            int& phase, float4& mean, float4& var) {
     constexpr int RS = 256 / (G * P);
+    // a first row that is inf or NaN is no shift: x - inf would turn a mean of +inf (what the unshifted sums of the other paths and
+    // the reference give) into NaN
+    shift = make_float4(shift.x - shift.x == 0.f ? shift.x : 0.f, shift.y - shift.y == 0.f ? shift.y : 0.f,
+                        shift.z - shift.z == 0.f ? shift.z : 0.f, shift.w - shift.w == 0.f ? shift.w : 0.f);
     float4 s = f4(0.f), q = f4(0.f);
     chain_sum2<P, MJ>(s, q, h, [&](int j, float4& s_, float4& q_) {
         if (h * MJ + j < nj && rowslot + RS * (h * MJ + j) < M) { const float4 d = sub4(v[j], shift); s_ = add4(s_, d); q_ = fma4(d, d, q_); }
@@ -105,6 +111,11 @@ __device__ __forceinline__ void bn_moments(const float4 (&v)[MJ], const float4 s
     mean = add4(shift, md);
     var = sub4(mul4(q, f4(invM)), mul4(md, md));
     var = make_float4(fmaxf(var.x, 0.f), fmaxf(var.y, 0.f), fmaxf(var.z, 0.f), fmaxf(var.w, 0.f));
+    // a sum of squares that is inf or NaN has no variance (inf - inf), and fmaxf would turn that NaN into 0: it stays NaN, as in
+    // bn_finalize_kernel.  (Asked of q, not of var: a second use of the difference changes how the compiler contracts it, and
+    // with it the bits of every finite variance.)
+    var = make_float4(q.x - q.x == 0.f ? var.x : NAN, q.y - q.y == 0.f ? var.y : NAN, q.z - q.z == 0.f ? var.z : NAN,
+                      q.w - q.w == 0.f ? var.w : NAN);
 }
 
 // The per-channel parameters a block needs, loaded TOGETHER WITH its data: read where they are used, behind the block-wide

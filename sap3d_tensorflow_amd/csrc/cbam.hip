@@ -14,11 +14,13 @@ namespace {
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 __device__ __forceinline__ float sigm(float v) { return 1.f / (1.f + expf(-v)); }
+// a max that keeps a NaN operand (fmaxf returns the other one); finite operands give fmaxf's bits
+__device__ __forceinline__ float nanmax(float a, float b) { return a != a ? a : (b != b ? b : fmaxf(a, b)); }
 
 // (sum, max, ties) merge
 __device__ __forceinline__ void merge(float& s, float& m, float& t, float s2, float m2, float t2) {
     s += s2;
-    if (m2 > m) { m = m2; t = t2; } else if (m2 == m) t += t2;
+    if (m2 > m) { m = m2; t = t2; } else if (m2 == m) t += t2; else if (m2 != m2 && m == m) { m = m2; t = t2; }     // a NaN maximum stays
 }
 
 // grid (chunks, N); thread = channel (strided if C > 256); rows of the chunk are walked serially (coalesced over c)
@@ -40,13 +42,13 @@ __global__ __launch_bounds__(256) void chan_pool_kernel(CbamArgs a) {
             for (int q = 0; q < 8; ++q) {
                 const float v = v8[q];
                 s += v;
-                if (v > m) { m = v; t = 1.f; } else if (v == m) t += 1.f;
+                if (v > m) { m = v; t = 1.f; } else if (v == m) t += 1.f; else if (v != v && m == m) { m = v; t = 1.f; }
             }
         }
         for (; r < r1; ++r) {
             const float v = a.x[((long long)n * R + r) * a.ld + c];
             s += v;
-            if (v > m) { m = v; t = 1.f; } else if (v == m) t += 1.f;
+            if (v > m) { m = v; t = 1.f; } else if (v == m) t += 1.f; else if (v != v && m == m) { m = v; t = 1.f; }
         }
         float* o = a.part + (((long long)n * a.chunks + ch) * a.C + c) * 3;
         o[0] = s; o[1] = m; o[2] = t;
@@ -88,7 +90,7 @@ __global__ __launch_bounds__(256) void chan_hidden_kernel(CbamArgs a) {
         if (j < a.Ch) {
             float s = a.b0[j];
             for (int q = 0; q < 32; ++q) s += part[(q * 8 + u) * 2 + br];
-            (br ? a.hmx : a.havg)[(long long)n * a.Ch + j] = fmaxf(s, 0.f);
+            (br ? a.hmx : a.havg)[(long long)n * a.Ch + j] = s > 0.f ? s : (s != s ? s : 0.f);      // relu(NaN) is NaN
         }
     }
 }
@@ -124,9 +126,9 @@ __global__ __launch_bounds__(256) void spat_pool_kernel(CbamArgs a) {
             const float4 v = ld4(a.x + pos * a.ld + c), k = ld4(a.cs + (long long)n * a.C + c);
             const float f0 = v.x * k.x, f1 = v.y * k.y, f2 = v.z * k.z, f3 = v.w * k.w;
             s += f0 + f1 + f2 + f3;
-            m = fmaxf(fmaxf(m, fmaxf(f0, f1)), fmaxf(f2, f3));
+            m = nanmax(nanmax(m, nanmax(f0, f1)), nanmax(f2, f3));
         }
-        for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); m = fmaxf(m, __shfl_xor(m, o)); }
+        for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); m = nanmax(m, __shfl_xor(m, o)); }
         if (lane == 0) { a.sp[pos * 2] = s / (float)a.C; a.sp[pos * 2 + 1] = m; }
     }
 }

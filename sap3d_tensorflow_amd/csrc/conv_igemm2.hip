@@ -236,9 +236,11 @@ __device__ __forceinline__ void issue_a_raw(const IgemmArgs& p, P3dKTap* taps, f
     ++st.issued;
     if (++st.kc == kchunks) { st.kc = 0; ++st.t; }
 }
+// relu(NaN) is NaN (fmaxf would return the 0); finite values and -0.f give the bits fmaxf gave
+__device__ __forceinline__ float relu_nan(float v) { return v > 0.f ? v : (v != v ? v : 0.f); }
 __device__ __forceinline__ float4 relu_affine4(float4 s, float4 u, float4 t) {
-    return make_float4(fmaxf(fmaf(s.x, u.x, t.x), 0.f), fmaxf(fmaf(s.y, u.y, t.y), 0.f), fmaxf(fmaf(s.z, u.z, t.z), 0.f),
-                       fmaxf(fmaf(s.w, u.w, t.w), 0.f));
+    return make_float4(relu_nan(fmaf(s.x, u.x, t.x)), relu_nan(fmaf(s.y, u.y, t.y)), relu_nan(fmaf(s.z, u.z, t.z)),
+                       relu_nan(fmaf(s.w, u.w, t.w)));
 }
 // The transform in two parts: the LDS reads (the lane's raw chunk(s) and its channels' coefficients) are issued with the
 // step's fragment reads, the arithmetic and the store of the transformed chunk run between the MFMA halves, when the data

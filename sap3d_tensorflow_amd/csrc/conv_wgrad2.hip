@@ -215,9 +215,11 @@ __device__ __forceinline__ void raw_load(const WRaw<BM, BN> r, WXIn<BM, BN>& x, 
         x.bv[i] = two_dy ? *reinterpret_cast<const float4*>(r.b2 + at) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
 }
+// relu(NaN) is NaN (fmaxf would return the 0); finite values and -0.f give the bits fmaxf gave
+__device__ __forceinline__ float relu_nan(float v) { return v > 0.f ? v : (v != v ? v : 0.f); }
 __device__ __forceinline__ float4 wrelu4(float4 s, float4 u, float4 t) {
-    return make_float4(fmaxf(fmaf(s.x, u.x, t.x), 0.f), fmaxf(fmaf(s.y, u.y, t.y), 0.f), fmaxf(fmaf(s.z, u.z, t.z), 0.f),
-                       fmaxf(fmaf(s.w, u.w, t.w), 0.f));
+    return make_float4(relu_nan(fmaf(s.x, u.x, t.x)), relu_nan(fmaf(s.y, u.y, t.y)), relu_nan(fmaf(s.z, u.z, t.z)),
+                       relu_nan(fmaf(s.w, u.w, t.w)));
 }
 template <int BM, int BN>
 __device__ __forceinline__ void transform_store(const WXIn<BM, BN>& x, const WMeta& mt, const WCoef& cf, int xt, int dyt,

@@ -18,7 +18,9 @@ __device__ __forceinline__ float4 fma4(float4 a, float4 b, float4 c) {
 __device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ float4 sub4(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
 __device__ __forceinline__ float4 mul4(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
-__device__ __forceinline__ float4 relu4(float4 a) { return make_float4(fmaxf(a.x, 0.f), fmaxf(a.y, 0.f), fmaxf(a.z, 0.f), fmaxf(a.w, 0.f)); }
+// relu(NaN) is NaN (fmaxf would return the 0); finite values and -0.f give the bits fmaxf gave
+__device__ __forceinline__ float relu1(float v) { return v > 0.f ? v : (v != v ? v : 0.f); }
+__device__ __forceinline__ float4 relu4(float4 a) { return make_float4(relu1(a.x), relu1(a.y), relu1(a.z), relu1(a.w)); }
 __device__ __forceinline__ float4 gate4(float4 g, float4 pre) {   // g where pre > 0 (tf.nn.relu gradient)
     return make_float4(pre.x > 0.f ? g.x : 0.f, pre.y > 0.f ? g.y : 0.f, pre.z > 0.f ? g.z : 0.f, pre.w > 0.f ? g.w : 0.f);
 }
@@ -441,7 +443,8 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(PoolArgs a) {
         const int oh = (int)(pos % a.Ho); pos /= a.Ho;
         const int od = (int)(pos % a.Do); const int n = (int)(pos / a.Do);
         float4 best = f4(-INFINITY);
-        unsigned bx = 0, by = 0, bz = 0, bw = 0;          // tap of the first maximum, per channel
+        unsigned bx = 0, by = 0, bz = 0, bw = 0;          // tap of the first NaN if the window holds one, else of the first maximum, per channel
+        bool none = true;                                 // no tap yet: the first one inside the tensor is kept whatever it holds (a window of -inf)
         for (int kd = 0; kd < a.kd; ++kd) {
             const int id = od * a.sd - a.pd + kd;
             if ((unsigned)id >= (unsigned)a.Di) continue;
@@ -453,10 +456,11 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(PoolArgs a) {
                     if ((unsigned)iw >= (unsigned)a.Wi) continue;
                     const float4 v = ld4(a.x + ((((long long)n * a.Di + id) * a.Hi + ih) * a.Wi + iw) * a.ldx + c);
                     const unsigned t = (unsigned)((kd * a.kh + kh) * a.kw + kw);
-                    if (v.x > best.x) { best.x = v.x; bx = t; }
-                    if (v.y > best.y) { best.y = v.y; by = t; }
-                    if (v.z > best.z) { best.z = v.z; bz = t; }
-                    if (v.w > best.w) { best.w = v.w; bw = t; }
+                    if (none || v.x > best.x || (v.x != v.x && best.x == best.x)) { best.x = v.x; bx = t; }
+                    if (none || v.y > best.y || (v.y != v.y && best.y == best.y)) { best.y = v.y; by = t; }
+                    if (none || v.z > best.z || (v.z != v.z && best.z == best.z)) { best.z = v.z; bz = t; }
+                    if (none || v.w > best.w || (v.w != v.w && best.w == best.w)) { best.w = v.w; bw = t; }
+                    none = false;
                 }
             }
         }
@@ -487,7 +491,7 @@ __device__ __forceinline__ float loss_term(float z, float p, float t, int throug
     const float d = p - t;
     const float ad = fabsf(d);
     const bool quad = KIND == 0 && ad < 1.f;
-    g = quad ? d : (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f));
+    g = quad ? d : (d > 0.f ? 1.f : (d < 0.f ? -1.f : (d != d ? d : 0.f)));      // sign(NaN) is NaN
     if (through_sigmoid) g *= p * (1.f - p);
     return KIND == 2 ? ad : (quad ? 0.5f * d * d : ad - 0.5f);
 }
@@ -1103,6 +1107,8 @@ hipError_t p3d_maxpool_fwd(const PoolArgs& a, hipStream_t s) {
 
 // Non-overlapping windows (k == s, no padding: the temporal pools p3d.py:183,189,195): every input cell belongs to
 // exactly one window, so dx is written (or accumulated) directly -- no atomics, no zero fill.
+// the tap the forward kept: the first one equal to y, or the first NaN one where y is NaN
+__device__ __forceinline__ bool pool_hit(float v, float y) { return v == y || (v != v && y != y); }
 __global__ __launch_bounds__(256) void maxpool_bwd_disjoint_kernel(PoolArgs a, int accumulate) {
     p3d_warm_kernarg_lines<(int)(sizeof(PoolArgs) / 64)>();
     P3D_CHAIN_PRIO();
@@ -1125,10 +1131,10 @@ __global__ __launch_bounds__(256) void maxpool_bwd_disjoint_kernel(PoolArgs a, i
                     const long long ipos = (((long long)n * a.Di + od * a.sd + kd) * a.Hi + oh * a.sh + kh) * a.Wi + ow * a.sw + kw;
                     const float4 v = ld4(a.x + ipos * a.ldx + c);
                     float4 d = f4(0.f);
-                    if (!done[0] && v.x == y.x) { d.x = left.x; done[0] = true; }
-                    if (!done[1] && v.y == y.y) { d.y = left.y; done[1] = true; }
-                    if (!done[2] && v.z == y.z) { d.z = left.z; done[2] = true; }
-                    if (!done[3] && v.w == y.w) { d.w = left.w; done[3] = true; }
+                    if (!done[0] && pool_hit(v.x, y.x)) { d.x = left.x; done[0] = true; }
+                    if (!done[1] && pool_hit(v.y, y.y)) { d.y = left.y; done[1] = true; }
+                    if (!done[2] && pool_hit(v.z, y.z)) { d.z = left.z; done[2] = true; }
+                    if (!done[3] && pool_hit(v.w, y.w)) { d.w = left.w; done[3] = true; }
                     float* dst = a.dx + ipos * a.lddx + c;
                     if (accumulate) d = add4(d, ld4(dst));
                     st4(dst, d);
