@@ -33,7 +33,10 @@ on the device (P3DSession.video_render), whatever `--write` and `--truth` do bes
 shot table on every video before its maps are read -- the hard cuts found on the device in the decoded frames
 (P3DSession.video_detect_shots, shaped by `--shots-grid`, `-threshold`, `-window`, `-ratio`, `-min-length`), or the starts in FILE.npy
 -- so that `--temporal` filters inside the shots and `--reframe` smooths its track inside them; it writes `<out>/<video>_shots.npy`
-and, under detect, `<out>/<video>_cutsignal.npy`.  `--reframe DIR` (an addition, needs
+and, under detect, `<out>/<video>_cutsignal.npy`.  `--shot-windows` (an addition, needs `--shots`) installs the table before the
+windows are cut and keeps every window inside its shot (P3DSession.video_predict_shots, dataflow.shot_window_starts): per shot a
+window every `--stride` frames and a last one at the shot's end; a shot shorter than 16 frames takes one window, filled by reflecting
+inside the shot, and no map is predicted from frames of another shot.  `--reframe DIR` (an addition, needs
 `--resident`, may stand beside `--render`) writes DIR/<video>/frame_<k>.png, every frame cut -- not resized -- to the window of
 `--reframe-size HC WC` or `--reframe-aspect A:B` (width : height; default 9:16) that holds the most saliency at or above
 `--reframe-gate`, on a track averaged over `--reframe-smooth` frames to either side (P3DSession.video_reframe, one call per
@@ -104,10 +107,12 @@ def window_starts(F, stride):
 PUT_CHUNK = 64      # frames per upload of the resident path
 
 
-def predict_video_resident(sess, video_u8, batch, stride=1, overlap="newest", times=None, keep_source=False):
+def predict_video_resident(sess, video_u8, batch, stride=1, overlap="newest", times=None, keep_source=False, shot_windows=None):
     """video_u8 [F,H0,W0,3] uint8 RGB -> the open video on the device, every window predicted (P3DSession.open_video /
     video_put_u8 / video_predict); read it with sess.video_maps / video_maps_u8.  times (a dict or None) collects the HIP-event
-    milliseconds of the window cuts and map folds.  keep_source: the decoded frames stay on the device too, for video_render."""
+    milliseconds of the window cuts and map folds.  keep_source: the decoded frames stay on the device too, for video_render.
+    shot_windows (--shot-windows; a callable F -> the shot starts, which installs the video's shot table once the frames are put):
+    the windows are dataflow.shot_window_starts' and stay inside their shots (video_predict_shots)."""
     F = len(video_u8)
     if F < 16:
         raise ValueError("need at least 16 frames")
@@ -116,9 +121,13 @@ def predict_video_resident(sess, video_u8, batch, stride=1, overlap="newest", ti
         sess.video_keep_source(True)
     for i in range(0, F, PUT_CHUNK):
         sess.video_put_u8(i, video_u8[i:i + PUT_CHUNK, ..., ::-1])       # the kernel takes cv2's BGR order
-    starts = window_starts(F, stride)
+    if shot_windows is not None:
+        from sap3d_tensorflow_amd import dataflow
+        starts, predict = dataflow.shot_window_starts(shot_windows(F), F, stride), sess.video_predict_shots
+    else:
+        starts, predict = window_starts(F, stride), sess.video_predict
     for i in range(0, len(starts), batch):
-        sess.video_predict(starts[i:i + batch])
+        predict(starts[i:i + batch])
         if times is not None:
             ms = sess.video_last_ms()
             times["gather"] = times.get("gather", 0.0) + ms["gather"]
@@ -483,6 +492,9 @@ def parse_args(argv=None):
                    "smooths its track inside them.  detect: the hard cuts found on the device in the decoded frames "
                    "(P3DSession.video_detect_shots; the frames are kept on the device); FILE.npy: the shot starts, ascending from 0.  "
                    "Writes <out>/<video>_shots.npy and, under detect, <out>/<video>_cutsignal.npy")
+    p.add_argument("--shot-windows", action="store_true", help="[addition] needs --shots: install the table before the windows are cut and keep "
+                   "every window inside its shot (P3DSession.video_predict_shots) -- per shot a window every --stride frames and a last one "
+                   "at the shot's end; a shot shorter than 16 frames takes one window, filled by reflecting inside the shot")
     p.add_argument("--shots-grid", type=int, nargs=2, default=None, metavar=("GY", "GX"), help="[addition] --shots detect: cells of histograms a frame, 1 .. 4 each (2 2)")
     p.add_argument("--shots-threshold", type=int, default=None, metavar="PERMILLE", help="[addition] --shots detect: a cut's distance is at least "
                    "this many permille of the largest possible, 1 .. 1000 (250)")
@@ -545,6 +557,8 @@ def shots_args(args, error):
     if not args.shots:
         if shaped:
             error("--shots-grid / -threshold / -window / -ratio / -min-length need --shots detect")
+        if args.shot_windows:
+            error("--shot-windows needs --shots detect|FILE.npy: the windows stay inside the table's shots")
         return
     if not args.resident:
         error("--shots needs --resident: the table belongs to a video on the device")
@@ -770,9 +784,15 @@ def run_resident(sess, args, path):
     if reframe_dir:
         os.makedirs(reframe_dir, exist_ok=True)
     detect = bool(args.shots_kw and args.shots_kw["detect"])
-    F = predict_video_resident(sess, np.load(path), args.batch, args.stride, args.overlap, times, keep_source=bool(render_dir or reframe_dir or detect))
+    keep = bool(render_dir or reframe_dir or detect)
+    if args.shot_windows:      # the table goes in before the windows are cut, and they stay inside its shots
+        F = predict_video_resident(sess, np.load(path), args.batch, args.stride, args.overlap, times, keep_source=keep,
+                                   shot_windows=lambda F: shots_video_resident(sess, F, args.out, name, args.shots_kw))
+        starts = sess.video_shots()
+    else:
+        F = predict_video_resident(sess, np.load(path), args.batch, args.stride, args.overlap, times, keep_source=keep)
+        starts = shots_video_resident(sess, F, args.out, name, args.shots_kw) if args.shots_kw else None
     if args.shots_kw:
-        starts = shots_video_resident(sess, F, args.out, name, args.shots_kw)
         print(name, "%d shots, starting at frames %s%s" % (len(starts), " ".join(str(int(v)) for v in starts[:12]), " ..." if len(starts) > 12 else ""))
     t1 = time.perf_counter()
     means = ts = None
@@ -826,9 +846,9 @@ def run_resident(sess, args, path):
     temporal_ms = sess.video_temporal_last_ms() if args.temporal != "off" and args.time else None
     sess.close_video()
     if args.time:
-        print("  %s: wall %.1f ms | resident, stride %d, overlap %s: %d forward passes in %.1f ms (window cuts %.3f ms, map folds %.3f ms "
-              "on the device)" % (os.path.basename(path), (time.perf_counter() - t0) * 1e3, args.stride, args.overlap, times["batches"],
-                                  (t1 - t0) * 1e3, times["gather"], times["scatter"]))
+        print("  %s: wall %.1f ms | resident, stride %d%s, overlap %s: %d forward passes in %.1f ms (window cuts %.3f ms, map folds %.3f ms "
+              "on the device)" % (os.path.basename(path), (time.perf_counter() - t0) * 1e3, args.stride, " inside the shots" if args.shot_windows else "",
+                                  args.overlap, times["batches"], (t1 - t0) * 1e3, times["gather"], times["scatter"]))
         if temporal_ms is not None:
             print("  %s: temporal %s: %.3f ms on the device in the last read-out" % (name, args.temporal, temporal_ms))
         if ts is not None:

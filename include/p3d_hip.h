@@ -1724,7 +1724,8 @@ int p3d_debug_reframe_plan(int H, int W, int crop_h, int crop_w, int n, int* pos
  *             and the bits of a partial read are the slice of a full read.
  *   REFRAME   p3d_video_reframe's SMOOTHED TRACK takes c(i) = min(max(i, a), b), [a, b] the frame's shot intersected with the frames
  *             of the call: the ends of a shot repeat and the window may jump at a cut.  BEST WINDOW, MASSES and CROP are unchanged.
- *   p3d_video_predict's windows still straddle cuts, and p3d_video_score and p3d_video_render do not read the table.
+ *   p3d_video_predict's windows straddle cuts by design, table or no table; p3d_video_predict_shots ("Shot-aware windows" below)
+ *   keeps every window inside its shot.  p3d_video_score and p3d_video_render do not read the table.
  * p3d_temporal_filter_shots  the temporal stage alone under a table, on a host store [F][hw] and counts [F] (NULL: every count 1)
  *                         under `mode`, frames first .. first + n - 1 -> out [n][hw]; every device buffer, the run table included,
  *                         sits between guards, the floats `offset` (0 .. 3) elements past a 16-byte boundary.
@@ -1750,6 +1751,50 @@ int p3d_temporal_filter_shots(int device, int mode, const p3d_video_temporal* cf
 int p3d_reframe_shots_u8(int device, const unsigned char* sal, const unsigned char* frames /* may be NULL */, int n, int H, int W,
                          const p3d_reframe* cfg, const int32_t* starts, int n_shots, int offset /* -1, or 0 .. 15 */, int32_t* track,
                          int32_t* raw /* may be NULL */, uint32_t* mass /* may be NULL */, unsigned char* out /* NULL exactly when frames is */);
+
+/* ---- Shot-aware windows (an ADDITION beside p3d_video_predict, whose windows are T consecutive frames wherever the cuts lie: a
+ * window across a cut shows the network a clip of two unrelated scenes, and every map within T - 1 frames of the cut is predicted
+ * from it).  p3d_video_predict_shots keeps every window inside the shot of its start in the installed table; p3d_video_predict
+ * itself is unchanged, with or without a table, and nothing is allocated until the first call (the per-call slot table [B * T],
+ * freed with the video).  PARITY UNPINNED: the reference has no shots, so this text is the contract and tests/shot_windows_ref.py
+ * replays it in numpy bit for bit.  T, B, F as in "Resident video inference".  Needs an open video with a shot table.
+ * For window k, s = starts[k], [lo, hi] the shot of s in the installed table and L = hi - lo + 1:
+ *   LEGAL    n_windows in 1 .. B; starts strictly ascending, every start greater than last_start and inside [0, F - 1]; and
+ *            s == lo, or s + T - 1 <= hi.  So a shot of at least T frames takes any window that lies wholly inside it, and a shorter
+ *            shot takes exactly one window, at its first frame.
+ *   SLOTS    slot t of clip k reads frame g(k, t) = lo + refl(s - lo + t, L), refl the periodic reflect-101 of TEMPORAL above
+ *            (refl(j, 1) = 0, otherwise m = j mod (2 L - 2), and m where m < L, else 2 L - 2 - m).  For a window inside its shot this
+ *            is the identity; no slot ever leaves [lo, hi].  Every frame g(k, t) must have been put.
+ *   LIVE     live(k) = min(T, hi - s + 1).  Slots t < live(k) are frame s + t itself and are the only ones folded into the map store;
+ *            the reflected slots are padding for the network: their predictions are dropped and the scatter does not read them.
+ *   GATHER   one launch: clip k, slot t of the staged input = frame g(k, t), a copy of the bits.  Clips n_windows .. B - 1 repeat the
+ *            last window's slot row (and fold nothing).
+ *   FORWARD  exactly p3d_video_predict's pass.
+ *   SCATTER  p3d_video_predict's NEWEST / MEAN rules with "t = 0 .. T - 1" replaced by "t = 0 .. live(k) - 1": one launch, k
+ *            ascending, no atomics, the same laws for the counts; last_start = starts[n_windows - 1].  p3d_video_last_ms reports this
+ *            call's gather and scatter.  The call returns synchronised.
+ * Refused (-1, p3d_last_error names the first offender, nothing is launched and nothing changes): no open video; no table;
+ * n_windows outside 1 .. B; then per window, in this order: a start outside [0, F - 1]; not ascending; a start that is neither its
+ * shot's first frame nor T - 1 frames from its end (the message names the shot's [lo, hi]); a frame g(k, t) never put (the message
+ * names the window and the first such slot's frame).
+ * Calls of p3d_video_predict and p3d_video_predict_shots may be mixed on one video: they share the stores and last_start.  Under a
+ * table of one shot the call returns p3d_video_predict's results bit for bit (the gather kernel differs: a slot at a time).
+ * Example: F = 41, table 0 20 25 26 28 (shots of 20, 5, 1, 2, 13 frames).  Start 20 reads 20 21 22 23 24 23 22 21 20 21 22 23 24 23 22 21,
+ * live 5; start 25 reads frame 25 sixteen times, live 1; start 26 reads 26 27 26 27 ..., live 2; start 28 reads 28 .. 40 39 38 37, live 13.
+ * TEST HOOKS (tests/test_gpu_video_shot_windows.py, tests/test_shot_windows_cpu.py), under the table shot_starts [n_shots], validated as
+ * p3d_video_set_shots validates it, with every frame counting as put:
+ *   gather_slots   store [F][frame_elems] -> x [B][T][frame_elems] by GATHER (last_start -1), buffers and offset as p3d_debug_video_gather;
+ *   scatter_shots  p3d_debug_video_scatter with LIVE: pred [B][T][hw][ld], store and count in place, device counts == plan counts;
+ *   plan_shots     host only, no HIP call: the counts after the call in count_out [F], g in slots_out [B][T] (the padding clips'
+ *                  rows included) and live_out [B] (0 for a padding clip); all three untouched after a refusal. */
+int p3d_video_predict_shots(p3d_handle* h, const int* starts, int n_windows);
+int p3d_debug_video_gather_slots(int device, const float* store, int F, int T, int64_t frame_elems, const int32_t* shot_starts, int n_shots,
+                                 const int* starts, int n_windows, int B, int offset, float* x);
+int p3d_debug_video_scatter_shots(int device, int mode, const float* pred, int B, int T, int64_t hw, int ld, const int32_t* shot_starts,
+                                  int n_shots, const int* starts, int n_windows, int F, int last_start, float* store /* in/out [F][hw] */,
+                                  int32_t* count /* in/out [F] */, int offset);
+int p3d_debug_video_plan_shots(int mode, int F, int T, int B, int last_start, const int32_t* count_in, const int32_t* shot_starts, int n_shots,
+                               const int* starts, int n_windows, int32_t* count_out, int* slots_out /* [B*T] */, int* live_out /* [B] */);
 
 /* CRC-32C of a host buffer (host-side helper of the TensorFlow checkpoint reader / writer, sap3d_tensorflow_amd/tf_checkpoint.py:
  * the bundle format of train.py:180-185,266-267 checksums every tensor); crc = running value, 0 to start. */

@@ -1710,6 +1710,14 @@ int p3d_video_predict(p3d_handle* h, const int* starts, int n_windows) {
     API_END
 }
 
+int p3d_video_predict_shots(p3d_handle* h, const int* starts, int n_windows) {
+    API_BEGIN
+    if (!h || !starts) throw P3dError("null argument");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    h->video_predict_shots(starts, n_windows);
+    API_END
+}
+
 int p3d_video_last_ms(p3d_handle* h, double ms[2]) {
     API_BEGIN
     if (!h || !ms) throw P3dError("null argument");
@@ -2473,7 +2481,7 @@ int p3d_video_score_auc(p3d_handle* h, int first, int n, float scale, int H, int
     API_END
 }
 
-// The three launches of video.hip from their launch descriptions, on host arrays.  Every device buffer sits `offset` elements past
+// The launches of video.hip from their launch descriptions, on host arrays.  Every device buffer sits `offset` elements past
 // a 16-byte boundary between guard elements; a guard or an input that a launch changed is an error.
 }  // extern "C"
 namespace {
@@ -2510,12 +2518,14 @@ int p3d_debug_video_gather(int device, const float* store, int F, int T, int64_t
     API_END
 }
 
-int p3d_debug_video_scatter(int device, int mode, const float* pred, int B, int T, int64_t hw, int ld, const int* starts, int n_windows,
-                            int F, int last_start, float* store, int32_t* count, int offset) {
-    API_BEGIN
+}  // extern "C"
+namespace {
+// p3d_debug_video_scatter and, with a shot table, p3d_debug_video_scatter_shots: the scatter launch of the plan of one call
+void video_scatter_hook(int device, int mode, const float* pred, int B, int T, int64_t hw, int ld, const int32_t* shots, int n_shots,
+                        const int* starts, int n_windows, int F, int last_start, float* store, int32_t* count, int offset) {
     if (!pred || !starts || !store || !count) throw P3dError("null argument");
     if (hw < 1 || ld < 1) throw P3dError("video_scatter: bad shape");
-    const p3d_handle::VideoPlan p = p3d_handle::video_plan(mode, F, T, B, last_start, count, nullptr, starts, n_windows);
+    const p3d_handle::VideoPlan p = p3d_handle::video_plan(mode, F, T, B, last_start, count, nullptr, starts, n_windows, shots, n_shots);
     const int64_t np = (int64_t)B * T * hw * ld, ns = (int64_t)F * hw;
     if (np > (int64_t)1 << 31 || ns > (int64_t)1 << 31) throw P3dError("video_scatter: the hook takes up to 2^31 floats");
     video_hook_device(device, offset);
@@ -2540,6 +2550,56 @@ int p3d_debug_video_scatter(int device, int mode, const float* pred, int B, int 
     if (memcmp(co.data(), p.count.data(), (size_t)F * 4) != 0) throw P3dError("video_scatter: the device's counts differ from the plan's");
     sb.back(store, "video_scatter");
     memcpy(count, p.count.data(), (size_t)F * 4);
+}
+}  // namespace
+extern "C" {
+
+int p3d_debug_video_scatter(int device, int mode, const float* pred, int B, int T, int64_t hw, int ld, const int* starts, int n_windows,
+                            int F, int last_start, float* store, int32_t* count, int offset) {
+    API_BEGIN
+    video_scatter_hook(device, mode, pred, B, T, hw, ld, nullptr, 0, starts, n_windows, F, last_start, store, count, offset);
+    API_END
+}
+
+int p3d_debug_video_scatter_shots(int device, int mode, const float* pred, int B, int T, int64_t hw, int ld, const int32_t* shot_starts,
+                                  int n_shots, const int* starts, int n_windows, int F, int last_start, float* store, int32_t* count,
+                                  int offset) {
+    API_BEGIN
+    if (!shot_starts) throw P3dError("null argument");
+    video_scatter_hook(device, mode, pred, B, T, hw, ld, shot_starts, n_shots, starts, n_windows, F, last_start, store, count, offset);
+    API_END
+}
+
+int p3d_debug_video_gather_slots(int device, const float* store, int F, int T, int64_t frame_elems, const int32_t* shot_starts, int n_shots,
+                                 const int* starts, int n_windows, int B, int offset, float* x) {
+    API_BEGIN
+    if (!store || !shot_starts || !starts || !x) throw P3dError("null argument");
+    if (T < 1 || F < T || frame_elems < 1 || B < 1) throw P3dError("video_gather_slots: bad shape");
+    if ((int64_t)F * frame_elems > (int64_t)1 << 31 || (int64_t)B * T * frame_elems > (int64_t)1 << 31) throw P3dError("video_gather_slots: the hook takes up to 2^31 floats");
+    const std::vector<int32_t> none((size_t)F, 0);      // the windows as p3d_video_predict_shots validates them, every frame put
+    const p3d_handle::VideoPlan p = p3d_handle::video_plan(VIDEO_NEWEST, F, T, B, -1, none.data(), nullptr, starts, n_windows, shot_starts, n_shots);
+    video_hook_device(device, offset);
+    const int64_t ns = (int64_t)F * frame_elems, nx = (int64_t)B * T * frame_elems;
+    Guarded<float> sb((size_t)ns, 8, (size_t)offset, store), xb((size_t)nx, 8, (size_t)offset, nullptr);
+    DevArr<int> tab(p.slots.size(), p.slots.data());
+    VideoGatherSlotsArgs a;
+    a.store = sb.data(); a.x = xb.data(); a.frames = tab.p; a.frames_host = p.slots.data(); a.B = B; a.T = T; a.F = F; a.frame_elems = frame_elems;
+    if (std::string(p3d_video_gather_slots_desc(a).kernel) != "video_gather_slots_kernel") throw P3dError("video_gather_slots: launch description names another kernel");
+    HIPCHECK(p3d_video_gather_slots(a, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    sb.unchanged("video_gather_slots");
+    xb.back(x, "video_gather_slots");
+    API_END
+}
+
+int p3d_debug_video_plan_shots(int mode, int F, int T, int B, int last_start, const int32_t* count_in, const int32_t* shot_starts, int n_shots,
+                               const int* starts, int n_windows, int32_t* count_out, int* slots_out, int* live_out) {
+    API_BEGIN
+    if (!shot_starts || !count_out || !slots_out || !live_out) throw P3dError("null argument");
+    const p3d_handle::VideoPlan p = p3d_handle::video_plan(mode, F, T, B, last_start, count_in, nullptr, starts, n_windows, shot_starts, n_shots);
+    memcpy(count_out, p.count.data(), (size_t)F * sizeof(int32_t));
+    std::copy(p.slots.begin(), p.slots.end(), slots_out);
+    std::copy(p.live.begin(), p.live.end(), live_out);
     API_END
 }
 

@@ -1036,6 +1036,7 @@
     int vid_H0 = 0, vid_W0 = 0;
     std::vector<unsigned char> vid_has_src;                        // [F]: the frame's bytes are in the store
     P3dVideoDst* d_vid_dst = nullptr; int* d_vid_src = nullptr; int* d_vid_starts = nullptr;      // the per-call tables, [B*T], [B*T], [B]
+    int* d_vid_slots = nullptr;                                    // p3d_video_predict_shots's per-call table [B*T], from its first call
     std::vector<int32_t> vid_count; std::vector<unsigned char> vid_put;
     hipEvent_t ev_vid[4] = {nullptr, nullptr, nullptr, nullptr};      // around the last call's gather and scatter (p3d_video_last_ms)
     bool vid_timed = false;
@@ -1045,30 +1046,68 @@
     // What one p3d_video_predict does to the stores, from host state alone (no HIP call): validates as the header says -- the
     // message names the first offending window or frame -- and builds the padded starts, the scatter table and the counts after
     // the call.  put (or null: every frame counts as put) has F entries.
-    struct VideoPlan { std::vector<int> starts; std::vector<P3dVideoDst> dst; std::vector<int> src; std::vector<int32_t> count; };
+    //
+    // shots (or null: p3d_video_predict's plan, windows of T consecutive frames wherever they lie) is the installed table of
+    // n_shots starts: the plan of p3d_video_predict_shots ("Shot-aware windows").  Window k then reads slots [k * T + t] = g(k, t),
+    // reflected inside its shot, and only its first live [k] slots -- the frames starts[k] + t themselves -- reach the scatter table.
+    struct VideoPlan {
+        std::vector<int> starts; std::vector<P3dVideoDst> dst; std::vector<int> src; std::vector<int32_t> count;
+        std::vector<int> slots, live;      // [B * T], [B]: under a shot table only; the padding clips repeat the last window's slots, live 0
+    };
+    static int video_refl(int j, int L) {      // the TEMPORAL paragraph's periodic reflect-101 of j >= 0 into 0 .. L - 1
+        if (L == 1) return 0;
+        const int m = j % (2 * L - 2);
+        return m < L ? m : 2 * L - 2 - m;
+    }
     static VideoPlan video_plan(int mode, int F, int T, int B, int last_start, const int32_t* count, const unsigned char* put,
-                                const int* starts, int n_windows) {
+                                const int* starts, int n_windows, const int32_t* shots = nullptr, int n_shots = 0) {
         if (mode != VIDEO_NEWEST && mode != VIDEO_MEAN) throw P3dError("video: mode " + std::to_string(mode) + " is neither P3D_VIDEO_NEWEST (0) nor P3D_VIDEO_MEAN (1)");
         if (T < 1 || B < 1 || F < T) throw P3dError("video: needs at least T = " + std::to_string(T) + " frames, has " + std::to_string(F));
         if (!starts || !count) throw P3dError("null argument");
+        if (shots) {
+            if (n_shots < 1 || shots[0] != 0 || shots[n_shots - 1] >= F) throw P3dError("video: the shot table starts at 0 and every shot starts before frame F = " + std::to_string(F));
+            for (int i = 1; i < n_shots; ++i)
+                if (shots[i] <= shots[i - 1]) throw P3dError("video: the shot table does not ascend at shot " + std::to_string(i));
+        }
         if (n_windows < 1 || n_windows > B) throw P3dError("video: n_windows = " + std::to_string(n_windows) + " is outside 1 .. batch = " + std::to_string(B));
+        VideoPlan p;
+        if (shots) { p.slots.assign((size_t)B * T, 0); p.live.assign((size_t)B, 0); }
         for (int k = 0; k < n_windows; ++k) {
             const int prev = k ? starts[k - 1] : last_start;
             const std::string w = "video: window " + std::to_string(k) + " starts at " + std::to_string(starts[k]);
-            if (starts[k] < 0 || starts[k] > F - T) throw P3dError(w + ", outside [0, F - T = " + std::to_string(F - T) + "]");
+            if (!shots && (starts[k] < 0 || starts[k] > F - T)) throw P3dError(w + ", outside [0, F - T = " + std::to_string(F - T) + "]");
+            if (shots && (starts[k] < 0 || starts[k] > F - 1)) throw P3dError(w + ", outside [0, F - 1 = " + std::to_string(F - 1) + "]");
             if (starts[k] <= prev)
                 throw P3dError(w + (k ? ", not after window " + std::to_string(k - 1) + "'s " : ", not after the last start accepted, ") + std::to_string(prev));
-            for (int t = 0; put && t < T; ++t)
-                if (!put[starts[k] + t]) throw P3dError(w + " and holds frame " + std::to_string(starts[k] + t) + ", which was never put");
+            if (!shots) {
+                for (int t = 0; put && t < T; ++t)
+                    if (!put[starts[k] + t]) throw P3dError(w + " and holds frame " + std::to_string(starts[k] + t) + ", which was never put");
+                continue;
+            }
+            const int i = (int)(std::upper_bound(shots, shots + n_shots, (int32_t)starts[k]) - shots) - 1;
+            const int lo = shots[i], hi = (i + 1 < n_shots ? shots[i + 1] : F) - 1, L = hi - lo + 1;
+            if (starts[k] != lo && starts[k] + T - 1 > hi)
+                throw P3dError(w + ", which is neither the first frame of its shot [" + std::to_string(lo) + ", " + std::to_string(hi) + "] nor T - 1 = " +
+                               std::to_string(T - 1) + " frames from its end");
+            p.live[(size_t)k] = std::min(T, hi - starts[k] + 1);
+            for (int t = 0; t < T; ++t) {
+                const int g = lo + video_refl(starts[k] - lo + t, L);
+                if (put && !put[g]) throw P3dError(w + " and reads frame " + std::to_string(g) + ", which was never put");
+                p.slots[(size_t)k * T + t] = g;
+            }
         }
-        VideoPlan p;
+        for (int k = n_windows; shots && k < B; ++k)      // the padding clips repeat the last window's slot row and fold nothing
+            std::copy(p.slots.begin() + (size_t)(n_windows - 1) * T, p.slots.begin() + (size_t)n_windows * T, p.slots.begin() + (size_t)k * T);
+        const auto live = [&](int k) { return shots ? p.live[(size_t)k] : T; };
         p.starts.assign(starts, starts + n_windows);
         p.starts.resize((size_t)B, starts[n_windows - 1]);      // the padding clips repeat the last window
         p.count.assign(count, count + F);
-        const int f0 = starts[0], span = starts[n_windows - 1] + T - f0;
+        const int f0 = starts[0];
+        int span = 0;      // starts ascend and a window ends no earlier than the one before it: the last window's end
+        for (int k = 0; k < n_windows; ++k) span = std::max(span, starts[k] + live(k) - f0);
         std::vector<int> n((size_t)span, 0), row((size_t)span, -1);
         for (int k = 0; k < n_windows; ++k)
-            for (int t = 0; t < T; ++t) ++n[(size_t)(starts[k] + t - f0)];
+            for (int t = 0; t < live(k); ++t) ++n[(size_t)(starts[k] + t - f0)];
         int nsrc = 0;
         for (int i = 0; i < span; ++i) {      // rows ascending by frame; NEWEST: only frames nothing has written, their first contributor
             const int before = count[f0 + i];
@@ -1081,7 +1120,7 @@
         }
         p.src.assign((size_t)nsrc, 0);
         for (int k = 0; k < n_windows; ++k)      // ascending k within every frame
-            for (int t = 0; t < T; ++t) {
+            for (int t = 0; t < live(k); ++t) {
                 const int r = row[(size_t)(starts[k] + t - f0)];
                 if (r < 0) continue;
                 P3dVideoDst& d = p.dst[(size_t)r];
@@ -1100,11 +1139,11 @@
                            " are outside [0, " + std::to_string(vid_F) + ")");
     }
     void video_free() {
-        for (void* p : {(void*)vid_frames, (void*)vid_maps, (void*)vid_count_dev, (void*)vid_u8, (void*)d_vid_dst, (void*)d_vid_src, (void*)d_vid_starts})
+        for (void* p : {(void*)vid_frames, (void*)vid_maps, (void*)vid_count_dev, (void*)vid_u8, (void*)d_vid_dst, (void*)d_vid_src, (void*)d_vid_starts, (void*)d_vid_slots})
             if (p) hipFree(p);
         video_source_drop();
         vid_frames = vid_maps = nullptr; vid_count_dev = nullptr; vid_u8 = nullptr; vid_u8_bytes = 0;
-        d_vid_dst = nullptr; d_vid_src = nullptr; d_vid_starts = nullptr;
+        d_vid_dst = nullptr; d_vid_src = nullptr; d_vid_starts = nullptr; d_vid_slots = nullptr;
         vid_cap = 0;
     }
     // the source store goes with the video it belongs to
@@ -1209,19 +1248,40 @@
         video_need_open("video_predict");
         const int B = x_in->N, T = x_in->D;
         const VideoPlan p = video_plan(vid_mode, vid_F, T, B, vid_last, vid_count.data(), vid_put.data(), starts, n_windows);
+        video_issue(p, starts[n_windows - 1]);
+    }
+    // p3d_video_predict_shots: the same call with every window held inside its shot of the installed table
+    void video_predict_shots(const int* starts, int n_windows) {
+        video_need_open("video_predict_shots");
+        if (vid_shots.empty()) throw P3dError("video_predict_shots: the open video has no shot table (p3d_video_set_shots, p3d_video_detect_shots)");
+        const int B = x_in->N, T = x_in->D;
+        if ((int64_t)B * T > 65535) throw P3dError("video_predict_shots: batch * T = " + std::to_string((int64_t)B * T) + " slots, the gather takes 65535");
+        const VideoPlan p = video_plan(vid_mode, vid_F, T, B, vid_last, vid_count.data(), vid_put.data(), starts, n_windows, vid_shots.data(), (int)vid_shots.size());
+        if (!d_vid_slots) HIPCHECK(hipMalloc((void**)&d_vid_slots, (size_t)B * T * sizeof(int)));
+        video_issue(p, starts[n_windows - 1]);
+    }
+    // One accepted call: the tables up, gather, p3d_predict_windows's pass, scatter; a plan with slots gathers slot by slot.
+    void video_issue(const VideoPlan& p, int last) {
+        const int B = x_in->N, T = x_in->D;
+        const bool by_slots = !p.slots.empty();
         VideoGatherArgs g;
         g.store = vid_frames; g.x = x_in->p; g.starts = d_vid_starts; g.starts_host = p.starts.data();
         g.B = B; g.T = T; g.F = vid_F; g.frame_elems = vid_frame_elems();
+        VideoGatherSlotsArgs gs;
+        gs.store = vid_frames; gs.x = x_in->p; gs.frames = d_vid_slots; gs.frames_host = p.slots.data();
+        gs.B = B; gs.T = T; gs.F = vid_F; gs.frame_elems = vid_frame_elems();
         VideoScatterArgs sc;
         sc.mode = vid_mode; sc.pred = pred->p; sc.ld = pred->ld; sc.maps = B * T; sc.hw = vid_hw();
         sc.store = vid_maps; sc.count = vid_count_dev; sc.F = vid_F;
         sc.dst = d_vid_dst; sc.src = d_vid_src; sc.dst_host = p.dst.data(); sc.src_host = p.src.data();
         sc.ndst = (int)p.dst.size(); sc.nsrc = (int)p.src.size();
-        HIPCHECK(hipMemcpyAsync(d_vid_starts, p.starts.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, stream));
+        if (by_slots) HIPCHECK(hipMemcpyAsync(d_vid_slots, p.slots.data(), p.slots.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+        else HIPCHECK(hipMemcpyAsync(d_vid_starts, p.starts.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, stream));
         if (sc.ndst) HIPCHECK(hipMemcpyAsync(d_vid_dst, p.dst.data(), p.dst.size() * sizeof(P3dVideoDst), hipMemcpyHostToDevice, stream));
         if (sc.ndst) HIPCHECK(hipMemcpyAsync(d_vid_src, p.src.data(), p.src.size() * sizeof(int), hipMemcpyHostToDevice, stream));
         HIPCHECK(hipEventRecord(ev_vid[0], stream));
-        HIPCHECK(p3d_video_gather(g, stream));
+        if (by_slots) HIPCHECK(p3d_video_gather_slots(gs, stream));
+        else HIPCHECK(p3d_video_gather(g, stream));
         HIPCHECK(hipEventRecord(ev_vid[1], stream));
         Ctx c; c.training = false; c.drop = 0.f; c.update_moving = false; c.per_sample = true; c.s = stream;      // p3d_predict_windows's pass
         run_forward(c);
@@ -1231,7 +1291,7 @@
         HIPCHECK(hipEventRecord(ev_vid[3], stream));
         HIPCHECK(hipStreamSynchronize(stream));
         vid_count = p.count;
-        vid_last = starts[n_windows - 1];
+        vid_last = last;
         vid_timed = true;
     }
     // frames first .. first + n - 1 as the read-out returns them: the map store itself under NEWEST; under MEAN `scratch`

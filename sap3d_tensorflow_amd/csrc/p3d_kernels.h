@@ -685,7 +685,7 @@ LaunchDesc p3d_augment_desc(int stage, const AugArgs& a);
 hipError_t p3d_augment_launch(int stage, const AugArgs& a, hipStream_t s);
 
 // ---- resident video inference (video.hip; p3d_video_*, the contract in include/p3d_hip.h) -----------------------------------------
-// A frame store [F][frame_elems] and a map store [F][hw] with a contribution count per frame.  Three launches, each described once
+// A frame store [F][frame_elems] and a map store [F][hw] with a contribution count per frame.  Four launches, each described once
 // for the handle and for the hooks.  Every table reaches its kernel in device memory; the launcher checks the same rows on the
 // host first (a row that leaves a buffer: hipErrorInvalidValue, nothing launched), because the kernels trust them.
 //   gather   clip b of x [B][T][frame_elems] = frames starts[b] .. starts[b] + T - 1 of the store, a copy of the bits (the caller
@@ -714,6 +714,16 @@ struct VideoScatterArgs {
 struct VideoMeanArgs { const float* sum = nullptr; const int32_t* count = nullptr; float* out = nullptr; int n = 0; long long hw = 0; };
 LaunchDesc p3d_video_gather_desc(const VideoGatherArgs& a);
 hipError_t p3d_video_gather(const VideoGatherArgs& a, hipStream_t s);
+//   gather_slots  (p3d_video_predict_shots) slot i of x [B * T][frame_elems] = frame frames[i] of the store, a copy of the bits: a
+//            window that reflects inside its shot is not one run of the store, so every slot names its frame.  frames [B * T] in
+//            device memory, the same rows on the host; a row outside [0, F) or B * T > 65535: hipErrorInvalidValue, nothing launched.
+struct VideoGatherSlotsArgs {
+    const float* store = nullptr; float* x = nullptr;
+    const int* frames = nullptr; const int* frames_host = nullptr;      // [B * T], device memory / the same rows on the host
+    int B = 0, T = 0, F = 0; long long frame_elems = 0;
+};
+LaunchDesc p3d_video_gather_slots_desc(const VideoGatherSlotsArgs& a);
+hipError_t p3d_video_gather_slots(const VideoGatherSlotsArgs& a, hipStream_t s);
 LaunchDesc p3d_video_scatter_desc(const VideoScatterArgs& a);
 hipError_t p3d_video_scatter(const VideoScatterArgs& a, hipStream_t s);
 LaunchDesc p3d_video_mean_desc(const VideoMeanArgs& a);

@@ -7,6 +7,9 @@
 //    run of T * frame_elems floats; consecutive lanes take consecutive floats, 16 bytes per lane where the clip's source and
 //    destination are 16-byte aligned (the network's case: H and W are multiples of 16), else element by element (the hook's
 //    misaligned bases, and whatever is left past the last whole 16 bytes).  A copy of the bits.
+//  * video_gather_slots_kernel (p3d_video_predict_shots): blockIdx.y is a slot of the call's table frames [B * T].  A window that
+//    reflects inside a short shot is not one run of the store, so every slot is its own contiguous run of frame_elems floats, copied
+//    as the clip above is: 16 bytes per lane where that slot's source and destination are 16-byte aligned, else element by element.
 //  * video_scatter_kernel<MODE>: blockIdx.y is a destination frame of the call's table (P3dVideoDst), and every destination element
 //    is written by exactly one lane, which walks the frame's contributing maps in the table's order (ascending window).  NEWEST
 //    copies the first contributor's bits; MEAN starts from them (count 0 before the call) or from the stored sum and adds the
@@ -41,6 +44,19 @@ __global__ __launch_bounds__(TPB) void video_gather_kernel(const float* store, f
         done = n4 << 2;
     }
     for (long long i = done + tid; i < clip_elems; i += stride) d[i] = s[i];
+}
+
+__global__ __launch_bounds__(TPB) void video_gather_slots_kernel(const float* store, float* x, const int* frames, long long frame_elems) {
+    const unsigned* s = reinterpret_cast<const unsigned*>(store + (long long)frames[blockIdx.y] * frame_elems);
+    unsigned* d = reinterpret_cast<unsigned*>(x + (long long)blockIdx.y * frame_elems);
+    const long long stride = (long long)gridDim.x * TPB, tid = (long long)blockIdx.x * TPB + threadIdx.x;
+    long long done = 0;
+    if (aligned16(s, d)) {
+        const long long n4 = frame_elems >> 2;
+        for (long long i = tid; i < n4; i += stride) reinterpret_cast<uint4*>(d)[i] = reinterpret_cast<const uint4*>(s)[i];
+        done = n4 << 2;
+    }
+    for (long long i = done + tid; i < frame_elems; i += stride) d[i] = s[i];
 }
 
 template <int MODE>
@@ -115,6 +131,14 @@ bool gather_ok(const VideoGatherArgs& a) {
     return true;
 }
 
+bool gather_slots_ok(const VideoGatherSlotsArgs& a) {
+    if (!a.store || !a.x || !a.frames || !a.frames_host) return false;
+    if (a.B < 1 || a.T < 1 || (long long)a.B * a.T > 65535 || a.F < 1 || a.frame_elems < 1) return false;
+    for (int i = 0; i < a.B * a.T; ++i)      // no slot may leave the store: the gather trusts the table
+        if (a.frames_host[i] < 0 || a.frames_host[i] >= a.F) return false;
+    return true;
+}
+
 bool scatter_ok(const VideoScatterArgs& a) {
     if (!a.pred || !a.store || !a.count || !a.dst || !a.src || !a.dst_host || !a.src_host) return false;
     if (a.mode != VIDEO_NEWEST && a.mode != VIDEO_MEAN) return false;
@@ -139,6 +163,17 @@ hipError_t p3d_video_gather(const VideoGatherArgs& a, hipStream_t s) {
     if (!gather_ok(a)) return hipErrorInvalidValue;
     const long long clip = (long long)a.T * a.frame_elems;
     hipLaunchKernelGGL(video_gather_kernel, dim3(grid_x((clip + 3) / 4), a.B), dim3(TPB), 0, s, a.store, a.x, a.starts, a.frame_elems, clip);
+    return hipGetLastError();
+}
+
+LaunchDesc p3d_video_gather_slots_desc(const VideoGatherSlotsArgs& a) {
+    return {"video_gather_slots_kernel", 0.0, (double)a.B * a.T * (double)a.frame_elems * 8.0};
+}
+
+hipError_t p3d_video_gather_slots(const VideoGatherSlotsArgs& a, hipStream_t s) {
+    if (!gather_slots_ok(a)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(video_gather_slots_kernel, dim3(grid_x((a.frame_elems + 3) / 4), a.B * a.T), dim3(TPB), 0, s, a.store, a.x, a.frames,
+                       a.frame_elems);
     return hipGetLastError();
 }
 

@@ -725,6 +725,29 @@ def shot_cuts(D, P, threshold=250, window=2, ratio=512, min_length=3, device=0):
     return starts[:count.value].copy()
 
 
+def shot_window_starts(shot_starts, frames, stride=1, T=16):
+    """The window starts of P3DSession.video_predict_shots that cover a video of `frames` frames under the table shot_starts
+    (ascending from 0): per shot of L frames from lo, [lo] where L < T -- the one window a short shot takes -- else lo + 0, stride,
+    2 stride, ... and a last one at L - T, so that every frame is covered; the shots' lists one after the other.  Host arithmetic."""
+    st = [int(s) for s in shot_starts]
+    F, stride, T = int(frames), int(stride), int(T)
+    if not st or st[0] != 0 or any(b <= a for a, b in zip(st, st[1:])) or st[-1] >= F:
+        raise ValueError("shot starts ascend strictly from 0 and stay below the %d frames" % F)
+    if stride < 1 or T < 1:
+        raise ValueError("stride and T are at least 1")
+    out = []
+    for lo, end in zip(st, st[1:] + [F]):
+        L = end - lo
+        if L < T:
+            out.append(lo)
+            continue
+        offs = list(range(0, L - T + 1, stride))
+        if offs[-1] != L - T:
+            offs.append(L - T)
+        out.extend(lo + o for o in offs)
+    return out
+
+
 def shots_plan(H, W, grid=(2, 2), n=1):
     """Test hook (p3d_debug_shots_plan, host only): dict(rows_per_block, blocks_per_frame, frames_per_chunk, scratch_bytes) of the cut
     signal's launches for n frames of H x W."""

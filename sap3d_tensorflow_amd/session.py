@@ -879,6 +879,17 @@ class P3DSession:
             raise ValueError("starts is a list of window starts")
         check(lib().p3d_video_predict(self._h, st.ctypes.data_as(_lib._ip), len(st)))
 
+    def video_predict_shots(self, starts):
+        """video_predict with every window held inside its shot of the installed table (video_set_shots / video_detect_shots; an
+        addition): a start is its shot's first frame or at least T - 1 frames from the shot's end (T the session's frames), a window of a
+        shorter shot is filled by reflecting inside the shot, and only the frames start .. min(start + T - 1, the shot's end) take
+        its maps.
+        dataflow.shot_window_starts lays such windows out; include/p3d_hip.h ("Shot-aware windows") holds the exact rules."""
+        st = np.ascontiguousarray(starts, dtype=np.int32)
+        if st.ndim != 1:
+            raise ValueError("starts is a list of window starts")
+        check(lib().p3d_video_predict_shots(self._h, st.ctypes.data_as(_lib._ip), len(st)))
+
     def video_last_ms(self):
         """HIP-event times of the last video_predict's window cut and map fold: dict(gather, scatter), milliseconds."""
         ms = (C.c_double * 2)()
