@@ -445,6 +445,13 @@ int p3d_debug_perturb(p3d_handle* h, int mode, int stream, int delay_us);
 int p3d_debug_perturb_count(p3d_handle* h, int64_t* delays, int64_t* syncs);
 int p3d_debug_perturb_selftest(int device, int mode, int slow, int delay_us, int with_wait, float* out);
 
+/* ---- what the host layer holds outside the graph's arenas (TEST HOOK, tests/test_gpu_private_resources.py): the device blocks
+ *      and bytes, and the timing events, that are live in this process at the moment of the call -- the stores of an open video,
+ *      training set, prior or fixation pool, the baseline of p3d_set_eval_extra, the buffers of an op-level entry point while it
+ *      runs.  Process-wide over all handles; a handle's arenas, its streams and its ordering events are not counted.  A facility
+ *      that is closed, and a handle that is destroyed, return what they took.  Any pointer may be NULL. */
+int p3d_debug_private_resources(int64_t* blocks, int64_t* bytes, int64_t* events);
+
 /* ---- decisions of the last forward (TEST HOOK, tests/test_gpu_pinned.py): the ReLU gates and max-pool choices the backward pass of
  *      this handle will use -- so that the oracle can differentiate the SAME piecewise-linear branch (a float32 forward takes
  *      a handful of near-zero decisions differently from a float64 one, and each moves a gradient tensor by per cent).

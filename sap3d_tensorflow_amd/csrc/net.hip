@@ -63,6 +63,8 @@ struct P3dError : std::runtime_error {
         if (r_ != ncclSuccess) throw P3dError(std::string(#expr) + " failed: " + ncclGetErrorString(r_)); \
     } while (0)
 
+#include "dev_mem.inc"
+
 enum InitKind { INIT_XAVIER = 0, INIT_ZEROS = 1, INIT_ONES = 2, INIT_VS = 3 };
 
 struct Param {
@@ -1567,6 +1569,11 @@ struct p3d_handle {
 #include "net_gn.inc"
 #include "net_graphs.inc"
 #include "net_plan.inc"
+#include "net_postcfg.inc"
+#include "net_prior.inc"
+#include "net_fixpool.inc"
+#include "net_video.inc"
+#include "net_trainset.inc"
 #include "net_sched.inc"
 };
 

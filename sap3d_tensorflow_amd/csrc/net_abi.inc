@@ -579,6 +579,14 @@ int p3d_debug_perturb_count(p3d_handle* h, int64_t* delays, int64_t* syncs) {
     API_END
 }
 
+int p3d_debug_private_resources(int64_t* blocks, int64_t* bytes, int64_t* events) {
+    API_BEGIN
+    if (blocks) *blocks = g_dev_blocks.load();
+    if (bytes) *bytes = g_dev_bytes.load();
+    if (events) *events = g_dev_events.load();
+    API_END
+}
+
 int p3d_train_step(p3d_handle* h, const float* x, const float* y, float dropout_rate, uint64_t seed, float* loss) {
     API_BEGIN
     if (!h || !x || !y) throw P3dError("null argument");
@@ -637,9 +645,9 @@ int p3d_last_augment_ms(p3d_handle* h, double* ms) {
     if (!h || !ms) throw P3dError("null argument");
     if (!h->aug_on || !h->aug_have) throw P3dError("augmentation: nothing was augmented (p3d_set_augment)");
     HIPCHECK(hipSetDevice(h->cfg.device));
-    HIPCHECK(hipEventSynchronize(h->ev_aug1));
+    HIPCHECK(hipEventSynchronize(h->aug_ev[1]));
     float t = 0.f;
-    HIPCHECK(hipEventElapsedTime(&t, h->ev_aug0, h->ev_aug1));
+    HIPCHECK(hipEventElapsedTime(&t, h->aug_ev[0], h->aug_ev[1]));
     *ms = (double)t;
     API_END
 }
@@ -975,16 +983,22 @@ int p3d_comm_info(p3d_handle* h, int* n_ranks, int* rank, int* device) {
 
 // ---- single-operator entry points ------------------------------------------------------------------
 namespace {
-struct DevBuf {
-    float* p = nullptr;
-    explicit DevBuf(int64_t n, const float* host = nullptr) {
-        HIPCHECK(hipMalloc((void**)&p, (size_t)(n > 0 ? n : 1) * 4));
-        // the single-operator entry points launch on the null stream (Ctx::s == nullptr), and so do their buffers
-        if (host) HIPCHECK(copy_now(p, host, (size_t)n * 4, hipMemcpyHostToDevice, nullptr));
-        else HIPCHECK(fill_now(p, 0, (size_t)(n > 0 ? n : 1) * 4, nullptr));
+// The single-operator entry points launch on the null stream (Ctx::s == nullptr), and so do their buffers: n elements (at least
+// one), uploaded from `host` when given.
+extern "C++" {
+template <typename T>
+struct DevArr : DevMem<T> {
+    explicit DevArr(size_t n, const T* host = nullptr) : DevMem<T>(n > 0 ? n : 1, "no device memory for an op-level buffer") {
+        if (host) HIPCHECK(copy_now(this->p, host, n * sizeof(T), hipMemcpyHostToDevice, nullptr));
     }
-    ~DevBuf() { hipFree(p); }
-    void get(float* host, int64_t n) { HIPCHECK(hipDeviceSynchronize()); HIPCHECK(copy_now(host, p, (size_t)n * 4, hipMemcpyDeviceToHost, nullptr)); }
+    void get(T* host, size_t n) { HIPCHECK(hipDeviceSynchronize()); HIPCHECK(copy_now(host, this->p, n * sizeof(T), hipMemcpyDeviceToHost, nullptr)); }
+};
+}
+// floats, zero where nothing is uploaded
+struct DevBuf : DevArr<float> {
+    explicit DevBuf(int64_t n, const float* host = nullptr) : DevArr<float>((size_t)(n > 0 ? n : 0), host) {
+        if (!host) HIPCHECK(fill_now(p, 0, this->n * 4, nullptr));
+    }
 };
 int64_t prod5(const int64_t s[5]) { return s[0] * s[1] * s[2] * s[3] * s[4]; }
 bool is_stem_shape(const int64_t xs[5], const int64_t ws[5]) { return xs[4] % 4 != 0 && ws[0] == 1; }

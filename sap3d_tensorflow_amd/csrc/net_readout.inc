@@ -1,15 +1,5 @@
 // ---- metrics / pre-processing entry points (metrics.hip) -------------------------------------------------------
 namespace {
-template <typename T>
-struct DevArr {
-    T* p = nullptr;
-    explicit DevArr(size_t n, const T* host = nullptr) {
-        HIPCHECK(hipMalloc((void**)&p, (n > 0 ? n : 1) * sizeof(T)));
-        if (host) HIPCHECK(copy_now(p, host, n * sizeof(T), hipMemcpyHostToDevice, nullptr));
-    }
-    ~DevArr() { hipFree(p); }
-    void get(T* host, size_t n) { HIPCHECK(hipDeviceSynchronize()); HIPCHECK(copy_now(host, p, n * sizeof(T), hipMemcpyDeviceToHost, nullptr)); }
-};
 // op level: a device array of `n` elements between `guard` elements of guard words on either side, the data `shift` elements in
 template <typename T>
 struct Guarded {
@@ -195,7 +185,6 @@ void check_indices(const int* idx, size_t n, long long n_pix, const char* what) 
     for (size_t i = 0; i < n; ++i)
         if (idx[i] < 0 || idx[i] >= n_pix) throw P3dError(std::string(what) + ": random index out of range");
 }
-using StageTimer = p3d_handle::StageTimer;
 // ---- the smoothing / normalisation stage of p3d_set_postprocess (postprocess.hip), one launch sequence for every caller ------
 // What a setting asks for: the effective radius, its weights, the normalisation.  Built on the host, no HIP call.
 struct PostPlan {
@@ -203,10 +192,10 @@ struct PostPlan {
     PostPlan() {}
     explicit PostPlan(const p3d_postprocess* cfg) {
         if (!cfg) return;
-        r = p3d_handle::post_radius(*cfg);
+        r = p3d_handle::PostCfg::radius(*cfg);
         norm = cfg->norm;
-        on = !p3d_handle::post_neutral(*cfg);
-        if (r > 0) taps = p3d_handle::post_taps(cfg->sigma, r);
+        on = !p3d_handle::PostCfg::neutral(*cfg);
+        if (r > 0) taps = p3d_handle::PostCfg::taps(cfg->sigma, r);
     }
     void fits(int H, int W) const {
         if (r > std::min(H, W) - 1)
@@ -233,10 +222,10 @@ struct Stages {
     Stages() {}
     // the handle's settings (each was parsed when it was set)
     explicit Stages(const p3d_handle* h)
-        : post(h->post_on ? &h->post_cfg : nullptr), match(h->match_cfg), prior{h->prior_mode, h->prior_a, h->prior_map, h->prior_H, h->prior_W} {}
+        : post(h->post.on ? &h->post.cfg : nullptr), match(h->match), prior{h->prior.mode, h->prior.a, h->prior.map, h->prior.H, h->prior.W} {}
     // a hook's arguments, refused in this order: cfg, match.  prior: H x W floats, or null until the hook has its copy on the device
     Stages(const p3d_postprocess* cfg, const p3d_hist_match* m, const float* prior_, int mode, float a, int H, int W)
-        : post(cfg), match(p3d_handle::match_parse(m)), prior{mode, a, prior_, H, W} {}
+        : post(cfg), match(p3d_handle::MatchCfg::parse(m)), prior{mode, a, prior_, H, W} {}
     bool chain() const { return post.on || match.on() || prior.on(); }
     void fits(int H, int W) const { post.fits(H, W); prior.fits(H, W); }
 };
@@ -410,7 +399,7 @@ void eval_maps(hipStream_t s, const EvalRequest& rq) {
             throw P3dError("eval_shuffled: the fixation pool is " + std::to_string(sh->H) + " x " + std::to_string(sh->W) + ", the evaluation " +
                            std::to_string(H) + " x " + std::to_string(W));
         if (!sh->per_rep) throw P3dError("null argument");
-        p3d_handle::shuffled_check_draws("eval_shuffled", sh->ranks, sh->n_rows, sh->n_other, B, sh->n_rep, sh->step);
+        p3d_handle::FixPool::check_draws("eval_shuffled", sh->ranks, sh->n_rows, sh->n_other, B, sh->n_rep, sh->step);
         for (int b = 0; b < B; ++b) {
             const long long want = std::min<long long>(n_fix[b], sh->n_other[b]);
             if (sh->n_rows[b] != want)
@@ -588,30 +577,30 @@ int p3d_eval_last_frames(p3d_handle* h, const unsigned char* density, int Hd, in
     rq.stages = Stages(h);
     // p3d_set_eval_extra: its launch joins the sequence; an evaluation of another size than the baseline's runs without it and
     // p3d_last_eval_extra says so
-    EvalExtra extra{h->extra_flags, h->extra_base, h->extra_bstat, h->extra_H, h->extra_W, nullptr};
+    EvalExtra extra{h->extra.flags, h->extra.base, h->extra.bstat, h->extra.H, h->extra.W, nullptr};
     const bool fits = !(extra.flags & P3D_EVAL_INFO_GAIN) || (extra.H == H && extra.W == W);
     std::vector<double> xv((size_t)pr->N * 2);
     extra.out = xv.data();
-    if (extra.flags) { h->extra_state = p3d_handle::EXTRA_NONE; h->extra_eval_H = H; h->extra_eval_W = W; }
+    if (extra.flags) { h->extra.state = p3d_handle::EXTRA_NONE; h->extra.eval_H = H; h->extra.eval_W = W; }
     // p3d_eval_shuffled_draws armed this one evaluation: whatever becomes of it, the next one is plain again
-    const bool armed = h->sh_armed;
-    h->sh_armed = false;
+    const bool armed = h->fixpool.armed;
+    h->fixpool.armed = false;
     std::vector<double> sv;
     ShuffledEval sh{};
     if (armed) {
-        if ((int)h->sh_n_other.size() != pr->N) throw P3dError("eval_shuffled: the union was taken for " + std::to_string(h->sh_n_other.size()) + " clips, the batch has " + std::to_string(pr->N));
-        sv.assign((size_t)pr->N * h->sh_n_rep, 0.0);
-        h->sh_have = false;
-        sh = ShuffledEval{h->sh_uni, h->sh_prefix, h->sh_bsum, h->sh_n_other_dev, h->sh_n_other.data(), h->fp_nw, h->fp_H, h->fp_W,
-                          h->sh_ranks.data(), h->sh_n_rows.data(), h->sh_n_rep, h->sh_step, sv.data(), h->fp_score_ms};
+        if ((int)h->fixpool.sh.n_other.size() != pr->N) throw P3dError("eval_shuffled: the union was taken for " + std::to_string(h->fixpool.sh.n_other.size()) + " clips, the batch has " + std::to_string(pr->N));
+        sv.assign((size_t)pr->N * h->fixpool.n_rep, 0.0);
+        h->fixpool.have = false;
+        sh = ShuffledEval{h->fixpool.sh.uni, h->fixpool.sh.prefix, h->fixpool.sh.bsum, h->fixpool.sh.n_other_dev, h->fixpool.sh.n_other.data(), h->fixpool.nw, h->fixpool.H, h->fixpool.W,
+                          h->fixpool.ranks.data(), h->fixpool.n_rows.data(), h->fixpool.n_rep, h->fixpool.step, sv.data(), h->fixpool_ms + 2};
     }
     rq.extra = extra.flags && fits ? &extra : nullptr;
     rq.sh = armed ? &sh : nullptr;
     eval_maps(h->stream, rq);
-    if (armed) { h->sh_last.swap(sv); h->sh_have = true; }
+    if (armed) { h->fixpool.last.swap(sv); h->fixpool.have = true; }
     if (extra.flags) {
-        h->extra_state = fits ? p3d_handle::EXTRA_HAVE : p3d_handle::EXTRA_SHAPE;
-        if (fits) h->extra_last.swap(xv);
+        h->extra.state = fits ? p3d_handle::EXTRA_HAVE : p3d_handle::EXTRA_SHAPE;
+        if (fits) h->extra.last.swap(xv);
     }
     API_END
 }
@@ -628,24 +617,24 @@ int p3d_set_eval_extra(p3d_handle* h, int flags, const float* baseline, int H, i
 int p3d_get_eval_extra(p3d_handle* h, int* flags, const float** baseline, int* H, int* W) {
     API_BEGIN
     if (!h) throw P3dError("null handle");
-    if (flags) *flags = h->extra_flags;
-    if (baseline) *baseline = h->extra_base_host.empty() ? nullptr : h->extra_base_host.data();
-    if (H) *H = h->extra_H;
-    if (W) *W = h->extra_W;
+    if (flags) *flags = h->extra.flags;
+    if (baseline) *baseline = h->extra.base_host.empty() ? nullptr : h->extra.base_host.data();
+    if (H) *H = h->extra.H;
+    if (W) *W = h->extra.W;
     API_END
 }
 
 int p3d_last_eval_extra(p3d_handle* h, double* out, int64_t cap) {
     API_BEGIN
     if (!h || !out) throw P3dError("null argument");
-    if (!h->extra_flags) throw P3dError("last_eval_extra: the option is off (p3d_set_eval_extra)");
-    if (h->extra_state == p3d_handle::EXTRA_SHAPE)
-        throw P3dError("last_eval_extra: the baseline is " + std::to_string(h->extra_H) + " x " + std::to_string(h->extra_W) +
-                       ", the last evaluation scored " + std::to_string(h->extra_eval_H) + " x " + std::to_string(h->extra_eval_W) + " maps");
-    if (h->extra_state != p3d_handle::EXTRA_HAVE) throw P3dError("last_eval_extra: no evaluation has run since the option was set");
-    if (cap < (int64_t)h->extra_last.size())
-        throw P3dError("last_eval_extra: room for " + std::to_string(cap) + " doubles, " + std::to_string(h->extra_last.size()) + " needed");
-    std::copy(h->extra_last.begin(), h->extra_last.end(), out);
+    if (!h->extra.flags) throw P3dError("last_eval_extra: the option is off (p3d_set_eval_extra)");
+    if (h->extra.state == p3d_handle::EXTRA_SHAPE)
+        throw P3dError("last_eval_extra: the baseline is " + std::to_string(h->extra.H) + " x " + std::to_string(h->extra.W) +
+                       ", the last evaluation scored " + std::to_string(h->extra.eval_H) + " x " + std::to_string(h->extra.eval_W) + " maps");
+    if (h->extra.state != p3d_handle::EXTRA_HAVE) throw P3dError("last_eval_extra: no evaluation has run since the option was set");
+    if (cap < (int64_t)h->extra.last.size())
+        throw P3dError("last_eval_extra: room for " + std::to_string(cap) + " doubles, " + std::to_string(h->extra.last.size()) + " needed");
+    std::copy(h->extra.last.begin(), h->extra.last.end(), out);
     API_END
 }
 
@@ -666,7 +655,7 @@ void metric_extra(int device, int flags, const float* map1, const float* map2, c
     metric_args(device, map1, map2, n_maps, n_pix, out);
     if (n_maps > 65535) throw P3dError("at most 65535 maps per call");
     const bool ig = flags == P3D_EVAL_INFO_GAIN;
-    if (ig) p3d_handle::eval_extra_check(flags, baseline, 1, n_pix);
+    if (ig) p3d_handle::Extra::check(flags, baseline, 1, n_pix);
     const size_t n = (size_t)n_maps * n_pix;
     DevArr<float> d1(n, map1), d2(n, map2), base(ig ? n_pix : 1, ig ? baseline : nullptr);
     Stats3 s1(n_maps, n_pix), s2(n_maps, n_pix), sb(1, n_pix);
@@ -920,8 +909,8 @@ int p3d_set_postprocess(p3d_handle* h, const p3d_postprocess* cfg) {
 int p3d_get_postprocess(p3d_handle* h, p3d_postprocess* cfg, int* on) {
     API_BEGIN
     if (!h) throw P3dError("null handle");
-    if (cfg) *cfg = h->post_cfg;
-    if (on) *on = h->post_on ? 1 : 0;
+    if (cfg) *cfg = h->post.cfg;
+    if (on) *on = h->post.on ? 1 : 0;
     API_END
 }
 
@@ -976,8 +965,8 @@ struct PostHook {
 void postprocess_maps(const PostHook& q) {
     const int n = q.n, H = q.H, W = q.W;
     Stages st(q.cfg, q.match, nullptr, q.mode, q.a, H, W);
-    p3d_handle::prior_stage_check(q.mode, q.a);
-    if (st.prior.on()) p3d_handle::prior_map_check(q.prior, H, W);      // (the prior of the hook has the stage's size)
+    p3d_handle::PriorMap::stage_check(q.mode, q.a);
+    if (st.prior.on()) p3d_handle::PriorMap::check(q.prior, H, W);      // (the prior of the hook has the stage's size)
     if (st.match.mode == P3D_MATCH_DENSITY) throw P3dError("hist_match: P3D_MATCH_DENSITY runs in evaluation only; supplied maps take P3D_MATCH_TABLE");
     metric_args(q.device, q.maps, q.maps, 1, 1, q.maps);
     if (n < 1 || q.h < 1 || q.w < 1 || q.elem_stride < 1 || H < 1 || W < 1) throw P3dError("postprocess_maps: empty map");
@@ -1019,7 +1008,7 @@ struct HistBufs {
     }
 };
 void hist_shape(const char* what, const void* maps, const void* out, int n, int H, int W, int nbins) {
-    p3d_handle::match_bins(what, nbins);
+    p3d_handle::MatchCfg::bins(what, nbins);
     if (!maps || !out) throw P3dError(std::string(what) + ": null argument");
     if (n < 1 || n > 65535 || H < 1 || W < 1) throw P3dError(std::string(what) + ": 1 .. 65535 maps of at least one pixel");
     if ((long long)H * W > INT32_MAX) throw P3dError(std::string(what) + ": H * W exceeds the kernels' int32 in-map offsets");
@@ -1060,7 +1049,7 @@ int p3d_set_hist_match(p3d_handle* h, const p3d_hist_match* cfg) {
 int p3d_get_hist_match(p3d_handle* h, p3d_hist_match* cfg) {
     API_BEGIN
     if (!h || !cfg) throw P3dError("null argument");
-    const p3d_handle::MatchCfg& m = h->match_cfg;
+    const p3d_handle::MatchCfg& m = h->match;
     cfg->mode = m.mode; cfg->nbins = m.on() ? m.nb : 0; cfg->nt = (int)m.cdf.size();
     cfg->cdf = m.cdf.empty() ? nullptr : m.cdf.data();
     cfg->centres = m.centres.empty() ? nullptr : m.centres.data();
@@ -1091,7 +1080,7 @@ int p3d_match_hist(int device, const float* maps, int n, int H, int W, int nbins
     API_BEGIN
     hist_shape("match_hist", maps, out, n, H, W, nbins);
     if (n_tables != 1 && n_tables != n) throw P3dError("match_hist: one table, or one per map");
-    p3d_handle::match_table("match_hist", cdf_t, centre_t, nt, n_tables);
+    p3d_handle::MatchCfg::table("match_hist", cdf_t, centre_t, nt, n_tables);
     metric_args(device, maps, maps, 1, 1, out);
     const long long N = (long long)H * W;
     DevArr<float> src((size_t)n * N, maps), dst((size_t)n * N);
@@ -1147,23 +1136,22 @@ Stages prior_plan(float sigma, int radius, int H, int W) {
     return st;
 }
 void prior_finish(p3d_handle* h, float sigma, int radius, float* out) {
-    h->prior_need_open("prior_finish");
-    const int H = h->prior_acc_H, W = h->prior_acc_W;
+    h->prior_acc.need_open("prior_finish");
+    const int H = h->prior_acc.H, W = h->prior_acc.W;
     const Stages plan = prior_plan(sigma, radius, H, W);
-    if (h->prior_n_maps < 1) throw P3dError("prior_finish: the accumulator holds no maps");
+    if (h->prior_acc.n_maps < 1) throw P3dError("prior_finish: the accumulator holds no maps");
     if (h->prior_underflowed()) throw P3dError("prior_finish: a subtraction took a count below zero (maps were taken out that were never added); open the accumulator again");
     const hipStream_t s = h->stream;
-    DevArr<float> map((size_t)H * W);          // the handle's from prior_map_take on
+    DevArr<float> map((size_t)H * W);          // the handle's from prior.take on
     StageTimer tm(true, 2);
     tm.mark(0, s);
-    const float mx = prior_finish_launches(s, h->prior_count, H, W, plan, map.p);
+    const float mx = prior_finish_launches(s, h->prior_acc.count, H, W, plan, map.p);
     tm.mark(1, s);
     HIPCHECK(hipStreamSynchronize(s));
     if (!(mx > 0.f)) throw P3dError("prior_finish: every count is zero");
-    h->prior_ms[1] = tm.ms(0);
+    h->prior.ms[1] = tm.ms(0);
     if (out) HIPCHECK(copy_now(out, map.p, (size_t)H * W * sizeof(float), hipMemcpyDeviceToHost, s));
-    h->prior_map_take(map.p, H, W);
-    map.p = nullptr;
+    h->prior.take(std::move(map), H, W);
 }
 }  // namespace
 extern "C" {
@@ -1180,18 +1168,18 @@ int p3d_prior_close(p3d_handle* h) {
     API_BEGIN
     if (!h) throw P3dError("null handle");
     HIPCHECK(hipSetDevice(h->cfg.device));
-    h->prior_close();
+    h->prior_acc = p3d_handle::PriorAcc();
     API_END
 }
 
 int p3d_prior_info(p3d_handle* h, int* H, int* W, int* kind, int64_t* n_maps) {
     API_BEGIN
     if (!h) throw P3dError("null handle");
-    h->prior_need_open("prior_info");
-    if (H) *H = h->prior_acc_H;
-    if (W) *W = h->prior_acc_W;
-    if (kind) *kind = h->prior_kind;
-    if (n_maps) *n_maps = h->prior_n_maps;
+    h->prior_acc.need_open("prior_info");
+    if (H) *H = h->prior_acc.H;
+    if (W) *W = h->prior_acc.W;
+    if (kind) *kind = h->prior_acc.kind;
+    if (n_maps) *n_maps = h->prior_acc.n_maps;
     API_END
 }
 
@@ -1207,10 +1195,10 @@ int p3d_prior_counts(p3d_handle* h, uint32_t* out, int64_t* n_maps) {
     API_BEGIN
     if (!h || !out) throw P3dError("null argument");
     HIPCHECK(hipSetDevice(h->cfg.device));
-    h->prior_need_open("prior_counts");
+    h->prior_acc.need_open("prior_counts");
     if (h->prior_underflowed()) throw P3dError("prior_counts: a subtraction took a count below zero (maps were taken out that were never added); open the accumulator again");
-    HIPCHECK(copy_now(out, h->prior_count, (size_t)h->prior_acc_H * h->prior_acc_W * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    if (n_maps) *n_maps = h->prior_n_maps;
+    HIPCHECK(copy_now(out, h->prior_acc.count, (size_t)h->prior_acc.H * h->prior_acc.W * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (n_maps) *n_maps = h->prior_acc.n_maps;
     API_END
 }
 
@@ -1225,7 +1213,7 @@ int p3d_prior_finish(p3d_handle* h, float sigma, int radius, float* out) {
 int p3d_prior_last_ms(p3d_handle* h, double ms[2]) {
     API_BEGIN
     if (!h || !ms) throw P3dError("null argument");
-    ms[0] = h->prior_ms[0]; ms[1] = h->prior_ms[1];
+    ms[0] = h->prior.ms[0]; ms[1] = h->prior.ms[1];
     API_END
 }
 
@@ -1240,14 +1228,14 @@ int p3d_set_prior_map(p3d_handle* h, const float* map, int H, int W) {
 int p3d_get_prior_map(p3d_handle* h, float* out, int64_t cap, int* H, int* W) {
     API_BEGIN
     if (!h) throw P3dError("null handle");
-    if (H) *H = h->prior_H;
-    if (W) *W = h->prior_W;
+    if (H) *H = h->prior.H;
+    if (W) *W = h->prior.W;
     if (out) {
-        if (!h->prior_map) throw P3dError("get_prior_map: the handle has no prior (p3d_prior_finish or p3d_set_prior_map)");
-        const int64_t n = (int64_t)h->prior_H * h->prior_W;
+        if (!h->prior.map) throw P3dError("get_prior_map: the handle has no prior (p3d_prior_finish or p3d_set_prior_map)");
+        const int64_t n = (int64_t)h->prior.H * h->prior.W;
         if (cap < n) throw P3dError("get_prior_map: room for " + std::to_string(cap) + " floats, " + std::to_string(n) + " needed");
         HIPCHECK(hipSetDevice(h->cfg.device));
-        HIPCHECK(copy_now(out, h->prior_map, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIPCHECK(copy_now(out, h->prior.map, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     }
     API_END
 }
@@ -1262,8 +1250,8 @@ int p3d_set_prior_stage(p3d_handle* h, int mode, float a) {
 int p3d_get_prior_stage(p3d_handle* h, int* mode, float* a) {
     API_BEGIN
     if (!h) throw P3dError("null handle");
-    if (mode) *mode = h->prior_mode;
-    if (a) *a = h->prior_a;
+    if (mode) *mode = h->prior.mode;
+    if (a) *a = h->prior.a;
     API_END
 }
 
@@ -1316,7 +1304,7 @@ int p3d_debug_prior_apply(int device, int mode, float a, const float* maps, int 
     API_BEGIN
     metric_args(device, maps, prior, 1, 1, out);
     if (n < 1 || n > 65535 || H < 1 || W < 1 || (long long)H * W > INT32_MAX / 2) throw P3dError("prior_apply: 1 .. 65535 maps of H x W floats, 1 <= H * W <= 2^30");
-    p3d_handle::prior_stage_check(mode, a);
+    p3d_handle::PriorMap::stage_check(mode, a);
     if (mode == P3D_PRIOR_OFF) throw P3dError("prior_apply: the mode is P3D_PRIOR_MUL or P3D_PRIOR_MIX");
     if (offset < 0 || offset > 15) throw P3dError("prior_apply: offset in [0, 15]");
     const size_t N = (size_t)H * W;
@@ -1343,19 +1331,19 @@ int p3d_fixpool_close(p3d_handle* h) {
     API_BEGIN
     if (!h) throw P3dError("null handle");
     HIPCHECK(hipSetDevice(h->cfg.device));
-    h->fixpool_close();
+    h->fixpool = p3d_handle::FixPool();
     API_END
 }
 
 int p3d_fixpool_info(p3d_handle* h, int* H, int* W, int64_t* capacity, int64_t* words_per_map, int64_t* n_filled) {
     API_BEGIN
     if (!h) throw P3dError("null handle");
-    h->fixpool_need_open("fixpool_info");
-    if (H) *H = h->fp_H;
-    if (W) *W = h->fp_W;
-    if (capacity) *capacity = h->fp_cap;
-    if (words_per_map) *words_per_map = h->fp_nw;
-    if (n_filled) *n_filled = (int64_t)std::count(h->fp_filled.begin(), h->fp_filled.end(), (char)1);
+    h->fixpool.need_open("fixpool_info");
+    if (H) *H = h->fixpool.H;
+    if (W) *W = h->fixpool.W;
+    if (capacity) *capacity = h->fixpool.cap;
+    if (words_per_map) *words_per_map = h->fixpool.nw;
+    if (n_filled) *n_filled = (int64_t)std::count(h->fixpool.filled.begin(), h->fixpool.filled.end(), (char)1);
     API_END
 }
 
@@ -1371,19 +1359,19 @@ int p3d_fixpool_get(p3d_handle* h, int64_t first, int64_t n, uint64_t* words) {
     API_BEGIN
     if (!h || !words) throw P3dError("null argument");
     HIPCHECK(hipSetDevice(h->cfg.device));
-    h->fixpool_need_open("fixpool_get");
-    if (n < 1 || first < 0 || first > h->fp_cap - n)
-        throw P3dError("fixpool_get: slots " + std::to_string(first) + " .. " + std::to_string(first + n - 1) + " are not inside [0, " + std::to_string(h->fp_cap) + ")");
+    h->fixpool.need_open("fixpool_get");
+    if (n < 1 || first < 0 || first > h->fixpool.cap - n)
+        throw P3dError("fixpool_get: slots " + std::to_string(first) + " .. " + std::to_string(first + n - 1) + " are not inside [0, " + std::to_string(h->fixpool.cap) + ")");
     for (int64_t i = first; i < first + n; ++i)
-        if (!h->fp_filled[(size_t)i]) throw P3dError("fixpool_get: slot " + std::to_string(i) + " was never filled (p3d_fixpool_put)");
-    HIPCHECK(copy_now(words, h->fp_words + first * h->fp_nw, (size_t)n * h->fp_nw * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+        if (!h->fixpool.filled[(size_t)i]) throw P3dError("fixpool_get: slot " + std::to_string(i) + " was never filled (p3d_fixpool_put)");
+    HIPCHECK(copy_now(words, h->fixpool.words + first * h->fixpool.nw, (size_t)n * h->fixpool.nw * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
     API_END
 }
 
 int p3d_fixpool_last_ms(p3d_handle* h, double ms[4]) {
     API_BEGIN
     if (!h || !ms) throw P3dError("null argument");
-    ms[0] = h->fp_pack_ms; ms[1] = h->fp_union_ms; ms[2] = h->fp_score_ms[0]; ms[3] = h->fp_score_ms[1];
+    ms[0] = h->fixpool_ms[0]; ms[1] = h->fixpool_ms[1]; ms[2] = h->fixpool_ms[2]; ms[3] = h->fixpool_ms[3];
     API_END
 }
 
@@ -1405,10 +1393,10 @@ int p3d_eval_shuffled_draws(p3d_handle* h, const int* ranks, const int* n_rows, 
 int p3d_last_eval_shuffled(p3d_handle* h, double* per_rep, int64_t cap) {
     API_BEGIN
     if (!h || !per_rep) throw P3dError("null argument");
-    if (!h->sh_have) throw P3dError("last_eval_shuffled: no evaluation has run armed (p3d_eval_shuffled_draws)");
-    if (cap < (int64_t)h->sh_last.size())
-        throw P3dError("last_eval_shuffled: room for " + std::to_string(cap) + " doubles, " + std::to_string(h->sh_last.size()) + " needed");
-    std::copy(h->sh_last.begin(), h->sh_last.end(), per_rep);
+    if (!h->fixpool.have) throw P3dError("last_eval_shuffled: no evaluation has run armed (p3d_eval_shuffled_draws)");
+    if (cap < (int64_t)h->fixpool.last.size())
+        throw P3dError("last_eval_shuffled: room for " + std::to_string(cap) + " doubles, " + std::to_string(h->fixpool.last.size()) + " needed");
+    std::copy(h->fixpool.last.begin(), h->fixpool.last.end(), per_rep);
     API_END
 }
 
@@ -1496,7 +1484,7 @@ int p3d_debug_fix_select(int device, const uint64_t* pool, int capacity, int H, 
     std::vector<uint32_t> n_other((size_t)B);
     std::vector<uint64_t> uni((size_t)B * u.nw);
     u.back(uni.data(), nullptr, n_other.data(), "fix_select");
-    p3d_handle::shuffled_check_draws("fix_select", ranks, n_rows, n_other.data(), B, n_rep, 1.0);
+    p3d_handle::FixPool::check_draws("fix_select", ranks, n_rows, n_other.data(), B, n_rep, 1.0);
     std::vector<int> meta((size_t)B * 3, 0);
     long long at = 0;
     int max_rows = 0;
@@ -1549,16 +1537,16 @@ void eval_hook(const EvalHook& q) {
         if (q.capacity < 1 || q.capacity > 65535) throw P3dError("eval_shuffled: 1 .. 65535 pool maps");
         fix_ids_check("eval_shuffled", q.ids, q.capacity, n_maps, q.M);
     }
-    p3d_handle::prior_stage_check(q.mode, q.a);
+    p3d_handle::PriorMap::stage_check(q.mode, q.a);
     const bool from_prior = q.prior_as_baseline && (q.flags & P3D_EVAL_INFO_GAIN) && !q.baseline;
-    if (q.mode != P3D_PRIOR_OFF || from_prior || q.prior) p3d_handle::prior_map_check(q.prior, H, W);
-    if (!from_prior) p3d_handle::eval_extra_check(q.flags, q.baseline, H, W);           // (the baseline of the hook has the evaluation's size)
+    if (q.mode != P3D_PRIOR_OFF || from_prior || q.prior) p3d_handle::PriorMap::check(q.prior, H, W);
+    if (!from_prior) p3d_handle::Extra::check(q.flags, q.baseline, H, W);           // (the baseline of the hook has the evaluation's size)
     else if (q.flags & ~(P3D_EVAL_KLDIV | P3D_EVAL_INFO_GAIN)) throw P3dError("eval_extra: unknown flags " + std::to_string(q.flags));
     const long long per_map = (long long)q.h * q.w * q.elem_stride;
     const bool ig = (q.flags & P3D_EVAL_INFO_GAIN) != 0;
     DevArr<float> src((size_t)n_maps * per_map, q.maps), base(ig ? (size_t)H * W : 1), dprior(q.prior ? (size_t)H * W : 1, q.prior);
     DevArr<double> bstat(3);
-    if (ig) p3d_handle::eval_extra_upload(from_prior ? dprior.p : q.baseline, H, W, base.p, bstat.p, nullptr,
+    if (ig) p3d_handle::Extra::upload(from_prior ? dprior.p : q.baseline, H, W, base.p, bstat.p, nullptr,
                                           from_prior ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice);
     const EvalExtra x{q.flags, ig ? base.p : nullptr, ig ? bstat.p : nullptr, H, W, q.extra};
     st.prior.map = dprior.p;
@@ -1679,10 +1667,10 @@ int p3d_video_close(p3d_handle* h) {
 int p3d_video_info(p3d_handle* h, int* frames, int* mode, int* last_start) {
     API_BEGIN
     if (!h) throw P3dError("null handle");
-    h->video_need_open("video_info");
-    if (frames) *frames = h->vid_F;
-    if (mode) *mode = h->vid_mode;
-    if (last_start) *last_start = h->vid_last;
+    h->video.need_open("video_info");
+    if (frames) *frames = h->video.F;
+    if (mode) *mode = h->video.mode;
+    if (last_start) *last_start = h->video.last;
     API_END
 }
 
@@ -1721,11 +1709,11 @@ int p3d_video_predict_shots(p3d_handle* h, const int* starts, int n_windows) {
 int p3d_video_last_ms(p3d_handle* h, double ms[2]) {
     API_BEGIN
     if (!h || !ms) throw P3dError("null argument");
-    if (!h->vid_is_open || !h->vid_timed) throw P3dError("video_last_ms: no p3d_video_predict has run on the open video");
+    if (!h->video.is_open || !h->video.timed) throw P3dError("video_last_ms: no p3d_video_predict has run on the open video");
     HIPCHECK(hipSetDevice(h->cfg.device));
     float g = 0.f, sc = 0.f;
-    HIPCHECK(hipEventElapsedTime(&g, h->ev_vid[0], h->ev_vid[1]));
-    HIPCHECK(hipEventElapsedTime(&sc, h->ev_vid[2], h->ev_vid[3]));
+    HIPCHECK(hipEventElapsedTime(&g, h->video.ev[0], h->video.ev[1]));
+    HIPCHECK(hipEventElapsedTime(&sc, h->video.ev[2], h->video.ev[3]));
     ms[0] = (double)g; ms[1] = (double)sc;
     API_END
 }
@@ -1738,16 +1726,16 @@ namespace {
 struct VideoSource {
     p3d_handle* h; const char* who; int first, n; bool temporal;
     VideoSource(p3d_handle* h_, const char* who_, int first_, int n_, bool predicted = true, int most = INT32_MAX)
-        : h(h_), who(who_), first(first_), n(n_), temporal(h_->temporal_cfg.on()) {
-        h->video_need_open(who);
-        h->video_range(who, first, n);
+        : h(h_), who(who_), first(first_), n(n_), temporal(h_->temporal.cfg.on()) {
+        h->video.need_open(who);
+        h->video.range(who, first, n);
         if (n > most) throw P3dError(std::string(who) + ": 1 .. " + std::to_string(most) + " maps");
         if (temporal) h->video_temporal_check(who, first, n);
-        if (predicted) h->video_need_predicted(who, first, n);
+        if (predicted) h->video.need_predicted(who, first, n);
     }
     // floats of scratch the maps need: the filtered maps under either mode, the divided sums under MEAN
     size_t extra() const {
-        return temporal || h->vid_mode == VIDEO_MEAN ? (size_t)n * (size_t)h->vid_hw() + (temporal ? h->video_temporal_table(n) : 0) : 0;
+        return temporal || h->video.mode == VIDEO_MEAN ? (size_t)n * (size_t)h->vid_hw() + (temporal ? h->video_temporal_table(n) : 0) : 0;
     }
     // queues whatever makes the maps readable; -> the maps [n][hw]
     const float* queue(hipStream_t s, float* scratch) const {
@@ -1768,7 +1756,7 @@ int p3d_video_get_maps(p3d_handle* h, int first, int n, float* maps, int32_t* co
     unsigned* counters = nullptr;
     if (src.extra()) HIPCHECK(p3d_stream_scratch(s, src.extra(), 0, &slab, &counters));
     HIPCHECK(copy_now(maps, src.queue(s, slab), (size_t)n * (size_t)h->vid_hw() * 4, hipMemcpyDeviceToHost, s));
-    if (counts) memcpy(counts, h->vid_count.data() + first, (size_t)n * sizeof(int32_t));
+    if (counts) memcpy(counts, h->video.count.data() + first, (size_t)n * sizeof(int32_t));
     API_END
 }
 
@@ -1804,15 +1792,15 @@ void stage_on_host_bytes(ByteStage& stage, const unsigned char* sal) {
 }
 // Frames first .. first + n - 1 of the source the open video keeps, for a call that `verb` ("renders", "reframes") H x W frames
 const unsigned char* kept_source(const p3d_handle* h, const char* who, int first, int n, int H, int W, const char* verb) {
-    if (H != h->vid_H0 || W != h->vid_W0)
-        throw P3dError(std::string(who) + ": the kept source is " + std::to_string(h->vid_H0) + " x " + std::to_string(h->vid_W0) + ", the call " + verb + " " +
+    if (H != h->video.H0 || W != h->video.W0)
+        throw P3dError(std::string(who) + ": the kept source is " + std::to_string(h->video.H0) + " x " + std::to_string(h->video.W0) + ", the call " + verb + " " +
                        std::to_string(H) + " x " + std::to_string(W));
     for (int f = first; f < first + n; ++f)
-        if (!h->vid_has_src[(size_t)f]) throw P3dError(std::string(who) + ": frame " + std::to_string(f) + " has no source (it was not put with p3d_video_put_frames_u8)");
-    return h->vid_src + (size_t)first * (size_t)H * (size_t)W * 3;
+        if (!h->video.has_src[(size_t)f]) throw P3dError(std::string(who) + ": frame " + std::to_string(f) + " has no source (it was not put with p3d_video_put_frames_u8)");
+    return h->video.source + (size_t)first * (size_t)H * (size_t)W * 3;
 }
 void need_kept_source(const p3d_handle* h, const char* who) {
-    if (!h->vid_src) throw P3dError(std::string(who) + ": no frames are given and the video keeps no source (p3d_video_keep_source before the first p3d_video_put_frames_u8)");
+    if (!h->video.source) throw P3dError(std::string(who) + ": no frames are given and the video keeps no source (p3d_video_keep_source before the first p3d_video_put_frames_u8)");
 }
 // p3d_video_score, _score_auc, _render and _reframe behind the checks of their arguments: at most 65535 of the video's frames
 // through the maps' chain, the stage behind its bytes.  make builds the stage once the source has passed, so that what the stage
@@ -2012,18 +2000,18 @@ int p3d_debug_render_plan(int H, int W, int n, int contour_thickness, int offset
 int p3d_video_keep_source(p3d_handle* h, int on) {
     API_BEGIN
     if (!h) throw P3dError("null handle");
-    h->video_keep_source(on);
+    h->video.keep_source(on);
     API_END
 }
 
 int p3d_video_source_info(p3d_handle* h, int* on, int* H0, int* W0, int64_t* bytes) {
     API_BEGIN
     if (!h) throw P3dError("null handle");
-    h->video_need_open("video_source_info");
-    if (on) *on = h->vid_keep ? 1 : 0;
-    if (H0) *H0 = h->vid_H0;
-    if (W0) *W0 = h->vid_W0;
-    if (bytes) *bytes = (int64_t)h->vid_src_bytes;
+    h->video.need_open("video_source_info");
+    if (on) *on = h->video.keep ? 1 : 0;
+    if (H0) *H0 = h->video.H0;
+    if (W0) *W0 = h->video.W0;
+    if (bytes) *bytes = (int64_t)h->video.source.n;
     API_END
 }
 
@@ -2032,7 +2020,7 @@ int p3d_video_render(p3d_handle* h, int first, int n, float scale, int H, int W,
     API_BEGIN
     const char* who = "video_render";
     if (!h) throw P3dError("null argument");
-    h->video_need_open(who);
+    h->video.need_open(who);
     // before the shape: a call that leaves the size to the source has none to name when there is no source
     if (!frames) need_kept_source(h, who);
     render_check(who, cfg, std::max(1, std::min(n, 65535)), H, W, out);
@@ -2170,7 +2158,7 @@ int p3d_video_reframe(p3d_handle* h, int first, int n, float scale, int H, int W
     API_BEGIN
     const char* who = "video_reframe";
     if (!h) throw P3dError("null argument");
-    h->video_need_open(who);
+    h->video.need_open(who);
     if (frames && !out) throw P3dError(std::string(who) + ": frames are given but no out to receive the windows");
     // before the shape: a call that leaves the size to the source has none to name when there is no source
     if (out && !frames) need_kept_source(h, who);
@@ -2181,9 +2169,9 @@ int p3d_video_reframe(p3d_handle* h, int first, int n, float scale, int H, int W
     std::vector<int32_t> shots;                            // the installed table in frames of the call: its shots cut the track's filter
     video_stage_run(h, who, first, n, scale, maps_out, stage_ms, 3, [&]() -> ByteStage& {
         if (out && !frames) r.frames_dev = kept_source(h, who, first, n, H, W, "reframes");
-        if (!h->vid_shots.empty()) {
+        if (!h->video.shots.empty()) {
             shots.push_back(0);
-            for (int32_t st : h->vid_shots)
+            for (int32_t st : h->video.shots)
                 if (st > first && st < first + n) shots.push_back(st - first);
             r.starts = shots.data(); r.n_shots = (int)shots.size();
         }
@@ -2266,17 +2254,17 @@ ScoreStage::ScoreStage(const ScoreRequest& r_)
     }
     if (r.shuffled) {
         const p3d_handle* h = r.pool;
-        h->fixpool_need_open(r.who);
-        if (!h->vu.begun) throw P3dError(std::string(r.who) + ": no union is held (p3d_video_shuffled_begin)");
-        if (h->fp_H != r.H || h->fp_W != r.W)
-            throw P3dError(std::string(r.who) + ": the fixation pool holds " + std::to_string(h->fp_H) + " x " + std::to_string(h->fp_W) + " maps, the call scores " +
+        h->fixpool.need_open(r.who);
+        if (!h->fixpool.vu.begun) throw P3dError(std::string(r.who) + ": no union is held (p3d_video_shuffled_begin)");
+        if (h->fixpool.H != r.H || h->fixpool.W != r.W)
+            throw P3dError(std::string(r.who) + ": the fixation pool holds " + std::to_string(h->fixpool.H) + " x " + std::to_string(h->fixpool.W) + " maps, the call scores " +
                            std::to_string(r.H) + " x " + std::to_string(r.W));
-        if (h->vu.n != r.n) throw P3dError(std::string(r.who) + ": the union was taken for " + std::to_string(h->vu.n) + " frames, the call scores " + std::to_string(r.n));
+        if (h->fixpool.vu.n != r.n) throw P3dError(std::string(r.who) + ": the union was taken for " + std::to_string(h->fixpool.vu.n) + " frames, the call scores " + std::to_string(r.n));
         for (int b = 0; b < r.n; ++b)
-            if (r.n_rows[b] != (int)std::min<long long>(nf[(size_t)b], h->vu.n_other[(size_t)b]))
+            if (r.n_rows[b] != (int)std::min<long long>(nf[(size_t)b], h->fixpool.vu.n_other[(size_t)b]))
                 throw P3dError(std::string(r.who) + ": frame " + std::to_string(b) + ": n_rows = " + std::to_string(r.n_rows[b]) + ", but min(n_fix, n_other) = min(" +
-                               std::to_string(nf[(size_t)b]) + ", " + std::to_string(h->vu.n_other[(size_t)b]) + ")");
-        p3d_handle::shuffled_check_draws(r.who, r.ranks, r.n_rows, h->vu.n_other.data(), r.n, r.n_rep, r.step);
+                               std::to_string(nf[(size_t)b]) + ", " + std::to_string(h->fixpool.vu.n_other[(size_t)b]) + ")");
+        p3d_handle::FixPool::check_draws(r.who, r.ranks, r.n_rows, h->fixpool.vu.n_other.data(), r.n, r.n_rep, r.step);
         metaS = sweep_meta(r.who, r.n_rows, r.n, r.n_rep, totS);
         meta3.assign((size_t)r.n * 3, 0);
         for (int b = 0; b < r.n; ++b) { meta3[(size_t)b * 3 + 2] = (int)metaS[(size_t)b * 2 + 1]; max_rows = std::max(max_rows, r.n_rows[b]); }
@@ -2328,8 +2316,8 @@ void ScoreStage::sweep_rest(hipStream_t s) {
         const p3d_handle* h = r.pool;
         if (totS) {
             FixSelectArgs e;
-            e.uni = h->vu.uni; e.prefix = h->vu.prefix; e.bsum = h->vu.bsum; e.n_other = h->vu.n_other_dev; e.nw = h->fp_nw; e.B = r.n;
-            e.nsb = p3d_fix_scan_blocks(h->fp_nw); e.n_rep = r.n_rep; e.max_rows = max_rows; e.meta = dmeta3; e.n_rows = drows; e.ranks = dranks; e.out = dsel;
+            e.uni = h->fixpool.vu.uni; e.prefix = h->fixpool.vu.prefix; e.bsum = h->fixpool.vu.bsum; e.n_other = h->fixpool.vu.n_other_dev; e.nw = h->fixpool.nw; e.B = r.n;
+            e.nsb = p3d_fix_scan_blocks(h->fixpool.nw); e.n_rep = r.n_rep; e.max_rows = max_rows; e.meta = dmeta3; e.n_rows = drows; e.ranks = dranks; e.out = dsel;
             HIPCHECK(p3d_fix_select_launch(e, s));
         }
         ScoreSweepArgs qs = q;
@@ -2525,7 +2513,7 @@ void video_scatter_hook(int device, int mode, const float* pred, int B, int T, i
                         const int* starts, int n_windows, int F, int last_start, float* store, int32_t* count, int offset) {
     if (!pred || !starts || !store || !count) throw P3dError("null argument");
     if (hw < 1 || ld < 1) throw P3dError("video_scatter: bad shape");
-    const p3d_handle::VideoPlan p = p3d_handle::video_plan(mode, F, T, B, last_start, count, nullptr, starts, n_windows, shots, n_shots);
+    const p3d_handle::Video::Plan p = p3d_handle::Video::plan(mode, F, T, B, last_start, count, nullptr, starts, n_windows, shots, n_shots);
     const int64_t np = (int64_t)B * T * hw * ld, ns = (int64_t)F * hw;
     if (np > (int64_t)1 << 31 || ns > (int64_t)1 << 31) throw P3dError("video_scatter: the hook takes up to 2^31 floats");
     video_hook_device(device, offset);
@@ -2577,7 +2565,7 @@ int p3d_debug_video_gather_slots(int device, const float* store, int F, int T, i
     if (T < 1 || F < T || frame_elems < 1 || B < 1) throw P3dError("video_gather_slots: bad shape");
     if ((int64_t)F * frame_elems > (int64_t)1 << 31 || (int64_t)B * T * frame_elems > (int64_t)1 << 31) throw P3dError("video_gather_slots: the hook takes up to 2^31 floats");
     const std::vector<int32_t> none((size_t)F, 0);      // the windows as p3d_video_predict_shots validates them, every frame put
-    const p3d_handle::VideoPlan p = p3d_handle::video_plan(VIDEO_NEWEST, F, T, B, -1, none.data(), nullptr, starts, n_windows, shot_starts, n_shots);
+    const p3d_handle::Video::Plan p = p3d_handle::Video::plan(VIDEO_NEWEST, F, T, B, -1, none.data(), nullptr, starts, n_windows, shot_starts, n_shots);
     video_hook_device(device, offset);
     const int64_t ns = (int64_t)F * frame_elems, nx = (int64_t)B * T * frame_elems;
     Guarded<float> sb((size_t)ns, 8, (size_t)offset, store), xb((size_t)nx, 8, (size_t)offset, nullptr);
@@ -2596,7 +2584,7 @@ int p3d_debug_video_plan_shots(int mode, int F, int T, int B, int last_start, co
                                const int* starts, int n_windows, int32_t* count_out, int* slots_out, int* live_out) {
     API_BEGIN
     if (!shot_starts || !count_out || !slots_out || !live_out) throw P3dError("null argument");
-    const p3d_handle::VideoPlan p = p3d_handle::video_plan(mode, F, T, B, last_start, count_in, nullptr, starts, n_windows, shot_starts, n_shots);
+    const p3d_handle::Video::Plan p = p3d_handle::Video::plan(mode, F, T, B, last_start, count_in, nullptr, starts, n_windows, shot_starts, n_shots);
     memcpy(count_out, p.count.data(), (size_t)F * sizeof(int32_t));
     std::copy(p.slots.begin(), p.slots.end(), slots_out);
     std::copy(p.live.begin(), p.live.end(), live_out);
@@ -2627,7 +2615,7 @@ int p3d_debug_video_plan(int mode, int F, int T, int B, int last_start, const in
                          int32_t* count_out) {
     API_BEGIN
     if (!count_out) throw P3dError("null argument");
-    const p3d_handle::VideoPlan p = p3d_handle::video_plan(mode, F, T, B, last_start, count_in, nullptr, starts, n_windows);
+    const p3d_handle::Video::Plan p = p3d_handle::Video::plan(mode, F, T, B, last_start, count_in, nullptr, starts, n_windows);
     memcpy(count_out, p.count.data(), (size_t)F * sizeof(int32_t));
     API_END
 }
@@ -2643,18 +2631,18 @@ int p3d_set_video_temporal(p3d_handle* h, const p3d_video_temporal* cfg) {
 int p3d_get_video_temporal(p3d_handle* h, p3d_video_temporal* cfg, int* on) {
     API_BEGIN
     if (!h) throw P3dError("null handle");
-    if (cfg) *cfg = h->temporal_cfg.set;
-    if (on) *on = h->temporal_cfg.on() ? 1 : 0;
+    if (cfg) *cfg = h->temporal.cfg.set;
+    if (on) *on = h->temporal.cfg.on() ? 1 : 0;
     API_END
 }
 
 int p3d_video_temporal_last_ms(p3d_handle* h, double* ms) {
     API_BEGIN
     if (!h || !ms) throw P3dError("null argument");
-    if (!h->temporal_timed) throw P3dError("video_temporal_last_ms: no read-out has run the temporal stage");
+    if (!h->temporal.timed) throw P3dError("video_temporal_last_ms: no read-out has run the temporal stage");
     HIPCHECK(hipSetDevice(h->cfg.device));
     float t = 0.f;
-    HIPCHECK(hipEventElapsedTime(&t, h->ev_temporal[0], h->ev_temporal[1]));
+    HIPCHECK(hipEventElapsedTime(&t, h->temporal.ev[0], h->temporal.ev[1]));
     *ms = (double)t;
     API_END
 }
@@ -2667,17 +2655,17 @@ void temporal_on_host(int device, int mode, const p3d_video_temporal* cfg, const
                       int first, int n, int offset, float* out) {
     if (!store || !out) throw P3dError("null argument");
     if (mode != VIDEO_NEWEST && mode != VIDEO_MEAN) throw P3dError("video_temporal: mode " + std::to_string(mode) + " is neither P3D_VIDEO_NEWEST (0) nor P3D_VIDEO_MEAN (1)");
-    const p3d_handle::TemporalCfg t = p3d_handle::temporal_parse(cfg);
+    const p3d_handle::TemporalCfg t = p3d_handle::TemporalCfg::parse(cfg);
     if (!t.on()) throw P3dError("video_temporal: the hook needs a kind (GAUSS or EMA)");
     if (F < 1 || hw < 1 || (int64_t)F * hw > (int64_t)1 << 31) throw P3dError("video_temporal: bad shape");
     std::vector<int32_t> ones;
     if (!count) { ones.assign((size_t)F, 1); count = ones.data(); }
-    p3d_handle::temporal_check("video_temporal", t, F, first, n, count);
+    p3d_handle::TemporalCfg::check("video_temporal", t, F, first, n, count);
     video_hook_device(device, offset);
     const int64_t ns = (int64_t)F * hw, no = (int64_t)n * hw;
     Guarded<float> sb((size_t)ns, 8, (size_t)offset, store), ob((size_t)no, 8, (size_t)offset, nullptr);
     Guarded<int32_t> cb((size_t)F, 8, 0, count);
-    const VideoTemporalArgs a = p3d_handle::temporal_args(t, sb.data(), mode == VIDEO_MEAN ? cb.data() : nullptr, ob.data(), F, hw, first, n);
+    const VideoTemporalArgs a = p3d_handle::TemporalCfg::args(t, sb.data(), mode == VIDEO_MEAN ? cb.data() : nullptr, ob.data(), F, hw, first, n);
     const std::string want = std::string(t.set.kind == P3D_TEMPORAL_GAUSS ? "video_temporal_gauss_kernel<" : "video_temporal_ema_kernel<") +
                              (mode == VIDEO_MEAN ? "1>" : "0>");
     if (std::string(p3d_video_temporal_desc(a).kernel) != want) throw P3dError("video_temporal: launch description names another kernel");
@@ -2710,14 +2698,14 @@ int p3d_debug_video_temporal_desc(int mode, const p3d_video_temporal* cfg, int F
     API_BEGIN
     if (!kernel || cap < 1 || !flops || !bytes) throw P3dError("null argument");
     if (mode != VIDEO_NEWEST && mode != VIDEO_MEAN) throw P3dError("video_temporal: mode " + std::to_string(mode) + " is neither P3D_VIDEO_NEWEST (0) nor P3D_VIDEO_MEAN (1)");
-    const p3d_handle::TemporalCfg t = p3d_handle::temporal_parse(cfg);
+    const p3d_handle::TemporalCfg t = p3d_handle::TemporalCfg::parse(cfg);
     if (!t.on()) throw P3dError("video_temporal: the hook needs a kind (GAUSS or EMA)");
     if (F < 1 || hw < 1) throw P3dError("video_temporal: bad shape");
     const std::vector<int32_t> ones((size_t)F, 1);
-    p3d_handle::temporal_check("video_temporal", t, F, first, n, ones.data());
+    p3d_handle::TemporalCfg::check("video_temporal", t, F, first, n, ones.data());
     // (the description reads no memory: the pointers only say which is there)
     const float* some = reinterpret_cast<const float*>(kernel);
-    const VideoTemporalArgs a = p3d_handle::temporal_args(t, some, mode == VIDEO_MEAN ? ones.data() : nullptr, nullptr, F, hw, first, n);
+    const VideoTemporalArgs a = p3d_handle::TemporalCfg::args(t, some, mode == VIDEO_MEAN ? ones.data() : nullptr, nullptr, F, hw, first, n);
     const LaunchDesc d = p3d_video_temporal_desc(a);
     snprintf(kernel, (size_t)cap, "%s", d.kernel);
     *flops = d.flops; *bytes = d.bytes;
@@ -2786,26 +2774,26 @@ int p3d_trainset_close(p3d_handle* h) {
 int p3d_trainset_info(p3d_handle* h, int* n_videos, int64_t* total_frames, int* frame_format, int* flags, int64_t* bytes) {
     API_BEGIN
     if (!h) throw P3dError("null handle");
-    h->trainset_need_open("trainset_info");
-    if (n_videos) *n_videos = (int)h->ts_frames.size();
-    if (total_frames) *total_frames = h->ts_total();
-    if (frame_format) *frame_format = h->ts_format;
-    if (flags) *flags = h->ts_flags;
-    if (bytes) *bytes = (int64_t)(h->ts_fr_bytes + h->ts_den_bytes + h->ts_fix_bytes);
+    h->trainset.need_open("trainset_info");
+    if (n_videos) *n_videos = (int)h->trainset.frames.size();
+    if (total_frames) *total_frames = h->trainset.total();
+    if (frame_format) *frame_format = h->trainset.format;
+    if (flags) *flags = h->trainset.flags;
+    if (bytes) *bytes = (int64_t)(h->trainset.fr.n + h->trainset.den.n + h->trainset.fix.n);
     API_END
 }
 
 int p3d_trainset_video_info(p3d_handle* h, int video, int* frames, int* put_frames, int* put_density, int* put_fixations) {
     API_BEGIN
     if (!h) throw P3dError("null handle");
-    h->trainset_need_open("trainset_video_info");
-    if (video < 0 || video >= (int)h->ts_frames.size())
-        throw P3dError("trainset_video_info: video " + std::to_string(video) + " is outside [0, " + std::to_string(h->ts_frames.size()) + ")");
-    const int F = h->ts_frames[(size_t)video];
+    h->trainset.need_open("trainset_video_info");
+    if (video < 0 || video >= (int)h->trainset.frames.size())
+        throw P3dError("trainset_video_info: video " + std::to_string(video) + " is outside [0, " + std::to_string(h->trainset.frames.size()) + ")");
+    const int F = h->trainset.frames[(size_t)video];
     int* out[3] = {put_frames, put_density, put_fixations};
     for (int t = 0; t < 3; ++t) {
         if (!out[t]) continue;
-        const unsigned char* p = h->ts_put[t].data() + h->ts_base[(size_t)video];
+        const unsigned char* p = h->trainset.put[t].data() + h->trainset.base[(size_t)video];
         *out[t] = (int)std::count(p, p + F, (unsigned char)1);
     }
     if (frames) *frames = F;
@@ -2883,7 +2871,7 @@ int p3d_trainset_get_staged(p3d_handle* h, float* x, float* y, unsigned char* fi
     API_BEGIN
     if (!h) throw P3dError("null handle");
     HIPCHECK(hipSetDevice(h->cfg.device));
-    h->trainset_need_open("trainset_get_staged");
+    h->trainset.need_open("trainset_get_staged");
     if (fix && !h->d_fix) throw P3dError("trainset_get_staged: no fixation maps were ever staged");
     const hipStream_t s = h->stream;
     if (x) HIPCHECK(hipMemcpyAsync(x, h->x_in->p, (size_t)h->x_in->rows() * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
@@ -2896,11 +2884,11 @@ int p3d_trainset_get_staged(p3d_handle* h, float* x, float* y, unsigned char* fi
 int p3d_trainset_last_ms(p3d_handle* h, double* ms) {
     API_BEGIN
     if (!h || !ms) throw P3dError("null argument");
-    h->trainset_need_open("trainset_last_ms");
-    if (!h->ts_timed) throw P3dError("trainset_last_ms: nothing was staged from the open training set");
+    h->trainset.need_open("trainset_last_ms");
+    if (!h->trainset.timed) throw P3dError("trainset_last_ms: nothing was staged from the open training set");
     HIPCHECK(hipSetDevice(h->cfg.device));
     float t = 0.f;
-    HIPCHECK(hipEventElapsedTime(&t, h->ev_ts[0], h->ev_ts[1]));
+    HIPCHECK(hipEventElapsedTime(&t, h->trainset.ev[0], h->trainset.ev[1]));
     *ms = (double)t;
     API_END
 }

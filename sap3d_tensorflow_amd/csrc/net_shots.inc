@@ -194,20 +194,20 @@ int p3d_temporal_filter_shots(int device, int mode, const p3d_video_temporal* cf
     const char* who = "temporal_filter_shots";
     if (!store || !out) throw P3dError("null argument");
     if (mode != VIDEO_NEWEST && mode != VIDEO_MEAN) throw P3dError(std::string(who) + ": mode " + std::to_string(mode) + " is neither P3D_VIDEO_NEWEST (0) nor P3D_VIDEO_MEAN (1)");
-    const p3d_handle::TemporalCfg t = p3d_handle::temporal_parse(cfg);
+    const p3d_handle::TemporalCfg t = p3d_handle::TemporalCfg::parse(cfg);
     if (!t.on()) throw P3dError(std::string(who) + ": needs a kind (GAUSS or EMA)");
     if (F < 1 || hw < 1 || (int64_t)F * hw > (int64_t)1 << 31) throw P3dError(std::string(who) + ": bad shape");
     shots_table_check(who, starts, n_shots, F);
     std::vector<int32_t> ones;
     if (!count) { ones.assign((size_t)F, 1); count = ones.data(); }
-    p3d_handle::temporal_check_shots(who, t, F, first, n, count, starts, n_shots);
+    p3d_handle::TemporalCfg::check_shots(who, t, F, first, n, count, starts, n_shots);
     video_hook_device(device, offset);
     const std::vector<int> runs = p3d_video_temporal_runs(t.set.kind, t.r, hw, F, first, n, starts, n_shots);
     const int64_t ns = (int64_t)F * hw, no = (int64_t)n * hw;
     Guarded<float> sb((size_t)ns, 8, (size_t)offset, store), ob((size_t)no, 8, (size_t)offset, nullptr);
     Guarded<int32_t> cb((size_t)F, 8, 0, count);
     Guarded<int> rb(runs.size(), 8, 0, runs.data());
-    const VideoTemporalArgs a = p3d_handle::temporal_args(t, sb.data(), mode == VIDEO_MEAN ? cb.data() : nullptr, ob.data(), F, hw, first, n);
+    const VideoTemporalArgs a = p3d_handle::TemporalCfg::args(t, sb.data(), mode == VIDEO_MEAN ? cb.data() : nullptr, ob.data(), F, hw, first, n);
     HIPCHECK(p3d_video_temporal_shots_launch(a, rb.data(), (int)(runs.size() / 4), nullptr));
     HIPCHECK(hipDeviceSynchronize());
     sb.unchanged(who); cb.unchanged(who); rb.unchanged(who);
@@ -220,10 +220,10 @@ int p3d_video_set_shots(p3d_handle* h, const int32_t* starts, int n_shots) {
     API_BEGIN
     const char* who = "video_set_shots";
     if (!h) throw P3dError("null argument");
-    h->video_need_open(who);
-    if (!starts) { h->vid_shots.clear(); return 0; }
-    shots_table_check(who, starts, n_shots, h->vid_F);
-    h->vid_shots.assign(starts, starts + n_shots);
+    h->video.need_open(who);
+    if (!starts) { h->video.shots.clear(); return 0; }
+    shots_table_check(who, starts, n_shots, h->video.F);
+    h->video.shots.assign(starts, starts + n_shots);
     API_END
 }
 
@@ -231,10 +231,10 @@ int p3d_video_get_shots(p3d_handle* h, int32_t* starts, int cap, int* n_shots) {
     API_BEGIN
     const char* who = "video_get_shots";
     if (!h || !n_shots) throw P3dError("null argument");
-    h->video_need_open(who);
+    h->video.need_open(who);
     if (starts && cap < 0) throw P3dError(std::string(who) + ": a negative cap");
-    if (starts) std::copy(h->vid_shots.begin(), h->vid_shots.begin() + std::min((size_t)cap, h->vid_shots.size()), starts);
-    *n_shots = (int)h->vid_shots.size();
+    if (starts) std::copy(h->video.shots.begin(), h->video.shots.begin() + std::min((size_t)cap, h->video.shots.size()), starts);
+    *n_shots = (int)h->video.shots.size();
     API_END
 }
 
@@ -242,9 +242,9 @@ int p3d_video_detect_shots(p3d_handle* h, const int cfg[6], uint32_t* D_out, int
     API_BEGIN
     const char* who = "video_detect_shots";
     if (!h || !cfg || !n_shots) throw P3dError("null argument");
-    h->video_need_open(who);
+    h->video.need_open(who);
     need_kept_source(h, who);
-    const int F = h->vid_F, H = h->vid_H0, W = h->vid_W0;
+    const int F = h->video.F, H = h->video.H0, W = h->video.W0;
     shots_shape_check(who, F, H, W, cfg[P3D_SHOTS_GRID_Y], cfg[P3D_SHOTS_GRID_X]);
     shots_rule_check(who, cfg);
     if (starts_out && cap < 1) throw P3dError(std::string(who) + ": room for at least one start");
@@ -262,14 +262,14 @@ int p3d_video_detect_shots(p3d_handle* h, const int cfg[6], uint32_t* D_out, int
         c.starts = cv.take<int32_t>((size_t)F);
         c.n_shots = cv.take<int32_t>(1);
     });
-    a.frames = h->vid_src; a.tabs = tabs; c.D = a.D;
-    if (!h->ev_shots[0]) for (auto& e : h->ev_shots) HIPCHECK(hipEventCreate(&e));
-    HIPCHECK(hipEventRecord(h->ev_shots[0], s));
+    a.frames = h->video.source; a.tabs = tabs; c.D = a.D;
+    h->shots_timer.ev.create();
+    HIPCHECK(hipEventRecord(h->shots_timer.ev[0], s));
     HIPCHECK(p3d_shots_launch(a, s));
-    HIPCHECK(hipEventRecord(h->ev_shots[1], s));
+    HIPCHECK(hipEventRecord(h->shots_timer.ev[1], s));
     HIPCHECK(p3d_shot_cuts_launch(c, s));
-    HIPCHECK(hipEventRecord(h->ev_shots[2], s));
-    h->shots_timed = true;
+    HIPCHECK(hipEventRecord(h->shots_timer.ev[2], s));
+    h->shots_timer.timed = true;
     std::vector<int32_t> starts((size_t)F);
     int32_t count = 0;
     HIPCHECK(copy_now(&count, c.n_shots, sizeof(count), hipMemcpyDeviceToHost, s));
@@ -281,7 +281,7 @@ int p3d_video_detect_shots(p3d_handle* h, const int cfg[6], uint32_t* D_out, int
     *n_shots = (int)count;
     if (install) {
         shots_table_check(who, starts.data(), (int)count, F);
-        h->vid_shots = starts;
+        h->video.shots = starts;
     }
     API_END
 }
@@ -289,11 +289,11 @@ int p3d_video_detect_shots(p3d_handle* h, const int cfg[6], uint32_t* D_out, int
 int p3d_video_shots_last_ms(p3d_handle* h, double* ms) {
     API_BEGIN
     if (!h || !ms) throw P3dError("null argument");
-    if (!h->shots_timed) throw P3dError("video_shots_last_ms: no p3d_video_detect_shots has run");
+    if (!h->shots_timer.timed) throw P3dError("video_shots_last_ms: no p3d_video_detect_shots has run");
     float t0 = 0.f, t1 = 0.f;
-    HIPCHECK(hipEventSynchronize(h->ev_shots[2]));
-    HIPCHECK(hipEventElapsedTime(&t0, h->ev_shots[0], h->ev_shots[1]));
-    HIPCHECK(hipEventElapsedTime(&t1, h->ev_shots[1], h->ev_shots[2]));
+    HIPCHECK(hipEventSynchronize(h->shots_timer.ev[2]));
+    HIPCHECK(hipEventElapsedTime(&t0, h->shots_timer.ev[0], h->shots_timer.ev[1]));
+    HIPCHECK(hipEventElapsedTime(&t1, h->shots_timer.ev[1], h->shots_timer.ev[2]));
     ms[0] = t0; ms[1] = t1;
     API_END
 }
