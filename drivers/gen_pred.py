@@ -33,7 +33,9 @@ on the device (P3DSession.video_render), whatever `--write` and `--truth` do bes
 shot table on every video before its maps are read -- the hard cuts found on the device in the decoded frames
 (P3DSession.video_detect_shots, shaped by `--shots-grid`, `-threshold`, `-window`, `-ratio`, `-min-length`), or the starts in FILE.npy
 -- so that `--temporal` filters inside the shots and `--reframe` smooths its track inside them; it writes `<out>/<video>_shots.npy`
-and, under detect, `<out>/<video>_cutsignal.npy`.  `--shot-windows` (an addition, needs `--shots`) installs the table before the
+and, under detect, `<out>/<video>_cutsignal.npy`.  `--shots-gradual` (an addition, with `--shots detect`) finds dissolves and fades as
+well (P3DSession.video_detect_transitions, shaped by `--shots-lag`, `-high`, `-dip`, `-mono`, `-mono-min`) and also writes
+`<out>/<video>_shotkinds.npy`, `_lagsignal.npy` and `_spread.npy`.  `--shot-windows` (an addition, needs `--shots`) installs the table before the
 windows are cut and keeps every window inside its shot (P3DSession.video_predict_shots, dataflow.shot_window_starts): per shot a
 window every `--stride` frames and a last one at the shot's end; a shot shorter than 16 frames takes one window, filled by reflecting
 inside the shot, and no map is predicted from frames of another shot.  `--reframe DIR` (an addition, needs
@@ -502,6 +504,19 @@ def parse_args(argv=None):
     p.add_argument("--shots-ratio", type=int, default=None, metavar="Q8", help="[addition] --shots detect: a cut's distance is at least Q8 / 256 times "
                    "every other within the window, 256 .. 65535 (512)")
     p.add_argument("--shots-min-length", type=int, default=None, metavar="FRAMES", help="[addition] --shots detect: the shortest shot, at least 1 (3)")
+    p.add_argument("--shots-gradual", action="store_true", help="[addition] --shots detect: find dissolves and fades as well "
+                   "(P3DSession.video_detect_transitions); also writes <out>/<video>_shotkinds.npy (0 first, 1 cut, 2 fade, 3 dissolve), "
+                   "_lagsignal.npy and _spread.npy")
+    p.add_argument("--shots-lag", type=int, default=None, metavar="FRAMES", help="[addition] --shots-gradual: a dissolve is looked for in the distance "
+                   "of a frame from the one this many before it, 2 .. 64, 0: no dissolves (12)")
+    p.add_argument("--shots-high", type=int, default=None, metavar="PERMILLE", help="[addition] --shots-gradual: that distance is at least this many "
+                   "permille of the largest possible through a dissolve, 1 .. 1000 (250)")
+    p.add_argument("--shots-dip", type=int, default=None, metavar="Q8", help="[addition] --shots-gradual: the spread of a dissolve's frames falls to "
+                   "Q8 / 256 of its ends', 1 .. 256, 256: not asked (230)")
+    p.add_argument("--shots-mono", type=int, default=None, metavar="Q8", help="[addition] --shots-gradual: a frame is monochrome up to a spread of "
+                   "Q8 / 256 a pixel, 0 .. 65535 (768)")
+    p.add_argument("--shots-mono-min", type=int, default=None, metavar="FRAMES", help="[addition] --shots-gradual: the shortest monochrome run that "
+                   "ends a shot, 0: no fades (2)")
     p.add_argument("--base", type=int, default=64, help=argparse.SUPPRESS)
     p.add_argument("--blocks", type=str, default="3,8,36", help=argparse.SUPPRESS)
     p.add_argument("--time", action="store_true", help="print per-video wall times (png / jpg: also the device stage and the host encode)")
@@ -545,15 +560,22 @@ def parse_args(argv=None):
 
 
 SHOTS_DEFAULTS = dict(grid=(2, 2), threshold=250, window=2, ratio=512, min_length=3)
+GRADUAL_DEFAULTS = dict(lag=12, high=250, dip=230, mono=768, mono_min=2)
 
 
 def shots_args(args, error):
     """Checks --shots and its values as P3DSession.video_detect_shots would refuse them, before anything runs; error(message) does not
     return.  Leaves dict(detect=dict(grid, threshold, window, ratio, min_length) or None, starts=array or None) in args.shots_kw (None
-    without --shots)."""
+    without --shots); under --shots-gradual also gradual=dict(lag, high, dip, mono, mono_min), checked as
+    P3DSession.video_detect_transitions would refuse it."""
     args.shots_kw = None
     given = dict(grid=args.shots_grid, threshold=args.shots_threshold, window=args.shots_window, ratio=args.shots_ratio, min_length=args.shots_min_length)
     shaped = any(v is not None for v in given.values())
+    gradual = dict(lag=args.shots_lag, high=args.shots_high, dip=args.shots_dip, mono=args.shots_mono, mono_min=args.shots_mono_min)
+    if args.shots != "detect" and args.shots_gradual:
+        error("--shots-gradual needs --shots detect")
+    if not args.shots_gradual and any(v is not None for v in gradual.values()):
+        error("--shots-lag / -high / -dip / -mono / -mono-min need --shots-gradual")
     if not args.shots:
         if shaped:
             error("--shots-grid / -threshold / -window / -ratio / -min-length need --shots detect")
@@ -586,12 +608,30 @@ def shots_args(args, error):
     if kw["min_length"] < 1:
         error("--shots-min-length is at least 1 frame")
     args.shots_kw = dict(detect=kw, starts=None)
+    if args.shots_gradual:
+        g = dict((k, GRADUAL_DEFAULTS[k] if v is None else v) for k, v in gradual.items())
+        if g["lag"] != 0 and not 2 <= g["lag"] <= 64:
+            error("--shots-lag is 2 .. 64 frames, or 0 for no dissolves")
+        if not 1 <= g["high"] <= 1000:
+            error("--shots-high is 1 .. 1000 permille")
+        if not 1 <= g["dip"] <= 256:
+            error("--shots-dip is 1 .. 256 (256: not asked)")
+        if not 0 <= g["mono"] <= 65535:
+            error("--shots-mono is 0 .. 65535")
+        if g["mono_min"] < 0:
+            error("--shots-mono-min is a number of frames, or 0 for no fades")
+        args.shots_kw["gradual"] = g
 
 
 def shots_video_resident(sess, F, out_dir, name, shots):
     """--shots: installs the open video's shot table before any map is read and writes <out>/<name>_shots.npy (and _cutsignal.npy
-    under detect).  -> the starts."""
-    if shots["detect"] is not None:
+    under detect; _shotkinds.npy, _lagsignal.npy and _spread.npy as well under --shots-gradual).  -> the starts."""
+    if shots.get("gradual") is not None:      # --shots-gradual: dissolves and fades as well, the kinds beside the starts
+        kw = dict(shots["detect"], **shots["gradual"])
+        starts, kinds, D, E, v = sess.video_detect_transitions(install=True, with_signals=True, **kw)
+        for suffix, what in (("_cutsignal.npy", D), ("_lagsignal.npy", E), ("_spread.npy", v), ("_shotkinds.npy", np.asarray(kinds, np.int32))):
+            np.save(os.path.join(out_dir, name + suffix), what)
+    elif shots["detect"] is not None:
         starts, D = sess.video_detect_shots(install=True, with_signal=True, **shots["detect"])
         np.save(os.path.join(out_dir, name + "_cutsignal.npy"), D)
     else:

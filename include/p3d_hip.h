@@ -1684,7 +1684,8 @@ int p3d_debug_reframe_plan(int H, int W, int crop_h, int crop_w, int n, int* pos
  * entry point issues what it issued before and returns the same bits.  PARITY UNPINNED: the reference's clips are single takes and
  * it has nothing of the kind; this text is the contract and tests/shots_ref.py replays it in numpy.  SIGNAL and DECISION are integer
  * arithmetic, no floating point anywhere: no order can show, and every test holds to 0.  Hard cuts only: a dissolve or a fade
- * spreads its change over many frames, none of which is a peak, and is NOT detected.
+ * spreads its change over many frames, none of which is a peak, and is NOT detected by the entry points of this section; "Gradual
+ * transitions" below finds them, behind entry points of its own.
  * Per frame: bytes [H][W][3] (B, G, R); a grid of gy x gx cells, 1 <= gy <= min(P3D_SHOTS_MAX_GRID, H), 1 <= gx <= min(.., W).
  *   LIMITS   1 <= n <= 65535 frames a call; P = H * W <= 2^28, so that 6 P fits 32 bits.
  *   CELL     pixel (y, x) lies in cell (y * gy / H, x * gx / W), integer division.
@@ -1758,6 +1759,75 @@ int p3d_temporal_filter_shots(int device, int mode, const p3d_video_temporal* cf
 int p3d_reframe_shots_u8(int device, const unsigned char* sal, const unsigned char* frames /* may be NULL */, int n, int H, int W,
                          const p3d_reframe* cfg, const int32_t* starts, int n_shots, int offset /* -1, or 0 .. 15 */, int32_t* track,
                          int32_t* raw /* may be NULL */, uint32_t* mass /* may be NULL */, unsigned char* out /* NULL exactly when frames is */);
+
+/* ---- Gradual transitions (an ADDITION beside the hard-cut detector above: edited video is full of dissolves and fades to black,
+ * and across one the temporal filter, the reframe track and the network's windows still mix two scenes).  OFF until called: every
+ * entry point above issues what it issued before and returns the same bits.  PARITY UNPINNED, as above: this text is the contract and
+ * tests/transitions_ref.py replays it in numpy and Python integers; every test holds to 0.  Frames, grid, LIMITS, CELL, HIST, DIST,
+ * CAND and the cut CONFIG cfg[6] are those of "Shot boundaries of 8-bit frames"; P = H * W.
+ *   SIGNAL   three numbers a frame, all from the cell histograms h_f:
+ *            D_f  exactly DIST.
+ *            E_f  for a lag K in 2 .. 64: 0 for f < K, otherwise the sum over cells, channels and bins of |h_f - h_{f-K}|.
+ *                 0 <= E_f <= 6 P.  K = 0: E_f = 0 for every f.
+ *            v_f  the spread, independent of the grid: per channel c, n_b = the sum of bin b over all cells, S1 = sum b n_b and
+ *                 S2 = sum b^2 n_b over b = 0 .. 63, w_c = S2 - floor(S1^2 / P); v_f = w_0 + w_1 + w_2, 0 <= v_f < 2^40, int64.
+ *                 S1^2 reaches 2^68 and is not formed: with q = S1 / P and r = S1 - q P, floor(S1^2 / P) = q^2 P + 2 q r +
+ *                 floor(r^2 / P), every term below 2^64.
+ *   CONFIG   five ints beside cfg[6], in the order of the P3D_GRADUAL_* indices below (`const int gcfg[5]`): LAG, the lag K, 0
+ *            (dissolves off) or 2 .. 64; HIGH, permille, 1 .. 1000; DIP, q8, 1 .. 256; MONO, q8, 0 .. 65535; MONO_MIN, frames, 0
+ *            (fades off) or >= 1.  The drivers' defaults: 12, 250, 230, 768, 2.
+ *   DECISION in 64-bit integers:
+ *     MONO(f)  v_f * 256 <= MONO * P.
+ *     FADE     every maximal run [a, b] of MONO frames with b - a + 1 >= MONO_MIN, a >= 1 and b <= F - 2 sets FADE(b + 1): the next
+ *              shot starts at the first frame that is no longer monochrome, the fade-out and the black frames stay with the shot
+ *              before.  MONO_MIN = 0: no FADE.
+ *     HIGH(f)  K >= 2, f >= K and E_f * 1000 >= HIGH * 6 * P.
+ *     DISS     every maximal run [p, q] of HIGH frames, n = q - p + 1, sets DISS(s), s = (p + q - K + 1) >> 1, when all four hold:
+ *              LENGTH   2 n >= K and n <= 2 K;
+ *              NO CUT   no g in [max(1, p - K + 1), q] has CAND(g) (a hard cut makes a bump of K frames in E by itself);
+ *              NO MONO  no g in [max(0, p - K), q] has MONO(g) (fades belong to FADE);
+ *              DIP      with lo = max(p - K, 0): 256 * the least v over [lo, q] <= DIP * min(v_lo, v_q) -- the variance dip of a
+ *                       blend of two uncorrelated scenes, which a pan or a brightness drift does not have.  DIP = 256: always true.
+ *              A hard cut at a would give s = a; a linear dissolve over frames a .. a + L - 1 gives s about a + L / 2.
+ *     KIND(f)  P3D_SHOT_CUT if CAND(f), else P3D_SHOT_FADE if FADE(f), else P3D_SHOT_DISSOLVE if DISS(f), else none.
+ *     ACCEPT   the ACCEPT above with "KIND(f) is not none" in place of CAND(f).
+ *   RESULT   starts [n_shots] as above and kinds [n_shots], kinds[0] = P3D_SHOT_FIRST, kinds[k] = KIND(starts[k]).  With LAG = 0 and
+ *            MONO_MIN = 0 the starts are p3d_shot_cuts's for every input.
+ *   NOT FOUND: a dissolve longer than about K frames (LENGTH fails); a wipe.  A pan that starts and stops within about K frames is
+ *            rejected by DIP alone.
+ * p3d_shot_signals_u8   op level, host frames [n][H][W][3] -> D, E [n] and v [n]; lag is K, 0 or 2 .. 64.
+ * p3d_shot_transitions  op level, host D, E, v [F] (every v in [0, 2^40)) and P -> the first min(cap, n_shots) starts and kinds, and
+ *                       n_shots (cap >= 1).  One block on the device; every buffer between guards; grid_y and grid_x are not read.
+ * p3d_video_detect_transitions  SIGNAL and DECISION on the kept source, as p3d_video_detect_shots and with its refusals; D_out, E_out,
+ *                       v_out [F], starts_out and kinds_out [cap] may be NULL; install != 0 installs the table and its kinds.
+ * p3d_video_get_shot_kinds  the first min(cap, n_shots) kinds of the installed table (kinds may be NULL) and n_shots, 0 without a
+ *                       table.  A table of p3d_video_set_shots or p3d_video_detect_shots has P3D_SHOT_CUT for every shot after the first.
+ * p3d_video_shots_last_ms reports the last detection of either kind.
+ * Refused (-1, p3d_last_error set, nothing launched): a null pointer, LIMITS, a grid or a value of either CONFIG outside its range.
+ * TEST HOOKS (tests/test_gpu_transitions.py, tests/test_transitions_cpu.py):
+ * p3d_debug_shot_signals_u8   the signal's launch description with every device buffer, the scratch included, between guards; the
+ *                       frames start `offset` bytes (0 .. 15) past a 16-byte boundary.  -1 if a guard or the frames changed.
+ * p3d_debug_transitions_plan  host only, no HIP call: tables = min(n, 64) + max(K, 1) tables of grid_y * grid_x * 192 words are held
+ *                       (a chunk of at most 64 frames behind the last max(K, 1) tables of the chunk before), scratch_bytes = 4 bytes
+ *                       a word.
+ * p3d_debug_transitions_time  HIP-event milliseconds of `reps` rounds of: the cut signal's launches (p3d_shot_distances_u8's) and
+ *                       this section's signal launches on the same frames, in turn, after one untimed round. */
+enum { P3D_GRADUAL_LAG = 0, P3D_GRADUAL_HIGH = 1, P3D_GRADUAL_DIP = 2, P3D_GRADUAL_MONO = 3, P3D_GRADUAL_MONO_MIN = 4 };
+enum { P3D_SHOT_FIRST = 0, P3D_SHOT_CUT = 1, P3D_SHOT_FADE = 2, P3D_SHOT_DISSOLVE = 3 };
+int p3d_shot_signals_u8(int device, const unsigned char* frames, int n, int H, int W, int grid_y, int grid_x, int lag, uint32_t* D /* [n] */,
+                        uint32_t* E /* [n] */, int64_t* v /* [n] */);
+int p3d_shot_transitions(int device, const uint32_t* D, const uint32_t* E, const int64_t* v, int F, int64_t P, const int cfg[6],
+                         const int gcfg[5], int32_t* starts /* [cap] */, int32_t* kinds /* [cap] */, int cap, int* n_shots);
+int p3d_video_detect_transitions(p3d_handle* h, const int cfg[6], const int gcfg[5], uint32_t* D_out /* [F], may be NULL */,
+                                 uint32_t* E_out /* [F], may be NULL */, int64_t* v_out /* [F], may be NULL */,
+                                 int32_t* starts_out /* [cap], may be NULL */, int32_t* kinds_out /* [cap], may be NULL */, int cap,
+                                 int* n_shots, int install);
+int p3d_video_get_shot_kinds(p3d_handle* h, int32_t* kinds /* [cap], may be NULL */, int cap, int* n_shots);
+int p3d_debug_shot_signals_u8(int device, const unsigned char* frames, int n, int H, int W, int grid_y, int grid_x, int lag, int offset,
+                              uint32_t* D, uint32_t* E, int64_t* v);
+int p3d_debug_transitions_plan(int H, int W, int grid_y, int grid_x, int n, int lag, int* tables, int64_t* scratch_bytes);
+int p3d_debug_transitions_time(int device, const unsigned char* frames, int n, int H, int W, int grid_y, int grid_x, int lag, int reps,
+                               double* cut_ms /* [reps] */, double* signal_ms /* [reps] */);
 
 /* ---- Shot-aware windows (an ADDITION beside p3d_video_predict, whose windows are T consecutive frames wherever the cuts lie: a
  * window across a cut shows the network a clip of two unrelated scenes, and every map within T - 1 frames of the cut is predicted

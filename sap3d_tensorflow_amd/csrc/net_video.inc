@@ -24,6 +24,7 @@
         // filters inside the shots (the *_shots launches of temporal.hip, from a run table that follows the filtered maps in the
         // scratch) and p3d_video_reframe smooths its track inside them; nothing else reads it.
         std::vector<int32_t> shots;                                 // the starts, ascending from 0; empty: no table
+        std::vector<int32_t> shot_kinds;                            // P3D_SHOT_* of every shot where p3d_video_detect_transitions installed the table; else empty
         std::vector<int> runs;                                      // the host's copy of the last run table (it outlives the asynchronous upload)
 
         // What one p3d_video_predict does to the stores, from host state alone (no HIP call): validates as the header says -- the
@@ -165,6 +166,7 @@
         video.put.assign((size_t)frames, 0);
         video.source_drop();
         video.shots.clear();
+        video.shot_kinds.clear();
         video.F = frames; video.mode = mode; video.last = -1; video.is_open = true; video.timed = false;
     }
     void video_close() {

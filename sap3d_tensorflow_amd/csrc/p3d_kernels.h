@@ -1188,6 +1188,33 @@ struct ShotCutArgs {
     int threshold_permille = 0, window = 0, ratio_q8 = 0, min_length = 0;
 };
 hipError_t p3d_shot_cuts_launch(const ShotCutArgs& a, hipStream_t s);
+// The three signals of "Gradual transitions" (p3d_shot_signals_u8): cut.D as above, E [n] the distance of frame f's histograms
+// from frame f - lag's (0 for f < lag; lag 0: all 0) and v [n] the spread of the frame's bins.  cut carries the frames, the grid and
+// the count's plan, which is p3d_shots_plan's; cut.tabs is scratch of p3d_transitions_plan's `tables` tables: the first carry =
+// max(lag, 1) slots hold the last tables of the chunk before, frame c of the chunk is slot carry + c.  Per chunk: a fill of its
+// slots, shots_count unchanged, one block a frame for D, E and v together, and a copy of the chunk's last carry tables to the front.
+// Refused (hipErrorInvalidValue): what p3d_shots_launch refuses, a missing E or v, a lag other than 0 or 2 .. P3D_SHOTS_MAX_LAG.
+constexpr int P3D_SHOTS_MAX_LAG = 64;                     // a chunk's carry comes from one chunk: P3D_SHOTS_MAX_LAG <= P3D_SHOTS_CHUNK
+struct TransitionsPlan {
+    int tables = 0;                                       // min(n, P3D_SHOTS_CHUNK) + max(lag, 1)
+    long long scratch_bytes = 0;                          // tables * gy * gx * 192 * 4
+};
+TransitionsPlan p3d_transitions_plan(int gy, int gx, int n, int lag);
+struct ShotSignalsArgs {
+    ShotsArgs cut;
+    uint32_t* E = nullptr; long long* v = nullptr;
+    int lag = 0;
+};
+hipError_t p3d_shot_signals_launch(const ShotSignalsArgs& a, hipStream_t s);
+// The decision of "Gradual transitions" on D, E, v [F] (one block): flags and marks are scratch of F words each; starts and kinds
+// [cap] receive the first min(cap, n_shots) shots, n_shots [1] their number.  cut holds D, the cut rule, F, P and cap; its cand,
+// starts and n_shots are the ones used.  Refused: what p3d_shot_cuts_launch refuses, a missing buffer, a CONFIG value outside its range.
+struct ShotTransitionArgs {
+    ShotCutArgs cut;
+    const uint32_t* E = nullptr; const long long* v = nullptr; unsigned* marks = nullptr; int32_t* kinds = nullptr;
+    int lag = 0, high_permille = 0, dip_q8 = 0, mono_q8 = 0, mono_min = 0;
+};
+hipError_t p3d_shot_transitions_launch(const ShotTransitionArgs& a, hipStream_t s);
 
 // ---- misc ---------------------------------------------------------------------------------------
 hipError_t p3d_add_inplace(float* dst, int lddst, const float* src, int ldsrc, long M, int C, hipStream_t s);

@@ -236,3 +236,180 @@ hipError_t p3d_shot_cuts_launch(const ShotCutArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(shots_cuts, dim3(1), dim3(TPB), 0, s, a);
     return hipGetLastError();
 }
+
+// ---- gradual transitions (p3d_shot_signals_u8, p3d_shot_transitions; the law in include/p3d_hip.h, "Gradual transitions") ----
+//  * shots_signals: a block a frame of the chunk, behind shots_count.  Thread j < 192 is channel j / 64 (its wave) and bin j mod 64
+//    (its lane): it walks the cells and reads word j of each cell of the frame's table, of the table before and of the table `lag`
+//    frames back once -- |h_f - h_{f-1}| and |h_f - h_{f-lag}| in 32 bits, the bin's count over all cells n_b beside them.  S1 and S2
+//    of a channel are then sums over the lanes of its wave, and lane 0 forms w_c with the header's q, r split: nothing above 64 bits.
+//  * shots_transitions: one block.  Every thread decides CAND, MONO and HIGH of its frames into scratch; thread 0 then walks the
+//    MONO runs, the HIGH runs (at most 3 lag frames looked at per run that passes LENGTH) and ACCEPT, in that order.
+namespace {
+
+static_assert(P3D_SHOTS_MAX_LAG <= P3D_SHOTS_CHUNK, "the carry of a chunk comes from the one chunk before it");
+static_assert(CELL_WORDS <= TPB && CELL_WORDS == 3 * WAVE, "a thread a word of a cell, a wave a channel");
+constexpr unsigned FLAG_CAND = 1u, FLAG_MONO = 2u, FLAG_HIGH = 4u, MARK_FADE = 1u, MARK_DISS = 2u;
+
+__device__ __forceinline__ unsigned absdiff(unsigned p, unsigned q) { return p > q ? p - q : q - p; }
+
+__global__ __launch_bounds__(TPB) void shots_signals(const unsigned* tabs, int cells, int carry, int lag, unsigned long long P, uint32_t* D,
+                                                     uint32_t* E, long long* v, int f0) {
+    __shared__ unsigned dsum[WAVES], esum[WAVES];
+    __shared__ unsigned long long wsum[WAVES];
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid >> 6, c = blockIdx.x, f = f0 + c;
+    const size_t words = (size_t)cells * CELL_WORDS;
+    const unsigned* cur = tabs + (size_t)(carry + c) * words;
+    const unsigned* prev = cur - words;
+    const unsigned* back = cur - (size_t)lag * words;
+    const bool has_d = f > 0, has_e = lag > 0 && f >= lag;
+    unsigned d = 0u, e = 0u, nb = 0u;
+    if (tid < CELL_WORDS)
+        for (int t = tid; t < (int)words; t += CELL_WORDS) {
+            const unsigned q = cur[t];
+            nb += q;
+            if (has_d) d += absdiff(prev[t], q);
+            if (has_e) e += absdiff(back[t], q);
+        }
+    unsigned long long s1 = (unsigned long long)lane * nb, s2 = (unsigned long long)(lane * lane) * nb;
+#pragma unroll
+    for (int o = WAVE / 2; o > 0; o >>= 1) {
+        d += __shfl_xor(d, o);
+        e += __shfl_xor(e, o);
+        s1 += __shfl_xor(s1, o);
+        s2 += __shfl_xor(s2, o);
+    }
+    if (lane == 0) {
+        const unsigned long long q = s1 / P, r = s1 - q * P;    // floor(S1^2 / P) = q^2 P + 2 q r + floor(r^2 / P)
+        dsum[wave] = d; esum[wave] = e;
+        wsum[wave] = s2 - (q * q * P + 2ull * q * r + r * r / P);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        unsigned td = 0u, te = 0u;
+        unsigned long long tv = 0ull;
+        for (int k = 0; k < CELL_WORDS / WAVE; ++k) { td += dsum[k]; te += esum[k]; tv += wsum[k]; }
+        D[f] = td; E[f] = te; v[f] = (long long)tv;
+    }
+}
+
+__global__ __launch_bounds__(TPB) void shots_transitions(ShotTransitionArgs a) {
+    const ShotCutArgs& c = a.cut;
+    const int tid = threadIdx.x, F = c.F, K = a.lag;
+    const unsigned long long floor_lhs = (unsigned long long)c.threshold_permille * 6ull * (unsigned long long)c.P;
+    const unsigned long long high_lhs = (unsigned long long)a.high_permille * 6ull * (unsigned long long)c.P;
+    const long long mono_rhs = (long long)a.mono_q8 * c.P;
+    for (int f = tid; f < F; f += TPB) {
+        unsigned is = 0u;
+        if (f >= 1) {
+            const unsigned long long d = c.D[f];
+            unsigned nmax = 0u;
+            for (int g = max(1, f - c.window); g <= min(F - 1, f + c.window); ++g)
+                if (g != f) nmax = max(nmax, c.D[g]);
+            if (d * 1000ull >= floor_lhs && d * 256ull >= (unsigned long long)c.ratio_q8 * nmax) is |= FLAG_CAND;
+        }
+        if (a.v[f] * 256ll <= mono_rhs) is |= FLAG_MONO;
+        if (K > 0 && f >= K && (unsigned long long)a.E[f] * 1000ull >= high_lhs) is |= FLAG_HIGH;
+        c.cand[f] = is;
+        a.marks[f] = 0u;
+    }
+    __syncthreads();                                        // one block: its own stores to cand and marks are visible behind the barrier
+    if (tid != 0) return;
+    const unsigned* flag = c.cand;
+    if (a.mono_min > 0) {                                   // FADE: the run [f - run, f - 1] ends before a frame f <= F - 1
+        int run = 0;
+        for (int f = 0; f < F; ++f) {
+            if (flag[f] & FLAG_MONO) { ++run; continue; }
+            if (run >= a.mono_min && f - run >= 1) a.marks[f] |= MARK_FADE;
+            run = 0;
+        }
+    }
+    for (int f = K; K > 0 && f < F;) {                      // DISS: the runs [p, q] of HIGH
+        if (!(flag[f] & FLAG_HIGH)) { ++f; continue; }
+        const int p = f;
+        while (f < F && (flag[f] & FLAG_HIGH)) ++f;
+        const int q = f - 1, n = q - p + 1;
+        if (2 * n < K || n > 2 * K) continue;
+        bool ok = true;
+        for (int g = max(1, p - K + 1); g <= q && ok; ++g) ok = !(flag[g] & FLAG_CAND);
+        const int lo = max(p - K, 0);
+        long long vmin = a.v[lo];
+        for (int g = lo; g <= q && ok; ++g) {
+            ok = !(flag[g] & FLAG_MONO);
+            vmin = min(vmin, a.v[g]);
+        }
+        if (ok && vmin * 256ll <= (long long)a.dip_q8 * min(a.v[lo], a.v[q])) a.marks[(p + q - K + 1) >> 1] |= MARK_DISS;
+    }
+    int last = 0, count = 1;
+    if (c.cap > 0) { c.starts[0] = 0; a.kinds[0] = P3D_SHOT_FIRST; }
+    for (int f = 1; f < F; ++f) {
+        const int kind = (flag[f] & FLAG_CAND) ? P3D_SHOT_CUT : (a.marks[f] & MARK_FADE) ? P3D_SHOT_FADE : (a.marks[f] & MARK_DISS) ? P3D_SHOT_DISSOLVE : P3D_SHOT_FIRST;
+        if (kind != P3D_SHOT_FIRST && f - last >= c.min_length && F - f >= c.min_length) {
+            if (count < c.cap) { c.starts[count] = f; a.kinds[count] = kind; }
+            ++count;
+            last = f;
+        }
+    }
+    *c.n_shots = count;
+}
+
+bool lag_ok(int lag) { return lag == 0 || (lag >= 2 && lag <= P3D_SHOTS_MAX_LAG); }
+
+}  // namespace
+
+TransitionsPlan p3d_transitions_plan(int gy, int gx, int n, int lag) {
+    TransitionsPlan p;
+    p.tables = std::min(n, P3D_SHOTS_CHUNK) + std::max(lag, 1);
+    p.scratch_bytes = (long long)p.tables * gy * gx * CELL_WORDS * 4;
+    return p;
+}
+
+hipError_t p3d_shot_signals_launch(const ShotSignalsArgs& a, hipStream_t s) {
+    const ShotsArgs& k = a.cut;
+    if (!k.frames || !k.D || !a.E || !a.v || !k.tabs || !shape_ok(k.n, k.H, k.W, k.gy, k.gx) || !lag_ok(a.lag)) return hipErrorInvalidValue;
+    const ShotsPlan p = p3d_shots_plan(k.H, k.W, k.gy, k.gx, k.n);
+    if (k.rows_per_block != p.rows_per_block || k.blocks_per_frame != p.blocks_per_frame || k.frames_per_chunk != p.frames_per_chunk)
+        return hipErrorInvalidValue;
+    const size_t T = (size_t)p.table_words;
+    const int carry = std::max(a.lag, 1);
+    CountArgs c;                                            // as p3d_shots_launch fills it; the count puts frame c of a chunk at slot c + 1 of its tabs
+    c.frames = k.frames; c.tabs = k.tabs + (size_t)(carry - 1) * T; c.H = k.H; c.W = k.W; c.gy = k.gy; c.gx = k.gx; c.rows_per_block = p.rows_per_block;
+    for (int r = 0; r <= MAX_GRID; ++r) { c.by[r] = k.H; c.nb[r] = p.blocks_per_frame; }
+    int blocks = 0;
+    for (int r = 0; r < k.gy; ++r) {
+        c.by[r] = ceil_div((long long)r * k.H, k.gy);
+        c.nb[r] = blocks;
+        blocks += ceil_div(ceil_div((long long)(r + 1) * k.H, k.gy) - c.by[r], p.rows_per_block);
+    }
+    for (int j = 1; j < MAX_GRID; ++j) c.bx[j - 1] = j < k.gx ? ceil_div((long long)j * k.W, k.gx) : INT32_MAX;
+    for (int f0 = 0; f0 < k.n; f0 += p.frames_per_chunk) {
+        const int m = std::min(p.frames_per_chunk, k.n - f0);
+        hipError_t e = hipMemsetAsync(k.tabs + (size_t)carry * T, 0, (size_t)m * T * sizeof(unsigned), s);
+        if (e != hipSuccess) return e;
+        const dim3 grid((unsigned)p.blocks_per_frame, (unsigned)m);
+        if (k.ballot) hipLaunchKernelGGL(shots_count<true>, grid, dim3(TPB), 0, s, c, f0);
+        else hipLaunchKernelGGL(shots_count<false>, grid, dim3(TPB), 0, s, c, f0);
+        hipLaunchKernelGGL(shots_signals, dim3((unsigned)m), dim3(TPB), 0, s, (const unsigned*)k.tabs, k.gy * k.gx, carry, a.lag,
+                           (unsigned long long)k.H * (unsigned long long)k.W, k.D, a.E, a.v, f0);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (f0 + m < k.n) {                                 // m is a whole chunk here, at least carry: its last carry tables seed the next
+            e = hipMemcpyAsync(k.tabs, k.tabs + (size_t)m * T, (size_t)carry * T * sizeof(unsigned), hipMemcpyDeviceToDevice, s);
+            if (e != hipSuccess) return e;
+        }
+    }
+    return hipSuccess;
+}
+
+hipError_t p3d_shot_transitions_launch(const ShotTransitionArgs& a, hipStream_t s) {
+    const ShotCutArgs& c = a.cut;
+    if (!c.D || !a.E || !a.v || !c.cand || !a.marks || !c.n_shots || c.F < 1 || c.F > 65535 || c.P < 1 || c.P > P3D_SHOTS_MAX_PIXELS || c.cap < 0 ||
+        (c.cap > 0 && (!c.starts || !a.kinds)))
+        return hipErrorInvalidValue;
+    if (c.threshold_permille < 1 || c.threshold_permille > 1000 || c.window < 0 || c.window > 32 || c.ratio_q8 < 256 || c.ratio_q8 > 65535 ||
+        c.min_length < 1)
+        return hipErrorInvalidValue;
+    if (!lag_ok(a.lag) || a.high_permille < 1 || a.high_permille > 1000 || a.dip_q8 < 1 || a.dip_q8 > 256 || a.mono_q8 < 0 || a.mono_q8 > 65535 ||
+        a.mono_min < 0)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(shots_transitions, dim3(1), dim3(TPB), 0, s, a);
+    return hipGetLastError();
+}

@@ -725,6 +725,75 @@ def shot_cuts(D, P, threshold=250, window=2, ratio=512, min_length=3, device=0):
     return starts[:count.value].copy()
 
 
+def gradual_cfg(lag=12, high=250, dip=230, mono=768, mono_min=2):
+    """The five ints of include/p3d_hip.h's CONFIG ("Gradual transitions") in the order of the P3D_GRADUAL_* indices: lag in frames
+    (0: dissolves off), high in permille of 6 H W, dip and mono in 1 / 256, mono_min in frames (0: fades off)."""
+    from . import _lib
+    cfg = (C.c_int * 5)()
+    for k, v in ((_lib.P3D_GRADUAL_LAG, lag), (_lib.P3D_GRADUAL_HIGH, high), (_lib.P3D_GRADUAL_DIP, dip), (_lib.P3D_GRADUAL_MONO, mono),
+                 (_lib.P3D_GRADUAL_MONO_MIN, mono_min)):
+        cfg[k] = int(v)
+    return cfg
+
+
+def shot_signals_u8(frames, grid=(2, 2), lag=12, device=0, offset=None):
+    """The signals of gradual transitions of frames uint8 [n, H, W, 3] on the device (p3d_shot_signals_u8): (D, E, v), uint32, uint32
+    and int64 [n] -- D as shot_distances, E[f] the distance of frame f's cell histograms from frame f - lag's (0 before frame lag),
+    v[f] the spread of the frame's bins.  offset (0 .. 15): the test hook p3d_debug_shot_signals_u8, every device buffer between
+    guards, the frames shifted off a 16-byte boundary."""
+    f = _shot_frames(frames)
+    n, H, W, _ = f.shape
+    gy, gx = (int(grid), int(grid)) if np.isscalar(grid) else (int(grid[0]), int(grid[1]))
+    D, E, v = np.empty(n, np.uint32), np.empty(n, np.uint32), np.empty(n, np.int64)
+    u8, u32, i64 = C.POINTER(C.c_ubyte), C.POINTER(C.c_uint32), C.POINTER(C.c_int64)
+    out = (D.ctypes.data_as(u32), E.ctypes.data_as(u32), v.ctypes.data_as(i64))
+    if offset is None:
+        check(lib().p3d_shot_signals_u8(device, f.ctypes.data_as(u8), n, H, W, gy, gx, int(lag), *out))
+    else:
+        check(lib().p3d_debug_shot_signals_u8(device, f.ctypes.data_as(u8), n, H, W, gy, gx, int(lag), int(offset), *out))
+    return D, E, v
+
+
+def shot_transitions(D, E, v, P, threshold=250, window=2, ratio=512, min_length=3, lag=12, high=250, dip=230, mono=768, mono_min=2,
+                     device=0, cap=None):
+    """The decision of gradual transitions on the device (p3d_shot_transitions): D, E uint32 [F] and v int64 [F] of
+    shot_signals_u8, P = H * W of their frames -> (starts, kinds, n_shots): int32 [min(cap, n_shots)] each, starts ascending from 0,
+    kinds the P3D_SHOT_* of every shot; cap: the room given (all F by default)."""
+    d, e = np.ascontiguousarray(D, np.uint32), np.ascontiguousarray(E, np.uint32)
+    w = np.ascontiguousarray(v, np.int64)
+    if d.ndim != 1 or d.size == 0 or e.shape != d.shape or w.shape != d.shape:
+        raise ValueError("D, E and v are non-empty vectors of one length")
+    cfg, gcfg = shots_cfg((1, 1), threshold, window, ratio, min_length), gradual_cfg(lag, high, dip, mono, mono_min)
+    cap = len(d) if cap is None else int(cap)
+    starts, kinds, count = np.empty(max(cap, 1), np.int32), np.empty(max(cap, 1), np.int32), C.c_int(0)
+    u32, i32 = C.POINTER(C.c_uint32), C.POINTER(C.c_int32)
+    check(lib().p3d_shot_transitions(device, d.ctypes.data_as(u32), e.ctypes.data_as(u32), w.ctypes.data_as(C.POINTER(C.c_int64)), len(d), int(P),
+                                     cfg, gcfg, starts.ctypes.data_as(i32), kinds.ctypes.data_as(i32), cap, C.byref(count)))
+    k = min(cap, count.value)
+    return starts[:k].copy(), kinds[:k].copy(), count.value
+
+
+def transitions_plan(H, W, grid=(2, 2), n=1, lag=12):
+    """Test hook (p3d_debug_transitions_plan, host only): dict(tables, scratch_bytes) of shot_signals_u8's launches for n frames."""
+    gy, gx = (int(grid), int(grid)) if np.isscalar(grid) else (int(grid[0]), int(grid[1]))
+    t, s = C.c_int(0), C.c_int64(0)
+    check(lib().p3d_debug_transitions_plan(int(H), int(W), gy, gx, int(n), int(lag), C.byref(t), C.byref(s)))
+    return dict(tables=t.value, scratch_bytes=s.value)
+
+
+def transitions_time(frames, grid=(2, 2), lag=12, reps=20, device=0):
+    """Measurement hook (p3d_debug_transitions_time): HIP-event ms of `reps` alternating rounds -> (cut_ms, signal_ms), float64
+    [reps] each: the cut signal's launches and shot_signals_u8's on the same frames."""
+    f = _shot_frames(frames)
+    n, H, W, _ = f.shape
+    gy, gx = (int(grid), int(grid)) if np.isscalar(grid) else (int(grid[0]), int(grid[1]))
+    out = [np.empty(int(reps), np.float64) for _ in range(2)]
+    dp = C.POINTER(C.c_double)
+    check(lib().p3d_debug_transitions_time(device, f.ctypes.data_as(C.POINTER(C.c_ubyte)), n, H, W, gy, gx, int(lag), int(reps),
+                                           *[o.ctypes.data_as(dp) for o in out]))
+    return tuple(out)
+
+
 def shot_window_starts(shot_starts, frames, stride=1, T=16):
     """The window starts of P3DSession.video_predict_shots that cover a video of `frames` frames under the table shot_starts
     (ascending from 0): per shot of L frames from lo, [lo] where L < T -- the one window a short shot takes -- else lo + 0, stride,

@@ -1041,7 +1041,8 @@ class P3DSession:
         when D_f is at least `threshold` permille of its largest possible value 6 H W, at least ratio / 256 times every other D
         within `window` frames (a flash fails this), and at least `min_length` frames from the last cut and from the end.  Returns
         the starts, int32 [n_shots] ascending from 0 (with_signal: also D, uint32 [frames]); install: the table is installed as
-        video_set_shots would.  Dissolves and fades are not detected.  include/p3d_hip.h holds the exact rules."""
+        video_set_shots would.  Dissolves and fades are not detected (video_detect_transitions finds them).  include/p3d_hip.h holds
+        the exact rules."""
         from . import dataflow
         F = self.video_info()["frames"]
         cfg = dataflow.shots_cfg(grid, threshold, window, ratio, min_length)
@@ -1050,6 +1051,37 @@ class P3DSession:
                                            1 if install else 0))
         starts = starts[:count.value].copy()
         return (starts, D) if with_signal else starts
+
+    def video_detect_transitions(self, grid=(2, 2), threshold=250, window=2, ratio=512, min_length=3, lag=12, high=250, dip=230, mono=768,
+                                 mono_min=2, install=True, with_signals=False):
+        """video_detect_shots with dissolves and fades (an addition): beside D_f, the distance E_f of frame f's histograms from
+        frame f - lag's and the spread v_f of its bins.  A run of monochrome frames (v_f 256 <= mono H W) of at least mono_min
+        frames ends a shot at its last frame (a fade); a run of E_f >= high permille of 6 H W that is lag / 2 .. 2 lag frames long,
+        holds no cut and no monochrome frame and dips in v to dip / 256 of its ends starts a shot at its middle less lag / 2 (a
+        dissolve).  lag = 0 switches dissolves off, mono_min = 0 fades.  Returns (starts, kinds), int32 [n_shots] each, kinds the
+        P3D_SHOT_* numbers (with_signals: also D, E uint32 [frames] and v int64 [frames]); install: the table is installed as
+        video_set_shots would, with its kinds (video_shot_kinds).  include/p3d_hip.h ("Gradual transitions") holds the exact rules."""
+        from . import dataflow
+        F = self.video_info()["frames"]
+        cfg, gcfg = dataflow.shots_cfg(grid, threshold, window, ratio, min_length), dataflow.gradual_cfg(lag, high, dip, mono, mono_min)
+        room = max(F, 1)
+        D, E, v = np.zeros(room, np.uint32), np.zeros(room, np.uint32), np.zeros(room, np.int64)
+        starts, kinds, count = np.zeros(room, np.int32), np.zeros(room, np.int32), C.c_int(0)
+        check(lib().p3d_video_detect_transitions(self._h, cfg, gcfg, _ptr(D, _lib._u32p), _ptr(E, _lib._u32p), _ptr(v, _lib._i64p),
+                                                 _ptr(starts, _lib._i32p), _ptr(kinds, _lib._i32p), room, C.byref(count), 1 if install else 0))
+        starts, kinds = starts[:count.value].copy(), kinds[:count.value].copy()
+        return (starts, kinds, D, E, v) if with_signals else (starts, kinds)
+
+    def video_shot_kinds(self):
+        """The kinds of the installed shot table, int32 [n_shots] of P3D_SHOT_* numbers, or None without a table: FIRST, then what
+        video_detect_transitions found, or CUT throughout for a table of video_set_shots or video_detect_shots."""
+        count = C.c_int(0)
+        check(lib().p3d_video_get_shot_kinds(self._h, None, 0, C.byref(count)))
+        if not count.value:
+            return None
+        kinds = np.empty(count.value, np.int32)
+        check(lib().p3d_video_get_shot_kinds(self._h, _ptr(kinds, _lib._i32p), len(kinds), C.byref(count)))
+        return kinds
 
     def video_set_shots(self, starts):
         """Install a shot table on the open video: starts ascending from 0, each the first frame of a shot; None removes it.  While
