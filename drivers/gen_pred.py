@@ -43,7 +43,12 @@ inside the shot, and no map is predicted from frames of another shot.  `--refram
 `--reframe-size HC WC` or `--reframe-aspect A:B` (width : height; default 9:16) that holds the most saliency at or above
 `--reframe-gate`, on a track averaged over `--reframe-smooth` frames to either side (P3DSession.video_reframe, one call per
 video so that the filter sees all of it), and DIR/<video>/track.npy, int64 [F, 7]: the smoothed (y, x), the raw (y, x), and the
-masses of the best window, of the window taken and of the whole map."""
+masses of the best window, of the window taken and of the whole map.  `--regions DIR` (an addition, needs `--resident`) writes
+DIR/<video>/regions.npy, int32 [F, K, 15], and counts.npy, int32 [F, 3]: the connected regions of every map's pixels at or above
+`--regions-gate` (`--regions-connectivity` 4 or 8), the `--regions-max` heaviest of at least `--regions-min-area` pixels a frame,
+each with its box, area, mass, peak and centre (P3DSession.video_regions at `--size`, one call per video; the fields are
+include/p3d_hip.h's P3D_REGION_*); `--regions-link` carries an ID from frame to frame by overlap, inside the shots of `--shots`;
+`--regions-labels` also writes labels.npy, uint8 [F, H, W]."""
 import argparse
 import glob
 import os
@@ -489,6 +494,17 @@ def parse_args(argv=None):
     p.add_argument("--reframe-gate", type=int, default=0, metavar="LEVEL", help="[addition] --reframe: map levels below it weigh nothing, 0 .. 255")
     p.add_argument("--reframe-smooth", type=int, default=0, metavar="R", help="[addition] --reframe: the track is averaged over R frames to "
                    "either side, 0 .. 255 (0: the raw track)")
+    p.add_argument("--regions", type=str, default="", metavar="DIR", help="[addition] needs --resident: label the connected regions of every "
+                   "map's pixels at or above --regions-gate on the device (P3DSession.video_regions, one call per video, at --size) and "
+                   "write DIR/<video>/regions.npy, int32 [F, K, 15], and counts.npy, int32 [F, 3]")
+    p.add_argument("--regions-gate", type=int, default=128, metavar="LEVEL", help="[addition] --regions: a pixel is foreground at or above it, 1 .. 255 (128)")
+    p.add_argument("--regions-connectivity", type=int, default=8, metavar="C", help="[addition] --regions: 4 or 8 neighbours (8)")
+    p.add_argument("--regions-min-area", type=int, default=1, metavar="PIXELS", help="[addition] --regions: smaller regions are not kept (1)")
+    p.add_argument("--regions-max", type=int, default=64, metavar="K", help="[addition] --regions: the K heaviest regions a frame are kept, 1 .. 64 (64)")
+    p.add_argument("--regions-link", action="store_true", help="[addition] --regions: regions carry an ID from frame to frame by overlap, "
+                   "inside the shots of --shots")
+    p.add_argument("--regions-labels", action="store_true", help="[addition] --regions: also write DIR/<video>/labels.npy, uint8 [F, H, W]: a "
+                   "region's rank, 255 elsewhere")
     p.add_argument("--shots", type=str, default="", metavar="detect|FILE.npy", help="[addition] needs --resident: a shot table for every video, "
                    "installed before its maps are read (P3DSession.video_set_shots) -- --temporal then filters inside the shots and --reframe "
                    "smooths its track inside them.  detect: the hard cuts found on the device in the decoded frames "
@@ -555,6 +571,7 @@ def parse_args(argv=None):
         p.error("--match-bins must be in 2..1024")
     render_args(args, p.error)
     reframe_args(args, p.error)
+    regions_args(args, p.error)
     shots_args(args, p.error)
     return args
 
@@ -641,6 +658,46 @@ def shots_video_resident(sess, F, out_dir, name, shots):
         sess.video_set_shots(starts)
     np.save(os.path.join(out_dir, name + "_shots.npy"), np.asarray(starts, np.int32))
     return starts
+
+
+def regions_args(args, error):
+    """Checks --regions and its values as P3DSession.video_regions would refuse them, before anything runs; error(message) does not
+    return.  Leaves dict(gate, connectivity, min_area, max_regions, link, labels) in args.regions_kw (None without --regions)."""
+    args.regions_kw = None
+    shaped = (args.regions_gate != 128 or args.regions_connectivity != 8 or args.regions_min_area != 1 or args.regions_max != 64 or
+              args.regions_link or args.regions_labels)
+    if not args.regions:
+        if shaped:
+            error("--regions-gate / -connectivity / -min-area / -max / -link / -labels need --regions DIR")
+        return
+    if not args.resident:
+        error("--regions needs --resident: the maps stay on the device")
+    if not 1 <= args.regions_gate <= 255:
+        error("--regions-gate is a level, 1 .. 255")
+    if args.regions_connectivity not in (4, 8):
+        error("--regions-connectivity is 4 or 8")
+    if args.regions_min_area < 1:
+        error("--regions-min-area is at least 1 pixel")
+    if not 1 <= args.regions_max <= 64:
+        error("--regions-max is 1 .. 64 regions")
+    args.regions_kw = dict(gate=args.regions_gate, connectivity=args.regions_connectivity, min_area=args.regions_min_area,
+                           max_regions=args.regions_max, link=args.regions_link, labels=args.regions_labels)
+
+
+def regions_video_resident(sess, F, video_dir, size, regions):
+    """--regions: the open video's maps at `size` labelled on the device (P3DSession.video_regions), ONE call for the whole video so
+    that the link sees every frame; writes regions.npy, counts.npy and, on request, labels.npy into video_dir.  -> dict(gpu, device,
+    regions: ms; kept: regions kept over the video)."""
+    t0 = time.perf_counter()
+    res = sess.video_regions(0, F, size, regions["gate"], connectivity=regions["connectivity"], min_area=regions["min_area"],
+                             max_regions=regions["max_regions"], link=regions["link"], with_labels=regions["labels"], timed=True)
+    t = dict(gpu=(time.perf_counter() - t0) * 1e3, device=sess.last_regions_ms["device"], regions=sess.last_regions_ms["regions"],
+             kept=int(res["counts"][:, 2].sum()))
+    np.save(os.path.join(video_dir, "regions.npy"), res["regions"])
+    np.save(os.path.join(video_dir, "counts.npy"), res["counts"])
+    if regions["labels"]:
+        np.save(os.path.join(video_dir, "labels.npy"), res["labels"])
+    return t
 
 
 def reframe_args(args, error):
@@ -883,6 +940,12 @@ def run_resident(sess, args, path):
     if reframe_dir:
         tf = reframe_video_resident(sess, F, reframe_dir, args.reframe_kw, writers=args.writers)
         print(name, "%d reframed %d x %d png files and track.npy in %s" % ((tf["files"],) + tf["window"] + (reframe_dir,)))
+    tg = None
+    if args.regions_kw:
+        regions_dir = os.path.join(args.regions, name)
+        os.makedirs(regions_dir, exist_ok=True)
+        tg = regions_video_resident(sess, F, regions_dir, tuple(args.size), args.regions_kw)
+        print(name, "%d regions over %d frames: regions.npy, counts.npy%s in %s" % (tg["kept"], F, ", labels.npy" if args.regions_kw["labels"] else "", regions_dir))
     temporal_ms = sess.video_temporal_last_ms() if args.temporal != "off" and args.time else None
     sess.close_video()
     if args.time:
@@ -904,6 +967,8 @@ def run_resident(sess, args, path):
         if tf is not None:
             print("  %s: reframe %.1f ms (uploads %.2f ms, maps %.2f ms, reframe launches %.3f ms on the device) | encode %.1f ms thread "
                   "time on %d writers" % (name, tf["gpu"], tf["upload"], tf["device"], tf["reframe"], tf["encode"], args.writers))
+        if tg is not None:
+            print("  %s: regions %.1f ms (maps %.2f ms, regions launches %.3f ms on the device)" % (name, tg["gpu"], tg["device"], tg["regions"]))
     return means
 
 

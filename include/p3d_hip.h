@@ -1679,6 +1679,74 @@ int p3d_debug_reframe_u8(int device, const unsigned char* sal, const unsigned ch
 int p3d_debug_reframe_plan(int H, int W, int crop_h, int crop_w, int n, int* positions_per_block, int* search_blocks, int* maps_per_chunk,
                            int64_t* scratch_bytes);
 
+/* ---- Salient regions of 8-bit maps (an ADDITION: what the viewers look at, as objects -- the two faces of a dialogue, a ball and a
+ * player, a caption; region-of-interest encoding, multi-subject reframing and annotation all start from this table, and the one
+ * window of p3d_video_reframe merges two subjects into the heavier).  OFF until called: every other entry point issues what it issued
+ * before and returns the same bits.  PARITY UNPINNED: the reference has nothing of the kind; this text is the contract and
+ * tests/regions_ref.py replays it in numpy.  Integer arithmetic throughout: no order can show, and every test holds to 0.
+ * Per frame: s [H][W] bytes, the saliency map; a gate g in 1 .. 255; a connectivity c, 4 or 8; a smallest area a >= 1; K in
+ * 1 .. P3D_REGIONS_MAX regions kept; link in {0, 1}.
+ *   CONFIG      five ints in the order of the P3D_REGIONS_* indices below (an array: `const int cfg[5]`, as the shots configuration
+ *               is): gate, connectivity, min_area, max_regions (K), link.
+ *   LIMITS      1 <= n <= 65535 maps a call; H * W <= 2^23.  The largest mass is 255 * 2^23 < 2^31, so every field of a region fits
+ *               int32_t; the moment sums SY and SX are 64-bit.
+ *   FOREGROUND  a pixel is foreground when s(y, x) >= g.  g >= 1: every foreground pixel weighs at least 1 and no region has mass 0.
+ *   COMPONENT   a maximal set of foreground pixels connected through 4-neighbours (c = 4) or 8-neighbours (c = 8).  Its ROOT is the
+ *               smallest linear index y * W + x among its pixels.
+ *   STATISTICS  per component: AREA the pixel count; MASS the sum of the bytes; Y0, X0, Y1, X1 the bounding box, inclusive; PEAK the
+ *               largest byte; PEAK_Y, PEAK_X the smallest linear index among the pixels with that byte;
+ *               CY = (2 * SY + MASS) / (2 * MASS) with SY = the sum of s(y, x) * y (64-bit, integer division), CX the same with x:
+ *               the mass centre rounded to nearest, half up.  It always lies inside the box (not always on a pixel of the region).
+ *   SELECTION   only components with AREA >= a are kept; they are ordered by MASS descending, then ROOT ascending; the first K are the
+ *               frame's regions, and a region's position in that order is its RANK, 0 .. K - 1.  counts [n][3] holds per frame the
+ *               components found, those with AREA >= a, and the regions kept (the smaller of the second count and K).
+ *   LABELS      labels [n][H][W] bytes: the rank of the kept region the pixel belongs to, or 255 (background, regions too small,
+ *               regions beyond K).
+ *   LINK        (link = 1) runs over the frames OF THE CALL.  An optional shot table, in frames of the call (starts [n_shots],
+ *               ascending from 0), splits the call into shots; frame 0 of the call and the first frame of every shot are STARTS.  For a
+ *               frame f that is not a start: O[j][i] = the number of pixels with labels_f = j and labels_{f-1} = i; PREV(j) = the i
+ *               with the largest O[j][i] >= 1, among equals the smallest i, or -1 without any overlap; OVERLAP(j) = O[j][PREV(j)], or
+ *               0.  IDs come from one counter that starts at 0 at the call's first frame, never resets and runs in frame order.  At
+ *               a start every region takes a new ID, in rank order.  Elsewhere, for every region i of frame f - 1 that is some
+ *               PREV(j): its HEIR is, among the j with PREV(j) = i, the one with the largest O[j][i], among equals the smallest j; the
+ *               heir takes ID(i).  Every other region of f takes a new ID, in rank order (a region with no overlap, the smaller
+ *               part of a split).  A region has one PREV and so inherits at most one ID, and an ID is held by at most one region per
+ *               frame; a merged region keeps the ID of the region it overlaps most.  A region that vanishes for a frame comes
+ *               back with a new ID.  With link = 0: ID = PREV = -1 and OVERLAP = 0.
+ *   RECORD      regions [n][K][P3D_REGION_FIELDS] int32_t, the fields in the order of the P3D_REGION_* indices below.  Slots beyond
+ *               the frame's kept count hold -1 in every field.
+ * p3d_regions_u8     op level, host arrays: sal [n][H][W], starts [n_shots] or NULL (then n_shots = 0) -> regions, counts (or NULL),
+ *                    labels (or NULL).
+ * p3d_video_regions  the regions of frames first .. first + n - 1 of the open video at H x W.  The saliency bytes are, bit for bit,
+ *                    what p3d_video_maps_u8(first, n, scale, H, W) returns under the handle's current settings; maps_out (or NULL)
+ *                    receives them.  The video's shot table, if one is set, is cut to the range exactly as p3d_video_reframe cuts
+ *                    it.  Validated as p3d_video_maps_u8 validates, plus cfg, LIMITS and regions == NULL, all before any launch,
+ *                    upload or scratch request: a refusal changes nothing.  stage_ms (or NULL) [3]: 0, the maps' chain, the regions
+ *                    launches.  Returns synchronised.
+ * TEST HOOKS (tests/test_gpu_regions.py):
+ * p3d_debug_regions_u8  the same launch description with every device buffer, the scratch included, between guards: sal starts
+ *                    `offset` bytes (0 .. 15) past a 16-byte boundary, labels (5 offset) mod 16 bytes past one; -1 if a guard or an
+ *                    input changed.
+ * p3d_debug_regions_plan  host only, no HIP call: the tile of the labelling (a block a tile), the tiles a map, the maps whose tables
+ *                    are held at a time (a call of more maps runs in chunks of that many) and the bytes of scratch, for a call with
+ *                    the given K, link and labels (0 or 1: whether the label maps are asked for). */
+#define P3D_REGIONS_MAX 64
+#define P3D_REGION_FIELDS 15
+enum { P3D_REGION_ROOT = 0, P3D_REGION_AREA = 1, P3D_REGION_MASS = 2, P3D_REGION_Y0 = 3, P3D_REGION_X0 = 4, P3D_REGION_Y1 = 5, P3D_REGION_X1 = 6,
+       P3D_REGION_PEAK = 7, P3D_REGION_PEAK_Y = 8, P3D_REGION_PEAK_X = 9, P3D_REGION_CY = 10, P3D_REGION_CX = 11, P3D_REGION_ID = 12,
+       P3D_REGION_PREV = 13, P3D_REGION_OVERLAP = 14 };
+enum { P3D_REGIONS_GATE = 0, P3D_REGIONS_CONNECTIVITY = 1, P3D_REGIONS_MIN_AREA = 2, P3D_REGIONS_MAX_REGIONS = 3, P3D_REGIONS_LINK = 4 };
+int p3d_regions_u8(int device, const unsigned char* sal, int n, int H, int W, const int cfg[5], const int32_t* starts /* may be NULL */,
+                   int n_shots, int32_t* regions /* [n][max_regions][15] */, int32_t* counts /* [n][3], may be NULL */,
+                   unsigned char* labels /* [n][H][W], may be NULL */);
+int p3d_video_regions(p3d_handle* h, int first, int n, float scale, int H, int W, const int cfg[5], int32_t* regions,
+                      int32_t* counts /* may be NULL */, unsigned char* labels /* may be NULL */, unsigned char* maps_out /* may be NULL */,
+                      double* stage_ms /* may be NULL, [3] */);
+int p3d_debug_regions_u8(int device, const unsigned char* sal, int n, int H, int W, const int cfg[5], const int32_t* starts, int n_shots,
+                         int offset, int32_t* regions, int32_t* counts, unsigned char* labels);
+int p3d_debug_regions_plan(int H, int W, int n, int max_regions, int link, int labels, int* tile_h, int* tile_w, int* tiles_per_map,
+                           int* maps_per_chunk, int64_t* scratch_bytes);
+
 /* ---- Shot boundaries of 8-bit frames (an ADDITION: the videos people reframe are edited, and a filter along the frame axis that
  * runs across a hard cut blends two unrelated scenes; automatic reframing tools find the cuts first).  OFF until called: every other
  * entry point issues what it issued before and returns the same bits.  PARITY UNPINNED: the reference's clips are single takes and

@@ -796,12 +796,33 @@ struct ReframeStage : ByteStage {
     void launch(hipStream_t s, const unsigned char* sal, unsigned*) override;
     void results(hipStream_t s) override;
 };
+// What one labelling of n maps of H x W bytes asks for: regions, counts and labels on the host, whatever is null is not copied back.
+struct RegionsCfg { int gate, connectivity, min_area, max_regions, link; };      // CONFIG's five ints under their names
+struct RegionsRequest {
+    const char* who; int n, H, W;
+    const RegionsCfg* cfg = nullptr;
+    int32_t* regions = nullptr; int32_t* counts = nullptr; unsigned char* labels = nullptr;
+    bool timed = false;
+    const int32_t* starts = nullptr; int n_shots = 0;      // host: a shot table in frames of the call (shots_table_check has passed it), or none
+};
+// The launches of regions.hip behind some device bytes, with no arrival counters: they hand results to one another from launch to
+// launch.  regions_check has passed cfg and the shape before one is built.
+struct RegionsStage : ByteStage {
+    const RegionsRequest r;
+    RegionsArgs a;
+    int32_t* dstarts = nullptr;
+    explicit RegionsStage(const RegionsRequest& r);
+    void carve(Carve& c) override;
+    void upload(hipStream_t s) override;
+    void launch(hipStream_t s, const unsigned char* sal, unsigned*) override;
+    void results(hipStream_t s) override;
+};
 // gen_pred.py's write-out of `maps` maps that live on the device, for p3d_pred_maps_u8 and p3d_video_maps_u8: the bytes, the
 // scratch of p3d_set_postprocess's stage and `extra` floats of the caller's share one slab of the stream's scratch.  sources runs
 // inside the device stage's time: it queues whatever makes the maps readable and names them as runs of maps of ph x pw pixels.
 // Off: one double-precision p3d_resize_u8 per run; on: the float32 resize / blur / normalise / byte sequence, P3D_POST_CHUNK maps
 // at a time.  Ends synchronised; stage_ms as p3d_pred_maps_u8's.
-// A stage (ByteStage: score, render, reframe) takes the device bytes where they are instead of a copy of the chain: its buffers are
+// A stage (ByteStage: score, render, reframe, regions) takes the device bytes where they are instead of a copy of the chain: its buffers are
 // carved after the chain's in the same layout, its upload is queued ahead of the sources, its launches behind the chain with the
 // bytes and counters() zeroed arrival counters of its own (after the chain's), its results (the copies back to the host) behind
 // that; out may then be NULL (the bytes stay on the device) and, timed, its ms [3] receives the times of the upload, of the device
@@ -1802,7 +1823,7 @@ const unsigned char* kept_source(const p3d_handle* h, const char* who, int first
 void need_kept_source(const p3d_handle* h, const char* who) {
     if (!h->video.source) throw P3dError(std::string(who) + ": no frames are given and the video keeps no source (p3d_video_keep_source before the first p3d_video_put_frames_u8)");
 }
-// p3d_video_score, _score_auc, _render and _reframe behind the checks of their arguments: at most 65535 of the video's frames
+// p3d_video_score, _score_auc, _render, _reframe and _regions behind the checks of their arguments: at most 65535 of the video's frames
 // through the maps' chain, the stage behind its bytes.  make builds the stage once the source has passed, so that what the stage
 // (or the kept source it reads) refuses is refused after it.  stage_ms (null, or n_ms >= 3 values): zeroed, then the stage's ms.
 void video_stage_run(p3d_handle* h, const char* who, int first, int n, float scale, unsigned char* maps_out, double* stage_ms, int n_ms,
@@ -2179,6 +2200,159 @@ int p3d_video_reframe(p3d_handle* h, int first, int n, float scale, int H, int W
         return *stage;
     });
     if (stage_ms && !frames) stage_ms[0] = 0.0;      // (nothing went up)
+    API_END
+}
+
+}  // extern "C"
+namespace {
+// ---- salient regions of 8-bit maps (regions.hip; the law in include/p3d_hip.h): one check, one table of buffer sizes and one launch
+// description for p3d_regions_u8, the regions stage and p3d_debug_regions_u8 --------------------------------------------------------
+void shots_table_check(const char* who, const int32_t* starts, int n_shots, int F);      // (net_shots.inc)
+RegionsCfg regions_check(const char* who, const int* cfg5, int n, int H, int W, const void* regions) {
+    if (!cfg5 || !regions) throw P3dError("null argument");
+    const RegionsCfg parsed{cfg5[P3D_REGIONS_GATE], cfg5[P3D_REGIONS_CONNECTIVITY], cfg5[P3D_REGIONS_MIN_AREA], cfg5[P3D_REGIONS_MAX_REGIONS], cfg5[P3D_REGIONS_LINK]};
+    const RegionsCfg* cfg = &parsed;
+    map_shape_check(who, n, H, W, P3D_REGIONS_MAX_PIXELS, "2^23, the bound that keeps a mass in 32 bits");
+    if (cfg->gate < 1 || cfg->gate > 255) throw P3dError(std::string(who) + ": the gate is a level, 1 .. 255");
+    if (cfg->connectivity != 4 && cfg->connectivity != 8) throw P3dError(std::string(who) + ": the connectivity is 4 or 8, not " + std::to_string(cfg->connectivity));
+    if (cfg->min_area < 1) throw P3dError(std::string(who) + ": the smallest area is at least 1 pixel");
+    if (cfg->max_regions < 1 || cfg->max_regions > P3D_REGIONS_MAX)
+        throw P3dError(std::string(who) + ": max_regions is 1 .. " + std::to_string(P3D_REGIONS_MAX) + ", not " + std::to_string(cfg->max_regions));
+    if (cfg->link != 0 && cfg->link != 1) throw P3dError(std::string(who) + ": link is 0 or 1");
+    return parsed;
+}
+RegionsArgs regions_args(const RegionsCfg& cfg, int n, int H, int W, bool labels) {
+    RegionsArgs a;
+    a.n = n; a.H = H; a.W = W; a.gate = cfg.gate; a.conn = cfg.connectivity; a.min_area = cfg.min_area; a.K = cfg.max_regions; a.link = cfg.link;
+    a.lab_full = labels ? 1 : 0;
+    const RegionsPlan p = p3d_regions_plan(H, W, n, a.K, a.link, a.lab_full);
+    a.maps_per_chunk = p.maps_per_chunk; a.tiles_y = p.tiles_y; a.tiles_x = p.tiles_x; a.slots = p.slots;
+    return a;
+}
+// Elements of the buffers of one labelling: what the stage carves and what the hook puts between guards
+struct RegionsSizes {
+    size_t sal, records, counts; RegionsPlan p;
+    explicit RegionsSizes(const RegionsArgs& a)
+        : sal((size_t)a.n * (size_t)a.H * (size_t)a.W), records((size_t)a.n * (size_t)a.K * P3D_REGION_FIELDS), counts((size_t)a.n * 3),
+          p(p3d_regions_plan(a.H, a.W, a.n, a.K, a.link, a.lab_full)) {}
+};
+
+// ---- the regions stage (declared above maps_u8_chain) -----------------------------------------------------------------------------
+RegionsStage::RegionsStage(const RegionsRequest& r_) : ByteStage(r_), r(r_), a(regions_args(*r_.cfg, r_.n, r_.H, r_.W, r_.labels != nullptr)) {}
+void RegionsStage::carve(Carve& c) {
+    const RegionsSizes z(a);
+    a.regions = c.take<int32_t>(z.records);
+    a.counts = c.take<int32_t>(z.counts);
+    a.parent = c.take<unsigned>((size_t)z.p.parent_elems);
+    a.tab32 = c.take<unsigned>((size_t)z.p.tab32_elems);
+    a.tab64 = c.take<unsigned long long>((size_t)z.p.tab64_elems);
+    a.rank = c.take<unsigned char>((size_t)z.p.rank_elems);
+    a.keys = c.take<unsigned long long>((size_t)z.p.key_elems);
+    a.cnt = c.take<unsigned>((size_t)z.p.cnt_elems);
+    a.ovl = z.p.ovl_elems ? c.take<unsigned>((size_t)z.p.ovl_elems) : nullptr;
+    a.state = z.p.state_elems ? c.take<int32_t>((size_t)z.p.state_elems) : nullptr;
+    a.lab = z.p.lab_elems ? c.take<unsigned char>((size_t)z.p.lab_elems) : nullptr;
+    dstarts = r.starts ? c.take<int32_t>((size_t)r.n_shots) : nullptr;
+}
+void RegionsStage::upload(hipStream_t s) {
+    if (dstarts) HIPCHECK(hipMemcpyAsync(dstarts, r.starts, (size_t)r.n_shots * sizeof(int32_t), hipMemcpyHostToDevice, s));
+}
+void RegionsStage::launch(hipStream_t s, const unsigned char* sal, unsigned*) {
+    a.sal = sal; a.starts = dstarts; a.n_shots = dstarts ? r.n_shots : 0;
+    HIPCHECK(p3d_regions_launch(a, s));
+}
+void RegionsStage::results(hipStream_t s) {
+    const RegionsSizes z(a);
+    HIPCHECK(hipMemcpyAsync(r.regions, a.regions, z.records * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (r.counts) HIPCHECK(hipMemcpyAsync(r.counts, a.counts, z.counts * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (r.labels) HIPCHECK(hipMemcpyAsync(r.labels, a.lab, z.sal, hipMemcpyDeviceToHost, s));
+}
+}  // namespace
+extern "C" {
+
+int p3d_regions_u8(int device, const unsigned char* sal, int n, int H, int W, const int cfg[5], const int32_t* starts, int n_shots,
+                   int32_t* regions, int32_t* counts, unsigned char* labels) {
+    API_BEGIN
+    const char* who = "regions_u8";
+    if (!sal) throw P3dError("null argument");
+    const RegionsCfg rc = regions_check(who, cfg, n, H, W, regions);
+    if (starts || n_shots) shots_table_check(who, starts, n_shots, n);
+    metric_args(device, sal, cfg, 1, 1, regions);
+    RegionsRequest r{who, n, H, W};
+    r.cfg = &rc; r.regions = regions; r.counts = counts; r.labels = labels; r.starts = starts; r.n_shots = n_shots;
+    RegionsStage stage(r);
+    stage_on_host_bytes(stage, sal);
+    API_END
+}
+
+int p3d_debug_regions_u8(int device, const unsigned char* sal, int n, int H, int W, const int cfg[5], const int32_t* starts, int n_shots,
+                         int offset, int32_t* regions, int32_t* counts, unsigned char* labels) {
+    API_BEGIN
+    const char* who = "debug_regions_u8";
+    if (!sal) throw P3dError("null argument");
+    const RegionsCfg rc = regions_check(who, cfg, n, H, W, regions);
+    if (starts || n_shots) shots_table_check(who, starts, n_shots, n);
+    if (offset < 0 || offset > 15) throw P3dError(std::string(who) + ": offset in [0, 15]");
+    metric_args(device, sal, cfg, 1, 1, regions);
+    RegionsArgs a = regions_args(rc, n, H, W, labels != nullptr);
+    const RegionsSizes sz(a);
+    const RegionsPlan& p = sz.p;
+    // guards of 16 elements keep a 16-byte boundary at the data's start; the two byte buffers are then shifted
+    Guarded<unsigned char> ds(sz.sal, 16, (size_t)offset, sal), dlab((size_t)p.lab_elems, 16, (size_t)(5 * offset % 16), nullptr),
+        drank((size_t)p.rank_elems, 16, 0, nullptr);
+    Guarded<int32_t> drec(sz.records, 16, 0, nullptr), dcounts(sz.counts, 16, 0, nullptr), dstate((size_t)p.state_elems, 16, 0, nullptr),
+        dst((size_t)n_shots, 16, 0, starts);
+    Guarded<unsigned> dpar((size_t)p.parent_elems, 16, 0, nullptr), dt32((size_t)p.tab32_elems, 16, 0, nullptr),
+        dcnt((size_t)p.cnt_elems, 16, 0, nullptr), dovl((size_t)p.ovl_elems, 16, 0, nullptr);
+    Guarded<unsigned long long> dt64((size_t)p.tab64_elems, 16, 0, nullptr), dkeys((size_t)p.key_elems, 16, 0, nullptr);
+    a.sal = ds.data(); a.regions = drec.data(); a.counts = dcounts.data(); a.lab = p.lab_elems ? dlab.data() : nullptr;
+    a.parent = dpar.data(); a.tab32 = dt32.data(); a.tab64 = dt64.data(); a.rank = drank.data(); a.keys = dkeys.data();
+    a.cnt = dcnt.data(); a.ovl = p.ovl_elems ? dovl.data() : nullptr; a.state = p.state_elems ? dstate.data() : nullptr;
+    a.starts = n_shots ? dst.data() : nullptr; a.n_shots = n_shots;
+    HIPCHECK(p3d_regions_launch(a, nullptr));
+    drec.back(regions, who); dcounts.back(counts, who);
+    dlab.back(labels, who);
+    dpar.back(nullptr, who); dt32.back(nullptr, who); dt64.back(nullptr, who); drank.back(nullptr, who);
+    dkeys.back(nullptr, who); dcnt.back(nullptr, who); dovl.back(nullptr, who); dstate.back(nullptr, who);
+    ds.unchanged(who); dst.unchanged(who);
+    API_END
+}
+
+int p3d_debug_regions_plan(int H, int W, int n, int max_regions, int link, int labels, int* tile_h, int* tile_w, int* tiles_per_map,
+                           int* maps_per_chunk, int64_t* scratch_bytes) {
+    API_BEGIN
+    if (!tile_h || !tile_w || !tiles_per_map || !maps_per_chunk || !scratch_bytes) throw P3dError("null argument");
+    if (H < 1 || W < 1 || (long long)H * W > P3D_REGIONS_MAX_PIXELS || n < 1 || n > 65535 || max_regions < 1 || max_regions > P3D_REGIONS_MAX ||
+        (link != 0 && link != 1) || (labels != 0 && labels != 1))
+        throw P3dError("debug_regions_plan: 1 <= H * W <= 2^23, 1 .. 65535 maps, 1 .. 64 regions, link and labels 0 or 1");
+    const RegionsPlan p = p3d_regions_plan(H, W, n, max_regions, link, labels);
+    *tile_h = p.tile_h; *tile_w = p.tile_w; *tiles_per_map = p.tiles_y * p.tiles_x; *maps_per_chunk = p.maps_per_chunk;
+    *scratch_bytes = (int64_t)p.scratch_bytes;
+    API_END
+}
+
+int p3d_video_regions(p3d_handle* h, int first, int n, float scale, int H, int W, const int cfg[5], int32_t* regions, int32_t* counts,
+                      unsigned char* labels, unsigned char* maps_out, double* stage_ms) {
+    API_BEGIN
+    const char* who = "video_regions";
+    if (!h) throw P3dError("null argument");
+    h->video.need_open(who);
+    const RegionsCfg rc = regions_check(who, cfg, std::max(1, std::min(n, 65535)), H, W, regions);
+    RegionsRequest r{who, n, H, W};
+    r.cfg = &rc; r.regions = regions; r.counts = counts; r.labels = labels; r.timed = stage_ms != nullptr;
+    std::unique_ptr<RegionsStage> stage;
+    std::vector<int32_t> shots;                            // the installed table in frames of the call, cut as p3d_video_reframe cuts it
+    video_stage_run(h, who, first, n, scale, maps_out, stage_ms, 3, [&]() -> ByteStage& {
+        if (!h->video.shots.empty()) {
+            shots.push_back(0);
+            for (int32_t st : h->video.shots)
+                if (st > first && st < first + n) shots.push_back(st - first);
+            r.starts = shots.data(); r.n_shots = (int)shots.size();
+        }
+        stage.reset(new RegionsStage(r));
+        return *stage;
+    });
+    if (stage_ms) stage_ms[0] = 0.0;                   // (nothing but a shot table went up)
     API_END
 }
 

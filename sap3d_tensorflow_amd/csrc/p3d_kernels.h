@@ -1157,6 +1157,41 @@ struct ReframeArgs {
 };
 hipError_t p3d_reframe_launch(const ReframeArgs& a, hipStream_t s);
 
+// ---- connected regions of 8-bit maps (regions.hip; p3d_video_regions / p3d_regions_u8, the law in include/p3d_hip.h) ----
+// One launch sequence on n maps of H x W bytes: sal [n][H][W] -> regions [n][K][P3D_REGIONS_NFIELDS] int32, counts [n][3] int32 and
+// label maps (lab); every buffer device memory.  A root's statistics live in tables indexed by SLOT(root) = y * ceil(W / 2) + x / 2
+// (two roots never share a slot: the pixels 2k and 2k + 1 of a row are neighbours), `slots` of them a map.  Scratch, for
+// p3d_regions_plan's maps_per_chunk maps at a time: parent [maps][H W] words (a foreground pixel's root; the background's entries are
+// never touched), tab32 [maps][7][slots] (area, mass, y0, x0, y1, x1, peak key), tab64 [maps][2][slots] (SY, SX), rank [maps][slots]
+// bytes, keys [maps][slots] (the roots in arrival order, then their selection keys), cnt [maps][2] (components, regions kept), ovl
+// [maps][K][K] and state [2 + K] (link only).  lab: [n][H W] bytes when lab_full (the caller wants the label maps), else, under link,
+// a ring of maps_per_chunk + 1 maps with frame f in slot (f + 1) mod that; null when neither.
+// Refused (hipErrorInvalidValue): a missing buffer, n outside [1, 65535], H * W outside [1, 2^23], a gate outside [1, 255], a
+// connectivity other than 4 or 8, min_area < 1, K outside [1, 64], a plan other than p3d_regions_plan's, starts without n_shots in
+// 1 .. n or n_shots without starts.
+constexpr int P3D_REGIONS_MAX_PIXELS = 1 << 23;               // 255 * 2^23 < 2^31: every field of a record fits int32
+constexpr int P3D_REGIONS_K = 64;                             // P3D_REGIONS_MAX of the header
+constexpr int P3D_REGIONS_NFIELDS = 15;                       // P3D_REGION_FIELDS of the header
+constexpr int P3D_REGIONS_CHUNK = 16;                         // at most this many maps' tables at a time
+constexpr long long P3D_REGIONS_SCRATCH_BYTES = 512LL << 20;  // and at most this many bytes of them (never less than one map's): 16 maps of 1080 x 960
+constexpr int P3D_REGIONS_TAB32 = 7, P3D_REGIONS_TAB64 = 2;   // 32- and 64-bit statistics a slot
+constexpr int REGIONS_TILE_H = 32, REGIONS_TILE_W = 64;       // the labelling's tile: a wave a row, a lane a column
+struct RegionsPlan {
+    int tile_h = 0, tile_w = 0, tiles_y = 0, tiles_x = 0, maps_per_chunk = 0;
+    long long slots = 0, parent_elems = 0, tab32_elems = 0, tab64_elems = 0, rank_elems = 0, key_elems = 0, cnt_elems = 0,
+              ovl_elems = 0, state_elems = 0, lab_elems = 0, scratch_bytes = 0;
+};
+RegionsPlan p3d_regions_plan(int H, int W, int n, int K, int link, int lab_full);
+struct RegionsArgs {
+    const unsigned char* sal = nullptr; int32_t* regions = nullptr; int32_t* counts = nullptr; unsigned char* lab = nullptr;
+    unsigned* parent = nullptr; unsigned* tab32 = nullptr; unsigned long long* tab64 = nullptr; unsigned char* rank = nullptr;
+    unsigned long long* keys = nullptr; unsigned* cnt = nullptr; unsigned* ovl = nullptr; int32_t* state = nullptr;
+    int n = 0, H = 0, W = 0, gate = 0, conn = 0, min_area = 0, K = 0, link = 0, lab_full = 0;
+    int maps_per_chunk = 0, tiles_y = 0, tiles_x = 0; long long slots = 0;      // p3d_regions_plan(H, W, n, K, link, lab_full)
+    const int32_t* starts = nullptr; int n_shots = 0;        // a shot table in frames of the call (device; ascending from 0), or none
+};
+hipError_t p3d_regions_launch(const RegionsArgs& a, hipStream_t s);
+
 // ---- shot boundaries of 8-bit frames (shots.hip; p3d_shot_distances_u8 / p3d_shot_cuts, the law in include/p3d_hip.h) ----
 // The cut signal of n frames [n][H][W][3] of device bytes: D [n] device words, D_0 = 0, D_f the distance of frame f's cell
 // histograms from frame f - 1's.  tabs is scratch of (frames_per_chunk + 1) tables of table_words words on a 16-byte boundary: slot 0

@@ -677,6 +677,51 @@ def reframe(sal, frames, crop, gate=0, smooth=0, device=0, offset=None, shots=No
     return track, raw, mass, (out if f is not None else None)
 
 
+def regions_plan(H, W, n=1, max_regions=64, link=False, labels=False):
+    """Test hook (p3d_debug_regions_plan, host only): dict(tile_h, tile_w, tiles_per_map, maps_per_chunk, scratch_bytes) of the
+    regions launches for n maps of H x W."""
+    th, tw, t, m, s = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int64(0)
+    check(lib().p3d_debug_regions_plan(int(H), int(W), int(n), int(max_regions), int(bool(link)), int(bool(labels)), C.byref(th), C.byref(tw),
+                                       C.byref(t), C.byref(m), C.byref(s)))
+    return dict(tile_h=th.value, tile_w=tw.value, tiles_per_map=t.value, maps_per_chunk=m.value, scratch_bytes=s.value)
+
+
+def regions_cfg(gate, connectivity=8, min_area=1, max_regions=64, link=False):
+    """The five ints of include/p3d_hip.h's CONFIG ("Salient regions of 8-bit maps") in the order of the P3D_REGIONS_* indices."""
+    from . import _lib
+    cfg = (C.c_int * 5)()
+    for k, v in ((_lib.P3D_REGIONS_GATE, gate), (_lib.P3D_REGIONS_CONNECTIVITY, connectivity), (_lib.P3D_REGIONS_MIN_AREA, min_area),
+                 (_lib.P3D_REGIONS_MAX_REGIONS, max_regions), (_lib.P3D_REGIONS_LINK, bool(link))):
+        cfg[k] = int(v)
+    return cfg
+
+
+def regions(sal, gate, connectivity=8, min_area=1, max_regions=None, link=False, shots=None, labels=False, device=0, offset=None):
+    """The connected regions of gated saliency maps on the device (p3d_regions_u8; include/p3d_hip.h, "Salient regions of 8-bit
+    maps"): maps uint8 [n, H, W] (or [H, W]: one frame) -> (regions int32 [n, K, P3D_REGION_FIELDS], counts int32 [n, 3], labels uint8
+    [n, H, W] or None).  K = max_regions (default P3D_REGIONS_MAX).  link: IDs carried from frame to frame by overlap, inside the
+    shots of `shots` (starts ascending from 0) where given.  offset (0 .. 15): the test hook p3d_debug_regions_u8, every device
+    buffer between guards and the byte buffers shifted off a 16-byte boundary."""
+    from . import _lib
+    s3, _, _ = _reframe_shape(sal, 1)
+    n, H, W = s3.shape
+    K = _lib.P3D_REGIONS_MAX if max_regions is None else int(max_regions)
+    cfg = regions_cfg(gate, connectivity, min_area, K, link)
+    ok = 1 <= K <= _lib.P3D_REGIONS_MAX                      # (the library refuses the rest before it writes)
+    rec = np.empty((n, K, _lib.P3D_REGION_FIELDS) if ok else (1,), np.int32)
+    counts = np.empty((n, 3), np.int32)
+    lab = np.empty((n, H, W), np.uint8) if labels else None
+    u8, i32 = C.POINTER(C.c_ubyte), C.POINTER(C.c_int32)
+    st = None if shots is None else np.ascontiguousarray(shots, np.int32).ravel()
+    head = (device, s3.ctypes.data_as(u8), n, H, W, cfg, None if st is None else st.ctypes.data_as(i32), 0 if st is None else len(st))
+    tail = (rec.ctypes.data_as(i32), counts.ctypes.data_as(i32), None if lab is None else lab.ctypes.data_as(u8))
+    if offset is None:
+        check(lib().p3d_regions_u8(*head, *tail))
+    else:
+        check(lib().p3d_debug_regions_u8(*head, int(offset), *tail))
+    return rec, counts, lab
+
+
 def _shot_frames(frames):
     f = np.ascontiguousarray(frames)
     if f.dtype != np.uint8 or f.ndim != 4 or f.shape[3] != 3 or f.size == 0:

@@ -1035,6 +1035,36 @@ class P3DSession:
             res["maps"] = maps
         return res
 
+    def video_regions(self, first, n, size, gate, connectivity=8, min_area=1, max_regions=None, link=False, scale=255., with_labels=False,
+                      with_maps=False, timed=False):
+        """The salient regions of frames first .. first + n - 1 of the open video, on the device (an addition): the connected
+        regions of the pixels at or above `gate` in video_maps_u8's bytes at `size`, per frame the max_regions heaviest of at least
+        min_area pixels -> dict(regions int32 [n, K, P3D_REGION_FIELDS], counts int32 [n, 3] (found, large enough, kept)).  link:
+        regions carry an ID from frame to frame by overlap WITHIN THIS CALL and inside the shots of video_set_shots' table.
+        with_labels / with_maps add labels uint8 [n, H, W] (a region's rank, 255 elsewhere) and maps uint8 [n, H, W].  timed: HIP-event
+        times are left in `last_regions_ms` (device = the maps' chain, regions).  include/p3d_hip.h holds the exact rules."""
+        from . import dataflow
+        H, W = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
+        n = max(int(n), 0)
+        K = _lib.P3D_REGIONS_MAX if max_regions is None else int(max_regions)
+        valid = H >= 1 and W >= 1 and H * W <= 2 ** 23 and 1 <= K <= _lib.P3D_REGIONS_MAX      # (the library refuses the rest)
+        cfg = dataflow.regions_cfg(gate, connectivity, min_area, K, link)
+        rec = np.empty((n, K, _lib.P3D_REGION_FIELDS) if valid else (1,), np.int32)
+        counts = np.empty((n, 3), np.int32)
+        lab = np.empty((n, H, W) if valid else (0,), np.uint8) if with_labels else None
+        maps = np.empty((n, H, W) if valid else (0,), np.uint8) if with_maps else None
+        ms = (C.c_double * 3)()
+        check(lib().p3d_video_regions(self._h, int(first), n, float(scale), H, W, cfg, _ptr(rec, _lib._i32p), _ptr(counts, _lib._i32p),
+                                      _ptr(lab, _lib._u8p), _ptr(maps, _lib._u8p), ms if timed else None))
+        if timed:
+            self.last_regions_ms = dict(device=ms[1], regions=ms[2])
+        res = dict(regions=rec, counts=counts)
+        if with_labels:
+            res["labels"] = lab
+        if with_maps:
+            res["maps"] = maps
+        return res
+
     def video_detect_shots(self, grid=(2, 2), threshold=250, window=2, ratio=512, min_length=3, install=True, with_signal=False):
         """Find the hard cuts of the open video on the device (an addition), from the source kept by video_keep_source: per frame a
         grid = (gy, gx) of cell histograms of the B, G, R bytes, D_f their distance from the frame before; frame f starts a shot
