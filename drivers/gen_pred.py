@@ -48,7 +48,13 @@ DIR/<video>/regions.npy, int32 [F, K, 15], and counts.npy, int32 [F, 3]: the con
 `--regions-gate` (`--regions-connectivity` 4 or 8), the `--regions-max` heaviest of at least `--regions-min-area` pixels a frame,
 each with its box, area, mass, peak and centre (P3DSession.video_regions at `--size`, one call per video; the fields are
 include/p3d_hip.h's P3D_REGION_*); `--regions-link` carries an ID from frame to frame by overlap, inside the shots of `--shots`;
-`--regions-labels` also writes labels.npy, uint8 [F, H, W]."""
+`--regions-labels` also writes labels.npy, uint8 [F, H, W].  `--qpmap DIR` (an addition, needs `--resident`) writes
+DIR/<video>/qp.npy, int32 [F, Hb, Wb]: one signed quantiser offset per `--qp-block` x `--qp-block` coding block of every map at
+`--size`, lower where the map is salient (P3DSession.video_qpmap, one call per video; the law is include/p3d_hip.h's "QP maps of 8-bit
+maps"), limited from frame to frame by `--qp-fall` / `--qp-rise` inside the shots of `--shots`; stats.npy, int32 [F, 4] (the smallest
+and largest offset, the area-weighted sums before and after the balance), on `--qp-levels` levels.npy, uint8 [F, Hb, Wb], and qp.txt,
+one line a frame: the frame's number from 1, then its Hb * Wb offsets in raster order, separated by spaces.  That layout is this
+driver's own; no particular encoder's input format is promised."""
 import argparse
 import glob
 import os
@@ -505,6 +511,31 @@ def parse_args(argv=None):
                    "inside the shots of --shots")
     p.add_argument("--regions-labels", action="store_true", help="[addition] --regions: also write DIR/<video>/labels.npy, uint8 [F, H, W]: a "
                    "region's rank, 255 elsewhere")
+    p.add_argument("--qpmap", type=str, default="", metavar="DIR", help="[addition] needs --resident: one signed quantiser offset per coding "
+                   "block of every map, lower where the map is salient, on the device (P3DSession.video_qpmap, one call per video, at "
+                   "--size); writes DIR/<video>/qp.npy, int32 [F, Hb, Wb], stats.npy, int32 [F, 4], and qp.txt, one line a frame: the frame's "
+                   "number from 1, then its Hb * Wb offsets in raster order, separated by spaces.  The layout is this driver's own: no "
+                   "particular encoder's input format is promised.  Uses the table of --shots when one is set")
+    p.add_argument("--qp-block", type=int, default=16, metavar="B", help="[addition] --qpmap: the coding block's side, 8, 16, 32, 64 or 128 pixels (16)")
+    p.add_argument("--qp-peak-weight", type=int, default=128, metavar="Q8", help="[addition] --qpmap: a block's level is Q8 / 256 of its largest "
+                   "byte and the rest its mean, 0 .. 256 (128)")
+    p.add_argument("--qp-dilate", type=int, default=0, metavar="BLOCKS", help="[addition] --qpmap: a block takes the largest level within this "
+                   "many blocks, 0 .. 8 (0)")
+    p.add_argument("--qp-fall", type=int, default=0, metavar="STEP", help="[addition] --qpmap: a block's offset falls by at most STEP a frame, "
+                   "0 .. 254, 0: unlimited (0)")
+    p.add_argument("--qp-rise", type=int, default=0, metavar="STEP", help="[addition] --qpmap: a block's offset rises by at most STEP a frame, "
+                   "0 .. 254, 0: unlimited (0)")
+    p.add_argument("--qp-min", type=int, default=-12, metavar="Q", help="[addition] --qpmap: the offset of the most salient level, and the clamp's "
+                   "lower end, -127 .. 127 (-12)")
+    p.add_argument("--qp-max", type=int, default=6, metavar="Q", help="[addition] --qpmap: the offset of the levels below --qp-gate, and the clamp's "
+                   "upper end, -127 .. 127 (6)")
+    p.add_argument("--qp-gate", type=int, default=0, metavar="LEVEL", help="[addition] --qpmap: levels below it take --qp-max, 0 .. 254 (0)")
+    p.add_argument("--qp-gamma", type=float, default=1.0, metavar="G", help="[addition] --qpmap: the law's exponent, > 0 (1: a straight line "
+                   "from --qp-max at the gate to --qp-min at level 255)")
+    p.add_argument("--qp-no-balance", action="store_true", help="[addition] --qpmap: do not shift every frame's offsets so that their "
+                   "area-weighted mean is 0")
+    p.add_argument("--qp-levels", action="store_true", help="[addition] --qpmap: also write DIR/<video>/levels.npy, uint8 [F, Hb, Wb]: the "
+                   "blocks' dilated levels")
     p.add_argument("--shots", type=str, default="", metavar="detect|FILE.npy", help="[addition] needs --resident: a shot table for every video, "
                    "installed before its maps are read (P3DSession.video_set_shots) -- --temporal then filters inside the shots and --reframe "
                    "smooths its track inside them.  detect: the hard cuts found on the device in the decoded frames "
@@ -572,6 +603,7 @@ def parse_args(argv=None):
     render_args(args, p.error)
     reframe_args(args, p.error)
     regions_args(args, p.error)
+    qpmap_args(args, p.error)
     shots_args(args, p.error)
     return args
 
@@ -697,6 +729,67 @@ def regions_video_resident(sess, F, video_dir, size, regions):
     np.save(os.path.join(video_dir, "counts.npy"), res["counts"])
     if regions["labels"]:
         np.save(os.path.join(video_dir, "labels.npy"), res["labels"])
+    return t
+
+
+QPMAP_DEFAULTS = dict(qp_block=16, qp_peak_weight=128, qp_dilate=0, qp_fall=0, qp_rise=0, qp_min=-12, qp_max=6, qp_gate=0, qp_gamma=1.0,
+                      qp_no_balance=False, qp_levels=False)
+
+
+def qpmap_args(args, error):
+    """Checks --qpmap and its values as P3DSession.video_qpmap and dataflow.qp_law would refuse them, before anything runs;
+    error(message) does not return.  Leaves dict(block, peak_weight, dilate, fall, rise, lo, hi, gate, gamma, balance, levels) in
+    args.qpmap_kw (None without --qpmap).  The balance's target is 0 where [--qp-min, --qp-max] holds it, else the nearer end."""
+    args.qpmap_kw = None
+    if not args.qpmap:
+        if any(getattr(args, k) != v for k, v in QPMAP_DEFAULTS.items()):
+            error("--qp-block / -peak-weight / -dilate / -fall / -rise / -min / -max / -gate / -gamma / -no-balance / -levels need --qpmap DIR")
+        return
+    if not args.resident:
+        error("--qpmap needs --resident: the maps stay on the device")
+    if args.qp_block not in (8, 16, 32, 64, 128):
+        error("--qp-block is 8, 16, 32, 64 or 128")
+    if not 0 <= args.qp_peak_weight <= 256:
+        error("--qp-peak-weight is 0 .. 256")
+    if not 0 <= args.qp_dilate <= 8:
+        error("--qp-dilate is 0 .. 8 blocks")
+    if not 0 <= args.qp_fall <= 254 or not 0 <= args.qp_rise <= 254:
+        error("--qp-fall and --qp-rise are 0 .. 254")
+    if not -127 <= args.qp_min <= args.qp_max <= 127:
+        error("-127 <= --qp-min <= --qp-max <= 127")
+    if not 0 <= args.qp_gate <= 254:
+        error("--qp-gate is a level, 0 .. 254")
+    if not (np.isfinite(args.qp_gamma) and args.qp_gamma > 0.):
+        error("--qp-gamma is finite and above 0")
+    args.qpmap_kw = dict(block=args.qp_block, peak_weight=args.qp_peak_weight, dilate=args.qp_dilate, fall=args.qp_fall, rise=args.qp_rise,
+                         lo=args.qp_min, hi=args.qp_max, gate=args.qp_gate, gamma=args.qp_gamma, balance=not args.qp_no_balance,
+                         levels=args.qp_levels)
+
+
+def write_qp_text(path, qp):
+    """qp.txt: one line a frame -- the frame's number from 1, then its offsets in raster order, separated by spaces."""
+    with open(path, "w") as f:
+        for k, q in enumerate(qp):
+            f.write("%d %s\n" % (k + 1, " ".join("%d" % v for v in q.ravel())))
+
+
+def qpmap_video_resident(sess, F, video_dir, size, qpmap):
+    """--qpmap: the open video's maps at `size` turned into quantiser offsets per coding block on the device (P3DSession.video_qpmap),
+    ONE call for the whole video so that the limiter sees every frame; writes qp.npy, stats.npy, qp.txt and, on request, levels.npy
+    into video_dir.  -> dict(gpu, device, qpmap: ms; grid: (Hb, Wb); lo, hi: the smallest and largest offset written)."""
+    from sap3d_tensorflow_amd import dataflow
+    law = dataflow.qp_law(qpmap["lo"], qpmap["hi"], qpmap["gate"], qpmap["gamma"])
+    t0 = time.perf_counter()
+    res = sess.video_qpmap(0, F, size, law, block=qpmap["block"], peak_weight=qpmap["peak_weight"], dilate=qpmap["dilate"], fall=qpmap["fall"],
+                           rise=qpmap["rise"], balance=qpmap["balance"], target=min(max(0, qpmap["lo"]), qpmap["hi"]), lo=qpmap["lo"],
+                           hi=qpmap["hi"], with_levels=qpmap["levels"], with_stats=True, timed=True)
+    t = dict(gpu=(time.perf_counter() - t0) * 1e3, device=sess.last_qpmap_ms["device"], qpmap=sess.last_qpmap_ms["qpmap"],
+             grid=res["qp"].shape[1:], lo=int(res["stats"][:, 0].min()), hi=int(res["stats"][:, 1].max()))
+    np.save(os.path.join(video_dir, "qp.npy"), res["qp"])
+    np.save(os.path.join(video_dir, "stats.npy"), res["stats"])
+    if qpmap["levels"]:
+        np.save(os.path.join(video_dir, "levels.npy"), res["levels"])
+    write_qp_text(os.path.join(video_dir, "qp.txt"), res["qp"])
     return t
 
 
@@ -946,6 +1039,13 @@ def run_resident(sess, args, path):
         os.makedirs(regions_dir, exist_ok=True)
         tg = regions_video_resident(sess, F, regions_dir, tuple(args.size), args.regions_kw)
         print(name, "%d regions over %d frames: regions.npy, counts.npy%s in %s" % (tg["kept"], F, ", labels.npy" if args.regions_kw["labels"] else "", regions_dir))
+    tq = None
+    if args.qpmap_kw:
+        qpmap_dir = os.path.join(args.qpmap, name)
+        os.makedirs(qpmap_dir, exist_ok=True)
+        tq = qpmap_video_resident(sess, F, qpmap_dir, tuple(args.size), args.qpmap_kw)
+        print(name, "%d x %d offsets in [%d, %d] over %d frames: qp.npy, stats.npy, qp.txt%s in %s"
+              % (tq["grid"] + (tq["lo"], tq["hi"], F, ", levels.npy" if args.qpmap_kw["levels"] else "", qpmap_dir)))
     temporal_ms = sess.video_temporal_last_ms() if args.temporal != "off" and args.time else None
     sess.close_video()
     if args.time:
@@ -969,6 +1069,8 @@ def run_resident(sess, args, path):
                   "time on %d writers" % (name, tf["gpu"], tf["upload"], tf["device"], tf["reframe"], tf["encode"], args.writers))
         if tg is not None:
             print("  %s: regions %.1f ms (maps %.2f ms, regions launches %.3f ms on the device)" % (name, tg["gpu"], tg["device"], tg["regions"]))
+        if tq is not None:
+            print("  %s: qpmap %.1f ms (maps %.2f ms, qpmap launches %.3f ms on the device)" % (name, tq["gpu"], tq["device"], tq["qpmap"]))
     return means
 
 

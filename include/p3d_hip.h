@@ -1747,6 +1747,66 @@ int p3d_debug_regions_u8(int device, const unsigned char* sal, int n, int H, int
 int p3d_debug_regions_plan(int H, int W, int n, int max_regions, int link, int labels, int* tile_h, int* tile_w, int* tiles_per_map,
                            int* maps_per_chunk, int64_t* scratch_bytes);
 
+/* ---- QP maps of 8-bit maps (an ADDITION: what a video encoder takes from a saliency model -- one signed quantiser offset per coding
+ * block, 16 x 16 macroblock or 64 x 64 CTU or superblock, lower where the viewers look, steady from frame to frame; the table is about
+ * block^2 times smaller than the maps it is made from).  OFF until called: every other entry point issues what it issued before and
+ * returns the same bits.  PARITY UNPINNED: the reference has nothing of the kind; this text is the contract and tests/qpmap_ref.py
+ * replays it in numpy.  Integer arithmetic throughout: no order can show, and every test holds to 0.  Nothing here drives an encoder
+ * or promises one's file format.
+ * Per frame: s [H][W] bytes, the saliency map.
+ *   CONFIG      nine ints in the order of the P3D_QPMAP_* indices below (an array: `const int cfg[9]`, as the regions configuration
+ *               is): block (B), one of 8, 16, 32, 64, 128; peak_weight 0 .. 256; dilate 0 .. 8 blocks; fall and rise 0 .. 254, 0 =
+ *               unlimited; balance 0 or 1; target, lo, hi with -127 <= lo <= target <= hi <= 127.  A law `const int32_t law[256]` comes
+ *               with it, every entry in -127 .. 127.
+ *   LIMITS      1 <= n <= 65535 maps a call; H * W <= 2^23.  Every sum below then fits 32 bits signed: a block sum is at most
+ *               255 * 128^2, an area-weighted sum of offsets at most 127 * 2^23.
+ *   GRID        Hb = ceil(H / B), Wb = ceil(W / B).  Block (by, bx) covers rows by B .. min(H, (by + 1) B) - 1 and columns likewise;
+ *               AREA is its pixel count (edge blocks are partial).
+ *   LEVEL       per block: SUM of its bytes and MAX byte; MEAN = (2 SUM + AREA) / (2 AREA), integer division;
+ *               L = (peak_weight * MAX + (256 - peak_weight) * MEAN + 128) >> 8, in 0 .. 255.
+ *   DILATE      L'(by, bx) = the largest L over the blocks with |dby| <= dilate and |dbx| <= dilate, clipped to the grid (a radius
+ *               beyond the grid is legal).
+ *   LAW         q0 = law[L'].
+ *   LIMIT       runs over the frames OF THE CALL, the whole world of the filter.  An optional shot table, in frames of the call
+ *               (starts [n_shots], ascending from 0), splits the call as the regions' LINK is split.  At the call's first frame and at
+ *               the first frame of every shot q1 = q0; elsewhere q1_f = min(max(q0_f, q1_{f-1} - fall), q1_{f-1} + rise), a bound
+ *               being absent when its field is 0: per block a fast attack and a slow release that never cross a cut.
+ *   BALANCE     S1 = the sum over the blocks of AREA * q1, A = H * W.  balance = 1: m = floor((2 S1 + A) / (2 A)), the division
+ *               rounding towards minus infinity, and q2 = clamp(q1 + (target - m), lo, hi).  balance = 0: q2 = clamp(q1, lo, hi).
+ *               One pass: after the clamp the mean need not equal target, and the statistics say what it is.  The limiter's state
+ *               is q1, never q2.
+ *   OUTPUTS     qp [n][Hb][Wb] int32_t: q2.  levels [n][Hb][Wb] bytes: L', or NULL.  stats [n][4] int32_t, or NULL: the smallest
+ *               q2, the largest q2, S1, and S2 = the sum of AREA * q2.
+ * p3d_qpmap_u8       op level, host arrays: sal [n][H][W], law [256], starts [n_shots] or NULL (then n_shots = 0) -> qp, levels (or
+ *                    NULL), stats (or NULL).
+ * p3d_video_qpmap    the QP maps of frames first .. first + n - 1 of the open video at H x W.  The saliency bytes are, bit for bit,
+ *                    what p3d_video_maps_u8(first, n, scale, H, W) returns under the handle's current settings; maps_out (or NULL)
+ *                    receives them.  The video's shot table, if one is set, is cut to the range exactly as p3d_video_reframe cuts
+ *                    it.  Validated as p3d_video_maps_u8 validates, plus cfg, the law, LIMITS and qp == NULL, all before any launch,
+ *                    upload or scratch request: a refusal changes nothing.  stage_ms (or NULL) [3]: 0, the maps' chain, the qpmap
+ *                    launches.  Returns synchronised.
+ * TEST HOOKS (tests/test_gpu_qpmap.py):
+ * p3d_debug_qpmap_u8  the same launch description with every device buffer, the scratch included, between guards: sal starts
+ *                    `offset` bytes (0 .. 15) past a 16-byte boundary, levels (5 offset) mod 16 bytes past one; -1 if a guard or an
+ *                    input changed.
+ * p3d_debug_qpmap_plan  host only, no HIP call: the strip of rows and the tile of columns a block of the reduction takes, the blocks
+ *                    a map, the maps whose first levels are held at a time (a call of more maps runs in chunks of that many) and
+ *                    the bytes of scratch. */
+#define P3D_QPMAP_FIELDS 9
+enum { P3D_QPMAP_BLOCK = 0, P3D_QPMAP_PEAK_WEIGHT = 1, P3D_QPMAP_DILATE = 2, P3D_QPMAP_FALL = 3, P3D_QPMAP_RISE = 4, P3D_QPMAP_BALANCE = 5,
+       P3D_QPMAP_TARGET = 6, P3D_QPMAP_LO = 7, P3D_QPMAP_HI = 8 };
+enum { P3D_QPMAP_STAT_MIN = 0, P3D_QPMAP_STAT_MAX = 1, P3D_QPMAP_STAT_S1 = 2, P3D_QPMAP_STAT_S2 = 3 };
+int p3d_qpmap_u8(int device, const unsigned char* sal, int n, int H, int W, const int cfg[9], const int32_t law[256],
+                 const int32_t* starts /* may be NULL */, int n_shots, int32_t* qp /* [n][Hb][Wb] */,
+                 unsigned char* levels /* [n][Hb][Wb], may be NULL */, int32_t* stats /* [n][4], may be NULL */);
+int p3d_video_qpmap(p3d_handle* h, int first, int n, float scale, int H, int W, const int cfg[9], const int32_t law[256], int32_t* qp,
+                    unsigned char* levels /* may be NULL */, int32_t* stats /* may be NULL */, unsigned char* maps_out /* may be NULL */,
+                    double* stage_ms /* may be NULL, [3] */);
+int p3d_debug_qpmap_u8(int device, const unsigned char* sal, int n, int H, int W, const int cfg[9], const int32_t law[256],
+                       const int32_t* starts, int n_shots, int offset, int32_t* qp, unsigned char* levels, int32_t* stats);
+int p3d_debug_qpmap_plan(int H, int W, int block, int n, int* strip_rows, int* tile_cols, int* blocks_per_map, int* maps_per_chunk,
+                         int64_t* scratch_bytes);
+
 /* ---- Shot boundaries of 8-bit frames (an ADDITION: the videos people reframe are edited, and a filter along the frame axis that
  * runs across a hard cut blends two unrelated scenes; automatic reframing tools find the cuts first).  OFF until called: every other
  * entry point issues what it issued before and returns the same bits.  PARITY UNPINNED: the reference's clips are single takes and

@@ -817,12 +817,33 @@ struct RegionsStage : ByteStage {
     void launch(hipStream_t s, const unsigned char* sal, unsigned*) override;
     void results(hipStream_t s) override;
 };
+// What one QP-map call on n maps of H x W bytes asks for: qp, levels and stats on the host, whatever is null is not copied back.
+struct QpmapCfg { int block, peak_weight, dilate, fall, rise, balance, target, lo, hi; };      // CONFIG's nine ints under their names
+struct QpmapRequest {
+    const char* who; int n, H, W;
+    const QpmapCfg* cfg = nullptr; const int32_t* law = nullptr;      // host: 256 entries (qpmap_check has passed them)
+    int32_t* qp = nullptr; unsigned char* levels = nullptr; int32_t* stats = nullptr;
+    bool timed = false;
+    const int32_t* starts = nullptr; int n_shots = 0;      // host: a shot table in frames of the call (shots_table_check has passed it), or none
+};
+// The launches of qpmap.hip behind some device bytes, with no arrival counters: they hand results to one another from launch to
+// launch.  qpmap_check has passed cfg, the law and the shape before one is built.
+struct QpmapStage : ByteStage {
+    const QpmapRequest r;
+    QpmapArgs a;
+    int32_t* dlaw = nullptr; int32_t* dstarts = nullptr;
+    explicit QpmapStage(const QpmapRequest& r);
+    void carve(Carve& c) override;
+    void upload(hipStream_t s) override;
+    void launch(hipStream_t s, const unsigned char* sal, unsigned*) override;
+    void results(hipStream_t s) override;
+};
 // gen_pred.py's write-out of `maps` maps that live on the device, for p3d_pred_maps_u8 and p3d_video_maps_u8: the bytes, the
 // scratch of p3d_set_postprocess's stage and `extra` floats of the caller's share one slab of the stream's scratch.  sources runs
 // inside the device stage's time: it queues whatever makes the maps readable and names them as runs of maps of ph x pw pixels.
 // Off: one double-precision p3d_resize_u8 per run; on: the float32 resize / blur / normalise / byte sequence, P3D_POST_CHUNK maps
 // at a time.  Ends synchronised; stage_ms as p3d_pred_maps_u8's.
-// A stage (ByteStage: score, render, reframe, regions) takes the device bytes where they are instead of a copy of the chain: its buffers are
+// A stage (ByteStage: score, render, reframe, regions, qpmap) takes the device bytes where they are instead of a copy of the chain: its buffers are
 // carved after the chain's in the same layout, its upload is queued ahead of the sources, its launches behind the chain with the
 // bytes and counters() zeroed arrival counters of its own (after the chain's), its results (the copies back to the host) behind
 // that; out may then be NULL (the bytes stay on the device) and, timed, its ms [3] receives the times of the upload, of the device
@@ -1823,7 +1844,7 @@ const unsigned char* kept_source(const p3d_handle* h, const char* who, int first
 void need_kept_source(const p3d_handle* h, const char* who) {
     if (!h->video.source) throw P3dError(std::string(who) + ": no frames are given and the video keeps no source (p3d_video_keep_source before the first p3d_video_put_frames_u8)");
 }
-// p3d_video_score, _score_auc, _render, _reframe and _regions behind the checks of their arguments: at most 65535 of the video's frames
+// p3d_video_score, _score_auc, _render, _reframe, _regions and _qpmap behind the checks of their arguments: at most 65535 of the video's frames
 // through the maps' chain, the stage behind its bytes.  make builds the stage once the source has passed, so that what the stage
 // (or the kept source it reads) refuses is refused after it.  stage_ms (null, or n_ms >= 3 values): zeroed, then the stage's ms.
 void video_stage_run(p3d_handle* h, const char* who, int first, int n, float scale, unsigned char* maps_out, double* stage_ms, int n_ms,
@@ -2353,6 +2374,149 @@ int p3d_video_regions(p3d_handle* h, int first, int n, float scale, int H, int W
         return *stage;
     });
     if (stage_ms) stage_ms[0] = 0.0;                   // (nothing but a shot table went up)
+    API_END
+}
+
+}  // extern "C"
+namespace {
+// ---- QP maps of 8-bit maps (qpmap.hip; the law in include/p3d_hip.h): one check, one table of buffer sizes and one launch description
+// for p3d_qpmap_u8, the qpmap stage and p3d_debug_qpmap_u8 ---------------------------------------------------------------------------
+QpmapCfg qpmap_check(const char* who, const int* cfg9, const int32_t* law, int n, int H, int W, const void* qp) {
+    if (!cfg9 || !law || !qp) throw P3dError("null argument");
+    const QpmapCfg c{cfg9[P3D_QPMAP_BLOCK], cfg9[P3D_QPMAP_PEAK_WEIGHT], cfg9[P3D_QPMAP_DILATE], cfg9[P3D_QPMAP_FALL], cfg9[P3D_QPMAP_RISE],
+                     cfg9[P3D_QPMAP_BALANCE], cfg9[P3D_QPMAP_TARGET], cfg9[P3D_QPMAP_LO], cfg9[P3D_QPMAP_HI]};
+    map_shape_check(who, n, H, W, P3D_QPMAP_MAX_PIXELS, "2^23, the bound that keeps an area-weighted sum of offsets in 32 bits");
+    if (c.block != 8 && c.block != 16 && c.block != 32 && c.block != 64 && c.block != 128)
+        throw P3dError(std::string(who) + ": the block is 8, 16, 32, 64 or 128, not " + std::to_string(c.block));
+    if (c.peak_weight < 0 || c.peak_weight > 256) throw P3dError(std::string(who) + ": peak_weight is 0 .. 256");
+    if (c.dilate < 0 || c.dilate > 8) throw P3dError(std::string(who) + ": dilate is 0 .. 8 blocks");
+    if (c.fall < 0 || c.fall > 254 || c.rise < 0 || c.rise > 254) throw P3dError(std::string(who) + ": fall and rise are 0 .. 254 (0: unlimited)");
+    if (c.balance != 0 && c.balance != 1) throw P3dError(std::string(who) + ": balance is 0 or 1");
+    if (c.lo < -127 || c.hi > 127 || c.lo > c.hi) throw P3dError(std::string(who) + ": -127 <= lo <= hi <= 127");
+    if (c.target < c.lo || c.target > c.hi) throw P3dError(std::string(who) + ": the target lies in [lo, hi]");
+    for (int v = 0; v < 256; ++v)
+        if (law[v] < -127 || law[v] > 127) throw P3dError(std::string(who) + ": law[" + std::to_string(v) + "] = " + std::to_string(law[v]) + " is outside -127 .. 127");
+    return c;
+}
+QpmapArgs qpmap_args(const QpmapCfg& c, int n, int H, int W) {
+    QpmapArgs a;
+    a.n = n; a.H = H; a.W = W; a.block = c.block; a.peak_weight = c.peak_weight; a.dilate = c.dilate; a.fall = c.fall; a.rise = c.rise;
+    a.balance = c.balance; a.target = c.target; a.lo = c.lo; a.hi = c.hi;
+    const QpmapPlan p = p3d_qpmap_plan(H, W, c.block, n);
+    a.maps_per_chunk = p.maps_per_chunk; a.Hb = p.Hb; a.Wb = p.Wb; a.tiles_x = p.tiles_x;
+    return a;
+}
+// Elements of the buffers of one call: what the stage carves and what the hook puts between guards
+struct QpmapSizes {
+    size_t sal, grid, stats, lev0;
+    explicit QpmapSizes(const QpmapArgs& a)
+        : sal((size_t)a.n * (size_t)a.H * (size_t)a.W), grid((size_t)a.n * (size_t)a.Hb * (size_t)a.Wb), stats((size_t)a.n * 4),
+          lev0((size_t)p3d_qpmap_plan(a.H, a.W, a.block, a.n).lev0_elems) {}
+};
+
+// ---- the qpmap stage (declared above maps_u8_chain) -------------------------------------------------------------------------------
+QpmapStage::QpmapStage(const QpmapRequest& r_) : ByteStage(r_), r(r_), a(qpmap_args(*r_.cfg, r_.n, r_.H, r_.W)) {}
+void QpmapStage::carve(Carve& c) {
+    const QpmapSizes z(a);
+    a.qp = c.take<int32_t>(z.grid);
+    a.levels = r.levels ? c.take<unsigned char>(z.grid) : nullptr;
+    a.stats = r.stats ? c.take<int32_t>(z.stats) : nullptr;
+    a.lev0 = c.take<unsigned char>(z.lev0);
+    dlaw = c.take<int32_t>(256);
+    dstarts = r.starts ? c.take<int32_t>((size_t)r.n_shots) : nullptr;
+}
+void QpmapStage::upload(hipStream_t s) {
+    HIPCHECK(hipMemcpyAsync(dlaw, r.law, 256 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (dstarts) HIPCHECK(hipMemcpyAsync(dstarts, r.starts, (size_t)r.n_shots * sizeof(int32_t), hipMemcpyHostToDevice, s));
+}
+void QpmapStage::launch(hipStream_t s, const unsigned char* sal, unsigned*) {
+    a.sal = sal; a.law = dlaw; a.starts = dstarts; a.n_shots = dstarts ? r.n_shots : 0;
+    HIPCHECK(p3d_qpmap_launch(a, s));
+}
+void QpmapStage::results(hipStream_t s) {
+    const QpmapSizes z(a);
+    HIPCHECK(hipMemcpyAsync(r.qp, a.qp, z.grid * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (r.levels) HIPCHECK(hipMemcpyAsync(r.levels, a.levels, z.grid, hipMemcpyDeviceToHost, s));
+    if (r.stats) HIPCHECK(hipMemcpyAsync(r.stats, a.stats, z.stats * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+}
+}  // namespace
+extern "C" {
+
+int p3d_qpmap_u8(int device, const unsigned char* sal, int n, int H, int W, const int cfg[9], const int32_t law[256], const int32_t* starts,
+                 int n_shots, int32_t* qp, unsigned char* levels, int32_t* stats) {
+    API_BEGIN
+    const char* who = "qpmap_u8";
+    if (!sal) throw P3dError("null argument");
+    const QpmapCfg qc = qpmap_check(who, cfg, law, n, H, W, qp);
+    if (starts || n_shots) shots_table_check(who, starts, n_shots, n);
+    metric_args(device, sal, cfg, 1, 1, qp);
+    QpmapRequest r{who, n, H, W};
+    r.cfg = &qc; r.law = law; r.qp = qp; r.levels = levels; r.stats = stats; r.starts = starts; r.n_shots = n_shots;
+    QpmapStage stage(r);
+    stage_on_host_bytes(stage, sal);
+    API_END
+}
+
+int p3d_debug_qpmap_u8(int device, const unsigned char* sal, int n, int H, int W, const int cfg[9], const int32_t law[256],
+                       const int32_t* starts, int n_shots, int offset, int32_t* qp, unsigned char* levels, int32_t* stats) {
+    API_BEGIN
+    const char* who = "debug_qpmap_u8";
+    if (!sal) throw P3dError("null argument");
+    const QpmapCfg qc = qpmap_check(who, cfg, law, n, H, W, qp);
+    if (starts || n_shots) shots_table_check(who, starts, n_shots, n);
+    if (offset < 0 || offset > 15) throw P3dError(std::string(who) + ": offset in [0, 15]");
+    metric_args(device, sal, cfg, 1, 1, qp);
+    QpmapArgs a = qpmap_args(qc, n, H, W);
+    const QpmapSizes sz(a);
+    // guards of 16 elements keep a 16-byte boundary at the data's start; the two byte buffers are then shifted
+    Guarded<unsigned char> ds(sz.sal, 16, (size_t)offset, sal), dlev(levels ? sz.grid : 0, 16, (size_t)(5 * offset % 16), nullptr),
+        dlev0(sz.lev0, 16, 0, nullptr);
+    Guarded<int32_t> dqp(sz.grid, 16, 0, nullptr), dstats(stats ? sz.stats : 0, 16, 0, nullptr), dlaw(256, 16, 0, law),
+        dst((size_t)n_shots, 16, 0, starts);
+    a.sal = ds.data(); a.law = dlaw.data(); a.qp = dqp.data(); a.levels = levels ? dlev.data() : nullptr;
+    a.stats = stats ? dstats.data() : nullptr; a.lev0 = dlev0.data();
+    a.starts = n_shots ? dst.data() : nullptr; a.n_shots = n_shots;
+    HIPCHECK(p3d_qpmap_launch(a, nullptr));
+    dqp.back(qp, who); dlev.back(levels, who); dstats.back(stats, who); dlev0.back(nullptr, who);
+    ds.unchanged(who); dlaw.unchanged(who); dst.unchanged(who);
+    API_END
+}
+
+int p3d_debug_qpmap_plan(int H, int W, int block, int n, int* strip_rows, int* tile_cols, int* blocks_per_map, int* maps_per_chunk,
+                         int64_t* scratch_bytes) {
+    API_BEGIN
+    if (!strip_rows || !tile_cols || !blocks_per_map || !maps_per_chunk || !scratch_bytes) throw P3dError("null argument");
+    if (H < 1 || W < 1 || (long long)H * W > P3D_QPMAP_MAX_PIXELS || n < 1 || n > 65535 ||
+        (block != 8 && block != 16 && block != 32 && block != 64 && block != 128))
+        throw P3dError("debug_qpmap_plan: 1 <= H * W <= 2^23, 1 .. 65535 maps, a block of 8, 16, 32, 64 or 128");
+    const QpmapPlan p = p3d_qpmap_plan(H, W, block, n);
+    *strip_rows = p.strip_rows; *tile_cols = p.tile_cols; *blocks_per_map = p.blocks_per_map; *maps_per_chunk = p.maps_per_chunk;
+    *scratch_bytes = (int64_t)p.scratch_bytes;
+    API_END
+}
+
+int p3d_video_qpmap(p3d_handle* h, int first, int n, float scale, int H, int W, const int cfg[9], const int32_t law[256], int32_t* qp,
+                    unsigned char* levels, int32_t* stats, unsigned char* maps_out, double* stage_ms) {
+    API_BEGIN
+    const char* who = "video_qpmap";
+    if (!h) throw P3dError("null argument");
+    h->video.need_open(who);
+    const QpmapCfg qc = qpmap_check(who, cfg, law, std::max(1, std::min(n, 65535)), H, W, qp);
+    QpmapRequest r{who, n, H, W};
+    r.cfg = &qc; r.law = law; r.qp = qp; r.levels = levels; r.stats = stats; r.timed = stage_ms != nullptr;
+    std::unique_ptr<QpmapStage> stage;
+    std::vector<int32_t> shots;                            // the installed table in frames of the call, cut as p3d_video_reframe cuts it
+    video_stage_run(h, who, first, n, scale, maps_out, stage_ms, 3, [&]() -> ByteStage& {
+        if (!h->video.shots.empty()) {
+            shots.push_back(0);
+            for (int32_t st : h->video.shots)
+                if (st > first && st < first + n) shots.push_back(st - first);
+            r.starts = shots.data(); r.n_shots = (int)shots.size();
+        }
+        stage.reset(new QpmapStage(r));
+        return *stage;
+    });
+    if (stage_ms) stage_ms[0] = 0.0;                   // (nothing but the law and a shot table went up)
     API_END
 }
 

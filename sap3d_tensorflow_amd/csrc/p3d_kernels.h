@@ -1192,6 +1192,31 @@ struct RegionsArgs {
 };
 hipError_t p3d_regions_launch(const RegionsArgs& a, hipStream_t s);
 
+// ---- block importance and QP offsets of 8-bit maps (qpmap.hip; p3d_video_qpmap / p3d_qpmap_u8, the law in include/p3d_hip.h) ----
+// One launch sequence on n maps of H x W bytes: sal [n][H][W] -> qp [n][Hb][Wb] int32 (q2), levels [n][Hb][Wb] bytes (L', or null) and
+// stats [n][4] int32 (or null), Hb = ceil(H / block), Wb = ceil(W / block); every buffer device memory, law [256] and starts too.
+// Scratch: lev0 [maps_per_chunk][Hb][Wb] bytes, the levels before DILATE of p3d_qpmap_plan's maps_per_chunk maps at a time.  qp holds
+// q0, then q1, then q2, each in place of the one before.
+// Refused (hipErrorInvalidValue): a missing buffer, n outside [1, 65535], H * W outside [1, 2^23], a configuration outside the header's
+// ranges, a plan other than p3d_qpmap_plan's, starts without n_shots in 1 .. n or n_shots without starts.  The law's entries are the
+// caller's to check: they live on the device.
+constexpr int P3D_QPMAP_MAX_PIXELS = 1 << 23;                 // 127 * 2^23 < 2^31: an area-weighted sum of offsets fits int32
+constexpr int P3D_QPMAP_CHUNK = 64;                           // at most this many maps' first levels at a time
+constexpr int QPMAP_TILE_WORDS = 256;                         // the reduction's tile: `block` rows of this many 16-byte words of a row
+struct QpmapPlan {
+    int strip_rows = 0, tile_cols = 0, tiles_x = 0, Hb = 0, Wb = 0, blocks_per_map = 0, maps_per_chunk = 0;
+    long long lev0_elems = 0, scratch_bytes = 0;
+};
+QpmapPlan p3d_qpmap_plan(int H, int W, int block, int n);
+struct QpmapArgs {
+    const unsigned char* sal = nullptr; const int32_t* law = nullptr; int32_t* qp = nullptr; unsigned char* levels = nullptr;
+    int32_t* stats = nullptr; unsigned char* lev0 = nullptr;
+    int n = 0, H = 0, W = 0, block = 0, peak_weight = 0, dilate = 0, fall = 0, rise = 0, balance = 0, target = 0, lo = 0, hi = 0;
+    int maps_per_chunk = 0, Hb = 0, Wb = 0, tiles_x = 0;      // p3d_qpmap_plan(H, W, block, n)
+    const int32_t* starts = nullptr; int n_shots = 0;        // a shot table in frames of the call (device; ascending from 0), or none
+};
+hipError_t p3d_qpmap_launch(const QpmapArgs& a, hipStream_t s);
+
 // ---- shot boundaries of 8-bit frames (shots.hip; p3d_shot_distances_u8 / p3d_shot_cuts, the law in include/p3d_hip.h) ----
 // The cut signal of n frames [n][H][W][3] of device bytes: D [n] device words, D_0 = 0, D_f the distance of frame f's cell
 // histograms from frame f - 1's.  tabs is scratch of (frames_per_chunk + 1) tables of table_words words on a 16-byte boundary: slot 0

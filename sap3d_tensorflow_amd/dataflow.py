@@ -722,6 +722,83 @@ def regions(sal, gate, connectivity=8, min_area=1, max_regions=None, link=False,
     return rec, counts, lab
 
 
+QPMAP_BLOCKS = (8, 16, 32, 64, 128)
+
+
+def qp_law(lo, hi, gate=0, gamma=1.0):
+    """The table that turns a block's level into its quantiser offset (LAW of include/p3d_hip.h, "QP maps of 8-bit maps") -> int32
+    [256].  A host table, built here in float64: level v < gate gives `hi` (the background's offset); otherwise, with
+    x = (v - gate) / (255 - gate), entry v = floor(hi - (hi - lo) x^gamma + 0.5) (round half up), so level `gate` gives hi, level 255
+    gives lo and the entries never rise with v.  -127 <= lo <= hi <= 127; gate is a level 0 .. 254; gamma is finite and > 0 (below
+    1: the offset falls early, above 1: only the most salient blocks reach lo)."""
+    lo, hi, gate, gamma = int(lo), int(hi), int(gate), float(gamma)
+    if not -127 <= lo <= hi <= 127:
+        raise ValueError("-127 <= lo <= hi <= 127")
+    if not 0 <= gate <= 254:
+        raise ValueError("gate is a level, 0 .. 254")
+    if not (np.isfinite(gamma) and gamma > 0.):
+        raise ValueError("gamma is finite and > 0")
+    v = np.arange(256, dtype=np.float64)
+    x = np.clip((v - gate) / (255. - gate), 0., 1.)
+    law = np.floor(hi - (hi - lo) * x ** gamma + 0.5).astype(np.int32)
+    law[:gate] = hi
+    return law
+
+
+def qpmap_cfg(block=16, peak_weight=128, dilate=0, fall=0, rise=0, balance=True, target=0, lo=-127, hi=127):
+    """The nine ints of include/p3d_hip.h's CONFIG ("QP maps of 8-bit maps") in the order of the P3D_QPMAP_* indices."""
+    from . import _lib
+    cfg = (C.c_int * _lib.P3D_QPMAP_FIELDS)()
+    for k, v in ((_lib.P3D_QPMAP_BLOCK, block), (_lib.P3D_QPMAP_PEAK_WEIGHT, peak_weight), (_lib.P3D_QPMAP_DILATE, dilate),
+                 (_lib.P3D_QPMAP_FALL, fall), (_lib.P3D_QPMAP_RISE, rise), (_lib.P3D_QPMAP_BALANCE, balance),
+                 (_lib.P3D_QPMAP_TARGET, target), (_lib.P3D_QPMAP_LO, lo), (_lib.P3D_QPMAP_HI, hi)):
+        cfg[k] = int(v)
+    return cfg
+
+
+def qpmap_plan(H, W, block=16, n=1):
+    """Test hook (p3d_debug_qpmap_plan, host only): dict(strip_rows, tile_cols, blocks_per_map, maps_per_chunk, scratch_bytes) of the
+    qpmap launches for n maps of H x W."""
+    sr, tc, b, m, s = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int64(0)
+    check(lib().p3d_debug_qpmap_plan(int(H), int(W), int(block), int(n), C.byref(sr), C.byref(tc), C.byref(b), C.byref(m), C.byref(s)))
+    return dict(strip_rows=sr.value, tile_cols=tc.value, blocks_per_map=b.value, maps_per_chunk=m.value, scratch_bytes=s.value)
+
+
+def _qp_law_array(law):
+    t = np.ascontiguousarray(law)
+    if t.dtype != np.int32 or t.shape != (256,):
+        raise ValueError("the law is int32 [256] (dataflow.qp_law)")
+    return t
+
+
+def qpmap(sal, law, block=16, peak_weight=128, dilate=0, fall=0, rise=0, balance=True, target=0, lo=-127, hi=127, shots=None,
+          levels=False, stats=False, device=0, offset=None):
+    """Block importance and quantiser offsets of saliency maps on the device (p3d_qpmap_u8; include/p3d_hip.h, "QP maps of 8-bit
+    maps"): maps uint8 [n, H, W] (or [H, W]: one frame) and a law int32 [256] (qp_law) -> (qp int32 [n, Hb, Wb], levels uint8
+    [n, Hb, Wb] or None, stats int32 [n, 4] or None), Hb = ceil(H / block), Wb = ceil(W / block).  fall / rise limit every block's
+    offset from frame to frame, inside the shots of `shots` (starts ascending from 0) where given.  offset (0 .. 15): the test hook
+    p3d_debug_qpmap_u8, every device buffer between guards and the byte buffers shifted off a 16-byte boundary."""
+    s3, _, _ = _reframe_shape(sal, 1)
+    n, H, W = s3.shape
+    t = _qp_law_array(law)
+    cfg = qpmap_cfg(block, peak_weight, dilate, fall, rise, balance, target, lo, hi)
+    B = int(block)
+    grid = (n, -(-H // B), -(-W // B)) if B in QPMAP_BLOCKS else (1,)      # (the library refuses the rest before it writes)
+    qp = np.empty(grid, np.int32)
+    lev = np.empty(grid, np.uint8) if levels else None
+    st4 = np.empty((n, 4), np.int32) if stats else None
+    u8, i32 = C.POINTER(C.c_ubyte), C.POINTER(C.c_int32)
+    st = None if shots is None else np.ascontiguousarray(shots, np.int32).ravel()
+    head = (device, s3.ctypes.data_as(u8), n, H, W, cfg, t.ctypes.data_as(i32), None if st is None else st.ctypes.data_as(i32),
+            0 if st is None else len(st))
+    tail = (qp.ctypes.data_as(i32), None if lev is None else lev.ctypes.data_as(u8), None if st4 is None else st4.ctypes.data_as(i32))
+    if offset is None:
+        check(lib().p3d_qpmap_u8(*head, *tail))
+    else:
+        check(lib().p3d_debug_qpmap_u8(*head, int(offset), *tail))
+    return qp, lev, st4
+
+
 def _shot_frames(frames):
     f = np.ascontiguousarray(frames)
     if f.dtype != np.uint8 or f.ndim != 4 or f.shape[3] != 3 or f.size == 0:

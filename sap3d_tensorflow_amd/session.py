@@ -1065,6 +1065,41 @@ class P3DSession:
             res["maps"] = maps
         return res
 
+    def video_qpmap(self, first, n, size, law, block=16, peak_weight=128, dilate=0, fall=0, rise=0, balance=True, target=0, lo=-127, hi=127,
+                    scale=255., with_levels=False, with_stats=False, with_maps=False, timed=False):
+        """Quantiser offsets per coding block of frames first .. first + n - 1 of the open video, on the device (an addition): the
+        level of every block x block block of video_maps_u8's bytes at `size` (peak_weight / 256 of its largest byte, the rest its
+        mean), dilated by `dilate` blocks, turned into an offset by `law` (int32 [256], dataflow.qp_law), limited to `fall` down and
+        `rise` up per frame WITHIN THIS CALL and inside the shots of video_set_shots' table, and with `balance` shifted so that the
+        frame's area-weighted mean is `target`, then clamped to [lo, hi] -> dict(qp int32 [n, Hb, Wb]).  with_levels / with_stats /
+        with_maps add levels uint8 [n, Hb, Wb], stats int32 [n, 4] (min, max, S1, S2) and maps uint8 [n, H, W].  timed: HIP-event
+        times are left in `last_qpmap_ms` (device = the maps' chain, qpmap).  include/p3d_hip.h holds the exact rules."""
+        from . import dataflow
+        H, W = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
+        n = max(int(n), 0)
+        B = int(block)
+        valid = H >= 1 and W >= 1 and H * W <= 2 ** 23 and B in dataflow.QPMAP_BLOCKS      # (the library refuses the rest)
+        t = dataflow._qp_law_array(law)
+        cfg = dataflow.qpmap_cfg(B, peak_weight, dilate, fall, rise, balance, target, lo, hi)
+        grid = (n, -(-H // B), -(-W // B)) if valid else (1,)
+        qp = np.empty(grid, np.int32)
+        lev = np.empty(grid, np.uint8) if with_levels else None
+        st4 = np.empty((n, 4), np.int32) if with_stats else None
+        maps = np.empty((n, H, W) if valid else (0,), np.uint8) if with_maps else None
+        ms = (C.c_double * 3)()
+        check(lib().p3d_video_qpmap(self._h, int(first), n, float(scale), H, W, cfg, _ptr(t, _lib._i32p), _ptr(qp, _lib._i32p),
+                                    _ptr(lev, _lib._u8p), _ptr(st4, _lib._i32p), _ptr(maps, _lib._u8p), ms if timed else None))
+        if timed:
+            self.last_qpmap_ms = dict(device=ms[1], qpmap=ms[2])
+        res = dict(qp=qp)
+        if with_levels:
+            res["levels"] = lev
+        if with_stats:
+            res["stats"] = st4
+        if with_maps:
+            res["maps"] = maps
+        return res
+
     def video_detect_shots(self, grid=(2, 2), threshold=250, window=2, ratio=512, min_length=3, install=True, with_signal=False):
         """Find the hard cuts of the open video on the device (an addition), from the source kept by video_keep_source: per frame a
         grid = (gy, gx) of cell histograms of the B, G, R bytes, D_f their distance from the frame before; frame f starts a shot
