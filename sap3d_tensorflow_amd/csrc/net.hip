@@ -1578,5 +1578,6 @@ struct p3d_handle {
 };
 
 #include "net_abi.inc"
+#include "net_carve.inc"
 #include "net_readout.inc"
 #include "net_shots.inc"

@@ -1,37 +1,5 @@
 // ---- metrics / pre-processing entry points (metrics.hip) -------------------------------------------------------
 namespace {
-// op level: a device array of `n` elements between `guard` elements of guard words on either side, the data `shift` elements in
-template <typename T>
-struct Guarded {
-    static constexpr uint32_t WORD = 0x7fc5a5a5u;          // a NaN no arithmetic here produces
-    size_t n, at, total; std::vector<T> init; DevArr<T> dev;
-    static std::vector<T> fill(size_t total) {
-        std::vector<T> v(total);
-        const unsigned char pat[4] = {0xa5, 0xa5, 0xc5, 0x7f};
-        unsigned char* b = reinterpret_cast<unsigned char*>(v.data());
-        for (size_t i = 0; i < total * sizeof(T); ++i) b[i] = pat[i & 3];
-        return v;
-    }
-    Guarded(size_t n_, size_t guard, size_t shift, const T* host)
-        : n(n_), at(guard + shift), total(n_ + 2 * guard + shift), init(fill(total)), dev(total) {
-        if (host) std::copy(host, host + n, init.begin() + at); else std::fill(init.begin() + at, init.begin() + at + n, T());
-        HIPCHECK(copy_now(dev.p, init.data(), total * sizeof(T), hipMemcpyHostToDevice, nullptr));
-    }
-    T* data() { return dev.p + at; }
-    // the data into out (or nowhere); throws if anything outside it changed
-    void back(T* out, const char* what) {
-        std::vector<T> got(total);
-        dev.get(got.data(), total);
-        if (memcmp(got.data(), init.data(), at * sizeof(T)) || memcmp(got.data() + at + n, init.data() + at + n, (total - at - n) * sizeof(T)))
-            throw P3dError(std::string(what) + ": a launch wrote outside its buffer");
-        if (out) memcpy(out, got.data() + at, n * sizeof(T));
-    }
-    void unchanged(const char* what) {
-        std::vector<T> got(total);
-        dev.get(got.data(), total);
-        if (memcmp(got.data(), init.data(), total * sizeof(T))) throw P3dError(std::string(what) + ": a launch wrote to a read-only buffer");
-    }
-};
 void metric_args(int device, const void* a, const void* b, int n_maps, int n_pix, const void* out) {
     if (!a || !b || !out) throw P3dError("null argument");
     if (n_maps < 1 || n_pix < 1) throw P3dError("metrics need at least one map and one pixel");
@@ -128,29 +96,6 @@ int p3d_mapf_density(int device, const unsigned char* grey, int n, int H0, int W
 // ---- ground-truth resolution (metrics_full.hip) ----------------------------------------------------------------------
 }  // extern "C"
 namespace {
-// Byte offsets of the buffers of one full-resolution evaluation inside one allocation (a first pass with base = null sizes it)
-struct Carve {
-    char* base = nullptr;
-    size_t off = 0;
-    template <typename T> T* take(size_t n) {
-        const size_t o = (off + 255) & ~(size_t)255;
-        off = o + (n > 0 ? n : 1) * sizeof(T);
-        return base ? (T*)(base + o) : nullptr;
-    }
-};
-// Buffers in the scratch of stream s.  layout(Carve&) only calls take: it runs once on a null base, which sizes the slab, and once
-// on the slab itself -- one statement list, so the two passes cannot drift apart.  -> the n_counters zeroed arrival counters.
-template <typename Layout>
-unsigned* carve_scratch(hipStream_t s, size_t n_counters, const Layout& layout) {
-    Carve c;
-    layout(c);
-    float* slab = nullptr;
-    unsigned* counters = nullptr;
-    HIPCHECK(p3d_stream_scratch(s, (c.off + 3) / 4, n_counters, &slab, &counters));
-    c = Carve{(char*)slab, 0};
-    layout(c);
-    return counters;
-}
 int next_pow2(int n) { int p = 1; while (p < n) p <<= 1; return p; }
 // every scratch buffer of P3dFullMaps / P3dFullBorji; slot offsets and meta come from n_fix[n_maps]
 void carve_full(Carve& c, P3dFullMaps& a, P3dFullBorji& r, const std::vector<int>& meta) {
@@ -716,6 +661,13 @@ struct ByteStage {
     virtual void launch(hipStream_t s, const unsigned char* sal, unsigned* counters) = 0;
     virtual void results(hipStream_t s) = 0;
 };
+// A stage's optional shot table in frames of the call: the host's (shots_table_check has passed it) and its copy on the device
+struct ShotTable {
+    const int32_t* host = nullptr; int n = 0; int32_t* dev = nullptr;
+    void carve(Carve& c) { dev = host ? c.input<int32_t>((size_t)n) : nullptr; }
+    void upload(hipStream_t s) const { if (dev) HIPCHECK(hipMemcpyAsync(dev, host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s)); }
+    template <typename Args> void bind(Args& a) const { a.starts = dev; a.n_shots = dev ? n : 0; }
+};
 // What one scoring of n maps of H x W bytes asks for; every pointer is host memory.  Whatever is not asked for is not issued.
 struct ScoreRequest {
     const char* who; int n, H, W;
@@ -726,6 +678,11 @@ struct ScoreRequest {
     // shuffled AUC -> shuffled [n][n_rep] (null: not asked for): ranks of n_rows[b] x n_rep draws into the union that `pool` holds
     const int* ranks = nullptr; const int* n_rows = nullptr; const p3d_handle* pool = nullptr; double* shuffled = nullptr;
     int n_rep = 0; double step = 0.0;
+    // rows_checked, for p3d_score_sweep_u8 and its hook alone: launch waits for the sweeps' preparation, reads the device's counts
+    // back and refuses idx_rows above them before it queues the sweeps.  A video caller must never set it: the wait would sit in
+    // the middle of its chain, and its rows come from the host's own counts.  top, the test hook alone: the sweep's capture
+    // [n][n_rep], carved, bound and copied back when set
+    bool rows_checked = false; int* top = nullptr;
     bool timed = false;                                   // events around the stage's moments (ms) and around the sweeps (sweep_ms)
 };
 // The launches of score_u8.hip and score_auc_u8.hip behind some device bytes: the launch arguments, the tables of the host and the
@@ -736,7 +693,7 @@ struct ScoreStage : ByteStage {
     std::vector<int> nf, meta3, info; std::vector<long long> metaB, metaS;
     size_t totB = 0, totS = 0; int max_rows = 0;
     unsigned char* dd = nullptr; unsigned char* dx = nullptr;
-    int* didx = nullptr; int* dranks = nullptr; int* dsel = nullptr; int* dmeta3 = nullptr; int* drows = nullptr;
+    int* didx = nullptr; int* dtop = nullptr; int* dranks = nullptr; int* dsel = nullptr; int* dmeta3 = nullptr; int* drows = nullptr;
     long long* dmetaB = nullptr; long long* dmetaS = nullptr; double* perB = nullptr; double* perS = nullptr;
     StageTimer sweeps;
     explicit ScoreStage(const ScoreRequest& r);
@@ -747,7 +704,7 @@ struct ScoreStage : ByteStage {
     // pass A and the columns, then the sweeps' preparation (q.info: the device's counts); sweep_rest: the sweeps themselves
     void prepare(hipStream_t s, const unsigned char* sal, unsigned* counters);
     void sweep_rest(hipStream_t s);
-    void launch(hipStream_t s, const unsigned char* sal, unsigned* counters) override { prepare(s, sal, counters); sweep_rest(s); }
+    void launch(hipStream_t s, const unsigned char* sal, unsigned* counters) override;
     void results(hipStream_t s) override;
     void check_counts() const;                            // after the results have arrived: the device's counts against nf
     double sweep_ms() const { return sweeps.ev[0] ? (double)sweeps.ms(0) : 0.0; }
@@ -767,6 +724,7 @@ struct RenderStage : ByteStage {
     RenderArgs a;
     unsigned char* df = nullptr; unsigned char* dout = nullptr; unsigned* dtab = nullptr;
     explicit RenderStage(const RenderRequest& r);
+    size_t bgr() const { return bytes * 3; }              // the bytes of n frames, in or out
     void carve(Carve& c) override;
     void upload(hipStream_t s) override;
     void launch(hipStream_t s, const unsigned char* sal, unsigned*) override;
@@ -788,7 +746,7 @@ struct ReframeStage : ByteStage {
     const ReframeRequest r;
     ReframeArgs a;
     unsigned char* df = nullptr;
-    int32_t* dstarts = nullptr;
+    ShotTable shots;
     explicit ReframeStage(const ReframeRequest& r);
     bool crops() const { return r.out != nullptr; }
     void carve(Carve& c) override;
@@ -810,7 +768,7 @@ struct RegionsRequest {
 struct RegionsStage : ByteStage {
     const RegionsRequest r;
     RegionsArgs a;
-    int32_t* dstarts = nullptr;
+    ShotTable shots;
     explicit RegionsStage(const RegionsRequest& r);
     void carve(Carve& c) override;
     void upload(hipStream_t s) override;
@@ -831,7 +789,7 @@ struct QpmapRequest {
 struct QpmapStage : ByteStage {
     const QpmapRequest r;
     QpmapArgs a;
-    int32_t* dlaw = nullptr; int32_t* dstarts = nullptr;
+    int32_t* dlaw = nullptr; ShotTable shots;
     explicit QpmapStage(const QpmapRequest& r);
     void carve(Carve& c) override;
     void upload(hipStream_t s) override;
@@ -1155,7 +1113,7 @@ int p3d_match_hist_maps(int device, const float* maps, const float* targets, int
 
 }  // extern "C"
 namespace {
-// ---- fixation priors (include/p3d_hip.h; the handle's part in net_sched.inc, the kernels in prior.hip) -------------------------
+// ---- fixation priors (include/p3d_hip.h; the handle's part in net_prior.inc, the kernels in prior.hip) -------------------------
 // Counts -> float32 -> BLUR -> NORM (max) on stream s: the conversion, then the shared launch sequence on one map, in place on
 // `map` [H * W] (device).  Returns the float32 maximum of the blurred counts (0: every count was zero, the map is left unscaled).
 float prior_finish_launches(hipStream_t s, const unsigned* count, int H, int W, const Stages& st, float* map) {
@@ -1348,7 +1306,7 @@ int p3d_debug_prior_apply(int device, int mode, float a, const float* maps, int 
     if (n < 1 || n > 65535 || H < 1 || W < 1 || (long long)H * W > INT32_MAX / 2) throw P3dError("prior_apply: 1 .. 65535 maps of H x W floats, 1 <= H * W <= 2^30");
     p3d_handle::PriorMap::stage_check(mode, a);
     if (mode == P3D_PRIOR_OFF) throw P3dError("prior_apply: the mode is P3D_PRIOR_MUL or P3D_PRIOR_MIX");
-    if (offset < 0 || offset > 15) throw P3dError("prior_apply: offset in [0, 15]");
+    offset_check("prior_apply", offset);
     const size_t N = (size_t)H * W;
     Guarded<float> v((size_t)n * N, 8, (size_t)(offset & 3), maps), g(N, 8, (size_t)((offset >> 2) & 3), prior);
     PriorApplyArgs q;
@@ -1360,7 +1318,7 @@ int p3d_debug_prior_apply(int device, int mode, float a, const float* maps, int 
     API_END
 }
 
-// ---- fixation pool and shuffled AUC in the evaluation pass (include/p3d_hip.h; the handle's part in net_sched.inc, fixpool.hip) ----
+// ---- fixation pool and shuffled AUC in the evaluation pass (include/p3d_hip.h; the handle's part in net_fixpool.inc, fixpool.hip) ----
 int p3d_fixpool_open(p3d_handle* h, int H, int W, int64_t capacity) {
     API_BEGIN
     if (!h) throw P3dError("null handle");
@@ -1689,7 +1647,7 @@ int p3d_debug_eval_maps_shuffled(int device, const float* maps, int n_maps, int 
     API_END
 }
 
-// ---- resident video inference (include/p3d_hip.h; the handle's part in net_sched.inc, the kernels in video.hip) --------------
+// ---- resident video inference (include/p3d_hip.h; the handle's part in net_video.inc, the kernels in video.hip) --------------
 int p3d_video_open(p3d_handle* h, int frames, int mode) {
     API_BEGIN
     if (!h) throw P3dError("null handle");
@@ -1823,14 +1781,72 @@ void map_shape_check(const char* who, int n, int H, int W, long long max_pixels,
     if (H < 1 || W < 1) throw P3dError(std::string(who) + ": empty map");
     if ((long long)H * W > max_pixels) throw P3dError(std::string(who) + ": H * W exceeds " + bound);
 }
-// op level: the stage behind the host's bytes, on the null stream's scratch.  Ends synchronised.
-void stage_on_host_bytes(ByteStage& stage, const unsigned char* sal) {
-    DevArr<unsigned char> ds(stage.bytes, sal);
-    unsigned* const counters = carve_scratch(nullptr, stage.counters(), [&](Carve& c) { stage.carve(c); });
+void shots_table_check(const char* who, const int32_t* starts, int n_shots, int F);      // (net_shots.inc)
+// The open video's installed shot table cut to frames first .. first + n - 1, in frames of the call: its shots cut a stage's filters
+// and links.  Empty: no table is installed.
+std::vector<int32_t> video_shots_within(const p3d_handle* h, int first, int n) {
+    std::vector<int32_t> shots;
+    if (h->video.shots.empty()) return shots;
+    shots.push_back(0);
+    for (int32_t st : h->video.shots)
+        if (st > first && st < first + n) shots.push_back(st - first);
+    return shots;
+}
+// What a hook sees of its block once a guarded run has passed the guards: the block as it was after the uploads and as it is after
+// the copies back.  A buffer is named by the device pointer its take returned.
+struct GuardedRun {
+    const char* who; const GuardExtents& g; const char* base; const unsigned char* before; const unsigned char* after;
+    const unsigned* counters; size_t n_counters;
+    const GuardExtents::Extent& extent(const void* dev) const { return g.find((size_t)((const char*)dev - base)); }
+    // the buffer as the launches left it, into out
+    void read(const void* dev, void* out) const { const GuardExtents::Extent& e = extent(dev); memcpy(out, after + e.at, e.bytes); }
+    // a buffer that launches may write, which these launches had no business writing
+    void unchanged(const void* dev) const { g.unchanged(who, extent(dev), before, after); }
+    void counters_at_zero() const {
+        std::vector<unsigned> c(n_counters);
+        read(counters, c.data());
+        for (unsigned z : c) if (z != 0u) throw P3dError(std::string(who) + ": an arrival counter was left at " + std::to_string(z));
+    }
+};
+// op level: the stage behind the host's bytes.  Ends synchronised.  offset < 0: on the null stream's scratch, as the product lays
+// it out.  offset in [0, 15], a hook: the same carve inside one block of the hook's own, the bytes (read-only, `offset` past their
+// boundary) and the arrival counters with it, every buffer between guards; a launch that wrote outside its buffer or to an input is
+// an error, and `inspect` (or none) then looks at what the launches left.
+void stage_on_host_bytes(ByteStage& stage, const unsigned char* sal, int offset = -1,
+                         const std::function<void(const GuardedRun&)>& inspect = nullptr) {
+    if (offset < 0) {
+        DevArr<unsigned char> ds(stage.bytes, sal);
+        unsigned* const counters = carve_scratch(nullptr, stage.counters(), [&](Carve& c) { stage.carve(c); });
+        stage.upload(nullptr);
+        stage.launch(nullptr, ds.p, counters);
+        stage.results(nullptr);
+        HIPCHECK(hipDeviceSynchronize());
+        return;
+    }
+    const unsigned char* ds = nullptr;
+    unsigned* counters = nullptr;
+    const auto layout = [&](Carve& c) {
+        ds = c.input<unsigned char>(stage.bytes, 1);
+        counters = c.take<unsigned>(stage.counters());
+        stage.carve(c);
+    };
+    GuardExtents sized(offset), placed(offset);
+    Carve c;
+    c.guards = &sized;
+    layout(c);
+    std::vector<unsigned char> before = sized.image(), after(sized.total);
+    memcpy(before.data() + sized.ext[0].at, sal, stage.bytes);
+    DevArr<unsigned char> block(sized.total, before.data());
+    c = Carve{(char*)block.p, 0, &placed};
+    layout(c);
+    if (placed.total != sized.total || !(placed.ext == sized.ext)) throw P3dError(std::string(stage.who) + ": the two passes of the carve disagree");
     stage.upload(nullptr);
-    stage.launch(nullptr, ds.p, counters);
+    block.get(before.data(), sized.total);
+    stage.launch(nullptr, ds, counters);
     stage.results(nullptr);
-    HIPCHECK(hipDeviceSynchronize());
+    block.get(after.data(), sized.total);
+    sized.verify(stage.who, before.data(), after.data());
+    if (inspect) inspect(GuardedRun{stage.who, sized, (const char*)block.p, before.data(), after.data(), counters, stage.counters()});
 }
 // Frames first .. first + n - 1 of the source the open video keeps, for a call that `verb` ("renders", "reframes") H x W frames
 const unsigned char* kept_source(const p3d_handle* h, const char* who, int first, int n, int H, int W, const char* verb) {
@@ -1856,8 +1872,8 @@ void video_stage_run(p3d_handle* h, const char* who, int first, int n, float sca
     maps_u8_chain(h, n, h->pred->H, h->pred->W, scale, stage.H, stage.W, maps_out, nullptr, src.extra(), src, &stage);
     for (int i = 0; stage_ms && i < 3; ++i) stage_ms[i] = stage.ms[i];
 }
-// ---- scoring 8-bit maps (score_u8.hip; the law in include/p3d_hip.h): one check, one table of buffer sizes and one launch
-// sequence for the score stage and p3d_debug_score_u8 ------------------------------------------------------------------------------
+// ---- scoring 8-bit maps (score_u8.hip; the law in include/p3d_hip.h): one check, one launch sequence and one stage (the
+// table of buffer sizes is its own) for p3d_score_maps_u8, the video entries and p3d_debug_score_u8 ----------------------------------
 void score_check(const char* who, const void* density, const void* fixation, int n, int H, int W, int flags, int ties, const void* out) {
     if (!density || !out) throw P3dError("null argument");
     map_shape_check(who, n, H, W, P3D_SCORE_MAX_PIXELS, "2^23, the bound of the 64-bit integer sums");
@@ -1871,7 +1887,7 @@ ScoreArgs score_args(int n, long long n_pix, int flags, int ties) {
     a.n = n; a.n_pix = (int)n_pix; a.flags = flags; a.ties = ties; a.nblk = p.nblk; a.chunk = p.chunk;
     return a;
 }
-// Elements of the buffers of one scoring: what the stage carves and what the hooks put between guards
+// Elements of the buffers of one scoring
 struct ScoreSizes {
     size_t tab, lut, part, out, counters;
     explicit ScoreSizes(const ScoreArgs& a)
@@ -1901,29 +1917,18 @@ int p3d_debug_score_u8(int device, const unsigned char* sal, const unsigned char
     API_BEGIN
     if (!sal) throw P3dError("null argument");
     score_check("debug_score_u8", density, fixation, n, H, W, flags, ties, out);
-    if (offset < 0 || offset > 15) throw P3dError("debug_score_u8: offset in [0, 15]");
+    offset_check("debug_score_u8", offset);
     metric_args(device, sal, density, 1, 1, out);
-    const long long N = (long long)H * W;
-    const size_t bytes = (size_t)n * (size_t)N;
-    ScoreArgs a = score_args(n, N, flags, ties);
-    const ScoreSizes sz(a);
-    // guards of 16 elements keep a 16-byte boundary at the data's start for every element type here; the sources are then shifted
-    Guarded<unsigned char> ds(bytes, 16, (size_t)offset, sal), dd(bytes, 16, (size_t)(2 * offset % 16), density),
-        dx(fixation ? bytes : 0, 16, (size_t)(3 * offset % 16), fixation);
-    Guarded<unsigned> tab(sz.tab, 16, 0, nullptr), counter(sz.counters, 16, 0, nullptr);
-    Guarded<double> lut(sz.lut, 16, 0, nullptr), part(sz.part, 16, 0, nullptr), dout(sz.out, 16, 0, nullptr);
-    a.sal = ds.data(); a.den = dd.data(); a.fix = fixation ? dx.data() : nullptr;
-    a.tab = tab.data(); a.counter = counter.data(); a.lut = lut.data(); a.part = part.data(); a.out = dout.data();
-    score_sequence(a, nullptr);
-    std::vector<unsigned> t(sz.tab), zero(sz.counters, 1u);
-    tab.back(t.data(), "debug_score_u8");
-    counter.back(zero.data(), "debug_score_u8");
-    dout.back(out, "debug_score_u8");
-    if (p3d_score_has(SCORE_TERMS, a)) { lut.back(nullptr, "debug_score_u8"); part.back(nullptr, "debug_score_u8"); }
-    else { lut.unchanged("debug_score_u8"); part.unchanged("debug_score_u8"); }      // no pass B: nothing of its was written
-    ds.unchanged("debug_score_u8"); dd.unchanged("debug_score_u8");
-    if (fixation) dx.unchanged("debug_score_u8");
-    for (unsigned z : zero) if (z != 0u) throw P3dError("debug_score_u8: an arrival counter was left at " + std::to_string(z));
+    ScoreRequest r{"debug_score_u8", n, H, W};
+    r.flags = flags; r.ties = ties; r.density = density; r.fixation = fixation; r.out = out;
+    ScoreStage stage(r);
+    std::vector<unsigned> t;
+    stage_on_host_bytes(stage, sal, offset, [&](const GuardedRun& g) {
+        t.resize(g.extent(stage.a.tab).bytes / sizeof(unsigned));
+        g.read(stage.a.tab, t.data());
+        if (!p3d_score_has(SCORE_TERMS, stage.a)) { g.unchanged(stage.a.lut); g.unchanged(stage.a.part); }      // no pass B: nothing of its was written
+        g.counters_at_zero();
+    });
     for (int m = 0; m < n; ++m) {
         const unsigned* row = t.data() + (size_t)m * P3D_SCORE_TAB_WORDS;
         if (hs) std::copy(row, row + 256, hs + (size_t)m * 256);
@@ -1941,14 +1946,14 @@ int p3d_debug_score_plan(int64_t n_pix, int n, int offset, int* blocks_per_map, 
         throw P3dError("debug_score_plan: 1 <= n_pix <= 2^23, 1 .. 65535 maps, offset in [0, 15]");
     const ScorePlan p = p3d_score_plan(n_pix);
     *blocks_per_map = p.nblk; *pixels_per_block = p.chunk;
-    *products_per_lane = p3d_score_lane_products(n_pix, n, (unsigned)offset, (unsigned)(2 * offset % 16), (unsigned)(3 * offset % 16));
+    *products_per_lane = p3d_score_lane_products(n_pix, n, (unsigned)guard_shift(1, offset), (unsigned)guard_shift(2, offset), (unsigned)guard_shift(3, offset));
     API_END
 }
 
 }  // extern "C"
 namespace {
-// ---- rendering 8-bit maps over their frames (render.hip; the law in include/p3d_hip.h): one check, one table of buffer sizes and
-// one launch description for p3d_render_u8, the render stage and p3d_debug_render_u8 ------------------------------------------------
+// ---- rendering 8-bit maps over their frames (render.hip; the law in include/p3d_hip.h): one check and one launch
+// description for p3d_render_u8, the render stage and p3d_debug_render_u8 ------------------------------------------------
 void render_check(const char* who, const p3d_render* cfg, int n, int H, int W, const void* out) {
     if (!cfg || !out) throw P3dError("null argument");
     map_shape_check(who, n, H, W, P3D_RENDER_MAX_PIXELS, "2^28, the bound of the int32 offsets inside a map");
@@ -1964,30 +1969,24 @@ RenderArgs render_args(const p3d_render& cfg, int n, int H, int W) {
     a.rows = p.rows; a.cols = p.cols; a.chunk = p.chunk; a.blocks = p.blocks;
     return a;
 }
-// Elements of the buffers of one rendering: what the stage carves and what the hook puts between guards
-struct RenderSizes {
-    size_t sal, bgr, table;
-    explicit RenderSizes(const RenderArgs& a) : sal((size_t)a.n * (size_t)a.H * (size_t)a.W), bgr(sal * 3), table(256) {}
-};
 
 // ---- the render stage (declared above maps_u8_chain) ------------------------------------------------------------------------------
 RenderStage::RenderStage(const RenderRequest& r_) : ByteStage(r_), r(r_), a(render_args(*r_.cfg, r_.n, r_.H, r_.W)) {}
 void RenderStage::carve(Carve& c) {
-    const RenderSizes z(a);
-    df = r.frames ? c.take<unsigned char>(z.bgr) : nullptr;
-    dout = c.take<unsigned char>(z.bgr);
-    dtab = c.take<unsigned>(z.table);
+    df = r.frames ? c.input<unsigned char>(bgr(), 3) : nullptr;
+    dout = c.take<unsigned char>(bgr(), 5);
+    dtab = c.input<unsigned>(256);
 }
 void RenderStage::upload(hipStream_t s) {
     HIPCHECK(hipMemcpyAsync(dtab, r.cfg->table, 256 * sizeof(unsigned), hipMemcpyHostToDevice, s));
-    if (df) HIPCHECK(hipMemcpyAsync(df, r.frames, RenderSizes(a).bgr, hipMemcpyHostToDevice, s));
+    if (df) HIPCHECK(hipMemcpyAsync(df, r.frames, bgr(), hipMemcpyHostToDevice, s));
 }
 void RenderStage::launch(hipStream_t s, const unsigned char* sal, unsigned*) {
     a.sal = sal; a.frames = df ? df : r.frames_dev; a.out = dout; a.table = dtab;
     HIPCHECK(p3d_render_launch(a, s));
 }
 void RenderStage::results(hipStream_t s) {
-    HIPCHECK(hipMemcpyAsync(r.out, dout, RenderSizes(a).bgr, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpyAsync(r.out, dout, bgr(), hipMemcpyDeviceToHost, s));
 }
 }  // namespace
 extern "C" {
@@ -2011,19 +2010,12 @@ int p3d_debug_render_u8(int device, const unsigned char* sal, const unsigned cha
     const char* who = "debug_render_u8";
     if (!sal) throw P3dError("null argument");
     render_check(who, cfg, n, H, W, out);
-    if (offset < 0 || offset > 15) throw P3dError(std::string(who) + ": offset in [0, 15]");
+    offset_check(who, offset);
     metric_args(device, sal, cfg, 1, 1, out);
-    RenderArgs a = render_args(*cfg, n, H, W);
-    const RenderSizes sz(a);
-    // guards of 16 elements keep a 16-byte boundary at the data's start; the three byte buffers are then shifted
-    Guarded<unsigned char> ds(sz.sal, 16, (size_t)offset, sal), df(frames ? sz.bgr : 0, 16, (size_t)(3 * offset % 16), frames),
-        dout(sz.bgr, 16, (size_t)(5 * offset % 16), nullptr);
-    Guarded<unsigned> tab(sz.table, 16, 0, cfg->table);
-    a.sal = ds.data(); a.frames = frames ? df.data() : nullptr; a.out = dout.data(); a.table = tab.data();
-    HIPCHECK(p3d_render_launch(a, nullptr));
-    dout.back(out, who);
-    ds.unchanged(who); tab.unchanged(who);
-    if (frames) df.unchanged(who);
+    RenderRequest r{who, n, H, W};
+    r.cfg = cfg; r.frames = frames; r.out = out;
+    RenderStage stage(r);
+    stage_on_host_bytes(stage, sal, offset);
     API_END
 }
 
@@ -2080,8 +2072,8 @@ int p3d_video_render(p3d_handle* h, int first, int n, float scale, int H, int W,
 
 }  // extern "C"
 namespace {
-// ---- reframing around 8-bit maps (reframe.hip; the law in include/p3d_hip.h): one check, one table of buffer sizes and one launch
-// description for p3d_reframe_u8, the reframe stage and p3d_debug_reframe_u8 --------------------------------------------------------
+// ---- reframing around 8-bit maps (reframe.hip; the law in include/p3d_hip.h): one check, one launch description and one stage
+// (the table of buffer sizes is its own) for p3d_reframe_u8, the video entry, p3d_debug_reframe_u8 and p3d_reframe_shots_u8 ---------
 void reframe_check(const char* who, const p3d_reframe* cfg, int n, int H, int W, const void* track) {
     if (!cfg || !track) throw P3dError("null argument");
     map_shape_check(who, n, H, W, P3D_REFRAME_MAX_PIXELS, "2^23, the bound that keeps a mass in 32 bits");
@@ -2098,7 +2090,7 @@ ReframeArgs reframe_args(const p3d_reframe& cfg, int n, int H, int W) {
     a.maps_per_chunk = p.maps_per_chunk; a.search_blocks = p.search_blocks;
     return a;
 }
-// Elements of the buffers of one reframing: what the stage carves and what the hook puts between guards
+// Elements of the buffers of one reframing
 struct ReframeSizes {
     size_t sal, bgr, crop, pairs, masses, sat, best, part;
     explicit ReframeSizes(const ReframeArgs& a)
@@ -2110,26 +2102,26 @@ struct ReframeSizes {
 };
 
 // ---- the reframe stage (declared above maps_u8_chain) -----------------------------------------------------------------------------
-ReframeStage::ReframeStage(const ReframeRequest& r_) : ByteStage(r_), r(r_), a(reframe_args(*r_.cfg, r_.n, r_.H, r_.W)) {}
+ReframeStage::ReframeStage(const ReframeRequest& r_) : ByteStage(r_), r(r_), a(reframe_args(*r_.cfg, r_.n, r_.H, r_.W)), shots{r_.starts, r_.n_shots} {}
 void ReframeStage::carve(Carve& c) {
     const ReframeSizes z(a);
-    df = crops() && r.frames ? c.take<unsigned char>(z.bgr) : nullptr;
-    a.out = crops() ? c.take<unsigned char>(z.crop) : nullptr;
+    df = crops() && r.frames ? c.input<unsigned char>(z.bgr, 3) : nullptr;
+    a.out = crops() ? c.take<unsigned char>(z.crop, 5) : nullptr;
     a.track = c.take<int32_t>(z.pairs);
     a.raw = c.take<int32_t>(z.pairs);
     a.mass = c.take<uint32_t>(z.masses);
     a.sat = c.take<unsigned>(z.sat);
     a.best = c.take<unsigned>(z.best);
     a.part = c.take<unsigned>(z.part);
-    dstarts = r.starts ? c.take<int32_t>((size_t)r.n_shots) : nullptr;
+    shots.carve(c);
 }
 void ReframeStage::upload(hipStream_t s) {
     if (df) HIPCHECK(hipMemcpyAsync(df, r.frames, ReframeSizes(a).bgr, hipMemcpyHostToDevice, s));
-    if (dstarts) HIPCHECK(hipMemcpyAsync(dstarts, r.starts, (size_t)r.n_shots * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    shots.upload(s);
 }
 void ReframeStage::launch(hipStream_t s, const unsigned char* sal, unsigned*) {
     a.sal = sal; a.frames = !crops() ? nullptr : df ? df : r.frames_dev;
-    a.starts = dstarts; a.n_shots = dstarts ? r.n_shots : 0;
+    shots.bind(a);
     HIPCHECK(p3d_reframe_launch(a, s));
 }
 void ReframeStage::results(hipStream_t s) {
@@ -2164,22 +2156,29 @@ int p3d_debug_reframe_u8(int device, const unsigned char* sal, const unsigned ch
     if (!sal) throw P3dError("null argument");
     reframe_check(who, cfg, n, H, W, track);
     if ((frames == nullptr) != (out == nullptr)) throw P3dError(std::string(who) + ": out is given exactly when frames are");
-    if (offset < 0 || offset > 15) throw P3dError(std::string(who) + ": offset in [0, 15]");
+    offset_check(who, offset);
     metric_args(device, sal, cfg, 1, 1, track);
-    ReframeArgs a = reframe_args(*cfg, n, H, W);
-    const ReframeSizes sz(a);
-    // guards of 16 elements keep a 16-byte boundary at the data's start; the three byte buffers are then shifted
-    Guarded<unsigned char> ds(sz.sal, 16, (size_t)offset, sal), df(frames ? sz.bgr : 0, 16, (size_t)(3 * offset % 16), frames),
-        dout(frames ? sz.crop : 0, 16, (size_t)(5 * offset % 16), nullptr);
-    Guarded<int32_t> dtrack(sz.pairs, 16, 0, nullptr), draw(sz.pairs, 16, 0, nullptr);
-    Guarded<uint32_t> dmass(sz.masses, 16, 0, nullptr), dsat(sz.sat, 16, 0, nullptr), dbest(sz.best, 16, 0, nullptr), dpart(sz.part, 16, 0, nullptr);
-    a.sal = ds.data(); a.frames = frames ? df.data() : nullptr; a.out = frames ? dout.data() : nullptr;
-    a.track = dtrack.data(); a.raw = draw.data(); a.mass = dmass.data(); a.sat = dsat.data(); a.best = dbest.data(); a.part = dpart.data();
-    HIPCHECK(p3d_reframe_launch(a, nullptr));
-    dtrack.back(track, who); draw.back(raw, who); dmass.back(mass, who);
-    dsat.back(nullptr, who); dbest.back(nullptr, who); dpart.back(nullptr, who);
-    if (frames) { dout.back(out, who); df.unchanged(who); }
-    ds.unchanged(who);
+    ReframeRequest r{who, n, H, W};
+    r.cfg = cfg; r.frames = frames; r.track = track; r.raw = raw; r.mass = mass; r.out = out;
+    ReframeStage stage(r);
+    stage_on_host_bytes(stage, sal, offset);
+    API_END
+}
+
+int p3d_reframe_shots_u8(int device, const unsigned char* sal, const unsigned char* frames, int n, int H, int W, const p3d_reframe* cfg,
+                         const int32_t* starts, int n_shots, int offset, int32_t* track, int32_t* raw, uint32_t* mass, unsigned char* out) {
+    API_BEGIN
+    const char* who = "reframe_shots_u8";
+    if (!sal) throw P3dError("null argument");
+    reframe_check(who, cfg, n, H, W, track);
+    if ((frames == nullptr) != (out == nullptr)) throw P3dError(std::string(who) + ": out is given exactly when frames are");
+    shots_table_check(who, starts, n_shots, n);
+    offset_check(who, offset, true);
+    metric_args(device, sal, cfg, 1, 1, track);
+    ReframeRequest r{who, n, H, W};
+    r.cfg = cfg; r.frames = frames; r.track = track; r.raw = raw; r.mass = mass; r.out = out; r.starts = starts; r.n_shots = n_shots;
+    ReframeStage stage(r);
+    stage_on_host_bytes(stage, sal, offset);
     API_END
 }
 
@@ -2211,12 +2210,8 @@ int p3d_video_reframe(p3d_handle* h, int first, int n, float scale, int H, int W
     std::vector<int32_t> shots;                            // the installed table in frames of the call: its shots cut the track's filter
     video_stage_run(h, who, first, n, scale, maps_out, stage_ms, 3, [&]() -> ByteStage& {
         if (out && !frames) r.frames_dev = kept_source(h, who, first, n, H, W, "reframes");
-        if (!h->video.shots.empty()) {
-            shots.push_back(0);
-            for (int32_t st : h->video.shots)
-                if (st > first && st < first + n) shots.push_back(st - first);
-            r.starts = shots.data(); r.n_shots = (int)shots.size();
-        }
+        shots = video_shots_within(h, first, n);
+        if (!shots.empty()) { r.starts = shots.data(); r.n_shots = (int)shots.size(); }
         stage.reset(new ReframeStage(r));
         return *stage;
     });
@@ -2226,9 +2221,8 @@ int p3d_video_reframe(p3d_handle* h, int first, int n, float scale, int H, int W
 
 }  // extern "C"
 namespace {
-// ---- salient regions of 8-bit maps (regions.hip; the law in include/p3d_hip.h): one check, one table of buffer sizes and one launch
-// description for p3d_regions_u8, the regions stage and p3d_debug_regions_u8 --------------------------------------------------------
-void shots_table_check(const char* who, const int32_t* starts, int n_shots, int F);      // (net_shots.inc)
+// ---- salient regions of 8-bit maps (regions.hip; the law in include/p3d_hip.h): one check, one launch description and one stage
+// (the table of buffer sizes is its own) for p3d_regions_u8, the video entry and p3d_debug_regions_u8 -------------------------------
 RegionsCfg regions_check(const char* who, const int* cfg5, int n, int H, int W, const void* regions) {
     if (!cfg5 || !regions) throw P3dError("null argument");
     const RegionsCfg parsed{cfg5[P3D_REGIONS_GATE], cfg5[P3D_REGIONS_CONNECTIVITY], cfg5[P3D_REGIONS_MIN_AREA], cfg5[P3D_REGIONS_MAX_REGIONS], cfg5[P3D_REGIONS_LINK]};
@@ -2250,7 +2244,7 @@ RegionsArgs regions_args(const RegionsCfg& cfg, int n, int H, int W, bool labels
     a.maps_per_chunk = p.maps_per_chunk; a.tiles_y = p.tiles_y; a.tiles_x = p.tiles_x; a.slots = p.slots;
     return a;
 }
-// Elements of the buffers of one labelling: what the stage carves and what the hook puts between guards
+// Elements of the buffers of one labelling
 struct RegionsSizes {
     size_t sal, records, counts; RegionsPlan p;
     explicit RegionsSizes(const RegionsArgs& a)
@@ -2259,7 +2253,8 @@ struct RegionsSizes {
 };
 
 // ---- the regions stage (declared above maps_u8_chain) -----------------------------------------------------------------------------
-RegionsStage::RegionsStage(const RegionsRequest& r_) : ByteStage(r_), r(r_), a(regions_args(*r_.cfg, r_.n, r_.H, r_.W, r_.labels != nullptr)) {}
+RegionsStage::RegionsStage(const RegionsRequest& r_) : ByteStage(r_), r(r_), a(regions_args(*r_.cfg, r_.n, r_.H, r_.W, r_.labels != nullptr)),
+      shots{r_.starts, r_.n_shots} {}
 void RegionsStage::carve(Carve& c) {
     const RegionsSizes z(a);
     a.regions = c.take<int32_t>(z.records);
@@ -2272,14 +2267,13 @@ void RegionsStage::carve(Carve& c) {
     a.cnt = c.take<unsigned>((size_t)z.p.cnt_elems);
     a.ovl = z.p.ovl_elems ? c.take<unsigned>((size_t)z.p.ovl_elems) : nullptr;
     a.state = z.p.state_elems ? c.take<int32_t>((size_t)z.p.state_elems) : nullptr;
-    a.lab = z.p.lab_elems ? c.take<unsigned char>((size_t)z.p.lab_elems) : nullptr;
-    dstarts = r.starts ? c.take<int32_t>((size_t)r.n_shots) : nullptr;
+    a.lab = z.p.lab_elems ? c.take<unsigned char>((size_t)z.p.lab_elems, 5) : nullptr;
+    shots.carve(c);
 }
-void RegionsStage::upload(hipStream_t s) {
-    if (dstarts) HIPCHECK(hipMemcpyAsync(dstarts, r.starts, (size_t)r.n_shots * sizeof(int32_t), hipMemcpyHostToDevice, s));
-}
+void RegionsStage::upload(hipStream_t s) { shots.upload(s); }
 void RegionsStage::launch(hipStream_t s, const unsigned char* sal, unsigned*) {
-    a.sal = sal; a.starts = dstarts; a.n_shots = dstarts ? r.n_shots : 0;
+    a.sal = sal;
+    shots.bind(a);
     HIPCHECK(p3d_regions_launch(a, s));
 }
 void RegionsStage::results(hipStream_t s) {
@@ -2313,29 +2307,12 @@ int p3d_debug_regions_u8(int device, const unsigned char* sal, int n, int H, int
     if (!sal) throw P3dError("null argument");
     const RegionsCfg rc = regions_check(who, cfg, n, H, W, regions);
     if (starts || n_shots) shots_table_check(who, starts, n_shots, n);
-    if (offset < 0 || offset > 15) throw P3dError(std::string(who) + ": offset in [0, 15]");
+    offset_check(who, offset);
     metric_args(device, sal, cfg, 1, 1, regions);
-    RegionsArgs a = regions_args(rc, n, H, W, labels != nullptr);
-    const RegionsSizes sz(a);
-    const RegionsPlan& p = sz.p;
-    // guards of 16 elements keep a 16-byte boundary at the data's start; the two byte buffers are then shifted
-    Guarded<unsigned char> ds(sz.sal, 16, (size_t)offset, sal), dlab((size_t)p.lab_elems, 16, (size_t)(5 * offset % 16), nullptr),
-        drank((size_t)p.rank_elems, 16, 0, nullptr);
-    Guarded<int32_t> drec(sz.records, 16, 0, nullptr), dcounts(sz.counts, 16, 0, nullptr), dstate((size_t)p.state_elems, 16, 0, nullptr),
-        dst((size_t)n_shots, 16, 0, starts);
-    Guarded<unsigned> dpar((size_t)p.parent_elems, 16, 0, nullptr), dt32((size_t)p.tab32_elems, 16, 0, nullptr),
-        dcnt((size_t)p.cnt_elems, 16, 0, nullptr), dovl((size_t)p.ovl_elems, 16, 0, nullptr);
-    Guarded<unsigned long long> dt64((size_t)p.tab64_elems, 16, 0, nullptr), dkeys((size_t)p.key_elems, 16, 0, nullptr);
-    a.sal = ds.data(); a.regions = drec.data(); a.counts = dcounts.data(); a.lab = p.lab_elems ? dlab.data() : nullptr;
-    a.parent = dpar.data(); a.tab32 = dt32.data(); a.tab64 = dt64.data(); a.rank = drank.data(); a.keys = dkeys.data();
-    a.cnt = dcnt.data(); a.ovl = p.ovl_elems ? dovl.data() : nullptr; a.state = p.state_elems ? dstate.data() : nullptr;
-    a.starts = n_shots ? dst.data() : nullptr; a.n_shots = n_shots;
-    HIPCHECK(p3d_regions_launch(a, nullptr));
-    drec.back(regions, who); dcounts.back(counts, who);
-    dlab.back(labels, who);
-    dpar.back(nullptr, who); dt32.back(nullptr, who); dt64.back(nullptr, who); drank.back(nullptr, who);
-    dkeys.back(nullptr, who); dcnt.back(nullptr, who); dovl.back(nullptr, who); dstate.back(nullptr, who);
-    ds.unchanged(who); dst.unchanged(who);
+    RegionsRequest r{who, n, H, W};
+    r.cfg = &rc; r.regions = regions; r.counts = counts; r.labels = labels; r.starts = starts; r.n_shots = n_shots;
+    RegionsStage stage(r);
+    stage_on_host_bytes(stage, sal, offset);
     API_END
 }
 
@@ -2364,12 +2341,8 @@ int p3d_video_regions(p3d_handle* h, int first, int n, float scale, int H, int W
     std::unique_ptr<RegionsStage> stage;
     std::vector<int32_t> shots;                            // the installed table in frames of the call, cut as p3d_video_reframe cuts it
     video_stage_run(h, who, first, n, scale, maps_out, stage_ms, 3, [&]() -> ByteStage& {
-        if (!h->video.shots.empty()) {
-            shots.push_back(0);
-            for (int32_t st : h->video.shots)
-                if (st > first && st < first + n) shots.push_back(st - first);
-            r.starts = shots.data(); r.n_shots = (int)shots.size();
-        }
+        shots = video_shots_within(h, first, n);
+        if (!shots.empty()) { r.starts = shots.data(); r.n_shots = (int)shots.size(); }
         stage.reset(new RegionsStage(r));
         return *stage;
     });
@@ -2379,8 +2352,8 @@ int p3d_video_regions(p3d_handle* h, int first, int n, float scale, int H, int W
 
 }  // extern "C"
 namespace {
-// ---- QP maps of 8-bit maps (qpmap.hip; the law in include/p3d_hip.h): one check, one table of buffer sizes and one launch description
-// for p3d_qpmap_u8, the qpmap stage and p3d_debug_qpmap_u8 ---------------------------------------------------------------------------
+// ---- QP maps of 8-bit maps (qpmap.hip; the law in include/p3d_hip.h): one check, one launch description and one stage (the table of
+// buffer sizes is its own) for p3d_qpmap_u8, the video entry and p3d_debug_qpmap_u8 -------------------------------------------------
 QpmapCfg qpmap_check(const char* who, const int* cfg9, const int32_t* law, int n, int H, int W, const void* qp) {
     if (!cfg9 || !law || !qp) throw P3dError("null argument");
     const QpmapCfg c{cfg9[P3D_QPMAP_BLOCK], cfg9[P3D_QPMAP_PEAK_WEIGHT], cfg9[P3D_QPMAP_DILATE], cfg9[P3D_QPMAP_FALL], cfg9[P3D_QPMAP_RISE],
@@ -2406,7 +2379,7 @@ QpmapArgs qpmap_args(const QpmapCfg& c, int n, int H, int W) {
     a.maps_per_chunk = p.maps_per_chunk; a.Hb = p.Hb; a.Wb = p.Wb; a.tiles_x = p.tiles_x;
     return a;
 }
-// Elements of the buffers of one call: what the stage carves and what the hook puts between guards
+// Elements of the buffers of one call
 struct QpmapSizes {
     size_t sal, grid, stats, lev0;
     explicit QpmapSizes(const QpmapArgs& a)
@@ -2415,22 +2388,23 @@ struct QpmapSizes {
 };
 
 // ---- the qpmap stage (declared above maps_u8_chain) -------------------------------------------------------------------------------
-QpmapStage::QpmapStage(const QpmapRequest& r_) : ByteStage(r_), r(r_), a(qpmap_args(*r_.cfg, r_.n, r_.H, r_.W)) {}
+QpmapStage::QpmapStage(const QpmapRequest& r_) : ByteStage(r_), r(r_), a(qpmap_args(*r_.cfg, r_.n, r_.H, r_.W)), shots{r_.starts, r_.n_shots} {}
 void QpmapStage::carve(Carve& c) {
     const QpmapSizes z(a);
     a.qp = c.take<int32_t>(z.grid);
-    a.levels = r.levels ? c.take<unsigned char>(z.grid) : nullptr;
+    a.levels = r.levels ? c.take<unsigned char>(z.grid, 5) : nullptr;
     a.stats = r.stats ? c.take<int32_t>(z.stats) : nullptr;
     a.lev0 = c.take<unsigned char>(z.lev0);
-    dlaw = c.take<int32_t>(256);
-    dstarts = r.starts ? c.take<int32_t>((size_t)r.n_shots) : nullptr;
+    dlaw = c.input<int32_t>(256);
+    shots.carve(c);
 }
 void QpmapStage::upload(hipStream_t s) {
     HIPCHECK(hipMemcpyAsync(dlaw, r.law, 256 * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    if (dstarts) HIPCHECK(hipMemcpyAsync(dstarts, r.starts, (size_t)r.n_shots * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    shots.upload(s);
 }
 void QpmapStage::launch(hipStream_t s, const unsigned char* sal, unsigned*) {
-    a.sal = sal; a.law = dlaw; a.starts = dstarts; a.n_shots = dstarts ? r.n_shots : 0;
+    a.sal = sal; a.law = dlaw;
+    shots.bind(a);
     HIPCHECK(p3d_qpmap_launch(a, s));
 }
 void QpmapStage::results(hipStream_t s) {
@@ -2464,21 +2438,12 @@ int p3d_debug_qpmap_u8(int device, const unsigned char* sal, int n, int H, int W
     if (!sal) throw P3dError("null argument");
     const QpmapCfg qc = qpmap_check(who, cfg, law, n, H, W, qp);
     if (starts || n_shots) shots_table_check(who, starts, n_shots, n);
-    if (offset < 0 || offset > 15) throw P3dError(std::string(who) + ": offset in [0, 15]");
+    offset_check(who, offset);
     metric_args(device, sal, cfg, 1, 1, qp);
-    QpmapArgs a = qpmap_args(qc, n, H, W);
-    const QpmapSizes sz(a);
-    // guards of 16 elements keep a 16-byte boundary at the data's start; the two byte buffers are then shifted
-    Guarded<unsigned char> ds(sz.sal, 16, (size_t)offset, sal), dlev(levels ? sz.grid : 0, 16, (size_t)(5 * offset % 16), nullptr),
-        dlev0(sz.lev0, 16, 0, nullptr);
-    Guarded<int32_t> dqp(sz.grid, 16, 0, nullptr), dstats(stats ? sz.stats : 0, 16, 0, nullptr), dlaw(256, 16, 0, law),
-        dst((size_t)n_shots, 16, 0, starts);
-    a.sal = ds.data(); a.law = dlaw.data(); a.qp = dqp.data(); a.levels = levels ? dlev.data() : nullptr;
-    a.stats = stats ? dstats.data() : nullptr; a.lev0 = dlev0.data();
-    a.starts = n_shots ? dst.data() : nullptr; a.n_shots = n_shots;
-    HIPCHECK(p3d_qpmap_launch(a, nullptr));
-    dqp.back(qp, who); dlev.back(levels, who); dstats.back(stats, who); dlev0.back(nullptr, who);
-    ds.unchanged(who); dlaw.unchanged(who); dst.unchanged(who);
+    QpmapRequest r{who, n, H, W};
+    r.cfg = &qc; r.law = law; r.qp = qp; r.levels = levels; r.stats = stats; r.starts = starts; r.n_shots = n_shots;
+    QpmapStage stage(r);
+    stage_on_host_bytes(stage, sal, offset);
     API_END
 }
 
@@ -2507,12 +2472,8 @@ int p3d_video_qpmap(p3d_handle* h, int first, int n, float scale, int H, int W, 
     std::unique_ptr<QpmapStage> stage;
     std::vector<int32_t> shots;                            // the installed table in frames of the call, cut as p3d_video_reframe cuts it
     video_stage_run(h, who, first, n, scale, maps_out, stage_ms, 3, [&]() -> ByteStage& {
-        if (!h->video.shots.empty()) {
-            shots.push_back(0);
-            for (int32_t st : h->video.shots)
-                if (st > first && st < first + n) shots.push_back(st - first);
-            r.starts = shots.data(); r.n_shots = (int)shots.size();
-        }
+        shots = video_shots_within(h, first, n);
+        if (!shots.empty()) { r.starts = shots.data(); r.n_shots = (int)shots.size(); }
         stage.reset(new QpmapStage(r));
         return *stage;
     });
@@ -2522,8 +2483,9 @@ int p3d_video_qpmap(p3d_handle* h, int first, int n, float scale, int H, int W, 
 
 }  // extern "C"
 namespace {
-// ---- SPLIT SWEEP on 8-bit maps: AUC-Borji and shuffled AUC (score_auc_u8.hip; the law in include/p3d_hip.h): one check, one table
-// of buffer sizes and one launch sequence for the score stage and p3d_debug_score_sweep_u8 ------------------------------------------
+// ---- SPLIT SWEEP on 8-bit maps: AUC-Borji and shuffled AUC (score_auc_u8.hip; the law in include/p3d_hip.h): one check and one
+// launch sequence, in the score stage (the table of buffer sizes is its own), for p3d_score_sweep_u8, p3d_video_score_auc and
+// p3d_debug_score_sweep_u8 ------------------------------------------------------------------------------------------------------------
 ScoreSweepArgs sweep_args(const char* who, int n, long long n_pix, int n_rep, double step) {
     ScoreSweepArgs q;
     q.kmax = p3d_sweep_kmax(step);
@@ -2611,16 +2573,17 @@ ScoreStage::ScoreStage(const ScoreRequest& r_)
 size_t ScoreStage::counters() const { return ScoreSizes(a).counters; }
 void ScoreStage::carve(Carve& c) {
     const ScoreSizes z(a);
-    dd = r.density && r.flags ? c.take<unsigned char>(bytes) : nullptr;
-    dx = r.fixation ? c.take<unsigned char>(bytes) : nullptr;
+    dd = r.density && r.flags ? c.input<unsigned char>(bytes, 2) : nullptr;
+    dx = r.fixation ? c.input<unsigned char>(bytes, 3) : nullptr;
     a.tab = c.take<unsigned>(z.tab); a.lut = c.take<double>(z.lut); a.part = c.take<double>(z.part); a.out = c.take<double>(z.out);
     if (!sweep()) return;
     const SweepSizes w(q);
     q.lev = c.take<int>(w.lev); q.lad = c.take<unsigned>(w.lad); q.info = c.take<int>(w.info);
-    if (r.borji) { didx = c.take<int>(totB); dmetaB = c.take<long long>(metaB.size()); perB = c.take<double>(w.per_rep); }
+    if (r.borji) { didx = c.input<int>(totB); dmetaB = c.input<long long>(metaB.size()); perB = c.take<double>(w.per_rep); }
+    if (r.top) dtop = c.take<int>(w.per_rep);
     if (r.shuffled) {
-        dranks = c.take<int>(totS); dsel = c.take<int>(totS); dmeta3 = c.take<int>(meta3.size()); drows = c.take<int>((size_t)r.n);
-        dmetaS = c.take<long long>(metaS.size()); perS = c.take<double>(w.per_rep);
+        dranks = c.input<int>(totS); dsel = c.take<int>(totS); dmeta3 = c.input<int>(meta3.size()); drows = c.input<int>((size_t)r.n);
+        dmetaS = c.input<long long>(metaS.size()); perS = c.take<double>(w.per_rep);
     }
 }
 void ScoreStage::upload(hipStream_t s) {
@@ -2645,9 +2608,19 @@ void ScoreStage::prepare(hipStream_t s, const unsigned char* sal, unsigned* coun
     q.sal = sal; q.tab = a.tab;
     HIPCHECK(p3d_sweep_launch(SWEEP_PREP, q, s));
 }
+void ScoreStage::launch(hipStream_t s, const unsigned char* sal, unsigned* counters) {
+    prepare(s, sal, counters);
+    if (r.rows_checked) {
+        std::vector<int> nf_dev(SweepSizes(q).info);
+        HIPCHECK(hipDeviceSynchronize());
+        HIPCHECK(copy_now(nf_dev.data(), q.info, nf_dev.size() * sizeof(int), hipMemcpyDeviceToHost, s));      // nf, read back once
+        sweep_check_rows(r.who, nf_dev, r.idx_rows, r.n);
+    }
+    sweep_rest(s);
+}
 void ScoreStage::sweep_rest(hipStream_t s) {
     if (r.borji) {
-        q.idx = didx; q.meta = dmetaB; q.per_rep = perB;
+        q.idx = didx; q.meta = dmetaB; q.per_rep = perB; q.top = dtop;
         HIPCHECK(p3d_sweep_launch(SWEEP_RUN, q, s));
     }
     if (r.shuffled) {
@@ -2659,7 +2632,7 @@ void ScoreStage::sweep_rest(hipStream_t s) {
             HIPCHECK(p3d_fix_select_launch(e, s));
         }
         ScoreSweepArgs qs = q;
-        qs.idx = dsel; qs.meta = dmetaS; qs.per_rep = perS;
+        qs.idx = dsel; qs.meta = dmetaS; qs.per_rep = perS; qs.top = nullptr;
         HIPCHECK(p3d_sweep_launch(SWEEP_RUN, qs, s));
     }
     sweeps.mark(1, s);
@@ -2669,6 +2642,7 @@ void ScoreStage::results(hipStream_t s) {
     if (!sweep()) return;
     const SweepSizes w(q);
     if (r.borji) HIPCHECK(hipMemcpyAsync(r.borji, perB, w.per_rep * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (dtop) HIPCHECK(hipMemcpyAsync(r.top, dtop, w.per_rep * sizeof(int), hipMemcpyDeviceToHost, s));
     if (r.shuffled) HIPCHECK(hipMemcpyAsync(r.shuffled, perS, w.per_rep * sizeof(double), hipMemcpyDeviceToHost, s));
     if (!nf.empty()) HIPCHECK(hipMemcpyAsync(info.data(), q.info, info.size() * sizeof(int), hipMemcpyDeviceToHost, s));      // (to hold against the host's)
 }
@@ -2701,20 +2675,10 @@ int p3d_score_sweep_u8(int device, const unsigned char* sal, const unsigned char
     sweep_args(who, n, (long long)H * W, n_rep, step);      // (the step and n_rep are refused first, as in the hook)
     sweep_op_shape(who, sal, fixation, n, H, W, n_rows, per_rep);
     ScoreRequest r{who, n, H, W};
-    r.fixation = fixation; r.idx = idx; r.idx_rows = n_rows; r.borji = per_rep; r.n_rep = n_rep; r.step = step;
+    r.fixation = fixation; r.idx = idx; r.idx_rows = n_rows; r.borji = per_rep; r.n_rep = n_rep; r.step = step; r.rows_checked = true;
     ScoreStage stage(r);
     metric_args(device, sal, fixation, 1, 1, per_rep);
-    DevArr<unsigned char> ds(stage.bytes, sal);
-    unsigned* const counters = carve_scratch(nullptr, stage.counters(), [&](Carve& c) { stage.carve(c); });
-    stage.upload(nullptr);
-    stage.prepare(nullptr, ds.p, counters);
-    HIPCHECK(hipDeviceSynchronize());
-    std::vector<int> info(SweepSizes(stage.q).info);
-    HIPCHECK(copy_now(info.data(), stage.q.info, info.size() * sizeof(int), hipMemcpyDeviceToHost, nullptr));      // nf, read back once
-    sweep_check_rows(who, info, n_rows, n);
-    stage.sweep_rest(nullptr);
-    stage.results(nullptr);
-    HIPCHECK(hipDeviceSynchronize());
+    stage_on_host_bytes(stage, sal);
     API_END
 }
 
@@ -2722,47 +2686,20 @@ int p3d_debug_score_sweep_u8(int device, const unsigned char* sal, const unsigne
                              const int* n_rows, int n_rep, double step, int offset, int* lev_out, int* top_out, double* per_rep) {
     API_BEGIN
     const char* who = "debug_score_sweep_u8";
-    const long long N = (long long)H * W;
-    ScoreSweepArgs q = sweep_args(who, n, N, n_rep, step);
-    size_t total = 0;
+    sweep_args(who, n, (long long)H * W, n_rep, step);
     sweep_op_shape(who, sal, fixation, n, H, W, n_rows, per_rep);
-    const std::vector<long long> meta = sweep_meta(who, n_rows, n, n_rep, total);
-    if (total > 0 && !idx) throw P3dError("null argument");
-    check_indices(idx, total, N, who);
+    ScoreRequest r{who, n, H, W};
+    r.fixation = fixation; r.idx = idx; r.idx_rows = n_rows; r.borji = per_rep; r.n_rep = n_rep; r.step = step; r.rows_checked = true;
+    r.top = top_out;
+    ScoreStage stage(r);
     if (!lev_out || !top_out) throw P3dError("null argument");
-    if (offset < 0 || offset > 15) throw P3dError(std::string(who) + ": offset in [0, 15]");
+    offset_check(who, offset);
     metric_args(device, sal, fixation, 1, 1, per_rep);
-    const size_t bytes = (size_t)n * (size_t)N;
-    ScoreArgs a = score_args(n, N, 0, P3D_SCORE_TIES_REFERENCE);
-    const ScoreSizes sz(a);
-    const SweepSizes w(q);
-    // as p3d_debug_score_u8: guards of 16 elements, the sources shifted off the boundary (no density map here)
-    Guarded<unsigned char> ds(bytes, 16, (size_t)offset, sal), dx(bytes, 16, (size_t)(3 * offset % 16), fixation);
-    Guarded<unsigned> tab(sz.tab, 16, 0, nullptr), counter(sz.counters, 16, 0, nullptr), lad(w.lad, 16, 0, nullptr);
-    Guarded<double> lut(sz.lut, 16, 0, nullptr), part(sz.part, 16, 0, nullptr), dout(sz.out, 16, 0, nullptr), dper(w.per_rep, 16, 0, nullptr);
-    Guarded<int> lev(w.lev, 16, 0, nullptr), dinfo(w.info, 16, 0, nullptr), dtop(w.per_rep, 16, 0, nullptr), didx(total, 16, 0, total ? idx : nullptr);
-    Guarded<long long> dmeta(meta.size(), 16, 0, meta.data());
-    a.sal = ds.data(); a.fix = dx.data();
-    a.tab = tab.data(); a.counter = counter.data(); a.lut = lut.data(); a.part = part.data(); a.out = dout.data();
-    q.sal = ds.data(); q.tab = tab.data(); q.lev = lev.data(); q.lad = lad.data(); q.info = dinfo.data();
-    q.idx = didx.data(); q.meta = dmeta.data(); q.top = dtop.data(); q.per_rep = dper.data();
-    score_sequence(a, nullptr);
-    HIPCHECK(p3d_sweep_launch(SWEEP_PREP, q, nullptr));
-    std::vector<int> info(w.info), levs(w.lev), tops(w.per_rep);
-    std::vector<double> per(w.per_rep);
-    dinfo.back(info.data(), who);
-    sweep_check_rows(who, info, n_rows, n);
-    HIPCHECK(p3d_sweep_launch(SWEEP_RUN, q, nullptr));
-    std::vector<unsigned> zero(sz.counters, 1u);
-    lev.back(levs.data(), who); dtop.back(tops.data(), who); dper.back(per.data(), who);
-    tab.back(nullptr, who); lad.back(nullptr, who); dinfo.back(nullptr, who); dout.back(nullptr, who);
-    counter.back(zero.data(), who);
-    lut.unchanged(who); part.unchanged(who);
-    ds.unchanged(who); dx.unchanged(who); didx.unchanged(who); dmeta.unchanged(who);
-    for (unsigned z : zero) if (z != 0u) throw P3dError(std::string(who) + ": an arrival counter was left at " + std::to_string(z));
-    std::copy(levs.begin(), levs.end(), lev_out);
-    std::copy(tops.begin(), tops.end(), top_out);
-    std::copy(per.begin(), per.end(), per_rep);
+    stage_on_host_bytes(stage, sal, offset, [&](const GuardedRun& g) {
+        g.read(stage.q.lev, lev_out);
+        g.unchanged(stage.a.lut); g.unchanged(stage.a.part);      // no pass B: nothing of its was written
+        g.counters_at_zero();
+    });
     API_END
 }
 
@@ -2958,7 +2895,7 @@ int p3d_debug_video_plan(int mode, int F, int T, int B, int last_start, const in
     API_END
 }
 
-// ---- temporal smoothing of the video's maps at read-out (include/p3d_hip.h; the handle's part in net_sched.inc, temporal.hip) --
+// ---- temporal smoothing of the video's maps at read-out (include/p3d_hip.h; the handle's part in net_video.inc, temporal.hip) --
 int p3d_set_video_temporal(p3d_handle* h, const p3d_video_temporal* cfg) {
     API_BEGIN
     if (!h) throw P3dError("null handle");
@@ -3092,7 +3029,7 @@ uint32_t p3d_crc32c(const void* data, size_t n, uint32_t crc) {
     return c ^ 0xFFFFFFFFu;
 }
 
-// ---- resident training set (include/p3d_hip.h; the handle's part in net_sched.inc, the kernel in trainset.hip) ------------------
+// ---- resident training set (include/p3d_hip.h; the handle's part in net_trainset.inc, the kernel in trainset.hip) ------------------
 int p3d_trainset_open(p3d_handle* h, int n_videos, const int* frames, int frame_format, int flags, const float mean_rgb[3]) {
     API_BEGIN
     if (!h || !frames || !mean_rgb) throw P3dError("null argument");

@@ -90,7 +90,7 @@ int p3d_debug_shot_distances_u8(int device, const unsigned char* frames, int n, 
     const char* who = "debug_shot_distances_u8";
     if (!frames || !D) throw P3dError("null argument");
     shots_shape_check(who, n, H, W, grid_y, grid_x);
-    if (offset < 0 || offset > 15) throw P3dError(std::string(who) + ": offset in [0, 15]");
+    offset_check(who, offset);
     if (ballot != 0 && ballot != 1) throw P3dError(std::string(who) + ": ballot is 0 or 1");
     metric_args(device, frames, frames, 1, 1, D);
     ShotsArgs a = shots_args(n, H, W, grid_y, grid_x, ballot);
@@ -179,40 +179,6 @@ int p3d_shot_cuts(int device, const uint32_t* D, int F, int64_t P, const int cfg
     API_END
 }
 
-int p3d_reframe_shots_u8(int device, const unsigned char* sal, const unsigned char* frames, int n, int H, int W, const p3d_reframe* cfg,
-                         const int32_t* starts, int n_shots, int offset, int32_t* track, int32_t* raw, uint32_t* mass, unsigned char* out) {
-    API_BEGIN
-    const char* who = "reframe_shots_u8";
-    if (!sal) throw P3dError("null argument");
-    reframe_check(who, cfg, n, H, W, track);
-    if ((frames == nullptr) != (out == nullptr)) throw P3dError(std::string(who) + ": out is given exactly when frames are");
-    shots_table_check(who, starts, n_shots, n);
-    if (offset < -1 || offset > 15) throw P3dError(std::string(who) + ": offset in [0, 15], or -1 for the stage on the stream's scratch");
-    metric_args(device, sal, cfg, 1, 1, track);
-    if (offset < 0) {
-        ReframeRequest r{who, n, H, W};
-        r.cfg = cfg; r.frames = frames; r.track = track; r.raw = raw; r.mass = mass; r.out = out; r.starts = starts; r.n_shots = n_shots;
-        ReframeStage stage(r);
-        stage_on_host_bytes(stage, sal);
-        return 0;
-    }
-    ReframeArgs a = reframe_args(*cfg, n, H, W);
-    const ReframeSizes sz(a);
-    Guarded<unsigned char> ds(sz.sal, 16, (size_t)offset, sal), df(frames ? sz.bgr : 0, 16, (size_t)(3 * offset % 16), frames),
-        dout(frames ? sz.crop : 0, 16, (size_t)(5 * offset % 16), nullptr);
-    Guarded<int32_t> dtrack(sz.pairs, 16, 0, nullptr), draw(sz.pairs, 16, 0, nullptr), dst((size_t)n_shots, 16, 0, starts);
-    Guarded<uint32_t> dmass(sz.masses, 16, 0, nullptr), dsat(sz.sat, 16, 0, nullptr), dbest(sz.best, 16, 0, nullptr), dpart(sz.part, 16, 0, nullptr);
-    a.sal = ds.data(); a.frames = frames ? df.data() : nullptr; a.out = frames ? dout.data() : nullptr;
-    a.track = dtrack.data(); a.raw = draw.data(); a.mass = dmass.data(); a.sat = dsat.data(); a.best = dbest.data(); a.part = dpart.data();
-    a.starts = dst.data(); a.n_shots = n_shots;
-    HIPCHECK(p3d_reframe_launch(a, nullptr));
-    dtrack.back(track, who); draw.back(raw, who); dmass.back(mass, who);
-    dsat.back(nullptr, who); dbest.back(nullptr, who); dpart.back(nullptr, who);
-    if (frames) { dout.back(out, who); df.unchanged(who); }
-    ds.unchanged(who); dst.unchanged(who);
-    API_END
-}
-
 int p3d_temporal_filter_shots(int device, int mode, const p3d_video_temporal* cfg, const float* store, const int32_t* count, int F, int64_t hw,
                               const int32_t* starts, int n_shots, int first, int n, int offset, float* out) {
     API_BEGIN
@@ -267,7 +233,7 @@ int p3d_debug_shot_signals_u8(int device, const unsigned char* frames, int n, in
     if (!frames || !D || !E || !v) throw P3dError("null argument");
     shots_shape_check(who, n, H, W, grid_y, grid_x);
     shots_lag_check(who, lag);
-    if (offset < 0 || offset > 15) throw P3dError(std::string(who) + ": offset in [0, 15]");
+    offset_check(who, offset);
     metric_args(device, frames, frames, 1, 1, D);
     ShotSignalsArgs a = shot_signals_args(n, H, W, grid_y, grid_x, lag);
     Guarded<unsigned char> df((size_t)n * H * W * 3, 16, (size_t)offset, frames);
