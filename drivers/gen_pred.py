@@ -54,7 +54,11 @@ DIR/<video>/qp.npy, int32 [F, Hb, Wb]: one signed quantiser offset per `--qp-blo
 maps"), limited from frame to frame by `--qp-fall` / `--qp-rise` inside the shots of `--shots`; stats.npy, int32 [F, 4] (the smallest
 and largest offset, the area-weighted sums before and after the balance), on `--qp-levels` levels.npy, uint8 [F, Hb, Wb], and qp.txt,
 one line a frame: the frame's number from 1, then its Hb * Wb offsets in raster order, separated by spaces.  That layout is this
-driver's own; no particular encoder's input format is promised."""
+driver's own; no particular encoder's input format is promised.  `--prefilter DIR` (an addition, needs `--resident`, keeps the decoded
+frames on the device) writes DIR/<video>/frame_<k>.png: every frame at its own size, low-pass filtered where its map is not salient
+and bit-exact where it is (P3DSession.video_prefilter, the law is include/p3d_hip.h's "Pre-filtering frames by their 8-bit maps"), for
+any encoder to take; grid.npy, int32 [F, Hb, Wb], holds the strength 0 .. 64 of every `--pf-block` block, limited from frame to frame
+by `--pf-fall` / `--pf-rise` inside the shots of `--shots`."""
 import argparse
 import glob
 import os
@@ -536,6 +540,25 @@ def parse_args(argv=None):
                    "area-weighted mean is 0")
     p.add_argument("--qp-levels", action="store_true", help="[addition] --qpmap: also write DIR/<video>/levels.npy, uint8 [F, Hb, Wb]: the "
                    "blocks' dilated levels")
+    p.add_argument("--prefilter", type=str, default="", metavar="DIR", help="[addition] needs --resident: keep every video's decoded frames on "
+                   "the device and write DIR/<video>/frame_<k>.png, the frame low-pass filtered where its map is not salient and bit-exact "
+                   "where it is, on the device (P3DSession.video_prefilter, one call per video, at the frames' own size), and grid.npy, "
+                   "int32 [F, Hb, Wb]: the strength 0 .. 64 of every block.  Uses the table of --shots when one is set")
+    p.add_argument("--pf-block", type=int, default=16, metavar="B", help="[addition] --prefilter: the side of a strength block, 8, 16, 32, 64 or 128 pixels (16)")
+    p.add_argument("--pf-radius", type=int, default=4, metavar="R", help="[addition] --prefilter: a box pass reaches R pixels either way, 1 .. 16 (4)")
+    p.add_argument("--pf-passes", type=int, default=2, metavar="P", help="[addition] --prefilter: box passes, 1 .. 3 (2)")
+    p.add_argument("--pf-gate", type=int, default=128, metavar="LEVEL", help="[addition] --prefilter: levels from it on are left alone, 0 .. 255 (128)")
+    p.add_argument("--pf-full", type=int, default=16, metavar="LEVEL", help="[addition] --prefilter: levels up to it get --pf-strength, 0 .. --pf-gate (16)")
+    p.add_argument("--pf-gamma", type=float, default=1.0, metavar="G", help="[addition] --prefilter: the law's exponent between the two, > 0 (1: a straight line)")
+    p.add_argument("--pf-strength", type=int, default=64, metavar="S", help="[addition] --prefilter: the largest strength, 0 .. 64 (64: the full low-pass)")
+    p.add_argument("--pf-dilate", type=int, default=1, metavar="BLOCKS", help="[addition] --prefilter: a block takes the largest level within this "
+                   "many blocks, 0 .. 8 (1)")
+    p.add_argument("--pf-peak-weight", type=int, default=128, metavar="Q8", help="[addition] --prefilter: a block's level is Q8 / 256 of its largest "
+                   "byte and the rest its mean, 0 .. 256 (128)")
+    p.add_argument("--pf-rise", type=int, default=0, metavar="STEP", help="[addition] --prefilter: a block's strength rises by at most STEP a frame, "
+                   "0 .. 64, 0: unlimited (0)")
+    p.add_argument("--pf-fall", type=int, default=0, metavar="STEP", help="[addition] --prefilter: a block's strength falls by at most STEP a frame, "
+                   "0 .. 64, 0: unlimited (0)")
     p.add_argument("--shots", type=str, default="", metavar="detect|FILE.npy", help="[addition] needs --resident: a shot table for every video, "
                    "installed before its maps are read (P3DSession.video_set_shots) -- --temporal then filters inside the shots and --reframe "
                    "smooths its track inside them.  detect: the hard cuts found on the device in the decoded frames "
@@ -604,6 +627,7 @@ def parse_args(argv=None):
     reframe_args(args, p.error)
     regions_args(args, p.error)
     qpmap_args(args, p.error)
+    prefilter_args(args, p.error)
     shots_args(args, p.error)
     return args
 
@@ -764,6 +788,67 @@ def qpmap_args(args, error):
     args.qpmap_kw = dict(block=args.qp_block, peak_weight=args.qp_peak_weight, dilate=args.qp_dilate, fall=args.qp_fall, rise=args.qp_rise,
                          lo=args.qp_min, hi=args.qp_max, gate=args.qp_gate, gamma=args.qp_gamma, balance=not args.qp_no_balance,
                          levels=args.qp_levels)
+
+
+PREFILTER_DEFAULTS = dict(pf_block=16, pf_radius=4, pf_passes=2, pf_gate=128, pf_full=16, pf_gamma=1.0, pf_strength=64, pf_dilate=1,
+                          pf_peak_weight=128, pf_rise=0, pf_fall=0)
+
+
+def prefilter_args(args, error):
+    """Checks --prefilter and its values as P3DSession.video_prefilter and dataflow.prefilter_law would refuse them, before anything
+    runs; error(message) does not return.  Leaves the keyword arguments of prefilter_video_resident in args.prefilter_kw (None without
+    --prefilter)."""
+    args.prefilter_kw = None
+    if not args.prefilter:
+        if any(getattr(args, k) != v for k, v in PREFILTER_DEFAULTS.items()):
+            error("--pf-block / -radius / -passes / -gate / -full / -gamma / -strength / -dilate / -peak-weight / -rise / -fall need --prefilter DIR")
+        return
+    if not args.resident:
+        error("--prefilter needs --resident: the frames and the maps stay on the device")
+    if args.pf_block not in (8, 16, 32, 64, 128):
+        error("--pf-block is 8, 16, 32, 64 or 128")
+    if not 1 <= args.pf_radius <= 16 or not 1 <= args.pf_passes <= 3:
+        error("--pf-radius is 1 .. 16 and --pf-passes 1 .. 3")
+    if not 0 <= args.pf_full <= args.pf_gate <= 255:
+        error("0 <= --pf-full <= --pf-gate <= 255")
+    if not (np.isfinite(args.pf_gamma) and args.pf_gamma > 0.):
+        error("--pf-gamma is finite and > 0")
+    if not 0 <= args.pf_strength <= 64:
+        error("--pf-strength is 0 .. 64")
+    if not 0 <= args.pf_peak_weight <= 256:
+        error("--pf-peak-weight is 0 .. 256")
+    if not 0 <= args.pf_dilate <= 8:
+        error("--pf-dilate is 0 .. 8 blocks")
+    if not 0 <= args.pf_fall <= 64 or not 0 <= args.pf_rise <= 64:
+        error("--pf-fall and --pf-rise are 0 .. 64 (0: unlimited)")
+    args.prefilter_kw = dict(block=args.pf_block, radius=args.pf_radius, passes=args.pf_passes, gate=args.pf_gate, full=args.pf_full,
+                             gamma=args.pf_gamma, strength=args.pf_strength, dilate=args.pf_dilate, peak_weight=args.pf_peak_weight,
+                             rise=args.pf_rise, fall=args.pf_fall)
+
+
+def prefilter_video_resident(sess, F, video_dir, prefilter, writers=4):
+    """--prefilter: the open video's frames low-pass filtered away from their saliency on the device (P3DSession.video_prefilter on
+    the kept source, at the video's own size) -> <video_dir>/frame_<k>.png, k = 1..F, colour, and <video_dir>/grid.npy, int32
+    [F, Hb, Wb].  ONE call for the whole video: the limiter sees every frame.  Returns milliseconds: gpu (wall time of the call), the
+    device stages, encode (thread time), the number of files, and strength: the area-weighted mean of g / 64 over the video,
+    computed here on the host from the grid."""
+    from sap3d_tensorflow_amd import dataflow
+    H0, W0 = sess.video_source_info()["size"]
+    B = prefilter["block"]
+    law = dataflow.prefilter_law(prefilter["gate"], prefilter["full"], prefilter["gamma"], prefilter["strength"])
+    t0 = time.perf_counter()
+    out, grid, _, ms = sess.video_prefilter(0, F, H0, W0, law, block=B, peak_weight=prefilter["peak_weight"], dilate=prefilter["dilate"],
+                                            fall=prefilter["fall"], rise=prefilter["rise"], radius=prefilter["radius"], passes=prefilter["passes"])
+    t = dict(gpu=(time.perf_counter() - t0) * 1e3, device=ms["device"], prefilter=ms["prefilter"], files=F)
+    np.save(os.path.join(video_dir, "grid.npy"), grid)
+    hs = np.minimum(H0, (np.arange(grid.shape[1]) + 1) * B) - np.arange(grid.shape[1]) * B
+    ws = np.minimum(W0, (np.arange(grid.shape[2]) + 1) * B) - np.arange(grid.shape[2]) * B
+    t["strength"] = float((grid.astype(np.float64) * (hs[:, None] * ws[None, :])[None]).sum() / (64.0 * F * H0 * W0))
+    with ChunkWriter(writers, lambda f, m: save_color_image(os.path.join(video_dir, "frame_%d.png" % (f + 1)), m)) as w:
+        for first in range(0, F, 16):
+            w.hand_over(range(first, min(F, first + 16)), out[first:first + 16])
+    t["encode"] = w.encode_ms
+    return t
 
 
 def write_qp_text(path, qp):
@@ -974,7 +1059,10 @@ def run_resident(sess, args, path):
     if reframe_dir:
         os.makedirs(reframe_dir, exist_ok=True)
     detect = bool(args.shots_kw and args.shots_kw["detect"])
-    keep = bool(render_dir or reframe_dir or detect)
+    prefilter_dir = os.path.join(args.prefilter, name) if args.prefilter else None
+    if prefilter_dir:
+        os.makedirs(prefilter_dir, exist_ok=True)
+    keep = bool(render_dir or reframe_dir or detect or prefilter_dir)
     if args.shot_windows:      # the table goes in before the windows are cut, and they stay inside its shots
         F = predict_video_resident(sess, np.load(path), args.batch, args.stride, args.overlap, times, keep_source=keep,
                                    shot_windows=lambda F: shots_video_resident(sess, F, args.out, name, args.shots_kw))
@@ -1046,6 +1134,10 @@ def run_resident(sess, args, path):
         tq = qpmap_video_resident(sess, F, qpmap_dir, tuple(args.size), args.qpmap_kw)
         print(name, "%d x %d offsets in [%d, %d] over %d frames: qp.npy, stats.npy, qp.txt%s in %s"
               % (tq["grid"] + (tq["lo"], tq["hi"], F, ", levels.npy" if args.qpmap_kw["levels"] else "", qpmap_dir)))
+    tp = None
+    if prefilter_dir:
+        tp = prefilter_video_resident(sess, F, prefilter_dir, args.prefilter_kw, writers=args.writers)
+        print(name, "%d pre-filtered png files and grid.npy in %s, mean strength %.4f" % (tp["files"], prefilter_dir, tp["strength"]))
     temporal_ms = sess.video_temporal_last_ms() if args.temporal != "off" and args.time else None
     sess.close_video()
     if args.time:
@@ -1071,6 +1163,9 @@ def run_resident(sess, args, path):
             print("  %s: regions %.1f ms (maps %.2f ms, regions launches %.3f ms on the device)" % (name, tg["gpu"], tg["device"], tg["regions"]))
         if tq is not None:
             print("  %s: qpmap %.1f ms (maps %.2f ms, qpmap launches %.3f ms on the device)" % (name, tq["gpu"], tq["device"], tq["qpmap"]))
+        if tp is not None:
+            print("  %s: prefilter %.1f ms (maps %.2f ms, prefilter launches %.3f ms on the device) | encode %.1f ms thread time on %d writers"
+                  % (name, tp["gpu"], tp["device"], tp["prefilter"], tp["encode"], args.writers))
     return means
 
 

@@ -1807,6 +1807,70 @@ int p3d_debug_qpmap_u8(int device, const unsigned char* sal, int n, int H, int W
 int p3d_debug_qpmap_plan(int H, int W, int block, int n, int* strip_rows, int* tile_cols, int* blocks_per_map, int* maps_per_chunk,
                          int64_t* scratch_bytes);
 
+/* ---- Pre-filtering frames by their 8-bit maps (an ADDITION: the other way to spend fewer bits where nobody looks, which needs no
+ * cooperation from an encoder -- the frame is low-pass filtered where the viewers do not look and left bit-exact where they do, the
+ * strength changing smoothly in space and slowly in time; any encoder takes the result).  OFF until called: every other entry point
+ * issues what it issued before and returns the same bits.  PARITY UNPINNED: the reference has nothing of the kind; this text is the
+ * contract and tests/prefilter_ref.py replays it in numpy.  Integer arithmetic throughout, no floating point: no order can show, and
+ * every test holds to 0.  Nothing here drives an encoder or says what bitrate one saves.
+ * Per frame: s [H][W] bytes, the saliency map; frame [H][W][3] bytes in cv2's B, G, R order.  -> out [H][W][3] bytes.
+ *   CONFIG      seven ints in the order of the P3D_PREFILTER_* indices below (an array, `const int cfg[P3D_PREFILTER_FIELDS]`, as the
+ *               QP maps' configuration is): block (B), one of 8, 16, 32, 64, 128; peak_weight 0 .. 256; dilate 0 .. 8 blocks; fall and
+ *               rise 0 .. 64, 0 = unlimited; radius (R) 1 .. 16; passes (P) 1 .. 3.  A law `const int32_t law[256]` comes with it,
+ *               every entry in 0 .. 64: 64 is the full low-pass, 0 leaves the frame alone, and a law meant for use falls with the
+ *               level.
+ *   LIMITS      1 <= n <= 65535 maps a call; H * W <= 2^23.  Frames are required: there is no frame-less form.
+ *   STRENGTH GRID  g [n][Hb][Wb] is, by definition, the qp that "QP maps of 8-bit maps" above gives for the same maps with block = B,
+ *               the same peak_weight, dilate, fall and rise, balance = 0, target = 0, lo = 0, hi = 64, this law and this shot table:
+ *               GRID, LEVEL, DILATE, LAW and LIMIT of that section, word for word.  So 0 <= g <= 64; rise bounds how fast the
+ *               smoothing comes on from frame to frame, fall how fast it goes away, and neither crosses the start of a shot.
+ *   PIXEL WEIGHT  interpolates g between block centres; an edge block's centre is taken as if the block were whole.  D = 2 B.  For
+ *               row y: u = 2 y + 1 - B, j0 = floor(u / D) (towards minus infinity), fy = u - D j0 in 0 .. D - 1,
+ *               ja = clamp(j0, 0, Hb - 1), jb = clamp(j0 + 1, 0, Hb - 1); for column x: i0, fx, ia, ib likewise from W and Wb.
+ *               Wn(y, x) = (D - fy)(D - fx) g[ja][ia] + (D - fy) fx g[ja][ib] + fy (D - fx) g[jb][ia] + fy fx g[jb][ib], in 0 .. Q,
+ *               Q = 64 D^2 = 2^(8 + 2 log2 B).
+ *   LOW-PASS    per channel k: l_0 = frame; for p = 1 .. P, SUM = the sum of l_{p-1}(clamp(y + dy, 0, H - 1), clamp(x + dx, 0, W - 1), k)
+ *               over |dy| <= R and |dx| <= R, A = (2 R + 1)^2, l_p(y, x, k) = (2 SUM + A) / (2 A), integer division; low = l_P.
+ *               Borders replicate, so A is one constant and a radius beyond the frame is legal; SUM <= 255 * 1089.  Each pass
+ *               rounds once, on the 2-D sum: the sum is separable, the rounding is not.
+ *   BLEND       out_k = (frame_k (Q - Wn) + low_k Wn + Q / 2) >> log2 Q; the largest numerator is below 2^31.  Wn = 0 returns the
+ *               frame's bytes, Wn = Q returns low, and a constant frame returns itself under any setting.
+ *   OUTPUTS     out [n][H][W][3] bytes.  grid [n][Hb][Wb] int32_t: g, or NULL.
+ * p3d_prefilter_u8   op level, host arrays: sal [n][H][W], frames [n][H][W][3], law [256], starts [n_shots] or NULL (then n_shots = 0)
+ *                    -> out, grid (or NULL).
+ * p3d_video_prefilter  filters frames first .. first + n - 1 of the open video at H x W.  The saliency bytes are, bit for bit, what
+ *                    p3d_video_maps_u8(first, n, scale, H, W) returns under the handle's current settings; maps_out (or NULL)
+ *                    receives them.  frames: host [n][H][W][3], uploaded as p3d_video_render uploads its frames, or NULL for the
+ *                    kept source -- then H = H0 and W = W0 are required and every frame of the range must have a source.  The
+ *                    video's shot table, if one is set, is cut to the range exactly as p3d_video_qpmap cuts it.  Validated as
+ *                    p3d_video_maps_u8 validates, plus cfg, the law, LIMITS and out == NULL, all before any launch, upload or scratch
+ *                    request: a refusal changes nothing.  stage_ms (or NULL) [3]: the frames' upload (0 with the kept source), the
+ *                    maps' chain, the prefilter launches (the grid's and the filter's).  Returns synchronised.
+ * TEST HOOKS (tests/test_gpu_prefilter.py):
+ * p3d_debug_prefilter_u8  the same launch description with every device buffer, the scratch included, between guards: sal starts
+ *                    `offset` bytes (0 .. 15) past a 16-byte boundary, frames (3 offset) mod 16 and out (5 offset) mod 16 bytes past
+ *                    one; -1 if a guard or an input changed.
+ * p3d_debug_prefilter_plan  host only, no HIP call, for n frames of H x W with block B, radius R and P passes: the tile of output
+ *                    rows and columns a block takes (the first tile starts at (0, 0)); the halo in pixels a block reads round its
+ *                    tile; fused = 1 when the P passes run inside one launch (halo = R P), 0 when each is a launch through memory
+ *                    (halo = R); the blocks a frame; the frames whose intermediate passes are held at a time (a call of more frames
+ *                    runs in chunks of that many); the bytes of scratch of those intermediate passes; and mul and shift with
+ *                    floor(x / (2 (2 R + 1)^2)) = (x * mul) >> shift for every 0 <= x <= 2 * 255 * (2 R + 1)^2 + (2 R + 1)^2, the
+ *                    product taken in 64 bits: how the kernel divides. */
+#define P3D_PREFILTER_FIELDS 7
+enum { P3D_PREFILTER_BLOCK = 0, P3D_PREFILTER_PEAK_WEIGHT = 1, P3D_PREFILTER_DILATE = 2, P3D_PREFILTER_FALL = 3, P3D_PREFILTER_RISE = 4,
+       P3D_PREFILTER_RADIUS = 5, P3D_PREFILTER_PASSES = 6 };
+int p3d_prefilter_u8(int device, const unsigned char* sal, const unsigned char* frames, int n, int H, int W, const int cfg[7],
+                     const int32_t law[256], const int32_t* starts /* may be NULL */, int n_shots, unsigned char* out /* [n][H][W][3] */,
+                     int32_t* grid /* [n][Hb][Wb], may be NULL */);
+int p3d_video_prefilter(p3d_handle* h, int first, int n, float scale, int H, int W, const unsigned char* frames /* NULL: kept source */,
+                        const int cfg[7], const int32_t law[256], unsigned char* out, int32_t* grid /* may be NULL */,
+                        unsigned char* maps_out /* may be NULL */, double* stage_ms /* may be NULL, [3] */);
+int p3d_debug_prefilter_u8(int device, const unsigned char* sal, const unsigned char* frames, int n, int H, int W, const int cfg[7],
+                           const int32_t law[256], const int32_t* starts, int n_shots, int offset, unsigned char* out, int32_t* grid);
+int p3d_debug_prefilter_plan(int H, int W, int block, int radius, int passes, int n, int* tile_rows, int* tile_cols, int* halo, int* fused,
+                             int* blocks_per_frame, int* frames_per_chunk, int64_t* scratch_bytes, uint32_t* mul, int* shift);
+
 /* ---- Shot boundaries of 8-bit frames (an ADDITION: the videos people reframe are edited, and a filter along the frame axis that
  * runs across a hard cut blends two unrelated scenes; automatic reframing tools find the cuts first).  OFF until called: every other
  * entry point issues what it issued before and returns the same bits.  PARITY UNPINNED: the reference's clips are single takes and

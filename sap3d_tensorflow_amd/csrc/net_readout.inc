@@ -784,13 +784,48 @@ struct QpmapRequest {
     bool timed = false;
     const int32_t* starts = nullptr; int n_shots = 0;      // host: a shot table in frames of the call (shots_table_check has passed it), or none
 };
+// qpmap.hip's launch sequence as a stage queues it: the launch arguments, the law and the optional shot table on the device, and
+// the scratch of the first levels.  The qpmap stage holds one, and so does the prefilter stage, whose strength grid is these launches'
+// qp: each carves it among its own buffers.
+struct QpmapLaunches {
+    QpmapArgs a;
+    const int32_t* law; int32_t* dlaw = nullptr; ShotTable shots;
+    QpmapLaunches(const QpmapCfg& c, int n, int H, int W, const int32_t* law, const int32_t* starts, int n_shots);
+    size_t grid() const { return (size_t)a.n * (size_t)a.Hb * (size_t)a.Wb; }      // elements of qp and of levels
+    void carve(Carve& c, bool levels, bool stats);         // qp, levels and stats where asked for, the scratch, the law, the shot table
+    void upload(hipStream_t s) const;
+    void launch(hipStream_t s, const unsigned char* sal);
+};
 // The launches of qpmap.hip behind some device bytes, with no arrival counters: they hand results to one another from launch to
 // launch.  qpmap_check has passed cfg, the law and the shape before one is built.
 struct QpmapStage : ByteStage {
     const QpmapRequest r;
-    QpmapArgs a;
-    int32_t* dlaw = nullptr; ShotTable shots;
+    QpmapLaunches q;
     explicit QpmapStage(const QpmapRequest& r);
+    void carve(Carve& c) override;
+    void upload(hipStream_t s) override;
+    void launch(hipStream_t s, const unsigned char* sal, unsigned*) override;
+    void results(hipStream_t s) override;
+};
+// What one pre-filtering of n frames of H x W pixels by their maps asks for: frames on the host (uploaded) or on the device where they
+// are (the kept source); out and grid on the host, a null grid is not copied back.
+struct PrefilterCfg { int block, peak_weight, dilate, fall, rise, radius, passes; };      // CONFIG's seven ints under their names
+struct PrefilterRequest {
+    const char* who; int n, H, W;
+    const PrefilterCfg* cfg = nullptr; const int32_t* law = nullptr;      // host: 256 entries (prefilter_check has passed them)
+    const unsigned char* frames = nullptr; const unsigned char* frames_dev = nullptr; unsigned char* out = nullptr; int32_t* grid = nullptr;
+    bool timed = false;
+    const int32_t* starts = nullptr; int n_shots = 0;      // host: a shot table in frames of the call (shots_table_check has passed it), or none
+};
+// The launches of qpmap.hip (the strength grid, on this stage's own scratch) and of prefilter.hip behind some device bytes, with no
+// arrival counters.  prefilter_check has passed cfg, the law and the shape before one is built.
+struct PrefilterStage : ByteStage {
+    const PrefilterRequest r;
+    QpmapLaunches q;
+    PrefilterArgs a;
+    unsigned char* df = nullptr;
+    explicit PrefilterStage(const PrefilterRequest& r);
+    size_t bgr() const { return bytes * 3; }              // the bytes of n frames, in or out
     void carve(Carve& c) override;
     void upload(hipStream_t s) override;
     void launch(hipStream_t s, const unsigned char* sal, unsigned*) override;
@@ -801,7 +836,7 @@ struct QpmapStage : ByteStage {
 // inside the device stage's time: it queues whatever makes the maps readable and names them as runs of maps of ph x pw pixels.
 // Off: one double-precision p3d_resize_u8 per run; on: the float32 resize / blur / normalise / byte sequence, P3D_POST_CHUNK maps
 // at a time.  Ends synchronised; stage_ms as p3d_pred_maps_u8's.
-// A stage (ByteStage: score, render, reframe, regions, qpmap) takes the device bytes where they are instead of a copy of the chain: its buffers are
+// A stage (ByteStage: score, render, reframe, regions, qpmap, prefilter) takes the device bytes where they are instead of a copy of the chain: its buffers are
 // carved after the chain's in the same layout, its upload is queued ahead of the sources, its launches behind the chain with the
 // bytes and counters() zeroed arrival counters of its own (after the chain's), its results (the copies back to the host) behind
 // that; out may then be NULL (the bytes stay on the device) and, timed, its ms [3] receives the times of the upload, of the device
@@ -1860,7 +1895,7 @@ const unsigned char* kept_source(const p3d_handle* h, const char* who, int first
 void need_kept_source(const p3d_handle* h, const char* who) {
     if (!h->video.source) throw P3dError(std::string(who) + ": no frames are given and the video keeps no source (p3d_video_keep_source before the first p3d_video_put_frames_u8)");
 }
-// p3d_video_score, _score_auc, _render, _reframe, _regions and _qpmap behind the checks of their arguments: at most 65535 of the video's frames
+// p3d_video_score, _score_auc, _render, _reframe, _regions, _qpmap and _prefilter behind the checks of their arguments: at most 65535 of the video's frames
 // through the maps' chain, the stage behind its bytes.  make builds the stage once the source has passed, so that what the stage
 // (or the kept source it reads) refuses is refused after it.  stage_ms (null, or n_ms >= 3 values): zeroed, then the stage's ms.
 void video_stage_run(p3d_handle* h, const char* who, int first, int n, float scale, unsigned char* maps_out, double* stage_ms, int n_ms,
@@ -2387,31 +2422,36 @@ struct QpmapSizes {
           lev0((size_t)p3d_qpmap_plan(a.H, a.W, a.block, a.n).lev0_elems) {}
 };
 
-// ---- the qpmap stage (declared above maps_u8_chain) -------------------------------------------------------------------------------
-QpmapStage::QpmapStage(const QpmapRequest& r_) : ByteStage(r_), r(r_), a(qpmap_args(*r_.cfg, r_.n, r_.H, r_.W)), shots{r_.starts, r_.n_shots} {}
-void QpmapStage::carve(Carve& c) {
+// ---- qpmap.hip's launches (declared above maps_u8_chain) and the qpmap stage ----------------------------------------------------------
+QpmapLaunches::QpmapLaunches(const QpmapCfg& c, int n, int H, int W, const int32_t* law_, const int32_t* starts, int n_shots)
+    : a(qpmap_args(c, n, H, W)), law(law_), shots{starts, n_shots} {}
+void QpmapLaunches::carve(Carve& c, bool levels, bool stats) {
     const QpmapSizes z(a);
     a.qp = c.take<int32_t>(z.grid);
-    a.levels = r.levels ? c.take<unsigned char>(z.grid, 5) : nullptr;
-    a.stats = r.stats ? c.take<int32_t>(z.stats) : nullptr;
+    a.levels = levels ? c.take<unsigned char>(z.grid, 5) : nullptr;
+    a.stats = stats ? c.take<int32_t>(z.stats) : nullptr;
     a.lev0 = c.take<unsigned char>(z.lev0);
     dlaw = c.input<int32_t>(256);
     shots.carve(c);
 }
-void QpmapStage::upload(hipStream_t s) {
-    HIPCHECK(hipMemcpyAsync(dlaw, r.law, 256 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+void QpmapLaunches::upload(hipStream_t s) const {
+    HIPCHECK(hipMemcpyAsync(dlaw, law, 256 * sizeof(int32_t), hipMemcpyHostToDevice, s));
     shots.upload(s);
 }
-void QpmapStage::launch(hipStream_t s, const unsigned char* sal, unsigned*) {
+void QpmapLaunches::launch(hipStream_t s, const unsigned char* sal) {
     a.sal = sal; a.law = dlaw;
     shots.bind(a);
     HIPCHECK(p3d_qpmap_launch(a, s));
 }
+QpmapStage::QpmapStage(const QpmapRequest& r_) : ByteStage(r_), r(r_), q(*r_.cfg, r_.n, r_.H, r_.W, r_.law, r_.starts, r_.n_shots) {}
+void QpmapStage::carve(Carve& c) { q.carve(c, r.levels != nullptr, r.stats != nullptr); }
+void QpmapStage::upload(hipStream_t s) { q.upload(s); }
+void QpmapStage::launch(hipStream_t s, const unsigned char* sal, unsigned*) { q.launch(s, sal); }
 void QpmapStage::results(hipStream_t s) {
-    const QpmapSizes z(a);
-    HIPCHECK(hipMemcpyAsync(r.qp, a.qp, z.grid * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (r.levels) HIPCHECK(hipMemcpyAsync(r.levels, a.levels, z.grid, hipMemcpyDeviceToHost, s));
-    if (r.stats) HIPCHECK(hipMemcpyAsync(r.stats, a.stats, z.stats * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    const QpmapSizes z(q.a);
+    HIPCHECK(hipMemcpyAsync(r.qp, q.a.qp, z.grid * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (r.levels) HIPCHECK(hipMemcpyAsync(r.levels, q.a.levels, z.grid, hipMemcpyDeviceToHost, s));
+    if (r.stats) HIPCHECK(hipMemcpyAsync(r.stats, q.a.stats, z.stats * sizeof(int32_t), hipMemcpyDeviceToHost, s));
 }
 }  // namespace
 extern "C" {
@@ -2478,6 +2518,132 @@ int p3d_video_qpmap(p3d_handle* h, int first, int n, float scale, int H, int W, 
         return *stage;
     });
     if (stage_ms) stage_ms[0] = 0.0;                   // (nothing but the law and a shot table went up)
+    API_END
+}
+
+}  // extern "C"
+namespace {
+// ---- pre-filtering frames by their 8-bit maps (prefilter.hip; the law in include/p3d_hip.h): one check, one launch description and
+// one stage for p3d_prefilter_u8, the video entry and p3d_debug_prefilter_u8.  The strength grid is qpmap.hip's launches ------------
+PrefilterCfg prefilter_check(const char* who, const int* cfg7, const int32_t* law, int n, int H, int W, const void* out) {
+    if (!cfg7 || !law || !out) throw P3dError("null argument");
+    const PrefilterCfg c{cfg7[P3D_PREFILTER_BLOCK], cfg7[P3D_PREFILTER_PEAK_WEIGHT], cfg7[P3D_PREFILTER_DILATE], cfg7[P3D_PREFILTER_FALL],
+                         cfg7[P3D_PREFILTER_RISE], cfg7[P3D_PREFILTER_RADIUS], cfg7[P3D_PREFILTER_PASSES]};
+    map_shape_check(who, n, H, W, P3D_PREFILTER_MAX_PIXELS, "2^23, the bound of the strength grid's launches");
+    if (c.block != 8 && c.block != 16 && c.block != 32 && c.block != 64 && c.block != 128)
+        throw P3dError(std::string(who) + ": the block is 8, 16, 32, 64 or 128, not " + std::to_string(c.block));
+    if (c.peak_weight < 0 || c.peak_weight > 256) throw P3dError(std::string(who) + ": peak_weight is 0 .. 256");
+    if (c.dilate < 0 || c.dilate > 8) throw P3dError(std::string(who) + ": dilate is 0 .. 8 blocks");
+    if (c.fall < 0 || c.fall > 64 || c.rise < 0 || c.rise > 64) throw P3dError(std::string(who) + ": fall and rise are 0 .. 64 (0: unlimited)");
+    if (c.radius < 1 || c.radius > P3D_PREFILTER_MAX_RADIUS) throw P3dError(std::string(who) + ": the radius is 1 .. 16 pixels");
+    if (c.passes < 1 || c.passes > P3D_PREFILTER_MAX_PASSES) throw P3dError(std::string(who) + ": 1 .. 3 passes");
+    for (int v = 0; v < 256; ++v)
+        if (law[v] < 0 || law[v] > 64) throw P3dError(std::string(who) + ": law[" + std::to_string(v) + "] = " + std::to_string(law[v]) + " is outside 0 .. 64");
+    return c;
+}
+// STRENGTH GRID: the QP maps' configuration whose qp is g
+QpmapCfg prefilter_grid_cfg(const PrefilterCfg& c) { return QpmapCfg{c.block, c.peak_weight, c.dilate, c.fall, c.rise, 0, 0, 0, 64}; }
+PrefilterArgs prefilter_args(const PrefilterCfg& c, int n, int H, int W) {
+    PrefilterArgs a;
+    a.n = n; a.H = H; a.W = W; a.block = c.block; a.radius = c.radius; a.passes = c.passes;
+    const PrefilterPlan p = p3d_prefilter_plan(H, W, c.block, c.radius, c.passes, n);
+    a.Hb = p.Hb; a.Wb = p.Wb; a.tiles_x = p.tiles_x; a.tiles_y = p.tiles_y; a.frames_per_chunk = p.frames_per_chunk; a.mul = p.mul; a.shift = p.shift;
+    return a;
+}
+
+// ---- the prefilter stage (declared above maps_u8_chain) ---------------------------------------------------------------------------
+PrefilterStage::PrefilterStage(const PrefilterRequest& r_)
+    : ByteStage(r_), r(r_), q(prefilter_grid_cfg(*r_.cfg), r_.n, r_.H, r_.W, r_.law, r_.starts, r_.n_shots), a(prefilter_args(*r_.cfg, r_.n, r_.H, r_.W)) {}
+void PrefilterStage::carve(Carve& c) {
+    df = r.frames ? c.input<unsigned char>(bgr(), 3) : nullptr;
+    a.out = c.take<unsigned char>(bgr(), 5);
+    q.carve(c, false, false);
+    const PrefilterPlan p = p3d_prefilter_plan(a.H, a.W, a.block, a.radius, a.passes, a.n);
+    for (int k = 0; k < 2; ++k) a.tmp[k] = k < a.passes - 1 ? c.take<unsigned char>((size_t)p.tmp_bytes) : nullptr;
+}
+void PrefilterStage::upload(hipStream_t s) {
+    q.upload(s);
+    if (df) HIPCHECK(hipMemcpyAsync(df, r.frames, bgr(), hipMemcpyHostToDevice, s));
+}
+void PrefilterStage::launch(hipStream_t s, const unsigned char* sal, unsigned*) {
+    q.launch(s, sal);
+    a.frames = df ? df : r.frames_dev; a.grid = q.a.qp;
+    HIPCHECK(p3d_prefilter_launch(a, s));
+}
+void PrefilterStage::results(hipStream_t s) {
+    HIPCHECK(hipMemcpyAsync(r.out, a.out, bgr(), hipMemcpyDeviceToHost, s));
+    if (r.grid) HIPCHECK(hipMemcpyAsync(r.grid, q.a.qp, q.grid() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+}
+}  // namespace
+extern "C" {
+
+int p3d_prefilter_u8(int device, const unsigned char* sal, const unsigned char* frames, int n, int H, int W, const int cfg[7],
+                     const int32_t law[256], const int32_t* starts, int n_shots, unsigned char* out, int32_t* grid) {
+    API_BEGIN
+    const char* who = "prefilter_u8";
+    if (!sal || !frames) throw P3dError("null argument");
+    const PrefilterCfg pc = prefilter_check(who, cfg, law, n, H, W, out);
+    if (starts || n_shots) shots_table_check(who, starts, n_shots, n);
+    metric_args(device, sal, cfg, 1, 1, out);
+    PrefilterRequest r{who, n, H, W};
+    r.cfg = &pc; r.law = law; r.frames = frames; r.out = out; r.grid = grid; r.starts = starts; r.n_shots = n_shots;
+    PrefilterStage stage(r);
+    stage_on_host_bytes(stage, sal);
+    API_END
+}
+
+int p3d_debug_prefilter_u8(int device, const unsigned char* sal, const unsigned char* frames, int n, int H, int W, const int cfg[7],
+                           const int32_t law[256], const int32_t* starts, int n_shots, int offset, unsigned char* out, int32_t* grid) {
+    API_BEGIN
+    const char* who = "debug_prefilter_u8";
+    if (!sal || !frames) throw P3dError("null argument");
+    const PrefilterCfg pc = prefilter_check(who, cfg, law, n, H, W, out);
+    if (starts || n_shots) shots_table_check(who, starts, n_shots, n);
+    offset_check(who, offset);
+    metric_args(device, sal, cfg, 1, 1, out);
+    PrefilterRequest r{who, n, H, W};
+    r.cfg = &pc; r.law = law; r.frames = frames; r.out = out; r.grid = grid; r.starts = starts; r.n_shots = n_shots;
+    PrefilterStage stage(r);
+    stage_on_host_bytes(stage, sal, offset);
+    API_END
+}
+
+int p3d_debug_prefilter_plan(int H, int W, int block, int radius, int passes, int n, int* tile_rows, int* tile_cols, int* halo, int* fused,
+                             int* blocks_per_frame, int* frames_per_chunk, int64_t* scratch_bytes, uint32_t* mul, int* shift) {
+    API_BEGIN
+    if (!tile_rows || !tile_cols || !halo || !fused || !blocks_per_frame || !frames_per_chunk || !scratch_bytes || !mul || !shift)
+        throw P3dError("null argument");
+    if (H < 1 || W < 1 || (long long)H * W > P3D_PREFILTER_MAX_PIXELS || n < 1 || n > 65535 ||
+        (block != 8 && block != 16 && block != 32 && block != 64 && block != 128) || radius < 1 || radius > P3D_PREFILTER_MAX_RADIUS ||
+        passes < 1 || passes > P3D_PREFILTER_MAX_PASSES)
+        throw P3dError("debug_prefilter_plan: 1 <= H * W <= 2^23, 1 .. 65535 frames, a block of 8, 16, 32, 64 or 128, a radius of 1 .. 16, 1 .. 3 passes");
+    const PrefilterPlan p = p3d_prefilter_plan(H, W, block, radius, passes, n);
+    *tile_rows = p.tile_rows; *tile_cols = p.tile_cols; *halo = p.halo; *fused = p.fused; *blocks_per_frame = (int)p.blocks_per_frame;
+    *frames_per_chunk = p.frames_per_chunk; *scratch_bytes = (int64_t)p.scratch_bytes; *mul = p.mul; *shift = p.shift;
+    API_END
+}
+
+int p3d_video_prefilter(p3d_handle* h, int first, int n, float scale, int H, int W, const unsigned char* frames, const int cfg[7],
+                        const int32_t law[256], unsigned char* out, int32_t* grid, unsigned char* maps_out, double* stage_ms) {
+    API_BEGIN
+    const char* who = "video_prefilter";
+    if (!h) throw P3dError("null argument");
+    h->video.need_open(who);
+    // before the shape: a call that leaves the size to the source has none to name when there is no source
+    if (!frames) need_kept_source(h, who);
+    const PrefilterCfg pc = prefilter_check(who, cfg, law, std::max(1, std::min(n, 65535)), H, W, out);
+    PrefilterRequest r{who, n, H, W};
+    r.cfg = &pc; r.law = law; r.frames = frames; r.out = out; r.grid = grid; r.timed = stage_ms != nullptr;
+    std::unique_ptr<PrefilterStage> stage;
+    std::vector<int32_t> shots;                            // the installed table in frames of the call, cut as p3d_video_qpmap cuts it
+    video_stage_run(h, who, first, n, scale, maps_out, stage_ms, 3, [&]() -> ByteStage& {
+        if (!frames) r.frames_dev = kept_source(h, who, first, n, H, W, "filters");
+        shots = video_shots_within(h, first, n);
+        if (!shots.empty()) { r.starts = shots.data(); r.n_shots = (int)shots.size(); }
+        stage.reset(new PrefilterStage(r));
+        return *stage;
+    });
+    if (stage_ms && !frames) stage_ms[0] = 0.0;      // (nothing but the law and a shot table went up)
     API_END
 }
 

@@ -1217,6 +1217,30 @@ struct QpmapArgs {
 };
 hipError_t p3d_qpmap_launch(const QpmapArgs& a, hipStream_t s);
 
+// ---- frames low-pass filtered away from their saliency (prefilter.hip; p3d_video_prefilter / p3d_prefilter_u8, the law in include/p3d_hip.h) ----
+// One launch sequence on n frames of H x W pixels: frames [n][H][W][3] and the strength grid [n][Hb][Wb] int32 that p3d_qpmap_launch
+// left (0 .. 64) -> out [n][H][W][3]; every buffer device memory.  Scratch: tmp[0] (passes >= 2) and tmp[1] (passes = 3), each
+// p3d_prefilter_plan's tmp_bytes, the intermediate passes of frames_per_chunk frames at a time.
+// Refused (hipErrorInvalidValue): a missing buffer, n outside [1, 65535], H * W outside [1, 2^23], a block, radius or pass count
+// outside the header's ranges, a plan other than p3d_prefilter_plan's.  The grid's entries are the caller's to keep in 0 .. 64.
+constexpr int P3D_PREFILTER_MAX_PIXELS = 1 << 23;             // the grid is the QP maps'
+constexpr int P3D_PREFILTER_MAX_RADIUS = 16, P3D_PREFILTER_MAX_PASSES = 3;
+constexpr int PREFILTER_TILE_ROWS = 32, PREFILTER_TILE_COLS = 64;      // pixels of a block's tile; both above the largest radius
+constexpr long long P3D_PREFILTER_CHUNK_BYTES = 1LL << 26;    // an intermediate pass holds at most this many bytes (and at least a frame)
+struct PrefilterPlan {
+    int tile_rows = 0, tile_cols = 0, halo = 0, fused = 0, tiles_x = 0, tiles_y = 0, Hb = 0, Wb = 0, frames_per_chunk = 0;
+    long long blocks_per_frame = 0, tmp_bytes = 0, scratch_bytes = 0;
+    unsigned mul = 0; int shift = 0;                          // floor(x / (2 (2 R + 1)^2)) = (x * mul) >> shift for 0 <= x < 2^20
+};
+PrefilterPlan p3d_prefilter_plan(int H, int W, int block, int radius, int passes, int n);
+struct PrefilterArgs {
+    const unsigned char* frames = nullptr; unsigned char* out = nullptr; const int32_t* grid = nullptr;
+    unsigned char* tmp[2] = {nullptr, nullptr};
+    int n = 0, H = 0, W = 0, block = 0, radius = 0, passes = 0;
+    int Hb = 0, Wb = 0, tiles_x = 0, tiles_y = 0, frames_per_chunk = 0; unsigned mul = 0; int shift = 0;      // p3d_prefilter_plan(H, W, block, radius, passes, n)
+};
+hipError_t p3d_prefilter_launch(const PrefilterArgs& a, hipStream_t s);
+
 // ---- shot boundaries of 8-bit frames (shots.hip; p3d_shot_distances_u8 / p3d_shot_cuts, the law in include/p3d_hip.h) ----
 // The cut signal of n frames [n][H][W][3] of device bytes: D [n] device words, D_0 = 0, D_f the distance of frame f's cell
 // histograms from frame f - 1's.  tabs is scratch of (frames_per_chunk + 1) tables of table_words words on a 16-byte boundary: slot 0

@@ -799,6 +799,91 @@ def qpmap(sal, law, block=16, peak_weight=128, dilate=0, fall=0, rise=0, balance
     return qp, lev, st4
 
 
+def prefilter_law(gate=0, full=0, gamma=1.0, strength=64):
+    """The table that turns a block's level into the strength of its low-pass (the law of include/p3d_hip.h, "Pre-filtering frames by
+    their 8-bit maps") -> int32 [256], every entry in 0 .. 64.  A host table, built here in float64: level v >= gate gives 0 (the
+    frame is left alone where the viewers look); level v <= full gives `strength` (64: the full low-pass); between them, with
+    x = (gate - v) / (gate - full) the normalised distance below the gate, entry v = floor(strength x^gamma + 0.5) (round half up), so
+    the entries never rise with v.  0 <= full <= gate <= 255 (where the two rules meet the gate wins: gate = full is a step at the gate, gate = 0 leaves every entry 0); gamma is
+    finite and > 0 (below 1: the smoothing comes on just under the gate, above 1: only the least salient blocks get all of it);
+    strength is 0 .. 64."""
+    gate, full, gamma, strength = int(gate), int(full), float(gamma), int(strength)
+    if not 0 <= full <= gate <= 255:
+        raise ValueError("0 <= full <= gate <= 255")
+    if not (np.isfinite(gamma) and gamma > 0.):
+        raise ValueError("gamma is finite and > 0")
+    if not 0 <= strength <= 64:
+        raise ValueError("strength is 0 .. 64")
+    v = np.arange(256, dtype=np.float64)
+    x = np.clip((gate - v) / max(gate - full, 1), 0., 1.)
+    law = np.floor(strength * x ** gamma + 0.5).astype(np.int32)
+    law[:full + 1] = strength
+    law[gate:] = 0                                         # (the gate wins where the two meet)
+    return law
+
+
+def prefilter_cfg(block=16, peak_weight=128, dilate=0, fall=0, rise=0, radius=4, passes=1):
+    """The seven ints of include/p3d_hip.h's CONFIG ("Pre-filtering frames by their 8-bit maps") in the order of the P3D_PREFILTER_*
+    indices."""
+    from . import _lib
+    cfg = (C.c_int * _lib.P3D_PREFILTER_FIELDS)()
+    for k, v in ((_lib.P3D_PREFILTER_BLOCK, block), (_lib.P3D_PREFILTER_PEAK_WEIGHT, peak_weight), (_lib.P3D_PREFILTER_DILATE, dilate),
+                 (_lib.P3D_PREFILTER_FALL, fall), (_lib.P3D_PREFILTER_RISE, rise), (_lib.P3D_PREFILTER_RADIUS, radius),
+                 (_lib.P3D_PREFILTER_PASSES, passes)):
+        cfg[k] = int(v)
+    return cfg
+
+
+def prefilter_plan(H, W, block=16, radius=4, passes=1, n=1):
+    """Test hook (p3d_debug_prefilter_plan, host only): dict(tile_rows, tile_cols, halo, fused, blocks_per_frame, frames_per_chunk,
+    scratch_bytes, mul, shift) of the prefilter launches for n frames of H x W."""
+    tr, tc, halo, fused, b, m, sh = (C.c_int(0) for _ in range(7))
+    s, mul = C.c_int64(0), C.c_uint32(0)
+    check(lib().p3d_debug_prefilter_plan(int(H), int(W), int(block), int(radius), int(passes), int(n), C.byref(tr), C.byref(tc),
+                                         C.byref(halo), C.byref(fused), C.byref(b), C.byref(m), C.byref(s), C.byref(mul), C.byref(sh)))
+    return dict(tile_rows=tr.value, tile_cols=tc.value, halo=halo.value, fused=bool(fused.value), blocks_per_frame=b.value,
+                frames_per_chunk=m.value, scratch_bytes=s.value, mul=mul.value, shift=sh.value)
+
+
+def _prefilter_law_array(law):
+    t = np.ascontiguousarray(law)
+    if t.dtype != np.int32 or t.shape != (256,):
+        raise ValueError("the law is int32 [256] (dataflow.prefilter_law)")
+    return t
+
+
+def prefilter(sal, frames, law, block=16, peak_weight=128, dilate=0, fall=0, rise=0, radius=4, passes=1, shots=None, grid=False,
+              device=0, offset=None):
+    """Frames low-pass filtered away from their saliency on the device (p3d_prefilter_u8; include/p3d_hip.h, "Pre-filtering frames by
+    their 8-bit maps"): maps uint8 [n, H, W] (or [H, W]: one frame), frames uint8 [n, H, W, 3] in B, G, R order and a law int32 [256]
+    (prefilter_law) -> (out uint8 [n, H, W, 3], grid int32 [n, Hb, Wb] or None), Hb = ceil(H / block), Wb = ceil(W / block).  Per
+    block a strength 0 .. 64 (the QP maps' level, dilation, law and limiter: fall / rise limit it from frame to frame, inside the
+    shots of `shots`, starts ascending from 0, where given), interpolated between block centres into a weight per pixel; `passes`
+    rounded box passes of `radius` pixels either way make the low-pass the weight blends in.  offset (0 .. 15): the test hook
+    p3d_debug_prefilter_u8, every device buffer between guards and the byte buffers shifted off a 16-byte boundary."""
+    s3, _, _ = _reframe_shape(sal, 1)
+    n, H, W = s3.shape
+    f = np.ascontiguousarray(frames)
+    f = f[None] if f.ndim == 3 else f
+    if f.dtype != np.uint8 or f.shape != (n, H, W, 3):
+        raise ValueError("frames are %s %s, expected uint8 %s" % (f.dtype, f.shape, (n, H, W, 3)))
+    t = _prefilter_law_array(law)
+    cfg = prefilter_cfg(block, peak_weight, dilate, fall, rise, radius, passes)
+    B = int(block)
+    out = np.empty((n, H, W, 3), np.uint8)
+    g = np.empty((n, -(-H // B), -(-W // B)) if B in QPMAP_BLOCKS else (1,), np.int32) if grid else None
+    u8, i32 = C.POINTER(C.c_ubyte), C.POINTER(C.c_int32)
+    st = None if shots is None else np.ascontiguousarray(shots, np.int32).ravel()
+    head = (device, s3.ctypes.data_as(u8), f.ctypes.data_as(u8), n, H, W, cfg, t.ctypes.data_as(i32),
+            None if st is None else st.ctypes.data_as(i32), 0 if st is None else len(st))
+    tail = (out.ctypes.data_as(u8), None if g is None else g.ctypes.data_as(i32))
+    if offset is None:
+        check(lib().p3d_prefilter_u8(*head, *tail))
+    else:
+        check(lib().p3d_debug_prefilter_u8(*head, int(offset), *tail))
+    return out, g
+
+
 def _shot_frames(frames):
     f = np.ascontiguousarray(frames)
     if f.dtype != np.uint8 or f.ndim != 4 or f.shape[3] != 3 or f.size == 0:

@@ -1100,6 +1100,29 @@ class P3DSession:
             res["maps"] = maps
         return res
 
+    def video_prefilter(self, first, n, H, W, law, block=16, peak_weight=128, dilate=0, fall=0, rise=0, radius=4, passes=1, frames=None,
+                        scale=255.):
+        """Frames first .. first + n - 1 of the open video low-pass filtered away from their saliency, on the device (an addition: a
+        pre-filter any encoder can take) -> (out uint8 [n, H, W, 3] in B, G, R order, grid int32 [n, Hb, Wb], maps uint8 [n, H, W],
+        stage_ms).  Per block x block block of video_maps_u8's bytes at H x W a strength 0 .. 64: the block's level (peak_weight /
+        256 of its largest byte, the rest its mean), dilated by `dilate` blocks, turned into a strength by `law` (int32 [256],
+        dataflow.prefilter_law), limited to `fall` down and `rise` up per frame WITHIN THIS CALL and inside the shots of
+        video_set_shots' table.  The strength is interpolated between block centres into a weight per pixel, which blends in a
+        low-pass of `passes` rounded box passes, `radius` pixels either way; where the weight is 0 the frame's bytes are returned.
+        frames: uint8 [n, H, W, 3], or None for the source kept by video_keep_source (H x W must then be the source's own).
+        stage_ms: dict(upload, device = the maps' chain, prefilter) of HIP-event times.  include/p3d_hip.h holds the exact rules."""
+        from . import dataflow
+        n, H, W, f, out, maps = _frame_inputs(self, n, (H, W), frames, 2 ** 23, True)
+        B = int(block)
+        valid = out.ndim == 4 and B in dataflow.QPMAP_BLOCKS      # (the library refuses the rest)
+        t = dataflow._prefilter_law_array(law)
+        cfg = dataflow.prefilter_cfg(B, peak_weight, dilate, fall, rise, radius, passes)
+        grid = np.empty((n, -(-H // B), -(-W // B)) if valid else (1,), np.int32)
+        ms = (C.c_double * 3)()
+        check(lib().p3d_video_prefilter(self._h, int(first), n, float(scale), H, W, _ptr(f, _lib._u8p), cfg, _ptr(t, _lib._i32p),
+                                        _ptr(out, _lib._u8p), _ptr(grid, _lib._i32p), _ptr(maps, _lib._u8p), ms))
+        return out, grid, maps, dict(upload=ms[0], device=ms[1], prefilter=ms[2])
+
     def video_detect_shots(self, grid=(2, 2), threshold=250, window=2, ratio=512, min_length=3, install=True, with_signal=False):
         """Find the hard cuts of the open video on the device (an addition), from the source kept by video_keep_source: per frame a
         grid = (gy, gx) of cell histograms of the B, G, R bytes, D_f their distance from the frame before; frame f starts a shot
