@@ -58,7 +58,13 @@ driver's own; no particular encoder's input format is promised.  `--prefilter DI
 frames on the device) writes DIR/<video>/frame_<k>.png: every frame at its own size, low-pass filtered where its map is not salient
 and bit-exact where it is (P3DSession.video_prefilter, the law is include/p3d_hip.h's "Pre-filtering frames by their 8-bit maps"), for
 any encoder to take; grid.npy, int32 [F, Hb, Wb], holds the strength 0 .. 64 of every `--pf-block` block, limited from frame to frame
-by `--pf-fall` / `--pf-rise` inside the shots of `--shots`."""
+by `--pf-fall` / `--pf-rise` inside the shots of `--shots`.  `--distortion DIR` (an addition, needs `--resident`) compares
+DIR/<video>.npy, uint8 [F, H0, W0, 3] in the videos' own channel order -- the frames as an encoder or a filter left them -- with the
+decoded frames kept on the device (or with `--dist-ref DIR`'s arrays) under the video's maps at the frames' size
+(P3DSession.video_distortion, the law is include/p3d_hip.h's "Distortion of frames under their 8-bit maps") and writes, into `--out`,
+<video>_distortion.npy, int64 [F, 20]: the table of integer sums; on `--dist-block` <video>_block_sse.npy, int64 [F, Hb, Wb]; and
+<video>_distortion.csv, a line a frame: PSNR and saliency-weighted PSNR of the planes B, G, R, Y, SSIM and weighted SSIM of Y, and the
+share of the pixels at or above `--dist-gate` that changed."""
 import argparse
 import glob
 import os
@@ -559,6 +565,20 @@ def parse_args(argv=None):
                    "0 .. 64, 0: unlimited (0)")
     p.add_argument("--pf-fall", type=int, default=0, metavar="STEP", help="[addition] --prefilter: a block's strength falls by at most STEP a frame, "
                    "0 .. 64, 0: unlimited (0)")
+    p.add_argument("--distortion", type=str, default="", metavar="DIR", help="[addition] needs --resident: compare DIR/<video>.npy, uint8 "
+                   "[F, H0, W0, 3] (the decoded or filtered frames, in the videos' channel order), with the video's own frames under its maps "
+                   "on the device (P3DSession.video_distortion, %d frames a call) and write <video>_distortion.npy (int64 [F, 20], the integer "
+                   "sums), <video>_distortion.csv (PSNR, weighted PSNR, SSIM, weighted SSIM a frame) and, on --dist-block, "
+                   "<video>_block_sse.npy into --out" % SCORE_CHUNK)
+    p.add_argument("--dist-gate", type=int, default=0, metavar="LEVEL", help="[addition] --distortion: pixels at or above it count as salient, and "
+                   "levels below it weigh --dist-floor, 0 .. 255 (0: off)")
+    p.add_argument("--dist-block", type=int, default=0, metavar="B", help="[addition] --distortion: also write the squared error of every B x B "
+                   "block, 8, 16, 32, 64 or 128 (0: no block map)")
+    p.add_argument("--dist-gamma", type=float, default=1.0, metavar="G", help="[addition] --distortion: the weight of level v is 255 (v / 255)^G, "
+                   "> 0 (1: the level itself)")
+    p.add_argument("--dist-floor", type=int, default=0, metavar="W", help="[addition] --distortion: the weight of the levels below --dist-gate, 0 .. 255 (0)")
+    p.add_argument("--dist-ref", type=str, default="", metavar="DIR", help="[addition] --distortion: DIR/<video>.npy, uint8 [F, H0, W0, 3], is the "
+                   "reference instead of the video's own frames")
     p.add_argument("--shots", type=str, default="", metavar="detect|FILE.npy", help="[addition] needs --resident: a shot table for every video, "
                    "installed before its maps are read (P3DSession.video_set_shots) -- --temporal then filters inside the shots and --reframe "
                    "smooths its track inside them.  detect: the hard cuts found on the device in the decoded frames "
@@ -628,6 +648,7 @@ def parse_args(argv=None):
     regions_args(args, p.error)
     qpmap_args(args, p.error)
     prefilter_args(args, p.error)
+    distortion_args(args, p.error)
     shots_args(args, p.error)
     return args
 
@@ -851,6 +872,96 @@ def prefilter_video_resident(sess, F, video_dir, prefilter, writers=4):
     return t
 
 
+DISTORTION_DEFAULTS = dict(dist_gate=0, dist_block=0, dist_gamma=1.0, dist_floor=0, dist_ref="")
+DISTORTION_PLANES = ("b", "g", "r", "y")
+
+
+def distortion_args(args, error):
+    """Checks --distortion and its values as P3DSession.video_distortion and dataflow.distortion_law would refuse them, before
+    anything is opened; error(message) does not return.  Leaves the keyword arguments of distortion_video_resident in
+    args.distortion_kw (None without --distortion)."""
+    args.distortion_kw = None
+    if not args.distortion:
+        if any(getattr(args, k) != v for k, v in DISTORTION_DEFAULTS.items()):
+            error("--dist-gate / -block / -gamma / -floor / -ref need --distortion DIR")
+        return
+    if not args.resident:
+        error("--distortion needs --resident: the frames and the maps stay on the device")
+    if not 0 <= args.dist_gate <= 255:
+        error("--dist-gate is 0 .. 255")
+    if args.dist_block not in (0, 8, 16, 32, 64, 128):
+        error("--dist-block is 0, 8, 16, 32, 64 or 128")
+    if not (np.isfinite(args.dist_gamma) and args.dist_gamma > 0.):
+        error("--dist-gamma is finite and > 0")
+    if not 0 <= args.dist_floor <= 255:
+        error("--dist-floor is 0 .. 255")
+    args.distortion_kw = dict(gate=args.dist_gate, block=args.dist_block, gamma=args.dist_gamma, floor=args.dist_floor, ref=args.dist_ref)
+
+
+def load_distortion_frames(frames_dir, name, F, size, flag):
+    """DIR/<name>.npy of --distortion or --dist-ref: uint8 [F, H0, W0, 3] in the videos' channel order; size None: the array names it."""
+    path = os.path.join(frames_dir, name + ".npy")
+    a = np.load(path)
+    if size is None and a.ndim == 4:
+        size = a.shape[1:3]
+    if a.dtype != np.uint8 or size is None or a.shape != (F,) + tuple(size) + (3,):
+        raise ValueError("%s: %s is %s %s, not uint8 %s" % (flag, path, a.dtype, a.shape, (F,) + (tuple(size) if size else ("H0", "W0")) + (3,)))
+    return a
+
+
+def distortion_video_resident(sess, F, out_dir, name, test_dir, distortion):
+    """--distortion: the open video's frames against <test_dir>/<name>.npy under the video's maps, on the device
+    (P3DSession.video_distortion at the video's own size, SCORE_CHUNK frames a call; the reference is the kept source, or
+    --dist-ref's array) -> <out_dir>/<name>_distortion.npy, int64 [F, 20], <name>_distortion.csv and, with a block,
+    <name>_block_sse.npy, int64 [F, Hb, Wb].  Returns the report (dataflow.distortion_report), the milliseconds of the calls (gpu:
+    wall time) and of the device stages, and the files written."""
+    from sap3d_tensorflow_amd import dataflow
+    ref = None
+    if distortion["ref"]:      # no source is kept: the reference names the size
+        ref = load_distortion_frames(distortion["ref"], name, F, None, "--dist-ref")
+        H0, W0 = ref.shape[1:3]
+    else:
+        H0, W0 = sess.video_source_info()["size"]
+    test = load_distortion_frames(test_dir, name, F, (H0, W0), "--distortion")
+    law = dataflow.distortion_law(distortion["gate"], distortion["gamma"], distortion["floor"])
+    tables, blocks = [], []
+    t = dict(gpu=0.0, upload=0.0, device=0.0, distortion=0.0)
+    for first in range(0, F, SCORE_CHUNK):
+        n = min(SCORE_CHUNK, F - first)
+        t0 = time.perf_counter()
+        table, bs, _, ms = sess.video_distortion(first, n, test[first:first + n, ..., ::-1], law, block=distortion["block"], gate=distortion["gate"],
+                                                 ref=None if ref is None else ref[first:first + n, ..., ::-1], size=(H0, W0))       # the kernel takes cv2's BGR order
+        t["gpu"] += (time.perf_counter() - t0) * 1e3
+        for k in ("upload", "device", "distortion"):
+            t[k] += ms[k]
+        tables.append(table)
+        blocks.append(bs)
+    table = np.concatenate(tables)
+    files = [name + "_distortion.npy", name + "_distortion.csv"]
+    np.save(os.path.join(out_dir, files[0]), table)
+    if distortion["block"]:
+        files.append(name + "_block_sse.npy")
+        np.save(os.path.join(out_dir, files[-1]), np.concatenate(blocks))
+    rep = dataflow.distortion_report(table, H0 * W0)
+    with open(os.path.join(out_dir, files[1]), "w") as f:
+        f.write("frame," + ",".join(["psnr_" + c for c in DISTORTION_PLANES] + ["wpsnr_" + c for c in DISTORTION_PLANES]) +
+                ",ssim,wssim,changed_salient_share\n")
+        for k in range(F):
+            row = list(rep["psnr"][k]) + list(rep["wpsnr"][k]) + [rep["ssim"][k], rep["wssim"][k], rep["changed_salient_share"][k]]
+            f.write("%d,%s\n" % (k + 1, ",".join(repr(float(v)) for v in row)))
+    t.update(report=rep, files=files)
+    return t
+
+
+def format_distortion_means(rep):
+    """The video's means of the Y plane's figures; frames without a figure (NaN) and frames equal to their reference (+inf) aside."""
+    def mean(v):
+        v = v[np.isfinite(v)]
+        return float(v.mean()) if v.size else float("nan")
+    return "psnr_y %.4f wpsnr_y %.4f ssim %.6f wssim %.6f changed_salient_share %.6f" % (
+        mean(rep["psnr"][:, 3]), mean(rep["wpsnr"][:, 3]), mean(rep["ssim"]), mean(rep["wssim"]), mean(rep["changed_salient_share"]))
+
+
 def write_qp_text(path, qp):
     """qp.txt: one line a frame -- the frame's number from 1, then its offsets in raster order, separated by spaces."""
     with open(path, "w") as f:
@@ -1062,7 +1173,7 @@ def run_resident(sess, args, path):
     prefilter_dir = os.path.join(args.prefilter, name) if args.prefilter else None
     if prefilter_dir:
         os.makedirs(prefilter_dir, exist_ok=True)
-    keep = bool(render_dir or reframe_dir or detect or prefilter_dir)
+    keep = bool(render_dir or reframe_dir or detect or prefilter_dir or (args.distortion_kw and not args.distortion_kw["ref"]))
     if args.shot_windows:      # the table goes in before the windows are cut, and they stay inside its shots
         F = predict_video_resident(sess, np.load(path), args.batch, args.stride, args.overlap, times, keep_source=keep,
                                    shot_windows=lambda F: shots_video_resident(sess, F, args.out, name, args.shots_kw))
@@ -1138,6 +1249,10 @@ def run_resident(sess, args, path):
     if prefilter_dir:
         tp = prefilter_video_resident(sess, F, prefilter_dir, args.prefilter_kw, writers=args.writers)
         print(name, "%d pre-filtered png files and grid.npy in %s, mean strength %.4f" % (tp["files"], prefilter_dir, tp["strength"]))
+    td = None
+    if args.distortion_kw:
+        td = distortion_video_resident(sess, F, args.out, name, args.distortion, args.distortion_kw)
+        print(name, "distortion over %d frames: %s; %s in %s" % (F, format_distortion_means(td["report"]), ", ".join(td["files"]), args.out))
     temporal_ms = sess.video_temporal_last_ms() if args.temporal != "off" and args.time else None
     sess.close_video()
     if args.time:
@@ -1166,6 +1281,9 @@ def run_resident(sess, args, path):
         if tp is not None:
             print("  %s: prefilter %.1f ms (maps %.2f ms, prefilter launches %.3f ms on the device) | encode %.1f ms thread time on %d writers"
                   % (name, tp["gpu"], tp["device"], tp["prefilter"], tp["encode"], args.writers))
+        if td is not None:
+            print("  %s: distortion %.1f ms (uploads %.2f ms, maps %.2f ms, distortion launches %.3f ms on the device)"
+                  % (name, td["gpu"], td["upload"], td["device"], td["distortion"]))
     return means
 
 

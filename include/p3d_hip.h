@@ -1871,6 +1871,75 @@ int p3d_debug_prefilter_u8(int device, const unsigned char* sal, const unsigned 
 int p3d_debug_prefilter_plan(int H, int W, int block, int radius, int passes, int n, int* tile_rows, int* tile_cols, int* halo, int* fused,
                              int* blocks_per_frame, int* frames_per_chunk, int64_t* scratch_bytes, uint32_t* mul, int* shift);
 
+/* ---- Distortion of frames under their 8-bit maps (an ADDITION: what a change to the frames -- a pre-filter, an encoder driven by the
+ * QP maps -- cost where the viewers look and what it cost elsewhere; the literature reports it as saliency-weighted PSNR, and SSIM
+ * is expected beside it).  OFF until called: every other entry point issues what it issued before and returns the same bits.
+ * PARITY UNPINNED: the reference has nothing of the kind; this text is the contract and tests/distortion_ref.py replays it in numpy.
+ * The device leaves integers only, and every integer test holds to 0; PSNR and SSIM are then a few float64 operations on the host
+ * (dataflow.distortion_report).  Nothing here drives an encoder or says what bitrate one saves.
+ * Per frame: s [H][W] bytes, the saliency map; ref [H][W][3] and test [H][W][3] bytes in cv2's B, G, R order.
+ *   CONFIG      two ints in the order of the P3D_DISTORTION_* indices below (an array, `const int cfg[P3D_DISTORTION_FIELDS]`):
+ *               block, 0 (no block map) or one of 8, 16, 32, 64, 128; gate 0 .. 255, 0 = off.  A weight law
+ *               `const int32_t wlaw[256]` comes with it, every entry in 0 .. 255: per pixel w = wlaw[s].
+ *   LIMITS      1 <= n <= 65535 frames a call; H * W <= 2^23.  test is required; so is ref, except where an entry point names what
+ *               stands in for it.
+ *   PLANES      four, k = 0 .. 3: B, G, R and Y = (29 B + 150 G + 77 R + 128) >> 8 (the coefficients sum to 256: Y is in 0 .. 255).
+ *               d_k = ref_k - test_k; Y's difference is the difference of the two frames' Y values.
+ *   RECORD      int64_t table [n][P3D_DISTORTION_RECORD], the sums over the frame's pixels under the P3D_DISTORTION_* indices:
+ *               SSE + k: sum of d_k^2 (<= 65025 * 2^23 < 2^39).  WSSE + k: sum of w d_k^2 (<= 255 * 65025 * 2^23 < 2^47, the largest
+ *               sum here).  SW: sum of w (< 2^31).  MAXABS + k: the largest |d_k| (<= 255).  CHANGED: the pixels where any of the
+ *               three B, G, R bytes differ.  SALIENT: the pixels with s >= gate, 0 when gate = 0.  CHANGED_SALIENT: the pixels
+ *               that are both (all three <= 2^23).  NW, SQ, SWQ, SWW: SSIM below.
+ *   SSIM        on Y alone, made of integers.  Windows are 8 x 8 pixels at stride 4 on both axes: a window's top-left corner is
+ *               row 4 j, column 4 i for every j, i >= 0 with 4 j + 8 <= H and 4 i + 8 <= W.  NW is their count (<= 2^19); H < 8 or
+ *               W < 8 gives NW = SQ = SWQ = SWW = 0.  Per window five sums over its 64 pixels, a = ref's Y and b = test's Y:
+ *               sa, sb, saa, sbb, sab.  c1 = 26634 = round(4096 * 6.5025), c2 = 235963 = round(64 * 63 * 58.5225) (the variance
+ *               is the unbiased one).  num = (2 sa sb + c1) (2 (64 sab - sa sb) + c2),
+ *               den = (sa^2 + sb^2 + c1) (64 (saa + sbb) - sa^2 - sb^2 + c2): int64, below 2^56 in magnitude, den > 0, num may be
+ *               negative.  q = floor(double(num) / double(den) * 65536 + 0.5) as an integer, in -65536 .. 65536: one correctly
+ *               rounded conversion of an int64 to a double each, one IEEE division; the multiplication by 2^16 is exact, so its
+ *               contraction with the addition into a fused multiply-add gives the same value.  (distortion.hip is built
+ *               without fast-math, as every file of the library is: a reciprocal in place of the division would break this.)
+ *               ww = the sum of w over the window's 64 pixels.  SQ = sum of q; SWQ = sum of ww q (< 2^49); SWW = sum of ww
+ *               (< 2^33).  q is quantised before it is summed, so no order of summation can show: SSIM holds to 0 like the rest.
+ *   BLOCK MAP   int64_t block_sse [n][Hb][Wb], or NULL: the sum of d_B^2 + d_G^2 + d_R^2 over the block (<= 3 * 65025 * 2^14);
+ *               Hb, Wb and the edge blocks as GRID of "QP maps of 8-bit maps".  Required to be NULL when block = 0, and optional
+ *               otherwise.
+ * p3d_distortion_u8   op level, host arrays: sal [n][H][W], ref and test [n][H][W][3], wlaw [256] -> table, block_sse (or NULL).
+ * p3d_video_distortion  compares frames first .. first + n - 1 of the open video at H x W.  The saliency bytes are, bit for bit,
+ *                    what p3d_video_maps_u8(first, n, scale, H, W) returns under the handle's current settings; maps_out (or
+ *                    NULL) receives them.  test: host [n][H][W][3], uploaded as p3d_video_render uploads its frames.  ref:
+ *                    likewise, or NULL for the kept source -- then H = H0 and W = W0 are required and every frame of the range
+ *                    must have a source.  Validated as p3d_video_maps_u8 validates, plus cfg, the law, LIMITS, test == NULL,
+ *                    table == NULL and a block map with block = 0, all before any launch, upload or scratch request: a refusal
+ *                    changes nothing.  stage_ms (or NULL) [3]: the frames' upload, the maps' chain, the distortion launches.
+ *                    Returns synchronised.
+ * TEST HOOKS (tests/test_gpu_distortion.py):
+ * p3d_debug_distortion_u8  the same launch description with every device buffer between guards: sal starts `offset` bytes (0 .. 15)
+ *                    past a 16-byte boundary, ref (3 offset) mod 16 and test (5 offset) mod 16 bytes past one; -1 if a guard or an
+ *                    input changed.
+ * p3d_debug_distortion_plan  host only, no HIP call, for n frames of H x W with this block (0: no block map): the tile of rows and
+ *                    columns a block of the sums' launch takes (the first tile starts at (0, 0)); the blocks a frame of that
+ *                    launch; the rows and columns of SSIM windows a frame (their product is NW); the bytes of scratch beyond the
+ *                    outputs (0: the sums meet in the table through 64-bit integer atomics, whose order cannot show). */
+#define P3D_DISTORTION_FIELDS 2
+enum { P3D_DISTORTION_BLOCK = 0, P3D_DISTORTION_GATE = 1 };
+#define P3D_DISTORTION_RECORD 20
+enum { P3D_DISTORTION_SSE = 0, P3D_DISTORTION_WSSE = 4, P3D_DISTORTION_SW = 8, P3D_DISTORTION_MAXABS = 9, P3D_DISTORTION_CHANGED = 13,
+       P3D_DISTORTION_SALIENT = 14, P3D_DISTORTION_CHANGED_SALIENT = 15, P3D_DISTORTION_NW = 16, P3D_DISTORTION_SQ = 17,
+       P3D_DISTORTION_SWQ = 18, P3D_DISTORTION_SWW = 19 };
+int p3d_distortion_u8(int device, const unsigned char* sal, const unsigned char* ref, const unsigned char* test, int n, int H, int W,
+                      const int cfg[2], const int32_t wlaw[256], int64_t* table /* [n][P3D_DISTORTION_RECORD] */,
+                      int64_t* block_sse /* [n][Hb][Wb], may be NULL */);
+int p3d_video_distortion(p3d_handle* h, int first, int n, float scale, int H, int W, const unsigned char* ref /* NULL: kept source */,
+                         const unsigned char* test, const int cfg[2], const int32_t wlaw[256], int64_t* table,
+                         int64_t* block_sse /* may be NULL */, unsigned char* maps_out /* may be NULL */,
+                         double* stage_ms /* may be NULL, [3] */);
+int p3d_debug_distortion_u8(int device, const unsigned char* sal, const unsigned char* ref, const unsigned char* test, int n, int H, int W,
+                            const int cfg[2], const int32_t wlaw[256], int offset, int64_t* table, int64_t* block_sse);
+int p3d_debug_distortion_plan(int H, int W, int block, int n, int* tile_rows, int* tile_cols, int* blocks_per_frame, int* window_rows,
+                              int* window_cols, int64_t* scratch_bytes);
+
 /* ---- Shot boundaries of 8-bit frames (an ADDITION: the videos people reframe are edited, and a filter along the frame axis that
  * runs across a hard cut blends two unrelated scenes; automatic reframing tools find the cuts first).  OFF until called: every other
  * entry point issues what it issued before and returns the same bits.  PARITY UNPINNED: the reference's clips are single takes and

@@ -11,7 +11,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libp3dhip.so")
-SOURCES = ["conv_igemm2.hip", "conv_pointwise.hip", "conv_wgrad2.hip", "stem_wgrad.hip", "elementwise.hip", "bn_small.hip", "gn.hip", "cbam.hip", "head.hip", "attention.hip", "attention_flash.hip", "metrics.hip", "metrics_full.hip", "map_loss.hip", "augment.hip", "postprocess.hip", "hist_match.hip", "prior.hip", "fixpool.hip", "video.hip", "trainset.hip", "temporal.hip", "score_u8.hip", "score_auc_u8.hip", "render.hip", "reframe.hip", "regions.hip", "qpmap.hip", "prefilter.hip", "shots.hip", "net.hip"]
+SOURCES = ["conv_igemm2.hip", "conv_pointwise.hip", "conv_wgrad2.hip", "stem_wgrad.hip", "elementwise.hip", "bn_small.hip", "gn.hip", "cbam.hip", "head.hip", "attention.hip", "attention_flash.hip", "metrics.hip", "metrics_full.hip", "map_loss.hip", "augment.hip", "postprocess.hip", "hist_match.hip", "prior.hip", "fixpool.hip", "video.hip", "trainset.hip", "temporal.hip", "score_u8.hip", "score_auc_u8.hip", "render.hip", "reframe.hip", "regions.hip", "qpmap.hip", "prefilter.hip", "distortion.hip", "shots.hip", "net.hip"]
 # every header and include file present: a new .inc is a dependency without being listed (net.hip keeps the include order)
 HEADERS = sorted(os.path.join(CSRC, n) for n in os.listdir(CSRC) if n.endswith((".h", ".inc"))) + [os.path.join(os.path.dirname(HERE), "include", "p3d_hip.h")]
 # P3D_EXTRA_HIPCC_FLAGS: extra compile flags for A/B builds of the tuning macros (e.g. -DP3D_PF64=0), see tools/README.md

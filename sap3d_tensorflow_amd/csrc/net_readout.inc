@@ -831,12 +831,37 @@ struct PrefilterStage : ByteStage {
     void launch(hipStream_t s, const unsigned char* sal, unsigned*) override;
     void results(hipStream_t s) override;
 };
+// What one comparison of n test frames of H x W pixels with their reference frames under their maps asks for: test on the host
+// (uploaded); ref on the host (uploaded) or on the device where it is (the kept source); table and block_sse on the host, a null
+// block_sse is neither made nor copied back.
+struct DistortionCfg { int block, gate; };                 // CONFIG's two ints under their names
+struct DistortionRequest {
+    const char* who; int n, H, W;
+    const DistortionCfg* cfg = nullptr; const int32_t* wlaw = nullptr;      // host: 256 entries (distortion_check has passed them)
+    const unsigned char* ref = nullptr; const unsigned char* ref_dev = nullptr; const unsigned char* test = nullptr;
+    int64_t* table = nullptr; int64_t* block_sse = nullptr;
+    bool timed = false;
+};
+// The launches of distortion.hip behind some device bytes, with no arrival counters: the sums meet in the table through integer
+// atomics.  distortion_check has passed cfg, the law and the shape before one is built.
+struct DistortionStage : ByteStage {
+    const DistortionRequest r;
+    DistortionArgs a;
+    unsigned char* dref = nullptr; unsigned char* dtest = nullptr; int32_t* dlaw = nullptr;
+    explicit DistortionStage(const DistortionRequest& r);
+    size_t bgr() const { return bytes * 3; }              // the bytes of n frames
+    size_t grid() const { return (size_t)a.n * (size_t)a.Hb * (size_t)a.Wb; }      // elements of the block map
+    void carve(Carve& c) override;
+    void upload(hipStream_t s) override;
+    void launch(hipStream_t s, const unsigned char* sal, unsigned*) override;
+    void results(hipStream_t s) override;
+};
 // gen_pred.py's write-out of `maps` maps that live on the device, for p3d_pred_maps_u8 and p3d_video_maps_u8: the bytes, the
 // scratch of p3d_set_postprocess's stage and `extra` floats of the caller's share one slab of the stream's scratch.  sources runs
 // inside the device stage's time: it queues whatever makes the maps readable and names them as runs of maps of ph x pw pixels.
 // Off: one double-precision p3d_resize_u8 per run; on: the float32 resize / blur / normalise / byte sequence, P3D_POST_CHUNK maps
 // at a time.  Ends synchronised; stage_ms as p3d_pred_maps_u8's.
-// A stage (ByteStage: score, render, reframe, regions, qpmap, prefilter) takes the device bytes where they are instead of a copy of the chain: its buffers are
+// A stage (ByteStage: score, render, reframe, regions, qpmap, prefilter, distortion) takes the device bytes where they are instead of a copy of the chain: its buffers are
 // carved after the chain's in the same layout, its upload is queued ahead of the sources, its launches behind the chain with the
 // bytes and counters() zeroed arrival counters of its own (after the chain's), its results (the copies back to the host) behind
 // that; out may then be NULL (the bytes stay on the device) and, timed, its ms [3] receives the times of the upload, of the device
@@ -1895,7 +1920,7 @@ const unsigned char* kept_source(const p3d_handle* h, const char* who, int first
 void need_kept_source(const p3d_handle* h, const char* who) {
     if (!h->video.source) throw P3dError(std::string(who) + ": no frames are given and the video keeps no source (p3d_video_keep_source before the first p3d_video_put_frames_u8)");
 }
-// p3d_video_score, _score_auc, _render, _reframe, _regions, _qpmap and _prefilter behind the checks of their arguments: at most 65535 of the video's frames
+// p3d_video_score, _score_auc, _render, _reframe, _regions, _qpmap, _prefilter and _distortion behind the checks of their arguments: at most 65535 of the video's frames
 // through the maps' chain, the stage behind its bytes.  make builds the stage once the source has passed, so that what the stage
 // (or the kept source it reads) refuses is refused after it.  stage_ms (null, or n_ms >= 3 values): zeroed, then the stage's ms.
 void video_stage_run(p3d_handle* h, const char* who, int first, int n, float scale, unsigned char* maps_out, double* stage_ms, int n_ms,
@@ -2644,6 +2669,117 @@ int p3d_video_prefilter(p3d_handle* h, int first, int n, float scale, int H, int
         return *stage;
     });
     if (stage_ms && !frames) stage_ms[0] = 0.0;      // (nothing but the law and a shot table went up)
+    API_END
+}
+
+}  // extern "C"
+namespace {
+// ---- distortion of frames under their 8-bit maps (distortion.hip; the law in include/p3d_hip.h): one check, one launch description
+// and one stage for p3d_distortion_u8, the video entry and p3d_debug_distortion_u8; the plan hook shares the check's ranges ---------
+bool distortion_block_ok(int b) { return b == 0 || b == 8 || b == 16 || b == 32 || b == 64 || b == 128; }
+DistortionCfg distortion_check(const char* who, const int* cfg2, const int32_t* wlaw, int n, int H, int W, const void* test, const void* table,
+                               const void* block_sse) {
+    if (!cfg2 || !wlaw || !test || !table) throw P3dError("null argument");
+    const DistortionCfg c{cfg2[P3D_DISTORTION_BLOCK], cfg2[P3D_DISTORTION_GATE]};
+    map_shape_check(who, n, H, W, P3D_DISTORTION_MAX_PIXELS, "2^23, the bound of the 64-bit integer sums");
+    if (!distortion_block_ok(c.block)) throw P3dError(std::string(who) + ": the block is 0 (no block map), 8, 16, 32, 64 or 128, not " + std::to_string(c.block));
+    if (c.block == 0 && block_sse) throw P3dError(std::string(who) + ": a block map is given and the block is 0");
+    if (c.gate < 0 || c.gate > 255) throw P3dError(std::string(who) + ": the gate is 0 .. 255 (0: off)");
+    for (int v = 0; v < 256; ++v)
+        if (wlaw[v] < 0 || wlaw[v] > 255) throw P3dError(std::string(who) + ": wlaw[" + std::to_string(v) + "] = " + std::to_string(wlaw[v]) + " is outside 0 .. 255");
+    return c;
+}
+DistortionArgs distortion_args(const DistortionCfg& c, int n, int H, int W) {
+    DistortionArgs a;
+    a.n = n; a.H = H; a.W = W; a.block = c.block; a.gate = c.gate;
+    const DistortionPlan p = p3d_distortion_plan(H, W, c.block, n);
+    a.Hb = p.Hb; a.Wb = p.Wb; a.tiles_x = p.tiles_x; a.tiles_y = p.tiles_y; a.win_rows = p.win_rows; a.win_cols = p.win_cols;
+    a.ssim_tiles_x = p.ssim_tiles_x; a.ssim_tiles_y = p.ssim_tiles_y;
+    return a;
+}
+
+// ---- the distortion stage (declared above maps_u8_chain) --------------------------------------------------------------------------
+DistortionStage::DistortionStage(const DistortionRequest& r_) : ByteStage(r_), r(r_), a(distortion_args(*r_.cfg, r_.n, r_.H, r_.W)) {}
+void DistortionStage::carve(Carve& c) {
+    dref = r.ref ? c.input<unsigned char>(bgr(), 3) : nullptr;
+    dtest = c.input<unsigned char>(bgr(), 5);
+    dlaw = c.input<int32_t>(256);
+    a.table = c.take<long long>((size_t)a.n * P3D_DISTORTION_RECORD);
+    a.block_sse = r.block_sse ? c.take<long long>(grid()) : nullptr;
+}
+void DistortionStage::upload(hipStream_t s) {
+    HIPCHECK(hipMemcpyAsync(dlaw, r.wlaw, 256 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (dref) HIPCHECK(hipMemcpyAsync(dref, r.ref, bgr(), hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(dtest, r.test, bgr(), hipMemcpyHostToDevice, s));
+}
+void DistortionStage::launch(hipStream_t s, const unsigned char* sal, unsigned*) {
+    a.sal = sal; a.ref = dref ? dref : r.ref_dev; a.test = dtest; a.wlaw = dlaw;
+    HIPCHECK(p3d_distortion_launch(a, s));
+}
+void DistortionStage::results(hipStream_t s) {
+    static_assert(sizeof(long long) == sizeof(int64_t), "the table's element");
+    HIPCHECK(hipMemcpyAsync(r.table, a.table, (size_t)a.n * P3D_DISTORTION_RECORD * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    if (r.block_sse) HIPCHECK(hipMemcpyAsync(r.block_sse, a.block_sse, grid() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+}
+// p3d_distortion_u8 (offset < 0) and p3d_debug_distortion_u8 (offset in [0, 15]): the stage behind the host's bytes
+void distortion_on_host_bytes(const char* who, int device, const unsigned char* sal, const unsigned char* ref, const unsigned char* test, int n,
+                              int H, int W, const int* cfg, const int32_t* wlaw, int offset, bool hook, int64_t* table, int64_t* block_sse) {
+    if (!sal || !ref) throw P3dError("null argument");
+    const DistortionCfg dc = distortion_check(who, cfg, wlaw, n, H, W, test, table, block_sse);
+    if (hook) offset_check(who, offset);
+    metric_args(device, sal, cfg, 1, 1, table);
+    DistortionRequest r{who, n, H, W};
+    r.cfg = &dc; r.wlaw = wlaw; r.ref = ref; r.test = test; r.table = table; r.block_sse = block_sse;
+    DistortionStage stage(r);
+    stage_on_host_bytes(stage, sal, hook ? offset : -1);
+}
+}  // namespace
+extern "C" {
+
+int p3d_distortion_u8(int device, const unsigned char* sal, const unsigned char* ref, const unsigned char* test, int n, int H, int W,
+                      const int cfg[2], const int32_t wlaw[256], int64_t* table, int64_t* block_sse) {
+    API_BEGIN
+    distortion_on_host_bytes("distortion_u8", device, sal, ref, test, n, H, W, cfg, wlaw, -1, false, table, block_sse);
+    API_END
+}
+
+int p3d_debug_distortion_u8(int device, const unsigned char* sal, const unsigned char* ref, const unsigned char* test, int n, int H, int W,
+                            const int cfg[2], const int32_t wlaw[256], int offset, int64_t* table, int64_t* block_sse) {
+    API_BEGIN
+    distortion_on_host_bytes("debug_distortion_u8", device, sal, ref, test, n, H, W, cfg, wlaw, offset, true, table, block_sse);
+    API_END
+}
+
+int p3d_debug_distortion_plan(int H, int W, int block, int n, int* tile_rows, int* tile_cols, int* blocks_per_frame, int* window_rows,
+                              int* window_cols, int64_t* scratch_bytes) {
+    API_BEGIN
+    if (!tile_rows || !tile_cols || !blocks_per_frame || !window_rows || !window_cols || !scratch_bytes) throw P3dError("null argument");
+    if (H < 1 || W < 1 || (long long)H * W > P3D_DISTORTION_MAX_PIXELS || n < 1 || n > 65535 || !distortion_block_ok(block))
+        throw P3dError("debug_distortion_plan: 1 <= H * W <= 2^23, 1 .. 65535 frames, a block of 0, 8, 16, 32, 64 or 128");
+    const DistortionPlan p = p3d_distortion_plan(H, W, block, n);
+    *tile_rows = p.tile_rows; *tile_cols = p.tile_cols; *blocks_per_frame = (int)p.blocks_per_frame; *window_rows = p.win_rows;
+    *window_cols = p.win_cols; *scratch_bytes = (int64_t)p.scratch_bytes;
+    API_END
+}
+
+int p3d_video_distortion(p3d_handle* h, int first, int n, float scale, int H, int W, const unsigned char* ref, const unsigned char* test,
+                         const int cfg[2], const int32_t wlaw[256], int64_t* table, int64_t* block_sse, unsigned char* maps_out,
+                         double* stage_ms) {
+    API_BEGIN
+    const char* who = "video_distortion";
+    if (!h) throw P3dError("null argument");
+    h->video.need_open(who);
+    // before the shape: a call that leaves the size to the source has none to name when there is no source
+    if (!ref) need_kept_source(h, who);
+    const DistortionCfg dc = distortion_check(who, cfg, wlaw, std::max(1, std::min(n, 65535)), H, W, test, table, block_sse);
+    DistortionRequest r{who, n, H, W};
+    r.cfg = &dc; r.wlaw = wlaw; r.ref = ref; r.test = test; r.table = table; r.block_sse = block_sse; r.timed = stage_ms != nullptr;
+    std::unique_ptr<DistortionStage> stage;
+    video_stage_run(h, who, first, n, scale, maps_out, stage_ms, 3, [&]() -> ByteStage& {
+        if (!ref) r.ref_dev = kept_source(h, who, first, n, H, W, "compares");
+        stage.reset(new DistortionStage(r));
+        return *stage;
+    });
     API_END
 }
 

@@ -1241,6 +1241,30 @@ struct PrefilterArgs {
 };
 hipError_t p3d_prefilter_launch(const PrefilterArgs& a, hipStream_t s);
 
+// ---- distortion of frames under their 8-bit maps (distortion.hip; p3d_video_distortion / p3d_distortion_u8, the law in include/p3d_hip.h) ----
+// One launch sequence on n frames of H x W pixels: sal [n][H][W], ref and test [n][H][W][3] and the weight law wlaw [256] (0 .. 255)
+// -> table [n][P3D_DISTORTION_RECORD] int64 and, with block != 0 and block_sse set, block_sse [n][Hb][Wb] int64; every buffer device
+// memory.  The launches zero both outputs themselves and add to them with 64-bit integer atomics: no scratch, and no order can show.
+// Refused (hipErrorInvalidValue): a missing buffer, n outside [1, 65535], H * W outside [1, 2^23], a block or gate outside the
+// header's ranges, a block map with block = 0, a plan other than p3d_distortion_plan's.  The law's entries are the caller's to keep
+// in 0 .. 255: the 32-bit partial sums are proven for those.
+constexpr int P3D_DISTORTION_MAX_PIXELS = 1 << 23;
+constexpr int DISTORTION_TILE_ROWS = 64, DISTORTION_TILE_COLS = 128;      // pixels of a block's tile in the sums' launch
+constexpr int DISTORTION_SSIM_ROWS = 32, DISTORTION_SSIM_COLS = 64;       // pixels of a block's tile in the SSIM launch: 8 x 16 windows
+struct DistortionPlan {
+    int tile_rows = 0, tile_cols = 0, tiles_x = 0, tiles_y = 0, Hb = 0, Wb = 0;
+    int win_rows = 0, win_cols = 0, ssim_tiles_x = 0, ssim_tiles_y = 0;      // SSIM windows a frame, and the tiles that hold their corners
+    long long blocks_per_frame = 0, scratch_bytes = 0;
+};
+DistortionPlan p3d_distortion_plan(int H, int W, int block, int n);
+struct DistortionArgs {
+    const unsigned char* sal = nullptr; const unsigned char* ref = nullptr; const unsigned char* test = nullptr;
+    const int32_t* wlaw = nullptr; long long* table = nullptr; long long* block_sse = nullptr;
+    int n = 0, H = 0, W = 0, block = 0, gate = 0;
+    int Hb = 0, Wb = 0, tiles_x = 0, tiles_y = 0, win_rows = 0, win_cols = 0, ssim_tiles_x = 0, ssim_tiles_y = 0;      // p3d_distortion_plan(H, W, block, n)
+};
+hipError_t p3d_distortion_launch(const DistortionArgs& a, hipStream_t s);
+
 // ---- shot boundaries of 8-bit frames (shots.hip; p3d_shot_distances_u8 / p3d_shot_cuts, the law in include/p3d_hip.h) ----
 // The cut signal of n frames [n][H][W][3] of device bytes: D [n] device words, D_0 = 0, D_f the distance of frame f's cell
 // histograms from frame f - 1's.  tabs is scratch of (frames_per_chunk + 1) tables of table_words words on a 16-byte boundary: slot 0

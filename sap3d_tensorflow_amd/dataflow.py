@@ -884,6 +884,130 @@ def prefilter(sal, frames, law, block=16, peak_weight=128, dilate=0, fall=0, ris
     return out, g
 
 
+DISTORTION_BLOCKS = (0,) + QPMAP_BLOCKS
+
+
+def distortion_law(gate=0, gamma=1.0, floor=0):
+    """The table that turns a pixel's saliency level into its weight (the weight law of include/p3d_hip.h, "Distortion of frames under
+    their 8-bit maps") -> int32 [256], every entry in 0 .. 255.  A host table, built here in float64: level v >= gate gives
+    floor(255 (v / 255)^gamma + 0.5) (round half up), which is v itself at gamma = 1, the default w = s; level v < gate gives `floor`.
+    gate is 0 .. 255 (0: no level is below it); gamma is finite and > 0; floor is 0 .. 255."""
+    gate, gamma, floor = int(gate), float(gamma), int(floor)
+    if not 0 <= gate <= 255:
+        raise ValueError("gate is 0 .. 255")
+    if not (np.isfinite(gamma) and gamma > 0.):
+        raise ValueError("gamma is finite and > 0")
+    if not 0 <= floor <= 255:
+        raise ValueError("floor is 0 .. 255")
+    v = np.arange(256, dtype=np.float64)
+    law = v.astype(np.int32) if gamma == 1. else np.floor(255. * (v / 255.) ** gamma + 0.5).astype(np.int32)
+    law[:gate] = floor
+    return law
+
+
+def distortion_cfg(block=0, gate=0):
+    """The two ints of include/p3d_hip.h's CONFIG ("Distortion of frames under their 8-bit maps") in the order of the
+    P3D_DISTORTION_* indices."""
+    from . import _lib
+    cfg = (C.c_int * _lib.P3D_DISTORTION_FIELDS)()
+    cfg[_lib.P3D_DISTORTION_BLOCK], cfg[_lib.P3D_DISTORTION_GATE] = int(block), int(gate)
+    return cfg
+
+
+def _distortion_cfg(cfg):
+    """cfg as the library takes it, and its block: a distortion_cfg(), or (block, gate), or dict(block=, gate=)."""
+    from . import _lib
+    if isinstance(cfg, dict):
+        cfg = distortion_cfg(**cfg)
+    elif not isinstance(cfg, C.Array):
+        cfg = distortion_cfg(*cfg)
+    return cfg, int(cfg[_lib.P3D_DISTORTION_BLOCK])
+
+
+def distortion_plan(H, W, block=0, n=1):
+    """Test hook (p3d_debug_distortion_plan, host only): dict(tile_rows, tile_cols, blocks_per_frame, window_rows, window_cols,
+    scratch_bytes) of the distortion launches for n frames of H x W."""
+    tr, tc, b, wr, wc = (C.c_int(0) for _ in range(5))
+    s = C.c_int64(0)
+    check(lib().p3d_debug_distortion_plan(int(H), int(W), int(block), int(n), C.byref(tr), C.byref(tc), C.byref(b), C.byref(wr),
+                                          C.byref(wc), C.byref(s)))
+    return dict(tile_rows=tr.value, tile_cols=tc.value, blocks_per_frame=b.value, window_rows=wr.value, window_cols=wc.value,
+                scratch_bytes=s.value)
+
+
+def _distortion_law_array(law):
+    t = np.ascontiguousarray(law)
+    if t.dtype != np.int32 or t.shape != (256,):
+        raise ValueError("the weight law is int32 [256] (dataflow.distortion_law)")
+    return t
+
+
+def _distortion_frames(f, shape, what):
+    f = np.ascontiguousarray(f)
+    f = f[None] if f.ndim == 3 else f
+    if f.dtype != np.uint8 or f.shape != shape:
+        raise ValueError("%s frames are %s %s, expected uint8 %s" % (what, f.dtype, f.shape, shape))
+    return f
+
+
+def distortion(sal, ref, test, cfg, law, block_map=None, device=0, offset=None):
+    """Test frames compared with reference frames under their saliency on the device (p3d_distortion_u8; include/p3d_hip.h,
+    "Distortion of frames under their 8-bit maps"): maps uint8 [n, H, W] (or [H, W]: one frame), ref and test uint8 [n, H, W, 3] in
+    B, G, R order, cfg a distortion_cfg() (or (block, gate)) and a weight law int32 [256] (distortion_law) -> (table int64
+    [n, P3D_DISTORTION_RECORD], block_sse int64 [n, Hb, Wb] or None).  The table holds integers alone -- squared errors, weighted
+    squared errors, the weights' sum, largest differences and counts per plane B, G, R, Y, and SSIM's quantised window sums;
+    distortion_report turns it into PSNR and SSIM.  block_map: whether the block map is made (default: when cfg's block is not 0).
+    offset (0 .. 15): the test hook p3d_debug_distortion_u8, every device buffer between guards and the byte buffers shifted off a
+    16-byte boundary."""
+    from . import _lib
+    s3, _, _ = _reframe_shape(sal, 1)
+    n, H, W = s3.shape
+    r, t = _distortion_frames(ref, (n, H, W, 3), "reference"), _distortion_frames(test, (n, H, W, 3), "test")
+    w = _distortion_law_array(law)
+    cfg, B = _distortion_cfg(cfg)
+    table = np.empty((n, _lib.P3D_DISTORTION_RECORD), np.int64)
+    want_map = B != 0 if block_map is None else bool(block_map)
+    bs = np.empty((n, -(-H // B), -(-W // B)) if B in QPMAP_BLOCKS else (1,), np.int64) if want_map else None
+    u8 = _lib._u8p
+    head = (device, s3.ctypes.data_as(u8), r.ctypes.data_as(u8), t.ctypes.data_as(u8), n, H, W, cfg, w.ctypes.data_as(_lib._i32p))
+    tail = (table.ctypes.data_as(_lib._i64p), None if bs is None else bs.ctypes.data_as(_lib._i64p))
+    if offset is None:
+        check(lib().p3d_distortion_u8(*head, *tail))
+    else:
+        check(lib().p3d_debug_distortion_u8(*head, int(offset), *tail))
+    return table, bs
+
+
+def distortion_report(table, pixels):
+    """The float64 figures of a distortion table (int64 [n, P3D_DISTORTION_RECORD], or one record) of frames of `pixels` = H * W
+    pixels -> dict of float64 arrays: psnr [n, 4] = 10 log10(255^2 pixels / SSE) and wpsnr [n, 4] = 10 log10(255^2 SW / WSSE) per plane
+    B, G, R, Y; ssim [n] = SQ / (65536 NW) and wssim [n] = SWQ / (65536 SWW); changed_salient_share [n] = CHANGED_SALIENT /
+    SALIENT.  An SSE (or WSSE) of 0 gives +inf; a denominator of 0 (no weight, no window, no salient pixel) gives NaN.  A handful of
+    float64 operations on the device's integers, on the host."""
+    from . import _lib
+    K = _lib.K
+    t = np.asarray(table)
+    if t.dtype != np.int64 or t.ndim not in (1, 2) or t.shape[-1] != K["P3D_DISTORTION_RECORD"]:
+        raise ValueError("the table is int64 [n, %d]" % K["P3D_DISTORTION_RECORD"])
+    t = t.reshape(-1, t.shape[-1]).astype(np.float64)          # exact: every entry is below 2^53
+    sse, wsse = t[:, K["P3D_DISTORTION_SSE"]:][:, :4], t[:, K["P3D_DISTORTION_WSSE"]:][:, :4]
+    sw = t[:, K["P3D_DISTORTION_SW"]][:, None]
+    peak = 255. * 255.
+
+    def db(count, err):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out = 10. * np.log10(peak * count / err)
+        return np.where(count > 0, out, np.nan)          # (0 / 0 is NaN already; count = 0 with an error cannot happen)
+
+    def ratio(num, den):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(den > 0, num / den, np.nan)
+    return dict(psnr=db(np.full_like(sse, float(pixels)), sse), wpsnr=db(np.broadcast_to(sw, wsse.shape), wsse),
+                ssim=ratio(t[:, K["P3D_DISTORTION_SQ"]], 65536. * t[:, K["P3D_DISTORTION_NW"]]),
+                wssim=ratio(t[:, K["P3D_DISTORTION_SWQ"]], 65536. * t[:, K["P3D_DISTORTION_SWW"]]),
+                changed_salient_share=ratio(t[:, K["P3D_DISTORTION_CHANGED_SALIENT"]], t[:, K["P3D_DISTORTION_SALIENT"]]))
+
+
 def _shot_frames(frames):
     f = np.ascontiguousarray(frames)
     if f.dtype != np.uint8 or f.ndim != 4 or f.shape[3] != 3 or f.size == 0:

@@ -1123,6 +1123,36 @@ class P3DSession:
                                         _ptr(out, _lib._u8p), _ptr(grid, _lib._i32p), _ptr(maps, _lib._u8p), ms))
         return out, grid, maps, dict(upload=ms[0], device=ms[1], prefilter=ms[2])
 
+    def video_distortion(self, first, n, test, law, block=0, gate=0, ref=None, size=None, block_map=None, scale=255.):
+        """Frames first .. first + n - 1 of the open video compared with `test` under their saliency, on the device (an addition: what
+        a pre-filter or an encoder cost where the viewers look) -> (table int64 [n, P3D_DISTORTION_RECORD], block_sse int64
+        [n, Hb, Wb] or None, maps uint8 [n, H, W], stage_ms).  test: uint8 [n, H, W, 3] in B, G, R order, the decoded or filtered
+        frames.  ref: uint8 [n, H, W, 3], or None for the source kept by video_keep_source (H x W must then be the source's own).
+        The weights are `law` (int32 [256], dataflow.distortion_law) of video_maps_u8's bytes at H x W; `gate` counts the salient
+        pixels and those of them that changed; `block` (8 .. 128, 0: none) sizes the map of squared errors per block.  The table
+        holds integers alone; dataflow.distortion_report(table, H * W) gives PSNR, weighted PSNR, SSIM and weighted SSIM.
+        stage_ms: dict(upload, device = the maps' chain, distortion) of HIP-event times.  include/p3d_hip.h holds the exact rules."""
+        from . import dataflow
+        if test is None:
+            raise ValueError("test frames are required")
+        if size is None and ref is None:
+            size = np.shape(test)[1:3]
+        n, H, W, r, _, maps = _frame_inputs(self, n, size, ref, 2 ** 23, True, with_out=False)
+        t = np.ascontiguousarray(test)
+        if t.dtype != np.uint8 or t.shape != (n, H, W, 3):
+            raise ValueError("test frames are %s %s, expected uint8 %s" % (t.dtype, t.shape, (n, H, W, 3)))
+        B = int(block)
+        w = dataflow._distortion_law_array(law)
+        cfg = dataflow.distortion_cfg(B, gate)
+        table = np.empty((n, _lib.P3D_DISTORTION_RECORD), np.int64)
+        want_map = B != 0 if block_map is None else bool(block_map)
+        valid = maps.ndim == 3 and B in dataflow.QPMAP_BLOCKS      # (the library refuses the rest)
+        bs = np.empty((n, -(-H // B), -(-W // B)) if valid else (1,), np.int64) if want_map else None
+        ms = (C.c_double * 3)()
+        check(lib().p3d_video_distortion(self._h, int(first), n, float(scale), H, W, _ptr(r, _lib._u8p), _ptr(t, _lib._u8p), cfg,
+                                         _ptr(w, _lib._i32p), _ptr(table, _lib._i64p), _ptr(bs, _lib._i64p), _ptr(maps, _lib._u8p), ms))
+        return table, bs, maps, dict(upload=ms[0], device=ms[1], distortion=ms[2])
+
     def video_detect_shots(self, grid=(2, 2), threshold=250, window=2, ratio=512, min_length=3, install=True, with_signal=False):
         """Find the hard cuts of the open video on the device (an addition), from the source kept by video_keep_source: per frame a
         grid = (gy, gx) of cell histograms of the B, G, R bytes, D_f their distance from the frame before; frame f starts a shot
