@@ -668,204 +668,16 @@ struct ShotTable {
     void upload(hipStream_t s) const { if (dev) HIPCHECK(hipMemcpyAsync(dev, host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s)); }
     template <typename Args> void bind(Args& a) const { a.starts = dev; a.n_shots = dev ? n : 0; }
 };
-// What one scoring of n maps of H x W bytes asks for; every pointer is host memory.  Whatever is not asked for is not issued.
-struct ScoreRequest {
-    const char* who; int n, H, W;
-    int flags = 0, ties = P3D_SCORE_TIES_REFERENCE;      // the columns -> out [n][5]; 0: none, and the density is not read
-    const unsigned char* density = nullptr; const unsigned char* fixation = nullptr; double* out = nullptr;
-    // AUC-Borji -> borji [n][n_rep] (null: not asked for): map b's idx_rows[b] x n_rep indices (null: its fixated pixels, counted here)
-    const int* idx = nullptr; const int* idx_rows = nullptr; double* borji = nullptr;
-    // shuffled AUC -> shuffled [n][n_rep] (null: not asked for): ranks of n_rows[b] x n_rep draws into the union that `pool` holds
-    const int* ranks = nullptr; const int* n_rows = nullptr; const p3d_handle* pool = nullptr; double* shuffled = nullptr;
-    int n_rep = 0; double step = 0.0;
-    // rows_checked, for p3d_score_sweep_u8 and its hook alone: launch waits for the sweeps' preparation, reads the device's counts
-    // back and refuses idx_rows above them before it queues the sweeps.  A video caller must never set it: the wait would sit in
-    // the middle of its chain, and its rows come from the host's own counts.  top, the test hook alone: the sweep's capture
-    // [n][n_rep], carved, bound and copied back when set
-    bool rows_checked = false; int* top = nullptr;
-    bool timed = false;                                   // events around the stage's moments (ms) and around the sweeps (sweep_ms)
-};
-// The launches of score_u8.hip and score_auc_u8.hip behind some device bytes: the launch arguments, the tables of the host and the
-// device buffers, carved from a caller's scratch.  The constructor refuses what the request's arrays get wrong and queues nothing.
-struct ScoreStage : ByteStage {
-    const ScoreRequest r;
-    ScoreArgs a; ScoreSweepArgs q;
-    std::vector<int> nf, meta3, info; std::vector<long long> metaB, metaS;
-    size_t totB = 0, totS = 0; int max_rows = 0;
-    unsigned char* dd = nullptr; unsigned char* dx = nullptr;
-    int* didx = nullptr; int* dtop = nullptr; int* dranks = nullptr; int* dsel = nullptr; int* dmeta3 = nullptr; int* drows = nullptr;
-    long long* dmetaB = nullptr; long long* dmetaS = nullptr; double* perB = nullptr; double* perS = nullptr;
-    StageTimer sweeps;
-    explicit ScoreStage(const ScoreRequest& r);
-    bool sweep() const { return r.borji || r.shuffled; }
-    size_t counters() const override;
-    void carve(Carve& c) override;
-    void upload(hipStream_t s) override;
-    // pass A and the columns, then the sweeps' preparation (q.info: the device's counts); sweep_rest: the sweeps themselves
-    void prepare(hipStream_t s, const unsigned char* sal, unsigned* counters);
-    void sweep_rest(hipStream_t s);
-    void launch(hipStream_t s, const unsigned char* sal, unsigned* counters) override;
-    void results(hipStream_t s) override;
-    void check_counts() const;                            // after the results have arrived: the device's counts against nf
-    double sweep_ms() const { return sweeps.ev[0] ? (double)sweeps.ms(0) : 0.0; }
-};
-// What one rendering of n maps of H x W bytes asks for: frames on the host (uploaded), or on the device where they are (the kept
-// source), or neither (the heat map); out on the host.
-struct RenderRequest {
-    const char* who; int n, H, W;
-    const p3d_render* cfg = nullptr;
-    const unsigned char* frames = nullptr; const unsigned char* frames_dev = nullptr; unsigned char* out = nullptr;
-    bool timed = false;
-};
-// The launch of render.hip behind some device bytes.  It has no arrival counters: its blocks share nothing.  render_check has
-// passed cfg and the shape before one is built.
-struct RenderStage : ByteStage {
-    const RenderRequest r;
-    RenderArgs a;
-    unsigned char* df = nullptr; unsigned char* dout = nullptr; unsigned* dtab = nullptr;
-    explicit RenderStage(const RenderRequest& r);
-    size_t bgr() const { return bytes * 3; }              // the bytes of n frames, in or out
-    void carve(Carve& c) override;
-    void upload(hipStream_t s) override;
-    void launch(hipStream_t s, const unsigned char* sal, unsigned*) override;
-    void results(hipStream_t s) override;
-};
-// What one reframing of n maps of H x W bytes asks for: frames on the host (uploaded), or on the device where they are (the kept
-// source), or neither (tracks and masses only); track, raw, mass and out on the host, whatever is null is not copied back.
-struct ReframeRequest {
-    const char* who; int n, H, W;
-    const p3d_reframe* cfg = nullptr;
-    const unsigned char* frames = nullptr; const unsigned char* frames_dev = nullptr;
-    int32_t* track = nullptr; int32_t* raw = nullptr; uint32_t* mass = nullptr; unsigned char* out = nullptr;
-    bool timed = false;
-    const int32_t* starts = nullptr; int n_shots = 0;      // host: a shot table in frames of the call (shots_table_check has passed it), or none
-};
-// The launches of reframe.hip behind some device bytes, with no arrival counters: they hand results to one another from launch to
-// launch.  reframe_check has passed cfg and the shape before one is built.
-struct ReframeStage : ByteStage {
-    const ReframeRequest r;
-    ReframeArgs a;
-    unsigned char* df = nullptr;
-    ShotTable shots;
-    explicit ReframeStage(const ReframeRequest& r);
-    bool crops() const { return r.out != nullptr; }
-    void carve(Carve& c) override;
-    void upload(hipStream_t s) override;
-    void launch(hipStream_t s, const unsigned char* sal, unsigned*) override;
-    void results(hipStream_t s) override;
-};
-// What one labelling of n maps of H x W bytes asks for: regions, counts and labels on the host, whatever is null is not copied back.
-struct RegionsCfg { int gate, connectivity, min_area, max_regions, link; };      // CONFIG's five ints under their names
-struct RegionsRequest {
-    const char* who; int n, H, W;
-    const RegionsCfg* cfg = nullptr;
-    int32_t* regions = nullptr; int32_t* counts = nullptr; unsigned char* labels = nullptr;
-    bool timed = false;
-    const int32_t* starts = nullptr; int n_shots = 0;      // host: a shot table in frames of the call (shots_table_check has passed it), or none
-};
-// The launches of regions.hip behind some device bytes, with no arrival counters: they hand results to one another from launch to
-// launch.  regions_check has passed cfg and the shape before one is built.
-struct RegionsStage : ByteStage {
-    const RegionsRequest r;
-    RegionsArgs a;
-    ShotTable shots;
-    explicit RegionsStage(const RegionsRequest& r);
-    void carve(Carve& c) override;
-    void upload(hipStream_t s) override;
-    void launch(hipStream_t s, const unsigned char* sal, unsigned*) override;
-    void results(hipStream_t s) override;
-};
-// What one QP-map call on n maps of H x W bytes asks for: qp, levels and stats on the host, whatever is null is not copied back.
-struct QpmapCfg { int block, peak_weight, dilate, fall, rise, balance, target, lo, hi; };      // CONFIG's nine ints under their names
-struct QpmapRequest {
-    const char* who; int n, H, W;
-    const QpmapCfg* cfg = nullptr; const int32_t* law = nullptr;      // host: 256 entries (qpmap_check has passed them)
-    int32_t* qp = nullptr; unsigned char* levels = nullptr; int32_t* stats = nullptr;
-    bool timed = false;
-    const int32_t* starts = nullptr; int n_shots = 0;      // host: a shot table in frames of the call (shots_table_check has passed it), or none
-};
-// qpmap.hip's launch sequence as a stage queues it: the launch arguments, the law and the optional shot table on the device, and
-// the scratch of the first levels.  The qpmap stage holds one, and so does the prefilter stage, whose strength grid is these launches'
-// qp: each carves it among its own buffers.
-struct QpmapLaunches {
-    QpmapArgs a;
-    const int32_t* law; int32_t* dlaw = nullptr; ShotTable shots;
-    QpmapLaunches(const QpmapCfg& c, int n, int H, int W, const int32_t* law, const int32_t* starts, int n_shots);
-    size_t grid() const { return (size_t)a.n * (size_t)a.Hb * (size_t)a.Wb; }      // elements of qp and of levels
-    void carve(Carve& c, bool levels, bool stats);         // qp, levels and stats where asked for, the scratch, the law, the shot table
-    void upload(hipStream_t s) const;
-    void launch(hipStream_t s, const unsigned char* sal);
-};
-// The launches of qpmap.hip behind some device bytes, with no arrival counters: they hand results to one another from launch to
-// launch.  qpmap_check has passed cfg, the law and the shape before one is built.
-struct QpmapStage : ByteStage {
-    const QpmapRequest r;
-    QpmapLaunches q;
-    explicit QpmapStage(const QpmapRequest& r);
-    void carve(Carve& c) override;
-    void upload(hipStream_t s) override;
-    void launch(hipStream_t s, const unsigned char* sal, unsigned*) override;
-    void results(hipStream_t s) override;
-};
-// What one pre-filtering of n frames of H x W pixels by their maps asks for: frames on the host (uploaded) or on the device where they
-// are (the kept source); out and grid on the host, a null grid is not copied back.
-struct PrefilterCfg { int block, peak_weight, dilate, fall, rise, radius, passes; };      // CONFIG's seven ints under their names
-struct PrefilterRequest {
-    const char* who; int n, H, W;
-    const PrefilterCfg* cfg = nullptr; const int32_t* law = nullptr;      // host: 256 entries (prefilter_check has passed them)
-    const unsigned char* frames = nullptr; const unsigned char* frames_dev = nullptr; unsigned char* out = nullptr; int32_t* grid = nullptr;
-    bool timed = false;
-    const int32_t* starts = nullptr; int n_shots = 0;      // host: a shot table in frames of the call (shots_table_check has passed it), or none
-};
-// The launches of qpmap.hip (the strength grid, on this stage's own scratch) and of prefilter.hip behind some device bytes, with no
-// arrival counters.  prefilter_check has passed cfg, the law and the shape before one is built.
-struct PrefilterStage : ByteStage {
-    const PrefilterRequest r;
-    QpmapLaunches q;
-    PrefilterArgs a;
-    unsigned char* df = nullptr;
-    explicit PrefilterStage(const PrefilterRequest& r);
-    size_t bgr() const { return bytes * 3; }              // the bytes of n frames, in or out
-    void carve(Carve& c) override;
-    void upload(hipStream_t s) override;
-    void launch(hipStream_t s, const unsigned char* sal, unsigned*) override;
-    void results(hipStream_t s) override;
-};
-// What one comparison of n test frames of H x W pixels with their reference frames under their maps asks for: test on the host
-// (uploaded); ref on the host (uploaded) or on the device where it is (the kept source); table and block_sse on the host, a null
-// block_sse is neither made nor copied back.
-struct DistortionCfg { int block, gate; };                 // CONFIG's two ints under their names
-struct DistortionRequest {
-    const char* who; int n, H, W;
-    const DistortionCfg* cfg = nullptr; const int32_t* wlaw = nullptr;      // host: 256 entries (distortion_check has passed them)
-    const unsigned char* ref = nullptr; const unsigned char* ref_dev = nullptr; const unsigned char* test = nullptr;
-    int64_t* table = nullptr; int64_t* block_sse = nullptr;
-    bool timed = false;
-};
-// The launches of distortion.hip behind some device bytes, with no arrival counters: the sums meet in the table through integer
-// atomics.  distortion_check has passed cfg, the law and the shape before one is built.
-struct DistortionStage : ByteStage {
-    const DistortionRequest r;
-    DistortionArgs a;
-    unsigned char* dref = nullptr; unsigned char* dtest = nullptr; int32_t* dlaw = nullptr;
-    explicit DistortionStage(const DistortionRequest& r);
-    size_t bgr() const { return bytes * 3; }              // the bytes of n frames
-    size_t grid() const { return (size_t)a.n * (size_t)a.Hb * (size_t)a.Wb; }      // elements of the block map
-    void carve(Carve& c) override;
-    void upload(hipStream_t s) override;
-    void launch(hipStream_t s, const unsigned char* sal, unsigned*) override;
-    void results(hipStream_t s) override;
-};
 // gen_pred.py's write-out of `maps` maps that live on the device, for p3d_pred_maps_u8 and p3d_video_maps_u8: the bytes, the
 // scratch of p3d_set_postprocess's stage and `extra` floats of the caller's share one slab of the stream's scratch.  sources runs
 // inside the device stage's time: it queues whatever makes the maps readable and names them as runs of maps of ph x pw pixels.
 // Off: one double-precision p3d_resize_u8 per run; on: the float32 resize / blur / normalise / byte sequence, P3D_POST_CHUNK maps
 // at a time.  Ends synchronised; stage_ms as p3d_pred_maps_u8's.
-// A stage (ByteStage: score, render, reframe, regions, qpmap, prefilter, distortion) takes the device bytes where they are instead of a copy of the chain: its buffers are
-// carved after the chain's in the same layout, its upload is queued ahead of the sources, its launches behind the chain with the
-// bytes and counters() zeroed arrival counters of its own (after the chain's), its results (the copies back to the host) behind
-// that; out may then be NULL (the bytes stay on the device) and, timed, its ms [3] receives the times of the upload, of the device
-// stage and of the launches.  Without one, nothing here differs from what p3d_pred_maps_u8 and p3d_video_maps_u8 issue.
+// A stage (a ByteStage) takes the device bytes where they are instead of a copy of the chain: its buffers are carved
+// after the chain's in the same layout, its upload is queued ahead of the sources, its launches behind the chain with the bytes
+// and counters() zeroed arrival counters of its own (after the chain's), its results (the copies back to the host) behind that;
+// out may then be NULL (the bytes stay on the device) and, timed, its ms [3] receives the times of the upload, of the device stage
+// and of the launches.  Without one, nothing here differs from what p3d_pred_maps_u8 and p3d_video_maps_u8 issue.
 void maps_u8_chain(p3d_handle* h, long long maps, int ph, int pw, float scale, int H, int W, unsigned char* out, double* stage_ms,
                    size_t extra, const std::function<void(hipStream_t, float*, std::vector<PostRun>&)>& sources,
                    ByteStage* stage = nullptr) {
@@ -1841,6 +1653,8 @@ void map_shape_check(const char* who, int n, int H, int W, long long max_pixels,
     if (H < 1 || W < 1) throw P3dError(std::string(who) + ": empty map");
     if ((long long)H * W > max_pixels) throw P3dError(std::string(who) + ": H * W exceeds " + bound);
 }
+// The block sizes of the stages that work on a grid of blocks (qpmap, prefilter, distortion)
+bool block_size_ok(int block) { return block == 8 || block == 16 || block == 32 || block == 64 || block == 128; }
 void shots_table_check(const char* who, const int32_t* starts, int n_shots, int F);      // (net_shots.inc)
 // The open video's installed shot table cut to frames first .. first + n - 1, in frames of the call: its shots cut a stage's filters
 // and links.  Empty: no table is installed.
@@ -1851,6 +1665,12 @@ std::vector<int32_t> video_shots_within(const p3d_handle* h, int first, int n) {
     for (int32_t st : h->video.shots)
         if (st > first && st < first + n) shots.push_back(st - first);
     return shots;
+}
+// ... cut into a video entry's request; shots keeps what the request then names
+template <typename Request>
+void video_shots_into(const p3d_handle* h, int first, std::vector<int32_t>& shots, Request& r) {
+    shots = video_shots_within(h, first, r.n);
+    if (!shots.empty()) { r.starts = shots.data(); r.n_shots = (int)shots.size(); }
 }
 // What a hook sees of its block once a guarded run has passed the guards: the block as it was after the uploads and as it is after
 // the copies back.  A buffer is named by the device pointer its take returned.
@@ -1920,20 +1740,64 @@ const unsigned char* kept_source(const p3d_handle* h, const char* who, int first
 void need_kept_source(const p3d_handle* h, const char* who) {
     if (!h->video.source) throw P3dError(std::string(who) + ": no frames are given and the video keeps no source (p3d_video_keep_source before the first p3d_video_put_frames_u8)");
 }
-// p3d_video_score, _score_auc, _render, _reframe, _regions, _qpmap, _prefilter and _distortion behind the checks of their arguments: at most 65535 of the video's frames
-// through the maps' chain, the stage behind its bytes.  make builds the stage once the source has passed, so that what the stage
-// (or the kept source it reads) refuses is refused after it.  stage_ms (null, or n_ms >= 3 values): zeroed, then the stage's ms.
-void video_stage_run(p3d_handle* h, const char* who, int first, int n, float scale, unsigned char* maps_out, double* stage_ms, int n_ms,
-                     const std::function<ByteStage&()>& make) {
+// A video entry behind the checks of its arguments: at most 65535 of the video's frames through the maps' chain, a Stage built from
+// r behind their bytes.  The source comes first, then `ready` (the kept source and the installed shot table into r), then the
+// stage, so that what the kept source or the stage refuses is refused after the source's.  stage_ms (null, or n_ms >= 3 values):
+// zeroed, then the stage's ms.  (video_score_run, which reads its stage after the chain, issues the same steps itself.)
+template <typename Stage, typename Request, typename Ready>
+void video_stage_run(p3d_handle* h, Request& r, int first, float scale, unsigned char* maps_out, double* stage_ms, int n_ms, Ready ready) {
     HIPCHECK(hipSetDevice(h->cfg.device));
-    const VideoSource src(h, who, first, n, true, 65535);
-    ByteStage& stage = make();
+    const VideoSource src(h, r.who, first, r.n, true, 65535);
+    ready();
+    r.timed = stage_ms != nullptr;
+    Stage stage(r);
     for (int i = 0; stage_ms && i < n_ms; ++i) stage_ms[i] = 0.0;
-    maps_u8_chain(h, n, h->pred->H, h->pred->W, scale, stage.H, stage.W, maps_out, nullptr, src.extra(), src, &stage);
+    maps_u8_chain(h, r.n, h->pred->H, h->pred->W, scale, r.H, r.W, maps_out, nullptr, src.extra(), src, &stage);
     for (int i = 0; stage_ms && i < 3; ++i) stage_ms[i] = stage.ms[i];
 }
 // ---- scoring 8-bit maps (score_u8.hip; the law in include/p3d_hip.h): one check, one launch sequence and one stage (the
 // table of buffer sizes is its own) for p3d_score_maps_u8, the video entries and p3d_debug_score_u8 ----------------------------------
+// What one scoring of n maps of H x W bytes asks for; every pointer is host memory.  Whatever is not asked for is not issued.
+struct ScoreRequest {
+    const char* who; int n, H, W;
+    int flags = 0, ties = P3D_SCORE_TIES_REFERENCE;      // the columns -> out [n][5]; 0: none, and the density is not read
+    const unsigned char* density = nullptr; const unsigned char* fixation = nullptr; double* out = nullptr;
+    // AUC-Borji -> borji [n][n_rep] (null: not asked for): map b's idx_rows[b] x n_rep indices (null: its fixated pixels, counted here)
+    const int* idx = nullptr; const int* idx_rows = nullptr; double* borji = nullptr;
+    // shuffled AUC -> shuffled [n][n_rep] (null: not asked for): ranks of n_rows[b] x n_rep draws into the union that `pool` holds
+    const int* ranks = nullptr; const int* n_rows = nullptr; const p3d_handle* pool = nullptr; double* shuffled = nullptr;
+    int n_rep = 0; double step = 0.0;
+    // rows_checked, for p3d_score_sweep_u8 and its hook alone: launch waits for the sweeps' preparation, reads the device's counts
+    // back and refuses idx_rows above them before it queues the sweeps.  A video caller must never set it: the wait would sit in
+    // the middle of its chain, and its rows come from the host's own counts.  top, the test hook alone: the sweep's capture
+    // [n][n_rep], carved, bound and copied back when set
+    bool rows_checked = false; int* top = nullptr;
+    bool timed = false;                                   // events around the stage's moments (ms) and around the sweeps (sweep_ms)
+};
+// The launches of score_u8.hip and score_auc_u8.hip behind some device bytes: the launch arguments, the tables of the host and the
+// device buffers, carved from a caller's scratch.  The constructor refuses what the request's arrays get wrong and queues nothing.
+struct ScoreStage : ByteStage {
+    const ScoreRequest r;
+    ScoreArgs a; ScoreSweepArgs q;
+    std::vector<int> nf, meta3, info; std::vector<long long> metaB, metaS;
+    size_t totB = 0, totS = 0; int max_rows = 0;
+    unsigned char* dd = nullptr; unsigned char* dx = nullptr;
+    int* didx = nullptr; int* dtop = nullptr; int* dranks = nullptr; int* dsel = nullptr; int* dmeta3 = nullptr; int* drows = nullptr;
+    long long* dmetaB = nullptr; long long* dmetaS = nullptr; double* perB = nullptr; double* perS = nullptr;
+    StageTimer sweeps;
+    explicit ScoreStage(const ScoreRequest& r);
+    bool sweep() const { return r.borji || r.shuffled; }
+    size_t counters() const override;
+    void carve(Carve& c) override;
+    void upload(hipStream_t s) override;
+    // pass A and the columns, then the sweeps' preparation (q.info: the device's counts); sweep_rest: the sweeps themselves
+    void prepare(hipStream_t s, const unsigned char* sal, unsigned* counters);
+    void sweep_rest(hipStream_t s);
+    void launch(hipStream_t s, const unsigned char* sal, unsigned* counters) override;
+    void results(hipStream_t s) override;
+    void check_counts() const;                            // after the results have arrived: the device's counts against nf
+    double sweep_ms() const { return sweeps.ev[0] ? (double)sweeps.ms(0) : 0.0; }
+};
 void score_check(const char* who, const void* density, const void* fixation, int n, int H, int W, int flags, int ties, const void* out) {
     if (!density || !out) throw P3dError("null argument");
     map_shape_check(who, n, H, W, P3D_SCORE_MAX_PIXELS, "2^23, the bound of the 64-bit integer sums");
@@ -2014,6 +1878,27 @@ int p3d_debug_score_plan(int64_t n_pix, int n, int offset, int* blocks_per_map, 
 namespace {
 // ---- rendering 8-bit maps over their frames (render.hip; the law in include/p3d_hip.h): one check and one launch
 // description for p3d_render_u8, the render stage and p3d_debug_render_u8 ------------------------------------------------
+// What one rendering of n maps of H x W bytes asks for: frames on the host (uploaded), or on the device where they are (the kept
+// source), or neither (the heat map); out on the host.
+struct RenderRequest {
+    const char* who; int n, H, W;
+    const p3d_render* cfg = nullptr;
+    const unsigned char* frames = nullptr; const unsigned char* frames_dev = nullptr; unsigned char* out = nullptr;
+    bool timed = false;
+};
+// The launch of render.hip behind some device bytes.  It has no arrival counters: its blocks share nothing.  render_check has
+// passed cfg and the shape before one is built.
+struct RenderStage : ByteStage {
+    const RenderRequest r;
+    RenderArgs a;
+    unsigned char* df = nullptr; unsigned char* dout = nullptr; unsigned* dtab = nullptr;
+    explicit RenderStage(const RenderRequest& r);
+    size_t bgr() const { return bytes * 3; }              // the bytes of n frames, in or out
+    void carve(Carve& c) override;
+    void upload(hipStream_t s) override;
+    void launch(hipStream_t s, const unsigned char* sal, unsigned*) override;
+    void results(hipStream_t s) override;
+};
 void render_check(const char* who, const p3d_render* cfg, int n, int H, int W, const void* out) {
     if (!cfg || !out) throw P3dError("null argument");
     map_shape_check(who, n, H, W, P3D_RENDER_MAX_PIXELS, "2^28, the bound of the int32 offsets inside a map");
@@ -2030,7 +1915,6 @@ RenderArgs render_args(const p3d_render& cfg, int n, int H, int W) {
     return a;
 }
 
-// ---- the render stage (declared above maps_u8_chain) ------------------------------------------------------------------------------
 RenderStage::RenderStage(const RenderRequest& r_) : ByteStage(r_), r(r_), a(render_args(*r_.cfg, r_.n, r_.H, r_.W)) {}
 void RenderStage::carve(Carve& c) {
     df = r.frames ? c.input<unsigned char>(bgr(), 3) : nullptr;
@@ -2048,34 +1932,32 @@ void RenderStage::launch(hipStream_t s, const unsigned char* sal, unsigned*) {
 void RenderStage::results(hipStream_t s) {
     HIPCHECK(hipMemcpyAsync(r.out, dout, bgr(), hipMemcpyDeviceToHost, s));
 }
+// p3d_render_u8 (offset < 0) and p3d_debug_render_u8 (offset in [0, 15]): the stage behind the host's bytes
+void render_on_host_bytes(const char* who, int device, const unsigned char* sal, const unsigned char* frames, int n, int H, int W,
+                          const p3d_render* cfg, int offset, bool hook, unsigned char* out) {
+    if (!sal) throw P3dError("null argument");
+    render_check(who, cfg, n, H, W, out);
+    if (hook) offset_check(who, offset);
+    metric_args(device, sal, cfg, 1, 1, out);
+    RenderRequest r{who, n, H, W};
+    r.cfg = cfg; r.frames = frames; r.out = out;
+    RenderStage stage(r);
+    stage_on_host_bytes(stage, sal, hook ? offset : -1);
+}
 }  // namespace
 extern "C" {
 
 int p3d_render_u8(int device, const unsigned char* sal, const unsigned char* frames, int n, int H, int W, const p3d_render* cfg,
                   unsigned char* out) {
     API_BEGIN
-    if (!sal) throw P3dError("null argument");
-    render_check("render_u8", cfg, n, H, W, out);
-    metric_args(device, sal, cfg, 1, 1, out);
-    RenderRequest r{"render_u8", n, H, W};
-    r.cfg = cfg; r.frames = frames; r.out = out;
-    RenderStage stage(r);
-    stage_on_host_bytes(stage, sal);
+    render_on_host_bytes("render_u8", device, sal, frames, n, H, W, cfg, -1, false, out);
     API_END
 }
 
 int p3d_debug_render_u8(int device, const unsigned char* sal, const unsigned char* frames, int n, int H, int W, const p3d_render* cfg,
                         int offset, unsigned char* out) {
     API_BEGIN
-    const char* who = "debug_render_u8";
-    if (!sal) throw P3dError("null argument");
-    render_check(who, cfg, n, H, W, out);
-    offset_check(who, offset);
-    metric_args(device, sal, cfg, 1, 1, out);
-    RenderRequest r{who, n, H, W};
-    r.cfg = cfg; r.frames = frames; r.out = out;
-    RenderStage stage(r);
-    stage_on_host_bytes(stage, sal, offset);
+    render_on_host_bytes("debug_render_u8", device, sal, frames, n, H, W, cfg, offset, true, out);
     API_END
 }
 
@@ -2119,12 +2001,9 @@ int p3d_video_render(p3d_handle* h, int first, int n, float scale, int H, int W,
     if (!frames) need_kept_source(h, who);
     render_check(who, cfg, std::max(1, std::min(n, 65535)), H, W, out);
     RenderRequest r{who, n, H, W};
-    r.cfg = cfg; r.frames = frames; r.out = out; r.timed = stage_ms != nullptr;
-    std::unique_ptr<RenderStage> stage;
-    video_stage_run(h, who, first, n, scale, maps_out, stage_ms, 3, [&]() -> ByteStage& {
+    r.cfg = cfg; r.frames = frames; r.out = out;
+    video_stage_run<RenderStage>(h, r, first, scale, maps_out, stage_ms, 3, [&] {
         if (!frames) r.frames_dev = kept_source(h, who, first, n, H, W, "renders");
-        stage.reset(new RenderStage(r));
-        return *stage;
     });
     if (stage_ms && !frames) stage_ms[0] = 0.0;      // (nothing but the table went up)
     API_END
@@ -2134,6 +2013,30 @@ int p3d_video_render(p3d_handle* h, int first, int n, float scale, int H, int W,
 namespace {
 // ---- reframing around 8-bit maps (reframe.hip; the law in include/p3d_hip.h): one check, one launch description and one stage
 // (the table of buffer sizes is its own) for p3d_reframe_u8, the video entry, p3d_debug_reframe_u8 and p3d_reframe_shots_u8 ---------
+// What one reframing of n maps of H x W bytes asks for: frames on the host (uploaded), or on the device where they are (the kept
+// source), or neither (tracks and masses only); track, raw, mass and out on the host, whatever is null is not copied back.
+struct ReframeRequest {
+    const char* who; int n, H, W;
+    const p3d_reframe* cfg = nullptr;
+    const unsigned char* frames = nullptr; const unsigned char* frames_dev = nullptr;
+    int32_t* track = nullptr; int32_t* raw = nullptr; uint32_t* mass = nullptr; unsigned char* out = nullptr;
+    bool timed = false;
+    const int32_t* starts = nullptr; int n_shots = 0;      // host: a shot table in frames of the call (shots_table_check has passed it), or none
+};
+// The launches of reframe.hip behind some device bytes, with no arrival counters: they hand results to one another from launch to
+// launch.  reframe_check has passed cfg and the shape before one is built.
+struct ReframeStage : ByteStage {
+    const ReframeRequest r;
+    ReframeArgs a;
+    unsigned char* df = nullptr;
+    ShotTable shots;
+    explicit ReframeStage(const ReframeRequest& r);
+    bool crops() const { return r.out != nullptr; }
+    void carve(Carve& c) override;
+    void upload(hipStream_t s) override;
+    void launch(hipStream_t s, const unsigned char* sal, unsigned*) override;
+    void results(hipStream_t s) override;
+};
 void reframe_check(const char* who, const p3d_reframe* cfg, int n, int H, int W, const void* track) {
     if (!cfg || !track) throw P3dError("null argument");
     map_shape_check(who, n, H, W, P3D_REFRAME_MAX_PIXELS, "2^23, the bound that keeps a mass in 32 bits");
@@ -2161,7 +2064,6 @@ struct ReframeSizes {
     }
 };
 
-// ---- the reframe stage (declared above maps_u8_chain) -----------------------------------------------------------------------------
 ReframeStage::ReframeStage(const ReframeRequest& r_) : ByteStage(r_), r(r_), a(reframe_args(*r_.cfg, r_.n, r_.H, r_.W)), shots{r_.starts, r_.n_shots} {}
 void ReframeStage::carve(Carve& c) {
     const ReframeSizes z(a);
@@ -2191,54 +2093,45 @@ void ReframeStage::results(hipStream_t s) {
     if (r.mass) HIPCHECK(hipMemcpyAsync(r.mass, a.mass, z.masses * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     if (crops()) HIPCHECK(hipMemcpyAsync(r.out, a.out, z.crop, hipMemcpyDeviceToHost, s));
 }
+// The stage behind the host's bytes, for the three entries: p3d_reframe_u8 (no shot table, no offset), p3d_debug_reframe_u8 (no
+// shot table, offset in [0, 15]) and p3d_reframe_shots_u8 (a shot table always, offset in [0, 15] or -1 for the stream's scratch)
+enum ReframeEntry { REFRAME_OP, REFRAME_HOOK, REFRAME_SHOTS };
+void reframe_on_host_bytes(ReframeEntry entry, const char* who, int device, const unsigned char* sal, const unsigned char* frames, int n, int H,
+                           int W, const p3d_reframe* cfg, const int32_t* starts, int n_shots, int offset, int32_t* track, int32_t* raw,
+                           uint32_t* mass, unsigned char* out) {
+    const bool hook = entry != REFRAME_OP, shots = entry == REFRAME_SHOTS;
+    if (!sal) throw P3dError("null argument");
+    reframe_check(who, cfg, n, H, W, track);
+    if ((frames == nullptr) != (out == nullptr)) throw P3dError(std::string(who) + ": out is given exactly when frames are");
+    if (shots) shots_table_check(who, starts, n_shots, n);
+    if (hook) offset_check(who, offset, shots);
+    metric_args(device, sal, cfg, 1, 1, track);
+    ReframeRequest r{who, n, H, W};
+    r.cfg = cfg; r.frames = frames; r.track = track; r.raw = raw; r.mass = mass; r.out = out; r.starts = starts; r.n_shots = n_shots;
+    ReframeStage stage(r);
+    stage_on_host_bytes(stage, sal, hook ? offset : -1);
+}
 }  // namespace
 extern "C" {
 
 int p3d_reframe_u8(int device, const unsigned char* sal, const unsigned char* frames, int n, int H, int W, const p3d_reframe* cfg,
                    int32_t* track, int32_t* raw, uint32_t* mass, unsigned char* out) {
     API_BEGIN
-    const char* who = "reframe_u8";
-    if (!sal) throw P3dError("null argument");
-    reframe_check(who, cfg, n, H, W, track);
-    if ((frames == nullptr) != (out == nullptr)) throw P3dError(std::string(who) + ": out is given exactly when frames are");
-    metric_args(device, sal, cfg, 1, 1, track);
-    ReframeRequest r{who, n, H, W};
-    r.cfg = cfg; r.frames = frames; r.track = track; r.raw = raw; r.mass = mass; r.out = out;
-    ReframeStage stage(r);
-    stage_on_host_bytes(stage, sal);
+    reframe_on_host_bytes(REFRAME_OP, "reframe_u8", device, sal, frames, n, H, W, cfg, nullptr, 0, -1, track, raw, mass, out);
     API_END
 }
 
 int p3d_debug_reframe_u8(int device, const unsigned char* sal, const unsigned char* frames, int n, int H, int W, const p3d_reframe* cfg,
                          int offset, int32_t* track, int32_t* raw, uint32_t* mass, unsigned char* out) {
     API_BEGIN
-    const char* who = "debug_reframe_u8";
-    if (!sal) throw P3dError("null argument");
-    reframe_check(who, cfg, n, H, W, track);
-    if ((frames == nullptr) != (out == nullptr)) throw P3dError(std::string(who) + ": out is given exactly when frames are");
-    offset_check(who, offset);
-    metric_args(device, sal, cfg, 1, 1, track);
-    ReframeRequest r{who, n, H, W};
-    r.cfg = cfg; r.frames = frames; r.track = track; r.raw = raw; r.mass = mass; r.out = out;
-    ReframeStage stage(r);
-    stage_on_host_bytes(stage, sal, offset);
+    reframe_on_host_bytes(REFRAME_HOOK, "debug_reframe_u8", device, sal, frames, n, H, W, cfg, nullptr, 0, offset, track, raw, mass, out);
     API_END
 }
 
 int p3d_reframe_shots_u8(int device, const unsigned char* sal, const unsigned char* frames, int n, int H, int W, const p3d_reframe* cfg,
                          const int32_t* starts, int n_shots, int offset, int32_t* track, int32_t* raw, uint32_t* mass, unsigned char* out) {
     API_BEGIN
-    const char* who = "reframe_shots_u8";
-    if (!sal) throw P3dError("null argument");
-    reframe_check(who, cfg, n, H, W, track);
-    if ((frames == nullptr) != (out == nullptr)) throw P3dError(std::string(who) + ": out is given exactly when frames are");
-    shots_table_check(who, starts, n_shots, n);
-    offset_check(who, offset, true);
-    metric_args(device, sal, cfg, 1, 1, track);
-    ReframeRequest r{who, n, H, W};
-    r.cfg = cfg; r.frames = frames; r.track = track; r.raw = raw; r.mass = mass; r.out = out; r.starts = starts; r.n_shots = n_shots;
-    ReframeStage stage(r);
-    stage_on_host_bytes(stage, sal, offset);
+    reframe_on_host_bytes(REFRAME_SHOTS, "reframe_shots_u8", device, sal, frames, n, H, W, cfg, starts, n_shots, offset, track, raw, mass, out);
     API_END
 }
 
@@ -2265,15 +2158,11 @@ int p3d_video_reframe(p3d_handle* h, int first, int n, float scale, int H, int W
     if (out && !frames) need_kept_source(h, who);
     reframe_check(who, cfg, std::max(1, std::min(n, 65535)), H, W, track);
     ReframeRequest r{who, n, H, W};
-    r.cfg = cfg; r.frames = frames; r.track = track; r.raw = raw; r.mass = mass; r.out = out; r.timed = stage_ms != nullptr;
-    std::unique_ptr<ReframeStage> stage;
+    r.cfg = cfg; r.frames = frames; r.track = track; r.raw = raw; r.mass = mass; r.out = out;
     std::vector<int32_t> shots;                            // the installed table in frames of the call: its shots cut the track's filter
-    video_stage_run(h, who, first, n, scale, maps_out, stage_ms, 3, [&]() -> ByteStage& {
+    video_stage_run<ReframeStage>(h, r, first, scale, maps_out, stage_ms, 3, [&] {
         if (out && !frames) r.frames_dev = kept_source(h, who, first, n, H, W, "reframes");
-        shots = video_shots_within(h, first, n);
-        if (!shots.empty()) { r.starts = shots.data(); r.n_shots = (int)shots.size(); }
-        stage.reset(new ReframeStage(r));
-        return *stage;
+        video_shots_into(h, first, shots, r);
     });
     if (stage_ms && !frames) stage_ms[0] = 0.0;      // (nothing went up)
     API_END
@@ -2283,6 +2172,27 @@ int p3d_video_reframe(p3d_handle* h, int first, int n, float scale, int H, int W
 namespace {
 // ---- salient regions of 8-bit maps (regions.hip; the law in include/p3d_hip.h): one check, one launch description and one stage
 // (the table of buffer sizes is its own) for p3d_regions_u8, the video entry and p3d_debug_regions_u8 -------------------------------
+// What one labelling of n maps of H x W bytes asks for: regions, counts and labels on the host, whatever is null is not copied back.
+struct RegionsCfg { int gate, connectivity, min_area, max_regions, link; };      // CONFIG's five ints under their names
+struct RegionsRequest {
+    const char* who; int n, H, W;
+    const RegionsCfg* cfg = nullptr;
+    int32_t* regions = nullptr; int32_t* counts = nullptr; unsigned char* labels = nullptr;
+    bool timed = false;
+    const int32_t* starts = nullptr; int n_shots = 0;      // host: a shot table in frames of the call (shots_table_check has passed it), or none
+};
+// The launches of regions.hip behind some device bytes, with no arrival counters: they hand results to one another from launch to
+// launch.  regions_check has passed cfg and the shape before one is built.
+struct RegionsStage : ByteStage {
+    const RegionsRequest r;
+    RegionsArgs a;
+    ShotTable shots;
+    explicit RegionsStage(const RegionsRequest& r);
+    void carve(Carve& c) override;
+    void upload(hipStream_t s) override;
+    void launch(hipStream_t s, const unsigned char* sal, unsigned*) override;
+    void results(hipStream_t s) override;
+};
 RegionsCfg regions_check(const char* who, const int* cfg5, int n, int H, int W, const void* regions) {
     if (!cfg5 || !regions) throw P3dError("null argument");
     const RegionsCfg parsed{cfg5[P3D_REGIONS_GATE], cfg5[P3D_REGIONS_CONNECTIVITY], cfg5[P3D_REGIONS_MIN_AREA], cfg5[P3D_REGIONS_MAX_REGIONS], cfg5[P3D_REGIONS_LINK]};
@@ -2312,7 +2222,6 @@ struct RegionsSizes {
           p(p3d_regions_plan(a.H, a.W, a.n, a.K, a.link, a.lab_full)) {}
 };
 
-// ---- the regions stage (declared above maps_u8_chain) -----------------------------------------------------------------------------
 RegionsStage::RegionsStage(const RegionsRequest& r_) : ByteStage(r_), r(r_), a(regions_args(*r_.cfg, r_.n, r_.H, r_.W, r_.labels != nullptr)),
       shots{r_.starts, r_.n_shots} {}
 void RegionsStage::carve(Carve& c) {
@@ -2342,37 +2251,33 @@ void RegionsStage::results(hipStream_t s) {
     if (r.counts) HIPCHECK(hipMemcpyAsync(r.counts, a.counts, z.counts * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     if (r.labels) HIPCHECK(hipMemcpyAsync(r.labels, a.lab, z.sal, hipMemcpyDeviceToHost, s));
 }
+// p3d_regions_u8 (offset < 0) and p3d_debug_regions_u8 (offset in [0, 15]): the stage behind the host's bytes
+void regions_on_host_bytes(const char* who, int device, const unsigned char* sal, int n, int H, int W, const int* cfg, const int32_t* starts,
+                           int n_shots, int offset, bool hook, int32_t* regions, int32_t* counts, unsigned char* labels) {
+    if (!sal) throw P3dError("null argument");
+    const RegionsCfg rc = regions_check(who, cfg, n, H, W, regions);
+    if (starts || n_shots) shots_table_check(who, starts, n_shots, n);
+    if (hook) offset_check(who, offset);
+    metric_args(device, sal, cfg, 1, 1, regions);
+    RegionsRequest r{who, n, H, W};
+    r.cfg = &rc; r.regions = regions; r.counts = counts; r.labels = labels; r.starts = starts; r.n_shots = n_shots;
+    RegionsStage stage(r);
+    stage_on_host_bytes(stage, sal, hook ? offset : -1);
+}
 }  // namespace
 extern "C" {
 
 int p3d_regions_u8(int device, const unsigned char* sal, int n, int H, int W, const int cfg[5], const int32_t* starts, int n_shots,
                    int32_t* regions, int32_t* counts, unsigned char* labels) {
     API_BEGIN
-    const char* who = "regions_u8";
-    if (!sal) throw P3dError("null argument");
-    const RegionsCfg rc = regions_check(who, cfg, n, H, W, regions);
-    if (starts || n_shots) shots_table_check(who, starts, n_shots, n);
-    metric_args(device, sal, cfg, 1, 1, regions);
-    RegionsRequest r{who, n, H, W};
-    r.cfg = &rc; r.regions = regions; r.counts = counts; r.labels = labels; r.starts = starts; r.n_shots = n_shots;
-    RegionsStage stage(r);
-    stage_on_host_bytes(stage, sal);
+    regions_on_host_bytes("regions_u8", device, sal, n, H, W, cfg, starts, n_shots, -1, false, regions, counts, labels);
     API_END
 }
 
 int p3d_debug_regions_u8(int device, const unsigned char* sal, int n, int H, int W, const int cfg[5], const int32_t* starts, int n_shots,
                          int offset, int32_t* regions, int32_t* counts, unsigned char* labels) {
     API_BEGIN
-    const char* who = "debug_regions_u8";
-    if (!sal) throw P3dError("null argument");
-    const RegionsCfg rc = regions_check(who, cfg, n, H, W, regions);
-    if (starts || n_shots) shots_table_check(who, starts, n_shots, n);
-    offset_check(who, offset);
-    metric_args(device, sal, cfg, 1, 1, regions);
-    RegionsRequest r{who, n, H, W};
-    r.cfg = &rc; r.regions = regions; r.counts = counts; r.labels = labels; r.starts = starts; r.n_shots = n_shots;
-    RegionsStage stage(r);
-    stage_on_host_bytes(stage, sal, offset);
+    regions_on_host_bytes("debug_regions_u8", device, sal, n, H, W, cfg, starts, n_shots, offset, true, regions, counts, labels);
     API_END
 }
 
@@ -2397,15 +2302,9 @@ int p3d_video_regions(p3d_handle* h, int first, int n, float scale, int H, int W
     h->video.need_open(who);
     const RegionsCfg rc = regions_check(who, cfg, std::max(1, std::min(n, 65535)), H, W, regions);
     RegionsRequest r{who, n, H, W};
-    r.cfg = &rc; r.regions = regions; r.counts = counts; r.labels = labels; r.timed = stage_ms != nullptr;
-    std::unique_ptr<RegionsStage> stage;
+    r.cfg = &rc; r.regions = regions; r.counts = counts; r.labels = labels;
     std::vector<int32_t> shots;                            // the installed table in frames of the call, cut as p3d_video_reframe cuts it
-    video_stage_run(h, who, first, n, scale, maps_out, stage_ms, 3, [&]() -> ByteStage& {
-        shots = video_shots_within(h, first, n);
-        if (!shots.empty()) { r.starts = shots.data(); r.n_shots = (int)shots.size(); }
-        stage.reset(new RegionsStage(r));
-        return *stage;
-    });
+    video_stage_run<RegionsStage>(h, r, first, scale, maps_out, stage_ms, 3, [&] { video_shots_into(h, first, shots, r); });
     if (stage_ms) stage_ms[0] = 0.0;                   // (nothing but a shot table went up)
     API_END
 }
@@ -2414,12 +2313,44 @@ int p3d_video_regions(p3d_handle* h, int first, int n, float scale, int H, int W
 namespace {
 // ---- QP maps of 8-bit maps (qpmap.hip; the law in include/p3d_hip.h): one check, one launch description and one stage (the table of
 // buffer sizes is its own) for p3d_qpmap_u8, the video entry and p3d_debug_qpmap_u8 -------------------------------------------------
+// What one QP-map call on n maps of H x W bytes asks for: qp, levels and stats on the host, whatever is null is not copied back.
+struct QpmapCfg { int block, peak_weight, dilate, fall, rise, balance, target, lo, hi; };      // CONFIG's nine ints under their names
+struct QpmapRequest {
+    const char* who; int n, H, W;
+    const QpmapCfg* cfg = nullptr; const int32_t* law = nullptr;      // host: 256 entries (qpmap_check has passed them)
+    int32_t* qp = nullptr; unsigned char* levels = nullptr; int32_t* stats = nullptr;
+    bool timed = false;
+    const int32_t* starts = nullptr; int n_shots = 0;      // host: a shot table in frames of the call (shots_table_check has passed it), or none
+};
+// qpmap.hip's launch sequence as a stage queues it: the launch arguments, the law and the optional shot table on the device, and
+// the scratch of the first levels.  The qpmap stage holds one, and so does the prefilter stage, whose strength grid is these launches'
+// qp: each carves it among its own buffers.
+struct QpmapLaunches {
+    QpmapArgs a;
+    const int32_t* law; int32_t* dlaw = nullptr; ShotTable shots;
+    QpmapLaunches(const QpmapCfg& c, int n, int H, int W, const int32_t* law, const int32_t* starts, int n_shots);
+    size_t grid() const { return (size_t)a.n * (size_t)a.Hb * (size_t)a.Wb; }      // elements of qp and of levels
+    void carve(Carve& c, bool levels, bool stats);         // qp, levels and stats where asked for, the scratch, the law, the shot table
+    void upload(hipStream_t s) const;
+    void launch(hipStream_t s, const unsigned char* sal);
+};
+// The launches of qpmap.hip behind some device bytes, with no arrival counters: they hand results to one another from launch to
+// launch.  qpmap_check has passed cfg, the law and the shape before one is built.
+struct QpmapStage : ByteStage {
+    const QpmapRequest r;
+    QpmapLaunches q;
+    explicit QpmapStage(const QpmapRequest& r);
+    void carve(Carve& c) override;
+    void upload(hipStream_t s) override;
+    void launch(hipStream_t s, const unsigned char* sal, unsigned*) override;
+    void results(hipStream_t s) override;
+};
 QpmapCfg qpmap_check(const char* who, const int* cfg9, const int32_t* law, int n, int H, int W, const void* qp) {
     if (!cfg9 || !law || !qp) throw P3dError("null argument");
     const QpmapCfg c{cfg9[P3D_QPMAP_BLOCK], cfg9[P3D_QPMAP_PEAK_WEIGHT], cfg9[P3D_QPMAP_DILATE], cfg9[P3D_QPMAP_FALL], cfg9[P3D_QPMAP_RISE],
                      cfg9[P3D_QPMAP_BALANCE], cfg9[P3D_QPMAP_TARGET], cfg9[P3D_QPMAP_LO], cfg9[P3D_QPMAP_HI]};
     map_shape_check(who, n, H, W, P3D_QPMAP_MAX_PIXELS, "2^23, the bound that keeps an area-weighted sum of offsets in 32 bits");
-    if (c.block != 8 && c.block != 16 && c.block != 32 && c.block != 64 && c.block != 128)
+    if (!block_size_ok(c.block))
         throw P3dError(std::string(who) + ": the block is 8, 16, 32, 64 or 128, not " + std::to_string(c.block));
     if (c.peak_weight < 0 || c.peak_weight > 256) throw P3dError(std::string(who) + ": peak_weight is 0 .. 256");
     if (c.dilate < 0 || c.dilate > 8) throw P3dError(std::string(who) + ": dilate is 0 .. 8 blocks");
@@ -2447,7 +2378,6 @@ struct QpmapSizes {
           lev0((size_t)p3d_qpmap_plan(a.H, a.W, a.block, a.n).lev0_elems) {}
 };
 
-// ---- qpmap.hip's launches (declared above maps_u8_chain) and the qpmap stage ----------------------------------------------------------
 QpmapLaunches::QpmapLaunches(const QpmapCfg& c, int n, int H, int W, const int32_t* law_, const int32_t* starts, int n_shots)
     : a(qpmap_args(c, n, H, W)), law(law_), shots{starts, n_shots} {}
 void QpmapLaunches::carve(Carve& c, bool levels, bool stats) {
@@ -2478,37 +2408,33 @@ void QpmapStage::results(hipStream_t s) {
     if (r.levels) HIPCHECK(hipMemcpyAsync(r.levels, q.a.levels, z.grid, hipMemcpyDeviceToHost, s));
     if (r.stats) HIPCHECK(hipMemcpyAsync(r.stats, q.a.stats, z.stats * sizeof(int32_t), hipMemcpyDeviceToHost, s));
 }
+// p3d_qpmap_u8 (offset < 0) and p3d_debug_qpmap_u8 (offset in [0, 15]): the stage behind the host's bytes
+void qpmap_on_host_bytes(const char* who, int device, const unsigned char* sal, int n, int H, int W, const int* cfg, const int32_t* law,
+                         const int32_t* starts, int n_shots, int offset, bool hook, int32_t* qp, unsigned char* levels, int32_t* stats) {
+    if (!sal) throw P3dError("null argument");
+    const QpmapCfg qc = qpmap_check(who, cfg, law, n, H, W, qp);
+    if (starts || n_shots) shots_table_check(who, starts, n_shots, n);
+    if (hook) offset_check(who, offset);
+    metric_args(device, sal, cfg, 1, 1, qp);
+    QpmapRequest r{who, n, H, W};
+    r.cfg = &qc; r.law = law; r.qp = qp; r.levels = levels; r.stats = stats; r.starts = starts; r.n_shots = n_shots;
+    QpmapStage stage(r);
+    stage_on_host_bytes(stage, sal, hook ? offset : -1);
+}
 }  // namespace
 extern "C" {
 
 int p3d_qpmap_u8(int device, const unsigned char* sal, int n, int H, int W, const int cfg[9], const int32_t law[256], const int32_t* starts,
                  int n_shots, int32_t* qp, unsigned char* levels, int32_t* stats) {
     API_BEGIN
-    const char* who = "qpmap_u8";
-    if (!sal) throw P3dError("null argument");
-    const QpmapCfg qc = qpmap_check(who, cfg, law, n, H, W, qp);
-    if (starts || n_shots) shots_table_check(who, starts, n_shots, n);
-    metric_args(device, sal, cfg, 1, 1, qp);
-    QpmapRequest r{who, n, H, W};
-    r.cfg = &qc; r.law = law; r.qp = qp; r.levels = levels; r.stats = stats; r.starts = starts; r.n_shots = n_shots;
-    QpmapStage stage(r);
-    stage_on_host_bytes(stage, sal);
+    qpmap_on_host_bytes("qpmap_u8", device, sal, n, H, W, cfg, law, starts, n_shots, -1, false, qp, levels, stats);
     API_END
 }
 
 int p3d_debug_qpmap_u8(int device, const unsigned char* sal, int n, int H, int W, const int cfg[9], const int32_t law[256],
                        const int32_t* starts, int n_shots, int offset, int32_t* qp, unsigned char* levels, int32_t* stats) {
     API_BEGIN
-    const char* who = "debug_qpmap_u8";
-    if (!sal) throw P3dError("null argument");
-    const QpmapCfg qc = qpmap_check(who, cfg, law, n, H, W, qp);
-    if (starts || n_shots) shots_table_check(who, starts, n_shots, n);
-    offset_check(who, offset);
-    metric_args(device, sal, cfg, 1, 1, qp);
-    QpmapRequest r{who, n, H, W};
-    r.cfg = &qc; r.law = law; r.qp = qp; r.levels = levels; r.stats = stats; r.starts = starts; r.n_shots = n_shots;
-    QpmapStage stage(r);
-    stage_on_host_bytes(stage, sal, offset);
+    qpmap_on_host_bytes("debug_qpmap_u8", device, sal, n, H, W, cfg, law, starts, n_shots, offset, true, qp, levels, stats);
     API_END
 }
 
@@ -2516,8 +2442,7 @@ int p3d_debug_qpmap_plan(int H, int W, int block, int n, int* strip_rows, int* t
                          int64_t* scratch_bytes) {
     API_BEGIN
     if (!strip_rows || !tile_cols || !blocks_per_map || !maps_per_chunk || !scratch_bytes) throw P3dError("null argument");
-    if (H < 1 || W < 1 || (long long)H * W > P3D_QPMAP_MAX_PIXELS || n < 1 || n > 65535 ||
-        (block != 8 && block != 16 && block != 32 && block != 64 && block != 128))
+    if (H < 1 || W < 1 || (long long)H * W > P3D_QPMAP_MAX_PIXELS || n < 1 || n > 65535 || !block_size_ok(block))
         throw P3dError("debug_qpmap_plan: 1 <= H * W <= 2^23, 1 .. 65535 maps, a block of 8, 16, 32, 64 or 128");
     const QpmapPlan p = p3d_qpmap_plan(H, W, block, n);
     *strip_rows = p.strip_rows; *tile_cols = p.tile_cols; *blocks_per_map = p.blocks_per_map; *maps_per_chunk = p.maps_per_chunk;
@@ -2533,15 +2458,9 @@ int p3d_video_qpmap(p3d_handle* h, int first, int n, float scale, int H, int W, 
     h->video.need_open(who);
     const QpmapCfg qc = qpmap_check(who, cfg, law, std::max(1, std::min(n, 65535)), H, W, qp);
     QpmapRequest r{who, n, H, W};
-    r.cfg = &qc; r.law = law; r.qp = qp; r.levels = levels; r.stats = stats; r.timed = stage_ms != nullptr;
-    std::unique_ptr<QpmapStage> stage;
+    r.cfg = &qc; r.law = law; r.qp = qp; r.levels = levels; r.stats = stats;
     std::vector<int32_t> shots;                            // the installed table in frames of the call, cut as p3d_video_reframe cuts it
-    video_stage_run(h, who, first, n, scale, maps_out, stage_ms, 3, [&]() -> ByteStage& {
-        shots = video_shots_within(h, first, n);
-        if (!shots.empty()) { r.starts = shots.data(); r.n_shots = (int)shots.size(); }
-        stage.reset(new QpmapStage(r));
-        return *stage;
-    });
+    video_stage_run<QpmapStage>(h, r, first, scale, maps_out, stage_ms, 3, [&] { video_shots_into(h, first, shots, r); });
     if (stage_ms) stage_ms[0] = 0.0;                   // (nothing but the law and a shot table went up)
     API_END
 }
@@ -2550,12 +2469,36 @@ int p3d_video_qpmap(p3d_handle* h, int first, int n, float scale, int H, int W, 
 namespace {
 // ---- pre-filtering frames by their 8-bit maps (prefilter.hip; the law in include/p3d_hip.h): one check, one launch description and
 // one stage for p3d_prefilter_u8, the video entry and p3d_debug_prefilter_u8.  The strength grid is qpmap.hip's launches ------------
+// What one pre-filtering of n frames of H x W pixels by their maps asks for: frames on the host (uploaded) or on the device where they
+// are (the kept source); out and grid on the host, a null grid is not copied back.
+struct PrefilterCfg { int block, peak_weight, dilate, fall, rise, radius, passes; };      // CONFIG's seven ints under their names
+struct PrefilterRequest {
+    const char* who; int n, H, W;
+    const PrefilterCfg* cfg = nullptr; const int32_t* law = nullptr;      // host: 256 entries (prefilter_check has passed them)
+    const unsigned char* frames = nullptr; const unsigned char* frames_dev = nullptr; unsigned char* out = nullptr; int32_t* grid = nullptr;
+    bool timed = false;
+    const int32_t* starts = nullptr; int n_shots = 0;      // host: a shot table in frames of the call (shots_table_check has passed it), or none
+};
+// The launches of qpmap.hip (the strength grid, on this stage's own scratch) and of prefilter.hip behind some device bytes, with no
+// arrival counters.  prefilter_check has passed cfg, the law and the shape before one is built.
+struct PrefilterStage : ByteStage {
+    const PrefilterRequest r;
+    QpmapLaunches q;
+    PrefilterArgs a;
+    unsigned char* df = nullptr;
+    explicit PrefilterStage(const PrefilterRequest& r);
+    size_t bgr() const { return bytes * 3; }              // the bytes of n frames, in or out
+    void carve(Carve& c) override;
+    void upload(hipStream_t s) override;
+    void launch(hipStream_t s, const unsigned char* sal, unsigned*) override;
+    void results(hipStream_t s) override;
+};
 PrefilterCfg prefilter_check(const char* who, const int* cfg7, const int32_t* law, int n, int H, int W, const void* out) {
     if (!cfg7 || !law || !out) throw P3dError("null argument");
     const PrefilterCfg c{cfg7[P3D_PREFILTER_BLOCK], cfg7[P3D_PREFILTER_PEAK_WEIGHT], cfg7[P3D_PREFILTER_DILATE], cfg7[P3D_PREFILTER_FALL],
                          cfg7[P3D_PREFILTER_RISE], cfg7[P3D_PREFILTER_RADIUS], cfg7[P3D_PREFILTER_PASSES]};
     map_shape_check(who, n, H, W, P3D_PREFILTER_MAX_PIXELS, "2^23, the bound of the strength grid's launches");
-    if (c.block != 8 && c.block != 16 && c.block != 32 && c.block != 64 && c.block != 128)
+    if (!block_size_ok(c.block))
         throw P3dError(std::string(who) + ": the block is 8, 16, 32, 64 or 128, not " + std::to_string(c.block));
     if (c.peak_weight < 0 || c.peak_weight > 256) throw P3dError(std::string(who) + ": peak_weight is 0 .. 256");
     if (c.dilate < 0 || c.dilate > 8) throw P3dError(std::string(who) + ": dilate is 0 .. 8 blocks");
@@ -2576,7 +2519,6 @@ PrefilterArgs prefilter_args(const PrefilterCfg& c, int n, int H, int W) {
     return a;
 }
 
-// ---- the prefilter stage (declared above maps_u8_chain) ---------------------------------------------------------------------------
 PrefilterStage::PrefilterStage(const PrefilterRequest& r_)
     : ByteStage(r_), r(r_), q(prefilter_grid_cfg(*r_.cfg), r_.n, r_.H, r_.W, r_.law, r_.starts, r_.n_shots), a(prefilter_args(*r_.cfg, r_.n, r_.H, r_.W)) {}
 void PrefilterStage::carve(Carve& c) {
@@ -2599,37 +2541,34 @@ void PrefilterStage::results(hipStream_t s) {
     HIPCHECK(hipMemcpyAsync(r.out, a.out, bgr(), hipMemcpyDeviceToHost, s));
     if (r.grid) HIPCHECK(hipMemcpyAsync(r.grid, q.a.qp, q.grid() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
 }
+// p3d_prefilter_u8 (offset < 0) and p3d_debug_prefilter_u8 (offset in [0, 15]): the stage behind the host's bytes
+void prefilter_on_host_bytes(const char* who, int device, const unsigned char* sal, const unsigned char* frames, int n, int H, int W,
+                             const int* cfg, const int32_t* law, const int32_t* starts, int n_shots, int offset, bool hook, unsigned char* out,
+                             int32_t* grid) {
+    if (!sal || !frames) throw P3dError("null argument");
+    const PrefilterCfg pc = prefilter_check(who, cfg, law, n, H, W, out);
+    if (starts || n_shots) shots_table_check(who, starts, n_shots, n);
+    if (hook) offset_check(who, offset);
+    metric_args(device, sal, cfg, 1, 1, out);
+    PrefilterRequest r{who, n, H, W};
+    r.cfg = &pc; r.law = law; r.frames = frames; r.out = out; r.grid = grid; r.starts = starts; r.n_shots = n_shots;
+    PrefilterStage stage(r);
+    stage_on_host_bytes(stage, sal, hook ? offset : -1);
+}
 }  // namespace
 extern "C" {
 
 int p3d_prefilter_u8(int device, const unsigned char* sal, const unsigned char* frames, int n, int H, int W, const int cfg[7],
                      const int32_t law[256], const int32_t* starts, int n_shots, unsigned char* out, int32_t* grid) {
     API_BEGIN
-    const char* who = "prefilter_u8";
-    if (!sal || !frames) throw P3dError("null argument");
-    const PrefilterCfg pc = prefilter_check(who, cfg, law, n, H, W, out);
-    if (starts || n_shots) shots_table_check(who, starts, n_shots, n);
-    metric_args(device, sal, cfg, 1, 1, out);
-    PrefilterRequest r{who, n, H, W};
-    r.cfg = &pc; r.law = law; r.frames = frames; r.out = out; r.grid = grid; r.starts = starts; r.n_shots = n_shots;
-    PrefilterStage stage(r);
-    stage_on_host_bytes(stage, sal);
+    prefilter_on_host_bytes("prefilter_u8", device, sal, frames, n, H, W, cfg, law, starts, n_shots, -1, false, out, grid);
     API_END
 }
 
 int p3d_debug_prefilter_u8(int device, const unsigned char* sal, const unsigned char* frames, int n, int H, int W, const int cfg[7],
                            const int32_t law[256], const int32_t* starts, int n_shots, int offset, unsigned char* out, int32_t* grid) {
     API_BEGIN
-    const char* who = "debug_prefilter_u8";
-    if (!sal || !frames) throw P3dError("null argument");
-    const PrefilterCfg pc = prefilter_check(who, cfg, law, n, H, W, out);
-    if (starts || n_shots) shots_table_check(who, starts, n_shots, n);
-    offset_check(who, offset);
-    metric_args(device, sal, cfg, 1, 1, out);
-    PrefilterRequest r{who, n, H, W};
-    r.cfg = &pc; r.law = law; r.frames = frames; r.out = out; r.grid = grid; r.starts = starts; r.n_shots = n_shots;
-    PrefilterStage stage(r);
-    stage_on_host_bytes(stage, sal, offset);
+    prefilter_on_host_bytes("debug_prefilter_u8", device, sal, frames, n, H, W, cfg, law, starts, n_shots, offset, true, out, grid);
     API_END
 }
 
@@ -2638,9 +2577,8 @@ int p3d_debug_prefilter_plan(int H, int W, int block, int radius, int passes, in
     API_BEGIN
     if (!tile_rows || !tile_cols || !halo || !fused || !blocks_per_frame || !frames_per_chunk || !scratch_bytes || !mul || !shift)
         throw P3dError("null argument");
-    if (H < 1 || W < 1 || (long long)H * W > P3D_PREFILTER_MAX_PIXELS || n < 1 || n > 65535 ||
-        (block != 8 && block != 16 && block != 32 && block != 64 && block != 128) || radius < 1 || radius > P3D_PREFILTER_MAX_RADIUS ||
-        passes < 1 || passes > P3D_PREFILTER_MAX_PASSES)
+    if (H < 1 || W < 1 || (long long)H * W > P3D_PREFILTER_MAX_PIXELS || n < 1 || n > 65535 || !block_size_ok(block) || radius < 1 ||
+        radius > P3D_PREFILTER_MAX_RADIUS || passes < 1 || passes > P3D_PREFILTER_MAX_PASSES)
         throw P3dError("debug_prefilter_plan: 1 <= H * W <= 2^23, 1 .. 65535 frames, a block of 8, 16, 32, 64 or 128, a radius of 1 .. 16, 1 .. 3 passes");
     const PrefilterPlan p = p3d_prefilter_plan(H, W, block, radius, passes, n);
     *tile_rows = p.tile_rows; *tile_cols = p.tile_cols; *halo = p.halo; *fused = p.fused; *blocks_per_frame = (int)p.blocks_per_frame;
@@ -2658,15 +2596,11 @@ int p3d_video_prefilter(p3d_handle* h, int first, int n, float scale, int H, int
     if (!frames) need_kept_source(h, who);
     const PrefilterCfg pc = prefilter_check(who, cfg, law, std::max(1, std::min(n, 65535)), H, W, out);
     PrefilterRequest r{who, n, H, W};
-    r.cfg = &pc; r.law = law; r.frames = frames; r.out = out; r.grid = grid; r.timed = stage_ms != nullptr;
-    std::unique_ptr<PrefilterStage> stage;
+    r.cfg = &pc; r.law = law; r.frames = frames; r.out = out; r.grid = grid;
     std::vector<int32_t> shots;                            // the installed table in frames of the call, cut as p3d_video_qpmap cuts it
-    video_stage_run(h, who, first, n, scale, maps_out, stage_ms, 3, [&]() -> ByteStage& {
+    video_stage_run<PrefilterStage>(h, r, first, scale, maps_out, stage_ms, 3, [&] {
         if (!frames) r.frames_dev = kept_source(h, who, first, n, H, W, "filters");
-        shots = video_shots_within(h, first, n);
-        if (!shots.empty()) { r.starts = shots.data(); r.n_shots = (int)shots.size(); }
-        stage.reset(new PrefilterStage(r));
-        return *stage;
+        video_shots_into(h, first, shots, r);
     });
     if (stage_ms && !frames) stage_ms[0] = 0.0;      // (nothing but the law and a shot table went up)
     API_END
@@ -2676,7 +2610,32 @@ int p3d_video_prefilter(p3d_handle* h, int first, int n, float scale, int H, int
 namespace {
 // ---- distortion of frames under their 8-bit maps (distortion.hip; the law in include/p3d_hip.h): one check, one launch description
 // and one stage for p3d_distortion_u8, the video entry and p3d_debug_distortion_u8; the plan hook shares the check's ranges ---------
-bool distortion_block_ok(int b) { return b == 0 || b == 8 || b == 16 || b == 32 || b == 64 || b == 128; }
+// What one comparison of n test frames of H x W pixels with their reference frames under their maps asks for: test on the host
+// (uploaded); ref on the host (uploaded) or on the device where it is (the kept source); table and block_sse on the host, a null
+// block_sse is neither made nor copied back.
+struct DistortionCfg { int block, gate; };                 // CONFIG's two ints under their names
+struct DistortionRequest {
+    const char* who; int n, H, W;
+    const DistortionCfg* cfg = nullptr; const int32_t* wlaw = nullptr;      // host: 256 entries (distortion_check has passed them)
+    const unsigned char* ref = nullptr; const unsigned char* ref_dev = nullptr; const unsigned char* test = nullptr;
+    int64_t* table = nullptr; int64_t* block_sse = nullptr;
+    bool timed = false;
+};
+// The launches of distortion.hip behind some device bytes, with no arrival counters: the sums meet in the table through integer
+// atomics.  distortion_check has passed cfg, the law and the shape before one is built.
+struct DistortionStage : ByteStage {
+    const DistortionRequest r;
+    DistortionArgs a;
+    unsigned char* dref = nullptr; unsigned char* dtest = nullptr; int32_t* dlaw = nullptr;
+    explicit DistortionStage(const DistortionRequest& r);
+    size_t bgr() const { return bytes * 3; }              // the bytes of n frames
+    size_t grid() const { return (size_t)a.n * (size_t)a.Hb * (size_t)a.Wb; }      // elements of the block map
+    void carve(Carve& c) override;
+    void upload(hipStream_t s) override;
+    void launch(hipStream_t s, const unsigned char* sal, unsigned*) override;
+    void results(hipStream_t s) override;
+};
+bool distortion_block_ok(int b) { return b == 0 || block_size_ok(b); }
 DistortionCfg distortion_check(const char* who, const int* cfg2, const int32_t* wlaw, int n, int H, int W, const void* test, const void* table,
                                const void* block_sse) {
     if (!cfg2 || !wlaw || !test || !table) throw P3dError("null argument");
@@ -2698,7 +2657,6 @@ DistortionArgs distortion_args(const DistortionCfg& c, int n, int H, int W) {
     return a;
 }
 
-// ---- the distortion stage (declared above maps_u8_chain) --------------------------------------------------------------------------
 DistortionStage::DistortionStage(const DistortionRequest& r_) : ByteStage(r_), r(r_), a(distortion_args(*r_.cfg, r_.n, r_.H, r_.W)) {}
 void DistortionStage::carve(Carve& c) {
     dref = r.ref ? c.input<unsigned char>(bgr(), 3) : nullptr;
@@ -2773,12 +2731,9 @@ int p3d_video_distortion(p3d_handle* h, int first, int n, float scale, int H, in
     if (!ref) need_kept_source(h, who);
     const DistortionCfg dc = distortion_check(who, cfg, wlaw, std::max(1, std::min(n, 65535)), H, W, test, table, block_sse);
     DistortionRequest r{who, n, H, W};
-    r.cfg = &dc; r.wlaw = wlaw; r.ref = ref; r.test = test; r.table = table; r.block_sse = block_sse; r.timed = stage_ms != nullptr;
-    std::unique_ptr<DistortionStage> stage;
-    video_stage_run(h, who, first, n, scale, maps_out, stage_ms, 3, [&]() -> ByteStage& {
+    r.cfg = &dc; r.wlaw = wlaw; r.ref = ref; r.test = test; r.table = table; r.block_sse = block_sse;
+    video_stage_run<DistortionStage>(h, r, first, scale, maps_out, stage_ms, 3, [&] {
         if (!ref) r.ref_dev = kept_source(h, who, first, n, H, W, "compares");
-        stage.reset(new DistortionStage(r));
-        return *stage;
     });
     API_END
 }
@@ -2838,7 +2793,6 @@ void sweep_check_rows(const char* who, const std::vector<int>& info, const int* 
                            std::to_string(info[(size_t)b * 4]) + " fixated pixels");
 }
 
-// ---- the score stage (declared above maps_u8_chain) -------------------------------------------------------------------------------
 ScoreStage::ScoreStage(const ScoreRequest& r_)
     : ByteStage(r_), r(r_),
       a(score_args(r_.n, (long long)r_.H * r_.W, r_.flags, r_.flags ? r_.ties : P3D_SCORE_TIES_REFERENCE)), sweeps(r_.timed && (r_.borji || r_.shuffled), 2) {
@@ -2957,15 +2911,18 @@ void ScoreStage::check_counts() const {
 // p3d_video_score and p3d_video_score_auc behind the checks of their arguments.  stage_ms (null, or n_ms = 3 or 4 values): uploads,
 // the chain, the launches less the sweeps, the sweeps.
 void video_score_run(p3d_handle* h, int first, float scale, ScoreRequest r, unsigned char* maps_out, double* stage_ms, int n_ms) {
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    const VideoSource src(h, r.who, first, r.n, true, 65535);
     r.timed = stage_ms != nullptr;
-    std::unique_ptr<ScoreStage> stage;
-    video_stage_run(h, r.who, first, r.n, scale, maps_out, stage_ms, n_ms, [&]() -> ByteStage& { stage.reset(new ScoreStage(r)); return *stage; });
+    ScoreStage stage(r);
+    for (int i = 0; stage_ms && i < n_ms; ++i) stage_ms[i] = 0.0;
+    maps_u8_chain(h, r.n, h->pred->H, h->pred->W, scale, r.H, r.W, maps_out, nullptr, src.extra(), src, &stage);
     if (stage_ms) {
-        const double sw = stage->sweep_ms();
-        stage_ms[2] = std::max(0.0, stage_ms[2] - sw);
+        const double sw = stage.sweep_ms();
+        stage_ms[0] = stage.ms[0]; stage_ms[1] = stage.ms[1]; stage_ms[2] = std::max(0.0, stage.ms[2] - sw);
         if (n_ms > 3) stage_ms[3] = sw;
     }
-    stage->check_counts();
+    stage.check_counts();
 }
 }  // namespace
 extern "C" {

@@ -1,20 +1,26 @@
 """A read-out facility's test hook runs the stage its op entry point runs: the same carve, upload, launches and copies back, the
 hook's inside a block of its own with every buffer between guards, the op's on the stream's scratch.  At offset 0 both see the same
 alignment modulo 16, so what they return is equal bit for bit, floats included -- once per option that changes the stage's list of
-buffers.  (The other offsets, and the values themselves, are the business of each facility's own tests.)  3 maps of 7 x 19 bytes."""
+buffers.  (The other offsets, and the values themselves, are the business of each facility's own tests.)  3 maps of 7 x 19 bytes;
+distortion takes 12 x 19, the smallest of this width with more than one row of SSIM windows."""
 import functools
+import os
+import sys
 
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import distortion_ref       # noqa: E402
+
 N, H, W = 3, 7, 19
 SHOTS = [0, 2]
 
 
 @functools.lru_cache(maxsize=None)
-def inputs():
+def inputs(H=H):
     rng = np.random.RandomState(11)
     yy, xx = np.mgrid[0:H, 0:W]
     sal = np.stack([255.0 * np.exp(-((yy - 2 - k) ** 2 / 6.0 + (xx - 5 - 4 * k) ** 2 / 14.0)) for k in range(N)])
@@ -77,6 +83,30 @@ def test_qpmap(kw):
     law = dataflow.qp_law(-20, 6)
     kw = dict(kw, block=8, dilate=1, fall=1, rise=3)
     same(dataflow.qpmap(sal, law, offset=0, **kw), dataflow.qpmap(sal, law, **kw), ("qpmap", sorted(kw.items())))
+
+
+@pytest.mark.parametrize("shots", [None, SHOTS])
+@pytest.mark.parametrize("grid", [True, False])
+@pytest.mark.parametrize("passes", [1, 2])      # 1: no temporary; 2: one
+def test_prefilter(passes, grid, shots):
+    from sap3d_tensorflow_amd import dataflow
+    sal, _, _, frames = inputs()
+    law = dataflow.prefilter_law(gate=200, full=20)
+    kw = dict(block=8, dilate=1, fall=2, rise=4, radius=2, passes=passes, grid=grid, shots=shots)
+    same(dataflow.prefilter(sal, frames, law, offset=0, **kw), dataflow.prefilter(sal, frames, law, **kw), ("prefilter", passes, grid, shots))
+
+
+@pytest.mark.parametrize("block", [0, 8])       # 0: no block map; 8: one
+def test_distortion(block):
+    from sap3d_tensorflow_amd import dataflow
+    rows, cols = distortion_ref.windows(12, W)
+    assert rows and cols                         # SSIM has windows
+    sal, _, _, ref = inputs(12)
+    test = distortion_ref.near(ref, 3)
+    args = (sal, ref, test, (block, 100), dataflow.distortion_law(gate=100, floor=1))
+    hook, op = dataflow.distortion(*args, offset=0), dataflow.distortion(*args)
+    assert (op[1] is None) == (block == 0)
+    same(hook, op, ("distortion", block))
 
 
 @pytest.mark.parametrize("with_fixation", [True, False])
